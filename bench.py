@@ -23,7 +23,12 @@ The Add half of the metric (all on the same 1M index):
 each beside the CPU restatement running the SAME schedule on the same vectors (graph hashes compared),
 plus `roofline_add` for the two build kernels.
 
-    python bench.py [--gpus N --steps K --warmup W] [--n 1000000 --nq 65536 ...]
+A plain run does only what the headline needs: it sets up (data, the build that `add_per_sec` times), warms up, times the K steps and
+prints the line (`roofline` / `roofline_add` come from HIP events of those same launches).  `--full` adds everything else after the
+timed steps: the resident-query step, small calls, recall@10, the CPU baseline, the Add modes and recall study, the clustered-data
+check and the crossover; without it those keys are null.  `--dump-outputs DIR` writes the last timed step's ids and distances as .npy.
+
+    python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR] [--n 1000000 --nq 65536 ...]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 """
 import argparse
@@ -95,7 +100,16 @@ def parse():
     p.add_argument("--traversal", choices=["device", "host"], default="device",
                    help="device: graph-resident search kernel (default); host: the literal north-star split -- traversal on "
                         "host threads, distances batched step by step through the inner C ABI (hnswdev_step_submit / _wait)")
-    return p.parse_args()
+    p.add_argument("--full", action="store_true",
+                   help="also run everything beyond the headline after the timed steps: resident-query and small-call steps, recall@10, "
+                        "CPU baseline, Add modes, recall study, clustered-data check, crossover (the --no-* options and the "
+                        "sample sizes above apply to these); without it a run sets up, warms up, times the steps and prints the line")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed step returned (neighbour ids and distances of every query) as DIR/<name>.npy")
+    a = p.parse_args()
+    if a.steps < 1:
+        p.error("--steps must be at least 1")
+    return a
 
 
 def make_data(n, dim, seed, metric, kind="uniform"):
@@ -135,6 +149,24 @@ def recall_of(x, q, k, metric, got_ids):
     gt = brute_force_topk(x_t, q, k, metric)
     del x_t
     return float(np.mean([len(set(gt[i]) & set(got_ids[i])) / k for i in range(q.shape[0])]))
+
+
+DUMP_BYTES_MAX = 64_000_000
+
+
+def dump_outputs(out_dir, ids, dists):
+    """--dump-outputs: the last timed step's answer as a caller of hnsw_knn_query receives it -- ids [nq, k] (as float64, exact for
+    int32) and distances [nq, k] (float32) -- into out_dir/knn_ids.npy and out_dir/knn_distances.npy.  Beyond DUMP_BYTES_MAX a fixed,
+    seeded sample of query rows is written instead, and its row numbers as out_dir/knn_rows.npy."""
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    nq, k = ids.shape
+    if nq * k * (8 + 4) > DUMP_BYTES_MAX:
+        rows = np.sort(np.random.default_rng(20241016).choice(nq, DUMP_BYTES_MAX // (k * (8 + 4) + 8), replace=False))
+        ids, dists = ids[rows], dists[rows]
+        np.save(out / "knn_rows.npy", rows.astype(np.float64))
+    np.save(out / "knn_ids.npy", ids.astype(np.float64))
+    np.save(out / "knn_distances.npy", np.ascontiguousarray(dists, dtype=np.float32))
 
 
 def quote_pmc_traffic(path, workload, fetched_row_bytes, build_id):
@@ -404,20 +436,24 @@ def main():
     last_set = (a.warmup + a.steps - 1) % R
     if res_ids is not None:  # views of the exchange buffer: keep them past the next call
         res_ids, res_d = np.array(res_ids), np.array(res_d)
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, res_ids, res_d)
     st = ix.stats()
     st_all = [ix.stats_at(g) for g in range(ndev_native)] if native else [st]
     ix.set_profiling(False)
-    ix.set_resident_queries(q_all[lo:hi])
-    step_resident()
-    barrier()
-    t0 = time.perf_counter()
-    nb_steps = max(2, min(5, a.steps))
-    for _ in range(nb_steps):
+    dt_resident = None
+    if a.full:
+        ix.set_resident_queries(q_all[lo:hi])
         step_resident()
-    barrier()
-    dt_resident = (time.perf_counter() - t0) / nb_steps
+        barrier()
+        t0 = time.perf_counter()
+        nb_steps = max(2, min(5, a.steps))
+        for _ in range(nb_steps):
+            step_resident()
+        barrier()
+        dt_resident = (time.perf_counter() - t0) / nb_steps
     small = None
-    if world == 1 and not native and 0 < a.small_batch < hi - lo:  # the same step on C4's per-GPU shard size: launch fill / tail effects
+    if a.full and world == 1 and not native and 0 < a.small_batch < hi - lo:  # the same step on C4's per-GPU shard size: launch fill / tail effects
         ix.set_resident_queries(q_all[:a.small_batch])
         ix.knn_query_resident(a.k)
         ix.set_profiling(True)
@@ -458,9 +494,9 @@ def main():
             small[f"queries_per_sec_{T}_host_threads"] = round(T * a.small_batch * 10 / dtt, 1)
             small[f"speedup_{T}_host_threads_vs_one"] = round(T * a.small_batch * 10 / dtt / small["queries_per_sec"], 3)
     if world > 1:
-        t = torch.tensor([dt, dt_resident], dtype=torch.float64, device="cuda" if backend == "nccl" else "cpu")
+        t = torch.tensor([dt, dt_resident or 0.0], dtype=torch.float64, device="cuda" if backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        dt, dt_resident = float(t[0].item()), float(t[1].item())
+        dt, dt_resident = float(t[0].item()), (float(t[1].item()) if a.full else None)
 
     if rank != 0:
         if world > 1:
@@ -468,10 +504,10 @@ def main():
             dist.destroy_process_group()
         return
 
-    # ---------------- rank 0: quality, rooflines, CPU baseline, Add modes ----------------
+    # ---------------- rank 0: rooflines; with --full also quality, CPU baseline, Add modes ----------------
     nrec = min(a.recall_queries, nq_total)
     q_last = q_sets[last_set]              # the set the last timed step answered
-    recall = recall_of(x, q_last[:nrec], a.k, a.metric, res_ids)
+    recall = recall_of(x, q_last[:nrec], a.k, a.metric, res_ids) if a.full else None
 
     if a.traversal == "device":
         # native sharding: the contexts run side by side -- evaluations of all, launches and kernel time of the slowest one
@@ -572,7 +608,7 @@ def main():
     cpu = None
     cpu_add = {}
     cpu_batched_evals = 0
-    if not a.no_cpu_baseline and world == 1:
+    if a.full and not a.no_cpu_baseline and world == 1:
         import oracle
         ref = oracle.OracleIndex(a.dim, a.metric, max_edges=a.max_edges, min_nn=a.ef_search,
                                  max_candidates=a.ef_construction, collection_size=a.n + extra_total,
@@ -638,7 +674,7 @@ def main():
             roofline["frac_of_measured_gather"] = round(alg / kernel_s / gref["rows_per_s"], 4)
 
     add_modes = None
-    if not a.no_add_modes and world == 1:
+    if a.full and not a.no_add_modes and world == 1:
         def leg(name, vecs, call, note):
             ix.reset_stats()
             t0 = time.perf_counter()
@@ -731,7 +767,7 @@ def main():
     # The headline data (i.i.d. uniform, the reference's own test distribution) has no neighbourhood structure at
     # this dimension, so recall@10 is low on CPU and GPU alike.  The same build and query on data that has some:
     clustered = None
-    if world == 1 and a.data == "uniform" and not a.no_clustered_check and a.n <= 2_000_000 and a.traversal == "device":
+    if a.full and world == 1 and a.data == "uniform" and not a.no_clustered_check and a.n <= 2_000_000 and a.traversal == "device":
         xc = make_data(a.n, a.dim, 65537, a.metric, "clustered")
         qc = make_data(4096, a.dim, 65538, a.metric, "clustered")
         ic = new_index(a, dev_index, a.n, a.insert_batch)
@@ -798,7 +834,7 @@ def main():
     n_gpus = world * ndev_native
     out = {
         "metric": "knn_queries_per_sec", "value": round(qps, 1), "unit": "queries/s", "n_gpus": n_gpus,
-        "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(1e3 * dt / a.steps, 3),
+        "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(1e3 * dt / a.steps, 3), "full": a.full,
         "higher_is_better": True, "scaling": a.scaling, "vs_baseline": None, "dtype": "i8 (int32 dot, f64 epilogue)" if a.metric == "sq_euclid_i8" else "f32", "data": "synthetic" if a.data == "uniform" else "synthetic (clustered)",
         "config": {
             "workload": f"{cfg_name}: {a.n}x{a.dim} {'int8+scale' if a.metric == 'sq_euclid_i8' else 'f32'} {a.metric}, M={a.max_edges} efConstruction={a.ef_construction} "
@@ -814,10 +850,10 @@ def main():
         "entry_point": "hnsw_knn_query", "build_id": build_id,
         "collective_backend": (("rccl (torch.distributed nccl)" if backend == "nccl" else backend) if world > 1 else None), "rccl_ranks_seen": ranks_seen,
         "per_gpu_workload_equals_n1": bool(a.scaling == "weak"),
-        "resident_queries_per_sec": round(nq_total / dt_resident, 1),
+        "resident_queries_per_sec": round(nq_total / dt_resident, 1) if dt_resident else None,
         "resident_note": "the same step with the query set uploaded once before the timed region (hnsw_mi355x_knn_query_resident); "
                          "`value` is the reference's export, PCIe-inclusive",
-        "recall_at_10": round(recall, 4),
+        "recall_at_10": round(recall, 4) if recall is not None else None,
         "recall_note": "exact brute-force ground truth; i.i.d. uniform data (the reference's test distribution) has no "
                        "neighbourhood structure at this size -- the CPU path returns the same ids (see cpu_baseline); "
                        "recall_on_clustered_data is the same build and query on data that has structure",

@@ -73,3 +73,39 @@ def test_pmc_traffic_is_quoted_only_for_the_running_build_and_workload(tmp_path)
 def test_the_committed_pmc_profile_names_a_build_per_configuration():
     pm = json.loads((ROOT / "profiles" / "r5_pmc_traffic.json").read_text())
     assert pm["configs"] and all(len(c.get("build_id", "")) == 64 for c in pm["configs"].values())
+
+
+def test_dump_outputs_writes_the_answer_as_float_arrays(tmp_path):
+    """--dump-outputs: ids (float64, exact for int32) and distances (float32) of every query, unchanged."""
+    import numpy as np
+    b = _bench_module()
+    rng = np.random.default_rng(7)
+    ids = rng.integers(-1, 1_000_000, (300, 10)).astype(np.int32)
+    d = rng.random((300, 10), dtype=np.float32)
+    b.dump_outputs(tmp_path / "out", ids, d)
+    got_i, got_d = np.load(tmp_path / "out" / "knn_ids.npy"), np.load(tmp_path / "out" / "knn_distances.npy")
+    assert got_i.dtype == np.float64 and got_d.dtype == np.float32
+    assert (got_i == ids).all() and got_d.tobytes() == d.tobytes()
+    assert not (tmp_path / "out" / "knn_rows.npy").exists()
+
+
+def test_dump_outputs_beyond_the_cap_is_a_fixed_sample(tmp_path, monkeypatch):
+    import numpy as np
+    b = _bench_module()
+    monkeypatch.setattr(b, "DUMP_BYTES_MAX", 100 * 10 * 12)
+    ids = np.arange(3000, dtype=np.int32).reshape(300, 10)
+    d = ids.astype(np.float32) / 7
+    for run in ("a", "b"):
+        b.dump_outputs(tmp_path / run, ids, d)
+    rows = np.load(tmp_path / "a" / "knn_rows.npy")
+    assert (rows == np.load(tmp_path / "b" / "knn_rows.npy")).all() and 0 < rows.size < 100
+    assert (np.diff(rows) > 0).all()
+    assert (np.load(tmp_path / "a" / "knn_ids.npy") == ids[rows.astype(np.int64)]).all()
+    assert np.load(tmp_path / "a" / "knn_distances.npy").tobytes() == d[rows.astype(np.int64)].tobytes()
+    sizes = sum(f.stat().st_size for f in (tmp_path / "a").iterdir())
+    assert sizes <= 100 * 10 * 12 + 3 * 128
+
+
+def test_steps_must_be_positive():
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "0", "--dry-run"], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 2 and "--steps" in r.stderr

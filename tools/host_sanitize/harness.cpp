@@ -11,6 +11,8 @@
 #include <string>
 #include <vector>
 
+#include <unistd.h>
+
 #include "host_structs.h"
 #include "range_replay.h"
 #include "snapshot_io.h"
@@ -29,6 +31,16 @@ static std::vector<uint8_t> slurp(const char *path)
     if (n > 0 && std::fread(b.data(), 1, (size_t)n, f) != (size_t)n) b.clear();
     std::fclose(f);
     return b;
+}
+
+// the round trip's file: one per process under TMPDIR (else /tmp), so that runs by other users or at the same time never share it
+static const std::string &roundtrip_path()
+{
+    static const std::string path = [] {
+        const char *dir = std::getenv("TMPDIR");
+        return std::string(dir && *dir ? dir : "/tmp") + "/hnsw_sanitize_roundtrip." + std::to_string((long)getpid()) + ".bin";
+    }();
+    return path;
 }
 
 // decode; whatever decodes is walked the way a traversal would walk it, re-encoded and decoded again
@@ -54,9 +66,10 @@ static int exercise(const std::vector<uint8_t> &buf, bool verbose)
         }
     }
     const uint64_t h1 = graph_hash_of(g);
-    const char *tmp = "/tmp/hnsw_sanitize_roundtrip.bin";
+    const char *tmp = roundtrip_path().c_str();
     if (!write_snapshot(tmp, sp, g, rows.data(), dim, cap, err)) { if (verbose) std::printf("write refused: %s\n", err.c_str()); return 0; }
     const std::vector<uint8_t> again = slurp(tmp);
+    std::remove(tmp);
     SnapshotParams sp2;
     Graph g2;
     std::vector<float> rows2;

@@ -2,7 +2,7 @@
 # Round 5: A/B of the Add paths (default build under the host-thread cap, B = 1, exact window, the bounded ladder, one 32 768-item snapshot) and of single-query calls
 # between the product library and variants.  VARIANTS="product <file>.so diag:<string> ..." as in tools/r5_lean_ab.sh; summary lines -> gpurun_out/r5_add_ab.log
 O=$GRAFT_REPO_ROOT/gpurun_out; L=$O/r5_add_ab.log; mkdir -p $O; : > $L
-A="--no-clustered-check --recall-study-n 0 --small-batch 0 --steps 5 --recall-queries 200 $EXTRA"
+A="--full --no-clustered-check --recall-study-n 0 --small-batch 0 --steps 5 --recall-queries 200 $EXTRA"
 for v in ${VARIANTS:-product}; do
   echo "== $v" >> $L
   ( case "$v" in product) ;; diag:*) export HNSW_MI355X_DIAG="${v#diag:}";; *) export HNSW_MI355X_LIB=$GRAFT_REPO_ROOT/build_variants/$v;; esac

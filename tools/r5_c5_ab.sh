@@ -3,7 +3,7 @@
 # product (5 waves per SIMD) against build variants -DHNSW_I8_WAVES=4 / 6 (build_variants/i8w4.so, i8w6.so), and the product with
 # the shadow traversals off.  One bench line each into gpurun_out/r5_c5_ab.log.
 O=$GRAFT_REPO_ROOT/gpurun_out; L=$O/r5_c5_ab.log; : > $L
-A="--metric sq_euclid_i8 --dim 96 --index-size 10000000 --nq ${NQ:-12500} --insert-batch 65536 --no-cpu-baseline --no-add-modes --small-batch 0 --no-clustered-check --steps 10 --recall-queries 200"
+A="--full --metric sq_euclid_i8 --dim 96 --index-size 10000000 --nq ${NQ:-12500} --insert-batch 65536 --no-cpu-baseline --no-add-modes --small-batch 0 --no-clustered-check --steps 10 --recall-queries 200"
 run() { echo "== $1" >> $L; shift; ( "$@" python3 bench.py $A 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads([l for l in sys.stdin if l.startswith('{')][-1]); r=d['roofline']

@@ -4,7 +4,7 @@
 # (-DHNSW_EXP_LEAN=true -DHNSW_COLD_EXACT -DHNSW_I8_WAVES=W -DHNSW_F32_WAVES=F).  One summary line per run into gpurun_out/r5_lean_ab.log.
 #   usage: tools/r5_lean_ab.sh [c5] [c5L] [c4] [c2]
 O=$GRAFT_REPO_ROOT/gpurun_out; L=$O/r5_lean_ab.log; mkdir -p $O; : > $L
-Q="--no-cpu-baseline --no-add-modes --small-batch 0 --no-clustered-check --steps 10 --recall-queries 200 --insert-batch 65536 --recall-study-n 0"
+Q="--full --no-cpu-baseline --no-add-modes --small-batch 0 --no-clustered-check --steps 10 --recall-queries 200 --insert-batch 65536 --recall-study-n 0"
 C5="--metric sq_euclid_i8 --dim 96 --index-size 10000000 --nq 12500"
 C5L="--metric sq_euclid_i8 --dim 96 --index-size 10000000 --nq 65536"
 C4="--index-size 10000000 --nq 12500"

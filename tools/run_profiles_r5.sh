@@ -18,20 +18,20 @@ C5="--metric sq_euclid_i8 --dim 96 --index-size 10000000 --nq 12500 --insert-bat
 C5L="--metric sq_euclid_i8 --dim 96 --index-size 10000000 --nq 65536 --insert-batch 65536"
 pmc() { # name, counters, bench args...
   local name=$1 ctr=$2; shift 2
-  rocprofv3 --pmc $ctr --output-format csv -d /tmp/p_$name -o p -- python3 $R/bench.py $Q --steps 2 --warmup 0 "$@" > $O/bench_$name.log 2>&1
+  rocprofv3 --pmc $ctr --output-format csv -d /tmp/p_$name -o p -- python3 $R/bench.py --full $Q --steps 2 --warmup 0 "$@" > $O/bench_$name.log 2>&1
   python3 $R/tools/prof_summary.py /tmp/p_$name $O/$name.json graph_search_kernel graph_insert_search_kernel graph_link_kernel > /dev/null
   echo "$name done"; rm -rf /tmp/p_$name
 }
 if [ $WHAT = plain ]; then # only the plain bench lines of every configuration (no profiler attached)
-python3 $R/bench.py > $O/bench_plain.log 2>&1; echo c2 plain done
-python3 $R/bench.py $C4 --small-batch 0 --steps 10 --recall-study-n 0 --no-clustered-check > $O/bench_c4_size.log 2>&1; echo c4 plain done
-python3 $R/bench.py $C5 --small-batch 0 --steps 10 --recall-study-n 0 --no-clustered-check > $O/bench_c5_size.log 2>&1; echo c5 plain done
-python3 $R/bench.py $C3 --small-batch 0 --steps 10 --recall-study-n 0 --seq-adds 500 --window-adds 2000 --bounded-adds 1024 --batched-adds 8192 --no-clustered-check > $O/bench_c3.log 2>&1; echo c3 plain done
-python3 $R/bench.py --data clustered > $O/bench_clustered.log 2>&1; echo clustered done
+python3 $R/bench.py --full > $O/bench_plain.log 2>&1; echo c2 plain done
+python3 $R/bench.py --full $C4 --small-batch 0 --steps 10 --recall-study-n 0 --no-clustered-check > $O/bench_c4_size.log 2>&1; echo c4 plain done
+python3 $R/bench.py --full $C5 --small-batch 0 --steps 10 --recall-study-n 0 --no-clustered-check > $O/bench_c5_size.log 2>&1; echo c5 plain done
+python3 $R/bench.py --full $C3 --small-batch 0 --steps 10 --recall-study-n 0 --seq-adds 500 --window-adds 2000 --bounded-adds 1024 --batched-adds 8192 --no-clustered-check > $O/bench_c3.log 2>&1; echo c3 plain done
+python3 $R/bench.py --full --data clustered > $O/bench_clustered.log 2>&1; echo clustered done
 fi
 if [ $WHAT = c2 ] || [ $WHAT = all ]; then
-python3 $R/bench.py > $O/bench_plain.log 2>&1; echo plain done
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_stats -o s -- python3 $R/bench.py $Q > $O/bench_under_rocprof.log 2>&1
+python3 $R/bench.py --full > $O/bench_plain.log 2>&1; echo plain done
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_stats -o s -- python3 $R/bench.py --full $Q > $O/bench_under_rocprof.log 2>&1
 python3 $R/tools/prof_summary.py /tmp/p_stats $O/kernel_stats.json hnsw:: > /dev/null
 cp /tmp/p_stats/*kernel_stats.csv $O/ 2>/dev/null; cp /tmp/p_stats/*/*kernel_stats.csv $O/ 2>/dev/null; rm -rf /tmp/p_stats
 pmc c2_fetch FETCH_SIZE
@@ -52,24 +52,24 @@ $R/tools/gather_bench 128 1.192093 16777216 0 > $O/gather_own_c5.log 2>&1     # 
 echo calib done
 fi
 if [ $WHAT = c3 ] || [ $WHAT = all ]; then
-python3 $R/bench.py $C3 --small-batch 0 --steps 10 --recall-study-n 0 --seq-adds 500 --window-adds 2000 --bounded-adds 1024 --batched-adds 8192 --no-clustered-check > $O/bench_c3.log 2>&1; echo c3 plain done
+python3 $R/bench.py --full $C3 --small-batch 0 --steps 10 --recall-study-n 0 --seq-adds 500 --window-adds 2000 --bounded-adds 1024 --batched-adds 8192 --no-clustered-check > $O/bench_c3.log 2>&1; echo c3 plain done
 pmc c3_fetch FETCH_SIZE $C3
 pmc c3_write WRITE_SIZE $C3
 pmc c3_mfma "SQ_INSTS_VALU_MFMA_MOPS_F32 SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES SQ_WAVE_CYCLES GRBM_GUI_ACTIVE" $C3
 fi
 if [ $WHAT = c4 ] || [ $WHAT = all ]; then
-python3 $R/bench.py $C4 --small-batch 0 --steps 10 --recall-study-n 0 --no-clustered-check > $O/bench_c4_size.log 2>&1; echo c4 plain done
+python3 $R/bench.py --full $C4 --small-batch 0 --steps 10 --recall-study-n 0 --no-clustered-check > $O/bench_c4_size.log 2>&1; echo c4 plain done
 pmc c4_fetch FETCH_SIZE $C4
 pmc c4_write WRITE_SIZE $C4
 fi
 if [ $WHAT = c5 ] || [ $WHAT = all ]; then
-python3 $R/bench.py $C5 --small-batch 0 --steps 10 --recall-study-n 0 --no-clustered-check > $O/bench_c5_size.log 2>&1; echo c5 plain done
+python3 $R/bench.py --full $C5 --small-batch 0 --steps 10 --recall-study-n 0 --no-clustered-check > $O/bench_c5_size.log 2>&1; echo c5 plain done
 pmc c5_fetch FETCH_SIZE $C5
 pmc c5_write WRITE_SIZE $C5
 fi
 if [ $WHAT = misc ] || [ $WHAT = all ]; then
-python3 $R/bench.py --data clustered > $O/bench_clustered.log 2>&1
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_host -o h -- python3 $R/bench.py --traversal host --n 200000 --nq 16384 --steps 3 --warmup 1 $Q > $O/bench_host_cabi.log 2>&1
+python3 $R/bench.py --full --data clustered > $O/bench_clustered.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_host -o h -- python3 $R/bench.py --full --traversal host --n 200000 --nq 16384 --steps 3 --warmup 1 $Q > $O/bench_host_cabi.log 2>&1
 python3 $R/tools/prof_summary.py /tmp/p_host $O/kernel_stats_host_cabi.json hnsw:: > /dev/null; rm -rf /tmp/p_host
 echo misc done
 fi
