@@ -21,6 +21,9 @@ namespace hnsw {
 void set_dev_error(const std::string &msg);
 std::string get_dev_error();
 class Device;
+struct VisitedScratch;   // device_backend.hip: the visited-set memory of a traversal launch
+struct TraversalLaunch;  // ... which traversal kernel form a launch runs, on how many waves, with which flags
+struct LaunchFamily;     // ... the hnswdev_stats counters of one kernel family
 struct ErrorScope { // RAII: the calling thread is inside a call on `d`
     explicit ErrorScope(Device *d);
     ~ErrorScope();
@@ -297,7 +300,9 @@ private:
     int *s_vistab_ = nullptr; // per-wave visited-id hash tables
     size_t s_vistab_cap_ = 0;
     int s_vistab_each_ = 0;
-    bool visited_table(size_t vis_bytes_per_job, int k, int **out, int *out_cap, int min_cap = 512, bool allow_hash = true);
+    bool visited_scratch(int k, int min_cap, bool allow_hash, VisitedScratch *out);
+    bool plan_traversal(bool insert, int k, bool two_heap, size_t lds, TraversalLaunch *out);
+    bool count_launch(const LaunchFamily *family, unsigned long long evals, bool hashed, bool timed, void *t0, void *t1);
     int num_cu_ = 256;
     // Persistent launches never use more than 16 one-wave blocks per CU (the traversal kernels need
     // >= 128 VGPRs): the per-wave scratch (visited bitsets, spill areas, logs) is sized for that.

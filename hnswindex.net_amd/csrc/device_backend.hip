@@ -41,6 +41,7 @@
 #include <cstring>
 #include <map>
 #include <mutex>
+#include <type_traits>
 #include <vector>
 
 #include "device_backend.h"
@@ -195,6 +196,48 @@ struct Device::HostGraphStage {
 };
 
 static inline hipStream_t S(void *p) { return (hipStream_t)p; }
+
+// The one place a context's metric becomes a template argument: f(std::integral_constant<int, M>{}).
+template <class F>
+static void with_metric(int metric, F &&f)
+{
+    switch (metric) {
+    case M_SQ: f(std::integral_constant<int, M_SQ>{}); break;
+    case M_COS: f(std::integral_constant<int, M_COS>{}); break;
+    case M_I8: f(std::integral_constant<int, M_I8>{}); break;
+    default: f(std::integral_constant<int, M_UCOS>{}); break;
+    }
+}
+
+// The hnswdev_stats counters of one kernel family.
+struct LaunchFamily {
+    uint64_t hnswdev_stats::*launches, hnswdev_stats::*evals, hnswdev_stats::*timed_launches, hnswdev_stats::*timed_evals;
+    double hnswdev_stats::*kernel_ms;
+};
+static constexpr LaunchFamily kSearchFamily{&hnswdev_stats::search_launches, &hnswdev_stats::search_evals, &hnswdev_stats::search_timed_launches,
+                                            &hnswdev_stats::search_timed_evals, &hnswdev_stats::search_kernel_ms};
+static constexpr LaunchFamily kInsertFamily{&hnswdev_stats::insert_launches, &hnswdev_stats::insert_evals, &hnswdev_stats::insert_timed_launches,
+                                            &hnswdev_stats::insert_timed_evals, &hnswdev_stats::insert_kernel_ms};
+static constexpr LaunchFamily kLinkFamily{&hnswdev_stats::link_launches, &hnswdev_stats::link_evals, &hnswdev_stats::link_timed_launches,
+                                          &hnswdev_stats::link_timed_evals, &hnswdev_stats::link_kernel_ms};
+static constexpr LaunchFamily kRangeFamily{&hnswdev_stats::range_launches, &hnswdev_stats::range_evals, &hnswdev_stats::range_timed_launches,
+                                           &hnswdev_stats::range_timed_evals, &hnswdev_stats::range_kernel_ms};
+
+// One finished traversal, link or range launch into the counters: search_* always, `family`'s own besides (nullptr: a KnnQuery
+// launch has none), visited_hash_launches when its visited sets were hash tables.  A timed launch (profiling on) adds the kernel
+// time between the events t0 and t1.  (link_dry_run and relink_batch count less: see there.)
+bool Device::count_launch(const LaunchFamily *family, unsigned long long evals, bool hashed, bool timed, void *t0, void *t1)
+{
+    for (const LaunchFamily *f : {&kSearchFamily, family})
+        if (f) { stats_.*f->launches += 1; stats_.*f->evals += evals; }
+    if (hashed) stats_.visited_hash_launches++;
+    if (!timed) return true;
+    float ms = 0.f;
+    HIP_OK(hipEventElapsedTime(&ms, (hipEvent_t)t0, (hipEvent_t)t1));
+    for (const LaunchFamily *f : {&kSearchFamily, family})
+        if (f) { stats_.*f->kernel_ms += ms; stats_.*f->timed_launches += 1; stats_.*f->timed_evals += evals; }
+    return true;
+}
 
 bool Device::bind()
 {
@@ -805,15 +848,11 @@ bool Device::launch_step(StepBuffers *sb, int nslots_used, uint64_t evals)
     HIP_OK(hipMemcpyAsync(sb->d_rec, sb->rec, sizeof(int) * (size_t)nslots_used * sb->rec_stride, hipMemcpyHostToDevice, st));
     if (sb->timed) HIP_OK(hipEventRecord((hipEvent_t)sb->t0, st));
     dim3 grid((nslots_used + 3) / 4), block(256);
-#define LAUNCH(M)                                                                                          \
-    hipLaunchKernelGGL(slot_distance_kernel<M>, grid, block, 0, st, d_rows_, d_row_sn_, d_queries_, d_q_sn_, pitch_, \
-                       sb->d_rec, sb->d_dist + StepBuffers::kHeader, sb->stride, sb->rec_stride, nslots_used,  \
-                       n_rows_hw_, n_queries_, reinterpret_cast<int *>(sb->d_dist))
-    if (metric_ == M_SQ) LAUNCH(M_SQ);
-    else if (metric_ == M_COS) LAUNCH(M_COS);
-    else if (metric_ == M_I8) LAUNCH(M_I8);
-    else LAUNCH(M_UCOS);
-#undef LAUNCH
+    with_metric(metric_, [&](auto m) {
+        hipLaunchKernelGGL(slot_distance_kernel<m>, grid, block, 0, st, d_rows_, d_row_sn_, d_queries_, d_q_sn_, pitch_, sb->d_rec,
+                           sb->d_dist + StepBuffers::kHeader, sb->stride, sb->rec_stride, nslots_used, n_rows_hw_, n_queries_,
+                           reinterpret_cast<int *>(sb->d_dist));
+    });
     HIP_OK(hipGetLastError());
     if (sb->timed) HIP_OK(hipEventRecord((hipEvent_t)sb->t1, st));
     // guard word + distances of the used slots: one copy
@@ -958,7 +997,7 @@ bool Device::set_graph(const int *adj0, long long n, int stride0, const int *lev
 // more resident waves to hide memory latency: 7.6 -> 6.1 ms per 10k-query launch going from 1024
 // to 512 entries.  Beyond LDS + spill capacity the traversal is flagged for the lock-step path.
 // Register sets of the sorted-list traversal (SortedTop<NS>: k <= 64 * NS); 0 = two-heap traversal
-// only.  HNSW_MI355X_SORTED_TOP=0 forces the latter (the tests run both).
+// only.  Diag sorted_top=0 forces the latter (the tests run both).
 static int sorted_top_sets(int k)
 {
     if (diag("sorted_top", 1) == 0) return 0;
@@ -999,10 +1038,10 @@ static int spill_cap_for_tests()
 // Row loads overlapped with the visited atomics in launches that do not fill the chip, and in every launch on a
 // graph large enough for the visited hash tables: there the traversal is bound by rows in flight, not by bytes
 // (10M x 96 int8: 2.19 -> 2.43 M queries/s, 1.03 -> 1.12 M adds/s; 10M x 128 f32: +3 % / +5 %), while a full
-// launch at 1M nodes is bandwidth-bound and gains nothing.  HNSW_MI355X_OVERLAP=0 disables, =2 forces it for
+// launch at 1M nodes is bandwidth-bound and gains nothing.  Diag overlap=0 disables, =2 forces it for
 // every launch (tests).
 // Shadow traversals in the search launches (graph_search_kernel): idle waves of a draining launch start the exact
-// traversal of the jobs still running.  HNSW_MI355X_SHADOW=0 disables (tests run both).
+// traversal of the jobs still running.  Diag shadow=0 disables (tests run both).
 static bool shadow_mode()
 {
     return diag("shadow", 1) != 0;
@@ -1016,7 +1055,7 @@ static int overlap_mode()
 // 2 whenever the graph allows it (adjacency lists of at most 64 entries; tests).
 // KnnQuery launches run WITHOUT a visited set (traverse_sorted, oflags bit 3): every listed neighbour's row is requested as
 // soon as the list is known, and a neighbour seen before is recognised by what the set was standing in for -- it is still in
-// the result list, or the push test turns it away again.  HNSW_MI355X_NOVIS=0 keeps the sets, =1 drops them only on the
+// the result list, or the push test turns it away again.  Diag novis=0 keeps the sets, =1 drops them only on the
 // graphs whose sets are hash tables (A/B runs; same answers either way).  Measured, same box: C2 (1M x 128, bitsets) 2.46-2.56
 // -> 3.07 M queries/s (25-26 -> 20.7 ms per 65 536-query launch, +2.5 % rows measured), 12 500-query calls 2.0 -> 2.39 M; C4-size
 // 1.68 -> 2.03 M, C5-size 2.26 -> 2.70 M.
@@ -1032,24 +1071,34 @@ static int lat_mode()
 }
 
 // The MFMA Gram-block prefilter of RelativeNeighborPruning (device_kernels.h): on by default where it applies
-// (cosine family, dim % 8 == 0); HNSW_MI355X_MFMA=0 keeps the exact-only forms (the tests run both).
+// (cosine family, dim % 8 == 0); diag mfma=0 keeps the exact-only forms (the tests run both).
 static bool mfma_heuristic()
 {
     return diag("mfma", 1) != 0;
 }
 
+// The visited set of a traversal launch: a bitset of `words` words per wave (s_visited_), or per-wave hash tables of tab_cap
+// entries (tab != nullptr), whose launches never touch the bitset arena -- bytes_per_job is what ensure_search_scratch sizes it by.
+struct VisitedScratch {
+    long long words = 0;
+    size_t bytes_per_job = 0;
+    int *tab = nullptr;
+    int tab_cap = 0;
+};
+
 // The per-wave visited-id hash tables (VisitedSet): capacity a power of two, >= 16384 and >= 64 per
 // beam entry (a traversal visits roughly 35 ids per beam entry), all entries -1 between jobs.
-// HNSW_MI355X_VIS_HASH=1/0 forces / forbids them; HNSW_MI355X_VIS_HASH_CAP overrides the capacity (tests).
-bool Device::visited_table(size_t vis_bytes_per_job, int k, int **out, int *out_cap, int min_cap, bool allow_hash)
+// Diag vis_hash=1/0 forces / forbids them; vis_hash_cap overrides the capacity (tests).
+bool Device::visited_scratch(int k, int min_cap, bool allow_hash, VisitedScratch *v)
 {
-    *out = nullptr;
-    *out_cap = 0;
+    *v = VisitedScratch{};
+    v->words = ((g_n_ + 31) / 32 + 3) & ~3LL;
+    v->bytes_per_job = sizeof(unsigned) * (size_t)v->words;
     if (!allow_hash) return true; // (the eight-set kernels have no hash-table form: their launches keep bitsets whatever the graph's size)
     const int e = diag("vis_hash", -1);
     // measured: at 1M nodes (125-KB bitsets) the bitset is faster (2.5 M vs 1.9 M queries/s on C2); at
     // 10M (1.25 MB) the table wins (1.48 M vs 1.28 M with the log-cleared bitset, 0.98 M streaming it)
-    const bool want = e >= 0 ? e != 0 : vis_bytes_per_job > (512u << 10);
+    const bool want = e >= 0 ? e != 0 : v->bytes_per_job > (512u << 10);
     if (!want) return true;
     int cap = 16384;
     while (cap < 64 * k && cap < (1 << 22)) cap <<= 1;
@@ -1066,9 +1115,102 @@ bool Device::visited_table(size_t vis_bytes_per_job, int k, int **out, int *out_
         s_vistab_cap_ = need;
         s_vistab_each_ = cap;
     }
-    *out = s_vistab_;
-    *out_cap = cap;
+    v->tab = s_vistab_;
+    v->tab_cap = cap;
+    v->words = 0;          // the hashed kernels never touch the bitset arena: do not allocate one
+    v->bytes_per_job = 16;
     return true;
+}
+
+// ---- traversal launches: which form of graph_search_kernel / graph_insert_search_kernel, on how many waves, with which flags ----
+// Device::plan_traversal decides what holds for a whole call (register sets, visited set, novis), place_traversal what holds for
+// one launch (form, waves, flags), traversal_kernel names the instantiation.
+struct TraversalLaunch {
+    int metric, max_slots, num_cu;
+    size_t lds;          // the traversal's LDS (search_lds_bytes)
+    int ns;              // sorted-top register sets: 2, 4, 8 (beams up to 128 / 256 / 512)
+    bool exact_only;     // the exact two-heap traversal alone: the two-set form with launch flag 0x200
+    VisitedScratch vis;
+    bool novis;          // no visited set at all: flags 9 (bit 3 with the overlap bit)
+    bool lat_ok;         // the latency form may run: sorted top, lists of at most 64 ids, room for its mailbox
+    // per launch
+    int form;            // kFormLat, kFormLean, kFormPlain
+    int slots, grid;     // the form's resident waves; grid = min(jobs, slots)
+    unsigned block;      // 128 threads for the latency form (logic wave + memory wave), else 64
+    size_t lds_total;    // lds, plus kTeamLds of mailbox for the latency form
+    int flags;           // 0x200 (exact only) | 9 (novis) or 1 (overlap); the launch site adds 0x100 (shadow, search) / 2 (mfma, insert)
+};
+
+bool Device::plan_traversal(bool insert, int k, bool two_heap, size_t lds, TraversalLaunch *t)
+{
+    const int ns = g_n_ < kSortedTopMaxNodes && !two_heap ? sorted_top_sets(k) : 0;
+    t->metric = metric_;
+    t->max_slots = max_slots();
+    t->num_cu = num_cu_;
+    t->lds = lds;
+    t->exact_only = ns == 0; // two_heap callers, beams beyond 512 entries, diag sorted_top=0
+    t->ns = t->exact_only ? 2 : ns;
+    if (!visited_scratch(k, 512, t->ns != 8, &t->vis)) return false;
+    // (rows of more than 1 KB keep the sets: their traffic is small beside the rows', and the rows of re-seen neighbours are what
+    //  costs -- C3's 3-KB rows: 282.7 k queries/s with the sets against 273.6 k without, build 69.5 k against 61.3 k adds/s.
+    //  Add's searches run without a set as well; diag novis_insert=0 keeps the sets there)
+    const int novis = novis_mode();
+    t->novis = (!insert || diag("novis_insert", 1) != 0) && g_stride0_ - 2 <= 64 && overlap_mode() != 0 && (size_t)pitch_ * sizeof(float) <= 1024 &&
+               (novis == 2 || (novis == 1 && t->vis.tab != nullptr));
+    t->lat_ok = !t->exact_only && g_stride0_ - 2 <= 64 && lds + kTeamLds <= 64 * 1024;
+    return true;
+}
+
+// The traversal kernel instantiation of (metric, NS, hashed, form).  This names exactly the forms device_kernels.h instantiates
+// (HNSW_FOR_EACH_TRAVERSAL, HNSW_FOR_EACH_TRAVERSAL_LAT, HNSW_FOR_EACH_TRAVERSAL_LEAN): NS = 8 has no hashed form (visited_scratch() is
+// told so), lean forms exist for graph_search_kernel with NS <= 4 only, graph_insert_search_kernel has none.  The forms of one kernel
+// share a type: one function pointer serves the occupancy query and the launch.
+template <bool Insert, int M, int NS, bool H>
+static auto traversal_form(int form)
+{
+    if constexpr (Insert)
+        return form == kFormLat ? &graph_insert_search_kernel<M, NS, H, kFormLat> : &graph_insert_search_kernel<M, NS, H, kFormPlain>;
+    else if constexpr (NS <= 4)
+        return form == kFormLat ? &graph_search_kernel<M, NS, H, kFormLat>
+               : form == kFormLean ? &graph_search_kernel<M, NS, H, kFormLean> : &graph_search_kernel<M, NS, H, kFormPlain>;
+    else
+        return form == kFormLat ? &graph_search_kernel<M, NS, H, kFormLat> : &graph_search_kernel<M, NS, H, kFormPlain>;
+}
+template <bool Insert>
+static auto traversal_kernel(const TraversalLaunch &t, int form)
+{
+    const bool hashed = t.vis.tab != nullptr;
+    decltype(traversal_form<Insert, M_SQ, 2, false>(0)) kernel = nullptr;
+    with_metric(t.metric, [&](auto m) {
+        if (t.ns == 2) kernel = hashed ? traversal_form<Insert, m, 2, true>(form) : traversal_form<Insert, m, 2, false>(form);
+        else if (t.ns == 4) kernel = hashed ? traversal_form<Insert, m, 4, true>(form) : traversal_form<Insert, m, 4, false>(form);
+        else kernel = traversal_form<Insert, m, 8, false>(form);
+    });
+    return kernel;
+}
+
+// One launch of nj jobs: the latency form when the jobs fit its resident waves (diag lat=2: whenever lat_ok), else the lean form for a
+// search without visited sets (diag lean=0: the plain form, which reads flags 9 itself), else the plain form.  (No lean form of the
+// insert kernel: measured, the f32 insert search LOSES 6 % with it -- profiles/r5_lean_ab.log.)  One occupancy query per form weighed.
+template <bool Insert>
+static auto place_traversal(TraversalLaunch &t, int nj)
+{
+    const bool hashed = t.vis.tab != nullptr;
+    const int lat = lat_mode();
+    t.form = kFormPlain;
+    if (t.lat_ok && lat != 0) {
+        const int slots = std::min(t.max_slots, resident_blocks(traversal_kernel<Insert>(t, kFormLat), t.lds + kTeamLds, t.num_cu, 128));
+        if (slots > 0 && (lat == 2 || nj <= slots)) { t.form = kFormLat; t.slots = slots; }
+    }
+    if (!Insert && t.form == kFormPlain && t.novis && !t.exact_only && lean_mode() && t.ns <= 4) t.form = kFormLean;
+    const auto kernel = traversal_kernel<Insert>(t, t.form);
+    if (t.form != kFormLat) t.slots = std::min(t.max_slots, resident_blocks(kernel, t.lds, t.num_cu));
+    t.grid = std::min(nj, t.slots);
+    t.block = t.form == kFormLat ? 128 : 64;
+    t.lds_total = t.lds + (t.form == kFormLat ? kTeamLds : 0);
+    const int overlap = overlap_mode();
+    t.flags = (t.exact_only ? 0x200 : 0) | (t.novis ? 9 : overlap == 2 || (overlap == 1 && (nj <= t.slots || hashed)) ? 1 : 0);
+    return kernel;
 }
 
 // chunk: jobs per launch (job / result buffers); slots: waves of a persistent launch (visited
@@ -1135,20 +1277,13 @@ bool Device::insert_search_batch(const SearchJob *jobs, int njobs, int k, int ma
     const int cand_cap = cand_lds_cap(k, pitch_, true, nbcap());
     const size_t lds = search_lds_bytes(k, cand_cap, pitch_, true, nbcap());
     if (lds > 64 * 1024) { set_dev_error("insert_search_batch: beam width / dimension exceed the LDS budget"); return false; }
-    const int ns_req = g_n_ < kSortedTopMaxNodes ? sorted_top_sets(k) : 0;
-    const bool exact_only = ns_req == 0;           // beams beyond 512 entries / HNSW_MI355X_SORTED_TOP=0: the two-set form with launch flag 0x200
-    const int ns = exact_only ? 2 : ns_req;
     if (!bind()) return false;
     hipStream_t st = S(stream_);
     const int sel_stride = max_edges0;
-    long long vis_words = ((g_n_ + 31) / 32 + 3) & ~3LL;
-    size_t vis_bytes_per_job = sizeof(unsigned) * (size_t)vis_words;
     const long long chunk = std::min<long long>(njobs, 1 << 20);
-    int *vis_tab = nullptr;
-    int vis_tab_cap = 0;
-    if (!visited_table(vis_bytes_per_job, k, &vis_tab, &vis_tab_cap, 512, ns != 8)) return false;
-    if (vis_tab) { vis_words = 0; vis_bytes_per_job = 16; } // the HASHED kernels never touch the bitset arena: do not allocate one
-    if (!ensure_search_scratch(chunk, max_slots(), 0, vis_bytes_per_job)) return false;
+    TraversalLaunch tl;
+    if (!plan_traversal(true, k, false, lds, &tl)) return false;
+    if (!ensure_search_scratch(chunk, max_slots(), 0, tl.vis.bytes_per_job)) return false;
     const size_t nU = (size_t)std::max(n_upper, 1);
     if (!grow_dev(&s_sel_, &s_sel_cap_, (size_t)njobs * sel_stride) || !grow_dev(&s_lcnt_, &s_lcnt_cap_, (size_t)njobs) ||
         !grow_dev(&s_selU_, &s_selU_cap_, nU * sel_stride) || !grow_dev(&s_cntU_, &s_cntU_cap_, nU) ||
@@ -1209,51 +1344,17 @@ bool Device::insert_search_batch(const SearchJob *jobs, int njobs, int k, int ma
                 d_order = s_order_;
             }
         }
-        // (Add's searches without a visited set as well -- see novis_mode(); HNSW_MI355X_NOVIS_INSERT=0 keeps the sets there)
-        const bool novis_ins_on = diag("novis_insert", 1) != 0; // (read per call, like every other switch)
-        const bool novis_ins_ = novis_ins_on && g_stride0_ - 2 <= 64 && overlap_mode() != 0 && (size_t)pitch_ * sizeof(float) <= 1024 && (novis_mode() == 2 || (novis_mode() == 1 && vis_tab != nullptr));
         HIP_OK(hipMemsetAsync(s_jobctr_, 0, sizeof(int), st));
         HIP_OK(hipMemsetAsync(p_evals, 0, sizeof(unsigned long long), st));
         const bool timed = profiling_;
         if (timed) HIP_OK(hipEventRecord((hipEvent_t)ev0_, st));
-#define LAUNCH2L(M, NS_, H_, LAT_, SLOTS, GRID, LDS, CAP) \
-        hipLaunchKernelGGL((graph_insert_search_kernel<M, NS_, H_, LAT_>), dim3(std::min<int>(GRID, SLOTS)), \
-                       dim3(LAT_ == kFormLat ? 128 : 64), (LDS) + (LAT_ == kFormLat ? kTeamLds : 0), st, d_rows_, d_row_sn_, pitch_, g_adj0_, g_stride0_, \
-                       g_upper_, g_pool_, g_strideU_, s_jobs_, k, CAP, reinterpret_cast<ND *>(s_spill_), spill_cap_for_tests(),  \
-                       max_edges0, s_visited_, vis_words, vis_tab, vis_tab_cap, p_sel0 + (size_t)off * sel_stride, p_cnt0 + off, p_selU, p_cntU,        \
-                       sel_stride, p_flag + off, p_evals, nbcap(), GRID, s_jobctr_, (exact_only ? 0x200 : 0) | (novis_ins_ ? 9 : (overlap_mode() == 2 || (overlap_mode() == 1 && (GRID <= SLOTS || vis_tab != nullptr))) ? 1 : 0) | (mfma_heuristic() ? 2 : 0), d_order, \
-                       windowed ? p_log : (int *)nullptr, read_log_cap)
-#define LAUNCH2(M, NS_, H_, GRID, LDS, CAP) \
-    do { \
-        const int lslots_ = !exact_only && lat_mode() != 0 && g_stride0_ - 2 <= 64 && (LDS) + kTeamLds <= 64 * 1024 ? std::min(max_slots(), resident_blocks(graph_insert_search_kernel<M, NS_, H_, kFormLat>, (LDS) + kTeamLds, num_cu_, 128)) : 0; \
-        if (lslots_ > 0 && (lat_mode() == 2 || GRID <= lslots_)) { LAUNCH2L(M, NS_, H_, kFormLat, lslots_, GRID, LDS, CAP); stats_.lat_launches++; } \
-        else { /* (no lean form of this kernel: measured, the f32 insert search LOSES 6 % with it -- profiles/r5_lean_ab.log) */ \
-            const int slots_ = std::min(max_slots(), resident_blocks(graph_insert_search_kernel<M, NS_, H_, kFormPlain>, LDS, num_cu_)); \
-            LAUNCH2L(M, NS_, H_, kFormPlain, slots_, GRID, LDS, CAP); \
-        } \
-    } while (0)
-#define LAUNCH3(NS_, H_, GRID, LDS, CAP)                                                                              \
-    do {                                                                                                                   \
-        if (metric_ == M_SQ) LAUNCH2(M_SQ, NS_, H_, GRID, LDS, CAP);                                                  \
-        else if (metric_ == M_COS) LAUNCH2(M_COS, NS_, H_, GRID, LDS, CAP);                                           \
-        else if (metric_ == M_I8) LAUNCH2(M_I8, NS_, H_, GRID, LDS, CAP);                                             \
-        else LAUNCH2(M_UCOS, NS_, H_, GRID, LDS, CAP);                                                                \
-    } while (0)
-#define LAUNCH(NS_, GRID, LDS, CAP)                                                                                   \
-    do {                                                                                                                   \
-        if (vis_tab) LAUNCH3(NS_, true, GRID, LDS, CAP);                                                              \
-        else LAUNCH3(NS_, false, GRID, LDS, CAP);                                                                     \
-    } while (0)
-        switch (ns) {
-        case 2: LAUNCH(2, nj, lds, cand_cap); break;
-        case 4: LAUNCH(4, nj, lds, cand_cap); break;
-        default: LAUNCH3(8, false, nj, lds, cand_cap); break; // (no hash-table form: visited_table() was told so)
-        }
+        const auto kernel = place_traversal<true>(tl, nj);
+        hipLaunchKernelGGL(kernel, dim3(tl.grid), dim3(tl.block), tl.lds_total, st, d_rows_, d_row_sn_, pitch_, g_adj0_, g_stride0_, g_upper_, g_pool_,
+                           g_strideU_, s_jobs_, k, cand_cap, reinterpret_cast<ND *>(s_spill_), spill_cap_for_tests(), max_edges0, s_visited_, tl.vis.words,
+                           tl.vis.tab, tl.vis.tab_cap, p_sel0 + (size_t)off * sel_stride, p_cnt0 + off, p_selU, p_cntU, sel_stride, p_flag + off, p_evals,
+                           nbcap(), nj, s_jobctr_, tl.flags | (mfma_heuristic() ? 2 : 0), d_order, windowed ? p_log : (int *)nullptr, read_log_cap);
+        if (tl.form == kFormLat) stats_.lat_launches++;
         HIP_OK(hipGetLastError());
-#undef LAUNCH
-#undef LAUNCH3
-#undef LAUNCH2
-#undef LAUNCH2L
         if (timed) HIP_OK(hipEventRecord((hipEvent_t)ev1_, st));
         if (!windowed) HIP_OK(hipMemcpyAsync(h_ev, s_evals_, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
         if (windowed) { // one launch (njobs <= chunk): everything the host validates with rides on the same wait
@@ -1266,36 +1367,18 @@ bool Device::insert_search_batch(const SearchJob *jobs, int njobs, int k, int ma
             const int k_cap = nbcap();
             const size_t lds_link = ((search_lds_bytes(k_cap, 0, pitch_, true, nbcap()) + 15) & ~(size_t)15) + 4u * (size_t)(kNewMax + 1) * nbcap();
             const int grid = (njobs + n_upper) * sel_stride;
-#define LAUNCH_DRY(M)                                                                                                          \
-    hipLaunchKernelGGL(graph_link_dry_sel_kernel<M>, dim3(grid), dim3(64), lds_link, st, d_rows_, d_row_sn_, pitch_, g_adj0_, g_stride0_, \
-                       g_upper_, g_pool_, g_strideU_, s_jobs_, p_flag, p_sel0, p_cnt0, p_selU, p_cntU, sel_stride, d_owner, njobs, max_edges0, \
-                       k_cap, d_dry0, d_dryU, p_evals, nbcap(), g_tested0_, g_testedU_, g_n_, d_drop0)
-            if (metric_ == M_SQ) LAUNCH_DRY(M_SQ);
-            else if (metric_ == M_COS) LAUNCH_DRY(M_COS);
-            else if (metric_ == M_I8) LAUNCH_DRY(M_I8);
-            else LAUNCH_DRY(M_UCOS);
-#undef LAUNCH_DRY
+            with_metric(metric_, [&](auto m) {
+                hipLaunchKernelGGL(graph_link_dry_sel_kernel<m>, dim3(grid), dim3(64), lds_link, st, d_rows_, d_row_sn_, pitch_, g_adj0_, g_stride0_,
+                                   g_upper_, g_pool_, g_strideU_, s_jobs_, p_flag, p_sel0, p_cnt0, p_selU, p_cntU, sel_stride, d_owner, njobs, max_edges0,
+                                   k_cap, d_dry0, d_dryU, p_evals, nbcap(), g_tested0_, g_testedU_, g_n_, d_drop0);
+            });
             HIP_OK(hipGetLastError());
             HIP_OK(hipMemcpyAsync(hb, db, need - b_rep, hipMemcpyDeviceToHost, st)); // selections, counts, flags, evaluations, read logs, dry-run codes, lost ids
         }
         const bool last_chunk = off + nj >= njobs;
         if (!windowed && last_chunk) HIP_OK(hipMemcpyAsync(h_flag, s_iflag_, b_flag, hipMemcpyDeviceToHost, st)); // the flags ride on the same wait
         HIP_OK(hipStreamSynchronize(st)); // the job staging buffer is reused by the next chunk
-        stats_.search_launches++;
-        stats_.search_evals += *h_ev;
-        stats_.insert_launches++;
-        stats_.insert_evals += *h_ev;
-        if (vis_tab) stats_.visited_hash_launches++;
-        if (timed) {
-            float ms = 0.f;
-            HIP_OK(hipEventElapsedTime(&ms, (hipEvent_t)ev0_, (hipEvent_t)ev1_));
-            stats_.search_kernel_ms += ms;
-            stats_.search_timed_launches++;
-            stats_.search_timed_evals += *h_ev;
-            stats_.insert_kernel_ms += ms;
-            stats_.insert_timed_launches++;
-            stats_.insert_timed_evals += *h_ev;
-        }
+        if (!count_launch(&kInsertFamily, *h_ev, tl.vis.tab != nullptr, timed, ev0_, ev1_)) return false;
     }
     // Only the flags come back (with the last launch's wait): the selections stay on the device, where the link half reads
     // them (link_batch_planned); a caller that links on the host fetches them (fetch_insert_selections).
@@ -1457,15 +1540,11 @@ bool Device::link_batch_begin(int set, const int *rows, int nrows, int row_strid
         if (ls.timed) HIP_OK(hipEventRecord((hipEvent_t)ls.ev_start, st));
         const int k_cap = nbcap();
         const size_t lds = ((search_lds_bytes(k_cap, 0, pitch_, true, nbcap()) + 15) & ~(size_t)15) + 4u * (size_t)(kNewMax + 1) * nbcap();
-#define LAUNCH(M)                                                                                                          \
-    hipLaunchKernelGGL(graph_link_kernel<M>, dim3(ngroups), dim3(64), lds, st, d_rows_, d_row_sn_, pitch_, g_adj0_, g_stride0_,  \
-                       g_upper_, g_pool_, g_strideU_, s_lk_[1], s_lk_[1] + ngroups, s_lk_[2], (const int *)nullptr, s_lk_[3], max_edges0, k_cap, \
-                       s_lk_[4], list_stride, s_evals_, nbcap(), g_tested0_, g_testedU_, (const int *)nullptr)
-        if (metric_ == M_SQ) LAUNCH(M_SQ);
-        else if (metric_ == M_COS) LAUNCH(M_COS);
-        else if (metric_ == M_I8) LAUNCH(M_I8);
-        else LAUNCH(M_UCOS);
-#undef LAUNCH
+        with_metric(metric_, [&](auto m) {
+            hipLaunchKernelGGL(graph_link_kernel<m>, dim3(ngroups), dim3(64), lds, st, d_rows_, d_row_sn_, pitch_, g_adj0_, g_stride0_, g_upper_, g_pool_,
+                               g_strideU_, s_lk_[1], s_lk_[1] + ngroups, s_lk_[2], (const int *)nullptr, s_lk_[3], max_edges0, k_cap, s_lk_[4], list_stride,
+                               s_evals_, nbcap(), g_tested0_, g_testedU_, (const int *)nullptr);
+        });
         HIP_OK(hipGetLastError());
         if (ls.timed) HIP_OK(hipEventRecord((hipEvent_t)ls.ev_stop, st));
         if (want_lists) HIP_OK(hipMemcpyAsync(ls.h_out, s_lk_[4], sizeof(int) * (size_t)ngroups * list_stride, hipMemcpyDeviceToHost, st));
@@ -1497,20 +1576,16 @@ bool Device::link_dry_run(const int *jobs3, int n, int max_edges0, int *changed)
     HIP_OK(hipMemsetAsync(s_evals_, 0, sizeof(unsigned long long), st));
     const int k_cap = nbcap();
     const size_t lds = ((search_lds_bytes(k_cap, 0, pitch_, true, nbcap()) + 15) & ~(size_t)15) + 4u * (size_t)(kNewMax + 1) * nbcap();
-#define LAUNCH(M)                                                                                                          \
-    hipLaunchKernelGGL(graph_link_dry_kernel<M>, dim3(n), dim3(64), lds, st, d_rows_, d_row_sn_, pitch_, g_adj0_, g_stride0_,   \
-                       g_upper_, g_pool_, g_strideU_, s_dry_, max_edges0, k_cap, s_dry_ + (size_t)n * 3, s_evals_, nbcap(), g_tested0_, g_testedU_)
-    if (metric_ == M_SQ) LAUNCH(M_SQ);
-    else if (metric_ == M_COS) LAUNCH(M_COS);
-    else if (metric_ == M_I8) LAUNCH(M_I8);
-    else LAUNCH(M_UCOS);
-#undef LAUNCH
+    with_metric(metric_, [&](auto m) {
+        hipLaunchKernelGGL(graph_link_dry_kernel<m>, dim3(n), dim3(64), lds, st, d_rows_, d_row_sn_, pitch_, g_adj0_, g_stride0_, g_upper_, g_pool_,
+                           g_strideU_, s_dry_, max_edges0, k_cap, s_dry_ + (size_t)n * 3, s_evals_, nbcap(), g_tested0_, g_testedU_);
+    });
     HIP_OK(hipGetLastError());
     HIP_OK(hipMemcpyAsync(h + (size_t)n * 3, s_dry_ + (size_t)n * 3, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, st));
     HIP_OK(hipMemcpyAsync(h_ev, s_evals_, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
     HIP_OK(hipStreamSynchronize(st));
     memcpy(changed, h + (size_t)n * 3, sizeof(int) * (size_t)n);
-    stats_.search_launches++;
+    stats_.search_launches++; // a search launch whose evaluations are link work -- but not a link launch
     stats_.search_evals += *h_ev;
     stats_.link_evals += *h_ev;
     return true;
@@ -1583,15 +1658,11 @@ bool Device::link_batch_planned(int njobs, int n_upper, int max_edges0)
         HIP_OK(hipGetLastError());
         const int k_cap = nbcap();
         const size_t lds = ((search_lds_bytes(k_cap, 0, pitch_, true, nbcap()) + 15) & ~(size_t)15) + 4u * (size_t)(kNewMax + 1) * nbcap();
-#define LAUNCH(M)                                                                                                          \
-    hipLaunchKernelGGL(graph_link_kernel<M>, dim3(G), dim3(64), lds, st, d_rows_, d_row_sn_, pitch_, g_adj0_, g_stride0_,       \
-                       g_upper_, g_pool_, g_strideU_, lp_grp_[0], lp_grp_[1], lp_grp_[2], lp_grp_[3], lp_grp_[5], max_edges0, k_cap, \
-                       (int *)nullptr, 0, s_evals_, nbcap(), g_tested0_, g_testedU_, bounded ? (const int *)lp_counters_ : (const int *)nullptr)
-        if (metric_ == M_SQ) LAUNCH(M_SQ);
-        else if (metric_ == M_COS) LAUNCH(M_COS);
-        else if (metric_ == M_I8) LAUNCH(M_I8);
-        else LAUNCH(M_UCOS);
-#undef LAUNCH
+        with_metric(metric_, [&](auto m) {
+            hipLaunchKernelGGL(graph_link_kernel<m>, dim3(G), dim3(64), lds, st, d_rows_, d_row_sn_, pitch_, g_adj0_, g_stride0_, g_upper_, g_pool_,
+                               g_strideU_, lp_grp_[0], lp_grp_[1], lp_grp_[2], lp_grp_[3], lp_grp_[5], max_edges0, k_cap, (int *)nullptr, 0, s_evals_,
+                               nbcap(), g_tested0_, g_testedU_, bounded ? (const int *)lp_counters_ : (const int *)nullptr);
+        });
         HIP_OK(hipGetLastError());
     }
     if (timed) HIP_OK(hipEventRecord((hipEvent_t)ev1_, st));
@@ -1602,21 +1673,7 @@ bool Device::link_batch_planned(int njobs, int n_upper, int max_edges0)
         set_dev_error("link_batch_planned: inconsistent selection data on the device (guard " + std::to_string(h_ctr[3]) + ")");
         return false;
     }
-    stats_.search_launches++;
-    stats_.search_evals += *h_ev;
-    stats_.link_launches++;
-    stats_.link_evals += *h_ev;
-    if (timed) {
-        float ms = 0.f;
-        HIP_OK(hipEventElapsedTime(&ms, (hipEvent_t)ev0_, (hipEvent_t)ev1_));
-        stats_.search_kernel_ms += ms;
-        stats_.search_timed_launches++;
-        stats_.search_timed_evals += *h_ev;
-        stats_.link_kernel_ms += ms;
-        stats_.link_timed_launches++;
-        stats_.link_timed_evals += *h_ev;
-    }
-    return true;
+    return count_launch(&kLinkFamily, *h_ev, false, timed, ev0_, ev1_);
 }
 
 bool Device::download_graph(int *adj0, long long n, int *pool, long long pool_len)
@@ -1638,22 +1695,7 @@ bool Device::link_batch_finish(int set, const int **out_lists)
     HIP_OK(hipEventSynchronize((hipEvent_t)ls.ev_done));
     ls.busy = false;
     if (out_lists) *out_lists = ls.h_out;
-    if (ls.ngroups > 0) {
-        stats_.search_launches++;
-        stats_.search_evals += *ls.h_ev;
-        stats_.link_launches++;
-        stats_.link_evals += *ls.h_ev;
-        if (ls.timed) {
-            float ms = 0.f;
-            HIP_OK(hipEventElapsedTime(&ms, (hipEvent_t)ls.ev_start, (hipEvent_t)ls.ev_stop));
-            stats_.search_kernel_ms += ms;
-            stats_.search_timed_launches++;
-            stats_.search_timed_evals += *ls.h_ev;
-            stats_.link_kernel_ms += ms;
-            stats_.link_timed_launches++;
-            stats_.link_timed_evals += *ls.h_ev;
-        }
-    }
+    if (ls.ngroups > 0 && !count_launch(&kLinkFamily, *ls.h_ev, false, ls.timed, ls.ev_start, ls.ev_stop)) return false;
     return true;
 }
 
@@ -1707,19 +1749,12 @@ bool Device::search_batch_impl(const SearchJob *jobs, int njobs, int k, int k_ou
     const int cand_cap = cand_lds_cap(k, pitch_, false, nbcap());
     const size_t lds = search_lds_bytes(k, cand_cap, pitch_, false, nbcap());
     if (lds > 64 * 1024) { set_dev_error("search_batch: beam width / dimension exceed the LDS budget"); return false; }
-    const int ns_req = (g_n_ < kSortedTopMaxNodes && !two_heap) ? sorted_top_sets(k) : 0;
-    const bool exact_only = ns_req == 0;           // two_heap callers, beams beyond 512 entries, HNSW_MI355X_SORTED_TOP=0: launch flag 0x200
-    const int ns = exact_only ? 2 : ns_req;
     if (!bind()) return false;
     hipStream_t st = S(stream_);
-    long long vis_words = ((g_n_ + 31) / 32 + 3) & ~3LL;
-    size_t vis_bytes_per_job = sizeof(unsigned) * (size_t)vis_words;
     const long long chunk = std::min<long long>(njobs, 1 << 20);
-    int *vis_tab = nullptr;
-    int vis_tab_cap = 0;
-    if (!visited_table(vis_bytes_per_job, k, &vis_tab, &vis_tab_cap, 512, ns != 8)) return false;
-    if (vis_tab) { vis_words = 0; vis_bytes_per_job = 16; } // see insert_search_batch
-    if (!ensure_search_scratch(chunk, max_slots(), k_out, vis_bytes_per_job)) return false;
+    TraversalLaunch tl;
+    if (!plan_traversal(false, k, two_heap, lds, &tl)) return false;
+    if (!ensure_search_scratch(chunk, max_slots(), k_out, tl.vis.bytes_per_job)) return false;
     // pinned layout: [evals (16 B) | jobs | ids | dists | flags]
     const size_t b_jobs = sizeof(SearchJob) * (size_t)chunk, b_res = 4u * (size_t)chunk * k_out;
     char *hs = static_cast<char *>(pinned_stage(16 + b_jobs + 2 * b_res + 4u * (size_t)chunk));
@@ -1739,9 +1774,6 @@ bool Device::search_batch_impl(const SearchJob *jobs, int njobs, int k, int k_ou
     const bool compact = njobs == chunk && 2 * b_res + 4u * (size_t)chunk <= (size_t)1 << 20;
     int *d_flag = compact ? reinterpret_cast<int *>(d_d + (size_t)chunk * k_out) : s_flag_;
     unsigned long long *d_ev = compact ? reinterpret_cast<unsigned long long *>(s_jobctr_ + 2) : s_evals_;
-    // (rows of more than 1 KB: the set's traffic is small beside the rows', and the rows of re-seen neighbours are what costs --
-    //  C3's 3-KB rows: 282.7 k queries/s with the sets against 273.6 k without, build 69.5 k against 61.3 k adds/s)
-    const bool novis_ = g_stride0_ - 2 <= 64 && overlap_mode() != 0 && (size_t)pitch_ * sizeof(float) <= 1024 && (novis_mode() == 2 || (novis_mode() == 1 && vis_tab != nullptr));
     // a query set whose tail is still on the host (set_queries_streamed): the launch is gated on the rows' arrival
     const int *gate = tail_.n > 0 ? d_ready_ : nullptr;
     // whatever happens below, nothing stays pending -- and a tail that never went up (an error between the launch and
@@ -1763,46 +1795,14 @@ bool Device::search_batch_impl(const SearchJob *jobs, int njobs, int k, int k_ou
         if (!compact) HIP_OK(hipMemsetAsync(s_evals_, 0, sizeof(unsigned long long), st));
         const bool timed = profiling_;
         if (timed) HIP_OK(hipEventRecord((hipEvent_t)ev0_, st));
-#define LAUNCH2L(M, NS_, H_, LAT_, SLOTS, GRID, LDS, CAP) \
-        hipLaunchKernelGGL((graph_search_kernel<M, NS_, H_, LAT_>), dim3(std::min<int>(GRID, SLOTS)), \
-                       dim3(LAT_ == kFormLat ? 128 : 64), (LDS) + (LAT_ == kFormLat ? kTeamLds : 0), st, d_rows_, d_row_sn_, d_queries_, d_q_sn_, pitch_, \
-                       g_adj0_, g_stride0_, g_upper_, g_pool_, g_strideU_, s_jobs_, k, CAP, reinterpret_cast<ND *>(s_spill_), \
-                       spill_cap_for_tests(), s_visited_, vis_words, vis_tab, vis_tab_cap, k_out, d_ids, d_d, s_cnt_, d_flag, d_ev, nbcap(), GRID, s_jobctr_, (exact_only ? 0x200 : 0) | (novis_ ? 9 : (overlap_mode() == 2 || (overlap_mode() == 1 && (GRID <= SLOTS || vis_tab != nullptr))) ? 1 : 0) | (shadow_mode() && shadows_allowed_ ? 0x100 : 0), \
-                       gate)
-#define LAUNCH2(M, NS_, H_, GRID, LDS, CAP) \
-    do { \
-        const int lslots_ = !exact_only && lat_mode() != 0 && g_stride0_ - 2 <= 64 && (LDS) + kTeamLds <= 64 * 1024 ? std::min(max_slots(), resident_blocks(graph_search_kernel<M, NS_, H_, kFormLat>, (LDS) + kTeamLds, num_cu_, 128)) : 0; \
-        if (lslots_ > 0 && (lat_mode() == 2 || GRID <= lslots_)) { LAUNCH2L(M, NS_, H_, kFormLat, lslots_, GRID, LDS, CAP); stats_.lat_launches++; } \
-        else if (novis_ && !exact_only && lean_mode() && NS_ <= 4) { /* flags 9: the lean form (kFormLean; NS = 8 has none) */ \
-            const int slots_ = std::min(max_slots(), resident_blocks(graph_search_kernel<M, NS_, H_, (NS_ <= 4 ? kFormLean : kFormPlain)>, LDS, num_cu_)); \
-            LAUNCH2L(M, NS_, H_, (NS_ <= 4 ? kFormLean : kFormPlain), slots_, GRID, LDS, CAP); stats_.lean_launches++; \
-        } else { \
-            const int slots_ = std::min(max_slots(), resident_blocks(graph_search_kernel<M, NS_, H_, kFormPlain>, LDS, num_cu_)); \
-            LAUNCH2L(M, NS_, H_, kFormPlain, slots_, GRID, LDS, CAP); \
-        } \
-    } while (0)
-#define LAUNCH3(NS_, H_, GRID, LDS, CAP)                                                                              \
-    do {                                                                                                                   \
-        if (metric_ == M_SQ) LAUNCH2(M_SQ, NS_, H_, GRID, LDS, CAP);                                                  \
-        else if (metric_ == M_COS) LAUNCH2(M_COS, NS_, H_, GRID, LDS, CAP);                                           \
-        else if (metric_ == M_I8) LAUNCH2(M_I8, NS_, H_, GRID, LDS, CAP);                                             \
-        else LAUNCH2(M_UCOS, NS_, H_, GRID, LDS, CAP);                                                                \
-    } while (0)
-#define LAUNCH(NS_, GRID, LDS, CAP)                                                                                   \
-    do {                                                                                                                   \
-        if (vis_tab) LAUNCH3(NS_, true, GRID, LDS, CAP);                                                              \
-        else LAUNCH3(NS_, false, GRID, LDS, CAP);                                                                     \
-    } while (0)
-        switch (ns) {
-        case 2: LAUNCH(2, nj, lds, cand_cap); break;
-        case 4: LAUNCH(4, nj, lds, cand_cap); break;
-        default: LAUNCH3(8, false, nj, lds, cand_cap); break; // (no hash-table form: visited_table() was told so)
-        }
+        const auto kernel = place_traversal<false>(tl, nj);
+        hipLaunchKernelGGL(kernel, dim3(tl.grid), dim3(tl.block), tl.lds_total, st, d_rows_, d_row_sn_, d_queries_, d_q_sn_, pitch_, g_adj0_, g_stride0_,
+                           g_upper_, g_pool_, g_strideU_, s_jobs_, k, cand_cap, reinterpret_cast<ND *>(s_spill_), spill_cap_for_tests(), s_visited_,
+                           tl.vis.words, tl.vis.tab, tl.vis.tab_cap, k_out, d_ids, d_d, s_cnt_, d_flag, d_ev, nbcap(), nj, s_jobctr_,
+                           tl.flags | (shadow_mode() && shadows_allowed_ ? 0x100 : 0), gate);
+        if (tl.form == kFormLat) stats_.lat_launches++;
+        if (tl.form == kFormLean) stats_.lean_launches++;
         HIP_OK(hipGetLastError());
-#undef LAUNCH
-#undef LAUNCH3
-#undef LAUNCH2
-#undef LAUNCH2L
         if (timed) HIP_OK(hipEventRecord((hipEvent_t)ev1_, st));
         if (tail_.n > 0 && !upload_tail()) return false; // the rest of the query set, while the launch above is running
         if (compact) { // [ids | distances | flags] in one piece (nj == chunk: the device slab and the staging are laid out alike)
@@ -1827,17 +1827,7 @@ bool Device::search_batch_impl(const SearchJob *jobs, int njobs, int k, int k_ou
             else if (h_flag[i] == 4) { stats_.tie_windows++; h_flag[i] = 0; } // informational: a group window closed cleanly
         }
         memcpy(out_flag + off, h_flag, sizeof(int) * (size_t)nj);
-        const unsigned long long ev = *h_ev;
-        if (vis_tab) stats_.visited_hash_launches++;
-        stats_.search_launches++;
-        stats_.search_evals += ev;
-        if (timed) {
-            float ms = 0.f;
-            HIP_OK(hipEventElapsedTime(&ms, (hipEvent_t)ev0_, (hipEvent_t)ev1_));
-            stats_.search_kernel_ms += ms;
-            stats_.search_timed_launches++;
-            stats_.search_timed_evals += ev;
-        }
+        if (!count_launch(nullptr, *h_ev, tl.vis.tab != nullptr, timed, ev0_, ev1_)) return false;
     }
     for (int i = 0; i < njobs; ++i) stats_.search_overflows += (uint64_t)(out_flag[i] == 1);
     return true;
@@ -1886,15 +1876,11 @@ bool Device::relink_batch(const int *affected, const int *layer, const int *remo
     if (total_c > 0) memcpy(hs + o_c, cands, sizeof(int) * (size_t)total_c);
     HIP_OK(hipMemcpyAsync(s_rl_, hs, sizeof(int) * o_s, hipMemcpyHostToDevice, st));
     HIP_OK(hipMemsetAsync(s_evals_, 0, sizeof(unsigned long long), st));
-#define LAUNCH_RL(M)                                                                                                                  \
-    hipLaunchKernelGGL(graph_relink_kernel<M>, dim3(n), dim3(64), lds, st, d_rows_, d_row_sn_, pitch_, g_adj0_, g_stride0_, g_upper_,   \
-                       g_pool_, g_strideU_, reinterpret_cast<const int4 *>(s_rl_), s_rl_ + o_c, s_rl_ + o_off, s_rl_ + o_cnt, max_edges0,  \
-                       kcap, nb, s_rl_ + o_s, s_rl_ + o_n, s_rl_ + o_f, sel_stride, s_evals_, heap_order ? 1 : 0)
-    if (metric_ == M_SQ) LAUNCH_RL(M_SQ);
-    else if (metric_ == M_COS) LAUNCH_RL(M_COS);
-    else if (metric_ == M_I8) LAUNCH_RL(M_I8);
-    else LAUNCH_RL(M_UCOS);
-#undef LAUNCH_RL
+    with_metric(metric_, [&](auto m) {
+        hipLaunchKernelGGL(graph_relink_kernel<m>, dim3(n), dim3(64), lds, st, d_rows_, d_row_sn_, pitch_, g_adj0_, g_stride0_, g_upper_, g_pool_,
+                           g_strideU_, reinterpret_cast<const int4 *>(s_rl_), s_rl_ + o_c, s_rl_ + o_off, s_rl_ + o_cnt, max_edges0, kcap, nb, s_rl_ + o_s,
+                           s_rl_ + o_n, s_rl_ + o_f, sel_stride, s_evals_, heap_order ? 1 : 0);
+    });
     HIP_OK(hipGetLastError());
     unsigned long long *h_ev = reinterpret_cast<unsigned long long *>(hs + ((total + 1) & ~(size_t)1));
     HIP_OK(hipMemcpyAsync(hs + o_s, s_rl_ + o_s, sizeof(int) * (total - o_s), hipMemcpyDeviceToHost, st));
@@ -1903,7 +1889,7 @@ bool Device::relink_batch(const int *affected, const int *layer, const int *remo
     memcpy(out_sel, hs + o_s, sizeof(int) * (size_t)n * sel_stride);
     memcpy(out_cnt, hs + o_n, sizeof(int) * (size_t)n);
     memcpy(out_flag, hs + o_f, sizeof(int) * (size_t)n);
-    stats_.search_evals += *h_ev;
+    stats_.search_evals += *h_ev; // (evaluations only: no launch is counted for Remove's re-link)
     return true;
 }
 
@@ -1977,15 +1963,10 @@ bool Device::range_batch(const SearchJob *jobs, int njobs, float range, RangeRes
     if (lds > 64 * 1024) { set_dev_error("range_batch: dimension exceeds the LDS budget"); return false; }
     if (!bind()) return false;
     hipStream_t st = S(stream_);
-    long long vis_words = ((g_n_ + 31) / 32 + 3) & ~3LL;
-    size_t vis_bytes_per_job = sizeof(unsigned) * (size_t)vis_words;
-    int *vis_tab = nullptr;
-    int vis_tab_cap = 0;
-    // 32 768 slots: 24 576 visited ids before a hand-back; a step inserts up to kRangeFan lists of 128 ids
-    if (!visited_table(vis_bytes_per_job, 512, &vis_tab, &vis_tab_cap, 4 * kRangeFan * 128)) return false;
-    if (vis_tab) { vis_words = 0; vis_bytes_per_job = 16; }
+    VisitedScratch vis; // 32 768 hash slots: 24 576 visited ids before a hand-back; a step inserts up to kRangeFan lists of 128 ids
+    if (!visited_scratch(512, 4 * kRangeFan * 128, true, &vis)) return false;
     const long long chunk = std::min<long long>(njobs, 1 << 20);
-    if (!ensure_search_scratch(chunk, max_slots(), 0, vis_bytes_per_job)) return false; // also the per-wave result lists (s_spill_)
+    if (!ensure_search_scratch(chunk, max_slots(), 0, vis.bytes_per_job)) return false; // also the per-wave result lists (s_spill_)
     if ((size_t)chunk > s_roff_cap_) {
         if (s_roff_) HIP_OK(hipFree(s_roff_));
         if (s_rentry_) HIP_OK(hipFree(s_rentry_));
@@ -2021,22 +2002,14 @@ bool Device::range_batch(const SearchJob *jobs, int njobs, float range, RangeRes
         HIP_OK(hipMemsetAsync(s_arena_used_, 0, sizeof(unsigned long long), st));
         const bool timed = profiling_;
         if (timed) HIP_OK(hipEventRecord((hipEvent_t)ev0_, st));
-#define LAUNCH_RANGE2(M, H_)                                                                                                          \
-    do {                                                                                                                               \
-        const int slots_ = std::min(std::min(max_slots(), grid_cap), resident_blocks(graph_range_kernel<M, H_>, lds, num_cu_));        \
-        hipLaunchKernelGGL((graph_range_kernel<M, H_>), dim3(std::min<int>(nj, slots_)), dim3(64), lds, st, d_rows_, d_row_sn_,        \
-                           d_queries_, d_q_sn_, pitch_, g_adj0_, g_stride0_, g_upper_, g_pool_, g_strideU_, s_jobs_, range,            \
-                           lists, list_cap, s_visited_, vis_words, vis_tab, vis_tab_cap,                                               \
-                           reinterpret_cast<ND *>(s_arena_), (unsigned long long)arena_cap, s_arena_used_, s_roff_, s_cnt_, s_flag_,   \
-                           s_rentry_, s_evals_, nbcap_r, nj, s_jobctr_);                                                               \
-    } while (0)
-#define LAUNCH_RANGE(M) do { if (vis_tab) LAUNCH_RANGE2(M, true); else LAUNCH_RANGE2(M, false); } while (0)
-        if (metric_ == M_SQ) LAUNCH_RANGE(M_SQ);
-        else if (metric_ == M_COS) LAUNCH_RANGE(M_COS);
-        else if (metric_ == M_I8) LAUNCH_RANGE(M_I8);
-        else LAUNCH_RANGE(M_UCOS);
-#undef LAUNCH_RANGE
-#undef LAUNCH_RANGE2
+        with_metric(metric_, [&](auto m) {
+            const auto kernel = vis.tab ? &graph_range_kernel<m, true> : &graph_range_kernel<m, false>;
+            const int slots = std::min(std::min(max_slots(), grid_cap), resident_blocks(kernel, lds, num_cu_));
+            hipLaunchKernelGGL(kernel, dim3(std::min<int>(nj, slots)), dim3(64), lds, st, d_rows_, d_row_sn_, d_queries_, d_q_sn_, pitch_, g_adj0_,
+                               g_stride0_, g_upper_, g_pool_, g_strideU_, s_jobs_, range, lists, list_cap, s_visited_, vis.words, vis.tab, vis.tab_cap,
+                               reinterpret_cast<ND *>(s_arena_), (unsigned long long)arena_cap, s_arena_used_, s_roff_, s_cnt_, s_flag_, s_rentry_, s_evals_,
+                               nbcap_r, nj, s_jobctr_);
+        });
         HIP_OK(hipGetLastError());
         // the ORDER, still on the device (dk_range_finish.h): every finished list ranked ascending in place; the lists that hold equal
         // distances replayed -- the reference's two heaps on the distances just found -- and ranked in heap-array order.  What these
@@ -2095,22 +2068,7 @@ bool Device::range_batch(const SearchJob *jobs, int njobs, float range, RangeRes
             res->found_n = base + (size_t)span;
         }
         res->found = h_range_;
-        if (vis_tab) stats_.visited_hash_launches++;
-        stats_.search_launches++;
-        stats_.search_evals += ev;
-        stats_.range_launches++;
-        stats_.range_evals += ev;
-        if (timed) {
-            float ms = 0.f;
-            HIP_OK(hipEventElapsedTime(&ms, (hipEvent_t)ev0_, (hipEvent_t)ev1_));
-            stats_.search_kernel_ms += ms;
-            stats_.search_timed_launches++;
-            stats_.search_timed_evals += ev;
-            stats_.range_kernel_ms += ms;
-            stats_.range_timed_launches++;
-            stats_.range_timed_evals += ev;
-        }
-        return true;
+        return count_launch(&kRangeFamily, ev, vis.tab != nullptr, timed, ev0_, ev1_);
     };
     // `todo` through `launch`, with one more pass for the jobs that found the arena full
     auto run = [&](std::vector<int> todo, ND *lists, int list_cap, int grid_cap, size_t arena_cap, std::vector<int> &handed) -> bool {
@@ -2136,7 +2094,7 @@ bool Device::range_batch(const SearchJob *jobs, int njobs, float range, RangeRes
     if (!run(std::move(all), reinterpret_cast<ND *>(s_spill_), kSpillCap, max_slots(), std::min(std::max<size_t>((size_t)1 << 20, guess), kArenaMax), handed)) return false;
     // result sets beyond a wave's list: again, with lists as long as the graph (at most 1 GB of them at a time);
     // a visited table filling up (graphs above 4M nodes) is not helped by that and stays handed back
-    if (!handed.empty() && !vis_tab && g_n_ > kSpillCap) {
+    if (!handed.empty() && !vis.tab && g_n_ > kSpillCap) {
         const size_t list_cap = (size_t)std::min<long long>(g_n_, 1 << 24);
         const int waves = (int)std::max<size_t>(1, std::min<size_t>(handed.size(), ((size_t)1 << 27) / list_cap));
         if (!grow_dev(&s_rlists_, &s_rlists_cap_, list_cap * (size_t)waves)) return false;
@@ -2338,12 +2296,9 @@ bool Device::dist_pair_batch(const int *a, const int *b, int n, float *out)
     float *dout = reinterpret_cast<float *>(pair_dev_ + 2 * (size_t)n);
     HIP_OK(hipMemcpyAsync(da, hs, sizeof(int) * 2 * (size_t)n, hipMemcpyHostToDevice, st));
     dim3 grid((unsigned)(((long long)n * 8 + 255) / 256)), block(256);
-#define LAUNCH(M) hipLaunchKernelGGL(pair_distance_kernel<M>, grid, block, 0, st, d_rows_, d_row_sn_, pitch_, da, db, dout, n, n_rows_hw_, d_guard_)
-    if (metric_ == M_SQ) LAUNCH(M_SQ);
-    else if (metric_ == M_COS) LAUNCH(M_COS);
-    else if (metric_ == M_I8) LAUNCH(M_I8);
-    else LAUNCH(M_UCOS);
-#undef LAUNCH
+    with_metric(metric_, [&](auto m) {
+        hipLaunchKernelGGL(pair_distance_kernel<m>, grid, block, 0, st, d_rows_, d_row_sn_, pitch_, da, db, dout, n, n_rows_hw_, d_guard_);
+    });
     HIP_OK(hipGetLastError());
     HIP_OK(hipMemcpyAsync(hs + 2 * (size_t)n, dout, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, st));
     HIP_OK(hipMemcpyAsync(hs + 3 * (size_t)n, d_guard_, sizeof(int), hipMemcpyDeviceToHost, st));
