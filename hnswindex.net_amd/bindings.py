@@ -98,6 +98,9 @@ lib.hnsw_mi355x_set_queries.restype = ct.c_int
 lib.hnsw_mi355x_set_queries.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_int]
 lib.hnsw_mi355x_knn_query_resident.restype = ct.c_int
 lib.hnsw_mi355x_knn_query_resident.argtypes = [ct.c_void_p, ct.c_int, _I, _F]
+_U32 = ct.POINTER(ct.c_uint32)
+lib.hnsw_mi355x_knn_query_filtered.restype = ct.c_int
+lib.hnsw_mi355x_knn_query_filtered.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_int, ct.c_int, _U32, ct.c_longlong, _I, _F]
 lib.hnsw_mi355x_active_ids.restype = ct.c_int
 lib.hnsw_mi355x_active_ids.argtypes = [ct.c_void_p, _I, ct.c_int]
 lib.hnsw_mi355x_node_max_layer.restype = ct.c_int
@@ -151,6 +154,8 @@ lib.hnswdev_graph_begin.argtypes = [ct.c_void_p, ct.c_int, ct.c_int, _I]
 lib.hnswdev_graph_set_layer.argtypes = [ct.c_void_p, ct.c_int, _I, _I, ct.c_int]
 lib.hnswdev_graph_commit.argtypes = [ct.c_void_p]
 lib.hnswdev_knn_search.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_int, ct.c_int, ct.c_int, _I, _F, _I]
+lib.hnswdev_knn_search_filtered.restype = ct.c_int
+lib.hnswdev_knn_search_filtered.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_int, ct.c_int, ct.c_int, _U32, ct.c_longlong, _I, _F, _I]
 lib.hnswdev_range_search.restype = ct.c_int
 lib.hnswdev_range_search.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_int, ct.c_float, _I, _I]
 lib.hnswdev_range_results.restype = ct.c_int
@@ -222,6 +227,35 @@ def _dev_error() -> str:
     buf = ct.create_string_buffer(1024)
     lib.hnswdev_last_error(buf, len(buf))
     return buf.value.decode("utf-8", "replace")
+
+
+def allow_bits(allowed) -> Tuple[npt.NDArray[np.uint32], int]:
+    """An allow-set in the C ABI's form (hnsw_mi355x_knn_query_filtered): (words, nbits), bit i = bit (i & 31) of word (i >> 5),
+    ids >= nbits not allowed.  `allowed` is a bool mask indexed by id (ids past its end are not allowed) or an integer array of
+    allowed ids (negative ids are an error)."""
+    a = np.asarray(allowed)
+    if a.dtype == np.bool_:
+        mask = a.ravel()
+    elif a.size == 0 or np.issubdtype(a.dtype, np.integer):
+        ids = a.astype(np.int64).ravel()
+        if ids.size and ids.min() < 0:
+            raise ValueError("allowed ids must be >= 0")
+        mask = np.zeros(int(ids.max()) + 1 if ids.size else 0, dtype=np.bool_)
+        mask[ids] = True
+    else:
+        raise TypeError("allowed must be a bool mask indexed by id or an integer array of ids")
+    nbits = int(mask.size)
+    padded = np.zeros((nbits + 31) // 32 * 32, dtype=np.bool_)
+    padded[:nbits] = mask
+    words = np.packbits(padded.reshape(-1, 32), axis=1, bitorder="little").view("<u4").ravel().astype(np.uint32)
+    return np.ascontiguousarray(words), nbits
+
+
+def _words_arg(words):
+    """A pointer the C ABI accepts even for an empty set (NULL is an error there)."""
+    if words.size == 0:
+        words = np.zeros(1, dtype=np.uint32)
+    return words, words.ctypes.data_as(ct.POINTER(ct.c_uint32))
 
 
 def _as_2d_f32(x: npt.ArrayLike, dim_expected=None):
@@ -368,12 +402,21 @@ class Index:
         if result < 0:
             raise RuntimeError(last_error())
 
-    def knn_query(self, queries: npt.ArrayLike, k: int) -> Tuple[npt.NDArray[np.int32], npt.NDArray[np.float32]]:
-        """bindings.py:474-521."""
+    def knn_query(self, queries: npt.ArrayLike, k: int, allowed=None) -> Tuple[npt.NDArray[np.int32], npt.NDArray[np.float32]]:
+        """bindings.py:474-521.  allowed (not in the reference's Python class; its C# KnnQuery takes a filterFnc): a bool mask
+        indexed by id or an integer array of allowed ids -- only those ids are results (hnsw_mi355x_knn_query_filtered)."""
         q = _as_2d_f32(queries, self.dim)
         n = int(q.shape[0])
         ids = np.empty((n, k), dtype=np.int32)
         dists = np.empty((n, k), dtype=np.float32)
+        if allowed is not None:
+            words, nbits = allow_bits(allowed)
+            words, wp = _words_arg(words)
+            status = lib.hnsw_mi355x_knn_query_filtered(self._h, q.ctypes.data_as(_F), n, self.dim, k, wp, nbits, ids.ctypes.data_as(_I),
+                                                        dists.ctypes.data_as(_F))
+            if status < 0:
+                raise RuntimeError(last_error())
+            return ids, dists
         status = lib.hnsw_knn_query(self._h, q.ctypes.data_as(_F), n, self.dim, k, ids.ctypes.data_as(_I),
                                     dists.ctypes.data_as(_F))
         if status < 0:
@@ -610,12 +653,19 @@ class DeviceBackend:
             self._check(lib.hnswdev_graph_set_layer(self._ctx, layer, c.ctypes.data_as(_I), e.ctypes.data_as(_I), e.shape[1]))
         self._check(lib.hnswdev_graph_commit(self._ctx))
 
-    def knn_search(self, queries, entry_point: int, k_beam: int, k_out: int):
+    def knn_search(self, queries, entry_point: int, k_beam: int, k_out: int, allowed=None):
+        """allowed: as for Index.knn_query (hnswdev_knn_search_filtered); None runs hnswdev_knn_search."""
         q = _as_2d_f32(queries, self.dim)
         n = q.shape[0]
         ids = np.empty((n, k_out), dtype=np.int32)
         d = np.empty((n, k_out), dtype=np.float32)
         flags = np.empty(n, dtype=np.int32)
+        if allowed is not None:
+            words, nbits = allow_bits(allowed)
+            words, wp = _words_arg(words)
+            self._check(lib.hnswdev_knn_search_filtered(self._ctx, q.ctypes.data_as(_F), n, int(entry_point), int(k_beam), int(k_out), wp, nbits,
+                                                        ids.ctypes.data_as(_I), d.ctypes.data_as(_F), flags.ctypes.data_as(_I)))
+            return ids, d, flags
         self._check(lib.hnswdev_knn_search(self._ctx, q.ctypes.data_as(_F), n, int(entry_point), int(k_beam), int(k_out),
                                            ids.ctypes.data_as(_I), d.ctypes.data_as(_F), flags.ctypes.data_as(_I)))
         return ids, d, flags

@@ -146,6 +146,11 @@ public:
     // search_batch for KnnQuery's own jobs -- resident query i from the entry point, i = 0 .. nq-1: the job array is written
     // on this side and stays on the device while entry point and top layer do not change (a call then uploads no jobs)
     bool search_queries(int nq, int entry, int entry_layer, int k, int k_out, int *out_ids, float *out_d, int *out_flag);
+    // search_queries with an allow-set (KnnQuery's filterFnc at layer 0, graph_search_filtered_kernel): a bitset of nbits bits over
+    // ids, bit i = bit i & 31 of word i >> 5, ids >= nbits not allowed.  The descent is not filtered; a disallowed node is a
+    // candidate but never a result.  The bitset is uploaded to this context for the call.  out_flag as search_batch (1: handed back).
+    bool search_filtered(int nq, int entry, int entry_layer, int k, int k_out, const uint32_t *allow_bits, long long nbits, int *out_ids,
+                         float *out_d, int *out_flag);
     // Remove, second half, for the `n` affected nodes of one (removed node, layer) step (graph_relink_kernel): per node
     // the new neighbour selection out_sel[i * sel_stride ..][0 .. out_cnt[i]); out_flag[i] = 1: this node's answer
     // depends on the heap-array order of the candidates (the caller repeats the step on the lock-step path).
@@ -234,6 +239,8 @@ public:
     bool graph_set_layer(int layer, const int *counts, const int *edges, int stride);
     bool graph_commit();
     bool knn_search(const float *queries, int nq, int entry_point, int k_beam, int k_out, int *out_ids, float *out_d, int *out_flag);
+    bool knn_search_filtered(const float *queries, int nq, int entry_point, int k_beam, int k_out, const uint32_t *allow_bits, long long nbits,
+                             int *out_ids, float *out_d, int *out_flag);
     // RangeQuery on the device (graph_range_kernel): per job the results within `range`, UNSORTED, at
     // found[off[i] .. off[i] + cnt[i]); flag[i] = 1: handed back (cnt 0).  jobs[].qref must name a resident query.
     struct RangeResults {
@@ -300,8 +307,11 @@ private:
     int *s_vistab_ = nullptr; // per-wave visited-id hash tables
     size_t s_vistab_cap_ = 0;
     int s_vistab_each_ = 0;
-    bool visited_scratch(int k, int min_cap, bool allow_hash, VisitedScratch *out);
-    bool plan_traversal(bool insert, int k, bool two_heap, size_t lds, TraversalLaunch *out);
+    int *s_fvistab_ = nullptr; // ... and those of the filtered search launches
+    size_t s_fvistab_cap_ = 0;
+    int s_fvistab_each_ = 0;
+    bool visited_scratch(int k, int min_cap, bool allow_hash, VisitedScratch *out, bool filtered = false);
+    bool plan_traversal(bool insert, int k, bool two_heap, size_t lds, TraversalLaunch *out, bool filtered = false);
     bool count_launch(const LaunchFamily *family, unsigned long long evals, bool hashed, bool timed, void *t0, void *t1);
     int num_cu_ = 256;
     // Persistent launches never use more than 16 one-wave blocks per CU (the traversal kernels need
@@ -336,6 +346,10 @@ private:
     size_t s_win_cap_ = 0;
     SearchHit *s_spill_ = nullptr;
     size_t s_spill_cap_ = 0;
+    SearchHit *s_fspill_ = nullptr; // filtered searches: their own, larger spill areas (allocated by the first such call)
+    size_t s_fspill_cap_ = 0;
+    unsigned *s_allow_ = nullptr;   // filtered searches: the call's allow-set
+    size_t s_allow_cap_ = 0;
     SearchHit *s_arena_ = nullptr; // range search: the launch's results, packed
     size_t s_arena_cap_ = 0;
     unsigned long long *s_roff_ = nullptr, *s_arena_used_ = nullptr;

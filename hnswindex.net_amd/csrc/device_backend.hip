@@ -39,6 +39,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <map>
 #include <mutex>
 #include <type_traits>
@@ -170,6 +171,10 @@ HNSW_FOR_EACH_TRAVERSAL_LEAN(HNSW_DEFINE_SEARCH, M_SQ)
 HNSW_FOR_EACH_TRAVERSAL_LEAN(HNSW_DEFINE_SEARCH, M_COS)
 HNSW_FOR_EACH_TRAVERSAL_LEAN(HNSW_DEFINE_SEARCH, M_UCOS)
 HNSW_FOR_EACH_TRAVERSAL_LEAN(HNSW_DEFINE_SEARCH, M_I8)
+HNSW_FOR_EACH_FILTERED(HNSW_DEFINE_FILTERED, M_SQ)
+HNSW_FOR_EACH_FILTERED(HNSW_DEFINE_FILTERED, M_COS)
+HNSW_FOR_EACH_FILTERED(HNSW_DEFINE_FILTERED, M_UCOS)
+HNSW_FOR_EACH_FILTERED(HNSW_DEFINE_FILTERED, M_I8)
 #else
 HNSW_FOR_EACH_TRAVERSAL(HNSW_DECLARE_TRAVERSAL, M_SQ)
 HNSW_FOR_EACH_TRAVERSAL(HNSW_DECLARE_TRAVERSAL, M_COS)
@@ -183,6 +188,10 @@ HNSW_FOR_EACH_TRAVERSAL_LEAN(HNSW_DECLARE_SEARCH, M_SQ)
 HNSW_FOR_EACH_TRAVERSAL_LEAN(HNSW_DECLARE_SEARCH, M_COS)
 HNSW_FOR_EACH_TRAVERSAL_LEAN(HNSW_DECLARE_SEARCH, M_UCOS)
 HNSW_FOR_EACH_TRAVERSAL_LEAN(HNSW_DECLARE_SEARCH, M_I8)
+HNSW_FOR_EACH_FILTERED(HNSW_DECLARE_FILTERED, M_SQ)
+HNSW_FOR_EACH_FILTERED(HNSW_DECLARE_FILTERED, M_COS)
+HNSW_FOR_EACH_FILTERED(HNSW_DECLARE_FILTERED, M_UCOS)
+HNSW_FOR_EACH_FILTERED(HNSW_DECLARE_FILTERED, M_I8)
 #endif
 
 // ------------------------------------------------------------------------------------
@@ -340,7 +349,7 @@ Device::~Device()
     phase_report("teardown");
 #endif
     for (void *p : {(void *)g_adj0_, (void *)g_level_, (void *)g_upper_, (void *)g_pool_, (void *)g_tested0_, (void *)g_testedU_, (void *)s_visited_, (void *)s_jobs_,
-                    (void *)s_hits_, (void *)s_cnt_, (void *)s_flag_, (void *)s_jobctr_, (void *)s_vistab_, (void *)lp_slot_[0], (void *)lp_slot_[1], (void *)lp_slot_[2], (void *)lp_grp_[0], (void *)lp_grp_[1], (void *)lp_grp_[2], (void *)lp_grp_[3], (void *)lp_grp_[4], (void *)lp_grp_[5], (void *)lp_counters_, (void *)s_evals_, (void *)s_sel_, (void *)s_lcnt_, (void *)s_selU_, (void *)s_cntU_, (void *)s_iflag_, (void *)s_lk_[0], (void *)s_lk_[1], (void *)s_lk_[2], (void *)s_lk_[3], (void *)s_lk_[4], (void *)s_spill_, (void *)s_order_, (void *)s_rlog_, (void *)s_dry_, (void *)s_wdry_, (void *)s_win_, (void *)s_arena_, (void *)s_roff_, (void *)s_arena_used_, (void *)s_rentry_, (void *)s_rlists_, (void *)s_rl_, (void *)s_rstate_, (void *)s_rtied_, (void *)s_rfin_ctr_})
+                    (void *)s_hits_, (void *)s_cnt_, (void *)s_flag_, (void *)s_jobctr_, (void *)s_vistab_, (void *)s_fvistab_, (void *)lp_slot_[0], (void *)lp_slot_[1], (void *)lp_slot_[2], (void *)lp_grp_[0], (void *)lp_grp_[1], (void *)lp_grp_[2], (void *)lp_grp_[3], (void *)lp_grp_[4], (void *)lp_grp_[5], (void *)lp_counters_, (void *)s_evals_, (void *)s_sel_, (void *)s_lcnt_, (void *)s_selU_, (void *)s_cntU_, (void *)s_iflag_, (void *)s_lk_[0], (void *)s_lk_[1], (void *)s_lk_[2], (void *)s_lk_[3], (void *)s_lk_[4], (void *)s_spill_, (void *)s_fspill_, (void *)s_allow_, (void *)s_order_, (void *)s_rlog_, (void *)s_dry_, (void *)s_wdry_, (void *)s_win_, (void *)s_arena_, (void *)s_roff_, (void *)s_arena_used_, (void *)s_rentry_, (void *)s_rlists_, (void *)s_rl_, (void *)s_rstate_, (void *)s_rtied_, (void *)s_rfin_ctr_})
         if (p) (void)hipFree(p);
     if (ev0_) (void)hipEventDestroy((hipEvent_t)ev0_);
     if (ev1_) (void)hipEventDestroy((hipEvent_t)ev1_);
@@ -1033,6 +1042,24 @@ static int spill_cap_for_tests()
     const int c = diag("spill_cap", -1);
     return c < 0 ? kSpillCap : std::min(kSpillCap, c);
 }
+// Filtered searches (graph_search_filtered_kernel): a candidate heap of cand_lds_cap() entries in LDS, as the unfiltered launches
+// have, plus kFilterSpillCap in HBM per resident wave -- 256 KB each, 0.75 GB for the 3 072 waves of the float kernels (164 VGPRs,
+// three per SIMD), 1.25 GB for the 5 120 of int8 (82 VGPRs) -- allocated by the first filtered call.  A selective filter keeps the
+// result heap short of k for about k / selectivity evaluations, and every fresh neighbour is pushed meanwhile: at 1 % and a beam
+// of 128 the heap was estimated to peak near 12 000 entries.  More LDS per wave would cost resident waves (the float kernel's
+// LDS at C2 is 5.6 KB against VGPRs that allow three waves per SIMD, so LDS is not what limits it).  A job that outgrows the
+// heap is handed back.  Diag spill_cap forces a smaller area (tests).
+constexpr int kFilterSpillCap = 32768;
+static int filter_spill_cap()
+{
+    const int c = diag("spill_cap", -1);
+    return c < 0 ? kFilterSpillCap : std::min(kFilterSpillCap, c);
+}
+// ... and their visited tables (graphs whose sets are hash tables, above ~4M nodes): at least this many entries per wave (512 KB;
+// 2.5 GB for the 5 120 waves the per-wave scratch is sized for), a table of their own (visited_scratch), crowded -- the job handed
+// back -- beyond 98 304 visited ids.
+// Each job clears its whole table, as every hashed launch does.  None of this is measured.
+constexpr int kFilterVisCap = 1 << 17;
 
 
 // Row loads overlapped with the visited atomics in launches that do not fill the chip, and in every launch on a
@@ -1089,7 +1116,9 @@ struct VisitedScratch {
 // The per-wave visited-id hash tables (VisitedSet): capacity a power of two, >= 16384 and >= 64 per
 // beam entry (a traversal visits roughly 35 ids per beam entry), all entries -1 between jobs.
 // Diag vis_hash=1/0 forces / forbids them; vis_hash_cap overrides the capacity (tests).
-bool Device::visited_scratch(int k, int min_cap, bool allow_hash, VisitedScratch *v)
+// filtered: the tables of the filtered search launches (far larger: kFilterVisCap), kept apart so that calls alternating between
+// filtered and unfiltered searches never reallocate either.
+bool Device::visited_scratch(int k, int min_cap, bool allow_hash, VisitedScratch *v, bool filtered)
 {
     *v = VisitedScratch{};
     v->words = ((g_n_ + 31) / 32 + 3) & ~3LL;
@@ -1106,16 +1135,19 @@ bool Device::visited_scratch(int k, int min_cap, bool allow_hash, VisitedScratch
     // a traversal step inserts up to min_cap / 4 ids between two looks at crowded() (limit: 3/4 of the table)
     while (cap < min_cap) cap <<= 1;
     const size_t need = (size_t)max_slots() * (size_t)cap;
-    if (need > s_vistab_cap_ || cap != s_vistab_each_) {
+    int *&tab = filtered ? s_fvistab_ : s_vistab_;
+    size_t &tab_cap = filtered ? s_fvistab_cap_ : s_vistab_cap_;
+    int &tab_each = filtered ? s_fvistab_each_ : s_vistab_each_;
+    if (need > tab_cap || cap != tab_each) {
         HIP_OK(hipStreamSynchronize(S(stream_)));
-        if (s_vistab_) HIP_OK(hipFree(s_vistab_));
-        s_vistab_ = nullptr; s_vistab_cap_ = 0;
-        HIP_OK(hipMalloc(&s_vistab_, sizeof(int) * need));
-        HIP_OK(hipMemsetAsync(s_vistab_, 0xff, sizeof(int) * need, S(stream_)));
-        s_vistab_cap_ = need;
-        s_vistab_each_ = cap;
+        if (tab) HIP_OK(hipFree(tab));
+        tab = nullptr; tab_cap = 0;
+        HIP_OK(hipMalloc(&tab, sizeof(int) * need));
+        HIP_OK(hipMemsetAsync(tab, 0xff, sizeof(int) * need, S(stream_)));
+        tab_cap = need;
+        tab_each = cap;
     }
-    v->tab = s_vistab_;
+    v->tab = tab;
     v->tab_cap = cap;
     v->words = 0;          // the hashed kernels never touch the bitset arena: do not allocate one
     v->bytes_per_job = 16;
@@ -1133,6 +1165,7 @@ struct TraversalLaunch {
     VisitedScratch vis;
     bool novis;          // no visited set at all: flags 9 (bit 3 with the overlap bit)
     bool lat_ok;         // the latency form may run: sorted top, lists of at most 64 ids, room for its mailbox
+    bool filtered;       // graph_search_filtered_kernel (an allow-set): exact traversal, visited sets kept, no latency form
     // per launch
     int form;            // kFormLat, kFormLean, kFormPlain
     int slots, grid;     // the form's resident waves; grid = min(jobs, slots)
@@ -1141,16 +1174,22 @@ struct TraversalLaunch {
     int flags;           // 0x200 (exact only) | 9 (novis) or 1 (overlap); the launch site adds 0x100 (shadow, search) / 2 (mfma, insert)
 };
 
-bool Device::plan_traversal(bool insert, int k, bool two_heap, size_t lds, TraversalLaunch *t)
+bool Device::plan_traversal(bool insert, int k, bool two_heap, size_t lds, TraversalLaunch *t, bool filtered)
 {
-    const int ns = g_n_ < kSortedTopMaxNodes && !two_heap ? sorted_top_sets(k) : 0;
+    const int ns = g_n_ < kSortedTopMaxNodes && !two_heap && !filtered ? sorted_top_sets(k) : 0;
     t->metric = metric_;
     t->max_slots = max_slots();
     t->num_cu = num_cu_;
     t->lds = lds;
-    t->exact_only = ns == 0; // two_heap callers, beams beyond 512 entries, diag sorted_top=0
+    t->filtered = filtered;
+    t->exact_only = ns == 0; // two_heap callers, beams beyond 512 entries, diag sorted_top=0, filtered searches
     t->ns = t->exact_only ? 2 : ns;
-    if (!visited_scratch(k, 512, t->ns != 8, &t->vis)) return false;
+    if (!visited_scratch(k, filtered ? kFilterVisCap : 512, t->ns != 8, &t->vis, filtered)) return false;
+    if (filtered) { // the visited set stays (a disallowed node that was expanded and left the heap would be pushed again: DESIGN.md 3.9)
+        t->novis = false;
+        t->lat_ok = false;
+        return true;
+    }
     // (rows of more than 1 KB keep the sets: their traffic is small beside the rows', and the rows of re-seen neighbours are what
     //  costs -- C3's 3-KB rows: 282.7 k queries/s with the sets against 273.6 k without, build 69.5 k against 61.3 k adds/s.
     //  Add's searches run without a set as well; diag novis_insert=0 keeps the sets there)
@@ -1186,6 +1225,27 @@ static auto traversal_kernel(const TraversalLaunch &t, int form)
         else if (t.ns == 4) kernel = hashed ? traversal_form<Insert, m, 4, true>(form) : traversal_form<Insert, m, 4, false>(form);
         else kernel = traversal_form<Insert, m, 8, false>(form);
     });
+    return kernel;
+}
+
+// The filtered search kernel of (metric, hashed): one form, its own parameter list (graph_search_kernel's stays as it is).
+static auto filtered_kernel(const TraversalLaunch &t)
+{
+    const bool hashed = t.vis.tab != nullptr;
+    decltype(&graph_search_filtered_kernel<M_SQ, false>) kernel = nullptr;
+    with_metric(t.metric, [&](auto m) { kernel = hashed ? &graph_search_filtered_kernel<m, true> : &graph_search_filtered_kernel<m, false>; });
+    return kernel;
+}
+// A filtered launch of nj jobs: the plain persistent form on what stays resident, no flags.
+static auto place_filtered(TraversalLaunch &t, int nj)
+{
+    const auto kernel = filtered_kernel(t);
+    t.form = kFormPlain;
+    t.slots = std::min(t.max_slots, resident_blocks(kernel, t.lds, t.num_cu));
+    t.grid = std::min(nj, t.slots);
+    t.block = 64;
+    t.lds_total = t.lds;
+    t.flags = 0;
     return kernel;
 }
 
@@ -1833,6 +1893,84 @@ bool Device::search_batch_impl(const SearchJob *jobs, int njobs, int k, int k_ou
     return true;
 }
 
+// KnnQuery with an allow-set (graph_search_filtered_kernel): resident query i from (entry, entry_layer), i < nq.  Only the words that
+// cover graph ids travel: bits of ids >= min(nbits, graph nodes) are never read.  A set that allows no graph id pads every
+// row without a launch (the result is empty whatever the order).
+bool Device::search_filtered(int nq, int entry, int entry_layer, int k, int k_out, const uint32_t *allow_bits, long long nbits, int *out_ids,
+                             float *out_d, int *out_flag)
+{
+    if (nq <= 0) return true;
+    if (!out_ids || !out_d || !out_flag || k < 1 || k_out < 1 || nbits < 0 || (!allow_bits && nbits > 0)) { set_dev_error("search_filtered: bad argument"); return false; }
+    if (g_n_ <= 0) { set_dev_error("search_filtered: no graph uploaded"); return false; }
+    if (!(entry >= 0 && entry < g_n_ && entry_layer >= 0 && nq <= n_queries_) || tail_.n > 0) {
+        set_dev_error("search_filtered: entry point outside the graph, or fewer resident queries than asked for");
+        return false;
+    }
+    const long long n_allow = std::min<long long>(nbits, g_n_);
+    const size_t words = (size_t)((n_allow + 31) / 32);
+    bool any = false;
+    for (size_t w = 0; w < words && !any; ++w) {
+        const uint32_t v = allow_bits[w];
+        any = (w + 1 < words || (n_allow & 31) == 0) ? v != 0u : (v & ((1u << (n_allow & 31)) - 1u)) != 0u;
+    }
+    if (!any) {
+        for (size_t j = 0; j < (size_t)nq * (size_t)k_out; ++j) { out_ids[j] = -1; out_d[j] = std::numeric_limits<float>::quiet_NaN(); }
+        for (int i = 0; i < nq; ++i) out_flag[i] = 0;
+        return true;
+    }
+    const int cand_cap = cand_lds_cap(k, pitch_, false, nbcap());
+    const size_t lds = search_lds_bytes(k, cand_cap, pitch_, false, nbcap());
+    if (lds > 64 * 1024) { set_dev_error("search_filtered: beam width / dimension exceed the LDS budget"); return false; }
+    if (!bind()) return false;
+    hipStream_t st = S(stream_);
+    const long long chunk = std::min<long long>(nq, 1 << 20);
+    TraversalLaunch tl;
+    if (!plan_traversal(false, k, true, lds, &tl, true)) return false;
+    const auto kernel = place_filtered(tl, (int)chunk);
+    const int fspill = filter_spill_cap();
+    if (!ensure_search_scratch(chunk, max_slots(), k_out, tl.vis.bytes_per_job)) return false;
+    if (!grow_dev(&s_fspill_, &s_fspill_cap_, (size_t)tl.slots * (size_t)std::max(fspill, 1) + 8)) return false; // +8: get2 may read one entry past a heap
+    if (!grow_dev(&s_allow_, &s_allow_cap_, std::max<size_t>(words, 1))) return false;
+    // pinned layout: [evals (16 B) | ids | dists | flags | allow words]
+    const size_t b_res = 4u * (size_t)chunk * k_out;
+    char *hs = static_cast<char *>(pinned_stage(16 + 2 * b_res + 4u * (size_t)chunk + 4u * words));
+    if (!hs) return false;
+    unsigned long long *h_ev = reinterpret_cast<unsigned long long *>(hs);
+    int *h_ids = reinterpret_cast<int *>(hs + 16);
+    float *h_d = reinterpret_cast<float *>(hs + 16 + b_res);
+    int *h_flag = reinterpret_cast<int *>(hs + 16 + 2 * b_res);
+    uint32_t *h_allow = reinterpret_cast<uint32_t *>(hs + 16 + 2 * b_res + 4u * (size_t)chunk);
+    memcpy(h_allow, allow_bits, 4u * words);
+    HIP_OK(hipMemcpyAsync(s_allow_, h_allow, 4u * words, hipMemcpyHostToDevice, st));
+    int *d_ids = reinterpret_cast<int *>(s_hits_);
+    float *d_d = reinterpret_cast<float *>(s_hits_) + (size_t)chunk * k_out;
+    for (long long off = 0; off < nq; off += chunk) {
+        const int nj = (int)std::min<long long>(chunk, nq - off);
+        HIP_OK(hipMemsetAsync(s_jobctr_, 0, sizeof(int) * 4, st));
+        HIP_OK(hipMemsetAsync(s_evals_, 0, sizeof(unsigned long long), st));
+        const bool timed = profiling_;
+        if (timed) HIP_OK(hipEventRecord((hipEvent_t)ev0_, st));
+        tl.grid = std::min(nj, tl.slots);
+        hipLaunchKernelGGL(kernel, dim3(tl.grid), dim3(tl.block), tl.lds_total, st, d_rows_, d_row_sn_, d_queries_ + (size_t)off * pitch_,
+                           d_q_sn_ ? d_q_sn_ + off : nullptr, pitch_, g_adj0_, g_stride0_, g_upper_, g_pool_, g_strideU_, entry, entry_layer, k, cand_cap,
+                           reinterpret_cast<ND *>(s_fspill_), fspill, s_visited_, tl.vis.words, tl.vis.tab, tl.vis.tab_cap,
+                           reinterpret_cast<const unsigned *>(s_allow_), n_allow, k_out, d_ids, d_d, s_flag_, s_evals_, nbcap(), nj, s_jobctr_);
+        HIP_OK(hipGetLastError());
+        if (timed) HIP_OK(hipEventRecord((hipEvent_t)ev1_, st));
+        HIP_OK(hipMemcpyAsync(h_ids, d_ids, 4u * (size_t)nj * k_out, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(h_d, d_d, 4u * (size_t)nj * k_out, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(h_flag, s_flag_, sizeof(int) * (size_t)nj, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(h_ev, s_evals_, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+        memcpy(out_ids + (size_t)off * k_out, h_ids, 4u * (size_t)nj * k_out);
+        memcpy(out_d + (size_t)off * k_out, h_d, 4u * (size_t)nj * k_out);
+        memcpy(out_flag + off, h_flag, sizeof(int) * (size_t)nj);
+        if (!count_launch(nullptr, *h_ev, tl.vis.tab != nullptr, timed, ev0_, ev1_)) return false;
+    }
+    for (int i = 0; i < nq; ++i) stats_.search_overflows += (uint64_t)(out_flag[i] == 1);
+    return true;
+}
+
 bool Device::relink_batch(const int *affected, const int *layer, const int *removed, const int *step, int n, const int *cands, const int *cand_off,
                           const int *cand_cnt, int nsteps, int max_edges0, int *out_sel, int *out_cnt, int *out_flag, int sel_stride, bool heap_order)
 {
@@ -2217,6 +2355,17 @@ bool Device::knn_search(const float *queries, int nq, int entry_point, int k_bea
     return search_batch(jobs.data(), nq, k_beam, k_out, out_ids, out_d, out_flag);
 }
 
+bool Device::knn_search_filtered(const float *queries, int nq, int entry_point, int k_beam, int k_out, const uint32_t *allow_bits, long long nbits,
+                                 int *out_ids, float *out_d, int *out_flag)
+{
+    if (!allow_bits || nbits < 0) { set_dev_error("knn_search_filtered: allow_bits must not be NULL and nbits must be >= 0"); return false; }
+    if (nq <= 0) return true;
+    if (!hg_ || g_n_ <= 0) { set_dev_error("knn_search_filtered: no graph committed"); return false; }
+    if (entry_point < 0 || entry_point >= hg_->n || k_out < 1 || k_beam < k_out) { set_dev_error("knn_search_filtered: bad argument"); return false; }
+    if (!set_queries(queries, nq)) return false;
+    return search_filtered(nq, entry_point, hg_->level[(size_t)entry_point], k_beam, k_out, allow_bits, nbits, out_ids, out_d, out_flag);
+}
+
 // ---- synchronous conveniences behind the C ABI ---------------------------------------
 // Distance(int, TVector) for nq (query, candidate list) pairs.  Runs on the context's two step-
 // buffer sets, ping-pong: while the GPU measures one set the host packs the next and unpacks the
@@ -2393,6 +2542,12 @@ DEV_API int hnswdev_knn_search(void *ctx, const float *queries, int nq, int entr
 {
     CTX_OR_FAIL();
     return d->knn_search(queries, nq, entry_point, k_beam, k_out, out_ids, out_dists, out_flags) ? 0 : -1;
+}
+DEV_API int hnswdev_knn_search_filtered(void *ctx, const float *queries, int nq, int entry_point, int k_beam, int k_out, const uint32_t *allow_bits,
+                                        long long nbits, int *out_ids, float *out_dists, int *out_flags)
+{
+    CTX_OR_FAIL();
+    return d->knn_search_filtered(queries, nq, entry_point, k_beam, k_out, allow_bits, nbits, out_ids, out_dists, out_flags) ? 0 : -1;
 }
 DEV_API int hnswdev_range_search(void *ctx, const float *queries, int nq, int entry_point, float range, int *out_counts, int *out_flags)
 {

@@ -43,6 +43,15 @@ __device__ __forceinline__ SearchLds carve_lds(unsigned char *smem, int k, int c
     return L;
 }
 
+// An allow-set over ids (KnnQuery's filterFnc as a bitset): bit i of `bits` is bit i & 31 of word i >> 5; ids >= n are not
+// allowed.  No word past the set is ever read.
+struct AllowSet {
+    const unsigned *bits;
+    long long n;
+    __device__ __forceinline__ unsigned word(int id) const { return (long long)id < n ? bits[id >> 5] : 0u; }
+    __device__ __forceinline__ bool has(int id) const { return ((word(id) >> (id & 31)) & 1u) != 0u; }
+};
+
 struct GraphView {
     const int *adj0;
     int stride0;

@@ -1,4 +1,4 @@
-// dk_search_kernels.h -- device code, part of device_kernels.h: KnnQuery / RangeQuery: search_job, graph_search_kernel (persistent, shadows, gated upload), graph_range_kernel.
+// dk_search_kernels.h -- device code, part of device_kernels.h: KnnQuery / RangeQuery: search_job, graph_search_kernel (persistent, shadows, gated upload), graph_search_filtered_kernel (allow-sets), graph_range_kernel.
 #pragma once
 #include "dk_sorted_top.h"
 #include "dk_pool_top.h"
@@ -25,6 +25,46 @@ struct SearchKernArgs {
 static_assert(offsetof(SearchKernArgs, jobs) == 80 && offsetof(SearchKernArgs, out_ids) == 144 && offsetof(SearchKernArgs, ready) == 208 && sizeof(SearchKernArgs) == 216,
               "SearchKernArgs must mirror graph_search_kernel's parameter list (the explicit arguments start the kernarg segment, each at its natural alignment)");
 #define HNSW_KA(field) kernarg_load<decltype(SearchKernArgs::field)>((unsigned)offsetof(SearchKernArgs, field))
+
+// KnnQuery's tail (HNSWIndex.cs:119-123): OrderBy(c => c.Dist) is a STABLE sort over the heap
+// array (ToArray(), BinaryHeap.cs:41-44) and only the first k_out survive -- so select the
+// k_out smallest (float.CompareTo order: NaN first, -0 == +0) with ties broken by array index:
+// exactly the stable sort's prefix.  Key = (order-preserving bits << 32) | index, wave min.
+// L.top[0 .. top_n) holds float distances; writes row `job` of out_ids / out_d (k_out entries, padded).
+__device__ __forceinline__ void take_stable(const SearchLds &L, int lane, int top_n, int k_out, int *__restrict__ out_ids, float *__restrict__ out_d, int job)
+{
+    wave_sync();
+    unsigned long long used = 0; // bit t: entry lane + 64*t already emitted
+    for (int r = 0; r < k_out; ++r) {
+        unsigned long long best = ~0ull;
+        for (int t = 0, i = lane; i < top_n; ++t, i += 64) {
+            if ((used >> t) & 1ull) continue;
+            float d = L.top[i].dist;
+            unsigned u;
+            if (d != d) u = 0u;                      // NaN sorts first
+            else {
+                if (d == 0.0f) d = 0.0f;             // -0 and +0 compare equal
+                u = __float_as_uint(d);
+                u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+                if (u == 0u) u = 1u;                 // keep NaN's key unique (only -NaN-like bit patterns reach 0)
+            }
+            unsigned long long key = ((unsigned long long)u << 32) | (unsigned)i;
+            best = key < best ? key : best;
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            unsigned long long o = __shfl_xor(best, off, 64);
+            best = o < best ? o : best;
+        }
+        if (best == ~0ull) { // fewer than k_out results: pad (HNSWIndexExports.cs:144)
+            if (lane == 0) { out_ids[(size_t)job * k_out + r] = -1; out_d[(size_t)job * k_out + r] = __uint_as_float(0x7fc00000u); }
+            continue;
+        }
+        const int wi = (int)(best & 0xffffffffu);
+        if ((wi & 63) == lane) used |= 1ull << (wi >> 6);
+        if (lane == 0) { ND w = L.top[wi]; out_ids[(size_t)job * k_out + r] = w.id; out_d[(size_t)job * k_out + r] = w.dist; }
+    }
+}
 
 template <int METRIC, int NS, bool HASHED, int FORM = kFormPlain>
 __device__ __forceinline__ void search_job(const float *__restrict__ rows, const double *__restrict__ row_sn, const float *__restrict__ queries,
@@ -148,41 +188,7 @@ __device__ __forceinline__ void search_job(const float *__restrict__ rows, const
         }
         return;
     }
-    // KnnQuery's tail (HNSWIndex.cs:119-123): OrderBy(c => c.Dist) is a STABLE sort over the heap
-    // array (ToArray(), BinaryHeap.cs:41-44) and only the first k_out survive -- so select the
-    // k_out smallest (float.CompareTo order: NaN first, -0 == +0) with ties broken by array index:
-    // exactly the stable sort's prefix.  Key = (order-preserving bits << 32) | index, wave min.
-    wave_sync();
-    unsigned long long used = 0; // bit t: entry lane + 64*t already emitted
-    for (int r = 0; r < k_out; ++r) {
-        unsigned long long best = ~0ull;
-        for (int t = 0, i = lane; i < top_n; ++t, i += 64) {
-            if ((used >> t) & 1ull) continue;
-            float d = L.top[i].dist;
-            unsigned u;
-            if (d != d) u = 0u;                      // NaN sorts first
-            else {
-                if (d == 0.0f) d = 0.0f;             // -0 and +0 compare equal
-                u = __float_as_uint(d);
-                u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-                if (u == 0u) u = 1u;                 // keep NaN's key unique (only -NaN-like bit patterns reach 0)
-            }
-            unsigned long long key = ((unsigned long long)u << 32) | (unsigned)i;
-            best = key < best ? key : best;
-        }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            unsigned long long o = __shfl_xor(best, off, 64);
-            best = o < best ? o : best;
-        }
-        if (best == ~0ull) { // fewer than k_out results: pad (HNSWIndexExports.cs:144)
-            if (lane == 0) { out_ids[(size_t)job * k_out + r] = -1; out_d[(size_t)job * k_out + r] = __uint_as_float(0x7fc00000u); }
-            continue;
-        }
-        const int wi = (int)(best & 0xffffffffu);
-        if ((wi & 63) == lane) used |= 1ull << (wi >> 6);
-        if (lane == 0) { ND w = L.top[wi]; out_ids[(size_t)job * k_out + r] = w.id; out_d[(size_t)job * k_out + r] = w.dist; }
-    }
+    take_stable(L, lane, top_n, k_out, out_ids, out_d, job);
     if (lane == 0) {
         out_cnt[job] = ok ? top_n : 0;
         out_flag[job] = ok ? (repeated ? 2 : 0) : 1; // 2: informational (answered by the exact traversal)
@@ -321,6 +327,66 @@ graph_search_kernel(const float *__restrict__ rows, const double *__restrict__ r
 
     if constexpr (LAT) port.post(-1, 0, lane); // the memory wave leaves
 }
+
+// KnnQuery with an allow-set (HNSWIndex.KnnQuery(query, k, filterFnc), HNSWIndex.cs:107-124, at layer 0): FindEntryPointQuery
+// unfiltered, then SearchLayerQuery with the filter (GraphNavigator.cs:194-256) in the exact two-heap traversal -- the sorted-list
+// forms cannot carry it: a disallowed node is a candidate that is never a result, and the result list no longer holds the live
+// candidates -- and the stable Take(k_out).  Persistent like graph_range_kernel: one wave per job, jobs from a
+// counter; job i is resident query i from (entry, entry_layer).  Each wave owns one visited set and one spill area of spill_cap
+// entries (filtered traversals keep far more candidates: the result heap fills only after ~k / selectivity evaluations) and
+// leaves the set clean after every job.  out_flag: 0 done, 1 handed back (candidate heap full, NaN / -0 distance, visited table
+// crowded).
+template <int METRIC, bool HASHED>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(HNSW_WAVES(3))))
+graph_search_filtered_kernel(const float *__restrict__ rows, const double *__restrict__ row_sn, const float *__restrict__ queries,
+                             const double *__restrict__ q_sn, int dim, const int *__restrict__ adj0, int stride0,
+                             const int64_t *__restrict__ upper, const int *__restrict__ pool, int strideU, int entry, int entry_layer,
+                             int k, int cand_cap, ND *__restrict__ spill, int spill_cap, unsigned *__restrict__ visited, long long vis_words,
+                             int *__restrict__ vis_tab, int vis_tab_cap, const unsigned *__restrict__ allow_bits, long long allow_n, int k_out,
+                             int *__restrict__ out_ids, float *__restrict__ out_d, int *__restrict__ out_flag,
+                             unsigned long long *__restrict__ eval_counter, int nbcap, int njobs, int *__restrict__ job_counter)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int lane = threadIdx.x & 63;
+    VisitedSet<HASHED> V{visited + (size_t)blockIdx.x * (size_t)vis_words, vis_words,
+                         vis_tab ? vis_tab + (size_t)blockIdx.x * (size_t)vis_tab_cap : nullptr, (unsigned)(vis_tab_cap - 1), 0, vis_tab_cap / 4 * 3};
+    ND *my_spill = spill + (size_t)blockIdx.x * (size_t)spill_cap;
+    const SearchLds L = carve_lds(smem, k, cand_cap, dim, nbcap);
+    const GraphView G{adj0, stride0, upper, pool, strideU};
+    const AllowSet allow{allow_bits, allow_n};
+    for (;;) {
+        int job = 0;
+        if (lane == 0) job = atomicAdd(job_counter, 1);
+        job = __builtin_amdgcn_readfirstlane(job);
+        if (job >= njobs) break;
+        const SearchJob jb{job, entry, entry_layer, 0, -1, 0};
+        const float *q = queries + (size_t)job * dim;
+        double sb = 0.0;
+        if (METRIC == M_COS) sb = q_sn[job];
+        wave_sync();
+        for (int i = lane; i < dim; i += 64) L.qs[i] = q[i];
+        unsigned long long evals = 0;
+        int top_n = 0;
+        ReadLog RL{nullptr, 0, 0};
+        const bool ok = traverse<METRIC, HASHED, true>(rows, row_sn, dim, sb, G, jb, k, cand_cap, my_spill, spill_cap, V, L, lane, top_n, evals, RL,
+                                                       nullptr, nullptr, true, allow);
+        take_stable(L, lane, top_n, k_out, out_ids, out_d, job);
+        if (lane == 0) {
+            out_flag[job] = ok ? 0 : 1;
+            atomicAdd(eval_counter, evals);
+        }
+        V.clear(lane);
+    }
+}
+#define HNSW_FILTERED_SIGNATURE(PREFIX, M, H)                                                                                       \
+    PREFIX template __global__ void graph_search_filtered_kernel<M, H>(                                                             \
+        const float *__restrict__, const double *__restrict__, const float *__restrict__, const double *__restrict__, int,      \
+        const int *__restrict__, int, const int64_t *__restrict__, const int *__restrict__, int, int, int, int, int, ND *__restrict__, \
+        int, unsigned *__restrict__, long long, int *__restrict__, int, const unsigned *__restrict__, long long, int, int *__restrict__, \
+        float *__restrict__, int *__restrict__, unsigned long long *__restrict__, int, int, int *__restrict__);
+#define HNSW_FOR_EACH_FILTERED(X, M) X(M, false) X(M, true)
+#define HNSW_DECLARE_FILTERED(M, H) HNSW_FILTERED_SIGNATURE(extern, M, H)
+#define HNSW_DEFINE_FILTERED(M, H) HNSW_FILTERED_SIGNATURE(, M, H)
 
 #ifdef HNSW_HOST_TU // few variants and launched from one place: defined only in the unit that launches it
 // RangeQuery on the device: FindEntryPointQuery + GraphNavigator.SearchLayerRange (GraphNavigator.cs:262-325)

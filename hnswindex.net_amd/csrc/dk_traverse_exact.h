@@ -6,11 +6,15 @@ namespace hnsw {
 
 // Descent + beam search of one job; result = L.top[0..top_n) in heap order.  Returns false on
 // candidate-heap overflow.  The query must already be staged in L.qs.
-template <int METRIC, bool HASHED>
+// FILTERED (graph_search_filtered_kernel, KnnQuery with an allow-set -- SearchLayerQuery's filterFnc, GraphNavigator.cs:194-256):
+// `allow` is a bitset of `allow_n` bits over ids (AllowSet); a node outside it is a candidate like any other but never enters
+// the result heap.  FILTERED = false (every other caller) compiles to the unfiltered traversal: the allow arguments are unused.
+template <int METRIC, bool HASHED, bool FILTERED = false>
 __device__ __forceinline__ bool traverse(const float *__restrict__ rows, const double *__restrict__ row_sn, int dim, double sb,
                                          const GraphView &G, const SearchJob jb, int k, int cand_cap, ND *spill, int spill_cap,
                                          VisitedSet<HASHED> &V, const SearchLds &L, int lane, int &top_n_out, unsigned long long &evals,
-                                         ReadLog &RL, const int *abort_word = nullptr, bool *aborted = nullptr, bool overlapped_form = false)
+                                         ReadLog &RL, const int *abort_word = nullptr, bool *aborted = nullptr, bool overlapped_form = false,
+                                         AllowSet allow = AllowSet{nullptr, 0})
 {
     const LdsHeap top{L.top};
     const SpillHeap cand{L.cand, cand_cap, spill};
@@ -58,7 +62,8 @@ __device__ __forceinline__ bool traverse(const float *__restrict__ rows, const d
     if (key_unsafe(cur)) overflow = true;
     // jb.aux == -2 (removal's search, GraphConnector.cs:96): the filter id != entry keeps the entry point out of the
     // results (:132-136) -- it is a candidate only, and farthestResultDist starts at MaxValue
-    const bool entry_filtered = jb.aux == -2;
+    // FILTERED: the entry point is a result only if it is allowed (:203-211); its word is read once
+    const bool entry_filtered = jb.aux == -2 || (FILTERED && !allow.has(best));
     {
         HEnt e{best, f2key(cur)};
         if (!entry_filtered) heap_push<false>(top, top_n, e); // :134
@@ -101,6 +106,7 @@ __device__ __forceinline__ bool traverse(const float *__restrict__ rows, const d
         bool have = false; // overlapped form: this lane holds an unvisited neighbour, its distance and id
         float lane_d = 0.0f;
         int lane_id = 0;
+        bool lane_ok = true; // FILTERED, overlapped form: this lane's neighbour is allowed
         const bool overlapped = overlapped_form && n <= 64;
         if (overlapped) {
             // as in traverse_sorted: the rows of ALL listed neighbours requested together with the visited atomics -- one
@@ -116,6 +122,9 @@ __device__ __forceinline__ bool traverse(const float *__restrict__ rows, const d
                 hpos = ((unsigned)nb_a * 2654435761u) & V.tab_mask;
                 if (in) old = (unsigned)atomicCAS(&V.tab[hpos], -1, nb_a);
             } else if (in) old = atomicOr(&V.bits[nb_a >> 5], bit); // :181
+            // FILTERED: the neighbour's allow word rides in the same round trip as its visited word and its row
+            unsigned aw = 0u;
+            if constexpr (FILTERED) aw = in ? allow.word(nb_a) : 0u;
             pre_id = -1;
             if (cand_n > 0) {
                 pre_id = cand.get(0).id;
@@ -141,6 +150,7 @@ __device__ __forceinline__ bool traverse(const float *__restrict__ rows, const d
             if (V.crowded()) { hash_full = true; break; }
             lane_d = in ? dbuf[lane] : 0.0f;
             lane_id = nb_a;
+            if constexpr (FILTERED) lane_ok = ((aw >> (nb_a & 31)) & 1u) != 0u;
             if (m == 0) continue;
             evals += (unsigned long long)m;
         } else {
@@ -181,6 +191,10 @@ __device__ __forceinline__ bool traverse(const float *__restrict__ rows, const d
             const unsigned my_key = f2key(my_d);
             if (__ballot(valid && key_unsafe(my_d))) { overflow = true; break; }
             unsigned long long maybe = __ballot(valid && (top_n < k || my_key < far_key));
+            // FILTERED: which of them may enter topCandidates (:238-239).  Lists beyond 64 ids (no overlapped form) read the
+            // allow word here, after the distances; lists of up to 64 ids brought it with the visited word.
+            unsigned long long allowed_mask = ~0ull;
+            if constexpr (FILTERED) allowed_mask = __ballot(valid && (overlapped ? lane_ok : allow.has(my_id)));
             while (maybe) {
                 const int src = __builtin_ctzll(maybe);
                 maybe &= maybe - 1;
@@ -189,9 +203,11 @@ __device__ __forceinline__ bool traverse(const float *__restrict__ rows, const d
                     HEnt sel{__builtin_amdgcn_readlane(my_id, src), dk};
                     if (cand_n >= cand_limit) { overflow = true; break; }
                     heap_push<true>(cand, cand_n, sel);               // :168
+                    if (!FILTERED || ((allowed_mask >> src) & 1ull)) { // (FILTERED: :238-239; top unchanged otherwise, and so is :244-245)
                     heap_push<false>(top, top_n, sel);                // :171
                     if (top_n > k) (void)heap_pop_wave<false>(top, top_n, lane); // :173-174
                     far_key = top.get(0).key;                         // :176-177
+                    }
                 }
             }
         }

@@ -134,6 +134,21 @@ API int hnsw_knn_query(void *handle, const float *vectors, int count, int dim, i
     return 0;
 }
 
+// hnsw_knn_query with an allow-set (BatchKnnQuery(queries, k, filterFnc), HNSWIndex.cs:129-137): filtered calls take the handle
+// exclusively (no query lane)
+API int hnsw_mi355x_knn_query_filtered(void *handle, const float *vectors, int count, int dim, int k, const uint32_t *allow_bits, long long nbits,
+                                       int *out_ids, float *out_dists)
+{
+    if (!handle) return 0;
+    if (count <= 0) return 0;
+    if (!vectors || !out_ids || !out_dists || dim <= 0) { set_error("System.ArgumentNullException: hnsw_mi355x_knn_query_filtered"); return -1; }
+    if (!allow_bits || nbits < 0) { set_error("System.ArgumentException: hnsw_mi355x_knn_query_filtered: allow_bits must not be NULL and nbits must be >= 0"); return -1; }
+    LOCK_INDEX(handle);
+    std::string err;
+    if (static_cast<HnswIndex *>(handle)->knn_query_filtered(vectors, count, dim, k, allow_bits, nbits, out_ids, out_dists, err) < 0) { set_error(err); return -1; }
+    return 0;
+}
+
 API void hnsw_free_results(void **ids_array, void **dists_array, int count);
 
 API int hnsw_range_query(void *handle, const float *vectors, int count, int dim, float range, void **out_ids, void **out_dists, int *counts) // :151-197

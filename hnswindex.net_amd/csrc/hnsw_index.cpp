@@ -77,24 +77,29 @@ struct Descent {
     }
 };
 
-// GraphNavigator.SearchLayer / SearchLayerQuery (GraphNavigator.cs:123-256), no filter.
+// GraphNavigator.SearchLayer / SearchLayerQuery (GraphNavigator.cs:123-256).  The filter: `id != exclude` (removal's search) and,
+// for a filtered KnnQuery (GraphNavigator.cs:194-256), membership of the allow-set.
 struct Expand {
     const Graph *g = nullptr;
     int layer = 0, k = 0;
     int exclude = -1; // the filter `id => id != removedNode.Id` of GraphConnector.cs:96 (-1: none)
+    AllowBits allow;  // KnnQuery's filterFnc as a bitset (none: everything allowed)
     float farthest = 0.f;
 
-    void begin(const Graph *graph, SlotScratch &sc, int capacity, int entry, float entry_dist, int at_layer, int kk, int exclude_id = -1)
+    bool allowed(int id) const { return id != exclude && allow.has(id); }
+    void begin(const Graph *graph, SlotScratch &sc, int capacity, int entry, float entry_dist, int at_layer, int kk, int exclude_id = -1,
+               AllowBits allow_set = AllowBits{})
     {
         g = graph;
         layer = at_layer;
         k = kk;
         exclude = exclude_id;
+        allow = allow_set;
         sc.top.reset(k);      // :126
         sc.cand.reset(k * 2); // :127
         NodeDist e{entry, entry_dist};
         farthest = std::numeric_limits<float>::max(); // TDistance.MaxValue :130
-        if (entry != exclude) { // filterFnc(entryPointId) :132
+        if (allowed(entry)) { // filterFnc(entryPointId) :132 (:203-211)
             sc.top.push(e);       // :134
             farthest = entry_dist; // :135
         }
@@ -125,7 +130,7 @@ struct Expand {
             if (sc.top.count < k || d < farthest) { // :165
                 NodeDist sel{io.ids[i], d};
                 sc.cand.push(sel);                  // :168
-                if (sel.id != exclude) sc.top.push(sel); // :170-171
+                if (allowed(sel.id)) sc.top.push(sel); // :170-171 (:238-239)
                 if (sc.top.count > k) sc.top.pop(); // :173-174
                 if (sc.top.count > 0) farthest = sc.top.peek().dist; // :176-177
             }
@@ -182,13 +187,14 @@ struct Prune {
 };
 
 // ------------------------------------------------------------------------------------
-// KnnQuery job: HNSWIndex.KnnQuery (src/HNSWIndex/HNSWIndex.cs:107-124), layer 0, no filter.
+// KnnQuery job: HNSWIndex.KnnQuery (src/HNSWIndex/HNSWIndex.cs:107-124), layer 0, with or without an allow-set.
 // ------------------------------------------------------------------------------------
 struct QueryJob : Job {
     const Graph *g;
     int capacity, qi, ef, k;
     int *out_ids;
     float *out_d;
+    AllowBits allow; // the descent is not filtered (:116); the layer-0 search is
     Descent desc;
     Expand exp;
     int stage = 0; // 0 descent, 1 expand
@@ -198,7 +204,7 @@ struct QueryJob : Job {
         *io.qidx = qi;
         if (stage == 0) {
             if (desc.prepare(io)) return true;
-            exp.begin(g, sc, capacity, desc.best, desc.cur, 0, ef); // :117 (entry distance reused, same bits)
+            exp.begin(g, sc, capacity, desc.best, desc.cur, 0, ef, -1, allow); // :117 (entry distance reused, same bits)
             stage = 1;
         }
         return exp.prepare(io, sc);
@@ -1444,7 +1450,7 @@ bool HnswIndex::sync_graph(std::string &err)
 }
 
 // Host lock-step traversal for the queries listed in `which` (nullptr: all `count` queries).
-int HnswIndex::knn_query_lockstep(const int *which, int count, int k, int *out_ids, float *out_dists, std::string &err)
+int HnswIndex::knn_query_lockstep(const int *which, int count, int k, int *out_ids, float *out_dists, std::string &err, AllowBits allow)
 {
     if (!refresh_host_lists(err)) return -1;
     QuerySource src;
@@ -1460,6 +1466,7 @@ int HnswIndex::knn_query_lockstep(const int *which, int count, int k, int *out_i
         j.k = k;
         j.out_ids = out_ids + (size_t)qi * k;
         j.out_d = out_dists + (size_t)qi * k;
+        j.allow = allow;
     }
     if (!engine()->run(src, count)) { err = get_dev_error(); return -1; }
     return 0;
@@ -1499,6 +1506,61 @@ int HnswIndex::knn_query(const float *queries, int count, int dim, int k, int *o
     for (int g = 0; g < (sharded_resident_ ? p_.devices : 1); ++g) context(g)->cancel_streamed(); // (only after an error: `queries` is borrowed for this call)
     if (rc < 0) resident_queries_ = 0; // a failed call leaves no resident set: part of it may never have been uploaded
     return rc;
+}
+
+// KnnQuery with an allow-set (HNSWIndex.KnnQuery(query, k, filterFnc), HNSWIndex.cs:107-124, layer 0): the device's filtered
+// traversal where it fits, the lock-step path for whatever it hands back and where it does not.  Runs under the exclusive lock.
+int HnswIndex::knn_query_filtered(const float *queries, int count, int dim, int k, const uint32_t *allow_bits, long long nbits, int *out_ids,
+                                  float *out_dists, std::string &err)
+{
+    if (count <= 0) return 0;
+    if (failed(err)) return -1;
+    const AllowBits allow{allow_bits, nbits};
+    bool any = false; // a set that allows no id of the graph: the result is empty in any order (no launch, no traversal)
+    const long long n_allow = std::min<long long>(nbits, graph_.length);
+    for (long long w = 0; w < (n_allow + 31) / 32 && !any; ++w)
+        any = (allow_bits[w] & ((w + 1) * 32 <= n_allow ? ~0u : (1u << (n_allow & 31)) - 1u)) != 0u;
+    if (k < 1 || graph_.entry < 0 || graph_.count <= 0 || !any) { // HNSWIndex.cs:109: empty result lists, padded by the export
+        for (long long j = 0; j < (long long)count * std::max(k, 0); ++j) { out_ids[j] = -1; out_dists[j] = std::numeric_limits<float>::quiet_NaN(); }
+        return 0;
+    }
+    if (set_resident_queries(queries, count, dim, err) < 0) return -1;
+    const int ef = std::max(p_.min_nn, k); // HNSWIndex.cs:115
+    if (!(p_.device_traversal && dev_->traversal_fits(ef, false, p_.max_edges))) {
+        if (sharded_resident_) { // the host traversal runs on the primary alone: it needs the whole set there (as knn_query_resident)
+            for (int g = 1; g < p_.devices; ++g)
+                if (!dev_->adopt_queries(context(g), 0, shard_lo_[(size_t)g + 1] - shard_lo_[(size_t)g], shard_lo_[(size_t)g], count)) { err = get_dev_error(); return -1; }
+            sharded_resident_ = false;
+        }
+        return knn_query_lockstep(nullptr, count, k, out_ids, out_dists, err, allow);
+    }
+    if (!sync_graph(err)) return -1;
+    const int ep = graph_.entry, top = graph_.top_layer();
+    std::vector<int> flag((size_t)count);
+    if (sharded_resident_) { // every context answers its shard with the bitset uploaded to it
+        if (!ensure_replicas(true, err)) return -1;
+        const int n = p_.devices;
+        std::vector<std::string> errs((size_t)n);
+        std::vector<std::thread> th;
+        for (int g = 0; g < n; ++g)
+            th.emplace_back([&, g] {
+                const long long lo = shard_lo_[(size_t)g], hi = shard_lo_[(size_t)g + 1];
+                const int cnt = (int)(hi - lo);
+                if (cnt > 0 && !context(g)->search_filtered(cnt, ep, top, ef, k, allow_bits, nbits, out_ids + (size_t)lo * k, out_dists + (size_t)lo * k, flag.data() + lo))
+                    errs[(size_t)g] = get_dev_error().empty() ? "search_filtered failed" : get_dev_error();
+            });
+        for (auto &t : th) t.join();
+        for (const std::string &e : errs) if (!e.empty()) { err = e; return -1; }
+    } else if (!dev_->search_filtered(count, ep, top, ef, k, allow_bits, nbits, out_ids, out_dists, flag.data())) { err = get_dev_error(); return -1; }
+    std::vector<int> redo;
+    for (int i = 0; i < count; ++i) if (flag[(size_t)i]) redo.push_back(i);
+    if (redo.empty()) return 0;
+    if (sharded_resident_) { // the exact host traversal names queries by their global index on the primary
+        for (int g = 1; g < p_.devices; ++g)
+            if (!dev_->adopt_queries(context(g), 0, shard_lo_[(size_t)g + 1] - shard_lo_[(size_t)g], shard_lo_[(size_t)g], count)) { err = get_dev_error(); return -1; }
+        sharded_resident_ = false;
+    }
+    return knn_query_lockstep(redo.data(), (int)redo.size(), k, out_ids, out_dists, err, allow);
 }
 
 // The device contexts 1 .. devices - 1 (created on first use; more contexts than GPUs share them round robin --

@@ -52,6 +52,12 @@ public:
     // hnsw_knn_query: 0 or -1.
     int knn_query(const float *queries, int count, int dim, int k, int *out_ids, float *out_dists, std::string &err);
 
+    // hnsw_mi355x_knn_query_filtered: hnsw_knn_query with an allow-set (KnnQuery's filterFnc at layer 0) -- a bitset of nbits
+    // bits over ids, ids >= nbits not allowed.  Same conventions as knn_query; the caller holds the index lock EXCLUSIVELY
+    // (filtered calls take no query lane).  0 or -1.
+    int knn_query_filtered(const float *queries, int count, int dim, int k, const uint32_t *allow_bits, long long nbits, int *out_ids,
+                           float *out_dists, std::string &err);
+
     // Measurement aid: upload a query set once (resident in HBM), then run KnnQuery on it any
     // number of times without host->device traffic for the inputs.
     int set_resident_queries(const float *queries, int count, int dim, std::string &err, bool streamed = false);
@@ -174,7 +180,7 @@ private:
     int knn_query_sharded(int k, int *out_ids, float *out_dists, std::string &err);
     bool refresh_host_lists(std::string &err);
     int knn_query_device(const float *queries, int count, int k, int *out_ids, float *out_dists, std::string &err);
-    int knn_query_lockstep(const int *which, int count, int k, int *out_ids, float *out_dists, std::string &err);
+    int knn_query_lockstep(const int *which, int count, int k, int *out_ids, float *out_dists, std::string &err, AllowBits allow = AllowBits{});
     int range_query_lockstep(const int *which, int count, float range, std::vector<std::vector<NodeDist>> &out, std::string &err);
     int range_query_device(int count, float range, std::vector<std::vector<NodeDist>> &out, std::string &err);
     int remove_batched(const int *ids, int count, std::string &err);

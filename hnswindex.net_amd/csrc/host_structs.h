@@ -26,6 +26,14 @@ static inline int float_compare_to(float x, float y)
     if (std::isnan(x)) return std::isnan(y) ? 0 : -1;
     return 1;
 }
+// An allow-set over ids (KnnQuery's filterFnc as a bitset, include/hnsw_mi355x.h): bit i of `bits` is bit i & 31 of word i >> 5;
+// ids >= n are not allowed.  bits == nullptr: no filter, every id is allowed.
+struct AllowBits {
+    const uint32_t *bits = nullptr;
+    long long n = 0;
+    bool has(int id) const { return !bits || (id >= 0 && id < n && ((bits[id >> 5] >> (id & 31)) & 1u) != 0u); }
+};
+
 // src/HNSWIndex/DistanceComparer.cs:9-14 ("farther first": larger distance compares greater)
 struct FartherFirst {
     static inline int cmp(const NodeDist &x, const NodeDist &y)

@@ -174,6 +174,21 @@ int hnsw_mi355x_device_count(void *handle);
 struct hnswdev_stats;
 int hnsw_mi355x_get_stats_at(void *handle, int context, struct hnswdev_stats *out);
 
+/* KnnQuery / BatchKnnQuery with a filter (HNSWIndex.KnnQuery(query, k, filterFnc), src/HNSWIndex/HNSWIndex.cs:107-137, layer 0):
+ * hnsw_knn_query restricted to an ALLOW-SET over ids -- a little-endian bitset allow_bits of nbits bits, bit i = bit (i & 31) of
+ * word (i >> 5); ids >= nbits are not allowed.  The reference's filterFnc(Items[id]) is a pure predicate of the item, so
+ * bits[id] = filterFnc(Items[id]) over the live ids computes the same results: the descent to layer 0 is not filtered, a
+ * disallowed node is still a candidate of the layer-0 search but never a result, and the output is the stable OrderBy(Dist).Take(k)
+ * of the allowed results found -- same ids, distance bits, order and -1 / NaN padding as the reference.  A selective filter makes a
+ * query explore about k / selectivity nodes (all of layer 0 that it reaches when fewer than max(MinNN, k) ids are allowed): that
+ * is the reference's cost.  A set that allows no id of the index returns padding at once.  Return codes, the null-handle rule
+ * (0) and padding are those of hnsw_knn_query; a NULL allow_bits or nbits < 0 is an error (-1, message in
+ * hnsw_get_last_error_utf8).  Filtered calls take the handle exclusively (they do not overlap with other calls on it).
+ * Traversal on the device (graph_search_filtered_kernel) with hand-backs to the host path; with hnsw_mi355x_set_devices(n) every
+ * context gets the bitset and answers its shard. */
+int hnsw_mi355x_knn_query_filtered(void *handle, const float *vectors, int count, int dim, int k, const uint32_t *allow_bits,
+                                   long long nbits, int *out_ids, float *out_dists);
+
 /* Measurement aid: hnsw_mi355x_set_queries uploads a query set (count x dim) once; every later
  * hnsw_mi355x_knn_query_resident(k) is hnsw_knn_query on that set with the inputs already in HBM
  * (out arrays: count x k). */
@@ -355,6 +370,11 @@ int hnswdev_graph_commit(void *ctx);
  * capacity, NaN or -0 distance) -- evaluate it with hnswdev_dist_query_batch instead. */
 int hnswdev_knn_search(void *ctx, const float *queries, int nq, int entry_point, int k_beam, int k_out, int *out_ids,
                        float *out_dists, int *out_flags);
+/* hnswdev_knn_search with an allow-set (SearchLayerQuery's filterFnc, GraphNavigator.cs:194-256): allow_bits / nbits as for
+ * hnsw_mi355x_knn_query_filtered (a NULL allow_bits or nbits < 0: -1).  Runs the exact two-heap traversal with the filter
+ * (graph_search_filtered_kernel); out_flags[i] = 1: handed back as above (a selective filter grows the candidate heap). */
+int hnswdev_knn_search_filtered(void *ctx, const float *queries, int nq, int entry_point, int k_beam, int k_out, const uint32_t *allow_bits,
+                                long long nbits, int *out_ids, float *out_dists, int *out_flags);
 
 /* RangeQuery for nq queries from `entry_point`: FindEntryPointQuery + SearchLayerRange at layer 0
  * (HNSWIndex.cs:144-156, GraphNavigator.cs:262-325), no filter.  out_counts[i] = results of query i, kept in the
