@@ -101,6 +101,9 @@ lib.hnsw_mi355x_knn_query_resident.argtypes = [ct.c_void_p, ct.c_int, _I, _F]
 _U32 = ct.POINTER(ct.c_uint32)
 lib.hnsw_mi355x_knn_query_filtered.restype = ct.c_int
 lib.hnsw_mi355x_knn_query_filtered.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_int, ct.c_int, _U32, ct.c_longlong, _I, _F]
+lib.hnsw_mi355x_range_query_filtered.restype = ct.c_int
+lib.hnsw_mi355x_range_query_filtered.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_int, ct.c_float, _U32, ct.c_longlong, ct.POINTER(ct.c_void_p),
+                                                 ct.POINTER(ct.c_void_p), ct.POINTER(ct.c_int)]
 lib.hnsw_mi355x_active_ids.restype = ct.c_int
 lib.hnsw_mi355x_active_ids.argtypes = [ct.c_void_p, _I, ct.c_int]
 lib.hnsw_mi355x_node_max_layer.restype = ct.c_int
@@ -158,6 +161,8 @@ lib.hnswdev_knn_search_filtered.restype = ct.c_int
 lib.hnswdev_knn_search_filtered.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_int, ct.c_int, ct.c_int, _U32, ct.c_longlong, _I, _F, _I]
 lib.hnswdev_range_search.restype = ct.c_int
 lib.hnswdev_range_search.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_int, ct.c_float, _I, _I]
+lib.hnswdev_range_search_filtered.restype = ct.c_int
+lib.hnswdev_range_search_filtered.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_int, ct.c_float, _U32, ct.c_longlong, _I, _I]
 lib.hnswdev_range_results.restype = ct.c_int
 lib.hnswdev_range_results.argtypes = [ct.c_void_p, _I, _F]
 lib.hnswdev_sync.argtypes = [ct.c_void_p]
@@ -423,14 +428,21 @@ class Index:
             raise RuntimeError(last_error())
         return ids, dists  # freshly allocated above (the reference returns copies of equally fresh arrays, bindings.py:521)
 
-    def range_query(self, queries: npt.ArrayLike, radius: float) -> Tuple[List[npt.NDArray[np.int32]], List[npt.NDArray[np.float32]]]:
-        """bindings.py:523-597."""
+    def range_query(self, queries: npt.ArrayLike, radius: float,
+                    allowed=None) -> Tuple[List[npt.NDArray[np.int32]], List[npt.NDArray[np.float32]]]:
+        """bindings.py:523-597.  allowed: as for knn_query -- only those ids are results (hnsw_mi355x_range_query_filtered); where
+        the reference throws on an empty heap (radius < 0) RuntimeError carries its message."""
         q = _as_2d_f32(queries, self.dim)
         n = int(q.shape[0])
         ids_pp = (ct.c_void_p * n)()
         dists_pp = (ct.c_void_p * n)()
         counts = (ct.c_int * n)()
-        status = lib.hnsw_range_query(self._h, q.ctypes.data_as(_F), n, self.dim, radius, ids_pp, dists_pp, counts)
+        if allowed is not None:
+            words, nbits = allow_bits(allowed)
+            words, wp = _words_arg(words)
+            status = lib.hnsw_mi355x_range_query_filtered(self._h, q.ctypes.data_as(_F), n, self.dim, radius, wp, nbits, ids_pp, dists_pp, counts)
+        else:
+            status = lib.hnsw_range_query(self._h, q.ctypes.data_as(_F), n, self.dim, radius, ids_pp, dists_pp, counts)
         if status < 0:
             raise RuntimeError(last_error())
         ids, dists = [], []
@@ -670,14 +682,21 @@ class DeviceBackend:
                                            ids.ctypes.data_as(_I), d.ctypes.data_as(_F), flags.ctypes.data_as(_I)))
         return ids, d, flags
 
-    def range_search(self, queries, entry_point: int, radius: float):
-        """Per query the ids / distances within `radius`, ascending by distance; flags[i] = 1: handed back (empty)."""
+    def range_search(self, queries, entry_point: int, radius: float, allowed=None):
+        """Per query the ids / distances within `radius`, ascending by distance; flags[i] = 1: handed back (empty).
+        allowed: as for Index.knn_query (hnswdev_range_search_filtered); None runs hnswdev_range_search."""
         q = _as_2d_f32(queries, self.dim)
         n = q.shape[0]
         counts = np.zeros(n, dtype=np.int32)
         flags = np.zeros(n, dtype=np.int32)
-        self._check(lib.hnswdev_range_search(self._ctx, q.ctypes.data_as(_F), n, int(entry_point), float(radius),
-                                             counts.ctypes.data_as(_I), flags.ctypes.data_as(_I)))
+        if allowed is not None:
+            words, nbits = allow_bits(allowed)
+            words, wp = _words_arg(words)
+            self._check(lib.hnswdev_range_search_filtered(self._ctx, q.ctypes.data_as(_F), n, int(entry_point), float(radius), wp, nbits,
+                                                          counts.ctypes.data_as(_I), flags.ctypes.data_as(_I)))
+        else:
+            self._check(lib.hnswdev_range_search(self._ctx, q.ctypes.data_as(_F), n, int(entry_point), float(radius),
+                                                 counts.ctypes.data_as(_I), flags.ctypes.data_as(_I)))
         total = int(counts.sum())
         ids = np.empty(max(total, 1), dtype=np.int32)
         d = np.empty(max(total, 1), dtype=np.float32)

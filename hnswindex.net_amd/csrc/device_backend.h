@@ -250,9 +250,17 @@ public:
         SearchHit *found = nullptr;        // the lists, in pinned memory the context owns: valid until its next range_batch
         size_t found_n = 0;
     };
-    bool range_batch(const SearchJob *jobs, int njobs, float range, RangeResults *res);
+    // allow_bits (a filtered RangeQuery; nbits bits as for search_filtered): the traversal is the unfiltered one,
+    // and what crosses back is packed -- a kRangeFinal job's cnt[i] entries are its RESULTS in the reference's order, any other
+    // job's are its whole CLOSURE (every node within range the traversal reached, allowed or not; kRangeTied: its allowed entries
+    // first, ascending), for the host to partition, sort and replay.  range < 0 leaves every closure to the host (the empty-heap rule).
+    bool range_batch(const SearchJob *jobs, int njobs, float range, RangeResults *res, const uint32_t *allow_bits = nullptr, long long nbits = 0);
     // the C ABI's form: sorted per query, equal distances handed back; results kept until the next call
     bool range_search(const float *queries, int nq, int entry_point, float range, int *out_counts, int *out_flags);
+    // ... with an allow-set (ids >= nbits not allowed); false with "System.InvalidOperationException: Heap is empty" where the
+    // reference throws (range_replay.h)
+    bool range_search_filtered(const float *queries, int nq, int entry_point, float range, const uint32_t *allow_bits, long long nbits,
+                               int *out_counts, int *out_flags);
     bool range_results(int *out_ids, float *out_d);
 
     void set_profiling(bool on) { profiling_ = on; }
@@ -358,6 +366,10 @@ private:
     size_t h_range_cap_ = 0;
     bool range_host_room(size_t entries, size_t keep);
     int *s_rstate_ = nullptr, *s_rtied_ = nullptr, *s_rfin_ctr_ = nullptr; // RangeQuery's finishing kernels: per-job state, the tied jobs, two job counters
+    int *s_rres_ = nullptr;                  // filtered RangeQuery: allowed entries per job (range_sort_kernel<true>)
+    unsigned long long *s_rdst_ = nullptr;   // ... where each job's list lands in the packed copy-back (range_pack_kernel)
+    SearchHit *s_rpack_ = nullptr;           // ... the packed copy-back
+    size_t s_rpack_cap_ = 0;
     SearchHit *s_rlists_ = nullptr; // range search: long per-wave result lists for the few jobs that outgrow s_spill_'s
     size_t s_rlists_cap_ = 0;
     double range_hint_ = 48.0;      // results per query of the last range search (sizes the next arena)

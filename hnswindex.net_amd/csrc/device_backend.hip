@@ -349,7 +349,7 @@ Device::~Device()
     phase_report("teardown");
 #endif
     for (void *p : {(void *)g_adj0_, (void *)g_level_, (void *)g_upper_, (void *)g_pool_, (void *)g_tested0_, (void *)g_testedU_, (void *)s_visited_, (void *)s_jobs_,
-                    (void *)s_hits_, (void *)s_cnt_, (void *)s_flag_, (void *)s_jobctr_, (void *)s_vistab_, (void *)s_fvistab_, (void *)lp_slot_[0], (void *)lp_slot_[1], (void *)lp_slot_[2], (void *)lp_grp_[0], (void *)lp_grp_[1], (void *)lp_grp_[2], (void *)lp_grp_[3], (void *)lp_grp_[4], (void *)lp_grp_[5], (void *)lp_counters_, (void *)s_evals_, (void *)s_sel_, (void *)s_lcnt_, (void *)s_selU_, (void *)s_cntU_, (void *)s_iflag_, (void *)s_lk_[0], (void *)s_lk_[1], (void *)s_lk_[2], (void *)s_lk_[3], (void *)s_lk_[4], (void *)s_spill_, (void *)s_fspill_, (void *)s_allow_, (void *)s_order_, (void *)s_rlog_, (void *)s_dry_, (void *)s_wdry_, (void *)s_win_, (void *)s_arena_, (void *)s_roff_, (void *)s_arena_used_, (void *)s_rentry_, (void *)s_rlists_, (void *)s_rl_, (void *)s_rstate_, (void *)s_rtied_, (void *)s_rfin_ctr_})
+                    (void *)s_hits_, (void *)s_cnt_, (void *)s_flag_, (void *)s_jobctr_, (void *)s_vistab_, (void *)s_fvistab_, (void *)lp_slot_[0], (void *)lp_slot_[1], (void *)lp_slot_[2], (void *)lp_grp_[0], (void *)lp_grp_[1], (void *)lp_grp_[2], (void *)lp_grp_[3], (void *)lp_grp_[4], (void *)lp_grp_[5], (void *)lp_counters_, (void *)s_evals_, (void *)s_sel_, (void *)s_lcnt_, (void *)s_selU_, (void *)s_cntU_, (void *)s_iflag_, (void *)s_lk_[0], (void *)s_lk_[1], (void *)s_lk_[2], (void *)s_lk_[3], (void *)s_lk_[4], (void *)s_spill_, (void *)s_fspill_, (void *)s_allow_, (void *)s_order_, (void *)s_rlog_, (void *)s_dry_, (void *)s_wdry_, (void *)s_win_, (void *)s_arena_, (void *)s_roff_, (void *)s_arena_used_, (void *)s_rentry_, (void *)s_rlists_, (void *)s_rl_, (void *)s_rstate_, (void *)s_rtied_, (void *)s_rfin_ctr_, (void *)s_rres_, (void *)s_rdst_, (void *)s_rpack_})
         if (p) (void)hipFree(p);
     if (ev0_) (void)hipEventDestroy((hipEvent_t)ev0_);
     if (ev1_) (void)hipEventDestroy((hipEvent_t)ev1_);
@@ -2081,8 +2081,9 @@ bool Device::range_host_room(size_t entries, size_t keep)
     return true;
 }
 
-bool Device::range_batch(const SearchJob *jobs, int njobs, float range, RangeResults *res)
+bool Device::range_batch(const SearchJob *jobs, int njobs, float range, RangeResults *res, const uint32_t *allow_bits, long long nbits)
 {
+    const bool filtered = allow_bits != nullptr;
     res->off.assign((size_t)std::max(njobs, 0), 0ull);
     res->cnt.assign((size_t)std::max(njobs, 0), 0);
     res->flag.assign((size_t)std::max(njobs, 0), 0);
@@ -2094,6 +2095,7 @@ bool Device::range_batch(const SearchJob *jobs, int njobs, float range, RangeRes
     if (!jobs) { set_dev_error("range_batch: bad argument"); return false; }
     if (g_n_ <= 0) { set_dev_error("range_batch: no graph uploaded"); return false; }
     if (!jobs_valid(jobs, njobs, g_n_, n_queries_, n_rows_hw_)) { set_dev_error("range_batch: job outside the uploaded graph / rows / queries"); return false; }
+    if (filtered && nbits < 0) { set_dev_error("range_batch: bad argument"); return false; }
     for (int i = 0; i < njobs; ++i)
         if (jobs[i].qref < 0 || jobs[i].search_layer != 0) { set_dev_error("range_batch: jobs must name a resident query and layer 0"); return false; }
     const int nbcap_r = kRangeFan * nbcap(); // the kernel expands kRangeFan lists per step
@@ -2116,8 +2118,24 @@ bool Device::range_batch(const SearchJob *jobs, int njobs, float range, RangeRes
         s_rstate_ = nullptr; s_rtied_ = nullptr;
         HIP_OK(hipMalloc(&s_rstate_, sizeof(int) * (size_t)chunk));
         HIP_OK(hipMalloc(&s_rtied_, sizeof(int) * ((size_t)chunk + 1)));
+        if (s_rres_) HIP_OK(hipFree(s_rres_));
+        if (s_rdst_) HIP_OK(hipFree(s_rdst_));
+        s_rres_ = nullptr; s_rdst_ = nullptr; // (allocated by the first filtered call)
         s_roff_cap_ = (size_t)chunk;
     }
+    long long n_allow = 0;
+    if (filtered) { // the call's allow-set: the words that cover graph ids, on this context (as search_filtered)
+        if (!s_rres_) HIP_OK(hipMalloc(&s_rres_, sizeof(int) * s_roff_cap_));
+        if (!s_rdst_) HIP_OK(hipMalloc(&s_rdst_, sizeof(unsigned long long) * s_roff_cap_));
+        n_allow = std::min<long long>(nbits, g_n_);
+        const size_t words = (size_t)((n_allow + 31) / 32);
+        if (!grow_dev(&s_allow_, &s_allow_cap_, std::max<size_t>(words, 1))) return false;
+        if (words) {
+            HIP_OK(hipMemcpyAsync(s_allow_, allow_bits, 4u * words, hipMemcpyHostToDevice, st));
+            HIP_OK(hipStreamSynchronize(st)); // (pageable source: the caller's buffer)
+        }
+    }
+    unsigned long long closure_total = 0; // entries the traversals found (sizes the next call's arena)
     if (!s_arena_used_) HIP_OK(hipMalloc(&s_arena_used_, sizeof(unsigned long long)));
     if (!s_rfin_ctr_) HIP_OK(hipMalloc(&s_rfin_ctr_, sizeof(int) * 2));
     constexpr size_t kArenaMax = (size_t)1 << 27; // 1 GB of results per launch; what does not fit then is handed back
@@ -2127,9 +2145,10 @@ bool Device::range_batch(const SearchJob *jobs, int njobs, float range, RangeRes
     auto launch = [&](const int *todo, int nj, ND *lists, int list_cap, int grid_cap, size_t arena_cap, std::vector<int> &again,
                       unsigned long long *need, std::vector<int> &handed) -> bool {
         if (!grow_dev(&s_arena_, &s_arena_cap_, arena_cap)) return false;
-        // pinned layout: [evals, used (16 B) | jobs | offsets | counts | flags | entries]; then reused for the results
+        // pinned layout: [evals, used (16 B) | jobs | offsets | counts | flags | entries | states]; then reused for the results
+        // (filtered: [... | allowed counts | packed offsets] besides)
         const size_t b_jobs = sizeof(SearchJob) * (size_t)nj, b_off = 8u * (size_t)nj, b_i = 4u * (size_t)nj;
-        char *hs = static_cast<char *>(pinned_stage(16 + b_jobs + b_off + 4 * b_i));
+        char *hs = static_cast<char *>(pinned_stage(16 + b_jobs + b_off + 4 * b_i + (filtered ? b_i + b_off : 0)));
         if (!hs) return false;
         SearchJob *h_jobs = reinterpret_cast<SearchJob *>(hs + 16);
         for (int i = 0; i < nj; ++i) h_jobs[i] = jobs[todo[i]];
@@ -2152,26 +2171,40 @@ bool Device::range_batch(const SearchJob *jobs, int njobs, float range, RangeRes
         // the ORDER, still on the device (dk_range_finish.h): every finished list ranked ascending in place; the lists that hold equal
         // distances replayed -- the reference's two heaps on the distances just found -- and ranked in heap-array order.  What these
         // hand back (lists beyond kRangeSortMax entries, -0 distances) the callers sort and replay on the host as before.
+        // Filtered calls always rank (the partition by the filter is what makes the copy-back small); range_finish=0 and range < 0
+        // then only count and leave every list to the host.
         const int finish = diag("range_finish", 2); // 0: order left to the host (as until round 5), 1: ranking only, 2: ranking and replays
         HIP_OK(hipMemsetAsync(s_rfin_ctr_, 0, sizeof(int) * 2, st));
         HIP_OK(hipMemsetAsync(s_rtied_, 0, sizeof(int), st));
         HIP_OK(hipMemsetAsync(s_rstate_, 0, sizeof(int) * (size_t)nj, st));
-        if (finish >= 1) {
-            hipLaunchKernelGGL(range_sort_kernel, dim3(std::min(nj, 8 * std::max(1, num_cu_))), dim3(64), 0, st, reinterpret_cast<ND *>(s_arena_), s_roff_, s_cnt_, s_flag_, nj,
+        const dim3 sort_grid(std::min(nj, 8 * std::max(1, num_cu_))), replay_grid(std::min(nj, 2 * std::max(1, num_cu_)));
+        if (filtered) {
+            hipLaunchKernelGGL(range_sort_filtered_kernel, sort_grid, dim3(64), 0, st, reinterpret_cast<ND *>(s_arena_), s_roff_, s_cnt_, s_flag_, nj,
+                               s_rstate_, s_rtied_, s_rfin_ctr_, reinterpret_cast<const unsigned *>(s_allow_), n_allow, s_rres_,
+                               (int)(finish == 0 || range < 0.0f));
+            HIP_OK(hipGetLastError());
+        } else if (finish >= 1) {
+            hipLaunchKernelGGL(range_sort_kernel, sort_grid, dim3(64), 0, st, reinterpret_cast<ND *>(s_arena_), s_roff_, s_cnt_, s_flag_, nj,
                                s_rstate_, s_rtied_, s_rfin_ctr_);
             HIP_OK(hipGetLastError());
         }
         if (finish >= 2) {
-            hipLaunchKernelGGL(range_replay_kernel, dim3(std::min(nj, 2 * std::max(1, num_cu_))), dim3(64), sizeof(RangeReplayLds) + 64, st, reinterpret_cast<ND *>(s_arena_), s_roff_,
-                               s_cnt_, s_rentry_, g_adj0_, g_stride0_, g_n_, range, s_rstate_, s_rtied_, s_rfin_ctr_ + 1);
+            if (filtered)
+                hipLaunchKernelGGL(range_replay_filtered_kernel, replay_grid, dim3(64), sizeof(RangeReplayLds) + 64, st, reinterpret_cast<ND *>(s_arena_), s_roff_,
+                                   s_cnt_, s_rentry_, g_adj0_, g_stride0_, g_n_, range, s_rstate_, s_rtied_, s_rfin_ctr_ + 1, s_rres_);
+            else
+                hipLaunchKernelGGL(range_replay_kernel, replay_grid, dim3(64), sizeof(RangeReplayLds) + 64, st, reinterpret_cast<ND *>(s_arena_), s_roff_,
+                                   s_cnt_, s_rentry_, g_adj0_, g_stride0_, g_n_, range, s_rstate_, s_rtied_, s_rfin_ctr_ + 1);
             HIP_OK(hipGetLastError());
         }
         if (timed) HIP_OK(hipEventRecord((hipEvent_t)ev1_, st));
         unsigned long long *h_hdr = reinterpret_cast<unsigned long long *>(hs);
         unsigned long long *h_off = reinterpret_cast<unsigned long long *>(hs + 16 + b_jobs);
         int *h_cnt = reinterpret_cast<int *>(hs + 16 + b_jobs + b_off);
-        int *h_flag = h_cnt + nj, *h_entry = h_flag + nj, *h_state = h_entry + nj;
+        int *h_flag = h_cnt + nj, *h_entry = h_flag + nj, *h_state = h_entry + nj, *h_res = h_state + nj;
+        unsigned long long *h_dst = reinterpret_cast<unsigned long long *>(h_res + nj);
         HIP_OK(hipMemcpyAsync(h_state, s_rstate_, b_i, hipMemcpyDeviceToHost, st));
+        if (filtered) HIP_OK(hipMemcpyAsync(h_res, s_rres_, b_i, hipMemcpyDeviceToHost, st));
         HIP_OK(hipMemcpyAsync(h_hdr, s_evals_, 8, hipMemcpyDeviceToHost, st));
         HIP_OK(hipMemcpyAsync(h_hdr + 1, s_arena_used_, 8, hipMemcpyDeviceToHost, st));
         HIP_OK(hipMemcpyAsync(h_off, s_roff_, b_off, hipMemcpyDeviceToHost, st));
@@ -2191,14 +2224,40 @@ bool Device::range_batch(const SearchJob *jobs, int njobs, float range, RangeRes
             if (h_flag[i] == 0) {
                 res->off[(size_t)j] = base + h_off[i];
                 res->cnt[(size_t)j] = h_cnt[i];
-                res->state[(size_t)j] = finish >= 1 ? h_state[i] : kRangeHostSort;
-                if (h_cnt[i] >= 2) { if (res->state[(size_t)j] == kRangeFinal) stats_.range_device_ordered++; else stats_.range_host_ordered++; }
+                res->state[(size_t)j] = finish >= 1 || filtered ? h_state[i] : kRangeHostSort;
+                const int results = filtered ? h_res[i] : h_cnt[i]; // (filtered, handed to the host: the allowed members of its closure)
+                if (results >= 2) { if (res->state[(size_t)j] == kRangeFinal) stats_.range_device_ordered++; else stats_.range_host_ordered++; }
                 finished += (unsigned long long)h_cnt[i];
                 if (h_cnt[i] > 0) span = std::max(span, h_off[i] + (unsigned long long)h_cnt[i]);
             } else if (h_flag[i] == 3) again.push_back(j);
             else { res->flag[(size_t)j] = 1; handed.push_back(j); }
         }
         *need = used - finished;
+        closure_total += finished;
+        if (filtered) { // only what the host needs crosses: final lists' results, other lists' closures -- packed in job order
+            unsigned long long packed = 0;
+            for (int i = 0; i < nj; ++i) {
+                h_dst[i] = packed;
+                if (h_flag[i] != 0) continue;
+                const int j = todo[i];
+                const int held = h_state[i] == kRangeFinal ? h_res[i] : h_cnt[i]; // (range_pack_kernel's own rule)
+                res->off[(size_t)j] = base + packed;
+                res->cnt[(size_t)j] = held;
+                packed += (unsigned long long)held;
+            }
+            if (packed > 0) {
+                if (!grow_dev(&s_rpack_, &s_rpack_cap_, (size_t)packed)) return false;
+                HIP_OK(hipMemcpyAsync(s_rdst_, h_dst, b_off, hipMemcpyHostToDevice, st));
+                hipLaunchKernelGGL(range_pack_kernel, dim3(std::min((nj + 3) / 4, 8 * std::max(1, num_cu_))), dim3(256), 0, st, reinterpret_cast<const ND *>(s_arena_),
+                                   s_roff_, s_cnt_, s_flag_, s_rstate_, s_rres_, s_rdst_, nj, reinterpret_cast<ND *>(s_rpack_));
+                HIP_OK(hipGetLastError());
+                if (!range_host_room(base + (size_t)packed, base)) return false;
+                HIP_OK(hipMemcpyAsync(h_range_ + base, s_rpack_, sizeof(SearchHit) * (size_t)packed, hipMemcpyDeviceToHost, st));
+                HIP_OK(hipStreamSynchronize(st));
+                res->found_n = base + (size_t)packed;
+            }
+            span = 0;
+        }
         if (span > 0) { // one copy, straight into the context's pinned result buffer (no staging hop, nothing zero-filled first)
             if (!range_host_room(base + (size_t)span, base)) return false;
             HIP_OK(hipMemcpyAsync(h_range_ + base, s_arena_, sizeof(SearchHit) * (size_t)span, hipMemcpyDeviceToHost, st));
@@ -2240,9 +2299,7 @@ bool Device::range_batch(const SearchJob *jobs, int njobs, float range, RangeRes
         handed.swap(still);
     }
     stats_.range_handbacks += handed.size();
-    unsigned long long total = 0;
-    for (int i = 0; i < njobs; ++i) total += (unsigned long long)res->cnt[(size_t)i];
-    range_hint_ = (double)total / (double)njobs;
+    range_hint_ = (double)closure_total / (double)njobs; // (filtered calls too: the arena holds closures)
     return true;
 }
 
@@ -2251,22 +2308,43 @@ static inline bool range_hit_less(const SearchHit &a, const SearchHit &b) { retu
 
 bool Device::range_search(const float *queries, int nq, int entry_point, float range, int *out_counts, int *out_flags)
 {
+    return range_search_filtered(queries, nq, entry_point, range, nullptr, 0, out_counts, out_flags);
+}
+
+// allow_bits == nullptr: no filter (range_search)
+bool Device::range_search_filtered(const float *queries, int nq, int entry_point, float range, const uint32_t *allow_bits, long long nbits,
+                                   int *out_counts, int *out_flags)
+{
     abi_range_.clear();
     if (nq <= 0) return true;
     if (!out_counts || !out_flags) { set_dev_error("range_search: null argument"); return false; }
     if (!hg_ || g_n_ <= 0) { set_dev_error("range_search: no graph committed"); return false; }
-    if (entry_point < 0 || entry_point >= hg_->n) { set_dev_error("range_search: bad argument"); return false; }
+    if (entry_point < 0 || entry_point >= hg_->n || (allow_bits && nbits < 0)) { set_dev_error("range_search: bad argument"); return false; }
     if (!set_queries(queries, nq)) return false;
     std::vector<SearchJob> jobs((size_t)nq);
     const int top = hg_->level[(size_t)entry_point];
     for (int i = 0; i < nq; ++i) jobs[(size_t)i] = SearchJob{i, entry_point, top, 0, -1};
     RangeResults r;
-    if (!range_batch(jobs.data(), nq, range, &r)) return false;
+    if (!range_batch(jobs.data(), nq, range, &r, allow_bits, nbits)) return false;
+    const auto list_of = [&](int id) { return hg_->adj0.data() + (size_t)id * (size_t)hg_->stride0; };
     for (int i = 0; i < nq; ++i) {
         out_counts[i] = 0;
         out_flags[i] = r.flag[(size_t)i];
         if (out_flags[i]) continue;
         SearchHit *b = r.found + r.off[(size_t)i], *e = b + r.cnt[(size_t)i];
+        if (allow_bits && r.state[(size_t)i] != kRangeFinal) { // a closure: partition, sort, replay where the allowed results tie
+            std::vector<NodeDist> ordered;
+            if (finish_filtered_range(list_of, 2 * hg_->M, r.entry[(size_t)i], range, b, r.cnt[(size_t)i], AllowBits{allow_bits, nbits}, ordered) ==
+                kRangeHeapEmpty) {
+                abi_range_.clear();
+                for (int j = 0; j < nq; ++j) out_counts[j] = 0;
+                set_dev_error(kHeapEmptyError);
+                return false;
+            }
+            out_counts[i] = (int)ordered.size();
+            for (const NodeDist &nd : ordered) abi_range_.push_back(SearchHit{nd.id, nd.dist});
+            continue;
+        }
         bool tie = r.state[(size_t)i] == kRangeTied; // (the device replays what it can: this is what it handed back)
         if (r.state[(size_t)i] == kRangeHostSort) {
             std::sort(b, e, range_hit_less);
@@ -2275,8 +2353,7 @@ bool Device::range_search(const float *queries, int nq, int entry_point, float r
         out_counts[i] = r.cnt[(size_t)i];
         if (tie) { // OrderBy keeps the heap array's order there (HNSWIndex.cs:155): replay the heaps on the committed graph
             std::vector<NodeDist> ordered;
-            replay_range_heaps([&](int id) { return hg_->adj0.data() + (size_t)id * (size_t)hg_->stride0; }, 2 * hg_->M, r.entry[(size_t)i], range, b,
-                               r.cnt[(size_t)i], ordered);
+            replay_range_heaps(list_of, 2 * hg_->M, r.entry[(size_t)i], range, b, r.cnt[(size_t)i], ordered);
             for (const NodeDist &nd : ordered) abi_range_.push_back(SearchHit{nd.id, nd.dist});
             continue;
         }
@@ -2553,6 +2630,13 @@ DEV_API int hnswdev_range_search(void *ctx, const float *queries, int nq, int en
 {
     CTX_OR_FAIL();
     return d->range_search(queries, nq, entry_point, range, out_counts, out_flags) ? 0 : -1;
+}
+DEV_API int hnswdev_range_search_filtered(void *ctx, const float *queries, int nq, int entry_point, float range, const uint32_t *allow_bits, long long nbits,
+                                          int *out_counts, int *out_flags)
+{
+    CTX_OR_FAIL();
+    if (!allow_bits || nbits < 0) { hnsw::set_dev_error("hnswdev_range_search_filtered: allow_bits must not be NULL and nbits must be >= 0"); return -1; }
+    return d->range_search_filtered(queries, nq, entry_point, range, allow_bits, nbits, out_counts, out_flags) ? 0 : -1;
 }
 DEV_API int hnswdev_range_results(void *ctx, int *out_ids, float *out_dists) { CTX_OR_FAIL(); return d->range_results(out_ids, out_dists) ? 0 : -1; }
 DEV_API int hnswdev_sync(void *ctx) { CTX_OR_FAIL(); return d->sync() ? 0 : -1; }

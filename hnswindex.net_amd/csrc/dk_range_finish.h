@@ -83,6 +83,89 @@ range_sort_kernel(ND *__restrict__ arena, const unsigned long long *__restrict__
     }
 }
 
+// FILTERED ranking: the allowed entries of e (a disallowed one carries its id with bit 31 set) stably ranked by (key, position)
+// to out[0, ma), the disallowed ones behind them in their order.  Returns (wave-uniform) whether two ALLOWED entries share a key.
+__device__ __forceinline__ bool rank_partition(const int2 *e, int m, int ma, ND *out, int lane)
+{
+    bool tie = false;
+    for (int i0 = 0; i0 < m; i0 += 64) {
+        const int i = i0 + lane;
+        const int2 ei = i < m ? e[i] : make_int2(0, 0);
+        const unsigned ki = (unsigned)ei.y;
+        const bool ai = ei.x >= 0;
+        int below = 0, before = 0;
+        bool eq = false;
+        for (int j = 0; j < m; ++j) {
+            const int2 ej = e[j];
+            const unsigned kj = (unsigned)ej.y;
+            const bool aj = ej.x >= 0;
+            below += (aj && (kj < ki || (kj == ki && j < i))) ? 1 : 0;
+            before += (!aj && j < i) ? 1 : 0;
+            eq = eq || (aj && kj == ki && j != i);
+        }
+        if (i < m) out[ai ? below : ma + before] = ND{ei.x & 0x7fffffff, key2f(ki)};
+        tie = tie || (i < m && ai && eq);
+    }
+    return __ballot(tie) != 0ull;
+}
+
+// range_sort_kernel for a RangeQuery with an allow-set.  The list is the query's whole CLOSURE, allowed or not --
+// the traversal does not depend on the filter.  The allowed entries (bits of `allow`, ids >= n_allow not allowed) come first,
+// ranked as above, the disallowed ones behind them; res[job] = the number of allowed entries; the tie test looks at the allowed
+// entries alone.  A list of 0 or 1 allowed entries is final at any length (its one result moved to the front).  host_all (range <
+// 0: the empty-heap rule is the host's; diag range_finish=0): every list that holds entries is left to the host as found, res[]
+// still counted.  (Kernels of their own: the unfiltered ones keep their code.)
+__global__ void __launch_bounds__(64)
+range_sort_filtered_kernel(ND *__restrict__ arena, const unsigned long long *__restrict__ off, const int *__restrict__ cnt, const int *__restrict__ flag,
+                           int njobs, int *__restrict__ state, int *__restrict__ tied, int *__restrict__ job_counter, const unsigned *__restrict__ allow,
+                           long long n_allow, int *__restrict__ res, int host_all)
+{
+    __shared__ int2 e[kRangeSortMax];
+    const int lane = threadIdx.x;
+    for (;;) {
+        int job = 0;
+        if (lane == 0) job = atomicAdd(job_counter, 1);
+        job = __builtin_amdgcn_readfirstlane(job);
+        if (job >= njobs) break;
+        const int m = __builtin_amdgcn_readfirstlane(cnt[job]);
+        int st = kRangeFinal;
+        int ma = 0; // allowed entries
+        if (__builtin_amdgcn_readfirstlane(flag[job]) == 0 && m > 0) {
+            ND *a = arena + off[job];
+            const bool fits = m <= kRangeSortMax;
+            bool unsafe = false;
+            int first = m; // the first allowed entry
+            wave_sync();
+            for (int i0 = 0; i0 < m; i0 += 64) {
+                const int i = i0 + lane;
+                bool ok = false;
+                if (i < m) {
+                    const ND v = a[i];
+                    ok = (long long)v.id < n_allow && ((allow[v.id >> 5] >> (v.id & 31)) & 1u) != 0u;
+                    unsafe = unsafe || key_unsafe(v.dist);
+                    if (fits) e[i] = make_int2(ok ? v.id : (int)((unsigned)v.id | 0x80000000u), (int)f2key(v.dist));
+                }
+                const unsigned long long b = __ballot(ok);
+                if (first == m && b != 0ull) first = i0 + (int)__builtin_ctzll(b);
+                ma += __popcll(b);
+            }
+            wave_sync();
+            if (host_all) st = kRangeHostSort; // left as found
+            else if (ma <= 1) {
+                if (ma == 1 && first > 0 && lane == 0) a[0] = a[first];
+            } else if (!fits || __ballot(unsafe) != 0ull) st = kRangeHostSort; // -0 anywhere: the candidate heap's order is float.CompareTo's
+            else st = rank_partition(e, m, ma, a, lane) ? kRangeTied : kRangeFinal;
+        }
+        wave_sync();
+        if (lane == 0) { // (one store point: see range_sort_kernel)
+            state[job] = st;
+            res[job] = ma;
+            if (st == kRangeTied) tied[1 + atomicAdd(&tied[0], 1)] = job;
+        }
+        __builtin_amdgcn_wave_barrier();
+    }
+}
+
 // LDS of one replaying wave: entries (id, key) in ascending order, an id -> entry hash, visited bits, the two heaps.
 struct RangeReplayLds {
     int2 e[kRangeSortMax];                      // the list, ascending (as range_sort_kernel left it)
@@ -210,6 +293,148 @@ range_replay_kernel(ND *__restrict__ arena, const unsigned long long *__restrict
         wave_sync();
         if (lane == 0) state[job] = st; // (one store point, no `continue` behind a lane-0 branch: see range_sort_kernel)
         __builtin_amdgcn_wave_barrier();
+    }
+}
+
+// range_replay_kernel for a RangeQuery with an allow-set: the table holds the whole closure as range_sort_filtered_kernel left it,
+// its res[job] allowed entries first -- entry index < res[job] is the allow bit.  Only those enter the top heap (:271, :307-308);
+// the candidate heap takes every closure member.  (range >= 0 here: an empty top heap's Peek, buffer[0] = default(NodeDistance),
+// is never beyond range, :310.)
+__global__ void __launch_bounds__(64)
+range_replay_filtered_kernel(ND *__restrict__ arena, const unsigned long long *__restrict__ off, const int *__restrict__ cnt, const int *__restrict__ entry,
+                             const int *__restrict__ adj0, int stride0, long long n_nodes, float range, int *__restrict__ state,
+                             const int *__restrict__ tied, int *__restrict__ job_counter, const int *__restrict__ res)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    RangeReplayLds &L = *reinterpret_cast<RangeReplayLds *>(smem);
+    const int lane = threadIdx.x;
+    const int n_tied = tied[0];
+    const LdsHeap top{L.top}, cand{L.cand};
+    for (;;) {
+        int t = 0;
+        if (lane == 0) t = atomicAdd(job_counter, 1);
+        t = __builtin_amdgcn_readfirstlane(t);
+        if (t >= n_tied) break;
+        const int job = __builtin_amdgcn_readfirstlane(tied[1 + t]);
+        const int m = __builtin_amdgcn_readfirstlane(cnt[job]);
+        const int ma = __builtin_amdgcn_readfirstlane(res[job]); // results: the allowed entries
+        ND *a = arena + off[job];
+        int st = kRangeTied; // what the host finds if this wave gives up: an ascending list to replay
+        if (m >= 2 && m <= kRangeSortMax) { // (always: range_sort_kernel listed it)
+        wave_sync();
+        for (int i = lane; i < 2 * kRangeSortMax; i += 64) L.slot[i] = 0;
+        for (int i = lane; i < kRangeSortMax / 32; i += 64) L.visited[i] = 0u;
+        for (int i = lane; i < m; i += 64) { const ND v = a[i]; L.e[i] = make_int2(v.id, (int)f2key(v.dist)); }
+        wave_sync();
+        // the table is filled by one lane at a time per slot (atomicCAS on LDS shorts is not available: 32-bit words of two slots)
+        unsigned *slot32 = reinterpret_cast<unsigned *>(L.slot);
+        constexpr unsigned kMask = 2 * kRangeSortMax - 1;
+        for (int i = lane; i < m; i += 64) {
+            unsigned h = ((unsigned)L.e[i].x * 2654435761u) & kMask;
+            for (unsigned probes = 0; probes <= kMask; ++probes) {
+                const unsigned w = h >> 1, sh = (h & 1u) * 16u;
+                const unsigned old = slot32[w];
+                if (((old >> sh) & 0xffffu) == 0u) {
+                    if (atomicCAS(&slot32[w], old, old | ((unsigned)(i + 1) << sh)) == old) break;
+                    continue; // the word changed under us (its other half, or this one): look again
+                }
+                h = (h + 1) & kMask;
+            }
+        }
+        wave_sync();
+        auto find = [&](int id) -> int { // entry index of id, or -1
+            unsigned h = ((unsigned)id * 2654435761u) & kMask;
+            for (unsigned probes = 0; probes <= kMask; ++probes) {
+                const unsigned s = L.slot[h];
+                if (s == 0u) return -1;
+                if (L.e[s - 1].x == id) return (int)s - 1;
+                h = (h + 1) & kMask;
+            }
+            return -1;
+        };
+        int n_top = 0, n_cand = 0;
+        const int ep = entry[job];
+        const int es = __builtin_amdgcn_readfirstlane(find(ep));
+        const unsigned range_key = f2key(range);
+        unsigned farthest = 0xffffffffu; // :269 MaxValue
+        bool entry_out = es < 0;         // the entry point lies out of range: a candidate all the same (:277), never a result
+        if (!entry_out) { // :271-275, :279
+            const HEnt en{es, (unsigned)L.e[es].y};
+            if (es < ma) {
+                heap_push<false>(top, n_top, en);
+                farthest = en.key;
+            }
+            if (lane == 0) L.visited[es >> 5] |= 1u << (es & 31);
+            heap_push<true>(cand, n_cand, en);
+        }
+        wave_sync();
+        bool first = true;
+        for (int step = 0; step <= m + 1; ++step) { // (every listed node and the entry point are expanded once: m + 1 steps at most)
+            int node;
+            if (entry_out && first) node = ep; // alone in `candidates` when popped; :286 cannot fire (farthestResultDist is still MaxValue)
+            else {
+                if (n_cand == 0) break;                                  // :283
+                const HEnt c = cand.get(0);                              // :285
+                if (c.key > farthest && c.key > range_key) break;        // :286-289 (every candidate is in range: never fires)
+                const HEnt popped = heap_pop_wave<true>(cand, n_cand, lane); // :290
+                wave_sync();
+                node = L.e[popped.id].x;
+            }
+            first = false;
+            if (node < 0 || (long long)node >= n_nodes) break; // (guard: ids come from the graph the list was found on)
+            const int *l = adj0 + (size_t)node * stride0;
+            const int n = __builtin_amdgcn_readfirstlane(l[0]);
+            for (int base = 0; base < n; base += 64) {                   // :294
+                const int i = base + lane;
+                int idx = -1;
+                if (i < n) idx = find(l[1 + i]);
+                bool fresh = idx >= 0 && ((L.visited[idx >> 5] >> (idx & 31)) & 1u) == 0u; // :297; not listed = out of range (:302 fails, :318)
+                wave_sync();
+                if (fresh) atomicOr(&L.visited[idx >> 5], 1u << (idx & 31));             // :318 (a list holds no duplicates)
+                unsigned long long mask = __ballot(fresh);
+                while (mask) {                                           // in adjacency order
+                    const int src = (int)__builtin_ctzll(mask);
+                    mask &= mask - 1;
+                    const int ix = __builtin_amdgcn_readlane(idx, src);
+                    const HEnt sel{ix, (unsigned)L.e[ix].y};
+                    heap_push<true>(cand, n_cand, sel);                  // :305
+                    if (ix < ma) heap_push<false>(top, n_top, sel);      // :307-308 (:310-311 never pops: sel is in range)
+                    if (n_top > 0) farthest = top.get(0).key;            // :313-314
+                }
+                wave_sync();
+            }
+        }
+        wave_sync();
+        // the top heap's array, stably ranked by key (HNSWIndex.cs:155): entries of the arena list that the replay did not reach
+        // cannot exist (the kernel's closure and the heaps' closure are the same set); if they do, leave the job to the host
+        if (n_top == ma && ma >= 2 && ma <= kRangeSortMax) { // (always, for a tied list; spelled out, rank_stable's callers all bound its m so)
+            int2 *h2 = reinterpret_cast<int2 *>(L.cand); // the candidate heap is empty now: its LDS holds (id, key) in heap-array order
+            for (int i = lane; i < ma; i += 64) { const ND t2 = L.top[i]; h2[i] = make_int2(L.e[t2.id].x, L.e[t2.id].y); }
+            wave_sync();
+            // distances: the original bits (a key maps back to its float exactly; -0 lists never get here)
+            (void)rank_stable(h2, ma, a, nullptr, lane);
+            st = kRangeFinal;
+        }
+        }
+        wave_sync();
+        if (lane == 0) state[job] = st; // (one store point, no `continue` behind a lane-0 branch: see range_sort_kernel)
+        __builtin_amdgcn_wave_barrier();
+    }
+}
+
+// FILTERED calls: what crosses to the host, packed at dst[job] in `out` -- a final list's results (res[job] entries), any other
+// list's closure (cnt[job] entries); handed-back jobs carry nothing.  The host computed dst from the same state / res / cnt.
+__global__ void __launch_bounds__(256)
+range_pack_kernel(const ND *__restrict__ arena, const unsigned long long *__restrict__ off, const int *__restrict__ cnt, const int *__restrict__ flag,
+                  const int *__restrict__ state, const int *__restrict__ res, const unsigned long long *__restrict__ dst, int njobs, ND *__restrict__ out)
+{
+    const int lane = threadIdx.x & 63;
+    for (int job = blockIdx.x * 4 + (threadIdx.x >> 6); job < njobs; job += gridDim.x * 4) {
+        if (flag[job] != 0) continue;
+        const int n = state[job] == kRangeFinal ? res[job] : cnt[job];
+        const ND *s = arena + off[job];
+        ND *d = out + dst[job];
+        for (int i = lane; i < n; i += 64) d[i] = s[i];
     }
 }
 #endif

@@ -151,21 +151,21 @@ API int hnsw_mi355x_knn_query_filtered(void *handle, const float *vectors, int c
 
 API void hnsw_free_results(void **ids_array, void **dists_array, int count);
 
-API int hnsw_range_query(void *handle, const float *vectors, int count, int dim, float range, void **out_ids, void **out_dists, int *counts) // :151-197
+// hnsw_range_query and its filtered sibling: `name` for the errors, allow (none: no filter)
+static int range_query_export(void *handle, const float *vectors, int count, int dim, float range, hnsw::AllowBits allow, void **out_ids,
+                              void **out_dists, int *counts, const char *name)
 {
-    if (!handle) return 0;
-    if (count <= 0) return 0;
-    if (!vectors || !out_ids || !out_dists || !counts || dim <= 0) { set_error("System.ArgumentNullException: hnsw_range_query"); return -1; }
+    if (!vectors || !out_ids || !out_dists || !counts || dim <= 0) { set_error(std::string("System.ArgumentNullException: ") + name); return -1; }
     for (int i = 0; i < count; ++i) { out_ids[i] = nullptr; out_dists[i] = nullptr; counts[i] = 0; }
     std::string err;
     std::vector<std::vector<hnsw::NodeDist>> res;
     {
         LOCK_INDEX(handle);
-        if (static_cast<HnswIndex *>(handle)->range_query(vectors, count, dim, range, res, err) < 0) { set_error(err); return -1; }
+        if (static_cast<HnswIndex *>(handle)->range_query(vectors, count, dim, range, res, err, allow) < 0) { set_error(err); return -1; }
     }
     const bool trace = hnsw::diag("trace", 0) != 0;
     const auto t_out0 = std::chrono::steady_clock::now();
-    struct OutTimer { bool on; std::chrono::steady_clock::time_point t0; int count; ~OutTimer() { if (on) fprintf(stderr, "[hnsw trace] hnsw_range_query: handing out %d per-query arrays %.4fs\n", count, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count()); } } out_timer{trace, t_out0, count};
+    struct OutTimer { bool on; std::chrono::steady_clock::time_point t0; int count; const char *name; ~OutTimer() { if (on) fprintf(stderr, "[hnsw trace] %s: handing out %d per-query arrays %.4fs\n", name, count, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count()); } } out_timer{trace, t_out0, count, name};
     // callee-allocated per-query arrays (Marshal.AllocHGlobal :172-173), freed by hnsw_free_results: a call of thousands of queries hands out
     // millions of results, so the copies are spread over host threads (malloc is thread-safe; a failed allocation fails the call as before)
     std::atomic<int> next{0};
@@ -195,10 +195,30 @@ API int hnsw_range_query(void *handle, const float *vectors, int count, int dim,
     if (oom.load()) {
         hnsw_free_results(out_ids, out_dists, count);
         for (int j = 0; j < count; ++j) counts[j] = 0;
-        set_error("System.OutOfMemoryException: hnsw_range_query");
+        set_error(std::string("System.OutOfMemoryException: ") + name);
         return -1;
     }
     return 0;
+}
+
+API int hnsw_range_query(void *handle, const float *vectors, int count, int dim, float range, void **out_ids, void **out_dists, int *counts) // :151-197
+{
+    if (!handle) return 0;
+    if (count <= 0) return 0;
+    return range_query_export(handle, vectors, count, dim, range, hnsw::AllowBits{}, out_ids, out_dists, counts, "hnsw_range_query");
+}
+
+// hnsw_range_query with an allow-set (BatchRangeQuery(queries, range, filterFnc), HNSWIndex.cs:158-168): the bitset as for
+// hnsw_mi355x_knn_query_filtered.  Where the reference pops an empty heap (range < 0) the call returns -1 with
+// every array NULL and every count 0, as the reference export's catch block leaves them (:187-196).
+API int hnsw_mi355x_range_query_filtered(void *handle, const float *vectors, int count, int dim, float range, const uint32_t *allow_bits,
+                                         long long nbits, void **out_ids, void **out_dists, int *counts)
+{
+    if (!handle) return 0;
+    if (count <= 0) return 0;
+    if (!allow_bits || nbits < 0) { set_error("System.ArgumentException: hnsw_mi355x_range_query_filtered: allow_bits must not be NULL and nbits must be >= 0"); return -1; }
+    return range_query_export(handle, vectors, count, dim, range, hnsw::AllowBits{allow_bits, nbits}, out_ids, out_dists, counts,
+                              "hnsw_mi355x_range_query_filtered");
 }
 
 API void hnsw_free_results(void **ids_array, void **dists_array, int count) // :199-217
@@ -556,6 +576,21 @@ API int hnswhost_test_range_replay(const int *adj0, int stride, int max_edges0, 
     for (int i = 0; i < m; ++i) found[(size_t)i] = Hit{found_ids[i], found_d[i]};
     std::vector<hnsw::NodeDist> out;
     hnsw::replay_range_heaps([&](int id) { return adj0 + (size_t)id * (size_t)stride; }, max_edges0, entry, range, found.data(), m, out);
+    for (size_t i = 0; i < out.size(); ++i) { out_ids[i] = out[i].id; out_d[i] = out[i].dist; }
+    return (int)out.size();
+}
+// ... with an allow-set (ids >= nbits not allowed): found = the query's whole closure.  Returns the result count, or -2 where the
+// reference pops an empty heap (range_replay.h).
+API int hnswhost_test_range_replay_filtered(const int *adj0, int stride, int max_edges0, int entry, float range, const int *found_ids, const float *found_d,
+                                            int m, const uint32_t *allow_bits, long long nbits, int *out_ids, float *out_d)
+{
+    struct Hit { int id; float dist; };
+    std::vector<Hit> found((size_t)m);
+    for (int i = 0; i < m; ++i) found[(size_t)i] = Hit{found_ids[i], found_d[i]};
+    std::vector<hnsw::NodeDist> out;
+    if (hnsw::replay_range_heaps([&](int id) { return adj0 + (size_t)id * (size_t)stride; }, max_edges0, entry, range, found.data(), m, out,
+                                 hnsw::AllowBits{allow_bits, nbits}) == hnsw::kRangeHeapEmpty)
+        return -2;
     for (size_t i = 0; i < out.size(); ++i) { out_ids[i] = out[i].id; out_d[i] = out[i].dist; }
     return (int)out.size();
 }

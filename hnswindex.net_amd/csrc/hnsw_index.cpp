@@ -242,7 +242,10 @@ struct QuerySource : JobSource {
 
 // ------------------------------------------------------------------------------------
 // RangeQuery job: HNSWIndex.RangeQuery (src/HNSWIndex/HNSWIndex.cs:144-156) =
-// FindEntryPointQuery + GraphNavigator.SearchLayerRange (GraphNavigator.cs:262-325), no filter.
+// FindEntryPointQuery + GraphNavigator.SearchLayerRange (GraphNavigator.cs:262-325), with or without an allow-set.
+// The descent is not filtered (:152); only allowed nodes enter topCandidates (:271, :307-308).  A disallowed in-range
+// neighbour met while topCandidates is still empty, with range < 0, is where the reference pops an empty heap
+// (range_replay.h): the job stops with heap_empty set.
 // ------------------------------------------------------------------------------------
 struct RangeJob : Job {
     const Graph *g;
@@ -251,6 +254,8 @@ struct RangeJob : Job {
     std::vector<NodeDist> *out;
     Descent desc;
     int stage = 0;
+    AllowBits allow;         // filterFnc as a bitset (none: everything allowed)
+    bool heap_empty = false; // InvalidOperationException("Heap is empty") (BinaryHeap.cs:56)
 
     void begin_search(SlotScratch &sc)
     {
@@ -259,7 +264,7 @@ struct RangeJob : Job {
         sc.cand.reset(maxE * 2); // :266
         NodeDist e{desc.best, desc.cur}; // :268 (entry distance reused, same bits)
         farthest = std::numeric_limits<float>::max(); // TDistance.MaxValue :269
-        if (e.dist <= range) { sc.top.push(e); farthest = e.dist; } // :271-275
+        if (allow.has(e.id) && e.dist <= range) { sc.top.push(e); farthest = e.dist; } // :271-275
         sc.cand.push(e);         // :277
         sc.visited.begin(capacity);
         sc.visited.test_and_set(e.id); // :279
@@ -272,6 +277,7 @@ struct RangeJob : Job {
             begin_search(sc);
             stage = 1;
         }
+        if (heap_empty) return false;
         while (sc.cand.count > 0) {
             const NodeDist closest = sc.cand.peek();                             // :285
             if (closest.dist > farthest && closest.dist > range) return false;  // :286-289
@@ -288,12 +294,13 @@ struct RangeJob : Job {
     {
         if (stage == 0) { desc.consume(io); return; }
         const int n = *io.cnt;
-        for (int i = 0; i < n; ++i) {
+        for (int i = 0; i < n && !heap_empty; ++i) {
             const float d = io.dist[i];
             if (d <= range) { // :302
                 NodeDist sel{io.ids[i], d};
                 sc.cand.push(sel);                                   // :305
-                sc.top.push(sel);                                    // :308
+                if (allow.has(sel.id)) sc.top.push(sel);             // :307-308
+                else if (sc.top.count == 0) { heap_empty = 0.0f > range; continue; } // :310-311 peeks default(NodeDistance) (dist 0)
                 if (sc.top.peek().dist > range) sc.top.pop();        // :310-311
                 if (sc.top.count > 0) farthest = sc.top.peek().dist; // :313-314
             }
@@ -301,6 +308,7 @@ struct RangeJob : Job {
     }
     void finish(SlotScratch &sc)
     {
+        if (heap_empty) { out->clear(); return; }
         out->assign(sc.top.buf.begin(), sc.top.buf.begin() + sc.top.count);
         std::stable_sort(out->begin(), out->end(), [](const NodeDist &a, const NodeDist &b) { return float_compare_to(a.dist, b.dist) < 0; }); // OrderBy :155
     }
@@ -316,6 +324,7 @@ struct RangeSource : JobSource {
         RangeJob &j = jobs[(size_t)i];
         j.desc.begin(j.g, j.g->entry, 0);
         j.stage = 0;
+        j.heap_empty = false;
         return &j;
     }
     void release(Job *job, SlotScratch &sc) override { static_cast<RangeJob *>(job)->finish(sc); }
@@ -1757,7 +1766,8 @@ int HnswIndex::knn_query_sharded(int k, int *out_ids, float *out_dists, std::str
 }
 
 // Host lock-step range search for the queries listed in `which` (nullptr: all `count` queries).
-int HnswIndex::range_query_lockstep(const int *which, int count, float range, std::vector<std::vector<NodeDist>> &out, std::string &err)
+int HnswIndex::range_query_lockstep(const int *which, int count, float range, std::vector<std::vector<NodeDist>> &out, std::string &err,
+                                    AllowBits allow)
 {
     if (!refresh_host_lists(err)) return -1;
     RangeSource src;
@@ -1770,15 +1780,20 @@ int HnswIndex::range_query_lockstep(const int *which, int count, float range, st
         j.qi = qi;
         j.range = range;
         j.out = &out[(size_t)qi];
+        j.allow = allow;
     }
     if (!engine()->run(src, count)) { err = get_dev_error(); return -1; }
+    for (const RangeJob &j : src.jobs)
+        if (j.heap_empty) { err = kHeapEmptyError; return -1; }
     return 0;
 }
 
 // Graph-resident range search (graph_range_kernel): the result SET of SearchLayerRange does not depend on the
 // order its heaps pop in; the reference's stable OrderBy (HNSWIndex.cs:155) does only between results of equal
 // distance, and for a query holding such a pair the heaps are replayed on the host from the known distances.
-int HnswIndex::range_query_device(int count, float range, std::vector<std::vector<NodeDist>> &out, std::string &err)
+// With an allow-set the device hands back each list either final or as its closure (Device::range_batch); closures are
+// partitioned by the filter, sorted and, where allowed results tie or range < 0, replayed (finish_filtered_range).
+int HnswIndex::range_query_device(int count, float range, std::vector<std::vector<NodeDist>> &out, std::string &err, AllowBits allow)
 {
     if (!sync_graph(err)) return -1;
     std::vector<SearchJob> jobs((size_t)count);
@@ -1786,7 +1801,8 @@ int HnswIndex::range_query_device(int count, float range, std::vector<std::vecto
     for (int i = 0; i < count; ++i) jobs[(size_t)i] = SearchJob{i, ep, top, 0, -1};
     Device::RangeResults r;
     g_pt.rq_queries += count;
-    { Tick t(g_pt.rq_batch); if (!dev_->range_batch(jobs.data(), count, range, &r)) { err = get_dev_error(); return -1; } }
+    const bool filtered = allow.bits != nullptr;
+    { Tick t(g_pt.rq_batch); if (!dev_->range_batch(jobs.data(), count, range, &r, allow.bits, allow.n)) { err = get_dev_error(); return -1; } }
     // host threads over the queries: sort each result list; a list holding two equal distances is replayed instead
     auto parallel_for = [&](size_t n, size_t grain, const std::function<void(size_t, size_t)> &body) {
         std::atomic<size_t> next{0};
@@ -1804,6 +1820,7 @@ int HnswIndex::range_query_device(int count, float range, std::vector<std::vecto
     parallel_for((size_t)count, 256, [&](size_t lo, size_t hi) {
         for (size_t i = lo; i < hi; ++i) {
             if (r.flag[i]) { state[i] = 1; continue; }
+            if (filtered && r.state[i] != kRangeFinal) { state[i] = 2; continue; } // a closure: finished with the lists at hand
             SearchHit *b = r.found + r.off[i], *e = b + r.cnt[i];
             bool tie = r.state[i] == kRangeTied; // ascending, equal distances in it, and the device did not replay it
             if (r.state[i] == kRangeHostSort) {  // beyond the device ranking's reach (length, a -0 distance): as until round 5
@@ -1826,19 +1843,27 @@ int HnswIndex::range_query_device(int count, float range, std::vector<std::vecto
     if (!replay.empty()) {
         { Tick t(g_pt.rq_refresh); if (!refresh_host_lists(err)) return -1; } // the replay walks the host's copy of the lists
         Tick t_rep(g_pt.rq_replay);
+        std::atomic<bool> heap_empty{false};
         parallel_for(replay.size(), 1, [&](size_t lo, size_t hi) {
             for (size_t t = lo; t < hi; ++t) {
                 const int i = replay[t];
-                replay_range_heaps([&](int id) { return graph_.list(id, 0); }, graph_.max_edges_at(0), r.entry[(size_t)i], range,
-                                   r.found + r.off[(size_t)i], r.cnt[(size_t)i], out[(size_t)i]);
+                const auto list_of = [&](int id) { return graph_.list(id, 0); };
+                if (filtered) {
+                    if (finish_filtered_range(list_of, graph_.max_edges_at(0), r.entry[(size_t)i], range, r.found + r.off[(size_t)i], r.cnt[(size_t)i], allow,
+                                              out[(size_t)i]) == kRangeHeapEmpty)
+                        heap_empty.store(true);
+                } else
+                    replay_range_heaps(list_of, graph_.max_edges_at(0), r.entry[(size_t)i], range, r.found + r.off[(size_t)i], r.cnt[(size_t)i], out[(size_t)i]);
             }
         });
+        if (heap_empty.load()) { err = kHeapEmptyError; return -1; }
     }
-    if (!redo.empty()) return range_query_lockstep(redo.data(), (int)redo.size(), range, out, err);
+    if (!redo.empty()) return range_query_lockstep(redo.data(), (int)redo.size(), range, out, err, allow);
     return 0;
 }
 
-int HnswIndex::range_query(const float *queries, int count, int dim, float range, std::vector<std::vector<NodeDist>> &out, std::string &err)
+int HnswIndex::range_query(const float *queries, int count, int dim, float range, std::vector<std::vector<NodeDist>> &out, std::string &err,
+                           AllowBits allow)
 {
     out.assign((size_t)std::max(count, 0), {});
     if (failed(err)) return -1;
@@ -1846,8 +1871,11 @@ int HnswIndex::range_query(const float *queries, int count, int dim, float range
     if (!ensure_dim(dim, err)) return -1;
     resident_queries_ = 0; // the resident set is replaced: a later knn_query_resident must not answer for these rows
     if (!dev_->set_queries(queries, count)) { err = get_dev_error(); return -1; }
-    if (p_.device_traversal && dev_->traversal_fits(1, false, p_.max_edges)) return range_query_device(count, range, out, err);
-    return range_query_lockstep(nullptr, count, range, out, err);
+    int rc;
+    if (p_.device_traversal && dev_->traversal_fits(1, false, p_.max_edges)) rc = range_query_device(count, range, out, err, allow);
+    else rc = range_query_lockstep(nullptr, count, range, out, err, allow);
+    if (rc < 0 && err == kHeapEmptyError) out.assign((size_t)count, {}); // the whole batch fails (Parallel.For rethrows)
+    return rc;
 }
 
 // ---- HNSWIndex.Remove (src/HNSWIndex/HNSWIndex.cs:83-102) ------------------------------------

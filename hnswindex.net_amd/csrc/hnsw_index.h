@@ -65,7 +65,10 @@ public:
 
     // hnsw_range_query (HNSWIndex.RangeQuery, src/HNSWIndex/HNSWIndex.cs:144-168): per query the
     // in-range results ordered by distance.  Host lock-step traversal.
-    int range_query(const float *queries, int count, int dim, float range, std::vector<std::vector<NodeDist>> &out, std::string &err);
+    // allow: RangeQuery(query, range, filterFnc) as a bitset over ids (none: no filter).  Where the reference pops an empty
+    // top heap (range < 0, range_replay.h) the call fails with kHeapEmptyError.
+    int range_query(const float *queries, int count, int dim, float range, std::vector<std::vector<NodeDist>> &out, std::string &err,
+                    AllowBits allow = AllowBits{});
 
     // hnsw_remove (HNSWIndex.Remove, src/HNSWIndex/HNSWIndex.cs:83-102), ids in order.
     int remove(const int *ids, int count, std::string &err);
@@ -181,8 +184,9 @@ private:
     bool refresh_host_lists(std::string &err);
     int knn_query_device(const float *queries, int count, int k, int *out_ids, float *out_dists, std::string &err);
     int knn_query_lockstep(const int *which, int count, int k, int *out_ids, float *out_dists, std::string &err, AllowBits allow = AllowBits{});
-    int range_query_lockstep(const int *which, int count, float range, std::vector<std::vector<NodeDist>> &out, std::string &err);
-    int range_query_device(int count, float range, std::vector<std::vector<NodeDist>> &out, std::string &err);
+    int range_query_lockstep(const int *which, int count, float range, std::vector<std::vector<NodeDist>> &out, std::string &err,
+                             AllowBits allow = AllowBits{});
+    int range_query_device(int count, float range, std::vector<std::vector<NodeDist>> &out, std::string &err, AllowBits allow);
     int remove_batched(const int *ids, int count, std::string &err);
 
     int metric_ = 0;

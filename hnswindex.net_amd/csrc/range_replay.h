@@ -15,8 +15,16 @@ namespace hnsw {
 // point's own distance is never compared when it is out of range (it is alone in `candidates` when popped, and
 // farthestResultDist is still MaxValue at :286).  Result: topCandidates' array, stably sorted (HNSWIndex.cs:155).
 // list_of(id) -> the node's layer-0 list as [count, ids...]; Hit: {int id; float dist}.
+// With an allow-set (RangeQuery's filterFnc), `found` is the query's whole CLOSURE -- every node within range the traversal
+// reached, allowed or not: the traversal does not depend on the filter -- and only allowed nodes enter the top heap (:271,
+// :307-308).  Its Peek (:310) then reads buffer[0] before the first push: default(NodeDistance), distance 0.  With range < 0
+// that is beyond range, and Pop throws on the empty heap (BinaryHeap.cs:56): returned as kRangeHeapEmpty (out cleared).
+// (Written out: this heap is fresh, but the lock-step path's scratch heaps are reused, and their buffer[0] is stale.)
+constexpr int kRangeHeapEmpty = -1;
+constexpr const char *kHeapEmptyError = "System.InvalidOperationException: Heap is empty"; // (the reference export's last error)
 template <class ListOf, class Hit>
-inline void replay_range_heaps(ListOf list_of, int max_edges0, int entry, float range, const Hit *found, int m, std::vector<NodeDist> &out)
+inline int replay_range_heaps(ListOf list_of, int max_edges0, int entry, float range, const Hit *found, int m, std::vector<NodeDist> &out,
+                              AllowBits allow = AllowBits{})
 {
     size_t cap = 16;
     while (cap < 2 * (size_t)m) cap <<= 1;
@@ -42,7 +50,10 @@ inline void replay_range_heaps(ListOf list_of, int max_edges0, int entry, float 
     float farthest = std::numeric_limits<float>::max(); // :269
     Slot *es = slot_of(entry);
     NodeDist e{entry, es ? es->dist : std::numeric_limits<float>::infinity()};
-    if (es) { top.push(e); farthest = e.dist; es->visited = true; } // :271-275, :279
+    if (es) { // :271-275, :279
+        if (allow.has(entry)) { top.push(e); farthest = e.dist; }
+        es->visited = true;
+    }
     cand.push(e);                                                  // :277
     while (cand.count > 0) {
         const NodeDist closest = cand.peek();                                        // :285
@@ -56,13 +67,32 @@ inline void replay_range_heaps(ListOf list_of, int max_edges0, int entry, float 
             sl->visited = true;
             NodeDist sel{sl->id, sl->dist};
             cand.push(sel);                                   // :305
-            top.push(sel);                                    // :308
-            if (top.peek().dist > range) top.pop();           // :310-311
+            if (allow.has(sel.id)) top.push(sel);             // :307-308
+            else if (top.count == 0 && 0.0f > range) { out.clear(); return kRangeHeapEmpty; } // :310-311 on an empty heap
+            if (top.count > 0 && top.peek().dist > range) top.pop(); // :310-311 (an empty heap's distance 0 is within range here)
             if (top.count > 0) farthest = top.peek().dist;    // :313-314
         }
     }
     out.assign(top.buf.begin(), top.buf.begin() + top.count);
     std::stable_sort(out.begin(), out.end(), [](const NodeDist &a, const NodeDist &b) { return float_compare_to(a.dist, b.dist) < 0; });
+    return 0;
+}
+
+// A filtered list held as its closure (any order; reordered in place): its allowed members in the reference's order.  Their
+// ascending order when their distances are pairwise different (-0 next to +0 counts as equal), the replay over the whole
+// closure otherwise -- and always for range < 0, where the empty-heap rule depends on the discovery order.  Returns 0 or
+// kRangeHeapEmpty.
+template <class ListOf, class Hit>
+inline int finish_filtered_range(ListOf list_of, int max_edges0, int entry, float range, Hit *b, int m, AllowBits allow, std::vector<NodeDist> &out)
+{
+    Hit *mid = std::partition(b, b + m, [&](const Hit &h) { return allow.has(h.id); });
+    std::sort(b, mid, [](const Hit &x, const Hit &y) { return x.dist < y.dist; }); // no NaN: d <= range held
+    bool tie = m > 0 && 0.0f > range;
+    for (Hit *q = b; q + 1 < mid; ++q) tie |= q[0].dist == q[1].dist;
+    if (tie) return replay_range_heaps(list_of, max_edges0, entry, range, b, m, out, allow);
+    out.resize((size_t)(mid - b));
+    for (size_t a = 0; a < out.size(); ++a) out[a] = NodeDist{b[a].id, b[a].dist};
+    return 0;
 }
 
 } // namespace hnsw

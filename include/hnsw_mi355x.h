@@ -189,6 +189,19 @@ int hnsw_mi355x_get_stats_at(void *handle, int context, struct hnswdev_stats *ou
 int hnsw_mi355x_knn_query_filtered(void *handle, const float *vectors, int count, int dim, int k, const uint32_t *allow_bits,
                                    long long nbits, int *out_ids, float *out_dists);
 
+/* RangeQuery / BatchRangeQuery with a filter (HNSWIndex.RangeQuery(query, range, filterFnc), src/HNSWIndex/HNSWIndex.cs:144-168,
+ * layer 0): hnsw_range_query restricted to an allow-set, the bitset of hnsw_mi355x_knn_query_filtered (ids >= nbits not allowed).
+ * The descent and the layer-0 traversal are those of the unfiltered call -- a disallowed node within range is still a candidate
+ * and is expanded -- and only allowed nodes enter the result heap; each list is the stable OrderBy(Dist) of that heap's array:
+ * same ids, distance bits and order as the reference, including the order among equal distances.  Allocation, freeing
+ * (hnsw_free_results), the null-handle rule (0) and the exclusive lock are those of hnsw_range_query; a NULL allow_bits or
+ * nbits < 0 is an error (-1).  With range < 0 (cosine / ucosine distances can be negative) the reference can pop its empty result
+ * heap and throw: when the entry point is not both allowed and within range, its distance is not +inf, and the first id of its
+ * layer-0 list within range is disallowed.  Then the whole call returns -1 with every out_ids / out_dists entry NULL and every
+ * count 0, and hnsw_get_last_error_utf8 names System.InvalidOperationException: Heap is empty. */
+int hnsw_mi355x_range_query_filtered(void *handle, const float *vectors, int count, int dim, float range, const uint32_t *allow_bits,
+                                     long long nbits, void **out_ids, void **out_dists, int *counts);
+
 /* Measurement aid: hnsw_mi355x_set_queries uploads a query set (count x dim) once; every later
  * hnsw_mi355x_knn_query_resident(k) is hnsw_knn_query on that set with the inputs already in HBM
  * (out arrays: count x k). */
@@ -384,6 +397,11 @@ int hnswdev_knn_search_filtered(void *ctx, const float *queries, int nq, int ent
  * out_flags[i] = 1: handed back (count 0; on graphs above 4M nodes, a traversal that outgrows its visited table):
  * evaluate it with hnswdev_dist_query_batch instead. */
 int hnswdev_range_search(void *ctx, const float *queries, int nq, int entry_point, float range, int *out_counts, int *out_flags);
+/* hnswdev_range_search with an allow-set (the bitset of hnsw_mi355x_range_query_filtered; a NULL allow_bits or nbits < 0: -1):
+ * only allowed results are counted and returned, through hnswdev_range_results, in the reference's order.  Where the reference
+ * throws (range < 0, see hnsw_mi355x_range_query_filtered) it returns -1 with "System.InvalidOperationException: Heap is empty". */
+int hnswdev_range_search_filtered(void *ctx, const float *queries, int nq, int entry_point, float range, const uint32_t *allow_bits,
+                                  long long nbits, int *out_counts, int *out_flags);
 int hnswdev_range_results(void *ctx, int *out_ids, float *out_dists);
 
 int hnswdev_sync(void *ctx);
