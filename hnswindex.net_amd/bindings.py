@@ -55,7 +55,8 @@ class Stats(ct.Structure):
                 ("range_timed_evals", ct.c_uint64), ("range_kernel_ms", ct.c_double), ("range_handbacks", ct.c_uint64),
                 ("replica_bytes", ct.c_uint64),
                 ("tie_windows", ct.c_uint64), ("peer_direct_copies", ct.c_uint64), ("peer_staged_copies", ct.c_uint64), ("lat_launches", ct.c_uint64),
-                ("range_device_ordered", ct.c_uint64), ("range_host_ordered", ct.c_uint64), ("insert_tie_reruns", ct.c_uint64), ("lean_launches", ct.c_uint64)]
+                ("range_device_ordered", ct.c_uint64), ("range_host_ordered", ct.c_uint64), ("insert_tie_reruns", ct.c_uint64), ("lean_launches", ct.c_uint64),
+                ("multilayer_launches", ct.c_uint64), ("multilayer_jobs", ct.c_uint64), ("multilayer_handbacks", ct.c_uint64)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -105,6 +106,13 @@ lib.hnsw_mi355x_range_query_filtered.restype = ct.c_int
 lib.hnsw_mi355x_range_query_filtered.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_int, ct.c_float, _U32, ct.c_longlong, ct.POINTER(ct.c_void_p),
                                                  ct.POINTER(ct.c_void_p), ct.POINTER(ct.c_int)]
 lib.hnsw_mi355x_active_ids.restype = ct.c_int
+lib.hnsw_mi355x_knn_query_at_layer.restype = ct.c_int
+lib.hnsw_mi355x_knn_query_at_layer.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_int, ct.c_int, ct.c_int, _U32, ct.c_longlong, _I, _F]
+lib.hnsw_mi355x_range_query_at_layer.restype = ct.c_int
+lib.hnsw_mi355x_range_query_at_layer.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_int, ct.c_float, ct.c_int, _U32, ct.c_longlong, ct.POINTER(ct.c_void_p),
+                                                 ct.POINTER(ct.c_void_p), ct.POINTER(ct.c_int)]
+lib.hnsw_mi355x_multilayer_knn_query.restype = ct.c_int
+lib.hnsw_mi355x_multilayer_knn_query.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int, _I, _F]
 lib.hnsw_mi355x_active_ids.argtypes = [ct.c_void_p, _I, ct.c_int]
 lib.hnsw_mi355x_node_max_layer.restype = ct.c_int
 lib.hnsw_mi355x_node_max_layer.argtypes = [ct.c_void_p, ct.c_int]
@@ -165,6 +173,12 @@ lib.hnswdev_range_search_filtered.restype = ct.c_int
 lib.hnswdev_range_search_filtered.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_int, ct.c_float, _U32, ct.c_longlong, _I, _I]
 lib.hnswdev_range_results.restype = ct.c_int
 lib.hnswdev_range_results.argtypes = [ct.c_void_p, _I, _F]
+lib.hnswdev_knn_search_at_layer.restype = ct.c_int
+lib.hnswdev_knn_search_at_layer.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int, _U32, ct.c_longlong, _I, _F, _I]
+lib.hnswdev_range_search_at_layer.restype = ct.c_int
+lib.hnswdev_range_search_at_layer.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_int, ct.c_float, ct.c_int, _U32, ct.c_longlong, _I, _I]
+lib.hnswdev_multilayer_search.restype = ct.c_int
+lib.hnswdev_multilayer_search.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int, _I, _F, _I]
 lib.hnswdev_sync.argtypes = [ct.c_void_p]
 lib.hnswdev_set_profiling.argtypes = [ct.c_void_p, ct.c_int]
 lib.hnswdev_get_stats.argtypes = [ct.c_void_p, ct.POINTER(Stats)]
@@ -407,13 +421,25 @@ class Index:
         if result < 0:
             raise RuntimeError(last_error())
 
-    def knn_query(self, queries: npt.ArrayLike, k: int, allowed=None) -> Tuple[npt.NDArray[np.int32], npt.NDArray[np.float32]]:
+    def knn_query(self, queries: npt.ArrayLike, k: int, allowed=None, layer: int = 0) -> Tuple[npt.NDArray[np.int32], npt.NDArray[np.float32]]:
         """bindings.py:474-521.  allowed (not in the reference's Python class; its C# KnnQuery takes a filterFnc): a bool mask
-        indexed by id or an integer array of allowed ids -- only those ids are results (hnsw_mi355x_knn_query_filtered)."""
+        indexed by id or an integer array of allowed ids -- only those ids are results (hnsw_mi355x_knn_query_filtered).
+        layer (the C# KnnQuery's `layer`): search that layer's nodes only (hnsw_mi355x_knn_query_at_layer); outside
+        0 .. top_layer() on a non-empty index: RuntimeError."""
         q = _as_2d_f32(queries, self.dim)
         n = int(q.shape[0])
         ids = np.empty((n, k), dtype=np.int32)
         dists = np.empty((n, k), dtype=np.float32)
+        if layer != 0:
+            ids.fill(-1)          # (an index nothing was added to has no native handle yet: padding, as an empty index answers)
+            dists.fill(np.nan)
+            words, nbits = allow_bits(allowed) if allowed is not None else (None, 0)
+            words, wp = _words_arg(words) if allowed is not None else (None, None)
+            status = lib.hnsw_mi355x_knn_query_at_layer(self._h, q.ctypes.data_as(_F), n, self.dim, k, int(layer), wp, nbits, ids.ctypes.data_as(_I),
+                                                        dists.ctypes.data_as(_F))
+            if status < 0:
+                raise RuntimeError(last_error())
+            return ids, dists
         if allowed is not None:
             words, nbits = allow_bits(allowed)
             words, wp = _words_arg(words)
@@ -429,15 +455,20 @@ class Index:
         return ids, dists  # freshly allocated above (the reference returns copies of equally fresh arrays, bindings.py:521)
 
     def range_query(self, queries: npt.ArrayLike, radius: float,
-                    allowed=None) -> Tuple[List[npt.NDArray[np.int32]], List[npt.NDArray[np.float32]]]:
+                    allowed=None, layer: int = 0) -> Tuple[List[npt.NDArray[np.int32]], List[npt.NDArray[np.float32]]]:
         """bindings.py:523-597.  allowed: as for knn_query -- only those ids are results (hnsw_mi355x_range_query_filtered); where
-        the reference throws on an empty heap (radius < 0) RuntimeError carries its message."""
+        the reference throws on an empty heap (radius < 0) RuntimeError carries its message.  layer: as for knn_query
+        (hnsw_mi355x_range_query_at_layer)."""
         q = _as_2d_f32(queries, self.dim)
         n = int(q.shape[0])
         ids_pp = (ct.c_void_p * n)()
         dists_pp = (ct.c_void_p * n)()
         counts = (ct.c_int * n)()
-        if allowed is not None:
+        if layer != 0:
+            words, nbits = allow_bits(allowed) if allowed is not None else (None, 0)
+            words, wp = _words_arg(words) if allowed is not None else (None, None)
+            status = lib.hnsw_mi355x_range_query_at_layer(self._h, q.ctypes.data_as(_F), n, self.dim, radius, int(layer), wp, nbits, ids_pp, dists_pp, counts)
+        elif allowed is not None:
             words, nbits = allow_bits(allowed)
             words, wp = _words_arg(words)
             status = lib.hnsw_mi355x_range_query_filtered(self._h, q.ctypes.data_as(_F), n, self.dim, radius, wp, nbits, ids_pp, dists_pp, counts)
@@ -464,6 +495,27 @@ class Index:
         q = _as_2d_f32(queries, self.dim)
         if lib.hnsw_mi355x_set_queries(self._h, q.ctypes.data_as(_F), int(q.shape[0]), self.dim) < 0:
             raise RuntimeError(last_error())
+
+    def multilayer_knn_query(self, queries: npt.ArrayLike, k: int, max_layer=None, min_layer: int = 0):
+        """The C# MultiLayerKnnQuery for a batch of independent queries (hnsw_mi355x_multilayer_knn_query): (ids, dists) of shape
+        [nq, nlayers, k - 1], nlayers = min(top_layer(), max_layer) + 1 -- slot L holds layer L's neighbours in distance order without
+        the nearest one (it is the entry point of the layer below), -1 / NaN where a layer has fewer and in slots below min_layer."""
+        q = _as_2d_f32(queries, self.dim)
+        n = int(q.shape[0])
+        cap = max(self.top_layer() + 1, 1)
+        per = max(int(k) - 1, 0)
+        ids = np.full((n, cap, per), -1, dtype=np.int32)
+        dists = np.full((n, cap, per), np.nan, dtype=np.float32)
+        nl = lib.hnsw_mi355x_multilayer_knn_query(self._h, q.ctypes.data_as(_F), n, self.dim, int(k), 2 ** 31 - 1 if max_layer is None else int(max_layer),
+                                                  int(min_layer), cap, ids.ctypes.data_as(_I), dists.ctypes.data_as(_F))
+        if nl < 0:
+            raise RuntimeError(last_error())
+        return np.ascontiguousarray(ids[:, :nl]), np.ascontiguousarray(dists[:, :nl])
+
+    def top_layer(self) -> int:
+        """max_layer(entry_point): the highest layer of the graph (-1: empty index)."""
+        ep = self.entry_point
+        return self.max_layer(ep) if ep >= 0 else -1
 
     def knn_query_resident(self, k: int):
         n = int(lib.hnsw_mi355x_resident_count(self._h)) if self._h else 0  # asked, not remembered: knn_query / range_query replace the set
@@ -665,13 +717,20 @@ class DeviceBackend:
             self._check(lib.hnswdev_graph_set_layer(self._ctx, layer, c.ctypes.data_as(_I), e.ctypes.data_as(_I), e.shape[1]))
         self._check(lib.hnswdev_graph_commit(self._ctx))
 
-    def knn_search(self, queries, entry_point: int, k_beam: int, k_out: int, allowed=None):
-        """allowed: as for Index.knn_query (hnswdev_knn_search_filtered); None runs hnswdev_knn_search."""
+    def knn_search(self, queries, entry_point: int, k_beam: int, k_out: int, allowed=None, layer: int = 0):
+        """allowed: as for Index.knn_query (hnswdev_knn_search_filtered); None runs hnswdev_knn_search.  layer != 0:
+        hnswdev_knn_search_at_layer."""
         q = _as_2d_f32(queries, self.dim)
         n = q.shape[0]
         ids = np.empty((n, k_out), dtype=np.int32)
         d = np.empty((n, k_out), dtype=np.float32)
         flags = np.empty(n, dtype=np.int32)
+        if layer != 0:
+            words, nbits = allow_bits(allowed) if allowed is not None else (None, 0)
+            words, wp = _words_arg(words) if allowed is not None else (None, None)
+            self._check(lib.hnswdev_knn_search_at_layer(self._ctx, q.ctypes.data_as(_F), n, int(entry_point), int(k_beam), int(k_out), int(layer), wp, nbits,
+                                                        ids.ctypes.data_as(_I), d.ctypes.data_as(_F), flags.ctypes.data_as(_I)))
+            return ids, d, flags
         if allowed is not None:
             words, nbits = allow_bits(allowed)
             words, wp = _words_arg(words)
@@ -682,14 +741,35 @@ class DeviceBackend:
                                            ids.ctypes.data_as(_I), d.ctypes.data_as(_F), flags.ctypes.data_as(_I)))
         return ids, d, flags
 
-    def range_search(self, queries, entry_point: int, radius: float, allowed=None):
+    def multilayer_search(self, queries, entry_point: int, k: int, max_layer=None, min_layer: int = 0, layers_cap=None):
+        """hnswdev_multilayer_search: (ids, dists, flags), ids / dists of shape [nq, nlayers, k - 1] as Index.multilayer_knn_query;
+        flags[i] = 1: query i was handed back."""
+        q = _as_2d_f32(queries, self.dim)
+        n = q.shape[0]
+        cap = 64 if layers_cap is None else int(layers_cap)
+        per = max(int(k) - 1, 0)
+        ids = np.full((n, cap, per), -1, dtype=np.int32)
+        d = np.full((n, cap, per), np.nan, dtype=np.float32)
+        flags = np.zeros(n, dtype=np.int32)
+        nl = lib.hnswdev_multilayer_search(self._ctx, q.ctypes.data_as(_F), n, int(entry_point), int(k), 2 ** 31 - 1 if max_layer is None else int(max_layer),
+                                           int(min_layer), cap, ids.ctypes.data_as(_I), d.ctypes.data_as(_F), flags.ctypes.data_as(_I))
+        self._check(min(nl, 0))
+        return np.ascontiguousarray(ids[:, :nl]), np.ascontiguousarray(d[:, :nl]), flags
+
+    def range_search(self, queries, entry_point: int, radius: float, allowed=None, layer: int = 0):
         """Per query the ids / distances within `radius`, ascending by distance; flags[i] = 1: handed back (empty).
-        allowed: as for Index.knn_query (hnswdev_range_search_filtered); None runs hnswdev_range_search."""
+        allowed: as for Index.knn_query (hnswdev_range_search_filtered); None runs hnswdev_range_search.  layer != 0:
+        hnswdev_range_search_at_layer."""
         q = _as_2d_f32(queries, self.dim)
         n = q.shape[0]
         counts = np.zeros(n, dtype=np.int32)
         flags = np.zeros(n, dtype=np.int32)
-        if allowed is not None:
+        if layer != 0:
+            words, nbits = allow_bits(allowed) if allowed is not None else (None, 0)
+            words, wp = _words_arg(words) if allowed is not None else (None, None)
+            self._check(lib.hnswdev_range_search_at_layer(self._ctx, q.ctypes.data_as(_F), n, int(entry_point), float(radius), int(layer), wp, nbits,
+                                                          counts.ctypes.data_as(_I), flags.ctypes.data_as(_I)))
+        elif allowed is not None:
             words, nbits = allow_bits(allowed)
             words, wp = _words_arg(words)
             self._check(lib.hnswdev_range_search_filtered(self._ctx, q.ctypes.data_as(_F), n, int(entry_point), float(radius), wp, nbits,

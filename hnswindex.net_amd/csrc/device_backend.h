@@ -149,8 +149,13 @@ public:
     // search_queries with an allow-set (KnnQuery's filterFnc at layer 0, graph_search_filtered_kernel): a bitset of nbits bits over
     // ids, bit i = bit i & 31 of word i >> 5, ids >= nbits not allowed.  The descent is not filtered; a disallowed node is a
     // candidate but never a result.  The bitset is uploaded to this context for the call.  out_flag as search_batch (1: handed back).
+    // search_layer: KnnQuery's `layer` (the descent stops above it, the search reads that layer's lists).
     bool search_filtered(int nq, int entry, int entry_layer, int k, int k_out, const uint32_t *allow_bits, long long nbits, int *out_ids,
-                         float *out_d, int *out_flag);
+                         float *out_d, int *out_flag, int search_layer = 0);
+    // MultiLayerKnnQuery's chains (graph_multilayer_kernel): resident query i searched with beam k (>= 2) on every layer from
+    // first_layer (<= entry_layer) down to min_layer, each step entering at the nearest result of the one before.
+    // out_ids / out_d: [nq][first_layer + 1][k - 1], padded; out_flag[i] = 1: handed back whole.
+    bool multilayer_search(int nq, int entry, int entry_layer, int first_layer, int min_layer, int k, int *out_ids, float *out_d, int *out_flag);
     // Remove, second half, for the `n` affected nodes of one (removed node, layer) step (graph_relink_kernel): per node
     // the new neighbour selection out_sel[i * sel_stride ..][0 .. out_cnt[i]); out_flag[i] = 1: this node's answer
     // depends on the heap-array order of the candidates (the caller repeats the step on the lock-step path).
@@ -238,11 +243,15 @@ public:
     bool graph_begin(int n, int max_edges, const int *levels);
     bool graph_set_layer(int layer, const int *counts, const int *edges, int stride);
     bool graph_commit();
-    bool knn_search(const float *queries, int nq, int entry_point, int k_beam, int k_out, int *out_ids, float *out_d, int *out_flag);
+    bool knn_search(const float *queries, int nq, int entry_point, int k_beam, int k_out, int *out_ids, float *out_d, int *out_flag, int layer = 0);
     bool knn_search_filtered(const float *queries, int nq, int entry_point, int k_beam, int k_out, const uint32_t *allow_bits, long long nbits,
-                             int *out_ids, float *out_d, int *out_flag);
+                             int *out_ids, float *out_d, int *out_flag, int layer = 0);
+    // hnswdev_multilayer_search: the slot count, or -1
+    int multilayer_search_abi(const float *queries, int nq, int entry_point, int k, int max_layer, int min_layer, int layers_cap, int *out_ids,
+                              float *out_d, int *out_flag);
     // RangeQuery on the device (graph_range_kernel): per job the results within `range`, UNSORTED, at
-    // found[off[i] .. off[i] + cnt[i]); flag[i] = 1: handed back (cnt 0).  jobs[].qref must name a resident query.
+    // found[off[i] .. off[i] + cnt[i]); flag[i] = 1: handed back (cnt 0).  jobs[].qref must name a resident query; the jobs of
+    // a call share one search_layer (RangeQuery's `layer`).
     struct RangeResults {
         std::vector<unsigned long long> off;
         std::vector<int> cnt, flag, entry; // entry[i]: the layer-0 entry node FindEntryPointQuery reached
@@ -260,7 +269,7 @@ public:
     // ... with an allow-set (ids >= nbits not allowed); false with "System.InvalidOperationException: Heap is empty" where the
     // reference throws (range_replay.h)
     bool range_search_filtered(const float *queries, int nq, int entry_point, float range, const uint32_t *allow_bits, long long nbits,
-                               int *out_counts, int *out_flags);
+                               int *out_counts, int *out_flags, int layer = 0);
     bool range_results(int *out_ids, float *out_d);
 
     void set_profiling(bool on) { profiling_ = on; }
@@ -282,6 +291,7 @@ private:
     std::mutex mu_, err_mu_;
     std::string err_;
     bool bind();
+    bool abi_layer_ok(const char *who, int entry_point, int layer);
     int device_ = 0, dim_ = 0, metric_ = 0;
     int pitch_ = 0; // 32-bit words per stored row / resident query (== dim_ for the float metrics; the int8 record otherwise)
     float *q_stage_ = nullptr; // int8: float staging area on the device (quantise on upload, dequantise on download)

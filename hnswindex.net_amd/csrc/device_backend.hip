@@ -175,6 +175,10 @@ HNSW_FOR_EACH_FILTERED(HNSW_DEFINE_FILTERED, M_SQ)
 HNSW_FOR_EACH_FILTERED(HNSW_DEFINE_FILTERED, M_COS)
 HNSW_FOR_EACH_FILTERED(HNSW_DEFINE_FILTERED, M_UCOS)
 HNSW_FOR_EACH_FILTERED(HNSW_DEFINE_FILTERED, M_I8)
+HNSW_FOR_EACH_MULTILAYER(HNSW_DEFINE_MULTILAYER, M_SQ)
+HNSW_FOR_EACH_MULTILAYER(HNSW_DEFINE_MULTILAYER, M_COS)
+HNSW_FOR_EACH_MULTILAYER(HNSW_DEFINE_MULTILAYER, M_UCOS)
+HNSW_FOR_EACH_MULTILAYER(HNSW_DEFINE_MULTILAYER, M_I8)
 #else
 HNSW_FOR_EACH_TRAVERSAL(HNSW_DECLARE_TRAVERSAL, M_SQ)
 HNSW_FOR_EACH_TRAVERSAL(HNSW_DECLARE_TRAVERSAL, M_COS)
@@ -192,6 +196,10 @@ HNSW_FOR_EACH_FILTERED(HNSW_DECLARE_FILTERED, M_SQ)
 HNSW_FOR_EACH_FILTERED(HNSW_DECLARE_FILTERED, M_COS)
 HNSW_FOR_EACH_FILTERED(HNSW_DECLARE_FILTERED, M_UCOS)
 HNSW_FOR_EACH_FILTERED(HNSW_DECLARE_FILTERED, M_I8)
+HNSW_FOR_EACH_MULTILAYER(HNSW_DECLARE_MULTILAYER, M_SQ)
+HNSW_FOR_EACH_MULTILAYER(HNSW_DECLARE_MULTILAYER, M_COS)
+HNSW_FOR_EACH_MULTILAYER(HNSW_DECLARE_MULTILAYER, M_UCOS)
+HNSW_FOR_EACH_MULTILAYER(HNSW_DECLARE_MULTILAYER, M_I8)
 #endif
 
 // ------------------------------------------------------------------------------------
@@ -1897,11 +1905,12 @@ bool Device::search_batch_impl(const SearchJob *jobs, int njobs, int k, int k_ou
 // cover graph ids travel: bits of ids >= min(nbits, graph nodes) are never read.  A set that allows no graph id pads every
 // row without a launch (the result is empty whatever the order).
 bool Device::search_filtered(int nq, int entry, int entry_layer, int k, int k_out, const uint32_t *allow_bits, long long nbits, int *out_ids,
-                             float *out_d, int *out_flag)
+                             float *out_d, int *out_flag, int search_layer)
 {
     if (nq <= 0) return true;
     if (!out_ids || !out_d || !out_flag || k < 1 || k_out < 1 || nbits < 0 || (!allow_bits && nbits > 0)) { set_dev_error("search_filtered: bad argument"); return false; }
     if (g_n_ <= 0) { set_dev_error("search_filtered: no graph uploaded"); return false; }
+    if (search_layer < 0 || search_layer > entry_layer) { set_dev_error("search_filtered: the search layer must lie between 0 and the entry point's top layer"); return false; }
     if (!(entry >= 0 && entry < g_n_ && entry_layer >= 0 && nq <= n_queries_) || tail_.n > 0) {
         set_dev_error("search_filtered: entry point outside the graph, or fewer resident queries than asked for");
         return false;
@@ -1952,8 +1961,8 @@ bool Device::search_filtered(int nq, int entry, int entry_layer, int k, int k_ou
         if (timed) HIP_OK(hipEventRecord((hipEvent_t)ev0_, st));
         tl.grid = std::min(nj, tl.slots);
         hipLaunchKernelGGL(kernel, dim3(tl.grid), dim3(tl.block), tl.lds_total, st, d_rows_, d_row_sn_, d_queries_ + (size_t)off * pitch_,
-                           d_q_sn_ ? d_q_sn_ + off : nullptr, pitch_, g_adj0_, g_stride0_, g_upper_, g_pool_, g_strideU_, entry, entry_layer, k, cand_cap,
-                           reinterpret_cast<ND *>(s_fspill_), fspill, s_visited_, tl.vis.words, tl.vis.tab, tl.vis.tab_cap,
+                           d_q_sn_ ? d_q_sn_ + off : nullptr, pitch_, g_adj0_, g_stride0_, g_upper_, g_pool_, g_strideU_, entry, entry_layer, search_layer, k,
+                           cand_cap, reinterpret_cast<ND *>(s_fspill_), fspill, s_visited_, tl.vis.words, tl.vis.tab, tl.vis.tab_cap,
                            reinterpret_cast<const unsigned *>(s_allow_), n_allow, k_out, d_ids, d_d, s_flag_, s_evals_, nbcap(), nj, s_jobctr_);
         HIP_OK(hipGetLastError());
         if (timed) HIP_OK(hipEventRecord((hipEvent_t)ev1_, st));
@@ -1968,6 +1977,77 @@ bool Device::search_filtered(int nq, int entry, int entry_layer, int k, int k_ou
         if (!count_launch(nullptr, *h_ev, tl.vis.tab != nullptr, timed, ev0_, ev1_)) return false;
     }
     for (int i = 0; i < nq; ++i) stats_.search_overflows += (uint64_t)(out_flag[i] == 1);
+    return true;
+}
+
+// MultiLayerKnnQuery's chains (graph_multilayer_kernel): resident query i from (entry, entry_layer), searched on every layer from
+// first_layer down to min_layer with beam k, each step entering at the one before's nearest result.  out_ids / out_d:
+// [nq][first_layer + 1][k - 1], slots below min_layer padded; out_flag[i] = 1: the job is handed back (the caller redoes it).
+bool Device::multilayer_search(int nq, int entry, int entry_layer, int first_layer, int min_layer, int k, int *out_ids, float *out_d, int *out_flag)
+{
+    if (nq <= 0) return true;
+    if (!out_ids || !out_d || !out_flag || k < 2) { set_dev_error("multilayer_search: bad argument"); return false; }
+    if (g_n_ <= 0) { set_dev_error("multilayer_search: no graph uploaded"); return false; }
+    if (!(entry >= 0 && entry < g_n_ && nq <= n_queries_) || tail_.n > 0) {
+        set_dev_error("multilayer_search: entry point outside the graph, or fewer resident queries than asked for");
+        return false;
+    }
+    if (!(min_layer >= 0 && min_layer <= first_layer && first_layer <= entry_layer && entry_layer < 0x4000)) {
+        set_dev_error("multilayer_search: layers must satisfy 0 <= min_layer <= first_layer <= the entry point's top layer");
+        return false;
+    }
+    const int per = k - 1, nslots = first_layer + 1;
+    const size_t row = (size_t)nslots * (size_t)per; // results of one job
+    const int cand_cap = cand_lds_cap(k, pitch_, false, nbcap());
+    const size_t lds = search_lds_bytes(k, cand_cap, pitch_, false, nbcap());
+    if (lds > 64 * 1024) { set_dev_error("multilayer_search: beam width / dimension exceed the LDS budget"); return false; }
+    if (!bind()) return false;
+    hipStream_t st = S(stream_);
+    const long long chunk = std::max<long long>(1, std::min<long long>(nq, (long long)((size_t)(1 << 24) / row)));
+    TraversalLaunch tl;
+    if (!plan_traversal(false, k, true, lds, &tl)) return false;
+    const bool hashed = tl.vis.tab != nullptr;
+    decltype(&graph_multilayer_kernel<M_SQ, false>) kernel = nullptr;
+    with_metric(metric_, [&](auto m) { kernel = hashed ? &graph_multilayer_kernel<m, true> : &graph_multilayer_kernel<m, false>; });
+    const int slots = std::min(max_slots(), resident_blocks(kernel, lds, num_cu_));
+    if (slots < 1) { set_dev_error("multilayer_search: the kernel does not fit the device"); return false; }
+    if (!ensure_search_scratch(chunk, max_slots(), (int)row, tl.vis.bytes_per_job)) return false;
+    const int spill_cap = spill_cap_for_tests();
+    // pinned layout: [evals (16 B) | ids | dists | flags]
+    const size_t b_res = 4u * (size_t)chunk * row;
+    char *hs = static_cast<char *>(pinned_stage(16 + 2 * b_res + 4u * (size_t)chunk));
+    if (!hs) return false;
+    unsigned long long *h_ev = reinterpret_cast<unsigned long long *>(hs);
+    int *h_ids = reinterpret_cast<int *>(hs + 16);
+    float *h_d = reinterpret_cast<float *>(hs + 16 + b_res);
+    int *h_flag = reinterpret_cast<int *>(hs + 16 + 2 * b_res);
+    int *d_ids = reinterpret_cast<int *>(s_hits_);
+    float *d_d = reinterpret_cast<float *>(s_hits_) + (size_t)chunk * row;
+    for (long long off = 0; off < nq; off += chunk) {
+        const int nj = (int)std::min<long long>(chunk, nq - off);
+        HIP_OK(hipMemsetAsync(s_jobctr_, 0, sizeof(int) * 4, st));
+        HIP_OK(hipMemsetAsync(s_evals_, 0, sizeof(unsigned long long), st));
+        const bool timed = profiling_;
+        if (timed) HIP_OK(hipEventRecord((hipEvent_t)ev0_, st));
+        hipLaunchKernelGGL(kernel, dim3(std::min(nj, slots)), dim3(64), lds, st, d_rows_, d_row_sn_, d_queries_ + (size_t)off * pitch_,
+                           d_q_sn_ ? d_q_sn_ + off : nullptr, pitch_, g_adj0_, g_stride0_, g_upper_, g_pool_, g_strideU_, entry, entry_layer, first_layer,
+                           min_layer, k, cand_cap, reinterpret_cast<ND *>(s_spill_), spill_cap, s_visited_, tl.vis.words, tl.vis.tab, tl.vis.tab_cap, d_ids,
+                           d_d, s_flag_, s_evals_, nbcap(), nj, s_jobctr_);
+        HIP_OK(hipGetLastError());
+        if (timed) HIP_OK(hipEventRecord((hipEvent_t)ev1_, st));
+        HIP_OK(hipMemcpyAsync(h_ids, d_ids, 4u * (size_t)nj * row, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(h_d, d_d, 4u * (size_t)nj * row, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(h_flag, s_flag_, sizeof(int) * (size_t)nj, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(h_ev, s_evals_, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+        memcpy(out_ids + (size_t)off * row, h_ids, 4u * (size_t)nj * row);
+        memcpy(out_d + (size_t)off * row, h_d, 4u * (size_t)nj * row);
+        memcpy(out_flag + off, h_flag, sizeof(int) * (size_t)nj);
+        if (!count_launch(nullptr, *h_ev, hashed, timed, ev0_, ev1_)) return false;
+        stats_.multilayer_launches += 1;
+    }
+    stats_.multilayer_jobs += (uint64_t)nq;
+    for (int i = 0; i < nq; ++i) stats_.multilayer_handbacks += (uint64_t)(out_flag[i] != 0);
     return true;
 }
 
@@ -2096,8 +2176,10 @@ bool Device::range_batch(const SearchJob *jobs, int njobs, float range, RangeRes
     if (g_n_ <= 0) { set_dev_error("range_batch: no graph uploaded"); return false; }
     if (!jobs_valid(jobs, njobs, g_n_, n_queries_, n_rows_hw_)) { set_dev_error("range_batch: job outside the uploaded graph / rows / queries"); return false; }
     if (filtered && nbits < 0) { set_dev_error("range_batch: bad argument"); return false; }
+    const int layer = jobs[0].search_layer; // RangeQuery's `layer`: one per call (the replay kernels walk that layer's lists)
     for (int i = 0; i < njobs; ++i)
-        if (jobs[i].qref < 0 || jobs[i].search_layer != 0) { set_dev_error("range_batch: jobs must name a resident query and layer 0"); return false; }
+        if (jobs[i].qref < 0 || jobs[i].search_layer != layer) { set_dev_error("range_batch: jobs must name a resident query and one search layer"); return false; }
+    if (layer >= 0x4000) { set_dev_error("range_batch: bad argument"); return false; }
     const int nbcap_r = kRangeFan * nbcap(); // the kernel expands kRangeFan lists per step
     const size_t lds = search_lds_bytes(0, 0, pitch_, false, nbcap_r);
     if (lds > 64 * 1024) { set_dev_error("range_batch: dimension exceeds the LDS budget"); return false; }
@@ -2160,7 +2242,8 @@ bool Device::range_batch(const SearchJob *jobs, int njobs, float range, RangeRes
         const bool timed = profiling_;
         if (timed) HIP_OK(hipEventRecord((hipEvent_t)ev0_, st));
         with_metric(metric_, [&](auto m) {
-            const auto kernel = vis.tab ? &graph_range_kernel<m, true> : &graph_range_kernel<m, false>;
+            const auto kernel = layer != 0 ? (vis.tab ? &graph_range_kernel<m, true, true> : &graph_range_kernel<m, false, true>)
+                                           : (vis.tab ? &graph_range_kernel<m, true> : &graph_range_kernel<m, false>);
             const int slots = std::min(std::min(max_slots(), grid_cap), resident_blocks(kernel, lds, num_cu_));
             hipLaunchKernelGGL(kernel, dim3(std::min<int>(nj, slots)), dim3(64), lds, st, d_rows_, d_row_sn_, d_queries_, d_q_sn_, pitch_, g_adj0_,
                                g_stride0_, g_upper_, g_pool_, g_strideU_, s_jobs_, range, lists, list_cap, s_visited_, vis.words, vis.tab, vis.tab_cap,
@@ -2191,10 +2274,10 @@ bool Device::range_batch(const SearchJob *jobs, int njobs, float range, RangeRes
         if (finish >= 2) {
             if (filtered)
                 hipLaunchKernelGGL(range_replay_filtered_kernel, replay_grid, dim3(64), sizeof(RangeReplayLds) + 64, st, reinterpret_cast<ND *>(s_arena_), s_roff_,
-                                   s_cnt_, s_rentry_, g_adj0_, g_stride0_, g_n_, range, s_rstate_, s_rtied_, s_rfin_ctr_ + 1, s_rres_);
+                                   s_cnt_, s_rentry_, g_adj0_, g_stride0_, g_upper_, g_pool_, g_strideU_, layer, g_n_, range, s_rstate_, s_rtied_, s_rfin_ctr_ + 1, s_rres_);
             else
                 hipLaunchKernelGGL(range_replay_kernel, replay_grid, dim3(64), sizeof(RangeReplayLds) + 64, st, reinterpret_cast<ND *>(s_arena_), s_roff_,
-                                   s_cnt_, s_rentry_, g_adj0_, g_stride0_, g_n_, range, s_rstate_, s_rtied_, s_rfin_ctr_ + 1);
+                                   s_cnt_, s_rentry_, g_adj0_, g_stride0_, g_upper_, g_pool_, g_strideU_, layer, g_n_, range, s_rstate_, s_rtied_, s_rfin_ctr_ + 1);
             HIP_OK(hipGetLastError());
         }
         if (timed) HIP_OK(hipEventRecord((hipEvent_t)ev1_, st));
@@ -2311,22 +2394,35 @@ bool Device::range_search(const float *queries, int nq, int entry_point, float r
     return range_search_filtered(queries, nq, entry_point, range, nullptr, 0, out_counts, out_flags);
 }
 
+// A layer the committed graph has, as seen from the entry point (the reference indexes OutEdges[layer] of nodes reached from it)
+bool Device::abi_layer_ok(const char *who, int entry_point, int layer)
+{
+    if (layer >= 0 && layer <= hg_->level[(size_t)entry_point]) return true;
+    set_dev_error(std::string(who) + ": layer " + std::to_string(layer) + " outside 0 .. " + std::to_string(hg_->level[(size_t)entry_point]) +
+                  " (the entry point's top layer)");
+    return false;
+}
+
 // allow_bits == nullptr: no filter (range_search)
 bool Device::range_search_filtered(const float *queries, int nq, int entry_point, float range, const uint32_t *allow_bits, long long nbits,
-                                   int *out_counts, int *out_flags)
+                                   int *out_counts, int *out_flags, int layer)
 {
     abi_range_.clear();
     if (nq <= 0) return true;
     if (!out_counts || !out_flags) { set_dev_error("range_search: null argument"); return false; }
     if (!hg_ || g_n_ <= 0) { set_dev_error("range_search: no graph committed"); return false; }
     if (entry_point < 0 || entry_point >= hg_->n || (allow_bits && nbits < 0)) { set_dev_error("range_search: bad argument"); return false; }
+    if (!abi_layer_ok("range_search", entry_point, layer)) return false;
     if (!set_queries(queries, nq)) return false;
     std::vector<SearchJob> jobs((size_t)nq);
     const int top = hg_->level[(size_t)entry_point];
-    for (int i = 0; i < nq; ++i) jobs[(size_t)i] = SearchJob{i, entry_point, top, 0, -1};
+    for (int i = 0; i < nq; ++i) jobs[(size_t)i] = SearchJob{i, entry_point, top, layer, -1};
     RangeResults r;
     if (!range_batch(jobs.data(), nq, range, &r, allow_bits, nbits)) return false;
-    const auto list_of = [&](int id) { return hg_->adj0.data() + (size_t)id * (size_t)hg_->stride0; };
+    const auto list_of = [&](int id) {
+        return layer == 0 ? hg_->adj0.data() + (size_t)id * (size_t)hg_->stride0
+                          : hg_->pool.data() + hg_->upper[(size_t)id] + (size_t)(layer - 1) * (size_t)hg_->strideU;
+    };
     for (int i = 0; i < nq; ++i) {
         out_counts[i] = 0;
         out_flags[i] = r.flag[(size_t)i];
@@ -2420,27 +2516,58 @@ bool Device::graph_commit()
     return set_graph(g.adj0.data(), g.n, g.stride0, g.level.data(), g.upper.data(), g.pool.data(), (long long)g.pool.size(), g.strideU);
 }
 
-bool Device::knn_search(const float *queries, int nq, int entry_point, int k_beam, int k_out, int *out_ids, float *out_d, int *out_flag)
+bool Device::knn_search(const float *queries, int nq, int entry_point, int k_beam, int k_out, int *out_ids, float *out_d, int *out_flag, int layer)
 {
     if (nq <= 0) return true;
     if (!hg_ || g_n_ <= 0) { set_dev_error("knn_search: no graph committed"); return false; }
     if (entry_point < 0 || entry_point >= hg_->n || k_out < 1 || k_beam < k_out) { set_dev_error("knn_search: bad argument"); return false; }
+    if (!abi_layer_ok("knn_search", entry_point, layer)) return false;
     if (!set_queries(queries, nq)) return false;
     std::vector<SearchJob> jobs((size_t)nq);
     const int top = hg_->level[(size_t)entry_point];
-    for (int i = 0; i < nq; ++i) jobs[(size_t)i] = SearchJob{i, entry_point, top, 0, -1};
+    for (int i = 0; i < nq; ++i) jobs[(size_t)i] = SearchJob{i, entry_point, top, layer, -1};
     return search_batch(jobs.data(), nq, k_beam, k_out, out_ids, out_d, out_flag);
 }
 
+int Device::multilayer_search_abi(const float *queries, int nq, int entry_point, int k, int max_layer, int min_layer, int layers_cap, int *out_ids,
+                                  float *out_d, int *out_flag)
+{
+    if (max_layer < -1 || min_layer < 0) { set_dev_error("multilayer_search: max_layer must be >= -1 and min_layer >= 0"); return -1; }
+    if (nq <= 0 || k < 1 || max_layer == -1) return 0;
+    if (!hg_ || g_n_ <= 0) { set_dev_error("multilayer_search: no graph committed"); return -1; }
+    if (entry_point < 0 || entry_point >= hg_->n) { set_dev_error("multilayer_search: bad argument"); return -1; }
+    const int top = hg_->level[(size_t)entry_point], first = std::min(top, max_layer), nslots = first + 1;
+    if (layers_cap < nslots) { set_dev_error("multilayer_search: layers_cap " + std::to_string(layers_cap) + " is too small, " + std::to_string(nslots) + " layer slots are needed"); return -1; }
+    if (k == 1) return nslots;
+    if (!out_ids || !out_d || !out_flag) { set_dev_error("multilayer_search: null argument"); return -1; }
+    const size_t per = (size_t)(k - 1);
+    for (int i = 0; i < nq; ++i) {
+        out_flag[i] = 0;
+        for (size_t j = 0; j < (size_t)nslots * per; ++j) { out_ids[(size_t)i * layers_cap * per + j] = -1; out_d[(size_t)i * layers_cap * per + j] = std::numeric_limits<float>::quiet_NaN(); }
+    }
+    if (min_layer > first) return nslots;
+    if (!set_queries(queries, nq)) return -1;
+    if (layers_cap == nslots) return multilayer_search(nq, entry_point, top, first, min_layer, k, out_ids, out_d, out_flag) ? nslots : -1;
+    std::vector<int> ids((size_t)nq * nslots * per);
+    std::vector<float> ds(ids.size());
+    if (!multilayer_search(nq, entry_point, top, first, min_layer, k, ids.data(), ds.data(), out_flag)) return -1;
+    for (int i = 0; i < nq; ++i) {
+        memcpy(out_ids + (size_t)i * layers_cap * per, ids.data() + (size_t)i * nslots * per, sizeof(int) * nslots * per);
+        memcpy(out_d + (size_t)i * layers_cap * per, ds.data() + (size_t)i * nslots * per, sizeof(float) * nslots * per);
+    }
+    return nslots;
+}
+
 bool Device::knn_search_filtered(const float *queries, int nq, int entry_point, int k_beam, int k_out, const uint32_t *allow_bits, long long nbits,
-                                 int *out_ids, float *out_d, int *out_flag)
+                                 int *out_ids, float *out_d, int *out_flag, int layer)
 {
     if (!allow_bits || nbits < 0) { set_dev_error("knn_search_filtered: allow_bits must not be NULL and nbits must be >= 0"); return false; }
     if (nq <= 0) return true;
     if (!hg_ || g_n_ <= 0) { set_dev_error("knn_search_filtered: no graph committed"); return false; }
     if (entry_point < 0 || entry_point >= hg_->n || k_out < 1 || k_beam < k_out) { set_dev_error("knn_search_filtered: bad argument"); return false; }
+    if (!abi_layer_ok("knn_search_filtered", entry_point, layer)) return false;
     if (!set_queries(queries, nq)) return false;
-    return search_filtered(nq, entry_point, hg_->level[(size_t)entry_point], k_beam, k_out, allow_bits, nbits, out_ids, out_d, out_flag);
+    return search_filtered(nq, entry_point, hg_->level[(size_t)entry_point], k_beam, k_out, allow_bits, nbits, out_ids, out_d, out_flag, layer);
 }
 
 // ---- synchronous conveniences behind the C ABI ---------------------------------------
@@ -2637,6 +2764,26 @@ DEV_API int hnswdev_range_search_filtered(void *ctx, const float *queries, int n
     CTX_OR_FAIL();
     if (!allow_bits || nbits < 0) { hnsw::set_dev_error("hnswdev_range_search_filtered: allow_bits must not be NULL and nbits must be >= 0"); return -1; }
     return d->range_search_filtered(queries, nq, entry_point, range, allow_bits, nbits, out_counts, out_flags) ? 0 : -1;
+}
+DEV_API int hnswdev_knn_search_at_layer(void *ctx, const float *queries, int nq, int entry_point, int k_beam, int k_out, int layer,
+                                        const uint32_t *allow_bits, long long nbits, int *out_ids, float *out_dists, int *out_flags)
+{
+    CTX_OR_FAIL();
+    if (!allow_bits) return d->knn_search(queries, nq, entry_point, k_beam, k_out, out_ids, out_dists, out_flags, layer) ? 0 : -1;
+    return d->knn_search_filtered(queries, nq, entry_point, k_beam, k_out, allow_bits, nbits, out_ids, out_dists, out_flags, layer) ? 0 : -1;
+}
+DEV_API int hnswdev_range_search_at_layer(void *ctx, const float *queries, int nq, int entry_point, float range, int layer, const uint32_t *allow_bits,
+                                          long long nbits, int *out_counts, int *out_flags)
+{
+    CTX_OR_FAIL();
+    if (allow_bits && nbits < 0) { hnsw::set_dev_error("hnswdev_range_search_at_layer: nbits must be >= 0"); return -1; }
+    return d->range_search_filtered(queries, nq, entry_point, range, allow_bits, allow_bits ? nbits : 0, out_counts, out_flags, layer) ? 0 : -1;
+}
+DEV_API int hnswdev_multilayer_search(void *ctx, const float *queries, int nq, int entry_point, int k, int max_layer, int min_layer, int layers_cap,
+                                      int *out_ids, float *out_dists, int *out_flags)
+{
+    CTX_OR_FAIL();
+    return d->multilayer_search_abi(queries, nq, entry_point, k, max_layer, min_layer, layers_cap, out_ids, out_dists, out_flags);
 }
 DEV_API int hnswdev_range_results(void *ctx, int *out_ids, float *out_dists) { CTX_OR_FAIL(); return d->range_results(out_ids, out_dists) ? 0 : -1; }
 DEV_API int hnswdev_sync(void *ctx) { CTX_OR_FAIL(); return d->sync() ? 0 : -1; }

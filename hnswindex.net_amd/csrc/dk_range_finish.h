@@ -11,6 +11,7 @@
 // kRangeSortMax entries, a -0 distance (key order is not float.CompareTo order there), the lock-step mode.
 #pragma once
 #include "dk_heaps.h"
+#include "dk_search_common.h"
 
 namespace hnsw {
 
@@ -179,7 +180,8 @@ struct RangeReplayLds {
 // ARRAY, stably ranked by key, is the reference's answer and overwrites the list in the arena; state[job] = kRangeFinal.
 __global__ void __launch_bounds__(64)
 range_replay_kernel(ND *__restrict__ arena, const unsigned long long *__restrict__ off, const int *__restrict__ cnt, const int *__restrict__ entry,
-                    const int *__restrict__ adj0, int stride0, long long n_nodes, float range, int *__restrict__ state,
+                    const int *__restrict__ adj0, int stride0, const int64_t *__restrict__ upper, const int *__restrict__ pool, int strideU, int layer,
+                    long long n_nodes, float range, int *__restrict__ state,
                     const int *__restrict__ tied, int *__restrict__ job_counter)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -256,7 +258,7 @@ range_replay_kernel(ND *__restrict__ arena, const unsigned long long *__restrict
             }
             first = false;
             if (node < 0 || (long long)node >= n_nodes) break; // (guard: ids come from the graph the list was found on)
-            const int *l = adj0 + (size_t)node * stride0;
+            const int *l = GraphView{adj0, stride0, upper, pool, strideU}.list(node, layer); // the lists the closure was found on (RangeQuery's `layer`)
             const int n = __builtin_amdgcn_readfirstlane(l[0]);
             for (int base = 0; base < n; base += 64) {                   // :294
                 const int i = base + lane;
@@ -302,7 +304,8 @@ range_replay_kernel(ND *__restrict__ arena, const unsigned long long *__restrict
 // is never beyond range, :310.)
 __global__ void __launch_bounds__(64)
 range_replay_filtered_kernel(ND *__restrict__ arena, const unsigned long long *__restrict__ off, const int *__restrict__ cnt, const int *__restrict__ entry,
-                             const int *__restrict__ adj0, int stride0, long long n_nodes, float range, int *__restrict__ state,
+                             const int *__restrict__ adj0, int stride0, const int64_t *__restrict__ upper, const int *__restrict__ pool, int strideU, int layer,
+                    long long n_nodes, float range, int *__restrict__ state,
                              const int *__restrict__ tied, int *__restrict__ job_counter, const int *__restrict__ res)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -382,7 +385,7 @@ range_replay_filtered_kernel(ND *__restrict__ arena, const unsigned long long *_
             }
             first = false;
             if (node < 0 || (long long)node >= n_nodes) break; // (guard: ids come from the graph the list was found on)
-            const int *l = adj0 + (size_t)node * stride0;
+            const int *l = GraphView{adj0, stride0, upper, pool, strideU}.list(node, layer); // the lists the closure was found on (RangeQuery's `layer`)
             const int n = __builtin_amdgcn_readfirstlane(l[0]);
             for (int base = 0; base < n; base += 64) {                   // :294
                 const int i = base + lane;

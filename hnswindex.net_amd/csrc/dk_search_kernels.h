@@ -328,8 +328,8 @@ graph_search_kernel(const float *__restrict__ rows, const double *__restrict__ r
     if constexpr (LAT) port.post(-1, 0, lane); // the memory wave leaves
 }
 
-// KnnQuery with an allow-set (HNSWIndex.KnnQuery(query, k, filterFnc), HNSWIndex.cs:107-124, at layer 0): FindEntryPointQuery
-// unfiltered, then SearchLayerQuery with the filter (GraphNavigator.cs:194-256) in the exact two-heap traversal -- the sorted-list
+// KnnQuery with an allow-set (HNSWIndex.KnnQuery(query, k, filterFnc, layer), HNSWIndex.cs:107-124): FindEntryPointQuery down to
+// search_layer (exclusive), unfiltered, then SearchLayerQuery with the filter (GraphNavigator.cs:194-256) in the exact two-heap traversal -- the sorted-list
 // forms cannot carry it: a disallowed node is a candidate that is never a result, and the result list no longer holds the live
 // candidates -- and the stable Take(k_out).  Persistent like graph_range_kernel: one wave per job, jobs from a
 // counter; job i is resident query i from (entry, entry_layer).  Each wave owns one visited set and one spill area of spill_cap
@@ -341,8 +341,8 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(HNSW_WA
 graph_search_filtered_kernel(const float *__restrict__ rows, const double *__restrict__ row_sn, const float *__restrict__ queries,
                              const double *__restrict__ q_sn, int dim, const int *__restrict__ adj0, int stride0,
                              const int64_t *__restrict__ upper, const int *__restrict__ pool, int strideU, int entry, int entry_layer,
-                             int k, int cand_cap, ND *__restrict__ spill, int spill_cap, unsigned *__restrict__ visited, long long vis_words,
-                             int *__restrict__ vis_tab, int vis_tab_cap, const unsigned *__restrict__ allow_bits, long long allow_n, int k_out,
+                             int search_layer, int k, int cand_cap, ND *__restrict__ spill, int spill_cap, unsigned *__restrict__ visited,
+                             long long vis_words, int *__restrict__ vis_tab, int vis_tab_cap, const unsigned *__restrict__ allow_bits, long long allow_n, int k_out,
                              int *__restrict__ out_ids, float *__restrict__ out_d, int *__restrict__ out_flag,
                              unsigned long long *__restrict__ eval_counter, int nbcap, int njobs, int *__restrict__ job_counter)
 {
@@ -359,7 +359,7 @@ graph_search_filtered_kernel(const float *__restrict__ rows, const double *__res
         if (lane == 0) job = atomicAdd(job_counter, 1);
         job = __builtin_amdgcn_readfirstlane(job);
         if (job >= njobs) break;
-        const SearchJob jb{job, entry, entry_layer, 0, -1, 0};
+        const SearchJob jb{job, entry, entry_layer, search_layer, -1, 0};
         const float *q = queries + (size_t)job * dim;
         double sb = 0.0;
         if (METRIC == M_COS) sb = q_sn[job];
@@ -381,16 +381,126 @@ graph_search_filtered_kernel(const float *__restrict__ rows, const double *__res
 #define HNSW_FILTERED_SIGNATURE(PREFIX, M, H)                                                                                       \
     PREFIX template __global__ void graph_search_filtered_kernel<M, H>(                                                             \
         const float *__restrict__, const double *__restrict__, const float *__restrict__, const double *__restrict__, int,      \
-        const int *__restrict__, int, const int64_t *__restrict__, const int *__restrict__, int, int, int, int, int, ND *__restrict__, \
+        const int *__restrict__, int, const int64_t *__restrict__, const int *__restrict__, int, int, int, int, int, int, ND *__restrict__, \
         int, unsigned *__restrict__, long long, int *__restrict__, int, const unsigned *__restrict__, long long, int, int *__restrict__, \
         float *__restrict__, int *__restrict__, unsigned long long *__restrict__, int, int, int *__restrict__);
 #define HNSW_FOR_EACH_FILTERED(X, M) X(M, false) X(M, true)
 #define HNSW_DECLARE_FILTERED(M, H) HNSW_FILTERED_SIGNATURE(extern, M, H)
 #define HNSW_DEFINE_FILTERED(M, H) HNSW_FILTERED_SIGNATURE(, M, H)
 
+// MultiLayerKnnQuery (HNSWIndex.cs:173-187), one job = one query's whole chain.  The first step is FindEntryPointQuery from
+// (entry, entry_layer) down to first_layer = min(top, maxLayer) (exclusive) and SearchLayerQuery there; every later step searches
+// the next layer down from the previous step's NEAREST result (entry_layer == search_layer: no descent), to min_layer.  Each step
+// has beam k (not max(MinNN, k)), no filter and a fresh visited list: the wave clears its set between steps.  A step's results are
+// the heap array in stable distance order (take_stable's rule): rank 0 is the next entry -- read lane-uniformly from LDS -- and
+// ranks 1 .. k - 1 go to slot [job][layer][0 .. k - 1) of the output (nslots = first_layer + 1 slots per job, k - 1 >= 1 entries
+// each, padded with -1 / NaN; slots below min_layer are padding).  The exact two-heap traversal runs every step: the heap ARRAY
+// decides which of two equally near results leads.  Persistent like graph_search_filtered_kernel (one wave per job, jobs from a
+// counter, the query staged in LDS once per job).  out_flag: 0 done, 1 the whole job is handed back (a step met a NaN / -0
+// distance, a full candidate heap or a crowded visited table; the host redoes it from the start and rewrites its slots).
+template <int METRIC, bool HASHED>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(HNSW_WAVES(3))))
+graph_multilayer_kernel(const float *__restrict__ rows, const double *__restrict__ row_sn, const float *__restrict__ queries,
+                        const double *__restrict__ q_sn, int dim, const int *__restrict__ adj0, int stride0,
+                        const int64_t *__restrict__ upper, const int *__restrict__ pool, int strideU, int entry, int entry_layer,
+                        int first_layer, int min_layer, int k, int cand_cap, ND *__restrict__ spill, int spill_cap,
+                        unsigned *__restrict__ visited, long long vis_words, int *__restrict__ vis_tab, int vis_tab_cap,
+                        int *__restrict__ out_ids, float *__restrict__ out_d, int *__restrict__ out_flag,
+                        unsigned long long *__restrict__ eval_counter, int nbcap, int njobs, int *__restrict__ job_counter)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int lane = threadIdx.x & 63;
+    VisitedSet<HASHED> V{visited + (size_t)blockIdx.x * (size_t)vis_words, vis_words,
+                         vis_tab ? vis_tab + (size_t)blockIdx.x * (size_t)vis_tab_cap : nullptr, (unsigned)(vis_tab_cap - 1), 0, vis_tab_cap / 4 * 3};
+    ND *my_spill = spill + (size_t)blockIdx.x * (size_t)spill_cap;
+    const SearchLds L = carve_lds(smem, k, cand_cap, dim, nbcap);
+    const GraphView G{adj0, stride0, upper, pool, strideU};
+    const int per = k - 1, nslots = first_layer + 1;
+    for (;;) {
+        int job = 0;
+        if (lane == 0) job = atomicAdd(job_counter, 1);
+        job = __builtin_amdgcn_readfirstlane(job);
+        if (job >= njobs) break;
+        const float *q = queries + (size_t)job * dim;
+        double sb = 0.0;
+        if (METRIC == M_COS) sb = q_sn[job];
+        wave_sync();
+        for (int i = lane; i < dim; i += 64) L.qs[i] = q[i];
+        unsigned long long evals = 0;
+        int *const ids = out_ids + (size_t)job * nslots * per;
+        float *const ds = out_d + (size_t)job * nslots * per;
+        int ent = entry, ent_layer = entry_layer;
+        bool ok = true;
+        // the chain: a second lane-uniform loop inside the job loop -- no `continue` behind a lane-0 branch, the stores of a step at
+        // the end of its body
+        for (int layer = nslots - 1; layer >= 0; --layer) {
+            int top_n = 0;
+            if (ok && layer >= min_layer) {
+                const SearchJob jb{job, ent, ent_layer, layer, -1, 0};
+                ReadLog RL{nullptr, 0, 0};
+                ok = traverse<METRIC, HASHED>(rows, row_sn, dim, sb, G, jb, k, cand_cap, my_spill, spill_cap, V, L, lane, top_n, evals, RL,
+                                              nullptr, nullptr, true);
+                V.clear(lane); // a fresh visited list per SearchLayerQuery; the set is clean again after the job's last step
+                if (!ok) top_n = 0;
+            }
+            // OrderBy(Dist) over the heap array, stable (take_stable's key: order-preserving bits, then array index).  top_n = 0 (a slot
+            // below min_layer, a handed-back job): padding only.
+            wave_sync();
+            unsigned long long used = 0;
+            for (int r = 0; r < k; ++r) {
+                unsigned long long best = ~0ull;
+                for (int t = 0, i = lane; i < top_n; ++t, i += 64) {
+                    if ((used >> t) & 1ull) continue;
+                    float d = L.top[i].dist;
+                    unsigned u;
+                    if (d != d) u = 0u;
+                    else {
+                        if (d == 0.0f) d = 0.0f;
+                        u = __float_as_uint(d);
+                        u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+                        if (u == 0u) u = 1u;
+                    }
+                    const unsigned long long key = ((unsigned long long)u << 32) | (unsigned)i;
+                    best = key < best ? key : best;
+                }
+#pragma unroll
+                for (int off = 32; off > 0; off >>= 1) {
+                    const unsigned long long o = __shfl_xor(best, off, 64);
+                    best = o < best ? o : best;
+                }
+                const bool have = best != ~0ull;
+                const int wi = have ? (int)(best & 0xffffffffu) : 0;
+                if (have && (wi & 63) == lane) used |= 1ull << (wi >> 6);
+                ND w{-1, __uint_as_float(0x7fc00000u)};
+                if (have) w = L.top[wi]; // (every lane reads the same entry)
+                if (r == 0) {
+                    if (have) { ent = __builtin_amdgcn_readfirstlane(w.id); ent_layer = layer - 1; } // candidates[0] enters the next layer down: no descent
+                } else if (lane == 0) {
+                    ids[(size_t)layer * per + (r - 1)] = w.id;
+                    ds[(size_t)layer * per + (r - 1)] = w.dist;
+                }
+            }
+        }
+        if (lane == 0) {
+            out_flag[job] = ok ? 0 : 1;
+            atomicAdd(eval_counter, evals);
+        }
+        __builtin_amdgcn_wave_barrier();
+    }
+}
+#define HNSW_MULTILAYER_SIGNATURE(PREFIX, M, H)                                                                                     \
+    PREFIX template __global__ void graph_multilayer_kernel<M, H>(                                                                  \
+        const float *__restrict__, const double *__restrict__, const float *__restrict__, const double *__restrict__, int,      \
+        const int *__restrict__, int, const int64_t *__restrict__, const int *__restrict__, int, int, int, int, int, int, int,  \
+        ND *__restrict__, int, unsigned *__restrict__, long long, int *__restrict__, int, int *__restrict__, float *__restrict__, \
+        int *__restrict__, unsigned long long *__restrict__, int, int, int *__restrict__);
+#define HNSW_FOR_EACH_MULTILAYER(X, M) X(M, false) X(M, true)
+#define HNSW_DECLARE_MULTILAYER(M, H) HNSW_MULTILAYER_SIGNATURE(extern, M, H)
+#define HNSW_DEFINE_MULTILAYER(M, H) HNSW_MULTILAYER_SIGNATURE(, M, H)
+
 #ifdef HNSW_HOST_TU // few variants and launched from one place: defined only in the unit that launches it
 // RangeQuery on the device: FindEntryPointQuery + GraphNavigator.SearchLayerRange (GraphNavigator.cs:262-325)
-// for one query per wave.  What the reference's two heaps compute there is a closure: a neighbour enters
+// for one query per wave, on the lists of the job's search_layer (RangeQuery's `layer`; the descent stops above it).  What the reference's two heaps compute there is a closure: a neighbour enters
 // `candidates` and `topCandidates` iff its distance is <= range (:302-308), nothing ever leaves topCandidates
 // (its root never exceeds range, :310-311), and the stop test (:286-289) can only fire for the entry point, whose
 // farthestResultDist is still MaxValue -- so every listed node and the entry point are expanded exactly once,
@@ -402,7 +512,9 @@ graph_search_filtered_kernel(const float *__restrict__ rows, const double *__res
 // node to expand.  Results are then copied to a launch-wide arena at an offset taken with one atomic.
 // out_flag: 0 done; 1 hand back (more than found_cap results, or the visited table filling up); 3 arena full.
 constexpr int kRangeFan = 8; // nodes expanded per step; the id / distance scratch holds kRangeFan adjacency lists
-template <int METRIC, bool HASHED>
+// LAYERED: the lists of the job's search_layer (upper layers go through the per-node offset into the pool: eight more scalar
+// loads per step and 40 more spilled SGPRs, so layer-0 calls keep the form without them -- the kernel as it was)
+template <int METRIC, bool HASHED, bool LAYERED = false>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) // at most 168 VGPRs: three waves per SIMD
 graph_range_kernel(const float *__restrict__ rows, const double *__restrict__ row_sn, const float *__restrict__ queries,
                    const double *__restrict__ q_sn, int dim, const int *__restrict__ adj0, int stride0,
@@ -468,7 +580,7 @@ graph_range_kernel(const float *__restrict__ rows, const double *__restrict__ ro
             const int *lw[kRangeFan];
 #pragma unroll
             for (int w = 0; w < kRangeFan; ++w) {
-                lw[w] = G.list(__builtin_amdgcn_readlane(c0, w < W ? w : 0), 0);
+                lw[w] = G.list(__builtin_amdgcn_readlane(c0, w < W ? w : 0), LAYERED ? jb.search_layer : 0);
                 n[w] = w < W ? __builtin_amdgcn_readfirstlane(lw[w][0]) : 0;
                 nb[w] = lane < n[w] ? lw[w][1 + lane] : 0;
             }

@@ -153,7 +153,7 @@ API void hnsw_free_results(void **ids_array, void **dists_array, int count);
 
 // hnsw_range_query and its filtered sibling: `name` for the errors, allow (none: no filter)
 static int range_query_export(void *handle, const float *vectors, int count, int dim, float range, hnsw::AllowBits allow, void **out_ids,
-                              void **out_dists, int *counts, const char *name)
+                              void **out_dists, int *counts, const char *name, int layer = 0)
 {
     if (!vectors || !out_ids || !out_dists || !counts || dim <= 0) { set_error(std::string("System.ArgumentNullException: ") + name); return -1; }
     for (int i = 0; i < count; ++i) { out_ids[i] = nullptr; out_dists[i] = nullptr; counts[i] = 0; }
@@ -161,7 +161,7 @@ static int range_query_export(void *handle, const float *vectors, int count, int
     std::vector<std::vector<hnsw::NodeDist>> res;
     {
         LOCK_INDEX(handle);
-        if (static_cast<HnswIndex *>(handle)->range_query(vectors, count, dim, range, res, err, allow) < 0) { set_error(err); return -1; }
+        if (static_cast<HnswIndex *>(handle)->range_query(vectors, count, dim, range, res, err, allow, layer) < 0) { set_error(err); return -1; }
     }
     const bool trace = hnsw::diag("trace", 0) != 0;
     const auto t_out0 = std::chrono::steady_clock::now();
@@ -219,6 +219,48 @@ API int hnsw_mi355x_range_query_filtered(void *handle, const float *vectors, int
     if (!allow_bits || nbits < 0) { set_error("System.ArgumentException: hnsw_mi355x_range_query_filtered: allow_bits must not be NULL and nbits must be >= 0"); return -1; }
     return range_query_export(handle, vectors, count, dim, range, hnsw::AllowBits{allow_bits, nbits}, out_ids, out_dists, counts,
                               "hnsw_mi355x_range_query_filtered");
+}
+
+// KnnQuery / RangeQuery with the reference's `layer` argument (BatchKnnQuery / BatchRangeQuery(queries, ., filterFnc, layer),
+// HNSWIndex.cs:107-168); allow_bits == NULL: no filter.  Layer 0 goes through the code of the calls without a layer.
+API int hnsw_mi355x_knn_query_at_layer(void *handle, const float *vectors, int count, int dim, int k, int layer, const uint32_t *allow_bits,
+                                       long long nbits, int *out_ids, float *out_dists)
+{
+    if (!handle) return 0;
+    if (count <= 0) return 0;
+    if (layer == 0 && !allow_bits) return hnsw_knn_query(handle, vectors, count, dim, k, out_ids, out_dists);
+    if (!vectors || !out_ids || !out_dists || dim <= 0) { set_error("System.ArgumentNullException: hnsw_mi355x_knn_query_at_layer"); return -1; }
+    if (allow_bits && nbits < 0) { set_error("System.ArgumentException: hnsw_mi355x_knn_query_at_layer: nbits must be >= 0"); return -1; }
+    LOCK_INDEX(handle);
+    std::string err;
+    if (static_cast<HnswIndex *>(handle)->knn_query_general(vectors, count, dim, k, layer, allow_bits, nbits, out_ids, out_dists, err) < 0) {
+        set_error("System.IndexOutOfRangeException: hnsw_mi355x_knn_query_at_layer: " + err);
+        return -1;
+    }
+    return 0;
+}
+
+API int hnsw_mi355x_range_query_at_layer(void *handle, const float *vectors, int count, int dim, float range, int layer, const uint32_t *allow_bits,
+                                         long long nbits, void **out_ids, void **out_dists, int *counts)
+{
+    if (!handle) return 0;
+    if (count <= 0) return 0;
+    if (allow_bits && nbits < 0) { set_error("System.ArgumentException: hnsw_mi355x_range_query_at_layer: nbits must be >= 0"); return -1; }
+    return range_query_export(handle, vectors, count, dim, range, allow_bits ? hnsw::AllowBits{allow_bits, nbits} : hnsw::AllowBits{}, out_ids, out_dists,
+                              counts, "hnsw_mi355x_range_query_at_layer", layer);
+}
+
+// MultiLayerKnnQuery (HNSWIndex.cs:173-187) for a batch of independent queries: the number of layer slots, or -1
+API int hnsw_mi355x_multilayer_knn_query(void *handle, const float *vectors, int count, int dim, int k, int max_layer, int min_layer, int layers_cap,
+                                         int *out_ids, float *out_dists)
+{
+    if (!handle) return 0;
+    if (count > 0 && k > 1 && (!vectors || !out_ids || !out_dists || dim <= 0)) { set_error("System.ArgumentNullException: hnsw_mi355x_multilayer_knn_query"); return -1; }
+    LOCK_INDEX(handle);
+    std::string err;
+    const int n = static_cast<HnswIndex *>(handle)->multilayer_knn_query(vectors, count, dim, k, max_layer, min_layer, layers_cap, out_ids, out_dists, err);
+    if (n < 0) { set_error("System.ArgumentOutOfRangeException: hnsw_mi355x_multilayer_knn_query: " + err); return -1; }
+    return n;
 }
 
 API void hnsw_free_results(void **ids_array, void **dists_array, int count) // :199-217

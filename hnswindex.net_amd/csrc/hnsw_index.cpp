@@ -187,14 +187,15 @@ struct Prune {
 };
 
 // ------------------------------------------------------------------------------------
-// KnnQuery job: HNSWIndex.KnnQuery (src/HNSWIndex/HNSWIndex.cs:107-124), layer 0, with or without an allow-set.
+// KnnQuery job: HNSWIndex.KnnQuery (src/HNSWIndex/HNSWIndex.cs:107-124) on one layer, with or without an allow-set.
 // ------------------------------------------------------------------------------------
 struct QueryJob : Job {
     const Graph *g;
     int capacity, qi, ef, k;
     int *out_ids;
     float *out_d;
-    AllowBits allow; // the descent is not filtered (:116); the layer-0 search is
+    AllowBits allow; // the descent is not filtered (:116); the search on `layer` is
+    int layer = 0;   // KnnQuery's `layer`: FindEntryPointQuery stops above it, SearchLayerQuery reads its lists
     Descent desc;
     Expand exp;
     int stage = 0; // 0 descent, 1 expand
@@ -204,7 +205,7 @@ struct QueryJob : Job {
         *io.qidx = qi;
         if (stage == 0) {
             if (desc.prepare(io)) return true;
-            exp.begin(g, sc, capacity, desc.best, desc.cur, 0, ef, -1, allow); // :117 (entry distance reused, same bits)
+            exp.begin(g, sc, capacity, desc.best, desc.cur, layer, ef, -1, allow); // :117 (entry distance reused, same bits)
             stage = 1;
         }
         return exp.prepare(io, sc);
@@ -233,7 +234,7 @@ struct QuerySource : JobSource {
         int i = next.fetch_add(1, std::memory_order_relaxed);
         if (i >= (int)jobs.size()) return nullptr;
         QueryJob &j = jobs[(size_t)i];
-        j.desc.begin(j.g, j.g->entry, 0); // FindEntryPointQuery(layer 0) :116
+        j.desc.begin(j.g, j.g->entry, j.layer); // FindEntryPointQuery(layer) :116
         j.stage = 0;
         return &j;
     }
@@ -255,6 +256,7 @@ struct RangeJob : Job {
     Descent desc;
     int stage = 0;
     AllowBits allow;         // filterFnc as a bitset (none: everything allowed)
+    int layer = 0;           // RangeQuery's `layer`
     bool heap_empty = false; // InvalidOperationException("Heap is empty") (BinaryHeap.cs:56)
 
     void begin_search(SlotScratch &sc)
@@ -282,7 +284,7 @@ struct RangeJob : Job {
             const NodeDist closest = sc.cand.peek();                             // :285
             if (closest.dist > farthest && closest.dist > range) return false;  // :286-289
             sc.cand.pop();                                                       // :290
-            const int *l = g->list(closest.id, 0);
+            const int *l = g->list(closest.id, layer);
             int n = 0;
             for (int i = 1; i <= l[0]; ++i)
                 if (!sc.visited.test_and_set(l[i])) io.ids[n++] = l[i];          // :297 / :318
@@ -322,12 +324,71 @@ struct RangeSource : JobSource {
         int i = next.fetch_add(1, std::memory_order_relaxed);
         if (i >= (int)jobs.size()) return nullptr;
         RangeJob &j = jobs[(size_t)i];
-        j.desc.begin(j.g, j.g->entry, 0);
+        j.desc.begin(j.g, j.g->entry, j.layer);
         j.stage = 0;
         j.heap_empty = false;
         return &j;
     }
     void release(Job *job, SlotScratch &sc) override { static_cast<RangeJob *>(job)->finish(sc); }
+};
+
+// ------------------------------------------------------------------------------------
+// MultiLayerKnnQuery job: HNSWIndex.MultiLayerKnnQuery (src/HNSWIndex/HNSWIndex.cs:173-187) for one query -- the descent to
+// `first` = min(top, maxLayer), then SearchLayerQuery with beam k on every layer down to `min_layer`, each from the nearest
+// result of the layer above (the first from where the descent arrived, its distance reused).  out_*: [first + 1][k - 1], padded
+// beforehand by the caller; slot `layer` receives the step's stable order without its first entry.
+// ------------------------------------------------------------------------------------
+struct MultiLayerJob : Job {
+    const Graph *g;
+    int capacity, qi, k, first, min_layer;
+    int *out_ids;
+    float *out_d;
+    Descent desc;
+    Expand exp;
+    int stage = 0; // 0 descent, 1 a layer's search
+    int layer = 0;
+
+    bool prepare(SlotIO &io, SlotScratch &sc) override
+    {
+        *io.qidx = qi;
+        if (stage == 0) {
+            if (desc.prepare(io)) return true;
+            layer = first;
+            exp.begin(g, sc, capacity, desc.best, desc.cur, layer, k);
+            stage = 1;
+        }
+        for (;;) {
+            if (exp.prepare(io, sc)) return true;
+            // the step is complete: candidates = OrderBy(Dist) of the heap array (:180); candidates[0] leads on (:181)
+            const int n = sc.top.count;
+            sc.tmp.assign(sc.top.buf.begin(), sc.top.buf.begin() + n);
+            stable_sort_by_dist(sc.tmp.data(), n);
+            for (int j = 1; j < n; ++j) { out_ids[(size_t)layer * (k - 1) + (j - 1)] = sc.tmp[(size_t)j].id; out_d[(size_t)layer * (k - 1) + (j - 1)] = sc.tmp[(size_t)j].dist; } // :182
+            if (layer == min_layer) return false;
+            --layer;
+            exp.begin(g, sc, capacity, sc.tmp[0].id, sc.tmp[0].dist, layer, k); // (SearchLayerQuery measures its entry point again: the same bits)
+        }
+    }
+    void consume(const SlotIO &io, SlotScratch &sc) override
+    {
+        if (stage == 0) desc.consume(io);
+        else exp.consume(io, sc);
+    }
+};
+
+struct MultiLayerSource : JobSource {
+    std::vector<MultiLayerJob> jobs;
+    std::atomic<int> next{0};
+    Job *acquire(SlotScratch &) override
+    {
+        int i = next.fetch_add(1, std::memory_order_relaxed);
+        if (i >= (int)jobs.size()) return nullptr;
+        MultiLayerJob &j = jobs[(size_t)i];
+        j.desc.begin(j.g, j.g->entry, j.first);
+        j.stage = 0;
+        return &j;
+    }
+    void release(Job *, SlotScratch &) override {}
 };
 
 // ------------------------------------------------------------------------------------
@@ -1459,7 +1520,7 @@ bool HnswIndex::sync_graph(std::string &err)
 }
 
 // Host lock-step traversal for the queries listed in `which` (nullptr: all `count` queries).
-int HnswIndex::knn_query_lockstep(const int *which, int count, int k, int *out_ids, float *out_dists, std::string &err, AllowBits allow)
+int HnswIndex::knn_query_lockstep(const int *which, int count, int k, int *out_ids, float *out_dists, std::string &err, AllowBits allow, int layer)
 {
     if (!refresh_host_lists(err)) return -1;
     QuerySource src;
@@ -1476,6 +1537,7 @@ int HnswIndex::knn_query_lockstep(const int *which, int count, int k, int *out_i
         j.out_ids = out_ids + (size_t)qi * k;
         j.out_d = out_dists + (size_t)qi * k;
         j.allow = allow;
+        j.layer = layer;
     }
     if (!engine()->run(src, count)) { err = get_dev_error(); return -1; }
     return 0;
@@ -1522,14 +1584,35 @@ int HnswIndex::knn_query(const float *queries, int count, int dim, int k, int *o
 int HnswIndex::knn_query_filtered(const float *queries, int count, int dim, int k, const uint32_t *allow_bits, long long nbits, int *out_ids,
                                   float *out_dists, std::string &err)
 {
+    return knn_query_general(queries, count, dim, k, 0, allow_bits, nbits, out_ids, out_dists, err);
+}
+
+// A layer the reference can search: OutEdges[layer] of the nodes FindEntryPointQuery reaches from the entry point exists for
+// 0 <= layer <= the entry point's MaxLayer; anything else indexes out of range there and throws.
+bool HnswIndex::layer_ok(int layer, std::string &err) const
+{
+    if (layer >= 0 && layer <= graph_.top_layer()) return true;
+    err = "layer " + std::to_string(layer) + " is outside 0 .. " + std::to_string(graph_.top_layer()) + " (the entry point's top layer)";
+    return false;
+}
+
+// KnnQuery(query, k, filterFnc, layer) (HNSWIndex.cs:107-124) in every form but the plain one (no filter at layer 0: knn_query):
+// allow_bits == nullptr means no filter.  With a filter the device runs graph_search_filtered_kernel on `layer`; without one the
+// jobs of graph_search_kernel carry search_layer = layer (the sorted-list forms with their tie rule, as at layer 0).
+int HnswIndex::knn_query_general(const float *queries, int count, int dim, int k, int layer, const uint32_t *allow_bits, long long nbits, int *out_ids,
+                                 float *out_dists, std::string &err)
+{
     if (count <= 0) return 0;
     if (failed(err)) return -1;
-    const AllowBits allow{allow_bits, nbits};
-    bool any = false; // a set that allows no id of the graph: the result is empty in any order (no launch, no traversal)
-    const long long n_allow = std::min<long long>(nbits, graph_.length);
+    const bool filtered = allow_bits != nullptr;
+    const AllowBits allow = filtered ? AllowBits{allow_bits, nbits} : AllowBits{};
+    bool any = !filtered; // a set that allows no id of the graph: the result is empty in any order (no launch, no traversal)
+    const long long n_allow = filtered ? std::min<long long>(nbits, graph_.length) : 0;
     for (long long w = 0; w < (n_allow + 31) / 32 && !any; ++w)
         any = (allow_bits[w] & ((w + 1) * 32 <= n_allow ? ~0u : (1u << (n_allow & 31)) - 1u)) != 0u;
-    if (k < 1 || graph_.entry < 0 || graph_.count <= 0 || !any) { // HNSWIndex.cs:109: empty result lists, padded by the export
+    const bool empty = k < 1 || graph_.entry < 0 || graph_.count <= 0;
+    if (!empty && !layer_ok(layer, err)) return -1; // (the reference returns before it looks at `layer` only where :109 does)
+    if (empty || !any) { // HNSWIndex.cs:109: empty result lists, padded by the export
         for (long long j = 0; j < (long long)count * std::max(k, 0); ++j) { out_ids[j] = -1; out_dists[j] = std::numeric_limits<float>::quiet_NaN(); }
         return 0;
     }
@@ -1541,11 +1624,18 @@ int HnswIndex::knn_query_filtered(const float *queries, int count, int dim, int 
                 if (!dev_->adopt_queries(context(g), 0, shard_lo_[(size_t)g + 1] - shard_lo_[(size_t)g], shard_lo_[(size_t)g], count)) { err = get_dev_error(); return -1; }
             sharded_resident_ = false;
         }
-        return knn_query_lockstep(nullptr, count, k, out_ids, out_dists, err, allow);
+        return knn_query_lockstep(nullptr, count, k, out_ids, out_dists, err, allow, layer);
     }
     if (!sync_graph(err)) return -1;
     const int ep = graph_.entry, top = graph_.top_layer();
     std::vector<int> flag((size_t)count);
+    // one context's share: cnt resident queries of its own, rows lo.. of the caller's arrays
+    const auto search = [&](Device *ctx, int cnt, long long lo) -> bool {
+        if (filtered) return ctx->search_filtered(cnt, ep, top, ef, k, allow_bits, nbits, out_ids + (size_t)lo * k, out_dists + (size_t)lo * k, flag.data() + lo, layer);
+        std::vector<SearchJob> jobs((size_t)cnt);
+        for (int i = 0; i < cnt; ++i) jobs[(size_t)i] = SearchJob{i, ep, top, layer, -1, 0};
+        return ctx->search_batch(jobs.data(), cnt, ef, k, out_ids + (size_t)lo * k, out_dists + (size_t)lo * k, flag.data() + lo);
+    };
     if (sharded_resident_) { // every context answers its shard with the bitset uploaded to it
         if (!ensure_replicas(true, err)) return -1;
         const int n = p_.devices;
@@ -1555,12 +1645,12 @@ int HnswIndex::knn_query_filtered(const float *queries, int count, int dim, int 
             th.emplace_back([&, g] {
                 const long long lo = shard_lo_[(size_t)g], hi = shard_lo_[(size_t)g + 1];
                 const int cnt = (int)(hi - lo);
-                if (cnt > 0 && !context(g)->search_filtered(cnt, ep, top, ef, k, allow_bits, nbits, out_ids + (size_t)lo * k, out_dists + (size_t)lo * k, flag.data() + lo))
+                if (cnt > 0 && !search(context(g), cnt, lo))
                     errs[(size_t)g] = get_dev_error().empty() ? "search_filtered failed" : get_dev_error();
             });
         for (auto &t : th) t.join();
         for (const std::string &e : errs) if (!e.empty()) { err = e; return -1; }
-    } else if (!dev_->search_filtered(count, ep, top, ef, k, allow_bits, nbits, out_ids, out_dists, flag.data())) { err = get_dev_error(); return -1; }
+    } else if (!search(dev_.get(), count, 0)) { err = get_dev_error(); return -1; }
     std::vector<int> redo;
     for (int i = 0; i < count; ++i) if (flag[(size_t)i]) redo.push_back(i);
     if (redo.empty()) return 0;
@@ -1569,7 +1659,86 @@ int HnswIndex::knn_query_filtered(const float *queries, int count, int dim, int 
             if (!dev_->adopt_queries(context(g), 0, shard_lo_[(size_t)g + 1] - shard_lo_[(size_t)g], shard_lo_[(size_t)g], count)) { err = get_dev_error(); return -1; }
         sharded_resident_ = false;
     }
-    return knn_query_lockstep(redo.data(), (int)redo.size(), k, out_ids, out_dists, err, allow);
+    return knn_query_lockstep(redo.data(), (int)redo.size(), k, out_ids, out_dists, err, allow, layer);
+}
+
+// Host lock-step chains for the queries listed in `which` (nullptr: all `count`): MultiLayerJob.  out_*: [query][first + 1][k - 1].
+int HnswIndex::multilayer_lockstep(const int *which, int count, int k, int first, int min_layer, int *out_ids, float *out_dists, std::string &err)
+{
+    if (!refresh_host_lists(err)) return -1;
+    MultiLayerSource src;
+    src.jobs.resize((size_t)count);
+    const size_t row = (size_t)(first + 1) * (size_t)(k - 1);
+    for (int i = 0; i < count; ++i) {
+        const int qi = which ? which[i] : i;
+        MultiLayerJob &j = src.jobs[(size_t)i];
+        j.g = &graph_;
+        j.capacity = (int)capacity_;
+        j.qi = qi;
+        j.k = k;
+        j.first = first;
+        j.min_layer = min_layer;
+        j.out_ids = out_ids + (size_t)qi * row;
+        j.out_d = out_dists + (size_t)qi * row;
+        for (size_t x = 0; x < row; ++x) { j.out_ids[x] = -1; j.out_d[x] = std::numeric_limits<float>::quiet_NaN(); }
+    }
+    if (!engine()->run(src, count)) { err = get_dev_error(); return -1; }
+    return 0;
+}
+
+// MultiLayerKnnQuery (HNSWIndex.cs:173-187) for a batch of independent queries: the number of layer slots, or -1.  Each query's
+// chain is one job of graph_multilayer_kernel; what it hands back, host traversal and shapes the kernels do not fit go through
+// MultiLayerJob.  The query set is uploaded to the primary context (with several devices the call is answered there: the same
+// answers).  Runs under the exclusive lock.
+int HnswIndex::multilayer_knn_query(const float *queries, int count, int dim, int k, int max_layer, int min_layer, int layers_cap, int *out_ids,
+                                    float *out_dists, std::string &err)
+{
+    if (failed(err)) return -1;
+    if (graph_.entry < 0 || graph_.count <= 0 || k < 1) return 0; // :176
+    if (max_layer < -1 || min_layer < 0) { // a negative array length, OutEdges[-1]: the reference throws
+        err = "max_layer must be >= -1 and min_layer >= 0 (max_layer " + std::to_string(max_layer) + ", min_layer " + std::to_string(min_layer) + ")";
+        return -1;
+    }
+    if (max_layer == -1) return 0; // an empty array, no search
+    const int top = graph_.top_layer(), first = std::min(top, max_layer), nslots = first + 1; // :178-179
+    if (layers_cap < nslots) {
+        err = "layers_cap " + std::to_string(layers_cap) + " is too small: " + std::to_string(nslots) + " layer slots are needed";
+        return -1;
+    }
+    if (k == 1 || count <= 0) return nslots; // k == 1: every list is empty (candidates[1..]); nothing to write
+    const size_t per = (size_t)(k - 1), row = (size_t)nslots * per, out_row = (size_t)layers_cap * per;
+    if (min_layer > first) { // the loop never runs: every slot stays null
+        for (int i = 0; i < count; ++i)
+            for (size_t x = 0; x < row; ++x) { out_ids[(size_t)i * out_row + x] = -1; out_dists[(size_t)i * out_row + x] = std::numeric_limits<float>::quiet_NaN(); }
+        return nslots;
+    }
+    if (!ensure_dim(dim, err)) return -1;
+    resident_queries_ = 0; // the resident set is replaced (as RangeQuery does)
+    sharded_resident_ = false;
+    if (!dev_->set_queries(queries, count)) { err = get_dev_error(); return -1; }
+    // results in the compact layout [count][nslots][k - 1]; the caller's rows are layers_cap slots long
+    std::vector<int> ids_c;
+    std::vector<float> ds_c;
+    int *ids = out_ids;
+    float *ds = out_dists;
+    if (layers_cap != nslots) { ids_c.resize((size_t)count * row); ds_c.resize((size_t)count * row); ids = ids_c.data(); ds = ds_c.data(); }
+    int rc = 0;
+    if (p_.device_traversal && dev_->traversal_fits(k, false, p_.max_edges)) {
+        if (!sync_graph(err)) return -1;
+        std::vector<int> flag((size_t)count);
+        if (!dev_->multilayer_search(count, graph_.entry, top, first, min_layer, k, ids, ds, flag.data())) { err = get_dev_error(); return -1; }
+        std::vector<int> redo;
+        for (int i = 0; i < count; ++i) if (flag[(size_t)i]) redo.push_back(i);
+        if (!redo.empty()) rc = multilayer_lockstep(redo.data(), (int)redo.size(), k, first, min_layer, ids, ds, err); // the whole chain, from the start
+    } else
+        rc = multilayer_lockstep(nullptr, count, k, first, min_layer, ids, ds, err);
+    if (rc < 0) return -1;
+    if (layers_cap != nslots)
+        for (int i = 0; i < count; ++i) {
+            std::memcpy(out_ids + (size_t)i * out_row, ids + (size_t)i * row, sizeof(int) * row);
+            std::memcpy(out_dists + (size_t)i * out_row, ds + (size_t)i * row, sizeof(float) * row);
+        }
+    return nslots;
 }
 
 // The device contexts 1 .. devices - 1 (created on first use; more contexts than GPUs share them round robin --
@@ -1767,7 +1936,7 @@ int HnswIndex::knn_query_sharded(int k, int *out_ids, float *out_dists, std::str
 
 // Host lock-step range search for the queries listed in `which` (nullptr: all `count` queries).
 int HnswIndex::range_query_lockstep(const int *which, int count, float range, std::vector<std::vector<NodeDist>> &out, std::string &err,
-                                    AllowBits allow)
+                                    AllowBits allow, int layer)
 {
     if (!refresh_host_lists(err)) return -1;
     RangeSource src;
@@ -1781,6 +1950,7 @@ int HnswIndex::range_query_lockstep(const int *which, int count, float range, st
         j.range = range;
         j.out = &out[(size_t)qi];
         j.allow = allow;
+        j.layer = layer;
     }
     if (!engine()->run(src, count)) { err = get_dev_error(); return -1; }
     for (const RangeJob &j : src.jobs)
@@ -1793,12 +1963,12 @@ int HnswIndex::range_query_lockstep(const int *which, int count, float range, st
 // distance, and for a query holding such a pair the heaps are replayed on the host from the known distances.
 // With an allow-set the device hands back each list either final or as its closure (Device::range_batch); closures are
 // partitioned by the filter, sorted and, where allowed results tie or range < 0, replayed (finish_filtered_range).
-int HnswIndex::range_query_device(int count, float range, std::vector<std::vector<NodeDist>> &out, std::string &err, AllowBits allow)
+int HnswIndex::range_query_device(int count, float range, std::vector<std::vector<NodeDist>> &out, std::string &err, AllowBits allow, int layer)
 {
     if (!sync_graph(err)) return -1;
     std::vector<SearchJob> jobs((size_t)count);
     const int ep = graph_.entry, top = graph_.top_layer();
-    for (int i = 0; i < count; ++i) jobs[(size_t)i] = SearchJob{i, ep, top, 0, -1};
+    for (int i = 0; i < count; ++i) jobs[(size_t)i] = SearchJob{i, ep, top, layer, -1};
     Device::RangeResults r;
     g_pt.rq_queries += count;
     const bool filtered = allow.bits != nullptr;
@@ -1847,7 +2017,7 @@ int HnswIndex::range_query_device(int count, float range, std::vector<std::vecto
         parallel_for(replay.size(), 1, [&](size_t lo, size_t hi) {
             for (size_t t = lo; t < hi; ++t) {
                 const int i = replay[t];
-                const auto list_of = [&](int id) { return graph_.list(id, 0); };
+                const auto list_of = [&](int id) { return graph_.list(id, layer); };
                 if (filtered) {
                     if (finish_filtered_range(list_of, graph_.max_edges_at(0), r.entry[(size_t)i], range, r.found + r.off[(size_t)i], r.cnt[(size_t)i], allow,
                                               out[(size_t)i]) == kRangeHeapEmpty)
@@ -1858,22 +2028,23 @@ int HnswIndex::range_query_device(int count, float range, std::vector<std::vecto
         });
         if (heap_empty.load()) { err = kHeapEmptyError; return -1; }
     }
-    if (!redo.empty()) return range_query_lockstep(redo.data(), (int)redo.size(), range, out, err, allow);
+    if (!redo.empty()) return range_query_lockstep(redo.data(), (int)redo.size(), range, out, err, allow, layer);
     return 0;
 }
 
 int HnswIndex::range_query(const float *queries, int count, int dim, float range, std::vector<std::vector<NodeDist>> &out, std::string &err,
-                           AllowBits allow)
+                           AllowBits allow, int layer)
 {
     out.assign((size_t)std::max(count, 0), {});
     if (failed(err)) return -1;
     if (count <= 0 || graph_.entry < 0) return 0; // HNSWIndex.cs:146
+    if (!layer_ok(layer, err)) return -1;
     if (!ensure_dim(dim, err)) return -1;
     resident_queries_ = 0; // the resident set is replaced: a later knn_query_resident must not answer for these rows
     if (!dev_->set_queries(queries, count)) { err = get_dev_error(); return -1; }
     int rc;
-    if (p_.device_traversal && dev_->traversal_fits(1, false, p_.max_edges)) rc = range_query_device(count, range, out, err, allow);
-    else rc = range_query_lockstep(nullptr, count, range, out, err, allow);
+    if (p_.device_traversal && dev_->traversal_fits(1, false, p_.max_edges)) rc = range_query_device(count, range, out, err, allow, layer);
+    else rc = range_query_lockstep(nullptr, count, range, out, err, allow, layer);
     if (rc < 0 && err == kHeapEmptyError) out.assign((size_t)count, {}); // the whole batch fails (Parallel.For rethrows)
     return rc;
 }

@@ -28,7 +28,7 @@ struct Params {
     int random_seed = 31337;
     bool allow_removals = true;
     // backend
-    int device = -1;         // -1: HNSW_MI355X_DEVICE or 0
+    int device = -1;         // -1: what hnsw_mi355x_set_device chose, or 0
     int insert_batch = 0;     // cap of a snapshot batch (which is also <= linked/16).  0 (default) = the host's hardware threads:
                               // B items searching one snapshot and linking in id order is an interleaving the reference's
                               // Parallel.For (HNSWIndex.cs:70-78) can produce iff B <= its threads, so the default stays inside
@@ -39,7 +39,7 @@ struct Params {
     int search_slots = 16384;
     int host_threads = 0;    // 0: min(hardware threads, 16)
     int device_traversal = 1; // 1: graph-resident search kernel; 0: host lock-step traversal
-    int devices = 0;          // 0: HNSW_MI355X_DEVICES or 1; > 1: KnnQuery shards its queries over this many device contexts (replicas of rows + graph)
+    int devices = 0;          // 0: what hnsw_mi355x_set_devices chose, or 1; > 1: KnnQuery shards its queries over this many device contexts (replicas of rows + graph)
 };
 
 class HnswIndex {
@@ -58,6 +58,16 @@ public:
     int knn_query_filtered(const float *queries, int count, int dim, int k, const uint32_t *allow_bits, long long nbits, int *out_ids,
                            float *out_dists, std::string &err);
 
+    // hnsw_mi355x_knn_query_at_layer: KnnQuery(query, k, filterFnc, layer) -- allow_bits == nullptr: no filter.  layer outside
+    // 0 .. the entry point's top layer on a non-empty index: -1.  Exclusive lock.
+    int knn_query_general(const float *queries, int count, int dim, int k, int layer, const uint32_t *allow_bits, long long nbits, int *out_ids,
+                          float *out_dists, std::string &err);
+    // hnsw_mi355x_multilayer_knn_query: the number of layer slots (min(top, max_layer) + 1; 0 for an empty index, k < 1 or
+    // max_layer == -1), or -1.  out_*: [count][layers_cap][k - 1].  Exclusive lock.
+    int multilayer_knn_query(const float *queries, int count, int dim, int k, int max_layer, int min_layer, int layers_cap, int *out_ids,
+                             float *out_dists, std::string &err);
+    int top_layer() const { return graph_.entry < 0 ? -1 : graph_.top_layer(); }
+
     // Measurement aid: upload a query set once (resident in HBM), then run KnnQuery on it any
     // number of times without host->device traffic for the inputs.
     int set_resident_queries(const float *queries, int count, int dim, std::string &err, bool streamed = false);
@@ -67,8 +77,9 @@ public:
     // in-range results ordered by distance.  Host lock-step traversal.
     // allow: RangeQuery(query, range, filterFnc) as a bitset over ids (none: no filter).  Where the reference pops an empty
     // top heap (range < 0, range_replay.h) the call fails with kHeapEmptyError.
+    // layer: RangeQuery's `layer` (outside 0 .. the entry point's top layer on a non-empty index: -1).
     int range_query(const float *queries, int count, int dim, float range, std::vector<std::vector<NodeDist>> &out, std::string &err,
-                    AllowBits allow = AllowBits{});
+                    AllowBits allow = AllowBits{}, int layer = 0);
 
     // hnsw_remove (HNSWIndex.Remove, src/HNSWIndex/HNSWIndex.cs:83-102), ids in order.
     int remove(const int *ids, int count, std::string &err);
@@ -183,10 +194,13 @@ private:
     int knn_query_sharded(int k, int *out_ids, float *out_dists, std::string &err);
     bool refresh_host_lists(std::string &err);
     int knn_query_device(const float *queries, int count, int k, int *out_ids, float *out_dists, std::string &err);
-    int knn_query_lockstep(const int *which, int count, int k, int *out_ids, float *out_dists, std::string &err, AllowBits allow = AllowBits{});
+    int knn_query_lockstep(const int *which, int count, int k, int *out_ids, float *out_dists, std::string &err, AllowBits allow = AllowBits{},
+                           int layer = 0);
     int range_query_lockstep(const int *which, int count, float range, std::vector<std::vector<NodeDist>> &out, std::string &err,
-                             AllowBits allow = AllowBits{});
-    int range_query_device(int count, float range, std::vector<std::vector<NodeDist>> &out, std::string &err, AllowBits allow);
+                             AllowBits allow = AllowBits{}, int layer = 0);
+    int range_query_device(int count, float range, std::vector<std::vector<NodeDist>> &out, std::string &err, AllowBits allow, int layer);
+    int multilayer_lockstep(const int *which, int count, int k, int first, int min_layer, int *out_ids, float *out_dists, std::string &err);
+    bool layer_ok(int layer, std::string &err) const;
     int remove_batched(const int *ids, int count, std::string &err);
 
     int metric_ = 0;

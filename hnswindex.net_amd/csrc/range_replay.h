@@ -14,7 +14,8 @@ namespace hnsw {
 // is out of range -- it would be marked visited and dropped (:302, :318) -- and needs no evaluation; the entry
 // point's own distance is never compared when it is out of range (it is alone in `candidates` when popped, and
 // farthestResultDist is still MaxValue at :286).  Result: topCandidates' array, stably sorted (HNSWIndex.cs:155).
-// list_of(id) -> the node's layer-0 list as [count, ids...]; Hit: {int id; float dist}.
+// list_of(id) -> the node's list on the layer the search ran on (RangeQuery's `layer`: the caller's lambda carries it) as
+// [count, ids...]; Hit: {int id; float dist}.
 // With an allow-set (RangeQuery's filterFnc), `found` is the query's whole CLOSURE -- every node within range the traversal
 // reached, allowed or not: the traversal does not depend on the filter -- and only allowed nodes enter the top heap (:271,
 // :307-308).  Its Peek (:310) then reads buffer[0] before the first push: default(NodeDistance), distance 0.  With range < 0

@@ -202,6 +202,36 @@ int hnsw_mi355x_knn_query_filtered(void *handle, const float *vectors, int count
 int hnsw_mi355x_range_query_filtered(void *handle, const float *vectors, int count, int dim, float range, const uint32_t *allow_bits,
                                      long long nbits, void **out_ids, void **out_dists, int *counts);
 
+/* KnnQuery / RangeQuery on an upper layer (the `layer` argument of HNSWIndex.KnnQuery / RangeQuery, src/HNSWIndex/HNSWIndex.cs:107-168):
+ * FindEntryPointQuery descends, unfiltered, from the entry point's top layer down to but not including `layer`, and the search
+ * runs on `layer`'s lists (MaxEdges ids per list above layer 0), so every result is a node of that layer -- about n / M^layer
+ * of the data.  Everything else is hnsw_knn_query / hnsw_range_query: beam max(MinNN, k), stable OrderBy(Dist), -1 / NaN padding,
+ * the allocation contract of hnsw_range_query (hnsw_free_results), the null-handle rule (0).  allow_bits == NULL: no filter;
+ * otherwise the allow-set of hnsw_mi355x_knn_query_filtered / hnsw_mi355x_range_query_filtered with their rules (nbits < 0: -1; the
+ * empty-heap failure of a filtered range < 0).  layer < 0 or layer > the entry point's top layer (hnsw_mi355x_max_layer of
+ * hnsw_mi355x_entry_point) on a non-empty index is -1 with a message, where the reference indexes OutEdges out of range and throws;
+ * an empty index (and k < 1) returns padding / empty lists and success whatever `layer` is.  layer == 0 takes the paths of the
+ * calls without a layer.  Calls with layer > 0 or a filter take the handle exclusively. */
+int hnsw_mi355x_knn_query_at_layer(void *handle, const float *vectors, int count, int dim, int k, int layer, const uint32_t *allow_bits,
+                                   long long nbits, int *out_ids, float *out_dists);
+int hnsw_mi355x_range_query_at_layer(void *handle, const float *vectors, int count, int dim, float range, int layer, const uint32_t *allow_bits,
+                                     long long nbits, void **out_ids, void **out_dists, int *counts);
+
+/* MultiLayerKnnQuery (src/HNSWIndex/HNSWIndex.cs:173-187) for a batch of independent queries: each query's neighbours on every
+ * layer from min(top, max_layer) down to min_layer, top = the entry point's top layer.  The first search enters where
+ * FindEntryPointQuery(min(top, max_layer)) arrives; every later one enters at the NEAREST result of the layer above.  Each layer's
+ * search has beam k (not max(MinNN, k)), no filter, and yields the stable OrderBy(Dist) of its result heap WITHOUT its first entry
+ * (that entry is the next layer's entry point): at most k - 1 results per layer.
+ * Returns the number of layer slots, min(top, max_layer) + 1, or -1.  out_ids / out_dists: [count][layers_cap][k - 1]; slot L of
+ * a query holds layer L's results, -1 / NaN where a layer has fewer; slots below min_layer are -1 / NaN (the reference leaves
+ * them null), slots at or above the returned count are not written.  layers_cap below the returned count is an error whose message
+ * names the count needed.  k == 1 writes nothing and returns the count; an empty index, k < 1 or max_layer == -1 returns 0;
+ * max_layer < -1 or min_layer < 0 is -1 (the reference throws); max_layer above top means top; min_layer above the last slot:
+ * nothing is searched, every slot padded.  A null handle returns 0.  Takes the handle exclusively.  The chain of a query runs
+ * as one job of graph_multilayer_kernel; a job it hands back is redone on the host path. */
+int hnsw_mi355x_multilayer_knn_query(void *handle, const float *vectors, int count, int dim, int k, int max_layer, int min_layer,
+                                     int layers_cap, int *out_ids, float *out_dists);
+
 /* Measurement aid: hnsw_mi355x_set_queries uploads a query set (count x dim) once; every later
  * hnsw_mi355x_knn_query_resident(k) is hnsw_knn_query on that set with the inputs already in HBM
  * (out arrays: count x k). */
@@ -307,6 +337,10 @@ typedef struct hnswdev_stats {
                                      * whose outcome rests on BCL tie behaviour this build restates from memory -- the "parity unpinned" exposure as a number
                                      * (also counted in search_repeats) */
     uint64_t lean_launches;         /* traversal launches that ran the lean form of their kernel (no visited sets: the default wherever lists hold <= 64 ids and rows <= 1 KB) */
+    /* graph_multilayer_kernel (MultiLayerKnnQuery's chains; its launches and evaluations are also part of the search_* totals) */
+    uint64_t multilayer_launches;   /* launches */
+    uint64_t multilayer_jobs;       /* chains given to the device (one per query) */
+    uint64_t multilayer_handbacks;  /* ... of which handed back whole (NaN / -0 distance, candidate heap full, visited table crowded) */
 } hnswdev_stats;
 
 /* All return 0 on success, < 0 on error (message via hnswdev_ctx_last_error / hnswdev_last_error).
@@ -403,6 +437,19 @@ int hnswdev_range_search(void *ctx, const float *queries, int nq, int entry_poin
 int hnswdev_range_search_filtered(void *ctx, const float *queries, int nq, int entry_point, float range, const uint32_t *allow_bits,
                                   long long nbits, int *out_counts, int *out_flags);
 int hnswdev_range_results(void *ctx, int *out_ids, float *out_dists);
+/* The searches above on the lists of `layer` (0 .. the entry point's level; outside: -1): the descent stops above it.
+ * allow_bits == NULL: no filter (nbits ignored).  A layer per call, not a setting of the context. */
+int hnswdev_knn_search_at_layer(void *ctx, const float *queries, int nq, int entry_point, int k_beam, int k_out, int layer,
+                                const uint32_t *allow_bits, long long nbits, int *out_ids, float *out_dists, int *out_flags);
+int hnswdev_range_search_at_layer(void *ctx, const float *queries, int nq, int entry_point, float range, int layer, const uint32_t *allow_bits,
+                                  long long nbits, int *out_counts, int *out_flags);
+/* MultiLayerKnnQuery's chains (graph_multilayer_kernel), one job per query: layers min(top, max_layer) .. min_layer with beam k
+ * (k >= 2), top = entry_point's level; semantics of hnsw_mi355x_multilayer_knn_query.  Returns the slot count min(top, max_layer) + 1
+ * (0 for max_layer == -1), or -1 (max_layer < -1, min_layer < 0, layers_cap below the count).  out_ids / out_dists:
+ * [nq][layers_cap][k - 1]; out_flags[i] = 1: query i was handed back whole (its slots hold nothing to rely on) -- evaluate it
+ * with hnswdev_dist_query_batch instead. */
+int hnswdev_multilayer_search(void *ctx, const float *queries, int nq, int entry_point, int k, int max_layer, int min_layer, int layers_cap,
+                              int *out_ids, float *out_dists, int *out_flags);
 
 int hnswdev_sync(void *ctx);
 int hnswdev_set_profiling(void *ctx, int enabled);
