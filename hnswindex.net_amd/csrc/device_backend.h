@@ -291,7 +291,8 @@ private:
     std::mutex mu_, err_mu_;
     std::string err_;
     bool bind();
-    bool abi_layer_ok(const char *who, int entry_point, int layer);
+    bool abi_entry(const char *who, int entry_point, int *top, bool args_ok = true);
+    bool abi_begin(const char *who, const float *queries, int nq, int entry_point, int layer, int *top, bool args_ok = true);
     int device_ = 0, dim_ = 0, metric_ = 0;
     int pitch_ = 0; // 32-bit words per stored row / resident query (== dim_ for the float metrics; the int8 record otherwise)
     float *q_stage_ = nullptr; // int8: float staging area on the device (quantise on upload, dequantise on download)
@@ -330,6 +331,9 @@ private:
     int s_fvistab_each_ = 0;
     bool visited_scratch(int k, int min_cap, bool allow_hash, VisitedScratch *out, bool filtered = false);
     bool plan_traversal(bool insert, int k, bool two_heap, size_t lds, TraversalLaunch *out, bool filtered = false);
+    template <class Upload, class Launch> // the one launcher of the resident-query kernels (search_filtered, multilayer_search)
+    bool run_resident(size_t row, long long chunk, size_t extra, bool hashed, int nq, int *out_ids, float *out_d, int *out_flag, Upload &&upload,
+                      Launch &&launch);
     bool count_launch(const LaunchFamily *family, unsigned long long evals, bool hashed, bool timed, void *t0, void *t1);
     int num_cu_ = 256;
     // Persistent launches never use more than 16 one-wave blocks per CU (the traversal kernels need

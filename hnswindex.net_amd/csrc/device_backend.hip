@@ -1236,25 +1236,25 @@ static auto traversal_kernel(const TraversalLaunch &t, int form)
     return kernel;
 }
 
-// The filtered search kernel of (metric, hashed): one form, its own parameter list (graph_search_kernel's stays as it is).
-static auto filtered_kernel(const TraversalLaunch &t)
+// The single-form persistent kernels (graph_search_filtered_kernel, graph_multilayer_kernel, graph_range_kernel; each with its own
+// parameter list): the instantiation of (metric, hashed), named by of(m, h): [](auto m, auto h) { return &graph_multilayer_kernel<m, h>; }.
+template <class Of>
+static auto persistent_kernel(int metric, bool hashed, Of of)
 {
-    const bool hashed = t.vis.tab != nullptr;
-    decltype(&graph_search_filtered_kernel<M_SQ, false>) kernel = nullptr;
-    with_metric(t.metric, [&](auto m) { kernel = hashed ? &graph_search_filtered_kernel<m, true> : &graph_search_filtered_kernel<m, false>; });
+    decltype(of(std::integral_constant<int, M_SQ>{}, std::false_type{})) kernel = nullptr;
+    with_metric(metric, [&](auto m) { kernel = hashed ? of(m, std::true_type{}) : of(m, std::false_type{}); });
     return kernel;
 }
-// A filtered launch of nj jobs: the plain persistent form on what stays resident, no flags.
-static auto place_filtered(TraversalLaunch &t, int nj)
+// A launch of nj jobs of one of them: the plain persistent form on what stays resident, no flags.
+template <class K>
+static void place_persistent(K kernel, TraversalLaunch &t, int nj)
 {
-    const auto kernel = filtered_kernel(t);
     t.form = kFormPlain;
     t.slots = std::min(t.max_slots, resident_blocks(kernel, t.lds, t.num_cu));
     t.grid = std::min(nj, t.slots);
     t.block = 64;
     t.lds_total = t.lds;
     t.flags = 0;
-    return kernel;
 }
 
 // One launch of nj jobs: the latency form when the jobs fit its resident waves (diag lat=2: whenever lat_ok), else the lean form for a
@@ -1901,6 +1901,49 @@ bool Device::search_batch_impl(const SearchJob *jobs, int njobs, int k, int k_ou
     return true;
 }
 
+// ---- the resident-query kernels (graph_search_filtered_kernel, graph_multilayer_kernel): job i is resident query i, all from one
+// entry point.  One call over nq of them, in launches of up to `chunk` jobs with result rows of `row` entries: the pinned staging
+// [evals (16 B) | ids | dists | flags | `extra` bytes], upload(those bytes) once before the first launch (what the caller sends up
+// from pinned memory), then per launch the counters zeroed, launch(off, nj, d_ids, d_d) -- the kernel for queries off .. off + nj,
+// flags to s_flag_, evaluations to s_evals_, jobs from s_jobctr_ -- and rows and flags copied to the caller's arrays.  The callers
+// keep their own checks, scratch and counters.  (search_batch_impl is not built on this: job upload, the compact copy, the gated tail.)
+template <class Upload, class Launch>
+bool Device::run_resident(size_t row, long long chunk, size_t extra, bool hashed, int nq, int *out_ids, float *out_d, int *out_flag, Upload &&upload,
+                          Launch &&launch)
+{
+    hipStream_t st = S(stream_);
+    const size_t b_res = 4u * (size_t)chunk * row;
+    char *hs = static_cast<char *>(pinned_stage(16 + 2 * b_res + 4u * (size_t)chunk + extra));
+    if (!hs) return false;
+    unsigned long long *h_ev = reinterpret_cast<unsigned long long *>(hs);
+    int *h_ids = reinterpret_cast<int *>(hs + 16);
+    float *h_d = reinterpret_cast<float *>(hs + 16 + b_res);
+    int *h_flag = reinterpret_cast<int *>(hs + 16 + 2 * b_res);
+    if (!upload(hs + 16 + 2 * b_res + 4u * (size_t)chunk)) return false;
+    int *d_ids = reinterpret_cast<int *>(s_hits_);
+    float *d_d = reinterpret_cast<float *>(s_hits_) + (size_t)chunk * row;
+    for (long long off = 0; off < nq; off += chunk) {
+        const int nj = (int)std::min<long long>(chunk, nq - off);
+        HIP_OK(hipMemsetAsync(s_jobctr_, 0, sizeof(int) * 4, st));
+        HIP_OK(hipMemsetAsync(s_evals_, 0, sizeof(unsigned long long), st));
+        const bool timed = profiling_;
+        if (timed) HIP_OK(hipEventRecord((hipEvent_t)ev0_, st));
+        launch(off, nj, d_ids, d_d);
+        HIP_OK(hipGetLastError());
+        if (timed) HIP_OK(hipEventRecord((hipEvent_t)ev1_, st));
+        HIP_OK(hipMemcpyAsync(h_ids, d_ids, 4u * (size_t)nj * row, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(h_d, d_d, 4u * (size_t)nj * row, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(h_flag, s_flag_, sizeof(int) * (size_t)nj, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(h_ev, s_evals_, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+        memcpy(out_ids + (size_t)off * row, h_ids, 4u * (size_t)nj * row);
+        memcpy(out_d + (size_t)off * row, h_d, 4u * (size_t)nj * row);
+        memcpy(out_flag + off, h_flag, sizeof(int) * (size_t)nj);
+        if (!count_launch(nullptr, *h_ev, hashed, timed, ev0_, ev1_)) return false;
+    }
+    return true;
+}
+
 // KnnQuery with an allow-set (graph_search_filtered_kernel): resident query i from (entry, entry_layer), i < nq.  Only the words that
 // cover graph ids travel: bits of ids >= min(nbits, graph nodes) are never read.  A set that allows no graph id pads every
 // row without a launch (the result is empty whatever the order).
@@ -1915,18 +1958,13 @@ bool Device::search_filtered(int nq, int entry, int entry_layer, int k, int k_ou
         set_dev_error("search_filtered: entry point outside the graph, or fewer resident queries than asked for");
         return false;
     }
-    const long long n_allow = std::min<long long>(nbits, g_n_);
-    const size_t words = (size_t)((n_allow + 31) / 32);
-    bool any = false;
-    for (size_t w = 0; w < words && !any; ++w) {
-        const uint32_t v = allow_bits[w];
-        any = (w + 1 < words || (n_allow & 31) == 0) ? v != 0u : (v & ((1u << (n_allow & 31)) - 1u)) != 0u;
-    }
-    if (!any) {
-        for (size_t j = 0; j < (size_t)nq * (size_t)k_out; ++j) { out_ids[j] = -1; out_d[j] = std::numeric_limits<float>::quiet_NaN(); }
+    if (!allows_any(allow_bits, nbits, g_n_)) {
+        pad_results(out_ids, out_d, (size_t)nq * (size_t)k_out);
         for (int i = 0; i < nq; ++i) out_flag[i] = 0;
         return true;
     }
+    const long long n_allow = std::min<long long>(nbits, g_n_);
+    const size_t words = (size_t)((n_allow + 31) / 32);
     const int cand_cap = cand_lds_cap(k, pitch_, false, nbcap());
     const size_t lds = search_lds_bytes(k, cand_cap, pitch_, false, nbcap());
     if (lds > 64 * 1024) { set_dev_error("search_filtered: beam width / dimension exceed the LDS budget"); return false; }
@@ -1935,47 +1973,24 @@ bool Device::search_filtered(int nq, int entry, int entry_layer, int k, int k_ou
     const long long chunk = std::min<long long>(nq, 1 << 20);
     TraversalLaunch tl;
     if (!plan_traversal(false, k, true, lds, &tl, true)) return false;
-    const auto kernel = place_filtered(tl, (int)chunk);
+    const auto kernel = persistent_kernel(metric_, tl.vis.tab != nullptr, [](auto m, auto h) { return &graph_search_filtered_kernel<m, h>; });
+    place_persistent(kernel, tl, (int)chunk);
     const int fspill = filter_spill_cap();
     if (!ensure_search_scratch(chunk, max_slots(), k_out, tl.vis.bytes_per_job)) return false;
     if (!grow_dev(&s_fspill_, &s_fspill_cap_, (size_t)tl.slots * (size_t)std::max(fspill, 1) + 8)) return false; // +8: get2 may read one entry past a heap
     if (!grow_dev(&s_allow_, &s_allow_cap_, std::max<size_t>(words, 1))) return false;
-    // pinned layout: [evals (16 B) | ids | dists | flags | allow words]
-    const size_t b_res = 4u * (size_t)chunk * k_out;
-    char *hs = static_cast<char *>(pinned_stage(16 + 2 * b_res + 4u * (size_t)chunk + 4u * words));
-    if (!hs) return false;
-    unsigned long long *h_ev = reinterpret_cast<unsigned long long *>(hs);
-    int *h_ids = reinterpret_cast<int *>(hs + 16);
-    float *h_d = reinterpret_cast<float *>(hs + 16 + b_res);
-    int *h_flag = reinterpret_cast<int *>(hs + 16 + 2 * b_res);
-    uint32_t *h_allow = reinterpret_cast<uint32_t *>(hs + 16 + 2 * b_res + 4u * (size_t)chunk);
-    memcpy(h_allow, allow_bits, 4u * words);
-    HIP_OK(hipMemcpyAsync(s_allow_, h_allow, 4u * words, hipMemcpyHostToDevice, st));
-    int *d_ids = reinterpret_cast<int *>(s_hits_);
-    float *d_d = reinterpret_cast<float *>(s_hits_) + (size_t)chunk * k_out;
-    for (long long off = 0; off < nq; off += chunk) {
-        const int nj = (int)std::min<long long>(chunk, nq - off);
-        HIP_OK(hipMemsetAsync(s_jobctr_, 0, sizeof(int) * 4, st));
-        HIP_OK(hipMemsetAsync(s_evals_, 0, sizeof(unsigned long long), st));
-        const bool timed = profiling_;
-        if (timed) HIP_OK(hipEventRecord((hipEvent_t)ev0_, st));
-        tl.grid = std::min(nj, tl.slots);
-        hipLaunchKernelGGL(kernel, dim3(tl.grid), dim3(tl.block), tl.lds_total, st, d_rows_, d_row_sn_, d_queries_ + (size_t)off * pitch_,
+    const auto upload = [&](char *h_allow) { // the allow words go up from pinned memory
+        memcpy(h_allow, allow_bits, 4u * words);
+        HIP_OK(hipMemcpyAsync(s_allow_, h_allow, 4u * words, hipMemcpyHostToDevice, st));
+        return true;
+    };
+    const auto launch = [&](long long off, int nj, int *d_ids, float *d_d) {
+        hipLaunchKernelGGL(kernel, dim3(std::min(nj, tl.slots)), dim3(tl.block), tl.lds_total, st, d_rows_, d_row_sn_, d_queries_ + (size_t)off * pitch_,
                            d_q_sn_ ? d_q_sn_ + off : nullptr, pitch_, g_adj0_, g_stride0_, g_upper_, g_pool_, g_strideU_, entry, entry_layer, search_layer, k,
                            cand_cap, reinterpret_cast<ND *>(s_fspill_), fspill, s_visited_, tl.vis.words, tl.vis.tab, tl.vis.tab_cap,
                            reinterpret_cast<const unsigned *>(s_allow_), n_allow, k_out, d_ids, d_d, s_flag_, s_evals_, nbcap(), nj, s_jobctr_);
-        HIP_OK(hipGetLastError());
-        if (timed) HIP_OK(hipEventRecord((hipEvent_t)ev1_, st));
-        HIP_OK(hipMemcpyAsync(h_ids, d_ids, 4u * (size_t)nj * k_out, hipMemcpyDeviceToHost, st));
-        HIP_OK(hipMemcpyAsync(h_d, d_d, 4u * (size_t)nj * k_out, hipMemcpyDeviceToHost, st));
-        HIP_OK(hipMemcpyAsync(h_flag, s_flag_, sizeof(int) * (size_t)nj, hipMemcpyDeviceToHost, st));
-        HIP_OK(hipMemcpyAsync(h_ev, s_evals_, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-        HIP_OK(hipStreamSynchronize(st));
-        memcpy(out_ids + (size_t)off * k_out, h_ids, 4u * (size_t)nj * k_out);
-        memcpy(out_d + (size_t)off * k_out, h_d, 4u * (size_t)nj * k_out);
-        memcpy(out_flag + off, h_flag, sizeof(int) * (size_t)nj);
-        if (!count_launch(nullptr, *h_ev, tl.vis.tab != nullptr, timed, ev0_, ev1_)) return false;
-    }
+    };
+    if (!run_resident((size_t)k_out, chunk, 4u * words, tl.vis.tab != nullptr, nq, out_ids, out_d, out_flag, upload, launch)) return false;
     for (int i = 0; i < nq; ++i) stats_.search_overflows += (uint64_t)(out_flag[i] == 1);
     return true;
 }
@@ -1996,8 +2011,7 @@ bool Device::multilayer_search(int nq, int entry, int entry_layer, int first_lay
         set_dev_error("multilayer_search: layers must satisfy 0 <= min_layer <= first_layer <= the entry point's top layer");
         return false;
     }
-    const int per = k - 1, nslots = first_layer + 1;
-    const size_t row = (size_t)nslots * (size_t)per; // results of one job
+    const size_t row = (size_t)(first_layer + 1) * (size_t)(k - 1); // results of one job
     const int cand_cap = cand_lds_cap(k, pitch_, false, nbcap());
     const size_t lds = search_lds_bytes(k, cand_cap, pitch_, false, nbcap());
     if (lds > 64 * 1024) { set_dev_error("multilayer_search: beam width / dimension exceed the LDS budget"); return false; }
@@ -2006,46 +2020,19 @@ bool Device::multilayer_search(int nq, int entry, int entry_layer, int first_lay
     const long long chunk = std::max<long long>(1, std::min<long long>(nq, (long long)((size_t)(1 << 24) / row)));
     TraversalLaunch tl;
     if (!plan_traversal(false, k, true, lds, &tl)) return false;
-    const bool hashed = tl.vis.tab != nullptr;
-    decltype(&graph_multilayer_kernel<M_SQ, false>) kernel = nullptr;
-    with_metric(metric_, [&](auto m) { kernel = hashed ? &graph_multilayer_kernel<m, true> : &graph_multilayer_kernel<m, false>; });
-    const int slots = std::min(max_slots(), resident_blocks(kernel, lds, num_cu_));
-    if (slots < 1) { set_dev_error("multilayer_search: the kernel does not fit the device"); return false; }
+    const auto kernel = persistent_kernel(metric_, tl.vis.tab != nullptr, [](auto m, auto h) { return &graph_multilayer_kernel<m, h>; });
+    place_persistent(kernel, tl, (int)chunk);
+    if (tl.slots < 1) { set_dev_error("multilayer_search: the kernel does not fit the device"); return false; }
     if (!ensure_search_scratch(chunk, max_slots(), (int)row, tl.vis.bytes_per_job)) return false;
     const int spill_cap = spill_cap_for_tests();
-    // pinned layout: [evals (16 B) | ids | dists | flags]
-    const size_t b_res = 4u * (size_t)chunk * row;
-    char *hs = static_cast<char *>(pinned_stage(16 + 2 * b_res + 4u * (size_t)chunk));
-    if (!hs) return false;
-    unsigned long long *h_ev = reinterpret_cast<unsigned long long *>(hs);
-    int *h_ids = reinterpret_cast<int *>(hs + 16);
-    float *h_d = reinterpret_cast<float *>(hs + 16 + b_res);
-    int *h_flag = reinterpret_cast<int *>(hs + 16 + 2 * b_res);
-    int *d_ids = reinterpret_cast<int *>(s_hits_);
-    float *d_d = reinterpret_cast<float *>(s_hits_) + (size_t)chunk * row;
-    for (long long off = 0; off < nq; off += chunk) {
-        const int nj = (int)std::min<long long>(chunk, nq - off);
-        HIP_OK(hipMemsetAsync(s_jobctr_, 0, sizeof(int) * 4, st));
-        HIP_OK(hipMemsetAsync(s_evals_, 0, sizeof(unsigned long long), st));
-        const bool timed = profiling_;
-        if (timed) HIP_OK(hipEventRecord((hipEvent_t)ev0_, st));
-        hipLaunchKernelGGL(kernel, dim3(std::min(nj, slots)), dim3(64), lds, st, d_rows_, d_row_sn_, d_queries_ + (size_t)off * pitch_,
+    const auto launch = [&](long long off, int nj, int *d_ids, float *d_d) {
+        hipLaunchKernelGGL(kernel, dim3(std::min(nj, tl.slots)), dim3(tl.block), tl.lds_total, st, d_rows_, d_row_sn_, d_queries_ + (size_t)off * pitch_,
                            d_q_sn_ ? d_q_sn_ + off : nullptr, pitch_, g_adj0_, g_stride0_, g_upper_, g_pool_, g_strideU_, entry, entry_layer, first_layer,
                            min_layer, k, cand_cap, reinterpret_cast<ND *>(s_spill_), spill_cap, s_visited_, tl.vis.words, tl.vis.tab, tl.vis.tab_cap, d_ids,
                            d_d, s_flag_, s_evals_, nbcap(), nj, s_jobctr_);
-        HIP_OK(hipGetLastError());
-        if (timed) HIP_OK(hipEventRecord((hipEvent_t)ev1_, st));
-        HIP_OK(hipMemcpyAsync(h_ids, d_ids, 4u * (size_t)nj * row, hipMemcpyDeviceToHost, st));
-        HIP_OK(hipMemcpyAsync(h_d, d_d, 4u * (size_t)nj * row, hipMemcpyDeviceToHost, st));
-        HIP_OK(hipMemcpyAsync(h_flag, s_flag_, sizeof(int) * (size_t)nj, hipMemcpyDeviceToHost, st));
-        HIP_OK(hipMemcpyAsync(h_ev, s_evals_, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-        HIP_OK(hipStreamSynchronize(st));
-        memcpy(out_ids + (size_t)off * row, h_ids, 4u * (size_t)nj * row);
-        memcpy(out_d + (size_t)off * row, h_d, 4u * (size_t)nj * row);
-        memcpy(out_flag + off, h_flag, sizeof(int) * (size_t)nj);
-        if (!count_launch(nullptr, *h_ev, hashed, timed, ev0_, ev1_)) return false;
-        stats_.multilayer_launches += 1;
-    }
+        stats_.multilayer_launches += 1; // counted as made, so a call that fails part-way keeps the launches before the failure
+    };
+    if (!run_resident(row, chunk, 0, tl.vis.tab != nullptr, nq, out_ids, out_d, out_flag, [](char *) { return true; }, launch)) return false;
     stats_.multilayer_jobs += (uint64_t)nq;
     for (int i = 0; i < nq; ++i) stats_.multilayer_handbacks += (uint64_t)(out_flag[i] != 0);
     return true;
@@ -2241,15 +2228,14 @@ bool Device::range_batch(const SearchJob *jobs, int njobs, float range, RangeRes
         HIP_OK(hipMemsetAsync(s_arena_used_, 0, sizeof(unsigned long long), st));
         const bool timed = profiling_;
         if (timed) HIP_OK(hipEventRecord((hipEvent_t)ev0_, st));
-        with_metric(metric_, [&](auto m) {
-            const auto kernel = layer != 0 ? (vis.tab ? &graph_range_kernel<m, true, true> : &graph_range_kernel<m, false, true>)
-                                           : (vis.tab ? &graph_range_kernel<m, true> : &graph_range_kernel<m, false>);
-            const int slots = std::min(std::min(max_slots(), grid_cap), resident_blocks(kernel, lds, num_cu_));
-            hipLaunchKernelGGL(kernel, dim3(std::min<int>(nj, slots)), dim3(64), lds, st, d_rows_, d_row_sn_, d_queries_, d_q_sn_, pitch_, g_adj0_,
-                               g_stride0_, g_upper_, g_pool_, g_strideU_, s_jobs_, range, lists, list_cap, s_visited_, vis.words, vis.tab, vis.tab_cap,
-                               reinterpret_cast<ND *>(s_arena_), (unsigned long long)arena_cap, s_arena_used_, s_roff_, s_cnt_, s_flag_, s_rentry_, s_evals_,
-                               nbcap_r, nj, s_jobctr_);
+        const auto kernel = persistent_kernel(metric_, vis.tab != nullptr, [&](auto m, auto h) {
+            return layer != 0 ? &graph_range_kernel<m, h, true> : &graph_range_kernel<m, h>;
         });
+        const int slots = std::min(std::min(max_slots(), grid_cap), resident_blocks(kernel, lds, num_cu_));
+        hipLaunchKernelGGL(kernel, dim3(std::min<int>(nj, slots)), dim3(64), lds, st, d_rows_, d_row_sn_, d_queries_, d_q_sn_, pitch_, g_adj0_,
+                           g_stride0_, g_upper_, g_pool_, g_strideU_, s_jobs_, range, lists, list_cap, s_visited_, vis.words, vis.tab, vis.tab_cap,
+                           reinterpret_cast<ND *>(s_arena_), (unsigned long long)arena_cap, s_arena_used_, s_roff_, s_cnt_, s_flag_, s_rentry_, s_evals_,
+                           nbcap_r, nj, s_jobctr_);
         HIP_OK(hipGetLastError());
         // the ORDER, still on the device (dk_range_finish.h): every finished list ranked ascending in place; the lists that hold equal
         // distances replayed -- the reference's two heaps on the distances just found -- and ranked in heap-array order.  What these
@@ -2394,13 +2380,24 @@ bool Device::range_search(const float *queries, int nq, int entry_point, float r
     return range_search_filtered(queries, nq, entry_point, range, nullptr, 0, out_counts, out_flags);
 }
 
-// A layer the committed graph has, as seen from the entry point (the reference indexes OutEdges[layer] of nodes reached from it)
-bool Device::abi_layer_ok(const char *who, int entry_point, int layer)
+// What the C ABI's searches begin with: a committed graph, an entry point in it, *top = its top layer ...  args_ok is the shim's own
+// argument test: it fails with the entry point's "<who>: bad argument", after "no graph committed", as each shim had it.
+bool Device::abi_entry(const char *who, int entry_point, int *top, bool args_ok)
 {
-    if (layer >= 0 && layer <= hg_->level[(size_t)entry_point]) return true;
-    set_dev_error(std::string(who) + ": layer " + std::to_string(layer) + " outside 0 .. " + std::to_string(hg_->level[(size_t)entry_point]) +
-                  " (the entry point's top layer)");
-    return false;
+    if (!hg_ || g_n_ <= 0) { set_dev_error(std::string(who) + ": no graph committed"); return false; }
+    if (entry_point < 0 || entry_point >= hg_->n || !args_ok) { set_dev_error(std::string(who) + ": bad argument"); return false; }
+    *top = hg_->level[(size_t)entry_point];
+    return true;
+}
+// ... a layer the entry point has (the reference indexes OutEdges[layer] of nodes reached from it), and the queries made resident.
+bool Device::abi_begin(const char *who, const float *queries, int nq, int entry_point, int layer, int *top, bool args_ok)
+{
+    if (!abi_entry(who, entry_point, top, args_ok)) return false;
+    if (layer < 0 || layer > *top) {
+        set_dev_error(std::string(who) + ": layer " + std::to_string(layer) + " outside 0 .. " + std::to_string(*top) + " (the entry point's top layer)");
+        return false;
+    }
+    return set_queries(queries, nq);
 }
 
 // allow_bits == nullptr: no filter (range_search)
@@ -2410,12 +2407,10 @@ bool Device::range_search_filtered(const float *queries, int nq, int entry_point
     abi_range_.clear();
     if (nq <= 0) return true;
     if (!out_counts || !out_flags) { set_dev_error("range_search: null argument"); return false; }
-    if (!hg_ || g_n_ <= 0) { set_dev_error("range_search: no graph committed"); return false; }
-    if (entry_point < 0 || entry_point >= hg_->n || (allow_bits && nbits < 0)) { set_dev_error("range_search: bad argument"); return false; }
-    if (!abi_layer_ok("range_search", entry_point, layer)) return false;
-    if (!set_queries(queries, nq)) return false;
+    int top;
+    const bool args_ok = !(allow_bits && nbits < 0); // (false: "range_search: bad argument", in abi_entry's place for it)
+    if (!abi_begin("range_search", queries, nq, entry_point, layer, &top, args_ok)) return false;
     std::vector<SearchJob> jobs((size_t)nq);
-    const int top = hg_->level[(size_t)entry_point];
     for (int i = 0; i < nq; ++i) jobs[(size_t)i] = SearchJob{i, entry_point, top, layer, -1};
     RangeResults r;
     if (!range_batch(jobs.data(), nq, range, &r, allow_bits, nbits)) return false;
@@ -2519,12 +2514,10 @@ bool Device::graph_commit()
 bool Device::knn_search(const float *queries, int nq, int entry_point, int k_beam, int k_out, int *out_ids, float *out_d, int *out_flag, int layer)
 {
     if (nq <= 0) return true;
-    if (!hg_ || g_n_ <= 0) { set_dev_error("knn_search: no graph committed"); return false; }
-    if (entry_point < 0 || entry_point >= hg_->n || k_out < 1 || k_beam < k_out) { set_dev_error("knn_search: bad argument"); return false; }
-    if (!abi_layer_ok("knn_search", entry_point, layer)) return false;
-    if (!set_queries(queries, nq)) return false;
+    int top;
+    const bool args_ok = k_out >= 1 && k_beam >= k_out; // (false: "knn_search: bad argument", in abi_entry's place for it)
+    if (!abi_begin("knn_search", queries, nq, entry_point, layer, &top, args_ok)) return false;
     std::vector<SearchJob> jobs((size_t)nq);
-    const int top = hg_->level[(size_t)entry_point];
     for (int i = 0; i < nq; ++i) jobs[(size_t)i] = SearchJob{i, entry_point, top, layer, -1};
     return search_batch(jobs.data(), nq, k_beam, k_out, out_ids, out_d, out_flag);
 }
@@ -2534,16 +2527,16 @@ int Device::multilayer_search_abi(const float *queries, int nq, int entry_point,
 {
     if (max_layer < -1 || min_layer < 0) { set_dev_error("multilayer_search: max_layer must be >= -1 and min_layer >= 0"); return -1; }
     if (nq <= 0 || k < 1 || max_layer == -1) return 0;
-    if (!hg_ || g_n_ <= 0) { set_dev_error("multilayer_search: no graph committed"); return -1; }
-    if (entry_point < 0 || entry_point >= hg_->n) { set_dev_error("multilayer_search: bad argument"); return -1; }
-    const int top = hg_->level[(size_t)entry_point], first = std::min(top, max_layer), nslots = first + 1;
+    int top; // (no abi_begin: the layers are this call's own to check, and the queries go up only once something will be searched)
+    if (!abi_entry("multilayer_search", entry_point, &top)) return -1;
+    const int first = std::min(top, max_layer), nslots = first + 1;
     if (layers_cap < nslots) { set_dev_error("multilayer_search: layers_cap " + std::to_string(layers_cap) + " is too small, " + std::to_string(nslots) + " layer slots are needed"); return -1; }
     if (k == 1) return nslots;
     if (!out_ids || !out_d || !out_flag) { set_dev_error("multilayer_search: null argument"); return -1; }
     const size_t per = (size_t)(k - 1);
     for (int i = 0; i < nq; ++i) {
         out_flag[i] = 0;
-        for (size_t j = 0; j < (size_t)nslots * per; ++j) { out_ids[(size_t)i * layers_cap * per + j] = -1; out_d[(size_t)i * layers_cap * per + j] = std::numeric_limits<float>::quiet_NaN(); }
+        pad_results(out_ids + (size_t)i * layers_cap * per, out_d + (size_t)i * layers_cap * per, (size_t)nslots * per);
     }
     if (min_layer > first) return nslots;
     if (!set_queries(queries, nq)) return -1;
@@ -2551,10 +2544,7 @@ int Device::multilayer_search_abi(const float *queries, int nq, int entry_point,
     std::vector<int> ids((size_t)nq * nslots * per);
     std::vector<float> ds(ids.size());
     if (!multilayer_search(nq, entry_point, top, first, min_layer, k, ids.data(), ds.data(), out_flag)) return -1;
-    for (int i = 0; i < nq; ++i) {
-        memcpy(out_ids + (size_t)i * layers_cap * per, ids.data() + (size_t)i * nslots * per, sizeof(int) * nslots * per);
-        memcpy(out_d + (size_t)i * layers_cap * per, ds.data() + (size_t)i * nslots * per, sizeof(float) * nslots * per);
-    }
+    widen_rows(out_ids, out_d, ids.data(), ds.data(), (size_t)nq, (size_t)nslots * per, (size_t)layers_cap * per);
     return nslots;
 }
 
@@ -2563,11 +2553,10 @@ bool Device::knn_search_filtered(const float *queries, int nq, int entry_point, 
 {
     if (!allow_bits || nbits < 0) { set_dev_error("knn_search_filtered: allow_bits must not be NULL and nbits must be >= 0"); return false; }
     if (nq <= 0) return true;
-    if (!hg_ || g_n_ <= 0) { set_dev_error("knn_search_filtered: no graph committed"); return false; }
-    if (entry_point < 0 || entry_point >= hg_->n || k_out < 1 || k_beam < k_out) { set_dev_error("knn_search_filtered: bad argument"); return false; }
-    if (!abi_layer_ok("knn_search_filtered", entry_point, layer)) return false;
-    if (!set_queries(queries, nq)) return false;
-    return search_filtered(nq, entry_point, hg_->level[(size_t)entry_point], k_beam, k_out, allow_bits, nbits, out_ids, out_d, out_flag, layer);
+    int top;
+    const bool args_ok = k_out >= 1 && k_beam >= k_out; // (false: "knn_search_filtered: bad argument", in abi_entry's place for it)
+    if (!abi_begin("knn_search_filtered", queries, nq, entry_point, layer, &top, args_ok)) return false;
+    return search_filtered(nq, entry_point, top, k_beam, k_out, allow_bits, nbits, out_ids, out_d, out_flag, layer);
 }
 
 // ---- synchronous conveniences behind the C ABI ---------------------------------------

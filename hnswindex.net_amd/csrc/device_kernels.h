@@ -5,14 +5,14 @@
 //   dk_metric.h          the reference's lane arithmetic (EuclideanMetric.cs / CosineMetric.cs), int8 records, slot_distance_kernel
 //   dk_heaps.h           integer keys, the two BinaryHeaps in LDS with the reference's sift rules
 //   dk_measure.h         measure passes (rows of one expansion in one memory round trip)
-//   dk_search_common.h   LDS carve-up, graph view, visited set, read log, FindEntryAtLayer
+//   dk_search_common.h   LDS carve-up, graph view, visited set, read log, a persistent wave's prologue, FindEntryAtLayer
 //   dk_sorted_top.h      SearchLayer on one sorted register list (the loaded launches), tie rules, no visited set
 //   dk_team.h            the latency variants' memory wave and its mailbox
 //   dk_pool_top.h        SearchLayer on an unsorted register pool (the latency variants' logic wave)
 //   dk_traverse_exact.h  the exact two-heap traversal
 //   dk_heuristic.h       RelativeNeighborPruning (with its MFMA Gram-block prefilter)
 //   dk_range_finish.h   RangeQuery's order on the device: ranking by counting, the heaps replayed on known distances
-//   dk_search_kernels.h  graph_search_kernel, graph_range_kernel
+//   dk_search_kernels.h  graph_search_kernel, graph_search_filtered_kernel, graph_multilayer_kernel, graph_range_kernel
 //   dk_insert_kernels.h  graph_insert_search_kernel
 //   dk_link.h            the link half of Add, Remove's re-link
 //   dk_misc_kernels.h    small kernels

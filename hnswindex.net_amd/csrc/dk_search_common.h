@@ -1,4 +1,4 @@
-// dk_search_common.h -- device code, part of device_kernels.h: what the traversals share: LDS carve-up, graph view, visited set, phase clocks, read log, FindEntryAtLayer.
+// dk_search_common.h -- device code, part of device_kernels.h: what the traversals share: LDS carve-up, graph view, visited set, phase clocks, read log, a persistent wave's prologue, FindEntryAtLayer.
 #pragma once
 #include "dk_measure.h"
 
@@ -166,6 +166,34 @@ struct ReadLog {
     }
     __device__ __forceinline__ void layer(int l, int lane) { put(-(l + 1), lane); }
 };
+
+// The prologue of a persistent wave (one wave per block, jobs from a shared counter): its visited set, its next job, the job's query
+// staged in LDS.  (No __restrict__ here: the kernels' qualifiers carry the alias information, a second set changes the schedule.)
+template <bool HASHED>
+__device__ __forceinline__ VisitedSet<HASHED> wave_visited(unsigned *visited, long long vis_words, int *vis_tab, int vis_tab_cap)
+{
+    return VisitedSet<HASHED>{visited + (size_t)blockIdx.x * (size_t)vis_words, vis_words,
+                              vis_tab ? vis_tab + (size_t)blockIdx.x * (size_t)vis_tab_cap : nullptr, (unsigned)(vis_tab_cap - 1), 0, vis_tab_cap / 4 * 3};
+}
+// The wave's next job (wave-uniform) in `job`; false when the counter is past njobs.
+__device__ __forceinline__ bool claim_job(int *job_counter, int njobs, int lane, int &job)
+{
+    job = 0;
+    if (lane == 0) job = atomicAdd(job_counter, 1);
+    job = __builtin_amdgcn_readfirstlane(job);
+    return job < njobs;
+}
+// Resident query `qref` into L.qs; returns its squared norm (cosine) or 0.
+template <int METRIC>
+__device__ __forceinline__ double stage_query(const float *queries, const double *q_sn, int qref, int dim, const SearchLds &L, int lane)
+{
+    const float *q = queries + (size_t)qref * dim;
+    double sb = 0.0;
+    if (METRIC == M_COS) sb = q_sn[qref];
+    wave_sync();
+    for (int i = lane; i < dim; i += 64) L.qs[i] = q[i];
+    return sb;
+}
 
 // FindEntryPoint / FindEntryAtLayer (GraphNavigator.cs:27-82): greedy descent from jb.entry at
 // jb.entry_layer down to (not including) jb.search_layer.  Leaves the entry of the search layer

@@ -1,4 +1,4 @@
-// dk_search_kernels.h -- device code, part of device_kernels.h: KnnQuery / RangeQuery: search_job, graph_search_kernel (persistent, shadows, gated upload), graph_search_filtered_kernel (allow-sets), graph_range_kernel.
+// dk_search_kernels.h -- device code, part of device_kernels.h: KnnQuery / MultiLayerKnnQuery / RangeQuery: search_job, graph_search_kernel (persistent, shadows, gated upload), graph_search_filtered_kernel (allow-sets), graph_multilayer_kernel (layer chains), graph_range_kernel.
 #pragma once
 #include "dk_sorted_top.h"
 #include "dk_pool_top.h"
@@ -30,8 +30,15 @@ static_assert(offsetof(SearchKernArgs, jobs) == 80 && offsetof(SearchKernArgs, o
 // array (ToArray(), BinaryHeap.cs:41-44) and only the first k_out survive -- so select the
 // k_out smallest (float.CompareTo order: NaN first, -0 == +0) with ties broken by array index:
 // exactly the stable sort's prefix.  Key = (order-preserving bits << 32) | index, wave min.
-// L.top[0 .. top_n) holds float distances; writes row `job` of out_ids / out_d (k_out entries, padded).
-__device__ __forceinline__ void take_stable(const SearchLds &L, int lane, int top_n, int k_out, int *__restrict__ out_ids, float *__restrict__ out_d, int job)
+// L.top[0 .. top_n) holds float distances; writes row `row` of out_ids / out_d (k_out entries, padded).
+// CHAIN (a step of MultiLayerKnnQuery on layer `row`, graph_multilayer_kernel): rank 0 is not stored -- when there is one it becomes
+// *next, the entry of the layer below (wave-uniform) -- and ranks 1 .. k_out - 1 fill row `row` of rows `per` = k_out - 1 entries (the
+// caller's own value: it addresses its slab with it); one store point per rank, no `continue`.  One ranking loop, two
+// tails that are the kernels' code as it was: a shared step FUNCTION changed graph_search_kernel's instructions.
+struct ChainEntry { int node, layer; };
+template <bool CHAIN = false>
+__device__ __forceinline__ void take_stable(const SearchLds &L, int lane, int top_n, int k_out, int *__restrict__ out_ids, float *__restrict__ out_d, int row,
+                                            ChainEntry *next = nullptr, int per = 0)
 {
     wave_sync();
     unsigned long long used = 0; // bit t: entry lane + 64*t already emitted
@@ -56,13 +63,27 @@ __device__ __forceinline__ void take_stable(const SearchLds &L, int lane, int to
             unsigned long long o = __shfl_xor(best, off, 64);
             best = o < best ? o : best;
         }
-        if (best == ~0ull) { // fewer than k_out results: pad (HNSWIndexExports.cs:144)
-            if (lane == 0) { out_ids[(size_t)job * k_out + r] = -1; out_d[(size_t)job * k_out + r] = __uint_as_float(0x7fc00000u); }
-            continue;
+        if constexpr (CHAIN) {
+            const bool have = best != ~0ull;
+            const int wi = have ? (int)(best & 0xffffffffu) : 0;
+            if (have && (wi & 63) == lane) used |= 1ull << (wi >> 6);
+            ND w{-1, __uint_as_float(0x7fc00000u)};
+            if (have) w = L.top[wi]; // (every lane reads the same entry)
+            if (r == 0) {
+                if (have) { next->node = __builtin_amdgcn_readfirstlane(w.id); next->layer = row - 1; } // candidates[0] enters the next layer down: no descent
+            } else if (lane == 0) {
+                out_ids[(size_t)row * per + (r - 1)] = w.id;
+                out_d[(size_t)row * per + (r - 1)] = w.dist;
+            }
+        } else {
+            if (best == ~0ull) { // fewer than k_out results: pad (HNSWIndexExports.cs:144)
+                if (lane == 0) { out_ids[(size_t)row * k_out + r] = -1; out_d[(size_t)row * k_out + r] = __uint_as_float(0x7fc00000u); }
+                continue;
+            }
+            const int wi = (int)(best & 0xffffffffu);
+            if ((wi & 63) == lane) used |= 1ull << (wi >> 6);
+            if (lane == 0) { ND w = L.top[wi]; out_ids[(size_t)row * k_out + r] = w.id; out_d[(size_t)row * k_out + r] = w.dist; }
         }
-        const int wi = (int)(best & 0xffffffffu);
-        if ((wi & 63) == lane) used |= 1ull << (wi >> 6);
-        if (lane == 0) { ND w = L.top[wi]; out_ids[(size_t)job * k_out + r] = w.id; out_d[(size_t)job * k_out + r] = w.dist; }
     }
 }
 
@@ -348,23 +369,16 @@ graph_search_filtered_kernel(const float *__restrict__ rows, const double *__res
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x & 63;
-    VisitedSet<HASHED> V{visited + (size_t)blockIdx.x * (size_t)vis_words, vis_words,
-                         vis_tab ? vis_tab + (size_t)blockIdx.x * (size_t)vis_tab_cap : nullptr, (unsigned)(vis_tab_cap - 1), 0, vis_tab_cap / 4 * 3};
+    VisitedSet<HASHED> V = wave_visited<HASHED>(visited, vis_words, vis_tab, vis_tab_cap);
     ND *my_spill = spill + (size_t)blockIdx.x * (size_t)spill_cap;
     const SearchLds L = carve_lds(smem, k, cand_cap, dim, nbcap);
     const GraphView G{adj0, stride0, upper, pool, strideU};
     const AllowSet allow{allow_bits, allow_n};
     for (;;) {
-        int job = 0;
-        if (lane == 0) job = atomicAdd(job_counter, 1);
-        job = __builtin_amdgcn_readfirstlane(job);
-        if (job >= njobs) break;
+        int job;
+        if (!claim_job(job_counter, njobs, lane, job)) break;
         const SearchJob jb{job, entry, entry_layer, search_layer, -1, 0};
-        const float *q = queries + (size_t)job * dim;
-        double sb = 0.0;
-        if (METRIC == M_COS) sb = q_sn[job];
-        wave_sync();
-        for (int i = lane; i < dim; i += 64) L.qs[i] = q[i];
+        const double sb = stage_query<METRIC>(queries, q_sn, job, dim, L, lane);
         unsigned long long evals = 0;
         int top_n = 0;
         ReadLog RL{nullptr, 0, 0};
@@ -410,76 +424,35 @@ graph_multilayer_kernel(const float *__restrict__ rows, const double *__restrict
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x & 63;
-    VisitedSet<HASHED> V{visited + (size_t)blockIdx.x * (size_t)vis_words, vis_words,
-                         vis_tab ? vis_tab + (size_t)blockIdx.x * (size_t)vis_tab_cap : nullptr, (unsigned)(vis_tab_cap - 1), 0, vis_tab_cap / 4 * 3};
+    VisitedSet<HASHED> V = wave_visited<HASHED>(visited, vis_words, vis_tab, vis_tab_cap);
     ND *my_spill = spill + (size_t)blockIdx.x * (size_t)spill_cap;
     const SearchLds L = carve_lds(smem, k, cand_cap, dim, nbcap);
     const GraphView G{adj0, stride0, upper, pool, strideU};
     const int per = k - 1, nslots = first_layer + 1;
     for (;;) {
-        int job = 0;
-        if (lane == 0) job = atomicAdd(job_counter, 1);
-        job = __builtin_amdgcn_readfirstlane(job);
-        if (job >= njobs) break;
-        const float *q = queries + (size_t)job * dim;
-        double sb = 0.0;
-        if (METRIC == M_COS) sb = q_sn[job];
-        wave_sync();
-        for (int i = lane; i < dim; i += 64) L.qs[i] = q[i];
+        int job;
+        if (!claim_job(job_counter, njobs, lane, job)) break;
+        const double sb = stage_query<METRIC>(queries, q_sn, job, dim, L, lane);
         unsigned long long evals = 0;
         int *const ids = out_ids + (size_t)job * nslots * per;
         float *const ds = out_d + (size_t)job * nslots * per;
-        int ent = entry, ent_layer = entry_layer;
+        ChainEntry ent{entry, entry_layer};
         bool ok = true;
         // the chain: a second lane-uniform loop inside the job loop -- no `continue` behind a lane-0 branch, the stores of a step at
         // the end of its body
         for (int layer = nslots - 1; layer >= 0; --layer) {
             int top_n = 0;
             if (ok && layer >= min_layer) {
-                const SearchJob jb{job, ent, ent_layer, layer, -1, 0};
+                const SearchJob jb{job, ent.node, ent.layer, layer, -1, 0};
                 ReadLog RL{nullptr, 0, 0};
                 ok = traverse<METRIC, HASHED>(rows, row_sn, dim, sb, G, jb, k, cand_cap, my_spill, spill_cap, V, L, lane, top_n, evals, RL,
                                               nullptr, nullptr, true);
                 V.clear(lane); // a fresh visited list per SearchLayerQuery; the set is clean again after the job's last step
                 if (!ok) top_n = 0;
             }
-            // OrderBy(Dist) over the heap array, stable (take_stable's key: order-preserving bits, then array index).  top_n = 0 (a slot
-            // below min_layer, a handed-back job): padding only.
-            wave_sync();
-            unsigned long long used = 0;
-            for (int r = 0; r < k; ++r) {
-                unsigned long long best = ~0ull;
-                for (int t = 0, i = lane; i < top_n; ++t, i += 64) {
-                    if ((used >> t) & 1ull) continue;
-                    float d = L.top[i].dist;
-                    unsigned u;
-                    if (d != d) u = 0u;
-                    else {
-                        if (d == 0.0f) d = 0.0f;
-                        u = __float_as_uint(d);
-                        u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-                        if (u == 0u) u = 1u;
-                    }
-                    const unsigned long long key = ((unsigned long long)u << 32) | (unsigned)i;
-                    best = key < best ? key : best;
-                }
-#pragma unroll
-                for (int off = 32; off > 0; off >>= 1) {
-                    const unsigned long long o = __shfl_xor(best, off, 64);
-                    best = o < best ? o : best;
-                }
-                const bool have = best != ~0ull;
-                const int wi = have ? (int)(best & 0xffffffffu) : 0;
-                if (have && (wi & 63) == lane) used |= 1ull << (wi >> 6);
-                ND w{-1, __uint_as_float(0x7fc00000u)};
-                if (have) w = L.top[wi]; // (every lane reads the same entry)
-                if (r == 0) {
-                    if (have) { ent = __builtin_amdgcn_readfirstlane(w.id); ent_layer = layer - 1; } // candidates[0] enters the next layer down: no descent
-                } else if (lane == 0) {
-                    ids[(size_t)layer * per + (r - 1)] = w.id;
-                    ds[(size_t)layer * per + (r - 1)] = w.dist;
-                }
-            }
+            // OrderBy(Dist) over the heap array, stable: candidates[0] is the next step's entry, candidates[1 ..] are the slot's results.
+            // top_n = 0 (a slot below min_layer, a handed-back job): padding only, the entry stays.
+            take_stable<true>(L, lane, top_n, k, ids, ds, layer, &ent, per);
         }
         if (lane == 0) {
             out_flag[job] = ok ? 0 : 1;
@@ -528,8 +501,7 @@ graph_range_kernel(const float *__restrict__ rows, const double *__restrict__ ro
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x;
-    VisitedSet<HASHED> V{visited + (size_t)blockIdx.x * (size_t)vis_words, vis_words,
-                         vis_tab ? vis_tab + (size_t)blockIdx.x * (size_t)vis_tab_cap : nullptr, (unsigned)(vis_tab_cap - 1), 0, vis_tab_cap / 4 * 3};
+    VisitedSet<HASHED> V = wave_visited<HASHED>(visited, vis_words, vis_tab, vis_tab_cap);
     const SearchLds L = carve_lds(smem, 0, 0, dim, nbcap);
     const GraphView G{adj0, stride0, upper, pool, strideU};
     // the queue is read back through L2 (agent-scope loads): a line of it cached earlier may lack later entries
@@ -537,16 +509,10 @@ graph_range_kernel(const float *__restrict__ rows, const double *__restrict__ ro
     int *nbuf = L.nbuf;
     float *dbuf = L.dbuf;
     for (;;) {
-        int job = 0;
-        if (lane == 0) job = atomicAdd(job_counter, 1);
-        job = __builtin_amdgcn_readfirstlane(job);
-        if (job >= njobs) break;
+        int job;
+        if (!claim_job(job_counter, njobs, lane, job)) break;
         const SearchJob jb = jobs[job];
-        const float *q = queries + (size_t)jb.qref * dim;
-        double sb = 0.0;
-        if (METRIC == M_COS) sb = q_sn[jb.qref];
-        wave_sync();
-        for (int i = lane; i < dim; i += 64) L.qs[i] = q[i];
+        const double sb = stage_query<METRIC>(queries, q_sn, jb.qref, dim, L, lane);
         unsigned long long evals = 0;
         int best;
         float cur;

@@ -145,7 +145,7 @@ API int hnsw_mi355x_knn_query_filtered(void *handle, const float *vectors, int c
     if (!allow_bits || nbits < 0) { set_error("System.ArgumentException: hnsw_mi355x_knn_query_filtered: allow_bits must not be NULL and nbits must be >= 0"); return -1; }
     LOCK_INDEX(handle);
     std::string err;
-    if (static_cast<HnswIndex *>(handle)->knn_query_filtered(vectors, count, dim, k, allow_bits, nbits, out_ids, out_dists, err) < 0) { set_error(err); return -1; }
+    if (static_cast<HnswIndex *>(handle)->knn_query_general(vectors, count, dim, k, 0, allow_bits, nbits, out_ids, out_dists, err) < 0) { set_error(err); return -1; }
     return 0;
 }
 

@@ -222,7 +222,7 @@ struct QueryJob : Job {
         stable_sort_by_dist(sc.tmp.data(), n);                     // OrderBy(c => c.Dist) :121
         int m = std::min(n, k);
         for (int j = 0; j < m; ++j) { out_ids[j] = sc.tmp[(size_t)j].id; out_d[j] = sc.tmp[(size_t)j].dist; }
-        for (int j = m; j < k; ++j) { out_ids[j] = -1; out_d[j] = std::numeric_limits<float>::quiet_NaN(); } // Exports.cs:144
+        pad_results(out_ids + m, out_d + m, (size_t)(k - m)); // Exports.cs:144
     }
 };
 
@@ -1519,6 +1519,21 @@ bool HnswIndex::sync_graph(std::string &err)
     return true;
 }
 
+// The jobs a device launch handed back (flag != 0): they are redone on the lock-step path.
+static std::vector<int> flagged_jobs(const std::vector<int> &flag)
+{
+    std::vector<int> redo;
+    for (size_t i = 0; i < flag.size(); ++i) if (flag[i]) redo.push_back((int)i);
+    return redo;
+}
+// A sharded resident query set, whole on the primary: every other context's shard copied to its place among the `count` rows there.
+bool HnswIndex::gather_queries_to_primary(int count, std::string &err)
+{
+    for (int g = 1; g < p_.devices; ++g)
+        if (!dev_->adopt_queries(context(g), 0, shard_lo_[(size_t)g + 1] - shard_lo_[(size_t)g], shard_lo_[(size_t)g], count)) { err = get_dev_error(); return false; }
+    return true;
+}
+
 // Host lock-step traversal for the queries listed in `which` (nullptr: all `count` queries).
 int HnswIndex::knn_query_lockstep(const int *which, int count, int k, int *out_ids, float *out_dists, std::string &err, AllowBits allow, int layer)
 {
@@ -1554,8 +1569,7 @@ int HnswIndex::knn_query_device(const float *, int count, int k, int *out_ids, f
     { Tick t(g_pt.query_dev);
     if (!dev_->search_queries(count, ep, top, ef, k, out_ids, out_dists, flag.data())) { err = get_dev_error(); return -1; } }
     Tick t_post(g_pt.post);
-    std::vector<int> redo;
-    for (int i = 0; i < count; ++i) if (flag[(size_t)i]) redo.push_back(i);
+    const std::vector<int> redo = flagged_jobs(flag);
     if (!redo.empty()) // candidate heap outgrew LDS: exact re-run on the lock-step path
         return knn_query_lockstep(redo.data(), (int)redo.size(), k, out_ids, out_dists, err);
     return 0;
@@ -1566,7 +1580,7 @@ int HnswIndex::knn_query(const float *queries, int count, int dim, int k, int *o
     if (count <= 0) return 0;
     if (failed(err)) return -1;
     if (k < 1 || graph_.entry < 0 || graph_.count <= 0) { // HNSWIndex.cs:109: empty result lists, padded by the export
-        for (long long j = 0; j < (long long)count * std::max(k, 0); ++j) { out_ids[j] = -1; out_dists[j] = std::numeric_limits<float>::quiet_NaN(); }
+        pad_results(out_ids, out_dists, (size_t)count * (size_t)std::max(k, 0));
         return 0;
     }
     // the queries arrive as host buffers: where the traversal runs on the device, all but the first rows are uploaded
@@ -1577,14 +1591,6 @@ int HnswIndex::knn_query(const float *queries, int count, int dim, int k, int *o
     for (int g = 0; g < (sharded_resident_ ? p_.devices : 1); ++g) context(g)->cancel_streamed(); // (only after an error: `queries` is borrowed for this call)
     if (rc < 0) resident_queries_ = 0; // a failed call leaves no resident set: part of it may never have been uploaded
     return rc;
-}
-
-// KnnQuery with an allow-set (HNSWIndex.KnnQuery(query, k, filterFnc), HNSWIndex.cs:107-124, layer 0): the device's filtered
-// traversal where it fits, the lock-step path for whatever it hands back and where it does not.  Runs under the exclusive lock.
-int HnswIndex::knn_query_filtered(const float *queries, int count, int dim, int k, const uint32_t *allow_bits, long long nbits, int *out_ids,
-                                  float *out_dists, std::string &err)
-{
-    return knn_query_general(queries, count, dim, k, 0, allow_bits, nbits, out_ids, out_dists, err);
 }
 
 // A layer the reference can search: OutEdges[layer] of the nodes FindEntryPointQuery reaches from the entry point exists for
@@ -1606,22 +1612,18 @@ int HnswIndex::knn_query_general(const float *queries, int count, int dim, int k
     if (failed(err)) return -1;
     const bool filtered = allow_bits != nullptr;
     const AllowBits allow = filtered ? AllowBits{allow_bits, nbits} : AllowBits{};
-    bool any = !filtered; // a set that allows no id of the graph: the result is empty in any order (no launch, no traversal)
-    const long long n_allow = filtered ? std::min<long long>(nbits, graph_.length) : 0;
-    for (long long w = 0; w < (n_allow + 31) / 32 && !any; ++w)
-        any = (allow_bits[w] & ((w + 1) * 32 <= n_allow ? ~0u : (1u << (n_allow & 31)) - 1u)) != 0u;
+    const bool any = !filtered || allows_any(allow_bits, nbits, graph_.length); // a set that allows no id of the graph: the result is empty in any order (no launch, no traversal)
     const bool empty = k < 1 || graph_.entry < 0 || graph_.count <= 0;
     if (!empty && !layer_ok(layer, err)) return -1; // (the reference returns before it looks at `layer` only where :109 does)
     if (empty || !any) { // HNSWIndex.cs:109: empty result lists, padded by the export
-        for (long long j = 0; j < (long long)count * std::max(k, 0); ++j) { out_ids[j] = -1; out_dists[j] = std::numeric_limits<float>::quiet_NaN(); }
+        pad_results(out_ids, out_dists, (size_t)count * (size_t)std::max(k, 0));
         return 0;
     }
     if (set_resident_queries(queries, count, dim, err) < 0) return -1;
     const int ef = std::max(p_.min_nn, k); // HNSWIndex.cs:115
     if (!(p_.device_traversal && dev_->traversal_fits(ef, false, p_.max_edges))) {
         if (sharded_resident_) { // the host traversal runs on the primary alone: it needs the whole set there (as knn_query_resident)
-            for (int g = 1; g < p_.devices; ++g)
-                if (!dev_->adopt_queries(context(g), 0, shard_lo_[(size_t)g + 1] - shard_lo_[(size_t)g], shard_lo_[(size_t)g], count)) { err = get_dev_error(); return -1; }
+            if (!gather_queries_to_primary(count, err)) return -1;
             sharded_resident_ = false;
         }
         return knn_query_lockstep(nullptr, count, k, out_ids, out_dists, err, allow, layer);
@@ -1651,12 +1653,10 @@ int HnswIndex::knn_query_general(const float *queries, int count, int dim, int k
         for (auto &t : th) t.join();
         for (const std::string &e : errs) if (!e.empty()) { err = e; return -1; }
     } else if (!search(dev_.get(), count, 0)) { err = get_dev_error(); return -1; }
-    std::vector<int> redo;
-    for (int i = 0; i < count; ++i) if (flag[(size_t)i]) redo.push_back(i);
+    const std::vector<int> redo = flagged_jobs(flag);
     if (redo.empty()) return 0;
     if (sharded_resident_) { // the exact host traversal names queries by their global index on the primary
-        for (int g = 1; g < p_.devices; ++g)
-            if (!dev_->adopt_queries(context(g), 0, shard_lo_[(size_t)g + 1] - shard_lo_[(size_t)g], shard_lo_[(size_t)g], count)) { err = get_dev_error(); return -1; }
+        if (!gather_queries_to_primary(count, err)) return -1;
         sharded_resident_ = false;
     }
     return knn_query_lockstep(redo.data(), (int)redo.size(), k, out_ids, out_dists, err, allow, layer);
@@ -1680,7 +1680,7 @@ int HnswIndex::multilayer_lockstep(const int *which, int count, int k, int first
         j.min_layer = min_layer;
         j.out_ids = out_ids + (size_t)qi * row;
         j.out_d = out_dists + (size_t)qi * row;
-        for (size_t x = 0; x < row; ++x) { j.out_ids[x] = -1; j.out_d[x] = std::numeric_limits<float>::quiet_NaN(); }
+        pad_results(j.out_ids, j.out_d, row);
     }
     if (!engine()->run(src, count)) { err = get_dev_error(); return -1; }
     return 0;
@@ -1708,8 +1708,7 @@ int HnswIndex::multilayer_knn_query(const float *queries, int count, int dim, in
     if (k == 1 || count <= 0) return nslots; // k == 1: every list is empty (candidates[1..]); nothing to write
     const size_t per = (size_t)(k - 1), row = (size_t)nslots * per, out_row = (size_t)layers_cap * per;
     if (min_layer > first) { // the loop never runs: every slot stays null
-        for (int i = 0; i < count; ++i)
-            for (size_t x = 0; x < row; ++x) { out_ids[(size_t)i * out_row + x] = -1; out_dists[(size_t)i * out_row + x] = std::numeric_limits<float>::quiet_NaN(); }
+        for (int i = 0; i < count; ++i) pad_results(out_ids + (size_t)i * out_row, out_dists + (size_t)i * out_row, row);
         return nslots;
     }
     if (!ensure_dim(dim, err)) return -1;
@@ -1727,17 +1726,12 @@ int HnswIndex::multilayer_knn_query(const float *queries, int count, int dim, in
         if (!sync_graph(err)) return -1;
         std::vector<int> flag((size_t)count);
         if (!dev_->multilayer_search(count, graph_.entry, top, first, min_layer, k, ids, ds, flag.data())) { err = get_dev_error(); return -1; }
-        std::vector<int> redo;
-        for (int i = 0; i < count; ++i) if (flag[(size_t)i]) redo.push_back(i);
+        const std::vector<int> redo = flagged_jobs(flag);
         if (!redo.empty()) rc = multilayer_lockstep(redo.data(), (int)redo.size(), k, first, min_layer, ids, ds, err); // the whole chain, from the start
     } else
         rc = multilayer_lockstep(nullptr, count, k, first, min_layer, ids, ds, err);
     if (rc < 0) return -1;
-    if (layers_cap != nslots)
-        for (int i = 0; i < count; ++i) {
-            std::memcpy(out_ids + (size_t)i * out_row, ids + (size_t)i * row, sizeof(int) * row);
-            std::memcpy(out_dists + (size_t)i * out_row, ds + (size_t)i * row, sizeof(float) * row);
-        }
+    if (layers_cap != nslots) widen_rows(out_ids, out_dists, ids, ds, (size_t)count, row, out_row);
     return nslots;
 }
 
@@ -1888,15 +1882,14 @@ int HnswIndex::knn_query_resident(int k, int *out_ids, float *out_dists, std::st
     if (count <= 0) return 0;
     if (failed(err)) return -1;
     if (k < 1 || graph_.entry < 0 || graph_.count <= 0) {
-        for (long long j = 0; j < (long long)count * std::max(k, 0); ++j) { out_ids[j] = -1; out_dists[j] = std::numeric_limits<float>::quiet_NaN(); }
+        pad_results(out_ids, out_dists, (size_t)count * (size_t)std::max(k, 0));
         return 0;
     }
     const bool fits = p_.device_traversal && dev_->traversal_fits(std::max(p_.min_nn, k), false, p_.max_edges);
     if (sharded_resident_) {
         if (fits) return knn_query_sharded(k, out_ids, out_dists, err);
         // the host traversal runs on the primary alone: it needs the whole set there
-        for (int g = 1; g < p_.devices; ++g)
-            if (!dev_->adopt_queries(context(g), 0, shard_lo_[(size_t)g + 1] - shard_lo_[(size_t)g], shard_lo_[(size_t)g], count)) { err = get_dev_error(); return -1; }
+        if (!gather_queries_to_primary(count, err)) return -1;
         sharded_resident_ = false;
     }
     if (fits) return knn_query_device(nullptr, count, k, out_ids, out_dists, err);
@@ -1926,11 +1919,9 @@ int HnswIndex::knn_query_sharded(int k, int *out_ids, float *out_dists, std::str
         });
     for (auto &t2 : th) t2.join(); }
     for (const std::string &e : errs) if (!e.empty()) { err = e; return -1; }
-    std::vector<int> redo;
-    for (int i = 0; i < count; ++i) if (flag[(size_t)i]) redo.push_back(i);
+    const std::vector<int> redo = flagged_jobs(flag);
     if (redo.empty()) return 0;
-    for (int g = 1; g < n; ++g) // the exact host traversal names queries by their global index on the primary
-        if (!dev_->adopt_queries(context(g), 0, shard_lo_[(size_t)g + 1] - shard_lo_[(size_t)g], shard_lo_[(size_t)g], count)) { err = get_dev_error(); return -1; }
+    if (!gather_queries_to_primary(count, err)) return -1; // the exact host traversal names queries by their global index on the primary
     return knn_query_lockstep(redo.data(), (int)redo.size(), k, out_ids, out_dists, err);
 }
 

@@ -52,14 +52,9 @@ public:
     // hnsw_knn_query: 0 or -1.
     int knn_query(const float *queries, int count, int dim, int k, int *out_ids, float *out_dists, std::string &err);
 
-    // hnsw_mi355x_knn_query_filtered: hnsw_knn_query with an allow-set (KnnQuery's filterFnc at layer 0) -- a bitset of nbits
-    // bits over ids, ids >= nbits not allowed.  Same conventions as knn_query; the caller holds the index lock EXCLUSIVELY
-    // (filtered calls take no query lane).  0 or -1.
-    int knn_query_filtered(const float *queries, int count, int dim, int k, const uint32_t *allow_bits, long long nbits, int *out_ids,
-                           float *out_dists, std::string &err);
-
-    // hnsw_mi355x_knn_query_at_layer: KnnQuery(query, k, filterFnc, layer) -- allow_bits == nullptr: no filter.  layer outside
-    // 0 .. the entry point's top layer on a non-empty index: -1.  Exclusive lock.
+    // hnsw_mi355x_knn_query_at_layer, hnsw_mi355x_knn_query_filtered (layer 0): KnnQuery(query, k, filterFnc, layer) -- allow_bits ==
+    // nullptr: no filter; else a bitset of nbits bits over ids, ids >= nbits not allowed.  layer outside 0 .. the entry point's top
+    // layer on a non-empty index: -1.  The caller holds the index lock EXCLUSIVELY (these calls take no query lane).  0 or -1.
     int knn_query_general(const float *queries, int count, int dim, int k, int layer, const uint32_t *allow_bits, long long nbits, int *out_ids,
                           float *out_dists, std::string &err);
     // hnsw_mi355x_multilayer_knn_query: the number of layer slots (min(top, max_layer) + 1; 0 for an empty index, k < 1 or
@@ -192,6 +187,7 @@ private:
     Device *context(int g) { return g == 0 ? dev_.get() : replicas_[(size_t)g - 1].get(); }
     bool ensure_replicas(bool clone, std::string &err);
     int knn_query_sharded(int k, int *out_ids, float *out_dists, std::string &err);
+    bool gather_queries_to_primary(int count, std::string &err);
     bool refresh_host_lists(std::string &err);
     int knn_query_device(const float *queries, int count, int k, int *out_ids, float *out_dists, std::string &err);
     int knn_query_lockstep(const int *which, int count, int k, int *out_ids, float *out_dists, std::string &err, AllowBits allow = AllowBits{},

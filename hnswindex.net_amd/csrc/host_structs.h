@@ -3,10 +3,12 @@
 // lock-step driver walks the graph exactly as the reference does.  Citations relative to
 // /root/reference/.
 #pragma once
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <vector>
 
 namespace hnsw {
@@ -33,6 +35,27 @@ struct AllowBits {
     long long n = 0;
     bool has(int id) const { return !bits || (id >= 0 && id < n && ((bits[id >> 5] >> (id & 31)) & 1u) != 0u); }
 };
+// Does a set of nbits bits allow any id of a graph of n_graph nodes?  Reads only the words that cover ids < min(nbits, n_graph).
+static inline bool allows_any(const uint32_t *bits, long long nbits, long long n_graph)
+{
+    const long long n = std::min(nbits, n_graph);
+    for (long long w = 0; w < (n + 31) / 32; ++w)
+        if (bits[w] & ((w + 1) * 32 <= n ? ~0u : (1u << (n & 31)) - 1u)) return true;
+    return false;
+}
+// Result slots that hold nothing: id -1, distance NaN (HNSWIndexExports.cs:144).
+static inline void pad_results(int *ids, float *dists, size_t n)
+{
+    for (size_t j = 0; j < n; ++j) { ids[j] = -1; dists[j] = std::numeric_limits<float>::quiet_NaN(); }
+}
+// `count` packed rows of `row` entries into rows `out_row` entries apart (MultiLayerKnnQuery: nslots -> layers_cap slots); the rest of a row stays.
+static inline void widen_rows(int *dst_ids, float *dst_d, const int *src_ids, const float *src_d, size_t count, size_t row, size_t out_row)
+{
+    for (size_t i = 0; i < count; ++i) {
+        std::memcpy(dst_ids + i * out_row, src_ids + i * row, sizeof(int) * row);
+        std::memcpy(dst_d + i * out_row, src_d + i * row, sizeof(float) * row);
+    }
+}
 
 // src/HNSWIndex/DistanceComparer.cs:9-14 ("farther first": larger distance compares greater)
 struct FartherFirst {

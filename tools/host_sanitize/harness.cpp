@@ -186,6 +186,34 @@ static int structs(uint64_t seed)
         for (int i = 0; i < 2000; ++i) acc += level_from_uniform(r.next_single(), 0.36067376022224085);
         if (acc < 0) return 2;
     }
+    // allows_any against a bit-by-bit loop: random sets; nbits 0, a multiple of 32, below and above the graph, one bit just past it
+    for (int rep = 0; rep < 2000; ++rep) {
+        const long long n_graph = (long long)rng.below(200);
+        long long nbits = (long long)rng.below(260);
+        if (rep % 5 == 0) nbits = 0;
+        else if (rep % 5 == 1) nbits = 32 * (long long)rng.below(8);
+        std::vector<uint32_t> w((size_t)((nbits + 31) / 32)); // exactly the words nbits covers: a read past them is a sanitizer report
+        const uint32_t density = rng.below(4);
+        for (uint32_t &x : w) x = density == 0 ? 0u : density == 1 ? (rng.below(8) ? 0u : 1u << rng.below(32)) : (uint32_t)rng.next();
+        if (rep % 7 == 0 && n_graph < nbits) { // a single bit just past the graph
+            std::fill(w.begin(), w.end(), 0u);
+            w[(size_t)(n_graph >> 5)] = 1u << (n_graph & 31);
+        }
+        bool any = false;
+        for (long long i = 0; i < std::min(nbits, n_graph); ++i) any |= ((w[(size_t)(i >> 5)] >> (i & 31)) & 1u) != 0u;
+        if (allows_any(w.data(), nbits, n_graph) != any) { std::printf("allows_any differs from the bit loop (nbits %lld, graph %lld)\n", nbits, n_graph); return 2; }
+    }
+    // widen_rows against the obvious double loop; what lies beyond a row's entries stays as it was
+    for (int rep = 0; rep < 200; ++rep) {
+        const size_t count = rng.below(6), row = 1 + rng.below(8), out_row = row + rng.below(5);
+        std::vector<int> src_i(count * row), dst_i(count * out_row, -7), want_i(count * out_row, -7);
+        std::vector<float> src_d(count * row), dst_d(count * out_row, -7.0f), want_d(count * out_row, -7.0f);
+        for (size_t j = 0; j < src_i.size(); ++j) { src_i[j] = (int)rng.below(1000); src_d[j] = (float)rng.below(1000) * 0.5f; }
+        for (size_t i = 0; i < count; ++i)
+            for (size_t x = 0; x < row; ++x) { want_i[i * out_row + x] = src_i[i * row + x]; want_d[i * out_row + x] = src_d[i * row + x]; }
+        widen_rows(dst_i.data(), dst_d.data(), src_i.data(), src_d.data(), count, row, out_row);
+        if (dst_i != want_i || dst_d != want_d) { std::printf("widen_rows differs from the double loop\n"); return 2; }
+    }
     std::printf("structs: heaps, sort, random: no fault\n");
     return 0;
 }
