@@ -12,10 +12,11 @@ LIB = PKG / "artifacts" / "native" / "linux-x64" / "HNSWIndex.Native.so"
 # device_backend.hip: host side + the small kernels; traverse_<metric>_<kernel>.hip: the instantiations of the two
 # big traversal kernel templates (device code in device_kernels.h) -- separate units so that they
 # compile in parallel (one unit took two minutes).
-SOURCES = ["device_backend.hip", *[f"traverse_{m}_{k}{v}.hip" for m in ("sq", "cos", "ucos", "i8") for k in ("insert", "search") for v in ("", "_lat")],
-           *[f"traverse_{m}_search_lean.hip" for m in ("sq", "cos", "ucos", "i8")],
-           *[f"traverse_{m}_filtered.hip" for m in ("sq", "cos", "ucos", "i8")],
-           *[f"traverse_{m}_multilayer.hip" for m in ("sq", "cos", "ucos", "i8")],
+METRIC_UNITS = ("sq", "cos", "ucos", "i8", "sqh", "ucosh")  # sqh / ucosh: sq_euclid_f16 / ucosine_f16 (half-precision rows)
+SOURCES = ["device_backend.hip", *[f"traverse_{m}_{k}{v}.hip" for m in METRIC_UNITS for k in ("insert", "search") for v in ("", "_lat")],
+           *[f"traverse_{m}_search_lean.hip" for m in METRIC_UNITS],
+           *[f"traverse_{m}_filtered.hip" for m in METRIC_UNITS],
+           *[f"traverse_{m}_multilayer.hip" for m in METRIC_UNITS],
            "search_engine.cpp", "hnsw_index.cpp", "exports.cpp"]
 # -ffp-contract=off: the kernels fuse a*b+c only where __builtin_fmaf is written -- the
 # reference's AVX path fuses in sq_euclid (Fma.MultiplyAdd) and nowhere else.

@@ -294,8 +294,9 @@ private:
     bool abi_entry(const char *who, int entry_point, int *top, bool args_ok = true);
     bool abi_begin(const char *who, const float *queries, int nq, int entry_point, int layer, int *top, bool args_ok = true);
     int device_ = 0, dim_ = 0, metric_ = 0;
-    int pitch_ = 0; // 32-bit words per stored row / resident query (== dim_ for the float metrics; the int8 record otherwise)
-    float *q_stage_ = nullptr; // int8: float staging area on the device (quantise on upload, dequantise on download)
+    int pitch_ = 0; // 32-bit words per resident query, and what the kernels get as `dim` (== dim_ for the float metrics, f16 rows included; the int8 record otherwise)
+    int row_pitch_ = 0; // 32-bit words per STORED row: pitch_, but the half-precision record (8 * ceil(dim / 16)) for the _f16 metrics, whose queries stay f32
+    float *q_stage_ = nullptr; // int8 and f16 rows: float staging area on the device (quantise / round on upload, dequantise / widen on download)
     size_t q_stage_cap_ = 0;
     long long capacity_ = 0;
     long long n_rows_hw_ = 0; // high-water mark of uploaded rows (id validation)

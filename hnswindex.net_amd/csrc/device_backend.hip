@@ -108,6 +108,12 @@ hipError_t hnsw_phase_bind_sq_search_lean(unsigned long long *);
 hipError_t hnsw_phase_bind_cos_search_lean(unsigned long long *);
 hipError_t hnsw_phase_bind_ucos_search_lean(unsigned long long *);
 hipError_t hnsw_phase_bind_i8_search_lean(unsigned long long *);
+hipError_t hnsw_phase_bind_sqh_insert(unsigned long long *); hipError_t hnsw_phase_bind_sqh_search(unsigned long long *);
+hipError_t hnsw_phase_bind_ucosh_insert(unsigned long long *); hipError_t hnsw_phase_bind_ucosh_search(unsigned long long *);
+hipError_t hnsw_phase_bind_sqh_insert_lat(unsigned long long *); hipError_t hnsw_phase_bind_sqh_search_lat(unsigned long long *);
+hipError_t hnsw_phase_bind_ucosh_insert_lat(unsigned long long *); hipError_t hnsw_phase_bind_ucosh_search_lat(unsigned long long *);
+hipError_t hnsw_phase_bind_sqh_search_lean(unsigned long long *);
+hipError_t hnsw_phase_bind_ucosh_search_lean(unsigned long long *);
 }
 static unsigned long long *g_phase_buf = nullptr; // one buffer per process (diagnostic builds run one index at a time)
 static bool phase_bind_all()
@@ -128,7 +134,13 @@ static bool phase_bind_all()
          hnsw_phase_bind_sq_search_lean(g_phase_buf) == hipSuccess &&
          hnsw_phase_bind_cos_search_lean(g_phase_buf) == hipSuccess &&
          hnsw_phase_bind_ucos_search_lean(g_phase_buf) == hipSuccess &&
-         hnsw_phase_bind_i8_search_lean(g_phase_buf) == hipSuccess;
+         hnsw_phase_bind_i8_search_lean(g_phase_buf) == hipSuccess &&
+         hnsw_phase_bind_sqh_insert(g_phase_buf) == hipSuccess && hnsw_phase_bind_sqh_search(g_phase_buf) == hipSuccess &&
+         hnsw_phase_bind_ucosh_insert(g_phase_buf) == hipSuccess && hnsw_phase_bind_ucosh_search(g_phase_buf) == hipSuccess &&
+         hnsw_phase_bind_sqh_insert_lat(g_phase_buf) == hipSuccess && hnsw_phase_bind_sqh_search_lat(g_phase_buf) == hipSuccess &&
+         hnsw_phase_bind_ucosh_insert_lat(g_phase_buf) == hipSuccess && hnsw_phase_bind_ucosh_search_lat(g_phase_buf) == hipSuccess &&
+         hnsw_phase_bind_sqh_search_lean(g_phase_buf) == hipSuccess &&
+         hnsw_phase_bind_ucosh_search_lean(g_phase_buf) == hipSuccess;
 #endif
     return ok;
 }
@@ -163,43 +175,63 @@ HNSW_FOR_EACH_TRAVERSAL(HNSW_DEFINE_TRAVERSAL, M_SQ)
 HNSW_FOR_EACH_TRAVERSAL(HNSW_DEFINE_TRAVERSAL, M_COS)
 HNSW_FOR_EACH_TRAVERSAL(HNSW_DEFINE_TRAVERSAL, M_UCOS)
 HNSW_FOR_EACH_TRAVERSAL(HNSW_DEFINE_TRAVERSAL, M_I8)
+HNSW_FOR_EACH_TRAVERSAL(HNSW_DEFINE_TRAVERSAL, M_SQH)
+HNSW_FOR_EACH_TRAVERSAL(HNSW_DEFINE_TRAVERSAL, M_UCOSH)
 HNSW_FOR_EACH_TRAVERSAL_LAT(HNSW_DEFINE_TRAVERSAL, M_SQ)
 HNSW_FOR_EACH_TRAVERSAL_LAT(HNSW_DEFINE_TRAVERSAL, M_COS)
 HNSW_FOR_EACH_TRAVERSAL_LAT(HNSW_DEFINE_TRAVERSAL, M_UCOS)
 HNSW_FOR_EACH_TRAVERSAL_LAT(HNSW_DEFINE_TRAVERSAL, M_I8)
+HNSW_FOR_EACH_TRAVERSAL_LAT(HNSW_DEFINE_TRAVERSAL, M_SQH)
+HNSW_FOR_EACH_TRAVERSAL_LAT(HNSW_DEFINE_TRAVERSAL, M_UCOSH)
 HNSW_FOR_EACH_TRAVERSAL_LEAN(HNSW_DEFINE_SEARCH, M_SQ)
 HNSW_FOR_EACH_TRAVERSAL_LEAN(HNSW_DEFINE_SEARCH, M_COS)
 HNSW_FOR_EACH_TRAVERSAL_LEAN(HNSW_DEFINE_SEARCH, M_UCOS)
 HNSW_FOR_EACH_TRAVERSAL_LEAN(HNSW_DEFINE_SEARCH, M_I8)
+HNSW_FOR_EACH_TRAVERSAL_LEAN(HNSW_DEFINE_SEARCH, M_SQH)
+HNSW_FOR_EACH_TRAVERSAL_LEAN(HNSW_DEFINE_SEARCH, M_UCOSH)
 HNSW_FOR_EACH_FILTERED(HNSW_DEFINE_FILTERED, M_SQ)
 HNSW_FOR_EACH_FILTERED(HNSW_DEFINE_FILTERED, M_COS)
 HNSW_FOR_EACH_FILTERED(HNSW_DEFINE_FILTERED, M_UCOS)
 HNSW_FOR_EACH_FILTERED(HNSW_DEFINE_FILTERED, M_I8)
+HNSW_FOR_EACH_FILTERED(HNSW_DEFINE_FILTERED, M_SQH)
+HNSW_FOR_EACH_FILTERED(HNSW_DEFINE_FILTERED, M_UCOSH)
 HNSW_FOR_EACH_MULTILAYER(HNSW_DEFINE_MULTILAYER, M_SQ)
 HNSW_FOR_EACH_MULTILAYER(HNSW_DEFINE_MULTILAYER, M_COS)
 HNSW_FOR_EACH_MULTILAYER(HNSW_DEFINE_MULTILAYER, M_UCOS)
 HNSW_FOR_EACH_MULTILAYER(HNSW_DEFINE_MULTILAYER, M_I8)
+HNSW_FOR_EACH_MULTILAYER(HNSW_DEFINE_MULTILAYER, M_SQH)
+HNSW_FOR_EACH_MULTILAYER(HNSW_DEFINE_MULTILAYER, M_UCOSH)
 #else
 HNSW_FOR_EACH_TRAVERSAL(HNSW_DECLARE_TRAVERSAL, M_SQ)
 HNSW_FOR_EACH_TRAVERSAL(HNSW_DECLARE_TRAVERSAL, M_COS)
 HNSW_FOR_EACH_TRAVERSAL(HNSW_DECLARE_TRAVERSAL, M_UCOS)
 HNSW_FOR_EACH_TRAVERSAL(HNSW_DECLARE_TRAVERSAL, M_I8)
+HNSW_FOR_EACH_TRAVERSAL(HNSW_DECLARE_TRAVERSAL, M_SQH)
+HNSW_FOR_EACH_TRAVERSAL(HNSW_DECLARE_TRAVERSAL, M_UCOSH)
 HNSW_FOR_EACH_TRAVERSAL_LAT(HNSW_DECLARE_TRAVERSAL, M_SQ)
 HNSW_FOR_EACH_TRAVERSAL_LAT(HNSW_DECLARE_TRAVERSAL, M_COS)
 HNSW_FOR_EACH_TRAVERSAL_LAT(HNSW_DECLARE_TRAVERSAL, M_UCOS)
 HNSW_FOR_EACH_TRAVERSAL_LAT(HNSW_DECLARE_TRAVERSAL, M_I8)
+HNSW_FOR_EACH_TRAVERSAL_LAT(HNSW_DECLARE_TRAVERSAL, M_SQH)
+HNSW_FOR_EACH_TRAVERSAL_LAT(HNSW_DECLARE_TRAVERSAL, M_UCOSH)
 HNSW_FOR_EACH_TRAVERSAL_LEAN(HNSW_DECLARE_SEARCH, M_SQ)
 HNSW_FOR_EACH_TRAVERSAL_LEAN(HNSW_DECLARE_SEARCH, M_COS)
 HNSW_FOR_EACH_TRAVERSAL_LEAN(HNSW_DECLARE_SEARCH, M_UCOS)
 HNSW_FOR_EACH_TRAVERSAL_LEAN(HNSW_DECLARE_SEARCH, M_I8)
+HNSW_FOR_EACH_TRAVERSAL_LEAN(HNSW_DECLARE_SEARCH, M_SQH)
+HNSW_FOR_EACH_TRAVERSAL_LEAN(HNSW_DECLARE_SEARCH, M_UCOSH)
 HNSW_FOR_EACH_FILTERED(HNSW_DECLARE_FILTERED, M_SQ)
 HNSW_FOR_EACH_FILTERED(HNSW_DECLARE_FILTERED, M_COS)
 HNSW_FOR_EACH_FILTERED(HNSW_DECLARE_FILTERED, M_UCOS)
 HNSW_FOR_EACH_FILTERED(HNSW_DECLARE_FILTERED, M_I8)
+HNSW_FOR_EACH_FILTERED(HNSW_DECLARE_FILTERED, M_SQH)
+HNSW_FOR_EACH_FILTERED(HNSW_DECLARE_FILTERED, M_UCOSH)
 HNSW_FOR_EACH_MULTILAYER(HNSW_DECLARE_MULTILAYER, M_SQ)
 HNSW_FOR_EACH_MULTILAYER(HNSW_DECLARE_MULTILAYER, M_COS)
 HNSW_FOR_EACH_MULTILAYER(HNSW_DECLARE_MULTILAYER, M_UCOS)
 HNSW_FOR_EACH_MULTILAYER(HNSW_DECLARE_MULTILAYER, M_I8)
+HNSW_FOR_EACH_MULTILAYER(HNSW_DECLARE_MULTILAYER, M_SQH)
+HNSW_FOR_EACH_MULTILAYER(HNSW_DECLARE_MULTILAYER, M_UCOSH)
 #endif
 
 // ------------------------------------------------------------------------------------
@@ -222,6 +254,8 @@ static void with_metric(int metric, F &&f)
     case M_SQ: f(std::integral_constant<int, M_SQ>{}); break;
     case M_COS: f(std::integral_constant<int, M_COS>{}); break;
     case M_I8: f(std::integral_constant<int, M_I8>{}); break;
+    case M_SQH: f(std::integral_constant<int, M_SQH>{}); break;
+    case M_UCOSH: f(std::integral_constant<int, M_UCOSH>{}); break;
     default: f(std::integral_constant<int, M_UCOS>{}); break;
     }
 }
@@ -264,7 +298,7 @@ bool Device::bind()
 
 Device *Device::create(int device, int dim, int metric, long long capacity)
 {
-    if (dim <= 0 || metric < 0 || metric > 3 || capacity < 0) {
+    if (dim <= 0 || metric < 0 || metric > M_UCOSH || capacity < 0) {
         set_dev_error("hnswdev_create: bad argument");
         return nullptr;
     }
@@ -282,12 +316,14 @@ Device *Device::create(int device, int dim, int metric, long long capacity)
     Device *d = new Device();
     d->device_ = device;
     d->dim_ = dim;
-    // words per stored row: the floats themselves, or the int8 record (data words + scale + sumsq, a
+    // words per resident query and per stored f32 row: the floats themselves, or the int8 record (data words + scale + sumsq, a
     // multiple of 16 words = 64 B; device_kernels.h "int8 rows")
     d->pitch_ = metric == M_I8 ? (((dim + 3) / 4 + 2 + 15) & ~15) : dim;
+    // half-precision rows: the record of dk_base.h (32 B per 16 elements); queries and every LDS size stay those of `dim` floats
+    d->row_pitch_ = metric_f16(metric) ? f16_row_words(dim) : d->pitch_;
     d->metric_ = metric;
     // algorithmic bytes per evaluation: the row's elements, plus the 4-byte scale for int8
-    d->stats_.row_bytes = metric == M_I8 ? (uint64_t)dim + 4u : (uint64_t)dim * sizeof(float);
+    d->stats_.row_bytes = metric == M_I8 ? (uint64_t)dim + 4u : metric_f16(metric) ? (uint64_t)dim * 2u : (uint64_t)dim * sizeof(float);
     auto fail = [&]() -> Device * { delete d; return nullptr; };
     if (hipSetDevice(device) != hipSuccess) { set_dev_error("hipSetDevice failed"); return fail(); }
     hipStream_t st;
@@ -312,6 +348,7 @@ Device *Device::create_view(Device *primary)
     d->device_ = primary->device_;
     d->dim_ = primary->dim_;
     d->pitch_ = primary->pitch_;
+    d->row_pitch_ = primary->row_pitch_;
     d->metric_ = primary->metric_;
     d->stats_.row_bytes = primary->stats_.row_bytes;
     d->num_cu_ = primary->num_cu_;
@@ -380,10 +417,10 @@ bool Device::reserve(long long capacity)
     if (!bind()) return false;
     float *nr = nullptr;
     double *nsn = nullptr;
-    HIP_OK(hipMalloc(&nr, (size_t)capacity * pitch_ * sizeof(float)));
+    HIP_OK(hipMalloc(&nr, (size_t)capacity * row_pitch_ * sizeof(float)));
     if (metric_ == M_COS) HIP_OK(hipMalloc(&nsn, (size_t)capacity * sizeof(double)));
     if (d_rows_) {
-        HIP_OK(hipMemcpyAsync(nr, d_rows_, (size_t)capacity_ * pitch_ * sizeof(float), hipMemcpyDeviceToDevice, S(stream_)));
+        HIP_OK(hipMemcpyAsync(nr, d_rows_, (size_t)capacity_ * row_pitch_ * sizeof(float), hipMemcpyDeviceToDevice, S(stream_)));
         if (nsn) HIP_OK(hipMemcpyAsync(nsn, d_row_sn_, (size_t)capacity_ * sizeof(double), hipMemcpyDeviceToDevice, S(stream_)));
         HIP_OK(hipStreamSynchronize(S(stream_)));
         HIP_OK(hipFree(d_rows_));
@@ -403,13 +440,13 @@ bool Device::upload_rows(int first_id, int n, const float *rows)
         return false;
     }
     if (!bind()) return false;
-    {   // pageable -> pinned bounce buffer -> HBM, 64 MiB at a time (int8: through a float staging area on the
+    {   // pageable -> pinned bounce buffer -> HBM, 64 MiB at a time (int8 and f16 rows: through a float staging area on the
         // device, quantised into records there)
         const size_t row_bytes = (size_t)dim_ * sizeof(float);
         const size_t chunk_rows = std::max<size_t>(1, (64u << 20) / row_bytes);
         char *hs = static_cast<char *>(pinned_stage(std::min<size_t>((size_t)n, chunk_rows) * row_bytes));
         if (!hs) return false;
-        if (metric_ == M_I8 && !grow_dev(&q_stage_, &q_stage_cap_, std::min<size_t>((size_t)n, chunk_rows) * (size_t)dim_)) return false;
+        if ((metric_ == M_I8 || metric_f16(metric_)) && !grow_dev(&q_stage_, &q_stage_cap_, std::min<size_t>((size_t)n, chunk_rows) * (size_t)dim_)) return false;
         for (size_t r0 = 0; r0 < (size_t)n; r0 += chunk_rows) {
             const size_t nr = std::min(chunk_rows, (size_t)n - r0);
             memcpy(hs, rows + r0 * dim_, nr * row_bytes);
@@ -417,6 +454,11 @@ bool Device::upload_rows(int first_id, int n, const float *rows)
                 HIP_OK(hipMemcpyAsync(q_stage_, hs, nr * row_bytes, hipMemcpyHostToDevice, S(stream_)));
                 hipLaunchKernelGGL(quantize_rows_kernel, dim3((unsigned)((nr + 3) / 4)), dim3(256), 0, S(stream_), q_stage_, dim_, (int)nr, d_rows_,
                                    (long long)first_id + (long long)r0, pitch_);
+                HIP_OK(hipGetLastError());
+            } else if (metric_f16(metric_)) { // floats to the staging area, rounded into the resident records there
+                HIP_OK(hipMemcpyAsync(q_stage_, hs, nr * row_bytes, hipMemcpyHostToDevice, S(stream_)));
+                hipLaunchKernelGGL(pack_f16_rows_kernel, dim3((unsigned)((nr * (size_t)row_pitch_ + 255) / 256)), dim3(256), 0, S(stream_), q_stage_, dim_, (int)nr,
+                                   d_rows_, (long long)first_id + (long long)r0);
                 HIP_OK(hipGetLastError());
             } else {
                 HIP_OK(hipMemcpyAsync(d_rows_ + ((size_t)first_id + r0) * pitch_, hs, nr * row_bytes, hipMemcpyHostToDevice, S(stream_)));
@@ -434,6 +476,23 @@ bool Device::upload_rows(int first_id, int n, const float *rows)
     return true;
 }
 
+// float rows -> half-precision records on the host (the background upload): the device kernel's layout and rounding
+static void pack_f16_rows_host(unsigned *dst, const float *src, size_t n, int dim)
+{
+    const int pitch = f16_row_words(dim);
+    for (size_t r = 0; r < n; ++r) {
+        const float *x = src + r * (size_t)dim;
+        unsigned *rec = dst + r * (size_t)pitch;
+        for (int w = 0; w < pitch; ++w) {
+            const int i0 = ((w >> 3) << 4) | (w & 7), i1 = i0 + 8;
+            unsigned b0 = 0u, b1 = 0u;
+            if (i0 < dim) { memcpy(&b0, x + i0, 4); b0 = f32_to_f16_bits(b0); }
+            if (i1 < dim) { memcpy(&b1, x + i1, 4); b1 = f32_to_f16_bits(b1); }
+            rec[w] = b0 | (b1 << 16);
+        }
+    }
+}
+
 bool Device::upload_rows_begin(int first_id, int n, const float *rows)
 {
     if (n <= 0) return true;
@@ -448,19 +507,21 @@ bool Device::upload_rows_begin(int first_id, int n, const float *rows)
         bg_.stream = st;
         for (int i = 0; i < 2; ++i) { hipEvent_t e; HIP_OK(hipEventCreateWithFlags(&e, hipEventDisableTiming)); bg_.ev[i] = e; }
     }
-    if (bg_.pin_bytes < chunk_rows * row_bytes) {
+    const size_t pin_need = chunk_rows * std::max(row_bytes, (size_t)row_pitch_ * sizeof(float)); // (a half-precision record of a short row is longer than the row)
+    if (bg_.pin_bytes < pin_need) {
         for (int i = 0; i < 2; ++i) {
             if (bg_.pin[i]) (void)hipHostFree(bg_.pin[i]);
             bg_.pin[i] = nullptr;
-            HIP_OK(hipHostMalloc(&bg_.pin[i], chunk_rows * row_bytes, hipHostMallocDefault));
+            HIP_OK(hipHostMalloc(&bg_.pin[i], pin_need, hipHostMallocDefault));
         }
-        bg_.pin_bytes = chunk_rows * row_bytes;
+        bg_.pin_bytes = pin_need;
     }
     bg_.resident.store(first_id);
     bg_.failed.store(false);
     bg_.active.store(true);
     n_rows_hw_ = std::max(n_rows_hw_, (long long)first_id + n); // ids are valid from now on; their rows are awaited per batch
-    bg_.th = std::thread([this, first_id, n, rows, row_bytes, chunk_rows] {
+    const bool f16 = metric_f16(metric_); // the copy into the pinned buffer rounds the rows into records (half the bytes over the link)
+    bg_.th = std::thread([this, first_id, n, rows, row_bytes, chunk_rows, f16] {
         auto fail = [&](const char *what, hipError_t e) { bg_.err = std::string(what) + ": " + hipGetErrorString(e); bg_.failed.store(true); };
         hipError_t e = hipSetDevice(device_);
         if (e != hipSuccess) { fail("hipSetDevice", e); return; }
@@ -477,8 +538,9 @@ bool Device::upload_rows_begin(int first_id, int n, const float *rows)
                 bg_.resident.store(landed, std::memory_order_release);
                 in_flight[b] = false;
             }
-            memcpy(bg_.pin[b], rows + r0 * dim_, nr * row_bytes);
-            if ((e = hipMemcpyAsync(d_rows_ + ((size_t)first_id + r0) * pitch_, bg_.pin[b], nr * row_bytes, hipMemcpyHostToDevice, st)) != hipSuccess) { fail("hipMemcpyAsync", e); return; }
+            if (f16) pack_f16_rows_host(static_cast<unsigned *>(bg_.pin[b]), rows + r0 * dim_, nr, dim_);
+            else memcpy(bg_.pin[b], rows + r0 * dim_, nr * row_bytes);
+            if ((e = hipMemcpyAsync(d_rows_ + ((size_t)first_id + r0) * row_pitch_, bg_.pin[b], f16 ? nr * (size_t)row_pitch_ * sizeof(float) : nr * row_bytes, hipMemcpyHostToDevice, st)) != hipSuccess) { fail("hipMemcpyAsync", e); return; }
             if (metric_ == M_COS) {
                 const int blocks = (int)(((long long)nr * 8 + 255) / 256);
                 hipLaunchKernelGGL(row_sqrtnorm_kernel, dim3(blocks), dim3(256), 0, st, d_rows_, pitch_, (long long)first_id + (long long)r0, (int)nr, d_row_sn_);
@@ -524,6 +586,18 @@ bool Device::download_rows(int first_id, int n, float *rows)
                            (long long)first_id, n, dim_, q_stage_);
         HIP_OK(hipGetLastError());
         HIP_OK(hipMemcpyAsync(rows, q_stage_, (size_t)n * dim_ * sizeof(float), hipMemcpyDeviceToHost, S(stream_)));
+    } else if (metric_f16(metric_)) { // the stored rows widened to float: h(x), 64 MiB of floats at a time (Serialize downloads the whole
+        // index: a staging area of the whole f32 matrix would undo the halving)
+        const size_t chunk_rows = std::max<size_t>(1, (64u << 20) / ((size_t)dim_ * sizeof(float)));
+        if (!grow_dev(&q_stage_, &q_stage_cap_, std::min<size_t>((size_t)n, chunk_rows) * (size_t)dim_)) return false;
+        for (size_t r0 = 0; r0 < (size_t)n; r0 += chunk_rows) {
+            const size_t nr = std::min(chunk_rows, (size_t)n - r0);
+            hipLaunchKernelGGL(unpack_f16_rows_kernel, dim3((unsigned)((nr * (size_t)dim_ + 255) / 256)), dim3(256), 0, S(stream_), d_rows_,
+                               (long long)first_id + (long long)r0, (int)nr, dim_, q_stage_);
+            HIP_OK(hipGetLastError());
+            HIP_OK(hipMemcpyAsync(rows + r0 * (size_t)dim_, q_stage_, nr * (size_t)dim_ * sizeof(float), hipMemcpyDeviceToHost, S(stream_)));
+            HIP_OK(hipStreamSynchronize(S(stream_))); // (pageable destination: the copy has left the staging area when this returns)
+        }
     } else {
         HIP_OK(hipMemcpyAsync(rows, d_rows_ + (size_t)first_id * pitch_, (size_t)n * dim_ * sizeof(float), hipMemcpyDeviceToHost, S(stream_)));
     }
@@ -756,7 +830,7 @@ static bool peer_direct(int dst, int src)
 
 bool Device::clone_from(Device *src, long long pool_len)
 {
-    if (!src || src == this || src->dim_ != dim_ || src->metric_ != metric_ || src->pitch_ != pitch_) { set_dev_error("clone_from: contexts differ in shape"); return false; }
+    if (!src || src == this || src->dim_ != dim_ || src->metric_ != metric_ || src->pitch_ != pitch_ || src->row_pitch_ != row_pitch_) { set_dev_error("clone_from: contexts differ in shape"); return false; }
     if (pool_len < 0 || pool_len > src->g_pool_cap_) { set_dev_error("clone_from: bad pool length"); return false; }
     if (!src->sync()) return false; // what is copied must have landed
     if (!reserve(src->capacity_)) return false;
@@ -766,7 +840,7 @@ bool Device::clone_from(Device *src, long long pool_len)
     const long long have = std::min(n_rows_hw_, src->n_rows_hw_); // rows never change once uploaded (slot reuse re-clones: see HnswIndex)
     const long long more = src->n_rows_hw_ - have;
     if (more > 0) {
-        HIP_OK(hipMemcpyPeerAsync(d_rows_ + (size_t)have * pitch_, device_, src->d_rows_ + (size_t)have * pitch_, src->device_, (size_t)more * pitch_ * sizeof(float), st));
+        HIP_OK(hipMemcpyPeerAsync(d_rows_ + (size_t)have * row_pitch_, device_, src->d_rows_ + (size_t)have * row_pitch_, src->device_, (size_t)more * row_pitch_ * sizeof(float), st));
         if (metric_ == M_COS) HIP_OK(hipMemcpyPeerAsync(d_row_sn_ + have, device_, src->d_row_sn_ + have, src->device_, (size_t)more * sizeof(double), st));
     }
     const long long n = src->g_n_;
@@ -801,7 +875,7 @@ bool Device::clone_from(Device *src, long long pool_len)
     if (g_testedU_) HIP_OK(hipMemsetAsync(g_testedU_, 0, sizeof(int) * (size_t)g_pool_cap_, st));
     HIP_OK(hipStreamSynchronize(st));
     n_rows_hw_ = src->n_rows_hw_;
-    stats_.replica_bytes += (uint64_t)more * pitch_ * sizeof(float) + sizeof(int) * ((uint64_t)n * g_stride0_ + (uint64_t)n * 3 + (uint64_t)pool_len);
+    stats_.replica_bytes += (uint64_t)more * row_pitch_ * sizeof(float) + sizeof(int) * ((uint64_t)n * g_stride0_ + (uint64_t)n * 3 + (uint64_t)pool_len);
     (direct ? stats_.peer_direct_copies : stats_.peer_staged_copies) += 1;
     return true;
 }

@@ -65,6 +65,60 @@ __device__ __forceinline__ T kernarg_load(unsigned byte_offset)
     typedef const volatile T __attribute__((address_space(4))) *tptr;
     return *(tptr)((cptr)__builtin_amdgcn_kernarg_segment_ptr() + byte_offset);
 }
-enum { M_SQ = HNSWDEV_SQ_EUCLID, M_COS = HNSWDEV_COSINE, M_UCOS = HNSWDEV_UCOSINE, M_I8 = HNSWDEV_SQ_EUCLID_I8 };
+enum { M_SQ = HNSWDEV_SQ_EUCLID, M_COS = HNSWDEV_COSINE, M_UCOS = HNSWDEV_UCOSINE, M_I8 = HNSWDEV_SQ_EUCLID_I8,
+       M_SQH = HNSWDEV_SQ_EUCLID_F16, M_UCOSH = HNSWDEV_UCOSINE_F16 };
+
+// ---- half-precision row storage (M_SQH, M_UCOSH) --------------------------------------------------------
+// The arithmetic of X_f16 is X's, on stored rows widened from binary16 (exact): metric_is_sq / metric_is_ucos name the
+// arithmetic, metric_f16 the storage.  A stored row is a RECORD of row_words(dim) = 8 * ceil(dim / 16) 32-bit words (32 B
+// per 16 elements, zero padded): word 8 b + j holds element 16 b + j in its low half and element 16 b + 8 + j in its high
+// half -- so lane j of an 8-lane group reads one dword per TWO consecutive steps of its lane partial, and a lane of a pair
+// one 16-byte piece for four partials.  Queries (and rows staged in LDS) stay f32 in element order.  For the f32 metrics
+// every helper below is the expression it replaces.
+constexpr __host__ __device__ bool metric_f16(int m) { return m == M_SQH || m == M_UCOSH; }
+constexpr __host__ __device__ bool metric_is_sq(int m) { return m == M_SQ || m == M_SQH; }
+constexpr __host__ __device__ bool metric_is_ucos(int m) { return m == M_UCOS || m == M_UCOSH; }
+constexpr __host__ __device__ int metric_arith(int m) { return m == M_SQH ? (int)M_SQ : m == M_UCOSH ? (int)M_UCOS : m; }
+constexpr __host__ __device__ int f16_row_words(int dim) { return ((dim + 15) >> 4) << 3; }
+template <int METRIC>
+__host__ __device__ __forceinline__ int row_words(int dim) // `dim` as the kernels get it: elements (float metrics) or record words (int8)
+{
+    if constexpr (metric_f16(METRIC)) return f16_row_words(dim);
+    else return dim;
+}
+template <int METRIC>
+__device__ __forceinline__ const float *row_at(const float *__restrict__ rows, size_t id, int dim)
+{
+    if constexpr (metric_f16(METRIC)) return rows + id * (size_t)f16_row_words(dim);
+    else return rows + id * dim;
+}
+__device__ __forceinline__ float half_lo(unsigned w) { return (float)__builtin_bit_cast(_Float16, (unsigned short)(w & 0xffffu)); }
+__device__ __forceinline__ float half_hi(unsigned w) { return (float)__builtin_bit_cast(_Float16, (unsigned short)(w >> 16)); }
+// element i of a stored row
+template <int METRIC>
+__device__ __forceinline__ float row_elem(const float *__restrict__ rec, int i)
+{
+    if constexpr (metric_f16(METRIC)) {
+        const unsigned w = reinterpret_cast<const unsigned *>(rec)[((i >> 4) << 3) | (i & 7)];
+        return (i & 8) ? half_hi(w) : half_lo(w);
+    } else return rec[i];
+}
+// binary32 -> binary16 bits: round to nearest even, subnormals kept, beyond 65504 + half an ulp -> inf, NaN stays NaN (quiet), -0 stays -0
+// (numpy's astype(float16)); integer arithmetic, so host and device agree whatever the float modes.
+__host__ __device__ inline unsigned short f32_to_f16_bits(unsigned x)
+{
+    const unsigned sign = (x >> 16) & 0x8000u, a = x & 0x7fffffffu;
+    if (a >= 0x7f800000u) return (unsigned short)(sign | (a > 0x7f800000u ? 0x7e00u | ((a >> 13) & 0x3ffu) : 0x7c00u));
+    if (a >= 0x477ff000u) return (unsigned short)(sign | 0x7c00u); // >= 65520: rounds past the largest finite half
+    if (a >= 0x38800000u) { // normal half: rebias, round the 13 dropped bits to nearest even (a carry into the exponent is right)
+        const unsigned r = a - 0x38000000u;
+        return (unsigned short)(sign | ((r + 0xfffu + ((r >> 13) & 1u)) >> 13));
+    }
+    if (a < 0x33000000u) return (unsigned short)sign; // below 2^-25: to zero (2^-25 itself ties to even = 0)
+    const unsigned e = a >> 23, m = (a & 0x7fffffu) | 0x800000u; // subnormal half: m * 2^(e - 150) in units of 2^-24
+    const unsigned sh = 126u - e;                                 // 14 .. 24
+    const unsigned q = m >> sh, rem = m & ((1u << sh) - 1u), halfway = 1u << (sh - 1u);
+    return (unsigned short)(sign | (q + ((rem > halfway || (rem == halfway && (q & 1u))) ? 1u : 0u)));
+}
 
 } // namespace hnsw

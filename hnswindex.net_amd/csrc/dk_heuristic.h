@@ -186,6 +186,7 @@ __device__ __forceinline__ int relative_neighbor_pruning(const float *__restrict
     const bool prefetch = dim <= 64 * kPre;
     const int dimp = (dim + 3) & ~3;
     constexpr int kPreG = 4; // the grouped form prefetches four rows at once: rows up to 256 floats
+    // (half-precision rows: no prefilter -- the tile streams f32 rows; every decision there comes from the exact distances below)
     if constexpr (MFMA && (METRIC == M_UCOS || METRIC == M_COS || METRIC == M_SQ)) {
         // MFMA-prefiltered form (rows of a multiple of 8 floats, at least 256 of them: measured at C2's 128-float rows
         // the tiles cost more than the grouped form below -- insert kernel 0.94 s against 0.83 s -- at C3's 768 they
@@ -336,9 +337,9 @@ __device__ __forceinline__ int relative_neighbor_pruning(const float *__restrict
             {   // stage the first group
                 const int gsz = min(4, n);
                 for (int t = 0; t < gsz; ++t) {
-                    const float *crow = rows + (size_t)cands[t].id * dim;
+                    const float *crow = row_at<METRIC>(rows, (size_t)cands[t].id, dim);
                     float *dst = gq(t);
-                    for (int e = lane; e < dim; e += 64) dst[e] = crow[e];
+                    for (int e = lane; e < dim; e += 64) dst[e] = row_elem<METRIC>(crow, e);
                     if (METRIC == M_COS && lane == 0) sbq[t] = row_sn[cands[t].id];
                 }
                 wave_sync();
@@ -351,9 +352,9 @@ __device__ __forceinline__ int relative_neighbor_pruning(const float *__restrict
 #define HNSW_PRE_LOAD(T, PRE)                                                                          \
                 if (T < nsz) {                                                                         \
                     const int nid = cands[g0 + 4 + T].id;                                              \
-                    const float *nrow = rows + (size_t)nid * dim;                                      \
+                    const float *nrow = row_at<METRIC>(rows, (size_t)nid, dim);                        \
                     _Pragma("unroll") for (int e = 0; e < kPreG; ++e)                                  \
-                        if (64 * e < dim) PRE[e] = lane + 64 * e < dim ? nrow[lane + 64 * e] : 0.0f;   \
+                        if (64 * e < dim) PRE[e] = lane + 64 * e < dim ? row_elem<METRIC>(nrow, lane + 64 * e) : 0.0f;   \
                     if (METRIC == M_COS && lane == 0) sbq[4 + T] = row_sn[nid];                        \
                 }
                 HNSW_PRE_LOAD(0, pre0) HNSW_PRE_LOAD(1, pre1) HNSW_PRE_LOAD(2, pre2) HNSW_PRE_LOAD(3, pre3)
@@ -374,7 +375,7 @@ __device__ __forceinline__ int relative_neighbor_pruning(const float *__restrict
                     const bool live = pg < 6 && pt < gsz;
                     double sa = 0.0, sb = 0.0;
                     if (METRIC == M_COS) { sa = sbq[live ? pu : 0]; sb = sbq[live ? pt : 0]; }
-                    const float v = group_metric<METRIC>(gq(live ? pu : 0), gq(live ? pt : 0), dim, j, sa, sb);
+                    const float v = group_metric<METRIC, false, false>(gq(live ? pu : 0), gq(live ? pt : 0), dim, j, sa, sb); // (both staged in LDS: f32)
                     if (live && j == 0) P[pu * 4 + pt] = v;
                 }
                 wave_sync();
@@ -417,17 +418,17 @@ __device__ __forceinline__ int relative_neighbor_pruning(const float *__restrict
         const bool have_next = prefetch && i + 1 < n;
         if (have_next) {
             const int nid = cands[i + 1].id;
-            const float *nrow = rows + (size_t)nid * dim;
+            const float *nrow = row_at<METRIC>(rows, (size_t)nid, dim);
 #pragma unroll
             for (int t = 0; t < kPre; ++t)
-                if (64 * t < dim) pre[t] = lane + 64 * t < dim ? nrow[lane + 64 * t] : 0.0f;
+                if (64 * t < dim) pre[t] = lane + 64 * t < dim ? row_elem<METRIC>(nrow, lane + 64 * t) : 0.0f;
             if (METRIC == M_COS) sbn = row_sn[nid];
         }
         bool ok = true;
         if (rc > 0) {
             if (!prefetch) { // candidate i on demand
-                const float *crow = rows + (size_t)c.id * dim;
-                for (int t = lane; t < dim; t += 64) buf[cur][t] = crow[t];
+                const float *crow = row_at<METRIC>(rows, (size_t)c.id, dim);
+                for (int t = lane; t < dim; t += 64) buf[cur][t] = row_elem<METRIC>(crow, t);
                 if (METRIC == M_COS) sbc = row_sn[c.id];
                 wave_sync();
             }

@@ -50,10 +50,10 @@ __device__ __forceinline__ void insert_job(const float *__restrict__ rows, const
     SearchJob jb = jobs[job];
     const GraphView G{adj0, stride0, upper, pool, strideU};
     const int item = ~jb.qref;
-    const float *q = rows + (size_t)item * dim;
+    const float *q = row_at<METRIC>(rows, (size_t)item, dim);
     double sb = 0.0;
     if (METRIC == M_COS) sb = row_sn[item];
-    for (int i = lane; i < dim; i += 64) L.qs[i] = q[i];
+    for (int i = lane; i < dim; i += 64) L.qs[i] = row_elem<METRIC>(q, i);
     if constexpr (LAT) { if (lane == 0) port->m->sb = sb; }
     unsigned long long evals = 0;
     bool ok = true, repeat = false;
@@ -103,7 +103,7 @@ __device__ __forceinline__ void insert_job(const float *__restrict__ rows, const
 #endif
             // the candidate heap's LDS area is idle now: the grouped heuristic borrows it
             if constexpr (KA) cand_cap = HNSW_KAI(cand_cap);
-            rc = relative_neighbor_pruning<METRIC, NS == 8>(rows, row_sn, dim, L.top, top_n, max_edges, L, lane, evals, !exact,
+            rc = relative_neighbor_pruning<METRIC, NS == 8 && !metric_f16(METRIC)>(rows, row_sn, dim, L.top, top_n, max_edges, L, lane, evals, !exact,
 #ifdef HNSW_NO_GROUPED
                                                             nullptr, 0);
 #else

@@ -32,10 +32,10 @@ graph_relink_kernel(const float *__restrict__ rows, const double *__restrict__ r
     const int *cands = cands_all + cand_off[jd.w];
     const int ncand = cand_cnt[jd.w];
     const int max_edges = layer == 0 ? max_edges0 : (max_edges0 >> 1); // GraphData.MaxEdges :247-250
-    const float *q = rows + (size_t)aid * dim;
+    const float *q = row_at<METRIC>(rows, (size_t)aid, dim);
     double sb = 0.0;
     if (METRIC == M_COS) sb = row_sn[aid];
-    for (int i = lane; i < dim; i += 64) L.qs[i] = q[i];
+    for (int i = lane; i < dim; i += 64) L.qs[i] = row_elem<METRIC>(q, i);
     const int *l = G.list(aid, layer);
     int cnt = l[0];
     // RemoveOutEdge :104 (EdgeList.Remove, Node.cs:79-93: swap with the last)
@@ -135,10 +135,10 @@ __device__ __forceinline__ void link_group(const float *__restrict__ rows, const
     const int lane = threadIdx.x;
     const int max_edges = layer == 0 ? max_edges0 : (max_edges0 >> 1);
     int *l = layer == 0 ? adj0 + (size_t)node * stride0 : pool + upper[node] + (size_t)(layer - 1) * strideU;
-    const float *q = rows + (size_t)node * dim;
+    const float *q = row_at<METRIC>(rows, (size_t)node, dim);
     double sb = 0.0;
     if (METRIC == M_COS) sb = row_sn[node];
-    for (int i = lane; i < dim; i += 64) L.qs[i] = q[i];
+    for (int i = lane; i < dim; i += 64) L.qs[i] = row_elem<METRIC>(q, i);
     int cnt = l[0];
     for (int i = lane; i < cnt; i += 64) L.nbuf[i] = l[1 + i];
     int *tested_p = layer == 0 ? tested0 + node : testedU + (upper[node] / strideU + (layer - 1));
@@ -186,9 +186,9 @@ __device__ __forceinline__ void link_group(const float *__restrict__ rows, const
                     // distances of every new entry to all entries of the list
                     for (int jn = 0; jn < u; ++jn) {
                         const int xid = L.nbuf[tested + jn];
-                        const float *xrow = rows + (size_t)xid * dim;
+                        const float *xrow = row_at<METRIC>(rows, (size_t)xid, dim);
                         wave_sync();
-                        for (int t2 = lane; t2 < dim; t2 += 64) L.qs2[t2] = xrow[t2];
+                        for (int t2 = lane; t2 < dim; t2 += 64) L.qs2[t2] = row_elem<METRIC>(xrow, t2);
                         double sbx = 0.0;
                         if (METRIC == M_COS) sbx = row_sn[xid];
                         wave_sync();

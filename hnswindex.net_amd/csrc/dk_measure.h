@@ -41,7 +41,7 @@ __device__ __forceinline__ void measure_pass(const float *__restrict__ rows, con
             const float y = qs[8 * (k + kk) + j];
 #pragma unroll
             for (int p = 0; p < NP; ++p) {
-                if (METRIC == M_SQ) {
+                if (metric_is_sq(METRIC)) {
                     const float d = x[p][kk] - y;
                     acc[p] = __builtin_fmaf(d, d, acc[p]);
                 } else {
@@ -57,7 +57,7 @@ __device__ __forceinline__ void measure_pass(const float *__restrict__ rows, con
 #pragma unroll
         for (int p = 0; p < NP; ++p) {
             float x = a[p][8 * k + j];
-            if (METRIC == M_SQ) {
+            if (metric_is_sq(METRIC)) {
                 float d = x - y;
                 acc[p] = __builtin_fmaf(d, d, acc[p]);
             } else {
@@ -68,11 +68,11 @@ __device__ __forceinline__ void measure_pass(const float *__restrict__ rows, con
     }
 #pragma unroll
     for (int p = 0; p < NP; ++p) {
-        float s = (METRIC == M_SQ) ? collapse_l2(acc[p]) : collapse_cos(acc[p]);
+        float s = (metric_is_sq(METRIC)) ? collapse_l2(acc[p]) : collapse_cos(acc[p]);
         if (dim & 7) s = scalar_tail<METRIC>(s, a[p], qs, dim);
         float r;
-        if (METRIC == M_SQ) r = s;
-        else if (METRIC == M_UCOS) r = 1.0f - s;
+        if (metric_is_sq(METRIC)) r = s;
+        else if (metric_is_ucos(METRIC)) r = 1.0f - s;
         else {
             int id = nbuf[cidx[p] < m ? cidx[p] : p0];
             float denom = (float)(row_sn[id] * sb);
@@ -199,7 +199,7 @@ __device__ __forceinline__ void measure_pass2(const float *__restrict__ rows, co
     int k = 0;
     auto step = [&](const f32x4 x, const f32x4 y) {
         const f32x2 x01 = {x.x, x.y}, x23 = {x.z, x.w}, y01 = {y.x, y.y}, y23 = {y.z, y.w};
-        if (METRIC == M_SQ) {
+        if (metric_is_sq(METRIC)) {
             const f32x2 d01 = x01 - y01, d23 = x23 - y23;
             acc01 = __builtin_elementwise_fma(d01, d01, acc01);
             acc23 = __builtin_elementwise_fma(d23, d23, acc23);
@@ -232,11 +232,11 @@ __device__ __forceinline__ void measure_pass2(const float *__restrict__ rows, co
     const float t0 = acc01.x + dpp_pair_swap(acc01.x), t1 = acc01.y + dpp_pair_swap(acc01.y);
     const float t2 = acc23.x + dpp_pair_swap(acc23.x), t3 = acc23.y + dpp_pair_swap(acc23.y);
     float s;
-    if (METRIC == M_SQ) { const float u = t0 + t1, v = t2 + t3; s = u + v; }
+    if (metric_is_sq(METRIC)) { const float u = t0 + t1, v = t2 + t3; s = u + v; }
     else { const float u = t0 + t2, v = t1 + t3; s = u + v; }
     float res;
-    if (METRIC == M_SQ) res = s;
-    else if (METRIC == M_UCOS) res = 1.0f - s;
+    if (metric_is_sq(METRIC)) res = s;
+    else if (metric_is_ucos(METRIC)) res = 1.0f - s;
     else {
         const float denom = (float)(row_sn[id] * sb);
         res = (denom < 1e-30f) ? 1.0f : 1.0f - s / denom;
@@ -244,10 +244,182 @@ __device__ __forceinline__ void measure_pass2(const float *__restrict__ rows, co
     if (h == 0 && c < m) dbuf[c] = res;
 }
 
+// ---- half-precision records (dk_base.h): the passes above with half the loads ----------------------------------------
+// Lane j of a group reads word 8 b + j of 16-element block b: elements 16 b + j and 16 b + 8 + j, steps 2 b and 2 b + 1 of lane
+// partial j, widened (v_cvt_f32_f16: exact) and fed to the same operations in the same order.  All loads of a 128-element
+// chunk (8 words per row and lane) before any arithmetic.  An odd last 8-block uses the low halves of the last words only; the
+// elements past the last 8-block (the high or low halves next to it) go through the scalar tail, never through a lane chain.
+template <int METRIC>
+__device__ __forceinline__ void h_step(float &acc, float x, float y)
+{
+    if (metric_is_sq(METRIC)) { const float d = x - y; acc = __builtin_fmaf(d, d, acc); }
+    else { const float pr = x * y; acc = acc + pr; }
+}
+template <int METRIC>
+__device__ __forceinline__ float h_tail(float s, const float *rec, const float *qs, int dim)
+{
+    for (int i = dim & ~7; i < dim; ++i) {
+        const float x = row_elem<METRIC>(rec, i), y = qs[i];
+        if (metric_is_sq(METRIC)) { const float d = x - y; const float m = d * d; s = s + m; }
+        else { const float p = x * y; s = s + p; }
+    }
+    return s;
+}
+template <int METRIC, int NP>
+__device__ __forceinline__ void measure_pass_h(const float *__restrict__ rows, int dim, const float *qs, const int *nbuf, float *dbuf, int p0, int m, int lane)
+{
+    const int grp = lane >> 3, j = lane & 7;
+    const unsigned *a[NP];
+    int cidx[NP];
+    float acc[NP];
+#pragma unroll
+    for (int p = 0; p < NP; ++p) {
+        const int c = p0 + grp + 8 * p;
+        cidx[p] = c;
+        const int id = nbuf[c < m ? c : p0]; // idle groups shadow a valid row
+        a[p] = reinterpret_cast<const unsigned *>(row_at<METRIC>(rows, (size_t)id, dim));
+        acc[p] = 0.0f;
+    }
+    const int nblk = dim >> 3, npair = nblk >> 1;
+    int b = 0;
+    for (; b + 8 <= npair; b += 8) {
+        unsigned w[NP][8];
+#pragma unroll
+        for (int kk = 0; kk < 8; ++kk)
+#pragma unroll
+            for (int p = 0; p < NP; ++p) w[p][kk] = a[p][8 * (b + kk) + j];
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int kk = 0; kk < 8; ++kk) {
+            const float y0 = qs[16 * (b + kk) + j], y1 = qs[16 * (b + kk) + 8 + j];
+#pragma unroll
+            for (int p = 0; p < NP; ++p) h_step<METRIC>(acc[p], half_lo(w[p][kk]), y0);
+#pragma unroll
+            for (int p = 0; p < NP; ++p) h_step<METRIC>(acc[p], half_hi(w[p][kk]), y1);
+        }
+    }
+    if (b + 4 <= npair) {
+        unsigned w[NP][4];
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk)
+#pragma unroll
+            for (int p = 0; p < NP; ++p) w[p][kk] = a[p][8 * (b + kk) + j];
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk) {
+            const float y0 = qs[16 * (b + kk) + j], y1 = qs[16 * (b + kk) + 8 + j];
+#pragma unroll
+            for (int p = 0; p < NP; ++p) h_step<METRIC>(acc[p], half_lo(w[p][kk]), y0);
+#pragma unroll
+            for (int p = 0; p < NP; ++p) h_step<METRIC>(acc[p], half_hi(w[p][kk]), y1);
+        }
+        b += 4;
+    }
+#pragma unroll 2
+    for (; b < npair; ++b) {
+        const float y0 = qs[16 * b + j], y1 = qs[16 * b + 8 + j];
+        unsigned w[NP];
+#pragma unroll
+        for (int p = 0; p < NP; ++p) w[p] = a[p][8 * b + j];
+#pragma unroll
+        for (int p = 0; p < NP; ++p) h_step<METRIC>(acc[p], half_lo(w[p]), y0);
+#pragma unroll
+        for (int p = 0; p < NP; ++p) h_step<METRIC>(acc[p], half_hi(w[p]), y1);
+    }
+    if (nblk & 1) { // the last full 8-block: low halves of block npair
+        const float y0 = qs[16 * npair + j];
+#pragma unroll
+        for (int p = 0; p < NP; ++p) h_step<METRIC>(acc[p], half_lo(a[p][8 * npair + j]), y0);
+    }
+#pragma unroll
+    for (int p = 0; p < NP; ++p) {
+        float s = metric_is_sq(METRIC) ? collapse_l2(acc[p]) : collapse_cos(acc[p]);
+        if (dim & 7) s = h_tail<METRIC>(s, reinterpret_cast<const float *>(a[p]), qs, dim);
+        const float r = metric_is_sq(METRIC) ? s : 1.0f - s;
+        if (j == 0 && cidx[p] < m) dbuf[cidx[p]] = r;
+    }
+}
+// Two lanes per row (the latency form, see measure_pass2): lane 2 r + h reads words 4 h .. 4 h + 3 of every 16-element block in one
+// 16-byte load -- lane partials 4 h .. 4 h + 3, two steps each.  Rows of a multiple of 8 elements.
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+template <int METRIC>
+__device__ __forceinline__ void measure_pass2_h(const float *__restrict__ rows, int dim, const float *qs, const int *nbuf, float *dbuf, int p0, int m, int lane)
+{
+    const int r = lane >> 1, h = lane & 1;
+    const int c = p0 + r;
+    const int id = nbuf[c < m ? c : p0]; // idle pairs shadow a valid row
+    const unsigned *a = reinterpret_cast<const unsigned *>(row_at<METRIC>(rows, (size_t)id, dim)) + 4 * h;
+    const float *q = qs + 4 * h;
+    f32x2 acc01 = {0.0f, 0.0f}, acc23 = {0.0f, 0.0f}; // lane partials 4h + 0, 1 and 4h + 2, 3
+    const int nblk = dim >> 3, npair = nblk >> 1;
+    auto step = [&](const f32x2 x01, const f32x2 x23, const f32x4 y) {
+        const f32x2 y01 = {y.x, y.y}, y23 = {y.z, y.w};
+        if (metric_is_sq(METRIC)) {
+            const f32x2 d01 = x01 - y01, d23 = x23 - y23;
+            acc01 = __builtin_elementwise_fma(d01, d01, acc01);
+            acc23 = __builtin_elementwise_fma(d23, d23, acc23);
+        } else {
+            const f32x2 p01 = x01 * y01, p23 = x23 * y23;
+            acc01 = acc01 + p01;
+            acc23 = acc23 + p23;
+        }
+    };
+    auto lo_step = [&](const u32x4 w, int b) {
+        step(f32x2{half_lo(w.x), half_lo(w.y)}, f32x2{half_lo(w.z), half_lo(w.w)}, *reinterpret_cast<const f32x4 *>(q + 16 * b));
+    };
+    auto hi_step = [&](const u32x4 w, int b) {
+        step(f32x2{half_hi(w.x), half_hi(w.y)}, f32x2{half_hi(w.z), half_hi(w.w)}, *reinterpret_cast<const f32x4 *>(q + 16 * b + 8));
+    };
+    int b = 0;
+    for (; b + 8 <= npair; b += 8) { // one memory round trip per 128-element chunk
+        u32x4 w[8];
+#pragma unroll
+        for (int kk = 0; kk < 8; ++kk) w[kk] = *reinterpret_cast<const u32x4 *>(a + 8 * (b + kk));
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int kk = 0; kk < 8; ++kk) { lo_step(w[kk], b + kk); hi_step(w[kk], b + kk); }
+    }
+    if (b + 4 <= npair) {
+        u32x4 w[4];
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk) w[kk] = *reinterpret_cast<const u32x4 *>(a + 8 * (b + kk));
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk) { lo_step(w[kk], b + kk); hi_step(w[kk], b + kk); }
+        b += 4;
+    }
+#pragma unroll 2
+    for (; b < npair; ++b) { const u32x4 w = *reinterpret_cast<const u32x4 *>(a + 8 * b); lo_step(w, b); hi_step(w, b); }
+    if (nblk & 1) lo_step(*reinterpret_cast<const u32x4 *>(a + 8 * npair), npair);
+    const float t0 = acc01.x + dpp_pair_swap(acc01.x), t1 = acc01.y + dpp_pair_swap(acc01.y);
+    const float t2 = acc23.x + dpp_pair_swap(acc23.x), t3 = acc23.y + dpp_pair_swap(acc23.y);
+    float s;
+    if (metric_is_sq(METRIC)) { const float u = t0 + t1, v = t2 + t3; s = u + v; }
+    else { const float u = t0 + t2, v = t1 + t3; s = u + v; }
+    const float res = metric_is_sq(METRIC) ? s : 1.0f - s;
+    if (h == 0 && c < m) dbuf[c] = res;
+}
+
 template <int METRIC, bool TWO = false>
 __device__ __forceinline__ void measure_all(const float *rows, const double *row_sn, int dim, const float *qs, double sb,
                                             const int *nbuf, float *dbuf, int m, int lane)
 {
+    if constexpr (metric_f16(METRIC)) {
+        if constexpr (TWO) {
+            if (m > 8 && (dim & 7) == 0) {
+                for (int p0 = 0; p0 < m; p0 += 32) measure_pass2_h<METRIC>(rows, dim, qs, nbuf, dbuf, p0, m, lane);
+                return;
+            }
+        }
+        for (int p0 = 0; p0 < m; p0 += 32) {
+            const int left = m - p0;
+            if (left > 24) measure_pass_h<METRIC, 4>(rows, dim, qs, nbuf, dbuf, p0, m, lane);
+            else if (left > 16) measure_pass_h<METRIC, 3>(rows, dim, qs, nbuf, dbuf, p0, m, lane);
+            else if (left > 8) measure_pass_h<METRIC, 2>(rows, dim, qs, nbuf, dbuf, p0, m, lane);
+            else measure_pass_h<METRIC, 1>(rows, dim, qs, nbuf, dbuf, p0, m, lane);
+        }
+        return;
+    }
     if constexpr (METRIC != M_I8 && TWO) {
         if (m > 8 && (dim & 7) == 0) { // latency form: two lanes per row (up to 8 rows the eight-lane pass issues as few loads)
             for (int p0 = 0; p0 < m; p0 += 32) measure_pass2<METRIC>(rows, row_sn, dim, qs, sb, nbuf, dbuf, p0, m, lane);
@@ -312,7 +484,7 @@ __device__ __forceinline__ void measure_pass_multi(const float *__restrict__ row
                 const float y = qs[q][8 * (k + kk) + j];
 #pragma unroll
                 for (int p = 0; p < NP; ++p) {
-                    if (METRIC == M_SQ) {
+                    if (metric_is_sq(METRIC)) {
                         const float d = x[p][kk] - y;
                         acc[p][q] = __builtin_fmaf(d, d, acc[p][q]);
                     } else {
@@ -333,7 +505,7 @@ __device__ __forceinline__ void measure_pass_multi(const float *__restrict__ row
             const float y = qs[q][8 * k + j];
 #pragma unroll
             for (int p = 0; p < NP; ++p) {
-                if (METRIC == M_SQ) {
+                if (metric_is_sq(METRIC)) {
                     const float d = xr[p] - y;
                     acc[p][q] = __builtin_fmaf(d, d, acc[p][q]);
                 } else {
@@ -349,15 +521,87 @@ __device__ __forceinline__ void measure_pass_multi(const float *__restrict__ row
         if (METRIC == M_COS) sa = row_sn[ids[cidx[p] < m ? cidx[p] : p0]];
 #pragma unroll
         for (int q = 0; q < NQ; ++q) {
-            float s = (METRIC == M_SQ) ? collapse_l2(acc[p][q]) : collapse_cos(acc[p][q]);
+            float s = (metric_is_sq(METRIC)) ? collapse_l2(acc[p][q]) : collapse_cos(acc[p][q]);
             if (dim & 7) s = scalar_tail<METRIC>(s, a[p], qs[q], dim);
             float r;
-            if (METRIC == M_SQ) r = s;
-            else if (METRIC == M_UCOS) r = 1.0f - s;
+            if (metric_is_sq(METRIC)) r = s;
+            else if (metric_is_ucos(METRIC)) r = 1.0f - s;
             else {
                 const float denom = (float)(sa * sbq[q]);
                 r = (denom < 1e-30f) ? 1.0f : 1.0f - s / denom;
             }
+            if (j == 0 && cidx[p] < m) D[q * ds + cidx[p]] = r;
+        }
+    }
+}
+// measure_pass_multi on half-precision records (see measure_pass_h)
+template <int METRIC, int NP, int NQ>
+__device__ __forceinline__ void measure_pass_multi_h(const float *__restrict__ rows, int dim, const float *q0, const float *q1, const float *q2, const float *q3,
+                                                     const int *ids, float *D, int ds, int p0, int m, int lane)
+{
+    const int grp = lane >> 3, j = lane & 7;
+    const float *qs[4] = {q0, q1, q2, q3};
+    const unsigned *a[NP];
+    int cidx[NP];
+    float acc[NP][NQ];
+#pragma unroll
+    for (int p = 0; p < NP; ++p) {
+        const int c = p0 + grp + 8 * p;
+        cidx[p] = c;
+        const int id = ids[c < m ? c : p0];
+        a[p] = reinterpret_cast<const unsigned *>(row_at<METRIC>(rows, (size_t)id, dim));
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) acc[p][q] = 0.0f;
+    }
+    const int nblk = dim >> 3, npair = nblk >> 1;
+    int b = 0;
+    for (; b + 8 <= npair; b += 8) {
+        unsigned w[NP][8];
+#pragma unroll
+        for (int kk = 0; kk < 8; ++kk)
+#pragma unroll
+            for (int p = 0; p < NP; ++p) w[p][kk] = a[p][8 * (b + kk) + j];
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int kk = 0; kk < 8; ++kk) {
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) {
+                const float y0 = qs[q][16 * (b + kk) + j], y1 = qs[q][16 * (b + kk) + 8 + j];
+#pragma unroll
+                for (int p = 0; p < NP; ++p) { h_step<METRIC>(acc[p][q], half_lo(w[p][kk]), y0); h_step<METRIC>(acc[p][q], half_hi(w[p][kk]), y1); }
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+    for (; b < npair; ++b) {
+        unsigned w[NP];
+#pragma unroll
+        for (int p = 0; p < NP; ++p) w[p] = a[p][8 * b + j];
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) {
+            const float y0 = qs[q][16 * b + j], y1 = qs[q][16 * b + 8 + j];
+#pragma unroll
+            for (int p = 0; p < NP; ++p) { h_step<METRIC>(acc[p][q], half_lo(w[p]), y0); h_step<METRIC>(acc[p][q], half_hi(w[p]), y1); }
+        }
+    }
+    if (nblk & 1) {
+        unsigned w[NP];
+#pragma unroll
+        for (int p = 0; p < NP; ++p) w[p] = a[p][8 * npair + j];
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) {
+            const float y0 = qs[q][16 * npair + j];
+#pragma unroll
+            for (int p = 0; p < NP; ++p) h_step<METRIC>(acc[p][q], half_lo(w[p]), y0);
+        }
+    }
+#pragma unroll
+    for (int p = 0; p < NP; ++p) {
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) {
+            float s = metric_is_sq(METRIC) ? collapse_l2(acc[p][q]) : collapse_cos(acc[p][q]);
+            if (dim & 7) s = h_tail<METRIC>(s, reinterpret_cast<const float *>(a[p]), qs[q], dim);
+            const float r = metric_is_sq(METRIC) ? s : 1.0f - s;
             if (j == 0 && cidx[p] < m) D[q * ds + cidx[p]] = r;
         }
     }
@@ -369,6 +613,10 @@ __device__ __forceinline__ void measure_multi(const float *rows, const double *r
 #pragma nounroll
     for (int p0 = 0; p0 < m; p0 += 16) { // 16 rows x NQ vectors per pass: more rows in flight would spill (168 VGPRs)
         const int left = m - p0;
+        if constexpr (metric_f16(METRIC)) {
+            if (left > 8) measure_pass_multi_h<METRIC, 2, NQ>(rows, dim, q0, q1, q2, q3, ids, D, ds, p0, m, lane);
+            else measure_pass_multi_h<METRIC, 1, NQ>(rows, dim, q0, q1, q2, q3, ids, D, ds, p0, m, lane);
+        } else
         if (left > 8) measure_pass_multi<METRIC, 2, NQ>(rows, row_sn, dim, q0, q1, q2, q3, sbq, ids, D, ds, p0, m, lane);
         else measure_pass_multi<METRIC, 1, NQ>(rows, row_sn, dim, q0, q1, q2, q3, sbq, ids, D, ds, p0, m, lane);
     }

@@ -94,7 +94,7 @@ __device__ __forceinline__ float lane_chain(const float *__restrict__ a, const f
 #pragma unroll 8
     for (int k = 0; k < nblk; ++k) {
         float x = a[8 * k + j], y = b[8 * k + j];
-        if (METRIC == M_SQ) {
+        if (metric_is_sq(METRIC)) {
             float d = x - y;
             acc = __builtin_fmaf(d, d, acc); // Fma.MultiplyAdd, EuclideanMetric.cs:30
         } else {
@@ -111,7 +111,7 @@ __device__ __forceinline__ float scalar_tail(float s, const float *__restrict__ 
 {
     for (int i = dim & ~7; i < dim; ++i) {
         float x = a[i], y = b[i];
-        if (METRIC == M_SQ) {
+        if (metric_is_sq(METRIC)) {
             float d = x - y;
             float m = d * d;
             s = s + m; // EuclideanMetric.cs:53-57
@@ -145,11 +145,31 @@ __device__ inline double sqrt_rn(double x)
 
 // Full metric for one (row a, vector b) pair evaluated by an 8-lane group; every lane of the
 // group returns the same value.  sa/sb: precomputed sqrt((double)|.|^2) for cosine.
-template <int METRIC>
+// Half-precision rows: A_REC / B_REC say which operands are stored records (the other kind is an f32 vector in element order: a
+// query, a row staged in LDS); the lane chain, the collapse and the tail are those of the f32 metric on the widened elements.
+template <int METRIC, bool A_REC = true, bool B_REC = true>
 __device__ __forceinline__ float group_metric(const float *__restrict__ a, const float *__restrict__ b, int dim, int j,
                                               double sa, double sb)
 {
-    if constexpr (METRIC == M_I8) { // dim = record pitch in words; the last block's lanes 6 / 7 hold scale / sumsq
+    if constexpr (metric_f16(METRIC)) {
+        auto ea = [&](int i) -> float { if constexpr (A_REC) return row_elem<METRIC>(a, i); else return a[i]; };
+        auto eb = [&](int i) -> float { if constexpr (B_REC) return row_elem<METRIC>(b, i); else return b[i]; };
+        const int nblk = dim >> 3;
+        float acc = 0.0f;
+        for (int k = 0; k < nblk; ++k) {
+            const float x = ea(8 * k + j), y = eb(8 * k + j);
+            if (metric_is_sq(METRIC)) { const float d = x - y; acc = __builtin_fmaf(d, d, acc); }
+            else { const float p = x * y; acc = acc + p; }
+        }
+        float s = metric_is_sq(METRIC) ? collapse_l2(acc) : collapse_cos(acc);
+        for (int i = dim & ~7; i < dim; ++i) { // the scalar tail: never through a lane chain
+            const float x = ea(i), y = eb(i);
+            if (metric_is_sq(METRIC)) { const float d = x - y; const float m = d * d; s = s + m; }
+            else { const float p = x * y; s = s + p; }
+        }
+        return metric_is_sq(METRIC) ? s : 1.0f - s;
+    }
+    else if constexpr (METRIC == M_I8) { // dim = record pitch in words; the last block's lanes 6 / 7 hold scale / sumsq
         const int *ia = reinterpret_cast<const int *>(a), *ib = reinterpret_cast<const int *>(b);
         const int nblk = dim >> 3, lane = threadIdx.x & 63;
         int acc = 0, ta = 0, tb = 0;
@@ -164,10 +184,10 @@ __device__ __forceinline__ float group_metric(const float *__restrict__ a, const
     }
     else {
     float p = lane_chain<METRIC>(a, b, dim, j);
-    float s = (METRIC == M_SQ) ? collapse_l2(p) : collapse_cos(p);
+    float s = (metric_is_sq(METRIC)) ? collapse_l2(p) : collapse_cos(p);
     if (dim & 7) s = scalar_tail<METRIC>(s, a, b, dim);
-    if (METRIC == M_SQ) return s;
-    if (METRIC == M_UCOS) return 1.0f - s; // CosineMetric.cs:141
+    if (metric_is_sq(METRIC)) return s;
+    if (metric_is_ucos(METRIC)) return 1.0f - s; // CosineMetric.cs:141
     float denom = (float)(sa * sb);        // :88  (float)(Math.Sqrt(nA) * Math.Sqrt(nB))
     if (denom < 1e-30f) return 1.0f;       // :89-90
     return 1.0f - s / denom;               // :91
@@ -207,7 +227,7 @@ slot_distance_kernel(const float *__restrict__ rows, const double *__restrict__ 
         q = queries + (size_t)qraw * dim;
         if (METRIC == M_COS) sb = q_sn[qraw];
     } else {
-        q = rows + (size_t)(~qraw) * dim;
+        q = row_at<METRIC>(rows, (size_t)(~qraw), dim);
         if (METRIC == M_COS) sb = row_sn[~qraw];
     }
     const int grp = lane >> 3, j = lane & 7;
@@ -220,7 +240,11 @@ slot_distance_kernel(const float *__restrict__ rows, const double *__restrict__ 
         if (bad) id = 0;
         double sa = 0.0;
         if (METRIC == M_COS) sa = row_sn[id];
-        float v = group_metric<METRIC>(rows + (size_t)id * dim, q, dim, j, sa, sb);
+        float v;
+        if constexpr (metric_f16(METRIC)) // (a resident query is f32, a row used as the query is a record)
+            v = qraw >= 0 ? group_metric<METRIC, true, false>(row_at<METRIC>(rows, (size_t)id, dim), q, dim, j, sa, sb)
+                          : group_metric<METRIC, true, true>(row_at<METRIC>(rows, (size_t)id, dim), q, dim, j, sa, sb);
+        else v = group_metric<METRIC>(rows + (size_t)id * dim, q, dim, j, sa, sb);
         if (act && j == 0) {
             so[c] = bad ? __uint_as_float(0x7fc00000u) : v;
             if (bad) atomicOr(guard, 1);

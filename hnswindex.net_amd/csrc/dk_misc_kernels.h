@@ -20,7 +20,7 @@ pair_distance_kernel(const float *__restrict__ rows, const double *__restrict__ 
     if (bad) { a = 0; b = 0; }
     double sa = 0.0, sb = 0.0;
     if (METRIC == M_COS) { sa = row_sn[a]; sb = row_sn[b]; }
-    float r = group_metric<METRIC>(rows + (size_t)a * dim, rows + (size_t)b * dim, dim, j, sa, sb);
+    float r = group_metric<METRIC>(row_at<METRIC>(rows, (size_t)a, dim), row_at<METRIC>(rows, (size_t)b, dim), dim, j, sa, sb);
     if (act && j == 0) {
         out[g] = bad ? __uint_as_float(0x7fc00000u) : r;
         if (bad) atomicOr(guard, 1);
@@ -92,6 +92,30 @@ dequantize_rows_kernel(const float *__restrict__ recs, int pitch, long long firs
     const int *rec = reinterpret_cast<const int *>(recs + (size_t)(first + r) * pitch);
     const int q = (int)(signed char)((rec[i >> 2] >> (8 * (i & 3))) & 0xff);
     out[t] = (float)q * __int_as_float(rec[pitch - 2]);
+}
+#endif
+#ifdef HNSW_HOST_TU
+// float rows -> half-precision records (dk_base.h): one thread per record word; padding halves are zero
+__global__ void __launch_bounds__(256)
+pack_f16_rows_kernel(const float *__restrict__ src, int dim, int n, float *__restrict__ dst, long long first)
+{
+    const int pitch = f16_row_words(dim);
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= (long long)n * pitch) return;
+    const int r = (int)(t / pitch), w = (int)(t % pitch);
+    const int i0 = ((w >> 3) << 4) | (w & 7), i1 = i0 + 8;
+    const float *x = src + (size_t)r * dim;
+    const unsigned lo = i0 < dim ? f32_to_f16_bits(__float_as_uint(x[i0])) : 0u, hi = i1 < dim ? f32_to_f16_bits(__float_as_uint(x[i1])) : 0u;
+    reinterpret_cast<unsigned *>(dst)[(size_t)(first + r) * pitch + w] = lo | (hi << 16);
+}
+// records -> the stored rows widened to float (hnswdev_download_rows on a half-precision context)
+__global__ void __launch_bounds__(256)
+unpack_f16_rows_kernel(const float *__restrict__ recs, long long first, int n, int dim, float *__restrict__ out)
+{
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= (long long)n * dim) return;
+    const int r = (int)(t / dim), i = (int)(t % dim);
+    out[t] = row_elem<M_SQH>(recs + (size_t)(first + r) * f16_row_words(dim), i);
 }
 #endif
 #ifdef HNSW_HOST_TU // non-template kernels: only the unit that launches them defines them

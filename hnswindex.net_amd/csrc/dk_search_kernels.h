@@ -113,9 +113,13 @@ __device__ __forceinline__ void search_job(const float *__restrict__ rows, const
         q = queries + (size_t)jb.qref * dim;
         if (METRIC == M_COS) sb = q_sn[jb.qref];
     } else {
-        q = rows + (size_t)(~jb.qref) * dim;
+        q = row_at<METRIC>(rows, (size_t)(~jb.qref), dim);
         if (METRIC == M_COS) sb = row_sn[~jb.qref];
     }
+    if constexpr (metric_f16(METRIC)) { // a stored row as the query is unpacked to f32; a query is f32 as it is
+        if (jb.qref >= 0) for (int i = lane; i < dim; i += 64) L.qs[i] = q[i];
+        else for (int i = lane; i < dim; i += 64) L.qs[i] = row_elem<METRIC>(q, i);
+    } else
     for (int i = lane; i < dim; i += 64) L.qs[i] = q[i];
     if constexpr (LAT) { if (lane == 0) port->m->sb = sb; } // (the memory wave reads both after the first request's release)
     unsigned long long evals = 0;

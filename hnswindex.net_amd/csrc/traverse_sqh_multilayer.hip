@@ -1,0 +1,7 @@
+// traverse_sqh_multilayer.hip -- instantiates graph_multilayer_kernel for M_SQH (sq_euclid on half-precision rows) (MultiLayerKnnQuery's chain of searches; both
+// visited-set representations).  Device code: device_kernels.h; the split exists for build time.
+#include "device_kernels.h"
+
+namespace hnsw {
+HNSW_FOR_EACH_MULTILAYER(HNSW_DEFINE_MULTILAYER, M_SQH)
+} // namespace hnsw

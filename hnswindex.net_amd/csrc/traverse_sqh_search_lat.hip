@@ -1,0 +1,8 @@
+// traverse_sqh_search_lat.hip -- instantiates the latency variants of graph_search_kernel for M_SQH (sq_euclid on half-precision rows) (launches that do
+// not fill the chip: device_kernels.h, LAT).  Device code: device_kernels.h; the split exists for build time.
+#include "device_kernels.h"
+
+namespace hnsw {
+HNSW_FOR_EACH_TRAVERSAL_LAT(HNSW_DEFINE_SEARCH, M_SQH)
+} // namespace hnsw
+HNSW_PHASE_BIND(sqh_search_lat)

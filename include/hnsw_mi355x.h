@@ -295,8 +295,11 @@ int hnsw_mi355x_set_profiling(void *handle, int enabled);
  * int8-quantised rows with one float scale per row (BASELINE config 5; no reference counterpart) -- rows and
  * queries still cross the boundary as float32 and are quantised on the device, q = rint(x / scale), scale =
  * max|x| / 127; the distance is that of the dequantised vectors, computed from the exact int32 dot product
- * (metric name "sq_euclid_i8" for hnsw_create). */
-enum { HNSWDEV_SQ_EUCLID = 0, HNSWDEV_COSINE = 1, HNSWDEV_UCOSINE = 2, HNSWDEV_SQ_EUCLID_I8 = 3 };
+ * (metric name "sq_euclid_i8" for hnsw_create).  4, 5: sq_euclid / ucosine on rows STORED as IEEE binary16 ("sq_euclid_f16",
+ * "ucosine_f16"): a row is rounded element by element (nearest even, subnormals kept, beyond 65504 -> inf: numpy's
+ * astype(float16)) when it is uploaded, queries stay float32, and every distance is metric 0 / 2 on the rounded rows, bit for
+ * bit; hnswdev_download_rows returns the rounded rows as floats, hnswdev_stats.row_bytes is 2 * dim. */
+enum { HNSWDEV_SQ_EUCLID = 0, HNSWDEV_COSINE = 1, HNSWDEV_UCOSINE = 2, HNSWDEV_SQ_EUCLID_I8 = 3, HNSWDEV_SQ_EUCLID_F16 = 4, HNSWDEV_UCOSINE_F16 = 5 };
 
 typedef struct hnswdev_stats {
     uint64_t launches;      /* distance-kernel launches */
@@ -304,7 +307,7 @@ typedef struct hnswdev_stats {
     uint64_t timed_launches;/* launches bracketed by HIP events (profiling on) */
     uint64_t timed_evals;   /* evaluations inside those launches */
     double kernel_ms;       /* sum of HIP-event durations of the timed launches */
-    uint64_t row_bytes;     /* dim * sizeof(float): algorithmic bytes per evaluation */
+    uint64_t row_bytes;     /* dim * sizeof(float) (2 * dim for the _f16 metrics): algorithmic bytes per evaluation */
     /* graph-resident search kernel (traversal on the device) */
     uint64_t search_launches;
     uint64_t search_evals;        /* distance evaluations inside those launches (device-counted) */
