@@ -41,7 +41,10 @@ _I = ct.POINTER(ct.c_int)
 
 
 class Stats(ct.Structure):
-    """hnswdev_stats (include/hnsw_mi355x.h)."""
+    """The FIRST PART of hnswdev_stats (include/hnsw_mi355x.h): the counters up to multilayer_handbacks.  NOT large enough to
+    pass to hnswdev_get_stats / hnsw_mi355x_get_stats, which write the whole C struct: pass a DeviceStats (below), as every
+    call in this module does -- the argtypes of the three get_stats functions take POINTER(DeviceStats), so ctypes refuses
+    byref(Stats()) with an ArgumentError instead of letting the library write 40 bytes past it."""
     _fields_ = [("launches", ct.c_uint64), ("evals", ct.c_uint64), ("timed_launches", ct.c_uint64),
                 ("timed_evals", ct.c_uint64), ("kernel_ms", ct.c_double), ("row_bytes", ct.c_uint64),
                 ("search_launches", ct.c_uint64), ("search_evals", ct.c_uint64), ("search_timed_launches", ct.c_uint64),
@@ -59,7 +62,19 @@ class Stats(ct.Structure):
                 ("multilayer_launches", ct.c_uint64), ("multilayer_jobs", ct.c_uint64), ("multilayer_handbacks", ct.c_uint64)]
 
     def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
+        return {k: getattr(self, k) for c in reversed(type(self).__mro__) for k, _ in c.__dict__.get("_fields_", ())}
+
+
+class DeviceStats(Stats):
+    """The whole of hnswdev_stats: `Stats` (the struct as it stood before the flat scan; its layout is pinned) followed by the
+    counters appended to the C struct since -- a ctypes subclass lays its own fields out behind its base's, as the header
+    appends them.  Every get_stats call of this module fills one of these."""
+    _fields_ = [("exact_launches", ct.c_uint64), ("exact_evals", ct.c_uint64), ("exact_timed_launches", ct.c_uint64),
+                ("exact_timed_evals", ct.c_uint64), ("exact_kernel_ms", ct.c_double)]
+
+    @classmethod
+    def field_names(cls):
+        return [k for c in reversed(cls.__mro__) for k, _ in c.__dict__.get("_fields_", ())]
 
 
 # ---- (A) the reference's 16 exports: bindings.py:45-119 ---------------------------------
@@ -102,6 +117,8 @@ lib.hnsw_mi355x_knn_query_resident.argtypes = [ct.c_void_p, ct.c_int, _I, _F]
 _U32 = ct.POINTER(ct.c_uint32)
 lib.hnsw_mi355x_knn_query_filtered.restype = ct.c_int
 lib.hnsw_mi355x_knn_query_filtered.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_int, ct.c_int, _U32, ct.c_longlong, _I, _F]
+lib.hnsw_mi355x_exact_knn_query.restype = ct.c_int
+lib.hnsw_mi355x_exact_knn_query.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_int, ct.c_int, _U32, ct.c_longlong, _I, _F]
 lib.hnsw_mi355x_range_query_filtered.restype = ct.c_int
 lib.hnsw_mi355x_range_query_filtered.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_int, ct.c_float, _U32, ct.c_longlong, ct.POINTER(ct.c_void_p),
                                                  ct.POINTER(ct.c_void_p), ct.POINTER(ct.c_int)]
@@ -131,7 +148,7 @@ lib.hnsw_mi355x_deserialize.argtypes = [ct.c_char_p, ct.c_char_p]
 lib.hnsw_mi355x_graph_hash.restype = ct.c_uint64
 lib.hnsw_mi355x_graph_hash.argtypes = [ct.c_void_p]
 lib.hnsw_mi355x_get_stats.restype = ct.c_int
-lib.hnsw_mi355x_get_stats.argtypes = [ct.c_void_p, ct.POINTER(Stats)]
+lib.hnsw_mi355x_get_stats.argtypes = [ct.c_void_p, ct.POINTER(DeviceStats)]
 lib.hnsw_mi355x_set_profiling.restype = ct.c_int
 lib.hnsw_mi355x_set_profiling.argtypes = [ct.c_void_p, ct.c_int]
 lib.hnsw_mi355x_index_set_insert_batch.restype = ct.c_int
@@ -143,7 +160,7 @@ lib.hnsw_mi355x_host_parallelism.argtypes = []
 lib.hnsw_mi355x_device_count.restype = ct.c_int
 lib.hnsw_mi355x_device_count.argtypes = [ct.c_void_p]
 lib.hnsw_mi355x_get_stats_at.restype = ct.c_int
-lib.hnsw_mi355x_get_stats_at.argtypes = [ct.c_void_p, ct.c_int, ct.POINTER(Stats)]
+lib.hnsw_mi355x_get_stats_at.argtypes = [ct.c_void_p, ct.c_int, ct.POINTER(DeviceStats)]
 lib.hnsw_mi355x_build_id.restype = ct.c_char_p
 lib.hnsw_mi355x_build_id.argtypes = []
 lib.hnsw_mi355x_exact_window_stats.restype = ct.c_int
@@ -169,6 +186,8 @@ lib.hnswdev_knn_search_filtered.restype = ct.c_int
 lib.hnswdev_knn_search_filtered.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_int, ct.c_int, ct.c_int, _U32, ct.c_longlong, _I, _F, _I]
 lib.hnswdev_range_search.restype = ct.c_int
 lib.hnswdev_range_search.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_int, ct.c_float, _I, _I]
+lib.hnswdev_exact_knn.restype = ct.c_int
+lib.hnswdev_exact_knn.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_longlong, ct.c_int, _U32, ct.c_longlong, _I, _F]
 lib.hnswdev_range_search_filtered.restype = ct.c_int
 lib.hnswdev_range_search_filtered.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_int, ct.c_float, _U32, ct.c_longlong, _I, _I]
 lib.hnswdev_range_results.restype = ct.c_int
@@ -181,7 +200,7 @@ lib.hnswdev_multilayer_search.restype = ct.c_int
 lib.hnswdev_multilayer_search.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int, _I, _F, _I]
 lib.hnswdev_sync.argtypes = [ct.c_void_p]
 lib.hnswdev_set_profiling.argtypes = [ct.c_void_p, ct.c_int]
-lib.hnswdev_get_stats.argtypes = [ct.c_void_p, ct.POINTER(Stats)]
+lib.hnswdev_get_stats.argtypes = [ct.c_void_p, ct.POINTER(DeviceStats)]
 lib.hnswdev_reset_stats.argtypes = [ct.c_void_p]
 lib.hnswdev_last_error.argtypes = [ct.c_char_p, ct.c_int]
 lib.hnswdev_ctx_last_error.argtypes = [ct.c_void_p, ct.c_char_p, ct.c_int]
@@ -356,7 +375,7 @@ class Index:
         self._check(lib.hnsw_mi355x_set_devices(n))
 
     def stats_at(self, context: int):
-        st = Stats()
+        st = DeviceStats()
         if not self._h or lib.hnsw_mi355x_get_stats_at(self._h, context, ct.byref(st)) != 0:
             raise RuntimeError(last_error() or "no such device context")
         return st.as_dict()
@@ -453,6 +472,22 @@ class Index:
         if status < 0:
             raise RuntimeError(last_error())
         return ids, dists  # freshly allocated above (the reference returns copies of equally fresh arrays, bindings.py:521)
+
+    def exact_knn_query(self, queries: npt.ArrayLike, k: int, allowed=None) -> Tuple[npt.NDArray[np.int32], npt.NDArray[np.float32]]:
+        """The k live (and, with `allowed`, allowed) ids of smallest distance per query, ascending by (distance, id), from a flat
+        scan on the device (hnsw_mi355x_exact_knn_query): exact, independent of the graph.  allowed: as for knn_query.
+        1 <= k <= 1024; rows that run out of candidates are padded with -1 / NaN."""
+        q = _as_2d_f32(queries, self.dim)
+        n = int(q.shape[0])
+        ids = np.full((n, max(k, 0)), -1, dtype=np.int32)   # (an index nothing was added to has no native handle yet: padding)
+        dists = np.full((n, max(k, 0)), np.nan, dtype=np.float32)
+        words, nbits = allow_bits(allowed) if allowed is not None else (None, 0)
+        words, wp = _words_arg(words) if allowed is not None else (None, None)
+        status = lib.hnsw_mi355x_exact_knn_query(self._h, q.ctypes.data_as(_F), n, self.dim, k, wp, nbits, ids.ctypes.data_as(_I),
+                                                 dists.ctypes.data_as(_F))
+        if status < 0:
+            raise RuntimeError(last_error())
+        return ids, dists
 
     def range_query(self, queries: npt.ArrayLike, radius: float,
                     allowed=None, layer: int = 0) -> Tuple[List[npt.NDArray[np.int32]], List[npt.NDArray[np.float32]]]:
@@ -616,7 +651,7 @@ class Index:
         lib.hnsw_mi355x_set_profiling(self._h, int(on))
 
     def stats(self) -> dict:
-        s = Stats()
+        s = DeviceStats()
         if self._h:
             lib.hnsw_mi355x_get_stats(self._h, ct.byref(s))
         return s.as_dict()
@@ -741,6 +776,19 @@ class DeviceBackend:
                                            ids.ctypes.data_as(_I), d.ctypes.data_as(_F), flags.ctypes.data_as(_I)))
         return ids, d, flags
 
+    def exact_knn(self, queries, k: int, n_rows=None, allowed=None):
+        """hnswdev_exact_knn: (ids, dists) of shape [nq, k], per query the k uploaded rows of smallest (distance, id) among rows
+        [0, n_rows) (None: every uploaded row) that `allowed` allows (as for Index.knn_query; None: all).  A flat scan: no graph."""
+        q = _as_2d_f32(queries, self.dim)
+        n = q.shape[0]
+        ids = np.empty((n, k), dtype=np.int32)
+        d = np.empty((n, k), dtype=np.float32)
+        words, nbits = allow_bits(allowed) if allowed is not None else (None, 0)
+        words, wp = _words_arg(words) if allowed is not None else (None, None)
+        self._check(lib.hnswdev_exact_knn(self._ctx, q.ctypes.data_as(_F), n, (1 << 62) if n_rows is None else int(n_rows), int(k), wp, nbits,
+                                          ids.ctypes.data_as(_I), d.ctypes.data_as(_F)))
+        return ids, d
+
     def multilayer_search(self, queries, entry_point: int, k: int, max_layer=None, min_layer: int = 0, layers_cap=None):
         """hnswdev_multilayer_search: (ids, dists, flags), ids / dists of shape [nq, nlayers, k - 1] as Index.multilayer_knn_query;
         flags[i] = 1: query i was handed back."""
@@ -788,7 +836,7 @@ class DeviceBackend:
         self._check(lib.hnswdev_set_profiling(self._ctx, int(on)))
 
     def stats(self) -> dict:
-        s = Stats()
+        s = DeviceStats()
         self._check(lib.hnswdev_get_stats(self._ctx, ct.byref(s)))
         return s.as_dict()
 

@@ -17,6 +17,7 @@ SOURCES = ["device_backend.hip", *[f"traverse_{m}_{k}{v}.hip" for m in METRIC_UN
            *[f"traverse_{m}_search_lean.hip" for m in METRIC_UNITS],
            *[f"traverse_{m}_filtered.hip" for m in METRIC_UNITS],
            *[f"traverse_{m}_multilayer.hip" for m in METRIC_UNITS],
+           *[f"exact_{m}.hip" for m in METRIC_UNITS],  # the flat scan (dk_exact.h); exact_sq.hip also holds its metric-independent kernels
            "search_engine.cpp", "hnsw_index.cpp", "exports.cpp"]
 # -ffp-contract=off: the kernels fuse a*b+c only where __builtin_fmaf is written -- the
 # reference's AVX path fuses in sq_euclid (Fma.MultiplyAdd) and nowhere else.

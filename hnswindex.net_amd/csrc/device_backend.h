@@ -271,6 +271,12 @@ public:
     bool range_search_filtered(const float *queries, int nq, int entry_point, float range, const uint32_t *allow_bits, long long nbits,
                                int *out_counts, int *out_flags, int layer = 0);
     bool range_results(int *out_ids, float *out_d);
+    // hnswdev_exact_knn (dk_exact.h): for each query the k uploaded rows of smallest (distance, id) among ids
+    // [0, min(n_rows, uploaded)) that allow_bits allows (nullptr: all of them; else nbits bits as for search_filtered), ascending,
+    // padded with -1 / NaN (nbits is ignored without a bitset).  A flat scan: no graph is read.  queries == nullptr: the resident
+    // set (nq of its rows); otherwise the queries are staged by set_queries' code into a buffer of the scan's own and the
+    // resident set stays what it was.  1 <= k <= 1024.  Synchronous.
+    bool exact_knn(const float *queries, int nq, long long n_rows, int k, const uint32_t *allow_bits, long long nbits, int *out_ids, float *out_d);
 
     void set_profiling(bool on) { profiling_ = on; }
 
@@ -373,6 +379,19 @@ private:
     size_t s_fspill_cap_ = 0;
     unsigned *s_allow_ = nullptr;   // filtered searches: the call's allow-set
     size_t s_allow_cap_ = 0;
+    int *x_ids_ = nullptr;                 // exact_knn: the call's ascending id list (exact_compact_kernel)
+    size_t x_ids_cap_ = 0;
+    long long *x_boff_ = nullptr;          // ... set bits in front of each block of bitset words
+    size_t x_boff_cap_ = 0;
+    unsigned long long *x_lists_ = nullptr; // ... the per-(query, chunk) lists of a round: at most 1 GiB, allocated by the first call and kept
+    size_t x_lists_cap_ = 0;
+    int *x_out_ = nullptr;                 // ... a round's [ids | distances]
+    size_t x_out_cap_ = 0;
+    unsigned long long *x_evals_ = nullptr; // ... (query, row) pairs the scan kernel measured, counted on the device
+    size_t x_evals_cap_ = 0;
+    float *x_queries_ = nullptr;           // ... its own query set (set_queries writes it while it stands in for d_queries_)
+    double *x_q_sn_ = nullptr;
+    long long x_q_capacity_ = 0;
     SearchHit *s_arena_ = nullptr; // range search: the launch's results, packed
     size_t s_arena_cap_ = 0;
     unsigned long long *s_roff_ = nullptr, *s_arena_used_ = nullptr;

@@ -49,6 +49,7 @@
 #include "diag.h"
 #define HNSW_HOST_TU
 #include "device_kernels.h"
+#include "dk_exact.h"
 #include "range_replay.h"
 
 namespace hnsw {
@@ -394,7 +395,7 @@ Device::~Device()
     phase_report("teardown");
 #endif
     for (void *p : {(void *)g_adj0_, (void *)g_level_, (void *)g_upper_, (void *)g_pool_, (void *)g_tested0_, (void *)g_testedU_, (void *)s_visited_, (void *)s_jobs_,
-                    (void *)s_hits_, (void *)s_cnt_, (void *)s_flag_, (void *)s_jobctr_, (void *)s_vistab_, (void *)s_fvistab_, (void *)lp_slot_[0], (void *)lp_slot_[1], (void *)lp_slot_[2], (void *)lp_grp_[0], (void *)lp_grp_[1], (void *)lp_grp_[2], (void *)lp_grp_[3], (void *)lp_grp_[4], (void *)lp_grp_[5], (void *)lp_counters_, (void *)s_evals_, (void *)s_sel_, (void *)s_lcnt_, (void *)s_selU_, (void *)s_cntU_, (void *)s_iflag_, (void *)s_lk_[0], (void *)s_lk_[1], (void *)s_lk_[2], (void *)s_lk_[3], (void *)s_lk_[4], (void *)s_spill_, (void *)s_fspill_, (void *)s_allow_, (void *)s_order_, (void *)s_rlog_, (void *)s_dry_, (void *)s_wdry_, (void *)s_win_, (void *)s_arena_, (void *)s_roff_, (void *)s_arena_used_, (void *)s_rentry_, (void *)s_rlists_, (void *)s_rl_, (void *)s_rstate_, (void *)s_rtied_, (void *)s_rfin_ctr_, (void *)s_rres_, (void *)s_rdst_, (void *)s_rpack_})
+                    (void *)s_hits_, (void *)s_cnt_, (void *)s_flag_, (void *)s_jobctr_, (void *)s_vistab_, (void *)s_fvistab_, (void *)lp_slot_[0], (void *)lp_slot_[1], (void *)lp_slot_[2], (void *)lp_grp_[0], (void *)lp_grp_[1], (void *)lp_grp_[2], (void *)lp_grp_[3], (void *)lp_grp_[4], (void *)lp_grp_[5], (void *)lp_counters_, (void *)s_evals_, (void *)s_sel_, (void *)s_lcnt_, (void *)s_selU_, (void *)s_cntU_, (void *)s_iflag_, (void *)s_lk_[0], (void *)s_lk_[1], (void *)s_lk_[2], (void *)s_lk_[3], (void *)s_lk_[4], (void *)s_spill_, (void *)s_fspill_, (void *)s_allow_, (void *)s_order_, (void *)s_rlog_, (void *)s_dry_, (void *)s_wdry_, (void *)s_win_, (void *)s_arena_, (void *)s_roff_, (void *)s_arena_used_, (void *)s_rentry_, (void *)s_rlists_, (void *)s_rl_, (void *)s_rstate_, (void *)s_rtied_, (void *)s_rfin_ctr_, (void *)s_rres_, (void *)s_rdst_, (void *)s_rpack_, (void *)x_ids_, (void *)x_boff_, (void *)x_lists_, (void *)x_out_, (void *)x_evals_, (void *)x_queries_, (void *)x_q_sn_})
         if (p) (void)hipFree(p);
     if (ev0_) (void)hipEventDestroy((hipEvent_t)ev0_);
     if (ev1_) (void)hipEventDestroy((hipEvent_t)ev1_);
@@ -2633,6 +2634,135 @@ bool Device::knn_search_filtered(const float *queries, int nq, int entry_point, 
     return search_filtered(nq, entry_point, top, k_beam, k_out, allow_bits, nbits, out_ids, out_d, out_flag, layer);
 }
 
+// ---- the flat scan (hnswdev_exact_knn; device code in dk_exact.h) --------------------------------------
+// Tile and chunk of a call.  The query tile: as many queries as 16 KB of staged query words and 32 KB of k-entry lists hold, at
+// most 32 and no more than the call has; `exact_qtile` forces it.  The chunk: enough chunks that the tiles x chunks fill the chip
+// about twice over, none shorter than 1 024 rows; `exact_chunk` forces it.  At most 4 096 chunks either way (the merge walks them).
+struct ExactPlan {
+    int qtile, piece, n_chunks;
+    long long chunk, round; // rows per chunk, queries per round
+    size_t lds;
+};
+static ExactPlan exact_plan(int nq, long long m, int k, int pitch, int num_cu)
+{
+    ExactPlan p;
+    const int forced_q = diag("exact_qtile", 0);
+    const long long forced_c = diag("exact_chunk", 0);
+    int qt = forced_q > 0 ? std::min(forced_q, kExactMaxQTile) : kExactMaxQTile;
+    const auto tile_rows = [](int q) { return (size_t)((q + kExactRQ - 1) / kExactRQ * kExactRQ); };
+    while (qt > kExactRQ && (tile_rows(qt) * (size_t)k * 8 > 32768 || (forced_q <= 0 && ((size_t)qt * pitch * 4 > 16384 || qt / 2 >= nq)))) qt >>= 1;
+    p.qtile = qt;
+    const size_t qtr = tile_rows(qt);
+    p.piece = qtr * (size_t)pitch * 4 <= 16384 ? pitch : std::max(16, (int)(16384 / 4 / qtr) & ~15);
+    p.lds = exact_scan_lds(qt, p.piece, pitch, k);
+    const long long tiles = (std::min<long long>(nq, 65536) + qt - 1) / qt;
+    long long chunks = forced_c > 0 ? (m + forced_c - 1) / forced_c
+                                    : std::max<long long>(1, std::min<long long>((2LL * num_cu + tiles - 1) / tiles, m / 1024));
+    chunks = std::min<long long>(chunks, 4096);
+    p.chunk = (m + chunks - 1) / chunks;
+    if (forced_c <= 0) p.chunk = (p.chunk + kExactIterRows - 1) / kExactIterRows * kExactIterRows;
+    p.n_chunks = (int)((m + p.chunk - 1) / p.chunk);
+    // the lists of a round: at most 1 GiB; its results: at most 2^24 entries through the pinned stage
+    const long long by_lists = (1LL << 30) / ((long long)p.n_chunks * k * 8), by_out = (1LL << 24) / k;
+    p.round = std::max<long long>(1, std::min<long long>({(long long)nq, by_lists, by_out}));
+    return p;
+}
+
+bool Device::exact_knn(const float *queries, int nq, long long n_rows, int k, const uint32_t *allow_bits, long long nbits, int *out_ids, float *out_d)
+{
+    if (nq <= 0) return true;
+    if (!allow_bits) nbits = 0; // no filter: nbits means nothing, whatever the caller left in it
+    if (!out_ids || !out_d || k < 1 || n_rows < 0 || nbits < 0) { set_dev_error("exact_knn: bad argument"); return false; }
+    if (k > kExactMaxK) { set_dev_error("exact_knn: k = " + std::to_string(k) + " is above the limit of " + std::to_string(kExactMaxK)); return false; }
+    // rows that exist: a row beyond what was uploaded is never dereferenced, whatever n_rows and the bitset say
+    const long long n = std::min(n_rows, n_rows_hw_), n_allow = allow_bits ? std::min(nbits, n) : n;
+    if (n_allow <= 0 || (allow_bits && !allows_any(allow_bits, nbits, n))) { // nothing to measure: padding, no launch
+        pad_results(out_ids, out_d, (size_t)nq * (size_t)k);
+        return true;
+    }
+    // The queries: the resident set, or the scan's own -- uploaded by set_queries (the one staging path: pinned copy, int8
+    // quantisation, cosine norms) while the scan's buffers stand in for the resident set's, which is then put back untouched.
+    const float *d_q = d_queries_;
+    const double *d_qsn = d_q_sn_;
+    if (queries) {
+        if (tail_.n > 0) { set_dev_error("exact_knn: a streamed query set is still being uploaded"); return false; }
+        std::swap(d_queries_, x_queries_); std::swap(d_q_sn_, x_q_sn_); std::swap(q_capacity_, x_q_capacity_);
+        const long long kept = n_queries_;
+        const bool ok = set_queries(queries, nq);
+        std::swap(d_queries_, x_queries_); std::swap(d_q_sn_, x_q_sn_); std::swap(q_capacity_, x_q_capacity_);
+        n_queries_ = kept;
+        if (!ok) return false;
+        d_q = x_queries_; d_qsn = x_q_sn_;
+    } else if (nq > n_queries_ || tail_.n > 0) { set_dev_error("exact_knn: queries == NULL needs a resident query set of at least nq rows (hnswdev_set_queries)"); return false; }
+    if (!bind()) return false;
+    hipStream_t st = S(stream_);
+    // the id list: the identity without a bitset; otherwise the masked words go up from pinned memory with the bit counts in front
+    // of each block of them (counted while they are copied), and exact_compact_kernel writes the ascending ids
+    long long m = n_allow;
+    const size_t words = allow_bits ? (size_t)((n_allow + 31) / 32) : 0, blocks = (words + kExactCompactWords - 1) / kExactCompactWords;
+    if (allow_bits) {
+        char *hs = static_cast<char *>(pinned_stage(8 * blocks + 4 * words));
+        if (!hs) return false;
+        long long *h_off = reinterpret_cast<long long *>(hs);
+        unsigned *h_words = reinterpret_cast<unsigned *>(hs + 8 * blocks);
+        m = 0;
+        for (size_t w = 0; w < words; ++w) {
+            if (w % kExactCompactWords == 0) h_off[w / kExactCompactWords] = m;
+            const unsigned v = allow_bits[w] & ((long long)(w + 1) * 32 <= n_allow ? ~0u : (1u << (n_allow & 31)) - 1u);
+            h_words[w] = v;
+            m += __builtin_popcount(v);
+        }
+        if (!grow_dev(&s_allow_, &s_allow_cap_, words) || !grow_dev(&x_boff_, &x_boff_cap_, blocks) || !grow_dev(&x_ids_, &x_ids_cap_, (size_t)m)) return false;
+        HIP_OK(hipMemcpyAsync(x_boff_, h_off, 8 * blocks, hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemcpyAsync(s_allow_, h_words, 4 * words, hipMemcpyHostToDevice, st));
+        HIP_OK(exact_compact_launch(s_allow_, (long long)words, x_boff_, x_ids_, st));
+        HIP_OK(hipStreamSynchronize(st)); // the pinned stage is used again below
+    }
+    const ExactPlan p = exact_plan(nq, m, k, pitch_, num_cu_);
+    if (p.lds > 64 * 1024) { set_dev_error("exact_knn: tile exceeds the LDS budget"); return false; }
+    if (!grow_dev(&x_lists_, &x_lists_cap_, (size_t)p.round * p.n_chunks * k) || !grow_dev(&x_out_, &x_out_cap_, 2 * (size_t)p.round * k)) return false;
+    if (!grow_dev(&x_evals_, &x_evals_cap_, 1)) return false;
+    char *hs = static_cast<char *>(pinned_stage(8 * (size_t)p.round * k + 8));
+    if (!hs) return false;
+    unsigned long long *h_ev = reinterpret_cast<unsigned long long *>(hs + 8 * (size_t)p.round * k);
+    if (!ev0_) { hipEvent_t e0, e1; HIP_OK(hipEventCreate(&e0)); ev0_ = e0; HIP_OK(hipEventCreate(&e1)); ev1_ = e1; }
+    for (long long off = 0; off < nq; off += p.round) {
+        const int nr = (int)std::min<long long>(p.round, nq - off);
+        ExactScanArgs a;
+        a.rows = d_rows_; a.row_sn = d_row_sn_;
+        a.queries = d_q + (size_t)off * pitch_;
+        a.q_sn = d_qsn ? d_qsn + off : nullptr;
+        a.dim = pitch_; a.ids = allow_bits ? x_ids_ : nullptr; a.m = m; a.chunk = p.chunk; a.nq = nr; a.qtile = p.qtile; a.piece = p.piece; a.k = k;
+        a.lists = x_lists_; a.n_chunks = p.n_chunks; a.evals = x_evals_;
+        const unsigned tiles = (unsigned)((nr + p.qtile - 1) / p.qtile);
+        int *d_ids = x_out_;
+        float *d_d = reinterpret_cast<float *>(x_out_ + (size_t)p.round * k);
+        const bool timed = profiling_;
+        HIP_OK(hipMemsetAsync(x_evals_, 0, sizeof(unsigned long long), st));
+        if (timed) HIP_OK(hipEventRecord((hipEvent_t)ev0_, st));
+        hipError_t e = hipSuccess;
+        with_metric(metric_, [&](auto mt) { e = exact_scan_launch<mt>(a, tiles, p.lds, st); });
+        HIP_OK(e);
+        HIP_OK(exact_merge_launch(x_lists_, p.n_chunks, k, nr, d_ids, d_d, st));
+        if (timed) HIP_OK(hipEventRecord((hipEvent_t)ev1_, st));
+        HIP_OK(hipMemcpyAsync(hs, d_ids, 4u * (size_t)nr * k, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(hs + 4u * (size_t)p.round * k, d_d, 4u * (size_t)nr * k, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(h_ev, x_evals_, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+        memcpy(out_ids + (size_t)off * k, hs, 4u * (size_t)nr * k);
+        memcpy(out_d + (size_t)off * k, hs + 4u * (size_t)p.round * k, 4u * (size_t)nr * k);
+        // (the flat scan is no traversal: it counts in its own family only, not in the search_* totals; the evaluations are the
+        // kernel's own count of the pairs it turned into keys -- shadows excluded -- not nr * m worked out here)
+        stats_.exact_launches += 1; stats_.exact_evals += *h_ev;
+        if (timed) {
+            float ms = 0.f;
+            HIP_OK(hipEventElapsedTime(&ms, (hipEvent_t)ev0_, (hipEvent_t)ev1_));
+            stats_.exact_kernel_ms += ms; stats_.exact_timed_launches += 1; stats_.exact_timed_evals += *h_ev;
+        }
+    }
+    return true;
+}
+
 // ---- synchronous conveniences behind the C ABI ---------------------------------------
 // Distance(int, TVector) for nq (query, candidate list) pairs.  Runs on the context's two step-
 // buffer sets, ping-pong: while the GPU measures one set the host packs the next and unpacks the
@@ -2847,6 +2977,12 @@ DEV_API int hnswdev_multilayer_search(void *ctx, const float *queries, int nq, i
 {
     CTX_OR_FAIL();
     return d->multilayer_search_abi(queries, nq, entry_point, k, max_layer, min_layer, layers_cap, out_ids, out_dists, out_flags);
+}
+DEV_API int hnswdev_exact_knn(void *ctx, const float *queries, int nq, long long n_rows, int k, const uint32_t *allow_bits, long long nbits, int *out_ids,
+                              float *out_dists)
+{
+    CTX_OR_FAIL();
+    return d->exact_knn(queries, nq, n_rows, k, allow_bits, nbits, out_ids, out_dists) ? 0 : -1;
 }
 DEV_API int hnswdev_range_results(void *ctx, int *out_ids, float *out_dists) { CTX_OR_FAIL(); return d->range_results(out_ids, out_dists) ? 0 : -1; }
 DEV_API int hnswdev_sync(void *ctx) { CTX_OR_FAIL(); return d->sync() ? 0 : -1; }

@@ -16,6 +16,8 @@
 //   dk_insert_kernels.h  graph_insert_search_kernel
 //   dk_link.h            the link half of Add, Remove's re-link
 //   dk_misc_kernels.h    small kernels
+// (dk_exact.h, the flat scan behind hnswdev_exact_knn, is not part of this umbrella: its kernels are compiled in the exact_*.hip
+// units alone and reached through launchers, so no other unit carries their code.)
 // See device_backend.hip's header comment for what the kernels replace and the numerical contract.
 #pragma once
 #include "dk_base.h"

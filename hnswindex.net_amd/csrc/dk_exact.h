@@ -1,0 +1,391 @@
+// dk_exact.h -- the flat scan behind hnswdev_exact_knn: every (query, row) pair of an id list measured with the
+// metric's own arithmetic (dk_metric.h: eight lane partials in element order, the collapse tree, the scalar tail, the epilogue --
+// bit for bit group_metric's value) and the k smallest (distance, id) kept per query.  No graph is read.
+//   exact_compact_kernel   bitset (allow AND live, masked on the host) -> ascending id list
+//   exact_scan_kernel<M>   a tile of queries x a chunk of the id list per block; per (query, chunk) a sorted list of k keys in LDS
+//   exact_merge_kernel     one wave per query: the chunks' lists -> the final k, ids and distances in the output layout
+// The kernels are compiled in the exact_<metric>.hip units (HNSW_EXACT_UNIT) and reached through the launchers declared here, so
+// that device_backend.hip holds none of their code.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+#include <cstdint>
+
+namespace hnsw {
+
+constexpr int kExactThreads = 256;   // 4 waves = 32 groups of 8 lanes
+constexpr int kExactRQ = 4;          // queries of a group's register tile (= waves of a block: wave w merges query w of the tile)
+constexpr int kExactRR = 4;          // rows of a group's register tile
+constexpr int kExactIterRows = (kExactThreads / 8) * kExactRR; // rows a block measures per step: 128
+constexpr int kExactMaxK = 1024;
+constexpr int kExactMaxQTile = 32;
+constexpr int kExactCompactWords = 256; // bitset words per block of exact_compact_kernel (one per thread)
+
+struct ExactScanArgs {
+    const float *rows;      // stored rows (f32 rows, int8 records, f16 records)
+    const double *row_sn;   // cosine: sqrt((double)|row|^2)
+    const float *queries;   // this round's resident queries (f32 in element order; int8: records)
+    const double *q_sn;     // cosine, this round's
+    int dim;                // what the kernels get as `dim`: elements, or the int8 record's words
+    const int *ids;         // the ascending id list, nullptr: the identity (row i is id i)
+    long long m;            // entries of the list
+    long long chunk;        // entries per chunk (blockIdx.y)
+    int nq;                 // queries of this round
+    int qtile;              // queries per block (blockIdx.x)
+    int piece;              // query words staged in LDS at a time: dim, or a multiple of 16 below it
+    int k;
+    unsigned long long *lists; // out: [nq][n_chunks][k] keys, ascending, ~0 where a list has no more
+    int n_chunks;
+    unsigned long long *evals; // out: (query, row) pairs measured, added up over the blocks
+};
+
+// LDS of one scan block
+inline size_t exact_scan_lds(int qtile, int piece, int dim, int k)
+{
+    const size_t qtr = (size_t)((qtile + kExactRQ - 1) / kExactRQ * kExactRQ), qw = (size_t)(piece < dim ? piece : dim);
+    return ((qtr * qw * 4 + 15) & ~(size_t)15) + qtr * (size_t)k * 8 + qtr * 8 + (size_t)kExactRQ * kExactIterRows * 8 + 16;
+}
+
+template <int METRIC>
+hipError_t exact_scan_launch(const ExactScanArgs &a, unsigned n_qtiles, size_t lds, hipStream_t st);
+// words: the masked bitset; block_off[b]: set bits in front of word b * kExactCompactWords
+hipError_t exact_compact_launch(const unsigned *words, long long n_words, const long long *block_off, int *out_ids, hipStream_t st);
+hipError_t exact_merge_launch(const unsigned long long *lists, int n_chunks, int k, int nq, int *out_ids, float *out_d, hipStream_t st);
+
+} // namespace hnsw
+
+#ifdef HNSW_EXACT_UNIT
+#include "dk_base.h"
+#include "dk_metric.h"
+#include "dk_heaps.h"
+
+namespace hnsw {
+
+constexpr unsigned long long kExactEmpty = ~0ull;
+
+// (distance, id) as one integer with np.lexsort((ids, dist))'s order: the distance key above the id.  dk_heaps.h's f2key orders
+// every number; -0 is made +0 first (they are equal: the lower id goes first) and every NaN becomes the one key above +inf's
+// (NaNs order among themselves by id).  No real entry equals kExactEmpty: ids are below 2^31.
+__device__ __forceinline__ unsigned long long exact_key(float d, int id)
+{
+    unsigned dk;
+    if (d != d) dk = 0xffffffffu;
+    else dk = f2key(__float_as_uint(d) == 0x80000000u ? 0.0f : d);
+    return ((unsigned long long)dk << 32) | (unsigned)id;
+}
+__device__ __forceinline__ float exact_key_dist(unsigned long long key)
+{
+    const unsigned dk = (unsigned)(key >> 32);
+    return dk == 0xffffffffu ? __uint_as_float(0x7fc00000u) : key2f(dk);
+}
+
+// x into the ascending list L[0, k) of one wave (x < L[k - 1]: the last entry drops out).  From the top down, 64 entries at a time:
+// every entry above x moves up one place, x lands below the lowest of them.  One wave: its LDS operations execute in order.
+__device__ __forceinline__ void exact_list_insert(unsigned long long *L, int k, unsigned long long x, int lane)
+{
+    for (int base = (k - 1) & ~63; base >= 0; base -= 64) {
+        const int i = base + lane;
+        const bool in = i < k;
+        const unsigned long long v = in ? L[i] : 0ull, pv = (in && i > 0) ? L[i - 1] : 0ull;
+        wave_lds_sync();
+        if (in && v > x) L[i] = pv > x ? pv : x;
+        wave_lds_sync();
+        if (L[base] <= x) break; // x (or something below it) is this piece's first entry: nothing further down moves
+    }
+}
+
+template <int METRIC>
+__global__ void __launch_bounds__(kExactThreads) exact_scan_kernel(const ExactScanArgs a)
+{
+    static_assert(kExactRQ == kExactThreads / 64, "wave w merges query w of a register tile");
+    constexpr int RQ = kExactRQ, RR = kExactRR;
+    extern __shared__ __align__(16) unsigned char exact_lds[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, grp = tid >> 3, j = tid & 7;
+    const int dim = a.dim, k = a.k, QT = a.qtile, QTR = (QT + RQ - 1) / RQ * RQ;
+    const int P = a.piece, qw = P < dim ? P : dim, npieces = (dim + P - 1) / P;
+    float *qs = reinterpret_cast<float *>(exact_lds);
+    unsigned long long *lists = reinterpret_cast<unsigned long long *>(exact_lds + (((size_t)QTR * qw * 4 + 15) & ~(size_t)15));
+    unsigned long long *thr = lists + (size_t)QTR * k;
+    unsigned long long *pend = thr + QTR;
+    int *pend_cnt = reinterpret_cast<int *>(pend + RQ * kExactIterRows);
+    const long long q0 = (long long)blockIdx.x * QT;
+    const long long lo = (long long)blockIdx.y * a.chunk, hi = lo + a.chunk < a.m ? lo + a.chunk : a.m;
+    const int rw = row_words<METRIC>(dim);
+    const int nblk = dim >> 3;
+
+    for (int i = tid; i < QTR * k; i += kExactThreads) lists[i] = kExactEmpty;
+    if (tid < QTR) thr[tid] = kExactEmpty;
+    if (tid < RQ) pend_cnt[tid] = 0;
+    // (the first staging's barriers order these writes before their first readers)
+
+    unsigned measured = 0; // pairs this lane turned into keys (lane 0 of a group: shadows of rows and queries excluded)
+    bool staged = false;
+    for (long long base = lo; base < hi; base += kExactIterRows) {
+        // this group's rows; past the chunk's end a group shadows the chunk's last row and discards (all eight lanes of every
+        // group stay live for the collapses)
+        int rid[RR];
+        bool rvalid[RR];
+        const float *rp[RR];
+#pragma unroll
+        for (int r = 0; r < RR; ++r) {
+            long long idx = base + grp * RR + r;
+            rvalid[r] = idx < hi;
+            if (!rvalid[r]) idx = hi - 1;
+            rid[r] = a.ids ? a.ids[idx] : (int)idx;
+            rp[r] = a.rows + (size_t)rid[r] * (size_t)rw;
+        }
+        for (int qsub = 0; qsub < QT && q0 + qsub < a.nq; qsub += RQ) {
+            float acc[RQ][RR];
+            int iacc[RQ][RR], ta[RR], tb[RQ];
+            float dist[RQ][RR];
+#pragma unroll
+            for (int q = 0; q < RQ; ++q) {
+                tb[q] = 0;
+#pragma unroll
+                for (int r = 0; r < RR; ++r) { acc[q][r] = 0.0f; iacc[q][r] = 0; ta[r] = 0; }
+            }
+            for (int p = 0; p < npieces; ++p) {
+                const int w0 = p * P, w1 = w0 + P < dim ? w0 + P : dim, len = w1 - w0;
+                if (npieces > 1 || !staged) { // the queries of the tile, words [w0, w1); past the last query a slot shadows it
+                    __syncthreads();
+                    for (int qi = wave; qi < QTR; qi += kExactThreads / 64) {
+                        long long src = q0 + qi;
+                        if (src >= a.nq) src = a.nq - 1;
+                        const float *s = a.queries + (size_t)src * dim + w0;
+                        for (int o = lane; o < len; o += 64) qs[(size_t)qi * qw + o] = s[o];
+                    }
+                    __syncthreads();
+                    staged = true;
+                }
+                const int s0 = w0 >> 3, s1 = w1 >> 3; // the 8-element steps of this piece (P is a multiple of 16)
+                const float *qb = qs + (size_t)qsub * qw + j;
+                if constexpr (METRIC == M_I8) {
+                    const int *qi8 = reinterpret_cast<const int *>(qb);
+#pragma unroll 2
+                    for (int s = s0; s < s1; ++s) {
+                        int wa[RR], wb[RQ];
+#pragma unroll
+                        for (int r = 0; r < RR; ++r) wa[r] = reinterpret_cast<const int *>(rp[r])[8 * s + j];
+#pragma unroll
+                        for (int q = 0; q < RQ; ++q) wb[q] = qi8[q * qw + 8 * (s - s0)];
+                        if (s == nblk - 1 && j >= 6) { // the record's scale / sumsq words
+#pragma unroll
+                            for (int r = 0; r < RR; ++r) ta[r] = wa[r];
+#pragma unroll
+                            for (int q = 0; q < RQ; ++q) tb[q] = wb[q];
+                        } else {
+#pragma unroll
+                            for (int q = 0; q < RQ; ++q)
+#pragma unroll
+                                for (int r = 0; r < RR; ++r) iacc[q][r] = dot4_i8(wa[r], wb[q], iacc[q][r]);
+                        }
+                    }
+                } else if constexpr (metric_f16(METRIC)) {
+                    for (int s = s0; s < s1; s += 2) { // one record word holds this lane's element of two consecutive steps
+                        unsigned w[RR];
+#pragma unroll
+                        for (int r = 0; r < RR; ++r) w[r] = reinterpret_cast<const unsigned *>(rp[r])[8 * (s >> 1) + j];
+#pragma unroll
+                        for (int h = 0; h < 2; ++h) {
+                            if (s + h < s1) {
+                                float y[RQ];
+#pragma unroll
+                                for (int q = 0; q < RQ; ++q) y[q] = qb[q * qw + 8 * (s + h - s0)];
+#pragma unroll
+                                for (int r = 0; r < RR; ++r) {
+                                    const float x = h ? half_hi(w[r]) : half_lo(w[r]);
+#pragma unroll
+                                    for (int q = 0; q < RQ; ++q) {
+                                        if (metric_is_sq(METRIC)) { const float d = x - y[q]; acc[q][r] = __builtin_fmaf(d, d, acc[q][r]); }
+                                        else { const float m = x * y[q]; acc[q][r] = acc[q][r] + m; }
+                                    }
+                                }
+                            }
+                        }
+                    }
+                } else {
+#pragma unroll 2
+                    for (int s = s0; s < s1; ++s) {
+                        float x[RR], y[RQ];
+#pragma unroll
+                        for (int r = 0; r < RR; ++r) x[r] = rp[r][8 * s + j];
+#pragma unroll
+                        for (int q = 0; q < RQ; ++q) y[q] = qb[q * qw + 8 * (s - s0)];
+#pragma unroll
+                        for (int q = 0; q < RQ; ++q)
+#pragma unroll
+                            for (int r = 0; r < RR; ++r) {
+                                if (metric_is_sq(METRIC)) { const float d = x[r] - y[q]; acc[q][r] = __builtin_fmaf(d, d, acc[q][r]); } // EuclideanMetric.cs:30
+                                else { const float m = x[r] * y[q]; acc[q][r] = acc[q][r] + m; }                                       // CosineMetric.cs:114-115
+                            }
+                    }
+                }
+                if (p != npieces - 1) continue;
+                // the last piece holds the tail elements: collapse, scalar tail, epilogue (group_metric's, pair by pair)
+                if constexpr (METRIC == M_I8) {
+                    const int g6 = (lane & ~7) | 6, g7 = (lane & ~7) | 7;
+                    float sb[RQ];
+                    int nb[RQ];
+#pragma unroll
+                    for (int q = 0; q < RQ; ++q) { sb[q] = __int_as_float(__shfl(tb[q], g6, 64)); nb[q] = __shfl(tb[q], g7, 64); }
+#pragma unroll
+                    for (int r = 0; r < RR; ++r) {
+                        const float sa = __int_as_float(__shfl(ta[r], g6, 64));
+                        const int na = __shfl(ta[r], g7, 64);
+#pragma unroll
+                        for (int q = 0; q < RQ; ++q) dist[q][r] = i8_epilogue(sa, na, sb[q], nb[q], group_sum_i32(iacc[q][r]));
+                    }
+                } else {
+#pragma unroll
+                    for (int q = 0; q < RQ; ++q) {
+                        double sqn = 0.0;
+                        if constexpr (METRIC == M_COS) {
+                            long long src = q0 + qsub + q;
+                            if (src >= a.nq) src = a.nq - 1;
+                            sqn = a.q_sn[src];
+                        }
+#pragma unroll
+                        for (int r = 0; r < RR; ++r) {
+                            float s = metric_is_sq(METRIC) ? collapse_l2(acc[q][r]) : collapse_cos(acc[q][r]);
+                            for (int i = dim & ~7; i < dim; ++i) { // every lane redundantly; mul then add, no fma
+                                const float x = row_elem<METRIC>(rp[r], i), y = qs[(size_t)(qsub + q) * qw + (i - w0)];
+                                if (metric_is_sq(METRIC)) { const float d = x - y; const float m = d * d; s = s + m; }
+                                else { const float m = x * y; s = s + m; }
+                            }
+                            if (metric_is_sq(METRIC)) dist[q][r] = s;
+                            else if (metric_is_ucos(METRIC)) dist[q][r] = 1.0f - s;
+                            else {
+                                const float denom = (float)(a.row_sn[rid[r]] * sqn); // CosineMetric.cs:88
+                                dist[q][r] = denom < 1e-30f ? 1.0f : 1.0f - s / denom; // :89-91
+                            }
+                        }
+                    }
+                }
+            }
+            // offers: a key goes to its query's pending list only when it is below that query's current k-th
+            int offered = 0;
+            if (j == 0) {
+#pragma unroll
+                for (int q = 0; q < RQ; ++q) {
+                    if (qsub + q >= QT || q0 + qsub + q >= a.nq) continue;
+                    const unsigned long long t = thr[qsub + q];
+#pragma unroll
+                    for (int r = 0; r < RR; ++r) {
+                        if (!rvalid[r]) continue;
+                        ++measured;
+                        const unsigned long long key = exact_key(dist[q][r], rid[r]);
+                        if (key < t) {
+                            const int slot = atomicAdd(&pend_cnt[q], 1);
+                            pend[q * kExactIterRows + slot] = key;
+                            offered = 1;
+                        }
+                    }
+                }
+            }
+            if (__syncthreads_or(offered)) {
+                const int cnt = pend_cnt[wave]; // wave w: query qsub + w (the set that results does not depend on the order of the offers)
+                if (cnt > 0) {
+                    unsigned long long *L = lists + (size_t)(qsub + wave) * k;
+                    for (int i = 0; i < cnt; ++i) {
+                        const unsigned long long x = pend[wave * kExactIterRows + i];
+                        if (x < L[k - 1]) exact_list_insert(L, k, x, lane);
+                    }
+                    wave_lds_sync();
+                    if (lane == 0) { thr[qsub + wave] = L[k - 1]; pend_cnt[wave] = 0; }
+                }
+                __syncthreads();
+            }
+        }
+    }
+    __syncthreads();
+    if (measured) atomicAdd(a.evals, (unsigned long long)measured); // one atomic per group that measured anything
+    for (int qi = 0; qi < QT && q0 + qi < a.nq; ++qi) {
+        unsigned long long *dst = a.lists + ((size_t)(q0 + qi) * a.n_chunks + blockIdx.y) * (size_t)k;
+        for (int i = tid; i < k; i += kExactThreads) dst[i] = lists[(size_t)qi * k + i];
+    }
+}
+
+template <int METRIC>
+hipError_t exact_scan_launch(const ExactScanArgs &a, unsigned n_qtiles, size_t lds, hipStream_t st)
+{
+    hipLaunchKernelGGL(exact_scan_kernel<METRIC>, dim3(n_qtiles, (unsigned)a.n_chunks), dim3(kExactThreads), lds, st, a);
+    return hipGetLastError();
+}
+
+#ifdef HNSW_EXACT_COMMON
+// The bitset as an ascending id list: one word per thread, its place = the block's offset (counted on the host while the words
+// were staged) + the prefix of the bit counts inside the block (wave prefix by shuffles rather than ballots: a lane holds a word, not a bit; wave totals through LDS).
+__global__ void __launch_bounds__(kExactCompactWords) exact_compact_kernel(const unsigned *__restrict__ words, long long n_words,
+                                                                           const long long *__restrict__ block_off, int *__restrict__ out_ids)
+{
+    __shared__ int wave_total[kExactCompactWords / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long long w = (long long)blockIdx.x * kExactCompactWords + tid;
+    unsigned v = w < n_words ? words[w] : 0u;
+    const int c = __popc(v);
+    int incl = c;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const int o = __shfl_up(incl, d, 64);
+        if (lane >= d) incl += o;
+    }
+    if (lane == 63) wave_total[wave] = incl;
+    __syncthreads();
+    long long pos = block_off[blockIdx.x] + (incl - c);
+    for (int i = 0; i < wave; ++i) pos += wave_total[i];
+    const long long id0 = w << 5;
+    while (v) {
+        const int b = __ffs((int)v) - 1;
+        out_ids[pos++] = (int)(id0 + b);
+        v &= v - 1;
+    }
+}
+
+// One wave per query: the chunks' ascending lists into the final k.  A list is left at its first entry that is not below the
+// current k-th (the rest of it is larger still; ~0 marks a list's end).
+__global__ void __launch_bounds__(64) exact_merge_kernel(const unsigned long long *__restrict__ lists, int n_chunks, int k, int *__restrict__ out_ids,
+                                                         float *__restrict__ out_d)
+{
+    __shared__ unsigned long long L[kExactMaxK];
+    const int lane = threadIdx.x;
+    const size_t q = blockIdx.x;
+    for (int i = lane; i < k; i += 64) L[i] = kExactEmpty;
+    wave_lds_sync();
+    for (int c = 0; c < n_chunks; ++c) {
+        const unsigned long long *src = lists + (q * n_chunks + c) * (size_t)k;
+        bool more = true;
+        for (int i0 = 0; i0 < k && more; i0 += 64) {
+            const unsigned long long mine = i0 + lane < k ? src[i0 + lane] : kExactEmpty;
+            const int n = k - i0 < 64 ? k - i0 : 64;
+            for (int t = 0; t < n; ++t) {
+                const unsigned lo32 = __shfl((unsigned)mine, t, 64), hi32 = __shfl((unsigned)(mine >> 32), t, 64);
+                const unsigned long long x = ((unsigned long long)hi32 << 32) | lo32;
+                if (x >= L[k - 1]) { more = false; break; }
+                exact_list_insert(L, k, x, lane);
+            }
+        }
+    }
+    wave_lds_sync();
+    for (int i = lane; i < k; i += 64) {
+        const unsigned long long key = L[i];
+        out_ids[q * k + i] = key == kExactEmpty ? -1 : (int)(unsigned)key;
+        out_d[q * k + i] = key == kExactEmpty ? __uint_as_float(0x7fc00000u) : exact_key_dist(key);
+    }
+}
+
+hipError_t exact_compact_launch(const unsigned *words, long long n_words, const long long *block_off, int *out_ids, hipStream_t st)
+{
+    const unsigned blocks = (unsigned)((n_words + kExactCompactWords - 1) / kExactCompactWords);
+    hipLaunchKernelGGL(exact_compact_kernel, dim3(blocks), dim3(kExactCompactWords), 0, st, words, n_words, block_off, out_ids);
+    return hipGetLastError();
+}
+hipError_t exact_merge_launch(const unsigned long long *lists, int n_chunks, int k, int nq, int *out_ids, float *out_d, hipStream_t st)
+{
+    hipLaunchKernelGGL(exact_merge_kernel, dim3((unsigned)nq), dim3(64), 0, st, lists, n_chunks, k, out_ids, out_d);
+    return hipGetLastError();
+}
+#endif // HNSW_EXACT_COMMON
+
+} // namespace hnsw
+#endif // HNSW_EXACT_UNIT

@@ -151,6 +151,20 @@ API int hnsw_mi355x_knn_query_filtered(void *handle, const float *vectors, int c
     return 0;
 }
 
+// Exact k nearest neighbours: the flat scan over the live ids an allow-set allows.  Exclusive, like the filtered call.
+API int hnsw_mi355x_exact_knn_query(void *handle, const float *vectors, int count, int dim, int k, const uint32_t *allow_bits, long long nbits,
+                                    int *out_ids, float *out_dists)
+{
+    if (!handle) return 0;
+    if (count <= 0) return 0;
+    if (!vectors || !out_ids || !out_dists || dim <= 0) { set_error("System.ArgumentNullException: hnsw_mi355x_exact_knn_query"); return -1; }
+    if (allow_bits && nbits < 0) { set_error("System.ArgumentException: hnsw_mi355x_exact_knn_query: nbits must be >= 0"); return -1; }
+    LOCK_INDEX(handle);
+    std::string err;
+    if (static_cast<HnswIndex *>(handle)->exact_knn_query(vectors, count, dim, k, allow_bits, nbits, out_ids, out_dists, err) < 0) { set_error(err); return -1; }
+    return 0;
+}
+
 API void hnsw_free_results(void **ids_array, void **dists_array, int count);
 
 // hnsw_range_query and its filtered sibling: `name` for the errors, allow (none: no filter)

@@ -1662,6 +1662,36 @@ int HnswIndex::knn_query_general(const float *queries, int count, int dim, int k
     return knn_query_lockstep(redo.data(), (int)redo.size(), k, out_ids, out_dists, err, allow, layer);
 }
 
+// The flat scan: every live, allowed row measured against every query.  The candidates are the live ids: while
+// nothing has been removed they are 0 .. length - 1 and the caller's bitset goes to the device as it is (none: the scan addresses
+// rows directly); once slots are vacant the live set is ANDed into it here.
+int HnswIndex::exact_knn_query(const float *queries, int count, int dim, int k, const uint32_t *allow_bits, long long nbits, int *out_ids, float *out_dists,
+                               std::string &err)
+{
+    if (count <= 0) return 0;
+    if (failed(err)) return -1;
+    if (k > 1024) { err = "System.ArgumentOutOfRangeException: hnsw_mi355x_exact_knn_query: k = " + std::to_string(k) + " is above the limit of 1024"; return -1; }
+    if (k < 1 || graph_.count <= 0) {
+        pad_results(out_ids, out_dists, (size_t)count * (size_t)std::max(k, 0));
+        return 0;
+    }
+    if (!ensure_dim(dim, err)) return -1;
+    if (!allow_bits) nbits = 0; // no filter: nbits means nothing
+    const long long length = graph_.length;
+    std::vector<uint32_t> live;
+    if (graph_.count != graph_.length) { // vacant slots: allow AND live
+        const long long n = allow_bits ? std::min(nbits, length) : length;
+        live.assign((size_t)((n + 31) / 32) + 1, 0u);
+        for (long long id = 0; id < n; ++id)
+            if (!graph_.removed[(size_t)id] && (!allow_bits || ((allow_bits[id >> 5] >> (id & 31)) & 1u))) live[(size_t)(id >> 5)] |= 1u << (id & 31);
+        allow_bits = live.data();
+        nbits = n;
+    }
+    // (the scan stages its queries in a buffer of its own: the resident set, sharded or not, stays what it was)
+    if (!dev_->exact_knn(queries, count, length, k, allow_bits, nbits, out_ids, out_dists)) { err = get_dev_error(); return -1; }
+    return 0;
+}
+
 // Host lock-step chains for the queries listed in `which` (nullptr: all `count`): MultiLayerJob.  out_*: [query][first + 1][k - 1].
 int HnswIndex::multilayer_lockstep(const int *which, int count, int k, int first, int min_layer, int *out_ids, float *out_dists, std::string &err)
 {

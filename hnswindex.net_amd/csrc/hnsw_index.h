@@ -55,6 +55,10 @@ public:
     // hnsw_mi355x_knn_query_at_layer, hnsw_mi355x_knn_query_filtered (layer 0): KnnQuery(query, k, filterFnc, layer) -- allow_bits ==
     // nullptr: no filter; else a bitset of nbits bits over ids, ids >= nbits not allowed.  layer outside 0 .. the entry point's top
     // layer on a non-empty index: -1.  The caller holds the index lock EXCLUSIVELY (these calls take no query lane).  0 or -1.
+    // hnsw_mi355x_exact_knn_query: the flat scan (Device::exact_knn) over the live ids that allow_bits allows (nullptr: no filter).
+    // Reads no graph; runs on the primary context, on the device whatever device_traversal says.
+    int exact_knn_query(const float *queries, int count, int dim, int k, const uint32_t *allow_bits, long long nbits, int *out_ids, float *out_dists,
+                        std::string &err);
     int knn_query_general(const float *queries, int count, int dim, int k, int layer, const uint32_t *allow_bits, long long nbits, int *out_ids,
                           float *out_dists, std::string &err);
     // hnsw_mi355x_multilayer_knn_query: the number of layer slots (min(top, max_layer) + 1; 0 for an empty index, k < 1 or

@@ -232,6 +232,21 @@ int hnsw_mi355x_range_query_at_layer(void *handle, const float *vectors, int cou
 int hnsw_mi355x_multilayer_knn_query(void *handle, const float *vectors, int count, int dim, int k, int max_layer, int min_layer,
                                      int layers_cap, int *out_ids, float *out_dists);
 
+/* Exact k nearest neighbours by a flat scan on the device (no reference counterpart): for each query the k
+ * CANDIDATES of smallest distance, where a candidate is a live id (hnsw_mi355x_active_ids) that the allow-set allows -- the bitset
+ * of hnsw_mi355x_knn_query_filtered with its rules (ids >= nbits not allowed); allow_bits == NULL: no filter.  No graph is read, so
+ * the answer does not depend on how the index was filled.  Distances are the index metric's values, bit for bit those of
+ * hnswdev_dist_query_batch (a NaN distance is returned as the quiet NaN 0x7fc00000, a -0 distance as +0).  Order: ascending by
+ * (distance, id) -- distances as IEEE numbers, NaN after +inf, equal distances (and NaNs) by id: the result is unique.
+ * out_ids / out_dists: [count][k] row-major, a row that runs out of candidates padded with -1 / NaN.  1 <= k <= 1024; k > 1024 is
+ * -1 with a message; k < 1, count <= 0 and a NULL handle behave as in hnsw_mi355x_knn_query_filtered (0, nothing or padding
+ * written); nbits < 0 with a bitset is -1.  A set that allows no live id is answered with padding and no launch.  Always runs on
+ * the device, whatever hnsw_set_device_traversal says, and on the primary context alone under hnsw_mi355x_set_devices(n).  Takes
+ * the handle exclusively.  The resident query set (hnsw_mi355x_set_queries, or what hnsw_knn_query left) is not touched: the scan
+ * stages its queries in a buffer of its own.  nbits is ignored when allow_bits is NULL. */
+int hnsw_mi355x_exact_knn_query(void *handle, const float *vectors, int count, int dim, int k, const uint32_t *allow_bits, long long nbits,
+                                int *out_ids, float *out_dists);
+
 /* Measurement aid: hnsw_mi355x_set_queries uploads a query set (count x dim) once; every later
  * hnsw_mi355x_knn_query_resident(k) is hnsw_knn_query on that set with the inputs already in HBM
  * (out arrays: count x k). */
@@ -344,6 +359,11 @@ typedef struct hnswdev_stats {
     uint64_t multilayer_launches;   /* launches */
     uint64_t multilayer_jobs;       /* chains given to the device (one per query) */
     uint64_t multilayer_handbacks;  /* ... of which handed back whole (NaN / -0 distance, candidate heap full, visited table crowded) */
+    /* the flat scan (hnswdev_exact_knn: exact_scan_kernel + exact_merge_kernel; no traversal, so NOT part of the search_* totals) */
+    uint64_t exact_launches;        /* scan launches (one per round of queries) */
+    uint64_t exact_evals;           /* (query, row) pairs measured: queries x rows that are live and allowed, exactly */
+    uint64_t exact_timed_launches, exact_timed_evals;
+    double exact_kernel_ms;         /* HIP-event durations of the timed rounds (scan + merge) */
 } hnswdev_stats;
 
 /* All return 0 on success, < 0 on error (message via hnswdev_ctx_last_error / hnswdev_last_error).
@@ -456,6 +476,14 @@ int hnswdev_multilayer_search(void *ctx, const float *queries, int nq, int entry
 
 int hnswdev_sync(void *ctx);
 int hnswdev_set_profiling(void *ctx, int enabled);
+/* The flat scan behind hnsw_mi355x_exact_knn_query: per query the k rows of smallest (distance, id) among the uploaded rows
+ * [0, n_rows) that allow_bits allows (NULL: all; else nbits bits, ids >= nbits not allowed), ascending, padded with -1 / NaN.
+ * No graph and no active set are involved.  n_rows and nbits beyond what was uploaded are clamped: a row that does not exist is
+ * never dereferenced.  queries == NULL: the resident set (hnswdev_set_queries); otherwise the queries go to a buffer of the
+ * scan's own and the resident set stays.  nbits is ignored when allow_bits is NULL.  1 <= k <= 1024.  hnswdev_stats.exact_evals is
+ * counted by the scan kernel itself. */
+int hnswdev_exact_knn(void *ctx, const float *queries, int nq, long long n_rows, int k, const uint32_t *allow_bits, long long nbits,
+                      int *out_ids, float *out_dists);
 int hnswdev_get_stats(void *ctx, hnswdev_stats *out);
 int hnswdev_reset_stats(void *ctx);
 /* Last error, process-wide (creation failures have no context yet) ... */
