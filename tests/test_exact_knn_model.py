@@ -43,6 +43,20 @@ def test_k_beyond_the_candidates_pads():
     assert e_ids.tolist() == [PAD_ID, PAD_ID] and np.isnan(e_d).all()
 
 
+def test_select_rows_is_select_row_by_row():
+    from exact_knn_model import select_rows
+    rng = np.random.default_rng(5)
+    d = rng.integers(0, 6, (7, 40)).astype(np.float32)          # equal distances abound
+    d[1, 3] = d[1, 30] = np.nan; d[2, 5] = np.inf; d[3, :4] = [0.0, -0.0, -0.0, 0.0]
+    ids = np.sort(rng.choice(1000, 40, replace=False)).astype(np.int32)
+    for k in (1, 7, 40, 50):
+        got = select_rows(d, ids, k)
+        want = [select(d[i], ids, k) for i in range(7)]
+        assert (got[0] == np.stack([w[0] for w in want])).all() and got[1].tobytes() == np.stack([w[1] for w in want]).tobytes()
+    e_ids, e_d = select_rows(np.zeros((2, 0), np.float32), np.zeros(0, np.int32), 3)
+    assert (e_ids == PAD_ID).all() and np.isnan(e_d).all()
+
+
 @pytest.mark.parametrize("metric", ["sq_euclid", "cosine", "ucosine", "sq_euclid_i8", "sq_euclid_f16"])
 def test_every_id_left_out_is_greater_than_the_last_returned(metric):
     import oracle
@@ -71,6 +85,47 @@ def test_f16_model_is_the_f32_model_on_rounded_rows():
     a = exact_knn("ucosine_f16", x, q, 7)
     b = exact_knn("ucosine", x.astype(np.float16).astype(np.float32), q, 7)
     assert (a[0] == b[0]).all() and a[1].tobytes() == b[1].tobytes()
+
+
+PLAN_PINS = [   # (nq, m, k, pitch, forced chunk) -> (qtile, chunk, n_chunks, round), worked by hand from exact_plan at 256 CUs
+    ((9, 20000, 10, 8, 0), (16, 1152, 18, 9)),
+    ((67, 20000, 10, 8, 0), (32, 1152, 18, 67)),
+    ((9, 20000, 1024, 8, 0), (4, 1152, 18, 9)),
+    ((9, 1500, 10, 16, 0), (16, 1536, 1, 9)),
+    ((16400, 300, 1024, 8, 0), (4, 384, 1, 16384)),
+    ((600, 20000, 64, 8, 5), (32, 5, 4000, 524)),
+]
+
+
+@pytest.mark.parametrize("args,want", PLAN_PINS)
+def test_plan_restates_the_picker(args, want):
+    from exact_knn_model import plan
+    nq, m, k, pitch, forced = args
+    p = plan(nq, m, k, pitch, forced_chunk=forced)
+    assert (p["qtile"], p["chunk"], p["n_chunks"], p["round"]) == want
+    assert p["piece"] == pitch                                   # rows this short are staged whole
+    for cu in (32, 64, 304):                                     # tiles <= 3 in every unforced line but the 16400-query one,
+        assert plan(nq, m, k, pitch, forced_chunk=forced, num_cu=cu) == p   # whose m // 1024 is 0: no CU count changes any
+
+
+def test_plan_pieces_caps_and_forced_tiles():
+    from exact_knn_model import plan
+    # rows beyond the 16 KB staging area at the smallest tile: pieces of 1024 words
+    assert plan(5, 300, 10, 1100)["qtile"] == 4 and plan(5, 300, 10, 1100)["piece"] == 1024
+    assert plan(5, 300, 10, 1056)["piece"] == 1024 and plan(5, 300, 10, 1024)["piece"] == 1024
+    assert plan(40, 300, 10, 264, forced_qtile=32)["piece"] == 128
+    # the 4096-chunk cap: 4096 chunks of one id; beyond it the list is divided again
+    assert plan(9, 4096, 10, 8, forced_chunk=1)["n_chunks"] == 4096
+    p = plan(9, 5000, 10, 8, forced_chunk=1)
+    assert (p["chunk"], p["n_chunks"]) == (2, 2500)
+    p = plan(600, 4097, 128, 8, forced_chunk=1)
+    assert (p["chunk"], p["n_chunks"], p["round"]) == (2, 2049, 511)
+    # a forced tile is taken as it is (no multiple of the register tile needed); a forced chunk gives the number of chunks, over
+    # which the list is divided evenly (ceil(20000 / 1153) = 18 chunks of ceil(20000 / 18) ids), not rounded to 128
+    p = plan(67, 20000, 10, 8, forced_qtile=3, forced_chunk=1153)
+    assert (p["qtile"], p["chunk"], p["n_chunks"]) == (3, 1112, 18)
+    assert plan(67, 20000, 10, 8, forced_chunk=128)["n_chunks"] == 157
+    assert plan(65600, 64, 10, 16)["round"] == 65600 and plan(65600, 64, 10, 16)["qtile"] == 32
 
 
 def _header():

@@ -8,8 +8,10 @@ import pytest
 
 import oracle
 from common import default_cap, uniform
+from int8_edges import EDGE_DIMS, edge_rows
 
 DIMS = [4, 7, 33, 96, 100, 120, 128, 200, 768]
+HALF_EVEN = np.array([-12, -10, -10, -8, -8, -6, -6, -4, -4, -2, -2, 0, 0, 2, 2, 4, 4, 6, 6, 8, 8, 10, 10, 12], np.int8)   # rintf of -11.5 ... 11.5
 
 
 def np_quantize(x):
@@ -31,16 +33,28 @@ def np_distance(qa, sa, na, qb, sb, nb):
     return np.float32((A + B) - 2.0 * C)
 
 
-@pytest.mark.parametrize("dim", DIMS)
+@pytest.mark.parametrize("dim", DIMS + [d for d in EDGE_DIMS if d not in DIMS])
 def test_quantiser_and_distance_follow_the_stated_definition(dim):
     rng = np.random.default_rng(dim)
-    x = np.concatenate([uniform(40, dim, 1), (uniform(40, dim, 2) - 0.5) * np.float32(3.0), rng.standard_normal((20, dim)).astype(np.float32) * 1e-3])
+    edges = edge_rows(dim)[0]                         # rintf ties, denormal / zero / smallest-normal scales, the largest floats, -0
+    x = np.concatenate([uniform(40, dim, 1), (uniform(40, dim, 2) - 0.5) * np.float32(3.0), rng.standard_normal((20, dim)).astype(np.float32) * 1e-3, edges])
     x[5] = 0.0                                        # a zero vector: scale 0, every q 0
     x[6, :] = 0.0; x[6, 0] = -2.5                     # one element carries the maximum: q = -127
     q, s, n = oracle.i8_quantize(x)
     wq, ws, wn = np_quantize(x)
     assert (q == wq).all() and s.tobytes() == ws.tobytes() and (n == wn).all()
     assert (q[5] == 0).all() and s[5] == 0 and q[6, 0] == -127 and np.abs(q).max() <= 127
+    e = 100                                           # the edge rows, by what int8_edges.py says of each
+    mid = 256 if dim > 256 else dim // 2
+    ties = np.resize(HALF_EVEN, dim)                  # -11.5, -10.5, ... 11.5 to the even neighbour
+    assert s[e] == 1 and (np.delete(q[e], dim - 1) == np.delete(ties, dim - 1)).all() and q[e, -1] == 127
+    assert s[e + 1] == np.float32(2.0 ** -20) and (np.delete(q[e + 1], mid) == np.delete(ties, mid)).all() and q[e + 1, mid] == 127
+    assert 0 < s[e + 2] < np.finfo(np.float32).tiny and q[e + 2, mid] == -127 and (np.delete(q[e + 2], mid) == 4).all()
+    assert s[e + 3] == 0 and not q[e + 3].any() and n[e + 3] == 0
+    assert s[e + 4] == np.finfo(np.float32).tiny and q[e + 4, 0] == -127 and q[e + 4, -1] == 127
+    assert np.isfinite(s[e + 5]) and q[e + 5, -1] == -127 and (q[e + 5, :-1] == 112).all()
+    assert s[e + 6] == 0 and not q[e + 6].any()
+    assert (q[e + 7] == -q[e + 8]).all() and s[e + 7] == s[e + 8] and n[e + 7] == n[e + 8]
     for a, b in ((0, 1), (3, 50), (41, 42), (5, 7), (5, 5), (6, 6), (90, 2)):
         got = oracle.metric("sq_euclid_i8", x[a], x[b])
         assert got.tobytes() == np_distance(q[a], s[a], n[a], q[b], s[b], n[b]).tobytes()
@@ -52,6 +66,29 @@ def test_quantiser_and_distance_follow_the_stated_definition(dim):
         true = np.sqrt(((x[a].astype(np.float64) - x[b]) ** 2).sum())
         assert abs(np.sqrt(max(float(got), 0.0)) - true) <= err + 1e-6
     assert oracle.metric("sq_euclid_i8", x[9], x[9]) == 0    # identical records: exactly zero
+
+
+def test_non_finite_rows_are_what_the_oracle_makes_of_them():
+    """The numpy statement does not reach these rows (np.max propagates a NaN, fmaxf drops it): the oracle alone defines them.  An
+    infinite element makes the scale inf: every finite element divides to 0, inf / inf is NaN.  A NaN element leaves the scale to
+    the finite maximum.  A NaN quotient passes fmaxf(v, -127) as -127."""
+    x = edge_rows(7)[1]
+    assert x.tolist()[0] == [-2.75, 0.75, -1.5, np.inf, -0.25, -2.5, 1.0]
+    assert x.tolist()[1][:6] == [-2.75, 0.75, -1.5, 2.0, -0.25, -2.5] and np.isnan(x[1, 6])
+    assert x.tolist()[2][:3] == [-np.inf, 0.75, -1.5] and np.isnan(x[2, 3]) and x.tolist()[2][4:] == [-0.25, -2.5, 1.0]
+    q, s, n = oracle.i8_quantize(x)
+    assert q.tolist() == [[0, 0, 0, -127, 0, 0, 0], [-127, 35, -69, 92, -12, -115, -127], [-127, 0, 0, -127, 0, 0, 0]]
+    assert s[0] == np.inf and s[1].tobytes() == (np.float32(2.75) / np.float32(127.0)).tobytes() and s[2] == np.inf
+    assert n.tolist() == [16129, 60077, 32258]
+    for dim in EDGE_DIMS[1:]:                         # the same at the longer rows: the non-finite elements lie elsewhere
+        x = edge_rows(dim)[1]
+        hi, mid = dim - 1, 256 if dim > 256 else dim // 2
+        q, s, n = oracle.i8_quantize(x)
+        assert s[0] == np.inf and n[0] == 16129 and q[0, mid] == -127 and not np.delete(q[0], mid).any()
+        fin = x[1].copy(); fin[hi] = 0.0
+        wq, ws, _ = np_quantize(fin)                  # the NaN aside, the row is an ordinary one
+        assert s[1].tobytes() == ws.tobytes() and (q[1, :hi] == wq[:hi]).all() and q[1, hi] == -127 and n[1] == int((wq.astype(np.int64) ** 2).sum()) + 16129
+        assert s[2] == np.inf and n[2] == 32258 and q[2, 0] == -127 and q[2, mid] == -127 and not np.delete(q[2], [0, mid]).any()
 
 
 @pytest.mark.parametrize("dim", DIMS)
