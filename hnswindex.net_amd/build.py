@@ -9,16 +9,26 @@ CSRC = PKG / "csrc"
 # Same relative location and file name the reference's ctypes loader expects
 # (/root/reference/bindings/bindings.py:27-41), so its bindings.py binds unchanged.
 LIB = PKG / "artifacts" / "native" / "linux-x64" / "HNSWIndex.Native.so"
-# device_backend.hip: host side + the small kernels; traverse_<metric>_<kernel>.hip: the instantiations of the two
-# big traversal kernel templates (device code in device_kernels.h) -- separate units so that they
-# compile in parallel (one unit took two minutes).
-METRIC_UNITS = ("sq", "cos", "ucos", "i8", "sqh", "ucosh")  # sqh / ucosh: sq_euclid_f16 / ucosine_f16 (half-precision rows)
-SOURCES = ["device_backend.hip", *[f"traverse_{m}_{k}{v}.hip" for m in METRIC_UNITS for k in ("insert", "search") for v in ("", "_lat")],
-           *[f"traverse_{m}_search_lean.hip" for m in METRIC_UNITS],
-           *[f"traverse_{m}_filtered.hip" for m in METRIC_UNITS],
-           *[f"traverse_{m}_multilayer.hip" for m in METRIC_UNITS],
-           *[f"exact_{m}.hip" for m in METRIC_UNITS],  # the flat scan (dk_exact.h); exact_sq.hip also holds its metric-independent kernels
-           "search_engine.cpp", "hnsw_index.cpp", "exports.cpp"]
+# The library's translation units come from one table, units(): device_backend.hip (host side + the small kernels), the three host
+# sources, and -- separate units so that they compile in parallel (one unit took two minutes) -- the instantiations of the big kernel
+# templates, one unit per (kind, metric): kernel_unit.hip for the traversal kernels (device code in device_kernels.h) and
+# exact_unit.hip for the flat scan (dk_exact.h), each compiled once per row with the kind and the metric tag as -D flags.
+# METRICS: (unit tag, ABI name) in id order, the rows of HNSW_FOR_EACH_METRIC (csrc/device_backend.h); sqh / ucosh are sq_euclid_f16 /
+# ucosine_f16 (half-precision rows).  KINDS: HNSW_FOR_EACH_KIND (csrc/device_kernels.h).  tests/test_build_units.py holds the copies together.
+METRICS = (("sq", "sq_euclid"), ("cos", "cosine"), ("ucos", "ucosine"), ("i8", "sq_euclid_i8"), ("sqh", "sq_euclid_f16"), ("ucosh", "ucosine_f16"))
+KINDS = ("insert", "insert_lat", "search", "search_lat", "search_lean", "filtered", "multilayer")
+
+
+def units(single_tu: bool = False):
+    """(unit name, source file, extra -D flags) of every translation unit; a unit's object is <unit name>.o.  single_tu: the
+    -DHNSW_SINGLE_TU diagnostic build, where device_backend.hip defines the traversal kernels itself."""
+    us = [("device_backend", "device_backend.hip", ())]
+    if not single_tu:
+        us += [(f"{k}_{m}", "kernel_unit.hip", (f"-DHNSW_UNIT_KIND={k}", f"-DHNSW_UNIT_METRIC={m}")) for m, _ in METRICS for k in KINDS]
+    us += [(f"exact_{m}", "exact_unit.hip", (f"-DHNSW_UNIT_METRIC={m}",)) for m, _ in METRICS]
+    return us + [(Path(s).stem, s, ()) for s in ("search_engine.cpp", "hnsw_index.cpp", "exports.cpp")]
+
+
 # -ffp-contract=off: the kernels fuse a*b+c only where __builtin_fmaf is written -- the
 # reference's AVX path fuses in sq_euclid (Fma.MultiplyAdd) and nowhere else.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fvisibility=hidden", "-Wall"]
@@ -37,9 +47,9 @@ BUILD_ID_TAG = b"HNSW_MI355X_BUILD_ID="
 
 def source_id(extra=()) -> str:
     """sha256 over everything the library is compiled from: csrc/* and include/*, by name and content, plus the
-    compiler flags (and the extra flags of a diagnostic build).  The same string is compiled into the library
-    (hnsw_mi355x_build_id()), so a binary says which sources it came from -- file times say nothing once a tree has
-    been copied."""
+    compiler flags (and the extra flags of a diagnostic build) and the table of units with their -D flags.  The same string
+    is compiled into the library (hnsw_mi355x_build_id()), so a binary says which sources it came from -- file times say
+    nothing once a tree has been copied."""
     import hashlib
     h = hashlib.sha256()
     files = sorted(list(CSRC.glob("*")) + list((PKG.parent / "include").glob("*.h")), key=lambda f: f.name)
@@ -47,6 +57,8 @@ def source_id(extra=()) -> str:
         if f.is_file():
             h.update(f.name.encode() + b"\0" + f.read_bytes() + b"\0")
     h.update(" ".join(list(FLAGS) + sorted(extra)).encode())
+    for name, src, defs in units("-DHNSW_SINGLE_TU" in extra):
+        h.update(("\0" + " ".join((name, src, *defs))).encode())
     return h.hexdigest()
 
 
@@ -80,27 +92,27 @@ def build(force: bool = False, verbose: bool = False, out: Path = None) -> Path:
     LIB.parent.mkdir(parents=True, exist_ok=True)
     OBJ.mkdir(parents=True, exist_ok=True)
     extra = os.environ.get("HNSW_MI355X_EXTRA_FLAGS", "").split()  # kernel experiments (-D...)
-    sources = list(SOURCES)
-    if "-DHNSW_SINGLE_TU" in extra:  # diagnostic builds: every kernel in one unit
-        extra = sorted(set(extra) | {"-DHNSW_SINGLE_TU"})
-        sources = [s for s in sources if not s.startswith("traverse_")]
+    us = units("-DHNSW_SINGLE_TU" in extra)  # diagnostic builds: every traversal kernel in one unit
 
     sid = source_id() if out is None and not extra else source_id(extra) + "+variant"
 
-    def compile_one(src):
-        obj = OBJ / (Path(src).stem + ".o")
+    def compile_one(unit):
+        name, src, defs = unit
+        obj = OBJ / (name + ".o")
         ident = [f'-DHNSW_MI355X_BUILD_ID_STR="{sid}"'] if src == "exports.cpp" else []  # one unit carries the id
-        cmd = [hipcc(), *FLAGS, *extra, *ident, "-c", str(CSRC / src), "-o", str(obj)]
+        cmd = [hipcc(), *FLAGS, *extra, *defs, *ident, "-c", str(CSRC / src), "-o", str(obj)]
         if verbose:
             print(" ".join(cmd))
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
-            raise RuntimeError(f"hipcc failed on {src}:\n" + r.stdout + r.stderr)
+            raise RuntimeError(f"hipcc failed on {name} ({src}):\n" + r.stdout + r.stderr)
         return obj
 
-    with ThreadPoolExecutor(max_workers=min(len(sources), os.cpu_count() or 4)) as pool:
-        objs = list(pool.map(compile_one, sources))
-    cmd = [hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", *[str(o) for o in objs], "-o", str(LIB) + ".tmp", "-lpthread"]
+    jobs = int(os.environ.get("MAX_JOBS") or 0) or os.cpu_count() or 4  # a shared machine's cpu_count() is not this build's share
+    with ThreadPoolExecutor(max_workers=max(1, min(len(us), jobs))) as pool:
+        objs = list(pool.map(compile_one, us))
+    # -z defs: a kernel form that a launch names and no unit instantiates fails the link, not the first dlopen
+    cmd = [hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-Wl,-z,defs", *[str(o) for o in objs], "-o", str(LIB) + ".tmp", "-lpthread"]
     if verbose:
         print(" ".join(cmd))
     r = subprocess.run(cmd, capture_output=True, text=True)

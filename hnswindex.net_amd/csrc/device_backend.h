@@ -15,6 +15,57 @@
 
 namespace hnsw {
 
+// The metrics, one row each: X(id, unit tag, ABI name).  The id is the ABI's HNSWDEV_* value; the tag names the metric's kernel
+// units (build.py METRICS; a unit is compiled with -DHNSW_UNIT_METRIC=<tag>); the name is what hnsw_create() takes.  Whatever
+// walks the metrics is written from this list: with_metric and Device::create's range check (device_backend.hip), the metrics x
+// kinds grids of the traversal kernels (device_kernels.h), parse_metric (exports.cpp).  The last three are not in the
+// reference: int8 records (BASELINE config 5) and rows stored as binary16.  This header rather than dk_base.h,
+// where the ids are used, because exports.cpp is a host-only unit.
+#define HNSW_FOR_EACH_METRIC(X)      \
+    X(M_SQ, sq, "sq_euclid")         \
+    X(M_COS, cos, "cosine")          \
+    X(M_UCOS, ucos, "ucosine")       \
+    X(M_I8, i8, "sq_euclid_i8")      \
+    X(M_SQH, sqh, "sq_euclid_f16")   \
+    X(M_UCOSH, ucosh, "ucosine_f16")
+enum { M_SQ = HNSWDEV_SQ_EUCLID, M_COS = HNSWDEV_COSINE, M_UCOS = HNSWDEV_UCOSINE, M_I8 = HNSWDEV_SQ_EUCLID_I8,
+       M_SQH = HNSWDEV_SQ_EUCLID_F16, M_UCOSH = HNSWDEV_UCOSINE_F16 };
+#define HNSW_METRIC_ID(ID, TAG, NAME) ID,
+constexpr int kMetricIds[] = {HNSW_FOR_EACH_METRIC(HNSW_METRIC_ID)};
+#undef HNSW_METRIC_ID
+constexpr int kMetricCount = (int)(sizeof(kMetricIds) / sizeof(kMetricIds[0]));
+constexpr bool metric_ids_in_order()
+{
+    for (int i = 0; i < kMetricCount; ++i)
+        if (kMetricIds[i] != i) return false;
+    return true;
+}
+static_assert(metric_ids_in_order(), "HNSW_FOR_EACH_METRIC lists the ids 0 .. kMetricCount - 1 in order");
+constexpr bool metric_str_eq(const char *a, const char *b)
+{
+    for (; *a && *a == *b; ++a, ++b) {}
+    return *a == *b;
+}
+// the id of a unit tag / of an ABI name, -1 when the list has none such
+constexpr int metric_by_tag(const char *tag)
+{
+#define HNSW_METRIC_TAG(ID, TAG, NAME) if (metric_str_eq(tag, #TAG)) return ID;
+    HNSW_FOR_EACH_METRIC(HNSW_METRIC_TAG)
+#undef HNSW_METRIC_TAG
+    return -1;
+}
+constexpr int metric_by_name(const char *name)
+{
+#define HNSW_METRIC_NAME(ID, TAG, NAME) if (metric_str_eq(name, NAME)) return ID;
+    HNSW_FOR_EACH_METRIC(HNSW_METRIC_NAME)
+#undef HNSW_METRIC_NAME
+    return -1;
+}
+// A kernel unit's metric: the id of the tag it was compiled with (kernel_unit.hip, exact_unit.hip)
+#define HNSW_STR_(X) #X
+#define HNSW_STR(X) HNSW_STR_(X)
+#define HNSW_UNIT_METRIC_ID ::hnsw::metric_by_tag(HNSW_STR(HNSW_UNIT_METRIC))
+
 // Last error: one process-wide string (hnswdev_last_error: creation failures have no context yet)
 // and one per context (hnswdev_ctx_last_error).  set_dev_error() files the message under the context
 // the calling thread is currently inside (ErrorScope), if any.

@@ -96,25 +96,11 @@ static bool grow_dev(T **p, size_t *cap, size_t need)
 
 #ifdef EXP_PHASE_CLOCKS
 HNSW_PHASE_BIND(backend)
+// one bind per kernel unit, metrics x kinds (all seven kinds: the filtered and multilayer kernels run the same traversal code)
+#define HNSW_BIND_PROTO(KIND, ID, TAG) hipError_t hnsw_phase_bind_##TAG##_##KIND(unsigned long long *);
+#define HNSW_BIND_PROTOS(ID, TAG, NAME) HNSW_FOR_EACH_KIND(HNSW_BIND_PROTO, ID, TAG)
 extern "C" {
-hipError_t hnsw_phase_bind_sq_insert(unsigned long long *); hipError_t hnsw_phase_bind_sq_search(unsigned long long *);
-hipError_t hnsw_phase_bind_cos_insert(unsigned long long *); hipError_t hnsw_phase_bind_cos_search(unsigned long long *);
-hipError_t hnsw_phase_bind_ucos_insert(unsigned long long *); hipError_t hnsw_phase_bind_ucos_search(unsigned long long *);
-hipError_t hnsw_phase_bind_i8_insert(unsigned long long *); hipError_t hnsw_phase_bind_i8_search(unsigned long long *);
-hipError_t hnsw_phase_bind_sq_insert_lat(unsigned long long *); hipError_t hnsw_phase_bind_sq_search_lat(unsigned long long *);
-hipError_t hnsw_phase_bind_cos_insert_lat(unsigned long long *); hipError_t hnsw_phase_bind_cos_search_lat(unsigned long long *);
-hipError_t hnsw_phase_bind_ucos_insert_lat(unsigned long long *); hipError_t hnsw_phase_bind_ucos_search_lat(unsigned long long *);
-hipError_t hnsw_phase_bind_i8_insert_lat(unsigned long long *); hipError_t hnsw_phase_bind_i8_search_lat(unsigned long long *);
-hipError_t hnsw_phase_bind_sq_search_lean(unsigned long long *);
-hipError_t hnsw_phase_bind_cos_search_lean(unsigned long long *);
-hipError_t hnsw_phase_bind_ucos_search_lean(unsigned long long *);
-hipError_t hnsw_phase_bind_i8_search_lean(unsigned long long *);
-hipError_t hnsw_phase_bind_sqh_insert(unsigned long long *); hipError_t hnsw_phase_bind_sqh_search(unsigned long long *);
-hipError_t hnsw_phase_bind_ucosh_insert(unsigned long long *); hipError_t hnsw_phase_bind_ucosh_search(unsigned long long *);
-hipError_t hnsw_phase_bind_sqh_insert_lat(unsigned long long *); hipError_t hnsw_phase_bind_sqh_search_lat(unsigned long long *);
-hipError_t hnsw_phase_bind_ucosh_insert_lat(unsigned long long *); hipError_t hnsw_phase_bind_ucosh_search_lat(unsigned long long *);
-hipError_t hnsw_phase_bind_sqh_search_lean(unsigned long long *);
-hipError_t hnsw_phase_bind_ucosh_search_lean(unsigned long long *);
+HNSW_FOR_EACH_METRIC(HNSW_BIND_PROTOS)
 }
 static unsigned long long *g_phase_buf = nullptr; // one buffer per process (diagnostic builds run one index at a time)
 static bool phase_bind_all()
@@ -124,24 +110,9 @@ static bool phase_bind_all()
     (void)hipMemset(g_phase_buf, 0, sizeof(unsigned long long) * hnsw::kPhaseWords);
     bool ok = hnsw_phase_bind_backend(g_phase_buf) == hipSuccess;
 #ifndef HNSW_SINGLE_TU
-    ok = ok && hnsw_phase_bind_sq_insert(g_phase_buf) == hipSuccess && hnsw_phase_bind_sq_search(g_phase_buf) == hipSuccess &&
-         hnsw_phase_bind_cos_insert(g_phase_buf) == hipSuccess && hnsw_phase_bind_cos_search(g_phase_buf) == hipSuccess &&
-         hnsw_phase_bind_ucos_insert(g_phase_buf) == hipSuccess && hnsw_phase_bind_ucos_search(g_phase_buf) == hipSuccess &&
-         hnsw_phase_bind_i8_insert(g_phase_buf) == hipSuccess && hnsw_phase_bind_i8_search(g_phase_buf) == hipSuccess &&
-         hnsw_phase_bind_sq_insert_lat(g_phase_buf) == hipSuccess && hnsw_phase_bind_sq_search_lat(g_phase_buf) == hipSuccess &&
-         hnsw_phase_bind_cos_insert_lat(g_phase_buf) == hipSuccess && hnsw_phase_bind_cos_search_lat(g_phase_buf) == hipSuccess &&
-         hnsw_phase_bind_ucos_insert_lat(g_phase_buf) == hipSuccess && hnsw_phase_bind_ucos_search_lat(g_phase_buf) == hipSuccess &&
-         hnsw_phase_bind_i8_insert_lat(g_phase_buf) == hipSuccess && hnsw_phase_bind_i8_search_lat(g_phase_buf) == hipSuccess &&
-         hnsw_phase_bind_sq_search_lean(g_phase_buf) == hipSuccess &&
-         hnsw_phase_bind_cos_search_lean(g_phase_buf) == hipSuccess &&
-         hnsw_phase_bind_ucos_search_lean(g_phase_buf) == hipSuccess &&
-         hnsw_phase_bind_i8_search_lean(g_phase_buf) == hipSuccess &&
-         hnsw_phase_bind_sqh_insert(g_phase_buf) == hipSuccess && hnsw_phase_bind_sqh_search(g_phase_buf) == hipSuccess &&
-         hnsw_phase_bind_ucosh_insert(g_phase_buf) == hipSuccess && hnsw_phase_bind_ucosh_search(g_phase_buf) == hipSuccess &&
-         hnsw_phase_bind_sqh_insert_lat(g_phase_buf) == hipSuccess && hnsw_phase_bind_sqh_search_lat(g_phase_buf) == hipSuccess &&
-         hnsw_phase_bind_ucosh_insert_lat(g_phase_buf) == hipSuccess && hnsw_phase_bind_ucosh_search_lat(g_phase_buf) == hipSuccess &&
-         hnsw_phase_bind_sqh_search_lean(g_phase_buf) == hipSuccess &&
-         hnsw_phase_bind_ucosh_search_lean(g_phase_buf) == hipSuccess;
+#define HNSW_BIND_CALL(KIND, ID, TAG) ok = ok && hnsw_phase_bind_##TAG##_##KIND(g_phase_buf) == hipSuccess;
+#define HNSW_BIND_CALLS(ID, TAG, NAME) HNSW_FOR_EACH_KIND(HNSW_BIND_CALL, ID, TAG)
+    HNSW_FOR_EACH_METRIC(HNSW_BIND_CALLS)
 #endif
     return ok;
 }
@@ -170,70 +141,15 @@ static void phase_report(const char *when)
 }
 #endif
 
+// Every traversal kernel form, metrics x kinds (device_kernels.h): declared here and defined in the kernel_unit.hip units, or
+// (diagnostic builds) defined here, in one translation unit.
 #ifdef HNSW_SINGLE_TU
-// one translation unit (diagnostic builds)
-HNSW_FOR_EACH_TRAVERSAL(HNSW_DEFINE_TRAVERSAL, M_SQ)
-HNSW_FOR_EACH_TRAVERSAL(HNSW_DEFINE_TRAVERSAL, M_COS)
-HNSW_FOR_EACH_TRAVERSAL(HNSW_DEFINE_TRAVERSAL, M_UCOS)
-HNSW_FOR_EACH_TRAVERSAL(HNSW_DEFINE_TRAVERSAL, M_I8)
-HNSW_FOR_EACH_TRAVERSAL(HNSW_DEFINE_TRAVERSAL, M_SQH)
-HNSW_FOR_EACH_TRAVERSAL(HNSW_DEFINE_TRAVERSAL, M_UCOSH)
-HNSW_FOR_EACH_TRAVERSAL_LAT(HNSW_DEFINE_TRAVERSAL, M_SQ)
-HNSW_FOR_EACH_TRAVERSAL_LAT(HNSW_DEFINE_TRAVERSAL, M_COS)
-HNSW_FOR_EACH_TRAVERSAL_LAT(HNSW_DEFINE_TRAVERSAL, M_UCOS)
-HNSW_FOR_EACH_TRAVERSAL_LAT(HNSW_DEFINE_TRAVERSAL, M_I8)
-HNSW_FOR_EACH_TRAVERSAL_LAT(HNSW_DEFINE_TRAVERSAL, M_SQH)
-HNSW_FOR_EACH_TRAVERSAL_LAT(HNSW_DEFINE_TRAVERSAL, M_UCOSH)
-HNSW_FOR_EACH_TRAVERSAL_LEAN(HNSW_DEFINE_SEARCH, M_SQ)
-HNSW_FOR_EACH_TRAVERSAL_LEAN(HNSW_DEFINE_SEARCH, M_COS)
-HNSW_FOR_EACH_TRAVERSAL_LEAN(HNSW_DEFINE_SEARCH, M_UCOS)
-HNSW_FOR_EACH_TRAVERSAL_LEAN(HNSW_DEFINE_SEARCH, M_I8)
-HNSW_FOR_EACH_TRAVERSAL_LEAN(HNSW_DEFINE_SEARCH, M_SQH)
-HNSW_FOR_EACH_TRAVERSAL_LEAN(HNSW_DEFINE_SEARCH, M_UCOSH)
-HNSW_FOR_EACH_FILTERED(HNSW_DEFINE_FILTERED, M_SQ)
-HNSW_FOR_EACH_FILTERED(HNSW_DEFINE_FILTERED, M_COS)
-HNSW_FOR_EACH_FILTERED(HNSW_DEFINE_FILTERED, M_UCOS)
-HNSW_FOR_EACH_FILTERED(HNSW_DEFINE_FILTERED, M_I8)
-HNSW_FOR_EACH_FILTERED(HNSW_DEFINE_FILTERED, M_SQH)
-HNSW_FOR_EACH_FILTERED(HNSW_DEFINE_FILTERED, M_UCOSH)
-HNSW_FOR_EACH_MULTILAYER(HNSW_DEFINE_MULTILAYER, M_SQ)
-HNSW_FOR_EACH_MULTILAYER(HNSW_DEFINE_MULTILAYER, M_COS)
-HNSW_FOR_EACH_MULTILAYER(HNSW_DEFINE_MULTILAYER, M_UCOS)
-HNSW_FOR_EACH_MULTILAYER(HNSW_DEFINE_MULTILAYER, M_I8)
-HNSW_FOR_EACH_MULTILAYER(HNSW_DEFINE_MULTILAYER, M_SQH)
-HNSW_FOR_EACH_MULTILAYER(HNSW_DEFINE_MULTILAYER, M_UCOSH)
+#define HNSW_TRAVERSAL_UNIT(KIND, ID, TAG) HNSW_UNIT_##KIND(DEFINE, ID)
 #else
-HNSW_FOR_EACH_TRAVERSAL(HNSW_DECLARE_TRAVERSAL, M_SQ)
-HNSW_FOR_EACH_TRAVERSAL(HNSW_DECLARE_TRAVERSAL, M_COS)
-HNSW_FOR_EACH_TRAVERSAL(HNSW_DECLARE_TRAVERSAL, M_UCOS)
-HNSW_FOR_EACH_TRAVERSAL(HNSW_DECLARE_TRAVERSAL, M_I8)
-HNSW_FOR_EACH_TRAVERSAL(HNSW_DECLARE_TRAVERSAL, M_SQH)
-HNSW_FOR_EACH_TRAVERSAL(HNSW_DECLARE_TRAVERSAL, M_UCOSH)
-HNSW_FOR_EACH_TRAVERSAL_LAT(HNSW_DECLARE_TRAVERSAL, M_SQ)
-HNSW_FOR_EACH_TRAVERSAL_LAT(HNSW_DECLARE_TRAVERSAL, M_COS)
-HNSW_FOR_EACH_TRAVERSAL_LAT(HNSW_DECLARE_TRAVERSAL, M_UCOS)
-HNSW_FOR_EACH_TRAVERSAL_LAT(HNSW_DECLARE_TRAVERSAL, M_I8)
-HNSW_FOR_EACH_TRAVERSAL_LAT(HNSW_DECLARE_TRAVERSAL, M_SQH)
-HNSW_FOR_EACH_TRAVERSAL_LAT(HNSW_DECLARE_TRAVERSAL, M_UCOSH)
-HNSW_FOR_EACH_TRAVERSAL_LEAN(HNSW_DECLARE_SEARCH, M_SQ)
-HNSW_FOR_EACH_TRAVERSAL_LEAN(HNSW_DECLARE_SEARCH, M_COS)
-HNSW_FOR_EACH_TRAVERSAL_LEAN(HNSW_DECLARE_SEARCH, M_UCOS)
-HNSW_FOR_EACH_TRAVERSAL_LEAN(HNSW_DECLARE_SEARCH, M_I8)
-HNSW_FOR_EACH_TRAVERSAL_LEAN(HNSW_DECLARE_SEARCH, M_SQH)
-HNSW_FOR_EACH_TRAVERSAL_LEAN(HNSW_DECLARE_SEARCH, M_UCOSH)
-HNSW_FOR_EACH_FILTERED(HNSW_DECLARE_FILTERED, M_SQ)
-HNSW_FOR_EACH_FILTERED(HNSW_DECLARE_FILTERED, M_COS)
-HNSW_FOR_EACH_FILTERED(HNSW_DECLARE_FILTERED, M_UCOS)
-HNSW_FOR_EACH_FILTERED(HNSW_DECLARE_FILTERED, M_I8)
-HNSW_FOR_EACH_FILTERED(HNSW_DECLARE_FILTERED, M_SQH)
-HNSW_FOR_EACH_FILTERED(HNSW_DECLARE_FILTERED, M_UCOSH)
-HNSW_FOR_EACH_MULTILAYER(HNSW_DECLARE_MULTILAYER, M_SQ)
-HNSW_FOR_EACH_MULTILAYER(HNSW_DECLARE_MULTILAYER, M_COS)
-HNSW_FOR_EACH_MULTILAYER(HNSW_DECLARE_MULTILAYER, M_UCOS)
-HNSW_FOR_EACH_MULTILAYER(HNSW_DECLARE_MULTILAYER, M_I8)
-HNSW_FOR_EACH_MULTILAYER(HNSW_DECLARE_MULTILAYER, M_SQH)
-HNSW_FOR_EACH_MULTILAYER(HNSW_DECLARE_MULTILAYER, M_UCOSH)
+#define HNSW_TRAVERSAL_UNIT(KIND, ID, TAG) HNSW_UNIT_##KIND(DECLARE, ID)
 #endif
+#define HNSW_TRAVERSAL_UNITS(ID, TAG, NAME) HNSW_FOR_EACH_KIND(HNSW_TRAVERSAL_UNIT, ID, TAG)
+HNSW_FOR_EACH_METRIC(HNSW_TRAVERSAL_UNITS)
 
 // ------------------------------------------------------------------------------------
 // host side of the context
@@ -247,18 +163,23 @@ struct Device::HostGraphStage {
 
 static inline hipStream_t S(void *p) { return (hipStream_t)p; }
 
-// The one place a context's metric becomes a template argument: f(std::integral_constant<int, M>{}).
+// The one place a context's metric becomes a template argument: f(std::integral_constant<int, M>{}), one case per row of the
+// list of metrics.  ucosine's case passes: its turn is with_metric's last line, which also takes every id outside the list (and
+// so this unit's kernels keep the order in which they have always been instantiated: its device code is compared byte for byte).
+template <int ID, class F>
+static bool metric_case(int metric, F &f)
+{
+    if constexpr (ID != M_UCOS)
+        if (metric == ID) { f(std::integral_constant<int, ID>{}); return true; }
+    return false;
+}
 template <class F>
 static void with_metric(int metric, F &&f)
 {
-    switch (metric) {
-    case M_SQ: f(std::integral_constant<int, M_SQ>{}); break;
-    case M_COS: f(std::integral_constant<int, M_COS>{}); break;
-    case M_I8: f(std::integral_constant<int, M_I8>{}); break;
-    case M_SQH: f(std::integral_constant<int, M_SQH>{}); break;
-    case M_UCOSH: f(std::integral_constant<int, M_UCOSH>{}); break;
-    default: f(std::integral_constant<int, M_UCOS>{}); break;
-    }
+#define HNSW_METRIC_CASE(ID, TAG, NAME) if (metric_case<ID>(metric, f)) return;
+    HNSW_FOR_EACH_METRIC(HNSW_METRIC_CASE)
+#undef HNSW_METRIC_CASE
+    f(std::integral_constant<int, M_UCOS>{});
 }
 
 // The hnswdev_stats counters of one kernel family.
@@ -299,7 +220,7 @@ bool Device::bind()
 
 Device *Device::create(int device, int dim, int metric, long long capacity)
 {
-    if (dim <= 0 || metric < 0 || metric > M_UCOSH || capacity < 0) {
+    if (dim <= 0 || metric < 0 || metric >= kMetricCount || capacity < 0) {
         set_dev_error("hnswdev_create: bad argument");
         return nullptr;
     }

@@ -1,7 +1,7 @@
 // device_kernels.h -- all gfx950 device code of the backend (included by device_backend.hip, which holds the host side, and by
-// the traverse_*.hip units, which only instantiate the two big traversal kernel templates -- one metric each -- so that the
-// build compiles them in parallel).  The code lives in the dk_*.h parts, in dependency order:
-//   dk_base.h            includes, wave_sync / wave_lds_sync, metric ids
+// kernel_unit.hip, which only instantiates one kind of the big traversal kernel templates for one metric -- the build compiles it
+// once per (kind, metric), in parallel).  The code lives in the dk_*.h parts, in dependency order:
+//   dk_base.h            includes, wave_sync / wave_lds_sync, half-precision rows
 //   dk_metric.h          the reference's lane arithmetic (EuclideanMetric.cs / CosineMetric.cs), int8 records, slot_distance_kernel
 //   dk_heaps.h           integer keys, the two BinaryHeaps in LDS with the reference's sift rules
 //   dk_measure.h         measure passes (rows of one expansion in one memory round trip)
@@ -16,7 +16,7 @@
 //   dk_insert_kernels.h  graph_insert_search_kernel
 //   dk_link.h            the link half of Add, Remove's re-link
 //   dk_misc_kernels.h    small kernels
-// (dk_exact.h, the flat scan behind hnswdev_exact_knn, is not part of this umbrella: its kernels are compiled in the exact_*.hip
+// (dk_exact.h, the flat scan behind hnswdev_exact_knn, is not part of this umbrella: its kernels are compiled in the exact_unit.hip
 // units alone and reached through launchers, so no other unit carries their code.)
 // See device_backend.hip's header comment for what the kernels replace and the numerical contract.
 #pragma once
@@ -38,8 +38,8 @@
 
 namespace hnsw {
 
-// Explicit instantiations of the two traversal kernels live in traverse_<metric>_<search|insert>.hip;
-// every other unit only declares them.
+// Explicit instantiations of the traversal kernels live in the kernel_unit.hip units, one per (kind, metric) -- the kinds are listed
+// below, the metrics in device_backend.h; every other unit only declares them.
 // Ten forms per metric and kernel (eighteen until round 5) plus four lean ones: register sets NS in {2, 4, 8} (beams up to 128 / 256 / 512; a beam of
 // up to 64 runs in the two-set form), the visited set as a bitset or (graphs above 4M nodes, NS <= 4) a per-wave hash table, and the
 // latency variant of each.  What used to be forms of their own: NS = 1 (same code with one register less), NS = 0 (the exact
@@ -55,23 +55,22 @@ namespace hnsw {
 // units of their own.  (The insert kernel has none: measured, its f32 form loses 6 % that way.)
 #define HNSW_FOR_EACH_TRAVERSAL_LEAN(X, M) \
     X(M, 2, false, kFormLean) X(M, 4, false, kFormLean) X(M, 2, true, kFormLean) X(M, 4, true, kFormLean)
-#define HNSW_SEARCH_SIGNATURE(PREFIX, M, NS, H, LT)                                                                                  \
-    PREFIX template __global__ void graph_search_kernel<M, NS, H, LT>(                                                              \
-        const float *__restrict__, const double *__restrict__, const float *__restrict__, const double *__restrict__, int,      \
-        const int *__restrict__, int, const int64_t *__restrict__, const int *__restrict__, int, const SearchJob *__restrict__,  \
-        int, int, ND *__restrict__, int, unsigned *__restrict__, long long, int *__restrict__, int, int, int *__restrict__,      \
-        float *__restrict__, int *__restrict__, int *__restrict__, unsigned long long *__restrict__, int, int, int *__restrict__, int, \
-        const int *__restrict__);
-#define HNSW_INSERT_SIGNATURE(PREFIX, M, NS, H, LT)                                                                                  \
-    PREFIX template __global__ void graph_insert_search_kernel<M, NS, H, LT>(                                                       \
-        const float *__restrict__, const double *__restrict__, int, const int *__restrict__, int, const int64_t *__restrict__,   \
-        const int *__restrict__, int, const SearchJob *__restrict__, int, int, ND *__restrict__, int, int, unsigned *__restrict__, \
-        long long, int *__restrict__, int, int *__restrict__, int *__restrict__, int *__restrict__, int *__restrict__, int,      \
-        int *__restrict__, unsigned long long *__restrict__, int, int, int *__restrict__, int, const int *__restrict__, int *__restrict__, int);
-#define HNSW_DECLARE_TRAVERSAL(M, NS, H, LT) HNSW_SEARCH_SIGNATURE(extern, M, NS, H, LT) HNSW_INSERT_SIGNATURE(extern, M, NS, H, LT)
-#define HNSW_DECLARE_SEARCH(M, NS, H, LT) HNSW_SEARCH_SIGNATURE(extern, M, NS, H, LT)
-#define HNSW_DEFINE_TRAVERSAL(M, NS, H, LT) HNSW_SEARCH_SIGNATURE(, M, NS, H, LT) HNSW_INSERT_SIGNATURE(, M, NS, H, LT)
-#define HNSW_DEFINE_SEARCH(M, NS, H, LT) HNSW_SEARCH_SIGNATURE(, M, NS, H, LT)
-#define HNSW_DEFINE_INSERT(M, NS, H, LT) HNSW_INSERT_SIGNATURE(, M, NS, H, LT)
+
+// The kinds of kernel unit, X(kind, ...), and what each instantiates for a metric M: HNSW_UNIT_<kind>(DEFINE, M) is the unit's
+// content (kernel_unit.hip), HNSW_UNIT_<kind>(DECLARE, M) the extern template declarations of everyone else.  build.py's KINDS
+// is the same list: a unit is compiled with -DHNSW_UNIT_KIND=<kind>.  A grid over metrics x kinds is two lines where it is needed:
+//     #define PER_UNIT(KIND, ID, TAG) ...
+//     #define PER_METRIC(ID, TAG, NAME) HNSW_FOR_EACH_KIND(PER_UNIT, ID, TAG)
+//     HNSW_FOR_EACH_METRIC(PER_METRIC)
+#define HNSW_FOR_EACH_KIND(X, ...) \
+    X(insert, __VA_ARGS__) X(insert_lat, __VA_ARGS__) X(search, __VA_ARGS__) X(search_lat, __VA_ARGS__) X(search_lean, __VA_ARGS__) \
+    X(filtered, __VA_ARGS__) X(multilayer, __VA_ARGS__)
+#define HNSW_UNIT_insert(DO, M) HNSW_FOR_EACH_TRAVERSAL(HNSW_##DO##_INSERT, M)
+#define HNSW_UNIT_insert_lat(DO, M) HNSW_FOR_EACH_TRAVERSAL_LAT(HNSW_##DO##_INSERT, M)
+#define HNSW_UNIT_search(DO, M) HNSW_FOR_EACH_TRAVERSAL(HNSW_##DO##_SEARCH, M)
+#define HNSW_UNIT_search_lat(DO, M) HNSW_FOR_EACH_TRAVERSAL_LAT(HNSW_##DO##_SEARCH, M)
+#define HNSW_UNIT_search_lean(DO, M) HNSW_FOR_EACH_TRAVERSAL_LEAN(HNSW_##DO##_SEARCH, M)
+#define HNSW_UNIT_filtered(DO, M) HNSW_FOR_EACH_FILTERED(HNSW_##DO##_FILTERED, M)
+#define HNSW_UNIT_multilayer(DO, M) HNSW_FOR_EACH_MULTILAYER(HNSW_##DO##_MULTILAYER, M)
 
 } // namespace hnsw

@@ -1,4 +1,4 @@
-// dk_base.h -- device code, part of device_kernels.h: includes, launch-shape macros, wave-level synchronisation, metric ids.
+// dk_base.h -- device code, part of device_kernels.h: includes, launch-shape macros, wave-level synchronisation, half-precision rows.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -65,8 +65,7 @@ __device__ __forceinline__ T kernarg_load(unsigned byte_offset)
     typedef const volatile T __attribute__((address_space(4))) *tptr;
     return *(tptr)((cptr)__builtin_amdgcn_kernarg_segment_ptr() + byte_offset);
 }
-enum { M_SQ = HNSWDEV_SQ_EUCLID, M_COS = HNSWDEV_COSINE, M_UCOS = HNSWDEV_UCOSINE, M_I8 = HNSWDEV_SQ_EUCLID_I8,
-       M_SQH = HNSWDEV_SQ_EUCLID_F16, M_UCOSH = HNSWDEV_UCOSINE_F16 };
+// (the metric ids M_* and their list HNSW_FOR_EACH_METRIC: device_backend.h, which the host-only units can include too)
 
 // ---- half-precision row storage (M_SQH, M_UCOSH) --------------------------------------------------------
 // The arithmetic of X_f16 is X's, on stored rows widened from binary16 (exact): metric_is_sq / metric_is_ucos name the

@@ -4,7 +4,7 @@
 //   exact_compact_kernel   bitset (allow AND live, masked on the host) -> ascending id list
 //   exact_scan_kernel<M>   a tile of queries x a chunk of the id list per block; per (query, chunk) a sorted list of k keys in LDS
 //   exact_merge_kernel     one wave per query: the chunks' lists -> the final k, ids and distances in the output layout
-// The kernels are compiled in the exact_<metric>.hip units (HNSW_EXACT_UNIT) and reached through the launchers declared here, so
+// The kernels are compiled in the exact_<metric> units (exact_unit.hip, HNSW_EXACT_UNIT) and reached through the launchers declared here, so
 // that device_backend.hip holds none of their code.
 #pragma once
 #include <hip/hip_runtime.h>

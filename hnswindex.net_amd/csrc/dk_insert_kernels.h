@@ -207,5 +207,13 @@ graph_insert_search_kernel(const float *__restrict__ rows, const double *__restr
 
     if constexpr (LAT) port.post(-1, 0, lane); // the memory wave leaves
 }
+#define HNSW_INSERT_SIGNATURE(PREFIX, M, NS, H, LT)                                                                                  \
+    PREFIX template __global__ void graph_insert_search_kernel<M, NS, H, LT>(                                                       \
+        const float *__restrict__, const double *__restrict__, int, const int *__restrict__, int, const int64_t *__restrict__,   \
+        const int *__restrict__, int, const SearchJob *__restrict__, int, int, ND *__restrict__, int, int, unsigned *__restrict__, \
+        long long, int *__restrict__, int, int *__restrict__, int *__restrict__, int *__restrict__, int *__restrict__, int,      \
+        int *__restrict__, unsigned long long *__restrict__, int, int, int *__restrict__, int, const int *__restrict__, int *__restrict__, int);
+#define HNSW_DECLARE_INSERT(M, NS, H, LT) HNSW_INSERT_SIGNATURE(extern, M, NS, H, LT)
+#define HNSW_DEFINE_INSERT(M, NS, H, LT) HNSW_INSERT_SIGNATURE(, M, NS, H, LT)
 
 } // namespace hnsw

@@ -352,6 +352,15 @@ graph_search_kernel(const float *__restrict__ rows, const double *__restrict__ r
 
     if constexpr (LAT) port.post(-1, 0, lane); // the memory wave leaves
 }
+#define HNSW_SEARCH_SIGNATURE(PREFIX, M, NS, H, LT)                                                                                  \
+    PREFIX template __global__ void graph_search_kernel<M, NS, H, LT>(                                                              \
+        const float *__restrict__, const double *__restrict__, const float *__restrict__, const double *__restrict__, int,      \
+        const int *__restrict__, int, const int64_t *__restrict__, const int *__restrict__, int, const SearchJob *__restrict__,  \
+        int, int, ND *__restrict__, int, unsigned *__restrict__, long long, int *__restrict__, int, int, int *__restrict__,      \
+        float *__restrict__, int *__restrict__, int *__restrict__, unsigned long long *__restrict__, int, int, int *__restrict__, int, \
+        const int *__restrict__);
+#define HNSW_DECLARE_SEARCH(M, NS, H, LT) HNSW_SEARCH_SIGNATURE(extern, M, NS, H, LT)
+#define HNSW_DEFINE_SEARCH(M, NS, H, LT) HNSW_SEARCH_SIGNATURE(, M, NS, H, LT)
 
 // KnnQuery with an allow-set (HNSWIndex.KnnQuery(query, k, filterFnc, layer), HNSWIndex.cs:107-124): FindEntryPointQuery down to
 // search_layer (exclusive), unfiltered, then SearchLayerQuery with the filter (GraphNavigator.cs:194-256) in the exact two-heap traversal -- the sorted-list

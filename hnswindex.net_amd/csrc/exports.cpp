@@ -56,14 +56,7 @@ API int hnsw_get_last_error_utf8(void *buf, int buf_len) // :27-39
 
 static int parse_metric(const char *distance_metric) // :47-60
 {
-    if (!distance_metric) return -1;
-    if (!std::strcmp(distance_metric, "sq_euclid")) return HNSWDEV_SQ_EUCLID;
-    if (!std::strcmp(distance_metric, "cosine")) return HNSWDEV_COSINE;
-    if (!std::strcmp(distance_metric, "ucosine")) return HNSWDEV_UCOSINE;
-    if (!std::strcmp(distance_metric, "sq_euclid_i8")) return HNSWDEV_SQ_EUCLID_I8; // not in the reference: int8 rows (BASELINE config 5)
-    if (!std::strcmp(distance_metric, "sq_euclid_f16")) return HNSWDEV_SQ_EUCLID_F16; // not in the reference: rows stored as binary16
-    if (!std::strcmp(distance_metric, "ucosine_f16")) return HNSWDEV_UCOSINE_F16;
-    return -1;
+    return distance_metric ? hnsw::metric_by_name(distance_metric) : -1; // the names: device_backend.h, HNSW_FOR_EACH_METRIC
 }
 
 API void *hnsw_create(const char *distance_metric) // :41-65

@@ -698,7 +698,7 @@ struct Tick {
 // ------------------------------------------------------------------------------------
 HnswIndex *HnswIndex::create(int metric, const Params &p, std::string &err)
 {
-    if (metric < 0 || metric > HNSWDEV_UCOSINE_F16) { err = "Unsupported distance metric"; return nullptr; }
+    if (metric < 0 || metric >= kMetricCount) { err = "Unsupported distance metric"; return nullptr; }
     int ndev = hnswdev_device_count();
     if (ndev <= 0) {
         err = "HNSWIndex MI355X backend: no HIP device available (" + get_dev_error() +

@@ -21,9 +21,18 @@ for f, kern in (("dk_search_kernels.h", "graph_search_kernel(const float *__rest
     open(f, "w").write(s)
 E
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fvisibility=hidden -I. --cuda-device-only"
+unit_args() { # unit name -> its -D flags and source file, from build.py's table of units
+  python3 - "$R" "$1" <<'E'
+import importlib.util, sys
+spec = importlib.util.spec_from_file_location("hnsw_build", sys.argv[1] + "/hnswindex.net_amd/build.py")
+build = importlib.util.module_from_spec(spec)
+spec.loader.exec_module(build)
+print(*next((*defs, src) for name, src, defs in build.units() if name == sys.argv[2]))
+E
+}
 compile() { # unit, dim (0 = as shipped), tag
   local d=""; [ "$2" != 0 ] && d="-DEXP_ASSUME_DIM=$2"
-  hipcc $FLAGS $d -c $1 -o $T/$3.o -Rpass-analysis=kernel-resource-usage 2> $T/$3.txt
+  hipcc $FLAGS $d -c $(unit_args $1) -o $T/$3.o -Rpass-analysis=kernel-resource-usage 2> $T/$3.txt
 }
 report() { # unit, dim, tag
   python3 - $T/$3.txt $T/$3.o "$1" "$2" <<'E'
@@ -50,15 +59,15 @@ E
 }
 echo "# tools/fixed_dim_static.sh: the traversal kernels with the row length known at compile time (static; scratch copy + __builtin_assume; the product is unchanged)"
 echo "# graph_*_kernel<METRIC, NS, HASHED, FORM>: form 1 = latency variant, 2 = lean; 'waves/SIMD' is what the register count allows, the shipped kernels pin theirs with amdgpu_waves_per_eu"
-SPECS="traverse_sq_search_lean.hip:128 traverse_i8_search_lean.hip:32 traverse_sq_search_lat.hip:128 traverse_sq_insert_lat.hip:128"
+SPECS="search_lean_sq:128 search_lean_i8:32 search_lat_sq:128 insert_lat_sq:128"   # units by name (build.py units())
 for spec in $SPECS; do
   set -- ${spec%%:*} ${spec##*:}
-  compile $1 0 a_${1%.hip} &
-  compile $1 $2 b_${1%.hip} &
+  compile $1 0 a_$1 &
+  compile $1 $2 b_$1 &
 done
 wait
 for spec in $SPECS; do
   u=${spec%%:*}; d=${spec##*:}
-  report $u 0 a_${u%.hip}
-  report $u $d b_${u%.hip}
+  report $u 0 a_$u
+  report $u $d b_$u
 done

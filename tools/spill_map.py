@@ -4,7 +4,7 @@ loads / stores of one kernel, attributed to the source lines the compiler's line
 (label .. backward branch) they sit in.  A lane move counts as a spill when its vector register is touched by lane moves ONLY (the
 registers the compiler parks scalars in); the broadcasts the algorithm itself asks for use registers that ordinary instructions touch too.  The lean form of graph_search_kernel was found this way round from counters (half of a
 launch's vector instructions were such moves); this tool answers "which lines" before a change goes to the GPU.
-    python tools/spill_map.py traverse_sq_insert_lat.hip 'graph_insert_search_kernel<0, 4, false, 1>' [--top 25]"""
+    python tools/spill_map.py insert_lat_sq 'graph_insert_search_kernel<0, 4, false, 1>' [--top 25]"""
 import argparse
 import importlib.util
 import re
@@ -45,13 +45,17 @@ INSTR = re.compile(r"^\s+([a-z][a-z0-9_]+)\b")
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("unit")
+    ap.add_argument("unit", help="a unit name of build.py's units(), e.g. insert_lat_sq or device_backend")
     ap.add_argument("kernel", help="demangled name as tools/kernel_resources.py prints it")
     ap.add_argument("--top", type=int, default=25)
     a = ap.parse_args()
+    table = {name: (src, defs) for name, src, defs in build.units()}
+    if a.unit not in table:
+        sys.exit(f"no unit {a.unit!r}; the units: " + " ".join(table))
+    src, defs = table[a.unit]
     with tempfile.TemporaryDirectory() as tmp:
         asm = Path(tmp) / "k.s"
-        cmd = [build.hipcc(), *build.FLAGS, "-gline-tables-only", f"-I{ROOT / 'include'}", f"-I{CSRC}", "--cuda-device-only", "-S", str(CSRC / a.unit), "-o", str(asm)]
+        cmd = [build.hipcc(), *build.FLAGS, *defs, "-gline-tables-only", f"-I{ROOT / 'include'}", f"-I{CSRC}", "--cuda-device-only", "-S", str(CSRC / src), "-o", str(asm)]
         subprocess.run(cmd, check=True, capture_output=True)
         lines = asm.read_text().split("\n")
     files, body, inside = {}, [], False
