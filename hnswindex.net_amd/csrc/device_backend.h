@@ -12,6 +12,7 @@
 #include <thread>
 
 #include "../../include/hnsw_mi355x.h"
+#include "dev_buf.h"
 
 namespace hnsw {
 
@@ -353,39 +354,39 @@ private:
     int device_ = 0, dim_ = 0, metric_ = 0;
     int pitch_ = 0; // 32-bit words per resident query, and what the kernels get as `dim` (== dim_ for the float metrics, f16 rows included; the int8 record otherwise)
     int row_pitch_ = 0; // 32-bit words per STORED row: pitch_, but the half-precision record (8 * ceil(dim / 16)) for the _f16 metrics, whose queries stay f32
-    float *q_stage_ = nullptr; // int8 and f16 rows: float staging area on the device (quantise / round on upload, dequantise / widen on download)
-    size_t q_stage_cap_ = 0;
+    // Every buffer, event and stream below is a holder (dev_buf.h): it frees itself, and its cap() is the only record of its size.
+    DevBuf<float> q_stage_; // int8 and f16 rows: float staging area on the device (quantise / round on upload, dequantise / widen on download)
     long long capacity_ = 0;
     long long n_rows_hw_ = 0; // high-water mark of uploaded rows (id validation)
-    float *d_rows_ = nullptr;
-    double *d_row_sn_ = nullptr; // cosine: sqrt((double)|row|^2_f32)
-    float *d_queries_ = nullptr;
-    double *d_q_sn_ = nullptr;
-    long long q_capacity_ = 0, n_queries_ = 0;
-    // graph mirror
-    int *g_adj0_ = nullptr, *g_level_ = nullptr, *g_pool_ = nullptr;
-    int64_t *g_upper_ = nullptr;
-    long long g_n_ = 0, g_cap_n_ = 0, g_pool_cap_ = 0;
+    DevBuf<float> d_rows_;    // (a view borrows the rows, their norms and the graph mirror: rebind)
+    DevBuf<double> d_row_sn_; // cosine: sqrt((double)|row|^2_f32)
+    DevBuf<float> d_queries_;
+    DevBuf<double> d_q_sn_;
+    long long q_capacity() const { return (long long)(d_queries_.cap() / (size_t)pitch_); }
+    long long n_queries_ = 0;
+    // graph mirror; the node arrays are replaced together and g_tested0_, allocated last, stands for their capacity in nodes,
+    // as g_testedU_ does for the pool pair's
+    DevBuf<int> g_adj0_, g_level_, g_pool_;
+    DevBuf<int64_t> g_upper_;
+    long long g_n_ = 0;
+    long long g_cap_n() const { return (long long)g_tested0_.cap(); }
+    long long g_pool_cap() const { return (long long)g_testedU_.cap(); }
+    bool graph_room(long long n, long long node_cap, int stride0, long long pool_len);
     // per adjacency list: how many leading entries are the ordered, mutually tested output of a
     // RelativeNeighborPruning run (graph_link_kernel's shortcut); 0 = unknown
-    int *g_tested0_ = nullptr, *g_testedU_ = nullptr;
+    DevBuf<int> g_tested0_, g_testedU_;
     int g_stride0_ = 0, g_strideU_ = 0;
     // search scratch
-    unsigned *s_visited_ = nullptr;
-    size_t s_visited_bytes_ = 0;
-    int *s_jobctr_ = nullptr; // persistent launches: next job
-    int *lp_slot_[3] = {nullptr, nullptr, nullptr}; // device-side link grouping: per list slot count / fill / offset
-    long long lp_slots_ = 0;
-    int *lp_grp_[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; // per group node / layer / start / count; items as filed; items in batch order
-    size_t lp_grp_cap_[6] = {0, 0, 0, 0, 0, 0};
-    int *lp_counters_ = nullptr;
+    DevBuf<unsigned> s_visited_;
+    DevBuf<int> s_jobctr_; // persistent launches: next job
+    DevBuf<int> lp_slot_[3]; // device-side link grouping: per list slot count / fill / offset
+    DevBuf<int> lp_grp_[6];  // per group node / layer / start / count; items as filed; items in batch order
+    DevBuf<int> lp_counters_;
     int last_insert_jobs_ = 0, last_insert_upper_ = 0, last_insert_stride_ = 0; // what insert_search_batch left on the device
     int fetch_njobs_ = 0, fetch_nupper_ = 0;                                    // ... and what fetch_insert_selections would copy
-    int *s_vistab_ = nullptr; // per-wave visited-id hash tables
-    size_t s_vistab_cap_ = 0;
+    DevBuf<int> s_vistab_; // per-wave visited-id hash tables
     int s_vistab_each_ = 0;
-    int *s_fvistab_ = nullptr; // ... and those of the filtered search launches
-    size_t s_fvistab_cap_ = 0;
+    DevBuf<int> s_fvistab_; // ... and those of the filtered search launches
     int s_fvistab_each_ = 0;
     bool visited_scratch(int k, int min_cap, bool allow_hash, VisitedScratch *out, bool filtered = false);
     bool plan_traversal(bool insert, int k, bool two_heap, size_t lds, TraversalLaunch *out, bool filtered = false);
@@ -398,86 +399,60 @@ private:
     // >= 128 VGPRs): the per-wave scratch (visited bitsets, spill areas, logs) is sized for that.
     int max_slots() const { return num_cu_ * max_waves_per_cu(); }
     static int max_waves_per_cu(); // persistent waves per CU the per-wave scratch is sized for
-    SearchJob *s_jobs_ = nullptr;
-    SearchHit *s_hits_ = nullptr;
-    int *s_cnt_ = nullptr, *s_flag_ = nullptr;
-    unsigned long long *s_evals_ = nullptr;
-    size_t s_jobs_cap_ = 0, s_hits_cap_ = 0;
-    int *s_sel_ = nullptr, *s_lcnt_ = nullptr, *s_selU_ = nullptr, *s_cntU_ = nullptr, *s_iflag_ = nullptr;
-    size_t s_sel_cap_ = 0, s_lcnt_cap_ = 0, s_selU_cap_ = 0, s_cntU_cap_ = 0, s_iflag_cap_ = 0;
-    void *h_res_ = nullptr; // pinned: results of insert_search_batch
-    size_t h_res_cap_ = 0;
-    int *s_rl_ = nullptr; // relink / patch staging on the device
-    size_t s_rl_cap_ = 0;
-    int *s_order_ = nullptr; // insert search: processing order of a batch's jobs
-    size_t s_order_cap_ = 0;
-    int *s_rlog_ = nullptr; // insert search: per-job read logs (exact-window Add)
-    size_t s_rlog_cap_ = 0;
-    bool is_view_ = false;
+    DevBuf<SearchJob> s_jobs_; // s_jobs_, s_cnt_ and s_flag_ are replaced together: s_flag_, allocated last, stands for the job capacity
+    DevBuf<SearchHit> s_hits_;
+    DevBuf<int> s_cnt_, s_flag_;
+    DevBuf<unsigned long long> s_evals_;
+    DevBuf<int> s_sel_, s_lcnt_, s_selU_, s_cntU_, s_iflag_;
+    PinBuf<char> h_res_; // pinned: results of insert_search_batch
+    DevBuf<int> s_rl_; // relink / patch staging on the device
+    DevBuf<int> s_order_; // insert search: processing order of a batch's jobs
+    DevBuf<int> s_rlog_; // insert search: per-job read logs (exact-window Add)
     struct QueryTail { const float *src = nullptr; long long first = 0, n = 0; } tail_; // set_queries_streamed: rows still on the host
-    int *h_ready_ = nullptr, *d_ready_ = nullptr; // rows of the query set that have landed (host memory, read by the kernel)
-    void *copy_stream_ = nullptr;
+    PinBuf<int> h_ready_; // rows of the query set that have landed (host memory, read by the kernel ...
+    int *d_ready_ = nullptr; // ... through this device address of it)
+    DevStream copy_stream_;
     bool upload_tail();
-    int *s_dry_ = nullptr;  // link_dry_run: [jobs | flags]
-    size_t s_dry_cap_ = 0;
-    int *s_wdry_ = nullptr; // windowed insert search: upper_owner
-    size_t s_wdry_cap_ = 0;
-    int *s_win_ = nullptr;  // windowed insert search: every output of the launch, laid out like the pinned result block
-    size_t s_win_cap_ = 0;
-    SearchHit *s_spill_ = nullptr;
-    size_t s_spill_cap_ = 0;
-    SearchHit *s_fspill_ = nullptr; // filtered searches: their own, larger spill areas (allocated by the first such call)
-    size_t s_fspill_cap_ = 0;
-    unsigned *s_allow_ = nullptr;   // filtered searches: the call's allow-set
-    size_t s_allow_cap_ = 0;
-    int *x_ids_ = nullptr;                 // exact_knn: the call's ascending id list (exact_compact_kernel)
-    size_t x_ids_cap_ = 0;
-    long long *x_boff_ = nullptr;          // ... set bits in front of each block of bitset words
-    size_t x_boff_cap_ = 0;
-    unsigned long long *x_lists_ = nullptr; // ... the per-(query, chunk) lists of a round: at most 1 GiB, allocated by the first call and kept
-    size_t x_lists_cap_ = 0;
-    int *x_out_ = nullptr;                 // ... a round's [ids | distances]
-    size_t x_out_cap_ = 0;
-    unsigned long long *x_evals_ = nullptr; // ... (query, row) pairs the scan kernel measured, counted on the device
-    size_t x_evals_cap_ = 0;
-    float *x_queries_ = nullptr;           // ... its own query set (set_queries writes it while it stands in for d_queries_)
-    double *x_q_sn_ = nullptr;
-    long long x_q_capacity_ = 0;
-    SearchHit *s_arena_ = nullptr; // range search: the launch's results, packed
-    size_t s_arena_cap_ = 0;
-    unsigned long long *s_roff_ = nullptr, *s_arena_used_ = nullptr;
-    int *s_rentry_ = nullptr;
-    SearchHit *h_range_ = nullptr;     // RangeQuery results on the host (pinned, grown on demand, filled by ONE device-to-host copy per launch)
-    size_t h_range_cap_ = 0;
+    DevBuf<int> s_dry_;  // link_dry_run: [jobs | flags]
+    DevBuf<int> s_wdry_; // windowed insert search: upper_owner
+    DevBuf<int> s_win_;  // windowed insert search: every output of the launch, laid out like the pinned result block
+    DevBuf<SearchHit> s_spill_;
+    DevBuf<SearchHit> s_fspill_; // filtered searches: their own, larger spill areas (allocated by the first such call)
+    DevBuf<unsigned> s_allow_;   // filtered searches: the call's allow-set
+    DevBuf<int> x_ids_;                 // exact_knn: the call's ascending id list (exact_compact_kernel)
+    DevBuf<long long> x_boff_;          // ... set bits in front of each block of bitset words
+    DevBuf<unsigned long long> x_lists_; // ... the per-(query, chunk) lists of a round: at most 1 GiB, allocated by the first call and kept
+    DevBuf<int> x_out_;                 // ... a round's [ids | distances]
+    DevBuf<unsigned long long> x_evals_; // ... (query, row) pairs the scan kernel measured, counted on the device
+    DevBuf<float> x_queries_;           // ... its own query set (set_queries writes it while it stands in for d_queries_)
+    DevBuf<double> x_q_sn_;
+    DevBuf<SearchHit> s_arena_; // range search: the launch's results, packed
+    DevBuf<unsigned long long> s_roff_, s_arena_used_; // s_roff_ stands for the capacity of range_batch's per-job arrays
+    DevBuf<int> s_rentry_;
+    PinBuf<SearchHit> h_range_;     // RangeQuery results on the host (pinned, grown on demand, filled by ONE device-to-host copy per launch)
     bool range_host_room(size_t entries, size_t keep);
-    int *s_rstate_ = nullptr, *s_rtied_ = nullptr, *s_rfin_ctr_ = nullptr; // RangeQuery's finishing kernels: per-job state, the tied jobs, two job counters
-    int *s_rres_ = nullptr;                  // filtered RangeQuery: allowed entries per job (range_sort_kernel<true>)
-    unsigned long long *s_rdst_ = nullptr;   // ... where each job's list lands in the packed copy-back (range_pack_kernel)
-    SearchHit *s_rpack_ = nullptr;           // ... the packed copy-back
-    size_t s_rpack_cap_ = 0;
-    SearchHit *s_rlists_ = nullptr; // range search: long per-wave result lists for the few jobs that outgrow s_spill_'s
-    size_t s_rlists_cap_ = 0;
+    DevBuf<int> s_rstate_, s_rtied_, s_rfin_ctr_; // RangeQuery's finishing kernels: per-job state, the tied jobs, two job counters
+    DevBuf<int> s_rres_;                  // filtered RangeQuery: allowed entries per job (range_sort_kernel<true>)
+    DevBuf<unsigned long long> s_rdst_;   // ... where each job's list lands in the packed copy-back (range_pack_kernel)
+    DevBuf<SearchHit> s_rpack_;           // ... the packed copy-back
+    DevBuf<SearchHit> s_rlists_; // range search: long per-wave result lists for the few jobs that outgrow s_spill_'s
     double range_hint_ = 48.0;      // results per query of the last range search (sizes the next arena)
-    size_t s_roff_cap_ = 0;
     std::vector<SearchHit> abi_range_; // hnswdev_range_search's results until hnswdev_range_results
-    int *s_lk_[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    size_t s_lk_cap_[5] = {0, 0, 0, 0, 0};
+    DevBuf<int> s_lk_[5];
     bool ensure_search_scratch(long long chunk, long long slots, int k, size_t vis_bytes_per_job);
     void *pinned_stage(size_t bytes);
     bool staged_upload(float *dst, const float *src, size_t bytes);
-    void *up_pin_[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; // staged_upload: two pinned chunks per helper thread
-    void *up_ev_[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    PinBuf<char> up_pin_[8]; // staged_upload: two pinned chunks per helper thread
+    DevEvent up_ev_[8];
     bool up_busy_[8] = {false, false, false, false, false, false, false, false};
     struct HostGraphStage;
     HostGraphStage *hg_ = nullptr;
-    void *h_stage_ = nullptr;
-    size_t h_stage_cap_ = 0;
-    void *ev0_ = nullptr, *ev1_ = nullptr, *ev2_ = nullptr;
+    PinBuf<char> h_stage_;
+    DevEvent ev0_, ev1_, ev2_;
     struct LinkSet { // pinned staging of one in-flight link sub-batch
-        int *h_in = nullptr, *h_out = nullptr;
-        size_t in_cap = 0, out_cap = 0;
-        unsigned long long *h_ev = nullptr;
-        void *ev_start = nullptr, *ev_stop = nullptr, *ev_done = nullptr;
+        PinBuf<int> h_in, h_out;
+        PinBuf<unsigned long long> h_ev;
+        DevEvent ev_start, ev_stop, ev_done;
         bool busy = false, timed = false;
         int ngroups = 0;
     } lset_[2];
@@ -486,14 +461,14 @@ private:
         std::atomic<long long> resident{0}; // rows with id < resident have landed
         std::atomic<bool> failed{false}, active{false};
         std::string err;
-        void *stream = nullptr, *pin[2] = {nullptr, nullptr}, *ev[2] = {nullptr, nullptr};
-        size_t pin_bytes = 0;
+        DevStream stream;
+        PinBuf<char> pin[2];
+        DevEvent ev[2];
     } bg_;
     StepBuffers *abi_sb_[4] = {nullptr, nullptr, nullptr, nullptr}; // context-owned step-buffer sets: 0/1 handed out by hnswdev_step_buffers, 2/3 private to dist_query_batch (so it never moves buffers a caller holds)
-    int *d_guard_ = nullptr;                      // guard flag of pair_distance_kernel
-    int *pair_dev_ = nullptr;                     // dist_pair_batch: [a | b | out] on the device
-    size_t pair_dev_cap_ = 0;
-    void *stream_ = nullptr;
+    DevBuf<int> d_guard_;                         // guard flag of pair_distance_kernel
+    DevBuf<int> pair_dev_;                        // dist_pair_batch: [a | b | out] on the device
+    DevStream stream_; // (destroyed by ~Device itself, before any holder lets go of its memory)
     bool profiling_ = false;
     hnswdev_stats stats_{};
     bool shadows_allowed_ = true;

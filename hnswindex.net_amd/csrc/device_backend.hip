@@ -83,16 +83,50 @@ std::string get_dev_error()
         }                                                                                         \
     } while (0)
 
-template <class T>
-static bool grow_dev(T **p, size_t *cap, size_t need)
+// What the holders of dev_buf.h sit on: the only places a context's memory, events and streams are allocated and released
+// (alloc_step / free_step keep the StepBuffers' own matched pair).
+void *dev_mem_alloc(size_t bytes)
 {
-    if (need <= *cap) return true;
-    if (*p) HIP_OK(hipFree(*p));
-    *p = nullptr;
-    HIP_OK(hipMalloc(p, sizeof(T) * need));
-    *cap = need;
-    return true;
+    void *p = nullptr;
+    const hipError_t e = hipMalloc(&p, bytes);
+    if (e == hipSuccess) return p;
+    set_dev_error("hipMalloc(" + std::to_string(bytes) + " bytes): " + hipGetErrorString(e));
+    return nullptr;
 }
+bool dev_mem_free(void *p) { HIP_OK(hipFree(p)); return true; }
+void *pin_mem_alloc(size_t bytes, unsigned flags)
+{
+    void *p = nullptr;
+    const hipError_t e = hipHostMalloc(&p, bytes, flags);
+    if (e == hipSuccess) return p;
+    set_dev_error("pinned allocation failed: hipHostMalloc(" + std::to_string(bytes) + " bytes): " + hipGetErrorString(e));
+    return nullptr;
+}
+bool pin_mem_free(void *p) { HIP_OK(hipHostFree(p)); return true; }
+static constexpr unsigned kPinMappedCoherent = hipHostMallocMapped | hipHostMallocCoherent; // h_ready_: host memory the kernel reads
+void *dev_event_create(bool timing)
+{
+    hipEvent_t ev = nullptr;
+    const hipError_t e = timing ? hipEventCreate(&ev) : hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+    if (e == hipSuccess) return ev;
+    set_dev_error(std::string("hipEventCreate: ") + hipGetErrorString(e));
+    return nullptr;
+}
+void dev_event_destroy(void *e) { (void)hipEventDestroy((hipEvent_t)e); }
+// High priority (copy streams only): the copies a gated kernel waits for must never queue behind that kernel.  HIP multiplexes
+// streams onto a few hardware queues, and a copy stream that lands on the queue of a compute stream does exactly that (measured:
+// two lanes, every wave slept its full bound).  High-priority streams have hardware queues of their own.
+void *dev_stream_create(bool high_priority)
+{
+    hipStream_t st = nullptr;
+    int lo = 0, hi = 0;
+    hipError_t e = high_priority ? hipDeviceGetStreamPriorityRange(&lo, &hi) : hipSuccess;
+    if (e == hipSuccess) e = high_priority ? hipStreamCreateWithPriority(&st, hipStreamNonBlocking, hi) : hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
+    if (e == hipSuccess) return st;
+    set_dev_error(std::string("hipStreamCreate failed: ") + hipGetErrorString(e));
+    return nullptr;
+}
+void dev_stream_destroy(void *s) { (void)hipStreamDestroy((hipStream_t)s); }
 
 #ifdef EXP_PHASE_CLOCKS
 HNSW_PHASE_BIND(backend)
@@ -162,6 +196,7 @@ struct Device::HostGraphStage {
 };
 
 static inline hipStream_t S(void *p) { return (hipStream_t)p; }
+static inline hipEvent_t E(void *p) { return (hipEvent_t)p; }
 
 // The one place a context's metric becomes a template argument: f(std::integral_constant<int, M>{}), one case per row of the
 // list of metrics.  ucosine's case passes: its turn is with_metric's last line, which also takes every id outside the list (and
@@ -206,7 +241,7 @@ bool Device::count_launch(const LaunchFamily *family, unsigned long long evals, 
     if (hashed) stats_.visited_hash_launches++;
     if (!timed) return true;
     float ms = 0.f;
-    HIP_OK(hipEventElapsedTime(&ms, (hipEvent_t)t0, (hipEvent_t)t1));
+    HIP_OK(hipEventElapsedTime(&ms, E(t0), E(t1)));
     for (const LaunchFamily *f : {&kSearchFamily, family})
         if (f) { stats_.*f->kernel_ms += ms; stats_.*f->timed_launches += 1; stats_.*f->timed_evals += evals; }
     return true;
@@ -248,9 +283,7 @@ Device *Device::create(int device, int dim, int metric, long long capacity)
     d->stats_.row_bytes = metric == M_I8 ? (uint64_t)dim + 4u : metric_f16(metric) ? (uint64_t)dim * 2u : (uint64_t)dim * sizeof(float);
     auto fail = [&]() -> Device * { delete d; return nullptr; };
     if (hipSetDevice(device) != hipSuccess) { set_dev_error("hipSetDevice failed"); return fail(); }
-    hipStream_t st;
-    if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) { set_dev_error("hipStreamCreate failed"); return fail(); }
-    d->stream_ = st;
+    if (!d->stream_.create(false)) return fail();
     {
         int cus = 0;
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0) d->num_cu_ = cus;
@@ -266,7 +299,6 @@ Device *Device::create_view(Device *primary)
 {
     if (!primary) return nullptr;
     Device *d = new Device();
-    d->is_view_ = true;
     d->device_ = primary->device_;
     d->dim_ = primary->dim_;
     d->pitch_ = primary->pitch_;
@@ -275,61 +307,31 @@ Device *Device::create_view(Device *primary)
     d->stats_.row_bytes = primary->stats_.row_bytes;
     d->num_cu_ = primary->num_cu_;
     if (hipSetDevice(d->device_) != hipSuccess) { set_dev_error("hipSetDevice failed"); delete d; return nullptr; }
-    hipStream_t st;
-    if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) { set_dev_error("hipStreamCreate failed"); delete d; return nullptr; }
-    d->stream_ = st;
+    if (!d->stream_.create(false)) { delete d; return nullptr; }
     d->rebind(primary);
     return d;
 }
 
 void Device::rebind(const Device *p)
 {
-    d_rows_ = p->d_rows_; d_row_sn_ = p->d_row_sn_; capacity_ = p->capacity_; n_rows_hw_ = p->n_rows_hw_;
-    g_adj0_ = p->g_adj0_; g_level_ = p->g_level_; g_upper_ = p->g_upper_; g_pool_ = p->g_pool_;
-    g_tested0_ = p->g_tested0_; g_testedU_ = p->g_testedU_;
-    g_n_ = p->g_n_; g_cap_n_ = p->g_cap_n_; g_pool_cap_ = p->g_pool_cap_; g_stride0_ = p->g_stride0_; g_strideU_ = p->g_strideU_;
+    d_rows_.borrow(p->d_rows_); d_row_sn_.borrow(p->d_row_sn_); capacity_ = p->capacity_; n_rows_hw_ = p->n_rows_hw_;
+    g_adj0_.borrow(p->g_adj0_); g_level_.borrow(p->g_level_); g_upper_.borrow(p->g_upper_); g_pool_.borrow(p->g_pool_);
+    g_tested0_.borrow(p->g_tested0_); g_testedU_.borrow(p->g_testedU_);
+    g_n_ = p->g_n_; g_stride0_ = p->g_stride0_; g_strideU_ = p->g_strideU_;
 }
 
+// Only what has an order is written out; the holders release everything else after this body.  Should hipSetDevice fail, the
+// memory is still freed by pointer (it used to be left behind).
 Device::~Device()
 {
-    if (hipSetDevice(device_) != hipSuccess) return;
-    if (is_view_) { // borrowed: the primary frees them
-        d_rows_ = nullptr; d_row_sn_ = nullptr;
-        g_adj0_ = nullptr; g_level_ = nullptr; g_upper_ = nullptr; g_pool_ = nullptr; g_tested0_ = nullptr; g_testedU_ = nullptr;
-    }
-    if (stream_) { (void)hipStreamSynchronize(S(stream_)); (void)hipStreamDestroy(S(stream_)); }
-    for (int i = 0; i < 8; ++i) { if (up_pin_[i]) (void)hipHostFree(up_pin_[i]); if (up_ev_[i]) (void)hipEventDestroy((hipEvent_t)up_ev_[i]); }
-    if (h_ready_) (void)hipHostFree(h_ready_);
-    if (copy_stream_) (void)hipStreamDestroy(S(copy_stream_));
+    (void)hipSetDevice(device_);
+    if (stream_) (void)hipStreamSynchronize(S(stream_));
+    stream_.reset();
     if (bg_.th.joinable()) bg_.th.join();
-    if (bg_.stream) (void)hipStreamDestroy(S(bg_.stream));
-    for (int i = 0; i < 2; ++i) { if (bg_.pin[i]) (void)hipHostFree(bg_.pin[i]); if (bg_.ev[i]) (void)hipEventDestroy((hipEvent_t)bg_.ev[i]); }
-    for (StepBuffers *&sb : abi_sb_) { if (sb) free_step(sb); sb = nullptr; }
-    if (d_guard_) (void)hipFree(d_guard_);
-    if (q_stage_) (void)hipFree(q_stage_);
-    if (pair_dev_) (void)hipFree(pair_dev_);
-    if (d_rows_) (void)hipFree(d_rows_);
-    if (d_row_sn_) (void)hipFree(d_row_sn_);
-    if (d_queries_) (void)hipFree(d_queries_);
-    if (d_q_sn_) (void)hipFree(d_q_sn_);
 #ifdef EXP_PHASE_CLOCKS
     phase_report("teardown");
 #endif
-    for (void *p : {(void *)g_adj0_, (void *)g_level_, (void *)g_upper_, (void *)g_pool_, (void *)g_tested0_, (void *)g_testedU_, (void *)s_visited_, (void *)s_jobs_,
-                    (void *)s_hits_, (void *)s_cnt_, (void *)s_flag_, (void *)s_jobctr_, (void *)s_vistab_, (void *)s_fvistab_, (void *)lp_slot_[0], (void *)lp_slot_[1], (void *)lp_slot_[2], (void *)lp_grp_[0], (void *)lp_grp_[1], (void *)lp_grp_[2], (void *)lp_grp_[3], (void *)lp_grp_[4], (void *)lp_grp_[5], (void *)lp_counters_, (void *)s_evals_, (void *)s_sel_, (void *)s_lcnt_, (void *)s_selU_, (void *)s_cntU_, (void *)s_iflag_, (void *)s_lk_[0], (void *)s_lk_[1], (void *)s_lk_[2], (void *)s_lk_[3], (void *)s_lk_[4], (void *)s_spill_, (void *)s_fspill_, (void *)s_allow_, (void *)s_order_, (void *)s_rlog_, (void *)s_dry_, (void *)s_wdry_, (void *)s_win_, (void *)s_arena_, (void *)s_roff_, (void *)s_arena_used_, (void *)s_rentry_, (void *)s_rlists_, (void *)s_rl_, (void *)s_rstate_, (void *)s_rtied_, (void *)s_rfin_ctr_, (void *)s_rres_, (void *)s_rdst_, (void *)s_rpack_, (void *)x_ids_, (void *)x_boff_, (void *)x_lists_, (void *)x_out_, (void *)x_evals_, (void *)x_queries_, (void *)x_q_sn_})
-        if (p) (void)hipFree(p);
-    if (ev0_) (void)hipEventDestroy((hipEvent_t)ev0_);
-    if (ev1_) (void)hipEventDestroy((hipEvent_t)ev1_);
-    if (ev2_) (void)hipEventDestroy((hipEvent_t)ev2_);
-    if (h_stage_) (void)hipHostFree(h_stage_);
-    if (h_res_) (void)hipHostFree(h_res_);
-    if (h_range_) (void)hipHostFree(h_range_);
-    for (LinkSet &ls : lset_) {
-        if (ls.h_in) (void)hipHostFree(ls.h_in);
-        if (ls.h_out) (void)hipHostFree(ls.h_out);
-        if (ls.h_ev) (void)hipHostFree(ls.h_ev);
-        for (void *e : {ls.ev_start, ls.ev_stop, ls.ev_done}) if (e) (void)hipEventDestroy((hipEvent_t)e);
-    }
+    for (StepBuffers *&sb : abi_sb_) { if (sb) free_step(sb); sb = nullptr; }
     delete hg_;
 }
 
@@ -337,19 +339,16 @@ bool Device::reserve(long long capacity)
 {
     if (capacity <= capacity_) return true;
     if (!bind()) return false;
-    float *nr = nullptr;
-    double *nsn = nullptr;
-    HIP_OK(hipMalloc(&nr, (size_t)capacity * row_pitch_ * sizeof(float)));
-    if (metric_ == M_COS) HIP_OK(hipMalloc(&nsn, (size_t)capacity * sizeof(double)));
+    DevBuf<float> nr;
+    DevBuf<double> nsn;
+    if (!nr.grow((size_t)capacity * row_pitch_) || (metric_ == M_COS && !nsn.grow((size_t)capacity))) return false;
     if (d_rows_) {
         HIP_OK(hipMemcpyAsync(nr, d_rows_, (size_t)capacity_ * row_pitch_ * sizeof(float), hipMemcpyDeviceToDevice, S(stream_)));
         if (nsn) HIP_OK(hipMemcpyAsync(nsn, d_row_sn_, (size_t)capacity_ * sizeof(double), hipMemcpyDeviceToDevice, S(stream_)));
         HIP_OK(hipStreamSynchronize(S(stream_)));
-        HIP_OK(hipFree(d_rows_));
-        if (d_row_sn_) HIP_OK(hipFree(d_row_sn_));
     }
-    d_rows_ = nr;
-    d_row_sn_ = nsn;
+    d_rows_ = std::move(nr); // (the old blocks go here)
+    d_row_sn_ = std::move(nsn);
     capacity_ = capacity;
     return true;
 }
@@ -368,7 +367,7 @@ bool Device::upload_rows(int first_id, int n, const float *rows)
         const size_t chunk_rows = std::max<size_t>(1, (64u << 20) / row_bytes);
         char *hs = static_cast<char *>(pinned_stage(std::min<size_t>((size_t)n, chunk_rows) * row_bytes));
         if (!hs) return false;
-        if ((metric_ == M_I8 || metric_f16(metric_)) && !grow_dev(&q_stage_, &q_stage_cap_, std::min<size_t>((size_t)n, chunk_rows) * (size_t)dim_)) return false;
+        if ((metric_ == M_I8 || metric_f16(metric_)) && !q_stage_.grow(std::min<size_t>((size_t)n, chunk_rows) * (size_t)dim_)) return false;
         for (size_t r0 = 0; r0 < (size_t)n; r0 += chunk_rows) {
             const size_t nr = std::min(chunk_rows, (size_t)n - r0);
             memcpy(hs, rows + r0 * dim_, nr * row_bytes);
@@ -423,21 +422,9 @@ bool Device::upload_rows_begin(int first_id, int n, const float *rows)
     if (!bind()) return false;
     const size_t row_bytes = (size_t)dim_ * sizeof(float);
     const size_t chunk_rows = std::max<size_t>(1, (8u << 20) / row_bytes);
-    if (!bg_.stream) {
-        hipStream_t st;
-        HIP_OK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-        bg_.stream = st;
-        for (int i = 0; i < 2; ++i) { hipEvent_t e; HIP_OK(hipEventCreateWithFlags(&e, hipEventDisableTiming)); bg_.ev[i] = e; }
-    }
+    if (!bg_.stream.create(false) || !bg_.ev[0].create(false) || !bg_.ev[1].create(false)) return false;
     const size_t pin_need = chunk_rows * std::max(row_bytes, (size_t)row_pitch_ * sizeof(float)); // (a half-precision record of a short row is longer than the row)
-    if (bg_.pin_bytes < pin_need) {
-        for (int i = 0; i < 2; ++i) {
-            if (bg_.pin[i]) (void)hipHostFree(bg_.pin[i]);
-            bg_.pin[i] = nullptr;
-            HIP_OK(hipHostMalloc(&bg_.pin[i], pin_need, hipHostMallocDefault));
-        }
-        bg_.pin_bytes = pin_need;
-    }
+    if (!bg_.pin[0].grow(pin_need) || !bg_.pin[1].grow(pin_need)) return false;
     bg_.resident.store(first_id);
     bg_.failed.store(false);
     bg_.active.store(true);
@@ -455,25 +442,25 @@ bool Device::upload_rows_begin(int first_id, int n, const float *rows)
         for (size_t r0 = 0; r0 < (size_t)n; r0 += chunk_rows, b ^= 1) {
             const size_t nr = std::min(chunk_rows, (size_t)n - r0);
             if (in_flight[b]) { // this pinned buffer's previous copy must have left it
-                if ((e = hipEventSynchronize((hipEvent_t)bg_.ev[b])) != hipSuccess) { fail("hipEventSynchronize", e); return; }
+                if ((e = hipEventSynchronize(E(bg_.ev[b]))) != hipSuccess) { fail("hipEventSynchronize", e); return; }
                 landed += (long long)pending_rows[b];
                 bg_.resident.store(landed, std::memory_order_release);
                 in_flight[b] = false;
             }
-            if (f16) pack_f16_rows_host(static_cast<unsigned *>(bg_.pin[b]), rows + r0 * dim_, nr, dim_);
+            if (f16) pack_f16_rows_host(reinterpret_cast<unsigned *>(bg_.pin[b].get()), rows + r0 * dim_, nr, dim_);
             else memcpy(bg_.pin[b], rows + r0 * dim_, nr * row_bytes);
             if ((e = hipMemcpyAsync(d_rows_ + ((size_t)first_id + r0) * row_pitch_, bg_.pin[b], f16 ? nr * (size_t)row_pitch_ * sizeof(float) : nr * row_bytes, hipMemcpyHostToDevice, st)) != hipSuccess) { fail("hipMemcpyAsync", e); return; }
             if (metric_ == M_COS) {
                 const int blocks = (int)(((long long)nr * 8 + 255) / 256);
                 hipLaunchKernelGGL(row_sqrtnorm_kernel, dim3(blocks), dim3(256), 0, st, d_rows_, pitch_, (long long)first_id + (long long)r0, (int)nr, d_row_sn_);
             }
-            if ((e = hipEventRecord((hipEvent_t)bg_.ev[b], st)) != hipSuccess) { fail("hipEventRecord", e); return; }
+            if ((e = hipEventRecord(E(bg_.ev[b]), st)) != hipSuccess) { fail("hipEventRecord", e); return; }
             pending_rows[b] = nr;
             in_flight[b] = true;
         }
         for (int k = 0; k < 2; ++k, b ^= 1) // the two copies still in flight, oldest first
             if (in_flight[b]) {
-                if ((e = hipEventSynchronize((hipEvent_t)bg_.ev[b])) != hipSuccess) { fail("hipEventSynchronize", e); return; }
+                if ((e = hipEventSynchronize(E(bg_.ev[b]))) != hipSuccess) { fail("hipEventSynchronize", e); return; }
                 landed += (long long)pending_rows[b];
                 bg_.resident.store(landed, std::memory_order_release);
             }
@@ -503,7 +490,7 @@ bool Device::download_rows(int first_id, int n, float *rows)
     }
     if (!bind()) return false;
     if (metric_ == M_I8) { // the dequantised rows q_i * scale
-        if (!grow_dev(&q_stage_, &q_stage_cap_, (size_t)n * (size_t)dim_)) return false;
+        if (!q_stage_.grow((size_t)n * (size_t)dim_)) return false;
         hipLaunchKernelGGL(dequantize_rows_kernel, dim3((unsigned)(((long long)n * dim_ + 255) / 256)), dim3(256), 0, S(stream_), d_rows_, pitch_,
                            (long long)first_id, n, dim_, q_stage_);
         HIP_OK(hipGetLastError());
@@ -511,7 +498,7 @@ bool Device::download_rows(int first_id, int n, float *rows)
     } else if (metric_f16(metric_)) { // the stored rows widened to float: h(x), 64 MiB of floats at a time (Serialize downloads the whole
         // index: a staging area of the whole f32 matrix would undo the halving)
         const size_t chunk_rows = std::max<size_t>(1, (64u << 20) / ((size_t)dim_ * sizeof(float)));
-        if (!grow_dev(&q_stage_, &q_stage_cap_, std::min<size_t>((size_t)n, chunk_rows) * (size_t)dim_)) return false;
+        if (!q_stage_.grow(std::min<size_t>((size_t)n, chunk_rows) * (size_t)dim_)) return false;
         for (size_t r0 = 0; r0 < (size_t)n; r0 += chunk_rows) {
             const size_t nr = std::min(chunk_rows, (size_t)n - r0);
             hipLaunchKernelGGL(unpack_f16_rows_kernel, dim3((unsigned)((nr * (size_t)dim_ + 255) / 256)), dim3(256), 0, S(stream_), d_rows_,
@@ -537,8 +524,7 @@ bool Device::staged_upload(float *dst, const float *src, size_t bytes)
     constexpr int T = 4;
     constexpr size_t kChunk = 2u << 20;
     for (int i = 0; i < 2 * T; ++i) {
-        if (!up_pin_[i]) HIP_OK(hipHostMalloc(&up_pin_[i], kChunk, hipHostMallocDefault));
-        if (!up_ev_[i]) { hipEvent_t e; HIP_OK(hipEventCreateWithFlags(&e, hipEventDisableTiming)); up_ev_[i] = e; }
+        if (!up_pin_[i].grow(kChunk) || !up_ev_[i].create(false)) return false;
     }
     std::atomic<int> failed{0};
     const size_t slice = (((bytes + T - 1) / T) + 255) & ~(size_t)255;
@@ -549,10 +535,10 @@ bool Device::staged_upload(float *dst, const float *src, size_t bytes)
         for (size_t off = lo; off < hi; off += kChunk, b ^= 1) {
             const int slot = 2 * t + b;
             const size_t nb = std::min(kChunk, hi - off);
-            if (up_busy_[slot] && hipEventSynchronize((hipEvent_t)up_ev_[slot]) != hipSuccess) { failed.store(1); return; }
+            if (up_busy_[slot] && hipEventSynchronize(E(up_ev_[slot])) != hipSuccess) { failed.store(1); return; }
             memcpy(up_pin_[slot], reinterpret_cast<const char *>(src) + off, nb);
             if (hipMemcpyAsync(reinterpret_cast<char *>(dst) + off, up_pin_[slot], nb, hipMemcpyHostToDevice, S(stream_)) != hipSuccess ||
-                hipEventRecord((hipEvent_t)up_ev_[slot], S(stream_)) != hipSuccess) { failed.store(1); return; }
+                hipEventRecord(E(up_ev_[slot]), S(stream_)) != hipSuccess) { failed.store(1); return; }
             up_busy_[slot] = true;
         }
     };
@@ -568,14 +554,14 @@ bool Device::set_queries(const float *queries, int nq)
 {
     if (nq < 0 || (nq > 0 && !queries)) { set_dev_error("set_queries: bad argument"); return false; }
     if (!bind()) return false;
-    if (nq > q_capacity_) {
-        if (d_queries_) HIP_OK(hipFree(d_queries_));
-        if (d_q_sn_) HIP_OK(hipFree(d_q_sn_));
-        d_queries_ = nullptr; d_q_sn_ = nullptr;
-        long long cap = std::max<long long>(nq, 1024);
-        HIP_OK(hipMalloc(&d_queries_, (size_t)cap * pitch_ * sizeof(float)));
-        if (metric_ == M_COS) HIP_OK(hipMalloc(&d_q_sn_, (size_t)cap * sizeof(double)));
-        q_capacity_ = cap;
+    if (nq > q_capacity()) { // (nothing is kept: the old set goes first; the new one becomes the member once it is whole)
+        if (!reset_all(d_queries_, d_q_sn_)) return false;
+        const size_t cap = (size_t)std::max<long long>(nq, 1024);
+        DevBuf<float> nqbuf;
+        DevBuf<double> nsn;
+        if (!nqbuf.grow(cap * pitch_) || (metric_ == M_COS && !nsn.grow(cap))) return false;
+        d_queries_ = std::move(nqbuf);
+        d_q_sn_ = std::move(nsn);
     }
     n_queries_ = nq;
     if (nq == 0) return true;
@@ -584,7 +570,7 @@ bool Device::set_queries(const float *queries, int nq)
         void *hs = bytes < (4u << 20) ? pinned_stage(bytes) : nullptr;
         float *dst = d_queries_;
         if (metric_ == M_I8) { // floats to the staging area, quantised into the resident records
-            if (!grow_dev(&q_stage_, &q_stage_cap_, (size_t)nq * (size_t)dim_)) return false;
+            if (!q_stage_.grow((size_t)nq * (size_t)dim_)) return false;
             dst = q_stage_;
         }
         if (bytes >= (4u << 20)) { if (!staged_upload(dst, queries, bytes)) return false; }
@@ -649,32 +635,25 @@ bool Device::set_queries_streamed(const float *queries, int nq, int head)
     head = std::min(nq, (head + 31) & ~31);
     if (head >= nq) return set_queries(queries, nq);
     if (!bind()) return false;
-    if (!h_ready_) {
-        HIP_OK(hipHostMalloc((void **)&h_ready_, 64, hipHostMallocMapped | hipHostMallocCoherent));
+    if (!copy_stream_) {
+        if (!h_ready_) {
+            h_ready_ = PinBuf<int>(kPinMappedCoherent);
+            if (!h_ready_.grow(16)) return false;
+        }
         HIP_OK(hipHostGetDevicePointer((void **)&d_ready_, h_ready_, 0));
-        // The copies a gated kernel waits for must never queue behind that kernel.  HIP multiplexes streams onto a few
-        // hardware queues, and a copy stream that lands on the queue of a compute stream does exactly that (measured: two
-        // lanes, every wave slept its full bound).  High-priority streams have hardware queues of their own, and only
-        // copy streams are created with that priority here.
-        int lo = 0, hi = 0;
-        HIP_OK(hipDeviceGetStreamPriorityRange(&lo, &hi));
-        hipStream_t cs;
-        HIP_OK(hipStreamCreateWithPriority(&cs, hipStreamNonBlocking, hi));
-        copy_stream_ = cs;
+        if (!copy_stream_.create(true)) return false; // (high priority: only copy streams are, dev_stream_create)
     }
     if (!set_queries(queries, head)) return false; // allocates for `head` rows at least ...
-    if (nq > q_capacity_) {                         // ... and for the whole set, keeping the head
-        float *nqbuf = nullptr;
+    if (nq > q_capacity()) {                        // ... and for the whole set, keeping the head
+        DevBuf<float> nqbuf;
         const long long cap = std::max<long long>(nq, 1024);
-        HIP_OK(hipMalloc(&nqbuf, (size_t)cap * pitch_ * sizeof(float)));
+        if (!nqbuf.grow((size_t)cap * pitch_)) return false;
         HIP_OK(hipMemcpyAsync(nqbuf, d_queries_, (size_t)head * pitch_ * sizeof(float), hipMemcpyDeviceToDevice, S(stream_)));
         HIP_OK(hipStreamSynchronize(S(stream_)));
-        HIP_OK(hipFree(d_queries_));
-        d_queries_ = nqbuf;
-        q_capacity_ = cap;
+        d_queries_ = std::move(nqbuf);
     }
     n_queries_ = nq;
-    __atomic_store_n(h_ready_, head, __ATOMIC_RELEASE);
+    __atomic_store_n(h_ready_.get(), head, __ATOMIC_RELEASE);
     tail_.src = queries;
     tail_.first = head;
     tail_.n = nq - head;
@@ -689,8 +668,7 @@ bool Device::upload_tail()
     if (n <= 0) return true;
     constexpr size_t kChunk = 2u << 20;
     for (int i = 0; i < 2; ++i) {
-        if (!up_pin_[i]) HIP_OK(hipHostMalloc(&up_pin_[i], kChunk, hipHostMallocDefault));
-        if (!up_ev_[i]) { hipEvent_t e; HIP_OK(hipEventCreateWithFlags(&e, hipEventDisableTiming)); up_ev_[i] = e; }
+        if (!up_pin_[i].grow(kChunk) || !up_ev_[i].create(false)) return false;
     }
     const size_t row_bytes = (size_t)dim_ * sizeof(float);
     const long long rows_per_chunk = std::max<long long>(32, (long long)(kChunk / row_bytes) & ~31LL); // whole 128-B lines
@@ -703,7 +681,7 @@ bool Device::upload_tail()
             const long long r = std::min(rows_per_chunk, n - sent);
             memcpy(up_pin_[b], src + (size_t)(first + sent) * dim_, (size_t)r * row_bytes);
             HIP_OK(hipMemcpyAsync(d_queries_ + (size_t)(first + sent) * pitch_, up_pin_[b], (size_t)r * row_bytes, hipMemcpyHostToDevice, cs));
-            HIP_OK(hipEventRecord((hipEvent_t)up_ev_[b], cs));
+            HIP_OK(hipEventRecord(E(up_ev_[b]), cs));
             in_slot[b] = r;
             sent += r;
             b ^= 1;
@@ -711,11 +689,11 @@ bool Device::upload_tail()
         }
         // the older of the two copies in flight
         const int o = in_slot[b] != 0 ? b : b ^ 1;
-        HIP_OK(hipEventSynchronize((hipEvent_t)up_ev_[o]));
+        HIP_OK(hipEventSynchronize(E(up_ev_[o])));
         confirmed += in_slot[o];
         in_slot[o] = 0;
         b = o;
-        __atomic_store_n(h_ready_, (int)(first + confirmed), __ATOMIC_RELEASE);
+        __atomic_store_n(h_ready_.get(), (int)(first + confirmed), __ATOMIC_RELEASE);
     }
     up_busy_[0] = up_busy_[1] = false;
     return true;
@@ -753,7 +731,7 @@ static bool peer_direct(int dst, int src)
 bool Device::clone_from(Device *src, long long pool_len)
 {
     if (!src || src == this || src->dim_ != dim_ || src->metric_ != metric_ || src->pitch_ != pitch_ || src->row_pitch_ != row_pitch_) { set_dev_error("clone_from: contexts differ in shape"); return false; }
-    if (pool_len < 0 || pool_len > src->g_pool_cap_) { set_dev_error("clone_from: bad pool length"); return false; }
+    if (pool_len < 0 || pool_len > src->g_pool_cap()) { set_dev_error("clone_from: bad pool length"); return false; }
     if (!src->sync()) return false; // what is copied must have landed
     if (!reserve(src->capacity_)) return false;
     const bool direct = peer_direct(device_, src->device_);
@@ -766,25 +744,7 @@ bool Device::clone_from(Device *src, long long pool_len)
         if (metric_ == M_COS) HIP_OK(hipMemcpyPeerAsync(d_row_sn_ + have, device_, src->d_row_sn_ + have, src->device_, (size_t)more * sizeof(double), st));
     }
     const long long n = src->g_n_;
-    if (n > g_cap_n_ || src->g_stride0_ != g_stride0_) {
-        for (void *p : {(void *)g_adj0_, (void *)g_level_, (void *)g_upper_, (void *)g_tested0_}) if (p) HIP_OK(hipFree(p));
-        g_adj0_ = nullptr; g_level_ = nullptr; g_upper_ = nullptr; g_tested0_ = nullptr;
-        const long long cap = std::max<long long>(src->g_cap_n_, std::max<long long>(n, 1024));
-        HIP_OK(hipMalloc(&g_adj0_, sizeof(int) * (size_t)cap * src->g_stride0_));
-        HIP_OK(hipMalloc(&g_level_, sizeof(int) * (size_t)cap));
-        HIP_OK(hipMalloc(&g_upper_, sizeof(int64_t) * (size_t)cap));
-        HIP_OK(hipMalloc(&g_tested0_, sizeof(int) * (size_t)cap));
-        g_cap_n_ = cap;
-    }
-    if (pool_len > g_pool_cap_) {
-        if (g_pool_) HIP_OK(hipFree(g_pool_));
-        if (g_testedU_) HIP_OK(hipFree(g_testedU_));
-        g_pool_ = nullptr; g_testedU_ = nullptr;
-        const long long cap = std::max<long long>(pool_len * 2, 4096);
-        HIP_OK(hipMalloc(&g_pool_, sizeof(int) * (size_t)cap));
-        HIP_OK(hipMalloc(&g_testedU_, sizeof(int) * (size_t)cap));
-        g_pool_cap_ = cap;
-    }
+    if (!graph_room(n, std::max<long long>(src->g_cap_n(), std::max<long long>(n, 1024)), src->g_stride0_, pool_len)) return false;
     g_n_ = n; g_stride0_ = src->g_stride0_; g_strideU_ = src->g_strideU_;
     if (n > 0) {
         HIP_OK(hipMemcpyPeerAsync(g_adj0_, device_, src->g_adj0_, src->device_, sizeof(int) * (size_t)n * g_stride0_, st));
@@ -793,8 +753,8 @@ bool Device::clone_from(Device *src, long long pool_len)
     }
     if (pool_len > 0) HIP_OK(hipMemcpyPeerAsync(g_pool_, device_, src->g_pool_, src->device_, sizeof(int) * (size_t)pool_len, st));
     // a replica only answers queries: the link kernel's pruning history is not carried over
-    if (g_tested0_) HIP_OK(hipMemsetAsync(g_tested0_, 0, sizeof(int) * (size_t)g_cap_n_, st));
-    if (g_testedU_) HIP_OK(hipMemsetAsync(g_testedU_, 0, sizeof(int) * (size_t)g_pool_cap_, st));
+    if (g_tested0_) HIP_OK(hipMemsetAsync(g_tested0_, 0, sizeof(int) * g_tested0_.cap(), st));
+    if (g_testedU_) HIP_OK(hipMemsetAsync(g_testedU_, 0, sizeof(int) * g_testedU_.cap(), st));
     HIP_OK(hipStreamSynchronize(st));
     n_rows_hw_ = src->n_rows_hw_;
     stats_.replica_bytes += (uint64_t)more * row_pitch_ * sizeof(float) + sizeof(int) * ((uint64_t)n * g_stride0_ + (uint64_t)n * 3 + (uint64_t)pool_len);
@@ -812,20 +772,18 @@ bool Device::adopt_queries(Device *src, long long first, long long n, long long 
     (peer_direct(device_, src->device_) ? stats_.peer_direct_copies : stats_.peer_staged_copies) += 1;
     if (!bind()) return false;
     hipStream_t st = S(stream_);
-    if (total > q_capacity_) { // grow, keeping what is resident
-        float *nq = nullptr;
-        double *nsn = nullptr;
+    if (total > q_capacity()) { // grow, keeping what is resident
+        DevBuf<float> nq;
+        DevBuf<double> nsn;
         const long long cap = std::max<long long>(total, 1024);
-        HIP_OK(hipMalloc(&nq, (size_t)cap * pitch_ * sizeof(float)));
-        if (metric_ == M_COS) HIP_OK(hipMalloc(&nsn, (size_t)cap * sizeof(double)));
+        if (!nq.grow((size_t)cap * pitch_) || (metric_ == M_COS && !nsn.grow((size_t)cap))) return false;
         if (d_queries_ && n_queries_ > 0) {
             HIP_OK(hipMemcpyAsync(nq, d_queries_, (size_t)n_queries_ * pitch_ * sizeof(float), hipMemcpyDeviceToDevice, st));
             if (nsn) HIP_OK(hipMemcpyAsync(nsn, d_q_sn_, (size_t)n_queries_ * sizeof(double), hipMemcpyDeviceToDevice, st));
             HIP_OK(hipStreamSynchronize(st));
         }
-        if (d_queries_) HIP_OK(hipFree(d_queries_));
-        if (d_q_sn_) HIP_OK(hipFree(d_q_sn_));
-        d_queries_ = nq; d_q_sn_ = nsn; q_capacity_ = cap;
+        d_queries_ = std::move(nq);
+        d_q_sn_ = std::move(nsn);
     }
     if (n > 0 && src != this) {
         HIP_OK(hipMemcpyPeerAsync(d_queries_ + (size_t)at * pitch_, device_, src->d_queries_ + (size_t)first * pitch_, src->device_, (size_t)n * pitch_ * sizeof(float), st));
@@ -844,9 +802,9 @@ void Device::free_step(StepBuffers *sb)
     if (sb->dist) (void)hipHostFree(sb->dist - StepBuffers::kHeader);
     if (sb->d_rec) (void)hipFree(sb->d_rec);
     if (sb->d_dist) (void)hipFree(sb->d_dist);
-    if (sb->done) (void)hipEventDestroy((hipEvent_t)sb->done);
-    if (sb->t0) (void)hipEventDestroy((hipEvent_t)sb->t0);
-    if (sb->t1) (void)hipEventDestroy((hipEvent_t)sb->t1);
+    if (sb->done) (void)hipEventDestroy(E(sb->done));
+    if (sb->t0) (void)hipEventDestroy(E(sb->t0));
+    if (sb->t1) (void)hipEventDestroy(E(sb->t1));
     delete sb;
 }
 
@@ -859,7 +817,7 @@ bool Device::launch_step(StepBuffers *sb, int nslots_used, uint64_t evals)
     sb->timed = profiling_;
     sb->evals = evals;
     HIP_OK(hipMemcpyAsync(sb->d_rec, sb->rec, sizeof(int) * (size_t)nslots_used * sb->rec_stride, hipMemcpyHostToDevice, st));
-    if (sb->timed) HIP_OK(hipEventRecord((hipEvent_t)sb->t0, st));
+    if (sb->timed) HIP_OK(hipEventRecord(E(sb->t0), st));
     dim3 grid((nslots_used + 3) / 4), block(256);
     with_metric(metric_, [&](auto m) {
         hipLaunchKernelGGL(slot_distance_kernel<m>, grid, block, 0, st, d_rows_, d_row_sn_, d_queries_, d_q_sn_, pitch_, sb->d_rec,
@@ -867,11 +825,11 @@ bool Device::launch_step(StepBuffers *sb, int nslots_used, uint64_t evals)
                            reinterpret_cast<int *>(sb->d_dist));
     });
     HIP_OK(hipGetLastError());
-    if (sb->timed) HIP_OK(hipEventRecord((hipEvent_t)sb->t1, st));
+    if (sb->timed) HIP_OK(hipEventRecord(E(sb->t1), st));
     // guard word + distances of the used slots: one copy
     HIP_OK(hipMemcpyAsync(sb->dist - StepBuffers::kHeader, sb->d_dist, sizeof(float) * ((size_t)nslots_used * sb->stride + StepBuffers::kHeader),
                           hipMemcpyDeviceToHost, st));
-    HIP_OK(hipEventRecord((hipEvent_t)sb->done, st));
+    HIP_OK(hipEventRecord(E(sb->done), st));
     sb->in_flight = true;
     stats_.launches++;
     stats_.evals += evals;
@@ -881,11 +839,11 @@ bool Device::launch_step(StepBuffers *sb, int nslots_used, uint64_t evals)
 bool Device::wait_step(StepBuffers *sb)
 {
     if (!sb->in_flight) return true;
-    HIP_OK(hipEventSynchronize((hipEvent_t)sb->done));
+    HIP_OK(hipEventSynchronize(E(sb->done)));
     sb->in_flight = false;
     if (sb->timed) {
         float ms = 0.f;
-        HIP_OK(hipEventElapsedTime(&ms, (hipEvent_t)sb->t0, (hipEvent_t)sb->t1));
+        HIP_OK(hipEventElapsedTime(&ms, E(sb->t0), E(sb->t1)));
         stats_.kernel_ms += ms;
         stats_.timed_launches++;
         stats_.timed_evals += sb->evals;
@@ -962,6 +920,25 @@ void Device::reset_stats()
 
 
 // ---- graph mirror + graph-resident search -------------------------------------------------
+// Room in the mirror for n nodes of stride0 and pool_len pool ints.  The four node arrays are replaced together, node_cap nodes
+// each, when n outgrows them or the stride changes; the pool pair when pool_len outgrows it, doubled, 4096 ints at least.  (The
+// caller sets g_stride0_ afterwards: after a failure here the arrays are empty, and the next call allocates whatever the stride.)
+bool Device::graph_room(long long n, long long node_cap, int stride0, long long pool_len)
+{
+    if (n > g_cap_n() || stride0 != g_stride0_) {
+        if (!reset_all(g_adj0_, g_level_, g_upper_, g_tested0_)) return false;
+        if (!g_adj0_.grow((size_t)node_cap * stride0) || !g_level_.grow((size_t)node_cap) || !g_upper_.grow((size_t)node_cap) ||
+            !g_tested0_.grow((size_t)node_cap))
+            return false;
+    }
+    if (pool_len > g_pool_cap()) {
+        if (!reset_all(g_pool_, g_testedU_)) return false;
+        const size_t cap = (size_t)std::max<long long>(pool_len * 2, 4096);
+        if (!g_pool_.grow(cap) || !g_testedU_.grow(cap)) return false; // (g_testedU_ is indexed by list offset / strideU: never more than cap)
+    }
+    return true;
+}
+
 bool Device::set_graph(const int *adj0, long long n, int stride0, const int *level, const int64_t *upper, const int *pool,
                        long long pool_len, int strideU)
 {
@@ -969,28 +946,7 @@ bool Device::set_graph(const int *adj0, long long n, int stride0, const int *lev
     if (stride0 - 1 > 128 || strideU - 1 > 128) { set_dev_error("set_graph: MaxEdges > 63 is not supported by the graph-resident kernels (use hnsw_mi355x_set_device_traversal(0))"); return false; }
     if (!bind()) return false;
     hipStream_t st = S(stream_);
-    if (n > g_cap_n_ || stride0 != g_stride0_) {
-        if (g_adj0_) HIP_OK(hipFree(g_adj0_));
-        if (g_level_) HIP_OK(hipFree(g_level_));
-        if (g_upper_) HIP_OK(hipFree(g_upper_));
-        if (g_tested0_) HIP_OK(hipFree(g_tested0_));
-        g_adj0_ = nullptr; g_level_ = nullptr; g_upper_ = nullptr; g_tested0_ = nullptr;
-        long long cap = std::max<long long>(n, std::max<long long>(capacity_, 1024));
-        HIP_OK(hipMalloc(&g_adj0_, sizeof(int) * (size_t)cap * stride0));
-        HIP_OK(hipMalloc(&g_level_, sizeof(int) * (size_t)cap));
-        HIP_OK(hipMalloc(&g_upper_, sizeof(int64_t) * (size_t)cap));
-        HIP_OK(hipMalloc(&g_tested0_, sizeof(int) * (size_t)cap));
-        g_cap_n_ = cap;
-    }
-    if (pool_len > g_pool_cap_) {
-        if (g_pool_) HIP_OK(hipFree(g_pool_));
-        if (g_testedU_) HIP_OK(hipFree(g_testedU_));
-        g_pool_ = nullptr; g_testedU_ = nullptr;
-        long long cap = std::max<long long>(pool_len * 2, 4096);
-        HIP_OK(hipMalloc(&g_pool_, sizeof(int) * (size_t)cap));
-        HIP_OK(hipMalloc(&g_testedU_, sizeof(int) * (size_t)cap)); // indexed by list offset / strideU: never more than cap
-        g_pool_cap_ = cap;
-    }
+    if (!graph_room(n, std::max<long long>(n, std::max<long long>(capacity_, 1024)), stride0, pool_len)) return false;
     g_n_ = n; g_stride0_ = stride0; g_strideU_ = strideU;
     if (n > 0) {
         HIP_OK(hipMemcpyAsync(g_adj0_, adj0, sizeof(int) * (size_t)n * stride0, hipMemcpyHostToDevice, st));
@@ -999,8 +955,8 @@ bool Device::set_graph(const int *adj0, long long n, int stride0, const int *lev
     }
     if (pool_len > 0) HIP_OK(hipMemcpyAsync(g_pool_, pool, sizeof(int) * (size_t)pool_len, hipMemcpyHostToDevice, st));
     // lists that arrive from the host carry no pruning history
-    if (g_tested0_) HIP_OK(hipMemsetAsync(g_tested0_, 0, sizeof(int) * (size_t)g_cap_n_, st));
-    if (g_testedU_) HIP_OK(hipMemsetAsync(g_testedU_, 0, sizeof(int) * (size_t)g_pool_cap_, st));
+    if (g_tested0_) HIP_OK(hipMemsetAsync(g_tested0_, 0, sizeof(int) * g_tested0_.cap(), st));
+    if (g_testedU_) HIP_OK(hipMemsetAsync(g_testedU_, 0, sizeof(int) * g_testedU_.cap(), st));
     HIP_OK(hipStreamSynchronize(st)); // host arrays are borrowed only for this call
     return true;
 }
@@ -1139,16 +1095,12 @@ bool Device::visited_scratch(int k, int min_cap, bool allow_hash, VisitedScratch
     // a traversal step inserts up to min_cap / 4 ids between two looks at crowded() (limit: 3/4 of the table)
     while (cap < min_cap) cap <<= 1;
     const size_t need = (size_t)max_slots() * (size_t)cap;
-    int *&tab = filtered ? s_fvistab_ : s_vistab_;
-    size_t &tab_cap = filtered ? s_fvistab_cap_ : s_vistab_cap_;
+    DevBuf<int> &tab = filtered ? s_fvistab_ : s_vistab_;
     int &tab_each = filtered ? s_fvistab_each_ : s_vistab_each_;
-    if (need > tab_cap || cap != tab_each) {
+    if (need > tab.cap() || cap != tab_each) { // (another capacity per wave: a new table even where the total fits)
         HIP_OK(hipStreamSynchronize(S(stream_)));
-        if (tab) HIP_OK(hipFree(tab));
-        tab = nullptr; tab_cap = 0;
-        HIP_OK(hipMalloc(&tab, sizeof(int) * need));
+        if (!tab.reset() || !tab.grow(need)) return false;
         HIP_OK(hipMemsetAsync(tab, 0xff, sizeof(int) * need, S(stream_)));
-        tab_cap = need;
         tab_each = cap;
     }
     v->tab = tab;
@@ -1282,34 +1234,23 @@ static auto place_traversal(TraversalLaunch &t, int nj)
 // and every wave clears its bitset after each job.
 bool Device::ensure_search_scratch(long long chunk, long long slots, int k, size_t vis_bytes_per_job)
 {
-    if (vis_bytes_per_job * (size_t)slots > s_visited_bytes_) {
-        if (s_visited_) HIP_OK(hipFree(s_visited_));
-        s_visited_ = nullptr;
-        s_visited_bytes_ = vis_bytes_per_job * (size_t)slots;
-        HIP_OK(hipMalloc(&s_visited_, s_visited_bytes_));
-        HIP_OK(hipMemsetAsync(s_visited_, 0, s_visited_bytes_, S(stream_)));
+    const size_t vis_words = vis_bytes_per_job * (size_t)slots / sizeof(unsigned); // (bytes_per_job is whole words)
+    if (vis_words > s_visited_.cap()) {
+        if (!s_visited_.grow(vis_words)) return false;
+        HIP_OK(hipMemsetAsync(s_visited_, 0, sizeof(unsigned) * vis_words, S(stream_)));
     }
-    if (!s_jobctr_ || (size_t)chunk > s_jobs_cap_) { // [next job, next shadow, -, -, one word per job] (graph_search_kernel)
-        if (s_jobctr_) HIP_OK(hipFree(s_jobctr_));
-        s_jobctr_ = nullptr;
-        HIP_OK(hipMalloc(&s_jobctr_, sizeof(int) * (4 + std::max<size_t>((size_t)chunk, s_jobs_cap_))));
-    }
-    if ((size_t)chunk > s_jobs_cap_) {
-        if (s_jobs_) HIP_OK(hipFree(s_jobs_));
+    const size_t jobs_cap = s_flag_.cap();
+    // [next job, next shadow, -, -, one word per job] (graph_search_kernel): as many words as s_jobs_ has jobs, so it grows when s_jobs_ does
+    if (!s_jobctr_.grow(4 + std::max<size_t>((size_t)chunk, jobs_cap))) return false;
+    if ((size_t)chunk > jobs_cap) {
         uj_len_ = 0;
-        if (s_cnt_) HIP_OK(hipFree(s_cnt_));
-        if (s_flag_) HIP_OK(hipFree(s_flag_));
-        s_jobs_cap_ = (size_t)chunk;
-        HIP_OK(hipMalloc(&s_jobs_, sizeof(SearchJob) * s_jobs_cap_));
-        HIP_OK(hipMalloc(&s_cnt_, sizeof(int) * s_jobs_cap_));
-        HIP_OK(hipMalloc(&s_flag_, sizeof(int) * s_jobs_cap_));
+        if (!reset_all(s_jobs_, s_cnt_, s_flag_)) return false;
+        if (!s_jobs_.grow((size_t)chunk) || !s_cnt_.grow((size_t)chunk) || !s_flag_.grow((size_t)chunk)) return false;
     }
-    if (k > 0 && !grow_dev(&s_hits_, &s_hits_cap_, (size_t)chunk * k + ((size_t)chunk + 1) / 2)) return false; // ids, distances, and (single-launch calls) the flags behind them
-    if (!grow_dev(&s_spill_, &s_spill_cap_, (size_t)slots * kSpillCap + 8)) return false; // +8: get2 may read one entry past a heap
-    if (!s_evals_) HIP_OK(hipMalloc(&s_evals_, sizeof(unsigned long long)));
-    if (!ev0_) { hipEvent_t a, b; HIP_OK(hipEventCreate(&a)); HIP_OK(hipEventCreate(&b)); ev0_ = a; ev1_ = b; }
-    if (!ev2_) { hipEvent_t c; HIP_OK(hipEventCreateWithFlags(&c, hipEventDisableTiming)); ev2_ = c; }
-    return true;
+    if (k > 0 && !s_hits_.grow((size_t)chunk * k + ((size_t)chunk + 1) / 2)) return false; // ids, distances, and (single-launch calls) the flags behind them
+    if (!s_spill_.grow((size_t)slots * kSpillCap + 8)) return false; // +8: get2 may read one entry past a heap
+    if (!s_evals_.grow(1)) return false;
+    return ev0_.create(true) && ev1_.create(true) && ev2_.create(false);
 }
 
 static bool jobs_valid(const SearchJob *jobs, int njobs, long long g_n, long long n_queries, long long n_rows)
@@ -1349,36 +1290,29 @@ bool Device::insert_search_batch(const SearchJob *jobs, int njobs, int k, int ma
     if (!plan_traversal(true, k, false, lds, &tl)) return false;
     if (!ensure_search_scratch(chunk, max_slots(), 0, tl.vis.bytes_per_job)) return false;
     const size_t nU = (size_t)std::max(n_upper, 1);
-    if (!grow_dev(&s_sel_, &s_sel_cap_, (size_t)njobs * sel_stride) || !grow_dev(&s_lcnt_, &s_lcnt_cap_, (size_t)njobs) ||
-        !grow_dev(&s_selU_, &s_selU_cap_, nU * sel_stride) || !grow_dev(&s_cntU_, &s_cntU_cap_, nU) ||
-        !grow_dev(&s_iflag_, &s_iflag_cap_, (size_t)njobs))
+    if (!s_sel_.grow((size_t)njobs * sel_stride) || !s_lcnt_.grow((size_t)njobs) || !s_selU_.grow(nU * sel_stride) || !s_cntU_.grow(nU) || !s_iflag_.grow((size_t)njobs))
         return false;
-    if (windowed && !grow_dev(&s_rlog_, &s_rlog_cap_, (size_t)njobs * (size_t)read_log_cap)) return false;
+    if (windowed && !s_rlog_.grow((size_t)njobs * (size_t)read_log_cap)) return false;
     // pinned results: [sel0 | cnt0 | selU | cntU | flag | evals | read logs | dry0 | dryU]
     const size_t b_sel0 = 4u * (size_t)njobs * sel_stride, b_cnt0 = 4u * (size_t)njobs, b_selU = 4u * nU * sel_stride, b_cntU = 4u * nU, b_flag = 4u * (size_t)njobs;
     const size_t b_log = windowed ? 4u * (size_t)njobs * (size_t)read_log_cap : 0;
     const size_t b_dry = windowed ? b_sel0 + b_selU : 0;
     const size_t b_drop = windowed ? 3u * b_sel0 : 0;          // three ids per layer-0 selection entry
     const size_t b_rep = windowed ? b_flag : 0;                // the jobs' "repeated" flags (the job flags themselves are folded to 0 / 1 below)
-    if (windowed && !grow_dev(&s_wdry_, &s_wdry_cap_, nU)) return false; // (upper_owner)
+    if (windowed && !s_wdry_.grow(nU)) return false; // (upper_owner)
     const size_t need = b_sel0 + b_cnt0 + b_selU + b_cntU + b_flag + 16 + b_log + b_dry + b_drop + b_rep;
     // windowed: everything the kernels write lives in ONE device block laid out like the pinned results below, so that it comes
     // back in one copy (a round of the exact window is ~2 ms: a dozen 4-microsecond copies and their launch overhead showed)
-    if (windowed && !grow_dev(&s_win_, &s_win_cap_, (need - b_rep + 3) / 4u + 64)) return false;
-    if (need > h_res_cap_) {
-        if (h_res_) (void)hipHostFree(h_res_);
-        h_res_ = nullptr; h_res_cap_ = 0;
-        if (hipHostMalloc(&h_res_, need + need / 2, hipHostMallocDefault) != hipSuccess) { set_dev_error("insert_search_batch: pinned allocation failed"); return false; }
-        h_res_cap_ = need + need / 2;
-    }
-    char *hb = static_cast<char *>(h_res_);
+    if (windowed && !s_win_.grow((need - b_rep + 3) / 4u + 64)) return false;
+    if (!h_res_.grow(need, need + need / 2)) return false;
+    char *hb = h_res_;
     int *h_sel0 = reinterpret_cast<int *>(hb), *h_cnt0 = reinterpret_cast<int *>(hb + b_sel0);
     int *h_selU = reinterpret_cast<int *>(hb + b_sel0 + b_cnt0), *h_cntU = reinterpret_cast<int *>(hb + b_sel0 + b_cnt0 + b_selU);
     int *h_flag = reinterpret_cast<int *>(hb + b_sel0 + b_cnt0 + b_selU + b_cntU);
     unsigned long long *h_ev = reinterpret_cast<unsigned long long *>(hb + ((b_sel0 + b_cnt0 + b_selU + b_cntU + b_flag + 7) & ~(size_t)7));
     int *h_log = reinterpret_cast<int *>(reinterpret_cast<char *>(h_ev) + 8);
     // where the kernels write: the members, or (windowed) the same offsets inside s_win_
-    char *db = reinterpret_cast<char *>(s_win_);
+    char *db = reinterpret_cast<char *>(s_win_.get());
     int *p_sel0 = windowed ? reinterpret_cast<int *>(db) : s_sel_, *p_cnt0 = windowed ? reinterpret_cast<int *>(db + b_sel0) : s_lcnt_;
     int *p_selU = windowed ? reinterpret_cast<int *>(db + b_sel0 + b_cnt0) : s_selU_, *p_cntU = windowed ? reinterpret_cast<int *>(db + b_sel0 + b_cnt0 + b_selU) : s_cntU_;
     int *p_flag = windowed ? reinterpret_cast<int *>(db + b_sel0 + b_cnt0 + b_selU + b_cntU) : s_iflag_;
@@ -1389,7 +1323,7 @@ bool Device::insert_search_batch(const SearchJob *jobs, int njobs, int k, int ma
     SearchJob *h_jobs = static_cast<SearchJob *>(pinned_stage((sizeof(SearchJob) + sizeof(int)) * (size_t)chunk));
     if (!h_jobs) return false;
     int *h_order = reinterpret_cast<int *>(h_jobs + chunk);
-    if (!grow_dev(&s_order_, &s_order_cap_, (size_t)chunk)) return false;
+    if (!s_order_.grow((size_t)chunk)) return false;
     for (long long off = 0; off < njobs; off += chunk) {
         const int nj = (int)std::min<long long>(chunk, njobs - off);
         memcpy(h_jobs, jobs + off, sizeof(SearchJob) * (size_t)nj);
@@ -1411,15 +1345,15 @@ bool Device::insert_search_batch(const SearchJob *jobs, int njobs, int k, int ma
         HIP_OK(hipMemsetAsync(s_jobctr_, 0, sizeof(int), st));
         HIP_OK(hipMemsetAsync(p_evals, 0, sizeof(unsigned long long), st));
         const bool timed = profiling_;
-        if (timed) HIP_OK(hipEventRecord((hipEvent_t)ev0_, st));
+        if (timed) HIP_OK(hipEventRecord(E(ev0_), st));
         const auto kernel = place_traversal<true>(tl, nj);
         hipLaunchKernelGGL(kernel, dim3(tl.grid), dim3(tl.block), tl.lds_total, st, d_rows_, d_row_sn_, pitch_, g_adj0_, g_stride0_, g_upper_, g_pool_,
-                           g_strideU_, s_jobs_, k, cand_cap, reinterpret_cast<ND *>(s_spill_), spill_cap_for_tests(), max_edges0, s_visited_, tl.vis.words,
+                           g_strideU_, s_jobs_, k, cand_cap, reinterpret_cast<ND *>(s_spill_.get()), spill_cap_for_tests(), max_edges0, s_visited_, tl.vis.words,
                            tl.vis.tab, tl.vis.tab_cap, p_sel0 + (size_t)off * sel_stride, p_cnt0 + off, p_selU, p_cntU, sel_stride, p_flag + off, p_evals,
                            nbcap(), nj, s_jobctr_, tl.flags | (mfma_heuristic() ? 2 : 0), d_order, windowed ? p_log : (int *)nullptr, read_log_cap);
         if (tl.form == kFormLat) stats_.lat_launches++;
         HIP_OK(hipGetLastError());
-        if (timed) HIP_OK(hipEventRecord((hipEvent_t)ev1_, st));
+        if (timed) HIP_OK(hipEventRecord(E(ev1_), st));
         if (!windowed) HIP_OK(hipMemcpyAsync(h_ev, s_evals_, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
         if (windowed) { // one launch (njobs <= chunk): everything the host validates with rides on the same wait
             int *d_owner = s_wdry_, *d_dry0 = p_log + b_log / 4u, *d_dryU = d_dry0 + (size_t)njobs * sel_stride, *d_drop0 = d_dry0 + b_dry / 4u;
@@ -1496,7 +1430,7 @@ bool Device::graph_append_nodes(long long first, long long n, const int *level, 
 {
     *need_full_sync = false;
     if (n <= 0) return true;
-    if (!g_adj0_ || first != g_n_ || first + n > g_cap_n_ || pool_len > g_pool_cap_) { *need_full_sync = true; return true; }
+    if (!g_adj0_ || first != g_n_ || first + n > g_cap_n() || pool_len > g_pool_cap()) { *need_full_sync = true; return true; }
     if (!bind()) return false;
     hipStream_t st = S(stream_);
     HIP_OK(hipMemcpyAsync(g_level_ + first, level + first, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, st));
@@ -1553,31 +1487,15 @@ bool Device::link_batch_begin(int set, const int *rows, int nrows, int row_strid
     // device buffers are shared by both sets: the stream orders one sub-batch after the other.
     // Growing one frees the old allocation, which must not be in use any more.
     for (int i = 0; i < 5; ++i) {
-        if (std::max<size_t>(need[i], 1) > s_lk_cap_[i]) {
+        if (std::max<size_t>(need[i], 1) > s_lk_[i].cap()) {
             HIP_OK(hipStreamSynchronize(st));
-            if (!grow_dev(&s_lk_[i], &s_lk_cap_[i], std::max<size_t>(need[i], 1) * 2)) return false;
+            if (!s_lk_[i].grow(std::max<size_t>(need[i], 1), std::max<size_t>(need[i], 1) * 2)) return false;
         }
     }
     // pinned staging of this set: [rows | node | layer | off | items], results, evaluation count
     const size_t in_ints = need[0] + need[1] + need[2] + need[3];
-    if (in_ints > ls.in_cap) {
-        if (ls.h_in) (void)hipHostFree(ls.h_in);
-        ls.h_in = nullptr; ls.in_cap = 0;
-        if (hipHostMalloc((void **)&ls.h_in, sizeof(int) * in_ints * 2, hipHostMallocDefault) != hipSuccess) { set_dev_error("link_batch: pinned allocation failed"); return false; }
-        ls.in_cap = in_ints * 2;
-    }
-    if (std::max<size_t>(need[4], 1) > ls.out_cap) {
-        if (ls.h_out) (void)hipHostFree(ls.h_out);
-        ls.h_out = nullptr; ls.out_cap = 0;
-        if (hipHostMalloc((void **)&ls.h_out, sizeof(int) * std::max<size_t>(need[4], 1) * 2, hipHostMallocDefault) != hipSuccess) { set_dev_error("link_batch: pinned allocation failed"); return false; }
-        ls.out_cap = std::max<size_t>(need[4], 1) * 2;
-    }
-    if (!ls.h_ev && hipHostMalloc((void **)&ls.h_ev, 16, hipHostMallocDefault) != hipSuccess) { set_dev_error("link_batch: pinned allocation failed"); return false; }
-    if (!ls.ev_done) {
-        hipEvent_t a, b, c;
-        HIP_OK(hipEventCreate(&a)); HIP_OK(hipEventCreate(&b)); HIP_OK(hipEventCreate(&c));
-        ls.ev_start = a; ls.ev_stop = b; ls.ev_done = c;
-    }
+    if (!ls.h_in.grow(in_ints, in_ints * 2) || !ls.h_out.grow(std::max<size_t>(need[4], 1), std::max<size_t>(need[4], 1) * 2) || !ls.h_ev.grow(2)) return false;
+    if (!ls.ev_start.create(true) || !ls.ev_stop.create(true) || !ls.ev_done.create(true)) return false;
     int *h_rows = ls.h_in, *h_node = h_rows + need[0], *h_off = h_node + need[1], *h_items = h_off + need[2];
     if (nrows > 0) memcpy(h_rows, rows, sizeof(int) * need[0]);
     if (ngroups > 0) {
@@ -1601,7 +1519,7 @@ bool Device::link_batch_begin(int set, const int *rows, int nrows, int row_strid
         HIP_OK(hipMemcpyAsync(s_lk_[3], h_items, sizeof(int) * (size_t)total, hipMemcpyHostToDevice, st));
         HIP_OK(hipMemsetAsync(s_evals_, 0, sizeof(unsigned long long), st));
         ls.timed = profiling_;
-        if (ls.timed) HIP_OK(hipEventRecord((hipEvent_t)ls.ev_start, st));
+        if (ls.timed) HIP_OK(hipEventRecord(E(ls.ev_start), st));
         const int k_cap = nbcap();
         const size_t lds = ((search_lds_bytes(k_cap, 0, pitch_, true, nbcap()) + 15) & ~(size_t)15) + 4u * (size_t)(kNewMax + 1) * nbcap();
         with_metric(metric_, [&](auto m) {
@@ -1610,11 +1528,11 @@ bool Device::link_batch_begin(int set, const int *rows, int nrows, int row_strid
                                s_evals_, nbcap(), g_tested0_, g_testedU_, (const int *)nullptr);
         });
         HIP_OK(hipGetLastError());
-        if (ls.timed) HIP_OK(hipEventRecord((hipEvent_t)ls.ev_stop, st));
+        if (ls.timed) HIP_OK(hipEventRecord(E(ls.ev_stop), st));
         if (want_lists) HIP_OK(hipMemcpyAsync(ls.h_out, s_lk_[4], sizeof(int) * (size_t)ngroups * list_stride, hipMemcpyDeviceToHost, st));
         HIP_OK(hipMemcpyAsync(ls.h_ev, s_evals_, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
     }
-    HIP_OK(hipEventRecord((hipEvent_t)ls.ev_done, st));
+    HIP_OK(hipEventRecord(E(ls.ev_done), st));
     ls.busy = true;
     return true;
 }
@@ -1631,7 +1549,7 @@ bool Device::link_dry_run(const int *jobs3, int n, int max_edges0, int *changed)
     if (!bind()) return false;
     hipStream_t st = S(stream_);
     if (!ensure_search_scratch(1, 1, 0, 16)) return false;
-    if (!grow_dev(&s_dry_, &s_dry_cap_, (size_t)n * 4)) return false;
+    if (!s_dry_.grow((size_t)n * 4)) return false;
     int *h = static_cast<int *>(pinned_stage(sizeof(int) * (size_t)n * 4 + 16));
     if (!h) return false;
     unsigned long long *h_ev = reinterpret_cast<unsigned long long *>(h + (((size_t)n * 4 + 1) & ~(size_t)1));
@@ -1667,33 +1585,30 @@ bool Device::link_batch_planned(int njobs, int n_upper, int max_edges0)
     hipStream_t st = S(stream_);
     if (!ensure_search_scratch(1, 1, 0, 16)) return false;
     // per-slot counters: all zero between batches (the link kernel resets what it used)
-    const long long slots = g_cap_n_ + g_pool_cap_ / std::max(1, g_strideU_) + 2;
-    if (slots != lp_slots_) {
+    const long long slots = g_cap_n() + g_pool_cap() / std::max(1, g_strideU_) + 2;
+    if ((size_t)slots != lp_slot_[2].cap()) { // (the mirror was resized: the last of the three says for how many slots they stand)
         HIP_OK(hipStreamSynchronize(st));
         for (int i = 0; i < 3; ++i) {
-            if (lp_slot_[i]) HIP_OK(hipFree(lp_slot_[i]));
-            lp_slot_[i] = nullptr;
-            HIP_OK(hipMalloc(&lp_slot_[i], sizeof(int) * (size_t)slots));
+            if (!lp_slot_[i].reset() || !lp_slot_[i].grow((size_t)slots)) return false;
             HIP_OK(hipMemsetAsync(lp_slot_[i], 0, sizeof(int) * (size_t)slots, st));
         }
-        lp_slots_ = slots;
     }
     const size_t max_appends = (size_t)(njobs + n_upper) * (size_t)max_edges0 + 1;
     for (int i = 0; i < 6; ++i) {
-        if (max_appends > lp_grp_cap_[i]) {
+        if (max_appends > lp_grp_[i].cap()) {
             HIP_OK(hipStreamSynchronize(st));
-            if (!grow_dev(&lp_grp_[i], &lp_grp_cap_[i], max_appends * 2)) return false;
+            if (!lp_grp_[i].grow(max_appends, max_appends * 2)) return false;
         }
     }
-    if (!lp_counters_) HIP_OK(hipMalloc(&lp_counters_, sizeof(int) * 4));
+    if (!lp_counters_.grow(4)) return false;
     HIP_OK(hipMemsetAsync(lp_counters_, 0, sizeof(int) * 4, st));
     HIP_OK(hipMemsetAsync(s_evals_, 0, sizeof(unsigned long long), st));
-    size_t g_cap = lp_grp_cap_[0];
-    for (int i = 1; i < 6; ++i) g_cap = std::min(g_cap, lp_grp_cap_[i]);
-    LinkPlan P{lp_slot_[0], lp_slot_[1], lp_slot_[2], lp_grp_[0], lp_grp_[1], lp_grp_[2], lp_grp_[3], lp_grp_[4], lp_counters_, g_cap_n_,
+    size_t g_cap = lp_grp_[0].cap();
+    for (int i = 1; i < 6; ++i) g_cap = std::min(g_cap, lp_grp_[i].cap());
+    LinkPlan P{lp_slot_[0], lp_slot_[1], lp_slot_[2], lp_grp_[0], lp_grp_[1], lp_grp_[2], lp_grp_[3], lp_grp_[4], lp_counters_, g_cap_n(),
                slots, g_n_, (int)std::min<size_t>(g_cap, 0x7fffffff), njobs};
     const bool timed = profiling_;
-    if (timed) HIP_OK(hipEventRecord((hipEvent_t)ev0_, st));
+    if (timed) HIP_OK(hipEventRecord(E(ev0_), st));
     hipLaunchKernelGGL(link_plan_kernel<true>, dim3(njobs), dim3(64), 0, st, s_jobs_, s_sel_, s_lcnt_, s_selU_, s_cntU_, last_insert_stride_,
                        g_adj0_, g_stride0_, g_upper_, g_pool_, g_strideU_, g_tested0_, g_testedU_, max_edges0, P);
     hipLaunchKernelGGL(link_offsets_kernel, dim3(512), dim3(256), 0, st, g_upper_, g_strideU_, P);
@@ -1729,7 +1644,7 @@ bool Device::link_batch_planned(int njobs, int n_upper, int max_edges0)
         });
         HIP_OK(hipGetLastError());
     }
-    if (timed) HIP_OK(hipEventRecord((hipEvent_t)ev1_, st));
+    if (timed) HIP_OK(hipEventRecord(E(ev1_), st));
     HIP_OK(hipMemcpyAsync(h_ev, s_evals_, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
     HIP_OK(hipMemcpyAsync(h_ctr, lp_counters_, sizeof(int) * 4, hipMemcpyDeviceToHost, st));
     HIP_OK(hipStreamSynchronize(st));
@@ -1742,7 +1657,7 @@ bool Device::link_batch_planned(int njobs, int n_upper, int max_edges0)
 
 bool Device::download_graph(int *adj0, long long n, int *pool, long long pool_len)
 {
-    if (n < 0 || n > g_n_ || pool_len < 0 || pool_len > g_pool_cap_ || (n > 0 && !adj0) || (pool_len > 0 && !pool)) { set_dev_error("download_graph: bad argument"); return false; }
+    if (n < 0 || n > g_n_ || pool_len < 0 || pool_len > g_pool_cap() || (n > 0 && !adj0) || (pool_len > 0 && !pool)) { set_dev_error("download_graph: bad argument"); return false; }
     if (!bind()) return false;
     hipStream_t st = S(stream_);
     if (n > 0) HIP_OK(hipMemcpyAsync(adj0, g_adj0_, sizeof(int) * (size_t)n * g_stride0_, hipMemcpyDeviceToHost, st));
@@ -1756,7 +1671,7 @@ bool Device::link_batch_finish(int set, const int **out_lists)
     if (set < 0 || set > 1 || !lset_[set].busy) { set_dev_error("link_batch_finish: nothing in flight"); return false; }
     LinkSet &ls = lset_[set];
     if (!bind()) return false;
-    HIP_OK(hipEventSynchronize((hipEvent_t)ls.ev_done));
+    HIP_OK(hipEventSynchronize(E(ls.ev_done)));
     ls.busy = false;
     if (out_lists) *out_lists = ls.h_out;
     if (ls.ngroups > 0 && !count_launch(&kLinkFamily, *ls.h_ev, false, ls.timed, ls.ev_start, ls.ev_stop)) return false;
@@ -1768,14 +1683,7 @@ bool Device::link_batch_finish(int set, const int **out_lists)
 // through a pinned bounce buffer at PCIe rate.
 void *Device::pinned_stage(size_t bytes)
 {
-    if (bytes <= h_stage_cap_) return h_stage_;
-    if (h_stage_) (void)hipHostFree(h_stage_);
-    h_stage_ = nullptr;
-    h_stage_cap_ = 0;
-    size_t cap = std::max<size_t>(bytes, 1u << 20);
-    if (hipHostMalloc(&h_stage_, cap, hipHostMallocDefault) != hipSuccess) { set_dev_error("pinned staging allocation failed"); return nullptr; }
-    h_stage_cap_ = cap;
-    return h_stage_;
+    return h_stage_.grow(bytes, std::max<size_t>(bytes, 1u << 20)) ? h_stage_.get() : nullptr;
 }
 
 // KnnQuery on the device: descent + layer-0 beam search (width k) + the stable top-k_out tail.
@@ -1828,8 +1736,8 @@ bool Device::search_batch_impl(const SearchJob *jobs, int njobs, int k, int k_ou
     int *h_ids = reinterpret_cast<int *>(hs + 16 + b_jobs);
     float *h_d = reinterpret_cast<float *>(hs + 16 + b_jobs + b_res);
     int *h_flag = reinterpret_cast<int *>(hs + 16 + b_jobs + 2 * b_res);
-    int *d_ids = reinterpret_cast<int *>(s_hits_);
-    float *d_d = reinterpret_cast<float *>(s_hits_) + (size_t)chunk * k_out;
+    int *d_ids = reinterpret_cast<int *>(s_hits_.get());
+    float *d_d = reinterpret_cast<float *>(s_hits_.get()) + (size_t)chunk * k_out;
     // A call answered by ONE launch of modest size is mostly API calls around a latency-bound kernel (a single query: 0.37 ms
     // of kernel in a 0.45-ms call, eleven HIP calls): ids, distances and flags then sit in one device slab and come back in
     // one copy into the pinned staging (laid out alike), the evaluation counter lives in the job counter's spare words and
@@ -1837,7 +1745,7 @@ bool Device::search_batch_impl(const SearchJob *jobs, int njobs, int k, int k_ou
     // the distances are still crossing the link.)
     const bool compact = njobs == chunk && 2 * b_res + 4u * (size_t)chunk <= (size_t)1 << 20;
     int *d_flag = compact ? reinterpret_cast<int *>(d_d + (size_t)chunk * k_out) : s_flag_;
-    unsigned long long *d_ev = compact ? reinterpret_cast<unsigned long long *>(s_jobctr_ + 2) : s_evals_;
+    unsigned long long *d_ev = compact ? reinterpret_cast<unsigned long long *>(s_jobctr_.get() + 2) : s_evals_;
     // a query set whose tail is still on the host (set_queries_streamed): the launch is gated on the rows' arrival
     const int *gate = tail_.n > 0 ? d_ready_ : nullptr;
     // whatever happens below, nothing stays pending -- and a tail that never went up (an error between the launch and
@@ -1858,16 +1766,16 @@ bool Device::search_batch_impl(const SearchJob *jobs, int njobs, int k, int k_ou
         HIP_OK(hipMemsetAsync(s_jobctr_, 0, sizeof(int) * (4 + (size_t)nj), st));
         if (!compact) HIP_OK(hipMemsetAsync(s_evals_, 0, sizeof(unsigned long long), st));
         const bool timed = profiling_;
-        if (timed) HIP_OK(hipEventRecord((hipEvent_t)ev0_, st));
+        if (timed) HIP_OK(hipEventRecord(E(ev0_), st));
         const auto kernel = place_traversal<false>(tl, nj);
         hipLaunchKernelGGL(kernel, dim3(tl.grid), dim3(tl.block), tl.lds_total, st, d_rows_, d_row_sn_, d_queries_, d_q_sn_, pitch_, g_adj0_, g_stride0_,
-                           g_upper_, g_pool_, g_strideU_, s_jobs_, k, cand_cap, reinterpret_cast<ND *>(s_spill_), spill_cap_for_tests(), s_visited_,
+                           g_upper_, g_pool_, g_strideU_, s_jobs_, k, cand_cap, reinterpret_cast<ND *>(s_spill_.get()), spill_cap_for_tests(), s_visited_,
                            tl.vis.words, tl.vis.tab, tl.vis.tab_cap, k_out, d_ids, d_d, s_cnt_, d_flag, d_ev, nbcap(), nj, s_jobctr_,
                            tl.flags | (shadow_mode() && shadows_allowed_ ? 0x100 : 0), gate);
         if (tl.form == kFormLat) stats_.lat_launches++;
         if (tl.form == kFormLean) stats_.lean_launches++;
         HIP_OK(hipGetLastError());
-        if (timed) HIP_OK(hipEventRecord((hipEvent_t)ev1_, st));
+        if (timed) HIP_OK(hipEventRecord(E(ev1_), st));
         if (tail_.n > 0 && !upload_tail()) return false; // the rest of the query set, while the launch above is running
         if (compact) { // [ids | distances | flags] in one piece (nj == chunk: the device slab and the staging are laid out alike)
             HIP_OK(hipMemcpyAsync(h_ids, d_ids, 2 * b_res + sizeof(int) * (size_t)nj, hipMemcpyDeviceToHost, st));
@@ -1877,11 +1785,11 @@ bool Device::search_batch_impl(const SearchJob *jobs, int njobs, int k, int k_ou
         } else {
         // the ids are copied out to the caller's array while the distances are still crossing the link
         HIP_OK(hipMemcpyAsync(h_ids, d_ids, 4u * (size_t)nj * k_out, hipMemcpyDeviceToHost, st));
-        HIP_OK(hipEventRecord((hipEvent_t)ev2_, st));
+        HIP_OK(hipEventRecord(E(ev2_), st));
         HIP_OK(hipMemcpyAsync(h_d, d_d, 4u * (size_t)nj * k_out, hipMemcpyDeviceToHost, st));
         HIP_OK(hipMemcpyAsync(h_flag, s_flag_, sizeof(int) * (size_t)nj, hipMemcpyDeviceToHost, st));
         HIP_OK(hipMemcpyAsync(h_ev, s_evals_, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-        HIP_OK(hipEventSynchronize((hipEvent_t)ev2_));
+        HIP_OK(hipEventSynchronize(E(ev2_)));
         memcpy(out_ids + (size_t)off * k_out, h_ids, 4u * (size_t)nj * k_out);
         HIP_OK(hipStreamSynchronize(st));
         }
@@ -1916,17 +1824,17 @@ bool Device::run_resident(size_t row, long long chunk, size_t extra, bool hashed
     float *h_d = reinterpret_cast<float *>(hs + 16 + b_res);
     int *h_flag = reinterpret_cast<int *>(hs + 16 + 2 * b_res);
     if (!upload(hs + 16 + 2 * b_res + 4u * (size_t)chunk)) return false;
-    int *d_ids = reinterpret_cast<int *>(s_hits_);
-    float *d_d = reinterpret_cast<float *>(s_hits_) + (size_t)chunk * row;
+    int *d_ids = reinterpret_cast<int *>(s_hits_.get());
+    float *d_d = reinterpret_cast<float *>(s_hits_.get()) + (size_t)chunk * row;
     for (long long off = 0; off < nq; off += chunk) {
         const int nj = (int)std::min<long long>(chunk, nq - off);
         HIP_OK(hipMemsetAsync(s_jobctr_, 0, sizeof(int) * 4, st));
         HIP_OK(hipMemsetAsync(s_evals_, 0, sizeof(unsigned long long), st));
         const bool timed = profiling_;
-        if (timed) HIP_OK(hipEventRecord((hipEvent_t)ev0_, st));
+        if (timed) HIP_OK(hipEventRecord(E(ev0_), st));
         launch(off, nj, d_ids, d_d);
         HIP_OK(hipGetLastError());
-        if (timed) HIP_OK(hipEventRecord((hipEvent_t)ev1_, st));
+        if (timed) HIP_OK(hipEventRecord(E(ev1_), st));
         HIP_OK(hipMemcpyAsync(h_ids, d_ids, 4u * (size_t)nj * row, hipMemcpyDeviceToHost, st));
         HIP_OK(hipMemcpyAsync(h_d, d_d, 4u * (size_t)nj * row, hipMemcpyDeviceToHost, st));
         HIP_OK(hipMemcpyAsync(h_flag, s_flag_, sizeof(int) * (size_t)nj, hipMemcpyDeviceToHost, st));
@@ -1973,8 +1881,8 @@ bool Device::search_filtered(int nq, int entry, int entry_layer, int k, int k_ou
     place_persistent(kernel, tl, (int)chunk);
     const int fspill = filter_spill_cap();
     if (!ensure_search_scratch(chunk, max_slots(), k_out, tl.vis.bytes_per_job)) return false;
-    if (!grow_dev(&s_fspill_, &s_fspill_cap_, (size_t)tl.slots * (size_t)std::max(fspill, 1) + 8)) return false; // +8: get2 may read one entry past a heap
-    if (!grow_dev(&s_allow_, &s_allow_cap_, std::max<size_t>(words, 1))) return false;
+    if (!s_fspill_.grow((size_t)tl.slots * (size_t)std::max(fspill, 1) + 8)) return false; // +8: get2 may read one entry past a heap
+    if (!s_allow_.grow(std::max<size_t>(words, 1))) return false;
     const auto upload = [&](char *h_allow) { // the allow words go up from pinned memory
         memcpy(h_allow, allow_bits, 4u * words);
         HIP_OK(hipMemcpyAsync(s_allow_, h_allow, 4u * words, hipMemcpyHostToDevice, st));
@@ -1983,8 +1891,8 @@ bool Device::search_filtered(int nq, int entry, int entry_layer, int k, int k_ou
     const auto launch = [&](long long off, int nj, int *d_ids, float *d_d) {
         hipLaunchKernelGGL(kernel, dim3(std::min(nj, tl.slots)), dim3(tl.block), tl.lds_total, st, d_rows_, d_row_sn_, d_queries_ + (size_t)off * pitch_,
                            d_q_sn_ ? d_q_sn_ + off : nullptr, pitch_, g_adj0_, g_stride0_, g_upper_, g_pool_, g_strideU_, entry, entry_layer, search_layer, k,
-                           cand_cap, reinterpret_cast<ND *>(s_fspill_), fspill, s_visited_, tl.vis.words, tl.vis.tab, tl.vis.tab_cap,
-                           reinterpret_cast<const unsigned *>(s_allow_), n_allow, k_out, d_ids, d_d, s_flag_, s_evals_, nbcap(), nj, s_jobctr_);
+                           cand_cap, reinterpret_cast<ND *>(s_fspill_.get()), fspill, s_visited_, tl.vis.words, tl.vis.tab, tl.vis.tab_cap,
+                           reinterpret_cast<const unsigned *>(s_allow_.get()), n_allow, k_out, d_ids, d_d, s_flag_, s_evals_, nbcap(), nj, s_jobctr_);
     };
     if (!run_resident((size_t)k_out, chunk, 4u * words, tl.vis.tab != nullptr, nq, out_ids, out_d, out_flag, upload, launch)) return false;
     for (int i = 0; i < nq; ++i) stats_.search_overflows += (uint64_t)(out_flag[i] == 1);
@@ -2024,7 +1932,7 @@ bool Device::multilayer_search(int nq, int entry, int entry_layer, int first_lay
     const auto launch = [&](long long off, int nj, int *d_ids, float *d_d) {
         hipLaunchKernelGGL(kernel, dim3(std::min(nj, tl.slots)), dim3(tl.block), tl.lds_total, st, d_rows_, d_row_sn_, d_queries_ + (size_t)off * pitch_,
                            d_q_sn_ ? d_q_sn_ + off : nullptr, pitch_, g_adj0_, g_stride0_, g_upper_, g_pool_, g_strideU_, entry, entry_layer, first_layer,
-                           min_layer, k, cand_cap, reinterpret_cast<ND *>(s_spill_), spill_cap, s_visited_, tl.vis.words, tl.vis.tab, tl.vis.tab_cap, d_ids,
+                           min_layer, k, cand_cap, reinterpret_cast<ND *>(s_spill_.get()), spill_cap, s_visited_, tl.vis.words, tl.vis.tab, tl.vis.tab_cap, d_ids,
                            d_d, s_flag_, s_evals_, nbcap(), nj, s_jobctr_);
         stats_.multilayer_launches += 1; // counted as made, so a call that fails part-way keeps the launches before the failure
     };
@@ -2068,7 +1976,7 @@ bool Device::relink_batch(const int *affected, const int *layer, const int *remo
     // device staging: [jobs (4 n) | cand_off | cand_cnt | cands | sel | cnt | flag]
     const size_t o_off = 4u * (size_t)n, o_cnt = o_off + (size_t)nsteps, o_c = o_cnt + (size_t)nsteps, o_s = o_c + (size_t)std::max(total_c, 1),
                  o_n = o_s + (size_t)n * sel_stride, o_f = o_n + (size_t)n, total = o_f + (size_t)n;
-    if (!grow_dev(&s_rl_, &s_rl_cap_, total + 4)) return false; // (+4: the int4 view of the jobs starts aligned, hipMalloc is)
+    if (!s_rl_.grow(total + 4)) return false; // (+4: the int4 view of the jobs starts aligned, as a device allocation does)
     int *hs = static_cast<int *>(pinned_stage(sizeof(int) * total + 16));
     if (!hs) return false;
     for (int i = 0; i < n; ++i) { hs[4 * i] = affected[i]; hs[4 * i + 1] = layer[i]; hs[4 * i + 2] = removed[i]; hs[4 * i + 3] = step[i]; }
@@ -2079,7 +1987,7 @@ bool Device::relink_batch(const int *affected, const int *layer, const int *remo
     HIP_OK(hipMemsetAsync(s_evals_, 0, sizeof(unsigned long long), st));
     with_metric(metric_, [&](auto m) {
         hipLaunchKernelGGL(graph_relink_kernel<m>, dim3(n), dim3(64), lds, st, d_rows_, d_row_sn_, pitch_, g_adj0_, g_stride0_, g_upper_, g_pool_,
-                           g_strideU_, reinterpret_cast<const int4 *>(s_rl_), s_rl_ + o_c, s_rl_ + o_off, s_rl_ + o_cnt, max_edges0, kcap, nb, s_rl_ + o_s,
+                           g_strideU_, reinterpret_cast<const int4 *>(s_rl_.get()), s_rl_ + o_c, s_rl_ + o_off, s_rl_ + o_cnt, max_edges0, kcap, nb, s_rl_ + o_s,
                            s_rl_ + o_n, s_rl_ + o_f, sel_stride, s_evals_, heap_order ? 1 : 0);
     });
     HIP_OK(hipGetLastError());
@@ -2112,7 +2020,7 @@ bool Device::patch_lists(const int *recs, int nrows, int row_stride)
     if (!bind()) return false;
     hipStream_t st = S(stream_);
     const size_t total = (size_t)nrows * row_stride;
-    if (!grow_dev(&s_rl_, &s_rl_cap_, total)) return false;
+    if (!s_rl_.grow(total)) return false;
     int *hs = static_cast<int *>(pinned_stage(sizeof(int) * total));
     if (!hs) return false;
     memcpy(hs, tagged.data(), sizeof(int) * total);
@@ -2131,16 +2039,11 @@ bool Device::patch_lists(const int *recs, int nrows, int row_stride)
 // Room for `entries` results in the pinned host buffer, the first `keep` of which survive a reallocation.
 bool Device::range_host_room(size_t entries, size_t keep)
 {
-    if (entries <= h_range_cap_) return true;
-    const size_t cap = std::max(entries + entries / 2, (size_t)1 << 20);
-    SearchHit *p = nullptr;
-    if (hipHostMalloc((void **)&p, sizeof(SearchHit) * cap, hipHostMallocDefault) != hipSuccess) { set_dev_error("range_batch: pinned allocation failed"); return false; }
-    if (h_range_) {
-        if (keep) memcpy(p, h_range_, sizeof(SearchHit) * keep);
-        (void)hipHostFree(h_range_);
-    }
-    h_range_ = p;
-    h_range_cap_ = cap;
+    if (entries <= h_range_.cap()) return true;
+    PinBuf<SearchHit> p;
+    if (!p.grow(entries, std::max(entries + entries / 2, (size_t)1 << 20))) return false;
+    if (h_range_ && keep) memcpy(p, h_range_, sizeof(SearchHit) * keep);
+    h_range_ = std::move(p);
     return true;
 }
 
@@ -2172,44 +2075,32 @@ bool Device::range_batch(const SearchJob *jobs, int njobs, float range, RangeRes
     if (!visited_scratch(512, 4 * kRangeFan * 128, true, &vis)) return false;
     const long long chunk = std::min<long long>(njobs, 1 << 20);
     if (!ensure_search_scratch(chunk, max_slots(), 0, vis.bytes_per_job)) return false; // also the per-wave result lists (s_spill_)
-    if ((size_t)chunk > s_roff_cap_) {
-        if (s_roff_) HIP_OK(hipFree(s_roff_));
-        if (s_rentry_) HIP_OK(hipFree(s_rentry_));
-        s_roff_ = nullptr; s_rentry_ = nullptr; s_roff_cap_ = 0;
-        HIP_OK(hipMalloc(&s_roff_, sizeof(unsigned long long) * (size_t)chunk));
-        HIP_OK(hipMalloc(&s_rentry_, sizeof(int) * (size_t)chunk));
-        if (s_rstate_) HIP_OK(hipFree(s_rstate_));
-        if (s_rtied_) HIP_OK(hipFree(s_rtied_));
-        s_rstate_ = nullptr; s_rtied_ = nullptr;
-        HIP_OK(hipMalloc(&s_rstate_, sizeof(int) * (size_t)chunk));
-        HIP_OK(hipMalloc(&s_rtied_, sizeof(int) * ((size_t)chunk + 1)));
-        if (s_rres_) HIP_OK(hipFree(s_rres_));
-        if (s_rdst_) HIP_OK(hipFree(s_rdst_));
-        s_rres_ = nullptr; s_rdst_ = nullptr; // (allocated by the first filtered call)
-        s_roff_cap_ = (size_t)chunk;
+    if ((size_t)chunk > s_roff_.cap()) { // the per-job arrays grow together; s_roff_ says for how many jobs they stand, so it is let go when one of the others fails
+        const size_t c = (size_t)chunk;
+        const bool ok = reset_all(s_roff_, s_rentry_) && s_roff_.grow(c) && s_rentry_.grow(c) && reset_all(s_rstate_, s_rtied_) && s_rstate_.grow(c) &&
+                        s_rtied_.grow(c + 1) && reset_all(s_rres_, s_rdst_); // (those two: allocated by the first filtered call)
+        if (!ok) { (void)s_roff_.reset(); return false; }
     }
     long long n_allow = 0;
     if (filtered) { // the call's allow-set: the words that cover graph ids, on this context (as search_filtered)
-        if (!s_rres_) HIP_OK(hipMalloc(&s_rres_, sizeof(int) * s_roff_cap_));
-        if (!s_rdst_) HIP_OK(hipMalloc(&s_rdst_, sizeof(unsigned long long) * s_roff_cap_));
+        if (!s_rres_.grow(s_roff_.cap()) || !s_rdst_.grow(s_roff_.cap())) return false;
         n_allow = std::min<long long>(nbits, g_n_);
         const size_t words = (size_t)((n_allow + 31) / 32);
-        if (!grow_dev(&s_allow_, &s_allow_cap_, std::max<size_t>(words, 1))) return false;
+        if (!s_allow_.grow(std::max<size_t>(words, 1))) return false;
         if (words) {
             HIP_OK(hipMemcpyAsync(s_allow_, allow_bits, 4u * words, hipMemcpyHostToDevice, st));
             HIP_OK(hipStreamSynchronize(st)); // (pageable source: the caller's buffer)
         }
     }
     unsigned long long closure_total = 0; // entries the traversals found (sizes the next call's arena)
-    if (!s_arena_used_) HIP_OK(hipMalloc(&s_arena_used_, sizeof(unsigned long long)));
-    if (!s_rfin_ctr_) HIP_OK(hipMalloc(&s_rfin_ctr_, sizeof(int) * 2));
+    if (!s_arena_used_.grow(1) || !s_rfin_ctr_.grow(2)) return false;
     constexpr size_t kArenaMax = (size_t)1 << 27; // 1 GB of results per launch; what does not fit then is handed back
 
     // One launch over the jobs listed in `todo` (at most `chunk`): results appended to res->found; jobs that found
     // the arena full are listed in `again` and *need = the entries they asked for; handed-back jobs in `handed`.
     auto launch = [&](const int *todo, int nj, ND *lists, int list_cap, int grid_cap, size_t arena_cap, std::vector<int> &again,
                       unsigned long long *need, std::vector<int> &handed) -> bool {
-        if (!grow_dev(&s_arena_, &s_arena_cap_, arena_cap)) return false;
+        if (!s_arena_.grow(arena_cap)) return false;
         // pinned layout: [evals, used (16 B) | jobs | offsets | counts | flags | entries | states]; then reused for the results
         // (filtered: [... | allowed counts | packed offsets] besides)
         const size_t b_jobs = sizeof(SearchJob) * (size_t)nj, b_off = 8u * (size_t)nj, b_i = 4u * (size_t)nj;
@@ -2223,14 +2114,14 @@ bool Device::range_batch(const SearchJob *jobs, int njobs, float range, RangeRes
         HIP_OK(hipMemsetAsync(s_evals_, 0, sizeof(unsigned long long), st));
         HIP_OK(hipMemsetAsync(s_arena_used_, 0, sizeof(unsigned long long), st));
         const bool timed = profiling_;
-        if (timed) HIP_OK(hipEventRecord((hipEvent_t)ev0_, st));
+        if (timed) HIP_OK(hipEventRecord(E(ev0_), st));
         const auto kernel = persistent_kernel(metric_, vis.tab != nullptr, [&](auto m, auto h) {
             return layer != 0 ? &graph_range_kernel<m, h, true> : &graph_range_kernel<m, h>;
         });
         const int slots = std::min(std::min(max_slots(), grid_cap), resident_blocks(kernel, lds, num_cu_));
         hipLaunchKernelGGL(kernel, dim3(std::min<int>(nj, slots)), dim3(64), lds, st, d_rows_, d_row_sn_, d_queries_, d_q_sn_, pitch_, g_adj0_,
                            g_stride0_, g_upper_, g_pool_, g_strideU_, s_jobs_, range, lists, list_cap, s_visited_, vis.words, vis.tab, vis.tab_cap,
-                           reinterpret_cast<ND *>(s_arena_), (unsigned long long)arena_cap, s_arena_used_, s_roff_, s_cnt_, s_flag_, s_rentry_, s_evals_,
+                           reinterpret_cast<ND *>(s_arena_.get()), (unsigned long long)arena_cap, s_arena_used_, s_roff_, s_cnt_, s_flag_, s_rentry_, s_evals_,
                            nbcap_r, nj, s_jobctr_);
         HIP_OK(hipGetLastError());
         // the ORDER, still on the device (dk_range_finish.h): every finished list ranked ascending in place; the lists that hold equal
@@ -2244,25 +2135,25 @@ bool Device::range_batch(const SearchJob *jobs, int njobs, float range, RangeRes
         HIP_OK(hipMemsetAsync(s_rstate_, 0, sizeof(int) * (size_t)nj, st));
         const dim3 sort_grid(std::min(nj, 8 * std::max(1, num_cu_))), replay_grid(std::min(nj, 2 * std::max(1, num_cu_)));
         if (filtered) {
-            hipLaunchKernelGGL(range_sort_filtered_kernel, sort_grid, dim3(64), 0, st, reinterpret_cast<ND *>(s_arena_), s_roff_, s_cnt_, s_flag_, nj,
-                               s_rstate_, s_rtied_, s_rfin_ctr_, reinterpret_cast<const unsigned *>(s_allow_), n_allow, s_rres_,
+            hipLaunchKernelGGL(range_sort_filtered_kernel, sort_grid, dim3(64), 0, st, reinterpret_cast<ND *>(s_arena_.get()), s_roff_, s_cnt_, s_flag_, nj,
+                               s_rstate_, s_rtied_, s_rfin_ctr_, reinterpret_cast<const unsigned *>(s_allow_.get()), n_allow, s_rres_,
                                (int)(finish == 0 || range < 0.0f));
             HIP_OK(hipGetLastError());
         } else if (finish >= 1) {
-            hipLaunchKernelGGL(range_sort_kernel, sort_grid, dim3(64), 0, st, reinterpret_cast<ND *>(s_arena_), s_roff_, s_cnt_, s_flag_, nj,
+            hipLaunchKernelGGL(range_sort_kernel, sort_grid, dim3(64), 0, st, reinterpret_cast<ND *>(s_arena_.get()), s_roff_, s_cnt_, s_flag_, nj,
                                s_rstate_, s_rtied_, s_rfin_ctr_);
             HIP_OK(hipGetLastError());
         }
         if (finish >= 2) {
             if (filtered)
-                hipLaunchKernelGGL(range_replay_filtered_kernel, replay_grid, dim3(64), sizeof(RangeReplayLds) + 64, st, reinterpret_cast<ND *>(s_arena_), s_roff_,
+                hipLaunchKernelGGL(range_replay_filtered_kernel, replay_grid, dim3(64), sizeof(RangeReplayLds) + 64, st, reinterpret_cast<ND *>(s_arena_.get()), s_roff_,
                                    s_cnt_, s_rentry_, g_adj0_, g_stride0_, g_upper_, g_pool_, g_strideU_, layer, g_n_, range, s_rstate_, s_rtied_, s_rfin_ctr_ + 1, s_rres_);
             else
-                hipLaunchKernelGGL(range_replay_kernel, replay_grid, dim3(64), sizeof(RangeReplayLds) + 64, st, reinterpret_cast<ND *>(s_arena_), s_roff_,
+                hipLaunchKernelGGL(range_replay_kernel, replay_grid, dim3(64), sizeof(RangeReplayLds) + 64, st, reinterpret_cast<ND *>(s_arena_.get()), s_roff_,
                                    s_cnt_, s_rentry_, g_adj0_, g_stride0_, g_upper_, g_pool_, g_strideU_, layer, g_n_, range, s_rstate_, s_rtied_, s_rfin_ctr_ + 1);
             HIP_OK(hipGetLastError());
         }
-        if (timed) HIP_OK(hipEventRecord((hipEvent_t)ev1_, st));
+        if (timed) HIP_OK(hipEventRecord(E(ev1_), st));
         unsigned long long *h_hdr = reinterpret_cast<unsigned long long *>(hs);
         unsigned long long *h_off = reinterpret_cast<unsigned long long *>(hs + 16 + b_jobs);
         int *h_cnt = reinterpret_cast<int *>(hs + 16 + b_jobs + b_off);
@@ -2311,10 +2202,10 @@ bool Device::range_batch(const SearchJob *jobs, int njobs, float range, RangeRes
                 packed += (unsigned long long)held;
             }
             if (packed > 0) {
-                if (!grow_dev(&s_rpack_, &s_rpack_cap_, (size_t)packed)) return false;
+                if (!s_rpack_.grow((size_t)packed)) return false;
                 HIP_OK(hipMemcpyAsync(s_rdst_, h_dst, b_off, hipMemcpyHostToDevice, st));
-                hipLaunchKernelGGL(range_pack_kernel, dim3(std::min((nj + 3) / 4, 8 * std::max(1, num_cu_))), dim3(256), 0, st, reinterpret_cast<const ND *>(s_arena_),
-                                   s_roff_, s_cnt_, s_flag_, s_rstate_, s_rres_, s_rdst_, nj, reinterpret_cast<ND *>(s_rpack_));
+                hipLaunchKernelGGL(range_pack_kernel, dim3(std::min((nj + 3) / 4, 8 * std::max(1, num_cu_))), dim3(256), 0, st, reinterpret_cast<const ND *>(s_arena_.get()),
+                                   s_roff_, s_cnt_, s_flag_, s_rstate_, s_rres_, s_rdst_, nj, reinterpret_cast<ND *>(s_rpack_.get()));
                 HIP_OK(hipGetLastError());
                 if (!range_host_room(base + (size_t)packed, base)) return false;
                 HIP_OK(hipMemcpyAsync(h_range_ + base, s_rpack_, sizeof(SearchHit) * (size_t)packed, hipMemcpyDeviceToHost, st));
@@ -2353,14 +2244,14 @@ bool Device::range_batch(const SearchJob *jobs, int njobs, float range, RangeRes
     std::vector<int> all((size_t)njobs), handed, still;
     for (int i = 0; i < njobs; ++i) all[(size_t)i] = i;
     const size_t guess = (size_t)((range_hint_ * 1.25 + 16.0) * (double)std::min<long long>(chunk, njobs));
-    if (!run(std::move(all), reinterpret_cast<ND *>(s_spill_), kSpillCap, max_slots(), std::min(std::max<size_t>((size_t)1 << 20, guess), kArenaMax), handed)) return false;
+    if (!run(std::move(all), reinterpret_cast<ND *>(s_spill_.get()), kSpillCap, max_slots(), std::min(std::max<size_t>((size_t)1 << 20, guess), kArenaMax), handed)) return false;
     // result sets beyond a wave's list: again, with lists as long as the graph (at most 1 GB of them at a time);
     // a visited table filling up (graphs above 4M nodes) is not helped by that and stays handed back
     if (!handed.empty() && !vis.tab && g_n_ > kSpillCap) {
         const size_t list_cap = (size_t)std::min<long long>(g_n_, 1 << 24);
         const int waves = (int)std::max<size_t>(1, std::min<size_t>(handed.size(), ((size_t)1 << 27) / list_cap));
-        if (!grow_dev(&s_rlists_, &s_rlists_cap_, list_cap * (size_t)waves)) return false;
-        if (!run(handed, reinterpret_cast<ND *>(s_rlists_), (int)list_cap, waves, std::min(std::max<size_t>((size_t)1 << 20, list_cap), kArenaMax), still)) return false;
+        if (!s_rlists_.grow(list_cap * (size_t)waves)) return false;
+        if (!run(handed, reinterpret_cast<ND *>(s_rlists_.get()), (int)list_cap, waves, std::min(std::max<size_t>((size_t)1 << 20, list_cap), kArenaMax), still)) return false;
         handed.swap(still);
     }
     stats_.range_handbacks += handed.size();
@@ -2607,10 +2498,10 @@ bool Device::exact_knn(const float *queries, int nq, long long n_rows, int k, co
     const double *d_qsn = d_q_sn_;
     if (queries) {
         if (tail_.n > 0) { set_dev_error("exact_knn: a streamed query set is still being uploaded"); return false; }
-        std::swap(d_queries_, x_queries_); std::swap(d_q_sn_, x_q_sn_); std::swap(q_capacity_, x_q_capacity_);
+        std::swap(d_queries_, x_queries_); std::swap(d_q_sn_, x_q_sn_);
         const long long kept = n_queries_;
         const bool ok = set_queries(queries, nq);
-        std::swap(d_queries_, x_queries_); std::swap(d_q_sn_, x_q_sn_); std::swap(q_capacity_, x_q_capacity_);
+        std::swap(d_queries_, x_queries_); std::swap(d_q_sn_, x_q_sn_);
         n_queries_ = kept;
         if (!ok) return false;
         d_q = x_queries_; d_qsn = x_q_sn_;
@@ -2633,7 +2524,7 @@ bool Device::exact_knn(const float *queries, int nq, long long n_rows, int k, co
             h_words[w] = v;
             m += __builtin_popcount(v);
         }
-        if (!grow_dev(&s_allow_, &s_allow_cap_, words) || !grow_dev(&x_boff_, &x_boff_cap_, blocks) || !grow_dev(&x_ids_, &x_ids_cap_, (size_t)m)) return false;
+        if (!s_allow_.grow(words) || !x_boff_.grow(blocks) || !x_ids_.grow((size_t)m)) return false;
         HIP_OK(hipMemcpyAsync(x_boff_, h_off, 8 * blocks, hipMemcpyHostToDevice, st));
         HIP_OK(hipMemcpyAsync(s_allow_, h_words, 4 * words, hipMemcpyHostToDevice, st));
         HIP_OK(exact_compact_launch(s_allow_, (long long)words, x_boff_, x_ids_, st));
@@ -2641,12 +2532,12 @@ bool Device::exact_knn(const float *queries, int nq, long long n_rows, int k, co
     }
     const ExactPlan p = exact_plan(nq, m, k, pitch_, num_cu_);
     if (p.lds > 64 * 1024) { set_dev_error("exact_knn: tile exceeds the LDS budget"); return false; }
-    if (!grow_dev(&x_lists_, &x_lists_cap_, (size_t)p.round * p.n_chunks * k) || !grow_dev(&x_out_, &x_out_cap_, 2 * (size_t)p.round * k)) return false;
-    if (!grow_dev(&x_evals_, &x_evals_cap_, 1)) return false;
+    if (!x_lists_.grow((size_t)p.round * p.n_chunks * k) || !x_out_.grow(2 * (size_t)p.round * k)) return false;
+    if (!x_evals_.grow(1)) return false;
     char *hs = static_cast<char *>(pinned_stage(8 * (size_t)p.round * k + 8));
     if (!hs) return false;
     unsigned long long *h_ev = reinterpret_cast<unsigned long long *>(hs + 8 * (size_t)p.round * k);
-    if (!ev0_) { hipEvent_t e0, e1; HIP_OK(hipEventCreate(&e0)); ev0_ = e0; HIP_OK(hipEventCreate(&e1)); ev1_ = e1; }
+    if (!ev0_.create(true) || !ev1_.create(true)) return false;
     for (long long off = 0; off < nq; off += p.round) {
         const int nr = (int)std::min<long long>(p.round, nq - off);
         ExactScanArgs a;
@@ -2657,15 +2548,15 @@ bool Device::exact_knn(const float *queries, int nq, long long n_rows, int k, co
         a.lists = x_lists_; a.n_chunks = p.n_chunks; a.evals = x_evals_;
         const unsigned tiles = (unsigned)((nr + p.qtile - 1) / p.qtile);
         int *d_ids = x_out_;
-        float *d_d = reinterpret_cast<float *>(x_out_ + (size_t)p.round * k);
+        float *d_d = reinterpret_cast<float *>(x_out_.get() + (size_t)p.round * k);
         const bool timed = profiling_;
         HIP_OK(hipMemsetAsync(x_evals_, 0, sizeof(unsigned long long), st));
-        if (timed) HIP_OK(hipEventRecord((hipEvent_t)ev0_, st));
+        if (timed) HIP_OK(hipEventRecord(E(ev0_), st));
         hipError_t e = hipSuccess;
         with_metric(metric_, [&](auto mt) { e = exact_scan_launch<mt>(a, tiles, p.lds, st); });
         HIP_OK(e);
         HIP_OK(exact_merge_launch(x_lists_, p.n_chunks, k, nr, d_ids, d_d, st));
-        if (timed) HIP_OK(hipEventRecord((hipEvent_t)ev1_, st));
+        if (timed) HIP_OK(hipEventRecord(E(ev1_), st));
         HIP_OK(hipMemcpyAsync(hs, d_ids, 4u * (size_t)nr * k, hipMemcpyDeviceToHost, st));
         HIP_OK(hipMemcpyAsync(hs + 4u * (size_t)p.round * k, d_d, 4u * (size_t)nr * k, hipMemcpyDeviceToHost, st));
         HIP_OK(hipMemcpyAsync(h_ev, x_evals_, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
@@ -2677,7 +2568,7 @@ bool Device::exact_knn(const float *queries, int nq, long long n_rows, int k, co
         stats_.exact_launches += 1; stats_.exact_evals += *h_ev;
         if (timed) {
             float ms = 0.f;
-            HIP_OK(hipEventElapsedTime(&ms, (hipEvent_t)ev0_, (hipEvent_t)ev1_));
+            HIP_OK(hipEventElapsedTime(&ms, E(ev0_), E(ev1_)));
             stats_.exact_kernel_ms += ms; stats_.exact_timed_launches += 1; stats_.exact_timed_evals += *h_ev;
         }
     }
@@ -2753,14 +2644,14 @@ bool Device::dist_pair_batch(const int *a, const int *b, int n, float *out)
     if (!a || !b || !out) { set_dev_error("dist_pair_batch: null argument"); return false; }
     if (!bind()) return false;
     hipStream_t st = S(stream_);
-    if (!d_guard_) { HIP_OK(hipMalloc(&d_guard_, sizeof(int))); HIP_OK(hipMemsetAsync(d_guard_, 0, sizeof(int), st)); }
-    if (!grow_dev(&pair_dev_, &pair_dev_cap_, 3 * (size_t)n)) return false; // [a | b | out], grown on demand, kept
+    if (!d_guard_) { if (!d_guard_.grow(1)) return false; HIP_OK(hipMemsetAsync(d_guard_, 0, sizeof(int), st)); }
+    if (!pair_dev_.grow(3 * (size_t)n)) return false; // [a | b | out], grown on demand, kept
     int *hs = static_cast<int *>(pinned_stage(sizeof(int) * (3 * (size_t)n + 1)));
     if (!hs) return false;
     memcpy(hs, a, sizeof(int) * (size_t)n);
     memcpy(hs + n, b, sizeof(int) * (size_t)n);
     int *da = pair_dev_, *db = pair_dev_ + n;
-    float *dout = reinterpret_cast<float *>(pair_dev_ + 2 * (size_t)n);
+    float *dout = reinterpret_cast<float *>(pair_dev_.get() + 2 * (size_t)n);
     HIP_OK(hipMemcpyAsync(da, hs, sizeof(int) * 2 * (size_t)n, hipMemcpyHostToDevice, st));
     dim3 grid((unsigned)(((long long)n * 8 + 255) / 256)), block(256);
     with_metric(metric_, [&](auto m) {
@@ -2785,14 +2676,12 @@ bool Device::dist_pair_batch(const int *a, const int *b, int n, float *out)
 bool device_sqrt_rn(int device, const double *in, double *out, int n)
 {
     HIP_OK(hipSetDevice(device));
-    double *di = nullptr, *dout = nullptr;
-    HIP_OK(hipMalloc(&di, sizeof(double) * (size_t)n));
-    HIP_OK(hipMalloc(&dout, sizeof(double) * (size_t)n));
+    DevBuf<double> di, dout;
+    if (!di.grow((size_t)n) || !dout.grow((size_t)n)) return false;
     HIP_OK(hipMemcpy(di, in, sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(sqrt_rn_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, di, dout, n);
+    hipLaunchKernelGGL(sqrt_rn_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, di.get(), dout.get(), n);
     HIP_OK(hipGetLastError());
     HIP_OK(hipMemcpy(out, dout, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
-    (void)hipFree(di); (void)hipFree(dout);
     return true;
 }
 

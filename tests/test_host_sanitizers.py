@@ -1,7 +1,8 @@
 """CPU tier: the library's pure-host code and the oracle under AddressSanitizer + UndefinedBehaviorSanitizer (GPU ASan is
 not available on this pool; these parts need no GPU).  csrc/snapshot_io.h parses untrusted files: the malformed-input corpus
 of test_snapshot_codec.py plus a structure-aware fuzzer run through tools/host_sanitize/harness.cpp; csrc/host_structs.h
-and csrc/range_replay.h (heaps, the restated Span.Sort, System.Random, the range replay) through the same binary;
+and csrc/range_replay.h (heaps, the restated Span.Sort, System.Random, the range replay) through the same binary, and with
+them csrc/dev_buf.h, the owning holders of the device context's buffers, on malloc / free with allocations made to fail;
 oracle/hnsw_oracle.c through tools/host_sanitize/oracle_main.c.  Any sanitizer report aborts the run (non-zero exit)."""
 import shutil
 import subprocess
@@ -64,6 +65,18 @@ def test_snapshot_reader_under_structure_aware_fuzzing(harness, tmp_path):
 def test_host_structures_under_sanitizers(harness):
     for seed in (1, 2, 3):
         assert "no fault" in _run([harness, "structs", seed])
+
+
+def test_buffer_holders_under_sanitizers(harness):
+    """csrc/dev_buf.h on the host: the harness defines the allocation functions the header declares with malloc / free, counts
+    the live blocks and fails an allocation on request; each property it has checked is a line of its output."""
+    out = _run([harness, "buffers"])
+    for line in ("ok: grow below capacity allocates nothing", "ok: grow above capacity frees the old block first",
+                 "ok: grow(need, alloc) reports alloc", "ok: a failed allocation leaves the holder empty and the next grow succeeds",
+                 "ok: a borrowed alias is never freed", "ok: a move leaves the source empty",
+                 "ok: arrays and members of holders free exactly once"):
+        assert line in out, out
+    assert "live 0 at exit: no fault" in out, out
 
 
 def test_oracle_under_sanitizers(tmp_path):

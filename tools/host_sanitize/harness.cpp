@@ -1,10 +1,12 @@
 // tools/host_sanitize/harness.cpp -- the library's pure-host code under AddressSanitizer + UBSan (CPU only; GPU ASan is not
 // available on this pool): csrc/snapshot_io.h parses untrusted files, csrc/host_structs.h and csrc/range_replay.h hold the
-// restated BCL pieces.  Built and run by tests/test_host_sanitizers.py:
+// restated BCL pieces; csrc/dev_buf.h holds the owning buffer / event / stream holders of the device context, run here on
+// malloc / free through the allocation functions that header only declares.  Built and run by tests/test_host_sanitizers.py:
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -I hnswindex.net_amd/csrc harness.cpp
 //   harness parse <file>...            decode each file (errors are fine: only a sanitizer report is a failure)
 //   harness fuzz <seed file> <iterations> <rng seed>   structure-aware mutations of a valid snapshot
 //   harness structs <rng seed>         heaps, the restated Span.Sort (NaN / -0 / ties), System.Random, the range replay
+//   harness buffers                    the holders of dev_buf.h: growth, failed allocations, aliases, moves, arrays, members
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -13,6 +15,7 @@
 
 #include <unistd.h>
 
+#include "dev_buf.h"
 #include "host_structs.h"
 #include "range_replay.h"
 #include "snapshot_io.h"
@@ -218,6 +221,121 @@ static int structs(uint64_t seed)
     return 0;
 }
 
+// ---- dev_buf.h on the host: the functions it declares, on malloc / free, counting what lives and failing on request
+static struct HostAllocs {
+    long live = 0, peak = 0, allocs = 0, frees = 0, handles = 0;
+    long fail_at = 0; // the allocation (counted from the next one, 1-based) that fails; 0: none
+    bool error_set = false;
+    void *take(size_t bytes)
+    {
+        if (fail_at > 0 && --fail_at == 0) { error_set = true; return nullptr; }
+        ++allocs; ++live; peak = std::max(peak, live);
+        return std::malloc(bytes ? bytes : 1);
+    }
+    bool give(void *p) { ++frees; --live; std::free(p); return true; }
+} g_host;
+namespace hnsw {
+void *dev_mem_alloc(size_t bytes) { return g_host.take(bytes); }
+bool dev_mem_free(void *p) { return g_host.give(p); }
+void *pin_mem_alloc(size_t bytes, unsigned) { return g_host.take(bytes); }
+bool pin_mem_free(void *p) { return g_host.give(p); }
+void *dev_event_create(bool) { ++g_host.handles; return std::malloc(1); }
+void dev_event_destroy(void *e) { --g_host.handles; std::free(e); }
+void *dev_stream_create(bool) { ++g_host.handles; return std::malloc(1); }
+void dev_stream_destroy(void *s) { --g_host.handles; std::free(s); }
+}
+
+#define BUF_CHECK(cond) do { if (!(cond)) { std::printf("buffers: FAILED at line %d: %s\n", __LINE__, #cond); return 2; } } while (0)
+
+static int buffers()
+{
+    HostAllocs &h = g_host;
+    {   // growth: below capacity nothing is allocated; above it the old block goes before the new one is asked for
+        DevBuf<int> b;
+        BUF_CHECK(b.get() == nullptr && b.cap() == 0 && b.grow(0) && h.allocs == 0);
+        BUF_CHECK(b.grow(100) && b.cap() == 100 && b.get() != nullptr && h.allocs == 1 && h.live == 1);
+        for (int i = 0; i < 100; ++i) b[i] = i; // (the whole block is the holder's: a short allocation is a sanitizer report)
+        int *const first = b;
+        BUF_CHECK(b.grow(100) && b.grow(7) && b.grow(0) && h.allocs == 1 && b.get() == first);
+        std::printf("ok: grow below capacity allocates nothing\n");
+        h.peak = h.live;
+        BUF_CHECK(b.grow(101) && b.cap() == 101 && h.allocs == 2 && h.frees == 1 && h.live == 1 && h.peak == 1);
+        b[100] = 1;
+        std::printf("ok: grow above capacity frees the old block first\n");
+        // grow(need, alloc): tested against need, allocated and reported as alloc
+        PinBuf<char> p;
+        BUF_CHECK(p.grow(10, 20) && p.cap() == 20 && h.allocs == 3);
+        p[19] = 1;
+        BUF_CHECK(p.grow(20, 40) && p.cap() == 20 && h.allocs == 3);
+        BUF_CHECK(p.grow(21, 42) && p.cap() == 42 && h.allocs == 4 && h.live == 2);
+        p[41] = 1;
+        std::printf("ok: grow(need, alloc) reports alloc\n");
+        // a failed allocation: empty, zero capacity, false, error set; the next call asks again
+        h.fail_at = 1;
+        h.error_set = false;
+        BUF_CHECK(!b.grow(1000) && b.get() == nullptr && b.cap() == 0 && h.error_set && h.live == 1);
+        BUF_CHECK(b.grow(5) && b.cap() == 5 && b.get() != nullptr && h.live == 2);
+        b[4] = 1;
+        std::printf("ok: a failed allocation leaves the holder empty and the next grow succeeds\n");
+        BUF_CHECK(b.reset() && b.get() == nullptr && b.cap() == 0 && h.live == 1 && b.reset());
+    }
+    BUF_CHECK(h.live == 0);
+    {   // an alias is never freed, and is borrowed again after the owner regrew
+        DevBuf<float> owner, alias;
+        BUF_CHECK(owner.grow(8));
+        const long frees = h.frees;
+        alias.borrow(owner);
+        BUF_CHECK(alias.get() == owner.get() && alias.cap() == 8 && h.live == 1);
+        BUF_CHECK(owner.grow(16) && h.frees == frees + 1); // (the alias dangles now, as a view does until rebind)
+        alias.borrow(owner);
+        BUF_CHECK(alias.get() == owner.get() && alias.cap() == 16 && h.frees == frees + 1);
+        alias[15] = 1.0f;
+        {
+            DevBuf<float> second;
+            second.borrow(owner);
+            DevBuf<float> moved(std::move(second)); // an alias stays one when it moves
+            BUF_CHECK(second.get() == nullptr && moved.get() == owner.get());
+        }
+        BUF_CHECK(h.frees == frees + 1 && alias.reset() && h.frees == frees + 1 && h.live == 1);
+        alias.borrow(owner);
+    }   // (alias and owner both go: one free)
+    BUF_CHECK(h.live == 0);
+    std::printf("ok: a borrowed alias is never freed\n");
+    {   // a move leaves the source empty; move assignment releases what the target held
+        DevBuf<int> a, b;
+        BUF_CHECK(a.grow(4) && b.grow(6) && h.live == 2);
+        int *const pa = a;
+        DevBuf<int> c(std::move(a));
+        BUF_CHECK(a.get() == nullptr && a.cap() == 0 && c.get() == pa && c.cap() == 4 && h.live == 2);
+        b = std::move(c);
+        BUF_CHECK(c.get() == nullptr && c.cap() == 0 && b.get() == pa && b.cap() == 4 && h.live == 1);
+        BUF_CHECK(a.grow(3) && h.live == 2); // a moved-from holder is an empty one
+        std::swap(a, b);
+        BUF_CHECK(a.get() == pa && a.cap() == 4 && b.cap() == 3 && h.live == 2);
+    }
+    BUF_CHECK(h.live == 0);
+    std::printf("ok: a move leaves the source empty\n");
+    {   // arrays of holders, holders inside a struct, events and streams: each freed exactly once
+        struct Set { PinBuf<int> in, out; DevEvent done; bool busy = false; } sets[2];
+        DevBuf<int> arr[5];
+        DevEvent ev[3];
+        DevStream st;
+        const long allocs = h.allocs, frees = h.frees;
+        for (int i = 0; i < 5; ++i) BUF_CHECK(arr[i].grow((size_t)i + 1, 2 * ((size_t)i + 1)));
+        for (Set &s : sets) BUF_CHECK(s.in.grow(3) && s.out.grow(9) && s.done.create(true) && s.done.create(true));
+        for (DevEvent &e : ev) BUF_CHECK(e.create(false) && (void *)e != nullptr);
+        BUF_CHECK(st.create(true) && h.handles == 6 && h.allocs == allocs + 9 && h.live == 9);
+        BUF_CHECK(reset_all(arr[0], arr[1]) && h.live == 7 && h.frees == frees + 2);
+        st.reset();
+        st.reset();
+        BUF_CHECK(h.handles == 5 && (void *)st == nullptr && st.create(false) && h.handles == 6);
+    }
+    BUF_CHECK(h.live == 0 && h.handles == 0 && h.allocs == h.frees);
+    std::printf("ok: arrays and members of holders free exactly once\n");
+    std::printf("buffers: %ld blocks allocated and freed, live 0 at exit: no fault\n", h.allocs);
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
     if (argc >= 3 && !std::strcmp(argv[1], "parse")) {
@@ -230,6 +348,7 @@ int main(int argc, char **argv)
     }
     if (argc >= 5 && !std::strcmp(argv[1], "fuzz")) return fuzz(argv[2], std::atoi(argv[3]), (uint64_t)std::atoll(argv[4]));
     if (argc >= 3 && !std::strcmp(argv[1], "structs")) return structs((uint64_t)std::atoll(argv[2]));
-    std::printf("usage: harness parse <file>... | fuzz <seed file> <iterations> <rng seed> | structs <rng seed>\n");
+    if (argc >= 2 && !std::strcmp(argv[1], "buffers")) return buffers();
+    std::printf("usage: harness parse <file>... | fuzz <seed file> <iterations> <rng seed> | structs <rng seed> | buffers\n");
     return 64;
 }
