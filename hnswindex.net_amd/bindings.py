@@ -119,6 +119,12 @@ lib.hnsw_mi355x_knn_query_filtered.restype = ct.c_int
 lib.hnsw_mi355x_knn_query_filtered.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_int, ct.c_int, _U32, ct.c_longlong, _I, _F]
 lib.hnsw_mi355x_exact_knn_query.restype = ct.c_int
 lib.hnsw_mi355x_exact_knn_query.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_int, ct.c_int, _U32, ct.c_longlong, _I, _F]
+_EXACT_RANGE_INFO = ("device_sorted", "host_sorted", "repeated_rounds", "results")   # hnswdev_exact_range_info's out[0 .. 3]
+lib.hnsw_mi355x_exact_range_query.restype = ct.c_int
+lib.hnsw_mi355x_exact_range_query.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_int, ct.c_float, _U32, ct.c_longlong, ct.POINTER(ct.c_void_p),
+                                              ct.POINTER(ct.c_void_p), _I]
+lib.hnsw_mi355x_exact_range_info.restype = ct.c_int
+lib.hnsw_mi355x_exact_range_info.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
 lib.hnsw_mi355x_range_query_filtered.restype = ct.c_int
 lib.hnsw_mi355x_range_query_filtered.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_int, ct.c_float, _U32, ct.c_longlong, ct.POINTER(ct.c_void_p),
                                                  ct.POINTER(ct.c_void_p), ct.POINTER(ct.c_int)]
@@ -190,6 +196,12 @@ lib.hnswdev_exact_knn.restype = ct.c_int
 lib.hnswdev_exact_knn.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_longlong, ct.c_int, _U32, ct.c_longlong, _I, _F]
 lib.hnswdev_range_search_filtered.restype = ct.c_int
 lib.hnswdev_range_search_filtered.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_int, ct.c_float, _U32, ct.c_longlong, _I, _I]
+lib.hnswdev_exact_range.restype = ct.c_int
+lib.hnswdev_exact_range.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_longlong, ct.c_float, _U32, ct.c_longlong, _I]
+lib.hnswdev_exact_range_results.restype = ct.c_int
+lib.hnswdev_exact_range_results.argtypes = [ct.c_void_p, _I, _F]
+lib.hnswdev_exact_range_info.restype = ct.c_int
+lib.hnswdev_exact_range_info.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
 lib.hnswdev_range_results.restype = ct.c_int
 lib.hnswdev_range_results.argtypes = [ct.c_void_p, _I, _F]
 lib.hnswdev_knn_search_at_layer.restype = ct.c_int
@@ -488,6 +500,42 @@ class Index:
         if status < 0:
             raise RuntimeError(last_error())
         return ids, dists
+
+    def exact_range_query(self, queries: npt.ArrayLike, radius: float,
+                          allowed=None) -> Tuple[List[npt.NDArray[np.int32]], List[npt.NDArray[np.float32]]]:
+        """Per query every live (and, with `allowed`, allowed) id whose distance is <= radius, ascending by (distance, id), from
+        the flat scan on the device (hnsw_mi355x_exact_range_query): exact, independent of the graph, of any length.  allowed: as
+        for knn_query.  The shape range_query returns."""
+        q = _as_2d_f32(queries, self.dim)
+        n = int(q.shape[0])
+        ids_pp = (ct.c_void_p * n)()
+        dists_pp = (ct.c_void_p * n)()
+        counts = (ct.c_int * n)()
+        words, nbits = allow_bits(allowed) if allowed is not None else (None, 0)
+        words, wp = _words_arg(words) if allowed is not None else (None, None)
+        status = lib.hnsw_mi355x_exact_range_query(self._h, q.ctypes.data_as(_F), n, self.dim, radius, wp, nbits, ids_pp, dists_pp, counts)
+        if status < 0:
+            raise RuntimeError(last_error())
+        ids, dists = [], []
+        try:
+            for i in range(n):
+                m = counts[i]
+                if m == 0:
+                    ids.append(np.empty(0, dtype=np.int32))
+                    dists.append(np.empty(0, dtype=np.float32))
+                    continue
+                ids.append(np.ctypeslib.as_array(ct.cast(ids_pp[i], _I), shape=(m,)).copy())
+                dists.append(np.ctypeslib.as_array(ct.cast(dists_pp[i], _F), shape=(m,)).copy())
+        finally:
+            lib.hnsw_free_results(ids_pp, dists_pp, n)
+        return ids, dists
+
+    def exact_range_info(self) -> dict:
+        """Counters of exact_range_query since reset_stats (hnsw_mi355x_exact_range_info)."""
+        out = (ct.c_uint64 * 4)()
+        if self._h:
+            lib.hnsw_mi355x_exact_range_info(self._h, out)
+        return dict(zip(_EXACT_RANGE_INFO, (int(v) for v in out)))
 
     def range_query(self, queries: npt.ArrayLike, radius: float,
                     allowed=None, layer: int = 0) -> Tuple[List[npt.NDArray[np.int32]], List[npt.NDArray[np.float32]]]:
@@ -788,6 +836,29 @@ class DeviceBackend:
         self._check(lib.hnswdev_exact_knn(self._ctx, q.ctypes.data_as(_F), n, (1 << 62) if n_rows is None else int(n_rows), int(k), wp, nbits,
                                           ids.ctypes.data_as(_I), d.ctypes.data_as(_F)))
         return ids, d
+
+    def exact_range(self, queries, radius: float, n_rows=None, allowed=None):
+        """hnswdev_exact_range: (list of ids, list of dists), per query every uploaded row of [0, n_rows) (None: all) that `allowed`
+        allows with distance <= radius, ascending by (distance, id).  A flat scan: no graph."""
+        q = _as_2d_f32(queries, self.dim)
+        n = q.shape[0]
+        counts = np.zeros(n, dtype=np.int32)
+        words, nbits = allow_bits(allowed) if allowed is not None else (None, 0)
+        words, wp = _words_arg(words) if allowed is not None else (None, None)
+        self._check(lib.hnswdev_exact_range(self._ctx, q.ctypes.data_as(_F), n, (1 << 62) if n_rows is None else int(n_rows), float(radius), wp, nbits,
+                                            counts.ctypes.data_as(_I)))
+        total = int(counts.sum(dtype=np.int64))
+        ids = np.empty(max(total, 1), dtype=np.int32)
+        d = np.empty(max(total, 1), dtype=np.float32)
+        self._check(lib.hnswdev_exact_range_results(self._ctx, ids.ctypes.data_as(_I), d.ctypes.data_as(_F)))
+        cuts = np.cumsum(counts, dtype=np.int64)[:-1]
+        return np.split(ids[:total], cuts), np.split(d[:total], cuts)
+
+    def exact_range_info(self) -> dict:
+        """Counters of exact_range since reset_stats (hnswdev_exact_range_info)."""
+        out = (ct.c_uint64 * 4)()
+        self._check(lib.hnswdev_exact_range_info(self._ctx, out))
+        return dict(zip(_EXACT_RANGE_INFO, (int(v) for v in out)))
 
     def multilayer_search(self, queries, entry_point: int, k: int, max_layer=None, min_layer: int = 0, layers_cap=None):
         """hnswdev_multilayer_search: (ids, dists, flags), ids / dists of shape [nq, nlayers, k - 1] as Index.multilayer_knn_query;

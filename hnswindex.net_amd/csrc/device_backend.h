@@ -329,6 +329,15 @@ public:
     // set (nq of its rows); otherwise the queries are staged by set_queries' code into a buffer of the scan's own and the
     // resident set stays what it was.  1 <= k <= 1024.  Synchronous.
     bool exact_knn(const float *queries, int nq, long long n_rows, int k, const uint32_t *allow_bits, long long nbits, int *out_ids, float *out_d);
+    // hnswdev_exact_range: exact_knn's candidates, queries and distances; per query EVERY candidate with
+    // distance <= range (the float compare), ascending by (distance, id), of any number.  out_counts[i]: query i's; the lists stay
+    // in the context, concatenated in query order, until the next exact_range and are copied out by exact_range_results (the
+    // traversal's range_results has buffers of its own).  false: no results are kept and every count is 0.  Synchronous.
+    bool exact_range(const float *queries, int nq, long long n_rows, float range, const uint32_t *allow_bits, long long nbits, int *out_counts);
+    bool exact_range_results(int *out_ids, float *out_d);
+    size_t exact_range_total() const { return xr_ids_.size(); }
+    // lists of >= 2 entries ordered on the device, lists ordered on the host, rounds repeated with exact capacities, results returned
+    void exact_range_info(uint64_t out[4]) const { for (int i = 0; i < 4; ++i) out[i] = xr_info_[i]; }
 
     void set_profiling(bool on) { profiling_ = on; }
 
@@ -426,6 +435,17 @@ private:
     DevBuf<unsigned long long> x_evals_; // ... (query, row) pairs the scan kernel measured, counted on the device
     DevBuf<float> x_queries_;           // ... its own query set (set_queries writes it while it stands in for d_queries_)
     DevBuf<double> x_q_sn_;
+    bool exact_queries(const char *who, const float *queries, int nq, const float **d_q, const double **d_qsn);
+    bool exact_id_list(const uint32_t *allow_bits, long long n_allow, long long *m);
+    bool exact_copy_out(void *dst, const void *src, size_t bytes);
+    bool exact_range_run(const float *queries, int nq, long long n_rows, float range, const uint32_t *allow_bits, long long nbits, int *out_counts);
+    DevBuf<unsigned long long> x_rarena_; // exact_range: the round's keys, a segment per query: at most 1 GiB, grown on demand and kept
+    DevBuf<long long> x_rseg_, x_rooff_;  // ... per query of a round: where its segment starts (one more: the end), where its ordered list goes
+    DevBuf<unsigned> x_rcnt_;             // ... keys within the range
+    DevBuf<int> x_rout_;                  // ... the lists ordered on the device: [ids | distances]
+    std::vector<int> xr_ids_;             // ... the call's results until the next call (exact_range_results)
+    std::vector<float> xr_d_;
+    uint64_t xr_info_[4] = {0, 0, 0, 0};
     DevBuf<SearchHit> s_arena_; // range search: the launch's results, packed
     DevBuf<unsigned long long> s_roff_, s_arena_used_; // s_roff_ stands for the capacity of range_batch's per-job arrays
     DevBuf<int> s_rentry_;

@@ -911,6 +911,7 @@ void Device::reset_stats()
     uint64_t rb = stats_.row_bytes;
     stats_ = hnswdev_stats{};
     stats_.row_bytes = rb;
+    for (uint64_t &v : xr_info_) v = 0;
 #ifdef EXP_PHASE_CLOCKS
     (void)hipDeviceSynchronize();
     phase_report("reset_stats");
@@ -2480,6 +2481,57 @@ static ExactPlan exact_plan(int nq, long long m, int k, int pitch, int num_cu)
     return p;
 }
 
+// The queries of a flat scan: the resident set, or the scan's own -- uploaded by set_queries (the one staging path: pinned copy,
+// int8 quantisation, cosine norms) while the scan's buffers stand in for the resident set's, which is then put back untouched.
+bool Device::exact_queries(const char *who, const float *queries, int nq, const float **d_q, const double **d_qsn)
+{
+    *d_q = d_queries_;
+    *d_qsn = d_q_sn_;
+    if (queries) {
+        if (tail_.n > 0) { set_dev_error(std::string(who) + ": a streamed query set is still being uploaded"); return false; }
+        std::swap(d_queries_, x_queries_); std::swap(d_q_sn_, x_q_sn_);
+        const long long kept = n_queries_;
+        const bool ok = set_queries(queries, nq);
+        std::swap(d_queries_, x_queries_); std::swap(d_q_sn_, x_q_sn_);
+        n_queries_ = kept;
+        if (!ok) return false;
+        *d_q = x_queries_; *d_qsn = x_q_sn_;
+    } else if (nq > n_queries_ || tail_.n > 0) {
+        set_dev_error(std::string(who) + ": queries == NULL needs a resident query set of at least nq rows (hnswdev_set_queries)");
+        return false;
+    }
+    return true;
+}
+
+// The id list of a flat scan in x_ids_, *m entries: the identity without a bitset (x_ids_ is not used: *m = n_allow); otherwise
+// the masked words go up from pinned memory with the bit counts in front of each block of them (counted while they are copied),
+// and exact_compact_kernel writes the ascending ids.  The stream is idle and the pinned stage free when this returns.
+bool Device::exact_id_list(const uint32_t *allow_bits, long long n_allow, long long *m_out)
+{
+    *m_out = n_allow;
+    if (!allow_bits) return true;
+    hipStream_t st = S(stream_);
+    const size_t words = (size_t)((n_allow + 31) / 32), blocks = (words + kExactCompactWords - 1) / kExactCompactWords;
+    char *hs = static_cast<char *>(pinned_stage(8 * blocks + 4 * words));
+    if (!hs) return false;
+    long long *h_off = reinterpret_cast<long long *>(hs);
+    unsigned *h_words = reinterpret_cast<unsigned *>(hs + 8 * blocks);
+    long long m = 0;
+    for (size_t w = 0; w < words; ++w) {
+        if (w % kExactCompactWords == 0) h_off[w / kExactCompactWords] = m;
+        const unsigned v = allow_bits[w] & ((long long)(w + 1) * 32 <= n_allow ? ~0u : (1u << (n_allow & 31)) - 1u);
+        h_words[w] = v;
+        m += __builtin_popcount(v);
+    }
+    if (!s_allow_.grow(words) || !x_boff_.grow(blocks) || !x_ids_.grow((size_t)m)) return false;
+    HIP_OK(hipMemcpyAsync(x_boff_, h_off, 8 * blocks, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(s_allow_, h_words, 4 * words, hipMemcpyHostToDevice, st));
+    HIP_OK(exact_compact_launch(s_allow_, (long long)words, x_boff_, x_ids_, st));
+    HIP_OK(hipStreamSynchronize(st)); // the pinned stage is used again by the caller
+    *m_out = m;
+    return true;
+}
+
 bool Device::exact_knn(const float *queries, int nq, long long n_rows, int k, const uint32_t *allow_bits, long long nbits, int *out_ids, float *out_d)
 {
     if (nq <= 0) return true;
@@ -2492,44 +2544,11 @@ bool Device::exact_knn(const float *queries, int nq, long long n_rows, int k, co
         pad_results(out_ids, out_d, (size_t)nq * (size_t)k);
         return true;
     }
-    // The queries: the resident set, or the scan's own -- uploaded by set_queries (the one staging path: pinned copy, int8
-    // quantisation, cosine norms) while the scan's buffers stand in for the resident set's, which is then put back untouched.
-    const float *d_q = d_queries_;
-    const double *d_qsn = d_q_sn_;
-    if (queries) {
-        if (tail_.n > 0) { set_dev_error("exact_knn: a streamed query set is still being uploaded"); return false; }
-        std::swap(d_queries_, x_queries_); std::swap(d_q_sn_, x_q_sn_);
-        const long long kept = n_queries_;
-        const bool ok = set_queries(queries, nq);
-        std::swap(d_queries_, x_queries_); std::swap(d_q_sn_, x_q_sn_);
-        n_queries_ = kept;
-        if (!ok) return false;
-        d_q = x_queries_; d_qsn = x_q_sn_;
-    } else if (nq > n_queries_ || tail_.n > 0) { set_dev_error("exact_knn: queries == NULL needs a resident query set of at least nq rows (hnswdev_set_queries)"); return false; }
-    if (!bind()) return false;
+    const float *d_q;
+    const double *d_qsn;
+    long long m;
+    if (!exact_queries("exact_knn", queries, nq, &d_q, &d_qsn) || !bind() || !exact_id_list(allow_bits, n_allow, &m)) return false;
     hipStream_t st = S(stream_);
-    // the id list: the identity without a bitset; otherwise the masked words go up from pinned memory with the bit counts in front
-    // of each block of them (counted while they are copied), and exact_compact_kernel writes the ascending ids
-    long long m = n_allow;
-    const size_t words = allow_bits ? (size_t)((n_allow + 31) / 32) : 0, blocks = (words + kExactCompactWords - 1) / kExactCompactWords;
-    if (allow_bits) {
-        char *hs = static_cast<char *>(pinned_stage(8 * blocks + 4 * words));
-        if (!hs) return false;
-        long long *h_off = reinterpret_cast<long long *>(hs);
-        unsigned *h_words = reinterpret_cast<unsigned *>(hs + 8 * blocks);
-        m = 0;
-        for (size_t w = 0; w < words; ++w) {
-            if (w % kExactCompactWords == 0) h_off[w / kExactCompactWords] = m;
-            const unsigned v = allow_bits[w] & ((long long)(w + 1) * 32 <= n_allow ? ~0u : (1u << (n_allow & 31)) - 1u);
-            h_words[w] = v;
-            m += __builtin_popcount(v);
-        }
-        if (!s_allow_.grow(words) || !x_boff_.grow(blocks) || !x_ids_.grow((size_t)m)) return false;
-        HIP_OK(hipMemcpyAsync(x_boff_, h_off, 8 * blocks, hipMemcpyHostToDevice, st));
-        HIP_OK(hipMemcpyAsync(s_allow_, h_words, 4 * words, hipMemcpyHostToDevice, st));
-        HIP_OK(exact_compact_launch(s_allow_, (long long)words, x_boff_, x_ids_, st));
-        HIP_OK(hipStreamSynchronize(st)); // the pinned stage is used again below
-    }
     const ExactPlan p = exact_plan(nq, m, k, pitch_, num_cu_);
     if (p.lds > 64 * 1024) { set_dev_error("exact_knn: tile exceeds the LDS budget"); return false; }
     if (!x_lists_.grow((size_t)p.round * p.n_chunks * k) || !x_out_.grow(2 * (size_t)p.round * k)) return false;
@@ -2572,6 +2591,214 @@ bool Device::exact_knn(const float *queries, int nq, long long n_rows, int k, co
             stats_.exact_kernel_ms += ms; stats_.exact_timed_launches += 1; stats_.exact_timed_evals += *h_ev;
         }
     }
+    return true;
+}
+
+// ---- hnswdev_exact_range: the same scan with the range sink -------------------------------------------
+// Pass A scans a round of queries with one capacity for each (the arena's entries / the round's queries, or less: the picker
+// stops at kExactRangePickCap, `exact_range_cap` forces it).  The counts come back exact; where one exceeds its capacity the round
+// is cut into pieces whose counts fit the arena and each piece is scanned again with segments of exactly its counts (pass B).
+// Lists of up to `exact_range_sort` (4096) keys are ordered by exact_range_sort_kernel, longer ones cross as keys and are ordered
+// here: the keys are unique, so the order is the same.
+constexpr long long kExactRangeArena = 1LL << 27;  // keys: 1 GiB
+constexpr long long kExactRangePickCap = 8192;     // pass A's capacity per query unless forced (unmeasured: DESIGN.md 3.16)
+constexpr size_t kExactRangePiece = 1u << 21;      // entries per copy through the pinned stage
+
+static inline float exact_host_key_dist(unsigned long long key) // exact_key_dist (dk_exact.h) on the host
+{
+    const uint32_t dk = (uint32_t)(key >> 32), u = dk == 0xffffffffu ? 0x7fc00000u : (dk & 0x80000000u) ? (dk & 0x7fffffffu) : ~dk;
+    float f;
+    memcpy(&f, &u, 4);
+    return f;
+}
+
+// device -> host through the pinned stage, in pieces
+bool Device::exact_copy_out(void *dst, const void *src, size_t bytes)
+{
+    hipStream_t st = S(stream_);
+    const size_t piece = kExactRangePiece * 8;
+    for (size_t o = 0; o < bytes; o += piece) {
+        const size_t n = std::min(piece, bytes - o);
+        void *hs = pinned_stage(n);
+        if (!hs) return false;
+        HIP_OK(hipMemcpyAsync(hs, static_cast<const char *>(src) + o, n, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+        memcpy(static_cast<char *>(dst) + o, hs, n);
+    }
+    return true;
+}
+
+bool Device::exact_range(const float *queries, int nq, long long n_rows, float range, const uint32_t *allow_bits, long long nbits, int *out_counts)
+{
+    if (exact_range_run(queries, nq, n_rows, range, allow_bits, nbits, out_counts)) return true;
+    xr_ids_.clear(); // a failed call keeps nothing
+    xr_d_.clear();
+    for (int i = 0; out_counts && i < nq; ++i) out_counts[i] = 0;
+    return false;
+}
+
+bool Device::exact_range_run(const float *queries, int nq, long long n_rows, float range, const uint32_t *allow_bits, long long nbits, int *out_counts)
+{
+    xr_ids_.clear();
+    xr_d_.clear();
+    if (nq <= 0) return true;
+    if (!allow_bits) nbits = 0; // no filter: nbits means nothing, whatever the caller left in it
+    if (!out_counts || n_rows < 0 || nbits < 0) { set_dev_error("exact_range: bad argument"); return false; }
+    for (int i = 0; i < nq; ++i) out_counts[i] = 0;
+    // rows that exist: a row beyond what was uploaded is never dereferenced, whatever n_rows and the bitset say
+    const long long n = std::min(n_rows, n_rows_hw_), n_allow = allow_bits ? std::min(nbits, n) : n;
+    if (n_allow <= 0 || (allow_bits && !allows_any(allow_bits, nbits, n))) return true; // nothing to measure: empty lists, no launch
+    const float *d_q;
+    const double *d_qsn;
+    long long m;
+    if (!exact_queries("exact_range", queries, nq, &d_q, &d_qsn) || !bind() || !exact_id_list(allow_bits, n_allow, &m)) return false;
+    hipStream_t st = S(stream_);
+    ExactPlan p = exact_plan(std::min(nq, 65536), m, 1, pitch_, num_cu_); // tile and chunks as for lists of one key: this sink keeps none
+    p.lds = exact_scan_lds(p.qtile, p.piece, pitch_, 0);
+    if (p.lds > 64 * 1024) { set_dev_error("exact_range: tile exceeds the LDS budget"); return false; }
+    const int d_arena = diag("exact_range_arena", 0), d_cap = diag("exact_range_cap", 0), d_sort = diag("exact_range_sort", 0);
+    const long long arena_max = d_arena > 0 ? d_arena : kExactRangeArena;
+    const int sort_max = d_sort > 0 ? std::min(d_sort, kExactRangeSortMax) : kExactRangeSortMax;
+    const long long cap = std::min<long long>({d_cap > 0 ? (long long)d_cap : kExactRangePickCap, m, arena_max});
+    const long long round = std::max<long long>(1, std::min<long long>({(long long)nq, 65536LL, arena_max / cap}));
+    if (!x_rcnt_.grow((size_t)round) || !x_rseg_.grow((size_t)round + 1) || !x_rooff_.grow((size_t)round) || !x_evals_.grow(1)) return false;
+    if (!ev0_.create(true) || !ev1_.create(true)) return false;
+    std::vector<long long> seg((size_t)round + 1), ooff((size_t)round);
+    std::vector<unsigned> cnt((size_t)round), cnt_b;
+    std::vector<unsigned long long> keys;
+    std::vector<int> t_ids;
+    std::vector<float> t_d;
+
+    // one scan of queries [q0, q0 + nr) with the segments seg[0 .. nr]: the counts into c[0 .. nr)
+    const auto scan = [&](long long q0, int nr, unsigned *c) -> bool {
+        if (!x_rarena_.grow((size_t)std::max<long long>(seg[(size_t)nr], 1))) return false;
+        char *hs = static_cast<char *>(pinned_stage(8 * ((size_t)nr + 1) + 4 * (size_t)nr + 8));
+        if (!hs) return false;
+        unsigned long long *h_ev = reinterpret_cast<unsigned long long *>(hs);
+        long long *h_seg = reinterpret_cast<long long *>(hs + 8);
+        unsigned *h_cnt = reinterpret_cast<unsigned *>(hs + 8 + 8 * ((size_t)nr + 1));
+        memcpy(h_seg, seg.data(), 8 * ((size_t)nr + 1));
+        ExactScanArgs a;
+        a.rows = d_rows_; a.row_sn = d_row_sn_;
+        a.queries = d_q + (size_t)q0 * pitch_;
+        a.q_sn = d_qsn ? d_qsn + q0 : nullptr;
+        a.dim = pitch_; a.ids = allow_bits ? x_ids_ : nullptr; a.m = m; a.chunk = p.chunk; a.nq = nr; a.qtile = p.qtile; a.piece = p.piece; a.k = 0;
+        a.lists = nullptr; a.n_chunks = p.n_chunks; a.evals = x_evals_;
+        ExactRange sink;
+        sink.range = range; sink.counts = x_rcnt_; sink.seg_off = x_rseg_; sink.arena = x_rarena_;
+        const unsigned tiles = (unsigned)((nr + p.qtile - 1) / p.qtile);
+        const bool timed = profiling_;
+        HIP_OK(hipMemcpyAsync(x_rseg_, h_seg, 8 * ((size_t)nr + 1), hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemsetAsync(x_rcnt_, 0, 4 * (size_t)nr, st));
+        HIP_OK(hipMemsetAsync(x_evals_, 0, sizeof(unsigned long long), st));
+        if (timed) HIP_OK(hipEventRecord(E(ev0_), st));
+        hipError_t e = hipSuccess;
+        with_metric(metric_, [&](auto mt) { e = exact_range_scan_launch<mt>(a, sink, tiles, p.lds, st); });
+        HIP_OK(e);
+        if (timed) HIP_OK(hipEventRecord(E(ev1_), st));
+        HIP_OK(hipMemcpyAsync(h_cnt, x_rcnt_, 4 * (size_t)nr, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(h_ev, x_evals_, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+        memcpy(c, h_cnt, 4 * (size_t)nr);
+        // (both sinks are the flat scan: they count in the same family, and a repeated pass counts its pairs again)
+        stats_.exact_launches += 1; stats_.exact_evals += *h_ev;
+        if (timed) {
+            float ms = 0.f;
+            HIP_OK(hipEventElapsedTime(&ms, E(ev0_), E(ev1_)));
+            stats_.exact_kernel_ms += ms; stats_.exact_timed_launches += 1; stats_.exact_timed_evals += *h_ev;
+        }
+        return true;
+    };
+
+    // the lists of queries [q0, q0 + nr), every one inside its segment seg[i] .. : ordered and appended to the call's results
+    const auto finish = [&](long long q0, int nr, const unsigned *c) -> bool {
+        size_t total = 0, on_dev = 0;
+        int n_dev = 0;
+        for (int i = 0; i < nr; ++i) {
+            ooff[(size_t)i] = (long long)on_dev;
+            total += c[i];
+            if (c[i] > 0 && c[i] <= (unsigned)sort_max) { on_dev += c[i]; ++n_dev; }
+        }
+        const size_t base = xr_ids_.size();
+        xr_ids_.resize(base + total);
+        xr_d_.resize(base + total);
+        if (n_dev > 0) {
+            if (!x_rout_.grow(2 * on_dev)) return false;
+            char *hs = static_cast<char *>(pinned_stage(8 * (size_t)nr));
+            if (!hs) return false;
+            memcpy(hs, ooff.data(), 8 * (size_t)nr);
+            HIP_OK(hipMemcpyAsync(x_rooff_, hs, 8 * (size_t)nr, hipMemcpyHostToDevice, st));
+            ExactRangeSortArgs sa;
+            sa.arena = x_rarena_; sa.seg_off = x_rseg_; sa.counts = x_rcnt_; sa.out_off = x_rooff_;
+            sa.out_ids = x_rout_; sa.out_d = reinterpret_cast<float *>(x_rout_.get() + on_dev); sa.sort_max = sort_max;
+            HIP_OK(exact_range_sort_launch(sa, nr, st));
+            HIP_OK(hipStreamSynchronize(st)); // (the pinned stage is used again by the copies)
+            t_ids.resize(on_dev);
+            t_d.resize(on_dev);
+            if (!exact_copy_out(t_ids.data(), sa.out_ids, 4 * on_dev) || !exact_copy_out(t_d.data(), sa.out_d, 4 * on_dev)) return false;
+        }
+        size_t at = base;
+        for (int i = 0; i < nr; ++i) {
+            const size_t ci = c[i];
+            if (ci > 0 && ci <= (size_t)sort_max) {
+                memcpy(xr_ids_.data() + at, t_ids.data() + ooff[(size_t)i], 4 * ci);
+                memcpy(xr_d_.data() + at, t_d.data() + ooff[(size_t)i], 4 * ci);
+                if (ci >= 2) xr_info_[0] += 1;
+            } else if (ci > 0) {
+                keys.resize(ci);
+                if (!exact_copy_out(keys.data(), x_rarena_.get() + seg[(size_t)i], 8 * ci)) return false;
+                std::sort(keys.begin(), keys.end());
+                for (size_t j = 0; j < ci; ++j) { xr_ids_[at + j] = (int)(uint32_t)keys[j]; xr_d_[at + j] = exact_host_key_dist(keys[j]); }
+                xr_info_[1] += 1;
+            }
+            out_counts[q0 + i] = (int)ci;
+            at += ci;
+        }
+        xr_info_[3] += total;
+        return true;
+    };
+
+    for (long long off = 0; off < nq; off += round) {
+        const int nr = (int)std::min<long long>(round, nq - off);
+        for (int i = 0; i <= nr; ++i) seg[(size_t)i] = (long long)i * cap;
+        if (!scan(off, nr, cnt.data())) return false;
+        bool fits = true;
+        for (int i = 0; i < nr; ++i) fits = fits && cnt[(size_t)i] <= (unsigned long long)cap;
+        if (fits) {
+            if (!finish(off, nr, cnt.data())) return false;
+            continue;
+        }
+        // pass B: pieces of the round whose exact counts fit the arena, each with segments of exactly its counts
+        cnt_b.resize((size_t)nr);
+        for (int s0 = 0; s0 < nr;) {
+            int s1 = s0;
+            seg[0] = 0;
+            while (s1 < nr && seg[(size_t)(s1 - s0)] + (long long)cnt[(size_t)s1] <= arena_max) {
+                seg[(size_t)(s1 - s0) + 1] = seg[(size_t)(s1 - s0)] + (long long)cnt[(size_t)s1];
+                ++s1;
+            }
+            if (s1 == s0) {
+                set_dev_error("exact_range: a query has " + std::to_string(cnt[(size_t)s0]) + " results within the range, above the arena's limit of " +
+                              std::to_string(arena_max) + " entries per call round");
+                return false;
+            }
+            xr_info_[2] += 1;
+            if (!scan(off + s0, s1 - s0, cnt_b.data())) return false;
+            for (int i = s0; i < s1; ++i)
+                if (cnt_b[(size_t)(i - s0)] != cnt[(size_t)i]) { set_dev_error("exact_range: the repeated scan counted differently"); return false; }
+            if (!finish(off + s0, s1 - s0, cnt_b.data())) return false;
+            s0 = s1;
+        }
+    }
+    return true;
+}
+
+bool Device::exact_range_results(int *out_ids, float *out_d)
+{
+    if (xr_ids_.empty()) return true;
+    if (!out_ids || !out_d) { set_dev_error("exact_range_results: null argument"); return false; }
+    memcpy(out_ids, xr_ids_.data(), 4 * xr_ids_.size());
+    memcpy(out_d, xr_d_.data(), 4 * xr_d_.size());
     return true;
 }
 
@@ -2793,6 +3020,20 @@ DEV_API int hnswdev_exact_knn(void *ctx, const float *queries, int nq, long long
 {
     CTX_OR_FAIL();
     return d->exact_knn(queries, nq, n_rows, k, allow_bits, nbits, out_ids, out_dists) ? 0 : -1;
+}
+DEV_API int hnswdev_exact_range(void *ctx, const float *queries, int nq, long long n_rows, float range, const uint32_t *allow_bits, long long nbits,
+                                int *out_counts)
+{
+    CTX_OR_FAIL();
+    return d->exact_range(queries, nq, n_rows, range, allow_bits, nbits, out_counts) ? 0 : -1;
+}
+DEV_API int hnswdev_exact_range_results(void *ctx, int *out_ids, float *out_dists) { CTX_OR_FAIL(); return d->exact_range_results(out_ids, out_dists) ? 0 : -1; }
+DEV_API int hnswdev_exact_range_info(void *ctx, uint64_t out[4])
+{
+    CTX_OR_FAIL();
+    if (!out) return -1;
+    d->exact_range_info(out);
+    return 0;
 }
 DEV_API int hnswdev_range_results(void *ctx, int *out_ids, float *out_dists) { CTX_OR_FAIL(); return d->range_results(out_ids, out_dists) ? 0 : -1; }
 DEV_API int hnswdev_sync(void *ctx) { CTX_OR_FAIL(); return d->sync() ? 0 : -1; }

@@ -10,6 +10,7 @@
 //       lat [1]  novis [2]  novis_insert [1]  sorted_top [1]  shadow [1]  overlap [1]  mfma [1]  vis_hash [-1 = by graph size]
 //       vis_hash_cap [0]  cand_cap [0]  spill_cap [-1]  link_plan [1]  concurrent_queries [1]  stream_queries [1]
 //       xw_dry [1]  xw_stage [1]  trace [0]  lean [1]  exact_chunk [0 = the picker's]  exact_qtile [0 = the picker's]
+//       exact_range_cap [0 = the picker's]  exact_range_sort [0 = 4096]  exact_range_arena [0 = 1 GiB of keys]
 #pragma once
 #include <cstdlib>
 #include <cstring>

@@ -4,6 +4,10 @@
 //   exact_compact_kernel   bitset (allow AND live, masked on the host) -> ascending id list
 //   exact_scan_kernel<M>   a tile of queries x a chunk of the id list per block; per (query, chunk) a sorted list of k keys in LDS
 //   exact_merge_kernel     one wave per query: the chunks' lists -> the final k, ids and distances in the output layout
+// and, behind the same measured pairs, hnswdev_exact_range: every key within a radius, of any number.  The scan
+// kernel takes its sink as a type -- ExactTopK, the lists above, or ExactRange:
+//   exact_scan_kernel<M, ExactRange>  keys with d <= range go from the pending lists to the query's segment of an arena; the count per query is exact
+//   exact_range_sort_kernel           one block per query: a segment of up to kExactRangeSortMax keys ordered in LDS -> ids and distances
 // The kernels are compiled in the exact_<metric> units (exact_unit.hip, HNSW_EXACT_UNIT) and reached through the launchers declared here, so
 // that device_backend.hip holds none of their code.
 #pragma once
@@ -21,6 +25,7 @@ constexpr int kExactIterRows = (kExactThreads / 8) * kExactRR; // rows a block m
 constexpr int kExactMaxK = 1024;
 constexpr int kExactMaxQTile = 32;
 constexpr int kExactCompactWords = 256; // bitset words per block of exact_compact_kernel (one per thread)
+constexpr int kExactRangeSortMax = 4096; // keys exact_range_sort_kernel orders in LDS (32 KB); longer lists are ordered on the host
 
 struct ExactScanArgs {
     const float *rows;      // stored rows (f32 rows, int8 records, f16 records)
@@ -40,6 +45,31 @@ struct ExactScanArgs {
     unsigned long long *evals; // out: (query, row) pairs measured, added up over the blocks
 };
 
+// The sinks of exact_scan_kernel.  ExactTopK: the k smallest keys per (query, chunk), in ExactScanArgs::lists.  ExactRange: every
+// key whose distance is <= range (the IEEE compare: a NaN distance or a NaN range admits nothing).  Query q of the round owns
+// arena[seg_off[q], seg_off[q + 1]); counts[q] (zeroed before the launch) ends as the number of keys within range, whether they
+// fitted the segment or not -- keys past the segment's end are dropped, in no particular order.  (ExactScanArgs::k is 0 and lists
+// unused for this sink.)
+struct ExactTopK {
+    static constexpr bool kRange = false;
+};
+struct ExactRange {
+    static constexpr bool kRange = true;
+    float range;
+    unsigned *counts;              // [nq]
+    const long long *seg_off;      // [nq + 1]
+    unsigned long long *arena;
+};
+struct ExactRangeSortArgs {
+    const unsigned long long *arena;
+    const long long *seg_off;      // [nq + 1]: as the scan's
+    const unsigned *counts;        // [nq]
+    const long long *out_off;      // [nq]: where query q's list goes in out_ids / out_d; only read for the lists this kernel orders
+    int *out_ids;
+    float *out_d;
+    int sort_max;                  // lists longer than this (<= kExactRangeSortMax) are left to the host
+};
+
 // LDS of one scan block
 inline size_t exact_scan_lds(int qtile, int piece, int dim, int k)
 {
@@ -49,9 +79,12 @@ inline size_t exact_scan_lds(int qtile, int piece, int dim, int k)
 
 template <int METRIC>
 hipError_t exact_scan_launch(const ExactScanArgs &a, unsigned n_qtiles, size_t lds, hipStream_t st);
+template <int METRIC>
+hipError_t exact_range_scan_launch(const ExactScanArgs &a, const ExactRange &sink, unsigned n_qtiles, size_t lds, hipStream_t st);
 // words: the masked bitset; block_off[b]: set bits in front of word b * kExactCompactWords
 hipError_t exact_compact_launch(const unsigned *words, long long n_words, const long long *block_off, int *out_ids, hipStream_t st);
 hipError_t exact_merge_launch(const unsigned long long *lists, int n_chunks, int k, int nq, int *out_ids, float *out_d, hipStream_t st);
+hipError_t exact_range_sort_launch(const ExactRangeSortArgs &a, int nq, hipStream_t st);
 
 } // namespace hnsw
 
@@ -95,8 +128,8 @@ __device__ __forceinline__ void exact_list_insert(unsigned long long *L, int k, 
     }
 }
 
-template <int METRIC>
-__global__ void __launch_bounds__(kExactThreads) exact_scan_kernel(const ExactScanArgs a)
+template <int METRIC, class SINK>
+__global__ void __launch_bounds__(kExactThreads) exact_scan_kernel(const ExactScanArgs a, const SINK sink)
 {
     static_assert(kExactRQ == kExactThreads / 64, "wave w merges query w of a register tile");
     constexpr int RQ = kExactRQ, RR = kExactRR;
@@ -263,53 +296,100 @@ __global__ void __launch_bounds__(kExactThreads) exact_scan_kernel(const ExactSc
                     }
                 }
             }
-            // offers: a key goes to its query's pending list only when it is below that query's current k-th
-            int offered = 0;
-            if (j == 0) {
+            if constexpr (SINK::kRange) {
+                // offers: every key within the range goes to its query's pending list (kExactIterRows entries per query of the
+                // register tile: what one step can produce)
+                int offered = 0;
+                if (j == 0) {
 #pragma unroll
-                for (int q = 0; q < RQ; ++q) {
-                    if (qsub + q >= QT || q0 + qsub + q >= a.nq) continue;
-                    const unsigned long long t = thr[qsub + q];
+                    for (int q = 0; q < RQ; ++q) {
+                        if (qsub + q >= QT || q0 + qsub + q >= a.nq) continue;
 #pragma unroll
-                    for (int r = 0; r < RR; ++r) {
-                        if (!rvalid[r]) continue;
-                        ++measured;
-                        const unsigned long long key = exact_key(dist[q][r], rid[r]);
-                        if (key < t) {
-                            const int slot = atomicAdd(&pend_cnt[q], 1);
-                            pend[q * kExactIterRows + slot] = key;
-                            offered = 1;
+                        for (int r = 0; r < RR; ++r) {
+                            if (!rvalid[r]) continue;
+                            ++measured;
+                            if (dist[q][r] <= sink.range) {
+                                const int slot = atomicAdd(&pend_cnt[q], 1);
+                                pend[q * kExactIterRows + slot] = exact_key(dist[q][r], rid[r]);
+                                offered = 1;
+                            }
                         }
                     }
                 }
-            }
-            if (__syncthreads_or(offered)) {
-                const int cnt = pend_cnt[wave]; // wave w: query qsub + w (the set that results does not depend on the order of the offers)
-                if (cnt > 0) {
-                    unsigned long long *L = lists + (size_t)(qsub + wave) * k;
-                    for (int i = 0; i < cnt; ++i) {
-                        const unsigned long long x = pend[wave * kExactIterRows + i];
-                        if (x < L[k - 1]) exact_list_insert(L, k, x, lane);
+                if (__syncthreads_or(offered)) {
+                    const int cnt = pend_cnt[wave]; // wave w: query qsub + w, a real query when anything was offered to it
+                    if (cnt > 0) {
+                        const long long qg = q0 + qsub + wave;
+                        unsigned first = 0;
+                        if (lane == 0) first = atomicAdd(&sink.counts[qg], (unsigned)cnt); // one global atomic per (query, step)
+                        first = __shfl(first, 0, 64);
+                        const long long off = sink.seg_off[qg], cap = sink.seg_off[qg + 1] - off;
+                        for (int i = lane; i < cnt; i += 64) {
+                            const long long slot = (long long)first + i;
+                            if (slot < cap) sink.arena[off + slot] = pend[wave * kExactIterRows + i];
+                        }
+                        wave_lds_sync();
+                        if (lane == 0) pend_cnt[wave] = 0;
                     }
-                    wave_lds_sync();
-                    if (lane == 0) { thr[qsub + wave] = L[k - 1]; pend_cnt[wave] = 0; }
+                    __syncthreads();
                 }
-                __syncthreads();
+            } else {
+                // offers: a key goes to its query's pending list only when it is below that query's current k-th
+                int offered = 0;
+                if (j == 0) {
+#pragma unroll
+                    for (int q = 0; q < RQ; ++q) {
+                        if (qsub + q >= QT || q0 + qsub + q >= a.nq) continue;
+                        const unsigned long long t = thr[qsub + q];
+#pragma unroll
+                        for (int r = 0; r < RR; ++r) {
+                            if (!rvalid[r]) continue;
+                            ++measured;
+                            const unsigned long long key = exact_key(dist[q][r], rid[r]);
+                            if (key < t) {
+                                const int slot = atomicAdd(&pend_cnt[q], 1);
+                                pend[q * kExactIterRows + slot] = key;
+                                offered = 1;
+                            }
+                        }
+                    }
+                }
+                if (__syncthreads_or(offered)) {
+                    const int cnt = pend_cnt[wave]; // wave w: query qsub + w (the set that results does not depend on the order of the offers)
+                    if (cnt > 0) {
+                        unsigned long long *L = lists + (size_t)(qsub + wave) * k;
+                        for (int i = 0; i < cnt; ++i) {
+                            const unsigned long long x = pend[wave * kExactIterRows + i];
+                            if (x < L[k - 1]) exact_list_insert(L, k, x, lane);
+                        }
+                        wave_lds_sync();
+                        if (lane == 0) { thr[qsub + wave] = L[k - 1]; pend_cnt[wave] = 0; }
+                    }
+                    __syncthreads();
+                }
             }
         }
     }
     __syncthreads();
     if (measured) atomicAdd(a.evals, (unsigned long long)measured); // one atomic per group that measured anything
-    for (int qi = 0; qi < QT && q0 + qi < a.nq; ++qi) {
-        unsigned long long *dst = a.lists + ((size_t)(q0 + qi) * a.n_chunks + blockIdx.y) * (size_t)k;
-        for (int i = tid; i < k; i += kExactThreads) dst[i] = lists[(size_t)qi * k + i];
+    if constexpr (!SINK::kRange) {
+        for (int qi = 0; qi < QT && q0 + qi < a.nq; ++qi) {
+            unsigned long long *dst = a.lists + ((size_t)(q0 + qi) * a.n_chunks + blockIdx.y) * (size_t)k;
+            for (int i = tid; i < k; i += kExactThreads) dst[i] = lists[(size_t)qi * k + i];
+        }
     }
 }
 
 template <int METRIC>
 hipError_t exact_scan_launch(const ExactScanArgs &a, unsigned n_qtiles, size_t lds, hipStream_t st)
 {
-    hipLaunchKernelGGL(exact_scan_kernel<METRIC>, dim3(n_qtiles, (unsigned)a.n_chunks), dim3(kExactThreads), lds, st, a);
+    hipLaunchKernelGGL((exact_scan_kernel<METRIC, ExactTopK>), dim3(n_qtiles, (unsigned)a.n_chunks), dim3(kExactThreads), lds, st, a, ExactTopK{});
+    return hipGetLastError();
+}
+template <int METRIC>
+hipError_t exact_range_scan_launch(const ExactScanArgs &a, const ExactRange &sink, unsigned n_qtiles, size_t lds, hipStream_t st)
+{
+    hipLaunchKernelGGL((exact_scan_kernel<METRIC, ExactRange>), dim3(n_qtiles, (unsigned)a.n_chunks), dim3(kExactThreads), lds, st, a, sink);
     return hipGetLastError();
 }
 
@@ -374,6 +454,44 @@ __global__ void __launch_bounds__(64) exact_merge_kernel(const unsigned long lon
     }
 }
 
+// One block per query: its segment's keys (counts[q] <= sort_max of them; longer and empty lists are not touched) into LDS, padded
+// with ~0 to a power of two, a bitonic network over them, ids and distances out.  n, and so every loop bound and barrier, is the
+// same for all threads of the block.
+__global__ void __launch_bounds__(256) exact_range_sort_kernel(const ExactRangeSortArgs a)
+{
+    __shared__ unsigned long long K[kExactRangeSortMax];
+    const int tid = threadIdx.x;
+    const size_t q = blockIdx.x;
+    const unsigned cnt = a.counts[q];
+    if (cnt == 0 || cnt > (unsigned)a.sort_max || cnt > (unsigned)kExactRangeSortMax) return;
+    const int n = (int)cnt;
+    int P = 1;
+    while (P < n) P <<= 1;
+    const unsigned long long *src = a.arena + a.seg_off[q];
+    for (int i = tid; i < P; i += 256) K[i] = i < n ? src[i] : kExactEmpty;
+    __syncthreads();
+    for (int k = 2; k <= P; k <<= 1)
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int t = tid; t < (P >> 1); t += 256) {
+                const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), l = i | j;
+                const unsigned long long x = K[i], y = K[l];
+                if ((x > y) == ((i & k) == 0)) { K[i] = y; K[l] = x; }
+            }
+            __syncthreads();
+        }
+    const long long o = a.out_off[q];
+    for (int i = tid; i < n; i += 256) {
+        const unsigned long long key = K[i];
+        a.out_ids[o + i] = (int)(unsigned)key;
+        a.out_d[o + i] = exact_key_dist(key);
+    }
+}
+
+hipError_t exact_range_sort_launch(const ExactRangeSortArgs &a, int nq, hipStream_t st)
+{
+    hipLaunchKernelGGL(exact_range_sort_kernel, dim3((unsigned)nq), dim3(256), 0, st, a);
+    return hipGetLastError();
+}
 hipError_t exact_compact_launch(const unsigned *words, long long n_words, const long long *block_off, int *out_ids, hipStream_t st)
 {
     const unsigned blocks = (unsigned)((n_words + kExactCompactWords - 1) / kExactCompactWords);

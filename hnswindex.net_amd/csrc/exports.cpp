@@ -230,6 +230,49 @@ API int hnsw_mi355x_range_query_filtered(void *handle, const float *vectors, int
                               "hnsw_mi355x_range_query_filtered");
 }
 
+// Every live, allowed id within `range` per query, ascending by (distance, id): the flat scan with the range sink.
+// hnsw_range_query's allocation contract (hnsw_free_results); exclusive, like the other scan.
+API int hnsw_mi355x_exact_range_query(void *handle, const float *vectors, int count, int dim, float range, const uint32_t *allow_bits, long long nbits,
+                                      void **out_ids, void **out_dists, int *counts)
+{
+    if (!handle) return 0;
+    if (count <= 0) return 0;
+    if (!vectors || !out_ids || !out_dists || !counts || dim <= 0) { set_error("System.ArgumentNullException: hnsw_mi355x_exact_range_query"); return -1; }
+    for (int i = 0; i < count; ++i) { out_ids[i] = nullptr; out_dists[i] = nullptr; counts[i] = 0; }
+    if (allow_bits && nbits < 0) { set_error("System.ArgumentException: hnsw_mi355x_exact_range_query: nbits must be >= 0"); return -1; }
+    std::string err;
+    std::vector<int> ids;
+    std::vector<float> ds;
+    {
+        LOCK_INDEX(handle);
+        if (static_cast<HnswIndex *>(handle)->exact_range_query(vectors, count, dim, range, allow_bits, nbits, counts, ids, ds, err) < 0) {
+            for (int i = 0; i < count; ++i) counts[i] = 0;
+            set_error(err);
+            return -1;
+        }
+    }
+    size_t at = 0;
+    for (int i = 0; i < count; ++i) {
+        const size_t n = (size_t)counts[i];
+        if (n == 0) continue;
+        int *pi = static_cast<int *>(std::malloc(sizeof(int) * n));
+        float *pd = static_cast<float *>(std::malloc(sizeof(float) * n));
+        if (!pi || !pd) {
+            std::free(pi); std::free(pd);
+            hnsw_free_results(out_ids, out_dists, count);
+            for (int j = 0; j < count; ++j) counts[j] = 0;
+            set_error("System.OutOfMemoryException: hnsw_mi355x_exact_range_query");
+            return -1;
+        }
+        std::memcpy(pi, ids.data() + at, sizeof(int) * n);
+        std::memcpy(pd, ds.data() + at, sizeof(float) * n);
+        out_ids[i] = pi;
+        out_dists[i] = pd;
+        at += n;
+    }
+    return 0;
+}
+
 // KnnQuery / RangeQuery with the reference's `layer` argument (BatchKnnQuery / BatchRangeQuery(queries, ., filterFnc, layer),
 // HNSWIndex.cs:107-168); allow_bits == NULL: no filter.  Layer 0 goes through the code of the calls without a layer.
 API int hnsw_mi355x_knn_query_at_layer(void *handle, const float *vectors, int count, int dim, int k, int layer, const uint32_t *allow_bits,
@@ -395,6 +438,13 @@ API int hnsw_mi355x_exact_window_stats(void *h, uint64_t out[4])
     if (!h || !out) return -1;
     LOCK_INDEX(h);
     static_cast<HnswIndex *>(h)->exact_window_stats(out);
+    return 0;
+}
+API int hnsw_mi355x_exact_range_info(void *h, uint64_t out[4])
+{
+    if (!h || !out) return -1;
+    LOCK_INDEX(h);
+    static_cast<HnswIndex *>(h)->exact_range_info(out);
     return 0;
 }
 API int hnsw_mi355x_dim(void *h)

@@ -1662,6 +1662,23 @@ int HnswIndex::knn_query_general(const float *queries, int count, int dim, int k
     return knn_query_lockstep(redo.data(), (int)redo.size(), k, out_ids, out_dists, err, allow, layer);
 }
 
+// The candidates of a flat scan as Device::exact_knn / exact_range take them: the row count, and allow_bits / nbits replaced by
+// allow AND live (in `live`) once slots are vacant.
+long long HnswIndex::exact_candidates(const uint32_t *&allow_bits, long long &nbits, std::vector<uint32_t> &live) const
+{
+    if (!allow_bits) nbits = 0; // no filter: nbits means nothing
+    const long long length = graph_.length;
+    if (graph_.count != graph_.length) { // vacant slots: allow AND live
+        const long long n = allow_bits ? std::min(nbits, length) : length;
+        live.assign((size_t)((n + 31) / 32) + 1, 0u);
+        for (long long id = 0; id < n; ++id)
+            if (!graph_.removed[(size_t)id] && (!allow_bits || ((allow_bits[id >> 5] >> (id & 31)) & 1u))) live[(size_t)(id >> 5)] |= 1u << (id & 31);
+        allow_bits = live.data();
+        nbits = n;
+    }
+    return length;
+}
+
 // The flat scan: every live, allowed row measured against every query.  The candidates are the live ids: while
 // nothing has been removed they are 0 .. length - 1 and the caller's bitset goes to the device as it is (none: the scan addresses
 // rows directly); once slots are vacant the live set is ANDed into it here.
@@ -1676,19 +1693,32 @@ int HnswIndex::exact_knn_query(const float *queries, int count, int dim, int k, 
         return 0;
     }
     if (!ensure_dim(dim, err)) return -1;
-    if (!allow_bits) nbits = 0; // no filter: nbits means nothing
-    const long long length = graph_.length;
     std::vector<uint32_t> live;
-    if (graph_.count != graph_.length) { // vacant slots: allow AND live
-        const long long n = allow_bits ? std::min(nbits, length) : length;
-        live.assign((size_t)((n + 31) / 32) + 1, 0u);
-        for (long long id = 0; id < n; ++id)
-            if (!graph_.removed[(size_t)id] && (!allow_bits || ((allow_bits[id >> 5] >> (id & 31)) & 1u))) live[(size_t)(id >> 5)] |= 1u << (id & 31);
-        allow_bits = live.data();
-        nbits = n;
-    }
+    const long long length = exact_candidates(allow_bits, nbits, live);
     // (the scan stages its queries in a buffer of its own: the resident set, sharded or not, stays what it was)
     if (!dev_->exact_knn(queries, count, length, k, allow_bits, nbits, out_ids, out_dists)) { err = get_dev_error(); return -1; }
+    return 0;
+}
+
+// The flat scan with the range sink: exact_knn_query's candidates; per query every one within `range`, ascending by
+// (distance, id).  counts[i], and the lists concatenated in query order in ids / dists.  Always on the device, on the primary context.
+int HnswIndex::exact_range_query(const float *queries, int count, int dim, float range, const uint32_t *allow_bits, long long nbits, int *counts,
+                                 std::vector<int> &ids, std::vector<float> &dists, std::string &err)
+{
+    ids.clear();
+    dists.clear();
+    if (count <= 0) return 0;
+    for (int i = 0; i < count; ++i) counts[i] = 0;
+    if (failed(err)) return -1;
+    if (graph_.count <= 0) return 0;
+    if (!ensure_dim(dim, err)) return -1;
+    std::vector<uint32_t> live;
+    const long long length = exact_candidates(allow_bits, nbits, live);
+    // (the scan stages its queries in a buffer of its own: the resident set, sharded or not, stays what it was)
+    if (!dev_->exact_range(queries, count, length, range, allow_bits, nbits, counts)) { err = get_dev_error(); return -1; }
+    ids.resize(dev_->exact_range_total());
+    dists.resize(ids.size());
+    if (!dev_->exact_range_results(ids.data(), dists.data())) { err = get_dev_error(); return -1; }
     return 0;
 }
 

@@ -59,6 +59,11 @@ public:
     // Reads no graph; runs on the primary context, on the device whatever device_traversal says.
     int exact_knn_query(const float *queries, int count, int dim, int k, const uint32_t *allow_bits, long long nbits, int *out_ids, float *out_dists,
                         std::string &err);
+    // hnsw_mi355x_exact_range_query: the same scan and candidates; per query every candidate within `range` (Device::exact_range),
+    // counts[count] and the lists concatenated in query order.  -1: counts are 0 and the lists empty.
+    int exact_range_query(const float *queries, int count, int dim, float range, const uint32_t *allow_bits, long long nbits, int *counts,
+                          std::vector<int> &ids, std::vector<float> &dists, std::string &err);
+    void exact_range_info(uint64_t out[4]) const { if (dev_) dev_->exact_range_info(out); else out[0] = out[1] = out[2] = out[3] = 0; }
     int knn_query_general(const float *queries, int count, int dim, int k, int layer, const uint32_t *allow_bits, long long nbits, int *out_ids,
                           float *out_dists, std::string &err);
     // hnsw_mi355x_multilayer_knn_query: the number of layer slots (min(top, max_layer) + 1; 0 for an empty index, k < 1 or
@@ -155,6 +160,7 @@ private:
     bool ensure_dim(int dim, std::string &err);
     bool ensure_capacity(long long need, std::string &err);
     bool insert_batch(const std::vector<int> &bid, std::string &err);
+    long long exact_candidates(const uint32_t *&allow_bits, long long &nbits, std::vector<uint32_t> &live) const;
     bool insert_exact_window(const std::vector<int> &fresh, int &p, int W, bool background, std::string &err);
     // Selected neighbour ids per (batch item, layer).  Device results are read in place from the
     // context's pinned buffers (layer 0: slot = item; layer L >= 1: slot upper_base[item] + L - 1);

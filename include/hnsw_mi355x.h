@@ -247,6 +247,26 @@ int hnsw_mi355x_multilayer_knn_query(void *handle, const float *vectors, int cou
 int hnsw_mi355x_exact_knn_query(void *handle, const float *vectors, int count, int dim, int k, const uint32_t *allow_bits, long long nbits,
                                 int *out_ids, float *out_dists);
 
+/* Every candidate within a radius, by the same flat scan (no reference counterpart): for each query ALL candidates
+ * of hnsw_mi355x_exact_knn_query -- the live ids the allow-set allows, allow_bits == NULL: no filter, nbits then ignored -- whose
+ * distance d satisfies the float compare d <= range (the reference's neighborDistance <= range).  Distances are those of
+ * hnsw_mi355x_exact_knn_query, with its two representation rules (-0 is returned as +0; a NaN distance is never a result).
+ * range = NaN: empty lists; range = +inf: every candidate whose distance is a number, +inf included; range = -0.0 admits distance 0;
+ * a negative range is an ordinary one (there is no empty-heap failure here).  Order: ascending by (distance, id); keys are unique,
+ * so the result is.  The length of a list is limited by memory alone -- 2^27 results per query (1 GiB of keys on the device); a
+ * longer list is -1 with a message naming the limit.
+ * Allocation is hnsw_range_query's: out_ids[i] / out_dists[i] are malloc'ed arrays of counts[i] entries, NULL where counts[i] is 0,
+ * released with hnsw_free_results.  A NULL handle and count <= 0 behave as in hnsw_mi355x_range_query_filtered (0, nothing
+ * written); nbits < 0 with a bitset is -1.  An empty index, or a set that allows no live id, gives counts of 0 and no launch.  On
+ * any error every out pointer is NULL and every count 0.  Always runs on the device, on the primary context alone under
+ * hnsw_mi355x_set_devices(n); takes the handle exclusively; the resident query set is not touched. */
+int hnsw_mi355x_exact_range_query(void *handle, const float *vectors, int count, int dim, float range, const uint32_t *allow_bits,
+                                  long long nbits, void **out_ids, void **out_dists, int *counts);
+/* Counters of hnsw_mi355x_exact_range_query on the primary context since hnsw_mi355x_reset_stats: out[0] lists of two or more entries
+ * ordered on the device, out[1] lists ordered on the host, out[2] rounds repeated with exact capacities, out[3] results returned.
+ * (Its launches and measured pairs count in hnswdev_stats.exact_*: both calls are the flat scan.)  0, or -1 for a NULL argument. */
+int hnsw_mi355x_exact_range_info(void *handle, uint64_t out[4]);
+
 /* Measurement aid: hnsw_mi355x_set_queries uploads a query set (count x dim) once; every later
  * hnsw_mi355x_knn_query_resident(k) is hnsw_knn_query on that set with the inputs already in HBM
  * (out arrays: count x k). */
@@ -484,6 +504,16 @@ int hnswdev_set_profiling(void *ctx, int enabled);
  * counted by the scan kernel itself. */
 int hnswdev_exact_knn(void *ctx, const float *queries, int nq, long long n_rows, int k, const uint32_t *allow_bits, long long nbits,
                       int *out_ids, float *out_dists);
+/* The flat scan behind hnsw_mi355x_exact_range_query: hnswdev_exact_knn's candidates, queries (NULL: the resident set) and
+ * distances; out_counts[i] = the candidates of query i with distance <= range.  The lists -- each ascending by (distance, id) --
+ * are kept in the context, concatenated in query order, until the next hnswdev_exact_range and are copied out by
+ * hnswdev_exact_range_results (out_ids / out_dists hold sum(out_counts) entries).  They live in buffers of their own: what
+ * hnswdev_range_results has pending is not disturbed.  -1: every count is 0 and nothing is kept. */
+int hnswdev_exact_range(void *ctx, const float *queries, int nq, long long n_rows, float range, const uint32_t *allow_bits, long long nbits,
+                        int *out_counts);
+int hnswdev_exact_range_results(void *ctx, int *out_ids, float *out_dists);
+/* out[0 .. 3] as hnsw_mi355x_exact_range_info, of this context; zeroed by hnswdev_reset_stats. */
+int hnswdev_exact_range_info(void *ctx, uint64_t out[4]);
 int hnswdev_get_stats(void *ctx, hnswdev_stats *out);
 int hnswdev_reset_stats(void *ctx);
 /* Last error, process-wide (creation failures have no context yet) ... */
