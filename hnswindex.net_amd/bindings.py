@@ -125,6 +125,30 @@ lib.hnsw_mi355x_exact_range_query.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_in
                                               ct.POINTER(ct.c_void_p), _I]
 lib.hnsw_mi355x_exact_range_info.restype = ct.c_int
 lib.hnsw_mi355x_exact_range_info.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
+
+
+class LayerInfo(ct.Structure):
+    """hnsw_mi355x_layer_info: HNSWInfo.LayerInfo (HNSWInfo.cs:18-29) of one layer."""
+    _fields_ = [(n, ct.c_int32) for n in ("layer_id", "nodes_count", "max_out_edges", "min_out_edges", "max_in_edges", "min_in_edges",
+                                          "out_edges_median", "in_edges_median")] + [("avg_out_edges", ct.c_double), ("avg_in_edges", ct.c_double)]
+
+    def as_dict(self) -> dict:
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+_GRAPH_INFO_COUNTERS = ("info_layers", "component_layers", "entries", "launches")   # hnswdev_graph_info_counters' out[0 .. 3]
+lib.hnsw_mi355x_get_info.restype = ct.c_int
+lib.hnsw_mi355x_get_info.argtypes = [ct.c_void_p, ct.POINTER(LayerInfo), ct.c_int]
+lib.hnsw_mi355x_connected_component_counts.restype = ct.c_int
+lib.hnsw_mi355x_connected_component_counts.argtypes = [ct.c_void_p, _I, ct.c_int]
+lib.hnsw_mi355x_graph_info_counters.restype = ct.c_int
+lib.hnsw_mi355x_graph_info_counters.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
+lib.hnswdev_graph_info.restype = ct.c_int
+lib.hnswdev_graph_info.argtypes = [ct.c_void_p, ct.c_int, _U32, ct.c_longlong, ct.c_int, ct.POINTER(LayerInfo)]
+lib.hnswdev_graph_components.restype = ct.c_int
+lib.hnswdev_graph_components.argtypes = [ct.c_void_p, ct.c_int, _U32, ct.c_longlong, _I]
+lib.hnswdev_graph_info_counters.restype = ct.c_int
+lib.hnswdev_graph_info_counters.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
 lib.hnsw_mi355x_range_query_filtered.restype = ct.c_int
 lib.hnsw_mi355x_range_query_filtered.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_int, ct.c_float, _U32, ct.c_longlong, ct.POINTER(ct.c_void_p),
                                                  ct.POINTER(ct.c_void_p), ct.POINTER(ct.c_int)]
@@ -656,6 +680,43 @@ class Index:
             raise IndexError((i, layer))
         return buf[:n].copy()
 
+    # ---- HNSWIndex.GetInfo / GetConnectedComponentCounts (src/HNSWIndex/HNSWIndex.cs:192-205) ----
+    def get_info(self) -> List[dict]:
+        """HNSWIndex.GetInfo(): one dict per layer 0 .. top with the fields of hnsw_mi355x_layer_info (HNSWInfo.LayerInfo), computed
+        on the device from the graph mirror.  An index with no items raises, as the reference does (IndexOutOfRangeException)."""
+        if not self._initialized:
+            self._initialize()
+        cap = 16
+        while True:
+            out = (LayerInfo * cap)()
+            n = lib.hnsw_mi355x_get_info(self._h, out, cap)
+            if n < 0:
+                raise RuntimeError(last_error())
+            if n <= cap:
+                return [out[i].as_dict() for i in range(n)]
+            cap = n
+
+    def connected_component_counts(self) -> npt.NDArray[np.int32]:
+        """HNSWIndex.GetConnectedComponentCounts(): weakly connected components per layer 0 .. top, counted on the device from the
+        graph mirror; an empty array for an empty index."""
+        if not self._initialized:
+            self._initialize()
+        out = np.zeros(16, dtype=np.int32)
+        while True:
+            n = lib.hnsw_mi355x_connected_component_counts(self._h, out.ctypes.data_as(_I), out.size)
+            if n < 0:
+                raise RuntimeError(last_error())
+            if n <= out.size:
+                return out[:n].copy()
+            out = np.zeros(n, dtype=np.int32)
+
+    def graph_info_counters(self) -> dict:
+        """Counters of get_info / connected_component_counts since reset_stats (hnsw_mi355x_graph_info_counters)."""
+        out = (ct.c_uint64 * 4)()
+        if self._h:
+            lib.hnsw_mi355x_graph_info_counters(self._h, out)
+        return dict(zip(_GRAPH_INFO_COUNTERS, (int(v) for v in out)))
+
     # ---- HNSWIndex.Serialize / Deserialize (src/HNSWIndex/HNSWIndex.cs:210-229) ----
     def serialize(self, path) -> None:
         """Write the reference's protobuf-net snapshot of this index to `path`."""
@@ -799,6 +860,35 @@ class DeviceBackend:
             e = np.ascontiguousarray(edges, dtype=np.int32)
             self._check(lib.hnswdev_graph_set_layer(self._ctx, layer, c.ctypes.data_as(_I), e.ctypes.data_as(_I), e.shape[1]))
         self._check(lib.hnswdev_graph_commit(self._ctx))
+
+    @staticmethod
+    def _live_arg(live):
+        """live: None (every node of the mirror) or a bool mask / id list as the allowed= arguments take it."""
+        if live is None:
+            return None, None, 0
+        words, nbits = allow_bits(live)
+        words, wp = _words_arg(words)
+        return words, wp, nbits
+
+    def graph_info(self, layer: int, live=None, with_in_edges: bool = True) -> dict:
+        """hnswdev_graph_info: HNSWInfo.LayerInfo of one layer of the committed graph, as a dict of hnsw_mi355x_layer_info's fields."""
+        words, wp, nbits = self._live_arg(live)
+        out = LayerInfo()
+        self._check(lib.hnswdev_graph_info(self._ctx, int(layer), wp, nbits, int(bool(with_in_edges)), ct.byref(out)))
+        return out.as_dict()
+
+    def graph_components(self, layer: int, live=None) -> int:
+        """hnswdev_graph_components: weakly connected components among the members of one layer of the committed graph."""
+        words, wp, nbits = self._live_arg(live)
+        out = ct.c_int(0)
+        self._check(lib.hnswdev_graph_components(self._ctx, int(layer), wp, nbits, ct.byref(out)))
+        return int(out.value)
+
+    def graph_info_counters(self) -> dict:
+        """Counters of graph_info / graph_components since reset_stats (hnswdev_graph_info_counters)."""
+        out = (ct.c_uint64 * 4)()
+        self._check(lib.hnswdev_graph_info_counters(self._ctx, out))
+        return dict(zip(_GRAPH_INFO_COUNTERS, (int(v) for v in out)))
 
     def knn_search(self, queries, entry_point: int, k_beam: int, k_out: int, allowed=None, layer: int = 0):
         """allowed: as for Index.knn_query (hnswdev_knn_search_filtered); None runs hnswdev_knn_search.  layer != 0:

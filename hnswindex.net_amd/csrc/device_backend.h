@@ -76,6 +76,8 @@ class Device;
 struct VisitedScratch;   // device_backend.hip: the visited-set memory of a traversal launch
 struct TraversalLaunch;  // ... which traversal kernel form a launch runs, on how many waves, with which flags
 struct LaunchFamily;     // ... the hnswdev_stats counters of one kernel family
+struct LayerView;        // dk_graph_info.h: the mirror as the graph-info kernels see one layer of it
+struct GraphAcc;         // ... what those kernels add up
 struct ErrorScope { // RAII: the calling thread is inside a call on `d`
     explicit ErrorScope(Device *d);
     ~ErrorScope();
@@ -338,6 +340,18 @@ public:
     size_t exact_range_total() const { return xr_ids_.size(); }
     // lists of >= 2 entries ordered on the device, lists ordered on the host, rounds repeated with exact capacities, results returned
     void exact_range_info(uint64_t out[4]) const { for (int i = 0; i < 4; ++i) out[i] = xr_info_[i]; }
+    // hnswdev_graph_info / hnswdev_graph_components (dk_graph_info.h): HNSWInfo.LayerInfo (HNSWInfo.cs:18-43) and the
+    // number of weakly connected components (GraphNavigator.cs:350-419) of one layer of the mirror, computed on the device from the
+    // mirror as it stands; nothing of it is copied back.  The layer's members: ids < graph_nodes() that are live -- live_bits ==
+    // nullptr: all of them; else nbits bits as for search_filtered, ids >= nbits not live -- with level >= layer.  A list entry that
+    // names no member counts in its owner's out-degree and nowhere else.  with_in_edges == false (AllowRemovals off): the in-edge
+    // fields are 0 and no in-degree pass runs.  No member: nodes_count 0, every statistic 0, 0 components.  Any layer >= 0 may be
+    // asked for (graph_info_layer is the C ABI's range test).  Synchronous.
+    bool graph_info(int layer, const uint32_t *live_bits, long long nbits, bool with_in_edges, hnsw_mi355x_layer_info *out);
+    bool graph_components(int layer, const uint32_t *live_bits, long long nbits, int *out_count);
+    bool graph_info_layer(const char *who, int layer);
+    // layers summarised, layers whose components were counted, list entries read (counted by the kernels), kernel launches
+    void graph_info_counters(uint64_t out[4]) const { for (int i = 0; i < 4; ++i) out[i] = gi_info_[i]; }
 
     void set_profiling(bool on) { profiling_ = on; }
 
@@ -446,6 +460,13 @@ private:
     std::vector<int> xr_ids_;             // ... the call's results until the next call (exact_range_results)
     std::vector<float> xr_d_;
     uint64_t xr_info_[4] = {0, 0, 0, 0};
+    bool graph_info_begin(const char *who, int layer, const uint32_t *live_bits, long long nbits, LayerView *g);
+    bool graph_info_fetch(const GraphAcc **acc);
+    DevBuf<unsigned long long> gi_acc_; // graph_info / graph_components: the call's GraphAcc
+    DevBuf<unsigned> gi_live_;          // ... its live set
+    DevBuf<int> gi_indeg_, gi_parent_;  // ... per node: in-degree on the layer; parent in the union-find's forest
+    DevBuf<int> gi_inhist_;             // ... nodes per in-degree, max in-degree + 1 bins
+    uint64_t gi_info_[4] = {0, 0, 0, 0};
     DevBuf<SearchHit> s_arena_; // range search: the launch's results, packed
     DevBuf<unsigned long long> s_roff_, s_arena_used_; // s_roff_ stands for the capacity of range_batch's per-job arrays
     DevBuf<int> s_rentry_;

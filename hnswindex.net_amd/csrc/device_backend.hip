@@ -50,6 +50,7 @@
 #define HNSW_HOST_TU
 #include "device_kernels.h"
 #include "dk_exact.h"
+#include "dk_graph_info.h"
 #include "range_replay.h"
 
 namespace hnsw {
@@ -912,6 +913,7 @@ void Device::reset_stats()
     stats_ = hnswdev_stats{};
     stats_.row_bytes = rb;
     for (uint64_t &v : xr_info_) v = 0;
+    for (uint64_t &v : gi_info_) v = 0;
 #ifdef EXP_PHASE_CLOCKS
     (void)hipDeviceSynchronize();
     phase_report("reset_stats");
@@ -2802,6 +2804,165 @@ bool Device::exact_range_results(int *out_ids, float *out_d)
     return true;
 }
 
+// ---- GetInfo / GetConnectedComponentCounts on the mirror (device code in dk_graph_info.h) ----------------
+// Grid-stride launches: enough blocks for the items, at most eight per CU.
+static unsigned graph_info_blocks(long long items, int num_cu)
+{
+    const long long want = (items + kGraphInfoBlock - 1) / kGraphInfoBlock;
+    return (unsigned)std::max<long long>(1, std::min<long long>(want, (long long)num_cu * 8));
+}
+
+// What both calls begin with: the arguments, the view of the mirror for `layer` with the live set uploaded (its words travel in the
+// pinned stage behind the GraphAcc that comes back, so the stage is asked for once), and the accumulators zeroed.
+bool Device::graph_info_begin(const char *who, int layer, const uint32_t *live_bits, long long nbits, LayerView *g)
+{
+    if (g_n_ <= 0 || !g_adj0_) { set_dev_error(std::string(who) + ": no graph committed"); return false; }
+    if (layer < 0 || (live_bits && nbits < 0)) { set_dev_error(std::string(who) + ": bad argument"); return false; }
+    if (g_stride0_ > kGraphInfoMaxStride || g_strideU_ > kGraphInfoMaxStride) { set_dev_error(std::string(who) + ": adjacency lists too long"); return false; }
+    if (!bind()) return false;
+    hipStream_t st = S(stream_);
+    const long long nb = live_bits ? std::min(nbits, g_n_) : 0;
+    const size_t words = (size_t)((nb + 31) / 32);
+    char *hs = static_cast<char *>(pinned_stage(sizeof(GraphAcc) + 4 * words));
+    if (!hs || !gi_acc_.grow((sizeof(GraphAcc) + 7) / 8)) return false;
+    if (live_bits) {
+        if (!gi_live_.grow(std::max<size_t>(words, 1))) return false;
+        memcpy(hs + sizeof(GraphAcc), live_bits, 4 * words);
+        if (words) HIP_OK(hipMemcpyAsync(gi_live_, hs + sizeof(GraphAcc), 4 * words, hipMemcpyHostToDevice, st));
+    }
+    g->adj0 = g_adj0_; g->level = g_level_; g->pool = g_pool_; g->upper = g_upper_;
+    g->n = g_n_; g->pool_cap = g_pool_ ? g_pool_cap() : 0;
+    g->stride0 = g_stride0_; g->strideU = g_strideU_; g->layer = layer;
+    g->live = live_bits ? gi_live_.get() : nullptr;
+    g->nbits = nb;
+    HIP_OK(hipMemsetAsync(gi_acc_, 0, sizeof(GraphAcc), st));
+    return true;
+}
+// ... and end with: the accumulators on the host (valid until the pinned stage is used again)
+bool Device::graph_info_fetch(const GraphAcc **acc)
+{
+    hipStream_t st = S(stream_);
+    HIP_OK(hipMemcpyAsync(h_stage_.get(), gi_acc_, sizeof(GraphAcc), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    *acc = reinterpret_cast<const GraphAcc *>(h_stage_.get());
+    return true;
+}
+
+// The value of rank r (0-based, ascending) among sum(hist) values, hist[d] of them equal to d
+static long long hist_rank(const int *hist, long long bins, long long r)
+{
+    long long seen = 0;
+    for (long long d = 0; d < bins; ++d) {
+        seen += hist[d];
+        if (seen > r) return d;
+    }
+    return bins - 1;
+}
+// HNSWInfo.LayerInfo.Median (HNSWInfo.cs:45-51) of such values: sorted[n / 2], for an even n the integer mean of the two middle ones
+static int hist_median(const int *hist, long long bins, long long n)
+{
+    if (n % 2) return (int)hist_rank(hist, bins, n / 2);
+    return (int)((hist_rank(hist, bins, n / 2 - 1) + hist_rank(hist, bins, n / 2)) / 2);
+}
+
+bool Device::graph_info(int layer, const uint32_t *live_bits, long long nbits, bool with_in_edges, hnsw_mi355x_layer_info *out)
+{
+    if (!out) { set_dev_error("graph_info: null argument"); return false; }
+    LayerView g;
+    if (!graph_info_begin("graph_info", layer, live_bits, nbits, &g)) return false;
+    hipStream_t st = S(stream_);
+    GraphAcc *d_acc = reinterpret_cast<GraphAcc *>(gi_acc_.get());
+    uint64_t launches = 0;
+    if (with_in_edges) {
+        if (!gi_indeg_.grow((size_t)g_n_, (size_t)std::max<long long>(g_n_, g_cap_n()))) return false;
+        HIP_OK(hipMemsetAsync(gi_indeg_, 0, sizeof(int) * (size_t)g_n_, st));
+    }
+    const unsigned edge_blocks = graph_info_blocks(g_n_ * (layer == 0 ? g_stride0_ : g_strideU_), num_cu_), node_blocks = graph_info_blocks(g_n_, num_cu_);
+    hipLaunchKernelGGL(graph_edge_pass_kernel<false>, dim3(edge_blocks), dim3(kGraphInfoBlock), 0, st, g, with_in_edges ? gi_indeg_.get() : nullptr, d_acc);
+    HIP_OK(hipGetLastError());
+    ++launches;
+    if (with_in_edges) {
+        hipLaunchKernelGGL(graph_indeg_reduce_kernel, dim3(node_blocks), dim3(kGraphInfoBlock), 0, st, g, gi_indeg_.get(), d_acc);
+        HIP_OK(hipGetLastError());
+        ++launches;
+    }
+    const GraphAcc *h;
+    if (!graph_info_fetch(&h)) return false;
+    const GraphAcc a = *h; // (the stage is used again below)
+    *out = hnsw_mi355x_layer_info{};
+    out->layer_id = layer;
+    // out-degrees: everything from the histogram (the integer sum as int64, then one division: LINQ's Average)
+    const int stride = layer == 0 ? g_stride0_ : g_strideU_;
+    long long nodes = 0, out_sum = 0;
+    int out_min = -1, out_max = 0;
+    for (int c = 0; c < stride && c < kGraphInfoMaxStride; ++c) {
+        if (!a.out_hist[c]) continue;
+        nodes += a.out_hist[c];
+        out_sum += (long long)c * a.out_hist[c];
+        if (out_min < 0) out_min = c;
+        out_max = c;
+    }
+    if (nodes > 0) {
+        out->nodes_count = (int)nodes;
+        out->max_out_edges = out_max; out->min_out_edges = out_min;
+        out->avg_out_edges = (double)out_sum / (double)nodes;
+        out->out_edges_median = hist_median(a.out_hist, stride, nodes);
+    }
+    if (nodes > 0 && with_in_edges) {
+        out->max_in_edges = a.in_max; out->min_in_edges = 0x7fffffff - a.in_min_inv;
+        out->avg_in_edges = (double)(long long)a.in_sum / (double)nodes;
+        // the median: a histogram with max + 1 bins, exact whatever the maximum is
+        const long long bins = (long long)a.in_max + 1;
+        if (!gi_inhist_.grow((size_t)bins)) return false;
+        HIP_OK(hipMemsetAsync(gi_inhist_, 0, sizeof(int) * (size_t)bins, st));
+        hipLaunchKernelGGL(graph_indeg_hist_kernel, dim3(node_blocks), dim3(kGraphInfoBlock), 0, st, g, gi_indeg_.get(), gi_inhist_.get(), bins);
+        HIP_OK(hipGetLastError());
+        ++launches;
+        std::vector<int> hist((size_t)bins);
+        if (!exact_copy_out(hist.data(), gi_inhist_, sizeof(int) * (size_t)bins)) return false;
+        long long seen = 0;
+        for (int v : hist) seen += v;
+        if (seen != nodes) { set_dev_error("graph_info: the in-degree histogram does not add up to the layer's nodes"); return false; }
+        out->in_edges_median = hist_median(hist.data(), bins, nodes);
+    }
+    gi_info_[0] += 1; gi_info_[2] += a.entries; gi_info_[3] += launches;
+    return true;
+}
+
+bool Device::graph_components(int layer, const uint32_t *live_bits, long long nbits, int *out_count)
+{
+    if (!out_count) { set_dev_error("graph_components: null argument"); return false; }
+    *out_count = 0;
+    LayerView g;
+    if (!graph_info_begin("graph_components", layer, live_bits, nbits, &g)) return false;
+    hipStream_t st = S(stream_);
+    GraphAcc *d_acc = reinterpret_cast<GraphAcc *>(gi_acc_.get());
+    if (!gi_parent_.grow((size_t)g_n_, (size_t)std::max<long long>(g_n_, g_cap_n()))) return false;
+    const unsigned edge_blocks = graph_info_blocks(g_n_ * (layer == 0 ? g_stride0_ : g_strideU_), num_cu_), node_blocks = graph_info_blocks(g_n_, num_cu_);
+    hipLaunchKernelGGL(graph_uf_init_kernel, dim3(node_blocks), dim3(kGraphInfoBlock), 0, st, g, gi_parent_.get());
+    HIP_OK(hipGetLastError());
+    hipLaunchKernelGGL(graph_edge_pass_kernel<true>, dim3(edge_blocks), dim3(kGraphInfoBlock), 0, st, g, gi_parent_.get(), d_acc);
+    HIP_OK(hipGetLastError());
+    hipLaunchKernelGGL(graph_uf_roots_kernel, dim3(node_blocks), dim3(kGraphInfoBlock), 0, st, g, gi_parent_.get(), d_acc);
+    HIP_OK(hipGetLastError());
+    const GraphAcc *h;
+    if (!graph_info_fetch(&h)) return false;
+    *out_count = (int)h->roots;
+    gi_info_[1] += 1; gi_info_[2] += h->entries; gi_info_[3] += 3;
+    return true;
+}
+
+// The C ABI's layer test: a committed graph, and a layer of 0 .. its top level
+bool Device::graph_info_layer(const char *who, int layer)
+{
+    if (!hg_ || g_n_ <= 0) { set_dev_error(std::string(who) + ": no graph committed"); return false; }
+    if (layer < 0 || layer > hg_->top) {
+        set_dev_error(std::string(who) + ": layer " + std::to_string(layer) + " outside 0 .. " + std::to_string(hg_->top) + " (the graph's top level)");
+        return false;
+    }
+    return true;
+}
+
 // ---- synchronous conveniences behind the C ABI ---------------------------------------
 // Distance(int, TVector) for nq (query, candidate list) pairs.  Runs on the context's two step-
 // buffer sets, ping-pong: while the GPU measures one set the host packs the next and unpacks the
@@ -3033,6 +3194,23 @@ DEV_API int hnswdev_exact_range_info(void *ctx, uint64_t out[4])
     CTX_OR_FAIL();
     if (!out) return -1;
     d->exact_range_info(out);
+    return 0;
+}
+DEV_API int hnswdev_graph_info(void *ctx, int layer, const uint32_t *live_bits, long long nbits, int with_in_edges, hnsw_mi355x_layer_info *out)
+{
+    CTX_OR_FAIL();
+    return d->graph_info_layer("hnswdev_graph_info", layer) && d->graph_info(layer, live_bits, nbits, with_in_edges != 0, out) ? 0 : -1;
+}
+DEV_API int hnswdev_graph_components(void *ctx, int layer, const uint32_t *live_bits, long long nbits, int *out_count)
+{
+    CTX_OR_FAIL();
+    return d->graph_info_layer("hnswdev_graph_components", layer) && d->graph_components(layer, live_bits, nbits, out_count) ? 0 : -1;
+}
+DEV_API int hnswdev_graph_info_counters(void *ctx, uint64_t out[4])
+{
+    CTX_OR_FAIL();
+    if (!out) return -1;
+    d->graph_info_counters(out);
     return 0;
 }
 DEV_API int hnswdev_range_results(void *ctx, int *out_ids, float *out_dists) { CTX_OR_FAIL(); return d->range_results(out_ids, out_dists) ? 0 : -1; }

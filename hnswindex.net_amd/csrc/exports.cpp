@@ -447,6 +447,35 @@ API int hnsw_mi355x_exact_range_info(void *h, uint64_t out[4])
     static_cast<HnswIndex *>(h)->exact_range_info(out);
     return 0;
 }
+// HNSWIndex.GetInfo() / GetConnectedComponentCounts() (HNSWIndex.cs:192-205) from the graph mirror on the device:
+// top + 1, with min(cap, top + 1) entries written.  Exclusive: Add edits the mirror.
+API int hnsw_mi355x_get_info(void *h, hnsw_mi355x_layer_info *out, int cap)
+{
+    if (!h) return 0;
+    if (cap < 0 || (cap > 0 && !out)) { set_error("System.ArgumentNullException: hnsw_mi355x_get_info"); return -1; }
+    std::string err;
+    LOCK_INDEX(h);
+    const int n = static_cast<HnswIndex *>(h)->get_info(out, cap, err);
+    if (n < 0) set_error(err);
+    return n;
+}
+API int hnsw_mi355x_connected_component_counts(void *h, int *out, int cap)
+{
+    if (!h) return 0;
+    if (cap < 0 || (cap > 0 && !out)) { set_error("System.ArgumentNullException: hnsw_mi355x_connected_component_counts"); return -1; }
+    std::string err;
+    LOCK_INDEX(h);
+    const int n = static_cast<HnswIndex *>(h)->connected_component_counts(out, cap, err);
+    if (n < 0) set_error(err);
+    return n;
+}
+API int hnsw_mi355x_graph_info_counters(void *h, uint64_t out[4])
+{
+    if (!h || !out) return -1;
+    LOCK_INDEX(h);
+    static_cast<HnswIndex *>(h)->graph_info_counters(out);
+    return 0;
+}
 API int hnsw_mi355x_dim(void *h)
 {
     if (!h) return 0;

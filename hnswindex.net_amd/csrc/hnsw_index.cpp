@@ -1722,6 +1722,41 @@ int HnswIndex::exact_range_query(const float *queries, int count, int dim, float
     return 0;
 }
 
+// GetInfo / GetConnectedComponentCounts (HNSWIndex.cs:192-205) on the graph mirror, a layer at a time.  The live
+// set goes to the device as exact_candidates builds it -- none while no slot is vacant.  Always on the device, on the primary context.
+int HnswIndex::get_info(hnsw_mi355x_layer_info *out, int cap, std::string &err)
+{
+    if (failed(err)) return -1;
+    if (graph_.count <= 0 || graph_.entry < 0) { // GraphData.GetTopLayer reads Nodes[EntryPointId] with EntryPointId == -1
+        err = "System.IndexOutOfRangeException: Index was outside the bounds of the array. (GetInfo on an index with no items)";
+        return -1;
+    }
+    if (!sync_graph(err)) return -1;
+    const uint32_t *bits = nullptr;
+    long long nbits = 0;
+    std::vector<uint32_t> live;
+    (void)exact_candidates(bits, nbits, live);
+    const int layers = graph_.top_layer() + 1;
+    for (int layer = 0; layer < layers && layer < cap; ++layer)
+        if (!dev_->graph_info(layer, bits, nbits, p_.allow_removals, out + layer)) { err = get_dev_error(); return -1; }
+    return layers;
+}
+
+int HnswIndex::connected_component_counts(int *out, int cap, std::string &err)
+{
+    if (failed(err)) return -1;
+    if (graph_.count <= 0 || graph_.entry < 0) return 0; // GraphNavigator.cs:333-336: the empty array
+    if (!sync_graph(err)) return -1;
+    const uint32_t *bits = nullptr;
+    long long nbits = 0;
+    std::vector<uint32_t> live;
+    (void)exact_candidates(bits, nbits, live);
+    const int layers = graph_.top_layer() + 1;
+    for (int layer = 0; layer < layers && layer < cap; ++layer)
+        if (!dev_->graph_components(layer, bits, nbits, out + layer)) { err = get_dev_error(); return -1; }
+    return layers;
+}
+
 // Host lock-step chains for the queries listed in `which` (nullptr: all `count`): MultiLayerJob.  out_*: [query][first + 1][k - 1].
 int HnswIndex::multilayer_lockstep(const int *which, int count, int k, int first, int min_layer, int *out_ids, float *out_dists, std::string &err)
 {

@@ -64,6 +64,14 @@ public:
     int exact_range_query(const float *queries, int count, int dim, float range, const uint32_t *allow_bits, long long nbits, int *counts,
                           std::vector<int> &ids, std::vector<float> &dists, std::string &err);
     void exact_range_info(uint64_t out[4]) const { if (dev_) dev_->exact_range_info(out); else out[0] = out[1] = out[2] = out[3] = 0; }
+    // hnsw_mi355x_get_info / hnsw_mi355x_connected_component_counts: HNSWIndex.GetInfo() / GetConnectedComponentCounts() for the
+    // layers 0 .. top, computed by the primary context from the graph mirror (Device::graph_info / graph_components)
+    // whatever device_traversal says.  The mirror is brought up to date first (sync_graph); when it is current the adjacency lists
+    // are neither uploaded nor fetched, and host_lists_stale_ stays what it was.  Both return top + 1 and write min(cap, top + 1)
+    // entries, or -1; an index with no live item: get_info -1 (the reference's IndexOutOfRangeException), the counts 0.
+    int get_info(hnsw_mi355x_layer_info *out, int cap, std::string &err);
+    int connected_component_counts(int *out, int cap, std::string &err);
+    void graph_info_counters(uint64_t out[4]) const { if (dev_) dev_->graph_info_counters(out); else out[0] = out[1] = out[2] = out[3] = 0; }
     int knn_query_general(const float *queries, int count, int dim, int k, int layer, const uint32_t *allow_bits, long long nbits, int *out_ids,
                           float *out_dists, std::string &err);
     // hnsw_mi355x_multilayer_knn_query: the number of layer slots (min(top, max_layer) + 1; 0 for an empty index, k < 1 or

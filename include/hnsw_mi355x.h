@@ -289,6 +289,32 @@ int hnsw_mi355x_node_max_layer(void *handle, int id);
 int hnsw_mi355x_get_out_edges(void *handle, int id, int layer, int *out, int cap);
 uint64_t hnsw_mi355x_graph_hash(void *handle);
 
+/* HNSWIndex.GetInfo() (src/HNSWIndex/HNSWIndex.cs:192-197): HNSWInfo.LayerInfo (HNSWInfo.cs:18-43), one per layer 0 .. top, top = the
+ * entry point's MaxLayer (GraphData.GetTopLayer).  A layer's members are the live ids with MaxLayer >= layer.  Out-degrees are the
+ * lengths of the members' lists on the layer; in-degrees count the list entries u -> v between members, which is what the reference's
+ * InEdges[layer] hold.  avg_*: the integer sum as int64, converted to double, divided by nodes_count (LINQ's Average).  *_median:
+ * Median (HNSWInfo.cs:45-51): sorted[n / 2] for an odd count, (sorted[n / 2 - 1] + sorted[n / 2]) / 2 in integer arithmetic for an
+ * even one.  Without AllowRemovals the four in-edge statistics and avg_in_edges are 0 (:39-42).
+ * Computed on the device from the graph mirror in HBM: the adjacency lists are not copied back to the host. */
+typedef struct hnsw_mi355x_layer_info {
+    int32_t layer_id, nodes_count, max_out_edges, min_out_edges, max_in_edges, min_in_edges, out_edges_median, in_edges_median;
+    double avg_out_edges, avg_in_edges;
+} hnsw_mi355x_layer_info; /* 48 bytes */
+/* Returns top + 1 and writes min(cap, top + 1) entries (cap smaller than that is no error: read the count, call again, as with
+ * hnsw_mi355x_active_ids).  A NULL handle: 0.  An index with no live item: -1 with System.IndexOutOfRangeException in the message
+ * (the reference indexes Nodes[-1], GraphData.GetTopLayer).  Other errors: -1 with a message.  Takes the handle exclusively; runs on
+ * the device, on the primary context, whatever hnsw_mi355x_set_device_traversal says (the mirror is brought up to date first). */
+int hnsw_mi355x_get_info(void *handle, hnsw_mi355x_layer_info *out, int cap);
+/* HNSWIndex.GetConnectedComponentCounts() (HNSWIndex.cs:199-205, GraphNavigator.cs:331-419): per layer 0 .. top the number of weakly
+ * connected components among the layer's members; an entry u -> v between two members joins them, whichever way it points.  Returns
+ * top + 1 and writes min(cap, top + 1) counts; 0 for an empty index (the reference's empty array) and for a NULL handle; -1 with a
+ * message on error.  Locking, device and context as hnsw_mi355x_get_info. */
+int hnsw_mi355x_connected_component_counts(void *handle, int *out, int cap);
+/* Counters of the two calls above on the primary context since hnsw_mi355x_reset_stats: out[0] layers summarised, out[1] layers whose
+ * components were counted, out[2] list entries read (the members' out-degrees, summed by the kernels themselves), out[3] kernel
+ * launches.  0, or -1 for a NULL argument. */
+int hnsw_mi355x_graph_info_counters(void *handle, uint64_t out[4]);
+
 /* HNSWIndex.Serialize(filePath) / HNSWIndex.Deserialize(distFnc, filePath)
  * (src/HNSWIndex/HNSWIndex.cs:210-229): the reference's protobuf-net snapshot of
  * HNSWIndexSnapshot<float[],float> (HNSWIndexSnapshot.cs:12-16, GraphDataSnapshot.cs:13-35,
@@ -514,6 +540,16 @@ int hnswdev_exact_range(void *ctx, const float *queries, int nq, long long n_row
 int hnswdev_exact_range_results(void *ctx, int *out_ids, float *out_dists);
 /* out[0 .. 3] as hnsw_mi355x_exact_range_info, of this context; zeroed by hnswdev_reset_stats. */
 int hnswdev_exact_range_info(void *ctx, uint64_t out[4]);
+/* hnsw_mi355x_get_info / hnsw_mi355x_connected_component_counts for ONE layer of the committed graph mirror of a context.
+ * live_bits == NULL: every node of the mirror is live; otherwise a bitset of nbits bits in the allow-sets' format, ids >= nbits not
+ * live.  A layer's members are the live nodes with level >= layer; an entry that points at no member counts in its owner's out-degree
+ * and is otherwise ignored (never dereferenced).  with_in_edges == 0: the in-edge fields are 0 and no in-degree pass runs.  A layer
+ * with no member: nodes_count 0 and every statistic 0 (layer_id is the layer asked for), 0 components.  layer outside 0 .. the
+ * mirror's top level, or no committed graph: -1. */
+int hnswdev_graph_info(void *ctx, int layer, const uint32_t *live_bits, long long nbits, int with_in_edges, hnsw_mi355x_layer_info *out);
+int hnswdev_graph_components(void *ctx, int layer, const uint32_t *live_bits, long long nbits, int *out_count);
+/* out[0 .. 3] as hnsw_mi355x_graph_info_counters, of this context; zeroed by hnswdev_reset_stats. */
+int hnswdev_graph_info_counters(void *ctx, uint64_t out[4]);
 int hnswdev_get_stats(void *ctx, hnswdev_stats *out);
 int hnswdev_reset_stats(void *ctx);
 /* Last error, process-wide (creation failures have no context yet) ... */
