@@ -125,6 +125,11 @@ lib.hnsw_mi355x_exact_range_query.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_in
                                               ct.POINTER(ct.c_void_p), _I]
 lib.hnsw_mi355x_exact_range_info.restype = ct.c_int
 lib.hnsw_mi355x_exact_range_info.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
+_EXACT_GROUPED_INFO = ("calls", "groups_scanned", "scan_blocks", "ids_listed")   # hnswdev_exact_grouped_info's out[0 .. 3]
+lib.hnsw_mi355x_exact_knn_query_grouped.restype = ct.c_int
+lib.hnsw_mi355x_exact_knn_query_grouped.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_int, ct.c_int, _I, ct.c_longlong, _I, ct.c_int, _I, _F]
+lib.hnsw_mi355x_exact_grouped_info.restype = ct.c_int
+lib.hnsw_mi355x_exact_grouped_info.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
 
 
 class LayerInfo(ct.Structure):
@@ -226,6 +231,12 @@ lib.hnswdev_exact_range_results.restype = ct.c_int
 lib.hnswdev_exact_range_results.argtypes = [ct.c_void_p, _I, _F]
 lib.hnswdev_exact_range_info.restype = ct.c_int
 lib.hnswdev_exact_range_info.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
+lib.hnswdev_exact_knn_grouped.restype = ct.c_int
+lib.hnswdev_exact_knn_grouped.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_longlong, ct.c_int, _I, ct.c_longlong, _I, ct.c_int, _I, _F]
+lib.hnswdev_exact_grouped_info.restype = ct.c_int
+lib.hnswdev_exact_grouped_info.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
+lib.hnswdev_exact_grouped_list_ms.restype = ct.c_int
+lib.hnswdev_exact_grouped_list_ms.argtypes = [ct.c_void_p, ct.POINTER(ct.c_double)]
 lib.hnswdev_range_results.restype = ct.c_int
 lib.hnswdev_range_results.argtypes = [ct.c_void_p, _I, _F]
 lib.hnswdev_knn_search_at_layer.restype = ct.c_int
@@ -284,6 +295,19 @@ def set_options(**knobs) -> None:
 def host_parallelism() -> int:
     """Hardware threads this process may run on = the default cap of Add's snapshot batches (include/hnsw_mi355x.h)."""
     return int(lib.hnsw_mi355x_host_parallelism())
+
+
+def _group_args(row_group, query_group, n_groups, nq):
+    """(row_group, query_group, n_groups) as the grouped scans take them: contiguous int32 arrays, query_group of nq entries;
+    n_groups None: the largest value in either array plus one, at least 1."""
+    rg = np.ascontiguousarray(np.asarray(row_group).reshape(-1), dtype=np.int32)
+    qg = np.ascontiguousarray(np.asarray(query_group).reshape(-1), dtype=np.int32)
+    if qg.shape[0] != nq:
+        raise ValueError(f"query_group has {qg.shape[0]} entries for {nq} queries")
+    if n_groups is None:
+        n_groups = max(int(rg.max(initial=-1)), int(qg.max(initial=-1))) + 1
+        n_groups = max(n_groups, 1)
+    return rg, qg, int(n_groups)
 
 
 def last_error() -> str:
@@ -524,6 +548,30 @@ class Index:
         if status < 0:
             raise RuntimeError(last_error())
         return ids, dists
+
+    def exact_knn_query_grouped(self, queries: npt.ArrayLike, k: int, row_group, query_group,
+                                n_groups=None) -> Tuple[npt.NDArray[np.int32], npt.NDArray[np.float32]]:
+        """exact_knn_query with a candidate group per query, every group in one scan (hnsw_mi355x_exact_knn_query_grouped):
+        row_group[id] is the group of an id (a value outside 0 .. n_groups - 1, or an id past the array's end: no group),
+        query_group[i] the group query i is answered from.  n_groups None: the largest value in either array plus one.  Per
+        group the rows equal exact_knn_query(queries[query_group == g], k, allowed=(row_group == g))."""
+        q = _as_2d_f32(queries, self.dim)
+        n = int(q.shape[0])
+        rg, qg, ng = _group_args(row_group, query_group, n_groups, n)
+        ids = np.full((n, max(k, 0)), -1, dtype=np.int32)   # (an index nothing was added to has no native handle yet: padding)
+        dists = np.full((n, max(k, 0)), np.nan, dtype=np.float32)
+        status = lib.hnsw_mi355x_exact_knn_query_grouped(self._h, q.ctypes.data_as(_F), n, self.dim, k, rg.ctypes.data_as(_I), rg.shape[0],
+                                                         qg.ctypes.data_as(_I), ng, ids.ctypes.data_as(_I), dists.ctypes.data_as(_F))
+        if status < 0:
+            raise RuntimeError(last_error())
+        return ids, dists
+
+    def exact_grouped_info(self) -> dict:
+        """Counters of exact_knn_query_grouped since reset_stats (hnsw_mi355x_exact_grouped_info)."""
+        out = (ct.c_uint64 * 4)()
+        if self._h:
+            lib.hnsw_mi355x_exact_grouped_info(self._h, out)
+        return dict(zip(_EXACT_GROUPED_INFO, (int(v) for v in out)))
 
     def exact_range_query(self, queries: npt.ArrayLike, radius: float,
                           allowed=None) -> Tuple[List[npt.NDArray[np.int32]], List[npt.NDArray[np.float32]]]:
@@ -926,6 +974,32 @@ class DeviceBackend:
         self._check(lib.hnswdev_exact_knn(self._ctx, q.ctypes.data_as(_F), n, (1 << 62) if n_rows is None else int(n_rows), int(k), wp, nbits,
                                           ids.ctypes.data_as(_I), d.ctypes.data_as(_F)))
         return ids, d
+
+    def exact_knn_grouped(self, queries, k: int, row_group, query_group, n_groups=None, n_rows=None):
+        """hnswdev_exact_knn_grouped: exact_knn with a candidate group per query -- query i is answered from the uploaded rows j of
+        [0, n_rows) (None: all) with row_group[j] == query_group[i].  queries None: the resident set (len(query_group) of its rows).
+        n_groups None: the largest value in either array plus one."""
+        q = None if queries is None else _as_2d_f32(queries, self.dim)
+        n = int(np.asarray(query_group).size) if q is None else int(q.shape[0])
+        rg, qg, ng = _group_args(row_group, query_group, n_groups, n)
+        ids = np.empty((n, k), dtype=np.int32)
+        d = np.empty((n, k), dtype=np.float32)
+        self._check(lib.hnswdev_exact_knn_grouped(self._ctx, None if q is None else q.ctypes.data_as(_F), n, (1 << 62) if n_rows is None else int(n_rows),
+                                                  int(k), rg.ctypes.data_as(_I), rg.shape[0], qg.ctypes.data_as(_I), ng, ids.ctypes.data_as(_I),
+                                                  d.ctypes.data_as(_F)))
+        return ids, d
+
+    def exact_grouped_info(self) -> dict:
+        """Counters of exact_knn_grouped since reset_stats (hnswdev_exact_grouped_info)."""
+        out = (ct.c_uint64 * 4)()
+        self._check(lib.hnswdev_exact_grouped_info(self._ctx, out))
+        return dict(zip(_EXACT_GROUPED_INFO, (int(v) for v in out)))
+
+    def exact_grouped_list_ms(self) -> float:
+        """HIP-event milliseconds of exact_knn_grouped's list-building kernels while profiling was on, since reset_stats."""
+        out = ct.c_double(0.0)
+        self._check(lib.hnswdev_exact_grouped_list_ms(self._ctx, ct.byref(out)))
+        return float(out.value)
 
     def exact_range(self, queries, radius: float, n_rows=None, allowed=None):
         """hnswdev_exact_range: (list of ids, list of dists), per query every uploaded row of [0, n_rows) (None: all) that `allowed`

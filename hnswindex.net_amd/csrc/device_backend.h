@@ -340,6 +340,18 @@ public:
     size_t exact_range_total() const { return xr_ids_.size(); }
     // lists of >= 2 entries ordered on the device, lists ordered on the host, rounds repeated with exact capacities, results returned
     void exact_range_info(uint64_t out[4]) const { for (int i = 0; i < 4; ++i) out[i] = xr_info_[i]; }
+    // hnswdev_exact_knn_grouped: exact_knn with a candidate set per query.  Query i's candidates are the uploaded
+    // ids j < min(n_rows, uploaded, n_row_group) with row_group[j] == query_group[i]; a row_group value outside [0, n_groups) puts
+    // the id in no group, a query_group value outside it is an error (nothing is written).  The groups' id lists are built on the
+    // device from row_group (one upload, one copy back of the n_groups counts) and every group is scanned in the same launch.
+    // Everything else -- distances, order, padding, k, queries == nullptr, the untouched resident set -- is exact_knn's.  Synchronous.
+    bool exact_knn_grouped(const float *queries, int nq, long long n_rows, int k, const int *row_group, long long n_row_group, const int *query_group,
+                           int n_groups, int *out_ids, float *out_d);
+    // grouped calls that launched, groups scanned (a query and a candidate each), scan blocks launched, ids placed in group lists
+    // (all four count the calls that launched a scan only)
+    void exact_grouped_info(uint64_t out[4]) const { for (int i = 0; i < 4; ++i) out[i] = xg_info_[i]; }
+    // HIP-event time of the list-building kernels (count, offsets, place) of the grouped calls made while profiling was on
+    double exact_grouped_list_ms() const { return xg_list_ms_; }
     // hnswdev_graph_info / hnswdev_graph_components (dk_graph_info.h): HNSWInfo.LayerInfo (HNSWInfo.cs:18-43) and the
     // number of weakly connected components (GraphNavigator.cs:350-419) of one layer of the mirror, computed on the device from the
     // mirror as it stands; nothing of it is copied back.  The layer's members: ids < graph_nodes() that are live -- live_bits ==
@@ -460,6 +472,12 @@ private:
     std::vector<int> xr_ids_;             // ... the call's results until the next call (exact_range_results)
     std::vector<float> xr_d_;
     uint64_t xr_info_[4] = {0, 0, 0, 0};
+    DevBuf<int> x_grow_;                  // exact_knn_grouped: row_group as uploaded
+    DevBuf<int> x_gcnt_;                  // ... per group: [members | offset of its segment in x_ids_ | the placing kernel's cursor]
+    DevBuf<int> x_gperm_;                 // ... queries == NULL: where each query of the sorted order is in the resident set
+    DevBuf<unsigned char> x_gwork_;       // ... a round's tables: [ExactMergeItem per query | ExactWorkItem per scan block]
+    uint64_t xg_info_[4] = {0, 0, 0, 0};
+    double xg_list_ms_ = 0.0;
     bool graph_info_begin(const char *who, int layer, const uint32_t *live_bits, long long nbits, LayerView *g);
     bool graph_info_fetch(const GraphAcc **acc);
     DevBuf<unsigned long long> gi_acc_; // graph_info / graph_components: the call's GraphAcc

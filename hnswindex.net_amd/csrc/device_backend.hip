@@ -913,6 +913,8 @@ void Device::reset_stats()
     stats_ = hnswdev_stats{};
     stats_.row_bytes = rb;
     for (uint64_t &v : xr_info_) v = 0;
+    for (uint64_t &v : xg_info_) v = 0;
+    xg_list_ms_ = 0.0;
     for (uint64_t &v : gi_info_) v = 0;
 #ifdef EXP_PHASE_CLOCKS
     (void)hipDeviceSynchronize();
@@ -2596,6 +2598,223 @@ bool Device::exact_knn(const float *queries, int nq, long long n_rows, int k, co
     return true;
 }
 
+// ---- hnswdev_exact_knn_grouped: a candidate group per query, every group scanned in one launch --------
+// The groups' id lists are a CSR in x_ids_, built on the device from row_group; the counts come back in one copy.  The queries are
+// uploaded sorted by group (stable), so a group's queries are a run that is cut into tiles, and its list into chunks: a scan block
+// is one (tile, chunk) pair read from a table.  Chunks: the (tile, row) work of the call spread over about two blocks per CU, no
+// chunk shorter than 1 024 rows, at most 4 096 per group -- a large group gets more chunks than a small one; `exact_chunk` forces
+// the rows per chunk and `exact_qtile` the tile for every group.  Rounds are ranges of the CALLER's order (at most 1 GiB of lists
+// and 2^24 output entries each); the sort is inside a round, so a round's results are rows [off, off + nr) of the output.
+bool Device::exact_knn_grouped(const float *queries, int nq, long long n_rows, int k, const int *row_group, long long n_row_group, const int *query_group,
+                               int n_groups, int *out_ids, float *out_d)
+{
+    if (nq <= 0) return true;
+    if (!out_ids || !out_d || k < 1 || n_rows < 0) { set_dev_error("exact_knn_grouped: bad argument"); return false; }
+    if (!row_group || n_row_group < 0) { set_dev_error("exact_knn_grouped: row_group must not be NULL and n_row_group must be >= 0"); return false; }
+    if (!query_group) { set_dev_error("exact_knn_grouped: query_group must not be NULL"); return false; }
+    if (k > kExactMaxK) { set_dev_error("exact_knn_grouped: k = " + std::to_string(k) + " is above the limit of " + std::to_string(kExactMaxK)); return false; }
+    if (n_groups < 1 || n_groups > kExactMaxGroups) {
+        set_dev_error("exact_knn_grouped: n_groups = " + std::to_string(n_groups) + " is outside 1 .. " + std::to_string(kExactMaxGroups));
+        return false;
+    }
+    std::vector<int> gq((size_t)n_groups, 0); // queries per group
+    for (int i = 0; i < nq; ++i) {
+        const int g = query_group[i];
+        if (g < 0 || g >= n_groups) {
+            set_dev_error("exact_knn_grouped: query_group[" + std::to_string(i) + "] = " + std::to_string(g) + " is outside 0 .. n_groups - 1 = " + std::to_string(n_groups - 1));
+            return false;
+        }
+        gq[(size_t)g] += 1;
+    }
+    // ids that exist and have a group: a row beyond what was uploaded is never dereferenced, whatever n_rows and n_row_group say
+    const long long n = std::min({n_rows, n_rows_hw_, n_row_group});
+    if (n <= 0) { pad_results(out_ids, out_d, (size_t)nq * (size_t)k); return true; }
+    if (!queries && (nq > n_queries_ || tail_.n > 0)) {
+        set_dev_error("exact_knn_grouped: queries == NULL needs a resident query set of at least nq rows (hnswdev_set_queries)");
+        return false;
+    }
+    if (!bind()) return false;
+    hipStream_t st = S(stream_);
+
+    // the group lists: row_group up, counts | offsets | cursors and the members on the device, the counts back
+    const size_t G = (size_t)n_groups, rg_bytes = 4 * (size_t)n;
+    if (!x_grow_.grow((size_t)n) || !x_gcnt_.grow(3 * G) || !x_ids_.grow((size_t)n)) return false;
+    std::vector<int> cnt(G), goff(G); // members of each group, where its segment starts in x_ids_
+    uint64_t listed = 0;
+    {
+        const size_t staged = rg_bytes < (4u << 20) ? rg_bytes : 0; // larger arrays go up in pieces, as query sets do
+        char *hs = static_cast<char *>(pinned_stage(staged + 4 * G));
+        if (!hs) return false;
+        if (staged) { memcpy(hs, row_group, rg_bytes); HIP_OK(hipMemcpyAsync(x_grow_, hs, rg_bytes, hipMemcpyHostToDevice, st)); }
+        else if (!staged_upload(reinterpret_cast<float *>(x_grow_.get()), reinterpret_cast<const float *>(row_group), rg_bytes)) return false;
+        const bool timed = profiling_; // the list-building kernels have an event pair of their own (exact_grouped_list_ms)
+        if (timed && (!ev0_.create(true) || !ev1_.create(true))) return false;
+        if (timed) HIP_OK(hipEventRecord(E(ev0_), st));
+        HIP_OK(exact_group_lists_launch(x_grow_, n, n_groups, x_gcnt_, x_gcnt_.get() + G, x_gcnt_.get() + 2 * G, x_ids_, st));
+        if (timed) HIP_OK(hipEventRecord(E(ev1_), st));
+        HIP_OK(hipMemcpyAsync(hs + staged, x_gcnt_, 4 * G, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+        if (timed) {
+            float ms = 0.f;
+            HIP_OK(hipEventElapsedTime(&ms, E(ev0_), E(ev1_)));
+            xg_list_ms_ += ms;
+        }
+        memcpy(cnt.data(), hs + staged, 4 * G); // (the stage is used again for the queries)
+        long long at = 0;
+        for (size_t g = 0; g < G; ++g) { goff[g] = (int)at; at += cnt[g]; }
+        if (at > n) { set_dev_error("exact_knn_grouped: the group counts exceed the ids"); return false; }
+        listed = (uint64_t)at;
+    }
+    int max_gq = 0;
+    uint64_t scanned = 0;
+    for (size_t g = 0; g < G; ++g)
+        if (gq[g] > 0 && cnt[g] > 0) { max_gq = std::max(max_gq, gq[g]); scanned += 1; }
+    if (scanned == 0) { pad_results(out_ids, out_d, (size_t)nq * (size_t)k); return true; } // no query has a candidate: padding, no scan
+
+    // the tile (one for the call: the LDS layout is the launch's) and each scanned group's chunks
+    const ExactPlan tp = exact_plan(max_gq, 1, k, pitch_, num_cu_);
+    if (tp.lds > 64 * 1024) { set_dev_error("exact_knn_grouped: tile exceeds the LDS budget"); return false; }
+    const int qt = tp.qtile;
+    const long long forced_c = diag("exact_chunk", 0);
+    long long work = 0; // (tile, row) pairs of the call
+    for (size_t g = 0; g < G; ++g)
+        if (gq[g] > 0 && cnt[g] > 0) work += (long long)((gq[g] + qt - 1) / qt) * cnt[g];
+    const long long target = std::max<long long>(1024, (work + 2LL * num_cu_ - 1) / (2LL * num_cu_));
+    std::vector<int> gchunk(G, 0), gnch(G, 0); // rows per chunk, chunks (0: not scanned)
+    for (size_t g = 0; g < G; ++g) {
+        if (gq[g] <= 0 || cnt[g] <= 0) continue;
+        const long long m = cnt[g];
+        long long chunks = forced_c > 0 ? (m + forced_c - 1) / forced_c : std::max<long long>(1, std::min<long long>((m + target - 1) / target, m / 1024));
+        chunks = std::min<long long>(chunks, kExactMaxChunks);
+        long long chunk = (m + chunks - 1) / chunks;
+        if (forced_c <= 0) chunk = (chunk + kExactIterRows - 1) / kExactIterRows * kExactIterRows;
+        gchunk[g] = (int)chunk;
+        gnch[g] = (int)((m + chunk - 1) / chunk);
+    }
+
+    // rounds: ranges of the caller's order within both budgets; inside each the queries sorted by group (counting sort: stable)
+    const long long lists_cap = (1LL << 30) / ((long long)k * 8), out_cap = std::max<long long>(1, (1LL << 24) / k);
+    std::vector<int> round_end; // one past the last query of each round
+    {
+        long long lists = 0, rows = 0;
+        for (int i = 0; i < nq; ++i) {
+            const long long c = gnch[(size_t)query_group[i]];
+            if (rows > 0 && (lists + c > lists_cap || rows + 1 > out_cap)) { round_end.push_back(i); lists = 0; rows = 0; }
+            lists += c; rows += 1;
+        }
+        round_end.push_back(nq);
+    }
+    std::vector<int> order((size_t)nq); // sorted position -> the caller's index
+    {
+        std::vector<int> at(G + 1);
+        int r0 = 0;
+        for (const int r1 : round_end) {
+            std::fill(at.begin(), at.end(), 0);
+            for (int i = r0; i < r1; ++i) at[(size_t)query_group[i] + 1] += 1;
+            for (size_t g = 0; g < G; ++g) at[g + 1] += at[g];
+            for (int i = r0; i < r1; ++i) order[(size_t)r0 + (size_t)at[(size_t)query_group[i]]++] = i;
+            r0 = r1;
+        }
+    }
+
+    // the queries in sorted order: uploaded through set_queries' path, or gathered from the resident set on the device
+    const float *d_q;
+    const double *d_qsn;
+    if (queries) {
+        std::vector<float> sorted((size_t)nq * (size_t)dim_);
+        for (int p = 0; p < nq; ++p) memcpy(&sorted[(size_t)p * dim_], queries + (size_t)order[(size_t)p] * dim_, sizeof(float) * (size_t)dim_);
+        if (!exact_queries("exact_knn_grouped", sorted.data(), nq, &d_q, &d_qsn)) return false;
+    } else {
+        if (!x_queries_.grow((size_t)nq * pitch_, (size_t)std::max(nq, 1024) * pitch_) || (metric_ == M_COS && !x_q_sn_.grow((size_t)nq, (size_t)std::max(nq, 1024)))) return false;
+        if (!x_gperm_.grow((size_t)nq)) return false;
+        int *hp = static_cast<int *>(pinned_stage(4 * (size_t)nq));
+        if (!hp) return false;
+        memcpy(hp, order.data(), 4 * (size_t)nq);
+        HIP_OK(hipMemcpyAsync(x_gperm_, hp, 4 * (size_t)nq, hipMemcpyHostToDevice, st));
+        HIP_OK(exact_gather_queries_launch(d_queries_, metric_ == M_COS ? d_q_sn_.get() : nullptr, x_gperm_, nq, pitch_, x_queries_, x_q_sn_, st));
+        HIP_OK(hipStreamSynchronize(st)); // the pinned stage is used again below
+        d_q = x_queries_; d_qsn = metric_ == M_COS ? x_q_sn_.get() : nullptr;
+    }
+
+    if (!x_evals_.grow(1)) return false;
+    if (!ev0_.create(true) || !ev1_.create(true)) return false;
+    std::vector<ExactMergeItem> mi;
+    std::vector<ExactWorkItem> wi;
+    bool launched = false;
+    int off = 0;
+    for (const int r1 : round_end) {
+        const int nr = r1 - off;
+        // the round's tables: a run of one group's queries at a time
+        mi.resize((size_t)nr);
+        wi.clear();
+        long long lists = 0;
+        for (int p = 0; p < nr;) {
+            const int g = query_group[order[(size_t)(off + p)]];
+            int e = p + 1;
+            while (e < nr && query_group[order[(size_t)(off + e)]] == g) ++e;
+            const int nch = gnch[(size_t)g], m = cnt[(size_t)g], chunk = gchunk[(size_t)g];
+            for (int j = p; j < e; ++j) mi[(size_t)j] = ExactMergeItem{lists + (long long)(j - p) * nch, nch, order[(size_t)(off + j)] - off};
+            if (nch > 0) {
+                for (int t = p; t < e; t += qt)
+                    for (int c = 0; c < nch; ++c) {
+                        const int lo = c * chunk; // (chunk * nch < m + chunk: no overflow of int while m is one)
+                        wi.push_back(ExactWorkItem{t, std::min(qt, e - t), goff[(size_t)g] + lo, std::min(chunk, m - lo), lists + (long long)(t - p) * nch, nch, c});
+                    }
+                lists += (long long)(e - p) * nch;
+            }
+            p = e;
+        }
+        const size_t res = 4u * (size_t)nr * k, b_mi = sizeof(ExactMergeItem) * (size_t)nr, b_wi = sizeof(ExactWorkItem) * wi.size();
+        if (wi.empty()) { // no query of this round has a candidate
+            pad_results(out_ids + (size_t)off * k, out_d + (size_t)off * k, (size_t)nr * (size_t)k);
+            off = r1;
+            continue;
+        }
+        char *hs = static_cast<char *>(pinned_stage(2 * res + 8 + b_mi + b_wi));
+        if (!hs || !x_out_.grow(2 * (size_t)nr * k) || !x_lists_.grow((size_t)lists * k) || !x_gwork_.grow(b_mi + b_wi)) return false;
+        int *d_ids = x_out_;
+        float *d_d = reinterpret_cast<float *>(x_out_.get() + (size_t)nr * k);
+        unsigned long long *h_ev = reinterpret_cast<unsigned long long *>(hs + 2 * res);
+        char *h_tab = hs + 2 * res + 8;
+        memcpy(h_tab, mi.data(), b_mi);
+        memcpy(h_tab + b_mi, wi.data(), b_wi);
+        HIP_OK(hipMemcpyAsync(x_gwork_, h_tab, b_mi + b_wi, hipMemcpyHostToDevice, st));
+        ExactScanArgs a;
+        a.rows = d_rows_; a.row_sn = d_row_sn_;
+        a.queries = d_q + (size_t)off * pitch_;
+        a.q_sn = d_qsn ? d_qsn + off : nullptr;
+        a.dim = pitch_; a.ids = x_ids_; a.m = 0; a.chunk = 0; a.nq = nr; a.qtile = qt; a.piece = tp.piece; a.k = k;
+        a.lists = x_lists_; a.n_chunks = 0; a.evals = x_evals_;
+        ExactTopKGrouped sink;
+        sink.items = reinterpret_cast<const ExactWorkItem *>(x_gwork_.get() + b_mi);
+        const bool timed = profiling_;
+        HIP_OK(hipMemsetAsync(x_evals_, 0, sizeof(unsigned long long), st));
+        if (timed) HIP_OK(hipEventRecord(E(ev0_), st));
+        hipError_t e = hipSuccess;
+        with_metric(metric_, [&](auto mt) { e = exact_grouped_scan_launch<mt>(a, sink, (unsigned)wi.size(), tp.lds, st); });
+        HIP_OK(e);
+        HIP_OK(exact_merge_grouped_launch(x_lists_, reinterpret_cast<const ExactMergeItem *>(x_gwork_.get()), k, nr, d_ids, d_d, st));
+        if (timed) HIP_OK(hipEventRecord(E(ev1_), st));
+        HIP_OK(hipMemcpyAsync(hs, d_ids, res, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(hs + res, d_d, res, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(h_ev, x_evals_, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+        memcpy(out_ids + (size_t)off * k, hs, res);
+        memcpy(out_d + (size_t)off * k, hs + res, res);
+        stats_.exact_launches += 1; stats_.exact_evals += *h_ev;
+        xg_info_[2] += wi.size();
+        launched = true;
+        if (timed) {
+            float ms = 0.f;
+            HIP_OK(hipEventElapsedTime(&ms, E(ev0_), E(ev1_)));
+            stats_.exact_kernel_ms += ms; stats_.exact_timed_launches += 1; stats_.exact_timed_evals += *h_ev;
+        }
+        off = r1;
+    }
+    if (launched) { xg_info_[0] += 1; xg_info_[1] += scanned; xg_info_[3] += listed; } // (a call that scans nothing counts nowhere)
+    return true;
+}
+
 // ---- hnswdev_exact_range: the same scan with the range sink -------------------------------------------
 // Pass A scans a round of queries with one capacity for each (the arena's entries / the round's queries, or less: the picker
 // stops at kExactRangePickCap, `exact_range_cap` forces it).  The counts come back exact; where one exceeds its capacity the round
@@ -3194,6 +3413,26 @@ DEV_API int hnswdev_exact_range_info(void *ctx, uint64_t out[4])
     CTX_OR_FAIL();
     if (!out) return -1;
     d->exact_range_info(out);
+    return 0;
+}
+DEV_API int hnswdev_exact_knn_grouped(void *ctx, const float *queries, int nq, long long n_rows, int k, const int *row_group, long long n_row_group,
+                                      const int *query_group, int n_groups, int *out_ids, float *out_dists)
+{
+    CTX_OR_FAIL();
+    return d->exact_knn_grouped(queries, nq, n_rows, k, row_group, n_row_group, query_group, n_groups, out_ids, out_dists) ? 0 : -1;
+}
+DEV_API int hnswdev_exact_grouped_info(void *ctx, uint64_t out[4])
+{
+    CTX_OR_FAIL();
+    if (!out) return -1;
+    d->exact_grouped_info(out);
+    return 0;
+}
+DEV_API int hnswdev_exact_grouped_list_ms(void *ctx, double *out_ms)
+{
+    CTX_OR_FAIL();
+    if (!out_ms) return -1;
+    *out_ms = d->exact_grouped_list_ms();
     return 0;
 }
 DEV_API int hnswdev_graph_info(void *ctx, int layer, const uint32_t *live_bits, long long nbits, int with_in_edges, hnsw_mi355x_layer_info *out)

@@ -8,6 +8,12 @@
 // kernel takes its sink as a type -- ExactTopK, the lists above, or ExactRange:
 //   exact_scan_kernel<M, ExactRange>  keys with d <= range go from the pending lists to the query's segment of an arena; the count per query is exact
 //   exact_range_sort_kernel           one block per query: a segment of up to kExactRangeSortMax keys ordered in LDS -> ids and distances
+// and hnswdev_exact_knn_grouped: a candidate group per query.  row_group[id] names the group of an id; the groups' id
+// lists are built on the device as one CSR and the scan's blocks take their (queries, list segment) from a table of work items:
+//   exact_group_kernel<false> / exact_group_offsets_kernel / exact_group_kernel<true>   row_group -> counts, offsets, the members of each group in its segment (unordered)
+//   exact_gather_queries_kernel                 the resident queries in the call's sorted order (queries == NULL)
+//   exact_scan_kernel<M, ExactTopKGrouped>      a block = one work item: a tile of one group's queries x a chunk of that group's list
+//   exact_merge_grouped_kernel                  one wave per query: its chunks' lists -> the final k at the query's original row
 // The kernels are compiled in the exact_<metric> units (exact_unit.hip, HNSW_EXACT_UNIT) and reached through the launchers declared here, so
 // that device_backend.hip holds none of their code.
 #pragma once
@@ -26,6 +32,8 @@ constexpr int kExactMaxK = 1024;
 constexpr int kExactMaxQTile = 32;
 constexpr int kExactCompactWords = 256; // bitset words per block of exact_compact_kernel (one per thread)
 constexpr int kExactRangeSortMax = 4096; // keys exact_range_sort_kernel orders in LDS (32 KB); longer lists are ordered on the host
+constexpr int kExactMaxGroups = 65536;   // groups of exact_knn_grouped: exact_group_offsets_kernel is one block that walks the counts
+constexpr int kExactMaxChunks = 4096;    // chunks per query (the merge walks them)
 
 struct ExactScanArgs {
     const float *rows;      // stored rows (f32 rows, int8 records, f16 records)
@@ -52,9 +60,11 @@ struct ExactScanArgs {
 // unused for this sink.)
 struct ExactTopK {
     static constexpr bool kRange = false;
+    static constexpr bool kGrouped = false;
 };
 struct ExactRange {
     static constexpr bool kRange = true;
+    static constexpr bool kGrouped = false;
     float range;
     unsigned *counts;              // [nq]
     const long long *seg_off;      // [nq + 1]
@@ -68,6 +78,27 @@ struct ExactRangeSortArgs {
     int *out_ids;
     float *out_d;
     int sort_max;                  // lists longer than this (<= kExactRangeSortMax) are left to the host
+};
+
+// ExactTopKGrouped: ExactTopK's lists, but block b of a 1-D grid takes its queries and its rows from items[b] instead of from
+// blockIdx and ExactScanArgs::m / chunk / nq / n_chunks (not read for this sink).  ExactScanArgs::ids is the groups' CSR, queries
+// the round's queries sorted by group, qtile the LDS layout's tile (an item has at most that many queries).
+struct ExactWorkItem {
+    int q0, nq;          // the tile: queries [q0, q0 + nq) of the round, one group's, 1 <= nq <= qtile
+    int off, len;        // the chunk: entries [off, off + len) of ids, len >= 1
+    long long list0;     // the first list of query q0: query q0 + i, chunk slot c writes list list0 + i * n_chunks + c
+    int n_chunks, slot;  // chunks of this group's list, and which of them this is
+};
+struct ExactTopKGrouped {
+    static constexpr bool kRange = false;
+    static constexpr bool kGrouped = true;
+    const ExactWorkItem *items;
+};
+// what exact_merge_grouped_kernel reads per query of the round (in sorted order)
+struct ExactMergeItem {
+    long long list0;     // its first list
+    int n_chunks;        // 0: its group has no member, the row is padding
+    int out_row;         // its row of the round's output: the query's original place in the round
 };
 
 // LDS of one scan block
@@ -85,6 +116,14 @@ hipError_t exact_range_scan_launch(const ExactScanArgs &a, const ExactRange &sin
 hipError_t exact_compact_launch(const unsigned *words, long long n_words, const long long *block_off, int *out_ids, hipStream_t st);
 hipError_t exact_merge_launch(const unsigned long long *lists, int n_chunks, int k, int nq, int *out_ids, float *out_d, hipStream_t st);
 hipError_t exact_range_sort_launch(const ExactRangeSortArgs &a, int nq, hipStream_t st);
+template <int METRIC>
+hipError_t exact_grouped_scan_launch(const ExactScanArgs &a, const ExactTopKGrouped &sink, unsigned n_items, size_t lds, hipStream_t st);
+// row_group[0, n) -> counts[g] (zeroed here), offsets[g] (exclusive prefix), ids: group g's members in [offsets[g], offsets[g] + counts[g]),
+// in no particular order; values outside [0, n_groups) are in no group.  cursors: n_groups ints of scratch.
+hipError_t exact_group_lists_launch(const int *row_group, long long n, int n_groups, int *counts, int *offsets, int *cursors, int *ids, hipStream_t st);
+// dst row i = src row perm[i] (words 4-byte words each), dst_sn[i] = src_sn[perm[i]] where src_sn is not nullptr
+hipError_t exact_gather_queries_launch(const float *src, const double *src_sn, const int *perm, int nq, int words, float *dst, double *dst_sn, hipStream_t st);
+hipError_t exact_merge_grouped_launch(const unsigned long long *lists, const ExactMergeItem *items, int k, int nq, int *out_ids, float *out_d, hipStream_t st);
 
 } // namespace hnsw
 
@@ -142,8 +181,28 @@ __global__ void __launch_bounds__(kExactThreads) exact_scan_kernel(const ExactSc
     unsigned long long *thr = lists + (size_t)QTR * k;
     unsigned long long *pend = thr + QTR;
     int *pend_cnt = reinterpret_cast<int *>(pend + RQ * kExactIterRows);
-    const long long q0 = (long long)blockIdx.x * QT;
-    const long long lo = (long long)blockIdx.y * a.chunk, hi = lo + a.chunk < a.m ? lo + a.chunk : a.m;
+    // the block's queries [q0, q0 + its number) of the round and entries [lo, hi) of the id list: a work item's, or worked out from
+    // blockIdx.  q_in: a query of the round that this block answers; q_clamp: past the last of them a slot shadows it.
+    long long q0, lo, hi;
+    [[maybe_unused]] int item_qend = 0;
+    if constexpr (SINK::kGrouped) { // (the item is the same for the whole block: its fields are kept in scalar registers)
+        const ExactWorkItem &it = sink.items[blockIdx.x];
+        const int iq0 = __builtin_amdgcn_readfirstlane(it.q0), ioff = __builtin_amdgcn_readfirstlane(it.off);
+        item_qend = iq0 + __builtin_amdgcn_readfirstlane(it.nq);
+        q0 = iq0;
+        lo = ioff; hi = ioff + __builtin_amdgcn_readfirstlane(it.len);
+    } else {
+        q0 = (long long)blockIdx.x * QT;
+        lo = (long long)blockIdx.y * a.chunk; hi = lo + a.chunk < a.m ? lo + a.chunk : a.m;
+    }
+    const auto q_in = [&](long long q) {
+        if constexpr (SINK::kGrouped) return q < item_qend;
+        else return q < a.nq;
+    };
+    const auto q_clamp = [&](long long q) {
+        if constexpr (SINK::kGrouped) return q >= item_qend ? item_qend - 1 : q;
+        else { if (q >= a.nq) q = a.nq - 1; return q; }
+    };
     const int rw = row_words<METRIC>(dim);
     const int nblk = dim >> 3;
 
@@ -168,7 +227,7 @@ __global__ void __launch_bounds__(kExactThreads) exact_scan_kernel(const ExactSc
             rid[r] = a.ids ? a.ids[idx] : (int)idx;
             rp[r] = a.rows + (size_t)rid[r] * (size_t)rw;
         }
-        for (int qsub = 0; qsub < QT && q0 + qsub < a.nq; qsub += RQ) {
+        for (int qsub = 0; qsub < QT && q_in(q0 + qsub); qsub += RQ) {
             float acc[RQ][RR];
             int iacc[RQ][RR], ta[RR], tb[RQ];
             float dist[RQ][RR];
@@ -183,8 +242,7 @@ __global__ void __launch_bounds__(kExactThreads) exact_scan_kernel(const ExactSc
                 if (npieces > 1 || !staged) { // the queries of the tile, words [w0, w1); past the last query a slot shadows it
                     __syncthreads();
                     for (int qi = wave; qi < QTR; qi += kExactThreads / 64) {
-                        long long src = q0 + qi;
-                        if (src >= a.nq) src = a.nq - 1;
+                        const long long src = q_clamp(q0 + qi);
                         const float *s = a.queries + (size_t)src * dim + w0;
                         for (int o = lane; o < len; o += 64) qs[(size_t)qi * qw + o] = s[o];
                     }
@@ -274,9 +332,7 @@ __global__ void __launch_bounds__(kExactThreads) exact_scan_kernel(const ExactSc
                     for (int q = 0; q < RQ; ++q) {
                         double sqn = 0.0;
                         if constexpr (METRIC == M_COS) {
-                            long long src = q0 + qsub + q;
-                            if (src >= a.nq) src = a.nq - 1;
-                            sqn = a.q_sn[src];
+                            sqn = a.q_sn[q_clamp(q0 + qsub + q)];
                         }
 #pragma unroll
                         for (int r = 0; r < RR; ++r) {
@@ -303,7 +359,7 @@ __global__ void __launch_bounds__(kExactThreads) exact_scan_kernel(const ExactSc
                 if (j == 0) {
 #pragma unroll
                     for (int q = 0; q < RQ; ++q) {
-                        if (qsub + q >= QT || q0 + qsub + q >= a.nq) continue;
+                        if (qsub + q >= QT || !q_in(q0 + qsub + q)) continue;
 #pragma unroll
                         for (int r = 0; r < RR; ++r) {
                             if (!rvalid[r]) continue;
@@ -339,7 +395,7 @@ __global__ void __launch_bounds__(kExactThreads) exact_scan_kernel(const ExactSc
                 if (j == 0) {
 #pragma unroll
                     for (int q = 0; q < RQ; ++q) {
-                        if (qsub + q >= QT || q0 + qsub + q >= a.nq) continue;
+                        if (qsub + q >= QT || !q_in(q0 + qsub + q)) continue;
                         const unsigned long long t = thr[qsub + q];
 #pragma unroll
                         for (int r = 0; r < RR; ++r) {
@@ -373,8 +429,12 @@ __global__ void __launch_bounds__(kExactThreads) exact_scan_kernel(const ExactSc
     __syncthreads();
     if (measured) atomicAdd(a.evals, (unsigned long long)measured); // one atomic per group that measured anything
     if constexpr (!SINK::kRange) {
-        for (int qi = 0; qi < QT && q0 + qi < a.nq; ++qi) {
-            unsigned long long *dst = a.lists + ((size_t)(q0 + qi) * a.n_chunks + blockIdx.y) * (size_t)k;
+        for (int qi = 0; qi < QT && q_in(q0 + qi); ++qi) {
+            unsigned long long *dst;
+            if constexpr (SINK::kGrouped) { // (the item is read again here rather than kept in registers through the scan)
+                const ExactWorkItem &it = sink.items[blockIdx.x];
+                dst = a.lists + (size_t)(it.list0 + (long long)qi * it.n_chunks + it.slot) * (size_t)k;
+            } else dst = a.lists + ((size_t)(q0 + qi) * a.n_chunks + blockIdx.y) * (size_t)k;
             for (int i = tid; i < k; i += kExactThreads) dst[i] = lists[(size_t)qi * k + i];
         }
     }
@@ -390,6 +450,13 @@ template <int METRIC>
 hipError_t exact_range_scan_launch(const ExactScanArgs &a, const ExactRange &sink, unsigned n_qtiles, size_t lds, hipStream_t st)
 {
     hipLaunchKernelGGL((exact_scan_kernel<METRIC, ExactRange>), dim3(n_qtiles, (unsigned)a.n_chunks), dim3(kExactThreads), lds, st, a, sink);
+    return hipGetLastError();
+}
+
+template <int METRIC>
+hipError_t exact_grouped_scan_launch(const ExactScanArgs &a, const ExactTopKGrouped &sink, unsigned n_items, size_t lds, hipStream_t st)
+{
+    hipLaunchKernelGGL((exact_scan_kernel<METRIC, ExactTopKGrouped>), dim3(n_items), dim3(kExactThreads), lds, st, a, sink);
     return hipGetLastError();
 }
 
@@ -487,6 +554,132 @@ __global__ void __launch_bounds__(256) exact_range_sort_kernel(const ExactRangeS
     }
 }
 
+// ---- the group lists of exact_knn_grouped: a CSR over the groups, built from row_group in three launches ----
+// One thread per id.  The lanes of a wave that hold the same group are served by one atomic: the wave takes the group of its first
+// unserved lane, ballots the lanes that share it, and that lane adds their number (with thousands of ids per group a wave would
+// otherwise send 64 atomics to a handful of addresses).  PLACE: the add returns the first free place of the group's segment and
+// lane r of the sharing lanes writes its id r places further -- the order inside a segment is that of the atomics: unordered.
+template <bool PLACE>
+__global__ void __launch_bounds__(256) exact_group_kernel(const int *__restrict__ row_group, long long n, int n_groups, int *__restrict__ counters,
+                                                          int *__restrict__ ids)
+{
+    const long long id = (long long)blockIdx.x * 256 + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    int g = id < n ? row_group[id] : -1;
+    if (g < 0 || g >= n_groups) g = -1;
+    unsigned long long todo = __ballot(g >= 0);
+    while (todo) { // wave-uniform: every lane sees the same mask
+        const int lead = __ffsll((long long)todo) - 1;
+        const int gl = __shfl(g, lead, 64);
+        const unsigned long long same = __ballot(g == gl) & todo; // (lanes with g == -1 never match: gl >= 0)
+        int first = 0;
+        if (lane == lead) first = atomicAdd(&counters[gl], __popcll(same));
+        if constexpr (PLACE) {
+            first = __shfl(first, lead, 64);
+            if (g == gl) ids[first + __popcll(same & ((1ull << lane) - 1ull))] = (int)id;
+        }
+        todo &= ~same;
+    }
+}
+
+// offsets[g] = cursors[g] = the counts in front of group g.  One block walks the counts 256 at a time (at most kExactMaxGroups of
+// them): a wave prefix by shuffles, the wave totals through LDS, the running total carried by every thread.
+__global__ void __launch_bounds__(256) exact_group_offsets_kernel(const int *__restrict__ counts, int n_groups, int *__restrict__ offsets,
+                                                                  int *__restrict__ cursors)
+{
+    __shared__ int wave_total[4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int carry = 0;
+    for (int base = 0; base < n_groups; base += 256) { // (n_groups is the same for all threads: so is every barrier)
+        const int g = base + tid;
+        const int c = g < n_groups ? counts[g] : 0;
+        int incl = c;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const int o = __shfl_up(incl, d, 64);
+            if (lane >= d) incl += o;
+        }
+        if (lane == 63) wave_total[wave] = incl;
+        __syncthreads();
+        int pos = carry + incl - c, total = 0;
+        for (int i = 0; i < 4; ++i) {
+            if (i < wave) pos += wave_total[i];
+            total += wave_total[i];
+        }
+        if (g < n_groups) { offsets[g] = pos; cursors[g] = pos; }
+        carry += total;
+        __syncthreads(); // wave_total is written again in the next step
+    }
+}
+
+// The resident queries in the call's order: one wave per query, `words` 4-byte words each (the int8 record's words included).
+__global__ void __launch_bounds__(256) exact_gather_queries_kernel(const float *__restrict__ src, const double *__restrict__ src_sn, const int *__restrict__ perm,
+                                                                   int nq, int words, float *__restrict__ dst, double *__restrict__ dst_sn)
+{
+    const int q = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (q >= nq) return;
+    const int from = perm[q];
+    const float *s = src + (size_t)from * words;
+    float *d = dst + (size_t)q * words;
+    for (int o = lane; o < words; o += 64) d[o] = s[o];
+    if (src_sn && lane == 0) dst_sn[q] = src_sn[from];
+}
+
+// exact_merge_kernel with the query's lists and its output row read from a table: block q is query q of the round in sorted order,
+// and its result goes to the row the query has in the caller's order.  (A copy, not a shared body: with the loop in a function of
+// its own exact_merge_kernel compiles to other code -- 55 SGPRs for 57 -- and that kernel is to stay as it was.  A change to the
+// merge goes into both.)
+__global__ void __launch_bounds__(64) exact_merge_grouped_kernel(const unsigned long long *__restrict__ lists, const ExactMergeItem *__restrict__ items, int k,
+                                                                 int *__restrict__ out_ids, float *__restrict__ out_d)
+{
+    __shared__ unsigned long long L[kExactMaxK];
+    const int lane = threadIdx.x;
+    const ExactMergeItem it = items[blockIdx.x];
+    for (int i = lane; i < k; i += 64) L[i] = kExactEmpty;
+    wave_lds_sync();
+    for (int c = 0; c < it.n_chunks; ++c) {
+        const unsigned long long *src = lists + (size_t)(it.list0 + c) * (size_t)k;
+        bool more = true;
+        for (int i0 = 0; i0 < k && more; i0 += 64) {
+            const unsigned long long mine = i0 + lane < k ? src[i0 + lane] : kExactEmpty;
+            const int n = k - i0 < 64 ? k - i0 : 64;
+            for (int t = 0; t < n; ++t) {
+                const unsigned lo32 = __shfl((unsigned)mine, t, 64), hi32 = __shfl((unsigned)(mine >> 32), t, 64);
+                const unsigned long long x = ((unsigned long long)hi32 << 32) | lo32;
+                if (x >= L[k - 1]) { more = false; break; }
+                exact_list_insert(L, k, x, lane);
+            }
+        }
+    }
+    wave_lds_sync();
+    const size_t row = (size_t)it.out_row * (size_t)k;
+    for (int i = lane; i < k; i += 64) {
+        const unsigned long long key = L[i];
+        out_ids[row + i] = key == kExactEmpty ? -1 : (int)(unsigned)key;
+        out_d[row + i] = key == kExactEmpty ? __uint_as_float(0x7fc00000u) : exact_key_dist(key);
+    }
+}
+
+hipError_t exact_group_lists_launch(const int *row_group, long long n, int n_groups, int *counts, int *offsets, int *cursors, int *ids, hipStream_t st)
+{
+    const unsigned blocks = (unsigned)((n + 255) / 256);
+    hipError_t e = hipMemsetAsync(counts, 0, sizeof(int) * (size_t)n_groups, st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(exact_group_kernel<false>, dim3(blocks), dim3(256), 0, st, row_group, n, n_groups, counts, (int *)nullptr);
+    hipLaunchKernelGGL(exact_group_offsets_kernel, dim3(1), dim3(256), 0, st, counts, n_groups, offsets, cursors);
+    hipLaunchKernelGGL((exact_group_kernel<true>), dim3(blocks), dim3(256), 0, st, row_group, n, n_groups, cursors, ids);
+    return hipGetLastError();
+}
+hipError_t exact_gather_queries_launch(const float *src, const double *src_sn, const int *perm, int nq, int words, float *dst, double *dst_sn, hipStream_t st)
+{
+    hipLaunchKernelGGL(exact_gather_queries_kernel, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, st, src, src_sn, perm, nq, words, dst, dst_sn);
+    return hipGetLastError();
+}
+hipError_t exact_merge_grouped_launch(const unsigned long long *lists, const ExactMergeItem *items, int k, int nq, int *out_ids, float *out_d, hipStream_t st)
+{
+    hipLaunchKernelGGL(exact_merge_grouped_kernel, dim3((unsigned)nq), dim3(64), 0, st, lists, items, k, out_ids, out_d);
+    return hipGetLastError();
+}
 hipError_t exact_range_sort_launch(const ExactRangeSortArgs &a, int nq, hipStream_t st)
 {
     hipLaunchKernelGGL(exact_range_sort_kernel, dim3((unsigned)nq), dim3(256), 0, st, a);

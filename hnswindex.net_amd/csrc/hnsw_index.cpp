@@ -1700,6 +1700,46 @@ int HnswIndex::exact_knn_query(const float *queries, int count, int dim, int k, 
     return 0;
 }
 
+// The flat scan with a candidate group per query.  The counterpart of exact_candidates: while nothing has been
+// removed the caller's row_group goes to the device as it is; once slots are vacant a copy does, with the vacant slots in no group.
+int HnswIndex::exact_knn_query_grouped(const float *queries, int count, int dim, int k, const int *row_group, long long n_row_group, const int *query_group,
+                                       int n_groups, int *out_ids, float *out_dists, std::string &err)
+{
+    if (count <= 0) return 0;
+    if (failed(err)) return -1;
+    const char *who = "hnsw_mi355x_exact_knn_query_grouped";
+    if (k > 1024) { err = std::string("System.ArgumentOutOfRangeException: ") + who + ": k = " + std::to_string(k) + " is above the limit of 1024"; return -1; }
+    if (n_groups < 1 || n_groups > 65536) {
+        err = std::string("System.ArgumentOutOfRangeException: ") + who + ": n_groups = " + std::to_string(n_groups) + " is outside 1 .. 65536";
+        return -1;
+    }
+    for (int i = 0; i < count; ++i)
+        if (query_group[i] < 0 || query_group[i] >= n_groups) {
+            err = std::string("System.ArgumentOutOfRangeException: ") + who + ": query_group[" + std::to_string(i) + "] = " + std::to_string(query_group[i]) +
+                  " is outside 0 .. n_groups - 1 = " + std::to_string(n_groups - 1);
+            return -1;
+        }
+    if (k < 1 || graph_.count <= 0) {
+        pad_results(out_ids, out_dists, (size_t)count * (size_t)std::max(k, 0));
+        return 0;
+    }
+    if (!ensure_dim(dim, err)) return -1;
+    const long long length = graph_.length;
+    std::vector<int> live;
+    if (graph_.count != graph_.length) { // vacant slots: in no group
+        const long long n = std::min(n_row_group, length);
+        live.assign(row_group, row_group + n);
+        for (long long id = 0; id < n; ++id)
+            if (graph_.removed[(size_t)id]) live[(size_t)id] = -1;
+        row_group = live.data(); // (never NULL: the vector of an empty copy still hands the device no row)
+        n_row_group = n;
+        if (n == 0) { pad_results(out_ids, out_dists, (size_t)count * (size_t)k); return 0; }
+    }
+    // (the scan stages its queries in a buffer of its own: the resident set, sharded or not, stays what it was)
+    if (!dev_->exact_knn_grouped(queries, count, length, k, row_group, n_row_group, query_group, n_groups, out_ids, out_dists)) { err = get_dev_error(); return -1; }
+    return 0;
+}
+
 // The flat scan with the range sink: exact_knn_query's candidates; per query every one within `range`, ascending by
 // (distance, id).  counts[i], and the lists concatenated in query order in ids / dists.  Always on the device, on the primary context.
 int HnswIndex::exact_range_query(const float *queries, int count, int dim, float range, const uint32_t *allow_bits, long long nbits, int *counts,

@@ -63,6 +63,11 @@ public:
     // counts[count] and the lists concatenated in query order.  -1: counts are 0 and the lists empty.
     int exact_range_query(const float *queries, int count, int dim, float range, const uint32_t *allow_bits, long long nbits, int *counts,
                           std::vector<int> &ids, std::vector<float> &dists, std::string &err);
+    // hnsw_mi355x_exact_knn_query_grouped: exact_knn_query with a candidate group per query (Device::exact_knn_grouped):
+    // query i's candidates are the live ids j < n_row_group with row_group[j] == query_group[i].
+    int exact_knn_query_grouped(const float *queries, int count, int dim, int k, const int *row_group, long long n_row_group, const int *query_group,
+                                int n_groups, int *out_ids, float *out_dists, std::string &err);
+    void exact_grouped_info(uint64_t out[4]) const { if (dev_) dev_->exact_grouped_info(out); else out[0] = out[1] = out[2] = out[3] = 0; }
     void exact_range_info(uint64_t out[4]) const { if (dev_) dev_->exact_range_info(out); else out[0] = out[1] = out[2] = out[3] = 0; }
     // hnsw_mi355x_get_info / hnsw_mi355x_connected_component_counts: HNSWIndex.GetInfo() / GetConnectedComponentCounts() for the
     // layers 0 .. top, computed by the primary context from the graph mirror (Device::graph_info / graph_components)

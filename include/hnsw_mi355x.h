@@ -267,6 +267,27 @@ int hnsw_mi355x_exact_range_query(void *handle, const float *vectors, int count,
  * (Its launches and measured pairs count in hnswdev_stats.exact_*: both calls are the flat scan.)  0, or -1 for a NULL argument. */
 int hnsw_mi355x_exact_range_info(void *handle, uint64_t out[4]);
 
+/* hnsw_mi355x_exact_knn_query with a candidate group per query (no reference counterpart): rows partitioned by
+ * tenant, category or language, every query answered from its own part, all parts in one scan.  row_group is int32[n_row_group],
+ * indexed by id; query_group is int32[count].  The candidates of query i are the live ids j < n_row_group with
+ * row_group[j] == query_group[i].  A row_group value outside [0, n_groups) puts the id in no group, and so do ids >= n_row_group;
+ * n_row_group beyond the index's length is clamped (a row that does not exist is never dereferenced).  1 <= n_groups <= 65 536.
+ * Everything else is hnsw_mi355x_exact_knn_query's contract: distances, -0 / NaN representation, order by (distance, id), padding
+ * with -1 / NaN (a query whose group has no live member gets a row of padding; when that holds for every query nothing is
+ * scanned), 1 <= k <= 1024, no graph read, always on the device and on the primary context alone, the handle taken exclusively,
+ * the resident query set untouched.  For every group g the rows of the result at query_group == g are byte for byte what
+ * hnsw_mi355x_exact_knn_query returns for those queries with the allow-set {j : row_group[j] == g}.
+ * -1 with a message, nothing written: row_group NULL or n_row_group < 0; n_groups outside 1 .. 65 536; a query_group value outside
+ * [0, n_groups) (the message names the first such index); k > 1024.  NULL handle, count <= 0 and k < 1 behave as in
+ * hnsw_mi355x_exact_knn_query. */
+int hnsw_mi355x_exact_knn_query_grouped(void *handle, const float *vectors, int count, int dim, int k, const int *row_group,
+                                        long long n_row_group, const int *query_group, int n_groups, int *out_ids, float *out_dists);
+/* Counters of hnsw_mi355x_exact_knn_query_grouped on the primary context since hnsw_mi355x_reset_stats: out[0] grouped calls that
+ * launched a scan, out[1] groups scanned (groups with a query and a candidate, summed over those calls), out[2] scan blocks
+ * launched, out[3] ids placed in group lists -- all four of the calls that launched a scan only.  (Launches -- one per round -- and measured pairs count in hnswdev_stats.exact_*.)
+ * 0, or -1 for a NULL argument. */
+int hnsw_mi355x_exact_grouped_info(void *handle, uint64_t out[4]);
+
 /* Measurement aid: hnsw_mi355x_set_queries uploads a query set (count x dim) once; every later
  * hnsw_mi355x_knn_query_resident(k) is hnsw_knn_query on that set with the inputs already in HBM
  * (out arrays: count x k). */
@@ -540,6 +561,20 @@ int hnswdev_exact_range(void *ctx, const float *queries, int nq, long long n_row
 int hnswdev_exact_range_results(void *ctx, int *out_ids, float *out_dists);
 /* out[0 .. 3] as hnsw_mi355x_exact_range_info, of this context; zeroed by hnswdev_reset_stats. */
 int hnswdev_exact_range_info(void *ctx, uint64_t out[4]);
+/* The flat scan behind hnsw_mi355x_exact_knn_query_grouped: hnswdev_exact_knn with a candidate set per query.  The candidates of
+ * query i are the uploaded rows j < min(n_rows, n_row_group) with row_group[j] == query_group[i] (n_rows and n_row_group beyond
+ * what was uploaded are clamped); no active set is involved.  row_group values outside [0, n_groups) are in no group; a
+ * query_group value outside it, row_group == NULL, n_row_group < 0 and n_groups outside 1 .. 65 536 are -1 with a message and
+ * nothing written.  queries == NULL: the resident set, as in hnswdev_exact_knn.  The groups' id lists are built on the device from
+ * row_group and are unordered; the result does not depend on their order. */
+int hnswdev_exact_knn_grouped(void *ctx, const float *queries, int nq, long long n_rows, int k, const int *row_group, long long n_row_group,
+                              const int *query_group, int n_groups, int *out_ids, float *out_dists);
+/* out[0 .. 3] as hnsw_mi355x_exact_grouped_info, of this context; zeroed by hnswdev_reset_stats. */
+int hnswdev_exact_grouped_info(void *ctx, uint64_t out[4]);
+/* Measurement aid: *out_ms = the HIP-event time, in milliseconds, of the list-building kernels (count, offsets, place) of the
+ * hnswdev_exact_knn_grouped calls made while profiling was on (hnswdev_set_profiling) since hnswdev_reset_stats.  The scan and the
+ * merge of those calls are in hnswdev_stats.exact_kernel_ms.  0, or -1 for a NULL argument. */
+int hnswdev_exact_grouped_list_ms(void *ctx, double *out_ms);
 /* hnsw_mi355x_get_info / hnsw_mi355x_connected_component_counts for ONE layer of the committed graph mirror of a context.
  * live_bits == NULL: every node of the mirror is live; otherwise a bitset of nbits bits in the allow-sets' format, ids >= nbits not
  * live.  A layer's members are the live nodes with level >= layer; an entry that points at no member counts in its owner's out-degree
