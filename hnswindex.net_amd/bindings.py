@@ -154,6 +154,32 @@ lib.hnswdev_graph_components.restype = ct.c_int
 lib.hnswdev_graph_components.argtypes = [ct.c_void_p, ct.c_int, _U32, ct.c_longlong, _I]
 lib.hnswdev_graph_info_counters.restype = ct.c_int
 lib.hnswdev_graph_info_counters.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
+
+
+class LayerReach(ct.Structure):
+    """hnsw_mi355x_layer_reach: one layer of the reachability chain from the entry point."""
+    _fields_ = [(n, ct.c_int32) for n in ("layer_id", "nodes_count", "seeds", "reached", "max_hops")]
+
+    def as_dict(self) -> dict:
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+_GRAPH_REACH_COUNTERS = ("layers", "rounds", "entries", "launches")   # hnswdev_graph_reach_counters' out[0 .. 3]
+_GRAPH_REACH_SUMMARY = ("nodes_count", "seeds", "reached", "max_hops")   # hnswdev_graph_reach_layer's out_summary[0 .. 3]
+lib.hnsw_mi355x_reachability.restype = ct.c_int
+lib.hnsw_mi355x_reachability.argtypes = [ct.c_void_p, ct.POINTER(LayerReach), ct.c_int]
+lib.hnsw_mi355x_unreachable_ids.restype = ct.c_int
+lib.hnsw_mi355x_unreachable_ids.argtypes = [ct.c_void_p, ct.c_int, _I, ct.c_int]
+lib.hnsw_mi355x_hop_counts.restype = ct.c_int
+lib.hnsw_mi355x_hop_counts.argtypes = [ct.c_void_p, ct.c_int, _I, ct.c_int]
+lib.hnsw_mi355x_graph_reach_counters.restype = ct.c_int
+lib.hnsw_mi355x_graph_reach_counters.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
+lib.hnswdev_graph_reach_layer.restype = ct.c_int
+lib.hnswdev_graph_reach_layer.argtypes = [ct.c_void_p, ct.c_int, _U32, ct.c_longlong, _U32, ct.c_longlong, _U32, _I, ct.POINTER(ct.c_uint64)]
+lib.hnswdev_graph_reach.restype = ct.c_int
+lib.hnswdev_graph_reach.argtypes = [ct.c_void_p, ct.c_int, _U32, ct.c_longlong, ct.c_int, ct.POINTER(LayerReach), ct.c_int, _U32, _I]
+lib.hnswdev_graph_reach_counters.restype = ct.c_int
+lib.hnswdev_graph_reach_counters.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
 lib.hnsw_mi355x_range_query_filtered.restype = ct.c_int
 lib.hnsw_mi355x_range_query_filtered.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_int, ct.c_float, _U32, ct.c_longlong, ct.POINTER(ct.c_void_p),
                                                  ct.POINTER(ct.c_void_p), ct.POINTER(ct.c_int)]
@@ -765,6 +791,52 @@ class Index:
             lib.hnsw_mi355x_graph_info_counters(self._h, out)
         return dict(zip(_GRAPH_INFO_COUNTERS, (int(v) for v in out)))
 
+    # ---- reachability from the entry point over out-edges ----
+    def reachability(self) -> List[dict]:
+        """One dict per layer 0 .. top with the fields of hnsw_mi355x_layer_reach: the layer's members, the seeds that arrive from the
+        layer above (the entry point on the top layer), how many members a traversal from them can reach over out-edges, and the
+        largest hop count.  Computed on the device from the graph mirror; an empty list for an empty index."""
+        if not self._initialized:
+            self._initialize()
+        cap = 16
+        while True:
+            out = (LayerReach * cap)()
+            n = lib.hnsw_mi355x_reachability(self._h, out, cap)
+            if n < 0:
+                raise RuntimeError(last_error())
+            if n <= cap:
+                return [out[i].as_dict() for i in range(n)]
+            cap = n
+
+    def unreachable_ids(self, layer: int = 0) -> npt.NDArray[np.int32]:
+        """The live members of `layer` that no query on that layer can return, ascending: they are outside everything the entry
+        point reaches over out-edges (a necessary condition for being found, not a sufficient one).  exact_knn_query returns them."""
+        if not self._initialized:
+            self._initialize()
+        out = np.zeros(max(1, self.count), dtype=np.int32)   # room for every live id: one call, one walk of the chain
+        n = lib.hnsw_mi355x_unreachable_ids(self._h, int(layer), out.ctypes.data_as(_I), out.size)
+        if n < 0:
+            raise RuntimeError(last_error())
+        return out[:n].copy()
+
+    def hop_counts(self, layer: int = 0) -> npt.NDArray[np.int32]:
+        """Per id < length: the hop count at which the chain from the entry point first reaches it on `layer` (>= 0), -1 for a member
+        of the layer that is not reached, -2 for an id that is no member (removed, or below the layer)."""
+        if not self._initialized:
+            self._initialize()
+        out = np.zeros(max(1, self.length), dtype=np.int32)
+        n = lib.hnsw_mi355x_hop_counts(self._h, int(layer), out.ctypes.data_as(_I), out.size)
+        if n < 0:
+            raise RuntimeError(last_error())
+        return out[:n].copy()
+
+    def graph_reach_counters(self) -> dict:
+        """Counters of reachability / unreachable_ids / hop_counts since reset_stats (hnsw_mi355x_graph_reach_counters)."""
+        out = (ct.c_uint64 * 4)()
+        if self._h:
+            lib.hnsw_mi355x_graph_reach_counters(self._h, out)
+        return dict(zip(_GRAPH_REACH_COUNTERS, (int(v) for v in out)))
+
     # ---- HNSWIndex.Serialize / Deserialize (src/HNSWIndex/HNSWIndex.cs:210-229) ----
     def serialize(self, path) -> None:
         """Write the reference's protobuf-net snapshot of this index to `path`."""
@@ -827,6 +899,7 @@ class DeviceBackend:
         if lib.hnswdev_create(device, dim, METRICS[metric], capacity, ct.byref(ctx)) != 0:
             raise RuntimeError("hnswdev_create failed: " + _dev_error())
         self._ctx = ctx
+        self._graph_n = 0   # nodes of the committed graph (set_graph)
 
     def __del__(self):
         if getattr(self, "_ctx", None):
@@ -902,12 +975,14 @@ class DeviceBackend:
     def set_graph(self, levels, layers, max_edges: int):
         """layers: per layer a (counts[n], edges[n, stride]) pair, EdgeList order (as Index.export_edges)."""
         lv = np.ascontiguousarray(levels, dtype=np.int32)
+        self._graph_n = 0
         self._check(lib.hnswdev_graph_begin(self._ctx, lv.size, int(max_edges), lv.ctypes.data_as(_I)))
         for layer, (counts, edges) in enumerate(layers):
             c = np.ascontiguousarray(counts, dtype=np.int32)
             e = np.ascontiguousarray(edges, dtype=np.int32)
             self._check(lib.hnswdev_graph_set_layer(self._ctx, layer, c.ctypes.data_as(_I), e.ctypes.data_as(_I), e.shape[1]))
         self._check(lib.hnswdev_graph_commit(self._ctx))
+        self._graph_n = int(lv.size)
 
     @staticmethod
     def _live_arg(live):
@@ -937,6 +1012,47 @@ class DeviceBackend:
         out = (ct.c_uint64 * 4)()
         self._check(lib.hnswdev_graph_info_counters(self._ctx, out))
         return dict(zip(_GRAPH_INFO_COUNTERS, (int(v) for v in out)))
+
+    def _reach_out(self):
+        """(n, reached words, hops) for a reachability call on the committed graph."""
+        n = int(self._graph_n)
+        return n, np.zeros((n + 31) // 32, dtype=np.uint32), np.zeros(n, dtype=np.int32)
+
+    @staticmethod
+    def _reached_mask(words, n):
+        return np.unpackbits(words.view(np.uint8), bitorder="little")[:n].astype(np.bool_)
+
+    def graph_reach_layer(self, layer: int, seeds, live=None):
+        """hnswdev_graph_reach_layer: what the members of one layer of the committed graph that are in `seeds` (a bool mask or an id
+        list, as `live`) reach over out-edges.  (reached mask[n], hops[n], summary dict)."""
+        _, wp, nbits = self._live_arg(live)
+        swords, snbits = allow_bits(seeds)
+        swords, sp = _words_arg(swords)
+        n, words, hops = self._reach_out()
+        summary = (ct.c_uint64 * 4)()
+        self._check(lib.hnswdev_graph_reach_layer(self._ctx, int(layer), wp, nbits, sp, snbits, words.ctypes.data_as(_U32), hops.ctypes.data_as(_I), summary))
+        return self._reached_mask(words, n), hops, dict(zip(_GRAPH_REACH_SUMMARY, (int(v) for v in summary)))
+
+    def graph_reach(self, entry_point: int, live=None, min_layer: int = 0):
+        """hnswdev_graph_reach: the chain from the entry point's level down to min_layer.  (per-layer dicts for min_layer .. top,
+        reached mask[n] and hops[n] of min_layer)."""
+        _, wp, nbits = self._live_arg(live)
+        n, words, hops = self._reach_out()
+        cap = 16
+        while True:
+            out = (LayerReach * cap)()
+            got = lib.hnswdev_graph_reach(self._ctx, int(entry_point), wp, nbits, int(min_layer), out, cap, words.ctypes.data_as(_U32), hops.ctypes.data_as(_I))
+            if got < 0:
+                raise RuntimeError(self.last_error())
+            if got <= cap:
+                return [out[i].as_dict() for i in range(int(min_layer), got)], self._reached_mask(words, n), hops
+            cap = got
+
+    def graph_reach_counters(self) -> dict:
+        """Counters of graph_reach_layer / graph_reach since reset_stats (hnswdev_graph_reach_counters)."""
+        out = (ct.c_uint64 * 4)()
+        self._check(lib.hnswdev_graph_reach_counters(self._ctx, out))
+        return dict(zip(_GRAPH_REACH_COUNTERS, (int(v) for v in out)))
 
     def knn_search(self, queries, entry_point: int, k_beam: int, k_out: int, allowed=None, layer: int = 0):
         """allowed: as for Index.knn_query (hnswdev_knn_search_filtered); None runs hnswdev_knn_search.  layer != 0:

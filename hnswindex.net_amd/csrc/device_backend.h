@@ -76,6 +76,7 @@ class Device;
 struct VisitedScratch;   // device_backend.hip: the visited-set memory of a traversal launch
 struct TraversalLaunch;  // ... which traversal kernel form a launch runs, on how many waves, with which flags
 struct LaunchFamily;     // ... the hnswdev_stats counters of one kernel family
+struct ReachSeeds;       // dk_graph_reach.h: the seed set of one layer's reachability pass
 struct LayerView;        // dk_graph_info.h: the mirror as the graph-info kernels see one layer of it
 struct GraphAcc;         // ... what those kernels add up
 struct ErrorScope { // RAII: the calling thread is inside a call on `d`
@@ -364,6 +365,23 @@ public:
     bool graph_info_layer(const char *who, int layer);
     // layers summarised, layers whose components were counted, list entries read (counted by the kernels), kernel launches
     void graph_info_counters(uint64_t out[4]) const { for (int i = 0; i < 4; ++i) out[i] = gi_info_[i]; }
+    // hnswdev_graph_reach_layer / hnswdev_graph_reach (dk_graph_reach.h): what can be reached over OUT-edges.  Members
+    // and the live set are graph_info's; an entry u -> v counts only between two members.  graph_reach_layer: one layer, the seeds a
+    // bitset (seed_nbits bits, ids beyond it and ids that are no members are no seeds; an empty set reaches nothing and launches no
+    // expansion).  out_reached_bits: ceil(graph_nodes() / 32) words or nullptr; out_hops: graph_nodes() ints or nullptr (>= 0: the BFS
+    // distance from the seeds, -1: a member not reached, -2: no member); out_summary: members, member seeds, reached, largest hop.
+    // graph_reach: the chain F_top = reach_top({entry_point}), F_L = reach_L(F_{L + 1}) down to min_layer, `top` the level the caller
+    // knows the entry point to have (graph_reach_top is the C ABI's); the seeds of a layer are the hop array of the layer above,
+    // on the device.  out_layers[L] is filled for min_layer <= L < min(cap, top + 1), the two arrays describe min_layer.  An entry
+    // point that is out of range or no member of layer `top` reaches nothing.  top + 1, or -1.  Synchronous; the rounds of a layer
+    // are bounded by its member count (every round reaches a new node), beyond that the call fails.
+    bool graph_reach_layer(int layer, const uint32_t *live_bits, long long nbits, const uint32_t *seed_bits, long long seed_nbits,
+                           uint32_t *out_reached_bits, int *out_hops, uint64_t out_summary[4]);
+    int graph_reach(int entry_point, int top, const uint32_t *live_bits, long long nbits, int min_layer, hnsw_mi355x_layer_reach *out_layers, int cap,
+                    uint32_t *out_reached_bits, int *out_hops);
+    bool graph_reach_top(const char *who, int entry_point, int *top);
+    // layers walked, rounds (expansion launches), list entries the expansions read (counted by the kernel), kernel launches
+    void graph_reach_counters(uint64_t out[4]) const { for (int i = 0; i < 4; ++i) out[i] = gr_info_[i]; }
 
     void set_profiling(bool on) { profiling_ = on; }
 
@@ -485,6 +503,13 @@ private:
     DevBuf<int> gi_indeg_, gi_parent_;  // ... per node: in-degree on the layer; parent in the union-find's forest
     DevBuf<int> gi_inhist_;             // ... nodes per in-degree, max in-degree + 1 bins
     uint64_t gi_info_[4] = {0, 0, 0, 0};
+    bool graph_reach_room();
+    bool graph_reach_run(const LayerView &g, const ReachSeeds &seeds, int which, bool want_bits, uint64_t summary[4]);
+    bool graph_reach_copy_out(int which, uint32_t *out_reached_bits, int *out_hops);
+    DevBuf<int> gr_hop_[2], gr_q_[2];   // graph_reach: per node the hop (two arrays: a layer's is the seed set of the layer below); the two frontier queues
+    DevBuf<unsigned> gr_bits_, gr_seed_; // ... the reached set as a bitset; graph_reach_layer's seed set
+    DevBuf<unsigned long long> gr_acc_; // ... the layer's ReachAcc
+    uint64_t gr_info_[4] = {0, 0, 0, 0};
     DevBuf<SearchHit> s_arena_; // range search: the launch's results, packed
     DevBuf<unsigned long long> s_roff_, s_arena_used_; // s_roff_ stands for the capacity of range_batch's per-job arrays
     DevBuf<int> s_rentry_;

@@ -51,6 +51,7 @@
 #include "device_kernels.h"
 #include "dk_exact.h"
 #include "dk_graph_info.h"
+#include "dk_graph_reach.h"
 #include "range_replay.h"
 
 namespace hnsw {
@@ -916,6 +917,7 @@ void Device::reset_stats()
     for (uint64_t &v : xg_info_) v = 0;
     xg_list_ms_ = 0.0;
     for (uint64_t &v : gi_info_) v = 0;
+    for (uint64_t &v : gr_info_) v = 0;
 #ifdef EXP_PHASE_CLOCKS
     (void)hipDeviceSynchronize();
     phase_report("reset_stats");
@@ -2380,15 +2382,19 @@ bool Device::graph_set_layer(int layer, const int *counts, const int *edges, int
     HostGraphStage &g = *hg_;
     if (layer < 0 || !counts || !edges || stride < 1) { set_dev_error("graph_set_layer: bad argument"); return false; }
     const int cap = layer == 0 ? 2 * g.M + 1 : g.M + 1;
+    // diag graph_unchecked=1 (tests of the graph-info / graph-reach kernels only: no traversal may run on such a graph): the count
+    // word and the entries are staged as given -- at most the list's capacity of them -- so that a test can hand the kernels lists
+    // that no build writes
+    const bool unchecked = diag("graph_unchecked", 0) != 0;
     for (int i = 0; i < g.n; ++i) {
         if (g.level[(size_t)i] < layer) continue;
         const int c = counts[i];
-        if (c < 0 || c > cap || c > stride) { set_dev_error("graph_set_layer: edge count exceeds MaxEdges(layer) + 1"); return false; }
+        if (!unchecked && (c < 0 || c > cap || c > stride)) { set_dev_error("graph_set_layer: edge count exceeds MaxEdges(layer) + 1"); return false; }
         int *l = layer == 0 ? g.adj0.data() + (size_t)i * g.stride0 : g.pool.data() + g.upper[(size_t)i] + (size_t)(layer - 1) * g.strideU;
         l[0] = c;
-        for (int j = 0; j < c; ++j) {
+        for (int j = 0; j < c && j < cap && j < stride; ++j) {
             const int e = edges[(size_t)i * stride + j];
-            if (e < 0 || e >= g.n || g.level[(size_t)e] < layer) { set_dev_error("graph_set_layer: edge to a node outside the layer"); return false; }
+            if (!unchecked && (e < 0 || e >= g.n || g.level[(size_t)e] < layer)) { set_dev_error("graph_set_layer: edge to a node outside the layer"); return false; }
             l[1 + j] = e;
         }
     }
@@ -3182,6 +3188,116 @@ bool Device::graph_info_layer(const char *who, int layer)
     return true;
 }
 
+// ---- reachability over out-edges on the mirror (device code in dk_graph_reach.h) ---------------------------
+// The call's scratch, sized with the mirror's node capacity as gi_parent_ is: two hop arrays, two queues, the bitset, the ReachAcc.
+bool Device::graph_reach_room()
+{
+    const size_t n = (size_t)g_n_, cap = (size_t)std::max<long long>(g_n_, g_cap_n());
+    for (int i = 0; i < 2; ++i)
+        if (!gr_hop_[i].grow(n, cap) || !gr_q_[i].grow(n, cap)) return false;
+    return gr_bits_.grow((n + 31) / 32, (cap + 31) / 32) && gr_acc_.grow((sizeof(ReachAcc) + 7) / 8);
+}
+
+// One layer (g.layer) from `seeds` into gr_hop_[which]: init, a round per BFS level, pack.  After every round the host reads the two
+// queue lengths (8 bytes) and stops at an empty frontier.  Every round but the first expands nodes that the round before reached for
+// the first time, so there are at most `members` rounds: the loop is bounded by that number and fails beyond it.
+bool Device::graph_reach_run(const LayerView &g, const ReachSeeds &seeds, int which, bool want_bits, uint64_t summary[4])
+{
+    hipStream_t st = S(stream_);
+    ReachAcc *d_acc = reinterpret_cast<ReachAcc *>(gr_acc_.get());
+    int *hop = gr_hop_[which].get();
+    ReachAcc *h = static_cast<ReachAcc *>(pinned_stage(sizeof(ReachAcc)));
+    if (!h) return false;
+    const unsigned node_blocks = graph_info_blocks(g_n_, num_cu_);
+    HIP_OK(hipMemsetAsync(d_acc, 0, sizeof(ReachAcc), st));
+    hipLaunchKernelGGL(graph_reach_init_kernel, dim3(node_blocks), dim3(kGraphInfoBlock), 0, st, g, seeds, hop, gr_q_[0].get(), d_acc);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipMemcpyAsync(h, d_acc, sizeof(ReachAcc), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    const unsigned long long members = h->members, n_seeds = h->seeds;
+    long long q_n = h->qn[0];
+    if (members > (unsigned long long)g_n_ || n_seeds > members || q_n != (long long)n_seeds) { set_dev_error("graph_reach: the seed queue does not add up"); return false; }
+    const int per = (g.layer == 0 ? g_stride0_ : g_strideU_) - 1;
+    unsigned long long rounds = 0, queued = n_seeds;
+    for (int src = 0; q_n > 0; src ^= 1) {
+        if (rounds >= members) { set_dev_error("graph_reach: more rounds than the layer has members"); return false; }
+        hipLaunchKernelGGL(graph_reach_expand_kernel, dim3(graph_info_blocks(q_n * per, num_cu_)), dim3(kGraphInfoBlock), 0, st, g, gr_q_[src].get(), (int)q_n,
+                           gr_q_[src ^ 1].get(), hop, (int)rounds, src, d_acc);
+        HIP_OK(hipGetLastError());
+        ++rounds;
+        HIP_OK(hipMemcpyAsync(h->qn, d_acc->qn, sizeof(h->qn), hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+        q_n = h->qn[src ^ 1];
+        if (q_n < 0 || queued + (unsigned long long)q_n > members) { set_dev_error("graph_reach: a frontier larger than the members left"); return false; }
+        queued += (unsigned long long)q_n;
+    }
+    hipLaunchKernelGGL(graph_reach_pack_kernel, dim3(node_blocks), dim3(kGraphInfoBlock), 0, st, (long long)g_n_, hop, want_bits ? gr_bits_.get() : nullptr, d_acc);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipMemcpyAsync(h, d_acc, sizeof(ReachAcc), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    if (h->reached != queued) { set_dev_error("graph_reach: the reached set is not what the rounds queued"); return false; }
+    summary[0] = members; summary[1] = n_seeds; summary[2] = h->reached; summary[3] = (uint64_t)h->max_hop;
+    gr_info_[0] += 1; gr_info_[1] += rounds; gr_info_[2] += h->entries; gr_info_[3] += rounds + 2;
+    return true;
+}
+
+bool Device::graph_reach_copy_out(int which, uint32_t *out_reached_bits, int *out_hops)
+{
+    if (out_reached_bits && !exact_copy_out(out_reached_bits, gr_bits_.get(), 4 * (size_t)((g_n_ + 31) / 32))) return false;
+    return !out_hops || exact_copy_out(out_hops, gr_hop_[which].get(), sizeof(int) * (size_t)g_n_);
+}
+
+bool Device::graph_reach_layer(int layer, const uint32_t *live_bits, long long nbits, const uint32_t *seed_bits, long long seed_nbits,
+                               uint32_t *out_reached_bits, int *out_hops, uint64_t out_summary[4])
+{
+    if (!seed_bits || seed_nbits < 0 || !out_summary) { set_dev_error("graph_reach_layer: seed_bits and out_summary must not be NULL and seed_nbits must be >= 0"); return false; }
+    LayerView g;
+    if (!graph_info_begin("graph_reach_layer", layer, live_bits, nbits, &g) || !graph_reach_room()) return false;
+    hipStream_t st = S(stream_);
+    HIP_OK(hipStreamSynchronize(st)); // (the live set has left the pinned stage: the seeds take its place)
+    const long long sb = std::min(seed_nbits, g_n_);
+    const size_t words = (size_t)((sb + 31) / 32);
+    void *hs = pinned_stage(std::max<size_t>(4 * words, sizeof(ReachAcc)));
+    if (!hs || !gr_seed_.grow(std::max<size_t>(words, 1))) return false;
+    memcpy(hs, seed_bits, 4 * words);
+    if (words) HIP_OK(hipMemcpyAsync(gr_seed_, hs, 4 * words, hipMemcpyHostToDevice, st));
+    HIP_OK(hipStreamSynchronize(st)); // (... and graph_reach_run reads its figures through the same stage)
+    const ReachSeeds seeds{kReachSeedBits, -1, gr_seed_.get(), sb, nullptr};
+    return graph_reach_run(g, seeds, 0, out_reached_bits != nullptr, out_summary) && graph_reach_copy_out(0, out_reached_bits, out_hops);
+}
+
+int Device::graph_reach(int entry_point, int top, const uint32_t *live_bits, long long nbits, int min_layer, hnsw_mi355x_layer_reach *out_layers, int cap,
+                        uint32_t *out_reached_bits, int *out_hops)
+{
+    if (top < 0 || min_layer < 0 || min_layer > top || cap < 0 || (cap > 0 && !out_layers)) {
+        set_dev_error("graph_reach: min_layer " + std::to_string(min_layer) + " outside 0 .. " + std::to_string(top) + " (the entry point's top layer), or a bad argument");
+        return -1;
+    }
+    LayerView g;
+    if (!graph_info_begin("graph_reach", top, live_bits, nbits, &g) || !graph_reach_room()) return -1;
+    if (hipStreamSynchronize(S(stream_)) != hipSuccess) { set_dev_error("graph_reach: hipStreamSynchronize failed"); return -1; }
+    int which = 0;
+    for (int layer = top; layer >= min_layer; --layer, which ^= 1) {
+        g.layer = layer;
+        // the top layer starts at the entry point (-1: an id that is nobody's); every other at what the layer above reached
+        const bool in_range = entry_point >= 0 && (long long)entry_point < g_n_;
+        const ReachSeeds seeds = layer == top ? ReachSeeds{kReachSeedId, in_range ? entry_point : -1, nullptr, 0, nullptr}
+                                              : ReachSeeds{kReachSeedHops, -1, nullptr, 0, gr_hop_[which ^ 1].get()};
+        uint64_t sum[4];
+        if (!graph_reach_run(g, seeds, which, layer == min_layer && out_reached_bits, sum)) return -1;
+        if (layer < cap) out_layers[layer] = hnsw_mi355x_layer_reach{layer, (int32_t)sum[0], (int32_t)sum[1], (int32_t)sum[2], (int32_t)sum[3]};
+    }
+    return graph_reach_copy_out(which ^ 1, out_reached_bits, out_hops) ? top + 1 : -1;
+}
+
+// The C ABI's `top`: the staged level of the entry point; of an entry point out of range (it reaches nothing) the graph's top level
+bool Device::graph_reach_top(const char *who, int entry_point, int *top)
+{
+    if (!hg_ || g_n_ <= 0) { set_dev_error(std::string(who) + ": no graph committed"); return false; }
+    *top = entry_point >= 0 && entry_point < hg_->n ? hg_->level[(size_t)entry_point] : hg_->top;
+    return true;
+}
+
 // ---- synchronous conveniences behind the C ABI ---------------------------------------
 // Distance(int, TVector) for nq (query, candidate list) pairs.  Runs on the context's two step-
 // buffer sets, ping-pong: while the GPU measures one set the host packs the next and unpacks the
@@ -3450,6 +3566,28 @@ DEV_API int hnswdev_graph_info_counters(void *ctx, uint64_t out[4])
     CTX_OR_FAIL();
     if (!out) return -1;
     d->graph_info_counters(out);
+    return 0;
+}
+DEV_API int hnswdev_graph_reach_layer(void *ctx, int layer, const uint32_t *live_bits, long long nbits, const uint32_t *seed_bits, long long seed_nbits,
+                                     uint32_t *out_reached_bits, int *out_hops, uint64_t out_summary[4])
+{
+    CTX_OR_FAIL();
+    return d->graph_info_layer("hnswdev_graph_reach_layer", layer) &&
+                   d->graph_reach_layer(layer, live_bits, nbits, seed_bits, seed_nbits, out_reached_bits, out_hops, out_summary) ? 0 : -1;
+}
+DEV_API int hnswdev_graph_reach(void *ctx, int entry_point, const uint32_t *live_bits, long long nbits, int min_layer, hnsw_mi355x_layer_reach *out_layers,
+                               int cap, uint32_t *out_reached_bits, int *out_hops)
+{
+    CTX_OR_FAIL();
+    int top;
+    if (!d->graph_reach_top("hnswdev_graph_reach", entry_point, &top)) return -1;
+    return d->graph_reach(entry_point, top, live_bits, nbits, min_layer, out_layers, cap, out_reached_bits, out_hops);
+}
+DEV_API int hnswdev_graph_reach_counters(void *ctx, uint64_t out[4])
+{
+    CTX_OR_FAIL();
+    if (!out) return -1;
+    d->graph_reach_counters(out);
     return 0;
 }
 DEV_API int hnswdev_range_results(void *ctx, int *out_ids, float *out_dists) { CTX_OR_FAIL(); return d->range_results(out_ids, out_dists) ? 0 : -1; }

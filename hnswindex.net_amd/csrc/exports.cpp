@@ -503,6 +503,45 @@ API int hnsw_mi355x_graph_info_counters(void *h, uint64_t out[4])
     static_cast<HnswIndex *>(h)->graph_info_counters(out);
     return 0;
 }
+// Reachability from the entry point over out-edges on the graph mirror.  Exclusive, as hnsw_mi355x_get_info.
+API int hnsw_mi355x_reachability(void *h, hnsw_mi355x_layer_reach *out, int cap)
+{
+    if (!h) return 0;
+    if (cap < 0 || (cap > 0 && !out)) { set_error("System.ArgumentNullException: hnsw_mi355x_reachability"); return -1; }
+    std::string err;
+    LOCK_INDEX(h);
+    const int n = static_cast<HnswIndex *>(h)->reachability(out, cap, err);
+    if (n < 0) set_error(err);
+    return n;
+}
+API int hnsw_mi355x_unreachable_ids(void *h, int layer, int *out, int cap)
+{
+    if (!h) return 0;
+    if (cap < 0 || (cap > 0 && !out)) { set_error("System.ArgumentNullException: hnsw_mi355x_unreachable_ids"); return -1; }
+    std::string err;
+    std::vector<int> ids;
+    LOCK_INDEX(h);
+    if (static_cast<HnswIndex *>(h)->unreachable_ids(layer, ids, err) < 0) { set_error(err); return -1; }
+    std::copy(ids.begin(), ids.begin() + std::min<size_t>(ids.size(), (size_t)cap), out);
+    return (int)ids.size();
+}
+API int hnsw_mi355x_hop_counts(void *h, int layer, int *out, int cap)
+{
+    if (!h) return 0;
+    if (cap < 0 || (cap > 0 && !out)) { set_error("System.ArgumentNullException: hnsw_mi355x_hop_counts"); return -1; }
+    std::string err;
+    LOCK_INDEX(h);
+    const int n = static_cast<HnswIndex *>(h)->hop_counts(layer, out, cap, err);
+    if (n < 0) set_error(err);
+    return n;
+}
+API int hnsw_mi355x_graph_reach_counters(void *h, uint64_t out[4])
+{
+    if (!h || !out) return -1;
+    LOCK_INDEX(h);
+    static_cast<HnswIndex *>(h)->graph_reach_counters(out);
+    return 0;
+}
 API int hnsw_mi355x_dim(void *h)
 {
     if (!h) return 0;

@@ -1797,6 +1797,58 @@ int HnswIndex::connected_component_counts(int *out, int cap, std::string &err)
     return layers;
 }
 
+// Reachability from the entry point over out-edges: connected_component_counts' preparation, then the chain on the
+// device from the entry point's level down to min_layer.  top + 1, or -1; the caller has dealt with the empty index.
+int HnswIndex::reach_chain(const char *who, int min_layer, hnsw_mi355x_layer_reach *out, int cap, uint32_t *bits, int *hops, std::string &err)
+{
+    const int top = graph_.top_layer();
+    if (min_layer < 0 || min_layer > top) {
+        err = std::string(who) + ": layer " + std::to_string(min_layer) + " outside 0 .. " + std::to_string(top) + " (the entry point's top layer)";
+        return -1;
+    }
+    if (!sync_graph(err)) return -1;
+    const uint32_t *live_bits = nullptr;
+    long long nbits = 0;
+    std::vector<uint32_t> live;
+    (void)exact_candidates(live_bits, nbits, live);
+    if (dev_->graph_nodes() != graph_.length) { err = std::string(who) + ": the graph mirror does not hold the index's nodes"; return -1; }
+    if (dev_->graph_reach(graph_.entry, top, live_bits, nbits, min_layer, out, cap, bits, hops) < 0) { err = get_dev_error(); return -1; }
+    return top + 1;
+}
+
+int HnswIndex::reachability(hnsw_mi355x_layer_reach *out, int cap, std::string &err)
+{
+    if (failed(err)) return -1;
+    if (graph_.count <= 0 || graph_.entry < 0) return 0;
+    return reach_chain("reachability", 0, out, cap, nullptr, nullptr, err);
+}
+
+int HnswIndex::unreachable_ids(int layer, std::vector<int> &ids, std::string &err)
+{
+    ids.clear();
+    if (failed(err)) return -1;
+    if (graph_.count <= 0 || graph_.entry < 0) return 0;
+    const long long n = graph_.length;
+    std::vector<uint32_t> reached((size_t)((n + 31) / 32), 0u);
+    if (reach_chain("unreachable_ids", layer, nullptr, 0, reached.data(), nullptr, err) < 0) return -1;
+    for (long long id = 0; id < n; ++id)
+        if (!graph_.removed[(size_t)id] && graph_.level[(size_t)id] >= layer && !((reached[(size_t)(id >> 5)] >> (id & 31)) & 1u)) ids.push_back((int)id);
+    return 0;
+}
+
+int HnswIndex::hop_counts(int layer, int *out, int cap, std::string &err)
+{
+    if (failed(err)) return -1;
+    if (graph_.count <= 0 || graph_.entry < 0) return 0;
+    const long long n = graph_.length;
+    std::vector<int> tmp;
+    int *hops = out;
+    if ((long long)cap < n) { tmp.resize((size_t)n); hops = tmp.data(); }
+    if (reach_chain("hop_counts", layer, nullptr, 0, nullptr, hops, err) < 0) return -1;
+    if (hops != out) std::copy(tmp.begin(), tmp.begin() + std::max(cap, 0), out);
+    return (int)n;
+}
+
 // Host lock-step chains for the queries listed in `which` (nullptr: all `count`): MultiLayerJob.  out_*: [query][first + 1][k - 1].
 int HnswIndex::multilayer_lockstep(const int *which, int count, int k, int first, int min_layer, int *out_ids, float *out_dists, std::string &err)
 {

@@ -77,6 +77,15 @@ public:
     int get_info(hnsw_mi355x_layer_info *out, int cap, std::string &err);
     int connected_component_counts(int *out, int cap, std::string &err);
     void graph_info_counters(uint64_t out[4]) const { if (dev_) dev_->graph_info_counters(out); else out[0] = out[1] = out[2] = out[3] = 0; }
+    // hnsw_mi355x_reachability / _unreachable_ids / _hop_counts: the chain of out-edge reachability from the entry
+    // point (Device::graph_reach) down to layer 0, or down to `layer`.  Locking, sync_graph, the live set and "always on the device,
+    // on the primary context" are connected_component_counts'.  reachability: top + 1 with min(cap, top + 1) entries written.
+    // unreachable_ids: the live members of `layer` outside F_layer, ascending, in `ids` (only the reached bitset crosses back; the
+    // member test is the host's).  hop_counts: length, with min(cap, length) entries written.  An empty index: 0.  -1 on error.
+    int reachability(hnsw_mi355x_layer_reach *out, int cap, std::string &err);
+    int unreachable_ids(int layer, std::vector<int> &ids, std::string &err);
+    int hop_counts(int layer, int *out, int cap, std::string &err);
+    void graph_reach_counters(uint64_t out[4]) const { if (dev_) dev_->graph_reach_counters(out); else out[0] = out[1] = out[2] = out[3] = 0; }
     int knn_query_general(const float *queries, int count, int dim, int k, int layer, const uint32_t *allow_bits, long long nbits, int *out_ids,
                           float *out_dists, std::string &err);
     // hnsw_mi355x_multilayer_knn_query: the number of layer slots (min(top, max_layer) + 1; 0 for an empty index, k < 1 or
@@ -174,6 +183,7 @@ private:
     bool ensure_capacity(long long need, std::string &err);
     bool insert_batch(const std::vector<int> &bid, std::string &err);
     long long exact_candidates(const uint32_t *&allow_bits, long long &nbits, std::vector<uint32_t> &live) const;
+    int reach_chain(const char *who, int min_layer, hnsw_mi355x_layer_reach *out, int cap, uint32_t *bits, int *hops, std::string &err);
     bool insert_exact_window(const std::vector<int> &fresh, int &p, int W, bool background, std::string &err);
     // Selected neighbour ids per (batch item, layer).  Device results are read in place from the
     // context's pinned buffers (layer 0: slot = item; layer L >= 1: slot upper_base[item] + L - 1);

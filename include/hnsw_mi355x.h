@@ -336,6 +336,33 @@ int hnsw_mi355x_connected_component_counts(void *handle, int *out, int cap);
  * launches.  0, or -1 for a NULL argument. */
 int hnsw_mi355x_graph_info_counters(void *handle, uint64_t out[4]);
 
+/* Reachability from the entry point over OUT-edges, computed on the device from the graph mirror.  Every query --
+ * KnnQuery, RangeQuery, their filtered and `layer` forms, MultiLayerKnnQuery -- starts at the entry point, descends over the out-lists
+ * of the layers above and expands out-lists on its target layer; weak connectivity (the call above) says nothing about that.
+ * An entry u -> v counts only between two members of the layer (live ids with MaxLayer >= layer).  For a seed set S, reach_L(S) is the
+ * set of members reachable from the member seeds over such entries, seeds included, and the hop count of a member is its BFS
+ * distance from them.  The chain, with ep the entry point and top its MaxLayer: F_top = reach_top({ep}), F_L = reach_L(F_{L+1}) for
+ * L = top - 1 .. 0.  F_L contains every node a descent can arrive at on L and every node a search on L can expand, so a member of L
+ * outside F_L is never a result of any query on L -- a NECESSARY condition for being found, not a sufficient one: a member of F_L may
+ * still be missed by a greedy search.  hnsw_mi355x_exact_knn_query returns such items; no traversal does. */
+typedef struct hnsw_mi355x_layer_reach {
+    int32_t layer_id, nodes_count, seeds, reached, max_hops; /* members of the layer; |F_{L+1}| (1 on the top layer); |F_L|; the largest hop count in F_L */
+} hnsw_mi355x_layer_reach; /* 20 bytes */
+/* The chain for the layers 0 .. top: returns top + 1 and writes min(cap, top + 1) entries (the whole chain is computed whatever cap
+ * is).  0 for an empty index and for a NULL handle; -1 with a message on error.  Locking, device and context as hnsw_mi355x_get_info. */
+int hnsw_mi355x_reachability(void *handle, hnsw_mi355x_layer_reach *out, int cap);
+/* The live members of `layer` outside F_layer, ascending: returns their number and writes min(cap, number) ids.  Only the reached set's
+ * bitset (length / 8 bytes) comes back from the device.  layer outside 0 .. top on a non-empty index: -1 with a message.  An empty index
+ * and a NULL handle: 0. */
+int hnsw_mi355x_unreachable_ids(void *handle, int layer, int *out, int cap);
+/* out[id] for ids < hnsw_mi355x_length: >= 0 the hop count of id in F_layer, -1 a member of `layer` outside F_layer, -2 no member of
+ * the layer (removed, or MaxLayer < layer).  Returns length and writes min(cap, length) entries.  Errors as above. */
+int hnsw_mi355x_hop_counts(void *handle, int layer, int *out, int cap);
+/* Counters of the three calls above on the primary context since hnsw_mi355x_reset_stats: out[0] layers walked, out[1] rounds (launches
+ * of the expansion kernel: one per BFS level), out[2] list entries the expansions read (counted by the kernel: the out-degrees of the
+ * reached members, each expanded once), out[3] kernel launches.  0, or -1 for a NULL argument. */
+int hnsw_mi355x_graph_reach_counters(void *handle, uint64_t out[4]);
+
 /* HNSWIndex.Serialize(filePath) / HNSWIndex.Deserialize(distFnc, filePath)
  * (src/HNSWIndex/HNSWIndex.cs:210-229): the reference's protobuf-net snapshot of
  * HNSWIndexSnapshot<float[],float> (HNSWIndexSnapshot.cs:12-16, GraphDataSnapshot.cs:13-35,
@@ -585,6 +612,21 @@ int hnswdev_graph_info(void *ctx, int layer, const uint32_t *live_bits, long lon
 int hnswdev_graph_components(void *ctx, int layer, const uint32_t *live_bits, long long nbits, int *out_count);
 /* out[0 .. 3] as hnsw_mi355x_graph_info_counters, of this context; zeroed by hnswdev_reset_stats. */
 int hnswdev_graph_info_counters(void *ctx, uint64_t out[4]);
+/* Reachability over out-edges (see hnsw_mi355x_layer_reach) on ONE layer of the committed graph mirror of a context, from explicit
+ * seeds.  live_bits / nbits and the layer test as hnswdev_graph_info.  seed_bits: a bitset of seed_nbits bits in the allow-sets'
+ * format (it may be longer than the graph); NULL is -1; seeds that are no members of the layer are ignored; an empty set is legal:
+ * nothing is reached and no expansion is launched.  out_reached_bits: ceil(n / 32) words, n the mirror's nodes, or NULL.  out_hops: n
+ * ints or NULL -- >= 0 the hop count, -1 a member not reached, -2 no member.  out_summary: members, member seeds, reached, largest hop. */
+int hnswdev_graph_reach_layer(void *ctx, int layer, const uint32_t *live_bits, long long nbits, const uint32_t *seed_bits, long long seed_nbits,
+                              uint32_t *out_reached_bits, int *out_hops, uint64_t out_summary[4]);
+/* The chain from entry_point's level (top) down to min_layer: returns top + 1, fills out_layers[L] for min_layer <= L < min(cap, top + 1);
+ * the two arrays (either may be NULL) describe min_layer.  The seeds of a layer are the reached set of the layer above and never leave
+ * the device.  An entry point that is no member of its own level reaches nothing on any layer; so does one out of range, for which
+ * top is the graph's top level.  min_layer outside 0 .. top, no committed graph: -1. */
+int hnswdev_graph_reach(void *ctx, int entry_point, const uint32_t *live_bits, long long nbits, int min_layer, hnsw_mi355x_layer_reach *out_layers,
+                        int cap, uint32_t *out_reached_bits, int *out_hops);
+/* out[0 .. 3] as hnsw_mi355x_graph_reach_counters, of this context; zeroed by hnswdev_reset_stats. */
+int hnswdev_graph_reach_counters(void *ctx, uint64_t out[4]);
 int hnswdev_get_stats(void *ctx, hnswdev_stats *out);
 int hnswdev_reset_stats(void *ctx);
 /* Last error, process-wide (creation failures have no context yet) ... */
