@@ -130,6 +130,11 @@ lib.hnsw_mi355x_exact_knn_query_grouped.restype = ct.c_int
 lib.hnsw_mi355x_exact_knn_query_grouped.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_int, ct.c_int, _I, ct.c_longlong, _I, ct.c_int, _I, _F]
 lib.hnsw_mi355x_exact_grouped_info.restype = ct.c_int
 lib.hnsw_mi355x_exact_grouped_info.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
+_KNN_GROUPED_INFO = ("calls", "launched", "skipped", "handbacks")   # hnswdev_knn_grouped_info's out[0 .. 3]
+lib.hnsw_mi355x_knn_query_grouped.restype = ct.c_int
+lib.hnsw_mi355x_knn_query_grouped.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_int, ct.c_int, ct.c_int, _I, ct.c_longlong, _I, ct.c_int, _I, _F]
+lib.hnsw_mi355x_knn_grouped_info.restype = ct.c_int
+lib.hnsw_mi355x_knn_grouped_info.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
 
 
 class LayerInfo(ct.Structure):
@@ -263,6 +268,10 @@ lib.hnswdev_exact_grouped_info.restype = ct.c_int
 lib.hnswdev_exact_grouped_info.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
 lib.hnswdev_exact_grouped_list_ms.restype = ct.c_int
 lib.hnswdev_exact_grouped_list_ms.argtypes = [ct.c_void_p, ct.POINTER(ct.c_double)]
+lib.hnswdev_knn_search_grouped.restype = ct.c_int
+lib.hnswdev_knn_search_grouped.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int, _I, ct.c_longlong, _I, ct.c_int, _I, _F, _I]
+lib.hnswdev_knn_grouped_info.restype = ct.c_int
+lib.hnswdev_knn_grouped_info.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
 lib.hnswdev_range_results.restype = ct.c_int
 lib.hnswdev_range_results.argtypes = [ct.c_void_p, _I, _F]
 lib.hnswdev_knn_search_at_layer.restype = ct.c_int
@@ -598,6 +607,32 @@ class Index:
         if self._h:
             lib.hnsw_mi355x_exact_grouped_info(self._h, out)
         return dict(zip(_EXACT_GROUPED_INFO, (int(v) for v in out)))
+
+    def knn_query_grouped(self, queries: npt.ArrayLike, k: int, row_group, query_group, n_groups=None,
+                          layer: int = 0) -> Tuple[npt.NDArray[np.int32], npt.NDArray[np.float32]]:
+        """knn_query with a group filter per query, every group in one device traversal (hnsw_mi355x_knn_query_grouped):
+        row_group[id] is the group of an id (a value outside 0 .. n_groups - 1, or an id past the array's end: no group),
+        query_group[i] the group query i is answered from.  n_groups None: the largest value in either array plus one.  Per
+        group the rows equal knn_query(queries[query_group == g], k, allowed=(row_group == g), layer=layer), ids and distance
+        bits; a query whose group holds no id of the graph gets a padded row."""
+        q = _as_2d_f32(queries, self.dim)
+        n = int(q.shape[0])
+        rg, qg, ng = _group_args(row_group, query_group, n_groups, n)
+        ids = np.full((n, max(k, 0)), -1, dtype=np.int32)   # (an index nothing was added to has no native handle yet: padding)
+        dists = np.full((n, max(k, 0)), np.nan, dtype=np.float32)
+        status = lib.hnsw_mi355x_knn_query_grouped(self._h, q.ctypes.data_as(_F), n, self.dim, k, int(layer), rg.ctypes.data_as(_I), rg.shape[0],
+                                                   qg.ctypes.data_as(_I), ng, ids.ctypes.data_as(_I), dists.ctypes.data_as(_F))
+        if status < 0:
+            raise RuntimeError(last_error())
+        return ids, dists
+
+    def knn_grouped_info(self) -> dict:
+        """Counters of knn_query_grouped's device launches since reset_stats (hnsw_mi355x_knn_grouped_info): calls that reached a
+        context, queries launched, queries skipped because their group holds no graph id, queries handed back to the host."""
+        out = (ct.c_uint64 * 4)()
+        if self._h:
+            lib.hnsw_mi355x_knn_grouped_info(self._h, out)
+        return dict(zip(_KNN_GROUPED_INFO, (int(v) for v in out)))
 
     def exact_range_query(self, queries: npt.ArrayLike, radius: float,
                           allowed=None) -> Tuple[List[npt.NDArray[np.int32]], List[npt.NDArray[np.float32]]]:
@@ -1077,6 +1112,26 @@ class DeviceBackend:
         self._check(lib.hnswdev_knn_search(self._ctx, q.ctypes.data_as(_F), n, int(entry_point), int(k_beam), int(k_out),
                                            ids.ctypes.data_as(_I), d.ctypes.data_as(_F), flags.ctypes.data_as(_I)))
         return ids, d, flags
+
+    def knn_search_grouped(self, queries, entry_point: int, k_beam: int, k_out: int, row_group, query_group, n_groups=None, layer: int = 0):
+        """hnswdev_knn_search_grouped: knn_search with a group filter per query -- query i is answered from the graph ids j with
+        row_group[j] == query_group[i].  (ids, dists, flags); n_groups None: the largest value in either array plus one."""
+        q = _as_2d_f32(queries, self.dim)
+        n = q.shape[0]
+        rg, qg, ng = _group_args(row_group, query_group, n_groups, n)
+        ids = np.empty((n, k_out), dtype=np.int32)
+        d = np.empty((n, k_out), dtype=np.float32)
+        flags = np.empty(n, dtype=np.int32)
+        self._check(lib.hnswdev_knn_search_grouped(self._ctx, q.ctypes.data_as(_F), n, int(entry_point), int(k_beam), int(k_out), int(layer),
+                                                   rg.ctypes.data_as(_I), rg.shape[0], qg.ctypes.data_as(_I), ng, ids.ctypes.data_as(_I),
+                                                   d.ctypes.data_as(_F), flags.ctypes.data_as(_I)))
+        return ids, d, flags
+
+    def knn_grouped_info(self) -> dict:
+        """Counters of knn_search_grouped since reset_stats (hnswdev_knn_grouped_info)."""
+        out = (ct.c_uint64 * 4)()
+        self._check(lib.hnswdev_knn_grouped_info(self._ctx, out))
+        return dict(zip(_KNN_GROUPED_INFO, (int(v) for v in out)))
 
     def exact_knn(self, queries, k: int, n_rows=None, allowed=None):
         """hnswdev_exact_knn: (ids, dists) of shape [nq, k], per query the k uploaded rows of smallest (distance, id) among rows

@@ -207,6 +207,16 @@ public:
     // search_layer: KnnQuery's `layer` (the descent stops above it, the search reads that layer's lists).
     bool search_filtered(int nq, int entry, int entry_layer, int k, int k_out, const uint32_t *allow_bits, long long nbits, int *out_ids,
                          float *out_d, int *out_flag, int search_layer = 0);
+    // search_filtered with a group filter per query (graph_search_grouped_kernel): resident query i is answered from
+    // the graph ids j < n_row_group with row_group[j] == query_group[i] -- byte for byte what search_filtered returns for it with
+    // that group's ids as the allow-set.  row_group values outside 0 .. n_groups - 1 are in no group; query_group values must lie
+    // inside (checked, with n_groups in 1 .. 65536, before anything runs).  The labels and the queries' groups are uploaded to this
+    // context for the call, as int32, to a buffer of their own.  A query whose group holds no graph id is padded and never launched
+    // (out_flag 0); the others are launched longest traversal first (ascending by their group's id count).  out_flag as search_filtered.
+    bool search_grouped(int nq, int entry, int entry_layer, int k, int k_out, const int *row_group, long long n_row_group, const int *query_group,
+                        int n_groups, int *out_ids, float *out_d, int *out_flag, int search_layer = 0);
+    // calls, queries launched, queries padded for an empty group, queries handed back -- of search_grouped on this context
+    void knn_grouped_info(uint64_t out[4]) const { for (int i = 0; i < 4; ++i) out[i] = kg_info_[i]; }
     // MultiLayerKnnQuery's chains (graph_multilayer_kernel): resident query i searched with beam k (>= 2) on every layer from
     // first_layer (<= entry_layer) down to min_layer, each step entering at the nearest result of the one before.
     // out_ids / out_d: [nq][first_layer + 1][k - 1], padded; out_flag[i] = 1: handed back whole.
@@ -301,6 +311,8 @@ public:
     bool knn_search(const float *queries, int nq, int entry_point, int k_beam, int k_out, int *out_ids, float *out_d, int *out_flag, int layer = 0);
     bool knn_search_filtered(const float *queries, int nq, int entry_point, int k_beam, int k_out, const uint32_t *allow_bits, long long nbits,
                              int *out_ids, float *out_d, int *out_flag, int layer = 0);
+    bool knn_search_grouped(const float *queries, int nq, int entry_point, int k_beam, int k_out, const int *row_group, long long n_row_group,
+                            const int *query_group, int n_groups, int *out_ids, float *out_d, int *out_flag, int layer = 0);
     // hnswdev_multilayer_search: the slot count, or -1
     int multilayer_search_abi(const float *queries, int nq, int entry_point, int k, int max_layer, int min_layer, int layers_cap, int *out_ids,
                               float *out_d, int *out_flag);
@@ -472,6 +484,9 @@ private:
     DevBuf<SearchHit> s_spill_;
     DevBuf<SearchHit> s_fspill_; // filtered searches: their own, larger spill areas (allocated by the first such call)
     DevBuf<unsigned> s_allow_;   // filtered searches: the call's allow-set
+    DevBuf<int> s_glabel_;       // grouped searches: the call's row_group
+    DevBuf<int> s_gquery_;       // ... [query_group of the call | order tables of its launches]
+    uint64_t kg_info_[4] = {0, 0, 0, 0};
     DevBuf<int> x_ids_;                 // exact_knn: the call's ascending id list (exact_compact_kernel)
     DevBuf<long long> x_boff_;          // ... set bits in front of each block of bitset words
     DevBuf<unsigned long long> x_lists_; // ... the per-(query, chunk) lists of a round: at most 1 GiB, allocated by the first call and kept

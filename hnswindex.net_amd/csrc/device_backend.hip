@@ -915,6 +915,7 @@ void Device::reset_stats()
     stats_.row_bytes = rb;
     for (uint64_t &v : xr_info_) v = 0;
     for (uint64_t &v : xg_info_) v = 0;
+    for (uint64_t &v : kg_info_) v = 0;
     xg_list_ms_ = 0.0;
     for (uint64_t &v : gi_info_) v = 0;
     for (uint64_t &v : gr_info_) v = 0;
@@ -1906,6 +1907,121 @@ bool Device::search_filtered(int nq, int entry, int entry_layer, int k, int k_ou
     return true;
 }
 
+// The argument rules the grouped calls share (exact_knn_grouped words them the same way): n_groups in 1 .. kExactMaxGroups, every
+// query_group value inside 0 .. n_groups - 1.
+static bool group_args_ok(const char *who, const int *query_group, int nq, int n_groups)
+{
+    if (n_groups < 1 || n_groups > kExactMaxGroups) {
+        set_dev_error(std::string(who) + ": n_groups = " + std::to_string(n_groups) + " is outside 1 .. " + std::to_string(kExactMaxGroups));
+        return false;
+    }
+    for (int i = 0; i < nq; ++i) {
+        const int g = query_group[i];
+        if (g < 0 || g >= n_groups) {
+            set_dev_error(std::string(who) + ": query_group[" + std::to_string(i) + "] = " + std::to_string(g) + " is outside 0 .. n_groups - 1 = " + std::to_string(n_groups - 1));
+            return false;
+        }
+    }
+    return true;
+}
+
+// KnnQuery with a group filter per query (graph_search_grouped_kernel): search_filtered's launch with the labels in
+// the allow words' place.  Only the labels of graph ids travel.  The graph ids of every group are counted here, on the host: a query
+// whose group has none is padded without a job, and the others are listed in the launch's order table longest traversal first -- a
+// traversal's length grows with 1 / selectivity and a persistent launch ends with its longest job -- ascending by
+// the group's count, queries of equal counts in query order.
+bool Device::search_grouped(int nq, int entry, int entry_layer, int k, int k_out, const int *row_group, long long n_row_group, const int *query_group,
+                            int n_groups, int *out_ids, float *out_d, int *out_flag, int search_layer)
+{
+    if (nq <= 0) return true;
+    if (!out_ids || !out_d || !out_flag || k < 1 || k_out < 1) { set_dev_error("search_grouped: bad argument"); return false; }
+    if (!row_group || n_row_group < 0) { set_dev_error("search_grouped: row_group must not be NULL and n_row_group must be >= 0"); return false; }
+    if (!query_group) { set_dev_error("search_grouped: query_group must not be NULL"); return false; }
+    if (!group_args_ok("search_grouped", query_group, nq, n_groups)) return false;
+    if (g_n_ <= 0) { set_dev_error("search_grouped: no graph uploaded"); return false; }
+    if (search_layer < 0 || search_layer > entry_layer) { set_dev_error("search_grouped: the search layer must lie between 0 and the entry point's top layer"); return false; }
+    if (!(entry >= 0 && entry < g_n_ && entry_layer >= 0 && nq <= n_queries_) || tail_.n > 0) {
+        set_dev_error("search_grouped: entry point outside the graph, or fewer resident queries than asked for");
+        return false;
+    }
+    const long long n_lab = std::min<long long>(n_row_group, g_n_);
+    std::vector<long long> members((size_t)n_groups, 0);
+    for (long long id = 0; id < n_lab; ++id) {
+        const int g = row_group[id];
+        if (g >= 0 && g < n_groups) members[(size_t)g] += 1;
+    }
+    // per launch (chunk) its order table: the chunk's own query indices with a non-empty group, ascending by the group's members
+    const long long chunk = std::min<long long>(nq, 1 << 20);
+    std::vector<int> order((size_t)nq), jobs_of;
+    long long launched = 0;
+    for (long long off = 0; off < nq; off += chunk) {
+        const int nj = (int)std::min<long long>(chunk, nq - off);
+        int *o = order.data() + off;
+        int n = 0;
+        for (int i = 0; i < nj; ++i)
+            if (members[(size_t)query_group[off + i]] > 0) o[n++] = i;
+        std::stable_sort(o, o + n, [&](int a, int b) { return members[(size_t)query_group[off + a]] < members[(size_t)query_group[off + b]]; });
+        for (int i = n; i < nj; ++i) o[i] = 0; // (never read: the launch has n jobs)
+        jobs_of.push_back(n);
+        launched += n;
+    }
+    // the rows no job writes: padding, flag 0 (after the launches' rows have been copied over the caller's arrays)
+    const auto pad_skipped = [&] {
+        for (int i = 0; i < nq; ++i)
+            if (members[(size_t)query_group[i]] == 0) {
+                pad_results(out_ids + (size_t)i * k_out, out_d + (size_t)i * k_out, (size_t)k_out);
+                out_flag[i] = 0;
+            }
+    };
+    if (launched == 0) { // (nothing to traverse: no launch, as a set that allows nothing)
+        pad_skipped();
+        kg_info_[0] += 1;
+        kg_info_[2] += (uint64_t)nq;
+        return true;
+    }
+    const int cand_cap = cand_lds_cap(k, pitch_, false, nbcap());
+    const size_t lds = search_lds_bytes(k, cand_cap, pitch_, false, nbcap());
+    if (lds > 64 * 1024) { set_dev_error("search_grouped: beam width / dimension exceed the LDS budget"); return false; }
+    if (!bind()) return false;
+    hipStream_t st = S(stream_);
+    TraversalLaunch tl;
+    if (!plan_traversal(false, k, true, lds, &tl, true)) return false;
+    const auto kernel = persistent_kernel(metric_, tl.vis.tab != nullptr, [](auto m, auto h) { return &graph_search_grouped_kernel<m, h>; });
+    place_persistent(kernel, tl, (int)chunk);
+    if (tl.slots < 1) { set_dev_error("search_grouped: the kernel does not fit the device"); return false; }
+    const int fspill = filter_spill_cap();
+    if (!ensure_search_scratch(chunk, max_slots(), k_out, tl.vis.bytes_per_job)) return false;
+    if (!s_fspill_.grow((size_t)tl.slots * (size_t)std::max(fspill, 1) + 8)) return false; // +8: get2 may read one entry past a heap
+    if (!s_glabel_.grow((size_t)n_lab) || !s_gquery_.grow(2 * (size_t)nq)) return false;
+    const size_t b_lab = 4u * (size_t)n_lab, b_q = 4u * (size_t)nq;
+    const auto upload = [&](char *h) { // labels, groups and order tables go up from pinned memory: [row_group | query_group | order]
+        memcpy(h, row_group, b_lab);
+        memcpy(h + b_lab, query_group, b_q);
+        memcpy(h + b_lab + b_q, order.data(), b_q);
+        HIP_OK(hipMemcpyAsync(s_glabel_, h, b_lab, hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemcpyAsync(s_gquery_, h + b_lab, 2 * b_q, hipMemcpyHostToDevice, st));
+        return true;
+    };
+    const auto launch = [&](long long off, int, int *d_ids, float *d_d) {
+        const int n = jobs_of[(size_t)(off / chunk)]; // (0: one wave finds the counter past the jobs and leaves)
+        hipLaunchKernelGGL(kernel, dim3(std::max(1, std::min(n, tl.slots))), dim3(tl.block), tl.lds_total, st, d_rows_, d_row_sn_, d_queries_ + (size_t)off * pitch_,
+                           d_q_sn_ ? d_q_sn_ + off : nullptr, pitch_, g_adj0_, g_stride0_, g_upper_, g_pool_, g_strideU_, entry, entry_layer, search_layer, k,
+                           cand_cap, reinterpret_cast<ND *>(s_fspill_.get()), fspill, s_visited_, tl.vis.words, tl.vis.tab, tl.vis.tab_cap,
+                           s_glabel_.get(), n_lab, s_gquery_.get() + off, s_gquery_.get() + (size_t)nq + off, k_out, d_ids, d_d, s_flag_, s_evals_, nbcap(), n,
+                           s_jobctr_);
+    };
+    if (!run_resident((size_t)k_out, chunk, b_lab + 2 * b_q, tl.vis.tab != nullptr, nq, out_ids, out_d, out_flag, upload, launch)) return false;
+    pad_skipped();
+    kg_info_[0] += 1;
+    kg_info_[1] += (uint64_t)launched;
+    kg_info_[2] += (uint64_t)(nq - launched);
+    for (int i = 0; i < nq; ++i) {
+        stats_.search_overflows += (uint64_t)(out_flag[i] == 1);
+        kg_info_[3] += (uint64_t)(out_flag[i] == 1);
+    }
+    return true;
+}
+
 // MultiLayerKnnQuery's chains (graph_multilayer_kernel): resident query i from (entry, entry_layer), searched on every layer from
 // first_layer down to min_layer with beam k, each step entering at the one before's nearest result.  out_ids / out_d:
 // [nq][first_layer + 1][k - 1], slots below min_layer padded; out_flag[i] = 1: the job is handed back (the caller redoes it).
@@ -2455,6 +2571,20 @@ bool Device::knn_search_filtered(const float *queries, int nq, int entry_point, 
     const bool args_ok = k_out >= 1 && k_beam >= k_out; // (false: "knn_search_filtered: bad argument", in abi_entry's place for it)
     if (!abi_begin("knn_search_filtered", queries, nq, entry_point, layer, &top, args_ok)) return false;
     return search_filtered(nq, entry_point, top, k_beam, k_out, allow_bits, nbits, out_ids, out_d, out_flag, layer);
+}
+
+bool Device::knn_search_grouped(const float *queries, int nq, int entry_point, int k_beam, int k_out, const int *row_group, long long n_row_group,
+                                const int *query_group, int n_groups, int *out_ids, float *out_d, int *out_flag, int layer)
+{
+    if (!row_group || n_row_group < 0) { set_dev_error("knn_search_grouped: row_group must not be NULL and n_row_group must be >= 0"); return false; }
+    if (nq <= 0) return true;
+    if (!query_group) { set_dev_error("knn_search_grouped: query_group must not be NULL"); return false; }
+    if (!queries || !out_ids || !out_d || !out_flag) { set_dev_error("knn_search_grouped: null argument"); return false; }
+    if (!group_args_ok("knn_search_grouped", query_group, nq, n_groups)) return false;
+    int top;
+    const bool args_ok = k_out >= 1 && k_beam >= k_out; // (false: "knn_search_grouped: bad argument", in abi_entry's place for it)
+    if (!abi_begin("knn_search_grouped", queries, nq, entry_point, layer, &top, args_ok)) return false;
+    return search_grouped(nq, entry_point, top, k_beam, k_out, row_group, n_row_group, query_group, n_groups, out_ids, out_d, out_flag, layer);
 }
 
 // ---- the flat scan (hnswdev_exact_knn; device code in dk_exact.h) --------------------------------------
@@ -3478,6 +3608,19 @@ DEV_API int hnswdev_knn_search_filtered(void *ctx, const float *queries, int nq,
 {
     CTX_OR_FAIL();
     return d->knn_search_filtered(queries, nq, entry_point, k_beam, k_out, allow_bits, nbits, out_ids, out_dists, out_flags) ? 0 : -1;
+}
+DEV_API int hnswdev_knn_search_grouped(void *ctx, const float *queries, int nq, int entry_point, int k_beam, int k_out, int layer, const int *row_group,
+                                       long long n_row_group, const int *query_group, int n_groups, int *out_ids, float *out_dists, int *out_flags)
+{
+    CTX_OR_FAIL();
+    return d->knn_search_grouped(queries, nq, entry_point, k_beam, k_out, row_group, n_row_group, query_group, n_groups, out_ids, out_dists, out_flags, layer) ? 0 : -1;
+}
+DEV_API int hnswdev_knn_grouped_info(void *ctx, uint64_t out[4])
+{
+    CTX_OR_FAIL();
+    if (!out) return -1;
+    d->knn_grouped_info(out);
+    return 0;
 }
 DEV_API int hnswdev_range_search(void *ctx, const float *queries, int nq, int entry_point, float range, int *out_counts, int *out_flags)
 {

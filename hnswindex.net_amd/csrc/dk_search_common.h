@@ -50,6 +50,21 @@ struct AllowSet {
     long long n;
     __device__ __forceinline__ unsigned word(int id) const { return (long long)id < n ? bits[id >> 5] : 0u; }
     __device__ __forceinline__ bool has(int id) const { return ((word(id) >> (id & 31)) & 1u) != 0u; }
+    static constexpr bool kBitset = true; // word(id) is a word of bits: traverse tests bit id & 31 of it itself
+};
+// A group filter over ids (knn_query_grouped, graph_search_grouped_kernel): label[id] is an id's group, and an id passes when its
+// label is this job's group `g` (0 .. n_groups - 1, wave-uniform).  Ids >= n have no label; a label outside 0 .. n_groups - 1 equals
+// no job's group.  What traverse<..., FILTERED, FILTER> asks of a filter: word(id), the one 4-byte gather per id (here the
+// label itself), has(id), and -- kBitset false -- test(word(id)), the decision on a word fetched earlier.  No label past the array
+// is ever read.
+struct GroupSet {
+    const int *label;
+    long long n;
+    int g;
+    __device__ __forceinline__ unsigned word(int id) const { return (long long)id < n ? (unsigned)label[id] : 0xffffffffu; }
+    __device__ __forceinline__ bool test(unsigned w) const { return (int)w == g; }
+    __device__ __forceinline__ bool has(int id) const { return test(word(id)); }
+    static constexpr bool kBitset = false;
 };
 
 struct GraphView {

@@ -1,4 +1,4 @@
-// dk_search_kernels.h -- device code, part of device_kernels.h: KnnQuery / MultiLayerKnnQuery / RangeQuery: search_job, graph_search_kernel (persistent, shadows, gated upload), graph_search_filtered_kernel (allow-sets), graph_multilayer_kernel (layer chains), graph_range_kernel.
+// dk_search_kernels.h -- device code, part of device_kernels.h: KnnQuery / MultiLayerKnnQuery / RangeQuery: search_job, graph_search_kernel (persistent, shadows, gated upload), graph_search_filtered_kernel (allow-sets), graph_search_grouped_kernel (a group per query), graph_multilayer_kernel (layer chains), graph_range_kernel.
 #pragma once
 #include "dk_sorted_top.h"
 #include "dk_pool_top.h"
@@ -414,6 +414,61 @@ graph_search_filtered_kernel(const float *__restrict__ rows, const double *__res
 #define HNSW_FOR_EACH_FILTERED(X, M) X(M, false) X(M, true)
 #define HNSW_DECLARE_FILTERED(M, H) HNSW_FILTERED_SIGNATURE(extern, M, H)
 #define HNSW_DEFINE_FILTERED(M, H) HNSW_FILTERED_SIGNATURE(, M, H)
+
+// KnnQuery with a group filter per query (knn_query_grouped): graph_search_filtered_kernel with the predicate
+// "row_group[id] == this query's group" (GroupSet) in the allow-set's place -- the same descent, traversal, stable Take(k_out), LDS
+// carve, spill areas, visited sets (cleared after every job) and out_flag values.  Job j of the launch is resident query
+// qi = order[j] (the host lists only the queries whose group holds a graph id, longest traversal first); its group is
+// query_group[qi], wave-uniform and so kept in a scalar register; its results and its flag go to row qi.  row_group has n_labels
+// entries (ids beyond have no group); query_group values lie in 0 .. n_groups - 1 and order entries in 0 .. the launch's queries - 1
+// (the host checks both before the launch).
+template <int METRIC, bool HASHED>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(HNSW_WAVES(3))))
+graph_search_grouped_kernel(const float *__restrict__ rows, const double *__restrict__ row_sn, const float *__restrict__ queries,
+                            const double *__restrict__ q_sn, int dim, const int *__restrict__ adj0, int stride0,
+                            const int64_t *__restrict__ upper, const int *__restrict__ pool, int strideU, int entry, int entry_layer,
+                            int search_layer, int k, int cand_cap, ND *__restrict__ spill, int spill_cap, unsigned *__restrict__ visited,
+                            long long vis_words, int *__restrict__ vis_tab, int vis_tab_cap, const int *__restrict__ row_group, long long n_labels,
+                            const int *__restrict__ query_group, const int *__restrict__ order, int k_out, int *__restrict__ out_ids,
+                            float *__restrict__ out_d, int *__restrict__ out_flag, unsigned long long *__restrict__ eval_counter, int nbcap,
+                            int njobs, int *__restrict__ job_counter)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int lane = threadIdx.x & 63;
+    VisitedSet<HASHED> V = wave_visited<HASHED>(visited, vis_words, vis_tab, vis_tab_cap);
+    ND *my_spill = spill + (size_t)blockIdx.x * (size_t)spill_cap;
+    const SearchLds L = carve_lds(smem, k, cand_cap, dim, nbcap);
+    const GraphView G{adj0, stride0, upper, pool, strideU};
+    for (;;) {
+        int job;
+        if (!claim_job(job_counter, njobs, lane, job)) break;
+        const int qi = __builtin_amdgcn_readfirstlane(order[job]);
+        const GroupSet group{row_group, n_labels, __builtin_amdgcn_readfirstlane(query_group[qi])};
+        const SearchJob jb{qi, entry, entry_layer, search_layer, -1, 0};
+        const double sb = stage_query<METRIC>(queries, q_sn, qi, dim, L, lane);
+        unsigned long long evals = 0;
+        int top_n = 0;
+        ReadLog RL{nullptr, 0, 0};
+        const bool ok = traverse<METRIC, HASHED, true, GroupSet>(rows, row_sn, dim, sb, G, jb, k, cand_cap, my_spill, spill_cap, V, L, lane, top_n, evals, RL,
+                                                                 nullptr, nullptr, true, group);
+        take_stable(L, lane, top_n, k_out, out_ids, out_d, qi);
+        if (lane == 0) {
+            out_flag[qi] = ok ? 0 : 1;
+            atomicAdd(eval_counter, evals);
+        }
+        V.clear(lane);
+    }
+}
+#define HNSW_GROUPED_SIGNATURE(PREFIX, M, H)                                                                                        \
+    PREFIX template __global__ void graph_search_grouped_kernel<M, H>(                                                              \
+        const float *__restrict__, const double *__restrict__, const float *__restrict__, const double *__restrict__, int,      \
+        const int *__restrict__, int, const int64_t *__restrict__, const int *__restrict__, int, int, int, int, int, int, ND *__restrict__, \
+        int, unsigned *__restrict__, long long, int *__restrict__, int, const int *__restrict__, long long, const int *__restrict__, \
+        const int *__restrict__, int, int *__restrict__, float *__restrict__, int *__restrict__, unsigned long long *__restrict__, int, int, \
+        int *__restrict__);
+// (the forms of HNSW_FOR_EACH_FILTERED, built in the units of the `filtered` kind: HNSW_UNIT_filtered, device_kernels.h)
+#define HNSW_DECLARE_GROUPED(M, H) HNSW_GROUPED_SIGNATURE(extern, M, H)
+#define HNSW_DEFINE_GROUPED(M, H) HNSW_GROUPED_SIGNATURE(, M, H)
 
 // MultiLayerKnnQuery (HNSWIndex.cs:173-187), one job = one query's whole chain.  The first step is FindEntryPointQuery from
 // (entry, entry_layer) down to first_layer = min(top, maxLayer) (exclusive) and SearchLayerQuery there; every later step searches

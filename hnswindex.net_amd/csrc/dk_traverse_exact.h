@@ -9,12 +9,14 @@ namespace hnsw {
 // FILTERED (graph_search_filtered_kernel, KnnQuery with an allow-set -- SearchLayerQuery's filterFnc, GraphNavigator.cs:194-256):
 // `allow` is a bitset of `allow_n` bits over ids (AllowSet); a node outside it is a candidate like any other but never enters
 // the result heap.  FILTERED = false (every other caller) compiles to the unfiltered traversal: the allow arguments are unused.
-template <int METRIC, bool HASHED, bool FILTERED = false>
+// FILTER: the predicate's type -- AllowSet, or GroupSet (graph_search_grouped_kernel: the id's group label equals the job's group);
+// either is asked for word(id), one 4-byte gather, where the traversal can overlap it, and for has(id) where it cannot.
+template <int METRIC, bool HASHED, bool FILTERED = false, class FILTER = AllowSet>
 __device__ __forceinline__ bool traverse(const float *__restrict__ rows, const double *__restrict__ row_sn, int dim, double sb,
                                          const GraphView &G, const SearchJob jb, int k, int cand_cap, ND *spill, int spill_cap,
                                          VisitedSet<HASHED> &V, const SearchLds &L, int lane, int &top_n_out, unsigned long long &evals,
                                          ReadLog &RL, const int *abort_word = nullptr, bool *aborted = nullptr, bool overlapped_form = false,
-                                         AllowSet allow = AllowSet{nullptr, 0})
+                                         FILTER allow = FILTER{})
 {
     const LdsHeap top{L.top};
     const SpillHeap cand{L.cand, cand_cap, spill};
@@ -150,7 +152,11 @@ __device__ __forceinline__ bool traverse(const float *__restrict__ rows, const d
             if (V.crowded()) { hash_full = true; break; }
             lane_d = in ? dbuf[lane] : 0.0f;
             lane_id = nb_a;
-            if constexpr (FILTERED) lane_ok = ((aw >> (nb_a & 31)) & 1u) != 0u;
+            if constexpr (FILTERED) {
+                // (the bit test is written out here: routed through a member of AllowSet it changes the bitset kernels' schedule)
+                if constexpr (FILTER::kBitset) lane_ok = ((aw >> (nb_a & 31)) & 1u) != 0u;
+                else lane_ok = allow.test(aw);
+            }
             if (m == 0) continue;
             evals += (unsigned long long)m;
         } else {

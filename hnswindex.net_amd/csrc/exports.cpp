@@ -178,6 +178,26 @@ API int hnsw_mi355x_exact_knn_query_grouped(void *handle, const float *vectors, 
     return 0;
 }
 
+// KnnQuery with a group filter per query: one device traversal for every group.  Exclusive, like the filtered call.
+API int hnsw_mi355x_knn_query_grouped(void *handle, const float *vectors, int count, int dim, int k, int layer, const int *row_group, long long n_row_group,
+                                      const int *query_group, int n_groups, int *out_ids, float *out_dists)
+{
+    if (!handle) return 0;
+    if (count <= 0) return 0;
+    if (!vectors || !out_ids || !out_dists || !query_group || dim <= 0) { set_error("System.ArgumentNullException: hnsw_mi355x_knn_query_grouped"); return -1; }
+    if (!row_group || n_row_group < 0) {
+        set_error("System.ArgumentException: hnsw_mi355x_knn_query_grouped: row_group must not be NULL and n_row_group must be >= 0");
+        return -1;
+    }
+    LOCK_INDEX(handle);
+    std::string err;
+    if (static_cast<HnswIndex *>(handle)->knn_query_grouped(vectors, count, dim, k, layer, row_group, n_row_group, query_group, n_groups, out_ids, out_dists, err) < 0) {
+        set_error(err);
+        return -1;
+    }
+    return 0;
+}
+
 API void hnsw_free_results(void **ids_array, void **dists_array, int count);
 
 // hnsw_range_query and its filtered sibling: `name` for the errors, allow (none: no filter)
@@ -472,6 +492,13 @@ API int hnsw_mi355x_exact_grouped_info(void *h, uint64_t out[4])
     if (!h || !out) return -1;
     LOCK_INDEX(h);
     static_cast<HnswIndex *>(h)->exact_grouped_info(out);
+    return 0;
+}
+API int hnsw_mi355x_knn_grouped_info(void *h, uint64_t out[4])
+{
+    if (!h || !out) return -1;
+    LOCK_INDEX(h);
+    static_cast<HnswIndex *>(h)->knn_grouped_info(out);
     return 0;
 }
 // HNSWIndex.GetInfo() / GetConnectedComponentCounts() (HNSWIndex.cs:192-205) from the graph mirror on the device:

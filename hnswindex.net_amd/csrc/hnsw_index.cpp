@@ -1662,6 +1662,117 @@ int HnswIndex::knn_query_general(const float *queries, int count, int dim, int k
     return knn_query_lockstep(redo.data(), (int)redo.size(), k, out_ids, out_dists, err, allow, layer);
 }
 
+// KnnQuery with a group filter per query: knn_query_general's filtered call for every group at once.  The labels go
+// to the device as they are; once slots are vacant a copy does, with the vacant slots in no group (as exact_knn_query_grouped).
+int HnswIndex::knn_query_grouped(const float *queries, int count, int dim, int k, int layer, const int *row_group, long long n_row_group, const int *query_group,
+                                 int n_groups, int *out_ids, float *out_dists, std::string &err)
+{
+    if (count <= 0) return 0;
+    if (failed(err)) return -1;
+    const char *who = "hnsw_mi355x_knn_query_grouped";
+    if (n_groups < 1 || n_groups > 65536) {
+        err = std::string("System.ArgumentOutOfRangeException: ") + who + ": n_groups = " + std::to_string(n_groups) + " is outside 1 .. 65536";
+        return -1;
+    }
+    for (int i = 0; i < count; ++i)
+        if (query_group[i] < 0 || query_group[i] >= n_groups) {
+            err = std::string("System.ArgumentOutOfRangeException: ") + who + ": query_group[" + std::to_string(i) + "] = " + std::to_string(query_group[i]) +
+                  " is outside 0 .. n_groups - 1 = " + std::to_string(n_groups - 1);
+            return -1;
+        }
+    const bool empty = k < 1 || graph_.entry < 0 || graph_.count <= 0;
+    if (!empty && !layer_ok(layer, err)) { err = "System.IndexOutOfRangeException: " + std::string(who) + ": " + err; return -1; }
+    if (empty) { // HNSWIndex.cs:109: empty result lists, padded by the export
+        pad_results(out_ids, out_dists, (size_t)count * (size_t)std::max(k, 0));
+        return 0;
+    }
+    const long long n_lab = std::min<long long>(n_row_group, graph_.length);
+    std::vector<int> live;
+    if (graph_.count != graph_.length) { // vacant slots: in no group
+        live.assign(row_group, row_group + n_lab);
+        for (long long id = 0; id < n_lab; ++id)
+            if (graph_.removed[(size_t)id]) live[(size_t)id] = -1;
+        live.push_back(-1); // (never NULL)
+        row_group = live.data();
+    }
+    std::vector<char> has_id((size_t)n_groups, 0); // groups that hold an id of the graph
+    for (long long id = 0; id < n_lab; ++id)
+        if (row_group[id] >= 0 && row_group[id] < n_groups) has_id[(size_t)row_group[id]] = 1;
+    bool any = false;
+    for (int i = 0; i < count && !any; ++i) any = has_id[(size_t)query_group[i]] != 0;
+    if (!any) { // no query's group holds an id: the result is empty in any order (no launch, no traversal)
+        pad_results(out_ids, out_dists, (size_t)count * (size_t)k);
+        return 0;
+    }
+    if (set_resident_queries(queries, count, dim, err) < 0) return -1;
+    // The lock-step way for the queries in `which` (nullptr: all of them): one bitset per group concerned, one filtered call per group;
+    // queries of a group without ids are padded.
+    const auto lockstep = [&](const int *which, int n) -> int {
+        std::vector<std::vector<int>> of((size_t)n_groups);
+        for (int i = 0; i < n; ++i) {
+            const int qi = which ? which[i] : i;
+            const int g = query_group[qi];
+            if (has_id[(size_t)g]) of[(size_t)g].push_back(qi);
+            else pad_results(out_ids + (size_t)qi * k, out_dists + (size_t)qi * k, (size_t)k);
+        }
+        std::vector<uint32_t> bits((size_t)((n_lab + 31) / 32) + 1);
+        for (int g = 0; g < n_groups; ++g) {
+            if (of[(size_t)g].empty()) continue;
+            std::fill(bits.begin(), bits.end(), 0u);
+            for (long long id = 0; id < n_lab; ++id)
+                if (row_group[id] == g) bits[(size_t)(id >> 5)] |= 1u << (id & 31);
+            if (knn_query_lockstep(of[(size_t)g].data(), (int)of[(size_t)g].size(), k, out_ids, out_dists, err, AllowBits{bits.data(), n_lab}, layer) < 0) return -1;
+        }
+        return 0;
+    };
+    const int ef = std::max(p_.min_nn, k); // HNSWIndex.cs:115
+    if (!(p_.device_traversal && dev_->traversal_fits(ef, false, p_.max_edges))) {
+        if (sharded_resident_) { // the host traversal runs on the primary alone: it needs the whole set there (as knn_query_resident)
+            if (!gather_queries_to_primary(count, err)) return -1;
+            sharded_resident_ = false;
+        }
+        return lockstep(nullptr, count);
+    }
+    if (!sync_graph(err)) return -1;
+    const int ep = graph_.entry, top = graph_.top_layer();
+    std::vector<int> flag((size_t)count);
+    // one context's share: cnt resident queries of its own, rows lo.. of the caller's arrays and of query_group
+    const auto search = [&](Device *ctx, int cnt, long long lo) -> bool {
+        return ctx->search_grouped(cnt, ep, top, ef, k, row_group, n_lab, query_group + lo, n_groups, out_ids + (size_t)lo * k, out_dists + (size_t)lo * k,
+                                   flag.data() + lo, layer);
+    };
+    if (sharded_resident_) { // every context answers its shard with the labels uploaded to it
+        if (!ensure_replicas(true, err)) return -1;
+        const int n = p_.devices;
+        std::vector<std::string> errs((size_t)n);
+        std::vector<std::thread> th;
+        for (int g = 0; g < n; ++g)
+            th.emplace_back([&, g] {
+                const long long lo = shard_lo_[(size_t)g], hi = shard_lo_[(size_t)g + 1];
+                const int cnt = (int)(hi - lo);
+                if (cnt > 0 && !search(context(g), cnt, lo))
+                    errs[(size_t)g] = get_dev_error().empty() ? "search_grouped failed" : get_dev_error();
+            });
+        for (auto &t : th) t.join();
+        for (const std::string &e : errs) if (!e.empty()) { err = e; return -1; }
+    } else if (!search(dev_.get(), count, 0)) { err = get_dev_error(); return -1; }
+    const std::vector<int> redo = flagged_jobs(flag);
+    if (redo.empty()) return 0;
+    if (sharded_resident_) { // the exact host traversal names queries by their global index on the primary
+        if (!gather_queries_to_primary(count, err)) return -1;
+        sharded_resident_ = false;
+    }
+    return lockstep(redo.data(), (int)redo.size());
+}
+
+void HnswIndex::knn_grouped_info(uint64_t out[4]) const
+{
+    out[0] = out[1] = out[2] = out[3] = 0;
+    uint64_t one[4];
+    if (dev_) { dev_->knn_grouped_info(one); for (int i = 0; i < 4; ++i) out[i] += one[i]; }
+    for (const auto &r : replicas_) { r->knn_grouped_info(one); for (int i = 0; i < 4; ++i) out[i] += one[i]; }
+}
+
 // The candidates of a flat scan as Device::exact_knn / exact_range take them: the row count, and allow_bits / nbits replaced by
 // allow AND live (in `live`) once slots are vacant.
 long long HnswIndex::exact_candidates(const uint32_t *&allow_bits, long long &nbits, std::vector<uint32_t> &live) const

@@ -88,6 +88,14 @@ public:
     void graph_reach_counters(uint64_t out[4]) const { if (dev_) dev_->graph_reach_counters(out); else out[0] = out[1] = out[2] = out[3] = 0; }
     int knn_query_general(const float *queries, int count, int dim, int k, int layer, const uint32_t *allow_bits, long long nbits, int *out_ids,
                           float *out_dists, std::string &err);
+    // hnsw_mi355x_knn_query_grouped: KnnQuery on `layer` with a group filter per query -- query i is answered from the
+    // ids j < n_row_group with row_group[j] == query_group[i], byte for byte what knn_query_general returns for it with that group's
+    // ids as the allow-set.  One device traversal for every group (Device::search_grouped); jobs handed back, and the whole call when
+    // the traversal does not run on the device, go the lock-step way once per group.  Exclusive lock.  0 or -1.
+    int knn_query_grouped(const float *queries, int count, int dim, int k, int layer, const int *row_group, long long n_row_group, const int *query_group,
+                          int n_groups, int *out_ids, float *out_dists, std::string &err);
+    // Device::knn_grouped_info summed over the contexts
+    void knn_grouped_info(uint64_t out[4]) const;
     // hnsw_mi355x_multilayer_knn_query: the number of layer slots (min(top, max_layer) + 1; 0 for an empty index, k < 1 or
     // max_layer == -1), or -1.  out_*: [count][layers_cap][k - 1].  Exclusive lock.
     int multilayer_knn_query(const float *queries, int count, int dim, int k, int max_layer, int min_layer, int layers_cap, int *out_ids,

@@ -288,6 +288,32 @@ int hnsw_mi355x_exact_knn_query_grouped(void *handle, const float *vectors, int 
  * 0, or -1 for a NULL argument. */
 int hnsw_mi355x_exact_grouped_info(void *handle, uint64_t out[4]);
 
+/* hnsw_mi355x_knn_query_at_layer with a group filter per query (no reference counterpart): rows partitioned by
+ * tenant, category or language, every query answered from its own part by the GRAPH traversal, all parts in one launch.
+ * row_group is int32[n_row_group], indexed by id; query_group is int32[count].  Query i's filter is
+ * "j < n_row_group && row_group[j] == query_group[i]": a row_group value outside [0, n_groups) puts the id in no group, and so do
+ * ids >= n_row_group and vacant slots (removed ids); n_row_group beyond the index's length is clamped.  1 <= n_groups <= 65 536.
+ * For every group g the rows of the result at query_group == g are byte for byte -- ids and distance bits -- what
+ * hnsw_mi355x_knn_query_at_layer returns for those queries with the allow-set {j : row_group[j] == g} and the same layer, and so
+ * carry its rules: the descent is not filtered, the beam is max(MinNN, k), the stable OrderBy(Dist).Take(k), -1 / NaN padding, the
+ * layer rule (layer outside 0 .. the entry point's top layer on a non-empty index: -1), padding for an empty index or k < 1.  A
+ * query whose group holds no id of the graph gets a row of padding and costs no traversal.  The labels are uploaded with every call
+ * (nothing is cached between calls); hnsw_mi355x_set_devices(n): every context answers its shard of the queries with the labels
+ * uploaded to it.  A job the device hands back, and the whole call when the traversal does not run on the device
+ * (hnsw_mi355x_set_device_traversal(0), shapes the kernels do not fit), is answered by the host traversal, one filtered pass per
+ * group concerned, with the same results.  Takes the handle exclusively.
+ * -1 with a message, nothing written: row_group NULL or n_row_group < 0; n_groups outside 1 .. 65 536; a query_group value outside
+ * [0, n_groups) (the message names the first such index).  NULL handle and count <= 0: 0, nothing written.
+ * When groups are small the flat scan (hnsw_mi355x_exact_knn_query_grouped) is the faster tool: see DESIGN.md 3.20. */
+int hnsw_mi355x_knn_query_grouped(void *handle, const float *vectors, int count, int dim, int k, int layer, const int *row_group,
+                                  long long n_row_group, const int *query_group, int n_groups, int *out_ids, float *out_dists);
+/* Counters of hnsw_mi355x_knn_query_grouped's device launches, summed over the contexts, since hnsw_mi355x_reset_stats: out[0]
+ * calls that reached a context (one per context and call), out[1] queries launched, out[2] queries padded without a job because
+ * their group holds no graph id, out[3] queries the device handed back to the host traversal.  (The launches, evaluations and
+ * hand-backs also count in hnswdev_stats.search_launches / search_evals / search_overflows, as a filtered call's do; a call
+ * answered by the host traversal alone counts nowhere here.)  0, or -1 for a NULL argument. */
+int hnsw_mi355x_knn_grouped_info(void *handle, uint64_t out[4]);
+
 /* Measurement aid: hnsw_mi355x_set_queries uploads a query set (count x dim) once; every later
  * hnsw_mi355x_knn_query_resident(k) is hnsw_knn_query on that set with the inputs already in HBM
  * (out arrays: count x k). */
@@ -560,6 +586,16 @@ int hnswdev_knn_search_at_layer(void *ctx, const float *queries, int nq, int ent
                                 const uint32_t *allow_bits, long long nbits, int *out_ids, float *out_dists, int *out_flags);
 int hnswdev_range_search_at_layer(void *ctx, const float *queries, int nq, int entry_point, float range, int layer, const uint32_t *allow_bits,
                                   long long nbits, int *out_counts, int *out_flags);
+/* hnswdev_knn_search_at_layer with a group filter per query (graph_search_grouped_kernel; the labels of
+ * hnsw_mi355x_knn_query_grouped): query i is answered from the graph ids j < n_row_group with row_group[j] == query_group[i], row by
+ * row what hnswdev_knn_search_at_layer returns for it with that group's ids as the allow-set.  A query whose group holds no graph id:
+ * a padded row, flag 0, no job.  out_flags[i] = 1: handed back, as hnswdev_knn_search_filtered.  -1 with a message and no launch:
+ * a NULL array, n_row_group < 0, n_groups outside 1 .. 65 536, a query_group value outside [0, n_groups), an entry point outside the
+ * graph, k_out < 1 or k_beam < k_out, a layer the entry point does not have. */
+int hnswdev_knn_search_grouped(void *ctx, const float *queries, int nq, int entry_point, int k_beam, int k_out, int layer, const int *row_group,
+                               long long n_row_group, const int *query_group, int n_groups, int *out_ids, float *out_dists, int *out_flags);
+/* out[0 .. 3] as hnsw_mi355x_knn_grouped_info, of this context; zeroed by hnswdev_reset_stats. */
+int hnswdev_knn_grouped_info(void *ctx, uint64_t out[4]);
 /* MultiLayerKnnQuery's chains (graph_multilayer_kernel), one job per query: layers min(top, max_layer) .. min_layer with beam k
  * (k >= 2), top = entry_point's level; semantics of hnsw_mi355x_multilayer_knn_query.  Returns the slot count min(top, max_layer) + 1
  * (0 for max_layer == -1), or -1 (max_layer < -1, min_layer < 0, layers_cap below the count).  out_ids / out_dists:
