@@ -7,7 +7,7 @@ string on a negative status).  `DeviceBackend` exposes the inner hnswdev_* bound
 import ctypes as ct
 import os
 from pathlib import Path
-from typing import List, Tuple
+from typing import List, Optional, Tuple
 
 import numpy as np
 import numpy.typing as npt
@@ -185,6 +185,25 @@ lib.hnswdev_graph_reach.restype = ct.c_int
 lib.hnswdev_graph_reach.argtypes = [ct.c_void_p, ct.c_int, _U32, ct.c_longlong, ct.c_int, ct.POINTER(LayerReach), ct.c_int, _U32, _I]
 lib.hnswdev_graph_reach_counters.restype = ct.c_int
 lib.hnswdev_graph_reach_counters.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
+
+
+class LayerRepair(ct.Structure):
+    """hnsw_mi355x_layer_repair: what repair_reachability did on one layer."""
+    _fields_ = [(n, ct.c_int32) for n in ("layer_id", "unreachable_before", "linked", "evicted", "rounds", "unreachable_after")]
+
+    def as_dict(self) -> dict:
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+_GRAPH_REPAIR_COUNTERS = ("rounds", "pairs", "distances", "lists_patched")   # hnswdev_graph_repair_counters' out[0 .. 3]
+lib.hnsw_mi355x_repair_reachability.restype = ct.c_int
+lib.hnsw_mi355x_repair_reachability.argtypes = [ct.c_void_p, ct.c_int, ct.c_int, ct.POINTER(LayerRepair), ct.c_int]
+lib.hnsw_mi355x_graph_repair_counters.restype = ct.c_int
+lib.hnsw_mi355x_graph_repair_counters.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
+lib.hnswdev_graph_repair_propose.restype = ct.c_int
+lib.hnswdev_graph_repair_propose.argtypes = [ct.c_void_p, ct.c_int, _U32, ct.c_longlong, _U32, ct.c_longlong, ct.c_int, ct.c_int, _I, _I, _I, _I, ct.c_int]
+lib.hnswdev_graph_repair_counters.restype = ct.c_int
+lib.hnswdev_graph_repair_counters.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
 lib.hnsw_mi355x_range_query_filtered.restype = ct.c_int
 lib.hnsw_mi355x_range_query_filtered.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_int, ct.c_float, _U32, ct.c_longlong, ct.POINTER(ct.c_void_p),
                                                  ct.POINTER(ct.c_void_p), ct.POINTER(ct.c_int)]
@@ -872,6 +891,28 @@ class Index:
             lib.hnsw_mi355x_graph_reach_counters(self._h, out)
         return dict(zip(_GRAPH_REACH_COUNTERS, (int(v) for v in out)))
 
+    # ---- repair of reachability ----
+    def repair_reachability(self, cands: int = 8, max_rounds: int = 8) -> List[dict]:
+        """Links the items that unreachable_ids() reports into the lists of their nearest reached members, on the device, layer by
+        layer from the top; one dict per layer 0 .. top with the fields of hnsw_mi355x_layer_repair.  Opt-in: it edits neighbour
+        lists, so the graph is no longer an outcome of the reference's Add (it stays well formed, and its snapshots load).  It
+        promises reachability, not recall.  cands, max_rounds: 1 .. 64.  An empty list for an empty index."""
+        if not self._initialized:
+            self._initialize()
+        cap = max(1, self.top_layer() + 1)   # one call: a second one would report what it found left to do, which is nothing
+        out = (LayerRepair * cap)()
+        n = lib.hnsw_mi355x_repair_reachability(self._h, int(cands), int(max_rounds), out, cap)
+        if n < 0:
+            raise RuntimeError(last_error())
+        return [out[i].as_dict() for i in range(min(n, cap))]
+
+    def graph_repair_counters(self) -> dict:
+        """Counters of repair_reachability since reset_stats (hnsw_mi355x_graph_repair_counters)."""
+        out = (ct.c_uint64 * 4)()
+        if self._h:
+            lib.hnsw_mi355x_graph_repair_counters(self._h, out)
+        return dict(zip(_GRAPH_REPAIR_COUNTERS, (int(v) for v in out)))
+
     # ---- HNSWIndex.Serialize / Deserialize (src/HNSWIndex/HNSWIndex.cs:210-229) ----
     def serialize(self, path) -> None:
         """Write the reference's protobuf-net snapshot of this index to `path`."""
@@ -935,6 +976,7 @@ class DeviceBackend:
             raise RuntimeError("hnswdev_create failed: " + _dev_error())
         self._ctx = ctx
         self._graph_n = 0   # nodes of the committed graph (set_graph)
+        self._graph_m = 0   # ... and its max_edges
 
     def __del__(self):
         if getattr(self, "_ctx", None):
@@ -1018,6 +1060,7 @@ class DeviceBackend:
             self._check(lib.hnswdev_graph_set_layer(self._ctx, layer, c.ctypes.data_as(_I), e.ctypes.data_as(_I), e.shape[1]))
         self._check(lib.hnswdev_graph_commit(self._ctx))
         self._graph_n = int(lv.size)
+        self._graph_m = int(max_edges)
 
     @staticmethod
     def _live_arg(live):
@@ -1088,6 +1131,31 @@ class DeviceBackend:
         out = (ct.c_uint64 * 4)()
         self._check(lib.hnswdev_graph_reach_counters(self._ctx, out))
         return dict(zip(_GRAPH_REACH_COUNTERS, (int(v) for v in out)))
+
+    def graph_repair_propose(self, layer: int, seeds, live=None, cands: int = 8, max_edges: Optional[int] = None):
+        """hnswdev_graph_repair_propose: steps 1 - 3 of one repair round on one layer of the committed graph (read, not changed), from
+        `seeds` (a bool mask or an id list, as `live`).  (U[n_u] ascending, cands[n_u, cands], codes[n_u, cands]).  max_edges:
+        MaxEdges(layer); None: 2 M on layer 0 and M above, M the max_edges given to set_graph."""
+        _, wp, nbits = self._live_arg(live)
+        swords, snbits = allow_bits(seeds)
+        swords, sp = _words_arg(swords)
+        if max_edges is None:
+            max_edges = self._graph_m * (2 if int(layer) == 0 else 1)
+        n, c = int(self._graph_n), int(cands)
+        n_u = ct.c_int(0)
+        ids = np.zeros(max(n, 1), dtype=np.int32)
+        cd = np.zeros((max(n, 1), max(c, 1)), dtype=np.int32)
+        code = np.zeros((max(n, 1), max(c, 1)), dtype=np.int32)
+        self._check(lib.hnswdev_graph_repair_propose(self._ctx, int(layer), wp, nbits, sp, snbits, c, int(max_edges), ct.byref(n_u), ids.ctypes.data_as(_I),
+                                                     cd.ctypes.data_as(_I), code.ctypes.data_as(_I), n))
+        k = int(n_u.value)
+        return ids[:k].copy(), cd[:k].copy(), code[:k].copy()
+
+    def graph_repair_counters(self) -> dict:
+        """Counters of graph_repair_propose since reset_stats (hnswdev_graph_repair_counters)."""
+        out = (ct.c_uint64 * 4)()
+        self._check(lib.hnswdev_graph_repair_counters(self._ctx, out))
+        return dict(zip(_GRAPH_REPAIR_COUNTERS, (int(v) for v in out)))
 
     def knn_search(self, queries, entry_point: int, k_beam: int, k_out: int, allowed=None, layer: int = 0):
         """allowed: as for Index.knn_query (hnswdev_knn_search_filtered); None runs hnswdev_knn_search.  layer != 0:

@@ -77,6 +77,16 @@ struct VisitedScratch;   // device_backend.hip: the visited-set memory of a trav
 struct TraversalLaunch;  // ... which traversal kernel form a launch runs, on how many waves, with which flags
 struct LaunchFamily;     // ... the hnswdev_stats counters of one kernel family
 struct ReachSeeds;       // dk_graph_reach.h: the seed set of one layer's reachability pass
+// What one round of repair_reachability brings back (Device::graph_repair_round).  The three arrays are pinned memory of the
+// context, valid until its next round; they are nullptr where no proposal ran (propose == false, or nothing is unreached).
+constexpr int kRepairSeedEntry = 0, kRepairSeedBits = 1, kRepairSeedAbove = 2; // graph_repair_round's seed_mode (dk_graph_reach.h's kReachSeed*)
+struct GraphRepairRound {
+    uint64_t summary[4] = {0, 0, 0, 0}; // the BFS's: members, member seeds, reached, largest hop
+    int n_u = 0;                        // members without a hop: members - reached
+    const int *ids = nullptr;           // [n_u] U, ascending
+    const int *cands = nullptr;         // [n_u][cands] the nearest reached members by (distance, id), padded with -1
+    const int *codes = nullptr;         // [n_u][cands] where in the candidate's list u could go, -1: nowhere
+};
 struct LayerView;        // dk_graph_info.h: the mirror as the graph-info kernels see one layer of it
 struct GraphAcc;         // ... what those kernels add up
 struct ErrorScope { // RAII: the calling thread is inside a call on `d`
@@ -395,6 +405,23 @@ public:
     // layers walked, rounds (expansion launches), list entries the expansions read (counted by the kernel), kernel launches
     void graph_reach_counters(uint64_t out[4]) const { for (int i = 0; i < 4; ++i) out[i] = gr_info_[i]; }
 
+    // One round of repair_reachability (dk_graph_repair.h), steps 1 - 3, on one layer of the mirror; the mirror is read,
+    // never written.  Members and the live set are graph_info's.  The seeds: seed_mode kRepairSeedEntry: the one id entry_point,
+    // kRepairSeedBits: seed_bits / seed_nbits as graph_reach_layer's, kRepairSeedAbove: the nodes that the round last run into
+    // slot which ^ 1 reached (the layer above).  The BFS writes slot `which` of the two hop arrays, which stay on the device.  With
+    // `propose` and members left unreached: for each of them, ascending, the `cands` nearest reached members -- the ids exact_knn
+    // returns for its stored row as the query, k = cands, the reached set as allow-set -- and for each such candidate v the slot of
+    // v's list that the proposal rule names (max_edges: MaxEdges(layer)).  1 <= cands <= 64.  Synchronous.
+    bool graph_repair_round(int layer, const uint32_t *live_bits, long long nbits, int seed_mode, int entry_point, const uint32_t *seed_bits, long long seed_nbits,
+                            int which, int cands, int max_edges, bool propose, GraphRepairRound *out);
+    // patch_lists for the lists a round's apply step changed, counted
+    bool graph_repair_patch(const int *recs, int nrows, int row_stride);
+    // hnswdev_graph_repair_propose: a round with seed_bits on slot 0, copied out: *out_n = |U|, min(cap, |U|) rows written.  0 or -1.
+    int graph_repair_propose(int layer, const uint32_t *live_bits, long long nbits, const uint32_t *seed_bits, long long seed_nbits, int cands, int max_edges,
+                             int *out_n, int *out_ids, int *out_cands, int *out_codes, int cap);
+    // rounds that ran the proposal kernel, (u, candidate) pairs it judged, distances it measured (counted by the kernel), lists patched
+    void graph_repair_counters(uint64_t out[4]) const { for (int i = 0; i < 4; ++i) out[i] = rp_info_[i]; }
+
     void set_profiling(bool on) { profiling_ = on; }
 
     // search launches of a call that shares the chip with another call (query lanes) keep no idle waves behind as shadows
@@ -496,6 +523,7 @@ private:
     DevBuf<double> x_q_sn_;
     bool exact_queries(const char *who, const float *queries, int nq, const float **d_q, const double **d_qsn);
     bool exact_id_list(const uint32_t *allow_bits, long long n_allow, long long *m);
+    bool exact_knn_rounds(const float *d_q, const double *d_qsn, int nq, const int *d_idlist, long long m, int k, int *out_ids, float *out_d, int *d_keep_ids);
     bool exact_copy_out(void *dst, const void *src, size_t bytes);
     bool exact_range_run(const float *queries, int nq, long long n_rows, float range, const uint32_t *allow_bits, long long nbits, int *out_counts);
     DevBuf<unsigned long long> x_rarena_; // exact_range: the round's keys, a segment per query: at most 1 GiB, grown on demand and kept
@@ -525,6 +553,15 @@ private:
     DevBuf<unsigned> gr_bits_, gr_seed_; // ... the reached set as a bitset; graph_reach_layer's seed set
     DevBuf<unsigned long long> gr_acc_; // ... the layer's ReachAcc
     uint64_t gr_info_[4] = {0, 0, 0, 0};
+    DevBuf<unsigned> rp_bits_;          // graph_repair_round: [the unreached members | the reached set] as bitsets
+    DevBuf<int> rp_bcnt_;               // ... their set bits per block of kExactCompactWords words
+    DevBuf<long long> rp_boff_;         // ... and the exclusive prefix of those (exact_compact_kernel's block offsets)
+    DevBuf<int> rp_uids_, rp_cand_;     // ... U ascending; [candidates | codes]
+    DevBuf<float> rp_q_;                // ... the rows of U as the scan's queries
+    DevBuf<double> rp_qsn_;
+    DevBuf<unsigned long long> rp_meas_; // ... distances the proposal kernel measured
+    PinBuf<int> rp_host_;               // ... [U | candidates | codes | measured] on the host
+    uint64_t rp_info_[4] = {0, 0, 0, 0};
     DevBuf<SearchHit> s_arena_; // range search: the launch's results, packed
     DevBuf<unsigned long long> s_roff_, s_arena_used_; // s_roff_ stands for the capacity of range_batch's per-job arrays
     DevBuf<int> s_rentry_;

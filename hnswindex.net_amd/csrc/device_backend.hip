@@ -52,6 +52,7 @@
 #include "dk_exact.h"
 #include "dk_graph_info.h"
 #include "dk_graph_reach.h"
+#include "dk_graph_repair.h"
 #include "range_replay.h"
 
 namespace hnsw {
@@ -919,6 +920,7 @@ void Device::reset_stats()
     xg_list_ms_ = 0.0;
     for (uint64_t &v : gi_info_) v = 0;
     for (uint64_t &v : gr_info_) v = 0;
+    for (uint64_t &v : rp_info_) v = 0;
 #ifdef EXP_PHASE_CLOCKS
     (void)hipDeviceSynchronize();
     phase_report("reset_stats");
@@ -2688,6 +2690,14 @@ bool Device::exact_knn(const float *queries, int nq, long long n_rows, int k, co
     const double *d_qsn;
     long long m;
     if (!exact_queries("exact_knn", queries, nq, &d_q, &d_qsn) || !bind() || !exact_id_list(allow_bits, n_allow, &m)) return false;
+    return exact_knn_rounds(d_q, d_qsn, nq, allow_bits ? x_ids_.get() : nullptr, m, k, out_ids, out_d, nullptr);
+}
+
+// The rounds of a top-k flat scan: nq queries on the device (d_q, pitch_ words each; d_qsn their cosine norms or nullptr) against the
+// m entries of the id list d_ids (nullptr: the identity).  out_d may be nullptr; d_keep_ids: nullptr, or nq x k ints on the device
+// that receive the ids as well (graph_repair_round's candidates stay there for the proposal kernel).
+bool Device::exact_knn_rounds(const float *d_q, const double *d_qsn, int nq, const int *d_idlist, long long m, int k, int *out_ids, float *out_d, int *d_keep_ids)
+{
     hipStream_t st = S(stream_);
     const ExactPlan p = exact_plan(nq, m, k, pitch_, num_cu_);
     if (p.lds > 64 * 1024) { set_dev_error("exact_knn: tile exceeds the LDS budget"); return false; }
@@ -2703,7 +2713,7 @@ bool Device::exact_knn(const float *queries, int nq, long long n_rows, int k, co
         a.rows = d_rows_; a.row_sn = d_row_sn_;
         a.queries = d_q + (size_t)off * pitch_;
         a.q_sn = d_qsn ? d_qsn + off : nullptr;
-        a.dim = pitch_; a.ids = allow_bits ? x_ids_ : nullptr; a.m = m; a.chunk = p.chunk; a.nq = nr; a.qtile = p.qtile; a.piece = p.piece; a.k = k;
+        a.dim = pitch_; a.ids = d_idlist; a.m = m; a.chunk = p.chunk; a.nq = nr; a.qtile = p.qtile; a.piece = p.piece; a.k = k;
         a.lists = x_lists_; a.n_chunks = p.n_chunks; a.evals = x_evals_;
         const unsigned tiles = (unsigned)((nr + p.qtile - 1) / p.qtile);
         int *d_ids = x_out_;
@@ -2719,9 +2729,10 @@ bool Device::exact_knn(const float *queries, int nq, long long n_rows, int k, co
         HIP_OK(hipMemcpyAsync(hs, d_ids, 4u * (size_t)nr * k, hipMemcpyDeviceToHost, st));
         HIP_OK(hipMemcpyAsync(hs + 4u * (size_t)p.round * k, d_d, 4u * (size_t)nr * k, hipMemcpyDeviceToHost, st));
         HIP_OK(hipMemcpyAsync(h_ev, x_evals_, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+        if (d_keep_ids) HIP_OK(hipMemcpyAsync(d_keep_ids + (size_t)off * k, d_ids, 4u * (size_t)nr * k, hipMemcpyDeviceToDevice, st));
         HIP_OK(hipStreamSynchronize(st));
         memcpy(out_ids + (size_t)off * k, hs, 4u * (size_t)nr * k);
-        memcpy(out_d + (size_t)off * k, hs + 4u * (size_t)p.round * k, 4u * (size_t)nr * k);
+        if (out_d) memcpy(out_d + (size_t)off * k, hs + 4u * (size_t)p.round * k, 4u * (size_t)nr * k);
         // (the flat scan is no traversal: it counts in its own family only, not in the search_* totals; the evaluations are the
         // kernel's own count of the pairs it turned into keys -- shadows excluded -- not nr * m worked out here)
         stats_.exact_launches += 1; stats_.exact_evals += *h_ev;
@@ -3428,6 +3439,139 @@ bool Device::graph_reach_top(const char *who, int entry_point, int *top)
     return true;
 }
 
+// ---- one round of repair_reachability on the mirror (device code in dk_graph_repair.h) ---------------------------
+// BFS (graph_reach_run into gr_hop_[which]); then, where it is asked for and members are left without a hop: U and the reached set
+// as ascending id lists (collect -> offsets -> exact_compact_kernel: the order is the bitset's, nothing is sorted and nothing goes
+// through the host), the rows of U as the scan's queries, the flat scan over the reached ids, and the proposal kernel.  What comes
+// back is U, the candidates and the codes, in pinned memory of the call's own; the hop array stays on the device.
+bool Device::graph_repair_round(int layer, const uint32_t *live_bits, long long nbits, int seed_mode, int entry_point, const uint32_t *seed_bits,
+                                long long seed_nbits, int which, int cands, int max_edges, bool propose, GraphRepairRound *out)
+{
+    static_assert(kRepairSeedEntry == kReachSeedId && kRepairSeedBits == kReachSeedBits && kRepairSeedAbove == kReachSeedHops, "the seed modes of device_backend.h");
+    const char *who = "graph_repair_round";
+    if (!out || which < 0 || which > 1 || seed_mode < kReachSeedId || seed_mode > kReachSeedHops || (seed_mode == kReachSeedBits && (!seed_bits || seed_nbits < 0))) {
+        set_dev_error(std::string(who) + ": bad argument");
+        return false;
+    }
+    if (cands < 1 || cands > kRepairMaxCands) { set_dev_error(std::string(who) + ": cands = " + std::to_string(cands) + " is outside 1 .. " + std::to_string(kRepairMaxCands)); return false; }
+    *out = GraphRepairRound{};
+    LayerView g;
+    if (!graph_info_begin(who, layer, live_bits, nbits, &g) || !graph_reach_room()) return false;
+    const int list_cap = (layer == 0 ? g_stride0_ : g_strideU_) - 1;
+    if (max_edges < 1 || max_edges > list_cap) {
+        set_dev_error(std::string(who) + ": max_edges = " + std::to_string(max_edges) + " is outside 1 .. " + std::to_string(list_cap) + " (what a list of the mirror holds)");
+        return false;
+    }
+    hipStream_t st = S(stream_);
+    HIP_OK(hipStreamSynchronize(st)); // (the live set has left the pinned stage)
+    ReachSeeds seeds{seed_mode, -1, nullptr, 0, nullptr};
+    if (seed_mode == kReachSeedId) seeds.id = entry_point >= 0 && (long long)entry_point < g_n_ ? entry_point : -1;
+    else if (seed_mode == kReachSeedHops) seeds.prev_hop = gr_hop_[which ^ 1].get();
+    else {
+        const long long sb = std::min(seed_nbits, g_n_);
+        const size_t words = (size_t)((sb + 31) / 32);
+        void *hs = pinned_stage(std::max<size_t>(4 * words, sizeof(ReachAcc)));
+        if (!hs || !gr_seed_.grow(std::max<size_t>(words, 1))) return false;
+        memcpy(hs, seed_bits, 4 * words);
+        if (words) HIP_OK(hipMemcpyAsync(gr_seed_, hs, 4 * words, hipMemcpyHostToDevice, st));
+        HIP_OK(hipStreamSynchronize(st));
+        seeds.bits = gr_seed_.get(); seeds.nbits = sb;
+    }
+    if (!graph_reach_run(g, seeds, which, false, out->summary)) return false;
+    const long long n_u = (long long)(out->summary[0] - out->summary[2]), reached = (long long)out->summary[2];
+    out->n_u = (int)n_u;
+    if (!propose || n_u <= 0) return true;
+    if (g_n_ > n_rows_hw_) { set_dev_error(std::string(who) + ": the graph has nodes whose rows were never uploaded"); return false; }
+    const size_t C = (size_t)cands, pairs = (size_t)n_u * C;
+    if (!rp_host_.grow((size_t)n_u + 2 * pairs + 4)) return false;
+    int *h_ids = rp_host_.get(), *h_cand = h_ids + n_u, *h_code = h_cand + pairs;
+    out->ids = h_ids; out->cands = h_cand; out->codes = h_code;
+
+    // U and the reached set, ascending
+    const long long words = (g_n_ + 31) / 32;
+    const int blocks = (int)((words + kExactCompactWords - 1) / kExactCompactWords);
+    const size_t cap_n = (size_t)std::max<long long>(g_n_, g_cap_n()), cap_w = (cap_n + 31) / 32, cap_b = (cap_w + kExactCompactWords - 1) / kExactCompactWords;
+    if (!rp_bits_.grow(2 * (size_t)words, 2 * cap_w) || !rp_bcnt_.grow(2 * (size_t)blocks, 2 * cap_b) || !rp_boff_.grow(2 * (size_t)blocks, 2 * cap_b) ||
+        !rp_uids_.grow((size_t)n_u) || !x_ids_.grow((size_t)std::max<long long>(reached, 1)) || !rp_cand_.grow(2 * pairs) || !rp_meas_.grow(1)) return false;
+    const unsigned node_blocks = graph_info_blocks(g_n_, num_cu_);
+    const int *hop = gr_hop_[which].get();
+    HIP_OK(hipMemsetAsync(rp_bcnt_, 0, sizeof(int) * 2 * (size_t)blocks, st));
+    for (int sel = 0; sel < 2; ++sel) { // 0: U, 1: the reached set
+        hipLaunchKernelGGL(graph_repair_collect_kernel, dim3(node_blocks), dim3(kRepairBlock), 0, st, (long long)g_n_, hop, sel == 0 ? 1 : 0, rp_bits_.get() + sel * words,
+                           rp_bcnt_.get() + sel * blocks);
+        HIP_OK(hipGetLastError());
+        hipLaunchKernelGGL(graph_repair_offsets_kernel, dim3(1), dim3(64), 0, st, rp_bcnt_.get() + sel * blocks, blocks, rp_boff_.get() + sel * blocks);
+        HIP_OK(hipGetLastError());
+        if (sel == 0 || reached > 0)
+            HIP_OK(exact_compact_launch(rp_bits_.get() + sel * words, words, rp_boff_.get() + sel * blocks, sel == 0 ? rp_uids_.get() : x_ids_.get(), st));
+    }
+    HIP_OK(hipMemcpyAsync(h_ids, rp_uids_, sizeof(int) * (size_t)n_u, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    if (reached <= 0) { // nobody to link to: every candidate is padding, nothing is proposed
+        std::fill(h_cand, h_cand + 2 * pairs, -1);
+        return true;
+    }
+
+    // the rows of U as the scan's query set: what set_queries makes of hnswdev_download_rows' rows, without the host
+    if (!rp_q_.grow((size_t)n_u * pitch_) || (metric_ == M_COS && !rp_qsn_.grow((size_t)n_u)) || (metric_ == M_I8 && !q_stage_.grow((size_t)n_u * (size_t)dim_))) return false;
+    const int kind = metric_ == M_I8 ? 2 : metric_f16(metric_) ? 1 : 0;
+    hipLaunchKernelGGL(graph_repair_gather_kernel, dim3(graph_info_blocks(n_u * dim_, num_cu_)), dim3(kRepairBlock), 0, st, d_rows_.get(), row_pitch_, n_rows_hw_, kind,
+                       rp_uids_.get(), n_u, dim_, metric_ == M_I8 ? q_stage_.get() : rp_q_.get());
+    HIP_OK(hipGetLastError());
+    if (metric_ == M_I8) {
+        hipLaunchKernelGGL(quantize_rows_kernel, dim3((unsigned)((n_u + 3) / 4)), dim3(256), 0, st, q_stage_, dim_, (int)n_u, rp_q_, 0LL, pitch_);
+        HIP_OK(hipGetLastError());
+    }
+    if (metric_ == M_COS) {
+        hipLaunchKernelGGL(row_sqrtnorm_kernel, dim3((unsigned)((n_u * 8 + 255) / 256)), dim3(256), 0, st, rp_q_, pitch_, 0LL, (int)n_u, rp_qsn_);
+        HIP_OK(hipGetLastError());
+    }
+    int *d_cand = rp_cand_.get(), *d_code = d_cand + pairs;
+    if (!exact_knn_rounds(rp_q_, metric_ == M_COS ? rp_qsn_.get() : nullptr, (int)n_u, x_ids_, reached, cands, h_cand, nullptr, d_cand)) return false;
+
+    // the proposals
+    rp_info_[0] += 1;
+    RepairProposeArgs a;
+    a.g = g; a.rows = d_rows_; a.row_sn = d_row_sn_; a.dim = pitch_; a.n_rows = n_rows_hw_; a.hop = hop; a.cand = d_cand; a.n_pairs = (long long)pairs;
+    a.max_edges = max_edges; a.code = d_code; a.measured = rp_meas_;
+    HIP_OK(hipMemsetAsync(rp_meas_, 0, sizeof(unsigned long long), st));
+    hipError_t e = hipSuccess;
+    with_metric(metric_, [&](auto mt) { e = graph_repair_propose_launch<mt>(a, graph_info_blocks((long long)pairs * 64, num_cu_), st); });
+    HIP_OK(e);
+    unsigned long long *h_meas = reinterpret_cast<unsigned long long *>(h_ids + (((size_t)n_u + 2 * pairs + 1) & ~(size_t)1));
+    HIP_OK(hipMemcpyAsync(h_code, d_code, sizeof(int) * pairs, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(h_meas, rp_meas_, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    uint64_t real = 0;
+    for (size_t i = 0; i < pairs; ++i) real += h_cand[i] >= 0;
+    rp_info_[1] += real; rp_info_[2] += *h_meas;
+    return true;
+}
+
+bool Device::graph_repair_patch(const int *recs, int nrows, int row_stride)
+{
+    if (!patch_lists(recs, nrows, row_stride)) return false;
+    rp_info_[3] += (uint64_t)std::max(nrows, 0);
+    return true;
+}
+
+// hnswdev_graph_repair_propose: steps 1 - 3 of one round on the committed graph, which is read and not changed
+int Device::graph_repair_propose(int layer, const uint32_t *live_bits, long long nbits, const uint32_t *seed_bits, long long seed_nbits, int cands, int max_edges,
+                                 int *out_n, int *out_ids, int *out_cands, int *out_codes, int cap)
+{
+    if (!out_n || cap < 0 || (cap > 0 && (!out_ids || !out_cands || !out_codes))) { set_dev_error("graph_repair_propose: bad argument"); return -1; }
+    GraphRepairRound r;
+    if (!graph_repair_round(layer, live_bits, nbits, kReachSeedBits, -1, seed_bits, seed_nbits, 0, cands, max_edges, true, &r)) return -1;
+    *out_n = r.n_u;
+    const size_t n = (size_t)std::min(cap, r.n_u), C = (size_t)cands;
+    if (n) {
+        memcpy(out_ids, r.ids, sizeof(int) * n);
+        memcpy(out_cands, r.cands, sizeof(int) * n * C);
+        memcpy(out_codes, r.codes, sizeof(int) * n * C);
+    }
+    return 0;
+}
+
 // ---- synchronous conveniences behind the C ABI ---------------------------------------
 // Distance(int, TVector) for nq (query, candidate list) pairs.  Runs on the context's two step-
 // buffer sets, ping-pong: while the GPU measures one set the host packs the next and unpacks the
@@ -3731,6 +3875,20 @@ DEV_API int hnswdev_graph_reach_counters(void *ctx, uint64_t out[4])
     CTX_OR_FAIL();
     if (!out) return -1;
     d->graph_reach_counters(out);
+    return 0;
+}
+DEV_API int hnswdev_graph_repair_propose(void *ctx, int layer, const uint32_t *live_bits, long long nbits, const uint32_t *seed_bits, long long seed_nbits, int cands,
+                                         int max_edges, int *out_n, int *out_ids, int *out_cands, int *out_codes, int cap)
+{
+    CTX_OR_FAIL();
+    if (!d->graph_info_layer("hnswdev_graph_repair_propose", layer)) return -1;
+    return d->graph_repair_propose(layer, live_bits, nbits, seed_bits, seed_nbits, cands, max_edges, out_n, out_ids, out_cands, out_codes, cap);
+}
+DEV_API int hnswdev_graph_repair_counters(void *ctx, uint64_t out[4])
+{
+    CTX_OR_FAIL();
+    if (!out) return -1;
+    d->graph_repair_counters(out);
     return 0;
 }
 DEV_API int hnswdev_range_results(void *ctx, int *out_ids, float *out_dists) { CTX_OR_FAIL(); return d->range_results(out_ids, out_dists) ? 0 : -1; }

@@ -569,6 +569,29 @@ API int hnsw_mi355x_graph_reach_counters(void *h, uint64_t out[4])
     static_cast<HnswIndex *>(h)->graph_reach_counters(out);
     return 0;
 }
+// repair_reachability.  Exclusive, as hnsw_mi355x_remove: it edits lists.
+API int hnsw_mi355x_repair_reachability(void *h, int cands, int max_rounds, hnsw_mi355x_layer_repair *out, int cap)
+{
+    if (!h) return 0;
+    if (cap < 0 || (cap > 0 && !out)) { set_error("System.ArgumentNullException: hnsw_mi355x_repair_reachability"); return -1; }
+    if (cands < 1 || cands > 64 || max_rounds < 1 || max_rounds > 64) {
+        set_error("System.ArgumentOutOfRangeException: hnsw_mi355x_repair_reachability: cands = " + std::to_string(cands) + " and max_rounds = " +
+                  std::to_string(max_rounds) + " must both be in 1 .. 64");
+        return -1;
+    }
+    std::string err;
+    LOCK_INDEX(h);
+    const int n = static_cast<HnswIndex *>(h)->repair_reachability(cands, max_rounds, out, cap, err);
+    if (n < 0) set_error(err);
+    return n;
+}
+API int hnsw_mi355x_graph_repair_counters(void *h, uint64_t out[4])
+{
+    if (!h || !out) return -1;
+    LOCK_INDEX(h);
+    static_cast<HnswIndex *>(h)->graph_repair_counters(out);
+    return 0;
+}
 API int hnsw_mi355x_dim(void *h)
 {
     if (!h) return 0;

@@ -4,6 +4,7 @@
 #include "diag.h"
 
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <chrono>
 #include <cmath>
@@ -1958,6 +1959,96 @@ int HnswIndex::hop_counts(int layer, int *out, int cap, std::string &err)
     if (reach_chain("hop_counts", layer, nullptr, 0, nullptr, hops, err) < 0) return -1;
     if (hops != out) std::copy(tmp.begin(), tmp.begin() + std::max(cap, 0), out);
     return (int)n;
+}
+
+// repair_reachability: per layer from the top down, rounds of BFS -> candidates -> proposals on the device
+// (Device::graph_repair_round) and the apply step here.  U is walked ascending; u takes its first candidate whose code is not -1 and
+// whose list has not been changed in this round, so every proposal that is applied was computed from the list as it still stands.
+// The changed lists go into graph_ and, through patch_lists, into the mirror.  top + 1, or -1; the caller has checked the arguments.
+int HnswIndex::repair_reachability(int cands, int max_rounds, hnsw_mi355x_layer_repair *out, int cap, std::string &err)
+{
+    if (failed(err)) return -1;
+    if (graph_.count <= 0 || graph_.entry < 0) return 0;
+    if (!refresh_host_lists(err) || !sync_graph(err)) return -1;
+    const uint32_t *live_bits = nullptr;
+    long long nbits = 0;
+    std::vector<uint32_t> live;
+    (void)exact_candidates(live_bits, nbits, live);
+    if (dev_->graph_nodes() != graph_.length) { err = "repair_reachability: the graph mirror does not hold the index's nodes"; return -1; }
+    const int top = graph_.top_layer();
+    const size_t C = (size_t)cands;
+    bool patched = false;
+    auto dev_fail = [&]() -> int { // once a list has been patched the index is between two states: as for a failed Remove
+        err = get_dev_error();
+        if (!patched) return -1;
+        graph_dirty_ = true;
+        return fail("repair_reachability: " + err, err);
+    };
+    std::vector<std::array<int, 3>> picks; // a round's (u, v, code), in the order they are applied
+    std::vector<int> claimed((size_t)graph_.length, -1), recs; // claimed[v]: the last round (numbered over the whole call) that changed v's list
+    int stamp = 0, which = 0;
+    for (int layer = top; layer >= 0; --layer, which ^= 1) {
+        hnsw_mi355x_layer_repair r{layer, 0, 0, 0, 0, 0};
+        const int me = graph_.max_edges_at(layer), stride = (layer == 0 ? graph_.stride0 : graph_.strideU) + 1;
+        const int seed_mode = layer == top ? kRepairSeedEntry : kRepairSeedAbove;
+        bool hops_current = false; // slot `which` holds the BFS of the lists as they stand
+        for (int round = 0; round < max_rounds; ++round, ++stamp) {
+            GraphRepairRound rr;
+            if (!dev_->graph_repair_round(layer, live_bits, nbits, seed_mode, graph_.entry, nullptr, 0, which, cands, me, true, &rr)) return dev_fail();
+            if (round == 0) r.unreachable_before = rr.n_u;
+            r.unreachable_after = rr.n_u;
+            hops_current = true;
+            if (rr.n_u == 0) break;
+            ++r.rounds;
+            // the whole round is chosen and checked against the device's output before any list is written (a list changes at most
+            // once per round, so every count read here is the round's start)
+            picks.clear();
+            for (int i = 0; i < rr.n_u; ++i) {
+                const int u = rr.ids[i];
+                for (size_t j = 0; j < C; ++j) {
+                    const int v = rr.cands[(size_t)i * C + j], code = rr.codes[(size_t)i * C + j];
+                    if (v < 0 || code < 0) continue;
+                    if (u < 0 || u >= graph_.length || v >= graph_.length || graph_.removed[(size_t)v] || graph_.level[(size_t)v] < layer) {
+                        set_dev_error("repair_reachability: a proposal for an id outside the layer");
+                        return dev_fail();
+                    }
+                    if (claimed[(size_t)v] == stamp) continue;
+                    const int *l = graph_.list(v, layer);
+                    if (l[0] > me) continue; // (a snapshot written elsewhere may hold MaxEdges + 1 entries: such a list is left alone)
+                    if (code > l[0] || code >= me) {
+                        set_dev_error("repair_reachability: a proposal outside the candidate's list");
+                        return dev_fail();
+                    }
+                    claimed[(size_t)v] = stamp;
+                    picks.push_back({u, v, code});
+                    break;
+                }
+            }
+            const int nrecs = (int)picks.size();
+            recs.assign((size_t)nrecs * (size_t)stride, 0);
+            for (int k = 0; k < nrecs; ++k) {
+                const int u = picks[(size_t)k][0], v = picks[(size_t)k][1], code = picks[(size_t)k][2];
+                int *l = graph_.list(v, layer);
+                if (code == l[0]) l[0] += 1; else r.evicted += 1;
+                l[1 + code] = u;
+                r.linked += 1;
+                int *x = recs.data() + (size_t)k * (size_t)stride;
+                x[0] = v; x[1] = layer; x[2] = l[0];
+                for (int e = 0; e < l[0]; ++e) x[3 + e] = l[1 + e];
+                if (!patched) { patched = true; ++graph_epoch_; in_valid_ = false; } // (replicas clone again; the next Remove rebuilds the in-edges)
+            }
+            if (nrecs == 0) break; // nothing could be applied: the lists, and with them the hop array, are what they were
+            hops_current = false;
+            if (!dev_->graph_repair_patch(recs.data(), nrecs, stride)) return dev_fail();
+        }
+        if (!hops_current) { // the rounds ran out on a changed layer: one more BFS for the figure and for the seeds of the layer below
+            GraphRepairRound rr;
+            if (!dev_->graph_repair_round(layer, live_bits, nbits, seed_mode, graph_.entry, nullptr, 0, which, cands, me, false, &rr)) return dev_fail();
+            r.unreachable_after = rr.n_u;
+        }
+        if (layer < cap) out[layer] = r;
+    }
+    return top + 1;
 }
 
 // Host lock-step chains for the queries listed in `which` (nullptr: all `count`): MultiLayerJob.  out_*: [query][first + 1][k - 1].

@@ -86,6 +86,14 @@ public:
     int unreachable_ids(int layer, std::vector<int> &ids, std::string &err);
     int hop_counts(int layer, int *out, int cap, std::string &err);
     void graph_reach_counters(uint64_t out[4]) const { if (dev_) dev_->graph_reach_counters(out); else out[0] = out[1] = out[2] = out[3] = 0; }
+    // hnsw_mi355x_repair_reachability: links the members that reachability() reports as lost into the lists of their
+    // nearest reached members, layer by layer from the top, at most max_rounds rounds per layer.  Locking, sync_graph, the live set
+    // and "always on the device, on the primary context" are reachability's; the host lists are fetched first where the mirror is
+    // ahead of them.  The only call besides Add and Remove that edits lists: graph_ and the mirror are changed together, replicas
+    // clone again, the in-edge sets are rebuilt by the next Remove.  top + 1 with min(cap, top + 1) entries written; an empty index: 0;
+    // -1 on error, and once a list has been patched a device failure fails the index as a failed Remove does.
+    int repair_reachability(int cands, int max_rounds, hnsw_mi355x_layer_repair *out, int cap, std::string &err);
+    void graph_repair_counters(uint64_t out[4]) const { if (dev_) dev_->graph_repair_counters(out); else out[0] = out[1] = out[2] = out[3] = 0; }
     int knn_query_general(const float *queries, int count, int dim, int k, int layer, const uint32_t *allow_bits, long long nbits, int *out_ids,
                           float *out_dists, std::string &err);
     // hnsw_mi355x_knn_query_grouped: KnnQuery on `layer` with a group filter per query -- query i is answered from the

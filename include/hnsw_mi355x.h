@@ -389,6 +389,32 @@ int hnsw_mi355x_hop_counts(void *handle, int layer, int *out, int cap);
  * reached members, each expanded once), out[3] kernel launches.  0, or -1 for a NULL argument. */
 int hnsw_mi355x_graph_reach_counters(void *handle, uint64_t out[4]);
 
+/* Repair of reachability: links the items that hnsw_mi355x_unreachable_ids reports into the lists of their nearest
+ * reached members, on the device, so that the chain above reaches them.  OPT-IN, and the only call besides Add and Remove that edits
+ * neighbour lists: a graph it has changed is no longer an outcome of the reference's Add.  It stays a well-formed graph -- every list
+ * within MaxEdges(layer), no duplicate, no self entry, members only -- so its snapshots load everywhere.  It promises reachability,
+ * not recall: a reached item can still be missed by a greedy search, and an evicted entry is an edge some search may have used.
+ * Layers are processed from the entry point's top layer down; the seeds of a layer are the final reached set of the layer above.  On a
+ * layer, up to max_rounds times: (1) the chain's BFS; U = the members without a hop count, ascending; none: the layer is done.  (2) For
+ * each u of U the `cands` nearest REACHED members: the ids hnsw_mi355x_exact_knn_query returns for the stored row of u with k = cands
+ * and this round's reached set as allow-set.  (3) For each candidate v a slot code from v's list as it stands: count(v) if the list is
+ * below MaxEdges(layer) (an append); otherwise the evictable entry of largest (distance to v, slot), where entry s -> w is evictable
+ * iff w is a member with 0 <= hop[w] <= hop[v] and the distance is no NaN; -1 if there is none.  (4) U ascending: u takes its first
+ * candidate with a code whose list no other u has taken in this round; slot `code` of that list becomes u.  A round that applies
+ * nothing ends the layer.  An evicted entry v -> w has hop[w] <= hop[v], and every reached non-seed keeps an in-edge from a node one
+ * hop nearer, which is never evictable: what was reached before a round is reached after it, in no more hops. */
+typedef struct hnsw_mi355x_layer_repair {
+    int32_t layer_id, unreachable_before, linked, evicted, rounds, unreachable_after; /* members outside F_L at the first BFS; u linked; ... of them by an eviction; rounds that found members outside F_L; members outside F_L at the end */
+} hnsw_mi355x_layer_repair; /* 24 bytes */
+/* Returns top + 1 and writes min(cap, top + 1) entries (every layer is repaired whatever cap is).  cands and max_rounds: 1 .. 64 each
+ * (8 and 8 are the bindings' defaults), outside that -1 with a message.  0 for an empty index and for a NULL handle; -1 with a message
+ * on error; a device failure after the first list was changed fails the index, as for Remove.  Exclusive, on the primary context, on
+ * the device whatever hnsw_mi355x_set_device_traversal says. */
+int hnsw_mi355x_repair_reachability(void *handle, int cands, int max_rounds, hnsw_mi355x_layer_repair *out, int cap);
+/* Counters of the call above on the primary context since hnsw_mi355x_reset_stats: out[0] rounds that ran the proposal kernel, out[1]
+ * (u, candidate) pairs it judged, out[2] distances it measured (counted by the kernel), out[3] lists patched.  0, or -1 for a NULL argument. */
+int hnsw_mi355x_graph_repair_counters(void *handle, uint64_t out[4]);
+
 /* HNSWIndex.Serialize(filePath) / HNSWIndex.Deserialize(distFnc, filePath)
  * (src/HNSWIndex/HNSWIndex.cs:210-229): the reference's protobuf-net snapshot of
  * HNSWIndexSnapshot<float[],float> (HNSWIndexSnapshot.cs:12-16, GraphDataSnapshot.cs:13-35,
@@ -663,6 +689,15 @@ int hnswdev_graph_reach(void *ctx, int entry_point, const uint32_t *live_bits, l
                         int cap, uint32_t *out_reached_bits, int *out_hops);
 /* out[0 .. 3] as hnsw_mi355x_graph_reach_counters, of this context; zeroed by hnswdev_reset_stats. */
 int hnswdev_graph_reach_counters(void *ctx, uint64_t out[4]);
+/* Steps (1) - (3) of one round of hnsw_mi355x_repair_reachability on ONE layer of the committed graph mirror, from explicit seeds; the
+ * graph is read, not changed.  live_bits / nbits, the layer test and seed_bits / seed_nbits as hnswdev_graph_reach_layer.  max_edges:
+ * MaxEdges(layer), 1 .. what a list of the mirror holds.  cands: 1 .. 64.  *out_n = |U|; min(cap, |U|) rows are written: out_ids[i] the
+ * i-th unreached member ascending, out_cands[i * cands + j] its j-th nearest reached member (-1: padding), out_codes[i * cands + j] the
+ * slot code of that pair (0-based position in the candidate's list, -1: none).  Every node of the graph needs an uploaded row. */
+int hnswdev_graph_repair_propose(void *ctx, int layer, const uint32_t *live_bits, long long nbits, const uint32_t *seed_bits, long long seed_nbits, int cands,
+                                 int max_edges, int *out_n, int *out_ids, int *out_cands, int *out_codes, int cap);
+/* out[0 .. 3] as hnsw_mi355x_graph_repair_counters, of this context (out[3]: lists patched through it); zeroed by hnswdev_reset_stats. */
+int hnswdev_graph_repair_counters(void *ctx, uint64_t out[4]);
 int hnswdev_get_stats(void *ctx, hnswdev_stats *out);
 int hnswdev_reset_stats(void *ctx);
 /* Last error, process-wide (creation failures have no context yet) ... */
