@@ -72,6 +72,21 @@ constexpr int metric_by_name(const char *name)
 // the calling thread is currently inside (ErrorScope), if any.
 void set_dev_error(const std::string &msg);
 std::string get_dev_error();
+
+// Limits of the flat scan (dk_exact.h) that the host checks as well: here, because hnsw_index.cpp is a host-only unit.
+constexpr int kExactMaxK = 1024;
+constexpr int kExactMaxGroups = 65536;   // groups of a grouped call: exact_group_offsets_kernel is one block that walks the counts
+// The argument rules every grouped call shares -- n_groups in 1 .. kExactMaxGroups, every query_group value inside 0 .. n_groups - 1 --
+// and the one wording of a breach: "" when the arguments are good, else "<who>: ..." (the index adds its exception prefix in front).
+inline std::string group_args_error(const char *who, const int *query_group, int nq, int n_groups)
+{
+    if (n_groups < 1 || n_groups > kExactMaxGroups)
+        return std::string(who) + ": n_groups = " + std::to_string(n_groups) + " is outside 1 .. " + std::to_string(kExactMaxGroups);
+    for (int i = 0; i < nq; ++i)
+        if (query_group[i] < 0 || query_group[i] >= n_groups)
+            return std::string(who) + ": query_group[" + std::to_string(i) + "] = " + std::to_string(query_group[i]) + " is outside 0 .. n_groups - 1 = " + std::to_string(n_groups - 1);
+    return std::string();
+}
 class Device;
 struct VisitedScratch;   // device_backend.hip: the visited-set memory of a traversal launch
 struct TraversalLaunch;  // ... which traversal kernel form a launch runs, on how many waves, with which flags

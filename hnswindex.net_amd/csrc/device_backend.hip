@@ -1909,22 +1909,12 @@ bool Device::search_filtered(int nq, int entry, int entry_layer, int k, int k_ou
     return true;
 }
 
-// The argument rules the grouped calls share (exact_knn_grouped words them the same way): n_groups in 1 .. kExactMaxGroups, every
-// query_group value inside 0 .. n_groups - 1.
+// The argument rules the grouped calls share (group_args_error, device_backend.h), filed as the context's error.
 static bool group_args_ok(const char *who, const int *query_group, int nq, int n_groups)
 {
-    if (n_groups < 1 || n_groups > kExactMaxGroups) {
-        set_dev_error(std::string(who) + ": n_groups = " + std::to_string(n_groups) + " is outside 1 .. " + std::to_string(kExactMaxGroups));
-        return false;
-    }
-    for (int i = 0; i < nq; ++i) {
-        const int g = query_group[i];
-        if (g < 0 || g >= n_groups) {
-            set_dev_error(std::string(who) + ": query_group[" + std::to_string(i) + "] = " + std::to_string(g) + " is outside 0 .. n_groups - 1 = " + std::to_string(n_groups - 1));
-            return false;
-        }
-    }
-    return true;
+    const std::string why = group_args_error(who, query_group, nq, n_groups);
+    if (!why.empty()) set_dev_error(why);
+    return why.empty();
 }
 
 // KnnQuery with a group filter per query (graph_search_grouped_kernel): search_filtered's launch with the labels in
@@ -2760,19 +2750,9 @@ bool Device::exact_knn_grouped(const float *queries, int nq, long long n_rows, i
     if (!row_group || n_row_group < 0) { set_dev_error("exact_knn_grouped: row_group must not be NULL and n_row_group must be >= 0"); return false; }
     if (!query_group) { set_dev_error("exact_knn_grouped: query_group must not be NULL"); return false; }
     if (k > kExactMaxK) { set_dev_error("exact_knn_grouped: k = " + std::to_string(k) + " is above the limit of " + std::to_string(kExactMaxK)); return false; }
-    if (n_groups < 1 || n_groups > kExactMaxGroups) {
-        set_dev_error("exact_knn_grouped: n_groups = " + std::to_string(n_groups) + " is outside 1 .. " + std::to_string(kExactMaxGroups));
-        return false;
-    }
+    if (!group_args_ok("exact_knn_grouped", query_group, nq, n_groups)) return false;
     std::vector<int> gq((size_t)n_groups, 0); // queries per group
-    for (int i = 0; i < nq; ++i) {
-        const int g = query_group[i];
-        if (g < 0 || g >= n_groups) {
-            set_dev_error("exact_knn_grouped: query_group[" + std::to_string(i) + "] = " + std::to_string(g) + " is outside 0 .. n_groups - 1 = " + std::to_string(n_groups - 1));
-            return false;
-        }
-        gq[(size_t)g] += 1;
-    }
+    for (int i = 0; i < nq; ++i) gq[(size_t)query_group[i]] += 1;
     // ids that exist and have a group: a row beyond what was uploaded is never dereferenced, whatever n_rows and n_row_group say
     const long long n = std::min({n_rows, n_rows_hw_, n_row_group});
     if (n <= 0) { pad_results(out_ids, out_d, (size_t)nq * (size_t)k); return true; }

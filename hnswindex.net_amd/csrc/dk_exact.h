@@ -22,17 +22,17 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "device_backend.h" // kExactMaxK, kExactMaxGroups: the limits the host checks as well
+
 namespace hnsw {
 
 constexpr int kExactThreads = 256;   // 4 waves = 32 groups of 8 lanes
 constexpr int kExactRQ = 4;          // queries of a group's register tile (= waves of a block: wave w merges query w of the tile)
 constexpr int kExactRR = 4;          // rows of a group's register tile
 constexpr int kExactIterRows = (kExactThreads / 8) * kExactRR; // rows a block measures per step: 128
-constexpr int kExactMaxK = 1024;
 constexpr int kExactMaxQTile = 32;
 constexpr int kExactCompactWords = 256; // bitset words per block of exact_compact_kernel (one per thread)
 constexpr int kExactRangeSortMax = 4096; // keys exact_range_sort_kernel orders in LDS (32 KB); longer lists are ordered on the host
-constexpr int kExactMaxGroups = 65536;   // groups of exact_knn_grouped: exact_group_offsets_kernel is one block that walks the counts
 constexpr int kExactMaxChunks = 4096;    // chunks per query (the merge walks them)
 
 struct ExactScanArgs {

@@ -663,6 +663,20 @@ void parallel_for(int n, int threads, F fn)
     for (auto &t : th) t.join();
 }
 
+// body(i) for i = 0 .. n - 1, each on a thread of its own, all joined: how the device contexts work side by side.  false when a
+// body returned false, with the error of the first such i: what the device left on that thread, or `fallback`.
+template <class F>
+bool fan_out(int n, const char *fallback, std::string &err, F body)
+{
+    std::vector<std::string> errs((size_t)n);
+    std::vector<std::thread> th;
+    for (int i = 0; i < n; ++i)
+        th.emplace_back([&, i] { if (!body(i)) errs[(size_t)i] = get_dev_error().empty() ? fallback : get_dev_error(); });
+    for (auto &t : th) t.join();
+    for (const std::string &e : errs) if (!e.empty()) { err = e; return false; }
+    return true;
+}
+
 // Growth rule of the snapshot schedule: a batch never exceeds 1/4 of the linked graph while that is below
 // 65 536 nodes, 1/16 of it afterwards.  Measured on 1M x 128 (tools/ramp_study.py, three data seeds, 4 000
 // queries each; profiles/r2_ramp_study.json): against 1/16 throughout, the build takes 1.24 s instead of
@@ -1559,21 +1573,50 @@ int HnswIndex::knn_query_lockstep(const int *which, int count, int k, int *out_i
     return 0;
 }
 
-// Graph-resident traversal: one kernel launch runs every query's FindEntryPointQuery +
-// SearchLayerQuery + stable OrderBy/Take(k) (HNSWIndex.cs:116-123).
-int HnswIndex::knn_query_device(const float *, int count, int k, int *out_ids, float *out_dists, std::string &err)
+// The one way every KnnQuery form over the resident query set is answered.  on_device(ctx, cnt, lo, flag) runs the
+// form's traversal launch on one context -- cnt resident queries of its own, rows lo .. of the caller's arrays, flag[0 .. cnt) != 0
+// where it hands a query back -- and on_host(which, n) answers the n queries listed in `which` (nullptr: all) by the exact lock-step
+// traversal, naming them by their global index on the primary.
+//   * The traversal does not run on the device: a sharded set is gathered to the primary, which then holds the whole set and nothing
+//     else is current, so sharded_resident_ is cleared; on_host answers everything.
+//   * Else one launch on the primary, or with a sharded set one per context side by side on its replica: each query's traversal is
+//     what the single-context launch runs, so the answer is bit for bit the same.  A shard without queries makes no call.
+//   * Hand-backs are answered by on_host, after a sharded set has been gathered to the primary.  sharded_resident_ STAYS set: the
+//     gather (Device::adopt_queries) writes context g's rows at shard_lo_[g] .. of the primary's buffer and raises its row count to
+//     `count`; the primary's own shard is rows 0 .. shard_lo_[1] of that buffer before and after (shard_lo_[0] == 0), the buffer is
+//     grown with what is resident kept, and no other context is touched.  So every context still holds its shard at rows 0 .. of its
+//     own buffer, which is all a sharded launch reads, and a following knn_query_resident stays sharded.
+// `fallback` is the error of a context that failed without leaving one.  0 or -1.
+template <class OnDevice, class OnHost>
+int HnswIndex::answer_resident(int count, int ef, OnDevice on_device, OnHost on_host, const char *fallback, std::string &err)
 {
+    if (!(p_.device_traversal && dev_->traversal_fits(ef, false, p_.max_edges))) {
+        if (sharded_resident_) {
+            if (!gather_queries_to_primary(count, err)) return -1;
+            sharded_resident_ = false;
+        }
+        return on_host(nullptr, count);
+    }
     if (!sync_graph(err)) return -1;
-    const int ef = std::max(p_.min_nn, k);
-    const int ep = graph_.entry, top = graph_.top_layer();
+    if (sharded_resident_ && !ensure_replicas(true, err)) return -1;
     std::vector<int> flag((size_t)count);
-    { Tick t(g_pt.query_dev);
-    if (!dev_->search_queries(count, ep, top, ef, k, out_ids, out_dists, flag.data())) { err = get_dev_error(); return -1; } }
+    bool ok;
+    {
+        Tick t(g_pt.query_dev);
+        if (sharded_resident_)
+            ok = fan_out(p_.devices, fallback, err, [&](int g) {
+                const long long lo = shard_lo_[(size_t)g];
+                const int cnt = (int)(shard_lo_[(size_t)g + 1] - lo);
+                return cnt <= 0 || on_device(context(g), cnt, lo, flag.data() + lo);
+            });
+        else if (!(ok = on_device(dev_.get(), count, 0, flag.data()))) err = get_dev_error();
+    }
+    if (!ok) return -1;
     Tick t_post(g_pt.post);
     const std::vector<int> redo = flagged_jobs(flag);
-    if (!redo.empty()) // candidate heap outgrew LDS: exact re-run on the lock-step path
-        return knn_query_lockstep(redo.data(), (int)redo.size(), k, out_ids, out_dists, err);
-    return 0;
+    if (redo.empty()) return 0;
+    if (sharded_resident_ && !gather_queries_to_primary(count, err)) return -1;
+    return on_host(redo.data(), (int)redo.size()); // (e.g. a candidate heap outgrew LDS)
 }
 
 int HnswIndex::knn_query(const float *queries, int count, int dim, int k, int *out_ids, float *out_dists, std::string &err)
@@ -1606,6 +1649,7 @@ bool HnswIndex::layer_ok(int layer, std::string &err) const
 // KnnQuery(query, k, filterFnc, layer) (HNSWIndex.cs:107-124) in every form but the plain one (no filter at layer 0: knn_query):
 // allow_bits == nullptr means no filter.  With a filter the device runs graph_search_filtered_kernel on `layer`; without one the
 // jobs of graph_search_kernel carry search_layer = layer (the sorted-list forms with their tie rule, as at layer 0).
+// Device or host, one context or several: answer_resident.
 int HnswIndex::knn_query_general(const float *queries, int count, int dim, int k, int layer, const uint32_t *allow_bits, long long nbits, int *out_ids,
                                  float *out_dists, std::string &err)
 {
@@ -1622,80 +1666,45 @@ int HnswIndex::knn_query_general(const float *queries, int count, int dim, int k
     }
     if (set_resident_queries(queries, count, dim, err) < 0) return -1;
     const int ef = std::max(p_.min_nn, k); // HNSWIndex.cs:115
-    if (!(p_.device_traversal && dev_->traversal_fits(ef, false, p_.max_edges))) {
-        if (sharded_resident_) { // the host traversal runs on the primary alone: it needs the whole set there (as knn_query_resident)
-            if (!gather_queries_to_primary(count, err)) return -1;
-            sharded_resident_ = false;
-        }
-        return knn_query_lockstep(nullptr, count, k, out_ids, out_dists, err, allow, layer);
-    }
-    if (!sync_graph(err)) return -1;
     const int ep = graph_.entry, top = graph_.top_layer();
-    std::vector<int> flag((size_t)count);
-    // one context's share: cnt resident queries of its own, rows lo.. of the caller's arrays
-    const auto search = [&](Device *ctx, int cnt, long long lo) -> bool {
-        if (filtered) return ctx->search_filtered(cnt, ep, top, ef, k, allow_bits, nbits, out_ids + (size_t)lo * k, out_dists + (size_t)lo * k, flag.data() + lo, layer);
-        std::vector<SearchJob> jobs((size_t)cnt);
-        for (int i = 0; i < cnt; ++i) jobs[(size_t)i] = SearchJob{i, ep, top, layer, -1, 0};
-        return ctx->search_batch(jobs.data(), cnt, ef, k, out_ids + (size_t)lo * k, out_dists + (size_t)lo * k, flag.data() + lo);
-    };
-    if (sharded_resident_) { // every context answers its shard with the bitset uploaded to it
-        if (!ensure_replicas(true, err)) return -1;
-        const int n = p_.devices;
-        std::vector<std::string> errs((size_t)n);
-        std::vector<std::thread> th;
-        for (int g = 0; g < n; ++g)
-            th.emplace_back([&, g] {
-                const long long lo = shard_lo_[(size_t)g], hi = shard_lo_[(size_t)g + 1];
-                const int cnt = (int)(hi - lo);
-                if (cnt > 0 && !search(context(g), cnt, lo))
-                    errs[(size_t)g] = get_dev_error().empty() ? "search_filtered failed" : get_dev_error();
-            });
-        for (auto &t : th) t.join();
-        for (const std::string &e : errs) if (!e.empty()) { err = e; return -1; }
-    } else if (!search(dev_.get(), count, 0)) { err = get_dev_error(); return -1; }
-    const std::vector<int> redo = flagged_jobs(flag);
-    if (redo.empty()) return 0;
-    if (sharded_resident_) { // the exact host traversal names queries by their global index on the primary
-        if (!gather_queries_to_primary(count, err)) return -1;
-        sharded_resident_ = false;
-    }
-    return knn_query_lockstep(redo.data(), (int)redo.size(), k, out_ids, out_dists, err, allow, layer);
+    return answer_resident(count, ef,
+        [&](Device *ctx, int cnt, long long lo, int *flag) -> bool { // with a filter, the bitset is uploaded to every context
+            if (filtered) return ctx->search_filtered(cnt, ep, top, ef, k, allow_bits, nbits, out_ids + (size_t)lo * k, out_dists + (size_t)lo * k, flag, layer);
+            std::vector<SearchJob> jobs((size_t)cnt);
+            for (int i = 0; i < cnt; ++i) jobs[(size_t)i] = SearchJob{i, ep, top, layer, -1, 0};
+            return ctx->search_batch(jobs.data(), cnt, ef, k, out_ids + (size_t)lo * k, out_dists + (size_t)lo * k, flag);
+        },
+        [&](const int *which, int n) { return knn_query_lockstep(which, n, k, out_ids, out_dists, err, allow, layer); },
+        "search_filtered failed", err);
+}
+
+// The grouped calls' argument rules (group_args_error, device_backend.h) as the ABI reports a breach: `who` is the ABI call.
+static bool group_args_ok(const char *who, const int *query_group, int count, int n_groups, std::string &err)
+{
+    const std::string why = group_args_error(who, query_group, count, n_groups);
+    if (!why.empty()) err = "System.ArgumentOutOfRangeException: " + why;
+    return why.empty();
 }
 
 // KnnQuery with a group filter per query: knn_query_general's filtered call for every group at once.  The labels go
-// to the device as they are; once slots are vacant a copy does, with the vacant slots in no group (as exact_knn_query_grouped).
+// to the device as they are; once slots are vacant a copy does, with the vacant slots in no group (live_labels).  Device or host,
+// one context or several: answer_resident, with the per-group lock-step calls below as its host way.
 int HnswIndex::knn_query_grouped(const float *queries, int count, int dim, int k, int layer, const int *row_group, long long n_row_group, const int *query_group,
                                  int n_groups, int *out_ids, float *out_dists, std::string &err)
 {
     if (count <= 0) return 0;
     if (failed(err)) return -1;
     const char *who = "hnsw_mi355x_knn_query_grouped";
-    if (n_groups < 1 || n_groups > 65536) {
-        err = std::string("System.ArgumentOutOfRangeException: ") + who + ": n_groups = " + std::to_string(n_groups) + " is outside 1 .. 65536";
-        return -1;
-    }
-    for (int i = 0; i < count; ++i)
-        if (query_group[i] < 0 || query_group[i] >= n_groups) {
-            err = std::string("System.ArgumentOutOfRangeException: ") + who + ": query_group[" + std::to_string(i) + "] = " + std::to_string(query_group[i]) +
-                  " is outside 0 .. n_groups - 1 = " + std::to_string(n_groups - 1);
-            return -1;
-        }
+    if (!group_args_ok(who, query_group, count, n_groups, err)) return -1;
     const bool empty = k < 1 || graph_.entry < 0 || graph_.count <= 0;
     if (!empty && !layer_ok(layer, err)) { err = "System.IndexOutOfRangeException: " + std::string(who) + ": " + err; return -1; }
     if (empty) { // HNSWIndex.cs:109: empty result lists, padded by the export
         pad_results(out_ids, out_dists, (size_t)count * (size_t)std::max(k, 0));
         return 0;
     }
-    const long long n_lab = std::min<long long>(n_row_group, graph_.length);
     std::vector<int> live;
-    if (graph_.count != graph_.length) { // vacant slots: in no group
-        live.assign(row_group, row_group + n_lab);
-        for (long long id = 0; id < n_lab; ++id)
-            if (graph_.removed[(size_t)id]) live[(size_t)id] = -1;
-        live.push_back(-1); // (never NULL)
-        row_group = live.data();
-    }
+    (void)live_labels(row_group, n_row_group, live);
+    const long long n_lab = std::min<long long>(n_row_group, graph_.length); // only the labels of graph ids count
     std::vector<char> has_id((size_t)n_groups, 0); // groups that hold an id of the graph
     for (long long id = 0; id < n_lab; ++id)
         if (row_group[id] >= 0 && row_group[id] < n_groups) has_id[(size_t)row_group[id]] = 1;
@@ -1727,43 +1736,12 @@ int HnswIndex::knn_query_grouped(const float *queries, int count, int dim, int k
         return 0;
     };
     const int ef = std::max(p_.min_nn, k); // HNSWIndex.cs:115
-    if (!(p_.device_traversal && dev_->traversal_fits(ef, false, p_.max_edges))) {
-        if (sharded_resident_) { // the host traversal runs on the primary alone: it needs the whole set there (as knn_query_resident)
-            if (!gather_queries_to_primary(count, err)) return -1;
-            sharded_resident_ = false;
-        }
-        return lockstep(nullptr, count);
-    }
-    if (!sync_graph(err)) return -1;
     const int ep = graph_.entry, top = graph_.top_layer();
-    std::vector<int> flag((size_t)count);
-    // one context's share: cnt resident queries of its own, rows lo.. of the caller's arrays and of query_group
-    const auto search = [&](Device *ctx, int cnt, long long lo) -> bool {
-        return ctx->search_grouped(cnt, ep, top, ef, k, row_group, n_lab, query_group + lo, n_groups, out_ids + (size_t)lo * k, out_dists + (size_t)lo * k,
-                                   flag.data() + lo, layer);
-    };
-    if (sharded_resident_) { // every context answers its shard with the labels uploaded to it
-        if (!ensure_replicas(true, err)) return -1;
-        const int n = p_.devices;
-        std::vector<std::string> errs((size_t)n);
-        std::vector<std::thread> th;
-        for (int g = 0; g < n; ++g)
-            th.emplace_back([&, g] {
-                const long long lo = shard_lo_[(size_t)g], hi = shard_lo_[(size_t)g + 1];
-                const int cnt = (int)(hi - lo);
-                if (cnt > 0 && !search(context(g), cnt, lo))
-                    errs[(size_t)g] = get_dev_error().empty() ? "search_grouped failed" : get_dev_error();
-            });
-        for (auto &t : th) t.join();
-        for (const std::string &e : errs) if (!e.empty()) { err = e; return -1; }
-    } else if (!search(dev_.get(), count, 0)) { err = get_dev_error(); return -1; }
-    const std::vector<int> redo = flagged_jobs(flag);
-    if (redo.empty()) return 0;
-    if (sharded_resident_) { // the exact host traversal names queries by their global index on the primary
-        if (!gather_queries_to_primary(count, err)) return -1;
-        sharded_resident_ = false;
-    }
-    return lockstep(redo.data(), (int)redo.size());
+    return answer_resident(count, ef,
+        [&](Device *ctx, int cnt, long long lo, int *flag) { // the labels are uploaded to every context; lo .. of query_group too
+            return ctx->search_grouped(cnt, ep, top, ef, k, row_group, n_lab, query_group + lo, n_groups, out_ids + (size_t)lo * k, out_dists + (size_t)lo * k, flag, layer);
+        },
+        lockstep, "search_grouped failed", err);
 }
 
 void HnswIndex::knn_grouped_info(uint64_t out[4]) const
@@ -1791,6 +1769,22 @@ long long HnswIndex::exact_candidates(const uint32_t *&allow_bits, long long &nb
     return length;
 }
 
+// exact_candidates' counterpart for the labels of a grouped call: while no slot is vacant they go to the device as the caller gave
+// them; once slots are vacant row_group / n_row_group are replaced by a copy (in `live`) of the labels of ids below the graph's length,
+// with the vacant slots in no group.  The copy ends with a -1 beyond n_row_group, so that it is never NULL.  true: a copy was made.
+bool HnswIndex::live_labels(const int *&row_group, long long &n_row_group, std::vector<int> &live) const
+{
+    if (graph_.count == graph_.length) return false;
+    const long long n = std::min<long long>(n_row_group, graph_.length);
+    live.assign(row_group, row_group + n);
+    for (long long id = 0; id < n; ++id)
+        if (graph_.removed[(size_t)id]) live[(size_t)id] = -1;
+    live.push_back(-1);
+    row_group = live.data();
+    n_row_group = n;
+    return true;
+}
+
 // The flat scan: every live, allowed row measured against every query.  The candidates are the live ids: while
 // nothing has been removed they are 0 .. length - 1 and the caller's bitset goes to the device as it is (none: the scan addresses
 // rows directly); once slots are vacant the live set is ANDed into it here.
@@ -1799,7 +1793,7 @@ int HnswIndex::exact_knn_query(const float *queries, int count, int dim, int k, 
 {
     if (count <= 0) return 0;
     if (failed(err)) return -1;
-    if (k > 1024) { err = "System.ArgumentOutOfRangeException: hnsw_mi355x_exact_knn_query: k = " + std::to_string(k) + " is above the limit of 1024"; return -1; }
+    if (k > kExactMaxK) { err = "System.ArgumentOutOfRangeException: hnsw_mi355x_exact_knn_query: k = " + std::to_string(k) + " is above the limit of " + std::to_string(kExactMaxK); return -1; }
     if (k < 1 || graph_.count <= 0) {
         pad_results(out_ids, out_dists, (size_t)count * (size_t)std::max(k, 0));
         return 0;
@@ -1812,25 +1806,15 @@ int HnswIndex::exact_knn_query(const float *queries, int count, int dim, int k, 
     return 0;
 }
 
-// The flat scan with a candidate group per query.  The counterpart of exact_candidates: while nothing has been
-// removed the caller's row_group goes to the device as it is; once slots are vacant a copy does, with the vacant slots in no group.
+// The flat scan with a candidate group per query.  The labels go to the device as live_labels leaves them.
 int HnswIndex::exact_knn_query_grouped(const float *queries, int count, int dim, int k, const int *row_group, long long n_row_group, const int *query_group,
                                        int n_groups, int *out_ids, float *out_dists, std::string &err)
 {
     if (count <= 0) return 0;
     if (failed(err)) return -1;
     const char *who = "hnsw_mi355x_exact_knn_query_grouped";
-    if (k > 1024) { err = std::string("System.ArgumentOutOfRangeException: ") + who + ": k = " + std::to_string(k) + " is above the limit of 1024"; return -1; }
-    if (n_groups < 1 || n_groups > 65536) {
-        err = std::string("System.ArgumentOutOfRangeException: ") + who + ": n_groups = " + std::to_string(n_groups) + " is outside 1 .. 65536";
-        return -1;
-    }
-    for (int i = 0; i < count; ++i)
-        if (query_group[i] < 0 || query_group[i] >= n_groups) {
-            err = std::string("System.ArgumentOutOfRangeException: ") + who + ": query_group[" + std::to_string(i) + "] = " + std::to_string(query_group[i]) +
-                  " is outside 0 .. n_groups - 1 = " + std::to_string(n_groups - 1);
-            return -1;
-        }
+    if (k > kExactMaxK) { err = std::string("System.ArgumentOutOfRangeException: ") + who + ": k = " + std::to_string(k) + " is above the limit of " + std::to_string(kExactMaxK); return -1; }
+    if (!group_args_ok(who, query_group, count, n_groups, err)) return -1;
     if (k < 1 || graph_.count <= 0) {
         pad_results(out_ids, out_dists, (size_t)count * (size_t)std::max(k, 0));
         return 0;
@@ -1838,15 +1822,7 @@ int HnswIndex::exact_knn_query_grouped(const float *queries, int count, int dim,
     if (!ensure_dim(dim, err)) return -1;
     const long long length = graph_.length;
     std::vector<int> live;
-    if (graph_.count != graph_.length) { // vacant slots: in no group
-        const long long n = std::min(n_row_group, length);
-        live.assign(row_group, row_group + n);
-        for (long long id = 0; id < n; ++id)
-            if (graph_.removed[(size_t)id]) live[(size_t)id] = -1;
-        row_group = live.data(); // (never NULL: the vector of an empty copy still hands the device no row)
-        n_row_group = n;
-        if (n == 0) { pad_results(out_ids, out_dists, (size_t)count * (size_t)k); return 0; }
-    }
+    if (live_labels(row_group, n_row_group, live) && n_row_group == 0) { pad_results(out_ids, out_dists, (size_t)count * (size_t)k); return 0; } // vacant slots and no label: no candidate
     // (the scan stages its queries in a buffer of its own: the resident set, sharded or not, stays what it was)
     if (!dev_->exact_knn_grouped(queries, count, length, k, row_group, n_row_group, query_group, n_groups, out_ids, out_dists)) { err = get_dev_error(); return -1; }
     return 0;
@@ -2145,16 +2121,12 @@ bool HnswIndex::ensure_replicas(bool clone, std::string &err)
     std::vector<int> stale;
     for (int g = 1; g < n; ++g) if (replica_epoch_[(size_t)g - 1] != graph_epoch_) stale.push_back(g);
     if (stale.empty()) return true;
-    std::vector<std::string> errs(stale.size());
-    std::vector<std::thread> th;
-    for (size_t i = 0; i < stale.size(); ++i)
-        th.emplace_back([&, i] { if (!replicas_[(size_t)stale[i] - 1]->clone_from(dev_.get(), dev_pool_len_)) errs[i] = get_dev_error().empty() ? "replica copy failed" : get_dev_error(); });
-    for (auto &t : th) t.join();
-    for (size_t i = 0; i < stale.size(); ++i) {
-        if (!errs[i].empty()) { err = errs[i]; return false; }
-        replica_epoch_[(size_t)stale[i] - 1] = graph_epoch_;
-    }
-    return true;
+    return fan_out((int)stale.size(), "replica copy failed", err, [&](int i) { // (a replica that has copied is current, whatever the others did)
+        const size_t r = (size_t)stale[(size_t)i] - 1;
+        if (!replicas_[r]->clone_from(dev_.get(), dev_pool_len_)) return false;
+        replica_epoch_[r] = graph_epoch_;
+        return true;
+    });
 }
 
 // a call of at least kStreamMin queries starts on its first kStreamHead rows; see Device::set_queries_streamed
@@ -2244,18 +2216,13 @@ int HnswIndex::set_resident_queries(const float *queries, int count, int dim, st
         if (!ensure_replicas(false, err)) return -1;
         shard_lo_.assign((size_t)n + 1, 0);
         for (int g = 0; g <= n; ++g) shard_lo_[(size_t)g] = (long long)count * g / n;
-        std::vector<std::string> errs((size_t)n);
-        std::vector<std::thread> th;
-        for (int g = 0; g < n; ++g)
-            th.emplace_back([&, g] {
-                const long long lo = shard_lo_[(size_t)g], hi = shard_lo_[(size_t)g + 1];
-                const float *qs = queries + (size_t)lo * (size_t)dim;
-                const int cnt = (int)(hi - lo);
-                if (!(streamed && cnt >= kStreamMin ? context(g)->set_queries_streamed(qs, cnt, kStreamHead) : context(g)->set_queries(qs, cnt)))
-                    errs[(size_t)g] = get_dev_error().empty() ? "set_queries failed" : get_dev_error();
-            });
-        for (auto &t2 : th) t2.join();
-        for (const std::string &e : errs) if (!e.empty()) { err = e; resident_queries_ = 0; return -1; }
+        const bool ok = fan_out(n, "set_queries failed", err, [&](int g) {
+            const long long lo = shard_lo_[(size_t)g], hi = shard_lo_[(size_t)g + 1];
+            const float *qs = queries + (size_t)lo * (size_t)dim;
+            const int cnt = (int)(hi - lo);
+            return streamed && cnt >= kStreamMin ? context(g)->set_queries_streamed(qs, cnt, kStreamHead) : context(g)->set_queries(qs, cnt);
+        });
+        if (!ok) { resident_queries_ = 0; return -1; }
         sharded_resident_ = true;
         resident_queries_ = count;
         return 0;
@@ -2274,44 +2241,13 @@ int HnswIndex::knn_query_resident(int k, int *out_ids, float *out_dists, std::st
         pad_results(out_ids, out_dists, (size_t)count * (size_t)std::max(k, 0));
         return 0;
     }
-    const bool fits = p_.device_traversal && dev_->traversal_fits(std::max(p_.min_nn, k), false, p_.max_edges);
-    if (sharded_resident_) {
-        if (fits) return knn_query_sharded(k, out_ids, out_dists, err);
-        // the host traversal runs on the primary alone: it needs the whole set there
-        if (!gather_queries_to_primary(count, err)) return -1;
-        sharded_resident_ = false;
-    }
-    if (fits) return knn_query_device(nullptr, count, k, out_ids, out_dists, err);
-    return knn_query_lockstep(nullptr, count, k, out_ids, out_dists, err);
-}
-
-// One traversal launch per context, side by side: context g answers its shard of the resident queries on its replica
-// and writes rows [lo_g, hi_g) of the caller's arrays.  Each query's traversal is what the single-device path runs, so
-// the answer is bit for bit the same.  Whatever a kernel hands back is answered by the exact host traversal on the primary.
-int HnswIndex::knn_query_sharded(int k, int *out_ids, float *out_dists, std::string &err)
-{
-    if (!sync_graph(err)) return -1;
-    if (!ensure_replicas(true, err)) return -1;
-    const int n = p_.devices, count = resident_queries_;
+    // FindEntryPointQuery + SearchLayerQuery + the stable OrderBy / Take(k) of every query (HNSWIndex.cs:116-123) in one launch per context
     const int ef = std::max(p_.min_nn, k);
     const int ep = graph_.entry, top = graph_.top_layer();
-    std::vector<int> flag((size_t)count);
-    std::vector<std::string> errs((size_t)n);
-    std::vector<std::thread> th;
-    { Tick t(g_pt.query_dev);
-    for (int g = 0; g < n; ++g)
-        th.emplace_back([&, g] {
-            const long long lo = shard_lo_[(size_t)g], hi = shard_lo_[(size_t)g + 1];
-            const int cnt = (int)(hi - lo);
-            if (cnt > 0 && !context(g)->search_queries(cnt, ep, top, ef, k, out_ids + (size_t)lo * k, out_dists + (size_t)lo * k, flag.data() + lo))
-                errs[(size_t)g] = get_dev_error().empty() ? "search_batch failed" : get_dev_error();
-        });
-    for (auto &t2 : th) t2.join(); }
-    for (const std::string &e : errs) if (!e.empty()) { err = e; return -1; }
-    const std::vector<int> redo = flagged_jobs(flag);
-    if (redo.empty()) return 0;
-    if (!gather_queries_to_primary(count, err)) return -1; // the exact host traversal names queries by their global index on the primary
-    return knn_query_lockstep(redo.data(), (int)redo.size(), k, out_ids, out_dists, err);
+    return answer_resident(count, ef,
+        [&](Device *ctx, int cnt, long long lo, int *flag) { return ctx->search_queries(cnt, ep, top, ef, k, out_ids + (size_t)lo * k, out_dists + (size_t)lo * k, flag); },
+        [&](const int *which, int n) { return knn_query_lockstep(which, n, k, out_ids, out_dists, err); },
+        "search_batch failed", err);
 }
 
 // Host lock-step range search for the queries listed in `which` (nullptr: all `count` queries).

@@ -199,6 +199,7 @@ private:
     bool ensure_capacity(long long need, std::string &err);
     bool insert_batch(const std::vector<int> &bid, std::string &err);
     long long exact_candidates(const uint32_t *&allow_bits, long long &nbits, std::vector<uint32_t> &live) const;
+    bool live_labels(const int *&row_group, long long &n_row_group, std::vector<int> &live) const;
     int reach_chain(const char *who, int min_layer, hnsw_mi355x_layer_reach *out, int cap, uint32_t *bits, int *hops, std::string &err);
     bool insert_exact_window(const std::vector<int> &fresh, int &p, int W, bool background, std::string &err);
     // Selected neighbour ids per (batch item, layer).  Device results are read in place from the
@@ -235,10 +236,11 @@ private:
     bool sharded_resident_ = false;
     Device *context(int g) { return g == 0 ? dev_.get() : replicas_[(size_t)g - 1].get(); }
     bool ensure_replicas(bool clone, std::string &err);
-    int knn_query_sharded(int k, int *out_ids, float *out_dists, std::string &err);
     bool gather_queries_to_primary(int count, std::string &err);
     bool refresh_host_lists(std::string &err);
-    int knn_query_device(const float *queries, int count, int k, int *out_ids, float *out_dists, std::string &err);
+    // every KnnQuery form over the resident set: on the device, one launch per context, or on the host, hand-backs included (hnsw_index.cpp)
+    template <class OnDevice, class OnHost>
+    int answer_resident(int count, int ef, OnDevice on_device, OnHost on_host, const char *fallback, std::string &err);
     int knn_query_lockstep(const int *which, int count, int k, int *out_ids, float *out_dists, std::string &err, AllowBits allow = AllowBits{},
                            int layer = 0);
     int range_query_lockstep(const int *which, int count, float range, std::vector<std::vector<NodeDist>> &out, std::string &err,

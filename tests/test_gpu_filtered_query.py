@@ -227,6 +227,29 @@ def test_forced_handbacks_give_the_same_answers(built, monkeypatch):
     assert ix.stats()["search_overflows"] > 0
 
 
+def _overflows(ix, contexts):
+    return ix.stats()["search_overflows"] + sum(ix.stats_at(g)["search_overflows"] for g in range(1, contexts))
+
+
+def test_two_contexts_with_forced_handbacks(built, monkeypatch):
+    """Sharded over two contexts AND jobs handed back: the shards are gathered to the primary, where the host traversal redoes them."""
+    import hnswindex
+    x, ix, ref = built("cosine")
+    q = _data("cosine", 24, 7)
+    masks = {k: v for k, v in _masks(x, 5).items() if k in ("sel0.5", "sel0.02")}
+    want = {(name, k): ix.knn_query(q, k, allowed=mask) for name, mask in masks.items() for k in (5, 40)}   # one context, nothing forced
+    assert _same(want["sel0.5", 40], filtered_knn_batch(ref, x, "cosine", q, 40, MIN_NN, masks["sel0.5"]))
+    two = hnswindex.Index(DIM, "cosine")
+    two.set_collection_size(N); two.set_max_edges(M); two.set_min_nn(MIN_NN); two.set_insert_batch(1); two.set_devices(2)
+    two.add(x)
+    assert two.graph_hash() == ref.graph_hash()
+    set_diag(monkeypatch, cand_cap="24", spill_cap="8")
+    two.reset_stats()
+    for (name, k), w in want.items():
+        assert _same(two.knn_query(q, k, allowed=masks[name]), w), (name, k)
+    assert _overflows(two, 2) > 0 and two.stats_at(1)["search_launches"] >= 4
+
+
 def test_hashed_visited_sets_host_traversal_and_two_contexts(built, monkeypatch):
     x, ix, ref = built("ucosine")
     q = _data("ucosine", 8, 11)

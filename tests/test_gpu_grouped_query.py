@@ -290,6 +290,21 @@ def test_forced_handbacks_give_the_same_answers(cases, monkeypatch):
     assert info["handbacks"] > 0 and st["search_overflows"] == info["handbacks"] and st["launches"] > 0, (info, st)
 
 
+def test_two_contexts_with_forced_handbacks(cases, monkeypatch):
+    """Sharded over two contexts AND jobs handed back: the shards are gathered to the primary, where the host traversal redoes them."""
+    c = cases("cosine")
+    two = _index(DIM, c.metric, M, set_devices=2)
+    two.add(c.x)
+    assert two.graph_hash() == c.ref.graph_hash()
+    set_diag(monkeypatch, cand_cap="24", spill_cap="8")
+    two.reset_stats()
+    for k in (5, 40):
+        assert _same(two.knn_query_grouped(c.q, k, c.rg, c.qg, N_GROUPS), c.want(k)), k
+    info = two.knn_grouped_info()   # (summed over the contexts)
+    assert two.stats()["search_overflows"] + two.stats_at(1)["search_overflows"] > 0 and info["handbacks"] > 0, info
+    assert two.stats_at(1)["search_launches"] >= 2 and two.stats()["launches"] > 0
+
+
 def _other_path(c, **knobs):
     ix = _index(DIM, c.metric, M, **knobs)
     ix.add(c.x)

@@ -296,6 +296,23 @@ def test_forced_handbacks_give_the_same_answers(built, monkeypatch):
     assert st["multilayer_handbacks"] > 0 and st["search_overflows"] > 0, st
 
 
+def test_two_contexts_with_forced_handbacks(built, monkeypatch):
+    """No filter at layer >= 1, sharded over two contexts AND jobs handed back: the shards are gathered to the primary, where the host
+    traversal redoes them."""
+    x, ix, ref = built("cosine", True)    # the grid data: without a filter a beam of 40 outgrows the forced caps on tie-heavy data only
+    q = _queries("cosine", 24, 19, True)
+    layers = (1, top_layer(ref) // 2)
+    want = {(layer, k): ix.knn_query(q, k, layer=layer) for layer in layers for k in (5, 40)}   # one context, nothing forced
+    assert _same(want[1, 40], knn_at_layer_batch(ref, x, "cosine", q, 40, MIN_NN, 1))
+    two = _imported("cosine", x, ref, set_devices=2)
+    set_diag(monkeypatch, cand_cap="24", spill_cap="8")
+    two.reset_stats()
+    for (layer, k), w in want.items():
+        assert _same(two.knn_query(q, k, layer=layer), w), (layer, k)
+    assert two.stats()["search_overflows"] + two.stats_at(1)["search_overflows"] > 0
+    assert two.stats_at(1)["search_launches"] >= 4
+
+
 def test_hashed_visited_sets_and_two_contexts(built, monkeypatch):
     x, _, ref = built("sq_euclid")
     q = _queries("sq_euclid", 6, 18)

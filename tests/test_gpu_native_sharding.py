@@ -84,6 +84,23 @@ def test_hand_backs_are_answered_on_the_primary(Index):
     assert three.stats()["search_overflows"] + three.stats_at(1)["search_overflows"] + three.stats_at(2)["search_overflows"] >= 3
 
 
+def test_resident_call_after_hand_backs_stays_sharded(Index):
+    # the gather for the hand-backs leaves every shard where it was: the set is still resident, and still answered by every context
+    n, dim = 1500, 16
+    x = uniform(n, dim, 5)
+    q = uniform(300, dim, 6)
+    q[7, 3] = np.nan; q[150, 0] = np.nan; q[299, 5] = np.nan     # one in every shard of three
+    three = _index(Index, x, "sq_euclid", 3)
+    a = three.knn_query(q, 10)
+    assert three.stats()["search_overflows"] + three.stats_at(1)["search_overflows"] + three.stats_at(2)["search_overflows"] >= 3
+    three.reset_stats()
+    for k, want in ((10, a), (3, _index(Index, x, "sq_euclid", 1).knn_query(q, 3))):
+        b = three.knn_query_resident(k)
+        assert b[0].shape == (300, k) and (want[0] == b[0]).all() and (np.isnan(want[1]) == np.isnan(b[1])).all()
+        assert want[1].view(np.uint32)[~np.isnan(want[1])].tobytes() == b[1].view(np.uint32)[~np.isnan(b[1])].tobytes()
+    assert all(st["search_launches"] >= 2 for st in (three.stats(), three.stats_at(1), three.stats_at(2)))
+
+
 def test_resident_set_is_sharded_too(Index):
     n, dim = 5000, 48
     x, q = uniform(n, dim, 13), uniform(2048, dim, 14)
