@@ -123,6 +123,12 @@ _EXACT_RANGE_INFO = ("device_sorted", "host_sorted", "repeated_rounds", "results
 lib.hnsw_mi355x_exact_range_query.restype = ct.c_int
 lib.hnsw_mi355x_exact_range_query.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_int, ct.c_float, _U32, ct.c_longlong, ct.POINTER(ct.c_void_p),
                                               ct.POINTER(ct.c_void_p), _I]
+_EXACT_RANGE_GROUPED_INFO = ("calls", "device_sorted", "host_sorted", "repeated_pieces")   # hnswdev_exact_range_grouped_info's out[0 .. 3]
+lib.hnsw_mi355x_exact_range_query_grouped.restype = ct.c_int
+lib.hnsw_mi355x_exact_range_query_grouped.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_int, ct.c_float, _I, ct.c_longlong, _I, ct.c_int,
+                                                      ct.POINTER(ct.c_void_p), ct.POINTER(ct.c_void_p), ct.POINTER(ct.c_int)]
+lib.hnsw_mi355x_exact_range_grouped_info.restype = ct.c_int
+lib.hnsw_mi355x_exact_range_grouped_info.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
 lib.hnsw_mi355x_exact_range_info.restype = ct.c_int
 lib.hnsw_mi355x_exact_range_info.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
 _EXACT_GROUPED_INFO = ("calls", "groups_scanned", "scan_blocks", "ids_listed")   # hnswdev_exact_grouped_info's out[0 .. 3]
@@ -133,6 +139,12 @@ lib.hnsw_mi355x_exact_grouped_info.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint
 _KNN_GROUPED_INFO = ("calls", "launched", "skipped", "handbacks")   # hnswdev_knn_grouped_info's out[0 .. 3]
 lib.hnsw_mi355x_knn_query_grouped.restype = ct.c_int
 lib.hnsw_mi355x_knn_query_grouped.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_int, ct.c_int, ct.c_int, _I, ct.c_longlong, _I, ct.c_int, _I, _F]
+_RANGE_GROUPED_INFO = ("calls", "launched", "skipped", "host_finished")   # hnswdev_range_grouped_info's out[0 .. 3]
+lib.hnsw_mi355x_range_query_grouped.restype = ct.c_int
+lib.hnsw_mi355x_range_query_grouped.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_int, ct.c_float, ct.c_int, _I, ct.c_longlong, _I, ct.c_int,
+                                                ct.POINTER(ct.c_void_p), ct.POINTER(ct.c_void_p), ct.POINTER(ct.c_int)]
+lib.hnsw_mi355x_range_grouped_info.restype = ct.c_int
+lib.hnsw_mi355x_range_grouped_info.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
 lib.hnsw_mi355x_knn_grouped_info.restype = ct.c_int
 lib.hnsw_mi355x_knn_grouped_info.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
 
@@ -279,6 +291,10 @@ lib.hnswdev_exact_range.restype = ct.c_int
 lib.hnswdev_exact_range.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_longlong, ct.c_float, _U32, ct.c_longlong, _I]
 lib.hnswdev_exact_range_results.restype = ct.c_int
 lib.hnswdev_exact_range_results.argtypes = [ct.c_void_p, _I, _F]
+lib.hnswdev_exact_range_grouped.restype = ct.c_int
+lib.hnswdev_exact_range_grouped.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_longlong, ct.c_float, _I, ct.c_longlong, _I, ct.c_int, _I]
+lib.hnswdev_exact_range_grouped_info.restype = ct.c_int
+lib.hnswdev_exact_range_grouped_info.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
 lib.hnswdev_exact_range_info.restype = ct.c_int
 lib.hnswdev_exact_range_info.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
 lib.hnswdev_exact_knn_grouped.restype = ct.c_int
@@ -289,6 +305,10 @@ lib.hnswdev_exact_grouped_list_ms.restype = ct.c_int
 lib.hnswdev_exact_grouped_list_ms.argtypes = [ct.c_void_p, ct.POINTER(ct.c_double)]
 lib.hnswdev_knn_search_grouped.restype = ct.c_int
 lib.hnswdev_knn_search_grouped.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int, _I, ct.c_longlong, _I, ct.c_int, _I, _F, _I]
+lib.hnswdev_range_search_grouped.restype = ct.c_int
+lib.hnswdev_range_search_grouped.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_int, ct.c_float, ct.c_int, _I, ct.c_longlong, _I, ct.c_int, _I, _I]
+lib.hnswdev_range_grouped_info.restype = ct.c_int
+lib.hnswdev_range_grouped_info.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
 lib.hnswdev_knn_grouped_info.restype = ct.c_int
 lib.hnswdev_knn_grouped_info.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
 lib.hnswdev_range_results.restype = ct.c_int
@@ -682,6 +702,42 @@ class Index:
             lib.hnsw_free_results(ids_pp, dists_pp, n)
         return ids, dists
 
+    def exact_range_query_grouped(self, queries: npt.ArrayLike, radius: float, row_group, query_group,
+                                  n_groups=None) -> Tuple[List[npt.NDArray[np.int32]], List[npt.NDArray[np.float32]]]:
+        """exact_range_query with a candidate group per query, every group in one scan (hnsw_mi355x_exact_range_query_grouped):
+        row_group / query_group / n_groups as for exact_knn_query_grouped.  Per group the lists equal
+        exact_range_query(queries[query_group == g], radius, allowed=(row_group == g)); they come back in the caller's order."""
+        q = _as_2d_f32(queries, self.dim)
+        n = int(q.shape[0])
+        rg, qg, ng = _group_args(row_group, query_group, n_groups, n)
+        ids_pp = (ct.c_void_p * n)()
+        dists_pp = (ct.c_void_p * n)()
+        counts = (ct.c_int * n)()
+        status = lib.hnsw_mi355x_exact_range_query_grouped(self._h, q.ctypes.data_as(_F), n, self.dim, radius, rg.ctypes.data_as(_I), rg.shape[0],
+                                                           qg.ctypes.data_as(_I), ng, ids_pp, dists_pp, counts)
+        if status < 0:
+            raise RuntimeError(last_error())
+        ids, dists = [], []
+        try:
+            for i in range(n):
+                m = counts[i]
+                if m == 0:
+                    ids.append(np.empty(0, dtype=np.int32))
+                    dists.append(np.empty(0, dtype=np.float32))
+                    continue
+                ids.append(np.ctypeslib.as_array(ct.cast(ids_pp[i], _I), shape=(m,)).copy())
+                dists.append(np.ctypeslib.as_array(ct.cast(dists_pp[i], _F), shape=(m,)).copy())
+        finally:
+            lib.hnsw_free_results(ids_pp, dists_pp, n)
+        return ids, dists
+
+    def exact_range_grouped_info(self) -> dict:
+        """Counters of exact_range_query_grouped since reset_stats (hnsw_mi355x_exact_range_grouped_info)."""
+        out = (ct.c_uint64 * 4)()
+        if self._h:
+            lib.hnsw_mi355x_exact_range_grouped_info(self._h, out)
+        return dict(zip(_EXACT_RANGE_GROUPED_INFO, (int(v) for v in out)))
+
     def exact_range_info(self) -> dict:
         """Counters of exact_range_query since reset_stats (hnsw_mi355x_exact_range_info)."""
         out = (ct.c_uint64 * 4)()
@@ -724,6 +780,44 @@ class Index:
         finally:
             lib.hnsw_free_results(ids_pp, dists_pp, n)
         return ids, dists
+
+    def range_query_grouped(self, queries: npt.ArrayLike, radius: float, row_group, query_group, n_groups=None,
+                            layer: int = 0) -> Tuple[List[npt.NDArray[np.int32]], List[npt.NDArray[np.float32]]]:
+        """range_query with a group filter per query, every group in one device traversal (hnsw_mi355x_range_query_grouped):
+        row_group / query_group / n_groups as for knn_query_grouped.  Per group the lists equal
+        range_query(queries[query_group == g], radius, allowed=(row_group == g), layer=layer), the order among equal distances
+        included; where the reference throws on an empty heap (radius < 0) RuntimeError carries its message."""
+        q = _as_2d_f32(queries, self.dim)
+        n = int(q.shape[0])
+        rg, qg, ng = _group_args(row_group, query_group, n_groups, n)
+        ids_pp = (ct.c_void_p * n)()
+        dists_pp = (ct.c_void_p * n)()
+        counts = (ct.c_int * n)()
+        status = lib.hnsw_mi355x_range_query_grouped(self._h, q.ctypes.data_as(_F), n, self.dim, radius, int(layer), rg.ctypes.data_as(_I), rg.shape[0],
+                                                     qg.ctypes.data_as(_I), ng, ids_pp, dists_pp, counts)
+        if status < 0:
+            raise RuntimeError(last_error())
+        ids, dists = [], []
+        try:
+            for i in range(n):
+                m = counts[i]
+                if m == 0:
+                    ids.append(np.empty(0, dtype=np.int32))
+                    dists.append(np.empty(0, dtype=np.float32))
+                    continue
+                ids.append(np.ctypeslib.as_array(ct.cast(ids_pp[i], _I), shape=(m,)).copy())
+                dists.append(np.ctypeslib.as_array(ct.cast(dists_pp[i], _F), shape=(m,)).copy())
+        finally:
+            lib.hnsw_free_results(ids_pp, dists_pp, n)
+        return ids, dists
+
+    def range_grouped_info(self) -> dict:
+        """Counters of range_query_grouped since reset_stats (hnsw_mi355x_range_grouped_info): calls that reached the context, queries
+        launched, queries skipped because their group holds no graph id, lists the device left to the host."""
+        out = (ct.c_uint64 * 4)()
+        if self._h:
+            lib.hnsw_mi355x_range_grouped_info(self._h, out)
+        return dict(zip(_RANGE_GROUPED_INFO, (int(v) for v in out)))
 
     # ---- measurement aid: query set resident in HBM across calls ----
     def set_resident_queries(self, queries: npt.ArrayLike):
@@ -1257,6 +1351,30 @@ class DeviceBackend:
         cuts = np.cumsum(counts, dtype=np.int64)[:-1]
         return np.split(ids[:total], cuts), np.split(d[:total], cuts)
 
+    def exact_range_grouped(self, queries, radius: float, row_group, query_group, n_groups=None, n_rows=None):
+        """hnswdev_exact_range_grouped: exact_range with a candidate group per query -- (list of ids, list of dists) in the caller's
+        query order, query i answered from the uploaded rows j of [0, n_rows) (None: all) with row_group[j] == query_group[i].
+        queries None: the resident set (len(query_group) of its rows).  n_groups None: the largest value in either array plus one."""
+        q = None if queries is None else _as_2d_f32(queries, self.dim)
+        n = int(np.asarray(query_group).size) if q is None else int(q.shape[0])
+        rg, qg, ng = _group_args(row_group, query_group, n_groups, n)
+        counts = np.zeros(n, dtype=np.int32)
+        self._check(lib.hnswdev_exact_range_grouped(self._ctx, None if q is None else q.ctypes.data_as(_F), n, (1 << 62) if n_rows is None else int(n_rows),
+                                                    float(radius), rg.ctypes.data_as(_I), rg.shape[0], qg.ctypes.data_as(_I), ng,
+                                                    counts.ctypes.data_as(_I)))
+        total = int(counts.sum(dtype=np.int64))
+        ids = np.empty(max(total, 1), dtype=np.int32)
+        d = np.empty(max(total, 1), dtype=np.float32)
+        self._check(lib.hnswdev_exact_range_results(self._ctx, ids.ctypes.data_as(_I), d.ctypes.data_as(_F)))
+        cuts = np.cumsum(counts, dtype=np.int64)[:-1]
+        return np.split(ids[:total], cuts), np.split(d[:total], cuts)
+
+    def exact_range_grouped_info(self) -> dict:
+        """Counters of exact_range_grouped since reset_stats (hnswdev_exact_range_grouped_info)."""
+        out = (ct.c_uint64 * 4)()
+        self._check(lib.hnswdev_exact_range_grouped_info(self._ctx, out))
+        return dict(zip(_EXACT_RANGE_GROUPED_INFO, (int(v) for v in out)))
+
     def exact_range_info(self) -> dict:
         """Counters of exact_range since reset_stats (hnswdev_exact_range_info)."""
         out = (ct.c_uint64 * 4)()
@@ -1305,6 +1423,29 @@ class DeviceBackend:
         self._check(lib.hnswdev_range_results(self._ctx, ids.ctypes.data_as(_I), d.ctypes.data_as(_F)))
         cuts = np.cumsum(counts)[:-1]
         return np.split(ids[:total], cuts), np.split(d[:total], cuts), flags
+
+    def range_search_grouped(self, queries, entry_point: int, radius: float, row_group, query_group, n_groups=None, layer: int = 0):
+        """hnswdev_range_search_grouped: range_search with a group filter per query -- (ids, dists, flags) as range_search returns
+        them, query i filtered by row_group == query_group[i]."""
+        q = _as_2d_f32(queries, self.dim)
+        n = q.shape[0]
+        rg, qg, ng = _group_args(row_group, query_group, n_groups, n)
+        counts = np.zeros(n, dtype=np.int32)
+        flags = np.zeros(n, dtype=np.int32)
+        self._check(lib.hnswdev_range_search_grouped(self._ctx, q.ctypes.data_as(_F), n, int(entry_point), float(radius), int(layer), rg.ctypes.data_as(_I),
+                                                     rg.shape[0], qg.ctypes.data_as(_I), ng, counts.ctypes.data_as(_I), flags.ctypes.data_as(_I)))
+        total = int(counts.sum())
+        ids = np.empty(max(total, 1), dtype=np.int32)
+        d = np.empty(max(total, 1), dtype=np.float32)
+        self._check(lib.hnswdev_range_results(self._ctx, ids.ctypes.data_as(_I), d.ctypes.data_as(_F)))
+        cuts = np.cumsum(counts)[:-1]
+        return np.split(ids[:total], cuts), np.split(d[:total], cuts), flags
+
+    def range_grouped_info(self) -> dict:
+        """Counters of range_search_grouped since reset_stats (hnswdev_range_grouped_info)."""
+        out = (ct.c_uint64 * 4)()
+        self._check(lib.hnswdev_range_grouped_info(self._ctx, out))
+        return dict(zip(_RANGE_GROUPED_INFO, (int(v) for v in out)))
 
     def set_profiling(self, on: bool):
         self._check(lib.hnswdev_set_profiling(self._ctx, int(on)))

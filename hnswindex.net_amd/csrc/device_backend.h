@@ -355,13 +355,30 @@ public:
     // and what crosses back is packed -- a kRangeFinal job's cnt[i] entries are its RESULTS in the reference's order, any other
     // job's are its whole CLOSURE (every node within range the traversal reached, allowed or not; kRangeTied: its allowed entries
     // first, ascending), for the host to partition, sort and replay.  range < 0 leaves every closure to the host (the empty-heap rule).
-    bool range_batch(const SearchJob *jobs, int njobs, float range, RangeResults *res, const uint32_t *allow_bits = nullptr, long long nbits = 0);
+    // grp (range_query_grouped): the filter is "label[id] == group_of[job]" instead of a bit set (allow_bits must be
+    // nullptr then) -- ids >= n_label are in no group -- ranked by range_sort_grouped_kernel; what crosses back is the filtered
+    // call's.  skipped: the queries the caller answered without a job (their group holds no graph id), for range_grouped_info.
+    struct RangeGroups {
+        const int *label = nullptr;
+        long long n_label = 0;
+        const int *group_of = nullptr; // [njobs]
+        long long skipped = 0;
+    };
+    bool range_batch(const SearchJob *jobs, int njobs, float range, RangeResults *res, const uint32_t *allow_bits = nullptr, long long nbits = 0,
+                     const RangeGroups *grp = nullptr);
+    // grouped range calls that reached this context, queries launched, queries skipped for a group without graph ids, lists the
+    // device left to the host (closures to partition / sort / replay, and hand-backs)
+    void range_grouped_info(uint64_t out[4]) const { for (int i = 0; i < 4; ++i) out[i] = rg_info_[i]; }
     // the C ABI's form: sorted per query, equal distances handed back; results kept until the next call
     bool range_search(const float *queries, int nq, int entry_point, float range, int *out_counts, int *out_flags);
     // ... with an allow-set (ids >= nbits not allowed); false with "System.InvalidOperationException: Heap is empty" where the
     // reference throws (range_replay.h)
     bool range_search_filtered(const float *queries, int nq, int entry_point, float range, const uint32_t *allow_bits, long long nbits,
                                int *out_counts, int *out_flags, int layer = 0);
+    // ... with a group filter per query (hnswdev_range_search_grouped): query i as with the allow-set
+    // { id : row_group[id] == query_group[i] }; the group arguments and their errors are knn_search_grouped's
+    bool range_search_grouped(const float *queries, int nq, int entry_point, float range, const int *row_group, long long n_row_group,
+                              const int *query_group, int n_groups, int *out_counts, int *out_flags, int layer = 0);
     bool range_results(int *out_ids, float *out_d);
     // hnswdev_exact_knn (dk_exact.h): for each query the k uploaded rows of smallest (distance, id) among ids
     // [0, min(n_rows, uploaded)) that allow_bits allows (nullptr: all of them; else nbits bits as for search_filtered), ascending,
@@ -388,6 +405,15 @@ public:
     // grouped calls that launched, groups scanned (a query and a candidate each), scan blocks launched, ids placed in group lists
     // (all four count the calls that launched a scan only)
     void exact_grouped_info(uint64_t out[4]) const { for (int i = 0; i < 4; ++i) out[i] = xg_info_[i]; }
+    // hnswdev_exact_range_grouped: exact_range with exact_knn_grouped's candidate set per query -- the group
+    // arguments, their errors and the group lists are that call's; radius, order, counts, capacities and the results kept for
+    // exact_range_results are exact_range's.  A query whose group has no member gets an empty list without being scanned.
+    // false: no results are kept and every count is 0.  Synchronous.
+    bool exact_range_grouped(const float *queries, int nq, long long n_rows, float range, const int *row_group, long long n_row_group,
+                             const int *query_group, int n_groups, int *out_counts);
+    // grouped range calls that launched a scan, lists of >= 2 entries ordered on the device, lists ordered on the host, pieces
+    // scanned again with exact capacities
+    void exact_range_grouped_info(uint64_t out[4]) const { for (int i = 0; i < 4; ++i) out[i] = xrg_info_[i]; }
     // HIP-event time of the list-building kernels (count, offsets, place) of the grouped calls made while profiling was on
     double exact_grouped_list_ms() const { return xg_list_ms_; }
     // hnswdev_graph_info / hnswdev_graph_components (dk_graph_info.h): HNSWInfo.LayerInfo (HNSWInfo.cs:18-43) and the
@@ -529,6 +555,7 @@ private:
     DevBuf<int> s_glabel_;       // grouped searches: the call's row_group
     DevBuf<int> s_gquery_;       // ... [query_group of the call | order tables of its launches]
     uint64_t kg_info_[4] = {0, 0, 0, 0};
+    uint64_t rg_info_[4] = {0, 0, 0, 0}; // range_grouped_info
     DevBuf<int> x_ids_;                 // exact_knn: the call's ascending id list (exact_compact_kernel)
     DevBuf<long long> x_boff_;          // ... set bits in front of each block of bitset words
     DevBuf<unsigned long long> x_lists_; // ... the per-(query, chunk) lists of a round: at most 1 GiB, allocated by the first call and kept
@@ -553,6 +580,11 @@ private:
     DevBuf<int> x_gperm_;                 // ... queries == NULL: where each query of the sorted order is in the resident set
     DevBuf<unsigned char> x_gwork_;       // ... a round's tables: [ExactMergeItem per query | ExactWorkItem per scan block]
     uint64_t xg_info_[4] = {0, 0, 0, 0};
+    uint64_t xrg_info_[4] = {0, 0, 0, 0}; // exact_range_grouped's counters
+    bool exact_group_lists(const char *who, const int *row_group, long long n, int n_groups, std::vector<int> &cnt, std::vector<int> &goff, uint64_t *listed);
+    bool exact_sorted_queries(const char *who, const float *queries, int nq, const std::vector<int> &order, const float **d_q, const double **d_qsn);
+    bool exact_range_grouped_run(const float *queries, int nq, long long n_rows, float range, const int *row_group, long long n_row_group,
+                                 const int *query_group, int n_groups, int *out_counts);
     double xg_list_ms_ = 0.0;
     bool graph_info_begin(const char *who, int layer, const uint32_t *live_bits, long long nbits, LayerView *g);
     bool graph_info_fetch(const GraphAcc **acc);

@@ -916,7 +916,9 @@ void Device::reset_stats()
     stats_.row_bytes = rb;
     for (uint64_t &v : xr_info_) v = 0;
     for (uint64_t &v : xg_info_) v = 0;
+    for (uint64_t &v : xrg_info_) v = 0;
     for (uint64_t &v : kg_info_) v = 0;
+    for (uint64_t &v : rg_info_) v = 0;
     xg_list_ms_ = 0.0;
     for (uint64_t &v : gi_info_) v = 0;
     for (uint64_t &v : gr_info_) v = 0;
@@ -2162,9 +2164,17 @@ bool Device::range_host_room(size_t entries, size_t keep)
     return true;
 }
 
-bool Device::range_batch(const SearchJob *jobs, int njobs, float range, RangeResults *res, const uint32_t *allow_bits, long long nbits)
+bool Device::range_batch(const SearchJob *jobs, int njobs, float range, RangeResults *res, const uint32_t *allow_bits, long long nbits,
+                         const RangeGroups *grp)
 {
-    const bool filtered = allow_bits != nullptr;
+    const bool grouped = grp != nullptr;
+    const bool filtered = allow_bits != nullptr || grouped; // (grouped: the filtered call's ranking, replay and packing, on the group predicate)
+    if (grouped) {
+        if (allow_bits || grp->n_label < 0 || (njobs > 0 && (!grp->label || !grp->group_of))) { set_dev_error("range_batch: bad argument"); return false; }
+        rg_info_[0] += 1;
+        rg_info_[1] += (uint64_t)std::max(njobs, 0);
+        rg_info_[2] += (uint64_t)std::max<long long>(grp->skipped, 0);
+    }
     res->off.assign((size_t)std::max(njobs, 0), 0ull);
     res->cnt.assign((size_t)std::max(njobs, 0), 0);
     res->flag.assign((size_t)std::max(njobs, 0), 0);
@@ -2197,7 +2207,16 @@ bool Device::range_batch(const SearchJob *jobs, int njobs, float range, RangeRes
         if (!ok) { (void)s_roff_.reset(); return false; }
     }
     long long n_allow = 0;
-    if (filtered) { // the call's allow-set: the words that cover graph ids, on this context (as search_filtered)
+    long long n_lab = 0;
+    if (grouped) { // the call's labels: those of graph ids, on this context (as search_grouped), and room for a launch's group table
+        if (!s_rres_.grow(s_roff_.cap()) || !s_rdst_.grow(s_roff_.cap())) return false;
+        n_lab = std::min<long long>(grp->n_label, g_n_);
+        if (!s_glabel_.grow(std::max<size_t>((size_t)n_lab, 1)) || !s_gquery_.grow((size_t)chunk)) return false;
+        if (n_lab > 0) {
+            HIP_OK(hipMemcpyAsync(s_glabel_, grp->label, 4u * (size_t)n_lab, hipMemcpyHostToDevice, st));
+            HIP_OK(hipStreamSynchronize(st)); // (pageable source: the caller's buffer)
+        }
+    } else if (filtered) { // the call's allow-set: the words that cover graph ids, on this context (as search_filtered)
         if (!s_rres_.grow(s_roff_.cap()) || !s_rdst_.grow(s_roff_.cap())) return false;
         n_allow = std::min<long long>(nbits, g_n_);
         const size_t words = (size_t)((n_allow + 31) / 32);
@@ -2219,11 +2238,17 @@ bool Device::range_batch(const SearchJob *jobs, int njobs, float range, RangeRes
         // pinned layout: [evals, used (16 B) | jobs | offsets | counts | flags | entries | states]; then reused for the results
         // (filtered: [... | allowed counts | packed offsets] besides)
         const size_t b_jobs = sizeof(SearchJob) * (size_t)nj, b_off = 8u * (size_t)nj, b_i = 4u * (size_t)nj;
-        char *hs = static_cast<char *>(pinned_stage(16 + b_jobs + b_off + 4 * b_i + (filtered ? b_i + b_off : 0)));
+        // (grouped: [... | the jobs' groups] behind those)
+        char *hs = static_cast<char *>(pinned_stage(16 + b_jobs + b_off + 4 * b_i + (filtered ? b_i + b_off : 0) + (grouped ? b_i : 0)));
         if (!hs) return false;
         SearchJob *h_jobs = reinterpret_cast<SearchJob *>(hs + 16);
         for (int i = 0; i < nj; ++i) h_jobs[i] = jobs[todo[i]];
         HIP_OK(hipMemcpyAsync(s_jobs_, h_jobs, b_jobs, hipMemcpyHostToDevice, st));
+        if (grouped) { // the sort kernel's table: job -> the group its query names
+            int *h_grp = reinterpret_cast<int *>(hs + 16 + b_jobs + b_off + 5 * b_i + b_off);
+            for (int i = 0; i < nj; ++i) h_grp[i] = grp->group_of[todo[i]];
+            HIP_OK(hipMemcpyAsync(s_gquery_, h_grp, b_i, hipMemcpyHostToDevice, st));
+        }
         uj_len_ = 0;
         HIP_OK(hipMemsetAsync(s_jobctr_, 0, sizeof(int), st));
         HIP_OK(hipMemsetAsync(s_evals_, 0, sizeof(unsigned long long), st));
@@ -2249,7 +2274,11 @@ bool Device::range_batch(const SearchJob *jobs, int njobs, float range, RangeRes
         HIP_OK(hipMemsetAsync(s_rtied_, 0, sizeof(int), st));
         HIP_OK(hipMemsetAsync(s_rstate_, 0, sizeof(int) * (size_t)nj, st));
         const dim3 sort_grid(std::min(nj, 8 * std::max(1, num_cu_))), replay_grid(std::min(nj, 2 * std::max(1, num_cu_)));
-        if (filtered) {
+        if (grouped) {
+            hipLaunchKernelGGL(range_sort_grouped_kernel, sort_grid, dim3(64), 0, st, reinterpret_cast<ND *>(s_arena_.get()), s_roff_, s_cnt_, s_flag_, nj,
+                               s_rstate_, s_rtied_, s_rfin_ctr_, s_glabel_.get(), n_lab, s_gquery_.get(), s_rres_, (int)(finish == 0 || range < 0.0f));
+            HIP_OK(hipGetLastError());
+        } else if (filtered) {
             hipLaunchKernelGGL(range_sort_filtered_kernel, sort_grid, dim3(64), 0, st, reinterpret_cast<ND *>(s_arena_.get()), s_roff_, s_cnt_, s_flag_, nj,
                                s_rstate_, s_rtied_, s_rfin_ctr_, reinterpret_cast<const unsigned *>(s_allow_.get()), n_allow, s_rres_,
                                (int)(finish == 0 || range < 0.0f));
@@ -2298,6 +2327,7 @@ bool Device::range_batch(const SearchJob *jobs, int njobs, float range, RangeRes
                 res->state[(size_t)j] = finish >= 1 || filtered ? h_state[i] : kRangeHostSort;
                 const int results = filtered ? h_res[i] : h_cnt[i]; // (filtered, handed to the host: the allowed members of its closure)
                 if (results >= 2) { if (res->state[(size_t)j] == kRangeFinal) stats_.range_device_ordered++; else stats_.range_host_ordered++; }
+                if (grouped && h_cnt[i] > 0 && h_state[i] != kRangeFinal) rg_info_[3] += 1; // a closure the host finishes
                 finished += (unsigned long long)h_cnt[i];
                 if (h_cnt[i] > 0) span = std::max(span, h_off[i] + (unsigned long long)h_cnt[i]);
             } else if (h_flag[i] == 3) again.push_back(j);
@@ -2370,6 +2400,7 @@ bool Device::range_batch(const SearchJob *jobs, int njobs, float range, RangeRes
         handed.swap(still);
     }
     stats_.range_handbacks += handed.size();
+    if (grouped) rg_info_[3] += handed.size();
     range_hint_ = (double)closure_total / (double)njobs; // (filtered calls too: the arena holds closures)
     return true;
 }
@@ -2451,6 +2482,70 @@ bool Device::range_search_filtered(const float *queries, int nq, int entry_point
             continue;
         }
         abi_range_.insert(abi_range_.end(), b, e);
+    }
+    return true;
+}
+
+// range_search_filtered with a group filter per query: query i is answered as with the allow-set
+// { id : row_group[id] == query_group[i] }, every group in one traversal launch.  Only the labels of graph ids count.  A query whose
+// group holds no graph id gets an empty list without a job -- when range >= 0 only: below zero the filtered call can throw on an
+// empty set too (range_replay.h), so those queries run.
+bool Device::range_search_grouped(const float *queries, int nq, int entry_point, float range, const int *row_group, long long n_row_group,
+                                  const int *query_group, int n_groups, int *out_counts, int *out_flags, int layer)
+{
+    abi_range_.clear();
+    if (nq <= 0) return true;
+    if (!out_counts || !out_flags) { set_dev_error("range_search_grouped: null argument"); return false; }
+    for (int i = 0; i < nq; ++i) { out_counts[i] = 0; out_flags[i] = 0; }
+    if (!row_group || n_row_group < 0) { set_dev_error("range_search_grouped: row_group must not be NULL and n_row_group must be >= 0"); return false; }
+    if (!query_group) { set_dev_error("range_search_grouped: query_group must not be NULL"); return false; }
+    if (!group_args_ok("range_search_grouped", query_group, nq, n_groups)) return false;
+    int top;
+    if (!abi_begin("range_search_grouped", queries, nq, entry_point, layer, &top, true)) return false;
+    const long long n_lab = std::min<long long>(n_row_group, g_n_);
+    std::vector<char> has_id((size_t)n_groups, 0);
+    for (long long id = 0; id < n_lab; ++id)
+        if (row_group[id] >= 0 && row_group[id] < n_groups) has_id[(size_t)row_group[id]] = 1;
+    std::vector<SearchJob> jobs;
+    std::vector<int> qi_of, group_of;
+    for (int i = 0; i < nq; ++i)
+        if (has_id[(size_t)query_group[i]] || !(range >= 0.0f)) {
+            jobs.push_back(SearchJob{i, entry_point, top, layer, -1});
+            qi_of.push_back(i);
+            group_of.push_back(query_group[i]);
+        }
+    const int nj = (int)jobs.size();
+    RangeGroups grp;
+    grp.label = row_group;
+    grp.n_label = n_lab;
+    grp.group_of = group_of.data();
+    grp.skipped = nq - nj;
+    RangeResults r;
+    if (!range_batch(jobs.data(), nj, range, &r, nullptr, 0, &grp)) return false;
+    const auto list_of = [&](int id) {
+        return layer == 0 ? hg_->adj0.data() + (size_t)id * (size_t)hg_->stride0
+                          : hg_->pool.data() + hg_->upper[(size_t)id] + (size_t)(layer - 1) * (size_t)hg_->strideU;
+    };
+    for (int j = 0; j < nj; ++j) { // (in query order: abi_range_ holds the lists as range_results hands them out)
+        const int i = qi_of[(size_t)j];
+        out_flags[i] = r.flag[(size_t)j];
+        if (out_flags[i]) continue;
+        SearchHit *b = r.found + r.off[(size_t)j], *e = b + r.cnt[(size_t)j];
+        if (r.state[(size_t)j] == kRangeFinal) { // the results, in the reference's order
+            out_counts[i] = r.cnt[(size_t)j];
+            abi_range_.insert(abi_range_.end(), b, e);
+            continue;
+        }
+        std::vector<NodeDist> ordered; // a closure: partition, sort, replay where the allowed results tie
+        if (finish_filtered_range(list_of, 2 * hg_->M, r.entry[(size_t)j], range, b, r.cnt[(size_t)j], AllowPred{row_group, n_lab, group_of[(size_t)j]}, ordered) ==
+            kRangeHeapEmpty) {
+            abi_range_.clear();
+            for (int q = 0; q < nq; ++q) out_counts[q] = 0;
+            set_dev_error(kHeapEmptyError);
+            return false;
+        }
+        out_counts[i] = (int)ordered.size();
+        for (const NodeDist &nd : ordered) abi_range_.push_back(SearchHit{nd.id, nd.dist});
     }
     return true;
 }
@@ -2735,6 +2830,106 @@ bool Device::exact_knn_rounds(const float *d_q, const double *d_qsn, int nq, con
     return true;
 }
 
+// The group lists of a grouped flat scan: row_group[0, n) up, counts | offsets | cursors and the members on the device (a CSR in
+// x_ids_, built by exact_group_lists_launch), the counts back in one copy.  cnt[g]: members of group g; goff[g]: where its segment
+// starts in x_ids_; *listed: ids that are in a group.  The stream is idle and the pinned stage free when this returns.
+bool Device::exact_group_lists(const char *who, const int *row_group, long long n, int n_groups, std::vector<int> &cnt, std::vector<int> &goff, uint64_t *listed)
+{
+    hipStream_t st = S(stream_);
+    const size_t G = (size_t)n_groups, rg_bytes = 4 * (size_t)n;
+    if (!x_grow_.grow((size_t)n) || !x_gcnt_.grow(3 * G) || !x_ids_.grow((size_t)n)) return false;
+    cnt.assign(G, 0);
+    goff.assign(G, 0);
+    const size_t staged = rg_bytes < (4u << 20) ? rg_bytes : 0; // larger arrays go up in pieces, as query sets do
+    char *hs = static_cast<char *>(pinned_stage(staged + 4 * G));
+    if (!hs) return false;
+    if (staged) { memcpy(hs, row_group, rg_bytes); HIP_OK(hipMemcpyAsync(x_grow_, hs, rg_bytes, hipMemcpyHostToDevice, st)); }
+    else if (!staged_upload(reinterpret_cast<float *>(x_grow_.get()), reinterpret_cast<const float *>(row_group), rg_bytes)) return false;
+    const bool timed = profiling_; // the list-building kernels have an event pair of their own (exact_grouped_list_ms)
+    if (timed && (!ev0_.create(true) || !ev1_.create(true))) return false;
+    if (timed) HIP_OK(hipEventRecord(E(ev0_), st));
+    HIP_OK(exact_group_lists_launch(x_grow_, n, n_groups, x_gcnt_, x_gcnt_.get() + G, x_gcnt_.get() + 2 * G, x_ids_, st));
+    if (timed) HIP_OK(hipEventRecord(E(ev1_), st));
+    HIP_OK(hipMemcpyAsync(hs + staged, x_gcnt_, 4 * G, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    if (timed) {
+        float ms = 0.f;
+        HIP_OK(hipEventElapsedTime(&ms, E(ev0_), E(ev1_)));
+        xg_list_ms_ += ms;
+    }
+    memcpy(cnt.data(), hs + staged, 4 * G); // (the stage is used again by the caller)
+    long long at = 0;
+    for (size_t g = 0; g < G; ++g) { goff[g] = (int)at; at += cnt[g]; }
+    if (at > n) { set_dev_error(std::string(who) + ": the group counts exceed the ids"); return false; }
+    *listed = (uint64_t)at;
+    return true;
+}
+
+// The queries of a grouped flat scan in the order `order` (sorted position -> the caller's index): uploaded through set_queries'
+// path, or (queries == nullptr) gathered from the resident set on the device.  The stream is idle and the pinned stage free when
+// this returns.
+bool Device::exact_sorted_queries(const char *who, const float *queries, int nq, const std::vector<int> &order, const float **d_q, const double **d_qsn)
+{
+    hipStream_t st = S(stream_);
+    if (queries) {
+        std::vector<float> sorted((size_t)nq * (size_t)dim_);
+        for (int p = 0; p < nq; ++p) memcpy(&sorted[(size_t)p * dim_], queries + (size_t)order[(size_t)p] * dim_, sizeof(float) * (size_t)dim_);
+        return exact_queries(who, sorted.data(), nq, d_q, d_qsn);
+    }
+    if (!x_queries_.grow((size_t)nq * pitch_, (size_t)std::max(nq, 1024) * pitch_) || (metric_ == M_COS && !x_q_sn_.grow((size_t)nq, (size_t)std::max(nq, 1024)))) return false;
+    if (!x_gperm_.grow((size_t)nq)) return false;
+    int *hp = static_cast<int *>(pinned_stage(4 * (size_t)nq));
+    if (!hp) return false;
+    memcpy(hp, order.data(), 4 * (size_t)nq);
+    HIP_OK(hipMemcpyAsync(x_gperm_, hp, 4 * (size_t)nq, hipMemcpyHostToDevice, st));
+    HIP_OK(exact_gather_queries_launch(d_queries_, metric_ == M_COS ? d_q_sn_.get() : nullptr, x_gperm_, nq, pitch_, x_queries_, x_q_sn_, st));
+    HIP_OK(hipStreamSynchronize(st)); // the pinned stage is used again by the caller
+    *d_q = x_queries_; *d_qsn = metric_ == M_COS ? x_q_sn_.get() : nullptr;
+    return true;
+}
+
+// Each scanned group's chunks (a group is scanned when it has a query and a member): the (tile, row) work of the call spread over
+// about two blocks per CU, no chunk shorter than 1 024 rows, at most kExactMaxChunks per group; `exact_chunk` forces the rows per
+// chunk.  gchunk[g]: rows per chunk; gnch[g]: chunks, 0 where the group is not scanned.
+static void exact_group_chunks(const std::vector<int> &gq, const std::vector<int> &cnt, int qt, int num_cu, std::vector<int> &gchunk, std::vector<int> &gnch)
+{
+    const size_t G = gq.size();
+    const long long forced_c = diag("exact_chunk", 0);
+    long long work = 0; // (tile, row) pairs of the call
+    for (size_t g = 0; g < G; ++g)
+        if (gq[g] > 0 && cnt[g] > 0) work += (long long)((gq[g] + qt - 1) / qt) * cnt[g];
+    const long long target = std::max<long long>(1024, (work + 2LL * num_cu - 1) / (2LL * num_cu));
+    gchunk.assign(G, 0);
+    gnch.assign(G, 0);
+    for (size_t g = 0; g < G; ++g) {
+        if (gq[g] <= 0 || cnt[g] <= 0) continue;
+        const long long m = cnt[g];
+        long long chunks = forced_c > 0 ? (m + forced_c - 1) / forced_c : std::max<long long>(1, std::min<long long>((m + target - 1) / target, m / 1024));
+        chunks = std::min<long long>(chunks, kExactMaxChunks);
+        long long chunk = (m + chunks - 1) / chunks;
+        if (forced_c <= 0) chunk = (chunk + kExactIterRows - 1) / kExactIterRows * kExactIterRows;
+        gchunk[g] = (int)chunk;
+        gnch[g] = (int)((m + chunk - 1) / chunk);
+    }
+}
+
+// The queries of each round (round_end: one past the last query of each, in the caller's order) sorted by group -- a counting sort,
+// stable.  order[sorted position] = the caller's index.
+static std::vector<int> exact_group_order(const int *query_group, int n_groups, const std::vector<int> &round_end)
+{
+    const size_t G = (size_t)n_groups;
+    std::vector<int> order((size_t)(round_end.empty() ? 0 : round_end.back())), at(G + 1);
+    int r0 = 0;
+    for (const int r1 : round_end) {
+        std::fill(at.begin(), at.end(), 0);
+        for (int i = r0; i < r1; ++i) at[(size_t)query_group[i] + 1] += 1;
+        for (size_t g = 0; g < G; ++g) at[g + 1] += at[g];
+        for (int i = r0; i < r1; ++i) order[(size_t)r0 + (size_t)at[(size_t)query_group[i]]++] = i;
+        r0 = r1;
+    }
+    return order;
+}
+
 // ---- hnswdev_exact_knn_grouped: a candidate group per query, every group scanned in one launch --------
 // The groups' id lists are a CSR in x_ids_, built on the device from row_group; the counts come back in one copy.  The queries are
 // uploaded sorted by group (stable), so a group's queries are a run that is cut into tiles, and its list into chunks: a scan block
@@ -2763,35 +2958,10 @@ bool Device::exact_knn_grouped(const float *queries, int nq, long long n_rows, i
     if (!bind()) return false;
     hipStream_t st = S(stream_);
 
-    // the group lists: row_group up, counts | offsets | cursors and the members on the device, the counts back
-    const size_t G = (size_t)n_groups, rg_bytes = 4 * (size_t)n;
-    if (!x_grow_.grow((size_t)n) || !x_gcnt_.grow(3 * G) || !x_ids_.grow((size_t)n)) return false;
-    std::vector<int> cnt(G), goff(G); // members of each group, where its segment starts in x_ids_
+    std::vector<int> cnt, goff; // members of each group, where its segment starts in x_ids_
     uint64_t listed = 0;
-    {
-        const size_t staged = rg_bytes < (4u << 20) ? rg_bytes : 0; // larger arrays go up in pieces, as query sets do
-        char *hs = static_cast<char *>(pinned_stage(staged + 4 * G));
-        if (!hs) return false;
-        if (staged) { memcpy(hs, row_group, rg_bytes); HIP_OK(hipMemcpyAsync(x_grow_, hs, rg_bytes, hipMemcpyHostToDevice, st)); }
-        else if (!staged_upload(reinterpret_cast<float *>(x_grow_.get()), reinterpret_cast<const float *>(row_group), rg_bytes)) return false;
-        const bool timed = profiling_; // the list-building kernels have an event pair of their own (exact_grouped_list_ms)
-        if (timed && (!ev0_.create(true) || !ev1_.create(true))) return false;
-        if (timed) HIP_OK(hipEventRecord(E(ev0_), st));
-        HIP_OK(exact_group_lists_launch(x_grow_, n, n_groups, x_gcnt_, x_gcnt_.get() + G, x_gcnt_.get() + 2 * G, x_ids_, st));
-        if (timed) HIP_OK(hipEventRecord(E(ev1_), st));
-        HIP_OK(hipMemcpyAsync(hs + staged, x_gcnt_, 4 * G, hipMemcpyDeviceToHost, st));
-        HIP_OK(hipStreamSynchronize(st));
-        if (timed) {
-            float ms = 0.f;
-            HIP_OK(hipEventElapsedTime(&ms, E(ev0_), E(ev1_)));
-            xg_list_ms_ += ms;
-        }
-        memcpy(cnt.data(), hs + staged, 4 * G); // (the stage is used again for the queries)
-        long long at = 0;
-        for (size_t g = 0; g < G; ++g) { goff[g] = (int)at; at += cnt[g]; }
-        if (at > n) { set_dev_error("exact_knn_grouped: the group counts exceed the ids"); return false; }
-        listed = (uint64_t)at;
-    }
+    if (!exact_group_lists("exact_knn_grouped", row_group, n, n_groups, cnt, goff, &listed)) return false;
+    const size_t G = (size_t)n_groups;
     int max_gq = 0;
     uint64_t scanned = 0;
     for (size_t g = 0; g < G; ++g)
@@ -2802,22 +2972,8 @@ bool Device::exact_knn_grouped(const float *queries, int nq, long long n_rows, i
     const ExactPlan tp = exact_plan(max_gq, 1, k, pitch_, num_cu_);
     if (tp.lds > 64 * 1024) { set_dev_error("exact_knn_grouped: tile exceeds the LDS budget"); return false; }
     const int qt = tp.qtile;
-    const long long forced_c = diag("exact_chunk", 0);
-    long long work = 0; // (tile, row) pairs of the call
-    for (size_t g = 0; g < G; ++g)
-        if (gq[g] > 0 && cnt[g] > 0) work += (long long)((gq[g] + qt - 1) / qt) * cnt[g];
-    const long long target = std::max<long long>(1024, (work + 2LL * num_cu_ - 1) / (2LL * num_cu_));
-    std::vector<int> gchunk(G, 0), gnch(G, 0); // rows per chunk, chunks (0: not scanned)
-    for (size_t g = 0; g < G; ++g) {
-        if (gq[g] <= 0 || cnt[g] <= 0) continue;
-        const long long m = cnt[g];
-        long long chunks = forced_c > 0 ? (m + forced_c - 1) / forced_c : std::max<long long>(1, std::min<long long>((m + target - 1) / target, m / 1024));
-        chunks = std::min<long long>(chunks, kExactMaxChunks);
-        long long chunk = (m + chunks - 1) / chunks;
-        if (forced_c <= 0) chunk = (chunk + kExactIterRows - 1) / kExactIterRows * kExactIterRows;
-        gchunk[g] = (int)chunk;
-        gnch[g] = (int)((m + chunk - 1) / chunk);
-    }
+    std::vector<int> gchunk, gnch; // rows per chunk, chunks (0: not scanned)
+    exact_group_chunks(gq, cnt, qt, num_cu_, gchunk, gnch);
 
     // rounds: ranges of the caller's order within both budgets; inside each the queries sorted by group (counting sort: stable)
     const long long lists_cap = (1LL << 30) / ((long long)k * 8), out_cap = std::max<long long>(1, (1LL << 24) / k);
@@ -2831,37 +2987,11 @@ bool Device::exact_knn_grouped(const float *queries, int nq, long long n_rows, i
         }
         round_end.push_back(nq);
     }
-    std::vector<int> order((size_t)nq); // sorted position -> the caller's index
-    {
-        std::vector<int> at(G + 1);
-        int r0 = 0;
-        for (const int r1 : round_end) {
-            std::fill(at.begin(), at.end(), 0);
-            for (int i = r0; i < r1; ++i) at[(size_t)query_group[i] + 1] += 1;
-            for (size_t g = 0; g < G; ++g) at[g + 1] += at[g];
-            for (int i = r0; i < r1; ++i) order[(size_t)r0 + (size_t)at[(size_t)query_group[i]]++] = i;
-            r0 = r1;
-        }
-    }
+    const std::vector<int> order = exact_group_order(query_group, n_groups, round_end);
 
-    // the queries in sorted order: uploaded through set_queries' path, or gathered from the resident set on the device
     const float *d_q;
     const double *d_qsn;
-    if (queries) {
-        std::vector<float> sorted((size_t)nq * (size_t)dim_);
-        for (int p = 0; p < nq; ++p) memcpy(&sorted[(size_t)p * dim_], queries + (size_t)order[(size_t)p] * dim_, sizeof(float) * (size_t)dim_);
-        if (!exact_queries("exact_knn_grouped", sorted.data(), nq, &d_q, &d_qsn)) return false;
-    } else {
-        if (!x_queries_.grow((size_t)nq * pitch_, (size_t)std::max(nq, 1024) * pitch_) || (metric_ == M_COS && !x_q_sn_.grow((size_t)nq, (size_t)std::max(nq, 1024)))) return false;
-        if (!x_gperm_.grow((size_t)nq)) return false;
-        int *hp = static_cast<int *>(pinned_stage(4 * (size_t)nq));
-        if (!hp) return false;
-        memcpy(hp, order.data(), 4 * (size_t)nq);
-        HIP_OK(hipMemcpyAsync(x_gperm_, hp, 4 * (size_t)nq, hipMemcpyHostToDevice, st));
-        HIP_OK(exact_gather_queries_launch(d_queries_, metric_ == M_COS ? d_q_sn_.get() : nullptr, x_gperm_, nq, pitch_, x_queries_, x_q_sn_, st));
-        HIP_OK(hipStreamSynchronize(st)); // the pinned stage is used again below
-        d_q = x_queries_; d_qsn = metric_ == M_COS ? x_q_sn_.get() : nullptr;
-    }
+    if (!exact_sorted_queries("exact_knn_grouped", queries, nq, order, &d_q, &d_qsn)) return false;
 
     if (!x_evals_.grow(1)) return false;
     if (!ev0_.create(true) || !ev1_.create(true)) return false;
@@ -3138,6 +3268,277 @@ bool Device::exact_range_run(const float *queries, int nq, long long n_rows, flo
             s0 = s1;
         }
     }
+    return true;
+}
+
+// ---- hnswdev_exact_range_grouped: the range sink behind exact_knn_grouped's work items ------------------
+// Group lists, tile, chunks and the sorted upload are exact_knn_grouped's; capacities, the two passes, the sort limit and the host
+// sort are exact_range's.  The scan writes to segments in the CALLER's order (ExactRangeGrouped::dest), so counts, segments and
+// exact_range_sort_kernel's output need no permutation.  A query's pass-A capacity is min(the picker's, its group's members, the
+// arena): a round is a range of the caller's order whose capacities fit the arena.  The counts of pass A are exact, so a round's
+// output places are known after it; the lists that fitted are finished from pass A's arena and only the tiles that hold a query
+// whose count exceeded its capacity are scanned again (pass B), in pieces whose exact counts fit the arena.
+bool Device::exact_range_grouped(const float *queries, int nq, long long n_rows, float range, const int *row_group, long long n_row_group,
+                                 const int *query_group, int n_groups, int *out_counts)
+{
+    if (exact_range_grouped_run(queries, nq, n_rows, range, row_group, n_row_group, query_group, n_groups, out_counts)) return true;
+    xr_ids_.clear(); // a failed call keeps nothing
+    xr_d_.clear();
+    for (int i = 0; out_counts && i < nq; ++i) out_counts[i] = 0;
+    return false;
+}
+
+bool Device::exact_range_grouped_run(const float *queries, int nq, long long n_rows, float range, const int *row_group, long long n_row_group,
+                                     const int *query_group, int n_groups, int *out_counts)
+{
+    xr_ids_.clear();
+    xr_d_.clear();
+    if (nq <= 0) return true;
+    if (!out_counts || n_rows < 0) { set_dev_error("exact_range_grouped: bad argument"); return false; }
+    if (!row_group || n_row_group < 0) { set_dev_error("exact_range_grouped: row_group must not be NULL and n_row_group must be >= 0"); return false; }
+    if (!query_group) { set_dev_error("exact_range_grouped: query_group must not be NULL"); return false; }
+    if (!group_args_ok("exact_range_grouped", query_group, nq, n_groups)) return false;
+    for (int i = 0; i < nq; ++i) out_counts[i] = 0;
+    std::vector<int> gq((size_t)n_groups, 0); // queries per group
+    for (int i = 0; i < nq; ++i) gq[(size_t)query_group[i]] += 1;
+    // ids that exist and have a group: a row beyond what was uploaded is never dereferenced, whatever n_rows and n_row_group say
+    const long long n = std::min({n_rows, n_rows_hw_, n_row_group});
+    if (n <= 0) return true;
+    if (!queries && (nq > n_queries_ || tail_.n > 0)) {
+        set_dev_error("exact_range_grouped: queries == NULL needs a resident query set of at least nq rows (hnswdev_set_queries)");
+        return false;
+    }
+    if (!bind()) return false;
+    hipStream_t st = S(stream_);
+
+    std::vector<int> cnt, goff; // members of each group, where its segment starts in x_ids_
+    uint64_t listed = 0; // (not reported by this call)
+    if (!exact_group_lists("exact_range_grouped", row_group, n, n_groups, cnt, goff, &listed)) return false;
+    int max_gq = 0;
+    for (size_t g = 0; g < (size_t)n_groups; ++g)
+        if (gq[g] > 0 && cnt[g] > 0) max_gq = std::max(max_gq, gq[g]);
+    if (max_gq == 0) return true; // no query has a candidate: empty lists, no scan
+
+    // the tile (one for the call, as for lists of one key: this sink keeps none)
+    ExactPlan tp = exact_plan(max_gq, 1, 1, pitch_, num_cu_);
+    tp.lds = exact_scan_lds(tp.qtile, tp.piece, pitch_, 0);
+    if (tp.lds > 64 * 1024) { set_dev_error("exact_range_grouped: tile exceeds the LDS budget"); return false; }
+    const int qt = tp.qtile;
+    std::vector<int> gchunk((size_t)n_groups, 0), gnch((size_t)n_groups, 0); // each scan's chunks: rows per chunk, chunks per group (planned by `items` below)
+
+    const int d_arena = diag("exact_range_arena", 0), d_cap = diag("exact_range_cap", 0), d_sort = diag("exact_range_sort", 0);
+    const long long arena_max = d_arena > 0 ? d_arena : kExactRangeArena;
+    const int sort_max = d_sort > 0 ? std::min(d_sort, kExactRangeSortMax) : kExactRangeSortMax;
+    const long long pick = d_cap > 0 ? (long long)d_cap : kExactRangePickCap;
+    const auto cap_of = [&](int i) { return std::min<long long>({pick, (long long)cnt[(size_t)query_group[i]], arena_max}); };
+
+    // rounds: ranges of the caller's order whose pass-A capacities fit the arena, at most 65 536 queries each
+    std::vector<int> round_end;
+    int max_round = 0;
+    {
+        long long keys = 0;
+        int r0 = 0;
+        for (int i = 0; i < nq; ++i) {
+            const long long c = cap_of(i);
+            if (i > r0 && (keys + c > arena_max || i - r0 >= 65536)) { round_end.push_back(i); max_round = std::max(max_round, i - r0); keys = 0; r0 = i; }
+            keys += c;
+        }
+        round_end.push_back(nq);
+        max_round = std::max(max_round, nq - r0);
+    }
+    const std::vector<int> order = exact_group_order(query_group, n_groups, round_end);
+    const float *d_q;
+    const double *d_qsn;
+    if (!exact_sorted_queries("exact_range_grouped", queries, nq, order, &d_q, &d_qsn)) return false;
+
+    if (!x_rcnt_.grow((size_t)max_round) || !x_rseg_.grow((size_t)max_round + 1) || !x_rooff_.grow((size_t)max_round) || !x_evals_.grow(1)) return false;
+    if (!ev0_.create(true) || !ev1_.create(true)) return false;
+    std::vector<long long> seg((size_t)max_round + 1), ooff((size_t)max_round), obase((size_t)max_round);
+    std::vector<unsigned> cnt_a((size_t)max_round), cnt_b, cnt_fit;
+    std::vector<int> dest((size_t)max_round), slot_q, ov;
+    std::vector<ExactWorkItem> wi;
+    std::vector<unsigned long long> keys;
+    std::vector<int> t_ids;
+    std::vector<float> t_d;
+    bool launched = false;
+
+    // the work items of the round at [off, off + nr): every (tile, chunk) of every scanned group whose tile holds a query with a
+    // segment in dest.  The chunks are planned for the tiles that are scanned (first the queries of those tiles are counted per
+    // group): a repeated pass of a few tiles is cut into many chunks, not left to a few blocks that each walk a whole group.
+    const auto tile_wanted = [&](int t, int tn) {
+        for (int j = t; j < t + tn; ++j)
+            if (dest[(size_t)j] >= 0) return true;
+        return false;
+    };
+    const auto items = [&](int off, int nr) {
+        wi.clear();
+        std::vector<int> wq(gq.size(), 0); // per group the queries of the wanted tiles (a count of its own: gq stays the call's)
+        for (int pass = 0; pass < 2; ++pass) {
+            if (pass == 1) exact_group_chunks(wq, cnt, qt, num_cu_, gchunk, gnch);
+            for (int p = 0; p < nr;) {
+                const int g = query_group[order[(size_t)(off + p)]];
+                int e = p + 1;
+                while (e < nr && query_group[order[(size_t)(off + e)]] == g) ++e;
+                const int nch = gnch[(size_t)g], m = cnt[(size_t)g], chunk = gchunk[(size_t)g];
+                for (int t = p; m > 0 && t < e; t += qt) {
+                    const int tn = std::min(qt, e - t);
+                    if (!tile_wanted(t, tn)) continue;
+                    if (pass == 0) { wq[(size_t)g] += tn; continue; }
+                    for (int c = 0; c < nch; ++c) {
+                        const int lo = c * chunk; // (chunk * nch < m + chunk: no overflow of int while m is one)
+                        wi.push_back(ExactWorkItem{t, tn, goff[(size_t)g] + lo, std::min(chunk, m - lo), 0, nch, c});
+                    }
+                }
+                p = e;
+            }
+        }
+    };
+
+    // one scan of the round at [off, off + nr) with `ns` segments seg[0 .. ns], dest[0 .. nr) and the work items wi: the counts of
+    // the segments into c[0 .. ns)
+    const auto scan = [&](int off, int nr, int ns, unsigned *c) -> bool {
+        if (!x_rarena_.grow((size_t)std::max<long long>(seg[(size_t)ns], 1))) return false;
+        const size_t b_wi = sizeof(ExactWorkItem) * wi.size(), b_dest = 4 * (size_t)nr, b_seg = 8 * ((size_t)ns + 1), b_cnt = 4 * (size_t)ns;
+        char *hs = static_cast<char *>(pinned_stage(8 + b_seg + b_wi + b_dest + b_cnt));
+        if (!hs || !x_gwork_.grow(b_wi + b_dest)) return false;
+        unsigned long long *h_ev = reinterpret_cast<unsigned long long *>(hs);
+        char *h_seg = hs + 8, *h_tab = h_seg + b_seg, *h_cnt = h_tab + b_wi + b_dest;
+        memcpy(h_seg, seg.data(), b_seg);
+        memcpy(h_tab, wi.data(), b_wi);
+        memcpy(h_tab + b_wi, dest.data(), b_dest);
+        ExactScanArgs a;
+        a.rows = d_rows_; a.row_sn = d_row_sn_;
+        a.queries = d_q + (size_t)off * pitch_;
+        a.q_sn = d_qsn ? d_qsn + off : nullptr;
+        a.dim = pitch_; a.ids = x_ids_; a.m = 0; a.chunk = 0; a.nq = nr; a.qtile = qt; a.piece = tp.piece; a.k = 0;
+        a.lists = nullptr; a.n_chunks = 0; a.evals = x_evals_;
+        ExactRangeGrouped sink;
+        sink.range = range; sink.counts = x_rcnt_; sink.seg_off = x_rseg_; sink.arena = x_rarena_;
+        sink.items = reinterpret_cast<const ExactWorkItem *>(x_gwork_.get());
+        sink.dest = reinterpret_cast<const int *>(x_gwork_.get() + b_wi);
+        const bool timed = profiling_;
+        HIP_OK(hipMemcpyAsync(x_rseg_, h_seg, b_seg, hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemcpyAsync(x_gwork_, h_tab, b_wi + b_dest, hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemsetAsync(x_rcnt_, 0, b_cnt, st));
+        HIP_OK(hipMemsetAsync(x_evals_, 0, sizeof(unsigned long long), st));
+        if (timed) HIP_OK(hipEventRecord(E(ev0_), st));
+        hipError_t e = hipSuccess;
+        with_metric(metric_, [&](auto mt) { e = exact_range_grouped_scan_launch<mt>(a, sink, (unsigned)wi.size(), tp.lds, st); });
+        HIP_OK(e);
+        if (timed) HIP_OK(hipEventRecord(E(ev1_), st));
+        HIP_OK(hipMemcpyAsync(h_cnt, x_rcnt_, b_cnt, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(h_ev, x_evals_, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+        memcpy(c, h_cnt, b_cnt);
+        // (the flat scan's family, as exact_range counts: a repeated pass counts its pairs again, the unwanted queries of its tiles included)
+        stats_.exact_launches += 1; stats_.exact_evals += *h_ev;
+        launched = true;
+        if (timed) {
+            float ms = 0.f;
+            HIP_OK(hipEventElapsedTime(&ms, E(ev0_), E(ev1_)));
+            stats_.exact_kernel_ms += ms; stats_.exact_timed_launches += 1; stats_.exact_timed_evals += *h_ev;
+        }
+        return true;
+    };
+
+    // the lists of segments [0, ns), c[s] keys each (0: nothing to do for that segment), every one inside its segment: ordered and
+    // written to the call's results.  Segment s is query sq[s] of the round (nullptr: s itself), whose list starts at base + obase[].
+    const auto finish = [&](int ns, const unsigned *c, const int *sq, size_t base, bool counts_on_device) -> bool {
+        size_t on_dev = 0;
+        int n_dev = 0;
+        for (int s = 0; s < ns; ++s) {
+            ooff[(size_t)s] = (long long)on_dev;
+            if (c[s] > 0 && c[s] <= (unsigned)sort_max) { on_dev += c[s]; ++n_dev; }
+        }
+        if (n_dev > 0) {
+            if (!x_rout_.grow(2 * on_dev)) return false;
+            char *hs = static_cast<char *>(pinned_stage(12 * (size_t)ns));
+            if (!hs) return false;
+            memcpy(hs, ooff.data(), 8 * (size_t)ns);
+            HIP_OK(hipMemcpyAsync(x_rooff_, hs, 8 * (size_t)ns, hipMemcpyHostToDevice, st));
+            if (!counts_on_device) { // the kernel orders what counts[] says: the segments that are not to be read get 0
+                memcpy(hs + 8 * (size_t)ns, c, 4 * (size_t)ns);
+                HIP_OK(hipMemcpyAsync(x_rcnt_, hs + 8 * (size_t)ns, 4 * (size_t)ns, hipMemcpyHostToDevice, st));
+            }
+            ExactRangeSortArgs sa;
+            sa.arena = x_rarena_; sa.seg_off = x_rseg_; sa.counts = x_rcnt_; sa.out_off = x_rooff_;
+            sa.out_ids = x_rout_; sa.out_d = reinterpret_cast<float *>(x_rout_.get() + on_dev); sa.sort_max = sort_max;
+            HIP_OK(exact_range_sort_launch(sa, ns, st));
+            HIP_OK(hipStreamSynchronize(st)); // (the pinned stage is used again by the copies)
+            t_ids.resize(on_dev);
+            t_d.resize(on_dev);
+            if (!exact_copy_out(t_ids.data(), sa.out_ids, 4 * on_dev) || !exact_copy_out(t_d.data(), sa.out_d, 4 * on_dev)) return false;
+        }
+        for (int s = 0; s < ns; ++s) {
+            const size_t cs = c[s], at = base + (size_t)obase[(size_t)(sq ? sq[s] : s)];
+            if (cs > 0 && cs <= (size_t)sort_max) {
+                memcpy(xr_ids_.data() + at, t_ids.data() + ooff[(size_t)s], 4 * cs);
+                memcpy(xr_d_.data() + at, t_d.data() + ooff[(size_t)s], 4 * cs);
+                if (cs >= 2) xrg_info_[1] += 1;
+            } else if (cs > 0) {
+                keys.resize(cs);
+                if (!exact_copy_out(keys.data(), x_rarena_.get() + seg[(size_t)s], 8 * cs)) return false;
+                std::sort(keys.begin(), keys.end());
+                for (size_t j = 0; j < cs; ++j) { xr_ids_[at + j] = (int)(uint32_t)keys[j]; xr_d_[at + j] = exact_host_key_dist(keys[j]); }
+                xrg_info_[2] += 1;
+            }
+        }
+        return true;
+    };
+
+    int off = 0;
+    for (const int r1 : round_end) {
+        const int nr = r1 - off;
+        // pass A: a segment per query at its place in the caller's order
+        seg[0] = 0;
+        for (int i = 0; i < nr; ++i) seg[(size_t)i + 1] = seg[(size_t)i] + cap_of(off + i);
+        for (int p = 0; p < nr; ++p) dest[(size_t)p] = order[(size_t)(off + p)] - off;
+        items(off, nr);
+        if (wi.empty()) { off = r1; continue; } // no query of this round has a candidate
+        if (!scan(off, nr, nr, cnt_a.data())) return false;
+        const size_t base = xr_ids_.size();
+        size_t total = 0;
+        ov.clear();
+        cnt_fit.assign(cnt_a.begin(), cnt_a.begin() + nr);
+        for (int i = 0; i < nr; ++i) {
+            obase[(size_t)i] = (long long)total;
+            total += cnt_a[(size_t)i];
+            out_counts[off + i] = (int)cnt_a[(size_t)i];
+            if ((long long)cnt_a[(size_t)i] > seg[(size_t)i + 1] - seg[(size_t)i]) { ov.push_back(i); cnt_fit[(size_t)i] = 0; }
+        }
+        xr_ids_.resize(base + total);
+        xr_d_.resize(base + total);
+        if (!finish(nr, cnt_fit.data(), nullptr, base, ov.empty())) return false;
+        // pass B: the queries whose count exceeded its capacity, in pieces whose exact counts fit the arena, each with segments of
+        // exactly its counts; the other queries of their tiles are measured again and their keys dropped
+        for (size_t s0 = 0; s0 < ov.size();) {
+            size_t s1 = s0;
+            seg[0] = 0;
+            while (s1 < ov.size() && seg[s1 - s0] + (long long)cnt_a[(size_t)ov[s1]] <= arena_max) {
+                seg[s1 - s0 + 1] = seg[s1 - s0] + (long long)cnt_a[(size_t)ov[s1]];
+                ++s1;
+            }
+            if (s1 == s0) {
+                set_dev_error("exact_range_grouped: a query has " + std::to_string(cnt_a[(size_t)ov[s0]]) + " results within the range, above the arena's limit of " +
+                              std::to_string(arena_max) + " entries per call round");
+                return false;
+            }
+            const int ns = (int)(s1 - s0);
+            slot_q.assign((size_t)nr, -1); // query of the round -> its segment in this piece
+            for (int s = 0; s < ns; ++s) slot_q[(size_t)ov[s0 + (size_t)s]] = s;
+            for (int p = 0; p < nr; ++p) dest[(size_t)p] = slot_q[(size_t)(order[(size_t)(off + p)] - off)];
+            items(off, nr);
+            xrg_info_[3] += 1;
+            cnt_b.resize((size_t)ns);
+            if (!scan(off, nr, ns, cnt_b.data())) return false;
+            for (int s = 0; s < ns; ++s)
+                if (cnt_b[(size_t)s] != cnt_a[(size_t)ov[s0 + (size_t)s]]) { set_dev_error("exact_range_grouped: the repeated scan counted differently"); return false; }
+            if (!finish(ns, cnt_b.data(), ov.data() + s0, base, true)) return false;
+            s0 = s1;
+        }
+        off = r1;
+    }
+    if (launched) xrg_info_[0] += 1;
     return true;
 }
 
@@ -3772,6 +4173,19 @@ DEV_API int hnswdev_range_search_at_layer(void *ctx, const float *queries, int n
     if (allow_bits && nbits < 0) { hnsw::set_dev_error("hnswdev_range_search_at_layer: nbits must be >= 0"); return -1; }
     return d->range_search_filtered(queries, nq, entry_point, range, allow_bits, allow_bits ? nbits : 0, out_counts, out_flags, layer) ? 0 : -1;
 }
+DEV_API int hnswdev_range_search_grouped(void *ctx, const float *queries, int nq, int entry_point, float range, int layer, const int *row_group,
+                                         long long n_row_group, const int *query_group, int n_groups, int *out_counts, int *out_flags)
+{
+    CTX_OR_FAIL();
+    return d->range_search_grouped(queries, nq, entry_point, range, row_group, n_row_group, query_group, n_groups, out_counts, out_flags, layer) ? 0 : -1;
+}
+DEV_API int hnswdev_range_grouped_info(void *ctx, uint64_t out[4])
+{
+    CTX_OR_FAIL();
+    if (!out) return -1;
+    d->range_grouped_info(out);
+    return 0;
+}
 DEV_API int hnswdev_multilayer_search(void *ctx, const float *queries, int nq, int entry_point, int k, int max_layer, int min_layer, int layers_cap,
                                       int *out_ids, float *out_dists, int *out_flags)
 {
@@ -3809,6 +4223,19 @@ DEV_API int hnswdev_exact_grouped_info(void *ctx, uint64_t out[4])
     CTX_OR_FAIL();
     if (!out) return -1;
     d->exact_grouped_info(out);
+    return 0;
+}
+DEV_API int hnswdev_exact_range_grouped(void *ctx, const float *queries, int nq, long long n_rows, float range, const int *row_group, long long n_row_group,
+                                        const int *query_group, int n_groups, int *out_counts)
+{
+    CTX_OR_FAIL();
+    return d->exact_range_grouped(queries, nq, n_rows, range, row_group, n_row_group, query_group, n_groups, out_counts) ? 0 : -1;
+}
+DEV_API int hnswdev_exact_range_grouped_info(void *ctx, uint64_t out[4])
+{
+    CTX_OR_FAIL();
+    if (!out) return -1;
+    d->exact_range_grouped_info(out);
     return 0;
 }
 DEV_API int hnswdev_exact_grouped_list_ms(void *ctx, double *out_ms)

@@ -14,6 +14,9 @@
 //   exact_gather_queries_kernel                 the resident queries in the call's sorted order (queries == NULL)
 //   exact_scan_kernel<M, ExactTopKGrouped>      a block = one work item: a tile of one group's queries x a chunk of that group's list
 //   exact_merge_grouped_kernel                  one wave per query: its chunks' lists -> the final k at the query's original row
+// and hnswdev_exact_range_grouped: the range sink behind the same work items.
+//   exact_scan_kernel<M, ExactRangeGrouped>     a block = one work item; the keys within the range go to the segment that a table names for the
+//                                               query -- its place in the caller's order -- so exact_range_sort_kernel runs as it is
 // The kernels are compiled in the exact_<metric> units (exact_unit.hip, HNSW_EXACT_UNIT) and reached through the launchers declared here, so
 // that device_backend.hip holds none of their code.
 #pragma once
@@ -94,6 +97,21 @@ struct ExactTopKGrouped {
     static constexpr bool kGrouped = true;
     const ExactWorkItem *items;
 };
+// ExactRangeGrouped: ExactRange's segments behind ExactTopKGrouped's work items (list0, n_chunks and slot of an item are not read).
+// Query q of the round's sorted order owns segment dest[q]: counts[dest[q]] and arena[seg_off[dest[q]], seg_off[dest[q] + 1]).  In a
+// first pass dest[q] is the query's place in the caller's order, so counts, segments and the ordered lists are in that order and
+// nothing is permuted afterwards; in a repeated pass it numbers the queries that are scanned again and is -1 for the others of a
+// tile, whose keys are dropped.
+struct ExactRangeGrouped {
+    static constexpr bool kRange = true;
+    static constexpr bool kGrouped = true;
+    float range;
+    unsigned *counts;              // [segments]
+    const long long *seg_off;      // [segments + 1]
+    unsigned long long *arena;
+    const ExactWorkItem *items;
+    const int *dest;               // [nq of the round, sorted order]: the query's segment, or -1
+};
 // what exact_merge_grouped_kernel reads per query of the round (in sorted order)
 struct ExactMergeItem {
     long long list0;     // its first list
@@ -118,6 +136,8 @@ hipError_t exact_merge_launch(const unsigned long long *lists, int n_chunks, int
 hipError_t exact_range_sort_launch(const ExactRangeSortArgs &a, int nq, hipStream_t st);
 template <int METRIC>
 hipError_t exact_grouped_scan_launch(const ExactScanArgs &a, const ExactTopKGrouped &sink, unsigned n_items, size_t lds, hipStream_t st);
+template <int METRIC>
+hipError_t exact_range_grouped_scan_launch(const ExactScanArgs &a, const ExactRangeGrouped &sink, unsigned n_items, size_t lds, hipStream_t st);
 // row_group[0, n) -> counts[g] (zeroed here), offsets[g] (exclusive prefix), ids: group g's members in [offsets[g], offsets[g] + counts[g]),
 // in no particular order; values outside [0, n_groups) are in no group.  cursors: n_groups ints of scratch.
 hipError_t exact_group_lists_launch(const int *row_group, long long n, int n_groups, int *counts, int *offsets, int *cursors, int *ids, hipStream_t st);
@@ -373,19 +393,41 @@ __global__ void __launch_bounds__(kExactThreads) exact_scan_kernel(const ExactSc
                     }
                 }
                 if (__syncthreads_or(offered)) {
-                    const int cnt = pend_cnt[wave]; // wave w: query qsub + w, a real query when anything was offered to it
-                    if (cnt > 0) {
-                        const long long qg = q0 + qsub + wave;
-                        unsigned first = 0;
-                        if (lane == 0) first = atomicAdd(&sink.counts[qg], (unsigned)cnt); // one global atomic per (query, step)
-                        first = __shfl(first, 0, 64);
-                        const long long off = sink.seg_off[qg], cap = sink.seg_off[qg + 1] - off;
-                        for (int i = lane; i < cnt; i += 64) {
-                            const long long slot = (long long)first + i;
-                            if (slot < cap) sink.arena[off + slot] = pend[wave * kExactIterRows + i];
+                    if constexpr (SINK::kGrouped) {
+                        // wave w: query qsub + w of the item.  Everything but the lane's place is the same for the whole wave and is
+                        // kept in scalar registers.  seg: the query's segment; -1: its keys are not wanted.  (A second copy of the
+                        // flush below, to be kept in step with it: addressing the segment through the branch-free form of both costs
+                        // 129 VGPRs against 127 here, 3 waves per SIMD against 4 -- DESIGN.md 3.23.)
+                        const int wv = __builtin_amdgcn_readfirstlane(wave);
+                        const int cnt = __builtin_amdgcn_readfirstlane(pend_cnt[wv]);
+                        if (cnt > 0) {
+                            const int seg = __builtin_amdgcn_readfirstlane(sink.dest[q0 + qsub + wv]);
+                            if (seg >= 0) {
+                                unsigned first = 0;
+                                if (lane == 0) first = atomicAdd(&sink.counts[seg], (unsigned)cnt); // one global atomic per (query, step)
+                                first = __builtin_amdgcn_readfirstlane(first); // (all 64 lanes are here: the first is lane 0)
+                                const long long off = sink.seg_off[seg], room = sink.seg_off[seg + 1] - off - (long long)first;
+                                for (int i = lane; i < cnt; i += 64)
+                                    if (i < room) sink.arena[off + first + i] = pend[wv * kExactIterRows + i];
+                            }
+                            wave_lds_sync();
+                            if (lane == 0) pend_cnt[wv] = 0;
                         }
-                        wave_lds_sync();
-                        if (lane == 0) pend_cnt[wave] = 0;
+                    } else {
+                        const int cnt = pend_cnt[wave]; // wave w: query qsub + w, a real query when anything was offered to it
+                        if (cnt > 0) {
+                            const long long qg = q0 + qsub + wave;
+                            unsigned first = 0;
+                            if (lane == 0) first = atomicAdd(&sink.counts[qg], (unsigned)cnt); // one global atomic per (query, step)
+                            first = __shfl(first, 0, 64);
+                            const long long off = sink.seg_off[qg], cap = sink.seg_off[qg + 1] - off;
+                            for (int i = lane; i < cnt; i += 64) {
+                                const long long slot = (long long)first + i;
+                                if (slot < cap) sink.arena[off + slot] = pend[wave * kExactIterRows + i];
+                            }
+                            wave_lds_sync();
+                            if (lane == 0) pend_cnt[wave] = 0;
+                        }
                     }
                     __syncthreads();
                 }
@@ -457,6 +499,12 @@ template <int METRIC>
 hipError_t exact_grouped_scan_launch(const ExactScanArgs &a, const ExactTopKGrouped &sink, unsigned n_items, size_t lds, hipStream_t st)
 {
     hipLaunchKernelGGL((exact_scan_kernel<METRIC, ExactTopKGrouped>), dim3(n_items), dim3(kExactThreads), lds, st, a, sink);
+    return hipGetLastError();
+}
+template <int METRIC>
+hipError_t exact_range_grouped_scan_launch(const ExactScanArgs &a, const ExactRangeGrouped &sink, unsigned n_items, size_t lds, hipStream_t st)
+{
+    hipLaunchKernelGGL((exact_scan_kernel<METRIC, ExactRangeGrouped>), dim3(n_items), dim3(kExactThreads), lds, st, a, sink);
     return hipGetLastError();
 }
 

@@ -167,6 +167,64 @@ range_sort_filtered_kernel(ND *__restrict__ arena, const unsigned long long *__r
     }
 }
 
+// range_sort_filtered_kernel for a RangeQuery with a group per query (range_query_grouped): an entry is allowed
+// when label[id] == group_of[job] (ids >= n_label are in no group).  Everything else -- the partition, bit 31 on the disallowed
+// entries in LDS, res[job], the tie test among the allowed entries, host_all, the one store point -- is that kernel's, line by
+// line, and the two must be kept in step.  What it leaves is what range_replay_filtered_kernel and range_pack_kernel read: they
+// know the filter only as "entry index < res[job]" and serve both.  (A kernel of its own, not a predicate type: the filtered
+// kernel keeps its name and its code.)
+__global__ void __launch_bounds__(64)
+range_sort_grouped_kernel(ND *__restrict__ arena, const unsigned long long *__restrict__ off, const int *__restrict__ cnt, const int *__restrict__ flag,
+                          int njobs, int *__restrict__ state, int *__restrict__ tied, int *__restrict__ job_counter, const int *__restrict__ label,
+                          long long n_label, const int *__restrict__ group_of, int *__restrict__ res, int host_all)
+{
+    __shared__ int2 e[kRangeSortMax];
+    const int lane = threadIdx.x;
+    for (;;) {
+        int job = 0;
+        if (lane == 0) job = atomicAdd(job_counter, 1);
+        job = __builtin_amdgcn_readfirstlane(job);
+        if (job >= njobs) break;
+        const int m = __builtin_amdgcn_readfirstlane(cnt[job]);
+        const int grp = __builtin_amdgcn_readfirstlane(group_of[job]);
+        int st = kRangeFinal;
+        int ma = 0; // allowed entries
+        if (__builtin_amdgcn_readfirstlane(flag[job]) == 0 && m > 0) {
+            ND *a = arena + off[job];
+            const bool fits = m <= kRangeSortMax;
+            bool unsafe = false;
+            int first = m; // the first allowed entry
+            wave_sync();
+            for (int i0 = 0; i0 < m; i0 += 64) {
+                const int i = i0 + lane;
+                bool ok = false;
+                if (i < m) {
+                    const ND v = a[i];
+                    ok = v.id >= 0 && (long long)v.id < n_label && label[v.id] == grp;
+                    unsafe = unsafe || key_unsafe(v.dist);
+                    if (fits) e[i] = make_int2(ok ? v.id : (int)((unsigned)v.id | 0x80000000u), (int)f2key(v.dist));
+                }
+                const unsigned long long b = __ballot(ok);
+                if (first == m && b != 0ull) first = i0 + (int)__builtin_ctzll(b);
+                ma += __popcll(b);
+            }
+            wave_sync();
+            if (host_all) st = kRangeHostSort; // left as found
+            else if (ma <= 1) {
+                if (ma == 1 && first > 0 && lane == 0) a[0] = a[first];
+            } else if (!fits || __ballot(unsafe) != 0ull) st = kRangeHostSort; // -0 anywhere: the candidate heap's order is float.CompareTo's
+            else st = rank_partition(e, m, ma, a, lane) ? kRangeTied : kRangeFinal;
+        }
+        wave_sync();
+        if (lane == 0) { // (one store point: see range_sort_kernel)
+            state[job] = st;
+            res[job] = ma;
+            if (st == kRangeTied) tied[1 + atomicAdd(&tied[0], 1)] = job;
+        }
+        __builtin_amdgcn_wave_barrier();
+    }
+}
+
 // LDS of one replaying wave: entries (id, key) in ascending order, an id -> entry hash, visited bits, the two heaps.
 struct RangeReplayLds {
     int2 e[kRangeSortMax];                      // the list, ascending (as range_sort_kernel left it)

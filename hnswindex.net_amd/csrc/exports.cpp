@@ -200,9 +200,10 @@ API int hnsw_mi355x_knn_query_grouped(void *handle, const float *vectors, int co
 
 API void hnsw_free_results(void **ids_array, void **dists_array, int count);
 
-// hnsw_range_query and its filtered sibling: `name` for the errors, allow (none: no filter)
+// hnsw_range_query and its filtered and grouped siblings: `name` for the errors, allow (none: no filter), or grp: a group per query
+struct RangeGroupArgs { const int *row_group; long long n_row_group; const int *query_group; int n_groups; };
 static int range_query_export(void *handle, const float *vectors, int count, int dim, float range, hnsw::AllowBits allow, void **out_ids,
-                              void **out_dists, int *counts, const char *name, int layer = 0)
+                              void **out_dists, int *counts, const char *name, int layer = 0, const RangeGroupArgs *grp = nullptr)
 {
     if (!vectors || !out_ids || !out_dists || !counts || dim <= 0) { set_error(std::string("System.ArgumentNullException: ") + name); return -1; }
     for (int i = 0; i < count; ++i) { out_ids[i] = nullptr; out_dists[i] = nullptr; counts[i] = 0; }
@@ -210,7 +211,10 @@ static int range_query_export(void *handle, const float *vectors, int count, int
     std::vector<std::vector<hnsw::NodeDist>> res;
     {
         LOCK_INDEX(handle);
-        if (static_cast<HnswIndex *>(handle)->range_query(vectors, count, dim, range, res, err, allow, layer) < 0) { set_error(err); return -1; }
+        HnswIndex *ix = static_cast<HnswIndex *>(handle);
+        const int rc = grp ? ix->range_query_grouped(vectors, count, dim, range, layer, grp->row_group, grp->n_row_group, grp->query_group, grp->n_groups, res, err)
+                           : ix->range_query(vectors, count, dim, range, res, err, allow, layer);
+        if (rc < 0) { set_error(err); return -1; }
     }
     const bool trace = hnsw::diag("trace", 0) != 0;
     const auto t_out0 = std::chrono::steady_clock::now();
@@ -270,6 +274,51 @@ API int hnsw_mi355x_range_query_filtered(void *handle, const float *vectors, int
                               "hnsw_mi355x_range_query_filtered");
 }
 
+// hnsw_mi355x_range_query_at_layer with a group filter per query: query i's list is what that call returns for it
+// with the ids j < n_row_group, row_group[j] == query_group[i] as the allow-set, the order among equal distances and the empty-heap
+// failure (-1, every array NULL, every count 0) included.  hnsw_mi355x_knn_query_grouped's group arguments.
+API int hnsw_mi355x_range_query_grouped(void *handle, const float *vectors, int count, int dim, float range, int layer, const int *row_group,
+                                        long long n_row_group, const int *query_group, int n_groups, void **out_ids, void **out_dists, int *counts)
+{
+    if (!handle) return 0;
+    if (count <= 0) return 0;
+    if (!vectors || !out_ids || !out_dists || !counts || dim <= 0) { set_error("System.ArgumentNullException: hnsw_mi355x_range_query_grouped"); return -1; }
+    for (int i = 0; i < count; ++i) { out_ids[i] = nullptr; out_dists[i] = nullptr; counts[i] = 0; }
+    if (!query_group) { set_error("System.ArgumentNullException: hnsw_mi355x_range_query_grouped: query_group"); return -1; }
+    if (!row_group || n_row_group < 0) {
+        set_error("System.ArgumentException: hnsw_mi355x_range_query_grouped: row_group must not be NULL and n_row_group must be >= 0");
+        return -1;
+    }
+    const RangeGroupArgs grp{row_group, n_row_group, query_group, n_groups};
+    return range_query_export(handle, vectors, count, dim, range, hnsw::AllowBits{}, out_ids, out_dists, counts, "hnsw_mi355x_range_query_grouped", layer, &grp);
+}
+
+// The lists of a flat range scan, concatenated in query order in ids / ds, handed out as hnsw_range_query hands its lists out: a
+// malloc'ed pair per query with results.  Out of memory: everything released, every count 0, -1.
+static int exact_range_hand_out(const char *name, int count, int *counts, const std::vector<int> &ids, const std::vector<float> &ds, void **out_ids, void **out_dists)
+{
+    size_t at = 0;
+    for (int i = 0; i < count; ++i) {
+        const size_t n = (size_t)counts[i];
+        if (n == 0) continue;
+        int *pi = static_cast<int *>(std::malloc(sizeof(int) * n));
+        float *pd = static_cast<float *>(std::malloc(sizeof(float) * n));
+        if (!pi || !pd) {
+            std::free(pi); std::free(pd);
+            hnsw_free_results(out_ids, out_dists, count);
+            for (int j = 0; j < count; ++j) counts[j] = 0;
+            set_error(std::string("System.OutOfMemoryException: ") + name);
+            return -1;
+        }
+        std::memcpy(pi, ids.data() + at, sizeof(int) * n);
+        std::memcpy(pd, ds.data() + at, sizeof(float) * n);
+        out_ids[i] = pi;
+        out_dists[i] = pd;
+        at += n;
+    }
+    return 0;
+}
+
 // Every live, allowed id within `range` per query, ascending by (distance, id): the flat scan with the range sink.
 // hnsw_range_query's allocation contract (hnsw_free_results); exclusive, like the other scan.
 API int hnsw_mi355x_exact_range_query(void *handle, const float *vectors, int count, int dim, float range, const uint32_t *allow_bits, long long nbits,
@@ -291,26 +340,35 @@ API int hnsw_mi355x_exact_range_query(void *handle, const float *vectors, int co
             return -1;
         }
     }
-    size_t at = 0;
-    for (int i = 0; i < count; ++i) {
-        const size_t n = (size_t)counts[i];
-        if (n == 0) continue;
-        int *pi = static_cast<int *>(std::malloc(sizeof(int) * n));
-        float *pd = static_cast<float *>(std::malloc(sizeof(float) * n));
-        if (!pi || !pd) {
-            std::free(pi); std::free(pd);
-            hnsw_free_results(out_ids, out_dists, count);
-            for (int j = 0; j < count; ++j) counts[j] = 0;
-            set_error("System.OutOfMemoryException: hnsw_mi355x_exact_range_query");
+    return exact_range_hand_out("hnsw_mi355x_exact_range_query", count, counts, ids, ds, out_ids, out_dists);
+}
+
+// hnsw_mi355x_exact_range_query with a candidate group per query: that call's lists and allocation contract,
+// hnsw_mi355x_exact_knn_query_grouped's group arguments.
+API int hnsw_mi355x_exact_range_query_grouped(void *handle, const float *vectors, int count, int dim, float range, const int *row_group, long long n_row_group,
+                                              const int *query_group, int n_groups, void **out_ids, void **out_dists, int *counts)
+{
+    if (!handle) return 0;
+    if (count <= 0) return 0;
+    if (!vectors || !out_ids || !out_dists || !counts || dim <= 0) { set_error("System.ArgumentNullException: hnsw_mi355x_exact_range_query_grouped"); return -1; }
+    for (int i = 0; i < count; ++i) { out_ids[i] = nullptr; out_dists[i] = nullptr; counts[i] = 0; }
+    if (!query_group) { set_error("System.ArgumentNullException: hnsw_mi355x_exact_range_query_grouped: query_group"); return -1; }
+    if (!row_group || n_row_group < 0) {
+        set_error("System.ArgumentException: hnsw_mi355x_exact_range_query_grouped: row_group must not be NULL and n_row_group must be >= 0");
+        return -1;
+    }
+    std::string err;
+    std::vector<int> ids;
+    std::vector<float> ds;
+    {
+        LOCK_INDEX(handle);
+        if (static_cast<HnswIndex *>(handle)->exact_range_query_grouped(vectors, count, dim, range, row_group, n_row_group, query_group, n_groups, counts, ids, ds, err) < 0) {
+            for (int i = 0; i < count; ++i) counts[i] = 0;
+            set_error(err);
             return -1;
         }
-        std::memcpy(pi, ids.data() + at, sizeof(int) * n);
-        std::memcpy(pd, ds.data() + at, sizeof(float) * n);
-        out_ids[i] = pi;
-        out_dists[i] = pd;
-        at += n;
     }
-    return 0;
+    return exact_range_hand_out("hnsw_mi355x_exact_range_query_grouped", count, counts, ids, ds, out_ids, out_dists);
 }
 
 // KnnQuery / RangeQuery with the reference's `layer` argument (BatchKnnQuery / BatchRangeQuery(queries, ., filterFnc, layer),
@@ -487,11 +545,25 @@ API int hnsw_mi355x_exact_range_info(void *h, uint64_t out[4])
     static_cast<HnswIndex *>(h)->exact_range_info(out);
     return 0;
 }
+API int hnsw_mi355x_exact_range_grouped_info(void *h, uint64_t out[4])
+{
+    if (!h || !out) return -1;
+    LOCK_INDEX(h);
+    static_cast<HnswIndex *>(h)->exact_range_grouped_info(out);
+    return 0;
+}
 API int hnsw_mi355x_exact_grouped_info(void *h, uint64_t out[4])
 {
     if (!h || !out) return -1;
     LOCK_INDEX(h);
     static_cast<HnswIndex *>(h)->exact_grouped_info(out);
+    return 0;
+}
+API int hnsw_mi355x_range_grouped_info(void *h, uint64_t out[4])
+{
+    if (!h || !out) return -1;
+    LOCK_INDEX(h);
+    static_cast<HnswIndex *>(h)->range_grouped_info(out);
     return 0;
 }
 API int hnsw_mi355x_knn_grouped_info(void *h, uint64_t out[4])

@@ -256,7 +256,7 @@ struct RangeJob : Job {
     std::vector<NodeDist> *out;
     Descent desc;
     int stage = 0;
-    AllowBits allow;         // filterFnc as a bitset (none: everything allowed)
+    AllowPred allow;         // filterFnc: a bitset or a group label (none: everything allowed)
     int layer = 0;           // RangeQuery's `layer`
     bool heap_empty = false; // InvalidOperationException("Heap is empty") (BinaryHeap.cs:56)
 
@@ -1850,6 +1850,29 @@ int HnswIndex::exact_range_query(const float *queries, int count, int dim, float
     return 0;
 }
 
+// The range sink with a candidate group per query.  The labels go to the device as live_labels leaves them.
+int HnswIndex::exact_range_query_grouped(const float *queries, int count, int dim, float range, const int *row_group, long long n_row_group,
+                                         const int *query_group, int n_groups, int *counts, std::vector<int> &ids, std::vector<float> &dists, std::string &err)
+{
+    ids.clear();
+    dists.clear();
+    if (count <= 0) return 0;
+    for (int i = 0; i < count; ++i) counts[i] = 0;
+    if (failed(err)) return -1;
+    if (!group_args_ok("hnsw_mi355x_exact_range_query_grouped", query_group, count, n_groups, err)) return -1;
+    if (graph_.count <= 0) return 0;
+    if (!ensure_dim(dim, err)) return -1;
+    const long long length = graph_.length;
+    std::vector<int> live;
+    if (live_labels(row_group, n_row_group, live) && n_row_group == 0) return 0; // vacant slots and no label: no candidate
+    // (the scan stages its queries in a buffer of its own: the resident set, sharded or not, stays what it was)
+    if (!dev_->exact_range_grouped(queries, count, length, range, row_group, n_row_group, query_group, n_groups, counts)) { err = get_dev_error(); return -1; }
+    ids.resize(dev_->exact_range_total());
+    dists.resize(ids.size());
+    if (!dev_->exact_range_results(ids.data(), dists.data())) { err = get_dev_error(); return -1; }
+    return 0;
+}
+
 // GetInfo / GetConnectedComponentCounts (HNSWIndex.cs:192-205) on the graph mirror, a layer at a time.  The live
 // set goes to the device as exact_candidates builds it -- none while no slot is vacant.  Always on the device, on the primary context.
 int HnswIndex::get_info(hnsw_mi355x_layer_info *out, int cap, std::string &err)
@@ -2252,7 +2275,7 @@ int HnswIndex::knn_query_resident(int k, int *out_ids, float *out_dists, std::st
 
 // Host lock-step range search for the queries listed in `which` (nullptr: all `count` queries).
 int HnswIndex::range_query_lockstep(const int *which, int count, float range, std::vector<std::vector<NodeDist>> &out, std::string &err,
-                                    AllowBits allow, int layer)
+                                    AllowBits allow, int layer, const RangeGroupSpec *grp)
 {
     if (!refresh_host_lists(err)) return -1;
     RangeSource src;
@@ -2265,7 +2288,7 @@ int HnswIndex::range_query_lockstep(const int *which, int count, float range, st
         j.qi = qi;
         j.range = range;
         j.out = &out[(size_t)qi];
-        j.allow = allow;
+        j.allow = grp ? grp->of(qi) : AllowPred{allow}; // (grouped: the label predicate of this query's group)
         j.layer = layer;
     }
     if (!engine()->run(src, count)) { err = get_dev_error(); return -1; }
@@ -2279,16 +2302,31 @@ int HnswIndex::range_query_lockstep(const int *which, int count, float range, st
 // distance, and for a query holding such a pair the heaps are replayed on the host from the known distances.
 // With an allow-set the device hands back each list either final or as its closure (Device::range_batch); closures are
 // partitioned by the filter, sorted and, where allowed results tie or range < 0, replayed (finish_filtered_range).
-int HnswIndex::range_query_device(int count, float range, std::vector<std::vector<NodeDist>> &out, std::string &err, AllowBits allow, int layer)
+// grp (range_query_grouped): the jobs are the queries of grp->run, each filtered by its group's label predicate; job i answers
+// query qi(i), and everything below indexes the device's results by job and `out` by query.
+int HnswIndex::range_query_device(int n_queries, float range, std::vector<std::vector<NodeDist>> &out, std::string &err, AllowBits allow, int layer,
+                                  const RangeGroupSpec *grp)
 {
     if (!sync_graph(err)) return -1;
+    const int count = grp ? (int)grp->run->size() : n_queries; // jobs
+    const auto qi = [&](size_t job) { return grp ? (*grp->run)[job] : (int)job; };
     std::vector<SearchJob> jobs((size_t)count);
     const int ep = graph_.entry, top = graph_.top_layer();
-    for (int i = 0; i < count; ++i) jobs[(size_t)i] = SearchJob{i, ep, top, layer, -1};
+    for (int i = 0; i < count; ++i) jobs[(size_t)i] = SearchJob{qi((size_t)i), ep, top, layer, -1};
     Device::RangeResults r;
     g_pt.rq_queries += count;
-    const bool filtered = allow.bits != nullptr;
-    { Tick t(g_pt.rq_batch); if (!dev_->range_batch(jobs.data(), count, range, &r, allow.bits, allow.n)) { err = get_dev_error(); return -1; } }
+    const bool filtered = allow.bits != nullptr || grp != nullptr;
+    std::vector<int> group_of;
+    Device::RangeGroups dev_grp;
+    if (grp) {
+        group_of.resize((size_t)count);
+        for (int i = 0; i < count; ++i) group_of[(size_t)i] = grp->query_group[qi((size_t)i)];
+        dev_grp.label = grp->label;
+        dev_grp.n_label = grp->n_label;
+        dev_grp.group_of = group_of.data();
+        dev_grp.skipped = grp->skipped;
+    }
+    { Tick t(g_pt.rq_batch); if (!dev_->range_batch(jobs.data(), count, range, &r, allow.bits, allow.n, grp ? &dev_grp : nullptr)) { err = get_dev_error(); return -1; } }
     // host threads over the queries: sort each result list; a list holding two equal distances is replayed instead
     auto parallel_for = [&](size_t n, size_t grain, const std::function<void(size_t, size_t)> &body) {
         std::atomic<size_t> next{0};
@@ -2314,7 +2352,7 @@ int HnswIndex::range_query_device(int count, float range, std::vector<std::vecto
                 for (SearchHit *p = b; p + 1 < e; ++p) tie |= p[0].dist == p[1].dist; // also -0 next to +0
             }
             if (tie) { state[i] = 2; continue; }
-            std::vector<NodeDist> &o = out[i];
+            std::vector<NodeDist> &o = out[(size_t)qi(i)];
             o.resize((size_t)(e - b));
             for (size_t a = 0; a < o.size(); ++a) o[a] = NodeDist{b[a].id, b[a].dist};
         }
@@ -2322,7 +2360,7 @@ int HnswIndex::range_query_device(int count, float range, std::vector<std::vecto
     if (g_pt.on) g_pt.rq_sort += now_s() - t_sort0;
     std::vector<int> redo, replay;
     for (int i = 0; i < count; ++i) {
-        if (state[(size_t)i] == 1) redo.push_back(i);
+        if (state[(size_t)i] == 1) redo.push_back(qi((size_t)i)); // (the lock-step way names queries)
         else if (state[(size_t)i] == 2) replay.push_back(i);
     }
     g_pt.rq_replayed += (long)replay.size();
@@ -2335,17 +2373,58 @@ int HnswIndex::range_query_device(int count, float range, std::vector<std::vecto
                 const int i = replay[t];
                 const auto list_of = [&](int id) { return graph_.list(id, layer); };
                 if (filtered) {
-                    if (finish_filtered_range(list_of, graph_.max_edges_at(0), r.entry[(size_t)i], range, r.found + r.off[(size_t)i], r.cnt[(size_t)i], allow,
-                                              out[(size_t)i]) == kRangeHeapEmpty)
+                    if (finish_filtered_range(list_of, graph_.max_edges_at(0), r.entry[(size_t)i], range, r.found + r.off[(size_t)i], r.cnt[(size_t)i],
+                                              grp ? grp->of(qi((size_t)i)) : AllowPred{allow}, out[(size_t)qi((size_t)i)]) == kRangeHeapEmpty)
                         heap_empty.store(true);
                 } else
-                    replay_range_heaps(list_of, graph_.max_edges_at(0), r.entry[(size_t)i], range, r.found + r.off[(size_t)i], r.cnt[(size_t)i], out[(size_t)i]);
+                    replay_range_heaps(list_of, graph_.max_edges_at(0), r.entry[(size_t)i], range, r.found + r.off[(size_t)i], r.cnt[(size_t)i], out[(size_t)qi((size_t)i)]);
             }
         });
         if (heap_empty.load()) { err = kHeapEmptyError; return -1; }
     }
-    if (!redo.empty()) return range_query_lockstep(redo.data(), (int)redo.size(), range, out, err, allow, layer);
+    if (!redo.empty()) return range_query_lockstep(redo.data(), (int)redo.size(), range, out, err, allow, layer, grp);
     return 0;
+}
+
+// RangeQuery with a group filter per query: range_query's filtered call for every group at once.  The labels go to
+// the device as they are; once slots are vacant a copy does, with the vacant slots in no group (live_labels).
+int HnswIndex::range_query_grouped(const float *queries, int count, int dim, float range, int layer, const int *row_group, long long n_row_group,
+                                   const int *query_group, int n_groups, std::vector<std::vector<NodeDist>> &out, std::string &err)
+{
+    out.assign((size_t)std::max(count, 0), {});
+    if (failed(err)) return -1;
+    if (count <= 0) return 0;
+    const char *who = "hnsw_mi355x_range_query_grouped";
+    if (!group_args_ok(who, query_group, count, n_groups, err)) return -1;
+    if (graph_.entry < 0) return 0; // HNSWIndex.cs:146
+    if (!layer_ok(layer, err)) { err = "System.IndexOutOfRangeException: " + std::string(who) + ": " + err; return -1; }
+    if (!ensure_dim(dim, err)) return -1;
+    std::vector<int> live;
+    (void)live_labels(row_group, n_row_group, live);
+    const long long n_lab = std::min<long long>(n_row_group, graph_.length); // only the labels of graph ids count
+    std::vector<char> has_id((size_t)n_groups, 0); // groups that hold an id of the graph
+    for (long long id = 0; id < n_lab; ++id)
+        if (row_group[id] >= 0 && row_group[id] < n_groups) has_id[(size_t)row_group[id]] = 1;
+    // a group without ids: an empty list, and no traversal -- when range >= 0; below zero the filtered call can pop an empty heap
+    // for an empty set too (range_replay.h), so those queries run
+    std::vector<int> run;
+    for (int i = 0; i < count; ++i)
+        if (has_id[(size_t)query_group[i]] || !(range >= 0.0f)) run.push_back(i);
+    RangeGroupSpec grp;
+    grp.label = row_group;
+    grp.n_label = n_lab;
+    grp.query_group = query_group;
+    grp.run = &run;
+    grp.skipped = count - (long long)run.size();
+    const bool on_device = p_.device_traversal && dev_->traversal_fits(1, false, p_.max_edges);
+    if (run.empty() && !on_device) return 0;
+    resident_queries_ = 0; // the resident set is replaced: a later knn_query_resident must not answer for these rows
+    if (!dev_->set_queries(queries, count)) { err = get_dev_error(); return -1; }
+    int rc;
+    if (on_device) rc = range_query_device(count, range, out, err, AllowBits{}, layer, &grp);
+    else rc = range_query_lockstep(run.data(), (int)run.size(), range, out, err, AllowBits{}, layer, &grp);
+    if (rc < 0 && err == kHeapEmptyError) out.assign((size_t)count, {}); // the whole batch fails (Parallel.For rethrows)
+    return rc;
 }
 
 int HnswIndex::range_query(const float *queries, int count, int dim, float range, std::vector<std::vector<NodeDist>> &out, std::string &err,

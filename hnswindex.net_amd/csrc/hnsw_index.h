@@ -68,6 +68,11 @@ public:
     int exact_knn_query_grouped(const float *queries, int count, int dim, int k, const int *row_group, long long n_row_group, const int *query_group,
                                 int n_groups, int *out_ids, float *out_dists, std::string &err);
     void exact_grouped_info(uint64_t out[4]) const { if (dev_) dev_->exact_grouped_info(out); else out[0] = out[1] = out[2] = out[3] = 0; }
+    // hnsw_mi355x_exact_range_query_grouped: exact_range_query with exact_knn_query_grouped's group per query
+    // (Device::exact_range_grouped); the labels of vacant slots are taken out as for that call
+    int exact_range_query_grouped(const float *queries, int count, int dim, float range, const int *row_group, long long n_row_group, const int *query_group,
+                                  int n_groups, int *counts, std::vector<int> &ids, std::vector<float> &dists, std::string &err);
+    void exact_range_grouped_info(uint64_t out[4]) const { if (dev_) dev_->exact_range_grouped_info(out); else out[0] = out[1] = out[2] = out[3] = 0; }
     void exact_range_info(uint64_t out[4]) const { if (dev_) dev_->exact_range_info(out); else out[0] = out[1] = out[2] = out[3] = 0; }
     // hnsw_mi355x_get_info / hnsw_mi355x_connected_component_counts: HNSWIndex.GetInfo() / GetConnectedComponentCounts() for the
     // layers 0 .. top, computed by the primary context from the graph mirror (Device::graph_info / graph_components)
@@ -122,6 +127,15 @@ public:
     // layer: RangeQuery's `layer` (outside 0 .. the entry point's top layer on a non-empty index: -1).
     int range_query(const float *queries, int count, int dim, float range, std::vector<std::vector<NodeDist>> &out, std::string &err,
                     AllowBits allow = AllowBits{}, int layer = 0);
+
+    // hnsw_mi355x_range_query_grouped: RangeQuery on `layer` with a group filter per query -- query i's list is byte
+    // for byte what range_query returns for it with the ids j < n_row_group, row_group[j] == query_group[i] as the allow-set; the
+    // empty-heap rule fails the whole call as there.  One device traversal for every group (Device::range_batch with RangeGroups);
+    // hand-backs, and the whole call when the traversal does not run on the device, go the lock-step way with the label predicate.
+    // A query whose group holds no graph id is answered with an empty list without a traversal when range >= 0.  Exclusive lock.
+    int range_query_grouped(const float *queries, int count, int dim, float range, int layer, const int *row_group, long long n_row_group,
+                            const int *query_group, int n_groups, std::vector<std::vector<NodeDist>> &out, std::string &err);
+    void range_grouped_info(uint64_t out[4]) const { if (dev_) dev_->range_grouped_info(out); else out[0] = out[1] = out[2] = out[3] = 0; }
 
     // hnsw_remove (HNSWIndex.Remove, src/HNSWIndex/HNSWIndex.cs:83-102), ids in order.
     int remove(const int *ids, int count, std::string &err);
@@ -243,9 +257,20 @@ private:
     int answer_resident(int count, int ef, OnDevice on_device, OnHost on_host, const char *fallback, std::string &err);
     int knn_query_lockstep(const int *which, int count, int k, int *out_ids, float *out_dists, std::string &err, AllowBits allow = AllowBits{},
                            int layer = 0);
+    // range_query_grouped's filter: the labels of graph ids, every query's group, and the queries that run (ascending), the others
+    // being answered with an empty list
+    struct RangeGroupSpec {
+        const int *label = nullptr;
+        long long n_label = 0;
+        const int *query_group = nullptr;
+        const std::vector<int> *run = nullptr;
+        long long skipped = 0;
+        AllowPred of(int qi) const { return AllowPred{label, n_label, query_group[qi]}; }
+    };
     int range_query_lockstep(const int *which, int count, float range, std::vector<std::vector<NodeDist>> &out, std::string &err,
-                             AllowBits allow = AllowBits{}, int layer = 0);
-    int range_query_device(int count, float range, std::vector<std::vector<NodeDist>> &out, std::string &err, AllowBits allow, int layer);
+                             AllowBits allow = AllowBits{}, int layer = 0, const RangeGroupSpec *grp = nullptr);
+    int range_query_device(int count, float range, std::vector<std::vector<NodeDist>> &out, std::string &err, AllowBits allow, int layer,
+                           const RangeGroupSpec *grp = nullptr);
     int multilayer_lockstep(const int *which, int count, int k, int first, int min_layer, int *out_ids, float *out_dists, std::string &err);
     bool layer_ok(int layer, std::string &err) const;
     int remove_batched(const int *ids, int count, std::string &err);

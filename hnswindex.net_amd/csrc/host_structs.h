@@ -35,6 +35,19 @@ struct AllowBits {
     long long n = 0;
     bool has(int id) const { return !bits || (id >= 0 && id < n && ((bits[id >> 5] >> (id & 31)) & 1u) != 0u); }
 };
+// RangeQuery's filterFnc in its two shapes (range_replay.h, RangeJob): a bit set, or "this id's label equals this query's group"
+// (range_query_grouped, DESIGN.md 3.23: ids >= n_label, and labels that name another group, are not allowed).  An AllowBits
+// converts to the first shape and answers as it always did.
+struct AllowPred {
+    AllowBits set;
+    const int *label = nullptr;
+    long long n_label = 0;
+    int group = 0;
+    AllowPred() = default;
+    AllowPred(AllowBits b) : set(b) {}
+    AllowPred(const int *labels, long long n, int g) : label(labels), n_label(n), group(g) {}
+    bool has(int id) const { return label ? (id >= 0 && id < n_label && label[id] == group) : set.has(id); }
+};
 // Does a set of nbits bits allow any id of a graph of n_graph nodes?  Reads only the words that cover ids < min(nbits, n_graph).
 static inline bool allows_any(const uint32_t *bits, long long nbits, long long n_graph)
 {

@@ -16,7 +16,7 @@ namespace hnsw {
 // farthestResultDist is still MaxValue at :286).  Result: topCandidates' array, stably sorted (HNSWIndex.cs:155).
 // list_of(id) -> the node's list on the layer the search ran on (RangeQuery's `layer`: the caller's lambda carries it) as
 // [count, ids...]; Hit: {int id; float dist}.
-// With an allow-set (RangeQuery's filterFnc), `found` is the query's whole CLOSURE -- every node within range the traversal
+// With a filter (RangeQuery's filterFnc: AllowPred, a bit set or a group label), `found` is the query's whole CLOSURE -- every node within range the traversal
 // reached, allowed or not: the traversal does not depend on the filter -- and only allowed nodes enter the top heap (:271,
 // :307-308).  Its Peek (:310) then reads buffer[0] before the first push: default(NodeDistance), distance 0.  With range < 0
 // that is beyond range, and Pop throws on the empty heap (BinaryHeap.cs:56): returned as kRangeHeapEmpty (out cleared).
@@ -25,7 +25,7 @@ constexpr int kRangeHeapEmpty = -1;
 constexpr const char *kHeapEmptyError = "System.InvalidOperationException: Heap is empty"; // (the reference export's last error)
 template <class ListOf, class Hit>
 inline int replay_range_heaps(ListOf list_of, int max_edges0, int entry, float range, const Hit *found, int m, std::vector<NodeDist> &out,
-                              AllowBits allow = AllowBits{})
+                              AllowPred allow = AllowPred{})
 {
     size_t cap = 16;
     while (cap < 2 * (size_t)m) cap <<= 1;
@@ -84,7 +84,7 @@ inline int replay_range_heaps(ListOf list_of, int max_edges0, int entry, float r
 // closure otherwise -- and always for range < 0, where the empty-heap rule depends on the discovery order.  Returns 0 or
 // kRangeHeapEmpty.
 template <class ListOf, class Hit>
-inline int finish_filtered_range(ListOf list_of, int max_edges0, int entry, float range, Hit *b, int m, AllowBits allow, std::vector<NodeDist> &out)
+inline int finish_filtered_range(ListOf list_of, int max_edges0, int entry, float range, Hit *b, int m, AllowPred allow, std::vector<NodeDist> &out)
 {
     Hit *mid = std::partition(b, b + m, [&](const Hit &h) { return allow.has(h.id); });
     std::sort(b, mid, [](const Hit &x, const Hit &y) { return x.dist < y.dist; }); // no NaN: d <= range held

@@ -288,6 +288,28 @@ int hnsw_mi355x_exact_knn_query_grouped(void *handle, const float *vectors, int 
  * 0, or -1 for a NULL argument. */
 int hnsw_mi355x_exact_grouped_info(void *handle, uint64_t out[4]);
 
+/* hnsw_mi355x_exact_range_query with a candidate group per query (no reference counterpart): the group arguments of
+ * hnsw_mi355x_exact_knn_query_grouped -- row_group int32[n_row_group] indexed by id, query_group int32[count], the candidates of
+ * query i the live ids j < n_row_group with row_group[j] == query_group[i], a value outside [0, n_groups) or an id past the
+ * array's end in no group, 1 <= n_groups <= 65 536 -- and everything else hnsw_mi355x_exact_range_query's contract: the compare
+ * d <= range on the distance itself, NaN never a result, the radii NaN / +inf / -0.0 / negative, order by (distance, id), 2^27
+ * results per query, malloc'ed lists released with hnsw_free_results, NULL where counts[i] is 0.  All groups are scanned in one
+ * launch per round; a query whose group has no live member gets an empty list without being scanned.  For every group g the lists
+ * of the queries with query_group == g are byte for byte what hnsw_mi355x_exact_range_query returns for those queries with the
+ * allow-set {j : row_group[j] == g}, and they come back in the caller's query order.
+ * -1 with a message, every out pointer NULL and every count 0: row_group NULL or n_row_group < 0; n_groups outside 1 .. 65 536; a
+ * query_group value outside [0, n_groups) (the message names the first such index); a list above the limit.  NULL handle and
+ * count <= 0: 0, nothing written.  Always on the device and on the primary context alone; takes the handle exclusively; the
+ * resident query set and the pending results of a range traversal are not touched. */
+int hnsw_mi355x_exact_range_query_grouped(void *handle, const float *vectors, int count, int dim, float range, const int *row_group,
+                                          long long n_row_group, const int *query_group, int n_groups, void **out_ids, void **out_dists,
+                                          int *counts);
+/* Counters of hnsw_mi355x_exact_range_query_grouped on the primary context since hnsw_mi355x_reset_stats: out[0] grouped range
+ * calls that launched a scan, out[1] lists of two or more entries ordered on the device, out[2] lists ordered on the host, out[3]
+ * pieces of a round scanned again with exact capacities.  (Launches and measured pairs count in hnswdev_stats.exact_*.)  0, or -1
+ * for a NULL argument. */
+int hnsw_mi355x_exact_range_grouped_info(void *handle, uint64_t out[4]);
+
 /* hnsw_mi355x_knn_query_at_layer with a group filter per query (no reference counterpart): rows partitioned by
  * tenant, category or language, every query answered from its own part by the GRAPH traversal, all parts in one launch.
  * row_group is int32[n_row_group], indexed by id; query_group is int32[count].  Query i's filter is
@@ -313,6 +335,20 @@ int hnsw_mi355x_knn_query_grouped(void *handle, const float *vectors, int count,
  * hand-backs also count in hnswdev_stats.search_launches / search_evals / search_overflows, as a filtered call's do; a call
  * answered by the host traversal alone counts nowhere here.)  0, or -1 for a NULL argument. */
 int hnsw_mi355x_knn_grouped_info(void *handle, uint64_t out[4]);
+/* RangeQuery with a GROUP FILTER PER QUERY: the graph traversal of hnsw_mi355x_range_query_at_layer, query i
+ * filtered by { j < n_row_group : row_group[j] == query_group[i] }.  Per group g the lists of the queries with query_group == g
+ * are byte for byte -- ids, distance bits, the order among equal distances -- what hnsw_mi355x_range_query_at_layer returns for
+ * those queries with that set as allow_bits.  One device traversal serves every group.  Where the reference pops an empty heap
+ * (range < 0) the whole call fails as the filtered call does: -1, "System.InvalidOperationException: Heap is empty", every array
+ * NULL and every count 0.  A query whose group holds no graph id gets an empty list without a traversal when range >= 0.
+ * Group arguments and their errors as hnsw_mi355x_knn_query_grouped; arrays as hnsw_range_query (hnsw_free_results).  NULL
+ * handle and count <= 0: 0, nothing written.  Takes the handle exclusively; replaces the resident query set. */
+int hnsw_mi355x_range_query_grouped(void *handle, const float *vectors, int count, int dim, float range, int layer, const int *row_group,
+                                    long long n_row_group, const int *query_group, int n_groups, void **out_ids, void **out_dists, int *counts);
+/* Counters of hnsw_mi355x_range_query_grouped on the primary context since hnsw_mi355x_reset_stats: out[0] calls that reached the
+ * context, out[1] queries launched, out[2] queries answered without a job because their group holds no graph id, out[3] lists the
+ * device left to the host (closures to partition, sort or replay, and hand-backs).  0, or -1 for a NULL argument. */
+int hnsw_mi355x_range_grouped_info(void *handle, uint64_t out[4]);
 
 /* Measurement aid: hnsw_mi355x_set_queries uploads a query set (count x dim) once; every later
  * hnsw_mi355x_knn_query_resident(k) is hnsw_knn_query on that set with the inputs already in HBM
@@ -622,6 +658,15 @@ int hnswdev_knn_search_grouped(void *ctx, const float *queries, int nq, int entr
                                long long n_row_group, const int *query_group, int n_groups, int *out_ids, float *out_dists, int *out_flags);
 /* out[0 .. 3] as hnsw_mi355x_knn_grouped_info, of this context; zeroed by hnswdev_reset_stats. */
 int hnswdev_knn_grouped_info(void *ctx, uint64_t out[4]);
+/* hnswdev_range_search_at_layer with a group filter per query (range_sort_grouped_kernel behind graph_range_kernel): query i is
+ * answered as with the allow-set { id : row_group[id] == query_group[i] }; only the labels of graph ids count.  out_counts /
+ * out_flags and the fetch with hnswdev_range_results as hnswdev_range_search_filtered; a query whose group holds no graph id gets
+ * count 0, flag 0 and no job when range >= 0.  -1 with a message: a NULL array, n_row_group < 0, n_groups outside 1 .. 65 536, a
+ * query_group value outside [0, n_groups), an entry point outside the graph, a layer it does not have, the empty-heap failure. */
+int hnswdev_range_search_grouped(void *ctx, const float *queries, int nq, int entry_point, float range, int layer, const int *row_group,
+                                 long long n_row_group, const int *query_group, int n_groups, int *out_counts, int *out_flags);
+/* out[0 .. 3] as hnsw_mi355x_range_grouped_info, of this context; zeroed by hnswdev_reset_stats. */
+int hnswdev_range_grouped_info(void *ctx, uint64_t out[4]);
 /* MultiLayerKnnQuery's chains (graph_multilayer_kernel), one job per query: layers min(top, max_layer) .. min_layer with beam k
  * (k >= 2), top = entry_point's level; semantics of hnsw_mi355x_multilayer_knn_query.  Returns the slot count min(top, max_layer) + 1
  * (0 for max_layer == -1), or -1 (max_layer < -1, min_layer < 0, layers_cap below the count).  out_ids / out_dists:
@@ -664,6 +709,14 @@ int hnswdev_exact_grouped_info(void *ctx, uint64_t out[4]);
  * hnswdev_exact_knn_grouped calls made while profiling was on (hnswdev_set_profiling) since hnswdev_reset_stats.  The scan and the
  * merge of those calls are in hnswdev_stats.exact_kernel_ms.  0, or -1 for a NULL argument. */
 int hnswdev_exact_grouped_list_ms(void *ctx, double *out_ms);
+/* The flat scan behind hnsw_mi355x_exact_range_query_grouped: hnswdev_exact_range with hnswdev_exact_knn_grouped's group arguments
+ * (queries == NULL: the resident set, gathered into the call's order on the device).  out_counts[i]: query i's number of results;
+ * the lists are kept like hnswdev_exact_range's, in the caller's query order, and fetched with hnswdev_exact_range_results.  The
+ * list-building kernels' time counts in hnswdev_exact_grouped_list_ms.  -1: nothing is kept and every count is 0. */
+int hnswdev_exact_range_grouped(void *ctx, const float *queries, int nq, long long n_rows, float range, const int *row_group, long long n_row_group,
+                                const int *query_group, int n_groups, int *out_counts);
+/* out[0 .. 3] as hnsw_mi355x_exact_range_grouped_info, of this context; zeroed by hnswdev_reset_stats. */
+int hnswdev_exact_range_grouped_info(void *ctx, uint64_t out[4]);
 /* hnsw_mi355x_get_info / hnsw_mi355x_connected_component_counts for ONE layer of the committed graph mirror of a context.
  * live_bits == NULL: every node of the mirror is live; otherwise a bitset of nbits bits in the allow-sets' format, ids >= nbits not
  * live.  A layer's members are the live nodes with level >= layer; an entry that points at no member counts in its owner's out-degree
