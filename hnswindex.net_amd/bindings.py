@@ -262,6 +262,8 @@ lib.hnsw_mi355x_build_id.restype = ct.c_char_p
 lib.hnsw_mi355x_build_id.argtypes = []
 lib.hnsw_mi355x_exact_window_stats.restype = ct.c_int
 lib.hnsw_mi355x_exact_window_stats.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
+lib.hnsw_mi355x_row_prefilter_stats.restype = ct.c_int
+lib.hnsw_mi355x_row_prefilter_stats.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
 
 # ---- (B) hnswdev_* -------------------------------------------------------------------------
 lib.hnsw_mi355x_import_nodes.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_int, _I, ct.c_int]
@@ -537,6 +539,14 @@ class Index:
         if not self._h or lib.hnsw_mi355x_exact_window_stats(self._h, out) != 0:
             return {"rounds": 0, "searches": 0, "alone": 0, "linked": 0}
         return {"rounds": int(out[0]), "searches": int(out[1]), "alone": int(out[2]), "linked": int(out[3])}
+
+    def row_prefilter_stats(self):
+        """Counters of KnnQuery's half-precision row prefilter: launches with it, rows measured on the shadow, rows re-read in f32,
+        shadow rows packed."""
+        out = (ct.c_uint64 * 4)()
+        if not self._h or lib.hnsw_mi355x_row_prefilter_stats(self._h, out) != 0:
+            return {"launches": 0, "rows_on_shadow": 0, "rows_reread": 0, "rows_packed": 0}
+        return {"launches": int(out[0]), "rows_on_shadow": int(out[1]), "rows_reread": int(out[2]), "rows_packed": int(out[3])}
 
     def set_remove_batch(self, max_batch: int):
         """1 (default): remove() takes the ids one after the other; B > 1: removals with disjoint neighbourhoods together."""

@@ -6,6 +6,7 @@
 #include <atomic>
 #include <cstdint>
 #include <functional>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -470,6 +471,9 @@ public:
     void set_shadows_allowed(bool on) { shadows_allowed_ = on; }
     void get_stats(hnswdev_stats *out);
     void reset_stats();
+    // The row prefilter's counters (a view adds to its primary's): launches that ran with it, rows measured on the shadow, rows
+    // measured again from f32, shadow rows packed.  All zero on a context that has none (every metric but sq_euclid, diag row_prefilter=0).
+    void row_prefilter_stats(uint64_t out[4]);
 
     // C-ABI callers: one call at a time per context (hnswdev_* exports hold this), and the
     // context's own last-error string.
@@ -493,6 +497,21 @@ private:
     long long n_rows_hw_ = 0; // high-water mark of uploaded rows (id validation)
     DevBuf<float> d_rows_;    // (a view borrows the rows, their norms and the graph mirror: rebind)
     DevBuf<double> d_row_sn_; // cosine: sqrt((double)|row|^2_f32)
+    // The half-precision SHADOW of the stored rows (sq_euclid contexts; dk_sorted_top.h "row prefilter"): shared by a
+    // primary and its views, allocated by the first launch that takes the lean search form.  Rows [0, packed) are current; every
+    // writer of stored rows goes through rows_written(), which lowers `packed`, and a launch packs [packed, n) before it reads.
+    struct RowPrefilter {
+        std::mutex mu;
+        DevBuf<float> rows;                // f16_row_words(dim) words per row, `row_cap` rows
+        DevBuf<unsigned long long> words;  // [bits of E, rows measured on the shadow, rows re-read] (device-side, cumulative)
+        long long row_cap = 0, packed = 0;
+        bool lost = false;                 // a launch re-read more than half of its rows: the lean form until the next repack
+        bool no_memory = false;            // the shadow could not be allocated: the lean form, no error
+        uint64_t launches = 0, on_shadow = 0, reread = 0, rows_packed = 0;
+    };
+    std::shared_ptr<RowPrefilter> pf_;
+    void rows_written(long long first_id); // stored rows [first_id, ...) have changed, or the row matrix has moved
+    bool row_prefilter_ready();            // the shadow is allocated and current for rows [0, n_rows_hw_) (packs what is missing)
     DevBuf<float> d_queries_;
     DevBuf<double> d_q_sn_;
     long long q_capacity() const { return (long long)(d_queries_.cap() / (size_t)pitch_); }

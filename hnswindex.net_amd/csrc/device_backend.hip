@@ -282,6 +282,7 @@ Device *Device::create(int device, int dim, int metric, long long capacity)
     // half-precision rows: the record of dk_base.h (32 B per 16 elements); queries and every LDS size stay those of `dim` floats
     d->row_pitch_ = metric_f16(metric) ? f16_row_words(dim) : d->pitch_;
     d->metric_ = metric;
+    if (metric == M_SQ) d->pf_ = std::make_shared<RowPrefilter>(); // (its device memory: the first lean launch, row_prefilter_ready)
     // algorithmic bytes per evaluation: the row's elements, plus the 4-byte scale for int8
     d->stats_.row_bytes = metric == M_I8 ? (uint64_t)dim + 4u : metric_f16(metric) ? (uint64_t)dim * 2u : (uint64_t)dim * sizeof(float);
     auto fail = [&]() -> Device * { delete d; return nullptr; };
@@ -321,6 +322,7 @@ void Device::rebind(const Device *p)
     g_adj0_.borrow(p->g_adj0_); g_level_.borrow(p->g_level_); g_upper_.borrow(p->g_upper_); g_pool_.borrow(p->g_pool_);
     g_tested0_.borrow(p->g_tested0_); g_testedU_.borrow(p->g_testedU_);
     g_n_ = p->g_n_; g_stride0_ = p->g_stride0_; g_strideU_ = p->g_strideU_;
+    pf_ = p->pf_; // (the shadow of the borrowed rows: one per index)
 }
 
 // Only what has an order is written out; the holders release everything else after this body.  Should hipSetDevice fail, the
@@ -353,6 +355,7 @@ bool Device::reserve(long long capacity)
     d_rows_ = std::move(nr); // (the old blocks go here)
     d_row_sn_ = std::move(nsn);
     capacity_ = capacity;
+    rows_written(0);
     return true;
 }
 
@@ -364,6 +367,7 @@ bool Device::upload_rows(int first_id, int n, const float *rows)
         return false;
     }
     if (!bind()) return false;
+    rows_written(first_id);
     {   // pageable -> pinned bounce buffer -> HBM, 64 MiB at a time (int8 and f16 rows: through a float staging area on the
         // device, quantised into records there)
         const size_t row_bytes = (size_t)dim_ * sizeof(float);
@@ -423,6 +427,7 @@ bool Device::upload_rows_begin(int first_id, int n, const float *rows)
     if (metric_ == M_I8 || bg_.active.load()) { set_dev_error("upload_rows_begin: not available (int8 rows, or an upload already in flight)"); return false; }
     if (first_id < 0 || (long long)first_id + n > capacity_ || !rows) { set_dev_error("upload_rows: range outside capacity"); return false; }
     if (!bind()) return false;
+    rows_written(first_id);
     const size_t row_bytes = (size_t)dim_ * sizeof(float);
     const size_t chunk_rows = std::max<size_t>(1, (8u << 20) / row_bytes);
     if (!bg_.stream.create(false) || !bg_.ev[0].create(false) || !bg_.ev[1].create(false)) return false;
@@ -482,6 +487,67 @@ bool Device::upload_rows_wait(long long upto)
     bg_.active.store(false);
     if (bg_.failed.load()) { set_dev_error("background row upload failed: " + bg_.err); return false; }
     return true;
+}
+
+// ---- the row prefilter's shadow (dk_sorted_top.h) ----
+// 0: off, and nothing is ever allocated; 1 (default): on, until a launch re-reads more than half of its rows; 2: on regardless (tests)
+static int row_prefilter_mode() { return diag("row_prefilter", 1); }
+
+// THE one place that learns of a change to the stored rows: upload_rows, upload_rows_begin (the background upload of a large Add),
+// reserve (the matrix moves: everything), clone_from (everything: a re-used slot changes a row the replica already holds).
+// Deserialize, import and slot re-use upload through the first two.  A stale shadow row would answer wrongly without a sign.
+void Device::rows_written(long long first_id)
+{
+    if (!pf_) return;
+    std::lock_guard<std::mutex> lk(pf_->mu);
+    pf_->packed = std::min(pf_->packed, std::max(0ll, first_id));
+    pf_->lost = false; // the next launch repacks, and with other rows the prefilter may pay again
+}
+
+bool Device::row_prefilter_ready()
+{
+    const int mode = row_prefilter_mode();
+    if (!pf_ || metric_ != M_SQ || mode == 0 || bg_.active.load() || n_rows_hw_ <= 0) return false;
+    RowPrefilter &P = *pf_;
+    std::lock_guard<std::mutex> lk(P.mu);
+    if (P.no_memory || (P.lost && mode != 2)) return false;
+    hipStream_t st = S(stream_);
+    const size_t words = (size_t)f16_row_words(dim_);
+    if (P.row_cap < capacity_ || !P.rows) {
+        const std::string before = get_dev_error();
+        const bool first = !P.words;
+        if (!P.rows.grow((size_t)capacity_ * words) || !P.words.grow(4)) { // run without it, and report nothing
+            (void)P.rows.reset();
+            P.row_cap = P.packed = 0;
+            P.no_memory = true;
+            (void)hipGetLastError();
+            set_dev_error(before);
+            return false;
+        }
+        P.row_cap = capacity_;
+        P.packed = 0;
+        if (first) HIP_OK(hipMemsetAsync(P.words, 0, 4 * sizeof(unsigned long long), st));
+    }
+    const long long n = n_rows_hw_;
+    if (P.packed < n) {
+        if (P.packed == 0) HIP_OK(hipMemsetAsync(P.words, 0, sizeof(unsigned long long), st)); // a full repack: E starts over
+        const long long more = n - P.packed;
+        hipLaunchKernelGGL(pack_shadow_rows_kernel, dim3((unsigned)((more + 3) / 4)), dim3(256), 0, st, d_rows_.get(), dim_, P.packed, more, P.rows.get(),
+                           reinterpret_cast<unsigned *>(P.words.get()));
+        HIP_OK(hipGetLastError());
+        HIP_OK(hipStreamSynchronize(st)); // (the views launch on streams of their own)
+        P.rows_packed += (uint64_t)more;
+        P.packed = n;
+    }
+    return true;
+}
+
+void Device::row_prefilter_stats(uint64_t out[4])
+{
+    out[0] = out[1] = out[2] = out[3] = 0;
+    if (!pf_) return;
+    std::lock_guard<std::mutex> lk(pf_->mu);
+    out[0] = pf_->launches; out[1] = pf_->on_shadow; out[2] = pf_->reread; out[3] = pf_->rows_packed;
 }
 
 bool Device::download_rows(int first_id, int n, float *rows)
@@ -742,6 +808,7 @@ bool Device::clone_from(Device *src, long long pool_len)
     hipStream_t st = S(stream_);
     const long long have = std::min(n_rows_hw_, src->n_rows_hw_); // rows never change once uploaded (slot reuse re-clones: see HnswIndex)
     const long long more = src->n_rows_hw_ - have;
+    rows_written(0);
     if (more > 0) {
         HIP_OK(hipMemcpyPeerAsync(d_rows_ + (size_t)have * row_pitch_, device_, src->d_rows_ + (size_t)have * row_pitch_, src->device_, (size_t)more * row_pitch_ * sizeof(float), st));
         if (metric_ == M_COS) HIP_OK(hipMemcpyPeerAsync(d_row_sn_ + have, device_, src->d_row_sn_ + have, src->device_, (size_t)more * sizeof(double), st));
@@ -1135,7 +1202,8 @@ struct TraversalLaunch {
     bool lat_ok;         // the latency form may run: sorted top, lists of at most 64 ids, room for its mailbox
     bool filtered;       // graph_search_filtered_kernel (an allow-set): exact traversal, visited sets kept, no latency form
     // per launch
-    int form;            // kFormLat, kFormLean, kFormPlain
+    bool prefilter;      // the lean form's row prefilter may run: the index's shadow rows are current (search_batch_impl says so)
+    int form;            // kFormLat, kFormLean, kFormLeanPF, kFormPlain
     int slots, grid;     // the form's resident waves; grid = min(jobs, slots)
     unsigned block;      // 128 threads for the latency form (logic wave + memory wave), else 64
     size_t lds_total;    // lds, plus kTeamLds of mailbox for the latency form
@@ -1150,6 +1218,7 @@ bool Device::plan_traversal(bool insert, int k, bool two_heap, size_t lds, Trave
     t->num_cu = num_cu_;
     t->lds = lds;
     t->filtered = filtered;
+    t->prefilter = false;
     t->exact_only = ns == 0; // two_heap callers, beams beyond 512 entries, diag sorted_top=0, filtered searches
     t->ns = t->exact_only ? 2 : ns;
     if (!visited_scratch(k, filtered ? kFilterVisCap : 512, t->ns != 8, &t->vis, filtered)) return false;
@@ -1179,7 +1248,8 @@ static auto traversal_form(int form)
         return form == kFormLat ? &graph_insert_search_kernel<M, NS, H, kFormLat> : &graph_insert_search_kernel<M, NS, H, kFormPlain>;
     else if constexpr (NS <= 4)
         return form == kFormLat ? &graph_search_kernel<M, NS, H, kFormLat>
-               : form == kFormLean ? &graph_search_kernel<M, NS, H, kFormLean> : &graph_search_kernel<M, NS, H, kFormPlain>;
+               : form == kFormLean ? &graph_search_kernel<M, NS, H, kFormLean>
+               : form == kFormLeanPF ? &graph_search_kernel<M, NS, H, kFormLeanPF> : &graph_search_kernel<M, NS, H, kFormPlain>;
     else
         return form == kFormLat ? &graph_search_kernel<M, NS, H, kFormLat> : &graph_search_kernel<M, NS, H, kFormPlain>;
 }
@@ -1230,7 +1300,7 @@ static auto place_traversal(TraversalLaunch &t, int nj)
         const int slots = std::min(t.max_slots, resident_blocks(traversal_kernel<Insert>(t, kFormLat), t.lds + kTeamLds, t.num_cu, 128));
         if (slots > 0 && (lat == 2 || nj <= slots)) { t.form = kFormLat; t.slots = slots; }
     }
-    if (!Insert && t.form == kFormPlain && t.novis && !t.exact_only && lean_mode() && t.ns <= 4) t.form = kFormLean;
+    if (!Insert && t.form == kFormPlain && t.novis && !t.exact_only && lean_mode() && t.ns <= 4) t.form = t.prefilter ? kFormLeanPF : kFormLean;
     const auto kernel = traversal_kernel<Insert>(t, t.form);
     if (t.form != kFormLat) t.slots = std::min(t.max_slots, resident_blocks(kernel, t.lds, t.num_cu));
     t.grid = std::min(nj, t.slots);
@@ -1741,9 +1811,10 @@ bool Device::search_batch_impl(const SearchJob *jobs, int njobs, int k, int k_ou
     if (!ensure_search_scratch(chunk, max_slots(), k_out, tl.vis.bytes_per_job)) return false;
     // pinned layout: [evals (16 B) | jobs | ids | dists | flags]
     const size_t b_jobs = sizeof(SearchJob) * (size_t)chunk, b_res = 4u * (size_t)chunk * k_out;
-    char *hs = static_cast<char *>(pinned_stage(16 + b_jobs + 2 * b_res + 4u * (size_t)chunk));
+    const size_t off_pf = (16 + b_jobs + 2 * b_res + 4u * (size_t)chunk + 7) & ~(size_t)7; // the row prefilter's two counters land behind the flags
+    char *hs = static_cast<char *>(pinned_stage(off_pf + 16));
     if (!hs) return false;
-    unsigned long long *h_ev = reinterpret_cast<unsigned long long *>(hs);
+    unsigned long long *h_ev = reinterpret_cast<unsigned long long *>(hs), *h_pf = reinterpret_cast<unsigned long long *>(hs + off_pf);
     SearchJob *h_jobs = reinterpret_cast<SearchJob *>(hs + 16);
     int *h_ids = reinterpret_cast<int *>(hs + 16 + b_jobs);
     float *h_d = reinterpret_cast<float *>(hs + 16 + b_jobs + b_res);
@@ -1775,19 +1846,28 @@ bool Device::search_batch_impl(const SearchJob *jobs, int njobs, int k, int k_ou
             HIP_OK(hipMemcpyAsync(s_jobs_, h_jobs, sizeof(SearchJob) * (size_t)nj, hipMemcpyHostToDevice, st));
             uj_len_ = nj; uj_entry_ = u_entry; uj_layer_ = u_layer;
         }
+        // a launch that would take the lean form takes its row-prefilter variant where the index has current shadow rows (the
+        // first such launch allocates and packs them, a launch after an Add packs what is new)
+        auto kernel = place_traversal<false>(tl, nj);
+        if (tl.form == kFormLean && row_prefilter_ready()) {
+            tl.prefilter = true;
+            kernel = place_traversal<false>(tl, nj);
+        }
+        const bool prefiltered = tl.form == kFormLeanPF;
         HIP_OK(hipMemsetAsync(s_jobctr_, 0, sizeof(int) * (4 + (size_t)nj), st));
         if (!compact) HIP_OK(hipMemsetAsync(s_evals_, 0, sizeof(unsigned long long), st));
         const bool timed = profiling_;
         if (timed) HIP_OK(hipEventRecord(E(ev0_), st));
-        const auto kernel = place_traversal<false>(tl, nj);
         hipLaunchKernelGGL(kernel, dim3(tl.grid), dim3(tl.block), tl.lds_total, st, d_rows_, d_row_sn_, d_queries_, d_q_sn_, pitch_, g_adj0_, g_stride0_,
                            g_upper_, g_pool_, g_strideU_, s_jobs_, k, cand_cap, reinterpret_cast<ND *>(s_spill_.get()), spill_cap_for_tests(), s_visited_,
                            tl.vis.words, tl.vis.tab, tl.vis.tab_cap, k_out, d_ids, d_d, s_cnt_, d_flag, d_ev, nbcap(), nj, s_jobctr_,
-                           tl.flags | (shadow_mode() && shadows_allowed_ ? 0x100 : 0), gate);
+                           tl.flags | (shadow_mode() && shadows_allowed_ ? 0x100 : 0), gate, prefiltered ? pf_->rows.get() : (const float *)nullptr,
+                           prefiltered ? pf_->words.get() : (unsigned long long *)nullptr);
         if (tl.form == kFormLat) stats_.lat_launches++;
-        if (tl.form == kFormLean) stats_.lean_launches++;
+        if (form_is_lean(tl.form)) stats_.lean_launches++;
         HIP_OK(hipGetLastError());
         if (timed) HIP_OK(hipEventRecord(E(ev1_), st));
+        if (prefiltered) HIP_OK(hipMemcpyAsync(h_pf, pf_->words.get() + 1, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
         if (tail_.n > 0 && !upload_tail()) return false; // the rest of the query set, while the launch above is running
         if (compact) { // [ids | distances | flags] in one piece (nj == chunk: the device slab and the staging are laid out alike)
             HIP_OK(hipMemcpyAsync(h_ids, d_ids, 2 * b_res + sizeof(int) * (size_t)nj, hipMemcpyDeviceToHost, st));
@@ -1811,6 +1891,15 @@ bool Device::search_batch_impl(const SearchJob *jobs, int njobs, int k, int k_ou
             else if (h_flag[i] == 4) { stats_.tie_windows++; h_flag[i] = 0; } // informational: a group window closed cleanly
         }
         memcpy(out_flag + off, h_flag, sizeof(int) * (size_t)nj);
+        if (prefiltered) { // the device words are cumulative; a launch that re-read more than half of its rows cost more than it saved
+            std::lock_guard<std::mutex> lk(pf_->mu);
+            const uint64_t d_shadow = h_pf[0] > pf_->on_shadow ? h_pf[0] - pf_->on_shadow : 0, d_reread = h_pf[1] > pf_->reread ? h_pf[1] - pf_->reread : 0;
+            pf_->launches++;
+            pf_->on_shadow += d_shadow;
+            pf_->reread += d_reread;
+            if (2 * d_reread > d_shadow && row_prefilter_mode() != 2) pf_->lost = true;
+        }
+        tl.prefilter = false; // (decided per launch)
         if (!count_launch(nullptr, *h_ev, tl.vis.tab != nullptr, timed, ev0_, ev1_)) return false;
     }
     for (int i = 0; i < njobs; ++i) stats_.search_overflows += (uint64_t)(out_flag[i] == 1);

@@ -17,6 +17,10 @@
 #define HNSW_I8_WAVES 5
 #endif
 
+#ifndef HNSW_PF_WAVES // waves per SIMD of the row-prefilter search kernels (-DHNSW_PF_WAVES=4 was measured: 128 VGPRs with 40 spilled, 19.7 ms per launch where three waves take 16.5)
+#define HNSW_PF_WAVES 3
+#endif
+
 namespace hnsw {
 
 // Every block of the kernels below that stage data through LDS is ONE wavefront working on its own job (the latency
@@ -51,7 +55,11 @@ __device__ __forceinline__ void wave_lds_sync()
 // where they are used (kernarg_load below): 316 -> 105 spilled scalars in the int8 two-set form, HALF the vector instructions
 // per launch (the spills' v_readlane / v_writelane sat in the expansion loop).  Measured (round 5, profiles/r5_lean_ab.log):
 // int8 records 12 500-query launches 3.73 -> 2.93 ms, 65 536-query launches 12.9 -> 9.2 ms; f32 rows within +-1.5 %.
-constexpr int kFormPlain = 0, kFormLat = 1, kFormLean = 2;
+// LEAN_PF (sq_euclid, f32 rows only): the lean form with the half-precision row prefilter -- the listed neighbours are measured on
+// the index's SHADOW rows (half the bytes), the ones that are provably farther than the farthest result are turned away on that
+// value, and only the rest is measured from its f32 row by the lean form's own pass (dk_sorted_top.h).
+constexpr int kFormPlain = 0, kFormLat = 1, kFormLean = 2, kFormLeanPF = 3;
+constexpr __host__ __device__ bool form_is_lean(int f) { return f == kFormLean || f == kFormLeanPF; }
 
 // A kernel argument read again from the kernarg segment at the point of use (a scalar load that hits the constant cache) instead of
 // being carried in SGPRs from the kernel's first instruction to its last: the lean search kernel does this for the two dozen

@@ -108,6 +108,46 @@ pack_f16_rows_kernel(const float *__restrict__ src, int dim, int n, float *__res
     const unsigned lo = i0 < dim ? f32_to_f16_bits(__float_as_uint(x[i0])) : 0u, hi = i1 < dim ? f32_to_f16_bits(__float_as_uint(x[i1])) : 0u;
     reinterpret_cast<unsigned *>(dst)[(size_t)(first + r) * pitch + w] = lo | (hi << 16);
 }
+// The row prefilter's shadow (dk_sorted_top.h): rows [first, first + n) of the f32 matrix `src` -> records [first, first + n) of
+// `dst`, pack_f16_rows_kernel's layout and rounding, one wave per row -- which also raises *e_bits (the bits of a float >= 0, so
+// atomicMax on them orders like the values) to an upper bound of ||x - h(x)||_2: the sum of squares in double (every difference is
+// exact there, the sum is off by less than dim * 2^-53 of itself), its root rounded up to float and raised by 2^-20.  An element
+// that does not convert to a finite half (or is not finite itself) makes the bound +inf: no row is turned away on such a shadow.
+__global__ void __launch_bounds__(256)
+pack_shadow_rows_kernel(const float *__restrict__ src, int dim, long long first, long long n, float *__restrict__ dst, unsigned *__restrict__ e_bits)
+{
+    const int pitch = f16_row_words(dim), lane = threadIdx.x & 63;
+    const long long r = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= n) return;
+    const float *x = src + (size_t)(first + r) * dim;
+    unsigned *rec = reinterpret_cast<unsigned *>(dst) + (size_t)(first + r) * pitch;
+    double ss = 0.0;
+    bool finite = true;
+    for (int w = lane; w < pitch; w += 64) {
+        const int i0 = ((w >> 3) << 4) | (w & 7), i1 = i0 + 8;
+        const float x0 = i0 < dim ? x[i0] : 0.0f, x1 = i1 < dim ? x[i1] : 0.0f;
+        const unsigned word = (unsigned)f32_to_f16_bits(__float_as_uint(x0)) | ((unsigned)f32_to_f16_bits(__float_as_uint(x1)) << 16);
+        rec[w] = word;
+        const float h0 = half_lo(word), h1 = half_hi(word);
+        finite = finite && (h0 - h0 == 0.0f) && (h1 - h1 == 0.0f) && (x0 - x0 == 0.0f) && (x1 - x1 == 0.0f);
+        const double d0 = (double)x0 - (double)h0, d1 = (double)x1 - (double)h1;
+        ss += d0 * d0 + d1 * d1;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o, 64);
+    const bool all_finite = __ballot(!finite) == 0ull;
+    if (lane == 0) {
+        unsigned bits = 0x7f800000u; // +inf
+        if (all_finite && ss < 1e300) {
+            const double e = sqrt(ss);
+            float f = (float)e;
+            if ((double)f < e) f = __uint_as_float(__float_as_uint(f) + 1u); // (f >= 0: the next float up)
+            f = f * 1.00000095367431640625f + 1e-37f; // the double sum's own rounding, and away from the subnormals
+            bits = __float_as_uint(f);
+        }
+        atomicMax(e_bits, bits);
+    }
+}
 // records -> the stored rows widened to float (hnswdev_download_rows on a half-precision context)
 __global__ void __launch_bounds__(256)
 unpack_f16_rows_kernel(const float *__restrict__ recs, long long first, int n, int dim, float *__restrict__ out)

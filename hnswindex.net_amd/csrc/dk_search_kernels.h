@@ -21,8 +21,10 @@ struct SearchKernArgs {
     const int64_t *upper; const int *pool; int strideU; const SearchJob *jobs; int k, cand_cap; ND *spill; int spill_cap;
     unsigned *visited; long long vis_words; int *vis_tab; int vis_tab_cap, k_out; int *out_ids; float *out_d; int *out_cnt, *out_flag;
     unsigned long long *eval_counter; int nbcap, njobs; int *job_counter; int overlap; const int *ready;
+    const float *pf_rows; unsigned long long *pf_words; // the row prefilter (kFormLeanPF): shadow records; [E's bits, rows on the shadow, rows re-read]
 };
-static_assert(offsetof(SearchKernArgs, jobs) == 80 && offsetof(SearchKernArgs, out_ids) == 144 && offsetof(SearchKernArgs, ready) == 208 && sizeof(SearchKernArgs) == 216,
+static_assert(offsetof(SearchKernArgs, jobs) == 80 && offsetof(SearchKernArgs, out_ids) == 144 && offsetof(SearchKernArgs, ready) == 208 &&
+              offsetof(SearchKernArgs, pf_rows) == 216 && offsetof(SearchKernArgs, pf_words) == 224 && sizeof(SearchKernArgs) == 232,
               "SearchKernArgs must mirror graph_search_kernel's parameter list (the explicit arguments start the kernarg segment, each at its natural alignment)");
 #define HNSW_KA(field) kernarg_load<decltype(SearchKernArgs::field)>((unsigned)offsetof(SearchKernArgs, field))
 
@@ -97,7 +99,7 @@ __device__ __forceinline__ void search_job(const float *__restrict__ rows, const
                     unsigned long long *__restrict__ eval_counter, int nbcap, unsigned char *smem, int job, int overlap,
                     int *__restrict__ job_word = nullptr, bool shadow = false, TeamPort *port = nullptr, bool *v_untouched = nullptr)
 {
-    constexpr bool LAT = FORM == kFormLat, LEAN = FORM == kFormLean;
+    constexpr bool LAT = FORM == kFormLat, LEAN = form_is_lean(FORM), PF = FORM == kFormLeanPF;
     if constexpr (LEAN) { // (what only the start and the end of a job need is read where it is needed: kernarg_load)
         cand_cap = HNSW_KA(cand_cap); nbcap = HNSW_KA(nbcap); jobs = HNSW_KA(jobs); queries = HNSW_KA(queries); q_sn = HNSW_KA(q_sn);
     }
@@ -140,6 +142,13 @@ __device__ __forceinline__ void search_job(const float *__restrict__ rows, const
         bool window = false;
         bool ok1;
         if constexpr (LAT) ok1 = traverse_pool<METRIC, NS, HASHED>(rows, row_sn, dim, sb, G, jb, k, k_out + 1, V, L, lane, top_n, tie, evals, RL, nullptr, &window, port);
+        else if constexpr (PF) {
+            // E is read once per job (a scalar load); the job's two row counts go to the words behind it
+            unsigned long long *const words = HNSW_KA(pf_words);
+            RowPrefilterIo pf{HNSW_KA(pf_rows), __uint_as_float(*reinterpret_cast<const unsigned *>(words)), row_prefilter_c(dim), 0u, 0u};
+            ok1 = traverse_sorted<METRIC, NS, HASHED, true, true>(rows, row_sn, dim, sb, G, jb, k, k_out + 1, V, L, lane, top_n, tie, evals, overlap, RL, nullptr, &window, &pf);
+            if (lane == 0) { atomicAdd(words + 1, (unsigned long long)pf.n_shadow); atomicAdd(words + 2, (unsigned long long)pf.n_reread); }
+        }
         else ok1 = traverse_sorted<METRIC, NS, HASHED, LEAN>(rows, row_sn, dim, sb, G, jb, k, k_out + 1, V, L, lane, top_n, tie, evals, overlap, RL, nullptr, &window);
         if (!(ok1 && tie)) {
             if (v_untouched) *v_untouched = LEAN || (!LAT && (overlap & 8) != 0); // the sorted traversal ran without a visited set: nothing to clear
@@ -229,7 +238,7 @@ template <int METRIC, int NS, bool HASHED, int FORM = kFormPlain>
 // float rows: 168 VGPRs, three waves per SIMD; int8 records keep 16 registers of rows in flight, not 64: five waves.
 // LAT (launches that do not fill the chip): no occupancy to buy -- every spilled register is a memory round trip a lone wave
 // waits out in full -- so two waves per SIMD at most (256 VGPRs), one with eight register sets
-__global__ void __launch_bounds__(FORM == kFormLat ? 128 : 64) __attribute__((amdgpu_waves_per_eu(HNSW_WAVES(FORM == kFormLat ? (NS <= 4 ? 2 : 1) : METRIC == M_I8 ? (NS <= 2 ? HNSW_I8_WAVES : 4) : (NS <= 4 ? 3 : 2)))))
+__global__ void __launch_bounds__(FORM == kFormLat ? 128 : 64) __attribute__((amdgpu_waves_per_eu(HNSW_WAVES(FORM == kFormLat ? (NS <= 4 ? 2 : 1) : FORM == kFormLeanPF ? HNSW_PF_WAVES : METRIC == M_I8 ? (NS <= 2 ? HNSW_I8_WAVES : 4) : (NS <= 4 ? 3 : 2)))))
 graph_search_kernel(const float *__restrict__ rows, const double *__restrict__ row_sn, const float *__restrict__ queries,
                     const double *__restrict__ q_sn, int dim, const int *__restrict__ adj0, int stride0,
                     const int64_t *__restrict__ upper, const int *__restrict__ pool, int strideU,
@@ -237,9 +246,11 @@ graph_search_kernel(const float *__restrict__ rows, const double *__restrict__ r
                     int spill_cap, unsigned *__restrict__ visited, long long vis_words, int *__restrict__ vis_tab, int vis_tab_cap, int k_out,
                     int *__restrict__ out_ids, float *__restrict__ out_d, int *__restrict__ out_cnt, int *__restrict__ out_flag,
                     unsigned long long *__restrict__ eval_counter, int nbcap, int njobs, int *__restrict__ job_counter, int overlap,
-                    const int *__restrict__ ready)
+                    const int *__restrict__ ready, const float *__restrict__ pf_rows, unsigned long long *__restrict__ pf_words)
 {
-    constexpr bool LAT = FORM == kFormLat, LEAN = FORM == kFormLean;
+    constexpr bool LAT = FORM == kFormLat, LEAN = form_is_lean(FORM);
+    if constexpr (FORM == kFormLeanPF && METRIC != M_SQ) return; // (the row prefilter exists for sq_euclid on f32 rows: never launched elsewhere)
+    else {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x & 63;
     // (the lean form looks its visited set and spill area up when a job takes the exact traversal: search_job)
@@ -351,6 +362,7 @@ graph_search_kernel(const float *__restrict__ rows, const double *__restrict__ r
     }
 
     if constexpr (LAT) port.post(-1, 0, lane); // the memory wave leaves
+    }
 }
 #define HNSW_SEARCH_SIGNATURE(PREFIX, M, NS, H, LT)                                                                                  \
     PREFIX template __global__ void graph_search_kernel<M, NS, H, LT>(                                                              \
@@ -358,7 +370,7 @@ graph_search_kernel(const float *__restrict__ rows, const double *__restrict__ r
         const int *__restrict__, int, const int64_t *__restrict__, const int *__restrict__, int, const SearchJob *__restrict__,  \
         int, int, ND *__restrict__, int, unsigned *__restrict__, long long, int *__restrict__, int, int, int *__restrict__,      \
         float *__restrict__, int *__restrict__, int *__restrict__, unsigned long long *__restrict__, int, int, int *__restrict__, int, \
-        const int *__restrict__);
+        const int *__restrict__, const float *__restrict__, unsigned long long *__restrict__);
 #define HNSW_DECLARE_SEARCH(M, NS, H, LT) HNSW_SEARCH_SIGNATURE(extern, M, NS, H, LT)
 #define HNSW_DEFINE_SEARCH(M, NS, H, LT) HNSW_SEARCH_SIGNATURE(, M, NS, H, LT)
 

@@ -246,13 +246,55 @@ struct SortedTop {
     }
 };
 
+// ---- the half-precision row prefilter (kFormLeanPF; sq_euclid on f32 rows) -----------------------------------
+// Nearly nine of ten listed neighbours are measured only to be turned away by the push test d < farthest (:165), and that
+// decision does not need 24 significand bits.  The index keeps a SHADOW of its rows as half-precision records h(x) (dk_base.h)
+// and one word E >= max over rows of ||x - h(x)||_2.  An expansion measures its listed neighbours on the shadow (D_h, the f32
+// arithmetic of measure_pass_h on half the bytes) and, once the list is full, turns a neighbour away on D_h alone when that
+// PROVES that the f32 distance D_x of its real row exceeds the farthest key; every other neighbour is measured from its f32 row
+// by the pass the lean form runs on all of them, so every distance that reaches the list is that pass's value, bit for bit.
+// The proof.  u = 2^-24; a term (a - b)^2 of either sum passes through at most m = dim / 8 + 14 roundings (the subtraction
+// counts twice, the fma chain of its lane dim / 8 times, the collapse 3, the tail's product and 7 additions), all terms are
+// >= 0, so D = ||.||^2 (1 + t) with |t| <= g_m = m u / (1 - m u) for both D_h and D_x -- as long as no product underflows;
+// an underflowing one adds at most 2^-149 per element, less than u times any sum above 1e-30, which two more roundings
+// cover: g = 1.001 (dim / 8 + 16) u.  Hence ||h - q|| >= sqrt(D_h (1 - g)) >= sqrt(D_h) (1 - g), the triangle inequality gives
+// ||x - q|| >= sqrt(D_h) (1 - g) - E, and D_x >= lb = (sqrt(D_h) (1 - g) - E)^2 (1 - g) (0 when sqrt(D_h) <= E).  lb > far is
+// tested as D_h > T with T >= ((sqrt(max(far, 1e-30) c) + E) c)^2, c = 1 + 1.5 g >= 1 / (1 - g): T is computed once per
+// expansion in f32 (seven roundings and a square root, under 16 u) and raised by 2^-18.  NaN or +inf in D_h, E or far makes
+// the comparison false: the row is kept.  A neighbour turned away carries +inf: a key above the farthest, which is what its
+// own key provably is, so the list lookup, the window tests (a), (b) and the merge see the lanes they see in the lean form.
+struct RowPrefilterIo {
+    const float *rows; // the shadow records (f16_row_words(dim) words per row)
+    float e, c;        // E and 1 + 1.5 g
+    unsigned n_shadow, n_reread; // rows this job measured on the shadow / measured again from f32
+};
+__device__ __forceinline__ float row_prefilter_c(int dim) { return 1.0f + 1.5f * (1.001f * (float)((dim >> 3) + 16) * 5.9604644775390625e-8f); }
+__device__ __forceinline__ float row_prefilter_threshold(float far, float e, float c)
+{
+    const float s = __builtin_sqrtf(fmaxf(far, 1e-30f) * c) + e;
+    const float t = s * c;
+    return t * t * 1.000003814697265625f;
+}
+// D_h of nbuf[0..m) on the shadow: measure_all's passes of the half-precision metric
+__device__ __forceinline__ void measure_shadow(const float *shadow, int dim, const float *qs, const int *nbuf, float *dbuf, int m, int lane)
+{
+    for (int p0 = 0; p0 < m; p0 += 32) {
+        const int left = m - p0;
+        if (left > 24) measure_pass_h<M_SQH, 4>(shadow, dim, qs, nbuf, dbuf, p0, m, lane);
+        else if (left > 16) measure_pass_h<M_SQH, 3>(shadow, dim, qs, nbuf, dbuf, p0, m, lane);
+        else if (left > 8) measure_pass_h<M_SQH, 2>(shadow, dim, qs, nbuf, dbuf, p0, m, lane);
+        else measure_pass_h<M_SQH, 1>(shadow, dim, qs, nbuf, dbuf, p0, m, lane);
+    }
+}
+
 // Returns false on a NaN / -0 distance (exact host re-run); `tie` asks for the exact two-heap
 // traversal.  Result: L.top[0..top_n) ascending by distance.  The query must be staged in L.qs.
-template <int METRIC, int NS, bool HASHED, bool LEAN = false>
+template <int METRIC, int NS, bool HASHED, bool LEAN = false, bool PF = false>
 __device__ __forceinline__ bool traverse_sorted(const float *__restrict__ rows, const double *__restrict__ row_sn, int dim, double sb,
                                                 const GraphView &G, const SearchJob jb, int k, int ordered_prefix, VisitedSet<HASHED> &V,
                                                 const SearchLds &L, int lane, int &top_n_out, bool &tie_out, unsigned long long &evals,
-                                                int oflags, ReadLog &RL, bool *order_tie_out = nullptr, bool *window_out = nullptr)
+                                                int oflags, ReadLog &RL, bool *order_tie_out = nullptr, bool *window_out = nullptr,
+                                                RowPrefilterIo *pf = nullptr)
 {
     int *nbuf = L.nbuf;
     float *dbuf = L.dbuf;
@@ -363,9 +405,30 @@ __device__ __forceinline__ bool traverse_sorted(const float *__restrict__ rows, 
                 }
             }
             PHX(0);
+            bool pf_keep = false; // (row prefilter: this lane's neighbour was measured from its f32 row, at dbuf[pf_pos])
+            int pf_pos = 0;
+            if constexpr (PF) {
+                if (n > 0) {
+                    measure_shadow(pf->rows, dim, qs, nbuf, dbuf, n, lane);
+                    wave_sync();
+                    const float dh = in ? dbuf[lane] : 0.0f;
+                    const float thr = top_n >= k ? row_prefilter_threshold(key2f(far_key), pf->e, pf->c) : __uint_as_float(0x7f800000u);
+                    pf_keep = in && !(dh > thr); // (nothing is turned away while the list is not full; NaN keeps the row)
+                    const unsigned long long km = __ballot(pf_keep);
+                    pf_pos = __builtin_amdgcn_mbcnt_hi((unsigned)(km >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)km, 0));
+                    const int kn = (int)__popcll(km);
+                    if (pf_keep) nbuf[pf_pos] = nb_a; // (every lane holds its id in nb_a: the compaction is in place)
+                    wave_sync();
+                    if (kn > 0) measure_all<METRIC>(rows, row_sn, dim, qs, sb, nbuf, dbuf, kn, lane); // :163, the lean form's bits
+                    pf->n_shadow += (unsigned)n;
+                    pf->n_reread += (unsigned)kn;
+                }
+            } else
             if (n > 0) measure_all<METRIC>(rows, row_sn, dim, qs, sb, nbuf, dbuf, n, lane); // :163 (and the visited ones)
             wave_sync();
             PHX(1);
+            if constexpr (PF) lane_d = pf_keep ? dbuf[pf_pos] : __uint_as_float(0x7f800000u); // turned away: a key above the farthest
+            else
             lane_d = in ? dbuf[lane] : 0.0f;
             lane_id = nb_a;
             if (novis) {

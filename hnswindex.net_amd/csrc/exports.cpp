@@ -538,6 +538,13 @@ API int hnsw_mi355x_exact_window_stats(void *h, uint64_t out[4])
     static_cast<HnswIndex *>(h)->exact_window_stats(out);
     return 0;
 }
+API int hnsw_mi355x_row_prefilter_stats(void *h, uint64_t out[4])
+{
+    if (!h || !out) return -1;
+    LOCK_INDEX(h);
+    static_cast<HnswIndex *>(h)->row_prefilter_stats(out);
+    return 0;
+}
 API int hnsw_mi355x_exact_range_info(void *h, uint64_t out[4])
 {
     if (!h || !out) return -1;

@@ -2220,6 +2220,17 @@ void HnswIndex::collect_stats(hnswdev_stats *out)
     }
 }
 
+void HnswIndex::row_prefilter_stats(uint64_t out[4])
+{
+    out[0] = out[1] = out[2] = out[3] = 0;
+    if (dev_) dev_->row_prefilter_stats(out);
+    for (auto &r : replicas_) {
+        uint64_t v[4];
+        r->row_prefilter_stats(v);
+        for (int i = 0; i < 4; ++i) out[i] += v[i];
+    }
+}
+
 void HnswIndex::reset_all_stats()
 {
     if (dev_) dev_->reset_stats();

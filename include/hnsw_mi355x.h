@@ -143,6 +143,10 @@ int hnsw_mi355x_index_insert_batch(void *handle);
  * out[1] insert searches run (>= items: the re-searched ones count again), out[2] items inserted alone (entry-point
  * moves, hand-backs), out[3] items linked through windows. */
 int hnsw_mi355x_exact_window_stats(void *handle, uint64_t out[4]);
+/* Counters of the half-precision row prefilter of KnnQuery (sq_euclid indices) since the index was created:
+ * out[0] search launches that ran with it, out[1] rows measured on the half-precision shadow, out[2] rows measured again from
+ * their f32 row (the others were turned away on the shadow value), out[3] shadow rows packed.  All zero where it does not run. */
+int hnsw_mi355x_row_prefilter_stats(void *handle, uint64_t out[4]);
 /* Pending: hnsw_remove's schedule.  1 (default): the ids one after the other, exactly HNSWIndex.Remove(int) per id.
  * B > 1: the deterministic counterpart of Remove(List<int>) = Parallel.For under region locks (HNSWIndex.cs:95-101,
  * GraphLocker.cs:28-72): removals whose neighbourhoods (the node, its out- and in-neighbours on every layer) are
