@@ -264,6 +264,8 @@ lib.hnsw_mi355x_exact_window_stats.restype = ct.c_int
 lib.hnsw_mi355x_exact_window_stats.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
 lib.hnsw_mi355x_row_prefilter_stats.restype = ct.c_int
 lib.hnsw_mi355x_row_prefilter_stats.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
+lib.hnsw_mi355x_row_prefilter_peek.restype = ct.c_int
+lib.hnsw_mi355x_row_prefilter_peek.argtypes = [ct.c_void_p, ct.c_int, ct.c_int, ct.POINTER(ct.c_uint64), ct.POINTER(ct.c_float)]
 
 # ---- (B) hnswdev_* -------------------------------------------------------------------------
 lib.hnsw_mi355x_import_nodes.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_int, _I, ct.c_int]
@@ -547,6 +549,20 @@ class Index:
         if not self._h or lib.hnsw_mi355x_row_prefilter_stats(self._h, out) != 0:
             return {"launches": 0, "rows_on_shadow": 0, "rows_reread": 0, "rows_packed": 0}
         return {"launches": int(out[0]), "rows_on_shadow": int(out[1]), "rows_reread": int(out[2]), "rows_packed": int(out[3])}
+
+    def row_prefilter_peek(self, first_id: int = 0, count: int = 0):
+        """The row prefilter's shadow as it stands, read only: {"packed": the watermark (shadow rows [0, packed) are current),
+        "e_bits": the 32 bits of E, "e": E as a float32, "rows": the shadow rows [first_id, first_id + count) widened to f32}.
+        An index without a shadow has packed 0; a range that is not below the watermark is an error."""
+        out = (ct.c_uint64 * 2)()
+        rows = np.zeros((max(int(count), 0), self.dim), dtype=np.float32)
+        if not self._h:
+            if count > 0:
+                raise RuntimeError("row_prefilter_peek: the index has no shadow rows")
+            return {"packed": 0, "e_bits": 0, "e": np.float32(0), "rows": rows}
+        self._check(lib.hnsw_mi355x_row_prefilter_peek(self._h, int(first_id), int(count), out, rows.ctypes.data_as(ct.POINTER(ct.c_float))))
+        bits = int(out[1]) & 0xffffffff
+        return {"packed": int(out[0]), "e_bits": bits, "e": np.array([bits], dtype=np.uint32).view(np.float32)[0], "rows": rows}
 
     def set_remove_batch(self, max_batch: int):
         """1 (default): remove() takes the ids one after the other; B > 1: removals with disjoint neighbourhoods together."""

@@ -474,6 +474,10 @@ public:
     // The row prefilter's counters (a view adds to its primary's): launches that ran with it, rows measured on the shadow, rows
     // measured again from f32, shadow rows packed.  All zero on a context that has none (every metric but sq_euclid, diag row_prefilter=0).
     void row_prefilter_stats(uint64_t out[4]);
+    // The shadow as it stands, read only (nothing is packed or allocated): out[0] the watermark (shadow rows [0, out[0]) are current),
+    // out[1] the 32 bits of E; rows: the shadow rows [first_id, first_id + count) widened to f32, `count` x dim floats (count 0: none).
+    // false for a range that is not below the watermark.  A context without a shadow has watermark 0.
+    bool row_prefilter_peek(long long first_id, int count, uint64_t out[2], float *rows);
 
     // C-ABI callers: one call at a time per context (hnswdev_* exports hold this), and the
     // context's own last-error string.

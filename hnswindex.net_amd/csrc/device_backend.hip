@@ -550,6 +550,42 @@ void Device::row_prefilter_stats(uint64_t out[4])
     out[0] = pf_->launches; out[1] = pf_->on_shadow; out[2] = pf_->reread; out[3] = pf_->rows_packed;
 }
 
+bool Device::row_prefilter_peek(long long first_id, int count, uint64_t out[2], float *rows)
+{
+    out[0] = out[1] = 0;
+    if (!pf_ || !pf_->rows || !pf_->words) {
+        if (count > 0) set_dev_error("row_prefilter_peek: the index has no shadow rows");
+        return count <= 0;
+    }
+    if (!bind()) return false;
+    RowPrefilter &P = *pf_;
+    std::lock_guard<std::mutex> lk(P.mu); // (a pack runs under it, and waits for its kernel)
+    unsigned long long e_word = 0;
+    HIP_OK(hipMemcpy(&e_word, P.words.get(), sizeof(e_word), hipMemcpyDeviceToHost));
+    out[0] = (uint64_t)P.packed;
+    out[1] = (uint64_t)(e_word & 0xffffffffull);
+    if (count <= 0) return true;
+    if (first_id < 0 || first_id + count > P.packed || !rows) {
+        set_dev_error("row_prefilter_peek: range outside the packed shadow rows");
+        return false;
+    }
+    // the records cross in pieces of a fixed buffer and are widened here, by the kernels' accessors (pack_f16_rows_kernel's layout)
+    const size_t words = (size_t)f16_row_words(dim_), total = (size_t)count * words;
+    const unsigned *src = reinterpret_cast<const unsigned *>(P.rows.get()) + (size_t)first_id * words;
+    unsigned buf[2048];
+    for (size_t w0 = 0; w0 < total; w0 += 2048) {
+        const size_t nw = std::min<size_t>(2048, total - w0);
+        HIP_OK(hipMemcpy(buf, src + w0, nw * sizeof(unsigned), hipMemcpyDeviceToHost));
+        for (size_t j = 0; j < nw; ++j) {
+            const size_t r = (w0 + j) / words;
+            const int w = (int)((w0 + j) % words), i0 = ((w >> 3) << 4) | (w & 7), i1 = i0 + 8;
+            if (i0 < dim_) rows[r * (size_t)dim_ + i0] = half_lo(buf[j]);
+            if (i1 < dim_) rows[r * (size_t)dim_ + i1] = half_hi(buf[j]);
+        }
+    }
+    return true;
+}
+
 bool Device::download_rows(int first_id, int n, float *rows)
 {
     if (n <= 0) return true;

@@ -99,8 +99,8 @@ __device__ __forceinline__ const float *row_at(const float *__restrict__ rows, s
     if constexpr (metric_f16(METRIC)) return rows + id * (size_t)f16_row_words(dim);
     else return rows + id * dim;
 }
-__device__ __forceinline__ float half_lo(unsigned w) { return (float)__builtin_bit_cast(_Float16, (unsigned short)(w & 0xffffu)); }
-__device__ __forceinline__ float half_hi(unsigned w) { return (float)__builtin_bit_cast(_Float16, (unsigned short)(w >> 16)); }
+__host__ __device__ __forceinline__ float half_lo(unsigned w) { return (float)__builtin_bit_cast(_Float16, (unsigned short)(w & 0xffffu)); }
+__host__ __device__ __forceinline__ float half_hi(unsigned w) { return (float)__builtin_bit_cast(_Float16, (unsigned short)(w >> 16)); }
 // element i of a stored row
 template <int METRIC>
 __device__ __forceinline__ float row_elem(const float *__restrict__ rec, int i)

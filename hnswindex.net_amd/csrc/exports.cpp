@@ -545,6 +545,14 @@ API int hnsw_mi355x_row_prefilter_stats(void *h, uint64_t out[4])
     static_cast<HnswIndex *>(h)->row_prefilter_stats(out);
     return 0;
 }
+API int hnsw_mi355x_row_prefilter_peek(void *h, int first_id, int count, uint64_t out[2], float *rows)
+{
+    if (!h || !out) return -1;
+    LOCK_INDEX(h);
+    std::string err;
+    if (!static_cast<HnswIndex *>(h)->row_prefilter_peek(first_id, count, out, rows, err)) { set_error(err); return -1; }
+    return 0;
+}
 API int hnsw_mi355x_exact_range_info(void *h, uint64_t out[4])
 {
     if (!h || !out) return -1;

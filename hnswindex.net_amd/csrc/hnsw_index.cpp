@@ -2231,6 +2231,18 @@ void HnswIndex::row_prefilter_stats(uint64_t out[4])
     }
 }
 
+bool HnswIndex::row_prefilter_peek(long long first_id, int count, uint64_t out[2], float *rows, std::string &err)
+{
+    out[0] = out[1] = 0;
+    if (!dev_) {
+        if (count > 0) err = "row_prefilter_peek: the index has no shadow rows";
+        return count <= 0;
+    }
+    if (dev_->row_prefilter_peek(first_id, count, out, rows)) return true;
+    err = get_dev_error();
+    return false;
+}
+
 void HnswIndex::reset_all_stats()
 {
     if (dev_) dev_->reset_stats();

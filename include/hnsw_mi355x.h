@@ -147,6 +147,12 @@ int hnsw_mi355x_exact_window_stats(void *handle, uint64_t out[4]);
  * out[0] search launches that ran with it, out[1] rows measured on the half-precision shadow, out[2] rows measured again from
  * their f32 row (the others were turned away on the shadow value), out[3] shadow rows packed.  All zero where it does not run. */
 int hnsw_mi355x_row_prefilter_stats(void *handle, uint64_t out[4]);
+/* Diagnostic, read only: the half-precision shadow of the row prefilter as it stands (it packs nothing and allocates nothing).
+ * out[0] the packed watermark (shadow rows [0, out[0]) are current), out[1] the 32 bits of E, the index-wide bound on
+ * ||x - h(x)||_2 (a float; 0x7f800000 = +inf: nothing is turned away).  rows (may be NULL when count is 0): count x dim floats, the
+ * shadow rows [first_id, first_id + count) widened to f32.  An index without a shadow (no lean launch yet, another metric, diag
+ * row_prefilter=0) has watermark 0.  -1 for a NULL handle or out, or a range that does not lie below the watermark. */
+int hnsw_mi355x_row_prefilter_peek(void *handle, int first_id, int count, uint64_t out[2], float *rows);
 /* Pending: hnsw_remove's schedule.  1 (default): the ids one after the other, exactly HNSWIndex.Remove(int) per id.
  * B > 1: the deterministic counterpart of Remove(List<int>) = Parallel.For under region locks (HNSWIndex.cs:95-101,
  * GraphLocker.cs:28-72): removals whose neighbourhoods (the node, its out- and in-neighbours on every layer) are
