@@ -92,6 +92,11 @@ class Device;
 struct VisitedScratch;   // device_backend.hip: the visited-set memory of a traversal launch
 struct TraversalLaunch;  // ... which traversal kernel form a launch runs, on how many waves, with which flags
 struct LaunchFamily;     // ... the hnswdev_stats counters of one kernel family
+struct ExactScanArgs;    // dk_exact.h: what one launch of the flat scan reads
+enum class ExactStart;   // device_backend.hip: how a flat-scan call begins -- failed, nothing to measure, ready
+struct ExactScanInput;   // ... the queries and the id list of an ungrouped flat scan
+struct ExactGroupedCall; // ... the group lists and the tile of a grouped one
+struct ExactRangeWork;   // ... the knobs and the scratch of the range calls
 struct ReachSeeds;       // dk_graph_reach.h: the seed set of one layer's reachability pass
 // What one round of repair_reachability brings back (Device::graph_repair_round).  The three arrays are pinned memory of the
 // context, valid until its next round; they are nullptr where no proposal ran (propose == false, or nothing is unreached).
@@ -590,7 +595,13 @@ private:
     bool exact_id_list(const uint32_t *allow_bits, long long n_allow, long long *m);
     bool exact_knn_rounds(const float *d_q, const double *d_qsn, int nq, const int *d_idlist, long long m, int k, int *out_ids, float *out_d, int *d_keep_ids);
     bool exact_copy_out(void *dst, const void *src, size_t bytes);
-    bool exact_range_run(const float *queries, int nq, long long n_rows, float range, const uint32_t *allow_bits, long long nbits, int *out_counts);
+    ExactStart exact_scan_begin(const char *who, const float *queries, int nq, long long n_rows, const uint32_t *allow_bits, long long nbits, ExactScanInput *in);
+    bool exact_scan_args(const float *d_q, const double *d_qsn, long long off, int nr, int qt, int piece, ExactScanArgs *a);
+    template <class Enqueue, class Fetch> // the one timed, counted launch of the flat scan: every exact_* statistic is written there
+    bool exact_timed_scan(unsigned long long *h_ev, Enqueue &&enqueue, Fetch &&fetch);
+    bool exact_range_call(int nq, int *out_counts, const std::function<bool()> &body);
+    bool exact_range_finish(ExactRangeWork &w, int ns, const unsigned *c, const long long *seg, const int *sq, const long long *obase, size_t base,
+                            bool counts_on_device, uint64_t *by_device, uint64_t *by_host);
     DevBuf<unsigned long long> x_rarena_; // exact_range: the round's keys, a segment per query: at most 1 GiB, grown on demand and kept
     DevBuf<long long> x_rseg_, x_rooff_;  // ... per query of a round: where its segment starts (one more: the end), where its ordered list goes
     DevBuf<unsigned> x_rcnt_;             // ... keys within the range
@@ -606,8 +617,8 @@ private:
     uint64_t xrg_info_[4] = {0, 0, 0, 0}; // exact_range_grouped's counters
     bool exact_group_lists(const char *who, const int *row_group, long long n, int n_groups, std::vector<int> &cnt, std::vector<int> &goff, uint64_t *listed);
     bool exact_sorted_queries(const char *who, const float *queries, int nq, const std::vector<int> &order, const float **d_q, const double **d_qsn);
-    bool exact_range_grouped_run(const float *queries, int nq, long long n_rows, float range, const int *row_group, long long n_row_group,
-                                 const int *query_group, int n_groups, int *out_counts);
+    ExactStart exact_grouped_begin(const char *who, bool args_ok, const float *queries, int nq, long long n_rows, int k, const int *row_group,
+                                   long long n_row_group, const int *query_group, int n_groups, ExactGroupedCall *gc);
     double xg_list_ms_ = 0.0;
     bool graph_info_begin(const char *who, int layer, const uint32_t *live_bits, long long nbits, LayerView *g);
     bool graph_info_fetch(const GraphAcc **acc);

@@ -2884,23 +2884,85 @@ bool Device::exact_id_list(const uint32_t *allow_bits, long long n_allow, long l
     return true;
 }
 
+// How a flat-scan call begins (exact_scan_begin, exact_grouped_begin): with an error; with nothing to measure -- no query has a
+// candidate, so the caller writes its padding or leaves its lists empty and succeeds without a launch; or ready to scan.
+enum class ExactStart { failed, nothing, ready };
+
+// What an ungrouped flat scan measures: the queries on the device (pitch_ words each; d_qsn their cosine norms or nullptr) and the
+// m entries of the id list `ids` (nullptr: the identity).
+struct ExactScanInput {
+    const float *d_q;
+    const double *d_qsn;
+    const int *ids;
+    long long m;
+};
+
+// The candidates and queries of an ungrouped flat scan, after the caller's own argument checks: the rows that exist and are
+// allowed (none: nothing to measure), then the queries, the device and the id list as exact_queries and exact_id_list leave them.
+ExactStart Device::exact_scan_begin(const char *who, const float *queries, int nq, long long n_rows, const uint32_t *allow_bits, long long nbits, ExactScanInput *in)
+{
+    if (!allow_bits) nbits = 0; // no filter: nbits means nothing, whatever the caller left in it
+    // rows that exist: a row beyond what was uploaded is never dereferenced, whatever n_rows and the bitset say
+    const long long n = std::min(n_rows, n_rows_hw_), n_allow = allow_bits ? std::min(nbits, n) : n;
+    if (n_allow <= 0 || (allow_bits && !allows_any(allow_bits, nbits, n))) return ExactStart::nothing;
+    if (!exact_queries(who, queries, nq, &in->d_q, &in->d_qsn) || !bind() || !exact_id_list(allow_bits, n_allow, &in->m)) return ExactStart::failed;
+    in->ids = allow_bits ? x_ids_.get() : nullptr;
+    return ExactStart::ready;
+}
+
+// The scan's arguments for one round: `nr` queries from query `off` of d_q on, the tile `qt` and `piece`, the pairs counted in
+// x_evals_ (allocated here).  The rest is left at nothing -- what a grouped range sink reads: the caller sets ids / m / chunk /
+// n_chunks where its blocks are not work items, and k / lists where its sink keeps lists.
+bool Device::exact_scan_args(const float *d_q, const double *d_qsn, long long off, int nr, int qt, int piece, ExactScanArgs *a)
+{
+    if (!x_evals_.grow(1)) return false;
+    *a = ExactScanArgs{};
+    a->rows = d_rows_; a->row_sn = d_row_sn_;
+    a->queries = d_q + (size_t)off * pitch_;
+    a->q_sn = d_qsn ? d_qsn + off : nullptr;
+    a->dim = pitch_; a->nq = nr; a->qtile = qt; a->piece = piece; a->evals = x_evals_;
+    return true;
+}
+
+// One launch of the flat scan, timed and counted -- the only place the exact_* statistics are written.  x_evals_ is zeroed;
+// `enqueue` launches the scan, and whatever else belongs inside the timed window (the top-k calls' merge; a range call's sort is
+// outside it), between the event pair when profiling is on; `fetch` enqueues the caller's own copies out; then the kernel's count
+// goes to the pinned word h_ev and the stream is synchronised, so what `fetch` asked for is on the host when this returns.
+// The flat scan is no traversal: it counts in its own family only, not in the search_* totals, and the evaluations are the kernel's
+// own count of the pairs it turned into keys -- shadows excluded -- not queries x rows worked out here.  Every sink counts here, so
+// a repeated pass counts its pairs again, the unwanted queries of its tiles included.
+template <class Enqueue, class Fetch>
+bool Device::exact_timed_scan(unsigned long long *h_ev, Enqueue &&enqueue, Fetch &&fetch)
+{
+    hipStream_t st = S(stream_);
+    if (!ev0_.create(true) || !ev1_.create(true)) return false;
+    const bool timed = profiling_;
+    HIP_OK(hipMemsetAsync(x_evals_, 0, sizeof(unsigned long long), st));
+    if (timed) HIP_OK(hipEventRecord(E(ev0_), st));
+    if (!enqueue()) return false;
+    if (timed) HIP_OK(hipEventRecord(E(ev1_), st));
+    if (!fetch()) return false;
+    HIP_OK(hipMemcpyAsync(h_ev, x_evals_, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    stats_.exact_launches += 1; stats_.exact_evals += *h_ev;
+    if (timed) {
+        float ms = 0.f;
+        HIP_OK(hipEventElapsedTime(&ms, E(ev0_), E(ev1_)));
+        stats_.exact_kernel_ms += ms; stats_.exact_timed_launches += 1; stats_.exact_timed_evals += *h_ev;
+    }
+    return true;
+}
+
 bool Device::exact_knn(const float *queries, int nq, long long n_rows, int k, const uint32_t *allow_bits, long long nbits, int *out_ids, float *out_d)
 {
     if (nq <= 0) return true;
-    if (!allow_bits) nbits = 0; // no filter: nbits means nothing, whatever the caller left in it
-    if (!out_ids || !out_d || k < 1 || n_rows < 0 || nbits < 0) { set_dev_error("exact_knn: bad argument"); return false; }
+    if (!out_ids || !out_d || k < 1 || n_rows < 0 || (allow_bits && nbits < 0)) { set_dev_error("exact_knn: bad argument"); return false; }
     if (k > kExactMaxK) { set_dev_error("exact_knn: k = " + std::to_string(k) + " is above the limit of " + std::to_string(kExactMaxK)); return false; }
-    // rows that exist: a row beyond what was uploaded is never dereferenced, whatever n_rows and the bitset say
-    const long long n = std::min(n_rows, n_rows_hw_), n_allow = allow_bits ? std::min(nbits, n) : n;
-    if (n_allow <= 0 || (allow_bits && !allows_any(allow_bits, nbits, n))) { // nothing to measure: padding, no launch
-        pad_results(out_ids, out_d, (size_t)nq * (size_t)k);
-        return true;
-    }
-    const float *d_q;
-    const double *d_qsn;
-    long long m;
-    if (!exact_queries("exact_knn", queries, nq, &d_q, &d_qsn) || !bind() || !exact_id_list(allow_bits, n_allow, &m)) return false;
-    return exact_knn_rounds(d_q, d_qsn, nq, allow_bits ? x_ids_.get() : nullptr, m, k, out_ids, out_d, nullptr);
+    ExactScanInput in;
+    const ExactStart s = exact_scan_begin("exact_knn", queries, nq, n_rows, allow_bits, nbits, &in);
+    if (s == ExactStart::nothing) pad_results(out_ids, out_d, (size_t)nq * (size_t)k); // padding, no launch
+    if (s != ExactStart::ready) return s == ExactStart::nothing;
+    return exact_knn_rounds(in.d_q, in.d_qsn, nq, in.ids, in.m, k, out_ids, out_d, nullptr);
 }
 
 // The rounds of a top-k flat scan: nq queries on the device (d_q, pitch_ words each; d_qsn their cosine norms or nullptr) against the
@@ -2912,45 +2974,34 @@ bool Device::exact_knn_rounds(const float *d_q, const double *d_qsn, int nq, con
     const ExactPlan p = exact_plan(nq, m, k, pitch_, num_cu_);
     if (p.lds > 64 * 1024) { set_dev_error("exact_knn: tile exceeds the LDS budget"); return false; }
     if (!x_lists_.grow((size_t)p.round * p.n_chunks * k) || !x_out_.grow(2 * (size_t)p.round * k)) return false;
-    if (!x_evals_.grow(1)) return false;
     char *hs = static_cast<char *>(pinned_stage(8 * (size_t)p.round * k + 8));
     if (!hs) return false;
     unsigned long long *h_ev = reinterpret_cast<unsigned long long *>(hs + 8 * (size_t)p.round * k);
-    if (!ev0_.create(true) || !ev1_.create(true)) return false;
     for (long long off = 0; off < nq; off += p.round) {
         const int nr = (int)std::min<long long>(p.round, nq - off);
         ExactScanArgs a;
-        a.rows = d_rows_; a.row_sn = d_row_sn_;
-        a.queries = d_q + (size_t)off * pitch_;
-        a.q_sn = d_qsn ? d_qsn + off : nullptr;
-        a.dim = pitch_; a.ids = d_idlist; a.m = m; a.chunk = p.chunk; a.nq = nr; a.qtile = p.qtile; a.piece = p.piece; a.k = k;
-        a.lists = x_lists_; a.n_chunks = p.n_chunks; a.evals = x_evals_;
+        if (!exact_scan_args(d_q, d_qsn, off, nr, p.qtile, p.piece, &a)) return false;
+        a.ids = d_idlist; a.m = m; a.chunk = p.chunk; a.n_chunks = p.n_chunks; a.k = k; a.lists = x_lists_;
         const unsigned tiles = (unsigned)((nr + p.qtile - 1) / p.qtile);
+        const size_t res = 4u * (size_t)nr * k;
         int *d_ids = x_out_;
         float *d_d = reinterpret_cast<float *>(x_out_.get() + (size_t)p.round * k);
-        const bool timed = profiling_;
-        HIP_OK(hipMemsetAsync(x_evals_, 0, sizeof(unsigned long long), st));
-        if (timed) HIP_OK(hipEventRecord(E(ev0_), st));
-        hipError_t e = hipSuccess;
-        with_metric(metric_, [&](auto mt) { e = exact_scan_launch<mt>(a, tiles, p.lds, st); });
-        HIP_OK(e);
-        HIP_OK(exact_merge_launch(x_lists_, p.n_chunks, k, nr, d_ids, d_d, st));
-        if (timed) HIP_OK(hipEventRecord(E(ev1_), st));
-        HIP_OK(hipMemcpyAsync(hs, d_ids, 4u * (size_t)nr * k, hipMemcpyDeviceToHost, st));
-        HIP_OK(hipMemcpyAsync(hs + 4u * (size_t)p.round * k, d_d, 4u * (size_t)nr * k, hipMemcpyDeviceToHost, st));
-        HIP_OK(hipMemcpyAsync(h_ev, x_evals_, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-        if (d_keep_ids) HIP_OK(hipMemcpyAsync(d_keep_ids + (size_t)off * k, d_ids, 4u * (size_t)nr * k, hipMemcpyDeviceToDevice, st));
-        HIP_OK(hipStreamSynchronize(st));
-        memcpy(out_ids + (size_t)off * k, hs, 4u * (size_t)nr * k);
-        if (out_d) memcpy(out_d + (size_t)off * k, hs + 4u * (size_t)p.round * k, 4u * (size_t)nr * k);
-        // (the flat scan is no traversal: it counts in its own family only, not in the search_* totals; the evaluations are the
-        // kernel's own count of the pairs it turned into keys -- shadows excluded -- not nr * m worked out here)
-        stats_.exact_launches += 1; stats_.exact_evals += *h_ev;
-        if (timed) {
-            float ms = 0.f;
-            HIP_OK(hipEventElapsedTime(&ms, E(ev0_), E(ev1_)));
-            stats_.exact_kernel_ms += ms; stats_.exact_timed_launches += 1; stats_.exact_timed_evals += *h_ev;
-        }
+        const auto enqueue = [&]() -> bool {
+            hipError_t e = hipSuccess;
+            with_metric(metric_, [&](auto mt) { e = exact_scan_launch<mt>(a, tiles, p.lds, st); });
+            HIP_OK(e);
+            HIP_OK(exact_merge_launch(x_lists_, p.n_chunks, k, nr, d_ids, d_d, st));
+            return true;
+        };
+        const auto fetch = [&]() -> bool {
+            HIP_OK(hipMemcpyAsync(hs, d_ids, res, hipMemcpyDeviceToHost, st));
+            HIP_OK(hipMemcpyAsync(hs + 4u * (size_t)p.round * k, d_d, res, hipMemcpyDeviceToHost, st));
+            if (d_keep_ids) HIP_OK(hipMemcpyAsync(d_keep_ids + (size_t)off * k, d_ids, res, hipMemcpyDeviceToDevice, st));
+            return true;
+        };
+        if (!exact_timed_scan(h_ev, enqueue, fetch)) return false;
+        memcpy(out_ids + (size_t)off * k, hs, res);
+        if (out_d) memcpy(out_d + (size_t)off * k, hs + 4u * (size_t)p.round * k, res);
     }
     return true;
 }
@@ -3055,6 +3106,68 @@ static std::vector<int> exact_group_order(const int *query_group, int n_groups, 
     return order;
 }
 
+// What a grouped flat scan knows once exact_grouped_begin is through.  A group is scanned when it has a query and a member.
+struct ExactGroupedCall {
+    std::vector<int> gq, cnt, goff;   // per group: queries of the call, members, where its segment starts in x_ids_
+    long long n = 0;                  // ids that exist and have a group
+    int max_gq = 0;                   // the most queries of a scanned group
+    uint64_t scanned = 0, listed = 0; // scanned groups; ids that are in a group
+    ExactPlan tp{};                   // the tile (one for the call: the LDS layout is the launch's); chunks are planned per group
+};
+
+// The arguments, group lists and tile of a grouped flat scan.  args_ok: the caller's check of the arguments that are its own; k: the
+// keys a list keeps (0: the sink keeps none, and the tile is planned as for lists of one key).  Nothing to measure: no id exists
+// and has a group (before anything touches the device), or no group has both a query and a member.  The stream is idle and the
+// pinned stage free when this returns.
+ExactStart Device::exact_grouped_begin(const char *who, bool args_ok, const float *queries, int nq, long long n_rows, int k, const int *row_group,
+                                       long long n_row_group, const int *query_group, int n_groups, ExactGroupedCall *gc)
+{
+    const auto fail = [&](const std::string &what) { set_dev_error(std::string(who) + ": " + what); return ExactStart::failed; };
+    if (!args_ok) return fail("bad argument");
+    if (!row_group || n_row_group < 0) return fail("row_group must not be NULL and n_row_group must be >= 0");
+    if (!query_group) return fail("query_group must not be NULL");
+    if (k > kExactMaxK) return fail("k = " + std::to_string(k) + " is above the limit of " + std::to_string(kExactMaxK));
+    if (!group_args_ok(who, query_group, nq, n_groups)) return ExactStart::failed;
+    gc->gq.assign((size_t)n_groups, 0);
+    for (int i = 0; i < nq; ++i) gc->gq[(size_t)query_group[i]] += 1;
+    // ids that exist and have a group: a row beyond what was uploaded is never dereferenced, whatever n_rows and n_row_group say
+    gc->n = std::min({n_rows, n_rows_hw_, n_row_group});
+    if (gc->n <= 0) return ExactStart::nothing;
+    if (!queries && (nq > n_queries_ || tail_.n > 0)) return fail("queries == NULL needs a resident query set of at least nq rows (hnswdev_set_queries)");
+    if (!bind() || !exact_group_lists(who, row_group, gc->n, n_groups, gc->cnt, gc->goff, &gc->listed)) return ExactStart::failed;
+    for (size_t g = 0; g < gc->gq.size(); ++g)
+        if (gc->gq[g] > 0 && gc->cnt[g] > 0) { gc->max_gq = std::max(gc->max_gq, gc->gq[g]); gc->scanned += 1; }
+    if (gc->scanned == 0) return ExactStart::nothing;
+    gc->tp = exact_plan(gc->max_gq, 1, std::max(k, 1), pitch_, num_cu_);
+    gc->tp.lds = exact_scan_lds(gc->tp.qtile, gc->tp.piece, pitch_, k);
+    if (gc->tp.lds > 64 * 1024) return fail("tile exceeds the LDS budget");
+    return ExactStart::ready;
+}
+
+// The queries of the round at sorted positions [off, off + nr) of `order`, a run of one group's queries at a time, each run cut
+// into tiles of qt: f(g, t, tn) for the tile of queries [t, t + tn) of the round, all of group g, in ascending t.
+template <class F>
+static void exact_for_each_tile(const int *query_group, const std::vector<int> &order, int off, int nr, int qt, F &&f)
+{
+    for (int p = 0; p < nr;) {
+        const int g = query_group[order[(size_t)(off + p)]];
+        int e = p + 1;
+        while (e < nr && query_group[order[(size_t)(off + e)]] == g) ++e;
+        for (int t = p; t < e; t += qt) f(g, t, std::min(qt, e - t));
+        p = e;
+    }
+}
+
+// A tile x each of the nch chunks of its group's list (m entries from entry `first` of x_ids_ on, `chunk` per chunk) is an
+// ExactWorkItem; list0: the tile's first list (top-k sinks).
+static void exact_tile_items(std::vector<ExactWorkItem> &wi, int t, int tn, int first, int m, int chunk, int nch, long long list0)
+{
+    for (int c = 0; c < nch; ++c) {
+        const int lo = c * chunk; // (chunk * nch < m + chunk: no overflow of int while m is one)
+        wi.push_back(ExactWorkItem{t, tn, first + lo, std::min(chunk, m - lo), list0, nch, c});
+    }
+}
+
 // ---- hnswdev_exact_knn_grouped: a candidate group per query, every group scanned in one launch --------
 // The groups' id lists are a CSR in x_ids_, built on the device from row_group; the counts come back in one copy.  The queries are
 // uploaded sorted by group (stable), so a group's queries are a run that is cut into tiles, and its list into chunks: a scan block
@@ -3066,39 +3179,16 @@ bool Device::exact_knn_grouped(const float *queries, int nq, long long n_rows, i
                                int n_groups, int *out_ids, float *out_d)
 {
     if (nq <= 0) return true;
-    if (!out_ids || !out_d || k < 1 || n_rows < 0) { set_dev_error("exact_knn_grouped: bad argument"); return false; }
-    if (!row_group || n_row_group < 0) { set_dev_error("exact_knn_grouped: row_group must not be NULL and n_row_group must be >= 0"); return false; }
-    if (!query_group) { set_dev_error("exact_knn_grouped: query_group must not be NULL"); return false; }
-    if (k > kExactMaxK) { set_dev_error("exact_knn_grouped: k = " + std::to_string(k) + " is above the limit of " + std::to_string(kExactMaxK)); return false; }
-    if (!group_args_ok("exact_knn_grouped", query_group, nq, n_groups)) return false;
-    std::vector<int> gq((size_t)n_groups, 0); // queries per group
-    for (int i = 0; i < nq; ++i) gq[(size_t)query_group[i]] += 1;
-    // ids that exist and have a group: a row beyond what was uploaded is never dereferenced, whatever n_rows and n_row_group say
-    const long long n = std::min({n_rows, n_rows_hw_, n_row_group});
-    if (n <= 0) { pad_results(out_ids, out_d, (size_t)nq * (size_t)k); return true; }
-    if (!queries && (nq > n_queries_ || tail_.n > 0)) {
-        set_dev_error("exact_knn_grouped: queries == NULL needs a resident query set of at least nq rows (hnswdev_set_queries)");
-        return false;
-    }
-    if (!bind()) return false;
+    ExactGroupedCall gc;
+    const ExactStart s = exact_grouped_begin("exact_knn_grouped", out_ids && out_d && k >= 1 && n_rows >= 0, queries, nq, n_rows, k, row_group, n_row_group,
+                                             query_group, n_groups, &gc);
+    if (s == ExactStart::nothing) pad_results(out_ids, out_d, (size_t)nq * (size_t)k); // no query has a candidate: padding, no scan
+    if (s != ExactStart::ready) return s == ExactStart::nothing;
     hipStream_t st = S(stream_);
-
-    std::vector<int> cnt, goff; // members of each group, where its segment starts in x_ids_
-    uint64_t listed = 0;
-    if (!exact_group_lists("exact_knn_grouped", row_group, n, n_groups, cnt, goff, &listed)) return false;
-    const size_t G = (size_t)n_groups;
-    int max_gq = 0;
-    uint64_t scanned = 0;
-    for (size_t g = 0; g < G; ++g)
-        if (gq[g] > 0 && cnt[g] > 0) { max_gq = std::max(max_gq, gq[g]); scanned += 1; }
-    if (scanned == 0) { pad_results(out_ids, out_d, (size_t)nq * (size_t)k); return true; } // no query has a candidate: padding, no scan
-
-    // the tile (one for the call: the LDS layout is the launch's) and each scanned group's chunks
-    const ExactPlan tp = exact_plan(max_gq, 1, k, pitch_, num_cu_);
-    if (tp.lds > 64 * 1024) { set_dev_error("exact_knn_grouped: tile exceeds the LDS budget"); return false; }
+    const ExactPlan &tp = gc.tp;
     const int qt = tp.qtile;
-    std::vector<int> gchunk, gnch; // rows per chunk, chunks (0: not scanned)
-    exact_group_chunks(gq, cnt, qt, num_cu_, gchunk, gnch);
+    std::vector<int> gchunk, gnch; // each scanned group's chunks: rows per chunk, chunks (0: not scanned)
+    exact_group_chunks(gc.gq, gc.cnt, qt, num_cu_, gchunk, gnch);
 
     // rounds: ranges of the caller's order within both budgets; inside each the queries sorted by group (counting sort: stable)
     const long long lists_cap = (1LL << 30) / ((long long)k * 8), out_cap = std::max<long long>(1, (1LL << 24) / k);
@@ -3118,34 +3208,22 @@ bool Device::exact_knn_grouped(const float *queries, int nq, long long n_rows, i
     const double *d_qsn;
     if (!exact_sorted_queries("exact_knn_grouped", queries, nq, order, &d_q, &d_qsn)) return false;
 
-    if (!x_evals_.grow(1)) return false;
-    if (!ev0_.create(true) || !ev1_.create(true)) return false;
     std::vector<ExactMergeItem> mi;
     std::vector<ExactWorkItem> wi;
     bool launched = false;
     int off = 0;
     for (const int r1 : round_end) {
         const int nr = r1 - off;
-        // the round's tables: a run of one group's queries at a time
+        // the round's tables: a query's lists follow those of the queries before it in the sorted order
         mi.resize((size_t)nr);
         wi.clear();
         long long lists = 0;
-        for (int p = 0; p < nr;) {
-            const int g = query_group[order[(size_t)(off + p)]];
-            int e = p + 1;
-            while (e < nr && query_group[order[(size_t)(off + e)]] == g) ++e;
-            const int nch = gnch[(size_t)g], m = cnt[(size_t)g], chunk = gchunk[(size_t)g];
-            for (int j = p; j < e; ++j) mi[(size_t)j] = ExactMergeItem{lists + (long long)(j - p) * nch, nch, order[(size_t)(off + j)] - off};
-            if (nch > 0) {
-                for (int t = p; t < e; t += qt)
-                    for (int c = 0; c < nch; ++c) {
-                        const int lo = c * chunk; // (chunk * nch < m + chunk: no overflow of int while m is one)
-                        wi.push_back(ExactWorkItem{t, std::min(qt, e - t), goff[(size_t)g] + lo, std::min(chunk, m - lo), lists + (long long)(t - p) * nch, nch, c});
-                    }
-                lists += (long long)(e - p) * nch;
-            }
-            p = e;
-        }
+        exact_for_each_tile(query_group, order, off, nr, qt, [&](int g, int t, int tn) {
+            const int nch = gnch[(size_t)g];
+            for (int j = t; j < t + tn; ++j) mi[(size_t)j] = ExactMergeItem{lists + (long long)(j - t) * nch, nch, order[(size_t)(off + j)] - off};
+            exact_tile_items(wi, t, tn, gc.goff[(size_t)g], gc.cnt[(size_t)g], gchunk[(size_t)g], nch, lists);
+            lists += (long long)tn * nch;
+        });
         const size_t res = 4u * (size_t)nr * k, b_mi = sizeof(ExactMergeItem) * (size_t)nr, b_wi = sizeof(ExactWorkItem) * wi.size();
         if (wi.empty()) { // no query of this round has a candidate
             pad_results(out_ids + (size_t)off * k, out_d + (size_t)off * k, (size_t)nr * (size_t)k);
@@ -3162,38 +3240,30 @@ bool Device::exact_knn_grouped(const float *queries, int nq, long long n_rows, i
         memcpy(h_tab + b_mi, wi.data(), b_wi);
         HIP_OK(hipMemcpyAsync(x_gwork_, h_tab, b_mi + b_wi, hipMemcpyHostToDevice, st));
         ExactScanArgs a;
-        a.rows = d_rows_; a.row_sn = d_row_sn_;
-        a.queries = d_q + (size_t)off * pitch_;
-        a.q_sn = d_qsn ? d_qsn + off : nullptr;
-        a.dim = pitch_; a.ids = x_ids_; a.m = 0; a.chunk = 0; a.nq = nr; a.qtile = qt; a.piece = tp.piece; a.k = k;
-        a.lists = x_lists_; a.n_chunks = 0; a.evals = x_evals_;
+        if (!exact_scan_args(d_q, d_qsn, off, nr, qt, tp.piece, &a)) return false;
+        a.ids = x_ids_; a.k = k; a.lists = x_lists_;
         ExactTopKGrouped sink;
         sink.items = reinterpret_cast<const ExactWorkItem *>(x_gwork_.get() + b_mi);
-        const bool timed = profiling_;
-        HIP_OK(hipMemsetAsync(x_evals_, 0, sizeof(unsigned long long), st));
-        if (timed) HIP_OK(hipEventRecord(E(ev0_), st));
-        hipError_t e = hipSuccess;
-        with_metric(metric_, [&](auto mt) { e = exact_grouped_scan_launch<mt>(a, sink, (unsigned)wi.size(), tp.lds, st); });
-        HIP_OK(e);
-        HIP_OK(exact_merge_grouped_launch(x_lists_, reinterpret_cast<const ExactMergeItem *>(x_gwork_.get()), k, nr, d_ids, d_d, st));
-        if (timed) HIP_OK(hipEventRecord(E(ev1_), st));
-        HIP_OK(hipMemcpyAsync(hs, d_ids, res, hipMemcpyDeviceToHost, st));
-        HIP_OK(hipMemcpyAsync(hs + res, d_d, res, hipMemcpyDeviceToHost, st));
-        HIP_OK(hipMemcpyAsync(h_ev, x_evals_, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-        HIP_OK(hipStreamSynchronize(st));
+        const auto enqueue = [&]() -> bool {
+            hipError_t e = hipSuccess;
+            with_metric(metric_, [&](auto mt) { e = exact_grouped_scan_launch<mt>(a, sink, (unsigned)wi.size(), tp.lds, st); });
+            HIP_OK(e);
+            HIP_OK(exact_merge_grouped_launch(x_lists_, reinterpret_cast<const ExactMergeItem *>(x_gwork_.get()), k, nr, d_ids, d_d, st));
+            return true;
+        };
+        const auto fetch = [&]() -> bool {
+            HIP_OK(hipMemcpyAsync(hs, d_ids, res, hipMemcpyDeviceToHost, st));
+            HIP_OK(hipMemcpyAsync(hs + res, d_d, res, hipMemcpyDeviceToHost, st));
+            return true;
+        };
+        if (!exact_timed_scan(h_ev, enqueue, fetch)) return false;
         memcpy(out_ids + (size_t)off * k, hs, res);
         memcpy(out_d + (size_t)off * k, hs + res, res);
-        stats_.exact_launches += 1; stats_.exact_evals += *h_ev;
         xg_info_[2] += wi.size();
         launched = true;
-        if (timed) {
-            float ms = 0.f;
-            HIP_OK(hipEventElapsedTime(&ms, E(ev0_), E(ev1_)));
-            stats_.exact_kernel_ms += ms; stats_.exact_timed_launches += 1; stats_.exact_timed_evals += *h_ev;
-        }
         off = r1;
     }
-    if (launched) { xg_info_[0] += 1; xg_info_[1] += scanned; xg_info_[3] += listed; } // (a call that scans nothing counts nowhere)
+    if (launched) { xg_info_[0] += 1; xg_info_[1] += gc.scanned; xg_info_[3] += gc.listed; } // (a call that scans nothing counts nowhere)
     return true;
 }
 
@@ -3231,169 +3301,199 @@ bool Device::exact_copy_out(void *dst, const void *src, size_t bytes)
     return true;
 }
 
-bool Device::exact_range(const float *queries, int nq, long long n_rows, float range, const uint32_t *allow_bits, long long nbits, int *out_counts)
+// What both range calls bring to their lists: the three knobs, read here and nowhere else, and exact_range_finish's scratch.
+struct ExactRangeWork {
+    long long arena_max; // keys of a round's arena (`exact_range_arena` forces it)
+    long long pick;      // pass A's capacity per query, where the candidates and the arena allow as much (`exact_range_cap` forces it)
+    int sort_max;        // the longest list exact_range_sort_kernel orders (`exact_range_sort` lowers it)
+    std::vector<long long> ooff; // per segment: where its list goes among those ordered on the device
+    std::vector<unsigned long long> keys;
+    std::vector<int> t_ids;
+    std::vector<float> t_d;
+    ExactRangeWork()
+    {
+        const int d_arena = diag("exact_range_arena", 0), d_cap = diag("exact_range_cap", 0), d_sort = diag("exact_range_sort", 0);
+        arena_max = d_arena > 0 ? d_arena : kExactRangeArena;
+        pick = d_cap > 0 ? (long long)d_cap : kExactRangePickCap;
+        sort_max = d_sort > 0 ? std::min(d_sort, kExactRangeSortMax) : kExactRangeSortMax;
+    }
+};
+
+// A range call around its `body`: the results of the call before are dropped first, and a failed call keeps nothing -- no
+// results, every count 0 where the caller gave counts.
+bool Device::exact_range_call(int nq, int *out_counts, const std::function<bool()> &body)
 {
-    if (exact_range_run(queries, nq, n_rows, range, allow_bits, nbits, out_counts)) return true;
-    xr_ids_.clear(); // a failed call keeps nothing
+    xr_ids_.clear();
+    xr_d_.clear();
+    if (body()) return true;
+    xr_ids_.clear();
     xr_d_.clear();
     for (int i = 0; out_counts && i < nq; ++i) out_counts[i] = 0;
     return false;
 }
 
-bool Device::exact_range_run(const float *queries, int nq, long long n_rows, float range, const uint32_t *allow_bits, long long nbits, int *out_counts)
+// The lists of segments [0, ns) of the arena, c[s] keys each (0: nothing to do for that segment), every one inside its segment,
+// which starts at seg[s]: ordered and written to the call's results, which have room for them.  Segment s is query sq[s] of the
+// round (nullptr: s itself), and that query's list starts at xr_ids_[base + obase[query]].  counts_on_device: x_rcnt_ holds c[]
+// as the scan left it; otherwise c[] goes up first -- the kernel orders what counts[] says, so the segments that are not to be
+// read get 0.  *by_device: lists of two or more keys that exact_range_sort_kernel ordered; *by_host: lists ordered here.  The
+// stream is idle and the pinned stage free when this returns.
+bool Device::exact_range_finish(ExactRangeWork &w, int ns, const unsigned *c, const long long *seg, const int *sq, const long long *obase, size_t base,
+                                bool counts_on_device, uint64_t *by_device, uint64_t *by_host)
 {
-    xr_ids_.clear();
-    xr_d_.clear();
-    if (nq <= 0) return true;
-    if (!allow_bits) nbits = 0; // no filter: nbits means nothing, whatever the caller left in it
-    if (!out_counts || n_rows < 0 || nbits < 0) { set_dev_error("exact_range: bad argument"); return false; }
-    for (int i = 0; i < nq; ++i) out_counts[i] = 0;
-    // rows that exist: a row beyond what was uploaded is never dereferenced, whatever n_rows and the bitset say
-    const long long n = std::min(n_rows, n_rows_hw_), n_allow = allow_bits ? std::min(nbits, n) : n;
-    if (n_allow <= 0 || (allow_bits && !allows_any(allow_bits, nbits, n))) return true; // nothing to measure: empty lists, no launch
-    const float *d_q;
-    const double *d_qsn;
-    long long m;
-    if (!exact_queries("exact_range", queries, nq, &d_q, &d_qsn) || !bind() || !exact_id_list(allow_bits, n_allow, &m)) return false;
     hipStream_t st = S(stream_);
-    ExactPlan p = exact_plan(std::min(nq, 65536), m, 1, pitch_, num_cu_); // tile and chunks as for lists of one key: this sink keeps none
-    p.lds = exact_scan_lds(p.qtile, p.piece, pitch_, 0);
-    if (p.lds > 64 * 1024) { set_dev_error("exact_range: tile exceeds the LDS budget"); return false; }
-    const int d_arena = diag("exact_range_arena", 0), d_cap = diag("exact_range_cap", 0), d_sort = diag("exact_range_sort", 0);
-    const long long arena_max = d_arena > 0 ? d_arena : kExactRangeArena;
-    const int sort_max = d_sort > 0 ? std::min(d_sort, kExactRangeSortMax) : kExactRangeSortMax;
-    const long long cap = std::min<long long>({d_cap > 0 ? (long long)d_cap : kExactRangePickCap, m, arena_max});
-    const long long round = std::max<long long>(1, std::min<long long>({(long long)nq, 65536LL, arena_max / cap}));
-    if (!x_rcnt_.grow((size_t)round) || !x_rseg_.grow((size_t)round + 1) || !x_rooff_.grow((size_t)round) || !x_evals_.grow(1)) return false;
-    if (!ev0_.create(true) || !ev1_.create(true)) return false;
-    std::vector<long long> seg((size_t)round + 1), ooff((size_t)round);
-    std::vector<unsigned> cnt((size_t)round), cnt_b;
-    std::vector<unsigned long long> keys;
-    std::vector<int> t_ids;
-    std::vector<float> t_d;
-
-    // one scan of queries [q0, q0 + nr) with the segments seg[0 .. nr]: the counts into c[0 .. nr)
-    const auto scan = [&](long long q0, int nr, unsigned *c) -> bool {
-        if (!x_rarena_.grow((size_t)std::max<long long>(seg[(size_t)nr], 1))) return false;
-        char *hs = static_cast<char *>(pinned_stage(8 * ((size_t)nr + 1) + 4 * (size_t)nr + 8));
+    size_t on_dev = 0;
+    int n_dev = 0;
+    w.ooff.resize((size_t)ns);
+    for (int s = 0; s < ns; ++s) {
+        w.ooff[(size_t)s] = (long long)on_dev;
+        if (c[s] > 0 && c[s] <= (unsigned)w.sort_max) { on_dev += c[s]; ++n_dev; }
+    }
+    if (n_dev > 0) {
+        if (!x_rout_.grow(2 * on_dev)) return false;
+        char *hs = static_cast<char *>(pinned_stage(12 * (size_t)ns));
         if (!hs) return false;
-        unsigned long long *h_ev = reinterpret_cast<unsigned long long *>(hs);
-        long long *h_seg = reinterpret_cast<long long *>(hs + 8);
-        unsigned *h_cnt = reinterpret_cast<unsigned *>(hs + 8 + 8 * ((size_t)nr + 1));
-        memcpy(h_seg, seg.data(), 8 * ((size_t)nr + 1));
-        ExactScanArgs a;
-        a.rows = d_rows_; a.row_sn = d_row_sn_;
-        a.queries = d_q + (size_t)q0 * pitch_;
-        a.q_sn = d_qsn ? d_qsn + q0 : nullptr;
-        a.dim = pitch_; a.ids = allow_bits ? x_ids_ : nullptr; a.m = m; a.chunk = p.chunk; a.nq = nr; a.qtile = p.qtile; a.piece = p.piece; a.k = 0;
-        a.lists = nullptr; a.n_chunks = p.n_chunks; a.evals = x_evals_;
-        ExactRange sink;
-        sink.range = range; sink.counts = x_rcnt_; sink.seg_off = x_rseg_; sink.arena = x_rarena_;
-        const unsigned tiles = (unsigned)((nr + p.qtile - 1) / p.qtile);
-        const bool timed = profiling_;
-        HIP_OK(hipMemcpyAsync(x_rseg_, h_seg, 8 * ((size_t)nr + 1), hipMemcpyHostToDevice, st));
-        HIP_OK(hipMemsetAsync(x_rcnt_, 0, 4 * (size_t)nr, st));
-        HIP_OK(hipMemsetAsync(x_evals_, 0, sizeof(unsigned long long), st));
-        if (timed) HIP_OK(hipEventRecord(E(ev0_), st));
-        hipError_t e = hipSuccess;
-        with_metric(metric_, [&](auto mt) { e = exact_range_scan_launch<mt>(a, sink, tiles, p.lds, st); });
-        HIP_OK(e);
-        if (timed) HIP_OK(hipEventRecord(E(ev1_), st));
-        HIP_OK(hipMemcpyAsync(h_cnt, x_rcnt_, 4 * (size_t)nr, hipMemcpyDeviceToHost, st));
-        HIP_OK(hipMemcpyAsync(h_ev, x_evals_, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-        HIP_OK(hipStreamSynchronize(st));
-        memcpy(c, h_cnt, 4 * (size_t)nr);
-        // (both sinks are the flat scan: they count in the same family, and a repeated pass counts its pairs again)
-        stats_.exact_launches += 1; stats_.exact_evals += *h_ev;
-        if (timed) {
-            float ms = 0.f;
-            HIP_OK(hipEventElapsedTime(&ms, E(ev0_), E(ev1_)));
-            stats_.exact_kernel_ms += ms; stats_.exact_timed_launches += 1; stats_.exact_timed_evals += *h_ev;
+        memcpy(hs, w.ooff.data(), 8 * (size_t)ns);
+        HIP_OK(hipMemcpyAsync(x_rooff_, hs, 8 * (size_t)ns, hipMemcpyHostToDevice, st));
+        if (!counts_on_device) {
+            memcpy(hs + 8 * (size_t)ns, c, 4 * (size_t)ns);
+            HIP_OK(hipMemcpyAsync(x_rcnt_, hs + 8 * (size_t)ns, 4 * (size_t)ns, hipMemcpyHostToDevice, st));
         }
-        return true;
-    };
-
-    // the lists of queries [q0, q0 + nr), every one inside its segment seg[i] .. : ordered and appended to the call's results
-    const auto finish = [&](long long q0, int nr, const unsigned *c) -> bool {
-        size_t total = 0, on_dev = 0;
-        int n_dev = 0;
-        for (int i = 0; i < nr; ++i) {
-            ooff[(size_t)i] = (long long)on_dev;
-            total += c[i];
-            if (c[i] > 0 && c[i] <= (unsigned)sort_max) { on_dev += c[i]; ++n_dev; }
-        }
-        const size_t base = xr_ids_.size();
-        xr_ids_.resize(base + total);
-        xr_d_.resize(base + total);
-        if (n_dev > 0) {
-            if (!x_rout_.grow(2 * on_dev)) return false;
-            char *hs = static_cast<char *>(pinned_stage(8 * (size_t)nr));
-            if (!hs) return false;
-            memcpy(hs, ooff.data(), 8 * (size_t)nr);
-            HIP_OK(hipMemcpyAsync(x_rooff_, hs, 8 * (size_t)nr, hipMemcpyHostToDevice, st));
-            ExactRangeSortArgs sa;
-            sa.arena = x_rarena_; sa.seg_off = x_rseg_; sa.counts = x_rcnt_; sa.out_off = x_rooff_;
-            sa.out_ids = x_rout_; sa.out_d = reinterpret_cast<float *>(x_rout_.get() + on_dev); sa.sort_max = sort_max;
-            HIP_OK(exact_range_sort_launch(sa, nr, st));
-            HIP_OK(hipStreamSynchronize(st)); // (the pinned stage is used again by the copies)
-            t_ids.resize(on_dev);
-            t_d.resize(on_dev);
-            if (!exact_copy_out(t_ids.data(), sa.out_ids, 4 * on_dev) || !exact_copy_out(t_d.data(), sa.out_d, 4 * on_dev)) return false;
-        }
-        size_t at = base;
-        for (int i = 0; i < nr; ++i) {
-            const size_t ci = c[i];
-            if (ci > 0 && ci <= (size_t)sort_max) {
-                memcpy(xr_ids_.data() + at, t_ids.data() + ooff[(size_t)i], 4 * ci);
-                memcpy(xr_d_.data() + at, t_d.data() + ooff[(size_t)i], 4 * ci);
-                if (ci >= 2) xr_info_[0] += 1;
-            } else if (ci > 0) {
-                keys.resize(ci);
-                if (!exact_copy_out(keys.data(), x_rarena_.get() + seg[(size_t)i], 8 * ci)) return false;
-                std::sort(keys.begin(), keys.end());
-                for (size_t j = 0; j < ci; ++j) { xr_ids_[at + j] = (int)(uint32_t)keys[j]; xr_d_[at + j] = exact_host_key_dist(keys[j]); }
-                xr_info_[1] += 1;
-            }
-            out_counts[q0 + i] = (int)ci;
-            at += ci;
-        }
-        xr_info_[3] += total;
-        return true;
-    };
-
-    for (long long off = 0; off < nq; off += round) {
-        const int nr = (int)std::min<long long>(round, nq - off);
-        for (int i = 0; i <= nr; ++i) seg[(size_t)i] = (long long)i * cap;
-        if (!scan(off, nr, cnt.data())) return false;
-        bool fits = true;
-        for (int i = 0; i < nr; ++i) fits = fits && cnt[(size_t)i] <= (unsigned long long)cap;
-        if (fits) {
-            if (!finish(off, nr, cnt.data())) return false;
-            continue;
-        }
-        // pass B: pieces of the round whose exact counts fit the arena, each with segments of exactly its counts
-        cnt_b.resize((size_t)nr);
-        for (int s0 = 0; s0 < nr;) {
-            int s1 = s0;
-            seg[0] = 0;
-            while (s1 < nr && seg[(size_t)(s1 - s0)] + (long long)cnt[(size_t)s1] <= arena_max) {
-                seg[(size_t)(s1 - s0) + 1] = seg[(size_t)(s1 - s0)] + (long long)cnt[(size_t)s1];
-                ++s1;
-            }
-            if (s1 == s0) {
-                set_dev_error("exact_range: a query has " + std::to_string(cnt[(size_t)s0]) + " results within the range, above the arena's limit of " +
-                              std::to_string(arena_max) + " entries per call round");
-                return false;
-            }
-            xr_info_[2] += 1;
-            if (!scan(off + s0, s1 - s0, cnt_b.data())) return false;
-            for (int i = s0; i < s1; ++i)
-                if (cnt_b[(size_t)(i - s0)] != cnt[(size_t)i]) { set_dev_error("exact_range: the repeated scan counted differently"); return false; }
-            if (!finish(off + s0, s1 - s0, cnt_b.data())) return false;
-            s0 = s1;
+        ExactRangeSortArgs sa;
+        sa.arena = x_rarena_; sa.seg_off = x_rseg_; sa.counts = x_rcnt_; sa.out_off = x_rooff_;
+        sa.out_ids = x_rout_; sa.out_d = reinterpret_cast<float *>(x_rout_.get() + on_dev); sa.sort_max = w.sort_max;
+        HIP_OK(exact_range_sort_launch(sa, ns, st));
+        HIP_OK(hipStreamSynchronize(st)); // (the pinned stage is used again by the copies)
+        w.t_ids.resize(on_dev);
+        w.t_d.resize(on_dev);
+        if (!exact_copy_out(w.t_ids.data(), sa.out_ids, 4 * on_dev) || !exact_copy_out(w.t_d.data(), sa.out_d, 4 * on_dev)) return false;
+    }
+    for (int s = 0; s < ns; ++s) {
+        const size_t cs = c[s], at = base + (size_t)obase[(size_t)(sq ? sq[s] : s)];
+        if (cs > 0 && cs <= (size_t)w.sort_max) {
+            memcpy(xr_ids_.data() + at, w.t_ids.data() + w.ooff[(size_t)s], 4 * cs);
+            memcpy(xr_d_.data() + at, w.t_d.data() + w.ooff[(size_t)s], 4 * cs);
+            if (cs >= 2) *by_device += 1;
+        } else if (cs > 0) { // longer than the kernel orders: the keys cross and are ordered here (they are unique: the same order)
+            w.keys.resize(cs);
+            if (!exact_copy_out(w.keys.data(), x_rarena_.get() + seg[(size_t)s], 8 * cs)) return false;
+            std::sort(w.keys.begin(), w.keys.end());
+            for (size_t j = 0; j < cs; ++j) { xr_ids_[at + j] = (int)(uint32_t)w.keys[j]; xr_d_[at + j] = exact_host_key_dist(w.keys[j]); }
+            *by_host += 1;
         }
     }
     return true;
+}
+
+// Pass B's next piece: as many of the counts c[s0 .. n) -- exact: pass A's -- as fit the arena together, with segments of
+// exactly those counts in seg[0 .. *s1 - s0].  A count that the arena cannot hold alone fails the call.
+static bool exact_range_piece(const char *who, const unsigned *c, size_t n, size_t s0, long long arena_max, std::vector<long long> &seg, size_t *s1)
+{
+    size_t s = s0;
+    seg[0] = 0;
+    for (; s < n && seg[s - s0] + (long long)c[s] <= arena_max; ++s) seg[s - s0 + 1] = seg[s - s0] + (long long)c[s];
+    *s1 = s;
+    if (s > s0) return true;
+    set_dev_error(std::string(who) + ": a query has " + std::to_string(c[s0]) + " results within the range, above the arena's limit of " +
+                  std::to_string(arena_max) + " entries per call round");
+    return false;
+}
+
+// ... and what its scan counted against pass A's counts of the same n segments: the segments were cut to these, so they must agree
+static bool exact_range_recount_ok(const char *who, const unsigned *again, const unsigned *first, size_t n)
+{
+    if (std::equal(again, again + n, first)) return true;
+    set_dev_error(std::string(who) + ": the repeated scan counted differently");
+    return false;
+}
+
+bool Device::exact_range(const float *queries, int nq, long long n_rows, float range, const uint32_t *allow_bits, long long nbits, int *out_counts)
+{
+    return exact_range_call(nq, out_counts, [&]() -> bool {
+        if (nq <= 0) return true;
+        if (!out_counts || n_rows < 0 || (allow_bits && nbits < 0)) { set_dev_error("exact_range: bad argument"); return false; }
+        for (int i = 0; i < nq; ++i) out_counts[i] = 0;
+        ExactScanInput in;
+        const ExactStart s = exact_scan_begin("exact_range", queries, nq, n_rows, allow_bits, nbits, &in);
+        if (s != ExactStart::ready) return s == ExactStart::nothing; // (nothing to measure: empty lists, no launch)
+        hipStream_t st = S(stream_);
+        ExactPlan p = exact_plan(std::min(nq, 65536), in.m, 1, pitch_, num_cu_); // tile and chunks as for lists of one key: this sink keeps none
+        p.lds = exact_scan_lds(p.qtile, p.piece, pitch_, 0);
+        if (p.lds > 64 * 1024) { set_dev_error("exact_range: tile exceeds the LDS budget"); return false; }
+        ExactRangeWork w;
+        const long long cap = std::min<long long>({w.pick, in.m, w.arena_max});
+        const long long round = std::max<long long>(1, std::min<long long>({(long long)nq, 65536LL, w.arena_max / cap}));
+        if (!x_rcnt_.grow((size_t)round) || !x_rseg_.grow((size_t)round + 1) || !x_rooff_.grow((size_t)round)) return false;
+        std::vector<long long> seg((size_t)round + 1), obase((size_t)round);
+        std::vector<unsigned> cnt((size_t)round), cnt_b;
+
+        // one scan of queries [q0, q0 + nr) with the segments seg[0 .. nr]: the counts into c[0 .. nr)
+        const auto scan = [&](long long q0, int nr, unsigned *c) -> bool {
+            if (!x_rarena_.grow((size_t)std::max<long long>(seg[(size_t)nr], 1))) return false;
+            char *hs = static_cast<char *>(pinned_stage(8 * ((size_t)nr + 1) + 4 * (size_t)nr + 8));
+            if (!hs) return false;
+            unsigned long long *h_ev = reinterpret_cast<unsigned long long *>(hs);
+            long long *h_seg = reinterpret_cast<long long *>(hs + 8);
+            unsigned *h_cnt = reinterpret_cast<unsigned *>(hs + 8 + 8 * ((size_t)nr + 1));
+            memcpy(h_seg, seg.data(), 8 * ((size_t)nr + 1));
+            ExactScanArgs a;
+            if (!exact_scan_args(in.d_q, in.d_qsn, q0, nr, p.qtile, p.piece, &a)) return false;
+            a.ids = in.ids; a.m = in.m; a.chunk = p.chunk; a.n_chunks = p.n_chunks;
+            ExactRange sink;
+            sink.range = range; sink.counts = x_rcnt_; sink.seg_off = x_rseg_; sink.arena = x_rarena_;
+            const unsigned tiles = (unsigned)((nr + p.qtile - 1) / p.qtile);
+            HIP_OK(hipMemcpyAsync(x_rseg_, h_seg, 8 * ((size_t)nr + 1), hipMemcpyHostToDevice, st));
+            HIP_OK(hipMemsetAsync(x_rcnt_, 0, 4 * (size_t)nr, st));
+            const auto enqueue = [&]() -> bool {
+                hipError_t e = hipSuccess;
+                with_metric(metric_, [&](auto mt) { e = exact_range_scan_launch<mt>(a, sink, tiles, p.lds, st); });
+                HIP_OK(e);
+                return true;
+            };
+            const auto fetch = [&]() -> bool { HIP_OK(hipMemcpyAsync(h_cnt, x_rcnt_, 4 * (size_t)nr, hipMemcpyDeviceToHost, st)); return true; };
+            if (!exact_timed_scan(h_ev, enqueue, fetch)) return false;
+            memcpy(c, h_cnt, 4 * (size_t)nr);
+            return true;
+        };
+
+        // the lists of queries [q0, q0 + nr), every one inside its segment seg[i] .. : ordered and appended to the call's results
+        const auto finish = [&](long long q0, int nr, const unsigned *c) -> bool {
+            size_t total = 0;
+            for (int i = 0; i < nr; ++i) {
+                obase[(size_t)i] = (long long)total;
+                total += c[i];
+                out_counts[q0 + i] = (int)c[i];
+            }
+            const size_t base = xr_ids_.size();
+            xr_ids_.resize(base + total);
+            xr_d_.resize(base + total);
+            if (!exact_range_finish(w, nr, c, seg.data(), nullptr, obase.data(), base, true, &xr_info_[0], &xr_info_[1])) return false;
+            xr_info_[3] += total;
+            return true;
+        };
+
+        for (long long off = 0; off < nq; off += round) {
+            const int nr = (int)std::min<long long>(round, nq - off);
+            for (int i = 0; i <= nr; ++i) seg[(size_t)i] = (long long)i * cap;
+            if (!scan(off, nr, cnt.data())) return false;
+            bool fits = true;
+            for (int i = 0; i < nr; ++i) fits = fits && cnt[(size_t)i] <= (unsigned long long)cap;
+            if (fits) {
+                if (!finish(off, nr, cnt.data())) return false;
+                continue;
+            }
+            // pass B: pieces of the round whose exact counts fit the arena, each with segments of exactly its counts
+            cnt_b.resize((size_t)nr);
+            for (size_t s0 = 0, s1; s0 < (size_t)nr; s0 = s1) {
+                if (!exact_range_piece("exact_range", cnt.data(), (size_t)nr, s0, w.arena_max, seg, &s1)) return false;
+                xr_info_[2] += 1;
+                const int ns = (int)(s1 - s0);
+                if (!scan(off + (long long)s0, ns, cnt_b.data()) || !exact_range_recount_ok("exact_range", cnt_b.data(), cnt.data() + s0, (size_t)ns)) return false;
+                if (!finish(off + (long long)s0, ns, cnt_b.data())) return false;
+            }
+        }
+        return true;
+    });
 }
 
 // ---- hnswdev_exact_range_grouped: the range sink behind exact_knn_grouped's work items ------------------
@@ -3406,265 +3506,147 @@ bool Device::exact_range_run(const float *queries, int nq, long long n_rows, flo
 bool Device::exact_range_grouped(const float *queries, int nq, long long n_rows, float range, const int *row_group, long long n_row_group,
                                  const int *query_group, int n_groups, int *out_counts)
 {
-    if (exact_range_grouped_run(queries, nq, n_rows, range, row_group, n_row_group, query_group, n_groups, out_counts)) return true;
-    xr_ids_.clear(); // a failed call keeps nothing
-    xr_d_.clear();
-    for (int i = 0; out_counts && i < nq; ++i) out_counts[i] = 0;
-    return false;
-}
+    return exact_range_call(nq, out_counts, [&]() -> bool {
+        if (nq <= 0) return true;
+        ExactGroupedCall gc;
+        const ExactStart s = exact_grouped_begin("exact_range_grouped", out_counts && n_rows >= 0, queries, nq, n_rows, 0, row_group, n_row_group,
+                                                 query_group, n_groups, &gc);
+        if (s == ExactStart::failed) return false;
+        for (int i = 0; i < nq; ++i) out_counts[i] = 0;
+        if (s == ExactStart::nothing) return true; // no query has a candidate: empty lists, no scan
+        hipStream_t st = S(stream_);
+        const std::vector<int> &cnt = gc.cnt;
+        const ExactPlan &tp = gc.tp;
+        const int qt = tp.qtile;
+        std::vector<int> gchunk((size_t)n_groups, 0), gnch((size_t)n_groups, 0); // each scan's chunks: rows per chunk, chunks per group (planned by `items` below)
 
-bool Device::exact_range_grouped_run(const float *queries, int nq, long long n_rows, float range, const int *row_group, long long n_row_group,
-                                     const int *query_group, int n_groups, int *out_counts)
-{
-    xr_ids_.clear();
-    xr_d_.clear();
-    if (nq <= 0) return true;
-    if (!out_counts || n_rows < 0) { set_dev_error("exact_range_grouped: bad argument"); return false; }
-    if (!row_group || n_row_group < 0) { set_dev_error("exact_range_grouped: row_group must not be NULL and n_row_group must be >= 0"); return false; }
-    if (!query_group) { set_dev_error("exact_range_grouped: query_group must not be NULL"); return false; }
-    if (!group_args_ok("exact_range_grouped", query_group, nq, n_groups)) return false;
-    for (int i = 0; i < nq; ++i) out_counts[i] = 0;
-    std::vector<int> gq((size_t)n_groups, 0); // queries per group
-    for (int i = 0; i < nq; ++i) gq[(size_t)query_group[i]] += 1;
-    // ids that exist and have a group: a row beyond what was uploaded is never dereferenced, whatever n_rows and n_row_group say
-    const long long n = std::min({n_rows, n_rows_hw_, n_row_group});
-    if (n <= 0) return true;
-    if (!queries && (nq > n_queries_ || tail_.n > 0)) {
-        set_dev_error("exact_range_grouped: queries == NULL needs a resident query set of at least nq rows (hnswdev_set_queries)");
-        return false;
-    }
-    if (!bind()) return false;
-    hipStream_t st = S(stream_);
+        ExactRangeWork w;
+        const auto cap_of = [&](int i) { return std::min<long long>({w.pick, (long long)cnt[(size_t)query_group[i]], w.arena_max}); };
 
-    std::vector<int> cnt, goff; // members of each group, where its segment starts in x_ids_
-    uint64_t listed = 0; // (not reported by this call)
-    if (!exact_group_lists("exact_range_grouped", row_group, n, n_groups, cnt, goff, &listed)) return false;
-    int max_gq = 0;
-    for (size_t g = 0; g < (size_t)n_groups; ++g)
-        if (gq[g] > 0 && cnt[g] > 0) max_gq = std::max(max_gq, gq[g]);
-    if (max_gq == 0) return true; // no query has a candidate: empty lists, no scan
-
-    // the tile (one for the call, as for lists of one key: this sink keeps none)
-    ExactPlan tp = exact_plan(max_gq, 1, 1, pitch_, num_cu_);
-    tp.lds = exact_scan_lds(tp.qtile, tp.piece, pitch_, 0);
-    if (tp.lds > 64 * 1024) { set_dev_error("exact_range_grouped: tile exceeds the LDS budget"); return false; }
-    const int qt = tp.qtile;
-    std::vector<int> gchunk((size_t)n_groups, 0), gnch((size_t)n_groups, 0); // each scan's chunks: rows per chunk, chunks per group (planned by `items` below)
-
-    const int d_arena = diag("exact_range_arena", 0), d_cap = diag("exact_range_cap", 0), d_sort = diag("exact_range_sort", 0);
-    const long long arena_max = d_arena > 0 ? d_arena : kExactRangeArena;
-    const int sort_max = d_sort > 0 ? std::min(d_sort, kExactRangeSortMax) : kExactRangeSortMax;
-    const long long pick = d_cap > 0 ? (long long)d_cap : kExactRangePickCap;
-    const auto cap_of = [&](int i) { return std::min<long long>({pick, (long long)cnt[(size_t)query_group[i]], arena_max}); };
-
-    // rounds: ranges of the caller's order whose pass-A capacities fit the arena, at most 65 536 queries each
-    std::vector<int> round_end;
-    int max_round = 0;
-    {
-        long long keys = 0;
-        int r0 = 0;
-        for (int i = 0; i < nq; ++i) {
-            const long long c = cap_of(i);
-            if (i > r0 && (keys + c > arena_max || i - r0 >= 65536)) { round_end.push_back(i); max_round = std::max(max_round, i - r0); keys = 0; r0 = i; }
-            keys += c;
-        }
-        round_end.push_back(nq);
-        max_round = std::max(max_round, nq - r0);
-    }
-    const std::vector<int> order = exact_group_order(query_group, n_groups, round_end);
-    const float *d_q;
-    const double *d_qsn;
-    if (!exact_sorted_queries("exact_range_grouped", queries, nq, order, &d_q, &d_qsn)) return false;
-
-    if (!x_rcnt_.grow((size_t)max_round) || !x_rseg_.grow((size_t)max_round + 1) || !x_rooff_.grow((size_t)max_round) || !x_evals_.grow(1)) return false;
-    if (!ev0_.create(true) || !ev1_.create(true)) return false;
-    std::vector<long long> seg((size_t)max_round + 1), ooff((size_t)max_round), obase((size_t)max_round);
-    std::vector<unsigned> cnt_a((size_t)max_round), cnt_b, cnt_fit;
-    std::vector<int> dest((size_t)max_round), slot_q, ov;
-    std::vector<ExactWorkItem> wi;
-    std::vector<unsigned long long> keys;
-    std::vector<int> t_ids;
-    std::vector<float> t_d;
-    bool launched = false;
-
-    // the work items of the round at [off, off + nr): every (tile, chunk) of every scanned group whose tile holds a query with a
-    // segment in dest.  The chunks are planned for the tiles that are scanned (first the queries of those tiles are counted per
-    // group): a repeated pass of a few tiles is cut into many chunks, not left to a few blocks that each walk a whole group.
-    const auto tile_wanted = [&](int t, int tn) {
-        for (int j = t; j < t + tn; ++j)
-            if (dest[(size_t)j] >= 0) return true;
-        return false;
-    };
-    const auto items = [&](int off, int nr) {
-        wi.clear();
-        std::vector<int> wq(gq.size(), 0); // per group the queries of the wanted tiles (a count of its own: gq stays the call's)
-        for (int pass = 0; pass < 2; ++pass) {
-            if (pass == 1) exact_group_chunks(wq, cnt, qt, num_cu_, gchunk, gnch);
-            for (int p = 0; p < nr;) {
-                const int g = query_group[order[(size_t)(off + p)]];
-                int e = p + 1;
-                while (e < nr && query_group[order[(size_t)(off + e)]] == g) ++e;
-                const int nch = gnch[(size_t)g], m = cnt[(size_t)g], chunk = gchunk[(size_t)g];
-                for (int t = p; m > 0 && t < e; t += qt) {
-                    const int tn = std::min(qt, e - t);
-                    if (!tile_wanted(t, tn)) continue;
-                    if (pass == 0) { wq[(size_t)g] += tn; continue; }
-                    for (int c = 0; c < nch; ++c) {
-                        const int lo = c * chunk; // (chunk * nch < m + chunk: no overflow of int while m is one)
-                        wi.push_back(ExactWorkItem{t, tn, goff[(size_t)g] + lo, std::min(chunk, m - lo), 0, nch, c});
-                    }
-                }
-                p = e;
+        // rounds: ranges of the caller's order whose pass-A capacities fit the arena, at most 65 536 queries each
+        std::vector<int> round_end;
+        int max_round = 0;
+        {
+            long long keys = 0;
+            int r0 = 0;
+            for (int i = 0; i < nq; ++i) {
+                const long long c = cap_of(i);
+                if (i > r0 && (keys + c > w.arena_max || i - r0 >= 65536)) { round_end.push_back(i); max_round = std::max(max_round, i - r0); keys = 0; r0 = i; }
+                keys += c;
             }
+            round_end.push_back(nq);
+            max_round = std::max(max_round, nq - r0);
         }
-    };
+        const std::vector<int> order = exact_group_order(query_group, n_groups, round_end);
+        const float *d_q;
+        const double *d_qsn;
+        if (!exact_sorted_queries("exact_range_grouped", queries, nq, order, &d_q, &d_qsn)) return false;
 
-    // one scan of the round at [off, off + nr) with `ns` segments seg[0 .. ns], dest[0 .. nr) and the work items wi: the counts of
-    // the segments into c[0 .. ns)
-    const auto scan = [&](int off, int nr, int ns, unsigned *c) -> bool {
-        if (!x_rarena_.grow((size_t)std::max<long long>(seg[(size_t)ns], 1))) return false;
-        const size_t b_wi = sizeof(ExactWorkItem) * wi.size(), b_dest = 4 * (size_t)nr, b_seg = 8 * ((size_t)ns + 1), b_cnt = 4 * (size_t)ns;
-        char *hs = static_cast<char *>(pinned_stage(8 + b_seg + b_wi + b_dest + b_cnt));
-        if (!hs || !x_gwork_.grow(b_wi + b_dest)) return false;
-        unsigned long long *h_ev = reinterpret_cast<unsigned long long *>(hs);
-        char *h_seg = hs + 8, *h_tab = h_seg + b_seg, *h_cnt = h_tab + b_wi + b_dest;
-        memcpy(h_seg, seg.data(), b_seg);
-        memcpy(h_tab, wi.data(), b_wi);
-        memcpy(h_tab + b_wi, dest.data(), b_dest);
-        ExactScanArgs a;
-        a.rows = d_rows_; a.row_sn = d_row_sn_;
-        a.queries = d_q + (size_t)off * pitch_;
-        a.q_sn = d_qsn ? d_qsn + off : nullptr;
-        a.dim = pitch_; a.ids = x_ids_; a.m = 0; a.chunk = 0; a.nq = nr; a.qtile = qt; a.piece = tp.piece; a.k = 0;
-        a.lists = nullptr; a.n_chunks = 0; a.evals = x_evals_;
-        ExactRangeGrouped sink;
-        sink.range = range; sink.counts = x_rcnt_; sink.seg_off = x_rseg_; sink.arena = x_rarena_;
-        sink.items = reinterpret_cast<const ExactWorkItem *>(x_gwork_.get());
-        sink.dest = reinterpret_cast<const int *>(x_gwork_.get() + b_wi);
-        const bool timed = profiling_;
-        HIP_OK(hipMemcpyAsync(x_rseg_, h_seg, b_seg, hipMemcpyHostToDevice, st));
-        HIP_OK(hipMemcpyAsync(x_gwork_, h_tab, b_wi + b_dest, hipMemcpyHostToDevice, st));
-        HIP_OK(hipMemsetAsync(x_rcnt_, 0, b_cnt, st));
-        HIP_OK(hipMemsetAsync(x_evals_, 0, sizeof(unsigned long long), st));
-        if (timed) HIP_OK(hipEventRecord(E(ev0_), st));
-        hipError_t e = hipSuccess;
-        with_metric(metric_, [&](auto mt) { e = exact_range_grouped_scan_launch<mt>(a, sink, (unsigned)wi.size(), tp.lds, st); });
-        HIP_OK(e);
-        if (timed) HIP_OK(hipEventRecord(E(ev1_), st));
-        HIP_OK(hipMemcpyAsync(h_cnt, x_rcnt_, b_cnt, hipMemcpyDeviceToHost, st));
-        HIP_OK(hipMemcpyAsync(h_ev, x_evals_, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-        HIP_OK(hipStreamSynchronize(st));
-        memcpy(c, h_cnt, b_cnt);
-        // (the flat scan's family, as exact_range counts: a repeated pass counts its pairs again, the unwanted queries of its tiles included)
-        stats_.exact_launches += 1; stats_.exact_evals += *h_ev;
-        launched = true;
-        if (timed) {
-            float ms = 0.f;
-            HIP_OK(hipEventElapsedTime(&ms, E(ev0_), E(ev1_)));
-            stats_.exact_kernel_ms += ms; stats_.exact_timed_launches += 1; stats_.exact_timed_evals += *h_ev;
-        }
-        return true;
-    };
+        if (!x_rcnt_.grow((size_t)max_round) || !x_rseg_.grow((size_t)max_round + 1) || !x_rooff_.grow((size_t)max_round)) return false;
+        std::vector<long long> seg((size_t)max_round + 1), obase((size_t)max_round);
+        std::vector<unsigned> cnt_a((size_t)max_round), cnt_b, cnt_fit, cnt_ov;
+        std::vector<int> dest((size_t)max_round), slot_q, ov;
+        std::vector<ExactWorkItem> wi;
+        bool launched = false;
 
-    // the lists of segments [0, ns), c[s] keys each (0: nothing to do for that segment), every one inside its segment: ordered and
-    // written to the call's results.  Segment s is query sq[s] of the round (nullptr: s itself), whose list starts at base + obase[].
-    const auto finish = [&](int ns, const unsigned *c, const int *sq, size_t base, bool counts_on_device) -> bool {
-        size_t on_dev = 0;
-        int n_dev = 0;
-        for (int s = 0; s < ns; ++s) {
-            ooff[(size_t)s] = (long long)on_dev;
-            if (c[s] > 0 && c[s] <= (unsigned)sort_max) { on_dev += c[s]; ++n_dev; }
-        }
-        if (n_dev > 0) {
-            if (!x_rout_.grow(2 * on_dev)) return false;
-            char *hs = static_cast<char *>(pinned_stage(12 * (size_t)ns));
-            if (!hs) return false;
-            memcpy(hs, ooff.data(), 8 * (size_t)ns);
-            HIP_OK(hipMemcpyAsync(x_rooff_, hs, 8 * (size_t)ns, hipMemcpyHostToDevice, st));
-            if (!counts_on_device) { // the kernel orders what counts[] says: the segments that are not to be read get 0
-                memcpy(hs + 8 * (size_t)ns, c, 4 * (size_t)ns);
-                HIP_OK(hipMemcpyAsync(x_rcnt_, hs + 8 * (size_t)ns, 4 * (size_t)ns, hipMemcpyHostToDevice, st));
-            }
-            ExactRangeSortArgs sa;
-            sa.arena = x_rarena_; sa.seg_off = x_rseg_; sa.counts = x_rcnt_; sa.out_off = x_rooff_;
-            sa.out_ids = x_rout_; sa.out_d = reinterpret_cast<float *>(x_rout_.get() + on_dev); sa.sort_max = sort_max;
-            HIP_OK(exact_range_sort_launch(sa, ns, st));
-            HIP_OK(hipStreamSynchronize(st)); // (the pinned stage is used again by the copies)
-            t_ids.resize(on_dev);
-            t_d.resize(on_dev);
-            if (!exact_copy_out(t_ids.data(), sa.out_ids, 4 * on_dev) || !exact_copy_out(t_d.data(), sa.out_d, 4 * on_dev)) return false;
-        }
-        for (int s = 0; s < ns; ++s) {
-            const size_t cs = c[s], at = base + (size_t)obase[(size_t)(sq ? sq[s] : s)];
-            if (cs > 0 && cs <= (size_t)sort_max) {
-                memcpy(xr_ids_.data() + at, t_ids.data() + ooff[(size_t)s], 4 * cs);
-                memcpy(xr_d_.data() + at, t_d.data() + ooff[(size_t)s], 4 * cs);
-                if (cs >= 2) xrg_info_[1] += 1;
-            } else if (cs > 0) {
-                keys.resize(cs);
-                if (!exact_copy_out(keys.data(), x_rarena_.get() + seg[(size_t)s], 8 * cs)) return false;
-                std::sort(keys.begin(), keys.end());
-                for (size_t j = 0; j < cs; ++j) { xr_ids_[at + j] = (int)(uint32_t)keys[j]; xr_d_[at + j] = exact_host_key_dist(keys[j]); }
-                xrg_info_[2] += 1;
-            }
-        }
-        return true;
-    };
+        // the work items of the round at [off, off + nr): every (tile, chunk) of every scanned group whose tile holds a query with a
+        // segment in dest.  The chunks are planned for the tiles that are scanned (first the queries of those tiles are counted per
+        // group): a repeated pass of a few tiles is cut into many chunks, not left to a few blocks that each walk a whole group.
+        const auto tile_wanted = [&](int t, int tn) {
+            for (int j = t; j < t + tn; ++j)
+                if (dest[(size_t)j] >= 0) return true;
+            return false;
+        };
+        const auto items = [&](int off, int nr) {
+            wi.clear();
+            std::vector<int> wq(gc.gq.size(), 0); // per group the queries of the wanted tiles (a count of its own: gc.gq stays the call's)
+            exact_for_each_tile(query_group, order, off, nr, qt, [&](int g, int t, int tn) {
+                if (cnt[(size_t)g] > 0 && tile_wanted(t, tn)) wq[(size_t)g] += tn;
+            });
+            exact_group_chunks(wq, cnt, qt, num_cu_, gchunk, gnch);
+            exact_for_each_tile(query_group, order, off, nr, qt, [&](int g, int t, int tn) {
+                if (cnt[(size_t)g] > 0 && tile_wanted(t, tn)) exact_tile_items(wi, t, tn, gc.goff[(size_t)g], cnt[(size_t)g], gchunk[(size_t)g], gnch[(size_t)g], 0);
+            });
+        };
 
-    int off = 0;
-    for (const int r1 : round_end) {
-        const int nr = r1 - off;
-        // pass A: a segment per query at its place in the caller's order
-        seg[0] = 0;
-        for (int i = 0; i < nr; ++i) seg[(size_t)i + 1] = seg[(size_t)i] + cap_of(off + i);
-        for (int p = 0; p < nr; ++p) dest[(size_t)p] = order[(size_t)(off + p)] - off;
-        items(off, nr);
-        if (wi.empty()) { off = r1; continue; } // no query of this round has a candidate
-        if (!scan(off, nr, nr, cnt_a.data())) return false;
-        const size_t base = xr_ids_.size();
-        size_t total = 0;
-        ov.clear();
-        cnt_fit.assign(cnt_a.begin(), cnt_a.begin() + nr);
-        for (int i = 0; i < nr; ++i) {
-            obase[(size_t)i] = (long long)total;
-            total += cnt_a[(size_t)i];
-            out_counts[off + i] = (int)cnt_a[(size_t)i];
-            if ((long long)cnt_a[(size_t)i] > seg[(size_t)i + 1] - seg[(size_t)i]) { ov.push_back(i); cnt_fit[(size_t)i] = 0; }
-        }
-        xr_ids_.resize(base + total);
-        xr_d_.resize(base + total);
-        if (!finish(nr, cnt_fit.data(), nullptr, base, ov.empty())) return false;
-        // pass B: the queries whose count exceeded its capacity, in pieces whose exact counts fit the arena, each with segments of
-        // exactly its counts; the other queries of their tiles are measured again and their keys dropped
-        for (size_t s0 = 0; s0 < ov.size();) {
-            size_t s1 = s0;
+        // one scan of the round at [off, off + nr) with `ns` segments seg[0 .. ns], dest[0 .. nr) and the work items wi: the counts of
+        // the segments into c[0 .. ns)
+        const auto scan = [&](int off, int nr, int ns, unsigned *c) -> bool {
+            if (!x_rarena_.grow((size_t)std::max<long long>(seg[(size_t)ns], 1))) return false;
+            const size_t b_wi = sizeof(ExactWorkItem) * wi.size(), b_dest = 4 * (size_t)nr, b_seg = 8 * ((size_t)ns + 1), b_cnt = 4 * (size_t)ns;
+            char *hs = static_cast<char *>(pinned_stage(8 + b_seg + b_wi + b_dest + b_cnt));
+            if (!hs || !x_gwork_.grow(b_wi + b_dest)) return false;
+            unsigned long long *h_ev = reinterpret_cast<unsigned long long *>(hs);
+            char *h_seg = hs + 8, *h_tab = h_seg + b_seg, *h_cnt = h_tab + b_wi + b_dest;
+            memcpy(h_seg, seg.data(), b_seg);
+            memcpy(h_tab, wi.data(), b_wi);
+            memcpy(h_tab + b_wi, dest.data(), b_dest);
+            ExactScanArgs a;
+            if (!exact_scan_args(d_q, d_qsn, off, nr, qt, tp.piece, &a)) return false;
+            a.ids = x_ids_;
+            ExactRangeGrouped sink;
+            sink.range = range; sink.counts = x_rcnt_; sink.seg_off = x_rseg_; sink.arena = x_rarena_;
+            sink.items = reinterpret_cast<const ExactWorkItem *>(x_gwork_.get());
+            sink.dest = reinterpret_cast<const int *>(x_gwork_.get() + b_wi);
+            HIP_OK(hipMemcpyAsync(x_rseg_, h_seg, b_seg, hipMemcpyHostToDevice, st));
+            HIP_OK(hipMemcpyAsync(x_gwork_, h_tab, b_wi + b_dest, hipMemcpyHostToDevice, st));
+            HIP_OK(hipMemsetAsync(x_rcnt_, 0, b_cnt, st));
+            const auto enqueue = [&]() -> bool {
+                hipError_t e = hipSuccess;
+                with_metric(metric_, [&](auto mt) { e = exact_range_grouped_scan_launch<mt>(a, sink, (unsigned)wi.size(), tp.lds, st); });
+                HIP_OK(e);
+                return true;
+            };
+            const auto fetch = [&]() -> bool { HIP_OK(hipMemcpyAsync(h_cnt, x_rcnt_, b_cnt, hipMemcpyDeviceToHost, st)); return true; };
+            if (!exact_timed_scan(h_ev, enqueue, fetch)) return false;
+            memcpy(c, h_cnt, b_cnt);
+            launched = true;
+            return true;
+        };
+
+        int off = 0;
+        for (const int r1 : round_end) {
+            const int nr = r1 - off;
+            // pass A: a segment per query at its place in the caller's order
             seg[0] = 0;
-            while (s1 < ov.size() && seg[s1 - s0] + (long long)cnt_a[(size_t)ov[s1]] <= arena_max) {
-                seg[s1 - s0 + 1] = seg[s1 - s0] + (long long)cnt_a[(size_t)ov[s1]];
-                ++s1;
-            }
-            if (s1 == s0) {
-                set_dev_error("exact_range_grouped: a query has " + std::to_string(cnt_a[(size_t)ov[s0]]) + " results within the range, above the arena's limit of " +
-                              std::to_string(arena_max) + " entries per call round");
-                return false;
-            }
-            const int ns = (int)(s1 - s0);
-            slot_q.assign((size_t)nr, -1); // query of the round -> its segment in this piece
-            for (int s = 0; s < ns; ++s) slot_q[(size_t)ov[s0 + (size_t)s]] = s;
-            for (int p = 0; p < nr; ++p) dest[(size_t)p] = slot_q[(size_t)(order[(size_t)(off + p)] - off)];
+            for (int i = 0; i < nr; ++i) seg[(size_t)i + 1] = seg[(size_t)i] + cap_of(off + i);
+            for (int p = 0; p < nr; ++p) dest[(size_t)p] = order[(size_t)(off + p)] - off;
             items(off, nr);
-            xrg_info_[3] += 1;
-            cnt_b.resize((size_t)ns);
-            if (!scan(off, nr, ns, cnt_b.data())) return false;
-            for (int s = 0; s < ns; ++s)
-                if (cnt_b[(size_t)s] != cnt_a[(size_t)ov[s0 + (size_t)s]]) { set_dev_error("exact_range_grouped: the repeated scan counted differently"); return false; }
-            if (!finish(ns, cnt_b.data(), ov.data() + s0, base, true)) return false;
-            s0 = s1;
+            if (wi.empty()) { off = r1; continue; } // no query of this round has a candidate
+            if (!scan(off, nr, nr, cnt_a.data())) return false;
+            const size_t base = xr_ids_.size();
+            size_t total = 0;
+            ov.clear();
+            cnt_ov.clear();
+            cnt_fit.assign(cnt_a.begin(), cnt_a.begin() + nr);
+            for (int i = 0; i < nr; ++i) {
+                obase[(size_t)i] = (long long)total;
+                total += cnt_a[(size_t)i];
+                out_counts[off + i] = (int)cnt_a[(size_t)i];
+                if ((long long)cnt_a[(size_t)i] > seg[(size_t)i + 1] - seg[(size_t)i]) { ov.push_back(i); cnt_ov.push_back(cnt_a[(size_t)i]); cnt_fit[(size_t)i] = 0; }
+            }
+            xr_ids_.resize(base + total);
+            xr_d_.resize(base + total);
+            if (!exact_range_finish(w, nr, cnt_fit.data(), seg.data(), nullptr, obase.data(), base, ov.empty(), &xrg_info_[1], &xrg_info_[2])) return false;
+            // pass B: the queries whose count exceeded its capacity (ov, their counts in cnt_ov), in pieces whose exact counts fit the
+            // arena, each with segments of exactly its counts; the other queries of their tiles are measured again and their keys dropped
+            for (size_t s0 = 0, s1; s0 < ov.size(); s0 = s1) {
+                if (!exact_range_piece("exact_range_grouped", cnt_ov.data(), ov.size(), s0, w.arena_max, seg, &s1)) return false;
+                const int ns = (int)(s1 - s0);
+                slot_q.assign((size_t)nr, -1); // query of the round -> its segment in this piece
+                for (int s = 0; s < ns; ++s) slot_q[(size_t)ov[s0 + (size_t)s]] = s;
+                for (int p = 0; p < nr; ++p) dest[(size_t)p] = slot_q[(size_t)(order[(size_t)(off + p)] - off)];
+                items(off, nr);
+                xrg_info_[3] += 1;
+                cnt_b.resize((size_t)ns);
+                if (!scan(off, nr, ns, cnt_b.data()) || !exact_range_recount_ok("exact_range_grouped", cnt_b.data(), cnt_ov.data() + s0, (size_t)ns)) return false;
+                if (!exact_range_finish(w, ns, cnt_b.data(), seg.data(), ov.data() + s0, obase.data(), base, true, &xrg_info_[1], &xrg_info_[2])) return false;
+            }
+            off = r1;
         }
-        off = r1;
-    }
-    if (launched) xrg_info_[0] += 1;
-    return true;
+        if (launched) xrg_info_[0] += 1;
+        return true;
+    });
 }
 
 bool Device::exact_range_results(int *out_ids, float *out_d)

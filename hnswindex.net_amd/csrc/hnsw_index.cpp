@@ -1828,6 +1828,16 @@ int HnswIndex::exact_knn_query_grouped(const float *queries, int count, int dim,
     return 0;
 }
 
+// What both range scans end with: `ran` is what the device call returned; the lists it left in the context go to ids / dists.
+static int exact_range_fetch(Device &dev, bool ran, std::vector<int> &ids, std::vector<float> &dists, std::string &err)
+{
+    ids.resize(ran ? dev.exact_range_total() : 0);
+    dists.resize(ids.size());
+    if (ran && dev.exact_range_results(ids.data(), dists.data())) return 0;
+    err = get_dev_error();
+    return -1;
+}
+
 // The flat scan with the range sink: exact_knn_query's candidates; per query every one within `range`, ascending by
 // (distance, id).  counts[i], and the lists concatenated in query order in ids / dists.  Always on the device, on the primary context.
 int HnswIndex::exact_range_query(const float *queries, int count, int dim, float range, const uint32_t *allow_bits, long long nbits, int *counts,
@@ -1843,11 +1853,7 @@ int HnswIndex::exact_range_query(const float *queries, int count, int dim, float
     std::vector<uint32_t> live;
     const long long length = exact_candidates(allow_bits, nbits, live);
     // (the scan stages its queries in a buffer of its own: the resident set, sharded or not, stays what it was)
-    if (!dev_->exact_range(queries, count, length, range, allow_bits, nbits, counts)) { err = get_dev_error(); return -1; }
-    ids.resize(dev_->exact_range_total());
-    dists.resize(ids.size());
-    if (!dev_->exact_range_results(ids.data(), dists.data())) { err = get_dev_error(); return -1; }
-    return 0;
+    return exact_range_fetch(*dev_, dev_->exact_range(queries, count, length, range, allow_bits, nbits, counts), ids, dists, err);
 }
 
 // The range sink with a candidate group per query.  The labels go to the device as live_labels leaves them.
@@ -1866,11 +1872,7 @@ int HnswIndex::exact_range_query_grouped(const float *queries, int count, int di
     std::vector<int> live;
     if (live_labels(row_group, n_row_group, live) && n_row_group == 0) return 0; // vacant slots and no label: no candidate
     // (the scan stages its queries in a buffer of its own: the resident set, sharded or not, stays what it was)
-    if (!dev_->exact_range_grouped(queries, count, length, range, row_group, n_row_group, query_group, n_groups, counts)) { err = get_dev_error(); return -1; }
-    ids.resize(dev_->exact_range_total());
-    dists.resize(ids.size());
-    if (!dev_->exact_range_results(ids.data(), dists.data())) { err = get_dev_error(); return -1; }
-    return 0;
+    return exact_range_fetch(*dev_, dev_->exact_range_grouped(queries, count, length, range, row_group, n_row_group, query_group, n_groups, counts), ids, dists, err);
 }
 
 // GetInfo / GetConnectedComponentCounts (HNSWIndex.cs:192-205) on the graph mirror, a layer at a time.  The live
