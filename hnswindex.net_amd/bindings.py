@@ -137,6 +137,17 @@ lib.hnsw_mi355x_exact_knn_query_grouped.argtypes = [ct.c_void_p, _F, ct.c_int, c
 lib.hnsw_mi355x_exact_grouped_info.restype = ct.c_int
 lib.hnsw_mi355x_exact_grouped_info.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
 _KNN_GROUPED_INFO = ("calls", "launched", "skipped", "handbacks")   # hnswdev_knn_grouped_info's out[0 .. 3]
+_KNN_TAGGED_INFO = ("calls", "masks", "launched", "skipped", "handbacks")   # hnswdev_knn_tagged_info's out[0 .. 4]
+_EXACT_TAGGED_INFO = ("calls", "masks", "scanned", "skipped", "ids_listed", "batches")   # hnswdev_exact_tagged_info's out[0 .. 5]
+_TAG_MATCH = {"any": 0, "all": 1}   # the `match` argument of the tagged calls
+lib.hnsw_mi355x_knn_query_tagged.restype = ct.c_int
+lib.hnsw_mi355x_knn_query_tagged.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_int, ct.c_int, ct.c_int, _U32, ct.c_longlong, _U32, ct.c_int, _I, _F]
+lib.hnsw_mi355x_exact_knn_query_tagged.restype = ct.c_int
+lib.hnsw_mi355x_exact_knn_query_tagged.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_int, ct.c_int, _U32, ct.c_longlong, _U32, ct.c_int, _I, _F]
+lib.hnsw_mi355x_knn_tagged_info.restype = ct.c_int
+lib.hnsw_mi355x_knn_tagged_info.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
+lib.hnsw_mi355x_exact_tagged_info.restype = ct.c_int
+lib.hnsw_mi355x_exact_tagged_info.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
 lib.hnsw_mi355x_knn_query_grouped.restype = ct.c_int
 lib.hnsw_mi355x_knn_query_grouped.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_int, ct.c_int, ct.c_int, _I, ct.c_longlong, _I, ct.c_int, _I, _F]
 _RANGE_GROUPED_INFO = ("calls", "launched", "skipped", "host_finished")   # hnswdev_range_grouped_info's out[0 .. 3]
@@ -307,6 +318,16 @@ lib.hnswdev_exact_grouped_info.restype = ct.c_int
 lib.hnswdev_exact_grouped_info.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
 lib.hnswdev_exact_grouped_list_ms.restype = ct.c_int
 lib.hnswdev_exact_grouped_list_ms.argtypes = [ct.c_void_p, ct.POINTER(ct.c_double)]
+lib.hnswdev_knn_search_tagged.restype = ct.c_int
+lib.hnswdev_knn_search_tagged.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int, _U32, ct.c_longlong, _U32, ct.c_int, _I, _F, _I]
+lib.hnswdev_knn_tagged_info.restype = ct.c_int
+lib.hnswdev_knn_tagged_info.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
+lib.hnswdev_exact_knn_tagged.restype = ct.c_int
+lib.hnswdev_exact_knn_tagged.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_longlong, ct.c_int, _U32, ct.c_longlong, _U32, ct.c_int, _I, _F]
+lib.hnswdev_exact_tagged_info.restype = ct.c_int
+lib.hnswdev_exact_tagged_info.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
+lib.hnswdev_tag_list_ms.restype = ct.c_int
+lib.hnswdev_tag_list_ms.argtypes = [ct.c_void_p, ct.POINTER(ct.c_double)]
 lib.hnswdev_knn_search_grouped.restype = ct.c_int
 lib.hnswdev_knn_search_grouped.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int, _I, ct.c_longlong, _I, ct.c_int, _I, _F, _I]
 lib.hnswdev_range_search_grouped.restype = ct.c_int
@@ -386,6 +407,32 @@ def _group_args(row_group, query_group, n_groups, nq):
         n_groups = max(int(rg.max(initial=-1)), int(qg.max(initial=-1))) + 1
         n_groups = max(n_groups, 1)
     return rg, qg, int(n_groups)
+
+
+def _tag_words(values, name):
+    """A tag array as the C ABI takes it: contiguous uint32, one word per entry.  Integers outside 0 .. 2^32 - 1 are an error, not
+    wrapped."""
+    a = np.asarray(values).reshape(-1)
+    if a.size and a.dtype.kind not in "iu":
+        raise ValueError(f"{name} must hold integers (uint32 tag words), not {a.dtype}")
+    if a.size and (int(a.min()) < 0 or int(a.max()) > 0xFFFFFFFF):
+        raise ValueError(f"{name} holds a value outside 0 .. 2^32 - 1")
+    return np.ascontiguousarray(a, dtype=np.uint32)
+
+
+def _tag_args(row_tags, query_tags, match, nq):
+    """(row_tags, query_tags, match) as the tagged calls take them: uint32 arrays, query_tags of nq entries with at most 65 536
+    distinct values, match "any" -> 0 / "all" -> 1.  Every breach is a ValueError here, before anything native runs."""
+    if match not in _TAG_MATCH:
+        raise ValueError(f"match = {match!r} is neither 'any' nor 'all'")
+    rt = _tag_words(row_tags, "row_tags")
+    qt = _tag_words(query_tags, "query_tags")
+    if qt.shape[0] != nq:
+        raise ValueError(f"query_tags has {qt.shape[0]} entries for {nq} queries")
+    distinct = int(np.unique(qt).size)
+    if distinct > 65536:
+        raise ValueError(f"query_tags holds {distinct} distinct masks, more than 65536")
+    return rt, qt, _TAG_MATCH[match]
 
 
 def last_error() -> str:
@@ -698,6 +745,56 @@ class Index:
         if self._h:
             lib.hnsw_mi355x_knn_grouped_info(self._h, out)
         return dict(zip(_KNN_GROUPED_INFO, (int(v) for v in out)))
+
+    def knn_query_tagged(self, queries: npt.ArrayLike, k: int, row_tags, query_tags, match: str = "any",
+                         layer: int = 0) -> Tuple[npt.NDArray[np.int32], npt.NDArray[np.float32]]:
+        """knn_query with a tag mask per query, every mask in one device traversal (hnsw_mi355x_knn_query_tagged): row_tags[id] is
+        a uint32 with one bit per tag (an id past the array's end, or the word 0: no tag), query_tags[i] the mask of query i.
+        match "any": id is a candidate of query i when row_tags[id] & query_tags[i] != 0; "all": when query_tags[i] != 0 and
+        row_tags[id] & query_tags[i] == query_tags[i].  Per distinct mask m the rows equal
+        knn_query(queries[query_tags == m], k, allowed=<the ids that match m>, layer=layer), ids and distance bits; a query whose mask
+        has no candidate gets a padded row."""
+        q = _as_2d_f32(queries, self.dim)
+        n = int(q.shape[0])
+        rt, qt, mode = _tag_args(row_tags, query_tags, match, n)
+        ids = np.full((n, max(k, 0)), -1, dtype=np.int32)   # (an index nothing was added to has no native handle yet: padding)
+        dists = np.full((n, max(k, 0)), np.nan, dtype=np.float32)
+        status = lib.hnsw_mi355x_knn_query_tagged(self._h, q.ctypes.data_as(_F), n, self.dim, k, int(layer), rt.ctypes.data_as(_U32), rt.shape[0],
+                                                  qt.ctypes.data_as(_U32), mode, ids.ctypes.data_as(_I), dists.ctypes.data_as(_F))
+        if status < 0:
+            raise RuntimeError(last_error())
+        return ids, dists
+
+    def knn_tagged_info(self) -> dict:
+        """Counters of knn_query_tagged's device launches since reset_stats (hnsw_mi355x_knn_tagged_info): calls that reached a
+        context, their distinct masks, queries launched, queries skipped because their mask has no candidate, queries handed back."""
+        out = (ct.c_uint64 * 5)()
+        if self._h:
+            lib.hnsw_mi355x_knn_tagged_info(self._h, out)
+        return dict(zip(_KNN_TAGGED_INFO, (int(v) for v in out)))
+
+    def exact_knn_query_tagged(self, queries: npt.ArrayLike, k: int, row_tags, query_tags,
+                               match: str = "any") -> Tuple[npt.NDArray[np.int32], npt.NDArray[np.float32]]:
+        """exact_knn_query with knn_query_tagged's tag mask per query (hnsw_mi355x_exact_knn_query_tagged): per distinct mask m the rows
+        equal exact_knn_query(queries[query_tags == m], k, allowed=<the ids that match m>).  1 <= k <= 1024."""
+        q = _as_2d_f32(queries, self.dim)
+        n = int(q.shape[0])
+        rt, qt, mode = _tag_args(row_tags, query_tags, match, n)
+        ids = np.full((n, max(k, 0)), -1, dtype=np.int32)   # (an index nothing was added to has no native handle yet: padding)
+        dists = np.full((n, max(k, 0)), np.nan, dtype=np.float32)
+        status = lib.hnsw_mi355x_exact_knn_query_tagged(self._h, q.ctypes.data_as(_F), n, self.dim, k, rt.ctypes.data_as(_U32), rt.shape[0],
+                                                        qt.ctypes.data_as(_U32), mode, ids.ctypes.data_as(_I), dists.ctypes.data_as(_F))
+        if status < 0:
+            raise RuntimeError(last_error())
+        return ids, dists
+
+    def exact_tagged_info(self) -> dict:
+        """Counters of exact_knn_query_tagged since reset_stats (hnsw_mi355x_exact_tagged_info): calls, their distinct masks, queries
+        scanned, queries skipped because their mask has no candidate, ids written into candidate lists, batches of masks."""
+        out = (ct.c_uint64 * 6)()
+        if self._h:
+            lib.hnsw_mi355x_exact_tagged_info(self._h, out)
+        return dict(zip(_EXACT_TAGGED_INFO, (int(v) for v in out)))
 
     def exact_range_query(self, queries: npt.ArrayLike, radius: float,
                           allowed=None) -> Tuple[List[npt.NDArray[np.int32]], List[npt.NDArray[np.float32]]]:
@@ -1320,6 +1417,51 @@ class DeviceBackend:
         out = (ct.c_uint64 * 4)()
         self._check(lib.hnswdev_knn_grouped_info(self._ctx, out))
         return dict(zip(_KNN_GROUPED_INFO, (int(v) for v in out)))
+
+    def knn_search_tagged(self, queries, entry_point: int, k_beam: int, k_out: int, row_tags, query_tags, match: str = "any", layer: int = 0):
+        """hnswdev_knn_search_tagged: knn_search with a tag mask per query -- query i is answered from the graph ids j whose word
+        row_tags[j] matches query_tags[i] (Index.knn_query_tagged's rule).  (ids, dists, flags)."""
+        q = _as_2d_f32(queries, self.dim)
+        n = q.shape[0]
+        rt, qt, mode = _tag_args(row_tags, query_tags, match, n)
+        ids = np.empty((n, k_out), dtype=np.int32)
+        d = np.empty((n, k_out), dtype=np.float32)
+        flags = np.empty(n, dtype=np.int32)
+        self._check(lib.hnswdev_knn_search_tagged(self._ctx, q.ctypes.data_as(_F), n, int(entry_point), int(k_beam), int(k_out), int(layer),
+                                                  rt.ctypes.data_as(_U32), rt.shape[0], qt.ctypes.data_as(_U32), mode, ids.ctypes.data_as(_I),
+                                                  d.ctypes.data_as(_F), flags.ctypes.data_as(_I)))
+        return ids, d, flags
+
+    def knn_tagged_info(self) -> dict:
+        """Counters of knn_search_tagged since reset_stats (hnswdev_knn_tagged_info)."""
+        out = (ct.c_uint64 * 5)()
+        self._check(lib.hnswdev_knn_tagged_info(self._ctx, out))
+        return dict(zip(_KNN_TAGGED_INFO, (int(v) for v in out)))
+
+    def exact_knn_tagged(self, queries, k: int, row_tags, query_tags, match: str = "any", n_rows=None):
+        """hnswdev_exact_knn_tagged: exact_knn with a tag mask per query -- query i is answered from the uploaded rows j of [0, n_rows)
+        (None: all) whose word row_tags[j] matches query_tags[i].  queries None: the resident set (len(query_tags) of its rows)."""
+        q = None if queries is None else _as_2d_f32(queries, self.dim)
+        n = int(np.asarray(query_tags).size) if q is None else int(q.shape[0])
+        rt, qt, mode = _tag_args(row_tags, query_tags, match, n)
+        ids = np.empty((n, k), dtype=np.int32)
+        d = np.empty((n, k), dtype=np.float32)
+        self._check(lib.hnswdev_exact_knn_tagged(self._ctx, None if q is None else q.ctypes.data_as(_F), n, (1 << 62) if n_rows is None else int(n_rows),
+                                                 int(k), rt.ctypes.data_as(_U32), rt.shape[0], qt.ctypes.data_as(_U32), mode, ids.ctypes.data_as(_I),
+                                                 d.ctypes.data_as(_F)))
+        return ids, d
+
+    def exact_tagged_info(self) -> dict:
+        """Counters of exact_knn_tagged since reset_stats (hnswdev_exact_tagged_info)."""
+        out = (ct.c_uint64 * 6)()
+        self._check(lib.hnswdev_exact_tagged_info(self._ctx, out))
+        return dict(zip(_EXACT_TAGGED_INFO, (int(v) for v in out)))
+
+    def tag_list_ms(self) -> float:
+        """HIP-event milliseconds of the tagged calls' list-building kernels while profiling was on, since reset_stats."""
+        out = ct.c_double(0.0)
+        self._check(lib.hnswdev_tag_list_ms(self._ctx, ct.byref(out)))
+        return float(out.value)
 
     def exact_knn(self, queries, k: int, n_rows=None, allowed=None):
         """hnswdev_exact_knn: (ids, dists) of shape [nq, k], per query the k uploaded rows of smallest (distance, id) among rows

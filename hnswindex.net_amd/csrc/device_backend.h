@@ -3,12 +3,14 @@
 // hnsw_index.cpp) both sit on this class.  Nothing here computes a distance on the CPU.
 #pragma once
 #include <cstddef>
+#include <algorithm>
 #include <atomic>
 #include <cstdint>
 #include <functional>
 #include <memory>
 #include <mutex>
 #include <string>
+#include <unordered_map>
 #include <vector>
 #include <thread>
 
@@ -86,6 +88,35 @@ inline std::string group_args_error(const char *who, const int *query_group, int
     for (int i = 0; i < nq; ++i)
         if (query_group[i] < 0 || query_group[i] >= n_groups)
             return std::string(who) + ": query_group[" + std::to_string(i) + "] = " + std::to_string(query_group[i]) + " is outside 0 .. n_groups - 1 = " + std::to_string(n_groups - 1);
+    return std::string();
+}
+// The tagged calls: a uint32 of tag bits per id, a uint32 mask per query, one mode for the call -- 0 "any": an id
+// is a candidate when it shares a tag with the mask, 1 "all": when it carries every tag of a mask that is not 0.  The word 0
+// matches no mask and the mask 0 no word, in either mode.
+constexpr long long kTagListEntries = 1LL << 28; // ids in the candidate lists of one batch of masks of exact_knn_tagged: 1 GiB (`tag_list_cap` lowers it)
+inline bool tag_match_host(uint32_t w, uint32_t m, int match) { return (w & m) != 0u && (match == 0 || (w & m) == m); }
+// The distinct masks of a call in the order they first appear, and each query's place among them.
+struct TagCall {
+    std::vector<uint32_t> masks; // at most kExactMaxGroups
+    std::vector<int> of;         // [nq] query i's mask is masks[of[i]]
+};
+// The argument rules every tagged call shares -- match 0 or 1, at most kExactMaxGroups distinct masks -- and the one wording of a
+// breach: "" when the arguments are good (tc filled), else "<who>: ...".
+inline std::string tag_args_error(const char *who, const uint32_t *query_tags, int nq, int match, TagCall *tc)
+{
+    if (match != 0 && match != 1) return std::string(who) + ": match = " + std::to_string(match) + " is neither 0 (any) nor 1 (all)";
+    std::unordered_map<uint32_t, int> seen;
+    tc->masks.clear();
+    tc->of.assign((size_t)std::max(nq, 0), 0);
+    for (int i = 0; i < nq; ++i) {
+        const auto it = seen.emplace(query_tags[i], (int)tc->masks.size());
+        if (it.second) {
+            if ((int)tc->masks.size() == kExactMaxGroups)
+                return std::string(who) + ": more than " + std::to_string(kExactMaxGroups) + " distinct masks in query_tags (the " + std::to_string(kExactMaxGroups + 1) + "th at index " + std::to_string(i) + ")";
+            tc->masks.push_back(query_tags[i]);
+        }
+        tc->of[(size_t)i] = it.first->second;
+    }
     return std::string();
 }
 class Device;
@@ -248,6 +279,17 @@ public:
                         int n_groups, int *out_ids, float *out_d, int *out_flag, int search_layer = 0);
     // calls, queries launched, queries padded for an empty group, queries handed back -- of search_grouped on this context
     void knn_grouped_info(uint64_t out[4]) const { for (int i = 0; i < 4; ++i) out[i] = kg_info_[i]; }
+    // search_grouped with a tag mask per query (graph_search_tagged_kernel): resident query i is answered from the
+    // graph ids j < n_row_tags whose word row_tags[j] matches query_tags[i] under `match` (0 any, 1 all) -- byte for byte what
+    // search_filtered returns for it with those ids as the allow-set.  The words, the masks and the order table are uploaded to this
+    // context for the call, to buffers of their own; the candidates of every distinct mask are counted on the device
+    // (dk_tag_lists.h).  A query whose mask has no candidate is padded and never launched (out_flag 0); the others are launched
+    // ascending by their mask's count.  match outside 0 / 1 and more than 65 536 distinct masks are errors, checked before
+    // anything runs.  out_flag as search_filtered.
+    bool search_tagged(int nq, int entry, int entry_layer, int k, int k_out, const uint32_t *row_tags, long long n_row_tags, const uint32_t *query_tags,
+                       int match, int *out_ids, float *out_d, int *out_flag, int search_layer = 0);
+    // calls, distinct masks, queries launched, queries padded for a mask without a candidate, queries handed back -- of search_tagged on this context
+    void knn_tagged_info(uint64_t out[5]) const { for (int i = 0; i < 5; ++i) out[i] = kt_info_[i]; }
     // MultiLayerKnnQuery's chains (graph_multilayer_kernel): resident query i searched with beam k (>= 2) on every layer from
     // first_layer (<= entry_layer) down to min_layer, each step entering at the nearest result of the one before.
     // out_ids / out_d: [nq][first_layer + 1][k - 1], padded; out_flag[i] = 1: handed back whole.
@@ -344,6 +386,8 @@ public:
                              int *out_ids, float *out_d, int *out_flag, int layer = 0);
     bool knn_search_grouped(const float *queries, int nq, int entry_point, int k_beam, int k_out, const int *row_group, long long n_row_group,
                             const int *query_group, int n_groups, int *out_ids, float *out_d, int *out_flag, int layer = 0);
+    bool knn_search_tagged(const float *queries, int nq, int entry_point, int k_beam, int k_out, const uint32_t *row_tags, long long n_row_tags,
+                           const uint32_t *query_tags, int match, int *out_ids, float *out_d, int *out_flag, int layer = 0);
     // hnswdev_multilayer_search: the slot count, or -1
     int multilayer_search_abi(const float *queries, int nq, int entry_point, int k, int max_layer, int min_layer, int layers_cap, int *out_ids,
                               float *out_d, int *out_flag);
@@ -411,6 +455,19 @@ public:
     // grouped calls that launched, groups scanned (a query and a candidate each), scan blocks launched, ids placed in group lists
     // (all four count the calls that launched a scan only)
     void exact_grouped_info(uint64_t out[4]) const { for (int i = 0; i < 4; ++i) out[i] = xg_info_[i]; }
+    // hnswdev_exact_knn_tagged: exact_knn_grouped where query i's candidates are the uploaded ids
+    // j < min(n_rows, uploaded, n_row_tags) whose word row_tags[j] matches query_tags[i] under `match` (0 any, 1 all).  Every
+    // distinct mask is a list; the lists overlap, and are built on the device (dk_tag_lists.h) in batches of masks whose counts sum
+    // to at most kTagListEntries (`tag_list_cap`); a mask with more is a batch alone.  Each batch is one grouped scan -- rounds,
+    // work items, scan and merge kernels are exact_knn_grouped's -- over the queries of its masks.  Distances, order, padding, k,
+    // queries == nullptr and the untouched resident set as exact_knn.  Synchronous.
+    bool exact_knn_tagged(const float *queries, int nq, long long n_rows, int k, const uint32_t *row_tags, long long n_row_tags, const uint32_t *query_tags,
+                          int match, int *out_ids, float *out_d);
+    // calls that counted candidates, distinct masks, queries scanned, queries padded for a mask without a candidate, list entries
+    // built, batches of masks scanned
+    void exact_tagged_info(uint64_t out[6]) const { for (int i = 0; i < 6; ++i) out[i] = xt_info_[i]; }
+    // HIP-event time of the tagged calls' list-building kernels (count, offsets, fill) made while profiling was on
+    double tag_list_ms() const { return xt_list_ms_; }
     // hnswdev_exact_range_grouped: exact_range with exact_knn_grouped's candidate set per query -- the group
     // arguments, their errors and the group lists are that call's; radius, order, counts, capacities and the results kept for
     // exact_range_results are exact_range's.  A query whose group has no member gets an empty list without being scanned.
@@ -584,6 +641,14 @@ private:
     DevBuf<int> s_gquery_;       // ... [query_group of the call | order tables of its launches]
     uint64_t kg_info_[4] = {0, 0, 0, 0};
     uint64_t rg_info_[4] = {0, 0, 0, 0}; // range_grouped_info
+    DevBuf<unsigned> s_ttags_;   // tagged calls: the call's row_tags
+    DevBuf<unsigned> s_tmask_;   // ... its distinct masks
+    DevBuf<int> s_tcnt_;         // ... per distinct mask: [candidates | offset of its segment in x_ids_ | the filling kernel's cursor]
+    DevBuf<int> s_tquery_;       // tagged searches: [query_tags of the call | order tables of its launches]
+    uint64_t kt_info_[5] = {0, 0, 0, 0, 0};
+    uint64_t xt_info_[6] = {0, 0, 0, 0, 0, 0};
+    double xt_list_ms_ = 0.0;
+    bool tag_counts(const unsigned *row_tags, long long n, const std::vector<uint32_t> &masks, int match, std::vector<int> &cnt);
     DevBuf<int> x_ids_;                 // exact_knn: the call's ascending id list (exact_compact_kernel)
     DevBuf<long long> x_boff_;          // ... set bits in front of each block of bitset words
     DevBuf<unsigned long long> x_lists_; // ... the per-(query, chunk) lists of a round: at most 1 GiB, allocated by the first call and kept
@@ -616,7 +681,11 @@ private:
     uint64_t xg_info_[4] = {0, 0, 0, 0};
     uint64_t xrg_info_[4] = {0, 0, 0, 0}; // exact_range_grouped's counters
     bool exact_group_lists(const char *who, const int *row_group, long long n, int n_groups, std::vector<int> &cnt, std::vector<int> &goff, uint64_t *listed);
-    bool exact_sorted_queries(const char *who, const float *queries, int nq, const std::vector<int> &order, const float **d_q, const double **d_qsn);
+    bool exact_sorted_queries(const char *who, const float *queries, int nq, const std::vector<int> &order, const float **d_q, const double **d_qsn,
+                              const int *resident = nullptr);
+    bool exact_grouped_plan(const char *who, int k, ExactGroupedCall *gc);
+    bool exact_knn_grouped_scan(const char *who, const float *queries, const int *resident, int nq, int k, const int *query_group, int n_groups,
+                                const ExactGroupedCall &gc, int *out_ids, float *out_d, uint64_t *blocks);
     ExactStart exact_grouped_begin(const char *who, bool args_ok, const float *queries, int nq, long long n_rows, int k, const int *row_group,
                                    long long n_row_group, const int *query_group, int n_groups, ExactGroupedCall *gc);
     double xg_list_ms_ = 0.0;

@@ -53,6 +53,7 @@
 #include "dk_graph_info.h"
 #include "dk_graph_reach.h"
 #include "dk_graph_repair.h"
+#include "dk_tag_lists.h"
 #include "range_replay.h"
 
 namespace hnsw {
@@ -1023,6 +1024,9 @@ void Device::reset_stats()
     for (uint64_t &v : kg_info_) v = 0;
     for (uint64_t &v : rg_info_) v = 0;
     xg_list_ms_ = 0.0;
+    for (uint64_t &v : kt_info_) v = 0;
+    for (uint64_t &v : xt_info_) v = 0;
+    xt_list_ms_ = 0.0;
     for (uint64_t &v : gi_info_) v = 0;
     for (uint64_t &v : gr_info_) v = 0;
     for (uint64_t &v : rp_info_) v = 0;
@@ -2141,6 +2145,143 @@ bool Device::search_grouped(int nq, int entry, int entry_layer, int k, int k_out
     return true;
 }
 
+// The tagged calls' argument rules (tag_args_error, device_backend.h), filed as the context's error.
+static bool tag_args_ok(const char *who, const uint32_t *query_tags, int nq, int match, TagCall *tc)
+{
+    const std::string why = tag_args_error(who, query_tags, nq, match, tc);
+    if (!why.empty()) set_dev_error(why);
+    return why.empty();
+}
+
+// What both tagged calls begin with (dk_tag_lists.h): row_tags[0, n) (n >= 1) and the call's distinct masks go up
+// to buffers of their own, tag_count_kernel counts every mask's candidates, and the counts come back in one copy -- cnt[d]: the ids
+// below n whose word matches masks[d].  The words and the masks stay on the device for the call (s_ttags_, s_tmask_; s_tcnt_ holds
+// [counts | offsets | cursors]).  The stream is idle and the pinned stage free when this returns.
+bool Device::tag_counts(const unsigned *row_tags, long long n, const std::vector<uint32_t> &masks, int match, std::vector<int> &cnt)
+{
+    hipStream_t st = S(stream_);
+    const size_t D = masks.size(), b_tags = 4 * (size_t)n, b_masks = 4 * D;
+    if (!s_ttags_.grow((size_t)n) || !s_tmask_.grow(D) || !s_tcnt_.grow(3 * D)) return false;
+    cnt.assign(D, 0);
+    const size_t staged = b_tags < (4u << 20) ? b_tags : 0; // larger arrays go up in pieces, as query sets do
+    char *hs = static_cast<char *>(pinned_stage(staged + 2 * b_masks));
+    if (!hs) return false;
+    if (staged) { memcpy(hs, row_tags, b_tags); HIP_OK(hipMemcpyAsync(s_ttags_, hs, b_tags, hipMemcpyHostToDevice, st)); }
+    else if (!staged_upload(reinterpret_cast<float *>(s_ttags_.get()), reinterpret_cast<const float *>(row_tags), b_tags)) return false;
+    memcpy(hs + staged, masks.data(), b_masks);
+    HIP_OK(hipMemcpyAsync(s_tmask_, hs + staged, b_masks, hipMemcpyHostToDevice, st));
+    const bool timed = profiling_; // the list-building kernels have an event pair of their own (tag_list_ms)
+    if (timed && (!ev0_.create(true) || !ev1_.create(true))) return false;
+    if (timed) HIP_OK(hipEventRecord(E(ev0_), st));
+    HIP_OK(tag_counts_launch(s_ttags_, n, s_tmask_, (int)D, match, s_tcnt_, st));
+    if (timed) HIP_OK(hipEventRecord(E(ev1_), st));
+    HIP_OK(hipMemcpyAsync(hs + staged + b_masks, s_tcnt_, b_masks, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    if (timed) {
+        float ms = 0.f;
+        HIP_OK(hipEventElapsedTime(&ms, E(ev0_), E(ev1_)));
+        xt_list_ms_ += ms;
+    }
+    memcpy(cnt.data(), hs + staged + b_masks, b_masks); // (the stage is used again by the caller)
+    for (size_t d = 0; d < D; ++d)
+        if (cnt[d] < 0 || cnt[d] > n) { set_dev_error("tag_counts: a mask's count is outside 0 .. the ids"); return false; }
+    return true;
+}
+
+// KnnQuery with a tag mask per query (graph_search_tagged_kernel): search_grouped's launch with the tag words in the
+// labels' place.  Only the words of graph ids travel.  The candidates of every distinct mask are counted on the device
+// (tag_counts): a query whose mask has none is padded without a job, and the others are listed in the launch's order table longest
+// traversal first, as search_grouped lists them -- ascending by their mask's count, queries of equal counts in query order.
+bool Device::search_tagged(int nq, int entry, int entry_layer, int k, int k_out, const uint32_t *row_tags, long long n_row_tags, const uint32_t *query_tags,
+                           int match, int *out_ids, float *out_d, int *out_flag, int search_layer)
+{
+    if (nq <= 0) return true;
+    if (!out_ids || !out_d || !out_flag || k < 1 || k_out < 1) { set_dev_error("search_tagged: bad argument"); return false; }
+    if (!row_tags || n_row_tags < 0) { set_dev_error("search_tagged: row_tags must not be NULL and n_row_tags must be >= 0"); return false; }
+    if (!query_tags) { set_dev_error("search_tagged: query_tags must not be NULL"); return false; }
+    TagCall tc;
+    if (!tag_args_ok("search_tagged", query_tags, nq, match, &tc)) return false;
+    if (g_n_ <= 0) { set_dev_error("search_tagged: no graph uploaded"); return false; }
+    if (search_layer < 0 || search_layer > entry_layer) { set_dev_error("search_tagged: the search layer must lie between 0 and the entry point's top layer"); return false; }
+    if (!(entry >= 0 && entry < g_n_ && entry_layer >= 0 && nq <= n_queries_) || tail_.n > 0) {
+        set_dev_error("search_tagged: entry point outside the graph, or fewer resident queries than asked for");
+        return false;
+    }
+    const long long n_lab = std::min<long long>(n_row_tags, g_n_);
+    std::vector<int> cnt(tc.masks.size(), 0);
+    if (n_lab > 0 && (!bind() || !tag_counts(row_tags, n_lab, tc.masks, match, cnt))) return false; // (no word of a graph id: no candidate, nothing goes up)
+    const auto members = [&](long long i) { return cnt[(size_t)tc.of[(size_t)i]]; };
+    // per launch (chunk) its order table: the chunk's own query indices whose mask has a candidate, ascending by the mask's count
+    const long long chunk = std::min<long long>(nq, 1 << 20);
+    std::vector<int> order((size_t)nq), jobs_of;
+    long long launched = 0;
+    for (long long off = 0; off < nq; off += chunk) {
+        const int nj = (int)std::min<long long>(chunk, nq - off);
+        int *o = order.data() + off;
+        int n = 0;
+        for (int i = 0; i < nj; ++i)
+            if (members(off + i) > 0) o[n++] = i;
+        std::stable_sort(o, o + n, [&](int a, int b) { return members(off + a) < members(off + b); });
+        for (int i = n; i < nj; ++i) o[i] = 0; // (never read: the launch has n jobs)
+        jobs_of.push_back(n);
+        launched += n;
+    }
+    // the rows no job writes: padding, flag 0 (after the launches' rows have been copied over the caller's arrays)
+    const auto pad_skipped = [&] {
+        for (int i = 0; i < nq; ++i)
+            if (members(i) == 0) {
+                pad_results(out_ids + (size_t)i * k_out, out_d + (size_t)i * k_out, (size_t)k_out);
+                out_flag[i] = 0;
+            }
+    };
+    if (launched == 0) { // (nothing to traverse: no launch, as a set that allows nothing)
+        pad_skipped();
+        kt_info_[0] += 1;
+        kt_info_[1] += (uint64_t)tc.masks.size();
+        kt_info_[3] += (uint64_t)nq;
+        return true;
+    }
+    const int cand_cap = cand_lds_cap(k, pitch_, false, nbcap());
+    const size_t lds = search_lds_bytes(k, cand_cap, pitch_, false, nbcap());
+    if (lds > 64 * 1024) { set_dev_error("search_tagged: beam width / dimension exceed the LDS budget"); return false; }
+    hipStream_t st = S(stream_);
+    TraversalLaunch tl;
+    if (!plan_traversal(false, k, true, lds, &tl, true)) return false;
+    const auto kernel = persistent_kernel(metric_, tl.vis.tab != nullptr, [](auto m, auto h) { return &graph_search_tagged_kernel<m, h>; });
+    place_persistent(kernel, tl, (int)chunk);
+    if (tl.slots < 1) { set_dev_error("search_tagged: the kernel does not fit the device"); return false; }
+    const int fspill = filter_spill_cap();
+    if (!ensure_search_scratch(chunk, max_slots(), k_out, tl.vis.bytes_per_job)) return false;
+    if (!s_fspill_.grow((size_t)tl.slots * (size_t)std::max(fspill, 1) + 8)) return false; // +8: get2 may read one entry past a heap
+    if (!s_tquery_.grow(2 * (size_t)nq)) return false;
+    const size_t b_q = 4u * (size_t)nq;
+    const auto upload = [&](char *h) { // masks and order tables go up from pinned memory, behind the words tag_counts sent: [query_tags | order]
+        memcpy(h, query_tags, b_q);
+        memcpy(h + b_q, order.data(), b_q);
+        HIP_OK(hipMemcpyAsync(s_tquery_, h, 2 * b_q, hipMemcpyHostToDevice, st));
+        return true;
+    };
+    const auto launch = [&](long long off, int, int *d_ids, float *d_d) {
+        const int n = jobs_of[(size_t)(off / chunk)]; // (0: one wave finds the counter past the jobs and leaves)
+        hipLaunchKernelGGL(kernel, dim3(std::max(1, std::min(n, tl.slots))), dim3(tl.block), tl.lds_total, st, d_rows_, d_row_sn_, d_queries_ + (size_t)off * pitch_,
+                           d_q_sn_ ? d_q_sn_ + off : nullptr, pitch_, g_adj0_, g_stride0_, g_upper_, g_pool_, g_strideU_, entry, entry_layer, search_layer, k,
+                           cand_cap, reinterpret_cast<ND *>(s_fspill_.get()), fspill, s_visited_, tl.vis.words, tl.vis.tab, tl.vis.tab_cap,
+                           s_ttags_.get(), n_lab, reinterpret_cast<const unsigned *>(s_tquery_.get()) + off, match, s_tquery_.get() + (size_t)nq + off, k_out, d_ids, d_d,
+                           s_flag_, s_evals_, nbcap(), n, s_jobctr_);
+    };
+    if (!run_resident((size_t)k_out, chunk, 2 * b_q, tl.vis.tab != nullptr, nq, out_ids, out_d, out_flag, upload, launch)) return false;
+    pad_skipped();
+    kt_info_[0] += 1;
+    kt_info_[1] += (uint64_t)tc.masks.size();
+    kt_info_[2] += (uint64_t)launched;
+    kt_info_[3] += (uint64_t)(nq - launched);
+    for (int i = 0; i < nq; ++i) {
+        stats_.search_overflows += (uint64_t)(out_flag[i] == 1);
+        kt_info_[4] += (uint64_t)(out_flag[i] == 1);
+    }
+    return true;
+}
+
 // MultiLayerKnnQuery's chains (graph_multilayer_kernel): resident query i from (entry, entry_layer), searched on every layer from
 // first_layer down to min_layer with beam k, each step entering at the one before's nearest result.  out_ids / out_d:
 // [nq][first_layer + 1][k - 1], slots below min_layer padded; out_flag[i] = 1: the job is handed back (the caller redoes it).
@@ -2799,6 +2940,22 @@ bool Device::knn_search_grouped(const float *queries, int nq, int entry_point, i
     return search_grouped(nq, entry_point, top, k_beam, k_out, row_group, n_row_group, query_group, n_groups, out_ids, out_d, out_flag, layer);
 }
 
+bool Device::knn_search_tagged(const float *queries, int nq, int entry_point, int k_beam, int k_out, const uint32_t *row_tags, long long n_row_tags,
+                               const uint32_t *query_tags, int match, int *out_ids, float *out_d, int *out_flag, int layer)
+{
+    if (!row_tags || n_row_tags < 0) { set_dev_error("knn_search_tagged: row_tags must not be NULL and n_row_tags must be >= 0"); return false; }
+    if (match != 0 && match != 1) { set_dev_error("knn_search_tagged: match = " + std::to_string(match) + " is neither 0 (any) nor 1 (all)"); return false; }
+    if (nq <= 0) return true;
+    if (!query_tags) { set_dev_error("knn_search_tagged: query_tags must not be NULL"); return false; }
+    if (!queries || !out_ids || !out_d || !out_flag) { set_dev_error("knn_search_tagged: null argument"); return false; }
+    TagCall tc;
+    if (!tag_args_ok("knn_search_tagged", query_tags, nq, match, &tc)) return false;
+    int top;
+    const bool args_ok = k_out >= 1 && k_beam >= k_out; // (false: "knn_search_tagged: bad argument", in abi_entry's place for it)
+    if (!abi_begin("knn_search_tagged", queries, nq, entry_point, layer, &top, args_ok)) return false;
+    return search_tagged(nq, entry_point, top, k_beam, k_out, row_tags, n_row_tags, query_tags, match, out_ids, out_d, out_flag, layer);
+}
+
 // ---- the flat scan (hnswdev_exact_knn; device code in dk_exact.h) --------------------------------------
 // Tile and chunk of a call.  The query tile: as many queries as 16 KB of staged query words and 32 KB of k-entry lists hold, at
 // most 32 and no more than the call has; `exact_qtile` forces it.  The chunk: enough chunks that the tiles x chunks fill the chip
@@ -3042,9 +3199,10 @@ bool Device::exact_group_lists(const char *who, const int *row_group, long long 
 }
 
 // The queries of a grouped flat scan in the order `order` (sorted position -> the caller's index): uploaded through set_queries'
-// path, or (queries == nullptr) gathered from the resident set on the device.  The stream is idle and the pinned stage free when
-// this returns.
-bool Device::exact_sorted_queries(const char *who, const float *queries, int nq, const std::vector<int> &order, const float **d_q, const double **d_qsn)
+// path, or (queries == nullptr) gathered from the resident set on the device -- the caller's query i is resident query resident[i]
+// (nullptr: i).  The stream is idle and the pinned stage free when this returns.
+bool Device::exact_sorted_queries(const char *who, const float *queries, int nq, const std::vector<int> &order, const float **d_q, const double **d_qsn,
+                                  const int *resident)
 {
     hipStream_t st = S(stream_);
     if (queries) {
@@ -3056,7 +3214,8 @@ bool Device::exact_sorted_queries(const char *who, const float *queries, int nq,
     if (!x_gperm_.grow((size_t)nq)) return false;
     int *hp = static_cast<int *>(pinned_stage(4 * (size_t)nq));
     if (!hp) return false;
-    memcpy(hp, order.data(), 4 * (size_t)nq);
+    if (resident) for (int p = 0; p < nq; ++p) hp[p] = resident[order[(size_t)p]];
+    else memcpy(hp, order.data(), 4 * (size_t)nq);
     HIP_OK(hipMemcpyAsync(x_gperm_, hp, 4 * (size_t)nq, hipMemcpyHostToDevice, st));
     HIP_OK(exact_gather_queries_launch(d_queries_, metric_ == M_COS ? d_q_sn_.get() : nullptr, x_gperm_, nq, pitch_, x_queries_, x_q_sn_, st));
     HIP_OK(hipStreamSynchronize(st)); // the pinned stage is used again by the caller
@@ -3135,13 +3294,23 @@ ExactStart Device::exact_grouped_begin(const char *who, bool args_ok, const floa
     if (gc->n <= 0) return ExactStart::nothing;
     if (!queries && (nq > n_queries_ || tail_.n > 0)) return fail("queries == NULL needs a resident query set of at least nq rows (hnswdev_set_queries)");
     if (!bind() || !exact_group_lists(who, row_group, gc->n, n_groups, gc->cnt, gc->goff, &gc->listed)) return ExactStart::failed;
+    if (!exact_grouped_plan(who, k, gc)) return ExactStart::failed;
+    return gc->scanned == 0 ? ExactStart::nothing : ExactStart::ready;
+}
+
+// The groups a grouped flat scan measures -- those with a query (gq) and a member (cnt) -- counted in gc->scanned, and the call's
+// tile planned for the most queries any of them has.  false: the tile does not fit LDS.
+bool Device::exact_grouped_plan(const char *who, int k, ExactGroupedCall *gc)
+{
+    gc->max_gq = 0;
+    gc->scanned = 0;
     for (size_t g = 0; g < gc->gq.size(); ++g)
         if (gc->gq[g] > 0 && gc->cnt[g] > 0) { gc->max_gq = std::max(gc->max_gq, gc->gq[g]); gc->scanned += 1; }
-    if (gc->scanned == 0) return ExactStart::nothing;
+    if (gc->scanned == 0) return true;
     gc->tp = exact_plan(gc->max_gq, 1, std::max(k, 1), pitch_, num_cu_);
     gc->tp.lds = exact_scan_lds(gc->tp.qtile, gc->tp.piece, pitch_, k);
-    if (gc->tp.lds > 64 * 1024) return fail("tile exceeds the LDS budget");
-    return ExactStart::ready;
+    if (gc->tp.lds > 64 * 1024) { set_dev_error(std::string(who) + ": tile exceeds the LDS budget"); return false; }
+    return true;
 }
 
 // The queries of the round at sorted positions [off, off + nr) of `order`, a run of one group's queries at a time, each run cut
@@ -3184,6 +3353,19 @@ bool Device::exact_knn_grouped(const float *queries, int nq, long long n_rows, i
                                              query_group, n_groups, &gc);
     if (s == ExactStart::nothing) pad_results(out_ids, out_d, (size_t)nq * (size_t)k); // no query has a candidate: padding, no scan
     if (s != ExactStart::ready) return s == ExactStart::nothing;
+    uint64_t blocks = 0;
+    if (!exact_knn_grouped_scan("exact_knn_grouped", queries, nullptr, nq, k, query_group, n_groups, gc, out_ids, out_d, &blocks)) return false;
+    if (blocks) { xg_info_[0] += 1; xg_info_[1] += gc.scanned; xg_info_[2] += blocks; xg_info_[3] += gc.listed; } // (a call that scans nothing counts nowhere)
+    return true;
+}
+
+// A grouped top-k scan once the groups' lists stand in x_ids_ (gc: per group its queries, members and segment; the tile): chunks,
+// rounds, the sorted upload, work items, scan and merge -- what exact_knn_grouped and every batch of exact_knn_tagged run.  The nq
+// queries are `queries`, or (nullptr) the resident queries resident[0 .. nq) (nullptr: 0 .. nq - 1); query_group[i] names query i's
+// list.  *blocks: the scan blocks launched, 0 when no query has a candidate (every row is padded).
+bool Device::exact_knn_grouped_scan(const char *who, const float *queries, const int *resident, int nq, int k, const int *query_group, int n_groups,
+                                    const ExactGroupedCall &gc, int *out_ids, float *out_d, uint64_t *blocks)
+{
     hipStream_t st = S(stream_);
     const ExactPlan &tp = gc.tp;
     const int qt = tp.qtile;
@@ -3206,11 +3388,11 @@ bool Device::exact_knn_grouped(const float *queries, int nq, long long n_rows, i
 
     const float *d_q;
     const double *d_qsn;
-    if (!exact_sorted_queries("exact_knn_grouped", queries, nq, order, &d_q, &d_qsn)) return false;
+    if (!exact_sorted_queries(who, queries, nq, order, &d_q, &d_qsn, resident)) return false;
 
     std::vector<ExactMergeItem> mi;
     std::vector<ExactWorkItem> wi;
-    bool launched = false;
+    *blocks = 0;
     int off = 0;
     for (const int r1 : round_end) {
         const int nr = r1 - off;
@@ -3259,11 +3441,104 @@ bool Device::exact_knn_grouped(const float *queries, int nq, long long n_rows, i
         if (!exact_timed_scan(h_ev, enqueue, fetch)) return false;
         memcpy(out_ids + (size_t)off * k, hs, res);
         memcpy(out_d + (size_t)off * k, hs + res, res);
-        xg_info_[2] += wi.size();
-        launched = true;
+        *blocks += wi.size();
         off = r1;
     }
-    if (launched) { xg_info_[0] += 1; xg_info_[1] += gc.scanned; xg_info_[3] += gc.listed; } // (a call that scans nothing counts nowhere)
+    return true;
+}
+
+// ---- hnswdev_exact_knn_tagged: a tag mask per query, every distinct mask a candidate list ------------------
+// The lists overlap -- a row is in the list of every mask it matches -- so together they can hold D x n ids, and an ExactWorkItem
+// addresses x_ids_ with an int.  The distinct masks are therefore taken in batches, in the order they first appear, whose counts
+// (tag_counts) sum to at most kTagListEntries (`tag_list_cap` lowers it); a mask with more is a batch alone, and fits because
+// n < 2^31.  Per batch dk_tag_lists.h builds the CSR in x_ids_ and exact_knn_grouped_scan answers the queries of the batch's masks;
+// with more than one batch their rows go through arrays of the batch's size and are scattered to the caller's order.
+bool Device::exact_knn_tagged(const float *queries, int nq, long long n_rows, int k, const uint32_t *row_tags, long long n_row_tags, const uint32_t *query_tags,
+                              int match, int *out_ids, float *out_d)
+{
+    if (nq <= 0) return true;
+    const char *who = "exact_knn_tagged";
+    const auto fail = [&](const std::string &what) { set_dev_error(std::string(who) + ": " + what); return false; };
+    if (!(out_ids && out_d && k >= 1 && n_rows >= 0)) return fail("bad argument");
+    if (!row_tags || n_row_tags < 0) return fail("row_tags must not be NULL and n_row_tags must be >= 0");
+    if (!query_tags) return fail("query_tags must not be NULL");
+    if (k > kExactMaxK) return fail("k = " + std::to_string(k) + " is above the limit of " + std::to_string(kExactMaxK));
+    TagCall tc;
+    if (!tag_args_ok(who, query_tags, nq, match, &tc)) return false;
+    // ids that exist and have a word: a row beyond what was uploaded is never dereferenced, whatever n_rows and n_row_tags say
+    const long long n = std::min({n_rows, n_rows_hw_, n_row_tags});
+    if (n <= 0) { pad_results(out_ids, out_d, (size_t)nq * (size_t)k); return true; }
+    if (!queries && (nq > n_queries_ || tail_.n > 0)) return fail("queries == NULL needs a resident query set of at least nq rows (hnswdev_set_queries)");
+    const int D = (int)tc.masks.size();
+    std::vector<int> cnt;
+    if (!bind() || !tag_counts(row_tags, n, tc.masks, match, cnt)) return false;
+    hipStream_t st = S(stream_);
+    const long long forced = diag("tag_list_cap", 0), cap = forced > 0 ? forced : kTagListEntries;
+    std::vector<int> gq((size_t)D, 0);
+    for (int i = 0; i < nq; ++i) gq[(size_t)tc.of[(size_t)i]] += 1;
+    uint64_t scanned_q = 0, listed = 0, batches = 0;
+    std::vector<int> sel, qg, t_ids;
+    std::vector<float> t_q, t_d;
+    for (int d0 = 0; d0 < D;) {
+        // the batch: masks d0 .. d1 - 1, `sum` entries
+        long long sum = cnt[(size_t)d0];
+        int d1 = d0 + 1;
+        while (d1 < D && sum + cnt[(size_t)d1] <= cap) sum += cnt[(size_t)d1++];
+        if (sum == 0) { d0 = d1; continue; } // (no mask of it has a candidate: its queries are padded below)
+        ExactGroupedCall gc;
+        gc.gq.assign((size_t)D, 0);
+        gc.cnt.assign((size_t)D, 0);
+        gc.goff.assign((size_t)D, 0);
+        gc.n = n;
+        gc.listed = (uint64_t)sum;
+        long long at = 0;
+        for (int d = d0; d < d1; ++d) { gc.gq[(size_t)d] = gq[(size_t)d]; gc.cnt[(size_t)d] = cnt[(size_t)d]; gc.goff[(size_t)d] = (int)at; at += cnt[(size_t)d]; }
+        if (!exact_grouped_plan(who, k, &gc)) return false;
+        if (!x_ids_.grow((size_t)sum)) return false;
+        const bool timed = profiling_;
+        if (timed && (!ev0_.create(true) || !ev1_.create(true))) return false;
+        if (timed) HIP_OK(hipEventRecord(E(ev0_), st));
+        HIP_OK(tag_lists_launch(s_ttags_, n, s_tmask_.get() + d0, d1 - d0, match, s_tcnt_.get() + d0, s_tcnt_.get() + D + d0, s_tcnt_.get() + 2 * (size_t)D + d0,
+                                x_ids_, sum, st));
+        if (timed) {
+            HIP_OK(hipEventRecord(E(ev1_), st));
+            HIP_OK(hipStreamSynchronize(st)); // (the scan records the same pair of events)
+            float ms = 0.f;
+            HIP_OK(hipEventElapsedTime(&ms, E(ev0_), E(ev1_)));
+            xt_list_ms_ += ms;
+        }
+        // the batch's queries: those of its masks that have a candidate
+        sel.clear();
+        qg.clear();
+        for (int i = 0; i < nq; ++i) {
+            const int d = tc.of[(size_t)i];
+            if (d >= d0 && d < d1 && cnt[(size_t)d] > 0) { sel.push_back(i); qg.push_back(d); }
+        }
+        const int nb = (int)sel.size();
+        uint64_t blocks = 0;
+        if (nb == nq) { // every query of the call: straight into the caller's arrays
+            if (!exact_knn_grouped_scan(who, queries, nullptr, nq, k, qg.data(), D, gc, out_ids, out_d, &blocks)) return false;
+        } else {
+            t_ids.resize((size_t)nb * k);
+            t_d.resize((size_t)nb * k);
+            if (queries) {
+                t_q.resize((size_t)nb * (size_t)dim_);
+                for (int j = 0; j < nb; ++j) memcpy(&t_q[(size_t)j * dim_], queries + (size_t)sel[(size_t)j] * dim_, sizeof(float) * (size_t)dim_);
+            }
+            if (!exact_knn_grouped_scan(who, queries ? t_q.data() : nullptr, queries ? nullptr : sel.data(), nb, k, qg.data(), D, gc, t_ids.data(), t_d.data(), &blocks)) return false;
+            for (int j = 0; j < nb; ++j) {
+                memcpy(out_ids + (size_t)sel[(size_t)j] * k, &t_ids[(size_t)j * k], 4u * (size_t)k);
+                memcpy(out_d + (size_t)sel[(size_t)j] * k, &t_d[(size_t)j * k], 4u * (size_t)k);
+            }
+        }
+        scanned_q += (uint64_t)nb;
+        listed += (uint64_t)sum;
+        batches += 1;
+        d0 = d1;
+    }
+    for (int i = 0; i < nq; ++i) // a mask without a candidate: padding, no scan
+        if (cnt[(size_t)tc.of[(size_t)i]] == 0) pad_results(out_ids + (size_t)i * k, out_d + (size_t)i * k, (size_t)k);
+    xt_info_[0] += 1; xt_info_[1] += (uint64_t)D; xt_info_[2] += scanned_q; xt_info_[3] += (uint64_t)nq - scanned_q; xt_info_[4] += listed; xt_info_[5] += batches;
     return true;
 }
 
@@ -4252,6 +4527,39 @@ DEV_API int hnswdev_knn_grouped_info(void *ctx, uint64_t out[4])
     CTX_OR_FAIL();
     if (!out) return -1;
     d->knn_grouped_info(out);
+    return 0;
+}
+DEV_API int hnswdev_knn_search_tagged(void *ctx, const float *queries, int nq, int entry_point, int k_beam, int k_out, int layer, const uint32_t *row_tags,
+                                      long long n_row_tags, const uint32_t *query_tags, int match, int *out_ids, float *out_dists, int *out_flags)
+{
+    CTX_OR_FAIL();
+    return d->knn_search_tagged(queries, nq, entry_point, k_beam, k_out, row_tags, n_row_tags, query_tags, match, out_ids, out_dists, out_flags, layer) ? 0 : -1;
+}
+DEV_API int hnswdev_knn_tagged_info(void *ctx, uint64_t out[5])
+{
+    CTX_OR_FAIL();
+    if (!out) return -1;
+    d->knn_tagged_info(out);
+    return 0;
+}
+DEV_API int hnswdev_exact_knn_tagged(void *ctx, const float *queries, int nq, long long n_rows, int k, const uint32_t *row_tags, long long n_row_tags,
+                                     const uint32_t *query_tags, int match, int *out_ids, float *out_dists)
+{
+    CTX_OR_FAIL();
+    return d->exact_knn_tagged(queries, nq, n_rows, k, row_tags, n_row_tags, query_tags, match, out_ids, out_dists) ? 0 : -1;
+}
+DEV_API int hnswdev_exact_tagged_info(void *ctx, uint64_t out[6])
+{
+    CTX_OR_FAIL();
+    if (!out) return -1;
+    d->exact_tagged_info(out);
+    return 0;
+}
+DEV_API int hnswdev_tag_list_ms(void *ctx, double *out_ms)
+{
+    CTX_OR_FAIL();
+    if (!out_ms) return -1;
+    *out_ms = d->tag_list_ms();
     return 0;
 }
 DEV_API int hnswdev_range_search(void *ctx, const float *queries, int nq, int entry_point, float range, int *out_counts, int *out_flags)

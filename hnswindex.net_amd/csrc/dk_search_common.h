@@ -66,6 +66,20 @@ struct GroupSet {
     __device__ __forceinline__ bool has(int id) const { return test(word(id)); }
     static constexpr bool kBitset = false;
 };
+// A tag filter over ids (knn_query_tagged, graph_search_tagged_kernel): tags[id] is an id's tag word, one bit per
+// tag, and `mask` this job's tags (wave-uniform, never 0: the host launches no job for a query without tags).  all == 0: an id
+// passes when it carries any of the mask's tags; all != 0: when it carries every one.  Ids >= n have the word 0, which passes
+// neither test -- the host writes it into vacant slots too.  The words are unsigned throughout: bit 31 is a tag like the others.
+struct TagSet {
+    const unsigned *tags;
+    long long n;
+    unsigned mask;
+    int all;
+    __device__ __forceinline__ unsigned word(int id) const { return (long long)id < n ? tags[id] : 0u; }
+    __device__ __forceinline__ bool test(unsigned w) const { return (w & mask) != 0u && (!all || (w & mask) == mask); }
+    __device__ __forceinline__ bool has(int id) const { return test(word(id)); }
+    static constexpr bool kBitset = false;
+};
 
 struct GraphView {
     const int *adj0;

@@ -178,6 +178,47 @@ API int hnsw_mi355x_exact_knn_query_grouped(void *handle, const float *vectors, 
     return 0;
 }
 
+// The tagged calls: a tag word per id, a mask per query, `match` 0 any / 1 all.  The arguments both check here.
+static bool tagged_args(const char *who, bool pointers_ok, const uint32_t *row_tags, long long n_row_tags, int match)
+{
+    if (!pointers_ok) { set_error(std::string("System.ArgumentNullException: ") + who); return false; }
+    if (!row_tags || n_row_tags < 0) { set_error(std::string("System.ArgumentException: ") + who + ": row_tags must not be NULL and n_row_tags must be >= 0"); return false; }
+    if (match != 0 && match != 1) { set_error(std::string("System.ArgumentOutOfRangeException: ") + who + ": match = " + std::to_string(match) + " is neither 0 (any) nor 1 (all)"); return false; }
+    return true;
+}
+// The flat scan with a tag mask per query: every distinct mask a candidate list, built on the device.
+API int hnsw_mi355x_exact_knn_query_tagged(void *handle, const float *vectors, int count, int dim, int k, const uint32_t *row_tags, long long n_row_tags,
+                                           const uint32_t *query_tags, int match, int *out_ids, float *out_dists)
+{
+    if (!handle) return 0;
+    if (count <= 0) return 0;
+    const bool ok = vectors && out_ids && out_dists && query_tags && dim > 0;
+    if (!tagged_args("hnsw_mi355x_exact_knn_query_tagged", ok, row_tags, n_row_tags, match)) return -1;
+    LOCK_INDEX(handle);
+    std::string err;
+    if (static_cast<HnswIndex *>(handle)->exact_knn_query_tagged(vectors, count, dim, k, row_tags, n_row_tags, query_tags, match, out_ids, out_dists, err) < 0) {
+        set_error(err);
+        return -1;
+    }
+    return 0;
+}
+// KnnQuery with a tag mask per query: one device traversal for every mask.  Exclusive, like the filtered call.
+API int hnsw_mi355x_knn_query_tagged(void *handle, const float *vectors, int count, int dim, int k, int layer, const uint32_t *row_tags, long long n_row_tags,
+                                     const uint32_t *query_tags, int match, int *out_ids, float *out_dists)
+{
+    if (!handle) return 0;
+    if (count <= 0) return 0;
+    const bool ok = vectors && out_ids && out_dists && query_tags && dim > 0;
+    if (!tagged_args("hnsw_mi355x_knn_query_tagged", ok, row_tags, n_row_tags, match)) return -1;
+    LOCK_INDEX(handle);
+    std::string err;
+    if (static_cast<HnswIndex *>(handle)->knn_query_tagged(vectors, count, dim, k, layer, row_tags, n_row_tags, query_tags, match, out_ids, out_dists, err) < 0) {
+        set_error(err);
+        return -1;
+    }
+    return 0;
+}
+
 // KnnQuery with a group filter per query: one device traversal for every group.  Exclusive, like the filtered call.
 API int hnsw_mi355x_knn_query_grouped(void *handle, const float *vectors, int count, int dim, int k, int layer, const int *row_group, long long n_row_group,
                                       const int *query_group, int n_groups, int *out_ids, float *out_dists)
@@ -586,6 +627,20 @@ API int hnsw_mi355x_knn_grouped_info(void *h, uint64_t out[4])
     if (!h || !out) return -1;
     LOCK_INDEX(h);
     static_cast<HnswIndex *>(h)->knn_grouped_info(out);
+    return 0;
+}
+API int hnsw_mi355x_knn_tagged_info(void *h, uint64_t out[5])
+{
+    if (!h || !out) return -1;
+    LOCK_INDEX(h);
+    static_cast<HnswIndex *>(h)->knn_tagged_info(out);
+    return 0;
+}
+API int hnsw_mi355x_exact_tagged_info(void *h, uint64_t out[6])
+{
+    if (!h || !out) return -1;
+    LOCK_INDEX(h);
+    static_cast<HnswIndex *>(h)->exact_tagged_info(out);
     return 0;
 }
 // HNSWIndex.GetInfo() / GetConnectedComponentCounts() (HNSWIndex.cs:192-205) from the graph mirror on the device:

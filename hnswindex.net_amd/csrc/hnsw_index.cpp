@@ -1752,6 +1752,98 @@ void HnswIndex::knn_grouped_info(uint64_t out[4]) const
     for (const auto &r : replicas_) { r->knn_grouped_info(one); for (int i = 0; i < 4; ++i) out[i] += one[i]; }
 }
 
+// The tagged calls' argument rules (tag_args_error, device_backend.h) as the ABI reports a breach: `who` is the ABI call.
+static bool tag_args_ok(const char *who, const uint32_t *query_tags, int count, int match, TagCall *tc, std::string &err)
+{
+    const std::string why = tag_args_error(who, query_tags, count, match, tc);
+    if (!why.empty()) err = "System.ArgumentOutOfRangeException: " + why;
+    return why.empty();
+}
+
+// live_labels' counterpart for the tag words of a tagged call: once slots are vacant row_tags / n_row_tags are replaced by a copy (in
+// `live`) of the words of ids below the graph's length with 0 -- no tag, a candidate of no query -- in the vacant slots.  The copy
+// ends with a 0 beyond n_row_tags, so that it is never NULL.  true: a copy was made.
+bool HnswIndex::live_tags(const uint32_t *&row_tags, long long &n_row_tags, std::vector<uint32_t> &live) const
+{
+    if (graph_.count == graph_.length) return false;
+    const long long n = std::min<long long>(n_row_tags, graph_.length);
+    live.assign(row_tags, row_tags + n);
+    for (long long id = 0; id < n; ++id)
+        if (graph_.removed[(size_t)id]) live[(size_t)id] = 0u;
+    live.push_back(0u);
+    row_tags = live.data();
+    n_row_tags = n;
+    return true;
+}
+
+// KnnQuery with a tag mask per query: knn_query_grouped with the predicate "the id's tag word matches the query's
+// mask".  The words go to the device as they are; once slots are vacant a copy does, with 0 in the vacant slots (live_tags).  Which
+// masks have a candidate the device finds out (Device::search_tagged); the host way below builds a mask's bitset only when a query
+// of that mask comes to it.
+int HnswIndex::knn_query_tagged(const float *queries, int count, int dim, int k, int layer, const uint32_t *row_tags, long long n_row_tags,
+                                const uint32_t *query_tags, int match, int *out_ids, float *out_dists, std::string &err)
+{
+    if (count <= 0) return 0;
+    if (failed(err)) return -1;
+    const char *who = "hnsw_mi355x_knn_query_tagged";
+    TagCall tc;
+    if (!tag_args_ok(who, query_tags, count, match, &tc, err)) return -1;
+    const bool empty = k < 1 || graph_.entry < 0 || graph_.count <= 0;
+    if (!empty && !layer_ok(layer, err)) { err = "System.IndexOutOfRangeException: " + std::string(who) + ": " + err; return -1; }
+    if (empty) { // HNSWIndex.cs:109: empty result lists, padded by the export
+        pad_results(out_ids, out_dists, (size_t)count * (size_t)std::max(k, 0));
+        return 0;
+    }
+    std::vector<uint32_t> live;
+    (void)live_tags(row_tags, n_row_tags, live);
+    const long long n_lab = std::min<long long>(n_row_tags, graph_.length); // only the words of graph ids count
+    bool any = false; // a call whose every mask is 0, or that brings no word of a graph id: the result is empty in any order
+    for (size_t d = 0; d < tc.masks.size() && !any; ++d) any = tc.masks[d] != 0u;
+    if (!any || n_lab <= 0) {
+        pad_results(out_ids, out_dists, (size_t)count * (size_t)k);
+        return 0;
+    }
+    if (set_resident_queries(queries, count, dim, err) < 0) return -1;
+    // The lock-step way for the queries in `which` (nullptr: all of them): one bitset per distinct mask concerned, one filtered call
+    // per mask; queries of a mask without a candidate are padded.
+    const auto lockstep = [&](const int *which, int n) -> int {
+        std::vector<std::vector<int>> of(tc.masks.size());
+        for (int i = 0; i < n; ++i) {
+            const int qi = which ? which[i] : i;
+            of[(size_t)tc.of[(size_t)qi]].push_back(qi);
+        }
+        std::vector<uint32_t> bits((size_t)((n_lab + 31) / 32) + 1);
+        for (size_t d = 0; d < of.size(); ++d) {
+            if (of[d].empty()) continue;
+            std::fill(bits.begin(), bits.end(), 0u);
+            bool has = false;
+            for (long long id = 0; id < n_lab; ++id)
+                if (tag_match_host(row_tags[id], tc.masks[d], match)) { bits[(size_t)(id >> 5)] |= 1u << (id & 31); has = true; }
+            if (!has) {
+                for (const int qi : of[d]) pad_results(out_ids + (size_t)qi * k, out_dists + (size_t)qi * k, (size_t)k);
+                continue;
+            }
+            if (knn_query_lockstep(of[d].data(), (int)of[d].size(), k, out_ids, out_dists, err, AllowBits{bits.data(), n_lab}, layer) < 0) return -1;
+        }
+        return 0;
+    };
+    const int ef = std::max(p_.min_nn, k); // HNSWIndex.cs:115
+    const int ep = graph_.entry, top = graph_.top_layer();
+    return answer_resident(count, ef,
+        [&](Device *ctx, int cnt, long long lo, int *flag) { // the words are uploaded to every context; lo .. of query_tags too
+            return ctx->search_tagged(cnt, ep, top, ef, k, row_tags, n_lab, query_tags + lo, match, out_ids + (size_t)lo * k, out_dists + (size_t)lo * k, flag, layer);
+        },
+        lockstep, "search_tagged failed", err);
+}
+
+void HnswIndex::knn_tagged_info(uint64_t out[5]) const
+{
+    for (int i = 0; i < 5; ++i) out[i] = 0;
+    uint64_t one[5];
+    if (dev_) { dev_->knn_tagged_info(one); for (int i = 0; i < 5; ++i) out[i] += one[i]; }
+    for (const auto &r : replicas_) { r->knn_tagged_info(one); for (int i = 0; i < 5; ++i) out[i] += one[i]; }
+}
+
 // The candidates of a flat scan as Device::exact_knn / exact_range take them: the row count, and allow_bits / nbits replaced by
 // allow AND live (in `live`) once slots are vacant.
 long long HnswIndex::exact_candidates(const uint32_t *&allow_bits, long long &nbits, std::vector<uint32_t> &live) const
@@ -1825,6 +1917,30 @@ int HnswIndex::exact_knn_query_grouped(const float *queries, int count, int dim,
     if (live_labels(row_group, n_row_group, live) && n_row_group == 0) { pad_results(out_ids, out_dists, (size_t)count * (size_t)k); return 0; } // vacant slots and no label: no candidate
     // (the scan stages its queries in a buffer of its own: the resident set, sharded or not, stays what it was)
     if (!dev_->exact_knn_grouped(queries, count, length, k, row_group, n_row_group, query_group, n_groups, out_ids, out_dists)) { err = get_dev_error(); return -1; }
+    return 0;
+}
+
+// The flat scan with a tag mask per query.  The words go to the device as live_tags leaves them: a vacant slot's
+// word is 0, so the scan needs no live set beside them.
+int HnswIndex::exact_knn_query_tagged(const float *queries, int count, int dim, int k, const uint32_t *row_tags, long long n_row_tags, const uint32_t *query_tags,
+                                      int match, int *out_ids, float *out_dists, std::string &err)
+{
+    if (count <= 0) return 0;
+    if (failed(err)) return -1;
+    const char *who = "hnsw_mi355x_exact_knn_query_tagged";
+    if (k > kExactMaxK) { err = std::string("System.ArgumentOutOfRangeException: ") + who + ": k = " + std::to_string(k) + " is above the limit of " + std::to_string(kExactMaxK); return -1; }
+    TagCall tc;
+    if (!tag_args_ok(who, query_tags, count, match, &tc, err)) return -1;
+    if (k < 1 || graph_.count <= 0) {
+        pad_results(out_ids, out_dists, (size_t)count * (size_t)std::max(k, 0));
+        return 0;
+    }
+    if (!ensure_dim(dim, err)) return -1;
+    const long long length = graph_.length;
+    std::vector<uint32_t> live;
+    if (live_tags(row_tags, n_row_tags, live) && n_row_tags == 0) { pad_results(out_ids, out_dists, (size_t)count * (size_t)k); return 0; } // vacant slots and no word: no candidate
+    // (the scan stages its queries in a buffer of its own: the resident set, sharded or not, stays what it was)
+    if (!dev_->exact_knn_tagged(queries, count, length, k, row_tags, n_row_tags, query_tags, match, out_ids, out_dists)) { err = get_dev_error(); return -1; }
     return 0;
 }
 

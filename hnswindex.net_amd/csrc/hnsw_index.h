@@ -68,6 +68,11 @@ public:
     int exact_knn_query_grouped(const float *queries, int count, int dim, int k, const int *row_group, long long n_row_group, const int *query_group,
                                 int n_groups, int *out_ids, float *out_dists, std::string &err);
     void exact_grouped_info(uint64_t out[4]) const { if (dev_) dev_->exact_grouped_info(out); else out[0] = out[1] = out[2] = out[3] = 0; }
+    // hnsw_mi355x_exact_knn_query_tagged: exact_knn_query with a tag mask per query (Device::exact_knn_tagged): query i's
+    // candidates are the live ids j < n_row_tags whose word row_tags[j] matches query_tags[i] under `match` (0 any, 1 all).  0 or -1.
+    int exact_knn_query_tagged(const float *queries, int count, int dim, int k, const uint32_t *row_tags, long long n_row_tags, const uint32_t *query_tags,
+                               int match, int *out_ids, float *out_dists, std::string &err);
+    void exact_tagged_info(uint64_t out[6]) const { for (int i = 0; i < 6; ++i) out[i] = 0; if (dev_) dev_->exact_tagged_info(out); }
     // hnsw_mi355x_exact_range_query_grouped: exact_range_query with exact_knn_query_grouped's group per query
     // (Device::exact_range_grouped); the labels of vacant slots are taken out as for that call
     int exact_range_query_grouped(const float *queries, int count, int dim, float range, const int *row_group, long long n_row_group, const int *query_group,
@@ -109,6 +114,15 @@ public:
                           int n_groups, int *out_ids, float *out_dists, std::string &err);
     // Device::knn_grouped_info summed over the contexts
     void knn_grouped_info(uint64_t out[4]) const;
+    // hnsw_mi355x_knn_query_tagged: KnnQuery on `layer` with a tag mask per query -- query i is answered from the ids
+    // j < n_row_tags whose word row_tags[j] matches query_tags[i] under `match` (0 any, 1 all), byte for byte what knn_query_general
+    // returns for it with those ids as the allow-set.  One device traversal for every mask (Device::search_tagged); jobs handed back,
+    // and the whole call when the traversal does not run on the device, go the lock-step way once per distinct mask.  Exclusive
+    // lock.  0 or -1.
+    int knn_query_tagged(const float *queries, int count, int dim, int k, int layer, const uint32_t *row_tags, long long n_row_tags, const uint32_t *query_tags,
+                         int match, int *out_ids, float *out_dists, std::string &err);
+    // Device::knn_tagged_info summed over the contexts
+    void knn_tagged_info(uint64_t out[5]) const;
     // hnsw_mi355x_multilayer_knn_query: the number of layer slots (min(top, max_layer) + 1; 0 for an empty index, k < 1 or
     // max_layer == -1), or -1.  out_*: [count][layers_cap][k - 1].  Exclusive lock.
     int multilayer_knn_query(const float *queries, int count, int dim, int k, int max_layer, int min_layer, int layers_cap, int *out_ids,
@@ -216,6 +230,7 @@ private:
     bool insert_batch(const std::vector<int> &bid, std::string &err);
     long long exact_candidates(const uint32_t *&allow_bits, long long &nbits, std::vector<uint32_t> &live) const;
     bool live_labels(const int *&row_group, long long &n_row_group, std::vector<int> &live) const;
+    bool live_tags(const uint32_t *&row_tags, long long &n_row_tags, std::vector<uint32_t> &live) const;
     int reach_chain(const char *who, int min_layer, hnsw_mi355x_layer_reach *out, int cap, uint32_t *bits, int *hops, std::string &err);
     bool insert_exact_window(const std::vector<int> &fresh, int &p, int W, bool background, std::string &err);
     // Selected neighbour ids per (batch item, layer).  Device results are read in place from the

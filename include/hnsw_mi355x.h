@@ -345,6 +345,45 @@ int hnsw_mi355x_knn_query_grouped(void *handle, const float *vectors, int count,
  * hand-backs also count in hnswdev_stats.search_launches / search_evals / search_overflows, as a filtered call's do; a call
  * answered by the host traversal alone counts nowhere here.)  0, or -1 for a NULL argument. */
 int hnsw_mi355x_knn_grouped_info(void *handle, uint64_t out[4]);
+
+/* The tagged calls (no reference counterpart): metadata that is not a partition -- a document with several labels,
+ * a user who may read several tenants' rows, a product in several categories.  row_tags is uint32[n_row_tags], indexed by id, one
+ * bit per tag (32 tags); query_tags is uint32[count], a mask per query; match is the mode of the whole call:
+ *   0 "any": id j is a candidate of query i iff (row_tags[j] & query_tags[i]) != 0;
+ *   1 "all": iff query_tags[i] != 0 and (row_tags[j] & query_tags[i]) == query_tags[i].
+ * An id past the end of row_tags, a vacant slot (a removed id) and a row whose word is 0 carry no tag and are candidates of no
+ * query; a query whose mask is 0 has no candidate; n_row_tags beyond the index's length is clamped.  The words are unsigned: bit 31
+ * is a tag like the others.  A call may hold at most 65 536 distinct masks.
+ * hnsw_mi355x_knn_query_tagged: for every distinct mask m the rows of the result at query_tags == m are byte for byte -- ids and
+ * distance bits -- what hnsw_mi355x_knn_query_at_layer returns for those queries with the allow-set {j : j matches m} and the same
+ * layer, and so carry its rules: the descent is not filtered, the beam is max(MinNN, k), the stable OrderBy(Dist).Take(k), -1 / NaN
+ * padding, the layer rule (layer outside 0 .. the entry point's top layer on a non-empty index: -1), padding for an empty index or
+ * k < 1.  All masks are answered by one device traversal (graph_search_tagged_kernel); a query whose mask has no candidate among
+ * the graph's ids gets a row of padding and costs no traversal.  The words and masks are uploaded with every call (nothing is
+ * cached between calls); hnsw_mi355x_set_devices(n): every context answers its shard of the queries with the words uploaded to it.
+ * A job the device hands back, and the whole call when the traversal does not run on the device, is answered by the host
+ * traversal, one filtered pass per distinct mask concerned, with the same results.  Takes the handle exclusively.
+ * hnsw_mi355x_exact_knn_query_tagged: the same candidates answered by the flat scan -- per distinct mask the rows of
+ * hnsw_mi355x_exact_knn_query with that allow-set, 1 <= k <= 1024 (above: -1), padding behind a mask's last candidate.  Every
+ * distinct mask is a candidate list built on the device; lists overlap, so the masks are scanned in batches whose lists hold at
+ * most 2^28 ids together (a longer list is a batch alone).  Always on the primary context.
+ * -1 with a message, nothing written: row_tags NULL or n_row_tags < 0; match other than 0 and 1; more than 65 536 distinct masks
+ * (the message names the index of the first mask beyond).  NULL handle and count <= 0: 0, nothing written. */
+int hnsw_mi355x_knn_query_tagged(void *handle, const float *vectors, int count, int dim, int k, int layer, const uint32_t *row_tags,
+                                 long long n_row_tags, const uint32_t *query_tags, int match, int *out_ids, float *out_dists);
+int hnsw_mi355x_exact_knn_query_tagged(void *handle, const float *vectors, int count, int dim, int k, const uint32_t *row_tags,
+                                       long long n_row_tags, const uint32_t *query_tags, int match, int *out_ids, float *out_dists);
+/* Counters of hnsw_mi355x_knn_query_tagged's device launches, summed over the contexts, since hnsw_mi355x_reset_stats: out[0] calls
+ * that reached a context (one per context and call), out[1] distinct masks of those calls, out[2] queries launched, out[3] queries
+ * padded without a job because their mask has no candidate, out[4] queries the device handed back to the host traversal.
+ * (Launches, evaluations and hand-backs also count in hnswdev_stats.search_*, as a filtered call's do; a call answered by the host
+ * traversal alone counts nowhere here.)  0, or -1 for a NULL argument. */
+int hnsw_mi355x_knn_tagged_info(void *handle, uint64_t out[5]);
+/* Counters of hnsw_mi355x_exact_knn_query_tagged since hnsw_mi355x_reset_stats: out[0] calls that counted candidates on the device,
+ * out[1] distinct masks of those calls, out[2] queries scanned, out[3] queries padded because their mask has no candidate, out[4]
+ * ids written into candidate lists, out[5] batches of masks scanned.  (Scan launches and pairs count in hnswdev_stats.exact_*.)
+ * 0, or -1 for a NULL argument. */
+int hnsw_mi355x_exact_tagged_info(void *handle, uint64_t out[6]);
 /* RangeQuery with a GROUP FILTER PER QUERY: the graph traversal of hnsw_mi355x_range_query_at_layer, query i
  * filtered by { j < n_row_group : row_group[j] == query_group[i] }.  Per group g the lists of the queries with query_group == g
  * are byte for byte -- ids, distance bits, the order among equal distances -- what hnsw_mi355x_range_query_at_layer returns for
@@ -668,6 +707,26 @@ int hnswdev_knn_search_grouped(void *ctx, const float *queries, int nq, int entr
                                long long n_row_group, const int *query_group, int n_groups, int *out_ids, float *out_dists, int *out_flags);
 /* out[0 .. 3] as hnsw_mi355x_knn_grouped_info, of this context; zeroed by hnswdev_reset_stats. */
 int hnswdev_knn_grouped_info(void *ctx, uint64_t out[4]);
+/* hnswdev_knn_search_at_layer with a tag mask per query (graph_search_tagged_kernel; the words, masks and match of
+ * hnsw_mi355x_knn_query_tagged): query i is answered from the graph ids j < n_row_tags whose word matches query_tags[i], row by row
+ * what hnswdev_knn_search_at_layer returns for it with those ids as the allow-set.  A query whose mask has no candidate: a padded
+ * row, flag 0, no job.  out_flags[i] = 1: handed back, as hnswdev_knn_search_filtered.  -1 with a message and no launch: a NULL
+ * array, n_row_tags < 0, match other than 0 and 1, more than 65 536 distinct masks, an entry point outside the graph, k_out < 1 or
+ * k_beam < k_out, a layer the entry point does not have. */
+int hnswdev_knn_search_tagged(void *ctx, const float *queries, int nq, int entry_point, int k_beam, int k_out, int layer, const uint32_t *row_tags,
+                              long long n_row_tags, const uint32_t *query_tags, int match, int *out_ids, float *out_dists, int *out_flags);
+/* out[0 .. 4] as hnsw_mi355x_knn_tagged_info, of this context; zeroed by hnswdev_reset_stats. */
+int hnswdev_knn_tagged_info(void *ctx, uint64_t out[5]);
+/* hnswdev_exact_knn_grouped with a tag mask per query (the words, masks and match of hnsw_mi355x_exact_knn_query_tagged) over the
+ * uploaded rows j < min(n_rows, uploaded, n_row_tags); queries == NULL: the resident query set.  -1 with a message and no scan: a
+ * NULL array, n_row_tags < 0, match other than 0 and 1, more than 65 536 distinct masks, k < 1 or k > 1024. */
+int hnswdev_exact_knn_tagged(void *ctx, const float *queries, int nq, long long n_rows, int k, const uint32_t *row_tags, long long n_row_tags,
+                             const uint32_t *query_tags, int match, int *out_ids, float *out_dists);
+/* out[0 .. 5] as hnsw_mi355x_exact_tagged_info, of this context; zeroed by hnswdev_reset_stats. */
+int hnswdev_exact_tagged_info(void *ctx, uint64_t out[6]);
+/* Measurement aid: the HIP-event time, in ms, of the tagged calls' list-building kernels (count, offsets, fill) on this context
+ * while profiling is on; zeroed by hnswdev_reset_stats. */
+int hnswdev_tag_list_ms(void *ctx, double *out_ms);
 /* hnswdev_range_search_at_layer with a group filter per query (range_sort_grouped_kernel behind graph_range_kernel): query i is
  * answered as with the allow-set { id : row_group[id] == query_group[i] }; only the labels of graph ids count.  out_counts /
  * out_flags and the fetch with hnswdev_range_results as hnswdev_range_search_filtered; a query whose group holds no graph id gets
