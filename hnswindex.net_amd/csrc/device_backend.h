@@ -123,6 +123,9 @@ class Device;
 struct VisitedScratch;   // device_backend.hip: the visited-set memory of a traversal launch
 struct TraversalLaunch;  // ... which traversal kernel form a launch runs, on how many waves, with which flags
 struct LaunchFamily;     // ... the hnswdev_stats counters of one kernel family
+struct AllowPred;        // host_structs.h: an allow-set or a group label over ids
+struct PredicateCall;    // device_backend.hip: the arguments every KnnQuery with a predicate over ids has
+template <class K> struct PredicatePlan; // ... and what its launches need, K the kernel's type
 struct ExactScanArgs;    // dk_exact.h: what one launch of the flat scan reads
 enum class ExactStart;   // device_backend.hip: how a flat-scan call begins -- failed, nothing to measure, ready
 struct ExactScanInput;   // ... the queries and the id list of an ungrouped flat scan
@@ -611,6 +614,12 @@ private:
     template <class Upload, class Launch> // the one launcher of the resident-query kernels (search_filtered, multilayer_search)
     bool run_resident(size_t row, long long chunk, size_t extra, bool hashed, int nq, int *out_ids, float *out_d, int *out_flag, Upload &&upload,
                       Launch &&launch);
+    // what search_filtered / search_grouped / search_tagged share: the entry checks, the planning step, the launches, the overflow count
+    template <class OwnRules> bool predicate_call_ok(const PredicateCall &c, OwnRules &&own_rules);
+    template <class Of> auto plan_predicate_search(const PredicateCall &c, Of of);
+    template <class K, class Upload, class JobsOf, class Predicate>
+    bool run_predicate_search(const PredicateCall &c, const PredicatePlan<K> &p, size_t extra, Upload &&upload, JobsOf &&jobs_of, Predicate &&predicate);
+    uint64_t count_search_overflows(const PredicateCall &c);
     bool count_launch(const LaunchFamily *family, unsigned long long evals, bool hashed, bool timed, void *t0, void *t1);
     int num_cu_ = 256;
     // Persistent launches never use more than 16 one-wave blocks per CU (the traversal kernels need
@@ -724,6 +733,8 @@ private:
     DevBuf<SearchHit> s_rlists_; // range search: long per-wave result lists for the few jobs that outgrow s_spill_'s
     double range_hint_ = 48.0;      // results per query of the last range search (sizes the next arena)
     std::vector<SearchHit> abi_range_; // hnswdev_range_search's results until hnswdev_range_results
+    auto host_list_of(int layer) const;  // what range_search_filtered / range_search_grouped share: the host graph's lists of a layer ...
+    bool finish_closure(int layer, int entry, float range, SearchHit *b, int m, const AllowPred &allow, int nq, int *out_counts, int *count); // ... and "finish a closure or fail the whole call"
     DevBuf<int> s_lk_[5];
     bool ensure_search_scratch(long long chunk, long long slots, int k, size_t vis_bytes_per_job);
     void *pinned_stage(size_t bytes);

@@ -1989,6 +1989,129 @@ bool Device::run_resident(size_t row, long long chunk, size_t extra, bool hashed
     return true;
 }
 
+// ---- KnnQuery with a predicate over ids (search_filtered, search_grouped, search_tagged; predicate_search in dk_search_kernels.h):
+// what the three calls share.  Each keeps its own argument rules, its upload layout and its counters.
+struct PredicateCall {
+    std::string who; // the caller's name, the prefix of every message
+    int nq, entry, entry_layer, search_layer, k, k_out;
+    int *out_ids;
+    float *out_d;
+    int *out_flag;
+};
+// What a launch needs beyond the call's own arguments (plan_predicate_search); ok: everything below it is set.
+template <class K>
+struct PredicatePlan {
+    bool ok;
+    K kernel;
+    TraversalLaunch tl;
+    int cand_cap, fspill;
+    long long chunk; // queries per launch
+};
+
+// The entry checks, in the order of their messages: the outputs and beams, the caller's own argument rules (own_rules(): the message
+// of the first one broken, empty when none is), the graph, the search layer, the entry point and the resident queries.
+template <class OwnRules>
+bool Device::predicate_call_ok(const PredicateCall &c, OwnRules &&own_rules)
+{
+    const std::string &who = c.who;
+    if (!c.out_ids || !c.out_d || !c.out_flag || c.k < 1 || c.k_out < 1) { set_dev_error(who + ": bad argument"); return false; }
+    if (const std::string why = own_rules(); !why.empty()) { set_dev_error(why); return false; }
+    if (g_n_ <= 0) { set_dev_error(who + ": no graph uploaded"); return false; }
+    if (c.search_layer < 0 || c.search_layer > c.entry_layer) { set_dev_error(who + ": the search layer must lie between 0 and the entry point's top layer"); return false; }
+    if (!(c.entry >= 0 && c.entry < g_n_ && c.entry_layer >= 0 && c.nq <= n_queries_) || tail_.n > 0) {
+        set_dev_error(who + ": entry point outside the graph, or fewer resident queries than asked for");
+        return false;
+    }
+    return true;
+}
+
+// The planning step: the candidate heap and its LDS, the traversal plan, the kernel of (metric, hashed) named by `of` (as
+// persistent_kernel takes it) placed on the device, the spill areas, and the scratch grown for launches of `chunk` queries.
+template <class Of>
+auto Device::plan_predicate_search(const PredicateCall &c, Of of)
+{
+    PredicatePlan<decltype(persistent_kernel(0, false, of))> p{};
+    const std::string &who = c.who;
+    p.chunk = std::min<long long>(c.nq, 1 << 20);
+    p.cand_cap = cand_lds_cap(c.k, pitch_, false, nbcap());
+    const size_t lds = search_lds_bytes(c.k, p.cand_cap, pitch_, false, nbcap());
+    if (lds > 64 * 1024) { set_dev_error(who + ": beam width / dimension exceed the LDS budget"); return p; }
+    if (!bind() || !plan_traversal(false, c.k, true, lds, &p.tl, true)) return p;
+    p.kernel = persistent_kernel(metric_, p.tl.vis.tab != nullptr, of);
+    place_persistent(p.kernel, p.tl, (int)p.chunk);
+    if (p.tl.slots < 1) { set_dev_error(who + ": the kernel does not fit the device"); return p; }
+    p.fspill = filter_spill_cap();
+    if (!ensure_search_scratch(p.chunk, max_slots(), c.k_out, p.tl.vis.bytes_per_job)) return p;
+    p.ok = s_fspill_.grow((size_t)p.tl.slots * (size_t)std::max(p.fspill, 1) + 8); // +8: get2 may read one entry past a heap
+    return p;
+}
+
+// The launches (run_resident): `extra` pinned bytes for upload(h); the launch for the queries from `off` has jobs_of(off, nj) jobs
+// (0: one wave finds the counter past the jobs and leaves) and, between the arguments that every predicate kernel begins and
+// ends with, the tuple predicate(off).
+template <class K, class Upload, class JobsOf, class Predicate>
+bool Device::run_predicate_search(const PredicateCall &c, const PredicatePlan<K> &p, size_t extra, Upload &&upload, JobsOf &&jobs_of, Predicate &&predicate)
+{
+    hipStream_t st = S(stream_);
+    const TraversalLaunch &tl = p.tl;
+    const auto launch = [&](long long off, int nj, int *d_ids, float *d_d) {
+        const int n = jobs_of(off, nj);
+        std::apply([&](auto... filter) {
+            hipLaunchKernelGGL(p.kernel, dim3(std::max(1, std::min(n, tl.slots))), dim3(tl.block), tl.lds_total, st, d_rows_, d_row_sn_,
+                               d_queries_ + (size_t)off * pitch_, d_q_sn_ ? d_q_sn_ + off : nullptr, pitch_, g_adj0_, g_stride0_, g_upper_, g_pool_, g_strideU_,
+                               c.entry, c.entry_layer, c.search_layer, c.k, p.cand_cap, reinterpret_cast<ND *>(s_fspill_.get()), p.fspill, s_visited_,
+                               tl.vis.words, tl.vis.tab, tl.vis.tab_cap, filter..., c.k_out, d_ids, d_d, s_flag_, s_evals_, nbcap(), n, s_jobctr_);
+        }, predicate(off));
+    };
+    return run_resident((size_t)c.k_out, p.chunk, extra, tl.vis.tab != nullptr, c.nq, c.out_ids, c.out_d, c.out_flag, upload, launch);
+}
+
+// The queries handed back (out_flag 1), counted once every row has its flag.
+uint64_t Device::count_search_overflows(const PredicateCall &c)
+{
+    uint64_t n = 0;
+    for (int i = 0; i < c.nq; ++i) n += (uint64_t)(c.out_flag[i] == 1);
+    stats_.search_overflows += n;
+    return n;
+}
+
+// The skip-and-order step of the calls with a predicate per query.  members(i): the graph ids that pass query i's predicate.  A
+// query with none is padded without a job; the others are listed per launch (chunk) in its order table -- the chunk's own query
+// indices -- longest traversal first: a traversal's length grows with 1 / selectivity and a persistent launch ends
+// with its longest job, so ascending by members, queries of equal counts in query order.
+struct LaunchOrder {
+    std::vector<int> order, jobs_of; // the tables, launch after launch ([nq]); the jobs of every launch
+    long long launched = 0;
+};
+template <class Members>
+static LaunchOrder order_by_members(int nq, long long chunk, Members &&members)
+{
+    LaunchOrder lo;
+    lo.order.resize((size_t)nq);
+    for (long long off = 0; off < nq; off += chunk) {
+        const int nj = (int)std::min<long long>(chunk, nq - off);
+        int *o = lo.order.data() + off;
+        int n = 0;
+        for (int i = 0; i < nj; ++i)
+            if (members(off + i) > 0) o[n++] = i;
+        std::stable_sort(o, o + n, [&](int a, int b) { return members(off + a) < members(off + b); });
+        for (int i = n; i < nj; ++i) o[i] = 0; // (never read: the launch has n jobs)
+        lo.jobs_of.push_back(n);
+        lo.launched += n;
+    }
+    return lo;
+}
+// ... and the rows no job writes: padding, flag 0 (after the launches' rows have been copied over the caller's arrays)
+template <class Members>
+static void pad_skipped(const PredicateCall &c, Members &&members)
+{
+    for (int i = 0; i < c.nq; ++i)
+        if (members(i) == 0) {
+            pad_results(c.out_ids + (size_t)i * c.k_out, c.out_d + (size_t)i * c.k_out, (size_t)c.k_out);
+            c.out_flag[i] = 0;
+        }
+}
+
 // KnnQuery with an allow-set (graph_search_filtered_kernel): resident query i from (entry, entry_layer), i < nq.  Only the words that
 // cover graph ids travel: bits of ids >= min(nbits, graph nodes) are never read.  A set that allows no graph id pads every
 // row without a launch (the result is empty whatever the order).
@@ -1996,13 +2119,9 @@ bool Device::search_filtered(int nq, int entry, int entry_layer, int k, int k_ou
                              float *out_d, int *out_flag, int search_layer)
 {
     if (nq <= 0) return true;
-    if (!out_ids || !out_d || !out_flag || k < 1 || k_out < 1 || nbits < 0 || (!allow_bits && nbits > 0)) { set_dev_error("search_filtered: bad argument"); return false; }
-    if (g_n_ <= 0) { set_dev_error("search_filtered: no graph uploaded"); return false; }
-    if (search_layer < 0 || search_layer > entry_layer) { set_dev_error("search_filtered: the search layer must lie between 0 and the entry point's top layer"); return false; }
-    if (!(entry >= 0 && entry < g_n_ && entry_layer >= 0 && nq <= n_queries_) || tail_.n > 0) {
-        set_dev_error("search_filtered: entry point outside the graph, or fewer resident queries than asked for");
-        return false;
-    }
+    const PredicateCall c{"search_filtered", nq, entry, entry_layer, search_layer, k, k_out, out_ids, out_d, out_flag};
+    const auto own_rules = [&] { return std::string(nbits < 0 || (!allow_bits && nbits > 0) ? "search_filtered: bad argument" : ""); };
+    if (!predicate_call_ok(c, own_rules)) return false;
     if (!allows_any(allow_bits, nbits, g_n_)) {
         pad_results(out_ids, out_d, (size_t)nq * (size_t)k_out);
         for (int i = 0; i < nq; ++i) out_flag[i] = 0;
@@ -2010,33 +2129,18 @@ bool Device::search_filtered(int nq, int entry, int entry_layer, int k, int k_ou
     }
     const long long n_allow = std::min<long long>(nbits, g_n_);
     const size_t words = (size_t)((n_allow + 31) / 32);
-    const int cand_cap = cand_lds_cap(k, pitch_, false, nbcap());
-    const size_t lds = search_lds_bytes(k, cand_cap, pitch_, false, nbcap());
-    if (lds > 64 * 1024) { set_dev_error("search_filtered: beam width / dimension exceed the LDS budget"); return false; }
-    if (!bind()) return false;
+    const auto p = plan_predicate_search(c, [](auto m, auto h) { return &graph_search_filtered_kernel<m, h>; });
+    if (!p.ok || !s_allow_.grow(std::max<size_t>(words, 1))) return false;
     hipStream_t st = S(stream_);
-    const long long chunk = std::min<long long>(nq, 1 << 20);
-    TraversalLaunch tl;
-    if (!plan_traversal(false, k, true, lds, &tl, true)) return false;
-    const auto kernel = persistent_kernel(metric_, tl.vis.tab != nullptr, [](auto m, auto h) { return &graph_search_filtered_kernel<m, h>; });
-    place_persistent(kernel, tl, (int)chunk);
-    const int fspill = filter_spill_cap();
-    if (!ensure_search_scratch(chunk, max_slots(), k_out, tl.vis.bytes_per_job)) return false;
-    if (!s_fspill_.grow((size_t)tl.slots * (size_t)std::max(fspill, 1) + 8)) return false; // +8: get2 may read one entry past a heap
-    if (!s_allow_.grow(std::max<size_t>(words, 1))) return false;
     const auto upload = [&](char *h_allow) { // the allow words go up from pinned memory
         memcpy(h_allow, allow_bits, 4u * words);
         HIP_OK(hipMemcpyAsync(s_allow_, h_allow, 4u * words, hipMemcpyHostToDevice, st));
         return true;
     };
-    const auto launch = [&](long long off, int nj, int *d_ids, float *d_d) {
-        hipLaunchKernelGGL(kernel, dim3(std::min(nj, tl.slots)), dim3(tl.block), tl.lds_total, st, d_rows_, d_row_sn_, d_queries_ + (size_t)off * pitch_,
-                           d_q_sn_ ? d_q_sn_ + off : nullptr, pitch_, g_adj0_, g_stride0_, g_upper_, g_pool_, g_strideU_, entry, entry_layer, search_layer, k,
-                           cand_cap, reinterpret_cast<ND *>(s_fspill_.get()), fspill, s_visited_, tl.vis.words, tl.vis.tab, tl.vis.tab_cap,
-                           reinterpret_cast<const unsigned *>(s_allow_.get()), n_allow, k_out, d_ids, d_d, s_flag_, s_evals_, nbcap(), nj, s_jobctr_);
-    };
-    if (!run_resident((size_t)k_out, chunk, 4u * words, tl.vis.tab != nullptr, nq, out_ids, out_d, out_flag, upload, launch)) return false;
-    for (int i = 0; i < nq; ++i) stats_.search_overflows += (uint64_t)(out_flag[i] == 1);
+    const auto every_query = [](long long, int nj) { return nj; };
+    const auto filter = [&](long long) { return std::make_tuple(reinterpret_cast<const unsigned *>(s_allow_.get()), n_allow); };
+    if (!run_predicate_search(c, p, 4u * words, upload, every_query, filter)) return false;
+    count_search_overflows(c);
     return true;
 }
 
@@ -2048,100 +2152,49 @@ static bool group_args_ok(const char *who, const int *query_group, int nq, int n
     return why.empty();
 }
 
-// KnnQuery with a group filter per query (graph_search_grouped_kernel): search_filtered's launch with the labels in
-// the allow words' place.  Only the labels of graph ids travel.  The graph ids of every group are counted here, on the host: a query
-// whose group has none is padded without a job, and the others are listed in the launch's order table longest traversal first -- a
-// traversal's length grows with 1 / selectivity and a persistent launch ends with its longest job -- ascending by
-// the group's count, queries of equal counts in query order.
+// KnnQuery with a group filter per query (graph_search_grouped_kernel): the labels in the allow words' place.  Only
+// the labels of graph ids travel.  The graph ids of every group are counted here, on the host, for order_by_members.
 bool Device::search_grouped(int nq, int entry, int entry_layer, int k, int k_out, const int *row_group, long long n_row_group, const int *query_group,
                             int n_groups, int *out_ids, float *out_d, int *out_flag, int search_layer)
 {
     if (nq <= 0) return true;
-    if (!out_ids || !out_d || !out_flag || k < 1 || k_out < 1) { set_dev_error("search_grouped: bad argument"); return false; }
-    if (!row_group || n_row_group < 0) { set_dev_error("search_grouped: row_group must not be NULL and n_row_group must be >= 0"); return false; }
-    if (!query_group) { set_dev_error("search_grouped: query_group must not be NULL"); return false; }
-    if (!group_args_ok("search_grouped", query_group, nq, n_groups)) return false;
-    if (g_n_ <= 0) { set_dev_error("search_grouped: no graph uploaded"); return false; }
-    if (search_layer < 0 || search_layer > entry_layer) { set_dev_error("search_grouped: the search layer must lie between 0 and the entry point's top layer"); return false; }
-    if (!(entry >= 0 && entry < g_n_ && entry_layer >= 0 && nq <= n_queries_) || tail_.n > 0) {
-        set_dev_error("search_grouped: entry point outside the graph, or fewer resident queries than asked for");
-        return false;
-    }
+    const PredicateCall c{"search_grouped", nq, entry, entry_layer, search_layer, k, k_out, out_ids, out_d, out_flag};
+    const auto own_rules = [&]() -> std::string {
+        if (!row_group || n_row_group < 0) return "search_grouped: row_group must not be NULL and n_row_group must be >= 0";
+        if (!query_group) return "search_grouped: query_group must not be NULL";
+        return group_args_error("search_grouped", query_group, nq, n_groups);
+    };
+    if (!predicate_call_ok(c, own_rules)) return false;
     const long long n_lab = std::min<long long>(n_row_group, g_n_);
-    std::vector<long long> members((size_t)n_groups, 0);
+    std::vector<long long> group_ids((size_t)n_groups, 0);
     for (long long id = 0; id < n_lab; ++id) {
         const int g = row_group[id];
-        if (g >= 0 && g < n_groups) members[(size_t)g] += 1;
+        if (g >= 0 && g < n_groups) group_ids[(size_t)g] += 1;
     }
-    // per launch (chunk) its order table: the chunk's own query indices with a non-empty group, ascending by the group's members
-    const long long chunk = std::min<long long>(nq, 1 << 20);
-    std::vector<int> order((size_t)nq), jobs_of;
-    long long launched = 0;
-    for (long long off = 0; off < nq; off += chunk) {
-        const int nj = (int)std::min<long long>(chunk, nq - off);
-        int *o = order.data() + off;
-        int n = 0;
-        for (int i = 0; i < nj; ++i)
-            if (members[(size_t)query_group[off + i]] > 0) o[n++] = i;
-        std::stable_sort(o, o + n, [&](int a, int b) { return members[(size_t)query_group[off + a]] < members[(size_t)query_group[off + b]]; });
-        for (int i = n; i < nj; ++i) o[i] = 0; // (never read: the launch has n jobs)
-        jobs_of.push_back(n);
-        launched += n;
+    const auto members = [&](long long i) { return group_ids[(size_t)query_group[i]]; };
+    const LaunchOrder lo = order_by_members(nq, std::min<long long>(nq, 1 << 20), members);
+    if (lo.launched > 0) { // (else nothing to traverse: no launch, as a set that allows nothing)
+        const auto p = plan_predicate_search(c, [](auto m, auto h) { return &graph_search_grouped_kernel<m, h>; });
+        if (!p.ok || !s_glabel_.grow((size_t)n_lab) || !s_gquery_.grow(2 * (size_t)nq)) return false;
+        hipStream_t st = S(stream_);
+        const size_t b_lab = 4u * (size_t)n_lab, b_q = 4u * (size_t)nq;
+        const auto upload = [&](char *h) { // labels, groups and order tables go up from pinned memory: [row_group | query_group | order]
+            memcpy(h, row_group, b_lab);
+            memcpy(h + b_lab, query_group, b_q);
+            memcpy(h + b_lab + b_q, lo.order.data(), b_q);
+            HIP_OK(hipMemcpyAsync(s_glabel_, h, b_lab, hipMemcpyHostToDevice, st));
+            HIP_OK(hipMemcpyAsync(s_gquery_, h + b_lab, 2 * b_q, hipMemcpyHostToDevice, st));
+            return true;
+        };
+        const auto listed = [&](long long off, int) { return lo.jobs_of[(size_t)(off / p.chunk)]; };
+        const auto filter = [&](long long off) { return std::make_tuple(s_glabel_.get(), n_lab, s_gquery_.get() + off, s_gquery_.get() + (size_t)nq + off); };
+        if (!run_predicate_search(c, p, b_lab + 2 * b_q, upload, listed, filter)) return false;
     }
-    // the rows no job writes: padding, flag 0 (after the launches' rows have been copied over the caller's arrays)
-    const auto pad_skipped = [&] {
-        for (int i = 0; i < nq; ++i)
-            if (members[(size_t)query_group[i]] == 0) {
-                pad_results(out_ids + (size_t)i * k_out, out_d + (size_t)i * k_out, (size_t)k_out);
-                out_flag[i] = 0;
-            }
-    };
-    if (launched == 0) { // (nothing to traverse: no launch, as a set that allows nothing)
-        pad_skipped();
-        kg_info_[0] += 1;
-        kg_info_[2] += (uint64_t)nq;
-        return true;
-    }
-    const int cand_cap = cand_lds_cap(k, pitch_, false, nbcap());
-    const size_t lds = search_lds_bytes(k, cand_cap, pitch_, false, nbcap());
-    if (lds > 64 * 1024) { set_dev_error("search_grouped: beam width / dimension exceed the LDS budget"); return false; }
-    if (!bind()) return false;
-    hipStream_t st = S(stream_);
-    TraversalLaunch tl;
-    if (!plan_traversal(false, k, true, lds, &tl, true)) return false;
-    const auto kernel = persistent_kernel(metric_, tl.vis.tab != nullptr, [](auto m, auto h) { return &graph_search_grouped_kernel<m, h>; });
-    place_persistent(kernel, tl, (int)chunk);
-    if (tl.slots < 1) { set_dev_error("search_grouped: the kernel does not fit the device"); return false; }
-    const int fspill = filter_spill_cap();
-    if (!ensure_search_scratch(chunk, max_slots(), k_out, tl.vis.bytes_per_job)) return false;
-    if (!s_fspill_.grow((size_t)tl.slots * (size_t)std::max(fspill, 1) + 8)) return false; // +8: get2 may read one entry past a heap
-    if (!s_glabel_.grow((size_t)n_lab) || !s_gquery_.grow(2 * (size_t)nq)) return false;
-    const size_t b_lab = 4u * (size_t)n_lab, b_q = 4u * (size_t)nq;
-    const auto upload = [&](char *h) { // labels, groups and order tables go up from pinned memory: [row_group | query_group | order]
-        memcpy(h, row_group, b_lab);
-        memcpy(h + b_lab, query_group, b_q);
-        memcpy(h + b_lab + b_q, order.data(), b_q);
-        HIP_OK(hipMemcpyAsync(s_glabel_, h, b_lab, hipMemcpyHostToDevice, st));
-        HIP_OK(hipMemcpyAsync(s_gquery_, h + b_lab, 2 * b_q, hipMemcpyHostToDevice, st));
-        return true;
-    };
-    const auto launch = [&](long long off, int, int *d_ids, float *d_d) {
-        const int n = jobs_of[(size_t)(off / chunk)]; // (0: one wave finds the counter past the jobs and leaves)
-        hipLaunchKernelGGL(kernel, dim3(std::max(1, std::min(n, tl.slots))), dim3(tl.block), tl.lds_total, st, d_rows_, d_row_sn_, d_queries_ + (size_t)off * pitch_,
-                           d_q_sn_ ? d_q_sn_ + off : nullptr, pitch_, g_adj0_, g_stride0_, g_upper_, g_pool_, g_strideU_, entry, entry_layer, search_layer, k,
-                           cand_cap, reinterpret_cast<ND *>(s_fspill_.get()), fspill, s_visited_, tl.vis.words, tl.vis.tab, tl.vis.tab_cap,
-                           s_glabel_.get(), n_lab, s_gquery_.get() + off, s_gquery_.get() + (size_t)nq + off, k_out, d_ids, d_d, s_flag_, s_evals_, nbcap(), n,
-                           s_jobctr_);
-    };
-    if (!run_resident((size_t)k_out, chunk, b_lab + 2 * b_q, tl.vis.tab != nullptr, nq, out_ids, out_d, out_flag, upload, launch)) return false;
-    pad_skipped();
+    pad_skipped(c, members); // (every row when nothing was launched: no flag is set then)
     kg_info_[0] += 1;
-    kg_info_[1] += (uint64_t)launched;
-    kg_info_[2] += (uint64_t)(nq - launched);
-    for (int i = 0; i < nq; ++i) {
-        stats_.search_overflows += (uint64_t)(out_flag[i] == 1);
-        kg_info_[3] += (uint64_t)(out_flag[i] == 1);
-    }
+    kg_info_[1] += (uint64_t)lo.launched;
+    kg_info_[2] += (uint64_t)(nq - lo.launched);
+    kg_info_[3] += count_search_overflows(c);
     return true;
 }
 
@@ -2188,97 +2241,48 @@ bool Device::tag_counts(const unsigned *row_tags, long long n, const std::vector
     return true;
 }
 
-// KnnQuery with a tag mask per query (graph_search_tagged_kernel): search_grouped's launch with the tag words in the
-// labels' place.  Only the words of graph ids travel.  The candidates of every distinct mask are counted on the device
-// (tag_counts): a query whose mask has none is padded without a job, and the others are listed in the launch's order table longest
-// traversal first, as search_grouped lists them -- ascending by their mask's count, queries of equal counts in query order.
+// KnnQuery with a tag mask per query (graph_search_tagged_kernel): the tag words in the labels' place.  Only the
+// words of graph ids travel.  The candidates of every distinct mask are counted on the device (tag_counts) for order_by_members.
 bool Device::search_tagged(int nq, int entry, int entry_layer, int k, int k_out, const uint32_t *row_tags, long long n_row_tags, const uint32_t *query_tags,
                            int match, int *out_ids, float *out_d, int *out_flag, int search_layer)
 {
     if (nq <= 0) return true;
-    if (!out_ids || !out_d || !out_flag || k < 1 || k_out < 1) { set_dev_error("search_tagged: bad argument"); return false; }
-    if (!row_tags || n_row_tags < 0) { set_dev_error("search_tagged: row_tags must not be NULL and n_row_tags must be >= 0"); return false; }
-    if (!query_tags) { set_dev_error("search_tagged: query_tags must not be NULL"); return false; }
+    const PredicateCall c{"search_tagged", nq, entry, entry_layer, search_layer, k, k_out, out_ids, out_d, out_flag};
     TagCall tc;
-    if (!tag_args_ok("search_tagged", query_tags, nq, match, &tc)) return false;
-    if (g_n_ <= 0) { set_dev_error("search_tagged: no graph uploaded"); return false; }
-    if (search_layer < 0 || search_layer > entry_layer) { set_dev_error("search_tagged: the search layer must lie between 0 and the entry point's top layer"); return false; }
-    if (!(entry >= 0 && entry < g_n_ && entry_layer >= 0 && nq <= n_queries_) || tail_.n > 0) {
-        set_dev_error("search_tagged: entry point outside the graph, or fewer resident queries than asked for");
-        return false;
-    }
+    const auto own_rules = [&]() -> std::string {
+        if (!row_tags || n_row_tags < 0) return "search_tagged: row_tags must not be NULL and n_row_tags must be >= 0";
+        if (!query_tags) return "search_tagged: query_tags must not be NULL";
+        return tag_args_error("search_tagged", query_tags, nq, match, &tc);
+    };
+    if (!predicate_call_ok(c, own_rules)) return false;
     const long long n_lab = std::min<long long>(n_row_tags, g_n_);
     std::vector<int> cnt(tc.masks.size(), 0);
     if (n_lab > 0 && (!bind() || !tag_counts(row_tags, n_lab, tc.masks, match, cnt))) return false; // (no word of a graph id: no candidate, nothing goes up)
     const auto members = [&](long long i) { return cnt[(size_t)tc.of[(size_t)i]]; };
-    // per launch (chunk) its order table: the chunk's own query indices whose mask has a candidate, ascending by the mask's count
-    const long long chunk = std::min<long long>(nq, 1 << 20);
-    std::vector<int> order((size_t)nq), jobs_of;
-    long long launched = 0;
-    for (long long off = 0; off < nq; off += chunk) {
-        const int nj = (int)std::min<long long>(chunk, nq - off);
-        int *o = order.data() + off;
-        int n = 0;
-        for (int i = 0; i < nj; ++i)
-            if (members(off + i) > 0) o[n++] = i;
-        std::stable_sort(o, o + n, [&](int a, int b) { return members(off + a) < members(off + b); });
-        for (int i = n; i < nj; ++i) o[i] = 0; // (never read: the launch has n jobs)
-        jobs_of.push_back(n);
-        launched += n;
+    const LaunchOrder lo = order_by_members(nq, std::min<long long>(nq, 1 << 20), members);
+    if (lo.launched > 0) { // (else nothing to traverse: no launch, as a set that allows nothing)
+        const auto p = plan_predicate_search(c, [](auto m, auto h) { return &graph_search_tagged_kernel<m, h>; });
+        if (!p.ok || !s_tquery_.grow(2 * (size_t)nq)) return false;
+        hipStream_t st = S(stream_);
+        const size_t b_q = 4u * (size_t)nq;
+        const auto upload = [&](char *h) { // masks and order tables go up from pinned memory, behind the words tag_counts sent: [query_tags | order]
+            memcpy(h, query_tags, b_q);
+            memcpy(h + b_q, lo.order.data(), b_q);
+            HIP_OK(hipMemcpyAsync(s_tquery_, h, 2 * b_q, hipMemcpyHostToDevice, st));
+            return true;
+        };
+        const auto listed = [&](long long off, int) { return lo.jobs_of[(size_t)(off / p.chunk)]; };
+        const auto filter = [&](long long off) {
+            return std::make_tuple(s_ttags_.get(), n_lab, reinterpret_cast<const unsigned *>(s_tquery_.get()) + off, match, s_tquery_.get() + (size_t)nq + off);
+        };
+        if (!run_predicate_search(c, p, 2 * b_q, upload, listed, filter)) return false;
     }
-    // the rows no job writes: padding, flag 0 (after the launches' rows have been copied over the caller's arrays)
-    const auto pad_skipped = [&] {
-        for (int i = 0; i < nq; ++i)
-            if (members(i) == 0) {
-                pad_results(out_ids + (size_t)i * k_out, out_d + (size_t)i * k_out, (size_t)k_out);
-                out_flag[i] = 0;
-            }
-    };
-    if (launched == 0) { // (nothing to traverse: no launch, as a set that allows nothing)
-        pad_skipped();
-        kt_info_[0] += 1;
-        kt_info_[1] += (uint64_t)tc.masks.size();
-        kt_info_[3] += (uint64_t)nq;
-        return true;
-    }
-    const int cand_cap = cand_lds_cap(k, pitch_, false, nbcap());
-    const size_t lds = search_lds_bytes(k, cand_cap, pitch_, false, nbcap());
-    if (lds > 64 * 1024) { set_dev_error("search_tagged: beam width / dimension exceed the LDS budget"); return false; }
-    hipStream_t st = S(stream_);
-    TraversalLaunch tl;
-    if (!plan_traversal(false, k, true, lds, &tl, true)) return false;
-    const auto kernel = persistent_kernel(metric_, tl.vis.tab != nullptr, [](auto m, auto h) { return &graph_search_tagged_kernel<m, h>; });
-    place_persistent(kernel, tl, (int)chunk);
-    if (tl.slots < 1) { set_dev_error("search_tagged: the kernel does not fit the device"); return false; }
-    const int fspill = filter_spill_cap();
-    if (!ensure_search_scratch(chunk, max_slots(), k_out, tl.vis.bytes_per_job)) return false;
-    if (!s_fspill_.grow((size_t)tl.slots * (size_t)std::max(fspill, 1) + 8)) return false; // +8: get2 may read one entry past a heap
-    if (!s_tquery_.grow(2 * (size_t)nq)) return false;
-    const size_t b_q = 4u * (size_t)nq;
-    const auto upload = [&](char *h) { // masks and order tables go up from pinned memory, behind the words tag_counts sent: [query_tags | order]
-        memcpy(h, query_tags, b_q);
-        memcpy(h + b_q, order.data(), b_q);
-        HIP_OK(hipMemcpyAsync(s_tquery_, h, 2 * b_q, hipMemcpyHostToDevice, st));
-        return true;
-    };
-    const auto launch = [&](long long off, int, int *d_ids, float *d_d) {
-        const int n = jobs_of[(size_t)(off / chunk)]; // (0: one wave finds the counter past the jobs and leaves)
-        hipLaunchKernelGGL(kernel, dim3(std::max(1, std::min(n, tl.slots))), dim3(tl.block), tl.lds_total, st, d_rows_, d_row_sn_, d_queries_ + (size_t)off * pitch_,
-                           d_q_sn_ ? d_q_sn_ + off : nullptr, pitch_, g_adj0_, g_stride0_, g_upper_, g_pool_, g_strideU_, entry, entry_layer, search_layer, k,
-                           cand_cap, reinterpret_cast<ND *>(s_fspill_.get()), fspill, s_visited_, tl.vis.words, tl.vis.tab, tl.vis.tab_cap,
-                           s_ttags_.get(), n_lab, reinterpret_cast<const unsigned *>(s_tquery_.get()) + off, match, s_tquery_.get() + (size_t)nq + off, k_out, d_ids, d_d,
-                           s_flag_, s_evals_, nbcap(), n, s_jobctr_);
-    };
-    if (!run_resident((size_t)k_out, chunk, 2 * b_q, tl.vis.tab != nullptr, nq, out_ids, out_d, out_flag, upload, launch)) return false;
-    pad_skipped();
+    pad_skipped(c, members); // (every row when nothing was launched: no flag is set then)
     kt_info_[0] += 1;
     kt_info_[1] += (uint64_t)tc.masks.size();
-    kt_info_[2] += (uint64_t)launched;
-    kt_info_[3] += (uint64_t)(nq - launched);
-    for (int i = 0; i < nq; ++i) {
-        stats_.search_overflows += (uint64_t)(out_flag[i] == 1);
-        kt_info_[4] += (uint64_t)(out_flag[i] == 1);
-    }
+    kt_info_[2] += (uint64_t)lo.launched;
+    kt_info_[3] += (uint64_t)(nq - lo.launched);
+    kt_info_[4] += count_search_overflows(c);
     return true;
 }
 
@@ -2699,6 +2703,31 @@ bool Device::abi_begin(const char *who, const float *queries, int nq, int entry_
     return set_queries(queries, nq);
 }
 
+// The committed host graph's list of `id` on `layer`: what the range replays walk.
+auto Device::host_list_of(int layer) const
+{
+    return [this, layer](int id) {
+        return layer == 0 ? hg_->adj0.data() + (size_t)id * (size_t)hg_->stride0
+                          : hg_->pool.data() + hg_->upper[(size_t)id] + (size_t)(layer - 1) * (size_t)hg_->strideU;
+    };
+}
+// A closure of m entries finished on the host -- partitioned by `allow`, sorted, replayed where the allowed results tie
+// (finish_filtered_range) -- and appended to abi_range_, *count its length.  An empty heap there fails the whole call, as the
+// reference's exception does: no list, out_counts[0, nq) zero, kHeapEmptyError.
+bool Device::finish_closure(int layer, int entry, float range, SearchHit *b, int m, const AllowPred &allow, int nq, int *out_counts, int *count)
+{
+    std::vector<NodeDist> ordered;
+    if (finish_filtered_range(host_list_of(layer), 2 * hg_->M, entry, range, b, m, allow, ordered) == kRangeHeapEmpty) {
+        abi_range_.clear();
+        for (int j = 0; j < nq; ++j) out_counts[j] = 0;
+        set_dev_error(kHeapEmptyError);
+        return false;
+    }
+    *count = (int)ordered.size();
+    for (const NodeDist &nd : ordered) abi_range_.push_back(SearchHit{nd.id, nd.dist});
+    return true;
+}
+
 // allow_bits == nullptr: no filter (range_search)
 bool Device::range_search_filtered(const float *queries, int nq, int entry_point, float range, const uint32_t *allow_bits, long long nbits,
                                    int *out_counts, int *out_flags, int layer)
@@ -2713,26 +2742,13 @@ bool Device::range_search_filtered(const float *queries, int nq, int entry_point
     for (int i = 0; i < nq; ++i) jobs[(size_t)i] = SearchJob{i, entry_point, top, layer, -1};
     RangeResults r;
     if (!range_batch(jobs.data(), nq, range, &r, allow_bits, nbits)) return false;
-    const auto list_of = [&](int id) {
-        return layer == 0 ? hg_->adj0.data() + (size_t)id * (size_t)hg_->stride0
-                          : hg_->pool.data() + hg_->upper[(size_t)id] + (size_t)(layer - 1) * (size_t)hg_->strideU;
-    };
     for (int i = 0; i < nq; ++i) {
         out_counts[i] = 0;
         out_flags[i] = r.flag[(size_t)i];
         if (out_flags[i]) continue;
         SearchHit *b = r.found + r.off[(size_t)i], *e = b + r.cnt[(size_t)i];
         if (allow_bits && r.state[(size_t)i] != kRangeFinal) { // a closure: partition, sort, replay where the allowed results tie
-            std::vector<NodeDist> ordered;
-            if (finish_filtered_range(list_of, 2 * hg_->M, r.entry[(size_t)i], range, b, r.cnt[(size_t)i], AllowBits{allow_bits, nbits}, ordered) ==
-                kRangeHeapEmpty) {
-                abi_range_.clear();
-                for (int j = 0; j < nq; ++j) out_counts[j] = 0;
-                set_dev_error(kHeapEmptyError);
-                return false;
-            }
-            out_counts[i] = (int)ordered.size();
-            for (const NodeDist &nd : ordered) abi_range_.push_back(SearchHit{nd.id, nd.dist});
+            if (!finish_closure(layer, r.entry[(size_t)i], range, b, r.cnt[(size_t)i], AllowBits{allow_bits, nbits}, nq, out_counts, &out_counts[i])) return false;
             continue;
         }
         bool tie = r.state[(size_t)i] == kRangeTied; // (the device replays what it can: this is what it handed back)
@@ -2743,7 +2759,7 @@ bool Device::range_search_filtered(const float *queries, int nq, int entry_point
         out_counts[i] = r.cnt[(size_t)i];
         if (tie) { // OrderBy keeps the heap array's order there (HNSWIndex.cs:155): replay the heaps on the committed graph
             std::vector<NodeDist> ordered;
-            replay_range_heaps(list_of, 2 * hg_->M, r.entry[(size_t)i], range, b, r.cnt[(size_t)i], ordered);
+            replay_range_heaps(host_list_of(layer), 2 * hg_->M, r.entry[(size_t)i], range, b, r.cnt[(size_t)i], ordered);
             for (const NodeDist &nd : ordered) abi_range_.push_back(SearchHit{nd.id, nd.dist});
             continue;
         }
@@ -2788,10 +2804,6 @@ bool Device::range_search_grouped(const float *queries, int nq, int entry_point,
     grp.skipped = nq - nj;
     RangeResults r;
     if (!range_batch(jobs.data(), nj, range, &r, nullptr, 0, &grp)) return false;
-    const auto list_of = [&](int id) {
-        return layer == 0 ? hg_->adj0.data() + (size_t)id * (size_t)hg_->stride0
-                          : hg_->pool.data() + hg_->upper[(size_t)id] + (size_t)(layer - 1) * (size_t)hg_->strideU;
-    };
     for (int j = 0; j < nj; ++j) { // (in query order: abi_range_ holds the lists as range_results hands them out)
         const int i = qi_of[(size_t)j];
         out_flags[i] = r.flag[(size_t)j];
@@ -2802,16 +2814,9 @@ bool Device::range_search_grouped(const float *queries, int nq, int entry_point,
             abi_range_.insert(abi_range_.end(), b, e);
             continue;
         }
-        std::vector<NodeDist> ordered; // a closure: partition, sort, replay where the allowed results tie
-        if (finish_filtered_range(list_of, 2 * hg_->M, r.entry[(size_t)j], range, b, r.cnt[(size_t)j], AllowPred{row_group, n_lab, group_of[(size_t)j]}, ordered) ==
-            kRangeHeapEmpty) {
-            abi_range_.clear();
-            for (int q = 0; q < nq; ++q) out_counts[q] = 0;
-            set_dev_error(kHeapEmptyError);
+        // a closure: partition, sort, replay where the allowed results tie
+        if (!finish_closure(layer, r.entry[(size_t)j], range, b, r.cnt[(size_t)j], AllowPred{row_group, n_lab, group_of[(size_t)j]}, nq, out_counts, &out_counts[i]))
             return false;
-        }
-        out_counts[i] = (int)ordered.size();
-        for (const NodeDist &nd : ordered) abi_range_.push_back(SearchHit{nd.id, nd.dist});
     }
     return true;
 }

@@ -1,4 +1,4 @@
-// dk_search_kernels.h -- device code, part of device_kernels.h: KnnQuery / MultiLayerKnnQuery / RangeQuery: search_job, graph_search_kernel (persistent, shadows, gated upload), graph_search_filtered_kernel (allow-sets), graph_search_grouped_kernel (a group per query), graph_search_tagged_kernel (a tag mask per query), graph_multilayer_kernel (layer chains), graph_range_kernel.
+// dk_search_kernels.h -- device code, part of device_kernels.h: KnnQuery / MultiLayerKnnQuery / RangeQuery: search_job, graph_search_kernel (persistent, shadows, gated upload), predicate_search with its kernels graph_search_filtered_kernel (allow-sets), graph_search_grouped_kernel (a group per query), graph_search_tagged_kernel (a tag mask per query), graph_multilayer_kernel (layer chains), graph_range_kernel.
 #pragma once
 #include "dk_sorted_top.h"
 #include "dk_pool_top.h"
@@ -374,14 +374,56 @@ graph_search_kernel(const float *__restrict__ rows, const double *__restrict__ r
 #define HNSW_DECLARE_SEARCH(M, NS, H, LT) HNSW_SEARCH_SIGNATURE(extern, M, NS, H, LT)
 #define HNSW_DEFINE_SEARCH(M, NS, H, LT) HNSW_SEARCH_SIGNATURE(, M, NS, H, LT)
 
-// KnnQuery with an allow-set (HNSWIndex.KnnQuery(query, k, filterFnc, layer), HNSWIndex.cs:107-124): FindEntryPointQuery down to
-// search_layer (exclusive), unfiltered, then SearchLayerQuery with the filter (GraphNavigator.cs:194-256) in the exact two-heap traversal -- the sorted-list
-// forms cannot carry it: a disallowed node is a candidate that is never a result, and the result list no longer holds the live
-// candidates -- and the stable Take(k_out).  Persistent like graph_range_kernel: one wave per job, jobs from a
-// counter; job i is resident query i from (entry, entry_layer).  Each wave owns one visited set and one spill area of spill_cap
-// entries (filtered traversals keep far more candidates: the result heap fills only after ~k / selectivity evaluations) and
-// leaves the set clean after every job.  out_flag: 0 done, 1 handed back (candidate heap full, NaN / -0 distance, visited table
-// crowded).
+// KnnQuery with a predicate over ids (HNSWIndex.KnnQuery(query, k, filterFnc, layer), HNSWIndex.cs:107-124): the one body of
+// graph_search_filtered_kernel, graph_search_grouped_kernel and graph_search_tagged_kernel.  FindEntryPointQuery
+// down to search_layer (exclusive), unfiltered, then SearchLayerQuery with the filter (GraphNavigator.cs:194-256) in the exact
+// two-heap traversal -- the sorted-list forms cannot carry it: a disallowed node is a candidate that is never a result, and the
+// result list no longer holds the live candidates -- and the stable Take(k_out).  Persistent like graph_range_kernel: one wave per
+// job, jobs from a counter; job j is resident query qi from (entry, entry_layer): qi = j, or with ORDERED qi = order[j] (the host
+// lists the queries to answer, order entries in 0 .. the launch's queries - 1).  filter_of(qi) builds the query's filter, what
+// traverse asks of a FILTER (dk_search_common.h); its per-query state is wave-uniform.  Results and flag go to row qi.  Each wave
+// owns one visited set and one spill area of spill_cap entries (filtered traversals keep far more candidates: the result heap
+// fills only after ~k / selectivity evaluations) and leaves the set clean after every job.  out_flag: 0 done, 1 handed back
+// (candidate heap full, NaN / -0 distance, visited table crowded).
+template <int METRIC, bool HASHED, bool ORDERED, class FilterOf>
+__device__ __forceinline__ void
+predicate_search(const float *__restrict__ rows, const double *__restrict__ row_sn, const float *__restrict__ queries,
+                 const double *__restrict__ q_sn, int dim, const int *__restrict__ adj0, int stride0, const int64_t *__restrict__ upper,
+                 const int *__restrict__ pool, int strideU, int entry, int entry_layer, int search_layer, int k, int cand_cap,
+                 ND *__restrict__ spill, int spill_cap, unsigned *__restrict__ visited, long long vis_words, int *__restrict__ vis_tab,
+                 int vis_tab_cap, const int *__restrict__ order, int k_out, int *__restrict__ out_ids, float *__restrict__ out_d,
+                 int *__restrict__ out_flag, unsigned long long *__restrict__ eval_counter, int nbcap, int njobs, int *__restrict__ job_counter,
+                 FilterOf filter_of)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int lane = threadIdx.x & 63;
+    VisitedSet<HASHED> V = wave_visited<HASHED>(visited, vis_words, vis_tab, vis_tab_cap);
+    ND *my_spill = spill + (size_t)blockIdx.x * (size_t)spill_cap;
+    const SearchLds L = carve_lds(smem, k, cand_cap, dim, nbcap);
+    const GraphView G{adj0, stride0, upper, pool, strideU};
+    for (;;) {
+        int job;
+        if (!claim_job(job_counter, njobs, lane, job)) break;
+        int qi = job;
+        if constexpr (ORDERED) qi = __builtin_amdgcn_readfirstlane(order[job]);
+        const auto filter = filter_of(qi);
+        const SearchJob jb{qi, entry, entry_layer, search_layer, -1, 0};
+        const double sb = stage_query<METRIC>(queries, q_sn, qi, dim, L, lane);
+        unsigned long long evals = 0;
+        int top_n = 0;
+        ReadLog RL{nullptr, 0, 0};
+        const bool ok = traverse<METRIC, HASHED, true, decltype(filter)>(rows, row_sn, dim, sb, G, jb, k, cand_cap, my_spill, spill_cap, V, L, lane, top_n,
+                                                                         evals, RL, nullptr, nullptr, true, filter);
+        take_stable(L, lane, top_n, k_out, out_ids, out_d, qi);
+        if (lane == 0) {
+            out_flag[qi] = ok ? 0 : 1;
+            atomicAdd(eval_counter, evals);
+        }
+        V.clear(lane);
+    }
+}
+
+// An allow-set (AllowSet): a bitset of allow_n bits over ids, the same for every query; job i is resident query i.
 template <int METRIC, bool HASHED>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(HNSW_WAVES(3))))
 graph_search_filtered_kernel(const float *__restrict__ rows, const double *__restrict__ row_sn, const float *__restrict__ queries,
@@ -392,30 +434,9 @@ graph_search_filtered_kernel(const float *__restrict__ rows, const double *__res
                              int *__restrict__ out_ids, float *__restrict__ out_d, int *__restrict__ out_flag,
                              unsigned long long *__restrict__ eval_counter, int nbcap, int njobs, int *__restrict__ job_counter)
 {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int lane = threadIdx.x & 63;
-    VisitedSet<HASHED> V = wave_visited<HASHED>(visited, vis_words, vis_tab, vis_tab_cap);
-    ND *my_spill = spill + (size_t)blockIdx.x * (size_t)spill_cap;
-    const SearchLds L = carve_lds(smem, k, cand_cap, dim, nbcap);
-    const GraphView G{adj0, stride0, upper, pool, strideU};
-    const AllowSet allow{allow_bits, allow_n};
-    for (;;) {
-        int job;
-        if (!claim_job(job_counter, njobs, lane, job)) break;
-        const SearchJob jb{job, entry, entry_layer, search_layer, -1, 0};
-        const double sb = stage_query<METRIC>(queries, q_sn, job, dim, L, lane);
-        unsigned long long evals = 0;
-        int top_n = 0;
-        ReadLog RL{nullptr, 0, 0};
-        const bool ok = traverse<METRIC, HASHED, true>(rows, row_sn, dim, sb, G, jb, k, cand_cap, my_spill, spill_cap, V, L, lane, top_n, evals, RL,
-                                                       nullptr, nullptr, true, allow);
-        take_stable(L, lane, top_n, k_out, out_ids, out_d, job);
-        if (lane == 0) {
-            out_flag[job] = ok ? 0 : 1;
-            atomicAdd(eval_counter, evals);
-        }
-        V.clear(lane);
-    }
+    predicate_search<METRIC, HASHED, false>(rows, row_sn, queries, q_sn, dim, adj0, stride0, upper, pool, strideU, entry, entry_layer, search_layer, k,
+                                            cand_cap, spill, spill_cap, visited, vis_words, vis_tab, vis_tab_cap, nullptr, k_out, out_ids, out_d, out_flag,
+                                            eval_counter, nbcap, njobs, job_counter, [=](int) { return AllowSet{allow_bits, allow_n}; });
 }
 #define HNSW_FILTERED_SIGNATURE(PREFIX, M, H)                                                                                       \
     PREFIX template __global__ void graph_search_filtered_kernel<M, H>(                                                             \
@@ -427,13 +448,9 @@ graph_search_filtered_kernel(const float *__restrict__ rows, const double *__res
 #define HNSW_DECLARE_FILTERED(M, H) HNSW_FILTERED_SIGNATURE(extern, M, H)
 #define HNSW_DEFINE_FILTERED(M, H) HNSW_FILTERED_SIGNATURE(, M, H)
 
-// KnnQuery with a group filter per query (knn_query_grouped): graph_search_filtered_kernel with the predicate
-// "row_group[id] == this query's group" (GroupSet) in the allow-set's place -- the same descent, traversal, stable Take(k_out), LDS
-// carve, spill areas, visited sets (cleared after every job) and out_flag values.  Job j of the launch is resident query
-// qi = order[j] (the host lists only the queries whose group holds a graph id, longest traversal first); its group is
-// query_group[qi], wave-uniform and so kept in a scalar register; its results and its flag go to row qi.  row_group has n_labels
-// entries (ids beyond have no group); query_group values lie in 0 .. n_groups - 1 and order entries in 0 .. the launch's queries - 1
-// (the host checks both before the launch).
+// A group filter per query (knn_query_grouped; GroupSet): "row_group[id] == query_group[qi]".  row_group has
+// n_labels entries (ids beyond have no group).  The host lists in `order` only the queries whose group holds a graph id, longest
+// traversal first, and checks before the launch that query_group values lie in 0 .. n_groups - 1.
 template <int METRIC, bool HASHED>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(HNSW_WAVES(3))))
 graph_search_grouped_kernel(const float *__restrict__ rows, const double *__restrict__ row_sn, const float *__restrict__ queries,
@@ -445,31 +462,11 @@ graph_search_grouped_kernel(const float *__restrict__ rows, const double *__rest
                             float *__restrict__ out_d, int *__restrict__ out_flag, unsigned long long *__restrict__ eval_counter, int nbcap,
                             int njobs, int *__restrict__ job_counter)
 {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int lane = threadIdx.x & 63;
-    VisitedSet<HASHED> V = wave_visited<HASHED>(visited, vis_words, vis_tab, vis_tab_cap);
-    ND *my_spill = spill + (size_t)blockIdx.x * (size_t)spill_cap;
-    const SearchLds L = carve_lds(smem, k, cand_cap, dim, nbcap);
-    const GraphView G{adj0, stride0, upper, pool, strideU};
-    for (;;) {
-        int job;
-        if (!claim_job(job_counter, njobs, lane, job)) break;
-        const int qi = __builtin_amdgcn_readfirstlane(order[job]);
-        const GroupSet group{row_group, n_labels, __builtin_amdgcn_readfirstlane(query_group[qi])};
-        const SearchJob jb{qi, entry, entry_layer, search_layer, -1, 0};
-        const double sb = stage_query<METRIC>(queries, q_sn, qi, dim, L, lane);
-        unsigned long long evals = 0;
-        int top_n = 0;
-        ReadLog RL{nullptr, 0, 0};
-        const bool ok = traverse<METRIC, HASHED, true, GroupSet>(rows, row_sn, dim, sb, G, jb, k, cand_cap, my_spill, spill_cap, V, L, lane, top_n, evals, RL,
-                                                                 nullptr, nullptr, true, group);
-        take_stable(L, lane, top_n, k_out, out_ids, out_d, qi);
-        if (lane == 0) {
-            out_flag[qi] = ok ? 0 : 1;
-            atomicAdd(eval_counter, evals);
-        }
-        V.clear(lane);
-    }
+    predicate_search<METRIC, HASHED, true>(rows, row_sn, queries, q_sn, dim, adj0, stride0, upper, pool, strideU, entry, entry_layer, search_layer, k,
+                                           cand_cap, spill, spill_cap, visited, vis_words, vis_tab, vis_tab_cap, order, k_out, out_ids, out_d, out_flag,
+                                           eval_counter, nbcap, njobs, job_counter, [=](int qi) {
+                                               return GroupSet{row_group, n_labels, __builtin_amdgcn_readfirstlane(query_group[qi])};
+                                           });
 }
 #define HNSW_GROUPED_SIGNATURE(PREFIX, M, H)                                                                                        \
     PREFIX template __global__ void graph_search_grouped_kernel<M, H>(                                                              \
@@ -482,12 +479,9 @@ graph_search_grouped_kernel(const float *__restrict__ rows, const double *__rest
 #define HNSW_DECLARE_GROUPED(M, H) HNSW_GROUPED_SIGNATURE(extern, M, H)
 #define HNSW_DEFINE_GROUPED(M, H) HNSW_GROUPED_SIGNATURE(, M, H)
 
-// KnnQuery with a tag mask per query (knn_query_tagged): graph_search_grouped_kernel with the predicate of TagSet --
-// "row_tags[id] shares a tag with the query's mask" (all == 0) or "carries every tag of it" (all != 0) -- where the group compare
-// was.  A kernel of its own, so that the grouped kernel's code stays what it was.  Job j is resident query qi = order[j]; its mask
-// is query_tags[qi], wave-uniform and kept in a scalar register, never 0 (the host lists only queries whose mask has a candidate
-// among the graph ids, fewest candidates first).  row_tags has n_tags entries: ids beyond carry no tag.  Descent, traversal, stable
-// Take(k_out), LDS carve, spill areas, visited sets, out_flag values and eval_counter are the grouped kernel's.
+// A tag mask per query (knn_query_tagged; TagSet): "row_tags[id] shares a tag with query_tags[qi]" (match_all == 0)
+// or "carries every tag of it" (match_all != 0).  row_tags has n_tags entries: ids beyond carry no tag.  The host lists in `order`
+// only the queries whose mask has a candidate among the graph ids, fewest candidates first, so the mask is never 0.
 template <int METRIC, bool HASHED>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(HNSW_WAVES(3))))
 graph_search_tagged_kernel(const float *__restrict__ rows, const double *__restrict__ row_sn, const float *__restrict__ queries,
@@ -499,31 +493,11 @@ graph_search_tagged_kernel(const float *__restrict__ rows, const double *__restr
                            float *__restrict__ out_d, int *__restrict__ out_flag, unsigned long long *__restrict__ eval_counter, int nbcap,
                            int njobs, int *__restrict__ job_counter)
 {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int lane = threadIdx.x & 63;
-    VisitedSet<HASHED> V = wave_visited<HASHED>(visited, vis_words, vis_tab, vis_tab_cap);
-    ND *my_spill = spill + (size_t)blockIdx.x * (size_t)spill_cap;
-    const SearchLds L = carve_lds(smem, k, cand_cap, dim, nbcap);
-    const GraphView G{adj0, stride0, upper, pool, strideU};
-    for (;;) {
-        int job;
-        if (!claim_job(job_counter, njobs, lane, job)) break;
-        const int qi = __builtin_amdgcn_readfirstlane(order[job]);
-        const TagSet tagged{row_tags, n_tags, (unsigned)__builtin_amdgcn_readfirstlane((int)query_tags[qi]), match_all};
-        const SearchJob jb{qi, entry, entry_layer, search_layer, -1, 0};
-        const double sb = stage_query<METRIC>(queries, q_sn, qi, dim, L, lane);
-        unsigned long long evals = 0;
-        int top_n = 0;
-        ReadLog RL{nullptr, 0, 0};
-        const bool ok = traverse<METRIC, HASHED, true, TagSet>(rows, row_sn, dim, sb, G, jb, k, cand_cap, my_spill, spill_cap, V, L, lane, top_n, evals, RL,
-                                                               nullptr, nullptr, true, tagged);
-        take_stable(L, lane, top_n, k_out, out_ids, out_d, qi);
-        if (lane == 0) {
-            out_flag[qi] = ok ? 0 : 1;
-            atomicAdd(eval_counter, evals);
-        }
-        V.clear(lane);
-    }
+    predicate_search<METRIC, HASHED, true>(rows, row_sn, queries, q_sn, dim, adj0, stride0, upper, pool, strideU, entry, entry_layer, search_layer, k,
+                                           cand_cap, spill, spill_cap, visited, vis_words, vis_tab, vis_tab_cap, order, k_out, out_ids, out_d, out_flag,
+                                           eval_counter, nbcap, njobs, job_counter, [=](int qi) {
+                                               return TagSet{row_tags, n_tags, (unsigned)__builtin_amdgcn_readfirstlane((int)query_tags[qi]), match_all};
+                                           });
 }
 #define HNSW_TAGGED_SIGNATURE(PREFIX, M, H)                                                                                         \
     PREFIX template __global__ void graph_search_tagged_kernel<M, H>(                                                               \

@@ -1686,22 +1686,82 @@ static bool group_args_ok(const char *who, const int *query_group, int count, in
     return why.empty();
 }
 
+// ---- KnnQuery with a predicate per query (knn_query_grouped, knn_query_tagged): what the two calls share.  The queries fall into
+// classes -- a class per group, a class per distinct mask -- and a class's queries have one allow-set.
+// The prologue.  args_ok(): the call's own argument rules, filing err.  1: go on; 0: answered (no query, or HNSWIndex.cs:109: empty
+// result lists, padded by the export); -1: failed.
+template <class ArgsOk>
+int HnswIndex::predicate_query_begin(const char *who, int count, int k, int layer, int *out_ids, float *out_dists, std::string &err, ArgsOk args_ok)
+{
+    if (count <= 0) return 0;
+    if (failed(err) || !args_ok()) return -1;
+    const bool empty = k < 1 || graph_.entry < 0 || graph_.count <= 0;
+    if (!empty && !layer_ok(layer, err)) { err = "System.IndexOutOfRangeException: " + std::string(who) + ": " + err; return -1; }
+    if (empty) pad_results(out_ids, out_dists, (size_t)count * (size_t)std::max(k, 0));
+    return empty ? 0 : 1;
+}
+
+// The lock-step way for the queries in `which` (nullptr: all n of them): query qi is of class class_of(qi) < n_classes, and
+// matches(id, c) says whether id < n_lab passes class c's predicate.  One bitset per class concerned -- built only when a query of
+// the class comes here -- and one filtered call per class; the queries of a class without an id are padded.
+template <class ClassOf, class Matches>
+int HnswIndex::lockstep_by_class(const int *which, int n, int k, int layer, long long n_lab, size_t n_classes, ClassOf class_of, Matches matches,
+                                 int *out_ids, float *out_dists, std::string &err)
+{
+    std::vector<std::vector<int>> of(n_classes);
+    for (int i = 0; i < n; ++i) {
+        const int qi = which ? which[i] : i;
+        of[(size_t)class_of(qi)].push_back(qi);
+    }
+    std::vector<uint32_t> bits((size_t)((n_lab + 31) / 32) + 1);
+    for (size_t c = 0; c < n_classes; ++c) {
+        if (of[c].empty()) continue;
+        std::fill(bits.begin(), bits.end(), 0u);
+        bool has = false;
+        for (long long id = 0; id < n_lab; ++id)
+            if (matches(id, c)) { bits[(size_t)(id >> 5)] |= 1u << (id & 31); has = true; }
+        if (!has) {
+            for (const int qi : of[c]) pad_results(out_ids + (size_t)qi * k, out_dists + (size_t)qi * k, (size_t)k);
+            continue;
+        }
+        if (knn_query_lockstep(of[c].data(), (int)of[c].size(), k, out_ids, out_dists, err, AllowBits{bits.data(), n_lab}, layer) < 0) return -1;
+    }
+    return 0;
+}
+
+// Device or host, one context or several: answer_resident, with lockstep_by_class as its host way.  search(ctx, cnt, ep, top, ef, lo,
+// ids, dists, flag): the call's launch on one context for its cnt resident queries, rows lo .. of the caller's arrays.
+template <class Search, class ClassOf, class Matches>
+int HnswIndex::answer_by_class(int count, int k, int layer, long long n_lab, size_t n_classes, ClassOf class_of, Matches matches, Search search,
+                               const char *fallback, int *out_ids, float *out_dists, std::string &err)
+{
+    const int ef = std::max(p_.min_nn, k); // HNSWIndex.cs:115
+    const int ep = graph_.entry, top = graph_.top_layer();
+    return answer_resident(count, ef,
+        [&](Device *ctx, int cnt, long long lo, int *flag) { return search(ctx, cnt, ep, top, ef, lo, out_ids + (size_t)lo * k, out_dists + (size_t)lo * k, flag); },
+        [&](const int *which, int n) { return lockstep_by_class(which, n, k, layer, n_lab, n_classes, class_of, matches, out_ids, out_dists, err); },
+        fallback, err);
+}
+
+// A per-context counter array of n <= 8 entries, fetched by get(device, one), summed over the contexts.
+template <class Get>
+void HnswIndex::sum_over_contexts(uint64_t *out, int n, Get get) const
+{
+    std::fill(out, out + n, (uint64_t)0);
+    uint64_t one[8];
+    const auto add = [&](const Device &d) { get(d, one); for (int i = 0; i < n; ++i) out[i] += one[i]; };
+    if (dev_) add(*dev_);
+    for (const auto &r : replicas_) add(*r);
+}
+
 // KnnQuery with a group filter per query: knn_query_general's filtered call for every group at once.  The labels go
-// to the device as they are; once slots are vacant a copy does, with the vacant slots in no group (live_labels).  Device or host,
-// one context or several: answer_resident, with the per-group lock-step calls below as its host way.
+// to the device as they are; once slots are vacant a copy does, with the vacant slots in no group (live_labels).
 int HnswIndex::knn_query_grouped(const float *queries, int count, int dim, int k, int layer, const int *row_group, long long n_row_group, const int *query_group,
                                  int n_groups, int *out_ids, float *out_dists, std::string &err)
 {
-    if (count <= 0) return 0;
-    if (failed(err)) return -1;
     const char *who = "hnsw_mi355x_knn_query_grouped";
-    if (!group_args_ok(who, query_group, count, n_groups, err)) return -1;
-    const bool empty = k < 1 || graph_.entry < 0 || graph_.count <= 0;
-    if (!empty && !layer_ok(layer, err)) { err = "System.IndexOutOfRangeException: " + std::string(who) + ": " + err; return -1; }
-    if (empty) { // HNSWIndex.cs:109: empty result lists, padded by the export
-        pad_results(out_ids, out_dists, (size_t)count * (size_t)std::max(k, 0));
-        return 0;
-    }
+    const int go = predicate_query_begin(who, count, k, layer, out_ids, out_dists, err, [&] { return group_args_ok(who, query_group, count, n_groups, err); });
+    if (go <= 0) return go;
     std::vector<int> live;
     (void)live_labels(row_group, n_row_group, live);
     const long long n_lab = std::min<long long>(n_row_group, graph_.length); // only the labels of graph ids count
@@ -1715,41 +1775,17 @@ int HnswIndex::knn_query_grouped(const float *queries, int count, int dim, int k
         return 0;
     }
     if (set_resident_queries(queries, count, dim, err) < 0) return -1;
-    // The lock-step way for the queries in `which` (nullptr: all of them): one bitset per group concerned, one filtered call per group;
-    // queries of a group without ids are padded.
-    const auto lockstep = [&](const int *which, int n) -> int {
-        std::vector<std::vector<int>> of((size_t)n_groups);
-        for (int i = 0; i < n; ++i) {
-            const int qi = which ? which[i] : i;
-            const int g = query_group[qi];
-            if (has_id[(size_t)g]) of[(size_t)g].push_back(qi);
-            else pad_results(out_ids + (size_t)qi * k, out_dists + (size_t)qi * k, (size_t)k);
-        }
-        std::vector<uint32_t> bits((size_t)((n_lab + 31) / 32) + 1);
-        for (int g = 0; g < n_groups; ++g) {
-            if (of[(size_t)g].empty()) continue;
-            std::fill(bits.begin(), bits.end(), 0u);
-            for (long long id = 0; id < n_lab; ++id)
-                if (row_group[id] == g) bits[(size_t)(id >> 5)] |= 1u << (id & 31);
-            if (knn_query_lockstep(of[(size_t)g].data(), (int)of[(size_t)g].size(), k, out_ids, out_dists, err, AllowBits{bits.data(), n_lab}, layer) < 0) return -1;
-        }
-        return 0;
-    };
-    const int ef = std::max(p_.min_nn, k); // HNSWIndex.cs:115
-    const int ep = graph_.entry, top = graph_.top_layer();
-    return answer_resident(count, ef,
-        [&](Device *ctx, int cnt, long long lo, int *flag) { // the labels are uploaded to every context; lo .. of query_group too
-            return ctx->search_grouped(cnt, ep, top, ef, k, row_group, n_lab, query_group + lo, n_groups, out_ids + (size_t)lo * k, out_dists + (size_t)lo * k, flag, layer);
+    return answer_by_class(count, k, layer, n_lab, (size_t)n_groups, [&](int qi) { return query_group[qi]; },
+        [&](long long id, size_t g) { return row_group[id] == (int)g; },
+        [&](Device *ctx, int cnt, int ep, int top, int ef, long long lo, int *ids, float *dists, int *flag) { // the labels are uploaded to every context; lo .. of query_group too
+            return ctx->search_grouped(cnt, ep, top, ef, k, row_group, n_lab, query_group + lo, n_groups, ids, dists, flag, layer);
         },
-        lockstep, "search_grouped failed", err);
+        "search_grouped failed", out_ids, out_dists, err);
 }
 
 void HnswIndex::knn_grouped_info(uint64_t out[4]) const
 {
-    out[0] = out[1] = out[2] = out[3] = 0;
-    uint64_t one[4];
-    if (dev_) { dev_->knn_grouped_info(one); for (int i = 0; i < 4; ++i) out[i] += one[i]; }
-    for (const auto &r : replicas_) { r->knn_grouped_info(one); for (int i = 0; i < 4; ++i) out[i] += one[i]; }
+    sum_over_contexts(out, 4, [](const Device &d, uint64_t *one) { d.knn_grouped_info(one); });
 }
 
 // The tagged calls' argument rules (tag_args_error, device_backend.h) as the ABI reports a breach: `who` is the ABI call.
@@ -1776,24 +1812,16 @@ bool HnswIndex::live_tags(const uint32_t *&row_tags, long long &n_row_tags, std:
     return true;
 }
 
-// KnnQuery with a tag mask per query: knn_query_grouped with the predicate "the id's tag word matches the query's
+// KnnQuery with a tag mask per query: a class per distinct mask, the predicate "the id's tag word matches the
 // mask".  The words go to the device as they are; once slots are vacant a copy does, with 0 in the vacant slots (live_tags).  Which
-// masks have a candidate the device finds out (Device::search_tagged); the host way below builds a mask's bitset only when a query
-// of that mask comes to it.
+// masks have a candidate the device finds out (Device::search_tagged).
 int HnswIndex::knn_query_tagged(const float *queries, int count, int dim, int k, int layer, const uint32_t *row_tags, long long n_row_tags,
                                 const uint32_t *query_tags, int match, int *out_ids, float *out_dists, std::string &err)
 {
-    if (count <= 0) return 0;
-    if (failed(err)) return -1;
     const char *who = "hnsw_mi355x_knn_query_tagged";
     TagCall tc;
-    if (!tag_args_ok(who, query_tags, count, match, &tc, err)) return -1;
-    const bool empty = k < 1 || graph_.entry < 0 || graph_.count <= 0;
-    if (!empty && !layer_ok(layer, err)) { err = "System.IndexOutOfRangeException: " + std::string(who) + ": " + err; return -1; }
-    if (empty) { // HNSWIndex.cs:109: empty result lists, padded by the export
-        pad_results(out_ids, out_dists, (size_t)count * (size_t)std::max(k, 0));
-        return 0;
-    }
+    const int go = predicate_query_begin(who, count, k, layer, out_ids, out_dists, err, [&] { return tag_args_ok(who, query_tags, count, match, &tc, err); });
+    if (go <= 0) return go;
     std::vector<uint32_t> live;
     (void)live_tags(row_tags, n_row_tags, live);
     const long long n_lab = std::min<long long>(n_row_tags, graph_.length); // only the words of graph ids count
@@ -1804,44 +1832,17 @@ int HnswIndex::knn_query_tagged(const float *queries, int count, int dim, int k,
         return 0;
     }
     if (set_resident_queries(queries, count, dim, err) < 0) return -1;
-    // The lock-step way for the queries in `which` (nullptr: all of them): one bitset per distinct mask concerned, one filtered call
-    // per mask; queries of a mask without a candidate are padded.
-    const auto lockstep = [&](const int *which, int n) -> int {
-        std::vector<std::vector<int>> of(tc.masks.size());
-        for (int i = 0; i < n; ++i) {
-            const int qi = which ? which[i] : i;
-            of[(size_t)tc.of[(size_t)qi]].push_back(qi);
-        }
-        std::vector<uint32_t> bits((size_t)((n_lab + 31) / 32) + 1);
-        for (size_t d = 0; d < of.size(); ++d) {
-            if (of[d].empty()) continue;
-            std::fill(bits.begin(), bits.end(), 0u);
-            bool has = false;
-            for (long long id = 0; id < n_lab; ++id)
-                if (tag_match_host(row_tags[id], tc.masks[d], match)) { bits[(size_t)(id >> 5)] |= 1u << (id & 31); has = true; }
-            if (!has) {
-                for (const int qi : of[d]) pad_results(out_ids + (size_t)qi * k, out_dists + (size_t)qi * k, (size_t)k);
-                continue;
-            }
-            if (knn_query_lockstep(of[d].data(), (int)of[d].size(), k, out_ids, out_dists, err, AllowBits{bits.data(), n_lab}, layer) < 0) return -1;
-        }
-        return 0;
-    };
-    const int ef = std::max(p_.min_nn, k); // HNSWIndex.cs:115
-    const int ep = graph_.entry, top = graph_.top_layer();
-    return answer_resident(count, ef,
-        [&](Device *ctx, int cnt, long long lo, int *flag) { // the words are uploaded to every context; lo .. of query_tags too
-            return ctx->search_tagged(cnt, ep, top, ef, k, row_tags, n_lab, query_tags + lo, match, out_ids + (size_t)lo * k, out_dists + (size_t)lo * k, flag, layer);
+    return answer_by_class(count, k, layer, n_lab, tc.masks.size(), [&](int qi) { return tc.of[(size_t)qi]; },
+        [&](long long id, size_t d) { return tag_match_host(row_tags[id], tc.masks[d], match); },
+        [&](Device *ctx, int cnt, int ep, int top, int ef, long long lo, int *ids, float *dists, int *flag) { // the words are uploaded to every context; lo .. of query_tags too
+            return ctx->search_tagged(cnt, ep, top, ef, k, row_tags, n_lab, query_tags + lo, match, ids, dists, flag, layer);
         },
-        lockstep, "search_tagged failed", err);
+        "search_tagged failed", out_ids, out_dists, err);
 }
 
 void HnswIndex::knn_tagged_info(uint64_t out[5]) const
 {
-    for (int i = 0; i < 5; ++i) out[i] = 0;
-    uint64_t one[5];
-    if (dev_) { dev_->knn_tagged_info(one); for (int i = 0; i < 5; ++i) out[i] += one[i]; }
-    for (const auto &r : replicas_) { r->knn_tagged_info(one); for (int i = 0; i < 5; ++i) out[i] += one[i]; }
+    sum_over_contexts(out, 5, [](const Device &d, uint64_t *one) { d.knn_tagged_info(one); });
 }
 
 // The candidates of a flat scan as Device::exact_knn / exact_range take them: the row count, and allow_bits / nbits replaced by

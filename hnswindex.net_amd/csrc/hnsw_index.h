@@ -272,6 +272,16 @@ private:
     // every KnnQuery form over the resident set: on the device, one launch per context, or on the host, hand-backs included (hnsw_index.cpp)
     template <class OnDevice, class OnHost>
     int answer_resident(int count, int ef, OnDevice on_device, OnHost on_host, const char *fallback, std::string &err);
+    // what knn_query_grouped / knn_query_tagged share: the prologue, the lock-step way class by class, the answer_resident call, the counter sums
+    template <class ArgsOk>
+    int predicate_query_begin(const char *who, int count, int k, int layer, int *out_ids, float *out_dists, std::string &err, ArgsOk args_ok);
+    template <class ClassOf, class Matches>
+    int lockstep_by_class(const int *which, int n, int k, int layer, long long n_lab, size_t n_classes, ClassOf class_of, Matches matches, int *out_ids,
+                          float *out_dists, std::string &err);
+    template <class Search, class ClassOf, class Matches>
+    int answer_by_class(int count, int k, int layer, long long n_lab, size_t n_classes, ClassOf class_of, Matches matches, Search search, const char *fallback,
+                        int *out_ids, float *out_dists, std::string &err);
+    template <class Get> void sum_over_contexts(uint64_t *out, int n, Get get) const;
     int knn_query_lockstep(const int *which, int count, int k, int *out_ids, float *out_dists, std::string &err, AllowBits allow = AllowBits{},
                            int layer = 0);
     // range_query_grouped's filter: the labels of graph ids, every query's group, and the queries that run (ascending), the others

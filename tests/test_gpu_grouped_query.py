@@ -255,6 +255,8 @@ def test_device_backend_knn_search_grouped(cases):
         assert _same((ids[sel], d[sel]), (f_ids, f_d)), g
     ids, d, flags = dev.knn_search_grouped(c.q, ep, 32, 10, c.rg, np.full(24, EMPTY), N_GROUPS)
     assert (ids == -1).all() and np.isnan(d).all() and (flags == 0).all()
+    # (every query skipped: a call and 24 skipped queries more, no launch)
+    assert dev.knn_grouped_info() == {"calls": 2, "launched": 24 - int((c.qg == EMPTY).sum()), "skipped": int((c.qg == EMPTY).sum()) + 24, "handbacks": 0}
     launches = dev.stats()["search_launches"]
     with pytest.raises(RuntimeError, match="knn_search_grouped: bad argument"):
         dev.knn_search_grouped(c.q, N + 5, 32, 10, c.rg, c.qg, N_GROUPS)           # entry point outside the graph

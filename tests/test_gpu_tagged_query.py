@@ -310,6 +310,8 @@ def test_device_backend_knn_search_tagged(cases):
                 assert _same((ids[sel], d[sel]), (f_ids, f_d)), (match, m)
         ids, d, flags = dev.knn_search_tagged(c.q, ep, 32, 10, c.rt, np.full(24, 16), match)
         assert (ids == -1).all() and np.isnan(d).all() and (flags == 0).all()
+        # (every query skipped: a call, a mask and 24 skipped queries more, no launch)
+        assert dev.knn_tagged_info() == {"calls": 2, "masks": MASKS.size + 1, "launched": 24 - int(none.sum()), "skipped": int(none.sum()) + 24, "handbacks": 0}
     launches = dev.stats()["search_launches"]
     with pytest.raises(RuntimeError, match="knn_search_tagged: bad argument"):
         dev.knn_search_tagged(c.q, N + 5, 32, 10, c.rt, c.qt)           # entry point outside the graph
@@ -331,6 +333,11 @@ def test_device_backend_knn_search_tagged(cases):
         assert message in dev.last_error(), dev.last_error()
     assert (o_ids == 7).all() and (o_d == 7.0).all() and (o_f == 7).all()
     assert dev.stats()["search_launches"] == launches
+    dev.reset_stats()   # n_row_tags == 0: no word of a graph id -- nothing goes up, nothing is counted, every row is padded
+    assert lib.hnswdev_knn_search_tagged(dev._ctx, good["q"], 24, ep, 32, 10, 0, good["rt"], 0, good["qt"], 0, good["ids"], good["d"], good["f"]) == 0
+    assert (o_ids == -1).all() and np.isnan(o_d).all() and (o_f == 0).all()
+    assert dev.knn_tagged_info() == {"calls": 1, "masks": MASKS.size, "launched": 0, "skipped": 24, "handbacks": 0}
+    assert dev.stats()["search_launches"] == 0
 
 
 def test_forced_handbacks_give_the_same_answers(cases, monkeypatch):
