@@ -158,6 +158,19 @@ lib.hnsw_mi355x_range_grouped_info.restype = ct.c_int
 lib.hnsw_mi355x_range_grouped_info.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
 lib.hnsw_mi355x_knn_grouped_info.restype = ct.c_int
 lib.hnsw_mi355x_knn_grouped_info.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
+_RANGE_TAGGED_INFO = ("calls", "masks", "launched", "skipped", "host_finished", "long_finished")   # hnswdev_range_tagged_info's out[0 .. 5]
+_EXACT_RANGE_TAGGED_INFO = ("calls", "masks", "scanned", "skipped", "ids_listed", "batches", "device_sorted", "host_sorted",
+                            "repeated_pieces")   # hnswdev_exact_range_tagged_info's out[0 .. 8]
+lib.hnsw_mi355x_range_query_tagged.restype = ct.c_int
+lib.hnsw_mi355x_range_query_tagged.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_int, ct.c_float, ct.c_int, _U32, ct.c_longlong, _U32, ct.c_int,
+                                               ct.POINTER(ct.c_void_p), ct.POINTER(ct.c_void_p), ct.POINTER(ct.c_int)]
+lib.hnsw_mi355x_exact_range_query_tagged.restype = ct.c_int
+lib.hnsw_mi355x_exact_range_query_tagged.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_int, ct.c_float, _U32, ct.c_longlong, _U32, ct.c_int,
+                                                     ct.POINTER(ct.c_void_p), ct.POINTER(ct.c_void_p), ct.POINTER(ct.c_int)]
+lib.hnsw_mi355x_range_tagged_info.restype = ct.c_int
+lib.hnsw_mi355x_range_tagged_info.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
+lib.hnsw_mi355x_exact_range_tagged_info.restype = ct.c_int
+lib.hnsw_mi355x_exact_range_tagged_info.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
 
 
 class LayerInfo(ct.Structure):
@@ -334,6 +347,14 @@ lib.hnswdev_range_search_grouped.restype = ct.c_int
 lib.hnswdev_range_search_grouped.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_int, ct.c_float, ct.c_int, _I, ct.c_longlong, _I, ct.c_int, _I, _I]
 lib.hnswdev_range_grouped_info.restype = ct.c_int
 lib.hnswdev_range_grouped_info.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
+lib.hnswdev_range_search_tagged.restype = ct.c_int
+lib.hnswdev_range_search_tagged.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_int, ct.c_float, ct.c_int, _U32, ct.c_longlong, _U32, ct.c_int, _I, _I]
+lib.hnswdev_range_tagged_info.restype = ct.c_int
+lib.hnswdev_range_tagged_info.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
+lib.hnswdev_exact_range_tagged.restype = ct.c_int
+lib.hnswdev_exact_range_tagged.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_longlong, ct.c_float, _U32, ct.c_longlong, _U32, ct.c_int, _I]
+lib.hnswdev_exact_range_tagged_info.restype = ct.c_int
+lib.hnswdev_exact_range_tagged_info.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
 lib.hnswdev_knn_grouped_info.restype = ct.c_int
 lib.hnswdev_knn_grouped_info.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
 lib.hnswdev_range_results.restype = ct.c_int
@@ -433,6 +454,23 @@ def _tag_args(row_tags, query_tags, match, nq):
     if distinct > 65536:
         raise ValueError(f"query_tags holds {distinct} distinct masks, more than 65536")
     return rt, qt, _TAG_MATCH[match]
+
+
+def _take_lists(ids_pp, dists_pp, counts, n):
+    """The per-query arrays a range export handed out, copied into numpy arrays and released (hnsw_free_results)."""
+    ids, dists = [], []
+    try:
+        for i in range(n):
+            m = counts[i]
+            if m == 0:
+                ids.append(np.empty(0, dtype=np.int32))
+                dists.append(np.empty(0, dtype=np.float32))
+                continue
+            ids.append(np.ctypeslib.as_array(ct.cast(ids_pp[i], _I), shape=(m,)).copy())
+            dists.append(np.ctypeslib.as_array(ct.cast(dists_pp[i], _F), shape=(m,)).copy())
+    finally:
+        lib.hnsw_free_results(ids_pp, dists_pp, n)
+    return ids, dists
 
 
 def last_error() -> str:
@@ -941,6 +979,57 @@ class Index:
         if self._h:
             lib.hnsw_mi355x_range_grouped_info(self._h, out)
         return dict(zip(_RANGE_GROUPED_INFO, (int(v) for v in out)))
+
+    def range_query_tagged(self, queries: npt.ArrayLike, radius: float, row_tags, query_tags, match: str = "any",
+                           layer: int = 0) -> Tuple[List[npt.NDArray[np.int32]], List[npt.NDArray[np.float32]]]:
+        """range_query with a tag mask per query, every mask in one device traversal (hnsw_mi355x_range_query_tagged): row_tags /
+        query_tags / match as for knn_query_tagged.  Per distinct mask m the lists equal
+        range_query(queries[query_tags == m], radius, allowed=<the ids that match m>, layer=layer), the order among equal distances
+        included; where the reference throws on an empty heap (radius < 0) RuntimeError carries its message."""
+        q = _as_2d_f32(queries, self.dim)
+        n = int(q.shape[0])
+        rt, qt, mode = _tag_args(row_tags, query_tags, match, n)
+        ids_pp = (ct.c_void_p * n)()
+        dists_pp = (ct.c_void_p * n)()
+        counts = (ct.c_int * n)()
+        status = lib.hnsw_mi355x_range_query_tagged(self._h, q.ctypes.data_as(_F), n, self.dim, radius, int(layer), rt.ctypes.data_as(_U32), rt.shape[0],
+                                                    qt.ctypes.data_as(_U32), mode, ids_pp, dists_pp, counts)
+        if status < 0:
+            raise RuntimeError(last_error())
+        return _take_lists(ids_pp, dists_pp, counts, n)
+
+    def range_tagged_info(self) -> dict:
+        """Counters of range_query_tagged since reset_stats (hnsw_mi355x_range_tagged_info): calls that reached the context, their
+        distinct masks, queries launched, queries skipped because their mask matches no graph id, lists the device left to the host,
+        closures beyond the device's table that it finished all the same."""
+        out = (ct.c_uint64 * 6)()
+        if self._h:
+            lib.hnsw_mi355x_range_tagged_info(self._h, out)
+        return dict(zip(_RANGE_TAGGED_INFO, (int(v) for v in out)))
+
+    def exact_range_query_tagged(self, queries: npt.ArrayLike, radius: float, row_tags, query_tags,
+                                 match: str = "any") -> Tuple[List[npt.NDArray[np.int32]], List[npt.NDArray[np.float32]]]:
+        """exact_range_query with a tag mask per query (hnsw_mi355x_exact_range_query_tagged): row_tags / query_tags / match as for
+        knn_query_tagged.  Per distinct mask m the lists equal
+        exact_range_query(queries[query_tags == m], radius, allowed=<the ids that match m>); they come back in the caller's order."""
+        q = _as_2d_f32(queries, self.dim)
+        n = int(q.shape[0])
+        rt, qt, mode = _tag_args(row_tags, query_tags, match, n)
+        ids_pp = (ct.c_void_p * n)()
+        dists_pp = (ct.c_void_p * n)()
+        counts = (ct.c_int * n)()
+        status = lib.hnsw_mi355x_exact_range_query_tagged(self._h, q.ctypes.data_as(_F), n, self.dim, radius, rt.ctypes.data_as(_U32), rt.shape[0],
+                                                          qt.ctypes.data_as(_U32), mode, ids_pp, dists_pp, counts)
+        if status < 0:
+            raise RuntimeError(last_error())
+        return _take_lists(ids_pp, dists_pp, counts, n)
+
+    def exact_range_tagged_info(self) -> dict:
+        """Counters of exact_range_query_tagged since reset_stats (hnsw_mi355x_exact_range_tagged_info)."""
+        out = (ct.c_uint64 * 9)()
+        if self._h:
+            lib.hnsw_mi355x_exact_range_tagged_info(self._h, out)
+        return dict(zip(_EXACT_RANGE_TAGGED_INFO, (int(v) for v in out)))
 
     # ---- measurement aid: query set resident in HBM across calls ----
     def set_resident_queries(self, queries: npt.ArrayLike):
@@ -1614,6 +1703,53 @@ class DeviceBackend:
         out = (ct.c_uint64 * 4)()
         self._check(lib.hnswdev_range_grouped_info(self._ctx, out))
         return dict(zip(_RANGE_GROUPED_INFO, (int(v) for v in out)))
+
+    def range_search_tagged(self, queries, entry_point: int, radius: float, row_tags, query_tags, match: str = "any", layer: int = 0):
+        """hnswdev_range_search_tagged: range_search with a tag mask per query -- (ids, dists, flags) as range_search returns them,
+        query i filtered by the ids whose word row_tags[id] matches query_tags[i]."""
+        q = _as_2d_f32(queries, self.dim)
+        n = q.shape[0]
+        rt, qt, mode = _tag_args(row_tags, query_tags, match, n)
+        counts = np.zeros(n, dtype=np.int32)
+        flags = np.zeros(n, dtype=np.int32)
+        self._check(lib.hnswdev_range_search_tagged(self._ctx, q.ctypes.data_as(_F), n, int(entry_point), float(radius), int(layer), rt.ctypes.data_as(_U32),
+                                                    rt.shape[0], qt.ctypes.data_as(_U32), mode, counts.ctypes.data_as(_I), flags.ctypes.data_as(_I)))
+        total = int(counts.sum())
+        ids = np.empty(max(total, 1), dtype=np.int32)
+        d = np.empty(max(total, 1), dtype=np.float32)
+        self._check(lib.hnswdev_range_results(self._ctx, ids.ctypes.data_as(_I), d.ctypes.data_as(_F)))
+        cuts = np.cumsum(counts)[:-1]
+        return np.split(ids[:total], cuts), np.split(d[:total], cuts), flags
+
+    def range_tagged_info(self) -> dict:
+        """Counters of range_search_tagged since reset_stats (hnswdev_range_tagged_info)."""
+        out = (ct.c_uint64 * 6)()
+        self._check(lib.hnswdev_range_tagged_info(self._ctx, out))
+        return dict(zip(_RANGE_TAGGED_INFO, (int(v) for v in out)))
+
+    def exact_range_tagged(self, queries, radius: float, row_tags, query_tags, match: str = "any", n_rows=None):
+        """hnswdev_exact_range_tagged: exact_range with a tag mask per query -- (list of ids, list of dists) in the caller's query
+        order, query i answered from the uploaded rows j of [0, n_rows) (None: all) whose word row_tags[j] matches query_tags[i].
+        queries None: the resident set (len(query_tags) of its rows)."""
+        q = None if queries is None else _as_2d_f32(queries, self.dim)
+        n = int(np.asarray(query_tags).size) if q is None else int(q.shape[0])
+        rt, qt, mode = _tag_args(row_tags, query_tags, match, n)
+        counts = np.zeros(n, dtype=np.int32)
+        self._check(lib.hnswdev_exact_range_tagged(self._ctx, None if q is None else q.ctypes.data_as(_F), n, (1 << 62) if n_rows is None else int(n_rows),
+                                                   float(radius), rt.ctypes.data_as(_U32), rt.shape[0], qt.ctypes.data_as(_U32), mode,
+                                                   counts.ctypes.data_as(_I)))
+        total = int(counts.sum(dtype=np.int64))
+        ids = np.empty(max(total, 1), dtype=np.int32)
+        d = np.empty(max(total, 1), dtype=np.float32)
+        self._check(lib.hnswdev_exact_range_results(self._ctx, ids.ctypes.data_as(_I), d.ctypes.data_as(_F)))
+        cuts = np.cumsum(counts, dtype=np.int64)[:-1]
+        return np.split(ids[:total], cuts), np.split(d[:total], cuts)
+
+    def exact_range_tagged_info(self) -> dict:
+        """Counters of exact_range_tagged since reset_stats (hnswdev_exact_range_tagged_info)."""
+        out = (ct.c_uint64 * 9)()
+        self._check(lib.hnswdev_exact_range_tagged_info(self._ctx, out))
+        return dict(zip(_EXACT_RANGE_TAGGED_INFO, (int(v) for v in out)))
 
     def set_profiling(self, on: bool):
         self._check(lib.hnswdev_set_profiling(self._ctx, int(on)))

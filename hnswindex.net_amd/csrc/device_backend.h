@@ -94,7 +94,7 @@ inline std::string group_args_error(const char *who, const int *query_group, int
 // is a candidate when it shares a tag with the mask, 1 "all": when it carries every tag of a mask that is not 0.  The word 0
 // matches no mask and the mask 0 no word, in either mode.
 constexpr long long kTagListEntries = 1LL << 28; // ids in the candidate lists of one batch of masks of exact_knn_tagged: 1 GiB (`tag_list_cap` lowers it)
-inline bool tag_match_host(uint32_t w, uint32_t m, int match) { return (w & m) != 0u && (match == 0 || (w & m) == m); }
+// (the rule itself on the host: tag_match_host, host_structs.h)
 // The distinct masks of a call in the order they first appear, and each query's place among them.
 struct TagCall {
     std::vector<uint32_t> masks; // at most kExactMaxGroups
@@ -417,8 +417,28 @@ public:
         const int *group_of = nullptr; // [njobs]
         long long skipped = 0;
     };
+    // tags (range_query_tagged): the filter is "words[id] matches mask_of[job] under `match`" (tag_match_host's rule;
+    // allow_bits and grp must be nullptr then) -- ids >= n_words carry the word 0 -- ranked by range_sort_tagged_kernel, which also
+    // finishes a closure beyond kRangeSortMax entries when its allowed entries fit the table and hold no equal keys (diag
+    // range_sort_long=0: handed to the host as the other two sorts do); what crosses back is the filtered call's.  resident: s_ttags_
+    // holds words[0, min(n_words, graph)) already (tag_candidates ran on them for this call) and nothing goes up.  skipped: as for grp.
+    struct RangeTags {
+        const uint32_t *words = nullptr;
+        long long n_words = 0;
+        const uint32_t *mask_of = nullptr; // [njobs]
+        int match = 0;
+        long long skipped = 0;
+        bool resident = false;
+        size_t n_masks = 0;                // distinct masks of the call, for range_tagged_info
+    };
     bool range_batch(const SearchJob *jobs, int njobs, float range, RangeResults *res, const uint32_t *allow_bits = nullptr, long long nbits = 0,
-                     const RangeGroups *grp = nullptr);
+                     const RangeGroups *grp = nullptr, const RangeTags *tags = nullptr);
+    // tagged range calls that reached this context, distinct masks, queries launched, queries skipped for a mask without a graph
+    // candidate, lists the device left to the host (closures and hand-backs), closures above kRangeSortMax entries that the device finished
+    void range_tagged_info(uint64_t out[6]) const { for (int i = 0; i < 6; ++i) out[i] = rt_info_[i]; }
+    // The candidates of every distinct mask among ids [0, n) of row_tags, counted on the device (tag_count_kernel): cnt[d] for
+    // masks[d].  The words stay in s_ttags_ for a range_batch that follows (RangeTags::resident).  n <= 0: every count 0, no launch.
+    bool tag_candidates(const uint32_t *row_tags, long long n, const std::vector<uint32_t> &masks, int match, std::vector<int> &cnt);
     // grouped range calls that reached this context, queries launched, queries skipped for a group without graph ids, lists the
     // device left to the host (closures to partition / sort / replay, and hand-backs)
     void range_grouped_info(uint64_t out[4]) const { for (int i = 0; i < 4; ++i) out[i] = rg_info_[i]; }
@@ -432,6 +452,11 @@ public:
     // { id : row_group[id] == query_group[i] }; the group arguments and their errors are knn_search_grouped's
     bool range_search_grouped(const float *queries, int nq, int entry_point, float range, const int *row_group, long long n_row_group,
                               const int *query_group, int n_groups, int *out_counts, int *out_flags, int layer = 0);
+    // ... with a tag mask per query (hnswdev_range_search_tagged): query i as with the allow-set
+    // { id : row_tags[id] matches query_tags[i] under `match` }; the tag arguments and their errors are knn_search_tagged's.  A query
+    // whose mask has no candidate among the graph's ids (counted on the device) gets an empty list without a job when range >= 0.
+    bool range_search_tagged(const float *queries, int nq, int entry_point, float range, const uint32_t *row_tags, long long n_row_tags,
+                             const uint32_t *query_tags, int match, int *out_counts, int *out_flags, int layer = 0);
     bool range_results(int *out_ids, float *out_d);
     // hnswdev_exact_knn (dk_exact.h): for each query the k uploaded rows of smallest (distance, id) among ids
     // [0, min(n_rows, uploaded)) that allow_bits allows (nullptr: all of them; else nbits bits as for search_filtered), ascending,
@@ -480,6 +505,16 @@ public:
     // grouped range calls that launched a scan, lists of >= 2 entries ordered on the device, lists ordered on the host, pieces
     // scanned again with exact capacities
     void exact_range_grouped_info(uint64_t out[4]) const { for (int i = 0; i < 4; ++i) out[i] = xrg_info_[i]; }
+    // hnswdev_exact_range_tagged: exact_range with exact_knn_tagged's candidate set per query -- the tag arguments,
+    // their errors, the lists and the batches of masks are that call's; each batch is one grouped range scan (exact_range_grouped's
+    // rounds, capacities, pass B and sort limit) over the queries of its masks.  The lists are kept for exact_range_results
+    // concatenated in the CALLER's query order, however many batches ran.  A query whose mask has no candidate gets an empty list
+    // without a scan.  false: no results are kept and every count is 0.  Synchronous.
+    bool exact_range_tagged(const float *queries, int nq, long long n_rows, float range, const uint32_t *row_tags, long long n_row_tags,
+                            const uint32_t *query_tags, int match, int *out_counts);
+    // calls that counted candidates, distinct masks, queries scanned, queries answered empty without a scan, list entries built,
+    // batches, lists of >= 2 entries ordered on the device, lists ordered on the host, pieces scanned again
+    void exact_range_tagged_info(uint64_t out[9]) const { for (int i = 0; i < 9; ++i) out[i] = xrt_info_[i]; }
     // HIP-event time of the list-building kernels (count, offsets, place) of the grouped calls made while profiling was on
     double exact_grouped_list_ms() const { return xg_list_ms_; }
     // hnswdev_graph_info / hnswdev_graph_components (dk_graph_info.h): HNSWInfo.LayerInfo (HNSWInfo.cs:18-43) and the
@@ -650,6 +685,8 @@ private:
     DevBuf<int> s_gquery_;       // ... [query_group of the call | order tables of its launches]
     uint64_t kg_info_[4] = {0, 0, 0, 0};
     uint64_t rg_info_[4] = {0, 0, 0, 0}; // range_grouped_info
+    uint64_t rt_info_[6] = {0, 0, 0, 0, 0, 0}; // range_tagged_info
+    uint64_t xrt_info_[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}; // exact_range_tagged_info
     DevBuf<unsigned> s_ttags_;   // tagged calls: the call's row_tags
     DevBuf<unsigned> s_tmask_;   // ... its distinct masks
     DevBuf<int> s_tcnt_;         // ... per distinct mask: [candidates | offset of its segment in x_ids_ | the filling kernel's cursor]
@@ -695,6 +732,8 @@ private:
     bool exact_grouped_plan(const char *who, int k, ExactGroupedCall *gc);
     bool exact_knn_grouped_scan(const char *who, const float *queries, const int *resident, int nq, int k, const int *query_group, int n_groups,
                                 const ExactGroupedCall &gc, int *out_ids, float *out_d, uint64_t *blocks);
+    bool exact_range_grouped_scan(const char *who, const float *queries, const int *resident, int nq, float range, const int *query_group, int n_groups,
+                                  const ExactGroupedCall &gc, int *out_counts, uint64_t info[4]);
     ExactStart exact_grouped_begin(const char *who, bool args_ok, const float *queries, int nq, long long n_rows, int k, const int *row_group,
                                    long long n_row_group, const int *query_group, int n_groups, ExactGroupedCall *gc);
     double xg_list_ms_ = 0.0;

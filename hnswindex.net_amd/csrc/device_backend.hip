@@ -1023,6 +1023,8 @@ void Device::reset_stats()
     for (uint64_t &v : xrg_info_) v = 0;
     for (uint64_t &v : kg_info_) v = 0;
     for (uint64_t &v : rg_info_) v = 0;
+    for (uint64_t &v : rt_info_) v = 0;
+    for (uint64_t &v : xrt_info_) v = 0;
     xg_list_ms_ = 0.0;
     for (uint64_t &v : kt_info_) v = 0;
     for (uint64_t &v : xt_info_) v = 0;
@@ -2241,6 +2243,13 @@ bool Device::tag_counts(const unsigned *row_tags, long long n, const std::vector
     return true;
 }
 
+bool Device::tag_candidates(const uint32_t *row_tags, long long n, const std::vector<uint32_t> &masks, int match, std::vector<int> &cnt)
+{
+    cnt.assign(masks.size(), 0);
+    if (n <= 0 || masks.empty()) return true;
+    return bind() && tag_counts(row_tags, n, masks, match, cnt);
+}
+
 // KnnQuery with a tag mask per query (graph_search_tagged_kernel): the tag words in the labels' place.  Only the
 // words of graph ids travel.  The candidates of every distinct mask are counted on the device (tag_counts) for order_by_members.
 bool Device::search_tagged(int nq, int entry, int entry_layer, int k, int k_out, const uint32_t *row_tags, long long n_row_tags, const uint32_t *query_tags,
@@ -2435,10 +2444,20 @@ bool Device::range_host_room(size_t entries, size_t keep)
 }
 
 bool Device::range_batch(const SearchJob *jobs, int njobs, float range, RangeResults *res, const uint32_t *allow_bits, long long nbits,
-                         const RangeGroups *grp)
+                         const RangeGroups *grp, const RangeTags *tags)
 {
-    const bool grouped = grp != nullptr;
-    const bool filtered = allow_bits != nullptr || grouped; // (grouped: the filtered call's ranking, replay and packing, on the group predicate)
+    const bool grouped = grp != nullptr, tagged = tags != nullptr;
+    const bool filtered = allow_bits != nullptr || grouped || tagged; // (grouped, tagged: the filtered call's ranking, replay and packing, on their predicate)
+    if (tagged) {
+        if (allow_bits || grouped || tags->n_words < 0 || (tags->match != 0 && tags->match != 1) || (njobs > 0 && (!tags->words || !tags->mask_of))) {
+            set_dev_error("range_batch: bad argument");
+            return false;
+        }
+        rt_info_[0] += 1;
+        rt_info_[1] += (uint64_t)tags->n_masks;
+        rt_info_[2] += (uint64_t)std::max(njobs, 0);
+        rt_info_[3] += (uint64_t)std::max<long long>(tags->skipped, 0);
+    }
     if (grouped) {
         if (allow_bits || grp->n_label < 0 || (njobs > 0 && (!grp->label || !grp->group_of))) { set_dev_error("range_batch: bad argument"); return false; }
         rg_info_[0] += 1;
@@ -2486,6 +2505,17 @@ bool Device::range_batch(const SearchJob *jobs, int njobs, float range, RangeRes
             HIP_OK(hipMemcpyAsync(s_glabel_, grp->label, 4u * (size_t)n_lab, hipMemcpyHostToDevice, st));
             HIP_OK(hipStreamSynchronize(st)); // (pageable source: the caller's buffer)
         }
+    } else if (tagged) { // the call's tag words: those of graph ids, on this context (as search_tagged), and room for a launch's mask table
+        if (!s_rres_.grow(s_roff_.cap()) || !s_rdst_.grow(s_roff_.cap())) return false;
+        n_lab = std::min<long long>(tags->n_words, g_n_);
+        if (!s_gquery_.grow((size_t)chunk)) return false;
+        if (!tags->resident || (size_t)n_lab > s_ttags_.cap()) {
+            if (!s_ttags_.grow(std::max<size_t>((size_t)n_lab, 1))) return false;
+            if (n_lab > 0) {
+                HIP_OK(hipMemcpyAsync(s_ttags_, tags->words, 4u * (size_t)n_lab, hipMemcpyHostToDevice, st));
+                HIP_OK(hipStreamSynchronize(st)); // (pageable source: the caller's buffer)
+            }
+        }
     } else if (filtered) { // the call's allow-set: the words that cover graph ids, on this context (as search_filtered)
         if (!s_rres_.grow(s_roff_.cap()) || !s_rdst_.grow(s_roff_.cap())) return false;
         n_allow = std::min<long long>(nbits, g_n_);
@@ -2508,8 +2538,8 @@ bool Device::range_batch(const SearchJob *jobs, int njobs, float range, RangeRes
         // pinned layout: [evals, used (16 B) | jobs | offsets | counts | flags | entries | states]; then reused for the results
         // (filtered: [... | allowed counts | packed offsets] besides)
         const size_t b_jobs = sizeof(SearchJob) * (size_t)nj, b_off = 8u * (size_t)nj, b_i = 4u * (size_t)nj;
-        // (grouped: [... | the jobs' groups] behind those)
-        char *hs = static_cast<char *>(pinned_stage(16 + b_jobs + b_off + 4 * b_i + (filtered ? b_i + b_off : 0) + (grouped ? b_i : 0)));
+        // (grouped: [... | the jobs' groups] behind those; tagged: the jobs' masks there)
+        char *hs = static_cast<char *>(pinned_stage(16 + b_jobs + b_off + 4 * b_i + (filtered ? b_i + b_off : 0) + (grouped || tagged ? b_i : 0)));
         if (!hs) return false;
         SearchJob *h_jobs = reinterpret_cast<SearchJob *>(hs + 16);
         for (int i = 0; i < nj; ++i) h_jobs[i] = jobs[todo[i]];
@@ -2518,6 +2548,11 @@ bool Device::range_batch(const SearchJob *jobs, int njobs, float range, RangeRes
             int *h_grp = reinterpret_cast<int *>(hs + 16 + b_jobs + b_off + 5 * b_i + b_off);
             for (int i = 0; i < nj; ++i) h_grp[i] = grp->group_of[todo[i]];
             HIP_OK(hipMemcpyAsync(s_gquery_, h_grp, b_i, hipMemcpyHostToDevice, st));
+        }
+        if (tagged) { // the sort kernel's table: job -> the mask its query brings (in the group table's place)
+            uint32_t *h_mask = reinterpret_cast<uint32_t *>(hs + 16 + b_jobs + b_off + 5 * b_i + b_off);
+            for (int i = 0; i < nj; ++i) h_mask[i] = tags->mask_of[todo[i]];
+            HIP_OK(hipMemcpyAsync(s_gquery_, h_mask, b_i, hipMemcpyHostToDevice, st));
         }
         uj_len_ = 0;
         HIP_OK(hipMemsetAsync(s_jobctr_, 0, sizeof(int), st));
@@ -2544,7 +2579,12 @@ bool Device::range_batch(const SearchJob *jobs, int njobs, float range, RangeRes
         HIP_OK(hipMemsetAsync(s_rtied_, 0, sizeof(int), st));
         HIP_OK(hipMemsetAsync(s_rstate_, 0, sizeof(int) * (size_t)nj, st));
         const dim3 sort_grid(std::min(nj, 8 * std::max(1, num_cu_))), replay_grid(std::min(nj, 2 * std::max(1, num_cu_)));
-        if (grouped) {
+        if (tagged) {
+            hipLaunchKernelGGL(range_sort_tagged_kernel, sort_grid, dim3(64), 0, st, reinterpret_cast<ND *>(s_arena_.get()), s_roff_, s_cnt_, s_flag_, nj,
+                               s_rstate_, s_rtied_, s_rfin_ctr_, s_ttags_.get(), n_lab, reinterpret_cast<const unsigned *>(s_gquery_.get()), tags->match, s_rres_,
+                               (int)(finish == 0 || range < 0.0f), (int)(diag("range_sort_long", 1) != 0));
+            HIP_OK(hipGetLastError());
+        } else if (grouped) {
             hipLaunchKernelGGL(range_sort_grouped_kernel, sort_grid, dim3(64), 0, st, reinterpret_cast<ND *>(s_arena_.get()), s_roff_, s_cnt_, s_flag_, nj,
                                s_rstate_, s_rtied_, s_rfin_ctr_, s_glabel_.get(), n_lab, s_gquery_.get(), s_rres_, (int)(finish == 0 || range < 0.0f));
             HIP_OK(hipGetLastError());
@@ -2598,6 +2638,8 @@ bool Device::range_batch(const SearchJob *jobs, int njobs, float range, RangeRes
                 const int results = filtered ? h_res[i] : h_cnt[i]; // (filtered, handed to the host: the allowed members of its closure)
                 if (results >= 2) { if (res->state[(size_t)j] == kRangeFinal) stats_.range_device_ordered++; else stats_.range_host_ordered++; }
                 if (grouped && h_cnt[i] > 0 && h_state[i] != kRangeFinal) rg_info_[3] += 1; // a closure the host finishes
+                if (tagged && h_cnt[i] > 0 && h_state[i] != kRangeFinal) rt_info_[4] += 1;
+                if (tagged && h_cnt[i] > kRangeSortMax && h_state[i] == kRangeFinal && h_res[i] >= 2) rt_info_[5] += 1; // rank_long's
                 finished += (unsigned long long)h_cnt[i];
                 if (h_cnt[i] > 0) span = std::max(span, h_off[i] + (unsigned long long)h_cnt[i]);
             } else if (h_flag[i] == 3) again.push_back(j);
@@ -2671,6 +2713,7 @@ bool Device::range_batch(const SearchJob *jobs, int njobs, float range, RangeRes
     }
     stats_.range_handbacks += handed.size();
     if (grouped) rg_info_[3] += handed.size();
+    if (tagged) rt_info_[4] += handed.size();
     range_hint_ = (double)closure_total / (double)njobs; // (filtered calls too: the arena holds closures)
     return true;
 }
@@ -2816,6 +2859,63 @@ bool Device::range_search_grouped(const float *queries, int nq, int entry_point,
         }
         // a closure: partition, sort, replay where the allowed results tie
         if (!finish_closure(layer, r.entry[(size_t)j], range, b, r.cnt[(size_t)j], AllowPred{row_group, n_lab, group_of[(size_t)j]}, nq, out_counts, &out_counts[i]))
+            return false;
+    }
+    return true;
+}
+
+// range_search_grouped with a tag mask per query: query i is answered as with the allow-set
+// { id : row_tags[id] matches query_tags[i] }, every mask in one traversal launch.  Only the words of graph ids count; which masks
+// have a candidate among them the device counts (tag_counts) -- no host pass over the words.  A query whose mask has none gets an
+// empty list without a job when range >= 0 only, as for a group without ids.
+bool Device::range_search_tagged(const float *queries, int nq, int entry_point, float range, const uint32_t *row_tags, long long n_row_tags,
+                                 const uint32_t *query_tags, int match, int *out_counts, int *out_flags, int layer)
+{
+    abi_range_.clear();
+    if (nq <= 0) return true;
+    if (!out_counts || !out_flags) { set_dev_error("range_search_tagged: null argument"); return false; }
+    for (int i = 0; i < nq; ++i) { out_counts[i] = 0; out_flags[i] = 0; }
+    if (!row_tags || n_row_tags < 0) { set_dev_error("range_search_tagged: row_tags must not be NULL and n_row_tags must be >= 0"); return false; }
+    if (!query_tags) { set_dev_error("range_search_tagged: query_tags must not be NULL"); return false; }
+    TagCall tc;
+    if (!tag_args_ok("range_search_tagged", query_tags, nq, match, &tc)) return false;
+    int top;
+    if (!abi_begin("range_search_tagged", queries, nq, entry_point, layer, &top, true)) return false;
+    const long long n_lab = std::min<long long>(n_row_tags, g_n_);
+    std::vector<int> cnt;
+    if (!tag_candidates(row_tags, n_lab, tc.masks, match, cnt)) return false;
+    std::vector<SearchJob> jobs;
+    std::vector<int> qi_of;
+    std::vector<uint32_t> mask_of;
+    for (int i = 0; i < nq; ++i)
+        if (cnt[(size_t)tc.of[(size_t)i]] > 0 || !(range >= 0.0f)) {
+            jobs.push_back(SearchJob{i, entry_point, top, layer, -1});
+            qi_of.push_back(i);
+            mask_of.push_back(query_tags[i]);
+        }
+    const int nj = (int)jobs.size();
+    RangeTags tags;
+    tags.words = row_tags;
+    tags.n_words = n_lab;
+    tags.mask_of = mask_of.data();
+    tags.match = match;
+    tags.skipped = nq - nj;
+    tags.resident = n_lab > 0;
+    tags.n_masks = tc.masks.size();
+    RangeResults r;
+    if (!range_batch(jobs.data(), nj, range, &r, nullptr, 0, nullptr, &tags)) return false;
+    for (int j = 0; j < nj; ++j) { // (in query order: abi_range_ holds the lists as range_results hands them out)
+        const int i = qi_of[(size_t)j];
+        out_flags[i] = r.flag[(size_t)j];
+        if (out_flags[i]) continue;
+        SearchHit *b = r.found + r.off[(size_t)j], *e = b + r.cnt[(size_t)j];
+        if (r.state[(size_t)j] == kRangeFinal) { // the results, in the reference's order
+            out_counts[i] = r.cnt[(size_t)j];
+            abi_range_.insert(abi_range_.end(), b, e);
+            continue;
+        }
+        // a closure: partition, sort, replay where the allowed results tie -- with the query's own predicate
+        if (!finish_closure(layer, r.entry[(size_t)j], range, b, r.cnt[(size_t)j], AllowPred{row_tags, n_lab, mask_of[(size_t)j], match}, nq, out_counts, &out_counts[i]))
             return false;
     }
     return true;
@@ -3794,6 +3894,20 @@ bool Device::exact_range_grouped(const float *queries, int nq, long long n_rows,
         if (s == ExactStart::failed) return false;
         for (int i = 0; i < nq; ++i) out_counts[i] = 0;
         if (s == ExactStart::nothing) return true; // no query has a candidate: empty lists, no scan
+        return exact_range_grouped_scan("exact_range_grouped", queries, nullptr, nq, range, query_group, n_groups, gc, out_counts, xrg_info_);
+    });
+}
+
+// A grouped range scan once the groups' lists stand in x_ids_ (gc: per group its queries, members and segment; the tile): rounds,
+// the sorted upload, work items, pass A, the finish and pass B -- what exact_range_grouped and every batch of exact_range_tagged
+// run.  The nq queries are `queries`, or (nullptr) the resident queries resident[0 .. nq) (nullptr: 0 .. nq - 1); query_group[i]
+// names query i's list.  out_counts[0, nq) are written (zeroed by the caller) and the lists APPENDED to xr_ids_ / xr_d_ in the order
+// of the nq queries.  info: [calls that launched a scan, lists of >= 2 entries ordered on the device, lists ordered on the host,
+// pieces scanned again], added to.
+bool Device::exact_range_grouped_scan(const char *who, const float *queries, const int *resident, int nq, float range, const int *query_group, int n_groups,
+                                      const ExactGroupedCall &gc, int *out_counts, uint64_t info[4])
+{
+    {
         hipStream_t st = S(stream_);
         const std::vector<int> &cnt = gc.cnt;
         const ExactPlan &tp = gc.tp;
@@ -3820,7 +3934,7 @@ bool Device::exact_range_grouped(const float *queries, int nq, long long n_rows,
         const std::vector<int> order = exact_group_order(query_group, n_groups, round_end);
         const float *d_q;
         const double *d_qsn;
-        if (!exact_sorted_queries("exact_range_grouped", queries, nq, order, &d_q, &d_qsn)) return false;
+        if (!exact_sorted_queries(who, queries, nq, order, &d_q, &d_qsn, resident)) return false;
 
         if (!x_rcnt_.grow((size_t)max_round) || !x_rseg_.grow((size_t)max_round + 1) || !x_rooff_.grow((size_t)max_round)) return false;
         std::vector<long long> seg((size_t)max_round + 1), obase((size_t)max_round);
@@ -3907,24 +4021,129 @@ bool Device::exact_range_grouped(const float *queries, int nq, long long n_rows,
             }
             xr_ids_.resize(base + total);
             xr_d_.resize(base + total);
-            if (!exact_range_finish(w, nr, cnt_fit.data(), seg.data(), nullptr, obase.data(), base, ov.empty(), &xrg_info_[1], &xrg_info_[2])) return false;
+            if (!exact_range_finish(w, nr, cnt_fit.data(), seg.data(), nullptr, obase.data(), base, ov.empty(), &info[1], &info[2])) return false;
             // pass B: the queries whose count exceeded its capacity (ov, their counts in cnt_ov), in pieces whose exact counts fit the
             // arena, each with segments of exactly its counts; the other queries of their tiles are measured again and their keys dropped
             for (size_t s0 = 0, s1; s0 < ov.size(); s0 = s1) {
-                if (!exact_range_piece("exact_range_grouped", cnt_ov.data(), ov.size(), s0, w.arena_max, seg, &s1)) return false;
+                if (!exact_range_piece(who, cnt_ov.data(), ov.size(), s0, w.arena_max, seg, &s1)) return false;
                 const int ns = (int)(s1 - s0);
                 slot_q.assign((size_t)nr, -1); // query of the round -> its segment in this piece
                 for (int s = 0; s < ns; ++s) slot_q[(size_t)ov[s0 + (size_t)s]] = s;
                 for (int p = 0; p < nr; ++p) dest[(size_t)p] = slot_q[(size_t)(order[(size_t)(off + p)] - off)];
                 items(off, nr);
-                xrg_info_[3] += 1;
+                info[3] += 1;
                 cnt_b.resize((size_t)ns);
-                if (!scan(off, nr, ns, cnt_b.data()) || !exact_range_recount_ok("exact_range_grouped", cnt_b.data(), cnt_ov.data() + s0, (size_t)ns)) return false;
-                if (!exact_range_finish(w, ns, cnt_b.data(), seg.data(), ov.data() + s0, obase.data(), base, true, &xrg_info_[1], &xrg_info_[2])) return false;
+                if (!scan(off, nr, ns, cnt_b.data()) || !exact_range_recount_ok(who, cnt_b.data(), cnt_ov.data() + s0, (size_t)ns)) return false;
+                if (!exact_range_finish(w, ns, cnt_b.data(), seg.data(), ov.data() + s0, obase.data(), base, true, &info[1], &info[2])) return false;
             }
             off = r1;
         }
-        if (launched) xrg_info_[0] += 1;
+        if (launched) info[0] += 1;
+        return true;
+    }
+}
+
+// ---- hnswdev_exact_range_tagged: a tag mask per query, every distinct mask a candidate list, the range sink ----
+// exact_knn_tagged's counts, batches of masks and lists (dk_tag_lists.h); per batch exact_range_grouped_scan answers the queries of
+// the batch's masks that have a candidate, in the caller's order among themselves.  A batch appends its lists to xr_ids_ / xr_d_;
+// with more than one batch the lists are moved into the caller's query order afterwards (exact_range_results hands them out so).
+bool Device::exact_range_tagged(const float *queries, int nq, long long n_rows, float range, const uint32_t *row_tags, long long n_row_tags,
+                                const uint32_t *query_tags, int match, int *out_counts)
+{
+    return exact_range_call(nq, out_counts, [&]() -> bool {
+        if (nq <= 0) return true;
+        const char *who = "exact_range_tagged";
+        const auto fail = [&](const std::string &what) { set_dev_error(std::string(who) + ": " + what); return false; };
+        if (!(out_counts && n_rows >= 0)) return fail("bad argument");
+        if (!row_tags || n_row_tags < 0) return fail("row_tags must not be NULL and n_row_tags must be >= 0");
+        if (!query_tags) return fail("query_tags must not be NULL");
+        TagCall tc;
+        if (!tag_args_ok(who, query_tags, nq, match, &tc)) return false;
+        for (int i = 0; i < nq; ++i) out_counts[i] = 0;
+        // ids that exist and have a word: a row beyond what was uploaded is never dereferenced, whatever n_rows and n_row_tags say
+        const long long n = std::min({n_rows, n_rows_hw_, n_row_tags});
+        if (n <= 0) return true; // no candidate: empty lists, nothing launched
+        if (!queries && (nq > n_queries_ || tail_.n > 0)) return fail("queries == NULL needs a resident query set of at least nq rows (hnswdev_set_queries)");
+        const int D = (int)tc.masks.size();
+        std::vector<int> cnt;
+        if (!bind() || !tag_counts(row_tags, n, tc.masks, match, cnt)) return false;
+        hipStream_t st = S(stream_);
+        const long long forced = diag("tag_list_cap", 0), cap = forced > 0 ? forced : kTagListEntries;
+        std::vector<int> gq((size_t)D, 0);
+        for (int i = 0; i < nq; ++i) gq[(size_t)tc.of[(size_t)i]] += 1;
+        uint64_t scanned_q = 0, listed = 0, batches = 0, info[4] = {0, 0, 0, 0};
+        std::vector<int> sel, qg, t_cnt;
+        std::vector<float> t_q;
+        std::vector<size_t> at_of((size_t)nq, 0); // where query i's list starts in xr_ids_ as the batches left it
+        for (int d0 = 0; d0 < D;) {
+            // the batch: masks d0 .. d1 - 1, `sum` entries
+            long long sum = cnt[(size_t)d0];
+            int d1 = d0 + 1;
+            while (d1 < D && sum + cnt[(size_t)d1] <= cap) sum += cnt[(size_t)d1++];
+            if (sum == 0) { d0 = d1; continue; } // (no mask of it has a candidate: its queries' lists stay empty)
+            ExactGroupedCall gc;
+            gc.gq.assign((size_t)D, 0);
+            gc.cnt.assign((size_t)D, 0);
+            gc.goff.assign((size_t)D, 0);
+            gc.n = n;
+            gc.listed = (uint64_t)sum;
+            long long at = 0;
+            for (int d = d0; d < d1; ++d) { gc.gq[(size_t)d] = gq[(size_t)d]; gc.cnt[(size_t)d] = cnt[(size_t)d]; gc.goff[(size_t)d] = (int)at; at += cnt[(size_t)d]; }
+            if (!exact_grouped_plan(who, 0, &gc)) return false;
+            if (!x_ids_.grow((size_t)sum)) return false;
+            const bool timed = profiling_;
+            if (timed && (!ev0_.create(true) || !ev1_.create(true))) return false;
+            if (timed) HIP_OK(hipEventRecord(E(ev0_), st));
+            HIP_OK(tag_lists_launch(s_ttags_, n, s_tmask_.get() + d0, d1 - d0, match, s_tcnt_.get() + d0, s_tcnt_.get() + D + d0, s_tcnt_.get() + 2 * (size_t)D + d0,
+                                    x_ids_, sum, st));
+            if (timed) {
+                HIP_OK(hipEventRecord(E(ev1_), st));
+                HIP_OK(hipStreamSynchronize(st)); // (the scan records the same pair of events)
+                float ms = 0.f;
+                HIP_OK(hipEventElapsedTime(&ms, E(ev0_), E(ev1_)));
+                xt_list_ms_ += ms;
+            }
+            // the batch's queries: those of its masks that have a candidate, in the caller's order
+            sel.clear();
+            qg.clear();
+            for (int i = 0; i < nq; ++i) {
+                const int d = tc.of[(size_t)i];
+                if (d >= d0 && d < d1 && cnt[(size_t)d] > 0) { sel.push_back(i); qg.push_back(d); }
+            }
+            const int nb = (int)sel.size();
+            const size_t base = xr_ids_.size();
+            if (nb == nq) { // every query of the call: straight into the caller's counts
+                if (!exact_range_grouped_scan(who, queries, nullptr, nq, range, qg.data(), D, gc, out_counts, info)) return false;
+            } else if (nb > 0) {
+                t_cnt.assign((size_t)nb, 0);
+                if (queries) {
+                    t_q.resize((size_t)nb * (size_t)dim_);
+                    for (int j = 0; j < nb; ++j) memcpy(&t_q[(size_t)j * dim_], queries + (size_t)sel[(size_t)j] * dim_, sizeof(float) * (size_t)dim_);
+                }
+                if (!exact_range_grouped_scan(who, queries ? t_q.data() : nullptr, queries ? nullptr : sel.data(), nb, range, qg.data(), D, gc, t_cnt.data(), info)) return false;
+                for (int j = 0; j < nb; ++j) out_counts[sel[(size_t)j]] = t_cnt[(size_t)j];
+            }
+            size_t o = base;
+            for (int j = 0; j < nb; ++j) { at_of[(size_t)sel[(size_t)j]] = o; o += (size_t)out_counts[sel[(size_t)j]]; }
+            scanned_q += (uint64_t)nb;
+            listed += (uint64_t)sum;
+            batches += 1;
+            d0 = d1;
+        }
+        if (batches > 1) { // the batches' lists, moved into the caller's query order
+            std::vector<int> ids(xr_ids_.size());
+            std::vector<float> d(xr_d_.size());
+            size_t o = 0;
+            for (int i = 0; i < nq; ++i) {
+                const size_t c = (size_t)out_counts[i];
+                if (c) { memcpy(ids.data() + o, xr_ids_.data() + at_of[(size_t)i], 4 * c); memcpy(d.data() + o, xr_d_.data() + at_of[(size_t)i], 4 * c); }
+                o += c;
+            }
+            xr_ids_.swap(ids);
+            xr_d_.swap(d);
+        }
+        xrt_info_[0] += 1; xrt_info_[1] += (uint64_t)D; xrt_info_[2] += scanned_q; xrt_info_[3] += (uint64_t)nq - scanned_q; xrt_info_[4] += listed; xrt_info_[5] += batches;
+        xrt_info_[6] += info[1]; xrt_info_[7] += info[2]; xrt_info_[8] += info[3];
         return true;
     });
 }
@@ -4606,6 +4825,19 @@ DEV_API int hnswdev_range_grouped_info(void *ctx, uint64_t out[4])
     d->range_grouped_info(out);
     return 0;
 }
+DEV_API int hnswdev_range_search_tagged(void *ctx, const float *queries, int nq, int entry_point, float range, int layer, const uint32_t *row_tags,
+                                        long long n_row_tags, const uint32_t *query_tags, int match, int *out_counts, int *out_flags)
+{
+    CTX_OR_FAIL();
+    return d->range_search_tagged(queries, nq, entry_point, range, row_tags, n_row_tags, query_tags, match, out_counts, out_flags, layer) ? 0 : -1;
+}
+DEV_API int hnswdev_range_tagged_info(void *ctx, uint64_t out[6])
+{
+    CTX_OR_FAIL();
+    if (!out) return -1;
+    d->range_tagged_info(out);
+    return 0;
+}
 DEV_API int hnswdev_multilayer_search(void *ctx, const float *queries, int nq, int entry_point, int k, int max_layer, int min_layer, int layers_cap,
                                       int *out_ids, float *out_dists, int *out_flags)
 {
@@ -4656,6 +4888,19 @@ DEV_API int hnswdev_exact_range_grouped_info(void *ctx, uint64_t out[4])
     CTX_OR_FAIL();
     if (!out) return -1;
     d->exact_range_grouped_info(out);
+    return 0;
+}
+DEV_API int hnswdev_exact_range_tagged(void *ctx, const float *queries, int nq, long long n_rows, float range, const uint32_t *row_tags, long long n_row_tags,
+                                       const uint32_t *query_tags, int match, int *out_counts)
+{
+    CTX_OR_FAIL();
+    return d->exact_range_tagged(queries, nq, n_rows, range, row_tags, n_row_tags, query_tags, match, out_counts) ? 0 : -1;
+}
+DEV_API int hnswdev_exact_range_tagged_info(void *ctx, uint64_t out[9])
+{
+    CTX_OR_FAIL();
+    if (!out) return -1;
+    d->exact_range_tagged_info(out);
     return 0;
 }
 DEV_API int hnswdev_exact_grouped_list_ms(void *ctx, double *out_ms)

@@ -110,6 +110,59 @@ __device__ __forceinline__ bool rank_partition(const int2 *e, int m, int ma, ND 
     return __ballot(tie) != 0ull;
 }
 
+// A closure of m > kRangeSortMax entries at `a`, 2 <= ma <= kRangeSortMax of them allowed (range_sort_by<LONG>): the allowed
+// entries are compacted into e[0, ma), stably by position, and ranked by (key, position) into rk[] -- nothing is written to the
+// arena until it is known whether two of them share a key.  No tie: they go to a[0, ma) in rank order, which is the reference's
+// order (one ascending order exists), over whatever stood there; returns false.  A tie (or a count that differs from ma, which
+// cannot be): the arena stays as found -- the replay needs the whole closure, and its table does not hold it -- and true returns.
+// Wave-uniform result; every barrier is reached by the whole wave.
+template <class Allowed>
+__device__ __forceinline__ bool rank_long(ND *a, int m, int ma, int2 *e, unsigned short *rk, Allowed allowed, int lane)
+{
+    const unsigned long long lanes_below = (1ull << lane) - 1ull;
+    int at = 0;
+    wave_sync();
+    for (int i0 = 0; i0 < m; i0 += 64) {
+        const int i = i0 + lane;
+        bool ok = false;
+        ND v{0, 0.0f};
+        if (i < m) {
+            v = a[i];
+            ok = allowed(v.id);
+        }
+        const unsigned long long b = __ballot(ok);
+        const int pos = at + __popcll(b & lanes_below);
+        if (ok && pos < ma) e[pos] = make_int2(v.id, (int)f2key(v.dist));
+        at += __popcll(b);
+    }
+    wave_sync();
+    if (at != ma) return true;
+    bool tie = false;
+    for (int i0 = 0; i0 < ma; i0 += 64) {
+        const int i = i0 + lane;
+        const unsigned ki = i < ma ? (unsigned)e[i].y : 0u;
+        int below = 0;
+        bool eq = false;
+        for (int j = 0; j < ma; ++j) {
+            const unsigned kj = (unsigned)e[j].y;
+            below += (kj < ki || (kj == ki && j < i)) ? 1 : 0;
+            eq = eq || (kj == ki && j != i);
+        }
+        if (i < ma) rk[i] = (unsigned short)below;
+        tie = tie || (i < ma && eq);
+    }
+    wave_sync();
+    if (__ballot(tie) != 0ull) return true;
+    for (int i0 = 0; i0 < ma; i0 += 64) { // (no tie: rk is a permutation of 0 .. ma - 1.  The loop keeps the shape of the ranking loop: as
+        const int i = i0 + lane;          // `for (i = lane; i < ma; i += 64)` it crashes instruction selection in hipcc 7.2)
+        if (i < ma) {
+            const int2 ei = e[i];
+            a[rk[i]] = ND{ei.x, key2f((unsigned)ei.y)};
+        }
+    }
+    return false;
+}
+
 // range_sort_kernel for a RangeQuery with a predicate over ids: the one body of range_sort_filtered_kernel
 // and range_sort_grouped_kernel.  The list is the query's whole CLOSURE, allowed or not -- the traversal does not depend on the
 // filter.  allowed_of(job) gives the job's test over an id (wave-uniform state read once per job).  The allowed entries come
@@ -118,10 +171,13 @@ __device__ __forceinline__ bool rank_partition(const int2 *e, int m, int ma, ND 
 // result moved to the front).  host_all (range < 0: the empty-heap rule is the host's; diag range_finish=0): every list that holds
 // entries is left to the host as found, res[] still counted.  What it leaves is what range_replay_filtered_kernel and
 // range_pack_kernel read: they know the filter only as "entry index < res[job]" and serve every predicate.
-template <class AllowedOf>
+// LONG (range_sort_tagged_kernel alone; long_on: its run-time switch, diag range_sort_long): a closure beyond the
+// table whose 2 .. kRangeSortMax ALLOWED entries hold no equal keys is finished here all the same (rank_long) -- final, res[job]
+// results at the front of the arena list, the rest of the list no longer a closure and read by nobody.
+template <bool LONG = false, class AllowedOf>
 __device__ __forceinline__ void range_sort_by(ND *__restrict__ arena, const unsigned long long *__restrict__ off, const int *__restrict__ cnt,
                                               const int *__restrict__ flag, int njobs, int *__restrict__ state, int *__restrict__ tied,
-                                              int *__restrict__ job_counter, int *__restrict__ res, int host_all, AllowedOf allowed_of)
+                                              int *__restrict__ job_counter, int *__restrict__ res, int host_all, AllowedOf allowed_of, int long_on = 0)
 {
     __shared__ int2 e[kRangeSortMax];
     const int lane = threadIdx.x;
@@ -157,8 +213,15 @@ __device__ __forceinline__ void range_sort_by(ND *__restrict__ arena, const unsi
             if (host_all) st = kRangeHostSort; // left as found
             else if (ma <= 1) {
                 if (ma == 1 && first > 0 && lane == 0) a[0] = a[first];
-            } else if (!fits || __ballot(unsafe) != 0ull) st = kRangeHostSort; // -0 anywhere: the candidate heap's order is float.CompareTo's
-            else st = rank_partition(e, m, ma, a, lane) ? kRangeTied : kRangeFinal;
+            } else if (!fits || __ballot(unsafe) != 0ull) { // -0 anywhere: the candidate heap's order is float.CompareTo's
+                st = kRangeHostSort;
+                if constexpr (LONG) { // (every term wave-uniform)
+                    if (long_on && !fits && ma <= kRangeSortMax && __ballot(unsafe) == 0ull) {
+                        __shared__ unsigned short rk[kRangeSortMax];
+                        st = rank_long(a, m, ma, e, rk, allowed, lane) ? kRangeHostSort : kRangeFinal;
+                    }
+                }
+            } else st = rank_partition(e, m, ma, a, lane) ? kRangeTied : kRangeFinal;
         }
         wave_sync();
         if (lane == 0) { // (one store point: see range_sort_kernel)
@@ -191,6 +254,20 @@ range_sort_grouped_kernel(ND *__restrict__ arena, const unsigned long long *__re
         const int grp = __builtin_amdgcn_readfirstlane(group_of[job]);
         return [=](int id) { return id >= 0 && (long long)id < n_label && label[id] == grp; };
     });
+}
+
+// A tag mask per query (range_query_tagged): an entry is allowed when its id's tag word matches mask_of[job] under
+// the call's mode (TagSet::test, the one text of the rule); ids >= n_tags carry the word 0.  The words are unsigned from the
+// caller's array to the compare.  The one wrapper with the long-closure path (long_on).
+__global__ void __launch_bounds__(64)
+range_sort_tagged_kernel(ND *__restrict__ arena, const unsigned long long *__restrict__ off, const int *__restrict__ cnt, const int *__restrict__ flag,
+                         int njobs, int *__restrict__ state, int *__restrict__ tied, int *__restrict__ job_counter, const unsigned *__restrict__ row_tags,
+                         long long n_tags, const unsigned *__restrict__ mask_of, int match_all, int *__restrict__ res, int host_all, int long_on)
+{
+    range_sort_by<true>(arena, off, cnt, flag, njobs, state, tied, job_counter, res, host_all, [=](int job) {
+        const TagSet ts{row_tags, n_tags, (unsigned)__builtin_amdgcn_readfirstlane((int)mask_of[job]), match_all};
+        return [=](int id) { return id >= 0 && ts.has(id); };
+    }, long_on);
 }
 
 // LDS of one replaying wave: entries (id, key) in ascending order, an id -> entry hash, visited bits, the two heaps.

@@ -241,10 +241,13 @@ API int hnsw_mi355x_knn_query_grouped(void *handle, const float *vectors, int co
 
 API void hnsw_free_results(void **ids_array, void **dists_array, int count);
 
-// hnsw_range_query and its filtered and grouped siblings: `name` for the errors, allow (none: no filter), or grp: a group per query
+// hnsw_range_query and its filtered, grouped and tagged siblings: `name` for the errors, allow (none: no filter), or grp: a group per
+// query, or tags: a tag mask per query
 struct RangeGroupArgs { const int *row_group; long long n_row_group; const int *query_group; int n_groups; };
+struct RangeTagArgs { const uint32_t *row_tags; long long n_row_tags; const uint32_t *query_tags; int match; };
 static int range_query_export(void *handle, const float *vectors, int count, int dim, float range, hnsw::AllowBits allow, void **out_ids,
-                              void **out_dists, int *counts, const char *name, int layer = 0, const RangeGroupArgs *grp = nullptr)
+                              void **out_dists, int *counts, const char *name, int layer = 0, const RangeGroupArgs *grp = nullptr,
+                              const RangeTagArgs *tags = nullptr)
 {
     if (!vectors || !out_ids || !out_dists || !counts || dim <= 0) { set_error(std::string("System.ArgumentNullException: ") + name); return -1; }
     for (int i = 0; i < count; ++i) { out_ids[i] = nullptr; out_dists[i] = nullptr; counts[i] = 0; }
@@ -253,7 +256,8 @@ static int range_query_export(void *handle, const float *vectors, int count, int
     {
         LOCK_INDEX(handle);
         HnswIndex *ix = static_cast<HnswIndex *>(handle);
-        const int rc = grp ? ix->range_query_grouped(vectors, count, dim, range, layer, grp->row_group, grp->n_row_group, grp->query_group, grp->n_groups, res, err)
+        const int rc = tags ? ix->range_query_tagged(vectors, count, dim, range, layer, tags->row_tags, tags->n_row_tags, tags->query_tags, tags->match, res, err)
+                     : grp ? ix->range_query_grouped(vectors, count, dim, range, layer, grp->row_group, grp->n_row_group, grp->query_group, grp->n_groups, res, err)
                            : ix->range_query(vectors, count, dim, range, res, err, allow, layer);
         if (rc < 0) { set_error(err); return -1; }
     }
@@ -334,6 +338,22 @@ API int hnsw_mi355x_range_query_grouped(void *handle, const float *vectors, int 
     return range_query_export(handle, vectors, count, dim, range, hnsw::AllowBits{}, out_ids, out_dists, counts, "hnsw_mi355x_range_query_grouped", layer, &grp);
 }
 
+// hnsw_mi355x_range_query_at_layer with a tag mask per query: query i's list is what that call returns for it with
+// the ids j < n_row_tags whose word row_tags[j] matches query_tags[i] under `match` as the allow-set, the order among equal
+// distances and the empty-heap failure (-1, every array NULL, every count 0) included.  hnsw_mi355x_knn_query_tagged's tag arguments.
+API int hnsw_mi355x_range_query_tagged(void *handle, const float *vectors, int count, int dim, float range, int layer, const uint32_t *row_tags,
+                                       long long n_row_tags, const uint32_t *query_tags, int match, void **out_ids, void **out_dists, int *counts)
+{
+    if (!handle) return 0;
+    if (count <= 0) return 0;
+    if (!vectors || !out_ids || !out_dists || !counts || dim <= 0) { set_error("System.ArgumentNullException: hnsw_mi355x_range_query_tagged"); return -1; }
+    for (int i = 0; i < count; ++i) { out_ids[i] = nullptr; out_dists[i] = nullptr; counts[i] = 0; }
+    if (!query_tags) { set_error("System.ArgumentNullException: hnsw_mi355x_range_query_tagged: query_tags"); return -1; }
+    if (!tagged_args("hnsw_mi355x_range_query_tagged", true, row_tags, n_row_tags, match)) return -1;
+    const RangeTagArgs tags{row_tags, n_row_tags, query_tags, match};
+    return range_query_export(handle, vectors, count, dim, range, hnsw::AllowBits{}, out_ids, out_dists, counts, "hnsw_mi355x_range_query_tagged", layer, nullptr, &tags);
+}
+
 // The lists of a flat range scan, concatenated in query order in ids / ds, handed out as hnsw_range_query hands its lists out: a
 // malloc'ed pair per query with results.  Out of memory: everything released, every count 0, -1.
 static int exact_range_hand_out(const char *name, int count, int *counts, const std::vector<int> &ids, const std::vector<float> &ds, void **out_ids, void **out_dists)
@@ -410,6 +430,31 @@ API int hnsw_mi355x_exact_range_query_grouped(void *handle, const float *vectors
         }
     }
     return exact_range_hand_out("hnsw_mi355x_exact_range_query_grouped", count, counts, ids, ds, out_ids, out_dists);
+}
+
+// hnsw_mi355x_exact_range_query with a tag mask per query: that call's lists and allocation contract,
+// hnsw_mi355x_exact_knn_query_tagged's tag arguments.
+API int hnsw_mi355x_exact_range_query_tagged(void *handle, const float *vectors, int count, int dim, float range, const uint32_t *row_tags, long long n_row_tags,
+                                             const uint32_t *query_tags, int match, void **out_ids, void **out_dists, int *counts)
+{
+    if (!handle) return 0;
+    if (count <= 0) return 0;
+    if (!vectors || !out_ids || !out_dists || !counts || dim <= 0) { set_error("System.ArgumentNullException: hnsw_mi355x_exact_range_query_tagged"); return -1; }
+    for (int i = 0; i < count; ++i) { out_ids[i] = nullptr; out_dists[i] = nullptr; counts[i] = 0; }
+    if (!query_tags) { set_error("System.ArgumentNullException: hnsw_mi355x_exact_range_query_tagged: query_tags"); return -1; }
+    if (!tagged_args("hnsw_mi355x_exact_range_query_tagged", true, row_tags, n_row_tags, match)) return -1;
+    std::string err;
+    std::vector<int> ids;
+    std::vector<float> ds;
+    {
+        LOCK_INDEX(handle);
+        if (static_cast<HnswIndex *>(handle)->exact_range_query_tagged(vectors, count, dim, range, row_tags, n_row_tags, query_tags, match, counts, ids, ds, err) < 0) {
+            for (int i = 0; i < count; ++i) counts[i] = 0;
+            set_error(err);
+            return -1;
+        }
+    }
+    return exact_range_hand_out("hnsw_mi355x_exact_range_query_tagged", count, counts, ids, ds, out_ids, out_dists);
 }
 
 // KnnQuery / RangeQuery with the reference's `layer` argument (BatchKnnQuery / BatchRangeQuery(queries, ., filterFnc, layer),
@@ -620,6 +665,20 @@ API int hnsw_mi355x_range_grouped_info(void *h, uint64_t out[4])
     if (!h || !out) return -1;
     LOCK_INDEX(h);
     static_cast<HnswIndex *>(h)->range_grouped_info(out);
+    return 0;
+}
+API int hnsw_mi355x_range_tagged_info(void *h, uint64_t out[6])
+{
+    if (!h || !out) return -1;
+    LOCK_INDEX(h);
+    static_cast<HnswIndex *>(h)->range_tagged_info(out);
+    return 0;
+}
+API int hnsw_mi355x_exact_range_tagged_info(void *h, uint64_t out[9])
+{
+    if (!h || !out) return -1;
+    LOCK_INDEX(h);
+    static_cast<HnswIndex *>(h)->exact_range_tagged_info(out);
     return 0;
 }
 API int hnsw_mi355x_knn_grouped_info(void *h, uint64_t out[4])

@@ -1992,6 +1992,26 @@ int HnswIndex::exact_range_query_grouped(const float *queries, int count, int di
     return exact_range_fetch(*dev_, dev_->exact_range_grouped(queries, count, length, range, row_group, n_row_group, query_group, n_groups, counts), ids, dists, err);
 }
 
+// The range sink with a tag mask per query.  The words go to the device as live_tags leaves them.
+int HnswIndex::exact_range_query_tagged(const float *queries, int count, int dim, float range, const uint32_t *row_tags, long long n_row_tags,
+                                        const uint32_t *query_tags, int match, int *counts, std::vector<int> &ids, std::vector<float> &dists, std::string &err)
+{
+    ids.clear();
+    dists.clear();
+    if (count <= 0) return 0;
+    for (int i = 0; i < count; ++i) counts[i] = 0;
+    if (failed(err)) return -1;
+    TagCall tc;
+    if (!tag_args_ok("hnsw_mi355x_exact_range_query_tagged", query_tags, count, match, &tc, err)) return -1;
+    if (graph_.count <= 0) return 0;
+    if (!ensure_dim(dim, err)) return -1;
+    const long long length = graph_.length;
+    std::vector<uint32_t> live;
+    if (live_tags(row_tags, n_row_tags, live) && n_row_tags == 0) return 0; // vacant slots and no word: no candidate
+    // (the scan stages its queries in a buffer of its own: the resident set, sharded or not, stays what it was)
+    return exact_range_fetch(*dev_, dev_->exact_range_tagged(queries, count, length, range, row_tags, n_row_tags, query_tags, match, counts), ids, dists, err);
+}
+
 // GetInfo / GetConnectedComponentCounts (HNSWIndex.cs:192-205) on the graph mirror, a layer at a time.  The live
 // set goes to the device as exact_candidates builds it -- none while no slot is vacant.  Always on the device, on the primary context.
 int HnswIndex::get_info(hnsw_mi355x_layer_info *out, int cap, std::string &err)
@@ -2460,7 +2480,20 @@ int HnswIndex::range_query_device(int n_queries, float range, std::vector<std::v
     const bool filtered = allow.bits != nullptr || grp != nullptr;
     std::vector<int> group_of;
     Device::RangeGroups dev_grp;
-    if (grp) {
+    std::vector<uint32_t> mask_of;
+    Device::RangeTags dev_tags;
+    const bool tagged = grp && grp->tags;
+    if (tagged) {
+        mask_of.resize((size_t)count);
+        for (int i = 0; i < count; ++i) mask_of[(size_t)i] = grp->query_tags[qi((size_t)i)];
+        dev_tags.words = grp->tags;
+        dev_tags.n_words = grp->n_tags;
+        dev_tags.mask_of = mask_of.data();
+        dev_tags.match = grp->match;
+        dev_tags.skipped = grp->skipped;
+        dev_tags.resident = grp->resident;
+        dev_tags.n_masks = grp->n_masks;
+    } else if (grp) {
         group_of.resize((size_t)count);
         for (int i = 0; i < count; ++i) group_of[(size_t)i] = grp->query_group[qi((size_t)i)];
         dev_grp.label = grp->label;
@@ -2468,7 +2501,7 @@ int HnswIndex::range_query_device(int n_queries, float range, std::vector<std::v
         dev_grp.group_of = group_of.data();
         dev_grp.skipped = grp->skipped;
     }
-    { Tick t(g_pt.rq_batch); if (!dev_->range_batch(jobs.data(), count, range, &r, allow.bits, allow.n, grp ? &dev_grp : nullptr)) { err = get_dev_error(); return -1; } }
+    { Tick t(g_pt.rq_batch); if (!dev_->range_batch(jobs.data(), count, range, &r, allow.bits, allow.n, grp && !tagged ? &dev_grp : nullptr, tagged ? &dev_tags : nullptr)) { err = get_dev_error(); return -1; } }
     // host threads over the queries: sort each result list; a list holding two equal distances is replayed instead
     auto parallel_for = [&](size_t n, size_t grain, const std::function<void(size_t, size_t)> &body) {
         std::atomic<size_t> next{0};
@@ -2556,6 +2589,51 @@ int HnswIndex::range_query_grouped(const float *queries, int count, int dim, flo
     grp.label = row_group;
     grp.n_label = n_lab;
     grp.query_group = query_group;
+    grp.run = &run;
+    grp.skipped = count - (long long)run.size();
+    const bool on_device = p_.device_traversal && dev_->traversal_fits(1, false, p_.max_edges);
+    if (run.empty() && !on_device) return 0;
+    resident_queries_ = 0; // the resident set is replaced: a later knn_query_resident must not answer for these rows
+    if (!dev_->set_queries(queries, count)) { err = get_dev_error(); return -1; }
+    int rc;
+    if (on_device) rc = range_query_device(count, range, out, err, AllowBits{}, layer, &grp);
+    else rc = range_query_lockstep(run.data(), (int)run.size(), range, out, err, AllowBits{}, layer, &grp);
+    if (rc < 0 && err == kHeapEmptyError) out.assign((size_t)count, {}); // the whole batch fails (Parallel.For rethrows)
+    return rc;
+}
+
+// RangeQuery with a tag mask per query: range_query's filtered call for every distinct mask at once.  The words
+// go to the device as they are; once slots are vacant a copy does, with 0 in the vacant slots (live_tags).  Which masks have a
+// candidate among the graph's ids the device counts (Device::tag_candidates); the words stay there for the sort kernel.
+int HnswIndex::range_query_tagged(const float *queries, int count, int dim, float range, int layer, const uint32_t *row_tags, long long n_row_tags,
+                                  const uint32_t *query_tags, int match, std::vector<std::vector<NodeDist>> &out, std::string &err)
+{
+    out.assign((size_t)std::max(count, 0), {});
+    if (failed(err)) return -1;
+    if (count <= 0) return 0;
+    const char *who = "hnsw_mi355x_range_query_tagged";
+    TagCall tc;
+    if (!tag_args_ok(who, query_tags, count, match, &tc, err)) return -1;
+    if (graph_.entry < 0) return 0; // HNSWIndex.cs:146
+    if (!layer_ok(layer, err)) { err = "System.IndexOutOfRangeException: " + std::string(who) + ": " + err; return -1; }
+    if (!ensure_dim(dim, err)) return -1;
+    std::vector<uint32_t> live;
+    (void)live_tags(row_tags, n_row_tags, live);
+    const long long n_lab = std::min<long long>(n_row_tags, graph_.length); // only the words of graph ids count
+    std::vector<int> cnt;
+    if (!dev_->tag_candidates(row_tags, n_lab, tc.masks, match, cnt)) { err = get_dev_error(); return -1; }
+    // a mask without a candidate: an empty list, and no traversal -- when range >= 0; below zero the filtered call can pop an empty
+    // heap for an empty set too (range_replay.h), so those queries run
+    std::vector<int> run;
+    for (int i = 0; i < count; ++i)
+        if (cnt[(size_t)tc.of[(size_t)i]] > 0 || !(range >= 0.0f)) run.push_back(i);
+    RangeGroupSpec grp;
+    grp.tags = row_tags;
+    grp.n_tags = n_lab;
+    grp.query_tags = query_tags;
+    grp.match = match;
+    grp.resident = n_lab > 0;
+    grp.n_masks = tc.masks.size();
     grp.run = &run;
     grp.skipped = count - (long long)run.size();
     const bool on_device = p_.device_traversal && dev_->traversal_fits(1, false, p_.max_edges);

@@ -78,6 +78,11 @@ public:
     int exact_range_query_grouped(const float *queries, int count, int dim, float range, const int *row_group, long long n_row_group, const int *query_group,
                                   int n_groups, int *counts, std::vector<int> &ids, std::vector<float> &dists, std::string &err);
     void exact_range_grouped_info(uint64_t out[4]) const { if (dev_) dev_->exact_range_grouped_info(out); else out[0] = out[1] = out[2] = out[3] = 0; }
+    // hnsw_mi355x_exact_range_query_tagged: exact_range_query with exact_knn_query_tagged's tag mask per query
+    // (Device::exact_range_tagged); the words of vacant slots are taken out as for that call
+    int exact_range_query_tagged(const float *queries, int count, int dim, float range, const uint32_t *row_tags, long long n_row_tags,
+                                 const uint32_t *query_tags, int match, int *counts, std::vector<int> &ids, std::vector<float> &dists, std::string &err);
+    void exact_range_tagged_info(uint64_t out[9]) const { for (int i = 0; i < 9; ++i) out[i] = 0; if (dev_) dev_->exact_range_tagged_info(out); }
     void exact_range_info(uint64_t out[4]) const { if (dev_) dev_->exact_range_info(out); else out[0] = out[1] = out[2] = out[3] = 0; }
     // hnsw_mi355x_get_info / hnsw_mi355x_connected_component_counts: HNSWIndex.GetInfo() / GetConnectedComponentCounts() for the
     // layers 0 .. top, computed by the primary context from the graph mirror (Device::graph_info / graph_components)
@@ -150,6 +155,15 @@ public:
     int range_query_grouped(const float *queries, int count, int dim, float range, int layer, const int *row_group, long long n_row_group,
                             const int *query_group, int n_groups, std::vector<std::vector<NodeDist>> &out, std::string &err);
     void range_grouped_info(uint64_t out[4]) const { if (dev_) dev_->range_grouped_info(out); else out[0] = out[1] = out[2] = out[3] = 0; }
+    // hnsw_mi355x_range_query_tagged: RangeQuery on `layer` with a tag mask per query -- query i's list is byte for
+    // byte what range_query returns for it with the ids j < n_row_tags whose word row_tags[j] matches query_tags[i] under `match`
+    // (0 any, 1 all) as the allow-set; the empty-heap rule fails the whole call as there.  One device traversal for every mask
+    // (Device::range_batch with RangeTags); hand-backs, and the whole call when the traversal does not run on the device, go the
+    // lock-step way with the tag predicate.  A query whose mask matches no graph id (counted on the device) is answered with an
+    // empty list without a traversal when range >= 0.  Primary context only.  Exclusive lock.
+    int range_query_tagged(const float *queries, int count, int dim, float range, int layer, const uint32_t *row_tags, long long n_row_tags,
+                           const uint32_t *query_tags, int match, std::vector<std::vector<NodeDist>> &out, std::string &err);
+    void range_tagged_info(uint64_t out[6]) const { for (int i = 0; i < 6; ++i) out[i] = 0; if (dev_) dev_->range_tagged_info(out); }
 
     // hnsw_remove (HNSWIndex.Remove, src/HNSWIndex/HNSWIndex.cs:83-102), ids in order.
     int remove(const int *ids, int count, std::string &err);
@@ -285,14 +299,22 @@ private:
     int knn_query_lockstep(const int *which, int count, int k, int *out_ids, float *out_dists, std::string &err, AllowBits allow = AllowBits{},
                            int layer = 0);
     // range_query_grouped's filter: the labels of graph ids, every query's group, and the queries that run (ascending), the others
-    // being answered with an empty list
+    // being answered with an empty list.  range_query_tagged's (tags != nullptr) in the same type: the tag words of graph ids, every
+    // query's mask and the call's mode in the labels' and groups' place; resident: the device counted the masks' candidates on these
+    // words for this call and still holds them.
     struct RangeGroupSpec {
         const int *label = nullptr;
         long long n_label = 0;
         const int *query_group = nullptr;
         const std::vector<int> *run = nullptr;
         long long skipped = 0;
-        AllowPred of(int qi) const { return AllowPred{label, n_label, query_group[qi]}; }
+        const uint32_t *tags = nullptr;
+        long long n_tags = 0;
+        const uint32_t *query_tags = nullptr;
+        int match = 0;
+        bool resident = false;
+        size_t n_masks = 0;
+        AllowPred of(int qi) const { return tags ? AllowPred{tags, n_tags, query_tags[qi], match} : AllowPred{label, n_label, query_group[qi]}; }
     };
     int range_query_lockstep(const int *which, int count, float range, std::vector<std::vector<NodeDist>> &out, std::string &err,
                              AllowBits allow = AllowBits{}, int layer = 0, const RangeGroupSpec *grp = nullptr);

@@ -35,18 +35,30 @@ struct AllowBits {
     long long n = 0;
     bool has(int id) const { return !bits || (id >= 0 && id < n && ((bits[id >> 5] >> (id & 31)) & 1u) != 0u); }
 };
-// RangeQuery's filterFnc in its two shapes (range_replay.h, RangeJob): a bit set, or "this id's label equals this query's group"
-// (range_query_grouped, DESIGN.md 3.23: ids >= n_label, and labels that name another group, are not allowed).  An AllowBits
-// converts to the first shape and answers as it always did.
+// The tagged calls' match rule on the host (TagSet::test on the device): match 0 "any", 1 "all"; the word 0 and the mask 0 match nothing.
+inline bool tag_match_host(uint32_t w, uint32_t m, int match) { return (w & m) != 0u && (match == 0 || (w & m) == m); }
+// RangeQuery's filterFnc in its three shapes (range_replay.h, RangeJob): a bit set, "this id's label equals this query's group"
+// (range_query_grouped, DESIGN.md 3.23: ids >= n_label, and labels that name another group, are not allowed), or "this id's tag
+// word matches this query's mask" (range_query_tagged, DESIGN.md 3.26: (w & m) != 0 for match 0, (w & m) == m != 0 for match 1 --
+// tag_match_host's rule; ids >= n_tags carry no tag).  An AllowBits converts to the first shape and answers as it always did.
 struct AllowPred {
     AllowBits set;
     const int *label = nullptr;
     long long n_label = 0;
     int group = 0;
+    const uint32_t *tags = nullptr;
+    long long n_tags = 0;
+    uint32_t mask = 0;
+    int match = 0;
     AllowPred() = default;
     AllowPred(AllowBits b) : set(b) {}
     AllowPred(const int *labels, long long n, int g) : label(labels), n_label(n), group(g) {}
-    bool has(int id) const { return label ? (id >= 0 && id < n_label && label[id] == group) : set.has(id); }
+    AllowPred(const uint32_t *words, long long n, uint32_t m, int mode) : tags(words), n_tags(n), mask(m), match(mode) {}
+    bool has(int id) const
+    {
+        if (tags) return id >= 0 && id < n_tags && tag_match_host(tags[id], mask, match);
+        return label ? (id >= 0 && id < n_label && label[id] == group) : set.has(id);
+    }
 };
 // Does a set of nbits bits allow any id of a graph of n_graph nodes?  Reads only the words that cover ids < min(nbits, n_graph).
 static inline bool allows_any(const uint32_t *bits, long long nbits, long long n_graph)

@@ -398,6 +398,40 @@ int hnsw_mi355x_range_query_grouped(void *handle, const float *vectors, int coun
  * context, out[1] queries launched, out[2] queries answered without a job because their group holds no graph id, out[3] lists the
  * device left to the host (closures to partition, sort or replay, and hand-backs).  0, or -1 for a NULL argument. */
 int hnsw_mi355x_range_grouped_info(void *handle, uint64_t out[4]);
+/* The two range families with a TAG MASK PER QUERY (row_tags, query_tags and match as for the tagged k-NN calls
+ * above: the word 0, an id past row_tags, a vacant slot and the mask 0 match nothing; at most 65 536 distinct masks).
+ * hnsw_mi355x_range_query_tagged: the graph traversal of hnsw_mi355x_range_query_at_layer, query i filtered by the ids whose word
+ * matches query_tags[i].  Per distinct mask m the lists of the queries with query_tags == m are byte for byte -- ids, distance
+ * bits, the order among equal distances -- what hnsw_mi355x_range_query_at_layer returns for those queries with that set as
+ * allow_bits.  One device traversal serves every mask; only the words of graph ids count.  Where the reference pops an empty heap
+ * (range < 0) the whole call fails as the filtered call does: -1, "System.InvalidOperationException: Heap is empty", every array
+ * NULL and every count 0.  A query whose mask matches no graph id gets an empty list without a traversal when range >= 0 (a NaN
+ * range runs).  Arrays as hnsw_range_query (hnsw_free_results).  Primary context only.  Takes the handle exclusively; replaces
+ * the resident query set.
+ * hnsw_mi355x_exact_range_query_tagged: the flat scan of hnsw_mi355x_exact_range_query over the same candidates -- per distinct
+ * mask the counts, ids, distance bits and ascending (distance, id) order of that call with the mask's ids as allow_bits, its rules
+ * for the radius (NaN, +inf, -0.0, negative), its limit of 2^27 keys per query and its allocation contract unchanged, the lists in
+ * the caller's query order.  A query whose mask has no candidate gets an empty list without a scan.  Always on the primary context.
+ * Both: -1 with a message, every array NULL and every count 0: vectors, out_ids, out_dists, counts or query_tags NULL, dim <= 0
+ * (System.ArgumentNullException); row_tags NULL or n_row_tags < 0 (System.ArgumentException); match other than 0 and 1, more than
+ * 65 536 distinct masks -- the message names the index of the first mask beyond (System.ArgumentOutOfRangeException); for the
+ * traversal a layer outside 0 .. the entry point's top layer on a non-empty index (System.IndexOutOfRangeException).  NULL handle
+ * and count <= 0: 0, nothing written. */
+int hnsw_mi355x_range_query_tagged(void *handle, const float *vectors, int count, int dim, float range, int layer, const uint32_t *row_tags,
+                                   long long n_row_tags, const uint32_t *query_tags, int match, void **out_ids, void **out_dists, int *counts);
+int hnsw_mi355x_exact_range_query_tagged(void *handle, const float *vectors, int count, int dim, float range, const uint32_t *row_tags,
+                                         long long n_row_tags, const uint32_t *query_tags, int match, void **out_ids, void **out_dists, int *counts);
+/* Counters of hnsw_mi355x_range_query_tagged on the primary context since hnsw_mi355x_reset_stats: out[0] calls that reached the
+ * context, out[1] distinct masks of those calls, out[2] queries launched, out[3] queries answered without a job because their mask
+ * matches no graph id, out[4] lists the device left to the host (closures to partition, sort or replay, and hand-backs), out[5]
+ * closures of more than 2 048 entries that the device finished all the same (their allowed entries fit its table and none tie).
+ * 0, or -1 for a NULL argument. */
+int hnsw_mi355x_range_tagged_info(void *handle, uint64_t out[6]);
+/* Counters of hnsw_mi355x_exact_range_query_tagged since hnsw_mi355x_reset_stats: out[0] calls that counted candidates on the
+ * device, out[1] distinct masks of those calls, out[2] queries scanned, out[3] queries answered empty without a scan, out[4] ids
+ * written into candidate lists, out[5] batches of masks scanned, out[6] lists of two or more entries ordered on the device, out[7]
+ * lists ordered on the host, out[8] pieces scanned again with exact capacities.  0, or -1 for a NULL argument. */
+int hnsw_mi355x_exact_range_tagged_info(void *handle, uint64_t out[9]);
 
 /* Measurement aid: hnsw_mi355x_set_queries uploads a query set (count x dim) once; every later
  * hnsw_mi355x_knn_query_resident(k) is hnsw_knn_query on that set with the inputs already in HBM
@@ -736,6 +770,16 @@ int hnswdev_range_search_grouped(void *ctx, const float *queries, int nq, int en
                                  long long n_row_group, const int *query_group, int n_groups, int *out_counts, int *out_flags);
 /* out[0 .. 3] as hnsw_mi355x_range_grouped_info, of this context; zeroed by hnswdev_reset_stats. */
 int hnswdev_range_grouped_info(void *ctx, uint64_t out[4]);
+/* hnswdev_range_search_at_layer with a tag mask per query (range_sort_tagged_kernel behind graph_range_kernel; the words, masks and
+ * match of hnsw_mi355x_range_query_tagged): query i is answered as with the allow-set { id : row_tags[id] matches query_tags[i] };
+ * only the words of graph ids count, and which masks have a candidate among them is counted on the device.  out_counts / out_flags
+ * and the fetch with hnswdev_range_results as hnswdev_range_search_filtered; a query whose mask has no candidate gets count 0,
+ * flag 0 and no job when range >= 0.  -1 with a message: a NULL array, n_row_tags < 0, match other than 0 and 1, more than 65 536
+ * distinct masks, an entry point outside the graph, a layer it does not have, the empty-heap failure. */
+int hnswdev_range_search_tagged(void *ctx, const float *queries, int nq, int entry_point, float range, int layer, const uint32_t *row_tags,
+                                long long n_row_tags, const uint32_t *query_tags, int match, int *out_counts, int *out_flags);
+/* out[0 .. 5] as hnsw_mi355x_range_tagged_info, of this context; zeroed by hnswdev_reset_stats. */
+int hnswdev_range_tagged_info(void *ctx, uint64_t out[6]);
 /* MultiLayerKnnQuery's chains (graph_multilayer_kernel), one job per query: layers min(top, max_layer) .. min_layer with beam k
  * (k >= 2), top = entry_point's level; semantics of hnsw_mi355x_multilayer_knn_query.  Returns the slot count min(top, max_layer) + 1
  * (0 for max_layer == -1), or -1 (max_layer < -1, min_layer < 0, layers_cap below the count).  out_ids / out_dists:
@@ -786,6 +830,15 @@ int hnswdev_exact_range_grouped(void *ctx, const float *queries, int nq, long lo
                                 const int *query_group, int n_groups, int *out_counts);
 /* out[0 .. 3] as hnsw_mi355x_exact_range_grouped_info, of this context; zeroed by hnswdev_reset_stats. */
 int hnswdev_exact_range_grouped_info(void *ctx, uint64_t out[4]);
+/* The flat scan behind hnsw_mi355x_exact_range_query_tagged: hnswdev_exact_range with hnswdev_exact_knn_tagged's tag arguments and
+ * batches of masks (queries == NULL: the resident set, which stays untouched).  out_counts[i]: query i's number of results; the
+ * lists are kept like hnswdev_exact_range's, in the caller's query order whatever the batches were, and fetched with
+ * hnswdev_exact_range_results.  When no query's mask has a candidate nothing is launched.  -1 with a message (a NULL array,
+ * n_rows < 0, n_row_tags < 0, match other than 0 and 1, more than 65 536 distinct masks): nothing is kept and every count is 0. */
+int hnswdev_exact_range_tagged(void *ctx, const float *queries, int nq, long long n_rows, float range, const uint32_t *row_tags, long long n_row_tags,
+                               const uint32_t *query_tags, int match, int *out_counts);
+/* out[0 .. 8] as hnsw_mi355x_exact_range_tagged_info, of this context; zeroed by hnswdev_reset_stats. */
+int hnswdev_exact_range_tagged_info(void *ctx, uint64_t out[9]);
 /* hnsw_mi355x_get_info / hnsw_mi355x_connected_component_counts for ONE layer of the committed graph mirror of a context.
  * live_bits == NULL: every node of the mirror is live; otherwise a bitset of nbits bits in the allow-sets' format, ids >= nbits not
  * live.  A layer's members are the live nodes with level >= layer; an entry that points at no member counts in its owner's out-degree
