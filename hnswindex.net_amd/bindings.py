@@ -148,6 +148,17 @@ lib.hnsw_mi355x_knn_tagged_info.restype = ct.c_int
 lib.hnsw_mi355x_knn_tagged_info.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
 lib.hnsw_mi355x_exact_tagged_info.restype = ct.c_int
 lib.hnsw_mi355x_exact_tagged_info.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
+# query by stored id
+_BY_ID_INFO = ("calls", "traversed", "handbacks", "scanned", "rows_gathered", "self_skipped")   # hnswdev_by_id_info's out[0 .. 5]
+_BY_ID_CHUNK = 65536   # ids per call of Index.exact_knn_graph: bounds the gathered query set
+lib.hnsw_mi355x_get_vectors.restype = ct.c_int
+lib.hnsw_mi355x_get_vectors.argtypes = [ct.c_void_p, _I, ct.c_int, _F]
+lib.hnsw_mi355x_knn_query_by_id.restype = ct.c_int
+lib.hnsw_mi355x_knn_query_by_id.argtypes = [ct.c_void_p, _I, ct.c_int, ct.c_int, ct.c_int, _I, _F]
+lib.hnsw_mi355x_exact_knn_query_by_id.restype = ct.c_int
+lib.hnsw_mi355x_exact_knn_query_by_id.argtypes = [ct.c_void_p, _I, ct.c_int, ct.c_int, _U32, ct.c_longlong, _I, _F]
+lib.hnsw_mi355x_by_id_info.restype = ct.c_int
+lib.hnsw_mi355x_by_id_info.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
 lib.hnsw_mi355x_knn_query_grouped.restype = ct.c_int
 lib.hnsw_mi355x_knn_query_grouped.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_int, ct.c_int, ct.c_int, _I, ct.c_longlong, _I, ct.c_int, _I, _F]
 _RANGE_GROUPED_INFO = ("calls", "launched", "skipped", "host_finished")   # hnswdev_range_grouped_info's out[0 .. 3]
@@ -339,6 +350,14 @@ lib.hnswdev_exact_knn_tagged.restype = ct.c_int
 lib.hnswdev_exact_knn_tagged.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_longlong, ct.c_int, _U32, ct.c_longlong, _U32, ct.c_int, _I, _F]
 lib.hnswdev_exact_tagged_info.restype = ct.c_int
 lib.hnswdev_exact_tagged_info.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
+lib.hnswdev_gather_rows.restype = ct.c_int
+lib.hnswdev_gather_rows.argtypes = [ct.c_void_p, _I, ct.c_int, _F]
+lib.hnswdev_knn_search_by_id.restype = ct.c_int
+lib.hnswdev_knn_search_by_id.argtypes = [ct.c_void_p, _I, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int, _I, _F, _I]
+lib.hnswdev_exact_knn_by_id.restype = ct.c_int
+lib.hnswdev_exact_knn_by_id.argtypes = [ct.c_void_p, _I, ct.c_int, ct.c_longlong, ct.c_int, _U32, ct.c_longlong, _I, _F]
+lib.hnswdev_by_id_info.restype = ct.c_int
+lib.hnswdev_by_id_info.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
 lib.hnswdev_tag_list_ms.restype = ct.c_int
 lib.hnswdev_tag_list_ms.argtypes = [ct.c_void_p, ct.POINTER(ct.c_double)]
 lib.hnswdev_knn_search_grouped.restype = ct.c_int
@@ -510,6 +529,14 @@ def allow_bits(allowed) -> Tuple[npt.NDArray[np.uint32], int]:
     padded[:nbits] = mask
     words = np.packbits(padded.reshape(-1, 32), axis=1, bitorder="little").view("<u4").ravel().astype(np.uint32)
     return np.ascontiguousarray(words), nbits
+
+
+def _id_list(ids) -> npt.NDArray[np.int32]:
+    """The id list of a by-id call: a contiguous int32 vector (a scalar is a list of one)."""
+    a = np.asarray(ids)
+    if a.size and a.dtype.kind not in "iu":
+        raise TypeError("ids must be integers")
+    return np.ascontiguousarray(a.reshape(-1), dtype=np.int32)
 
 
 def _words_arg(words):
@@ -833,6 +860,73 @@ class Index:
         if self._h:
             lib.hnsw_mi355x_exact_tagged_info(self._h, out)
         return dict(zip(_EXACT_TAGGED_INFO, (int(v) for v in out)))
+
+    # ---- query by stored id ----
+    def _by_id_list(self, ids, who: str) -> npt.NDArray[np.int32]:
+        a = _id_list(ids)
+        if a.size and not self._h:   # (an index nothing was added to has no native handle yet, and no live id)
+            raise RuntimeError(f"System.Collections.Generic.KeyNotFoundException: {who}: ids[0] = {int(a[0])} is not a live id")
+        return a
+
+    def get_vectors(self, ids) -> npt.NDArray[np.float32]:
+        """float32[n, dim]: the stored rows of `ids` (hnsw_mi355x_get_vectors), gathered on the device -- the values distances are
+        measured on: float32 rows as added, half-precision rows rounded and widened, int8 rows q * scale.  ids may repeat and come
+        in any order; one that is not live: RuntimeError naming it."""
+        a = self._by_id_list(ids, "hnsw_mi355x_get_vectors")
+        out = np.empty((a.size, self.dim), dtype=np.float32)
+        if a.size and lib.hnsw_mi355x_get_vectors(self._h, a.ctypes.data_as(_I), a.size, out.ctypes.data_as(_F)) < 0:
+            raise RuntimeError(last_error())
+        return out
+
+    def items(self) -> npt.NDArray[np.float32]:
+        """HNSWIndex.Items(): the stored rows of every live id, in ids() order (get_vectors(ids()))."""
+        return self.get_vectors(self.ids())
+
+    def knn_query_by_id(self, ids, k: int, layer: int = 0) -> Tuple[npt.NDArray[np.int32], npt.NDArray[np.float32]]:
+        """"What is near item i": knn_query for the stored rows of `ids`, each answered from every id but its own, without a vector
+        crossing the host boundary (hnsw_mi355x_knn_query_by_id).  Row i is byte for byte
+        knn_query(get_vectors([ids[i]]), k, allowed=<every id except ids[i]>, layer=layer); a duplicate of the row under another id is
+        an ordinary candidate.  An id that is not live: RuntimeError naming it."""
+        a = self._by_id_list(ids, "hnsw_mi355x_knn_query_by_id")
+        out_ids = np.full((a.size, max(k, 0)), -1, dtype=np.int32)
+        dists = np.full((a.size, max(k, 0)), np.nan, dtype=np.float32)
+        if a.size and lib.hnsw_mi355x_knn_query_by_id(self._h, a.ctypes.data_as(_I), a.size, k, int(layer), out_ids.ctypes.data_as(_I),
+                                                      dists.ctypes.data_as(_F)) < 0:
+            raise RuntimeError(last_error())
+        return out_ids, dists
+
+    def exact_knn_query_by_id(self, ids, k: int, allowed=None) -> Tuple[npt.NDArray[np.int32], npt.NDArray[np.float32]]:
+        """exact_knn_query for the stored rows of `ids` (hnsw_mi355x_exact_knn_query_by_id): row i equals
+        exact_knn_query(get_vectors([ids[i]]), k, allowed=<allowed, or every live id, minus ids[i]>) -- ascending by (distance, id),
+        padded where the candidates run out (n live items give at most n - 1 results).  1 <= k <= 1024."""
+        a = self._by_id_list(ids, "hnsw_mi355x_exact_knn_query_by_id")
+        out_ids = np.full((a.size, max(k, 0)), -1, dtype=np.int32)
+        dists = np.full((a.size, max(k, 0)), np.nan, dtype=np.float32)
+        words, nbits = allow_bits(allowed) if allowed is not None else (None, 0)
+        words, wp = _words_arg(words) if allowed is not None else (None, None)
+        if a.size and lib.hnsw_mi355x_exact_knn_query_by_id(self._h, a.ctypes.data_as(_I), a.size, k, wp, nbits, out_ids.ctypes.data_as(_I),
+                                                            dists.ctypes.data_as(_F)) < 0:
+            raise RuntimeError(last_error())
+        return out_ids, dists
+
+    def exact_knn_graph(self, k: int, ids=None) -> Tuple[npt.NDArray[np.int32], npt.NDArray[np.float32]]:
+        """The exact k-NN graph of the index: exact_knn_query_by_id over `ids` (None: every live id ascending), (int32[n, k],
+        float32[n, k]).  Row i never holds ids[i].  The ids go down in pieces of 65 536, so the gathered query set stays bounded;
+        inside a piece the scan picks its rounds as for any call."""
+        a = np.sort(self.ids()) if ids is None else _id_list(ids)
+        out_ids = np.full((a.size, max(k, 0)), -1, dtype=np.int32)
+        dists = np.full((a.size, max(k, 0)), np.nan, dtype=np.float32)
+        for lo in range(0, a.size, _BY_ID_CHUNK):
+            out_ids[lo:lo + _BY_ID_CHUNK], dists[lo:lo + _BY_ID_CHUNK] = self.exact_knn_query_by_id(a[lo:lo + _BY_ID_CHUNK], k)
+        return out_ids, dists
+
+    def by_id_info(self) -> dict:
+        """Counters of the by-id calls since reset_stats (hnsw_mi355x_by_id_info): calls that reached a device, queries traversed on
+        the device, of those handed back to the host, queries scanned, rows gathered, pairs the scan skipped as the query's own."""
+        out = (ct.c_uint64 * 6)()
+        if self._h:
+            lib.hnsw_mi355x_by_id_info(self._h, out)
+        return dict(zip(_BY_ID_INFO, (int(v) for v in out)))
 
     def exact_range_query(self, queries: npt.ArrayLike, radius: float,
                           allowed=None) -> Tuple[List[npt.NDArray[np.int32]], List[npt.NDArray[np.float32]]]:
@@ -1310,6 +1404,43 @@ class DeviceBackend:
         out = np.empty((n, self.dim), dtype=np.float32)
         self._check(lib.hnswdev_download_rows(self._ctx, first_id, n, out.ctypes.data_as(_F)))
         return out
+
+    def gather_rows(self, ids):
+        """hnswdev_gather_rows: float32[n, dim], the uploaded rows of `ids` in the order asked (download_rows' values); an id outside
+        the uploaded rows gives zeros."""
+        a = _id_list(ids)
+        out = np.empty((a.size, self.dim), dtype=np.float32)
+        self._check(lib.hnswdev_gather_rows(self._ctx, a.ctypes.data_as(_I), a.size, out.ctypes.data_as(_F)))
+        return out
+
+    def knn_search_by_id(self, ids, entry_point: int, k_beam: int, k_out: int, layer: int = 0):
+        """hnswdev_knn_search_by_id: knn_search whose query i is the uploaded row ids[i], answered from every graph id but ids[i].
+        (ids, dists, flags)."""
+        a = _id_list(ids)
+        out_ids = np.empty((a.size, k_out), dtype=np.int32)
+        d = np.empty((a.size, k_out), dtype=np.float32)
+        flags = np.empty(a.size, dtype=np.int32)
+        self._check(lib.hnswdev_knn_search_by_id(self._ctx, a.ctypes.data_as(_I), a.size, int(entry_point), int(k_beam), int(k_out), int(layer),
+                                                 out_ids.ctypes.data_as(_I), d.ctypes.data_as(_F), flags.ctypes.data_as(_I)))
+        return out_ids, d, flags
+
+    def exact_knn_by_id(self, ids, k: int, n_rows=None, allowed=None):
+        """hnswdev_exact_knn_by_id: exact_knn whose query i is the uploaded row ids[i] and whose candidates are exact_knn's minus
+        ids[i].  (ids, dists)."""
+        a = _id_list(ids)
+        out_ids = np.empty((a.size, k), dtype=np.int32)
+        d = np.empty((a.size, k), dtype=np.float32)
+        words, nbits = allow_bits(allowed) if allowed is not None else (None, 0)
+        words, wp = _words_arg(words) if allowed is not None else (None, None)
+        self._check(lib.hnswdev_exact_knn_by_id(self._ctx, a.ctypes.data_as(_I), a.size, (1 << 62) if n_rows is None else int(n_rows), int(k), wp, nbits,
+                                                out_ids.ctypes.data_as(_I), d.ctypes.data_as(_F)))
+        return out_ids, d
+
+    def by_id_info(self) -> dict:
+        """Counters of the by-id calls since reset_stats (hnswdev_by_id_info)."""
+        out = (ct.c_uint64 * 6)()
+        self._check(lib.hnswdev_by_id_info(self._ctx, out))
+        return dict(zip(_BY_ID_INFO, (int(v) for v in out)))
 
     def set_queries(self, queries):
         """Uploads the query set of a batch of searches once; records name queries by row index."""

@@ -464,6 +464,27 @@ public:
     // set (nq of its rows); otherwise the queries are staged by set_queries' code into a buffer of the scan's own and the
     // resident set stays what it was.  1 <= k <= 1024.  Synchronous.
     bool exact_knn(const float *queries, int nq, long long n_rows, int k, const uint32_t *allow_bits, long long nbits, int *out_ids, float *out_d);
+    // ---- query by stored id --------------------------------------------------------------------------------
+    // hnswdev_gather_rows: out[i] = the stored row ids[i] as dim floats -- hnswdev_download_rows' values for the row kind (f32: a
+    // copy; f16: the rounded row widened; int8: q * scale), gathered on the device in one launch (gather_rows_kernel) and copied back
+    // in one copy.  ids may repeat, in any order; an id outside the uploaded rows gives a row of zeros.  n <= 0: nothing is written.
+    bool gather_rows(const int *ids, int n, float *out);
+    // The resident query set made of stored rows: resident query i is what set_queries makes of gather_rows' row ids[i] (int8:
+    // quantised again by quantize_rows_kernel; cosine: norms by row_sqrtnorm_kernel), built on the device.  The ids stay on the
+    // device beside the set, for search_self, until the resident set is replaced.
+    bool set_queries_by_id(const int *ids, int nq);
+    // KnnQuery for the resident queries set_queries_by_id left (graph_search_self_kernel): query i is answered from every graph id
+    // but ids[i] -- byte for byte what search_filtered returns for it with that allow-set.  out_flag as search_filtered.
+    bool search_self(int nq, int entry, int entry_layer, int k, int k_out, int *out_ids, float *out_d, int *out_flag, int search_layer = 0);
+    // hnswdev_knn_search_by_id: set_queries_by_id + search_self on the committed graph
+    bool knn_search_by_id(const int *ids, int nq, int entry_point, int k_beam, int k_out, int *out_ids, float *out_d, int *out_flag, int layer = 0);
+    // hnswdev_exact_knn_by_id: exact_knn whose query i is the stored row ids[i] (gathered into the scan's own query buffer: the
+    // resident set stays what it was) and whose candidates are exact_knn's minus ids[i] -- the scan's sink drops the pair
+    // (exact_scan_kernel<M, ExactTopKSelf>), which is not counted in exact_evals.  An id outside the uploaded rows is an error.
+    bool exact_knn_by_id(const int *ids, int nq, long long n_rows, int k, const uint32_t *allow_bits, long long nbits, int *out_ids, float *out_d);
+    // by-id calls (search_self, exact_knn_by_id), queries traversed on the device, hand-backs, queries scanned, rows gathered, pairs
+    // skipped as self -- on this context
+    void by_id_info(uint64_t out[6]) const { for (int i = 0; i < 6; ++i) out[i] = bi_info_[i]; }
     // hnswdev_exact_range: exact_knn's candidates, queries and distances; per query EVERY candidate with
     // distance <= range (the float compare), ascending by (distance, id), of any number.  out_counts[i]: query i's; the lists stay
     // in the context, concatenated in query order, until the next exact_range and are copied out by exact_range_results (the
@@ -695,6 +716,14 @@ private:
     uint64_t xt_info_[6] = {0, 0, 0, 0, 0, 0};
     double xt_list_ms_ = 0.0;
     bool tag_counts(const unsigned *row_tags, long long n, const std::vector<uint32_t> &masks, int match, std::vector<int> &cnt);
+    DevBuf<int> s_self_;         // by-id calls: the ids whose rows are the resident queries (valid while q_by_id_)
+    DevBuf<int> x_self_;         // ... the ids of exact_knn_by_id's queries, and gather_rows' ids
+    bool q_by_id_ = false;       // the resident set was made by set_queries_by_id and s_self_ holds its n_queries_ ids
+    uint64_t bi_info_[6] = {0, 0, 0, 0, 0, 0};
+    bool query_room(int nq);
+    bool upload_ids(const int *ids, int n, DevBuf<int> &d_ids);
+    bool gather_launch(const int *d_ids, long long n, float *out);
+    bool gather_queries(const int *ids, int n, DevBuf<int> &d_ids, float *d_q, double *d_qsn);
     DevBuf<int> x_ids_;                 // exact_knn: the call's ascending id list (exact_compact_kernel)
     DevBuf<long long> x_boff_;          // ... set bits in front of each block of bitset words
     DevBuf<unsigned long long> x_lists_; // ... the per-(query, chunk) lists of a round: at most 1 GiB, allocated by the first call and kept
@@ -704,7 +733,8 @@ private:
     DevBuf<double> x_q_sn_;
     bool exact_queries(const char *who, const float *queries, int nq, const float **d_q, const double **d_qsn);
     bool exact_id_list(const uint32_t *allow_bits, long long n_allow, long long *m);
-    bool exact_knn_rounds(const float *d_q, const double *d_qsn, int nq, const int *d_idlist, long long m, int k, int *out_ids, float *out_d, int *d_keep_ids);
+    bool exact_knn_rounds(const float *d_q, const double *d_qsn, int nq, const int *d_idlist, long long m, int k, int *out_ids, float *out_d, int *d_keep_ids,
+                          const int *d_self = nullptr);
     bool exact_copy_out(void *dst, const void *src, size_t bytes);
     ExactStart exact_scan_begin(const char *who, const float *queries, int nq, long long n_rows, const uint32_t *allow_bits, long long nbits, ExactScanInput *in);
     bool exact_scan_args(const float *d_q, const double *d_qsn, long long off, int nr, int qt, int piece, ExactScanArgs *a);

@@ -656,20 +656,26 @@ bool Device::staged_upload(float *dst, const float *src, size_t bytes)
     return true;
 }
 
+// Room for a resident set of nq queries.  Nothing is kept: the old set goes first; the new one becomes the member once it is whole.
+bool Device::query_room(int nq)
+{
+    if (nq <= q_capacity()) return true;
+    if (!reset_all(d_queries_, d_q_sn_)) return false;
+    const size_t cap = (size_t)std::max<long long>(nq, 1024);
+    DevBuf<float> nqbuf;
+    DevBuf<double> nsn;
+    if (!nqbuf.grow(cap * pitch_) || (metric_ == M_COS && !nsn.grow(cap))) return false;
+    d_queries_ = std::move(nqbuf);
+    d_q_sn_ = std::move(nsn);
+    return true;
+}
+
 bool Device::set_queries(const float *queries, int nq)
 {
     if (nq < 0 || (nq > 0 && !queries)) { set_dev_error("set_queries: bad argument"); return false; }
-    if (!bind()) return false;
-    if (nq > q_capacity()) { // (nothing is kept: the old set goes first; the new one becomes the member once it is whole)
-        if (!reset_all(d_queries_, d_q_sn_)) return false;
-        const size_t cap = (size_t)std::max<long long>(nq, 1024);
-        DevBuf<float> nqbuf;
-        DevBuf<double> nsn;
-        if (!nqbuf.grow(cap * pitch_) || (metric_ == M_COS && !nsn.grow(cap))) return false;
-        d_queries_ = std::move(nqbuf);
-        d_q_sn_ = std::move(nsn);
-    }
+    if (!bind() || !query_room(nq)) return false;
     n_queries_ = nq;
+    q_by_id_ = false;
     if (nq == 0) return true;
     {
         const size_t bytes = (size_t)nq * dim_ * sizeof(float);
@@ -898,6 +904,7 @@ bool Device::adopt_queries(Device *src, long long first, long long n, long long 
         HIP_OK(hipStreamSynchronize(st));
     }
     n_queries_ = total;
+    q_by_id_ = false; // (the ids of a by-id set stay with the context that gathered it)
     return true;
 }
 
@@ -1027,6 +1034,7 @@ void Device::reset_stats()
     for (uint64_t &v : xrt_info_) v = 0;
     xg_list_ms_ = 0.0;
     for (uint64_t &v : kt_info_) v = 0;
+    for (uint64_t &v : bi_info_) v = 0;
     for (uint64_t &v : xt_info_) v = 0;
     xt_list_ms_ = 0.0;
     for (uint64_t &v : gi_info_) v = 0;
@@ -3105,9 +3113,11 @@ bool Device::exact_queries(const char *who, const float *queries, int nq, const 
         if (tail_.n > 0) { set_dev_error(std::string(who) + ": a streamed query set is still being uploaded"); return false; }
         std::swap(d_queries_, x_queries_); std::swap(d_q_sn_, x_q_sn_);
         const long long kept = n_queries_;
+        const bool kept_by_id = q_by_id_;
         const bool ok = set_queries(queries, nq);
         std::swap(d_queries_, x_queries_); std::swap(d_q_sn_, x_q_sn_);
         n_queries_ = kept;
+        q_by_id_ = kept_by_id;
         if (!ok) return false;
         *d_q = x_queries_; *d_qsn = x_q_sn_;
     } else if (nq > n_queries_ || tail_.n > 0) {
@@ -3230,7 +3240,9 @@ bool Device::exact_knn(const float *queries, int nq, long long n_rows, int k, co
 // The rounds of a top-k flat scan: nq queries on the device (d_q, pitch_ words each; d_qsn their cosine norms or nullptr) against the
 // m entries of the id list d_ids (nullptr: the identity).  out_d may be nullptr; d_keep_ids: nullptr, or nq x k ints on the device
 // that receive the ids as well (graph_repair_round's candidates stay there for the proposal kernel).
-bool Device::exact_knn_rounds(const float *d_q, const double *d_qsn, int nq, const int *d_idlist, long long m, int k, int *out_ids, float *out_d, int *d_keep_ids)
+// d_self: nullptr, or nq ids on the device -- query i is the stored row d_self[i], which is no candidate of it (ExactTopKSelf).
+bool Device::exact_knn_rounds(const float *d_q, const double *d_qsn, int nq, const int *d_idlist, long long m, int k, int *out_ids, float *out_d, int *d_keep_ids,
+                              const int *d_self)
 {
     hipStream_t st = S(stream_);
     const ExactPlan p = exact_plan(nq, m, k, pitch_, num_cu_);
@@ -3250,7 +3262,8 @@ bool Device::exact_knn_rounds(const float *d_q, const double *d_qsn, int nq, con
         float *d_d = reinterpret_cast<float *>(x_out_.get() + (size_t)p.round * k);
         const auto enqueue = [&]() -> bool {
             hipError_t e = hipSuccess;
-            with_metric(metric_, [&](auto mt) { e = exact_scan_launch<mt>(a, tiles, p.lds, st); });
+            if (d_self) with_metric(metric_, [&](auto mt) { e = exact_self_scan_launch<mt>(a, ExactTopKSelf{d_self + off}, tiles, p.lds, st); });
+            else with_metric(metric_, [&](auto mt) { e = exact_scan_launch<mt>(a, tiles, p.lds, st); });
             HIP_OK(e);
             HIP_OK(exact_merge_launch(x_lists_, p.n_chunks, k, nr, d_ids, d_d, st));
             return true;
@@ -4501,10 +4514,7 @@ bool Device::graph_repair_round(int layer, const uint32_t *live_bits, long long 
 
     // the rows of U as the scan's query set: what set_queries makes of hnswdev_download_rows' rows, without the host
     if (!rp_q_.grow((size_t)n_u * pitch_) || (metric_ == M_COS && !rp_qsn_.grow((size_t)n_u)) || (metric_ == M_I8 && !q_stage_.grow((size_t)n_u * (size_t)dim_))) return false;
-    const int kind = metric_ == M_I8 ? 2 : metric_f16(metric_) ? 1 : 0;
-    hipLaunchKernelGGL(graph_repair_gather_kernel, dim3(graph_info_blocks(n_u * dim_, num_cu_)), dim3(kRepairBlock), 0, st, d_rows_.get(), row_pitch_, n_rows_hw_, kind,
-                       rp_uids_.get(), n_u, dim_, metric_ == M_I8 ? q_stage_.get() : rp_q_.get());
-    HIP_OK(hipGetLastError());
+    if (!gather_launch(rp_uids_.get(), n_u, metric_ == M_I8 ? q_stage_.get() : rp_q_.get())) return false;
     if (metric_ == M_I8) {
         hipLaunchKernelGGL(quantize_rows_kernel, dim3((unsigned)((n_u + 3) / 4)), dim3(256), 0, st, q_stage_, dim_, (int)n_u, rp_q_, 0LL, pitch_);
         HIP_OK(hipGetLastError());
@@ -4557,6 +4567,149 @@ int Device::graph_repair_propose(int layer, const uint32_t *live_bits, long long
         memcpy(out_codes, r.codes, sizeof(int) * n * C);
     }
     return 0;
+}
+
+// ---- query by stored id: rows back out, and stored rows as queries without crossing the host boundary --------
+// n ids from the host to d_ids, enqueued: through the pinned stage (the caller synchronises before it uses the stage again), or in
+// pieces as query sets go up.
+bool Device::upload_ids(const int *ids, int n, DevBuf<int> &d_ids)
+{
+    const size_t bytes = 4u * (size_t)n;
+    if (!d_ids.grow((size_t)n)) return false;
+    if (bytes >= (4u << 20)) return staged_upload(reinterpret_cast<float *>(d_ids.get()), reinterpret_cast<const float *>(ids), bytes);
+    void *hs = pinned_stage(bytes);
+    if (!hs) return false;
+    memcpy(hs, ids, bytes);
+    HIP_OK(hipMemcpyAsync(d_ids, hs, bytes, hipMemcpyHostToDevice, S(stream_)));
+    return true;
+}
+
+// gather_rows_kernel over n ids on the device: out[i] = the stored row d_ids[i] as dim_ floats, zeros for an id outside the uploaded rows
+bool Device::gather_launch(const int *d_ids, long long n, float *out)
+{
+    const int kind = metric_ == M_I8 ? 2 : metric_f16(metric_) ? 1 : 0;
+    hipLaunchKernelGGL(gather_rows_kernel, dim3(graph_info_blocks(n * dim_, num_cu_)), dim3(kGatherBlock), 0, S(stream_), d_rows_.get(), row_pitch_, n_rows_hw_, kind, d_ids, n,
+                       dim_, out);
+    HIP_OK(hipGetLastError());
+    return true;
+}
+
+bool Device::gather_rows(const int *ids, int n, float *out)
+{
+    if (n <= 0) return true;
+    if (!ids || !out) { set_dev_error("gather_rows: null argument"); return false; }
+    if (!bind() || !q_stage_.grow((size_t)n * (size_t)dim_) || !upload_ids(ids, n, x_self_) || !gather_launch(x_self_, n, q_stage_)) return false;
+    HIP_OK(hipMemcpyAsync(out, q_stage_, (size_t)n * dim_ * sizeof(float), hipMemcpyDeviceToHost, S(stream_)));
+    HIP_OK(hipStreamSynchronize(S(stream_)));
+    bi_info_[4] += (uint64_t)n;
+    return true;
+}
+
+// The stored rows of ids[0, n) as a query set in d_q (pitch_ words a query; d_qsn: the cosine norms): the steps set_queries takes
+// for rows that come from the host, on rows that are gathered on the device.  The ids stay in d_ids.  The stream is idle and the
+// pinned stage free when this returns.
+bool Device::gather_queries(const int *ids, int n, DevBuf<int> &d_ids, float *d_q, double *d_qsn)
+{
+    hipStream_t st = S(stream_);
+    if (metric_ == M_I8 && !q_stage_.grow((size_t)n * (size_t)dim_)) return false;
+    if (!upload_ids(ids, n, d_ids) || !gather_launch(d_ids, n, metric_ == M_I8 ? q_stage_.get() : d_q)) return false;
+    if (metric_ == M_I8) {
+        hipLaunchKernelGGL(quantize_rows_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, q_stage_, dim_, n, d_q, 0LL, pitch_);
+        HIP_OK(hipGetLastError());
+    }
+    if (metric_ == M_COS) {
+        hipLaunchKernelGGL(row_sqrtnorm_kernel, dim3((unsigned)(((long long)n * 8 + 255) / 256)), dim3(256), 0, st, d_q, pitch_, 0LL, n, d_qsn);
+        HIP_OK(hipGetLastError());
+    }
+    HIP_OK(hipStreamSynchronize(st));
+    bi_info_[4] += (uint64_t)n;
+    return true;
+}
+
+// The ids of a by-id call that are no uploaded row: "" when there is none, else the message that names the first.
+static std::string by_id_rows_error(const char *who, const int *ids, int n, long long n_rows)
+{
+    for (int i = 0; i < n; ++i)
+        if (ids[i] < 0 || ids[i] >= n_rows) return std::string(who) + ": ids[" + std::to_string(i) + "] = " + std::to_string(ids[i]) + " is no uploaded row";
+    return std::string();
+}
+
+bool Device::set_queries_by_id(const int *ids, int nq)
+{
+    if (nq < 0 || (nq > 0 && !ids)) { set_dev_error("set_queries_by_id: bad argument"); return false; }
+    if (tail_.n > 0) { set_dev_error("set_queries_by_id: a streamed query set is still being uploaded"); return false; }
+    if (const std::string why = by_id_rows_error("set_queries_by_id", ids, nq, n_rows_hw_); !why.empty()) { set_dev_error(why); return false; }
+    if (!bind() || !query_room(nq)) return false;
+    n_queries_ = nq;
+    q_by_id_ = false;
+    if (nq == 0) return true;
+    if (!gather_queries(ids, nq, s_self_, d_queries_, d_q_sn_)) { n_queries_ = 0; return false; }
+    q_by_id_ = true;
+    return true;
+}
+
+// KnnQuery by stored id (graph_search_self_kernel): search_filtered's launch with the ids set_queries_by_id left in s_self_ where
+// the allow words were -- nothing goes up for the filter.
+bool Device::search_self(int nq, int entry, int entry_layer, int k, int k_out, int *out_ids, float *out_d, int *out_flag, int search_layer)
+{
+    if (nq <= 0) return true;
+    const PredicateCall c{"search_self", nq, entry, entry_layer, search_layer, k, k_out, out_ids, out_d, out_flag};
+    const auto own_rules = [&] { return std::string(q_by_id_ ? "" : "search_self: the resident queries were not set by id (set_queries_by_id)"); };
+    if (!predicate_call_ok(c, own_rules)) return false;
+    const auto p = plan_predicate_search(c, [](auto m, auto h) { return &graph_search_self_kernel<m, h>; });
+    if (!p.ok) return false;
+    const auto upload = [](char *) { return true; };
+    const auto every_query = [](long long, int nj) { return nj; };
+    const auto filter = [&](long long off) { return std::make_tuple(static_cast<const int *>(s_self_.get()) + off); };
+    if (!run_predicate_search(c, p, 0, upload, every_query, filter)) return false;
+    bi_info_[0] += 1;
+    bi_info_[1] += (uint64_t)nq;
+    bi_info_[2] += count_search_overflows(c);
+    return true;
+}
+
+bool Device::knn_search_by_id(const int *ids, int nq, int entry_point, int k_beam, int k_out, int *out_ids, float *out_d, int *out_flag, int layer)
+{
+    if (nq <= 0) return true;
+    if (!ids || !out_ids || !out_d || !out_flag) { set_dev_error("knn_search_by_id: null argument"); return false; }
+    int top;
+    const bool args_ok = k_out >= 1 && k_beam >= k_out; // (false: "knn_search_by_id: bad argument", in abi_entry's place for it)
+    if (!abi_begin("knn_search_by_id", nullptr, 0, entry_point, layer, &top, args_ok)) return false; // (no query goes up: the set is gathered below)
+    if (const std::string why = by_id_rows_error("knn_search_by_id", ids, nq, std::min<long long>(n_rows_hw_, g_n_)); !why.empty()) { set_dev_error(why); return false; }
+    return set_queries_by_id(ids, nq) && search_self(nq, entry_point, top, k_beam, k_out, out_ids, out_d, out_flag, layer);
+}
+
+// The flat scan by stored id: exact_knn with the queries gathered into the scan's own buffer and ExactTopKSelf as the sink.  The id
+// list, the chunks, the rounds and the merge are exact_knn's.
+bool Device::exact_knn_by_id(const int *ids, int nq, long long n_rows, int k, const uint32_t *allow_bits, long long nbits, int *out_ids, float *out_d)
+{
+    if (nq <= 0) return true;
+    if (!ids || !out_ids || !out_d || k < 1 || n_rows < 0 || (allow_bits && nbits < 0)) { set_dev_error("exact_knn_by_id: bad argument"); return false; }
+    if (k > kExactMaxK) { set_dev_error("exact_knn_by_id: k = " + std::to_string(k) + " is above the limit of " + std::to_string(kExactMaxK)); return false; }
+    if (const std::string why = by_id_rows_error("exact_knn_by_id", ids, nq, n_rows_hw_); !why.empty()) { set_dev_error(why); return false; }
+    if (!allow_bits) nbits = 0;
+    const long long n = std::min(n_rows, n_rows_hw_), n_allow = allow_bits ? std::min(nbits, n) : n;
+    if (n_allow <= 0 || (allow_bits && !allows_any(allow_bits, nbits, n))) { // no candidate: padding, no launch
+        pad_results(out_ids, out_d, (size_t)nq * (size_t)k);
+        return true;
+    }
+    if (!bind()) return false;
+    const size_t cap = (size_t)std::max(nq, 1024);
+    if (!x_queries_.grow((size_t)nq * pitch_, cap * pitch_) || (metric_ == M_COS && !x_q_sn_.grow((size_t)nq, cap))) return false;
+    const double *d_qsn = metric_ == M_COS ? x_q_sn_.get() : nullptr;
+    if (!gather_queries(ids, nq, x_self_, x_queries_, x_q_sn_)) return false;
+    long long m = 0;
+    if (!exact_id_list(allow_bits, n_allow, &m)) return false;
+    uint64_t skipped = 0; // the queries whose own id is a candidate: one pair each
+    for (int i = 0; i < nq; ++i) {
+        const long long id = ids[i];
+        skipped += (uint64_t)(id < n_allow && (!allow_bits || ((allow_bits[id >> 5] >> (id & 31)) & 1u)));
+    }
+    if (!exact_knn_rounds(x_queries_, d_qsn, nq, allow_bits ? x_ids_.get() : nullptr, m, k, out_ids, out_d, nullptr, x_self_)) return false;
+    bi_info_[0] += 1;
+    bi_info_[3] += (uint64_t)nq;
+    bi_info_[5] += skipped;
+    return true;
 }
 
 // ---- synchronous conveniences behind the C ABI ---------------------------------------
@@ -4849,6 +5002,31 @@ DEV_API int hnswdev_exact_knn(void *ctx, const float *queries, int nq, long long
 {
     CTX_OR_FAIL();
     return d->exact_knn(queries, nq, n_rows, k, allow_bits, nbits, out_ids, out_dists) ? 0 : -1;
+}
+// query by stored id
+DEV_API int hnswdev_gather_rows(void *ctx, const int *ids, int n, float *out)
+{
+    CTX_OR_FAIL();
+    return d->gather_rows(ids, n, out) ? 0 : -1;
+}
+DEV_API int hnswdev_knn_search_by_id(void *ctx, const int *ids, int nq, int entry_point, int k_beam, int k_out, int layer, int *out_ids, float *out_dists,
+                                     int *out_flags)
+{
+    CTX_OR_FAIL();
+    return d->knn_search_by_id(ids, nq, entry_point, k_beam, k_out, out_ids, out_dists, out_flags, layer) ? 0 : -1;
+}
+DEV_API int hnswdev_exact_knn_by_id(void *ctx, const int *ids, int nq, long long n_rows, int k, const uint32_t *allow_bits, long long nbits, int *out_ids,
+                                    float *out_dists)
+{
+    CTX_OR_FAIL();
+    return d->exact_knn_by_id(ids, nq, n_rows, k, allow_bits, nbits, out_ids, out_dists) ? 0 : -1;
+}
+DEV_API int hnswdev_by_id_info(void *ctx, uint64_t out[6])
+{
+    CTX_OR_FAIL();
+    if (!out) return -1;
+    d->by_id_info(out);
+    return 0;
 }
 DEV_API int hnswdev_exact_range(void *ctx, const float *queries, int nq, long long n_rows, float range, const uint32_t *allow_bits, long long nbits,
                                 int *out_counts)

@@ -12,7 +12,7 @@
 //   dk_traverse_exact.h  the exact two-heap traversal
 //   dk_heuristic.h       RelativeNeighborPruning (with its MFMA Gram-block prefilter)
 //   dk_range_finish.h   RangeQuery's order on the device: ranking by counting, the heaps replayed on known distances
-//   dk_search_kernels.h  graph_search_kernel, graph_search_filtered_kernel, graph_search_grouped_kernel, graph_search_tagged_kernel, graph_multilayer_kernel, graph_range_kernel
+//   dk_search_kernels.h  graph_search_kernel, graph_search_filtered_kernel, graph_search_grouped_kernel, graph_search_tagged_kernel, graph_search_self_kernel, graph_multilayer_kernel, graph_range_kernel
 //   dk_insert_kernels.h  graph_insert_search_kernel
 //   dk_link.h            the link half of Add, Remove's re-link
 //   dk_misc_kernels.h    small kernels
@@ -72,7 +72,7 @@ namespace hnsw {
 #define HNSW_UNIT_search(DO, M) HNSW_FOR_EACH_TRAVERSAL(HNSW_##DO##_SEARCH, M)
 #define HNSW_UNIT_search_lat(DO, M) HNSW_FOR_EACH_TRAVERSAL_LAT(HNSW_##DO##_SEARCH, M)
 #define HNSW_UNIT_search_lean(DO, M) HNSW_FOR_EACH_TRAVERSAL_LEAN(HNSW_##DO##_SEARCH, M)
-#define HNSW_UNIT_filtered(DO, M) HNSW_FOR_EACH_FILTERED(HNSW_##DO##_FILTERED, M) HNSW_FOR_EACH_FILTERED(HNSW_##DO##_GROUPED, M) HNSW_FOR_EACH_FILTERED(HNSW_##DO##_TAGGED, M) // (graph_search_grouped_kernel, graph_search_tagged_kernel: the same traversal, built beside it)
+#define HNSW_UNIT_filtered(DO, M) HNSW_FOR_EACH_FILTERED(HNSW_##DO##_FILTERED, M) HNSW_FOR_EACH_FILTERED(HNSW_##DO##_GROUPED, M) HNSW_FOR_EACH_FILTERED(HNSW_##DO##_TAGGED, M) HNSW_FOR_EACH_FILTERED(HNSW_##DO##_SELF, M) // (graph_search_grouped_kernel, graph_search_tagged_kernel, graph_search_self_kernel: the same traversal, built beside it)
 #define HNSW_UNIT_multilayer(DO, M) HNSW_FOR_EACH_MULTILAYER(HNSW_##DO##_MULTILAYER, M)
 
 } // namespace hnsw

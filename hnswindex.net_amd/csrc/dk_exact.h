@@ -17,6 +17,8 @@
 // and hnswdev_exact_range_grouped: the range sink behind the same work items.
 //   exact_scan_kernel<M, ExactRangeGrouped>     a block = one work item; the keys within the range go to the segment that a table names for the
 //                                               query -- its place in the caller's order -- so exact_range_sort_kernel runs as it is
+// and hnswdev_exact_knn_by_id: the queries are stored rows, and a query's own row is no candidate.
+//   exact_scan_kernel<M, ExactTopKSelf>         ExactTopK, but the pair (query q, row id self[q]) produces no key and is not counted
 // The kernels are compiled in the exact_<metric> units (exact_unit.hip, HNSW_EXACT_UNIT) and reached through the launchers declared here, so
 // that device_backend.hip holds none of their code.
 #pragma once
@@ -64,10 +66,20 @@ struct ExactScanArgs {
 struct ExactTopK {
     static constexpr bool kRange = false;
     static constexpr bool kGrouped = false;
+    static constexpr bool kSelf = false;
+};
+// ExactTopKSelf: ExactTopK where query q of the round is the stored row of id self[q] and that id is no candidate of it: the pair
+// produces no key and is not counted in ExactScanArgs::evals.  A duplicate of the row under another id is a candidate like any.
+struct ExactTopKSelf {
+    static constexpr bool kRange = false;
+    static constexpr bool kGrouped = false;
+    static constexpr bool kSelf = true;
+    const int *self;               // [nq of the round]
 };
 struct ExactRange {
     static constexpr bool kRange = true;
     static constexpr bool kGrouped = false;
+    static constexpr bool kSelf = false;
     float range;
     unsigned *counts;              // [nq]
     const long long *seg_off;      // [nq + 1]
@@ -95,6 +107,7 @@ struct ExactWorkItem {
 struct ExactTopKGrouped {
     static constexpr bool kRange = false;
     static constexpr bool kGrouped = true;
+    static constexpr bool kSelf = false;
     const ExactWorkItem *items;
 };
 // ExactRangeGrouped: ExactRange's segments behind ExactTopKGrouped's work items (list0, n_chunks and slot of an item are not read).
@@ -105,6 +118,7 @@ struct ExactTopKGrouped {
 struct ExactRangeGrouped {
     static constexpr bool kRange = true;
     static constexpr bool kGrouped = true;
+    static constexpr bool kSelf = false;
     float range;
     unsigned *counts;              // [segments]
     const long long *seg_off;      // [segments + 1]
@@ -130,6 +144,8 @@ template <int METRIC>
 hipError_t exact_scan_launch(const ExactScanArgs &a, unsigned n_qtiles, size_t lds, hipStream_t st);
 template <int METRIC>
 hipError_t exact_range_scan_launch(const ExactScanArgs &a, const ExactRange &sink, unsigned n_qtiles, size_t lds, hipStream_t st);
+template <int METRIC>
+hipError_t exact_self_scan_launch(const ExactScanArgs &a, const ExactTopKSelf &sink, unsigned n_qtiles, size_t lds, hipStream_t st);
 // words: the masked bitset; block_off[b]: set bits in front of word b * kExactCompactWords
 hipError_t exact_compact_launch(const unsigned *words, long long n_words, const long long *block_off, int *out_ids, hipStream_t st);
 hipError_t exact_merge_launch(const unsigned long long *lists, int n_chunks, int k, int nq, int *out_ids, float *out_d, hipStream_t st);
@@ -439,9 +455,12 @@ __global__ void __launch_bounds__(kExactThreads) exact_scan_kernel(const ExactSc
                     for (int q = 0; q < RQ; ++q) {
                         if (qsub + q >= QT || !q_in(q0 + qsub + q)) continue;
                         const unsigned long long t = thr[qsub + q];
+                        [[maybe_unused]] int self = -1;
+                        if constexpr (SINK::kSelf) self = sink.self[q0 + qsub + q]; // (a query of the round: q_in above)
 #pragma unroll
                         for (int r = 0; r < RR; ++r) {
                             if (!rvalid[r]) continue;
+                            if constexpr (SINK::kSelf) { if (rid[r] == self) continue; } // the query's own row: no key, not counted
                             ++measured;
                             const unsigned long long key = exact_key(dist[q][r], rid[r]);
                             if (key < t) {
@@ -492,6 +511,13 @@ template <int METRIC>
 hipError_t exact_range_scan_launch(const ExactScanArgs &a, const ExactRange &sink, unsigned n_qtiles, size_t lds, hipStream_t st)
 {
     hipLaunchKernelGGL((exact_scan_kernel<METRIC, ExactRange>), dim3(n_qtiles, (unsigned)a.n_chunks), dim3(kExactThreads), lds, st, a, sink);
+    return hipGetLastError();
+}
+
+template <int METRIC>
+hipError_t exact_self_scan_launch(const ExactScanArgs &a, const ExactTopKSelf &sink, unsigned n_qtiles, size_t lds, hipStream_t st)
+{
+    hipLaunchKernelGGL((exact_scan_kernel<METRIC, ExactTopKSelf>), dim3(n_qtiles, (unsigned)a.n_chunks), dim3(kExactThreads), lds, st, a, sink);
     return hipGetLastError();
 }
 

@@ -3,10 +3,10 @@
 //   graph_repair_collect_kernel    hop[] -> a bitset of the nodes with hop == -1 (or hop >= 0) and its set bits per block of
 //   graph_repair_offsets_kernel    kExactCompactWords words, their exclusive prefix: what exact_compact_kernel (dk_exact.h) turns
 //                                  into the ASCENDING id list -- U, and the reached members the flat scan measures
-//   graph_repair_gather_kernel     the stored rows of U as f32 rows in element order: hnswdev_download_rows' values
+//   gather_rows_kernel             (dk_misc_kernels.h) the stored rows of U as f32 rows in element order: hnswdev_download_rows' values
 //   graph_repair_propose_kernel<M> one wave per (u, j): where in the list of v = cand[u][j] the id u could go -- the append
 //                                  position, the evictable entry of largest (d(v, w), slot), or -1
-// The first three read no rows through a metric and live in device_backend.hip's unit (HNSW_HOST_TU); the proposal kernel measures
+// The first two read no rows through a metric and live in device_backend.hip's unit (HNSW_HOST_TU), as gather_rows_kernel does; the proposal kernel measures
 // with group_metric, so it is compiled in the exact_<metric> units (exact_unit.hip, HNSW_EXACT_UNIT) and reached through the
 // launcher declared here.  Every kernel is an ordinary grid-stride launch of 256-thread blocks; none waits for another wave.
 //
@@ -80,31 +80,6 @@ graph_repair_offsets_kernel(const int *__restrict__ block_cnt, int n_blocks, lon
         }
         if (b < n_blocks) block_off[b] = base + (incl - c);
         base += __shfl(incl, 63, 64);
-    }
-}
-
-// ---- thread per (row, element): out[i][e] = element e of the stored row ids[i], as f32 -------------------------------------
-// kind 0: f32 rows (a copy); 1: half-precision records widened (unpack_f16_rows_kernel's value); 2: int8 records dequantised,
-// q * scale (dequantize_rows_kernel's value).  pitch: words per stored row.  An id outside [0, n_rows) gives a row of zeros.
-__global__ void __launch_bounds__(kRepairBlock)
-graph_repair_gather_kernel(const float *__restrict__ rows, int pitch, long long n_rows, int kind, const int *__restrict__ ids, long long n_ids, int dim,
-                           float *__restrict__ out)
-{
-    const long long total = n_ids * dim, step = (long long)gridDim.x * kRepairBlock;
-    for (long long t = (long long)blockIdx.x * kRepairBlock + threadIdx.x; t < total; t += step) {
-        const long long i = t / dim;
-        const int e = (int)(t - i * dim);
-        const long long id = ids[i];
-        float x = 0.0f;
-        if ((unsigned long long)id < (unsigned long long)n_rows) {
-            const float *rec = rows + (size_t)id * pitch;
-            if (kind == 1) x = row_elem<M_SQH>(rec, e);
-            else if (kind == 2) {
-                const int *r = reinterpret_cast<const int *>(rec);
-                x = (float)(int)(signed char)((r[e >> 2] >> (8 * (e & 3))) & 0xff) * __int_as_float(r[pitch - 2]);
-            } else x = rec[e];
-        }
-        out[t] = x;
     }
 }
 

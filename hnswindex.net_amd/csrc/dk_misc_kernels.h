@@ -1,4 +1,4 @@
-// dk_misc_kernels.h -- device code, part of device_kernels.h: pair distances, per-row norms, int8 quantisation, row download, the sqrt test kernel.
+// dk_misc_kernels.h -- device code, part of device_kernels.h: pair distances, per-row norms, int8 quantisation, row download, the gather of stored rows by id, the sqrt test kernel.
 #pragma once
 #include "dk_metric.h"
 
@@ -156,6 +156,34 @@ unpack_f16_rows_kernel(const float *__restrict__ recs, long long first, int n, i
     if (t >= (long long)n * dim) return;
     const int r = (int)(t / dim), i = (int)(t % dim);
     out[t] = row_elem<M_SQH>(recs + (size_t)(first + r) * f16_row_words(dim), i);
+}
+#endif
+#ifdef HNSW_HOST_TU
+constexpr int kGatherBlock = 256;
+// Thread per (row, element): out[i][e] = element e of the stored row ids[i], as f32 -- the rows of an id list back out
+// (hnswdev_gather_rows) or as a query set on the device (repair_reachability, the by-id calls: DESIGN.md 3.21, 3.27).
+// kind 0: f32 rows (a copy); 1: half-precision records widened (unpack_f16_rows_kernel's value); 2: int8 records dequantised,
+// q * scale (dequantize_rows_kernel's value).  pitch: words per stored row.  An id outside [0, n_rows) gives a row of zeros.
+__global__ void __launch_bounds__(kGatherBlock)
+gather_rows_kernel(const float *__restrict__ rows, int pitch, long long n_rows, int kind, const int *__restrict__ ids, long long n_ids, int dim,
+                           float *__restrict__ out)
+{
+    const long long total = n_ids * dim, step = (long long)gridDim.x * kGatherBlock;
+    for (long long t = (long long)blockIdx.x * kGatherBlock + threadIdx.x; t < total; t += step) {
+        const long long i = t / dim;
+        const int e = (int)(t - i * dim);
+        const long long id = ids[i];
+        float x = 0.0f;
+        if ((unsigned long long)id < (unsigned long long)n_rows) {
+            const float *rec = rows + (size_t)id * pitch;
+            if (kind == 1) x = row_elem<M_SQH>(rec, e);
+            else if (kind == 2) {
+                const int *r = reinterpret_cast<const int *>(rec);
+                x = (float)(int)(signed char)((r[e >> 2] >> (8 * (e & 3))) & 0xff) * __int_as_float(r[pitch - 2]);
+            } else x = rec[e];
+        }
+        out[t] = x;
+    }
 }
 #endif
 #ifdef HNSW_HOST_TU // non-template kernels: only the unit that launches them defines them

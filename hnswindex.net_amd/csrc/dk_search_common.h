@@ -80,6 +80,15 @@ struct TagSet {
     __device__ __forceinline__ bool has(int id) const { return test(word(id)); }
     static constexpr bool kBitset = false;
 };
+// "Every id but one" (knn_query_by_id, graph_search_self_kernel): the job's query is the stored row of id `self`
+// (wave-uniform), and every id passes but that one.  The id is its own word: nothing is gathered.
+struct SelfSet {
+    int self;
+    __device__ __forceinline__ unsigned word(int id) const { return (unsigned)id; }
+    __device__ __forceinline__ bool test(unsigned w) const { return (int)w != self; }
+    __device__ __forceinline__ bool has(int id) const { return id != self; }
+    static constexpr bool kBitset = false;
+};
 
 struct GraphView {
     const int *adj0;

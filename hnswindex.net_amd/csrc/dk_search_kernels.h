@@ -1,4 +1,4 @@
-// dk_search_kernels.h -- device code, part of device_kernels.h: KnnQuery / MultiLayerKnnQuery / RangeQuery: search_job, graph_search_kernel (persistent, shadows, gated upload), predicate_search with its kernels graph_search_filtered_kernel (allow-sets), graph_search_grouped_kernel (a group per query), graph_search_tagged_kernel (a tag mask per query), graph_multilayer_kernel (layer chains), graph_range_kernel.
+// dk_search_kernels.h -- device code, part of device_kernels.h: KnnQuery / MultiLayerKnnQuery / RangeQuery: search_job, graph_search_kernel (persistent, shadows, gated upload), predicate_search with its kernels graph_search_filtered_kernel (allow-sets), graph_search_grouped_kernel (a group per query), graph_search_tagged_kernel (a tag mask per query), graph_search_self_kernel (every id but the query's own), graph_multilayer_kernel (layer chains), graph_range_kernel.
 #pragma once
 #include "dk_sorted_top.h"
 #include "dk_pool_top.h"
@@ -509,6 +509,35 @@ graph_search_tagged_kernel(const float *__restrict__ rows, const double *__restr
 // (the forms of HNSW_FOR_EACH_FILTERED, built in the units of the `filtered` kind: HNSW_UNIT_filtered, device_kernels.h)
 #define HNSW_DECLARE_TAGGED(M, H) HNSW_TAGGED_SIGNATURE(extern, M, H)
 #define HNSW_DEFINE_TAGGED(M, H) HNSW_TAGGED_SIGNATURE(, M, H)
+
+// Query by stored id (knn_query_by_id; SelfSet): resident query i is the stored row of id self_ids[i] (gathered on
+// the device before the launch), and every id but that one is a candidate -- a duplicate of the row under another id included.
+// Job i is resident query i.  The id is read once per job and kept in a scalar register.
+template <int METRIC, bool HASHED>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(HNSW_WAVES(3))))
+graph_search_self_kernel(const float *__restrict__ rows, const double *__restrict__ row_sn, const float *__restrict__ queries,
+                         const double *__restrict__ q_sn, int dim, const int *__restrict__ adj0, int stride0,
+                         const int64_t *__restrict__ upper, const int *__restrict__ pool, int strideU, int entry, int entry_layer,
+                         int search_layer, int k, int cand_cap, ND *__restrict__ spill, int spill_cap, unsigned *__restrict__ visited,
+                         long long vis_words, int *__restrict__ vis_tab, int vis_tab_cap, const int *__restrict__ self_ids, int k_out,
+                         int *__restrict__ out_ids, float *__restrict__ out_d, int *__restrict__ out_flag,
+                         unsigned long long *__restrict__ eval_counter, int nbcap, int njobs, int *__restrict__ job_counter)
+{
+    predicate_search<METRIC, HASHED, false>(rows, row_sn, queries, q_sn, dim, adj0, stride0, upper, pool, strideU, entry, entry_layer, search_layer, k,
+                                            cand_cap, spill, spill_cap, visited, vis_words, vis_tab, vis_tab_cap, nullptr, k_out, out_ids, out_d, out_flag,
+                                            eval_counter, nbcap, njobs, job_counter, [=](int qi) {
+                                                return SelfSet{__builtin_amdgcn_readfirstlane(self_ids[qi])};
+                                            });
+}
+#define HNSW_SELF_SIGNATURE(PREFIX, M, H)                                                                                           \
+    PREFIX template __global__ void graph_search_self_kernel<M, H>(                                                                 \
+        const float *__restrict__, const double *__restrict__, const float *__restrict__, const double *__restrict__, int,      \
+        const int *__restrict__, int, const int64_t *__restrict__, const int *__restrict__, int, int, int, int, int, int, ND *__restrict__, \
+        int, unsigned *__restrict__, long long, int *__restrict__, int, const int *__restrict__, int, int *__restrict__,          \
+        float *__restrict__, int *__restrict__, unsigned long long *__restrict__, int, int, int *__restrict__);
+// (the forms of HNSW_FOR_EACH_FILTERED, built in the units of the `filtered` kind: HNSW_UNIT_filtered, device_kernels.h)
+#define HNSW_DECLARE_SELF(M, H) HNSW_SELF_SIGNATURE(extern, M, H)
+#define HNSW_DEFINE_SELF(M, H) HNSW_SELF_SIGNATURE(, M, H)
 
 // MultiLayerKnnQuery (HNSWIndex.cs:173-187), one job = one query's whole chain.  The first step is FindEntryPointQuery from
 // (entry, entry_layer) down to first_layer = min(top, maxLayer) (exclusive) and SearchLayerQuery there; every later step searches

@@ -17,6 +17,7 @@ constexpr int kUnitMetric = HNSW_UNIT_METRIC_ID;
 static_assert(kUnitMetric >= 0, "HNSW_UNIT_METRIC is no tag of HNSW_FOR_EACH_METRIC");
 template hipError_t exact_scan_launch<kUnitMetric>(const ExactScanArgs &, unsigned, size_t, hipStream_t);
 template hipError_t exact_range_scan_launch<kUnitMetric>(const ExactScanArgs &, const ExactRange &, unsigned, size_t, hipStream_t);
+template hipError_t exact_self_scan_launch<kUnitMetric>(const ExactScanArgs &, const ExactTopKSelf &, unsigned, size_t, hipStream_t);
 template hipError_t exact_grouped_scan_launch<kUnitMetric>(const ExactScanArgs &, const ExactTopKGrouped &, unsigned, size_t, hipStream_t);
 template hipError_t exact_range_grouped_scan_launch<kUnitMetric>(const ExactScanArgs &, const ExactRangeGrouped &, unsigned, size_t, hipStream_t);
 template hipError_t graph_repair_propose_launch<kUnitMetric>(const RepairProposeArgs &, unsigned, hipStream_t);

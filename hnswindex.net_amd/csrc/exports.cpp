@@ -158,6 +158,52 @@ API int hnsw_mi355x_exact_knn_query(void *handle, const float *vectors, int coun
     return 0;
 }
 
+// ---- query by stored id.  Exclusive, like the filtered calls: they make the stored rows the resident queries or
+// use the scan's buffers.  An id that is not live: -1 and a message that names it.
+// HNSWIndex.Items() for a list of ids: the stored rows as floats, ids in any order, repeats allowed.
+API int hnsw_mi355x_get_vectors(void *handle, const int *ids, int n, float *out)
+{
+    if (!handle) return 0;
+    if (n <= 0) return 0;
+    if (!ids || !out) { set_error("System.ArgumentNullException: hnsw_mi355x_get_vectors"); return -1; }
+    LOCK_INDEX(handle);
+    std::string err;
+    if (static_cast<HnswIndex *>(handle)->get_vectors(ids, n, out, err) < 0) { set_error(err); return -1; }
+    return 0;
+}
+// KnnQuery on `layer` for the stored rows of ids, each answered from every id but its own: one gather and one traversal on the device.
+API int hnsw_mi355x_knn_query_by_id(void *handle, const int *ids, int count, int k, int layer, int *out_ids, float *out_dists)
+{
+    if (!handle) return 0;
+    if (count <= 0) return 0;
+    if (!ids || !out_ids || !out_dists) { set_error("System.ArgumentNullException: hnsw_mi355x_knn_query_by_id"); return -1; }
+    LOCK_INDEX(handle);
+    std::string err;
+    if (static_cast<HnswIndex *>(handle)->knn_query_by_id(ids, count, k, layer, out_ids, out_dists, err) < 0) { set_error(err); return -1; }
+    return 0;
+}
+// The flat scan for the stored rows of ids: the candidates are allow_bits (NULL: every live id) minus the query's own id.
+API int hnsw_mi355x_exact_knn_query_by_id(void *handle, const int *ids, int count, int k, const uint32_t *allow_bits, long long nbits, int *out_ids,
+                                          float *out_dists)
+{
+    if (!handle) return 0;
+    if (count <= 0) return 0;
+    if (!ids || !out_ids || !out_dists) { set_error("System.ArgumentNullException: hnsw_mi355x_exact_knn_query_by_id"); return -1; }
+    if (allow_bits && nbits < 0) { set_error("System.ArgumentException: hnsw_mi355x_exact_knn_query_by_id: nbits must be >= 0"); return -1; }
+    LOCK_INDEX(handle);
+    std::string err;
+    if (static_cast<HnswIndex *>(handle)->exact_knn_query_by_id(ids, count, k, allow_bits, nbits, out_ids, out_dists, err) < 0) { set_error(err); return -1; }
+    return 0;
+}
+// by-id calls, queries traversed on the device, hand-backs, queries scanned, rows gathered, pairs skipped as self
+API int hnsw_mi355x_by_id_info(void *h, uint64_t out[6])
+{
+    if (!h || !out) return -1;
+    LOCK_INDEX(h);
+    static_cast<HnswIndex *>(h)->by_id_info(out);
+    return 0;
+}
+
 // Exact k nearest neighbours with a candidate group per query: one scan for every group.  Exclusive, like the call above.
 API int hnsw_mi355x_exact_knn_query_grouped(void *handle, const float *vectors, int count, int dim, int k, const int *row_group, long long n_row_group,
                                             const int *query_group, int n_groups, int *out_ids, float *out_dists)

@@ -197,6 +197,7 @@ struct QueryJob : Job {
     float *out_d;
     AllowBits allow; // the descent is not filtered (:116); the search on `layer` is
     int layer = 0;   // KnnQuery's `layer`: FindEntryPointQuery stops above it, SearchLayerQuery reads its lists
+    int exclude = -1; // knn_query_by_id: the id whose row the query is -- a candidate, never a result (-1: none)
     Descent desc;
     Expand exp;
     int stage = 0; // 0 descent, 1 expand
@@ -206,7 +207,7 @@ struct QueryJob : Job {
         *io.qidx = qi;
         if (stage == 0) {
             if (desc.prepare(io)) return true;
-            exp.begin(g, sc, capacity, desc.best, desc.cur, layer, ef, -1, allow); // :117 (entry distance reused, same bits)
+            exp.begin(g, sc, capacity, desc.best, desc.cur, layer, ef, exclude, allow); // :117 (entry distance reused, same bits)
             stage = 1;
         }
         return exp.prepare(io, sc);
@@ -1550,7 +1551,8 @@ bool HnswIndex::gather_queries_to_primary(int count, std::string &err)
 }
 
 // Host lock-step traversal for the queries listed in `which` (nullptr: all `count` queries).
-int HnswIndex::knn_query_lockstep(const int *which, int count, int k, int *out_ids, float *out_dists, std::string &err, AllowBits allow, int layer)
+int HnswIndex::knn_query_lockstep(const int *which, int count, int k, int *out_ids, float *out_dists, std::string &err, AllowBits allow, int layer,
+                                  const int *exclude)
 {
     if (!refresh_host_lists(err)) return -1;
     QuerySource src;
@@ -1568,6 +1570,7 @@ int HnswIndex::knn_query_lockstep(const int *which, int count, int k, int *out_i
         j.out_d = out_dists + (size_t)qi * k;
         j.allow = allow;
         j.layer = layer;
+        j.exclude = exclude ? exclude[qi] : -1;
     }
     if (!engine()->run(src, count)) { err = get_dev_error(); return -1; }
     return 0;
@@ -1843,6 +1846,81 @@ int HnswIndex::knn_query_tagged(const float *queries, int count, int dim, int k,
 void HnswIndex::knn_tagged_info(uint64_t out[5]) const
 {
     sum_over_contexts(out, 5, [](const Device &d, uint64_t *one) { d.knn_tagged_info(one); });
+}
+
+// ---- query by stored id ------------------------------------------------------------------------------------
+// The ids of a by-id call are live, or err names the first that is not.
+bool HnswIndex::ids_live(const char *who, const int *ids, int n, std::string &err) const
+{
+    for (int i = 0; i < n; ++i) {
+        const int id = ids[i];
+        if (id >= 0 && id < graph_.length && !graph_.removed[(size_t)id]) continue;
+        err = std::string("System.Collections.Generic.KeyNotFoundException: ") + who + ": ids[" + std::to_string(i) + "] = " + std::to_string(id) + " is not a live id";
+        return false;
+    }
+    return true;
+}
+
+int HnswIndex::get_vectors(const int *ids, int n, float *out, std::string &err)
+{
+    if (n <= 0) return 0;
+    if (failed(err) || !ids_live("hnsw_mi355x_get_vectors", ids, n, err)) return -1;
+    if (!dev_->gather_rows(ids, n, out)) { err = get_dev_error(); return -1; }
+    return 0;
+}
+
+// KnnQuery by stored id.  The resident set is gathered where it is searched: on the primary, or -- set_resident_queries' rule for a
+// sharded set -- every context its shard of the ids from its own copy of the rows, which the replicas get with the graph mirror.
+int HnswIndex::knn_query_by_id(const int *ids, int count, int k, int layer, int *out_ids, float *out_dists, std::string &err)
+{
+    const char *who = "hnsw_mi355x_knn_query_by_id";
+    const int go = predicate_query_begin(who, count, k, layer, out_ids, out_dists, err, [&] { return ids_live(who, ids, count, err); });
+    if (go <= 0) return go;
+    const int ef = std::max(p_.min_nn, k); // HNSWIndex.cs:115
+    {
+        Tick t(g_pt.set_queries);
+        sharded_resident_ = false;
+        resident_queries_ = 0;
+        const int n = p_.devices;
+        if (n > 1 && p_.device_traversal && count >= n && dev_->traversal_fits(ef, false, p_.max_edges)) {
+            if (!sync_graph(err) || !ensure_replicas(true, err)) return -1; // (the replicas gather from their own rows: brought up to date first)
+            shard_lo_.assign((size_t)n + 1, 0);
+            for (int g = 0; g <= n; ++g) shard_lo_[(size_t)g] = (long long)count * g / n;
+            const bool ok = fan_out(n, "set_queries_by_id failed", err, [&](int g) {
+                const long long lo = shard_lo_[(size_t)g];
+                return context(g)->set_queries_by_id(ids + lo, (int)(shard_lo_[(size_t)g + 1] - lo));
+            });
+            if (!ok) return -1;
+            sharded_resident_ = true;
+        } else if (!dev_->set_queries_by_id(ids, count)) { err = get_dev_error(); return -1; }
+        resident_queries_ = count;
+    }
+    const int ep = graph_.entry, top = graph_.top_layer();
+    const int rc = answer_resident(count, ef,
+        [&](Device *ctx, int cnt, long long lo, int *flag) { return ctx->search_self(cnt, ep, top, ef, k, out_ids + (size_t)lo * k, out_dists + (size_t)lo * k, flag, layer); },
+        [&](const int *which, int n) { return knn_query_lockstep(which, n, k, out_ids, out_dists, err, AllowBits{}, layer, ids); },
+        "search_self failed", err);
+    if (rc < 0) resident_queries_ = 0;
+    return rc;
+}
+
+int HnswIndex::exact_knn_query_by_id(const int *ids, int count, int k, const uint32_t *allow_bits, long long nbits, int *out_ids, float *out_dists, std::string &err)
+{
+    if (count <= 0) return 0;
+    if (failed(err)) return -1;
+    const char *who = "hnsw_mi355x_exact_knn_query_by_id";
+    if (k > kExactMaxK) { err = std::string("System.ArgumentOutOfRangeException: ") + who + ": k = " + std::to_string(k) + " is above the limit of " + std::to_string(kExactMaxK); return -1; }
+    if (!ids_live(who, ids, count, err)) return -1;
+    if (k < 1) return 0;
+    std::vector<uint32_t> live;
+    const long long length = exact_candidates(allow_bits, nbits, live);
+    if (!dev_->exact_knn_by_id(ids, count, length, k, allow_bits, nbits, out_ids, out_dists)) { err = get_dev_error(); return -1; }
+    return 0;
+}
+
+void HnswIndex::by_id_info(uint64_t out[6]) const
+{
+    sum_over_contexts(out, 6, [](const Device &d, uint64_t *one) { d.by_id_info(one); });
 }
 
 // The candidates of a flat scan as Device::exact_knn / exact_range take them: the row count, and allow_bits / nbits replaced by

@@ -73,6 +73,20 @@ public:
     int exact_knn_query_tagged(const float *queries, int count, int dim, int k, const uint32_t *row_tags, long long n_row_tags, const uint32_t *query_tags,
                                int match, int *out_ids, float *out_dists, std::string &err);
     void exact_tagged_info(uint64_t out[6]) const { for (int i = 0; i < 6; ++i) out[i] = 0; if (dev_) dev_->exact_tagged_info(out); }
+    // ---- query by stored id.  Every id must be live: otherwise -1 with a message that names the first that is not,
+    // before anything is launched.
+    // hnsw_mi355x_get_vectors: out[i] = the stored row ids[i] as dim floats (Device::gather_rows: hnswdev_download_rows' values).
+    int get_vectors(const int *ids, int n, float *out, std::string &err);
+    // hnsw_mi355x_knn_query_by_id: row i is byte for byte what knn_query_general returns for the vector get_vectors gives for ids[i]
+    // with every id but ids[i] as the allow-set.  The queries are gathered on the device (Device::set_queries_by_id, every context
+    // its shard) and traversed by graph_search_self_kernel; hand-backs, and the whole call when the traversal does not run on the
+    // device, go the lock-step way with the id as the job's `exclude`.  Exclusive lock.  0 or -1.
+    int knn_query_by_id(const int *ids, int count, int k, int layer, int *out_ids, float *out_dists, std::string &err);
+    // hnsw_mi355x_exact_knn_query_by_id: row i is exact_knn_query's for that vector with allow_bits (nullptr: every live id) minus
+    // ids[i] as the candidates (Device::exact_knn_by_id).  Runs on the primary context; the resident set stays what it was.
+    int exact_knn_query_by_id(const int *ids, int count, int k, const uint32_t *allow_bits, long long nbits, int *out_ids, float *out_dists, std::string &err);
+    // Device::by_id_info summed over the contexts
+    void by_id_info(uint64_t out[6]) const;
     // hnsw_mi355x_exact_range_query_grouped: exact_range_query with exact_knn_query_grouped's group per query
     // (Device::exact_range_grouped); the labels of vacant slots are taken out as for that call
     int exact_range_query_grouped(const float *queries, int count, int dim, float range, const int *row_group, long long n_row_group, const int *query_group,
@@ -244,6 +258,7 @@ private:
     bool insert_batch(const std::vector<int> &bid, std::string &err);
     long long exact_candidates(const uint32_t *&allow_bits, long long &nbits, std::vector<uint32_t> &live) const;
     bool live_labels(const int *&row_group, long long &n_row_group, std::vector<int> &live) const;
+    bool ids_live(const char *who, const int *ids, int n, std::string &err) const;
     bool live_tags(const uint32_t *&row_tags, long long &n_row_tags, std::vector<uint32_t> &live) const;
     int reach_chain(const char *who, int min_layer, hnsw_mi355x_layer_reach *out, int cap, uint32_t *bits, int *hops, std::string &err);
     bool insert_exact_window(const std::vector<int> &fresh, int &p, int W, bool background, std::string &err);
@@ -296,8 +311,9 @@ private:
     int answer_by_class(int count, int k, int layer, long long n_lab, size_t n_classes, ClassOf class_of, Matches matches, Search search, const char *fallback,
                         int *out_ids, float *out_dists, std::string &err);
     template <class Get> void sum_over_contexts(uint64_t *out, int n, Get get) const;
+    // exclude: nullptr, or per resident query the id that is no result of it (knn_query_by_id: the query's own)
     int knn_query_lockstep(const int *which, int count, int k, int *out_ids, float *out_dists, std::string &err, AllowBits allow = AllowBits{},
-                           int layer = 0);
+                           int layer = 0, const int *exclude = nullptr);
     // range_query_grouped's filter: the labels of graph ids, every query's group, and the queries that run (ascending), the others
     // being answered with an empty list.  range_query_tagged's (tags != nullptr) in the same type: the tag words of graph ids, every
     // query's mask and the call's mode in the labels' and groups' place; resident: the device counted the masks' candidates on these

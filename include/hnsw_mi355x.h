@@ -384,6 +384,41 @@ int hnsw_mi355x_knn_tagged_info(void *handle, uint64_t out[5]);
  * ids written into candidate lists, out[5] batches of masks scanned.  (Scan launches and pairs count in hnswdev_stats.exact_*.)
  * 0, or -1 for a NULL argument. */
 int hnsw_mi355x_exact_tagged_info(void *handle, uint64_t out[6]);
+/* QUERY BY STORED ID.  The rows of an index live in device memory; these calls read them back and use them as
+ * queries without a copy on the host.  Every id must be live: one that is not (negative, beyond the ids handed out, or removed)
+ * makes the call return -1 before anything is launched, with a message that names it.  ids may repeat and come in any order.
+ * The calls take the handle exclusively, like the filtered calls.
+ *
+ * hnsw_mi355x_get_vectors: out[i * dim .. ) = the stored row of ids[i] as floats -- HNSWIndex.Items() for a list of ids.  The
+ * values are what the index measures distances on, exactly hnswdev_download_rows' for the row kind: float32 rows are a copy,
+ * half-precision rows the rounded row widened, int8 rows q * scale.  The rows are gathered on the device in one launch and
+ * n * dim floats come back in one copy.  n <= 0: 0, nothing is written.  NULL ids or out with n > 0: -1. */
+int hnsw_mi355x_get_vectors(void *handle, const int *ids, int n, float *out);
+/* KnnQuery on `layer` for the stored rows of ids, each answered from every id but its own.  Row i of out_ids / out_dists
+ * ([count][k], padded with -1 / NaN) is byte for byte -- ids, distance bits, the order among equal distances, the padding -- what
+ * hnsw_mi355x_knn_query_at_layer with an allow-set of every id except ids[i] returns for the vector hnsw_mi355x_get_vectors
+ * gives for ids[i].  A duplicate of the row under another id is an ordinary candidate (and ties at distance 0).  The queries are
+ * gathered from the stored rows on the device (int8 rows are quantised again as any query is, cosine norms computed there) and
+ * traversed in one launch per device context with the filter "id != ids[i]"; the descent is not filtered, the entry point is a
+ * candidate even when it is ids[i], the beam is max(MinNN, k), and a job that meets NaN, -0 or a full heap is answered on the
+ * host with the same exclusion.  hnsw_mi355x_set_device_traversal(0) answers everything that way, with the same bytes.
+ * count <= 0: 0.  k < 1: 0, nothing is written.  NULL ids / out_ids / out_dists: -1.  layer outside 0 .. the entry point's top
+ * layer: -1.  An index of one item answers with padding. */
+int hnsw_mi355x_knn_query_by_id(void *handle, const int *ids, int count, int k, int layer, int *out_ids, float *out_dists);
+/* The flat scan (hnsw_mi355x_exact_knn_query) for the stored rows of ids.  Row i is what hnsw_mi355x_exact_knn_query returns for
+ * the vector hnsw_mi355x_get_vectors gives for ids[i] with the candidates "allow_bits (NULL: every live id) minus ids[i]":
+ * ascending by (distance, id), unique, padded where the candidates run out -- an index of n live items gives at most n - 1
+ * results.  The exclusion happens where the scan turns a pair into a key: the pair (query i, row ids[i]) produces none and is not
+ * counted in hnswdev_stats.exact_evals; nothing is asked for k + 1 and dropped.  allow_bits / nbits as for
+ * hnsw_mi355x_exact_knn_query; a set that holds only ids[i] gives padding, one that does not hold ids[i] changes nothing for
+ * query i.  1 <= k <= 1024 (k < 1: 0, nothing written; k > 1024: -1).  The resident query set stays what it was. */
+int hnsw_mi355x_exact_knn_query_by_id(void *handle, const int *ids, int count, int k, const uint32_t *allow_bits, long long nbits, int *out_ids,
+                                      float *out_dists);
+/* Counters of the by-id calls since creation or hnswdev_reset_stats / hnsw_mi355x_reset_stats, summed over the device contexts:
+ * out[0] knn_query_by_id / exact_knn_query_by_id calls that reached a device, out[1] queries traversed on the device, out[2] of
+ * those handed back to the host traversal, out[3] queries scanned, out[4] rows gathered (get_vectors' included), out[5] pairs
+ * the scan skipped because the row was the query's own.  0, or -1 for a NULL argument. */
+int hnsw_mi355x_by_id_info(void *handle, uint64_t out[6]);
 /* RangeQuery with a GROUP FILTER PER QUERY: the graph traversal of hnsw_mi355x_range_query_at_layer, query i
  * filtered by { j < n_row_group : row_group[j] == query_group[i] }.  Per group g the lists of the queries with query_group == g
  * are byte for byte -- ids, distance bits, the order among equal distances -- what hnsw_mi355x_range_query_at_layer returns for
@@ -758,6 +793,24 @@ int hnswdev_exact_knn_tagged(void *ctx, const float *queries, int nq, long long 
                              const uint32_t *query_tags, int match, int *out_ids, float *out_dists);
 /* out[0 .. 5] as hnsw_mi355x_exact_tagged_info, of this context; zeroed by hnswdev_reset_stats. */
 int hnswdev_exact_tagged_info(void *ctx, uint64_t out[6]);
+/* Query by stored id on a context.
+ * hnswdev_gather_rows: out[i] = the uploaded row ids[i] as dim floats, hnswdev_download_rows' values for the row kind, gathered in
+ * one launch and copied back in one copy.  ids may repeat, in any order; an id outside the uploaded rows gives a row of zeros.
+ * n <= 0: 0, nothing is written. */
+int hnswdev_gather_rows(void *ctx, const int *ids, int n, float *out);
+/* hnswdev_knn_search_at_layer whose query i is the uploaded row ids[i] -- made resident on the device as hnswdev_set_queries
+ * would make hnswdev_gather_rows' row -- answered from every graph id but ids[i] (graph_search_self_kernel).  Row i is byte for
+ * byte hnswdev_knn_search_filtered's at that layer with that allow-set.  out_flags as there (1: handed back).  An id that is no
+ * uploaded row of a graph node is an error that names it. */
+int hnswdev_knn_search_by_id(void *ctx, const int *ids, int nq, int entry_point, int k_beam, int k_out, int layer, int *out_ids, float *out_dists,
+                             int *out_flags);
+/* hnswdev_exact_knn whose query i is the uploaded row ids[i] and whose candidates are hnswdev_exact_knn's minus ids[i]; the scan's
+ * sink drops that pair, which is not counted in exact_evals.  The resident set stays what it was.  An id that is no uploaded row is
+ * an error that names it. */
+int hnswdev_exact_knn_by_id(void *ctx, const int *ids, int nq, long long n_rows, int k, const uint32_t *allow_bits, long long nbits, int *out_ids,
+                            float *out_dists);
+/* out[0 .. 5] as hnsw_mi355x_by_id_info, of this context; zeroed by hnswdev_reset_stats. */
+int hnswdev_by_id_info(void *ctx, uint64_t out[6]);
 /* Measurement aid: the HIP-event time, in ms, of the tagged calls' list-building kernels (count, offsets, fill) on this context
  * while profiling is on; zeroed by hnswdev_reset_stats. */
 int hnswdev_tag_list_ms(void *ctx, double *out_ms);
