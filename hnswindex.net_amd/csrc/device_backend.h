@@ -124,6 +124,7 @@ struct VisitedScratch;   // device_backend.hip: the visited-set memory of a trav
 struct TraversalLaunch;  // ... which traversal kernel form a launch runs, on how many waves, with which flags
 struct LaunchFamily;     // ... the hnswdev_stats counters of one kernel family
 struct AllowPred;        // host_structs.h: an allow-set or a group label over ids
+struct RangeFilter;      // ... the filter of one range call: its kind, per-id array and per-query keys
 struct PredicateCall;    // device_backend.hip: the arguments every KnnQuery with a predicate over ids has
 template <class K> struct PredicatePlan; // ... and what its launches need, K the kernel's type
 struct ExactScanArgs;    // dk_exact.h: what one launch of the flat scan reads
@@ -404,40 +405,22 @@ public:
         SearchHit *found = nullptr;        // the lists, in pinned memory the context owns: valid until its next range_batch
         size_t found_n = 0;
     };
-    // allow_bits (a filtered RangeQuery; nbits bits as for search_filtered): the traversal is the unfiltered one,
-    // and what crosses back is packed -- a kRangeFinal job's cnt[i] entries are its RESULTS in the reference's order, any other
-    // job's are its whole CLOSURE (every node within range the traversal reached, allowed or not; kRangeTied: its allowed entries
-    // first, ascending), for the host to partition, sort and replay.  range < 0 leaves every closure to the host (the empty-heap rule).
-    // grp (range_query_grouped): the filter is "label[id] == group_of[job]" instead of a bit set (allow_bits must be
-    // nullptr then) -- ids >= n_label are in no group -- ranked by range_sort_grouped_kernel; what crosses back is the filtered
-    // call's.  skipped: the queries the caller answered without a job (their group holds no graph id), for range_grouped_info.
-    struct RangeGroups {
-        const int *label = nullptr;
-        long long n_label = 0;
-        const int *group_of = nullptr; // [njobs]
-        long long skipped = 0;
-    };
-    // tags (range_query_tagged): the filter is "words[id] matches mask_of[job] under `match`" (tag_match_host's rule;
-    // allow_bits and grp must be nullptr then) -- ids >= n_words carry the word 0 -- ranked by range_sort_tagged_kernel, which also
-    // finishes a closure beyond kRangeSortMax entries when its allowed entries fit the table and hold no equal keys (diag
-    // range_sort_long=0: handed to the host as the other two sorts do); what crosses back is the filtered call's.  resident: s_ttags_
-    // holds words[0, min(n_words, graph)) already (tag_candidates ran on them for this call) and nothing goes up.  skipped: as for grp.
-    struct RangeTags {
-        const uint32_t *words = nullptr;
-        long long n_words = 0;
-        const uint32_t *mask_of = nullptr; // [njobs]
-        int match = 0;
-        long long skipped = 0;
-        bool resident = false;
-        size_t n_masks = 0;                // distinct masks of the call, for range_tagged_info
-    };
-    bool range_batch(const SearchJob *jobs, int njobs, float range, RangeResults *res, const uint32_t *allow_bits = nullptr, long long nbits = 0,
-                     const RangeGroups *grp = nullptr, const RangeTags *tags = nullptr);
+    // f (host_structs.h): the call's filter.  kBits (a filtered RangeQuery): the traversal is the unfiltered one, and
+    // what crosses back is packed -- a kRangeFinal job's cnt[i] entries are its RESULTS in the reference's order, any other job's are
+    // its whole CLOSURE (every node within range the traversal reached, allowed or not; kRangeTied: its allowed entries first,
+    // ascending), for the host to partition, sort and replay.  range < 0 leaves every closure to the host (the empty-heap rule).
+    // kLabels (range_query_grouped): "label[id] == keys[job's query]", ranked by range_sort_grouped_kernel.  kTags
+    // (range_query_tagged): "words[id] matches keys[job's query] under `match`" (tag_match_host's rule), ranked by
+    // range_sort_tagged_kernel, which also finishes a closure beyond kRangeSortMax entries when its allowed entries fit the table and
+    // hold no equal keys (diag range_sort_long=0: handed to the host as the other two sorts do).  What crosses back for those two is
+    // the filtered call's.  The per-id array goes to s_allow_ / s_glabel_ / s_ttags_ -- the part that covers graph ids -- unless
+    // f.resident says s_ttags_ holds it already.
+    bool range_batch(const SearchJob *jobs, int njobs, float range, RangeResults *res, const RangeFilter &f);
     // tagged range calls that reached this context, distinct masks, queries launched, queries skipped for a mask without a graph
     // candidate, lists the device left to the host (closures and hand-backs), closures above kRangeSortMax entries that the device finished
     void range_tagged_info(uint64_t out[6]) const { for (int i = 0; i < 6; ++i) out[i] = rt_info_[i]; }
     // The candidates of every distinct mask among ids [0, n) of row_tags, counted on the device (tag_count_kernel): cnt[d] for
-    // masks[d].  The words stay in s_ttags_ for a range_batch that follows (RangeTags::resident).  n <= 0: every count 0, no launch.
+    // masks[d].  The words stay in s_ttags_ for a range_batch that follows (RangeFilter::resident).  n <= 0: every count 0, no launch.
     bool tag_candidates(const uint32_t *row_tags, long long n, const std::vector<uint32_t> &masks, int match, std::vector<int> &cnt);
     // grouped range calls that reached this context, queries launched, queries skipped for a group without graph ids, lists the
     // device left to the host (closures to partition / sort / replay, and hand-backs)
@@ -760,6 +743,9 @@ private:
     bool exact_sorted_queries(const char *who, const float *queries, int nq, const std::vector<int> &order, const float **d_q, const double **d_qsn,
                               const int *resident = nullptr);
     bool exact_grouped_plan(const char *who, int k, ExactGroupedCall *gc);
+    template <class OnBatch> // the batches of masks of exact_knn_tagged / exact_range_tagged, each handed to on_batch (device_backend.hip)
+    bool exact_tag_batches(const char *who, const float *queries, int nq, long long n, int k, const uint32_t *row_tags, const TagCall &tc, int match,
+                           std::vector<int> &cnt, uint64_t info[6], OnBatch &&on_batch);
     bool exact_knn_grouped_scan(const char *who, const float *queries, const int *resident, int nq, int k, const int *query_group, int n_groups,
                                 const ExactGroupedCall &gc, int *out_ids, float *out_d, uint64_t *blocks);
     bool exact_range_grouped_scan(const char *who, const float *queries, const int *resident, int nq, float range, const int *query_group, int n_groups,
@@ -802,8 +788,10 @@ private:
     DevBuf<SearchHit> s_rlists_; // range search: long per-wave result lists for the few jobs that outgrow s_spill_'s
     double range_hint_ = 48.0;      // results per query of the last range search (sizes the next arena)
     std::vector<SearchHit> abi_range_; // hnswdev_range_search's results until hnswdev_range_results
-    auto host_list_of(int layer) const;  // what range_search_filtered / range_search_grouped share: the host graph's lists of a layer ...
+    auto host_list_of(int layer) const;  // what the range_search_* forms share: the host graph's lists of a layer ...
     bool finish_closure(int layer, int entry, float range, SearchHit *b, int m, const AllowPred &allow, int nq, int *out_counts, int *count); // ... and "finish a closure or fail the whole call"
+    template <class HasCandidate> // ... and their body: the jobs, the launch, the lists collected in query order (device_backend.hip)
+    bool range_search_run(int nq, int entry_point, int top, float range, RangeFilter f, HasCandidate &&has_candidate, int *out_counts, int *out_flags, int layer);
     DevBuf<int> s_lk_[5];
     bool ensure_search_scratch(long long chunk, long long slots, int k, size_t vis_bytes_per_job);
     void *pinned_stage(size_t bytes);

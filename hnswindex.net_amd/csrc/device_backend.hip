@@ -2451,26 +2451,24 @@ bool Device::range_host_room(size_t entries, size_t keep)
     return true;
 }
 
-bool Device::range_batch(const SearchJob *jobs, int njobs, float range, RangeResults *res, const uint32_t *allow_bits, long long nbits,
-                         const RangeGroups *grp, const RangeTags *tags)
+bool Device::range_batch(const SearchJob *jobs, int njobs, float range, RangeResults *res, const RangeFilter &f)
 {
-    const bool grouped = grp != nullptr, tagged = tags != nullptr;
-    const bool filtered = allow_bits != nullptr || grouped || tagged; // (grouped, tagged: the filtered call's ranking, replay and packing, on their predicate)
-    if (tagged) {
-        if (allow_bits || grouped || tags->n_words < 0 || (tags->match != 0 && tags->match != 1) || (njobs > 0 && (!tags->words || !tags->mask_of))) {
-            set_dev_error("range_batch: bad argument");
-            return false;
-        }
-        rt_info_[0] += 1;
-        rt_info_[1] += (uint64_t)tags->n_masks;
-        rt_info_[2] += (uint64_t)std::max(njobs, 0);
-        rt_info_[3] += (uint64_t)std::max<long long>(tags->skipped, 0);
-    }
-    if (grouped) {
-        if (allow_bits || grp->n_label < 0 || (njobs > 0 && (!grp->label || !grp->group_of))) { set_dev_error("range_batch: bad argument"); return false; }
-        rg_info_[0] += 1;
-        rg_info_[1] += (uint64_t)std::max(njobs, 0);
-        rg_info_[2] += (uint64_t)std::max<long long>(grp->skipped, 0);
+    const bool filtered = f.kind != RangeFilter::kNone; // (labels, tags: the bit set's ranking, replay and packing, on their predicate)
+    const bool keyed = f.per_query();
+    // The info counters of the two per-query kinds, range_grouped_info and range_tagged_info: the same quantities at each array's own
+    // places (-1: it keeps no such counter); the other kinds keep none.
+    enum { kCalls, kMasks, kLaunched, kSkipped, kHostFinished, kLongFinished };
+    const auto count = [&](int what, uint64_t by) {
+        static constexpr int kLabelSlot[6] = {0, -1, 1, 2, 3, -1};
+        if (f.kind == RangeFilter::kTags) rt_info_[what] += by;
+        else if (f.kind == RangeFilter::kLabels && kLabelSlot[what] >= 0) rg_info_[kLabelSlot[what]] += by;
+    };
+    if (keyed) {
+        if (f.n < 0 || (f.match != 0 && f.match != 1) || (njobs > 0 && (!f.per_id || !f.keys))) { set_dev_error("range_batch: bad argument"); return false; }
+        count(kCalls, 1);
+        count(kMasks, (uint64_t)f.n_masks);
+        count(kLaunched, (uint64_t)std::max(njobs, 0));
+        count(kSkipped, (uint64_t)std::max<long long>(f.skipped, 0));
     }
     res->off.assign((size_t)std::max(njobs, 0), 0ull);
     res->cnt.assign((size_t)std::max(njobs, 0), 0);
@@ -2483,7 +2481,7 @@ bool Device::range_batch(const SearchJob *jobs, int njobs, float range, RangeRes
     if (!jobs) { set_dev_error("range_batch: bad argument"); return false; }
     if (g_n_ <= 0) { set_dev_error("range_batch: no graph uploaded"); return false; }
     if (!jobs_valid(jobs, njobs, g_n_, n_queries_, n_rows_hw_)) { set_dev_error("range_batch: job outside the uploaded graph / rows / queries"); return false; }
-    if (filtered && nbits < 0) { set_dev_error("range_batch: bad argument"); return false; }
+    if (filtered && f.n < 0) { set_dev_error("range_batch: bad argument"); return false; }
     const int layer = jobs[0].search_layer; // RangeQuery's `layer`: one per call (the replay kernels walk that layer's lists)
     for (int i = 0; i < njobs; ++i)
         if (jobs[i].qref < 0 || jobs[i].search_layer != layer) { set_dev_error("range_batch: jobs must name a resident query and one search layer"); return false; }
@@ -2503,36 +2501,25 @@ bool Device::range_batch(const SearchJob *jobs, int njobs, float range, RangeRes
                         s_rtied_.grow(c + 1) && reset_all(s_rres_, s_rdst_); // (those two: allocated by the first filtered call)
         if (!ok) { (void)s_roff_.reset(); return false; }
     }
-    long long n_allow = 0;
-    long long n_lab = 0;
-    if (grouped) { // the call's labels: those of graph ids, on this context (as search_grouped), and room for a launch's group table
-        if (!s_rres_.grow(s_roff_.cap()) || !s_rdst_.grow(s_roff_.cap())) return false;
-        n_lab = std::min<long long>(grp->n_label, g_n_);
-        if (!s_glabel_.grow(std::max<size_t>((size_t)n_lab, 1)) || !s_gquery_.grow((size_t)chunk)) return false;
-        if (n_lab > 0) {
-            HIP_OK(hipMemcpyAsync(s_glabel_, grp->label, 4u * (size_t)n_lab, hipMemcpyHostToDevice, st));
-            HIP_OK(hipStreamSynchronize(st)); // (pageable source: the caller's buffer)
-        }
-    } else if (tagged) { // the call's tag words: those of graph ids, on this context (as search_tagged), and room for a launch's mask table
-        if (!s_rres_.grow(s_roff_.cap()) || !s_rdst_.grow(s_roff_.cap())) return false;
-        n_lab = std::min<long long>(tags->n_words, g_n_);
-        if (!s_gquery_.grow((size_t)chunk)) return false;
-        if (!tags->resident || (size_t)n_lab > s_ttags_.cap()) {
-            if (!s_ttags_.grow(std::max<size_t>((size_t)n_lab, 1))) return false;
-            if (n_lab > 0) {
-                HIP_OK(hipMemcpyAsync(s_ttags_, tags->words, 4u * (size_t)n_lab, hipMemcpyHostToDevice, st));
-                HIP_OK(hipStreamSynchronize(st)); // (pageable source: the caller's buffer)
-            }
-        }
-    } else if (filtered) { // the call's allow-set: the words that cover graph ids, on this context (as search_filtered)
-        if (!s_rres_.grow(s_roff_.cap()) || !s_rdst_.grow(s_roff_.cap())) return false;
-        n_allow = std::min<long long>(nbits, g_n_);
-        const size_t words = (size_t)((n_allow + 31) / 32);
-        if (!s_allow_.grow(std::max<size_t>(words, 1))) return false;
+    // the call's per-id array -- the words of the bit set that cover graph ids, the labels or the tag words of graph ids -- on this
+    // context, as the KnnQuery forms have it; the per-query kinds besides need room for a launch's key table
+    const long long n_ids = filtered ? std::min<long long>(f.n, g_n_) : 0;
+    const auto make_resident = [&](auto &buf, size_t words, bool held) -> bool {
+        if (held && words <= buf.cap()) return true;
+        if (!buf.grow(std::max<size_t>(words, 1))) return false;
         if (words) {
-            HIP_OK(hipMemcpyAsync(s_allow_, allow_bits, 4u * words, hipMemcpyHostToDevice, st));
+            HIP_OK(hipMemcpyAsync(buf, f.per_id, 4u * words, hipMemcpyHostToDevice, st));
             HIP_OK(hipStreamSynchronize(st)); // (pageable source: the caller's buffer)
         }
+        return true;
+    };
+    if (filtered && (!s_rres_.grow(s_roff_.cap()) || !s_rdst_.grow(s_roff_.cap()))) return false;
+    if (keyed && !s_gquery_.grow((size_t)chunk)) return false;
+    switch (f.kind) {
+    case RangeFilter::kNone: break;
+    case RangeFilter::kBits: if (!make_resident(s_allow_, (size_t)((n_ids + 31) / 32), false)) return false; break;
+    case RangeFilter::kLabels: if (!make_resident(s_glabel_, (size_t)n_ids, false)) return false; break;
+    case RangeFilter::kTags: if (!make_resident(s_ttags_, (size_t)n_ids, f.resident)) return false; break;
     }
     unsigned long long closure_total = 0; // entries the traversals found (sizes the next call's arena)
     if (!s_arena_used_.grow(1) || !s_rfin_ctr_.grow(2)) return false;
@@ -2546,21 +2533,16 @@ bool Device::range_batch(const SearchJob *jobs, int njobs, float range, RangeRes
         // pinned layout: [evals, used (16 B) | jobs | offsets | counts | flags | entries | states]; then reused for the results
         // (filtered: [... | allowed counts | packed offsets] besides)
         const size_t b_jobs = sizeof(SearchJob) * (size_t)nj, b_off = 8u * (size_t)nj, b_i = 4u * (size_t)nj;
-        // (grouped: [... | the jobs' groups] behind those; tagged: the jobs' masks there)
-        char *hs = static_cast<char *>(pinned_stage(16 + b_jobs + b_off + 4 * b_i + (filtered ? b_i + b_off : 0) + (grouped || tagged ? b_i : 0)));
+        // (a key per query: [... | the jobs' groups, or their masks] behind those)
+        char *hs = static_cast<char *>(pinned_stage(16 + b_jobs + b_off + 4 * b_i + (filtered ? b_i + b_off : 0) + (keyed ? b_i : 0)));
         if (!hs) return false;
         SearchJob *h_jobs = reinterpret_cast<SearchJob *>(hs + 16);
         for (int i = 0; i < nj; ++i) h_jobs[i] = jobs[todo[i]];
         HIP_OK(hipMemcpyAsync(s_jobs_, h_jobs, b_jobs, hipMemcpyHostToDevice, st));
-        if (grouped) { // the sort kernel's table: job -> the group its query names
-            int *h_grp = reinterpret_cast<int *>(hs + 16 + b_jobs + b_off + 5 * b_i + b_off);
-            for (int i = 0; i < nj; ++i) h_grp[i] = grp->group_of[todo[i]];
-            HIP_OK(hipMemcpyAsync(s_gquery_, h_grp, b_i, hipMemcpyHostToDevice, st));
-        }
-        if (tagged) { // the sort kernel's table: job -> the mask its query brings (in the group table's place)
-            uint32_t *h_mask = reinterpret_cast<uint32_t *>(hs + 16 + b_jobs + b_off + 5 * b_i + b_off);
-            for (int i = 0; i < nj; ++i) h_mask[i] = tags->mask_of[todo[i]];
-            HIP_OK(hipMemcpyAsync(s_gquery_, h_mask, b_i, hipMemcpyHostToDevice, st));
+        if (keyed) { // the sort kernel's table: job -> the key of the query it names (its group, its mask)
+            uint32_t *h_key = reinterpret_cast<uint32_t *>(hs + 16 + b_jobs + b_off + 5 * b_i + b_off);
+            for (int i = 0; i < nj; ++i) h_key[i] = f.keys[h_jobs[i].qref];
+            HIP_OK(hipMemcpyAsync(s_gquery_, h_key, b_i, hipMemcpyHostToDevice, st));
         }
         uj_len_ = 0;
         HIP_OK(hipMemsetAsync(s_jobctr_, 0, sizeof(int), st));
@@ -2587,25 +2569,28 @@ bool Device::range_batch(const SearchJob *jobs, int njobs, float range, RangeRes
         HIP_OK(hipMemsetAsync(s_rtied_, 0, sizeof(int), st));
         HIP_OK(hipMemsetAsync(s_rstate_, 0, sizeof(int) * (size_t)nj, st));
         const dim3 sort_grid(std::min(nj, 8 * std::max(1, num_cu_))), replay_grid(std::min(nj, 2 * std::max(1, num_cu_)));
-        if (tagged) {
-            hipLaunchKernelGGL(range_sort_tagged_kernel, sort_grid, dim3(64), 0, st, reinterpret_cast<ND *>(s_arena_.get()), s_roff_, s_cnt_, s_flag_, nj,
-                               s_rstate_, s_rtied_, s_rfin_ctr_, s_ttags_.get(), n_lab, reinterpret_cast<const unsigned *>(s_gquery_.get()), tags->match, s_rres_,
-                               (int)(finish == 0 || range < 0.0f), (int)(diag("range_sort_long", 1) != 0));
-            HIP_OK(hipGetLastError());
-        } else if (grouped) {
-            hipLaunchKernelGGL(range_sort_grouped_kernel, sort_grid, dim3(64), 0, st, reinterpret_cast<ND *>(s_arena_.get()), s_roff_, s_cnt_, s_flag_, nj,
-                               s_rstate_, s_rtied_, s_rfin_ctr_, s_glabel_.get(), n_lab, s_gquery_.get(), s_rres_, (int)(finish == 0 || range < 0.0f));
-            HIP_OK(hipGetLastError());
-        } else if (filtered) {
-            hipLaunchKernelGGL(range_sort_filtered_kernel, sort_grid, dim3(64), 0, st, reinterpret_cast<ND *>(s_arena_.get()), s_roff_, s_cnt_, s_flag_, nj,
-                               s_rstate_, s_rtied_, s_rfin_ctr_, reinterpret_cast<const unsigned *>(s_allow_.get()), n_allow, s_rres_,
-                               (int)(finish == 0 || range < 0.0f));
-            HIP_OK(hipGetLastError());
-        } else if (finish >= 1) {
-            hipLaunchKernelGGL(range_sort_kernel, sort_grid, dim3(64), 0, st, reinterpret_cast<ND *>(s_arena_.get()), s_roff_, s_cnt_, s_flag_, nj,
-                               s_rstate_, s_rtied_, s_rfin_ctr_);
-            HIP_OK(hipGetLastError());
+        ND *arena = reinterpret_cast<ND *>(s_arena_.get());
+        const int host_all = (int)(finish == 0 || range < 0.0f);
+        switch (f.kind) {
+        case RangeFilter::kTags:
+            hipLaunchKernelGGL(range_sort_tagged_kernel, sort_grid, dim3(64), 0, st, arena, s_roff_, s_cnt_, s_flag_, nj, s_rstate_, s_rtied_, s_rfin_ctr_,
+                               s_ttags_.get(), n_ids, reinterpret_cast<const unsigned *>(s_gquery_.get()), f.match, s_rres_, host_all,
+                               (int)(diag("range_sort_long", 1) != 0));
+            break;
+        case RangeFilter::kLabels:
+            hipLaunchKernelGGL(range_sort_grouped_kernel, sort_grid, dim3(64), 0, st, arena, s_roff_, s_cnt_, s_flag_, nj, s_rstate_, s_rtied_, s_rfin_ctr_,
+                               s_glabel_.get(), n_ids, s_gquery_.get(), s_rres_, host_all);
+            break;
+        case RangeFilter::kBits:
+            hipLaunchKernelGGL(range_sort_filtered_kernel, sort_grid, dim3(64), 0, st, arena, s_roff_, s_cnt_, s_flag_, nj, s_rstate_, s_rtied_, s_rfin_ctr_,
+                               reinterpret_cast<const unsigned *>(s_allow_.get()), n_ids, s_rres_, host_all);
+            break;
+        case RangeFilter::kNone:
+            if (finish >= 1)
+                hipLaunchKernelGGL(range_sort_kernel, sort_grid, dim3(64), 0, st, arena, s_roff_, s_cnt_, s_flag_, nj, s_rstate_, s_rtied_, s_rfin_ctr_);
+            break;
         }
+        HIP_OK(hipGetLastError());
         if (finish >= 2) {
             if (filtered)
                 hipLaunchKernelGGL(range_replay_filtered_kernel, replay_grid, dim3(64), sizeof(RangeReplayLds) + 64, st, reinterpret_cast<ND *>(s_arena_.get()), s_roff_,
@@ -2645,9 +2630,8 @@ bool Device::range_batch(const SearchJob *jobs, int njobs, float range, RangeRes
                 res->state[(size_t)j] = finish >= 1 || filtered ? h_state[i] : kRangeHostSort;
                 const int results = filtered ? h_res[i] : h_cnt[i]; // (filtered, handed to the host: the allowed members of its closure)
                 if (results >= 2) { if (res->state[(size_t)j] == kRangeFinal) stats_.range_device_ordered++; else stats_.range_host_ordered++; }
-                if (grouped && h_cnt[i] > 0 && h_state[i] != kRangeFinal) rg_info_[3] += 1; // a closure the host finishes
-                if (tagged && h_cnt[i] > 0 && h_state[i] != kRangeFinal) rt_info_[4] += 1;
-                if (tagged && h_cnt[i] > kRangeSortMax && h_state[i] == kRangeFinal && h_res[i] >= 2) rt_info_[5] += 1; // rank_long's
+                if (h_cnt[i] > 0 && h_state[i] != kRangeFinal) count(kHostFinished, 1); // a closure the host finishes
+                if (keyed && h_cnt[i] > kRangeSortMax && h_state[i] == kRangeFinal && h_res[i] >= 2) count(kLongFinished, 1); // rank_long's
                 finished += (unsigned long long)h_cnt[i];
                 if (h_cnt[i] > 0) span = std::max(span, h_off[i] + (unsigned long long)h_cnt[i]);
             } else if (h_flag[i] == 3) again.push_back(j);
@@ -2720,8 +2704,7 @@ bool Device::range_batch(const SearchJob *jobs, int njobs, float range, RangeRes
         handed.swap(still);
     }
     stats_.range_handbacks += handed.size();
-    if (grouped) rg_info_[3] += handed.size();
-    if (tagged) rt_info_[4] += handed.size();
+    count(kHostFinished, handed.size());
     range_hint_ = (double)closure_total / (double)njobs; // (filtered calls too: the arena holds closures)
     return true;
 }
@@ -2779,6 +2762,51 @@ bool Device::finish_closure(int layer, int entry, float range, SearchHit *b, int
     return true;
 }
 
+// What the three range_search forms run once their arguments stand and the queries are resident: a job for every query that
+// has_candidate(i) -- or any query at all when range < 0: below zero the filtered call can throw on an empty set too
+// (range_replay.h), so those queries run -- the launch, and the lists collected into abi_range_ in query order, as range_results
+// hands them out.  A query without a job keeps the count and flag its caller gave it.  With a filter a list comes back final or as
+// a closure to finish with the query's own predicate; without one it comes back ranked, or to sort, and tied distances are replayed.
+template <class HasCandidate>
+bool Device::range_search_run(int nq, int entry_point, int top, float range, RangeFilter f, HasCandidate &&has_candidate, int *out_counts, int *out_flags,
+                              int layer)
+{
+    std::vector<SearchJob> jobs;
+    for (int i = 0; i < nq; ++i)
+        if (has_candidate(i) || !(range >= 0.0f)) jobs.push_back(SearchJob{i, entry_point, top, layer, -1});
+    const int nj = (int)jobs.size();
+    f.skipped = nq - nj;
+    RangeResults r;
+    if (!range_batch(jobs.data(), nj, range, &r, f)) return false;
+    for (int j = 0; j < nj; ++j) {
+        const int i = jobs[(size_t)j].qref;
+        out_counts[i] = 0;
+        out_flags[i] = r.flag[(size_t)j];
+        if (out_flags[i]) continue;
+        SearchHit *b = r.found + r.off[(size_t)j], *e = b + r.cnt[(size_t)j];
+        if (f.kind != RangeFilter::kNone && r.state[(size_t)j] != kRangeFinal) { // a closure: partition, sort, replay where the allowed results tie
+            if (!finish_closure(layer, r.entry[(size_t)j], range, b, r.cnt[(size_t)j], f.of(i), nq, out_counts, &out_counts[i])) return false;
+            continue;
+        }
+        out_counts[i] = r.cnt[(size_t)j];
+        if (f.kind == RangeFilter::kNone) {
+            bool tie = r.state[(size_t)j] == kRangeTied; // (the device replays what it can: this is what it handed back)
+            if (r.state[(size_t)j] == kRangeHostSort) {
+                std::sort(b, e, range_hit_less);
+                for (SearchHit *p = b; p + 1 < e; ++p) tie |= p[0].dist == p[1].dist; // also -0 next to +0
+            }
+            if (tie) { // OrderBy keeps the heap array's order there (HNSWIndex.cs:155): replay the heaps on the committed graph
+                std::vector<NodeDist> ordered;
+                replay_range_heaps(host_list_of(layer), 2 * hg_->M, r.entry[(size_t)j], range, b, r.cnt[(size_t)j], ordered);
+                for (const NodeDist &nd : ordered) abi_range_.push_back(SearchHit{nd.id, nd.dist});
+                continue;
+            }
+        }
+        abi_range_.insert(abi_range_.end(), b, e); // the results, in the reference's order
+    }
+    return true;
+}
+
 // allow_bits == nullptr: no filter (range_search)
 bool Device::range_search_filtered(const float *queries, int nq, int entry_point, float range, const uint32_t *allow_bits, long long nbits,
                                    int *out_counts, int *out_flags, int layer)
@@ -2789,40 +2817,12 @@ bool Device::range_search_filtered(const float *queries, int nq, int entry_point
     int top;
     const bool args_ok = !(allow_bits && nbits < 0); // (false: "range_search: bad argument", in abi_entry's place for it)
     if (!abi_begin("range_search", queries, nq, entry_point, layer, &top, args_ok)) return false;
-    std::vector<SearchJob> jobs((size_t)nq);
-    for (int i = 0; i < nq; ++i) jobs[(size_t)i] = SearchJob{i, entry_point, top, layer, -1};
-    RangeResults r;
-    if (!range_batch(jobs.data(), nq, range, &r, allow_bits, nbits)) return false;
-    for (int i = 0; i < nq; ++i) {
-        out_counts[i] = 0;
-        out_flags[i] = r.flag[(size_t)i];
-        if (out_flags[i]) continue;
-        SearchHit *b = r.found + r.off[(size_t)i], *e = b + r.cnt[(size_t)i];
-        if (allow_bits && r.state[(size_t)i] != kRangeFinal) { // a closure: partition, sort, replay where the allowed results tie
-            if (!finish_closure(layer, r.entry[(size_t)i], range, b, r.cnt[(size_t)i], AllowBits{allow_bits, nbits}, nq, out_counts, &out_counts[i])) return false;
-            continue;
-        }
-        bool tie = r.state[(size_t)i] == kRangeTied; // (the device replays what it can: this is what it handed back)
-        if (r.state[(size_t)i] == kRangeHostSort) {
-            std::sort(b, e, range_hit_less);
-            for (SearchHit *p = b; p + 1 < e; ++p) tie |= p[0].dist == p[1].dist; // also -0 next to +0
-        }
-        out_counts[i] = r.cnt[(size_t)i];
-        if (tie) { // OrderBy keeps the heap array's order there (HNSWIndex.cs:155): replay the heaps on the committed graph
-            std::vector<NodeDist> ordered;
-            replay_range_heaps(host_list_of(layer), 2 * hg_->M, r.entry[(size_t)i], range, b, r.cnt[(size_t)i], ordered);
-            for (const NodeDist &nd : ordered) abi_range_.push_back(SearchHit{nd.id, nd.dist});
-            continue;
-        }
-        abi_range_.insert(abi_range_.end(), b, e);
-    }
-    return true;
+    return range_search_run(nq, entry_point, top, range, AllowBits{allow_bits, nbits}, [](int) { return true; }, out_counts, out_flags, layer);
 }
 
 // range_search_filtered with a group filter per query: query i is answered as with the allow-set
 // { id : row_group[id] == query_group[i] }, every group in one traversal launch.  Only the labels of graph ids count.  A query whose
-// group holds no graph id gets an empty list without a job -- when range >= 0 only: below zero the filtered call can throw on an
-// empty set too (range_replay.h), so those queries run.
+// group holds no graph id gets an empty list without a job (when range >= 0: range_search_run).
 bool Device::range_search_grouped(const float *queries, int nq, int entry_point, float range, const int *row_group, long long n_row_group,
                                   const int *query_group, int n_groups, int *out_counts, int *out_flags, int layer)
 {
@@ -2839,43 +2839,14 @@ bool Device::range_search_grouped(const float *queries, int nq, int entry_point,
     std::vector<char> has_id((size_t)n_groups, 0);
     for (long long id = 0; id < n_lab; ++id)
         if (row_group[id] >= 0 && row_group[id] < n_groups) has_id[(size_t)row_group[id]] = 1;
-    std::vector<SearchJob> jobs;
-    std::vector<int> qi_of, group_of;
-    for (int i = 0; i < nq; ++i)
-        if (has_id[(size_t)query_group[i]] || !(range >= 0.0f)) {
-            jobs.push_back(SearchJob{i, entry_point, top, layer, -1});
-            qi_of.push_back(i);
-            group_of.push_back(query_group[i]);
-        }
-    const int nj = (int)jobs.size();
-    RangeGroups grp;
-    grp.label = row_group;
-    grp.n_label = n_lab;
-    grp.group_of = group_of.data();
-    grp.skipped = nq - nj;
-    RangeResults r;
-    if (!range_batch(jobs.data(), nj, range, &r, nullptr, 0, &grp)) return false;
-    for (int j = 0; j < nj; ++j) { // (in query order: abi_range_ holds the lists as range_results hands them out)
-        const int i = qi_of[(size_t)j];
-        out_flags[i] = r.flag[(size_t)j];
-        if (out_flags[i]) continue;
-        SearchHit *b = r.found + r.off[(size_t)j], *e = b + r.cnt[(size_t)j];
-        if (r.state[(size_t)j] == kRangeFinal) { // the results, in the reference's order
-            out_counts[i] = r.cnt[(size_t)j];
-            abi_range_.insert(abi_range_.end(), b, e);
-            continue;
-        }
-        // a closure: partition, sort, replay where the allowed results tie
-        if (!finish_closure(layer, r.entry[(size_t)j], range, b, r.cnt[(size_t)j], AllowPred{row_group, n_lab, group_of[(size_t)j]}, nq, out_counts, &out_counts[i]))
-            return false;
-    }
-    return true;
+    return range_search_run(nq, entry_point, top, range, RangeFilter::labels(row_group, n_lab, query_group),
+                            [&](int i) { return has_id[(size_t)query_group[i]] != 0; }, out_counts, out_flags, layer);
 }
 
 // range_search_grouped with a tag mask per query: query i is answered as with the allow-set
 // { id : row_tags[id] matches query_tags[i] }, every mask in one traversal launch.  Only the words of graph ids count; which masks
-// have a candidate among them the device counts (tag_counts) -- no host pass over the words.  A query whose mask has none gets an
-// empty list without a job when range >= 0 only, as for a group without ids.
+// have a candidate among them the device counts (tag_counts) -- no host pass over the words -- and the words stay there for the
+// sort kernel.  A query whose mask has none gets an empty list without a job, as for a group without ids.
 bool Device::range_search_tagged(const float *queries, int nq, int entry_point, float range, const uint32_t *row_tags, long long n_row_tags,
                                  const uint32_t *query_tags, int match, int *out_counts, int *out_flags, int layer)
 {
@@ -2892,41 +2863,9 @@ bool Device::range_search_tagged(const float *queries, int nq, int entry_point, 
     const long long n_lab = std::min<long long>(n_row_tags, g_n_);
     std::vector<int> cnt;
     if (!tag_candidates(row_tags, n_lab, tc.masks, match, cnt)) return false;
-    std::vector<SearchJob> jobs;
-    std::vector<int> qi_of;
-    std::vector<uint32_t> mask_of;
-    for (int i = 0; i < nq; ++i)
-        if (cnt[(size_t)tc.of[(size_t)i]] > 0 || !(range >= 0.0f)) {
-            jobs.push_back(SearchJob{i, entry_point, top, layer, -1});
-            qi_of.push_back(i);
-            mask_of.push_back(query_tags[i]);
-        }
-    const int nj = (int)jobs.size();
-    RangeTags tags;
-    tags.words = row_tags;
-    tags.n_words = n_lab;
-    tags.mask_of = mask_of.data();
-    tags.match = match;
-    tags.skipped = nq - nj;
-    tags.resident = n_lab > 0;
-    tags.n_masks = tc.masks.size();
-    RangeResults r;
-    if (!range_batch(jobs.data(), nj, range, &r, nullptr, 0, nullptr, &tags)) return false;
-    for (int j = 0; j < nj; ++j) { // (in query order: abi_range_ holds the lists as range_results hands them out)
-        const int i = qi_of[(size_t)j];
-        out_flags[i] = r.flag[(size_t)j];
-        if (out_flags[i]) continue;
-        SearchHit *b = r.found + r.off[(size_t)j], *e = b + r.cnt[(size_t)j];
-        if (r.state[(size_t)j] == kRangeFinal) { // the results, in the reference's order
-            out_counts[i] = r.cnt[(size_t)j];
-            abi_range_.insert(abi_range_.end(), b, e);
-            continue;
-        }
-        // a closure: partition, sort, replay where the allowed results tie -- with the query's own predicate
-        if (!finish_closure(layer, r.entry[(size_t)j], range, b, r.cnt[(size_t)j], AllowPred{row_tags, n_lab, mask_of[(size_t)j], match}, nq, out_counts, &out_counts[i]))
-            return false;
-    }
-    return true;
+    RangeFilter f = RangeFilter::tags(row_tags, n_lab, query_tags, match, tc.masks.size());
+    f.resident = n_lab > 0;
+    return range_search_run(nq, entry_point, top, range, f, [&](int i) { return cnt[(size_t)tc.of[(size_t)i]] > 0; }, out_counts, out_flags, layer);
 }
 
 bool Device::range_results(int *out_ids, float *out_d)
@@ -3571,38 +3510,37 @@ bool Device::exact_knn_grouped_scan(const char *who, const float *queries, const
 // (tag_counts) sum to at most kTagListEntries (`tag_list_cap` lowers it); a mask with more is a batch alone, and fits because
 // n < 2^31.  Per batch dk_tag_lists.h builds the CSR in x_ids_ and exact_knn_grouped_scan answers the queries of the batch's masks;
 // with more than one batch their rows go through arrays of the batch's size and are scattered to the caller's order.
-bool Device::exact_knn_tagged(const float *queries, int nq, long long n_rows, int k, const uint32_t *row_tags, long long n_row_tags, const uint32_t *query_tags,
-                              int match, int *out_ids, float *out_d)
+//
+// The batches of masks of a tagged flat scan, walked: the candidates of every distinct mask counted (tag_counts, into cnt); then, for
+// each batch of masks that holds a candidate, the ExactGroupedCall of its lists (k: the keys a list keeps, as exact_grouped_plan
+// takes it), the lists built in x_ids_ (timed into xt_list_ms_ while profiling is on), and on_batch(gc, bq, resident, sel, qg) for
+// the batch's queries -- those of its masks that have a candidate, sel[j] their places in the caller's order and qg[j] their
+// lists: bq / resident name them as the grouped scans take queries, the caller's own when the batch is the whole call, a gathered
+// copy otherwise.  info: the six counters a tagged scan leads with -- calls that counted candidates, distinct masks, queries
+// scanned, queries without a scan, list entries built, batches -- added to when every batch went through.
+template <class OnBatch>
+bool Device::exact_tag_batches(const char *who, const float *queries, int nq, long long n, int k, const uint32_t *row_tags, const TagCall &tc, int match,
+                               std::vector<int> &cnt, uint64_t info[6], OnBatch &&on_batch)
 {
-    if (nq <= 0) return true;
-    const char *who = "exact_knn_tagged";
-    const auto fail = [&](const std::string &what) { set_dev_error(std::string(who) + ": " + what); return false; };
-    if (!(out_ids && out_d && k >= 1 && n_rows >= 0)) return fail("bad argument");
-    if (!row_tags || n_row_tags < 0) return fail("row_tags must not be NULL and n_row_tags must be >= 0");
-    if (!query_tags) return fail("query_tags must not be NULL");
-    if (k > kExactMaxK) return fail("k = " + std::to_string(k) + " is above the limit of " + std::to_string(kExactMaxK));
-    TagCall tc;
-    if (!tag_args_ok(who, query_tags, nq, match, &tc)) return false;
-    // ids that exist and have a word: a row beyond what was uploaded is never dereferenced, whatever n_rows and n_row_tags say
-    const long long n = std::min({n_rows, n_rows_hw_, n_row_tags});
-    if (n <= 0) { pad_results(out_ids, out_d, (size_t)nq * (size_t)k); return true; }
-    if (!queries && (nq > n_queries_ || tail_.n > 0)) return fail("queries == NULL needs a resident query set of at least nq rows (hnswdev_set_queries)");
+    if (!queries && (nq > n_queries_ || tail_.n > 0)) {
+        set_dev_error(std::string(who) + ": queries == NULL needs a resident query set of at least nq rows (hnswdev_set_queries)");
+        return false;
+    }
     const int D = (int)tc.masks.size();
-    std::vector<int> cnt;
     if (!bind() || !tag_counts(row_tags, n, tc.masks, match, cnt)) return false;
     hipStream_t st = S(stream_);
     const long long forced = diag("tag_list_cap", 0), cap = forced > 0 ? forced : kTagListEntries;
     std::vector<int> gq((size_t)D, 0);
     for (int i = 0; i < nq; ++i) gq[(size_t)tc.of[(size_t)i]] += 1;
     uint64_t scanned_q = 0, listed = 0, batches = 0;
-    std::vector<int> sel, qg, t_ids;
-    std::vector<float> t_q, t_d;
+    std::vector<int> sel, qg;
+    std::vector<float> t_q;
     for (int d0 = 0; d0 < D;) {
         // the batch: masks d0 .. d1 - 1, `sum` entries
         long long sum = cnt[(size_t)d0];
         int d1 = d0 + 1;
         while (d1 < D && sum + cnt[(size_t)d1] <= cap) sum += cnt[(size_t)d1++];
-        if (sum == 0) { d0 = d1; continue; } // (no mask of it has a candidate: its queries are padded below)
+        if (sum == 0) { d0 = d1; continue; } // (no mask of it has a candidate: its queries are left to the caller)
         ExactGroupedCall gc;
         gc.gq.assign((size_t)D, 0);
         gc.cnt.assign((size_t)D, 0);
@@ -3625,7 +3563,7 @@ bool Device::exact_knn_tagged(const float *queries, int nq, long long n_rows, in
             HIP_OK(hipEventElapsedTime(&ms, E(ev0_), E(ev1_)));
             xt_list_ms_ += ms;
         }
-        // the batch's queries: those of its masks that have a candidate
+        // the batch's queries: those of its masks that have a candidate, in the caller's order
         sel.clear();
         qg.clear();
         for (int i = 0; i < nq; ++i) {
@@ -3633,30 +3571,56 @@ bool Device::exact_knn_tagged(const float *queries, int nq, long long n_rows, in
             if (d >= d0 && d < d1 && cnt[(size_t)d] > 0) { sel.push_back(i); qg.push_back(d); }
         }
         const int nb = (int)sel.size();
-        uint64_t blocks = 0;
-        if (nb == nq) { // every query of the call: straight into the caller's arrays
-            if (!exact_knn_grouped_scan(who, queries, nullptr, nq, k, qg.data(), D, gc, out_ids, out_d, &blocks)) return false;
-        } else {
-            t_ids.resize((size_t)nb * k);
-            t_d.resize((size_t)nb * k);
-            if (queries) {
-                t_q.resize((size_t)nb * (size_t)dim_);
-                for (int j = 0; j < nb; ++j) memcpy(&t_q[(size_t)j * dim_], queries + (size_t)sel[(size_t)j] * dim_, sizeof(float) * (size_t)dim_);
-            }
-            if (!exact_knn_grouped_scan(who, queries ? t_q.data() : nullptr, queries ? nullptr : sel.data(), nb, k, qg.data(), D, gc, t_ids.data(), t_d.data(), &blocks)) return false;
-            for (int j = 0; j < nb; ++j) {
-                memcpy(out_ids + (size_t)sel[(size_t)j] * k, &t_ids[(size_t)j * k], 4u * (size_t)k);
-                memcpy(out_d + (size_t)sel[(size_t)j] * k, &t_d[(size_t)j * k], 4u * (size_t)k);
-            }
+        const bool gathered = nb != nq && queries; // (resident queries are named by sel instead)
+        if (gathered) {
+            t_q.resize((size_t)nb * (size_t)dim_);
+            for (int j = 0; j < nb; ++j) memcpy(&t_q[(size_t)j * dim_], queries + (size_t)sel[(size_t)j] * dim_, sizeof(float) * (size_t)dim_);
         }
+        if (!on_batch(gc, gathered ? t_q.data() : queries, nb == nq || queries ? nullptr : sel.data(), sel, qg.data())) return false;
         scanned_q += (uint64_t)nb;
         listed += (uint64_t)sum;
         batches += 1;
         d0 = d1;
     }
+    info[0] += 1; info[1] += (uint64_t)D; info[2] += scanned_q; info[3] += (uint64_t)nq - scanned_q; info[4] += listed; info[5] += batches;
+    return true;
+}
+
+// exact_knn_tagged: every batch one grouped top-k scan.
+bool Device::exact_knn_tagged(const float *queries, int nq, long long n_rows, int k, const uint32_t *row_tags, long long n_row_tags, const uint32_t *query_tags,
+                              int match, int *out_ids, float *out_d)
+{
+    if (nq <= 0) return true;
+    const char *who = "exact_knn_tagged";
+    const auto fail = [&](const std::string &what) { set_dev_error(std::string(who) + ": " + what); return false; };
+    if (!(out_ids && out_d && k >= 1 && n_rows >= 0)) return fail("bad argument");
+    if (!row_tags || n_row_tags < 0) return fail("row_tags must not be NULL and n_row_tags must be >= 0");
+    if (!query_tags) return fail("query_tags must not be NULL");
+    if (k > kExactMaxK) return fail("k = " + std::to_string(k) + " is above the limit of " + std::to_string(kExactMaxK));
+    TagCall tc;
+    if (!tag_args_ok(who, query_tags, nq, match, &tc)) return false;
+    // ids that exist and have a word: a row beyond what was uploaded is never dereferenced, whatever n_rows and n_row_tags say
+    const long long n = std::min({n_rows, n_rows_hw_, n_row_tags});
+    if (n <= 0) { pad_results(out_ids, out_d, (size_t)nq * (size_t)k); return true; }
+    const int D = (int)tc.masks.size();
+    std::vector<int> cnt, t_ids;
+    std::vector<float> t_d;
+    const bool ok = exact_tag_batches(who, queries, nq, n, k, row_tags, tc, match, cnt, xt_info_, [&](const ExactGroupedCall &gc, const float *bq, const int *resident, const std::vector<int> &sel, const int *qg) {
+        const int nb = (int)sel.size();
+        uint64_t blocks = 0;
+        if (nb == nq) return exact_knn_grouped_scan(who, bq, resident, nq, k, qg, D, gc, out_ids, out_d, &blocks); // straight into the caller's arrays
+        t_ids.resize((size_t)nb * k);
+        t_d.resize((size_t)nb * k);
+        if (!exact_knn_grouped_scan(who, bq, resident, nb, k, qg, D, gc, t_ids.data(), t_d.data(), &blocks)) return false;
+        for (int j = 0; j < nb; ++j) {
+            memcpy(out_ids + (size_t)sel[(size_t)j] * k, &t_ids[(size_t)j * k], 4u * (size_t)k);
+            memcpy(out_d + (size_t)sel[(size_t)j] * k, &t_d[(size_t)j * k], 4u * (size_t)k);
+        }
+        return true;
+    });
+    if (!ok) return false;
     for (int i = 0; i < nq; ++i) // a mask without a candidate: padding, no scan
         if (cnt[(size_t)tc.of[(size_t)i]] == 0) pad_results(out_ids + (size_t)i * k, out_d + (size_t)i * k, (size_t)k);
-    xt_info_[0] += 1; xt_info_[1] += (uint64_t)D; xt_info_[2] += scanned_q; xt_info_[3] += (uint64_t)nq - scanned_q; xt_info_[4] += listed; xt_info_[5] += batches;
     return true;
 }
 
@@ -4076,73 +4040,26 @@ bool Device::exact_range_tagged(const float *queries, int nq, long long n_rows, 
         // ids that exist and have a word: a row beyond what was uploaded is never dereferenced, whatever n_rows and n_row_tags say
         const long long n = std::min({n_rows, n_rows_hw_, n_row_tags});
         if (n <= 0) return true; // no candidate: empty lists, nothing launched
-        if (!queries && (nq > n_queries_ || tail_.n > 0)) return fail("queries == NULL needs a resident query set of at least nq rows (hnswdev_set_queries)");
         const int D = (int)tc.masks.size();
-        std::vector<int> cnt;
-        if (!bind() || !tag_counts(row_tags, n, tc.masks, match, cnt)) return false;
-        hipStream_t st = S(stream_);
-        const long long forced = diag("tag_list_cap", 0), cap = forced > 0 ? forced : kTagListEntries;
-        std::vector<int> gq((size_t)D, 0);
-        for (int i = 0; i < nq; ++i) gq[(size_t)tc.of[(size_t)i]] += 1;
-        uint64_t scanned_q = 0, listed = 0, batches = 0, info[4] = {0, 0, 0, 0};
-        std::vector<int> sel, qg, t_cnt;
-        std::vector<float> t_q;
+        uint64_t info[4] = {0, 0, 0, 0};
+        int batches = 0;
+        std::vector<int> cnt, t_cnt;
         std::vector<size_t> at_of((size_t)nq, 0); // where query i's list starts in xr_ids_ as the batches left it
-        for (int d0 = 0; d0 < D;) {
-            // the batch: masks d0 .. d1 - 1, `sum` entries
-            long long sum = cnt[(size_t)d0];
-            int d1 = d0 + 1;
-            while (d1 < D && sum + cnt[(size_t)d1] <= cap) sum += cnt[(size_t)d1++];
-            if (sum == 0) { d0 = d1; continue; } // (no mask of it has a candidate: its queries' lists stay empty)
-            ExactGroupedCall gc;
-            gc.gq.assign((size_t)D, 0);
-            gc.cnt.assign((size_t)D, 0);
-            gc.goff.assign((size_t)D, 0);
-            gc.n = n;
-            gc.listed = (uint64_t)sum;
-            long long at = 0;
-            for (int d = d0; d < d1; ++d) { gc.gq[(size_t)d] = gq[(size_t)d]; gc.cnt[(size_t)d] = cnt[(size_t)d]; gc.goff[(size_t)d] = (int)at; at += cnt[(size_t)d]; }
-            if (!exact_grouped_plan(who, 0, &gc)) return false;
-            if (!x_ids_.grow((size_t)sum)) return false;
-            const bool timed = profiling_;
-            if (timed && (!ev0_.create(true) || !ev1_.create(true))) return false;
-            if (timed) HIP_OK(hipEventRecord(E(ev0_), st));
-            HIP_OK(tag_lists_launch(s_ttags_, n, s_tmask_.get() + d0, d1 - d0, match, s_tcnt_.get() + d0, s_tcnt_.get() + D + d0, s_tcnt_.get() + 2 * (size_t)D + d0,
-                                    x_ids_, sum, st));
-            if (timed) {
-                HIP_OK(hipEventRecord(E(ev1_), st));
-                HIP_OK(hipStreamSynchronize(st)); // (the scan records the same pair of events)
-                float ms = 0.f;
-                HIP_OK(hipEventElapsedTime(&ms, E(ev0_), E(ev1_)));
-                xt_list_ms_ += ms;
-            }
-            // the batch's queries: those of its masks that have a candidate, in the caller's order
-            sel.clear();
-            qg.clear();
-            for (int i = 0; i < nq; ++i) {
-                const int d = tc.of[(size_t)i];
-                if (d >= d0 && d < d1 && cnt[(size_t)d] > 0) { sel.push_back(i); qg.push_back(d); }
-            }
+        const bool ok = exact_tag_batches(who, queries, nq, n, 0, row_tags, tc, match, cnt, xrt_info_, [&](const ExactGroupedCall &gc, const float *bq, const int *resident, const std::vector<int> &sel, const int *qg) {
             const int nb = (int)sel.size();
-            const size_t base = xr_ids_.size();
+            size_t o = xr_ids_.size();
             if (nb == nq) { // every query of the call: straight into the caller's counts
-                if (!exact_range_grouped_scan(who, queries, nullptr, nq, range, qg.data(), D, gc, out_counts, info)) return false;
+                if (!exact_range_grouped_scan(who, bq, resident, nq, range, qg, D, gc, out_counts, info)) return false;
             } else if (nb > 0) {
                 t_cnt.assign((size_t)nb, 0);
-                if (queries) {
-                    t_q.resize((size_t)nb * (size_t)dim_);
-                    for (int j = 0; j < nb; ++j) memcpy(&t_q[(size_t)j * dim_], queries + (size_t)sel[(size_t)j] * dim_, sizeof(float) * (size_t)dim_);
-                }
-                if (!exact_range_grouped_scan(who, queries ? t_q.data() : nullptr, queries ? nullptr : sel.data(), nb, range, qg.data(), D, gc, t_cnt.data(), info)) return false;
+                if (!exact_range_grouped_scan(who, bq, resident, nb, range, qg, D, gc, t_cnt.data(), info)) return false;
                 for (int j = 0; j < nb; ++j) out_counts[sel[(size_t)j]] = t_cnt[(size_t)j];
             }
-            size_t o = base;
             for (int j = 0; j < nb; ++j) { at_of[(size_t)sel[(size_t)j]] = o; o += (size_t)out_counts[sel[(size_t)j]]; }
-            scanned_q += (uint64_t)nb;
-            listed += (uint64_t)sum;
             batches += 1;
-            d0 = d1;
-        }
+            return true;
+        });
+        if (!ok) return false;
         if (batches > 1) { // the batches' lists, moved into the caller's query order
             std::vector<int> ids(xr_ids_.size());
             std::vector<float> d(xr_d_.size());
@@ -4155,7 +4072,6 @@ bool Device::exact_range_tagged(const float *queries, int nq, long long n_rows, 
             xr_ids_.swap(ids);
             xr_d_.swap(d);
         }
-        xrt_info_[0] += 1; xrt_info_[1] += (uint64_t)D; xrt_info_[2] += scanned_q; xrt_info_[3] += (uint64_t)nq - scanned_q; xrt_info_[4] += listed; xrt_info_[5] += batches;
         xrt_info_[6] += info[1]; xrt_info_[7] += info[2]; xrt_info_[8] += info[3];
         return true;
     });

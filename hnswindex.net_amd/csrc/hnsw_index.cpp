@@ -2515,7 +2515,7 @@ int HnswIndex::knn_query_resident(int k, int *out_ids, float *out_dists, std::st
 
 // Host lock-step range search for the queries listed in `which` (nullptr: all `count` queries).
 int HnswIndex::range_query_lockstep(const int *which, int count, float range, std::vector<std::vector<NodeDist>> &out, std::string &err,
-                                    AllowBits allow, int layer, const RangeGroupSpec *grp)
+                                    const RangeFilter &f, int layer)
 {
     if (!refresh_host_lists(err)) return -1;
     RangeSource src;
@@ -2528,7 +2528,7 @@ int HnswIndex::range_query_lockstep(const int *which, int count, float range, st
         j.qi = qi;
         j.range = range;
         j.out = &out[(size_t)qi];
-        j.allow = grp ? grp->of(qi) : AllowPred{allow}; // (grouped: the label predicate of this query's group)
+        j.allow = f.of(qi); // (a key per query: the predicate of this query's group or mask)
         j.layer = layer;
     }
     if (!engine()->run(src, count)) { err = get_dev_error(); return -1; }
@@ -2542,44 +2542,20 @@ int HnswIndex::range_query_lockstep(const int *which, int count, float range, st
 // distance, and for a query holding such a pair the heaps are replayed on the host from the known distances.
 // With an allow-set the device hands back each list either final or as its closure (Device::range_batch); closures are
 // partitioned by the filter, sorted and, where allowed results tie or range < 0, replayed (finish_filtered_range).
-// grp (range_query_grouped): the jobs are the queries of grp->run, each filtered by its group's label predicate; job i answers
-// query qi(i), and everything below indexes the device's results by job and `out` by query.
-int HnswIndex::range_query_device(int n_queries, float range, std::vector<std::vector<NodeDist>> &out, std::string &err, AllowBits allow, int layer,
-                                  const RangeGroupSpec *grp)
+// The jobs are the queries listed in `which` (nullptr: all `count` queries), each filtered by f's predicate for it; job i answers
+// query jobs[i].qref, and everything below indexes the device's results by job and `out` by query.
+int HnswIndex::range_query_device(const int *which, int count, float range, std::vector<std::vector<NodeDist>> &out, std::string &err, const RangeFilter &f,
+                                  int layer)
 {
     if (!sync_graph(err)) return -1;
-    const int count = grp ? (int)grp->run->size() : n_queries; // jobs
-    const auto qi = [&](size_t job) { return grp ? (*grp->run)[job] : (int)job; };
     std::vector<SearchJob> jobs((size_t)count);
     const int ep = graph_.entry, top = graph_.top_layer();
-    for (int i = 0; i < count; ++i) jobs[(size_t)i] = SearchJob{qi((size_t)i), ep, top, layer, -1};
+    for (int i = 0; i < count; ++i) jobs[(size_t)i] = SearchJob{which ? which[i] : i, ep, top, layer, -1};
+    const auto qi = [&](size_t job) { return jobs[job].qref; };
     Device::RangeResults r;
     g_pt.rq_queries += count;
-    const bool filtered = allow.bits != nullptr || grp != nullptr;
-    std::vector<int> group_of;
-    Device::RangeGroups dev_grp;
-    std::vector<uint32_t> mask_of;
-    Device::RangeTags dev_tags;
-    const bool tagged = grp && grp->tags;
-    if (tagged) {
-        mask_of.resize((size_t)count);
-        for (int i = 0; i < count; ++i) mask_of[(size_t)i] = grp->query_tags[qi((size_t)i)];
-        dev_tags.words = grp->tags;
-        dev_tags.n_words = grp->n_tags;
-        dev_tags.mask_of = mask_of.data();
-        dev_tags.match = grp->match;
-        dev_tags.skipped = grp->skipped;
-        dev_tags.resident = grp->resident;
-        dev_tags.n_masks = grp->n_masks;
-    } else if (grp) {
-        group_of.resize((size_t)count);
-        for (int i = 0; i < count; ++i) group_of[(size_t)i] = grp->query_group[qi((size_t)i)];
-        dev_grp.label = grp->label;
-        dev_grp.n_label = grp->n_label;
-        dev_grp.group_of = group_of.data();
-        dev_grp.skipped = grp->skipped;
-    }
-    { Tick t(g_pt.rq_batch); if (!dev_->range_batch(jobs.data(), count, range, &r, allow.bits, allow.n, grp && !tagged ? &dev_grp : nullptr, tagged ? &dev_tags : nullptr)) { err = get_dev_error(); return -1; } }
+    const bool filtered = f.kind != RangeFilter::kNone;
+    { Tick t(g_pt.rq_batch); if (!dev_->range_batch(jobs.data(), count, range, &r, f)) { err = get_dev_error(); return -1; } }
     // host threads over the queries: sort each result list; a list holding two equal distances is replayed instead
     auto parallel_for = [&](size_t n, size_t grain, const std::function<void(size_t, size_t)> &body) {
         std::atomic<size_t> next{0};
@@ -2627,7 +2603,7 @@ int HnswIndex::range_query_device(int n_queries, float range, std::vector<std::v
                 const auto list_of = [&](int id) { return graph_.list(id, layer); };
                 if (filtered) {
                     if (finish_filtered_range(list_of, graph_.max_edges_at(0), r.entry[(size_t)i], range, r.found + r.off[(size_t)i], r.cnt[(size_t)i],
-                                              grp ? grp->of(qi((size_t)i)) : AllowPred{allow}, out[(size_t)qi((size_t)i)]) == kRangeHeapEmpty)
+                                              f.of(qi((size_t)i)), out[(size_t)qi((size_t)i)]) == kRangeHeapEmpty)
                         heap_empty.store(true);
                 } else
                     replay_range_heaps(list_of, graph_.max_edges_at(0), r.entry[(size_t)i], range, r.found + r.off[(size_t)i], r.cnt[(size_t)i], out[(size_t)qi((size_t)i)]);
@@ -2635,8 +2611,37 @@ int HnswIndex::range_query_device(int n_queries, float range, std::vector<std::v
         });
         if (heap_empty.load()) { err = kHeapEmptyError; return -1; }
     }
-    if (!redo.empty()) return range_query_lockstep(redo.data(), (int)redo.size(), range, out, err, allow, layer, grp);
+    if (!redo.empty()) return range_query_lockstep(redo.data(), (int)redo.size(), range, out, err, f, layer);
     return 0;
+}
+
+// What range_query_grouped and range_query_tagged share once their own arguments stand, in answer_by_class's idiom: the queries
+// fall into classes -- a group, a distinct mask -- class_of(qi) names query qi's, and classes_with_id(has) marks the classes that
+// hold a graph id (false: failed, err filed).  A query of a class without one gets an empty list and no traversal -- when range >= 0;
+// below zero the filtered call can pop an empty heap for an empty set too (range_replay.h), so those queries run.  The others are
+// answered in one device traversal (Device::range_batch with f); hand-backs, and the whole call when the traversal does not run on
+// the device, go the lock-step way with each query's own predicate.
+template <class ClassOf, class ClassesWithId>
+int HnswIndex::range_by_class(const char *who, const float *queries, int count, int dim, float range, int layer, RangeFilter f, ClassOf class_of,
+                              ClassesWithId classes_with_id, std::vector<std::vector<NodeDist>> &out, std::string &err)
+{
+    if (graph_.entry < 0) return 0; // HNSWIndex.cs:146
+    if (!layer_ok(layer, err)) { err = "System.IndexOutOfRangeException: " + std::string(who) + ": " + err; return -1; }
+    if (!ensure_dim(dim, err)) return -1;
+    std::vector<char> has_id;
+    if (!classes_with_id(has_id)) return -1;
+    std::vector<int> run;
+    for (int i = 0; i < count; ++i)
+        if (has_id[(size_t)class_of(i)] || !(range >= 0.0f)) run.push_back(i);
+    f.skipped = count - (long long)run.size();
+    const bool on_device = p_.device_traversal && dev_->traversal_fits(1, false, p_.max_edges);
+    if (run.empty() && !on_device) return 0;
+    resident_queries_ = 0; // the resident set is replaced: a later knn_query_resident must not answer for these rows
+    if (!dev_->set_queries(queries, count)) { err = get_dev_error(); return -1; }
+    const int rc = on_device ? range_query_device(run.data(), (int)run.size(), range, out, err, f, layer)
+                             : range_query_lockstep(run.data(), (int)run.size(), range, out, err, f, layer);
+    if (rc < 0 && err == kHeapEmptyError) out.assign((size_t)count, {}); // the whole batch fails (Parallel.For rethrows)
+    return rc;
 }
 
 // RangeQuery with a group filter per query: range_query's filtered call for every group at once.  The labels go to
@@ -2649,35 +2654,17 @@ int HnswIndex::range_query_grouped(const float *queries, int count, int dim, flo
     if (count <= 0) return 0;
     const char *who = "hnsw_mi355x_range_query_grouped";
     if (!group_args_ok(who, query_group, count, n_groups, err)) return -1;
-    if (graph_.entry < 0) return 0; // HNSWIndex.cs:146
-    if (!layer_ok(layer, err)) { err = "System.IndexOutOfRangeException: " + std::string(who) + ": " + err; return -1; }
-    if (!ensure_dim(dim, err)) return -1;
     std::vector<int> live;
     (void)live_labels(row_group, n_row_group, live);
     const long long n_lab = std::min<long long>(n_row_group, graph_.length); // only the labels of graph ids count
-    std::vector<char> has_id((size_t)n_groups, 0); // groups that hold an id of the graph
-    for (long long id = 0; id < n_lab; ++id)
-        if (row_group[id] >= 0 && row_group[id] < n_groups) has_id[(size_t)row_group[id]] = 1;
-    // a group without ids: an empty list, and no traversal -- when range >= 0; below zero the filtered call can pop an empty heap
-    // for an empty set too (range_replay.h), so those queries run
-    std::vector<int> run;
-    for (int i = 0; i < count; ++i)
-        if (has_id[(size_t)query_group[i]] || !(range >= 0.0f)) run.push_back(i);
-    RangeGroupSpec grp;
-    grp.label = row_group;
-    grp.n_label = n_lab;
-    grp.query_group = query_group;
-    grp.run = &run;
-    grp.skipped = count - (long long)run.size();
-    const bool on_device = p_.device_traversal && dev_->traversal_fits(1, false, p_.max_edges);
-    if (run.empty() && !on_device) return 0;
-    resident_queries_ = 0; // the resident set is replaced: a later knn_query_resident must not answer for these rows
-    if (!dev_->set_queries(queries, count)) { err = get_dev_error(); return -1; }
-    int rc;
-    if (on_device) rc = range_query_device(count, range, out, err, AllowBits{}, layer, &grp);
-    else rc = range_query_lockstep(run.data(), (int)run.size(), range, out, err, AllowBits{}, layer, &grp);
-    if (rc < 0 && err == kHeapEmptyError) out.assign((size_t)count, {}); // the whole batch fails (Parallel.For rethrows)
-    return rc;
+    return range_by_class(who, queries, count, dim, range, layer, RangeFilter::labels(row_group, n_lab, query_group), [&](int qi) { return query_group[qi]; },
+        [&](std::vector<char> &has_id) { // a host pass over the labels
+            has_id.assign((size_t)n_groups, 0);
+            for (long long id = 0; id < n_lab; ++id)
+                if (row_group[id] >= 0 && row_group[id] < n_groups) has_id[(size_t)row_group[id]] = 1;
+            return true;
+        },
+        out, err);
 }
 
 // RangeQuery with a tag mask per query: range_query's filtered call for every distinct mask at once.  The words
@@ -2692,37 +2679,20 @@ int HnswIndex::range_query_tagged(const float *queries, int count, int dim, floa
     const char *who = "hnsw_mi355x_range_query_tagged";
     TagCall tc;
     if (!tag_args_ok(who, query_tags, count, match, &tc, err)) return -1;
-    if (graph_.entry < 0) return 0; // HNSWIndex.cs:146
-    if (!layer_ok(layer, err)) { err = "System.IndexOutOfRangeException: " + std::string(who) + ": " + err; return -1; }
-    if (!ensure_dim(dim, err)) return -1;
     std::vector<uint32_t> live;
     (void)live_tags(row_tags, n_row_tags, live);
     const long long n_lab = std::min<long long>(n_row_tags, graph_.length); // only the words of graph ids count
-    std::vector<int> cnt;
-    if (!dev_->tag_candidates(row_tags, n_lab, tc.masks, match, cnt)) { err = get_dev_error(); return -1; }
-    // a mask without a candidate: an empty list, and no traversal -- when range >= 0; below zero the filtered call can pop an empty
-    // heap for an empty set too (range_replay.h), so those queries run
-    std::vector<int> run;
-    for (int i = 0; i < count; ++i)
-        if (cnt[(size_t)tc.of[(size_t)i]] > 0 || !(range >= 0.0f)) run.push_back(i);
-    RangeGroupSpec grp;
-    grp.tags = row_tags;
-    grp.n_tags = n_lab;
-    grp.query_tags = query_tags;
-    grp.match = match;
-    grp.resident = n_lab > 0;
-    grp.n_masks = tc.masks.size();
-    grp.run = &run;
-    grp.skipped = count - (long long)run.size();
-    const bool on_device = p_.device_traversal && dev_->traversal_fits(1, false, p_.max_edges);
-    if (run.empty() && !on_device) return 0;
-    resident_queries_ = 0; // the resident set is replaced: a later knn_query_resident must not answer for these rows
-    if (!dev_->set_queries(queries, count)) { err = get_dev_error(); return -1; }
-    int rc;
-    if (on_device) rc = range_query_device(count, range, out, err, AllowBits{}, layer, &grp);
-    else rc = range_query_lockstep(run.data(), (int)run.size(), range, out, err, AllowBits{}, layer, &grp);
-    if (rc < 0 && err == kHeapEmptyError) out.assign((size_t)count, {}); // the whole batch fails (Parallel.For rethrows)
-    return rc;
+    RangeFilter f = RangeFilter::tags(row_tags, n_lab, query_tags, match, tc.masks.size());
+    f.resident = n_lab > 0; // (classes_with_id below runs before the traversal, on these words)
+    return range_by_class(who, queries, count, dim, range, layer, f, [&](int qi) { return tc.of[(size_t)qi]; },
+        [&](std::vector<char> &has_id) {
+            std::vector<int> cnt;
+            if (!dev_->tag_candidates(row_tags, n_lab, tc.masks, match, cnt)) { err = get_dev_error(); return false; }
+            has_id.assign(cnt.size(), 0);
+            for (size_t d = 0; d < cnt.size(); ++d) has_id[d] = cnt[d] > 0;
+            return true;
+        },
+        out, err);
 }
 
 int HnswIndex::range_query(const float *queries, int count, int dim, float range, std::vector<std::vector<NodeDist>> &out, std::string &err,
@@ -2736,7 +2706,7 @@ int HnswIndex::range_query(const float *queries, int count, int dim, float range
     resident_queries_ = 0; // the resident set is replaced: a later knn_query_resident must not answer for these rows
     if (!dev_->set_queries(queries, count)) { err = get_dev_error(); return -1; }
     int rc;
-    if (p_.device_traversal && dev_->traversal_fits(1, false, p_.max_edges)) rc = range_query_device(count, range, out, err, allow, layer);
+    if (p_.device_traversal && dev_->traversal_fits(1, false, p_.max_edges)) rc = range_query_device(nullptr, count, range, out, err, allow, layer);
     else rc = range_query_lockstep(nullptr, count, range, out, err, allow, layer);
     if (rc < 0 && err == kHeapEmptyError) out.assign((size_t)count, {}); // the whole batch fails (Parallel.For rethrows)
     return rc;

@@ -163,7 +163,7 @@ public:
 
     // hnsw_mi355x_range_query_grouped: RangeQuery on `layer` with a group filter per query -- query i's list is byte
     // for byte what range_query returns for it with the ids j < n_row_group, row_group[j] == query_group[i] as the allow-set; the
-    // empty-heap rule fails the whole call as there.  One device traversal for every group (Device::range_batch with RangeGroups);
+    // empty-heap rule fails the whole call as there.  One device traversal for every group (Device::range_batch with a RangeFilter of labels);
     // hand-backs, and the whole call when the traversal does not run on the device, go the lock-step way with the label predicate.
     // A query whose group holds no graph id is answered with an empty list without a traversal when range >= 0.  Exclusive lock.
     int range_query_grouped(const float *queries, int count, int dim, float range, int layer, const int *row_group, long long n_row_group,
@@ -172,7 +172,7 @@ public:
     // hnsw_mi355x_range_query_tagged: RangeQuery on `layer` with a tag mask per query -- query i's list is byte for
     // byte what range_query returns for it with the ids j < n_row_tags whose word row_tags[j] matches query_tags[i] under `match`
     // (0 any, 1 all) as the allow-set; the empty-heap rule fails the whole call as there.  One device traversal for every mask
-    // (Device::range_batch with RangeTags); hand-backs, and the whole call when the traversal does not run on the device, go the
+    // (Device::range_batch with a RangeFilter of tags); hand-backs, and the whole call when the traversal does not run on the device, go the
     // lock-step way with the tag predicate.  A query whose mask matches no graph id (counted on the device) is answered with an
     // empty list without a traversal when range >= 0.  Primary context only.  Exclusive lock.
     int range_query_tagged(const float *queries, int count, int dim, float range, int layer, const uint32_t *row_tags, long long n_row_tags,
@@ -314,28 +314,13 @@ private:
     // exclude: nullptr, or per resident query the id that is no result of it (knn_query_by_id: the query's own)
     int knn_query_lockstep(const int *which, int count, int k, int *out_ids, float *out_dists, std::string &err, AllowBits allow = AllowBits{},
                            int layer = 0, const int *exclude = nullptr);
-    // range_query_grouped's filter: the labels of graph ids, every query's group, and the queries that run (ascending), the others
-    // being answered with an empty list.  range_query_tagged's (tags != nullptr) in the same type: the tag words of graph ids, every
-    // query's mask and the call's mode in the labels' and groups' place; resident: the device counted the masks' candidates on these
-    // words for this call and still holds them.
-    struct RangeGroupSpec {
-        const int *label = nullptr;
-        long long n_label = 0;
-        const int *query_group = nullptr;
-        const std::vector<int> *run = nullptr;
-        long long skipped = 0;
-        const uint32_t *tags = nullptr;
-        long long n_tags = 0;
-        const uint32_t *query_tags = nullptr;
-        int match = 0;
-        bool resident = false;
-        size_t n_masks = 0;
-        AllowPred of(int qi) const { return tags ? AllowPred{tags, n_tags, query_tags[qi], match} : AllowPred{label, n_label, query_group[qi]}; }
-    };
-    int range_query_lockstep(const int *which, int count, float range, std::vector<std::vector<NodeDist>> &out, std::string &err,
-                             AllowBits allow = AllowBits{}, int layer = 0, const RangeGroupSpec *grp = nullptr);
-    int range_query_device(int count, float range, std::vector<std::vector<NodeDist>> &out, std::string &err, AllowBits allow, int layer,
-                           const RangeGroupSpec *grp = nullptr);
+    // RangeQuery for the resident queries listed in `which` (nullptr: all `count` of them) under the call's filter f (host_structs.h),
+    // the lock-step way and on the device; and what range_query_grouped / range_query_tagged share (hnsw_index.cpp)
+    int range_query_lockstep(const int *which, int count, float range, std::vector<std::vector<NodeDist>> &out, std::string &err, const RangeFilter &f, int layer);
+    int range_query_device(const int *which, int count, float range, std::vector<std::vector<NodeDist>> &out, std::string &err, const RangeFilter &f, int layer);
+    template <class ClassOf, class ClassesWithId>
+    int range_by_class(const char *who, const float *queries, int count, int dim, float range, int layer, RangeFilter f, ClassOf class_of,
+                       ClassesWithId classes_with_id, std::vector<std::vector<NodeDist>> &out, std::string &err);
     int multilayer_lockstep(const int *which, int count, int k, int first, int min_layer, int *out_ids, float *out_dists, std::string &err);
     bool layer_ok(int layer, std::string &err) const;
     int remove_batched(const int *ids, int count, std::string &err);

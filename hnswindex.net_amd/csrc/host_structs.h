@@ -60,6 +60,53 @@ struct AllowPred {
         return label ? (id >= 0 && id < n_label && label[id] == group) : set.has(id);
     }
 };
+// The filter of ONE range call, as every layer passes it on (Device::range_batch and range_search_*, HnswIndex::range_query_*;
+// DESIGN.md 3.10, 3.23, 3.26): its kind -- none, a bit set, a label per id, a tag word per id -- and the one per-id array of 32-bit
+// words that the kind reads (`n` ids: bits, labels or tag words; ids >= n are not allowed, in no group, carry no tag).  The two
+// per-query kinds bring a 32-bit key per QUERY of the call -- its group, its mask -- so a job's key is keys[job.qref]; `match` is
+// the tagged calls' mode.  of(query) is that query's AllowPred for the host replay.  The rest is what the info counters need:
+// the queries the caller answered without a job (their class holds no graph id), the distinct masks of a tagged call, and
+// `resident`: the device counted the masks' candidates on these words for this call and still holds them (Device::tag_candidates).
+struct RangeFilter {
+    enum Kind { kNone, kBits, kLabels, kTags };
+    Kind kind = kNone;
+    const uint32_t *per_id = nullptr;
+    long long n = 0;
+    const uint32_t *keys = nullptr;
+    int match = 0;
+    long long skipped = 0;
+    size_t n_masks = 0;
+    bool resident = false;
+    RangeFilter() = default;
+    RangeFilter(AllowBits b) : kind(b.bits ? kBits : kNone), per_id(b.bits), n(b.bits ? b.n : 0) {}
+    static RangeFilter labels(const int *label, long long n_label, const int *query_group)
+    {
+        RangeFilter f;
+        f.kind = kLabels;
+        f.per_id = reinterpret_cast<const uint32_t *>(label);
+        f.n = n_label;
+        f.keys = reinterpret_cast<const uint32_t *>(query_group);
+        return f;
+    }
+    static RangeFilter tags(const uint32_t *words, long long n_words, const uint32_t *query_tags, int mode, size_t distinct_masks)
+    {
+        RangeFilter f;
+        f.kind = kTags;
+        f.per_id = words;
+        f.n = n_words;
+        f.keys = query_tags;
+        f.match = mode;
+        f.n_masks = distinct_masks;
+        return f;
+    }
+    bool per_query() const { return kind == kLabels || kind == kTags; }
+    AllowPred of(int query) const
+    {
+        if (kind == kTags) return AllowPred{per_id, n, keys[query], match};
+        if (kind == kLabels) return AllowPred{reinterpret_cast<const int *>(per_id), n, (int)keys[query]};
+        return AllowPred{AllowBits{per_id, n}};
+    }
+};
 // Does a set of nbits bits allow any id of a graph of n_graph nodes?  Reads only the words that cover ids < min(nbits, n_graph).
 static inline bool allows_any(const uint32_t *bits, long long nbits, long long n_graph)
 {

@@ -312,3 +312,29 @@ def test_device_backend_range_search_grouped(cases):
         dev.range_search_grouped(c.q, c.ref.entry_point, 8.0, c.rg, np.full(NQ, N_GROUPS, np.int32), N_GROUPS)
     with pytest.raises(RuntimeError, match="65536"):
         dev.range_search_grouped(c.q, c.ref.entry_point, 8.0, c.rg, c.qg, 65537)
+
+
+def test_jobs_launched_again_for_a_full_arena_keep_their_own_groups():
+    """range_batch's second pass: 320 closures of 4 096 entries exceed the arena's floor of 2^20, so the jobs that found it full run
+    again as a proper subset of the call's -- and the sort kernel's per-job group table must name THEIR groups.  Expected: the
+    per-group filtered calls, 80 queries each (one launch: 80 x 4 096 < 2^20)."""
+    import hnswindex
+    n, dim, nq, n_groups = 4096, 8, 320, 4
+    x, q = uniform(n, dim, 51), uniform(nq, dim, 52)
+    ix = hnswindex.Index(dim, "sq_euclid")
+    ix.set_collection_size(n); ix.set_max_edges(M); ix.set_min_nn(MIN_NN); ix.set_insert_batch(1)
+    ix.add(x)
+    rg = np.random.default_rng(53).integers(0, n_groups, n).astype(np.int32)
+    qg = np.random.default_rng(54).permutation(np.arange(nq) % n_groups).astype(np.int32)
+    radius = float(dim) + 1.0            # rows and queries lie in [0, 1)^8: no squared distance exceeds 8
+    assert nq * n > 1 << 20 and (nq // n_groups) * n < 1 << 20
+    ix.reset_stats()
+    got = ix.range_query_grouped(q, radius, rg, qg, n_groups)   # first: the arena is sized by the call before, and there is none
+    assert ix.stats()["range_launches"] > 1 and ix.range_grouped_info()["launched"] == nq
+    for g in range(n_groups):
+        sel = np.flatnonzero(qg == g)
+        ix.reset_stats()
+        want = ix.range_query(q[sel], radius, allowed=group_mask(rg, g, n))
+        assert sel.size == 80 and ix.stats()["range_launches"] == 1, g
+        assert all(a.size == int((rg == g).sum()) for a in want[0]), g          # every id of the group: the closure is the graph
+        assert _same(([got[0][i] for i in sel], [got[1][i] for i in sel]), want), g

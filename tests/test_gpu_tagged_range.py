@@ -455,3 +455,34 @@ def test_a_long_closure_with_more_allowed_entries_than_the_table_goes_to_the_hos
     info = ix.range_tagged_info()
     assert _same(got, want) and _same(got, _per_mask(ix, q, ref_r, rt, qt, "any", N_LONG))
     assert info["long_finished"] == on_device and info["host_finished"] == 3 - on_device, info
+
+
+def test_jobs_launched_again_for_a_full_arena_keep_their_own_masks():
+    """range_batch's second pass: 320 closures of 4 096 entries exceed the arena's floor of 2^20, so the jobs that found it full run
+    again as a proper subset of the call's -- and the sort kernel's per-job mask table must name THEIR masks.  Expected: the
+    per-mask filtered calls, 80 queries each (one launch: 80 x 4 096 < 2^20)."""
+    import hnswindex
+    n, dim, nq = 4096, 8, 320
+    masks = np.array([1, 2, 0b110, B31 | 1], np.uint32)
+    x, q = uniform(n, dim, 51), uniform(nq, dim, 52)
+    ix = hnswindex.Index(dim, "sq_euclid")
+    ix.set_collection_size(n); ix.set_max_edges(M); ix.set_min_nn(MIN_NN); ix.set_insert_batch(1)
+    ix.add(x)
+    rng = np.random.default_rng(53)
+    rt = np.zeros(n, np.uint32)
+    for bit, share in ((0, 0.4), (1, 0.3), (2, 0.2), (31, 0.1)):
+        rt |= np.where(rng.random(n) < share, np.uint32(1 << bit), np.uint32(0)).astype(np.uint32)
+    qt = masks[np.random.default_rng(54).permutation(np.arange(nq) % masks.size)]
+    radius = float(dim) + 1.0            # rows and queries lie in [0, 1)^8: no squared distance exceeds 8
+    assert nq * n > 1 << 20 and (nq // masks.size) * n < 1 << 20
+    ix.reset_stats()
+    got = ix.range_query_tagged(q, radius, rt, qt, "any")   # first: the arena is sized by the call before, and there is none
+    assert ix.stats()["range_launches"] > 1 and ix.range_tagged_info()["launched"] == nq
+    for m in masks:
+        sel = np.flatnonzero(qt == m)
+        allowed = tag_mask(rt, int(m), "any", n)
+        ix.reset_stats()
+        want = ix.range_query(q[sel], radius, allowed=allowed)
+        assert sel.size == 80 and ix.stats()["range_launches"] == 1, m
+        assert all(a.size == int(allowed.sum()) for a in want[0]), m            # every candidate of the mask: the closure is the graph
+        assert _same(([got[0][i] for i in sel], [got[1][i] for i in sel]), want), m
