@@ -299,6 +299,8 @@ lib.hnsw_mi355x_exact_window_stats.restype = ct.c_int
 lib.hnsw_mi355x_exact_window_stats.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
 lib.hnsw_mi355x_row_prefilter_stats.restype = ct.c_int
 lib.hnsw_mi355x_row_prefilter_stats.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
+lib.hnsw_mi355x_row_prefilter_form_stats.restype = ct.c_int
+lib.hnsw_mi355x_row_prefilter_form_stats.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
 lib.hnsw_mi355x_row_prefilter_peek.restype = ct.c_int
 lib.hnsw_mi355x_row_prefilter_peek.argtypes = [ct.c_void_p, ct.c_int, ct.c_int, ct.POINTER(ct.c_uint64), ct.POINTER(ct.c_float)]
 
@@ -661,6 +663,13 @@ class Index:
         if not self._h or lib.hnsw_mi355x_row_prefilter_stats(self._h, out) != 0:
             return {"launches": 0, "rows_on_shadow": 0, "rows_reread": 0, "rows_packed": 0}
         return {"launches": int(out[0]), "rows_on_shadow": int(out[1]), "rows_reread": int(out[2]), "rows_packed": int(out[3])}
+
+    def row_prefilter_form_stats(self):
+        """Which kernel form the row prefilter's launches took: the one that reads the row length at run time, the one with it compiled in."""
+        out = (ct.c_uint64 * 2)()
+        if not self._h or lib.hnsw_mi355x_row_prefilter_form_stats(self._h, out) != 0:
+            return {"runtime_dim": 0, "fixed_dim": 0}
+        return {"runtime_dim": int(out[0]), "fixed_dim": int(out[1])}
 
     def row_prefilter_peek(self, first_id: int = 0, count: int = 0):
         """The row prefilter's shadow as it stands, read only: {"packed": the watermark (shadow rows [0, packed) are current),

@@ -578,6 +578,8 @@ public:
     // The row prefilter's counters (a view adds to its primary's): launches that ran with it, rows measured on the shadow, rows
     // measured again from f32, shadow rows packed.  All zero on a context that has none (every metric but sq_euclid, diag row_prefilter=0).
     void row_prefilter_stats(uint64_t out[4]);
+    // Which kernel form those launches took: out[0] the run-time-length form (kFormLeanPF), out[1] the fixed-length one (kFormLeanPFFixed).
+    void row_prefilter_form_stats(uint64_t out[2]);
     // The shadow as it stands, read only (nothing is packed or allocated): out[0] the watermark (shadow rows [0, out[0]) are current),
     // out[1] the 32 bits of E; rows: the shadow rows [first_id, first_id + count) widened to f32, `count` x dim floats (count 0: none).
     // false for a range that is not below the watermark.  A context without a shadow has watermark 0.
@@ -616,6 +618,7 @@ private:
         bool lost = false;                 // a launch re-read more than half of its rows: the lean form until the next repack
         bool no_memory = false;            // the shadow could not be allocated: the lean form, no error
         uint64_t launches = 0, on_shadow = 0, reread = 0, rows_packed = 0;
+        uint64_t form_launches[2] = {0, 0}; // of `launches`: in the run-time-length form, in the fixed-length form (kFormLeanPFFixed)
     };
     std::shared_ptr<RowPrefilter> pf_;
     void rows_written(long long first_id); // stored rows [first_id, ...) have changed, or the row matrix has moved

@@ -551,6 +551,14 @@ void Device::row_prefilter_stats(uint64_t out[4])
     out[0] = pf_->launches; out[1] = pf_->on_shadow; out[2] = pf_->reread; out[3] = pf_->rows_packed;
 }
 
+void Device::row_prefilter_form_stats(uint64_t out[2])
+{
+    out[0] = out[1] = 0;
+    if (!pf_) return;
+    std::lock_guard<std::mutex> lk(pf_->mu);
+    out[0] = pf_->form_launches[0]; out[1] = pf_->form_launches[1];
+}
+
 bool Device::row_prefilter_peek(long long first_id, int count, uint64_t out[2], float *rows)
 {
     out[0] = out[1] = 0;
@@ -1253,7 +1261,8 @@ struct TraversalLaunch {
     bool filtered;       // graph_search_filtered_kernel (an allow-set): exact traversal, visited sets kept, no latency form
     // per launch
     bool prefilter;      // the lean form's row prefilter may run: the index's shadow rows are current (search_batch_impl says so)
-    int form;            // kFormLat, kFormLean, kFormLeanPF, kFormPlain
+    bool pf_fixed;       // ... in its fixed-length form: the row length is kPfFixedDim words (diag pf_fixed_dim=0: the run-time form)
+    int form;            // kFormLat, kFormLean, kFormLeanPF, kFormLeanPFFixed, kFormPlain
     int slots, grid;     // the form's resident waves; grid = min(jobs, slots)
     unsigned block;      // 128 threads for the latency form (logic wave + memory wave), else 64
     size_t lds_total;    // lds, plus kTeamLds of mailbox for the latency form
@@ -1269,6 +1278,7 @@ bool Device::plan_traversal(bool insert, int k, bool two_heap, size_t lds, Trave
     t->lds = lds;
     t->filtered = filtered;
     t->prefilter = false;
+    t->pf_fixed = pitch_ == kPfFixedDim && diag("pf_fixed_dim", 1) != 0; // (pitch_: the kernels' `dim` argument)
     t->exact_only = ns == 0; // two_heap callers, beams beyond 512 entries, diag sorted_top=0, filtered searches
     t->ns = t->exact_only ? 2 : ns;
     if (!visited_scratch(k, filtered ? kFilterVisCap : 512, t->ns != 8, &t->vis, filtered)) return false;
@@ -1299,7 +1309,8 @@ static auto traversal_form(int form)
     else if constexpr (NS <= 4)
         return form == kFormLat ? &graph_search_kernel<M, NS, H, kFormLat>
                : form == kFormLean ? &graph_search_kernel<M, NS, H, kFormLean>
-               : form == kFormLeanPF ? &graph_search_kernel<M, NS, H, kFormLeanPF> : &graph_search_kernel<M, NS, H, kFormPlain>;
+               : form == kFormLeanPF ? &graph_search_kernel<M, NS, H, kFormLeanPF>
+               : form == kFormLeanPFFixed ? &graph_search_kernel<M, NS, H, kFormLeanPFFixed> : &graph_search_kernel<M, NS, H, kFormPlain>;
     else
         return form == kFormLat ? &graph_search_kernel<M, NS, H, kFormLat> : &graph_search_kernel<M, NS, H, kFormPlain>;
 }
@@ -1350,7 +1361,7 @@ static auto place_traversal(TraversalLaunch &t, int nj)
         const int slots = std::min(t.max_slots, resident_blocks(traversal_kernel<Insert>(t, kFormLat), t.lds + kTeamLds, t.num_cu, 128));
         if (slots > 0 && (lat == 2 || nj <= slots)) { t.form = kFormLat; t.slots = slots; }
     }
-    if (!Insert && t.form == kFormPlain && t.novis && !t.exact_only && lean_mode() && t.ns <= 4) t.form = t.prefilter ? kFormLeanPF : kFormLean;
+    if (!Insert && t.form == kFormPlain && t.novis && !t.exact_only && lean_mode() && t.ns <= 4) t.form = !t.prefilter ? kFormLean : t.pf_fixed ? kFormLeanPFFixed : kFormLeanPF;
     const auto kernel = traversal_kernel<Insert>(t, t.form);
     if (t.form != kFormLat) t.slots = std::min(t.max_slots, resident_blocks(kernel, t.lds, t.num_cu));
     t.grid = std::min(nj, t.slots);
@@ -1903,7 +1914,7 @@ bool Device::search_batch_impl(const SearchJob *jobs, int njobs, int k, int k_ou
             tl.prefilter = true;
             kernel = place_traversal<false>(tl, nj);
         }
-        const bool prefiltered = tl.form == kFormLeanPF;
+        const bool prefiltered = form_is_pf(tl.form);
         HIP_OK(hipMemsetAsync(s_jobctr_, 0, sizeof(int) * (4 + (size_t)nj), st));
         if (!compact) HIP_OK(hipMemsetAsync(s_evals_, 0, sizeof(unsigned long long), st));
         const bool timed = profiling_;
@@ -1945,6 +1956,7 @@ bool Device::search_batch_impl(const SearchJob *jobs, int njobs, int k, int k_ou
             std::lock_guard<std::mutex> lk(pf_->mu);
             const uint64_t d_shadow = h_pf[0] > pf_->on_shadow ? h_pf[0] - pf_->on_shadow : 0, d_reread = h_pf[1] > pf_->reread ? h_pf[1] - pf_->reread : 0;
             pf_->launches++;
+            pf_->form_launches[tl.form == kFormLeanPFFixed]++;
             pf_->on_shadow += d_shadow;
             pf_->reread += d_reread;
             if (2 * d_reread > d_shadow && row_prefilter_mode() != 2) pf_->lost = true;

@@ -14,6 +14,7 @@
 //       tag_list_cap [0 = 2^28 ids in the candidate lists of one batch of masks of exact_knn_tagged]
 //       range_sort_long [1; 0 = range_sort_tagged_kernel hands a closure beyond its table to the host as the other two sorts do]
 //       graph_unchecked [0]  row_prefilter [1; 0 = off, nothing allocated; 2 = kept on after a launch that re-read most rows]
+//       pf_fixed_dim [1; 0 = the row prefilter's run-time-length kernel form also where the row length is the compiled-in one]
 #pragma once
 #include <cstdlib>
 #include <cstring>

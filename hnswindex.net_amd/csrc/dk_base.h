@@ -17,8 +17,11 @@
 #define HNSW_I8_WAVES 5
 #endif
 
-#ifndef HNSW_PF_WAVES // waves per SIMD of the row-prefilter search kernels (-DHNSW_PF_WAVES=4 was measured: 128 VGPRs with 40 spilled, 19.7 ms per launch where three waves take 16.5)
+#ifndef HNSW_PF_WAVES // waves per SIMD of the row-prefilter search kernels whose row length is a run-time value (-DHNSW_PF_WAVES=4 was measured: 128 VGPRs with 40-59 spilled, 19.7 ms per launch where three waves take 16.5.  The spills come from the run-time row length, not from the exact traversal in the same kernel: kFormLeanPFFixed below)
 #define HNSW_PF_WAVES 3
+#endif
+#ifndef HNSW_PF_FIXED_WAVES // waves per SIMD of the fixed-length row-prefilter kernels (kFormLeanPFFixed): 124-128 VGPRs, nothing spilled
+#define HNSW_PF_FIXED_WAVES 4
 #endif
 
 namespace hnsw {
@@ -58,8 +61,13 @@ __device__ __forceinline__ void wave_lds_sync()
 // LEAN_PF (sq_euclid, f32 rows only): the lean form with the half-precision row prefilter -- the listed neighbours are measured on
 // the index's SHADOW rows (half the bytes), the ones that are provably farther than the farthest result are turned away on that
 // value, and only the rest is measured from its f32 row by the lean form's own pass (dk_sorted_top.h).
-constexpr int kFormPlain = 0, kFormLat = 1, kFormLean = 2, kFormLeanPF = 3;
-constexpr __host__ __device__ bool form_is_lean(int f) { return f == kFormLean || f == kFormLeanPF; }
+// LEAN_PF_FIXED: LEAN_PF with the row length (in 32-bit words) compiled in -- kPfFixedDim, assigned to `dim` as graph_search_kernel's
+// first statement, so the trip counts of the measure passes are constants: four waves per SIMD without a spilled register, where
+// the run-time length spills 55-59 at that occupancy.  Launched where the index's row length is kPfFixedDim (place_traversal).
+constexpr int kFormPlain = 0, kFormLat = 1, kFormLean = 2, kFormLeanPF = 3, kFormLeanPFFixed = 4;
+constexpr int kPfFixedDim = 128; // the one length built (another one goes in with an A/B of its own)
+constexpr __host__ __device__ bool form_is_pf(int f) { return f == kFormLeanPF || f == kFormLeanPFFixed; }
+constexpr __host__ __device__ bool form_is_lean(int f) { return f == kFormLean || form_is_pf(f); }
 
 // A kernel argument read again from the kernarg segment at the point of use (a scalar load that hits the constant cache) instead of
 // being carried in SGPRs from the kernel's first instruction to its last: the lean search kernel does this for the two dozen

@@ -21,7 +21,7 @@ struct SearchKernArgs {
     const int64_t *upper; const int *pool; int strideU; const SearchJob *jobs; int k, cand_cap; ND *spill; int spill_cap;
     unsigned *visited; long long vis_words; int *vis_tab; int vis_tab_cap, k_out; int *out_ids; float *out_d; int *out_cnt, *out_flag;
     unsigned long long *eval_counter; int nbcap, njobs; int *job_counter; int overlap; const int *ready;
-    const float *pf_rows; unsigned long long *pf_words; // the row prefilter (kFormLeanPF): shadow records; [E's bits, rows on the shadow, rows re-read]
+    const float *pf_rows; unsigned long long *pf_words; // the row prefilter (kFormLeanPF, kFormLeanPFFixed): shadow records; [E's bits, rows on the shadow, rows re-read]
 };
 static_assert(offsetof(SearchKernArgs, jobs) == 80 && offsetof(SearchKernArgs, out_ids) == 144 && offsetof(SearchKernArgs, ready) == 208 &&
               offsetof(SearchKernArgs, pf_rows) == 216 && offsetof(SearchKernArgs, pf_words) == 224 && sizeof(SearchKernArgs) == 232,
@@ -99,7 +99,7 @@ __device__ __forceinline__ void search_job(const float *__restrict__ rows, const
                     unsigned long long *__restrict__ eval_counter, int nbcap, unsigned char *smem, int job, int overlap,
                     int *__restrict__ job_word = nullptr, bool shadow = false, TeamPort *port = nullptr, bool *v_untouched = nullptr)
 {
-    constexpr bool LAT = FORM == kFormLat, LEAN = form_is_lean(FORM), PF = FORM == kFormLeanPF;
+    constexpr bool LAT = FORM == kFormLat, LEAN = form_is_lean(FORM), PF = form_is_pf(FORM);
     if constexpr (LEAN) { // (what only the start and the end of a job need is read where it is needed: kernarg_load)
         cand_cap = HNSW_KA(cand_cap); nbcap = HNSW_KA(nbcap); jobs = HNSW_KA(jobs); queries = HNSW_KA(queries); q_sn = HNSW_KA(q_sn);
     }
@@ -236,9 +236,10 @@ __device__ __forceinline__ void search_job(const float *__restrict__ rows, const
 // resident waves (not by the batch) and nothing is memset between launches.
 template <int METRIC, int NS, bool HASHED, int FORM = kFormPlain>
 // float rows: 168 VGPRs, three waves per SIMD; int8 records keep 16 registers of rows in flight, not 64: five waves.
+// The fixed-length row-prefilter form (kFormLeanPFFixed): 124-128 VGPRs, four waves.
 // LAT (launches that do not fill the chip): no occupancy to buy -- every spilled register is a memory round trip a lone wave
 // waits out in full -- so two waves per SIMD at most (256 VGPRs), one with eight register sets
-__global__ void __launch_bounds__(FORM == kFormLat ? 128 : 64) __attribute__((amdgpu_waves_per_eu(HNSW_WAVES(FORM == kFormLat ? (NS <= 4 ? 2 : 1) : FORM == kFormLeanPF ? HNSW_PF_WAVES : METRIC == M_I8 ? (NS <= 2 ? HNSW_I8_WAVES : 4) : (NS <= 4 ? 3 : 2)))))
+__global__ void __launch_bounds__(FORM == kFormLat ? 128 : 64) __attribute__((amdgpu_waves_per_eu(HNSW_WAVES(FORM == kFormLat ? (NS <= 4 ? 2 : 1) : FORM == kFormLeanPF ? HNSW_PF_WAVES : FORM == kFormLeanPFFixed ? HNSW_PF_FIXED_WAVES : METRIC == M_I8 ? (NS <= 2 ? HNSW_I8_WAVES : 4) : (NS <= 4 ? 3 : 2)))))
 graph_search_kernel(const float *__restrict__ rows, const double *__restrict__ row_sn, const float *__restrict__ queries,
                     const double *__restrict__ q_sn, int dim, const int *__restrict__ adj0, int stride0,
                     const int64_t *__restrict__ upper, const int *__restrict__ pool, int strideU,
@@ -249,8 +250,9 @@ graph_search_kernel(const float *__restrict__ rows, const double *__restrict__ r
                     const int *__restrict__ ready, const float *__restrict__ pf_rows, unsigned long long *__restrict__ pf_words)
 {
     constexpr bool LAT = FORM == kFormLat, LEAN = form_is_lean(FORM);
-    if constexpr (FORM == kFormLeanPF && METRIC != M_SQ) return; // (the row prefilter exists for sq_euclid on f32 rows: never launched elsewhere)
+    if constexpr (form_is_pf(FORM) && METRIC != M_SQ) return; // (the row prefilter exists for sq_euclid on f32 rows: never launched elsewhere)
     else {
+    if constexpr (FORM == kFormLeanPFFixed) dim = kPfFixedDim; // (the launch site checks that the argument is this value: place_traversal)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x & 63;
     // (the lean form looks its visited set and spill area up when a job takes the exact traversal: search_job)

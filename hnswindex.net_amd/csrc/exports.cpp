@@ -677,6 +677,13 @@ API int hnsw_mi355x_row_prefilter_stats(void *h, uint64_t out[4])
     static_cast<HnswIndex *>(h)->row_prefilter_stats(out);
     return 0;
 }
+API int hnsw_mi355x_row_prefilter_form_stats(void *h, uint64_t out[2])
+{
+    if (!h || !out) return -1;
+    LOCK_INDEX(h);
+    static_cast<HnswIndex *>(h)->row_prefilter_form_stats(out);
+    return 0;
+}
 API int hnsw_mi355x_row_prefilter_peek(void *h, int first_id, int count, uint64_t out[2], float *rows)
 {
     if (!h || !out) return -1;

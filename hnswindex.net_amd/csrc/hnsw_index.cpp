@@ -2448,6 +2448,17 @@ void HnswIndex::row_prefilter_stats(uint64_t out[4])
     }
 }
 
+void HnswIndex::row_prefilter_form_stats(uint64_t out[2])
+{
+    out[0] = out[1] = 0;
+    if (dev_) dev_->row_prefilter_form_stats(out);
+    for (auto &r : replicas_) {
+        uint64_t v[2];
+        r->row_prefilter_form_stats(v);
+        for (int i = 0; i < 2; ++i) out[i] += v[i];
+    }
+}
+
 bool HnswIndex::row_prefilter_peek(long long first_id, int count, uint64_t out[2], float *rows, std::string &err)
 {
     out[0] = out[1] = 0;

@@ -210,6 +210,7 @@ public:
     int insert_batch_cap() const { return p_.insert_batch == 0 ? host_parallelism() : p_.insert_batch; }
     void exact_window_stats(uint64_t out[4]) const { out[0] = xw_rounds_; out[1] = xw_searches_; out[2] = xw_alone_; out[3] = xw_linked_; }
     void row_prefilter_stats(uint64_t out[4]); // the primary context's (its views add to it) plus every replica's
+    void row_prefilter_form_stats(uint64_t out[2]); // summed the same way
     bool row_prefilter_peek(long long first_id, int count, uint64_t out[2], float *rows, std::string &err); // the primary context's shadow, read only
     void set_profiling(bool on)
     {

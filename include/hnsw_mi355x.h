@@ -147,6 +147,9 @@ int hnsw_mi355x_exact_window_stats(void *handle, uint64_t out[4]);
  * out[0] search launches that ran with it, out[1] rows measured on the half-precision shadow, out[2] rows measured again from
  * their f32 row (the others were turned away on the shadow value), out[3] shadow rows packed.  All zero where it does not run. */
 int hnsw_mi355x_row_prefilter_stats(void *handle, uint64_t out[4]);
+/* Which kernel form those launches took: out[0] launches in the form that reads the row length at run time, out[1] launches in the
+ * form with the row length compiled in (dim 128; four waves per SIMD).  out[0] + out[1] is out[0] above. */
+int hnsw_mi355x_row_prefilter_form_stats(void *handle, uint64_t out[2]);
 /* Diagnostic, read only: the half-precision shadow of the row prefilter as it stands (it packs nothing and allocates nothing).
  * out[0] the packed watermark (shadow rows [0, out[0]) are current), out[1] the 32 bits of E, the index-wide bound on
  * ||x - h(x)||_2 (a float; 0x7f800000 = +inf: nothing is turned away).  rows (may be NULL when count is 0): count x dim floats, the
