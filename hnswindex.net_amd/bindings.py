@@ -134,6 +134,14 @@ lib.hnsw_mi355x_exact_range_info.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64
 _EXACT_GROUPED_INFO = ("calls", "groups_scanned", "scan_blocks", "ids_listed")   # hnswdev_exact_grouped_info's out[0 .. 3]
 lib.hnsw_mi355x_exact_knn_query_grouped.restype = ct.c_int
 lib.hnsw_mi355x_exact_knn_query_grouped.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_int, ct.c_int, _I, ct.c_longlong, _I, ct.c_int, _I, _F]
+_EXACT_COLLAPSED_INFO = ("calls", "queries", "dropped", "evicted")   # hnswdev_exact_collapsed_info's out[0 .. 3]
+lib.hnsw_mi355x_exact_knn_query_collapsed.restype = ct.c_int
+lib.hnsw_mi355x_exact_knn_query_collapsed.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_int, ct.c_int, _I, ct.c_longlong, ct.c_int, _U32, ct.c_longlong, _I, _F]
+lib.hnsw_mi355x_knn_query_collapsed.restype = ct.c_int
+lib.hnsw_mi355x_knn_query_collapsed.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_int, ct.c_int, ct.c_int, _I, ct.c_longlong, ct.c_int, ct.c_int, _U32, ct.c_longlong,
+                                                _I, _F]
+lib.hnsw_mi355x_exact_collapsed_info.restype = ct.c_int
+lib.hnsw_mi355x_exact_collapsed_info.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
 lib.hnsw_mi355x_exact_grouped_info.restype = ct.c_int
 lib.hnsw_mi355x_exact_grouped_info.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
 _KNN_GROUPED_INFO = ("calls", "launched", "skipped", "handbacks")   # hnswdev_knn_grouped_info's out[0 .. 3]
@@ -340,6 +348,10 @@ lib.hnswdev_exact_range_info.restype = ct.c_int
 lib.hnswdev_exact_range_info.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
 lib.hnswdev_exact_knn_grouped.restype = ct.c_int
 lib.hnswdev_exact_knn_grouped.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_longlong, ct.c_int, _I, ct.c_longlong, _I, ct.c_int, _I, _F]
+lib.hnswdev_exact_knn_collapsed.restype = ct.c_int
+lib.hnswdev_exact_knn_collapsed.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_longlong, ct.c_int, _I, ct.c_longlong, ct.c_int, _U32, ct.c_longlong, _I, _F]
+lib.hnswdev_exact_collapsed_info.restype = ct.c_int
+lib.hnswdev_exact_collapsed_info.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
 lib.hnswdev_exact_grouped_info.restype = ct.c_int
 lib.hnswdev_exact_grouped_info.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
 lib.hnswdev_exact_grouped_list_ms.restype = ct.c_int
@@ -449,6 +461,24 @@ def _group_args(row_group, query_group, n_groups, nq):
         n_groups = max(int(rg.max(initial=-1)), int(qg.max(initial=-1))) + 1
         n_groups = max(n_groups, 1)
     return rg, qg, int(n_groups)
+
+
+def _collapse_args(row_group, k, per_group, n_ids, k_limit=1024):
+    """row_group as the collapsed scan takes it -- a contiguous int32 array with a label for each of the n_ids ids -- after the checks
+    of k and per_group.  Every breach is a ValueError here, before anything native runs."""
+    k, per_group = int(k), int(per_group)
+    if k_limit is not None and k > k_limit:
+        raise ValueError(f"k = {k} is above the limit of {k_limit}")
+    if k >= 1 and not 1 <= per_group <= k:
+        raise ValueError(f"per_group = {per_group} is outside [1, k = {k}]")
+    rg = np.asarray(row_group).reshape(-1)
+    if rg.size and rg.dtype.kind not in "iu":
+        raise ValueError(f"row_group must hold integers (int32 labels), not {rg.dtype}")
+    if rg.size and (int(rg.min()) < -2 ** 31 or int(rg.max()) > 2 ** 31 - 1):
+        raise ValueError("row_group holds a value outside the int32 range")   # (wrapped, two labels could become one)
+    if rg.shape[0] < n_ids:
+        raise ValueError(f"row_group has {rg.shape[0]} entries, the index's length is {n_ids}")
+    return np.ascontiguousarray(rg, dtype=np.int32)
 
 
 def _tag_words(values, name):
@@ -786,6 +816,60 @@ class Index:
         if status < 0:
             raise RuntimeError(last_error())
         return ids, dists
+
+    def exact_knn_query_collapsed(self, queries: npt.ArrayLike, k: int, row_group, per_group: int = 1,
+                                  allowed=None) -> Tuple[npt.NDArray[np.int32], npt.NDArray[np.float32]]:
+        """exact_knn_query with at most per_group results per label (hnsw_mi355x_exact_knn_query_collapsed): row_group[id] is the
+        label of an id -- the document a chunk belongs to -- and needs an entry for every id below length().  Per query the live
+        (allowed) ids are walked in exact_knn_query's order, ascending (distance, id); an id is kept while fewer than per_group
+        kept ids have its label, until k are kept; rows that run out are padded with -1 / NaN.  Labels are compared for equality
+        (negative values are labels like any).  Exact, in one scan; per_group == k returns exact_knn_query's rows byte for byte.
+        1 <= per_group <= k <= 1024."""
+        q = _as_2d_f32(queries, self.dim)
+        n = int(q.shape[0])
+        rg = _collapse_args(row_group, k, per_group, self.length)
+        ids = np.full((n, max(k, 0)), -1, dtype=np.int32)   # (an index nothing was added to has no native handle yet: padding)
+        dists = np.full((n, max(k, 0)), np.nan, dtype=np.float32)
+        words, nbits = allow_bits(allowed) if allowed is not None else (None, 0)
+        words, wp = _words_arg(words) if allowed is not None else (None, None)
+        status = lib.hnsw_mi355x_exact_knn_query_collapsed(self._h, q.ctypes.data_as(_F), n, self.dim, k, rg.ctypes.data_as(_I), rg.shape[0], int(per_group),
+                                                           wp, nbits, ids.ctypes.data_as(_I), dists.ctypes.data_as(_F))
+        if status < 0:
+            raise RuntimeError(last_error())
+        return ids, dists
+
+    def knn_query_collapsed(self, queries: npt.ArrayLike, k: int, row_group, per_group: int = 1, beam=None, allowed=None,
+                            layer: int = 0) -> Tuple[npt.NDArray[np.int32], npt.NDArray[np.float32]]:
+        """The traversal form of exact_knn_query_collapsed (hnsw_mi355x_knn_query_collapsed): per query the first k survivors of the
+        same walk -- an id is kept while fewer than per_group kept ids have its label row_group[id] -- over the row that
+        knn_query(q, beam, allowed=allowed, layer=layer) returns, in that row's own order, padding skipped; byte for byte.  beam
+        defaults to 4 * k and may be any value >= k that knn_query accepts as k.  Approximate exactly as far as knn_query at that
+        beam is: what the traversal does not reach at width beam is not in the result, and a label with many near rows uses up
+        beam entries -- exact_knn_query_collapsed is the exact call.  Where the traversal runs on the device the rows are
+        collapsed there and only k columns come back."""
+        q = _as_2d_f32(queries, self.dim)
+        n = int(q.shape[0])
+        beam = 4 * int(k) if beam is None else int(beam)
+        if k >= 1 and beam < k:
+            raise ValueError(f"beam = {beam} is below k = {k}")
+        rg = _collapse_args(row_group, k, per_group, self.length, k_limit=None)   # (k and beam: whatever knn_query accepts)
+        ids = np.full((n, max(k, 0)), -1, dtype=np.int32)   # (an index nothing was added to has no native handle yet: padding)
+        dists = np.full((n, max(k, 0)), np.nan, dtype=np.float32)
+        words, nbits = allow_bits(allowed) if allowed is not None else (None, 0)
+        words, wp = _words_arg(words) if allowed is not None else (None, None)
+        status = lib.hnsw_mi355x_knn_query_collapsed(self._h, q.ctypes.data_as(_F), n, self.dim, k, beam, rg.ctypes.data_as(_I), rg.shape[0], int(per_group),
+                                                     int(layer), wp, nbits, ids.ctypes.data_as(_I), dists.ctypes.data_as(_F))
+        if status < 0:
+            raise RuntimeError(last_error())
+        return ids, dists
+
+    def exact_collapsed_info(self) -> dict:
+        """Counters of exact_knn_query_collapsed since reset_stats (hnsw_mi355x_exact_collapsed_info): calls that scanned, queries
+        scanned, keys dropped by the cap at a list, list entries evicted by a nearer key of their label."""
+        out = (ct.c_uint64 * 4)()
+        if self._h:
+            lib.hnsw_mi355x_exact_collapsed_info(self._h, out)
+        return dict(zip(_EXACT_COLLAPSED_INFO, (int(v) for v in out)))
 
     def exact_grouped_info(self) -> dict:
         """Counters of exact_knn_query_grouped since reset_stats (hnsw_mi355x_exact_grouped_info)."""
@@ -1718,6 +1802,26 @@ class DeviceBackend:
                                                   int(k), rg.ctypes.data_as(_I), rg.shape[0], qg.ctypes.data_as(_I), ng, ids.ctypes.data_as(_I),
                                                   d.ctypes.data_as(_F)))
         return ids, d
+
+    def exact_knn_collapsed(self, queries, k: int, row_group, per_group: int = 1, n_rows=None, allowed=None):
+        """hnswdev_exact_knn_collapsed: exact_knn with at most per_group results per label row_group[id]; row_group needs an entry
+        for every uploaded row below n_rows (the context checks that: a RuntimeError with both numbers)."""
+        q = _as_2d_f32(queries, self.dim)
+        n = q.shape[0]
+        rg = _collapse_args(row_group, k, per_group, 0)   # (the rows uploaded are the context's to know: it checks the length)
+        ids = np.empty((n, k), dtype=np.int32)
+        d = np.empty((n, k), dtype=np.float32)
+        words, nbits = allow_bits(allowed) if allowed is not None else (None, 0)
+        words, wp = _words_arg(words) if allowed is not None else (None, None)
+        self._check(lib.hnswdev_exact_knn_collapsed(self._ctx, q.ctypes.data_as(_F), n, (1 << 62) if n_rows is None else int(n_rows), int(k),
+                                                    rg.ctypes.data_as(_I), rg.shape[0], int(per_group), wp, nbits, ids.ctypes.data_as(_I), d.ctypes.data_as(_F)))
+        return ids, d
+
+    def exact_collapsed_info(self) -> dict:
+        """Counters of exact_knn_collapsed since reset_stats (hnswdev_exact_collapsed_info)."""
+        out = (ct.c_uint64 * 4)()
+        self._check(lib.hnswdev_exact_collapsed_info(self._ctx, out))
+        return dict(zip(_EXACT_COLLAPSED_INFO, (int(v) for v in out)))
 
     def exact_grouped_info(self) -> dict:
         """Counters of exact_knn_grouped since reset_stats (hnswdev_exact_grouped_info)."""

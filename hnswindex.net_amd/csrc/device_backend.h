@@ -130,6 +130,7 @@ template <class K> struct PredicatePlan; // ... and what its launches need, K th
 struct ExactScanArgs;    // dk_exact.h: what one launch of the flat scan reads
 enum class ExactStart;   // device_backend.hip: how a flat-scan call begins -- failed, nothing to measure, ready
 struct ExactScanInput;   // ... the queries and the id list of an ungrouped flat scan
+struct ExactCollapseArgs; // ... the labels on the device, the cap and the device counters of a collapsed one
 struct ExactGroupedCall; // ... the group lists and the tile of a grouped one
 struct ExactRangeWork;   // ... the knobs and the scratch of the range calls
 struct ReachSeeds;       // dk_graph_reach.h: the seed set of one layer's reachability pass
@@ -447,6 +448,23 @@ public:
     // set (nq of its rows); otherwise the queries are staged by set_queries' code into a buffer of the scan's own and the
     // resident set stays what it was.  1 <= k <= 1024.  Synchronous.
     bool exact_knn(const float *queries, int nq, long long n_rows, int k, const uint32_t *allow_bits, long long nbits, int *out_ids, float *out_d);
+    // hnswdev_exact_knn_collapsed: exact_knn whose result is shaped, not its candidates -- walk exact_knn's
+    // candidates in ascending (distance, id) order, keep an id while fewer than per_group kept ids have its label row_group[id], stop
+    // at k; padding as exact_knn.  Labels are compared for equality only.  row_group must cover every candidate id: n_row_group >=
+    // min(n_rows, uploaded), checked before anything is launched; 1 <= per_group <= k <= 1024.  With per_group == k the rows are
+    // exact_knn's, byte for byte.  The labels go up once per call; queries == nullptr and the resident set as exact_knn.  Synchronous.
+    bool exact_knn_collapsed(const float *queries, int nq, long long n_rows, int k, const int *row_group, long long n_row_group, int per_group,
+                             const uint32_t *allow_bits, long long nbits, int *out_ids, float *out_d);
+    // collapsed calls that scanned, queries they scanned, keys the cap dropped at an insert, entries evicted by a nearer key of their
+    // label (the last two are counted by the scan's and the merge's waves and depend on the order the keys arrived in)
+    void exact_collapsed_info(uint64_t out[4]) const { for (int i = 0; i < 4; ++i) out[i] = xc_info_[i]; }
+    // knn_query_collapsed on one context: search_filtered (allow_bits != nullptr) or search_batch's traversal of
+    // resident queries 0 .. nq - 1 with a result of `beam` entries per query, which stays on the device: collapse_rows_kernel
+    // walks every row there -- an entry is kept while fewer than per_group kept entries have its label row_group[id] -- and only
+    // the first k columns are copied out.  out_ids / out_d: nq x k.  row_group must cover the graph's ids (n_row_group >=
+    // graph_nodes()); 1 <= per_group <= k <= beam.  out_flag as search_filtered: a flagged row holds nothing.
+    bool search_collapsed(int nq, int entry, int entry_layer, int ef, int beam, int k, const int *row_group, long long n_row_group, int per_group,
+                          const uint32_t *allow_bits, long long nbits, int *out_ids, float *out_d, int *out_flag, int search_layer = 0);
     // ---- query by stored id --------------------------------------------------------------------------------
     // hnswdev_gather_rows: out[i] = the stored row ids[i] as dim floats -- hnswdev_download_rows' values for the row kind (f32: a
     // copy; f16: the rounded row widened; int8: q * scale), gathered on the device in one launch (gather_rows_kernel) and copied back
@@ -720,7 +738,15 @@ private:
     bool exact_queries(const char *who, const float *queries, int nq, const float **d_q, const double **d_qsn);
     bool exact_id_list(const uint32_t *allow_bits, long long n_allow, long long *m);
     bool exact_knn_rounds(const float *d_q, const double *d_qsn, int nq, const int *d_idlist, long long m, int k, int *out_ids, float *out_d, int *d_keep_ids,
-                          const int *d_self = nullptr);
+                          const int *d_self = nullptr, const ExactCollapseArgs *collapse = nullptr);
+    DevBuf<int> x_clabels_;               // exact_knn_collapsed: row_group as uploaded
+    DevBuf<unsigned long long> x_cinfo_;  // ... [keys dropped by the cap | entries evicted], counted on the device
+    uint64_t xc_info_[4] = {0, 0, 0, 0};
+    // search_collapsed: while set, run_resident and search_batch_impl collapse a launch's rows on the device (width -> k columns)
+    // before the copy-out and write rows of k entries to the caller's arrays
+    struct RowCollapse { const int *d_labels; long long n_labels; int per_group, k; };
+    const RowCollapse *row_collapse_ = nullptr;
+    bool collapse_and_fetch(int *d_ids, float *d_d, int nj, size_t width, int *h_ids, float *h_d);
     bool exact_copy_out(void *dst, const void *src, size_t bytes);
     ExactStart exact_scan_begin(const char *who, const float *queries, int nq, long long n_rows, const uint32_t *allow_bits, long long nbits, ExactScanInput *in);
     bool exact_scan_args(const float *d_q, const double *d_qsn, long long off, int nr, int qt, int piece, ExactScanArgs *a);

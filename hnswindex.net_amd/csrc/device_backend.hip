@@ -1035,6 +1035,7 @@ void Device::reset_stats()
     stats_.row_bytes = rb;
     for (uint64_t &v : xr_info_) v = 0;
     for (uint64_t &v : xg_info_) v = 0;
+    for (uint64_t &v : xc_info_) v = 0;
     for (uint64_t &v : xrg_info_) v = 0;
     for (uint64_t &v : kg_info_) v = 0;
     for (uint64_t &v : rg_info_) v = 0;
@@ -1887,7 +1888,8 @@ bool Device::search_batch_impl(const SearchJob *jobs, int njobs, int k, int k_ou
     // one copy into the pinned staging (laid out alike), the evaluation counter lives in the job counter's spare words and
     // is zeroed with it -- five HIP calls.  (A large call keeps the separate copies: its ids are handed to the caller while
     // the distances are still crossing the link.)
-    const bool compact = njobs == chunk && 2 * b_res + 4u * (size_t)chunk <= (size_t)1 << 20;
+    const bool compact = !row_collapse_ && njobs == chunk && 2 * b_res + 4u * (size_t)chunk <= (size_t)1 << 20;
+    const size_t w_out = row_collapse_ ? (size_t)row_collapse_->k : (size_t)k_out; // entries per row that leave the device
     int *d_flag = compact ? reinterpret_cast<int *>(d_d + (size_t)chunk * k_out) : s_flag_;
     unsigned long long *d_ev = compact ? reinterpret_cast<unsigned long long *>(s_jobctr_.get() + 2) : s_evals_;
     // a query set whose tail is still on the host (set_queries_streamed): the launch is gated on the rows' arrival
@@ -1935,6 +1937,12 @@ bool Device::search_batch_impl(const SearchJob *jobs, int njobs, int k, int k_ou
             HIP_OK(hipMemcpyAsync(h_ev, d_ev, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
             HIP_OK(hipStreamSynchronize(st));
             memcpy(out_ids + (size_t)off * k_out, h_ids, 4u * (size_t)nj * k_out);
+        } else if (row_collapse_) { // search_collapsed: the rows are collapsed where they are, and k columns of them come back
+            if (!collapse_and_fetch(d_ids, d_d, nj, (size_t)k_out, h_ids, h_d)) return false;
+            HIP_OK(hipMemcpyAsync(h_flag, s_flag_, sizeof(int) * (size_t)nj, hipMemcpyDeviceToHost, st));
+            HIP_OK(hipMemcpyAsync(h_ev, s_evals_, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+            HIP_OK(hipStreamSynchronize(st));
+            memcpy(out_ids + (size_t)off * w_out, h_ids, 4u * (size_t)nj * w_out);
         } else {
         // the ids are copied out to the caller's array while the distances are still crossing the link
         HIP_OK(hipMemcpyAsync(h_ids, d_ids, 4u * (size_t)nj * k_out, hipMemcpyDeviceToHost, st));
@@ -1946,7 +1954,7 @@ bool Device::search_batch_impl(const SearchJob *jobs, int njobs, int k, int k_ou
         memcpy(out_ids + (size_t)off * k_out, h_ids, 4u * (size_t)nj * k_out);
         HIP_OK(hipStreamSynchronize(st));
         }
-        memcpy(out_d + (size_t)off * k_out, h_d, 4u * (size_t)nj * k_out);
+        memcpy(out_d + (size_t)off * w_out, h_d, 4u * (size_t)nj * w_out);
         for (int i = 0; i < nj; ++i) {
             if (h_flag[i] == 2) { stats_.search_repeats++; if (!keep_repeat_flag) h_flag[i] = 0; }
             else if (h_flag[i] == 4) { stats_.tie_windows++; h_flag[i] = 0; } // informational: a group window closed cleanly
@@ -1965,6 +1973,21 @@ bool Device::search_batch_impl(const SearchJob *jobs, int njobs, int k, int k_ou
         if (!count_launch(nullptr, *h_ev, tl.vis.tab != nullptr, timed, ev0_, ev1_)) return false;
     }
     for (int i = 0; i < njobs; ++i) stats_.search_overflows += (uint64_t)(out_flag[i] == 1);
+    return true;
+}
+
+// search_collapsed's part of a launch's copy-out (row_collapse_ is set): the nj rows of `width` entries at d_ids / d_d are collapsed
+// in place by collapse_rows_kernel and their first k columns enqueued to h_ids / h_d as rows of k.
+bool Device::collapse_and_fetch(int *d_ids, float *d_d, int nj, size_t width, int *h_ids, float *h_d)
+{
+    hipStream_t st = S(stream_);
+    const RowCollapse &rc = *row_collapse_;
+    const size_t lds = 12 * width + 4 * (size_t)rc.k, w = (size_t)rc.k;
+    if (lds > 64 * 1024) { set_dev_error("search_collapsed: the beam exceeds the LDS budget of the collapse"); return false; }
+    hipLaunchKernelGGL(collapse_rows_kernel, dim3((unsigned)nj), dim3(64), lds, st, d_ids, d_d, (int)width, rc.k, rc.d_labels, rc.n_labels, rc.per_group);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipMemcpy2DAsync(h_ids, 4 * w, d_ids, 4 * width, 4 * w, (size_t)nj, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpy2DAsync(h_d, 4 * w, d_d, 4 * width, 4 * w, (size_t)nj, hipMemcpyDeviceToHost, st));
     return true;
 }
 
@@ -1998,13 +2021,17 @@ bool Device::run_resident(size_t row, long long chunk, size_t extra, bool hashed
         launch(off, nj, d_ids, d_d);
         HIP_OK(hipGetLastError());
         if (timed) HIP_OK(hipEventRecord(E(ev1_), st));
-        HIP_OK(hipMemcpyAsync(h_ids, d_ids, 4u * (size_t)nj * row, hipMemcpyDeviceToHost, st));
-        HIP_OK(hipMemcpyAsync(h_d, d_d, 4u * (size_t)nj * row, hipMemcpyDeviceToHost, st));
+        const size_t w = row_collapse_ ? (size_t)row_collapse_->k : row; // entries per row that leave the device
+        if (row_collapse_) { if (!collapse_and_fetch(d_ids, d_d, nj, row, h_ids, h_d)) return false; }
+        else {
+            HIP_OK(hipMemcpyAsync(h_ids, d_ids, 4u * (size_t)nj * row, hipMemcpyDeviceToHost, st));
+            HIP_OK(hipMemcpyAsync(h_d, d_d, 4u * (size_t)nj * row, hipMemcpyDeviceToHost, st));
+        }
         HIP_OK(hipMemcpyAsync(h_flag, s_flag_, sizeof(int) * (size_t)nj, hipMemcpyDeviceToHost, st));
         HIP_OK(hipMemcpyAsync(h_ev, s_evals_, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
         HIP_OK(hipStreamSynchronize(st));
-        memcpy(out_ids + (size_t)off * row, h_ids, 4u * (size_t)nj * row);
-        memcpy(out_d + (size_t)off * row, h_d, 4u * (size_t)nj * row);
+        memcpy(out_ids + (size_t)off * w, h_ids, 4u * (size_t)nj * w);
+        memcpy(out_d + (size_t)off * w, h_d, 4u * (size_t)nj * w);
         memcpy(out_flag + off, h_flag, sizeof(int) * (size_t)nj);
         if (!count_launch(nullptr, *h_ev, hashed, timed, ev0_, ev1_)) return false;
     }
@@ -3029,18 +3056,20 @@ struct ExactPlan {
     long long chunk, round; // rows per chunk, queries per round
     size_t lds;
 };
-static ExactPlan exact_plan(int nq, long long m, int k, int pitch, int num_cu)
+static ExactPlan exact_plan(int nq, long long m, int k, int pitch, int num_cu, int entry_bytes = kExactKeyBytes)
 {
     ExactPlan p;
     const int forced_q = diag("exact_qtile", 0);
     const long long forced_c = diag("exact_chunk", 0);
     int qt = forced_q > 0 ? std::min(forced_q, kExactMaxQTile) : kExactMaxQTile;
     const auto tile_rows = [](int q) { return (size_t)((q + kExactRQ - 1) / kExactRQ * kExactRQ); };
-    while (qt > kExactRQ && (tile_rows(qt) * (size_t)k * 8 > 32768 || (forced_q <= 0 && ((size_t)qt * pitch * 4 > 16384 || qt / 2 >= nq)))) qt >>= 1;
+    while (qt > kExactRQ && (tile_rows(qt) * (size_t)k * (size_t)entry_bytes > 32768 || (forced_q <= 0 && ((size_t)qt * pitch * 4 > 16384 || qt / 2 >= nq)))) qt >>= 1;
     p.qtile = qt;
     const size_t qtr = tile_rows(qt);
-    p.piece = qtr * (size_t)pitch * 4 <= 16384 ? pitch : std::max(16, (int)(16384 / 4 / qtr) & ~15);
-    p.lds = exact_scan_lds(qt, p.piece, pitch, k);
+    // (entries of 12 bytes can leave the smallest tile's lists above 32 KB -- k = 1024: 48 KB -- and the staged words take what is left)
+    const size_t fixed = exact_scan_lds(qt, 0, pitch, k, entry_bytes), q_room = std::min<size_t>(16384, (64 * 1024 - fixed) & ~(size_t)255); // (fixed <= 55 KB)
+    p.piece = qtr * (size_t)pitch * 4 <= q_room ? pitch : std::max(16, (int)(q_room / 4 / qtr) & ~15);
+    p.lds = exact_scan_lds(qt, p.piece, pitch, k, entry_bytes);
     const long long tiles = (std::min<long long>(nq, 65536) + qt - 1) / qt;
     long long chunks = forced_c > 0 ? (m + forced_c - 1) / forced_c
                                     : std::max<long long>(1, std::min<long long>((2LL * num_cu + tiles - 1) / tiles, m / 1024));
@@ -3188,15 +3217,23 @@ bool Device::exact_knn(const float *queries, int nq, long long n_rows, int k, co
     return exact_knn_rounds(in.d_q, in.d_qsn, nq, in.ids, in.m, k, out_ids, out_d, nullptr);
 }
 
+// What exact_knn_rounds needs for the collapsed sink (ExactTopKCollapse): row_group on the device, the cap, the two device counters.
+struct ExactCollapseArgs {
+    const int *d_row_group;
+    int per_group;
+    unsigned long long *d_info;
+};
+
 // The rounds of a top-k flat scan: nq queries on the device (d_q, pitch_ words each; d_qsn their cosine norms or nullptr) against the
 // m entries of the id list d_ids (nullptr: the identity).  out_d may be nullptr; d_keep_ids: nullptr, or nq x k ints on the device
 // that receive the ids as well (graph_repair_round's candidates stay there for the proposal kernel).
 // d_self: nullptr, or nq ids on the device -- query i is the stored row d_self[i], which is no candidate of it (ExactTopKSelf).
+// collapse: nullptr, or the collapsed sink's arguments -- scan and merge are then ExactTopKCollapse's, the tile planned for its entries.
 bool Device::exact_knn_rounds(const float *d_q, const double *d_qsn, int nq, const int *d_idlist, long long m, int k, int *out_ids, float *out_d, int *d_keep_ids,
-                              const int *d_self)
+                              const int *d_self, const ExactCollapseArgs *collapse)
 {
     hipStream_t st = S(stream_);
-    const ExactPlan p = exact_plan(nq, m, k, pitch_, num_cu_);
+    const ExactPlan p = exact_plan(nq, m, k, pitch_, num_cu_, collapse ? kExactCollapseEntryBytes : kExactKeyBytes);
     if (p.lds > 64 * 1024) { set_dev_error("exact_knn: tile exceeds the LDS budget"); return false; }
     if (!x_lists_.grow((size_t)p.round * p.n_chunks * k) || !x_out_.grow(2 * (size_t)p.round * k)) return false;
     char *hs = static_cast<char *>(pinned_stage(8 * (size_t)p.round * k + 8));
@@ -3213,6 +3250,13 @@ bool Device::exact_knn_rounds(const float *d_q, const double *d_qsn, int nq, con
         float *d_d = reinterpret_cast<float *>(x_out_.get() + (size_t)p.round * k);
         const auto enqueue = [&]() -> bool {
             hipError_t e = hipSuccess;
+            if (collapse) {
+                const ExactTopKCollapse sink{collapse->d_row_group, collapse->per_group, collapse->d_info};
+                with_metric(metric_, [&](auto mt) { e = exact_collapsed_scan_launch<mt>(a, sink, tiles, p.lds, st); });
+                HIP_OK(e);
+                HIP_OK(exact_merge_collapsed_launch(x_lists_, p.n_chunks, k, nr, sink.row_group, sink.per_group, sink.info, d_ids, d_d, st));
+                return true;
+            }
             if (d_self) with_metric(metric_, [&](auto mt) { e = exact_self_scan_launch<mt>(a, ExactTopKSelf{d_self + off}, tiles, p.lds, st); });
             else with_metric(metric_, [&](auto mt) { e = exact_scan_launch<mt>(a, tiles, p.lds, st); });
             HIP_OK(e);
@@ -3230,6 +3274,65 @@ bool Device::exact_knn_rounds(const float *d_q, const double *d_qsn, int nq, con
         if (out_d) memcpy(out_d + (size_t)off * k, hs + 4u * (size_t)p.round * k, res);
     }
     return true;
+}
+
+// ---- hnswdev_exact_knn_collapsed: at most per_group results per label ------------------------------------------
+// exact_knn with another sink: the same queries, id list, rounds and statistics; the labels of ids [0, min(n_rows, uploaded)) go up
+// once, before the rounds, into a buffer of the call's own, and two device counters come back after them.
+bool Device::exact_knn_collapsed(const float *queries, int nq, long long n_rows, int k, const int *row_group, long long n_row_group, int per_group,
+                                 const uint32_t *allow_bits, long long nbits, int *out_ids, float *out_d)
+{
+    if (nq <= 0) return true;
+    const char *who = "exact_knn_collapsed";
+    const auto fail = [&](const std::string &what) { set_dev_error(std::string(who) + ": " + what); return false; };
+    if (!out_ids || !out_d || k < 1 || n_rows < 0 || (allow_bits && nbits < 0)) return fail("bad argument");
+    if (k > kExactMaxK) return fail("k = " + std::to_string(k) + " is above the limit of " + std::to_string(kExactMaxK));
+    if (per_group < 1 || per_group > k) return fail("per_group = " + std::to_string(per_group) + " is outside [1, k = " + std::to_string(k) + "]");
+    if (!row_group || n_row_group < 0) return fail("row_group must not be NULL and n_row_group must be >= 0");
+    const long long n = std::min(n_rows, n_rows_hw_); // the ids that can be candidates: every one of them needs a label
+    if (n_row_group < n) return fail("row_group has " + std::to_string(n_row_group) + " entries, the scan's " + std::to_string(n) + " ids need one each");
+    ExactScanInput in;
+    const ExactStart s = exact_scan_begin(who, queries, nq, n_rows, allow_bits, nbits, &in);
+    if (s == ExactStart::nothing) pad_results(out_ids, out_d, (size_t)nq * (size_t)k); // padding, no launch
+    if (s != ExactStart::ready) return s == ExactStart::nothing;
+    hipStream_t st = S(stream_);
+    if (!x_clabels_.grow((size_t)n) || !x_cinfo_.grow(2)) return false;
+    if (!staged_upload(reinterpret_cast<float *>(x_clabels_.get()), reinterpret_cast<const float *>(row_group), 4 * (size_t)n)) return false;
+    HIP_OK(hipMemsetAsync(x_cinfo_, 0, 2 * sizeof(unsigned long long), st));
+    const ExactCollapseArgs ca{x_clabels_, per_group, x_cinfo_};
+    if (!exact_knn_rounds(in.d_q, in.d_qsn, nq, in.ids, in.m, k, out_ids, out_d, nullptr, nullptr, &ca)) return false;
+    unsigned long long *h = static_cast<unsigned long long *>(pinned_stage(2 * sizeof(unsigned long long)));
+    if (!h) return false;
+    HIP_OK(hipMemcpyAsync(h, x_cinfo_, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    xc_info_[0] += 1; xc_info_[1] += (uint64_t)nq; xc_info_[2] += h[0]; xc_info_[3] += h[1];
+    return true;
+}
+
+// knn_query_collapsed on this context: the labels of the graph's ids go up, then the traversal the plain calls run
+// -- search_filtered with a bitset, search_batch without -- with row_collapse_ set, so that its launches collapse their rows on the
+// device and copy k columns out.
+bool Device::search_collapsed(int nq, int entry, int entry_layer, int ef, int beam, int k, const int *row_group, long long n_row_group, int per_group,
+                              const uint32_t *allow_bits, long long nbits, int *out_ids, float *out_d, int *out_flag, int search_layer)
+{
+    if (nq <= 0) return true;
+    const auto fail = [&](const std::string &what) { set_dev_error("search_collapsed: " + what); return false; };
+    if (!out_ids || !out_d || !out_flag || !row_group || k < 1 || beam < k || per_group < 1 || per_group > k || (allow_bits && nbits < 0)) return fail("bad argument");
+    if (n_row_group < g_n_) return fail("row_group has " + std::to_string(n_row_group) + " entries, the graph has " + std::to_string(g_n_) + " ids");
+    if (allow_bits && !allows_any(allow_bits, nbits, g_n_)) { // no candidate: padding in rows of k, no launch
+        pad_results(out_ids, out_d, (size_t)nq * (size_t)k);
+        for (int i = 0; i < nq; ++i) out_flag[i] = 0;
+        return true;
+    }
+    if (!bind() || !x_clabels_.grow((size_t)std::max<long long>(g_n_, 1))) return false;
+    if (g_n_ > 0 && !staged_upload(reinterpret_cast<float *>(x_clabels_.get()), reinterpret_cast<const float *>(row_group), 4 * (size_t)g_n_)) return false;
+    const RowCollapse rc{x_clabels_, g_n_, per_group, k};
+    struct Scope { Device *d; ~Scope() { d->row_collapse_ = nullptr; } } scope{this};
+    row_collapse_ = &rc;
+    if (allow_bits) return search_filtered(nq, entry, entry_layer, ef, beam, allow_bits, nbits, out_ids, out_d, out_flag, search_layer);
+    std::vector<SearchJob> jobs((size_t)nq);
+    for (int i = 0; i < nq; ++i) jobs[(size_t)i] = SearchJob{i, entry, entry_layer, search_layer, -1, 0};
+    return search_batch(jobs.data(), nq, ef, beam, out_ids, out_d, out_flag);
 }
 
 // The group lists of a grouped flat scan: row_group[0, n) up, counts | offsets | cursors and the members on the device (a CSR in
@@ -4975,6 +5078,19 @@ DEV_API int hnswdev_exact_knn_grouped(void *ctx, const float *queries, int nq, l
 {
     CTX_OR_FAIL();
     return d->exact_knn_grouped(queries, nq, n_rows, k, row_group, n_row_group, query_group, n_groups, out_ids, out_dists) ? 0 : -1;
+}
+DEV_API int hnswdev_exact_knn_collapsed(void *ctx, const float *queries, int nq, long long n_rows, int k, const int *row_group, long long n_row_group,
+                                        int per_group, const uint32_t *allow_bits, long long nbits, int *out_ids, float *out_dists)
+{
+    CTX_OR_FAIL();
+    return d->exact_knn_collapsed(queries, nq, n_rows, k, row_group, n_row_group, per_group, allow_bits, nbits, out_ids, out_dists) ? 0 : -1;
+}
+DEV_API int hnswdev_exact_collapsed_info(void *ctx, uint64_t out[4])
+{
+    CTX_OR_FAIL();
+    if (!out) return -1;
+    d->exact_collapsed_info(out);
+    return 0;
 }
 DEV_API int hnswdev_exact_grouped_info(void *ctx, uint64_t out[4])
 {

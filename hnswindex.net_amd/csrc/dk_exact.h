@@ -19,6 +19,9 @@
 //                                               query -- its place in the caller's order -- so exact_range_sort_kernel runs as it is
 // and hnswdev_exact_knn_by_id: the queries are stored rows, and a query's own row is no candidate.
 //   exact_scan_kernel<M, ExactTopKSelf>         ExactTopK, but the pair (query q, row id self[q]) produces no key and is not counted
+// and hnswdev_exact_knn_collapsed: at most per_group results per label row_group[id] -- the result is shaped, not the candidates.
+//   exact_scan_kernel<M, ExactTopKCollapse>     ExactTopK's lists with a label beside every key; exact_list_insert_collapsed drops, evicts or inserts
+//   exact_merge_collapsed_kernel                one wave per query: the chunks' collapsed lists -> the collapsed final k
 // The kernels are compiled in the exact_<metric> units (exact_unit.hip, HNSW_EXACT_UNIT) and reached through the launchers declared here, so
 // that device_backend.hip holds none of their code.
 #pragma once
@@ -67,6 +70,7 @@ struct ExactTopK {
     static constexpr bool kRange = false;
     static constexpr bool kGrouped = false;
     static constexpr bool kSelf = false;
+    static constexpr bool kCollapse = false;
 };
 // ExactTopKSelf: ExactTopK where query q of the round is the stored row of id self[q] and that id is no candidate of it: the pair
 // produces no key and is not counted in ExactScanArgs::evals.  A duplicate of the row under another id is a candidate like any.
@@ -74,12 +78,28 @@ struct ExactTopKSelf {
     static constexpr bool kRange = false;
     static constexpr bool kGrouped = false;
     static constexpr bool kSelf = true;
+    static constexpr bool kCollapse = false;
     const int *self;               // [nq of the round]
+};
+// ExactTopKCollapse: the lists hold the COLLAPSED k smallest keys -- the first k keys of the ascending order that
+// have fewer than per_group keys of their own label row_group[id] in front of them.  A list of labels stands beside every list of
+// keys in LDS (4 more bytes per entry: exact_scan_lds' entry_bytes is 12).  Labels are compared for equality, nothing else.
+// info[0]: keys below their list's k-th that the cap dropped; info[1]: entries a key of their label evicted -- added up over
+// the scan's and the merge's waves (what they are depends on the order the keys arrive in; the lists do not).
+struct ExactTopKCollapse {
+    static constexpr bool kRange = false;
+    static constexpr bool kGrouped = false;
+    static constexpr bool kSelf = false;
+    static constexpr bool kCollapse = true;
+    const int *row_group;          // [every id of the list]
+    int per_group;                 // 1 <= per_group <= k
+    unsigned long long *info;      // [2]
 };
 struct ExactRange {
     static constexpr bool kRange = true;
     static constexpr bool kGrouped = false;
     static constexpr bool kSelf = false;
+    static constexpr bool kCollapse = false;
     float range;
     unsigned *counts;              // [nq]
     const long long *seg_off;      // [nq + 1]
@@ -108,6 +128,7 @@ struct ExactTopKGrouped {
     static constexpr bool kRange = false;
     static constexpr bool kGrouped = true;
     static constexpr bool kSelf = false;
+    static constexpr bool kCollapse = false;
     const ExactWorkItem *items;
 };
 // ExactRangeGrouped: ExactRange's segments behind ExactTopKGrouped's work items (list0, n_chunks and slot of an item are not read).
@@ -119,6 +140,7 @@ struct ExactRangeGrouped {
     static constexpr bool kRange = true;
     static constexpr bool kGrouped = true;
     static constexpr bool kSelf = false;
+    static constexpr bool kCollapse = false;
     float range;
     unsigned *counts;              // [segments]
     const long long *seg_off;      // [segments + 1]
@@ -133,11 +155,14 @@ struct ExactMergeItem {
     int out_row;         // its row of the round's output: the query's original place in the round
 };
 
-// LDS of one scan block
-inline size_t exact_scan_lds(int qtile, int piece, int dim, int k)
+// LDS of one scan block.  entry_bytes: what a list entry takes -- 8, the key; 12 with ExactTopKCollapse's label (the labels of all
+// lists, and then those of the pending keys, stand behind everything else, so the rest of the layout is the same for every sink).
+constexpr int kExactKeyBytes = 8, kExactCollapseEntryBytes = 12;
+inline size_t exact_scan_lds(int qtile, int piece, int dim, int k, int entry_bytes = kExactKeyBytes)
 {
     const size_t qtr = (size_t)((qtile + kExactRQ - 1) / kExactRQ * kExactRQ), qw = (size_t)(piece < dim ? piece : dim);
-    return ((qtr * qw * 4 + 15) & ~(size_t)15) + qtr * (size_t)k * 8 + qtr * 8 + (size_t)kExactRQ * kExactIterRows * 8 + 16;
+    const size_t pending = (size_t)kExactRQ * kExactIterRows * (entry_bytes > kExactKeyBytes ? 12 : 8); // (a pending key's label travels with it)
+    return ((qtr * qw * 4 + 15) & ~(size_t)15) + qtr * (size_t)k * (size_t)entry_bytes + qtr * 8 + pending + 16;
 }
 
 template <int METRIC>
@@ -146,6 +171,11 @@ template <int METRIC>
 hipError_t exact_range_scan_launch(const ExactScanArgs &a, const ExactRange &sink, unsigned n_qtiles, size_t lds, hipStream_t st);
 template <int METRIC>
 hipError_t exact_self_scan_launch(const ExactScanArgs &a, const ExactTopKSelf &sink, unsigned n_qtiles, size_t lds, hipStream_t st);
+template <int METRIC> // lds: exact_scan_lds with kExactCollapseEntryBytes
+hipError_t exact_collapsed_scan_launch(const ExactScanArgs &a, const ExactTopKCollapse &sink, unsigned n_qtiles, size_t lds, hipStream_t st);
+// exact_merge_launch for the collapsed lists: the labels are looked up in row_group, info as ExactTopKCollapse::info
+hipError_t exact_merge_collapsed_launch(const unsigned long long *lists, int n_chunks, int k, int nq, const int *row_group, int per_group,
+                                        unsigned long long *info, int *out_ids, float *out_d, hipStream_t st);
 // words: the masked bitset; block_off[b]: set bits in front of word b * kExactCompactWords
 hipError_t exact_compact_launch(const unsigned *words, long long n_words, const long long *block_off, int *out_ids, hipStream_t st);
 hipError_t exact_merge_launch(const unsigned long long *lists, int n_chunks, int k, int nq, int *out_ids, float *out_d, hipStream_t st);
@@ -203,6 +233,52 @@ __device__ __forceinline__ void exact_list_insert(unsigned long long *L, int k, 
     }
 }
 
+// x, whose label is g, into the COLLAPSED ascending list L[0, k) of one wave, G[0, k) the labels of its entries and m the cap per
+// label (ExactTopKCollapse).  The list stays what the walk over everything offered so far keeps: ascending keys, at
+// most m of a label.  First the wave counts, 64 entries at a time from the bottom up to the first empty slot (an empty slot is
+// key == kExactEmpty; its label is never read): `ins`, the entries below x -- x's place; `below` / `total`, the entries of label g
+// below x / at all; `last`, the place of the largest entry of label g.  Then
+//   below >= m                 x is dropped: m of its label go before it
+//   total >= m                 the largest entry of label g leaves (it is above x): entries [ins, last) move up one, x goes in at ins
+//   otherwise, x < L[k - 1]    the ordinary insert: entries [ins, end) move up one, end the first empty slot, or k - 1 whose entry drops out
+// x may be any key: the check against the k-th is this function's (a key that is not below the k-th can never enter: in a full list every
+// entry of its label is then below it, so below == total, and either that is >= m or the ordinary insert has no place for it).  The
+// callers skip such keys before the call only to save the counting pass.
+// Every count comes from a ballot and every bound of both loops is the same in all lanes: no lane leaves a loop on its own.
+// One wave: its LDS operations execute in order.
+__device__ __forceinline__ void exact_list_insert_collapsed(unsigned long long *L, int *G, int k, int m, unsigned long long x, int g, int lane,
+                                                            unsigned &dropped, unsigned &evicted)
+{
+    int ins = 0, below = 0, total = 0, last = -1, filled = 0;
+    for (int base = 0; base < k; base += 64) {
+        const int i = base + lane;
+        const unsigned long long v = i < k ? L[i] : kExactEmpty;
+        const bool same = v != kExactEmpty && G[i] == g; // (v is a real key: i < k)
+        const unsigned long long b_same = __ballot(same);
+        ins += __popcll(__ballot(v < x));
+        below += __popcll(__ballot(same && v < x));
+        total += __popcll(b_same);
+        filled += __popcll(__ballot(v != kExactEmpty));
+        if (b_same) last = base + 63 - __clzll((long long)b_same);
+        if (__ballot(v == kExactEmpty)) break; // the list ends in this piece
+    }
+    int end = -1; // the place that is vacated, -1: x does not enter
+    if (below >= m) ++dropped;
+    else if (total >= m) { ++evicted; end = last; }
+    else if (x < L[k - 1]) end = filled < k ? filled : k - 1; // a list that is not full gives up its first empty slot: nothing above it moves
+    if (end >= 0) {
+        for (int base = end & ~63; base >= (ins & ~63); base -= 64) { // from the top down: a piece reads the one below it before that is written
+            const int i = base + lane;
+            const bool in = i >= ins && i <= end, moved = in && i > ins;
+            const unsigned long long nk = moved ? L[i - 1] : x;
+            const int ng = moved ? G[i - 1] : g;
+            wave_lds_sync();
+            if (in) { L[i] = nk; G[i] = ng; }
+            wave_lds_sync();
+        }
+    }
+}
+
 template <int METRIC, class SINK>
 __global__ void __launch_bounds__(kExactThreads) exact_scan_kernel(const ExactScanArgs a, const SINK sink)
 {
@@ -217,6 +293,9 @@ __global__ void __launch_bounds__(kExactThreads) exact_scan_kernel(const ExactSc
     unsigned long long *thr = lists + (size_t)QTR * k;
     unsigned long long *pend = thr + QTR;
     int *pend_cnt = reinterpret_cast<int *>(pend + RQ * kExactIterRows);
+    [[maybe_unused]] int *labels = pend_cnt + 4; // ExactTopKCollapse: [QTR][k], the label of every list entry (exact_scan_lds: behind the rest)
+    [[maybe_unused]] int *pend_lab = labels + (size_t)QTR * k; // ... [RQ][kExactIterRows], the label of every pending key
+    [[maybe_unused]] unsigned dropped = 0, evicted = 0; // ... what this wave's inserts dropped and evicted (the same in all its lanes)
     // the block's queries [q0, q0 + its number) of the round and entries [lo, hi) of the id list: a work item's, or worked out from
     // blockIdx.  q_in: a query of the round that this block answers; q_clamp: past the last of them a slot shadows it.
     long long q0, lo, hi;
@@ -255,6 +334,7 @@ __global__ void __launch_bounds__(kExactThreads) exact_scan_kernel(const ExactSc
         int rid[RR];
         bool rvalid[RR];
         const float *rp[RR];
+        [[maybe_unused]] int rlab[RR]; // ExactTopKCollapse: the rows' labels, asked for here so that they arrive behind the measuring
 #pragma unroll
         for (int r = 0; r < RR; ++r) {
             long long idx = base + grp * RR + r;
@@ -262,6 +342,7 @@ __global__ void __launch_bounds__(kExactThreads) exact_scan_kernel(const ExactSc
             if (!rvalid[r]) idx = hi - 1;
             rid[r] = a.ids ? a.ids[idx] : (int)idx;
             rp[r] = a.rows + (size_t)rid[r] * (size_t)rw;
+            if constexpr (SINK::kCollapse) rlab[r] = sink.row_group[rid[r]];
         }
         for (int qsub = 0; qsub < QT && q_in(q0 + qsub); qsub += RQ) {
             float acc[RQ][RR];
@@ -466,6 +547,7 @@ __global__ void __launch_bounds__(kExactThreads) exact_scan_kernel(const ExactSc
                             if (key < t) {
                                 const int slot = atomicAdd(&pend_cnt[q], 1);
                                 pend[q * kExactIterRows + slot] = key;
+                                if constexpr (SINK::kCollapse) pend_lab[q * kExactIterRows + slot] = rlab[r];
                                 offered = 1;
                             }
                         }
@@ -477,7 +559,12 @@ __global__ void __launch_bounds__(kExactThreads) exact_scan_kernel(const ExactSc
                         unsigned long long *L = lists + (size_t)(qsub + wave) * k;
                         for (int i = 0; i < cnt; ++i) {
                             const unsigned long long x = pend[wave * kExactIterRows + i];
-                            if (x < L[k - 1]) exact_list_insert(L, k, x, lane);
+                            if constexpr (SINK::kCollapse) { // (the label travelled with the key: no flush waits for memory)
+                                const int g = pend_lab[wave * kExactIterRows + i];
+                                if (x < L[k - 1]) exact_list_insert_collapsed(L, labels + (size_t)(qsub + wave) * k, k, sink.per_group, x, g, lane, dropped, evicted);
+                            } else {
+                                if (x < L[k - 1]) exact_list_insert(L, k, x, lane);
+                            }
                         }
                         wave_lds_sync();
                         if (lane == 0) { thr[qsub + wave] = L[k - 1]; pend_cnt[wave] = 0; }
@@ -489,6 +576,10 @@ __global__ void __launch_bounds__(kExactThreads) exact_scan_kernel(const ExactSc
     }
     __syncthreads();
     if (measured) atomicAdd(a.evals, (unsigned long long)measured); // one atomic per group that measured anything
+    if constexpr (SINK::kCollapse) {
+        if (lane == 0 && dropped) atomicAdd(&sink.info[0], (unsigned long long)dropped);
+        if (lane == 0 && evicted) atomicAdd(&sink.info[1], (unsigned long long)evicted);
+    }
     if constexpr (!SINK::kRange) {
         for (int qi = 0; qi < QT && q_in(q0 + qi); ++qi) {
             unsigned long long *dst;
@@ -518,6 +609,13 @@ template <int METRIC>
 hipError_t exact_self_scan_launch(const ExactScanArgs &a, const ExactTopKSelf &sink, unsigned n_qtiles, size_t lds, hipStream_t st)
 {
     hipLaunchKernelGGL((exact_scan_kernel<METRIC, ExactTopKSelf>), dim3(n_qtiles, (unsigned)a.n_chunks), dim3(kExactThreads), lds, st, a, sink);
+    return hipGetLastError();
+}
+
+template <int METRIC>
+hipError_t exact_collapsed_scan_launch(const ExactScanArgs &a, const ExactTopKCollapse &sink, unsigned n_qtiles, size_t lds, hipStream_t st)
+{
+    hipLaunchKernelGGL((exact_scan_kernel<METRIC, ExactTopKCollapse>), dim3(n_qtiles, (unsigned)a.n_chunks), dim3(kExactThreads), lds, st, a, sink);
     return hipGetLastError();
 }
 
@@ -588,6 +686,46 @@ __global__ void __launch_bounds__(64) exact_merge_kernel(const unsigned long lon
         }
     }
     wave_lds_sync();
+    for (int i = lane; i < k; i += 64) {
+        const unsigned long long key = L[i];
+        out_ids[q * k + i] = key == kExactEmpty ? -1 : (int)(unsigned)key;
+        out_d[q * k + i] = key == kExactEmpty ? __uint_as_float(0x7fc00000u) : exact_key_dist(key);
+    }
+}
+
+// exact_merge_kernel over collapsed lists (ExactTopKCollapse): the chunks' lists hold keys only, so the label of an incoming key is
+// looked up in row_group, and the insert is the collapsed one.  A list is still left at its first entry that is not below the
+// current k-th: such a key cannot enter (in a full list every entry of its label is then below it), and the rest of its list is
+// larger still.  (A copy of the merge's loop, as exact_merge_grouped_kernel's is and for its reason; a change goes into all three.)
+__global__ void __launch_bounds__(64) exact_merge_collapsed_kernel(const unsigned long long *__restrict__ lists, int n_chunks, int k, const int *__restrict__ row_group,
+                                                                   int per_group, unsigned long long *__restrict__ info, int *__restrict__ out_ids,
+                                                                   float *__restrict__ out_d)
+{
+    __shared__ unsigned long long L[kExactMaxK];
+    __shared__ int G[kExactMaxK];
+    const int lane = threadIdx.x;
+    const size_t q = blockIdx.x;
+    unsigned dropped = 0, evicted = 0;
+    for (int i = lane; i < k; i += 64) L[i] = kExactEmpty;
+    wave_lds_sync();
+    for (int c = 0; c < n_chunks; ++c) {
+        const unsigned long long *src = lists + (q * n_chunks + c) * (size_t)k;
+        bool more = true;
+        for (int i0 = 0; i0 < k && more; i0 += 64) {
+            const unsigned long long mine = i0 + lane < k ? src[i0 + lane] : kExactEmpty;
+            const int mine_g = mine != kExactEmpty ? row_group[(unsigned)mine] : 0; // the labels of the piece's keys, looked up at once
+            const int n = k - i0 < 64 ? k - i0 : 64;
+            for (int t = 0; t < n; ++t) { // (x, and with it the break, is the same in all lanes)
+                const unsigned lo32 = __shfl((unsigned)mine, t, 64), hi32 = __shfl((unsigned)(mine >> 32), t, 64);
+                const unsigned long long x = ((unsigned long long)hi32 << 32) | lo32;
+                if (x >= L[k - 1]) { more = false; break; } // (a list's end, ~0, leaves here)
+                exact_list_insert_collapsed(L, G, k, per_group, x, __builtin_amdgcn_readfirstlane(__shfl(mine_g, t, 64)), lane, dropped, evicted);
+            }
+        }
+    }
+    wave_lds_sync();
+    if (lane == 0 && dropped) atomicAdd(&info[0], (unsigned long long)dropped);
+    if (lane == 0 && evicted) atomicAdd(&info[1], (unsigned long long)evicted);
     for (int i = lane; i < k; i += 64) {
         const unsigned long long key = L[i];
         out_ids[q * k + i] = key == kExactEmpty ? -1 : (int)(unsigned)key;
@@ -768,6 +906,12 @@ hipError_t exact_compact_launch(const unsigned *words, long long n_words, const 
 hipError_t exact_merge_launch(const unsigned long long *lists, int n_chunks, int k, int nq, int *out_ids, float *out_d, hipStream_t st)
 {
     hipLaunchKernelGGL(exact_merge_kernel, dim3((unsigned)nq), dim3(64), 0, st, lists, n_chunks, k, out_ids, out_d);
+    return hipGetLastError();
+}
+hipError_t exact_merge_collapsed_launch(const unsigned long long *lists, int n_chunks, int k, int nq, const int *row_group, int per_group,
+                                        unsigned long long *info, int *out_ids, float *out_d, hipStream_t st)
+{
+    hipLaunchKernelGGL(exact_merge_collapsed_kernel, dim3((unsigned)nq), dim3(64), 0, st, lists, n_chunks, k, row_group, per_group, info, out_ids, out_d);
     return hipGetLastError();
 }
 #endif // HNSW_EXACT_COMMON

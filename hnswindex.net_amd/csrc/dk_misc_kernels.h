@@ -186,6 +186,44 @@ gather_rows_kernel(const float *__restrict__ rows, int pitch, long long n_rows, 
     }
 }
 #endif
+#ifdef HNSW_HOST_TU
+// knn_query_collapsed: the rows of a traversal's answer, still on the device, collapsed in place.  One wave per row
+// of `width` entries (ids and distances, ascending as the traversal left them, padded with -1): the row and the labels of its
+// entries go to LDS first, then the wave walks the entries in order -- an entry is kept while fewer than m kept entries have its
+// label, counted with one ballot per 64 kept entries -- and lane 0 writes the kept entry to the next place of the row's first k
+// columns; what is left of those is padded with -1 / NaN.  Padding, and an id without a label (id >= n_labels: a row that was
+// handed back holds nothing meaningful), is skipped.  Every loop bound and branch is the same in all lanes of the wave.
+// LDS: width x 12 bytes + k x 4 bytes.
+__global__ void __launch_bounds__(64) collapse_rows_kernel(int *__restrict__ ids, float *__restrict__ d, int width, int k, const int *__restrict__ labels,
+                                                           long long n_labels, int m)
+{
+    extern __shared__ int collapse_lds[];
+    int *r_id = collapse_lds, *r_lab = r_id + width, *kept_lab = r_lab + width;
+    float *r_d = reinterpret_cast<float *>(kept_lab + k);
+    const int lane = threadIdx.x;
+    int *row_ids = ids + (size_t)blockIdx.x * width;
+    float *row_d = d + (size_t)blockIdx.x * width;
+    for (int i = lane; i < width; i += 64) {
+        const int id = row_ids[i];
+        const bool real = id >= 0 && id < n_labels;
+        r_id[i] = real ? id : -1;
+        r_d[i] = row_d[i];
+        r_lab[i] = real ? labels[id] : 0;
+    }
+    wave_lds_sync();
+    int kept = 0;
+    for (int e = 0; e < width && kept < k; ++e) {
+        const int id = r_id[e], g = r_lab[e]; // (the same address in every lane)
+        int same = 0;
+        for (int base = 0; base < kept; base += 64) same += __popcll(__ballot(base + lane < kept && kept_lab[base + lane] == g));
+        const bool keep = id >= 0 && same < m;
+        if (keep && lane == 0) { row_ids[kept] = id; row_d[kept] = r_d[e]; kept_lab[kept] = g; }
+        wave_lds_sync();
+        kept += keep ? 1 : 0;
+    }
+    for (int i = kept + lane; i < k; i += 64) { row_ids[i] = -1; row_d[i] = __uint_as_float(0x7fc00000u); }
+}
+#endif
 #ifdef HNSW_HOST_TU // non-template kernels: only the unit that launches them defines them
 __global__ void sqrt_rn_kernel(const double *in, double *out, int n)
 {

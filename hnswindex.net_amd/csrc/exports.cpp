@@ -224,6 +224,48 @@ API int hnsw_mi355x_exact_knn_query_grouped(void *handle, const float *vectors, 
     return 0;
 }
 
+// Exact k nearest neighbours with at most per_group results per label.  Exclusive, like the calls above.
+API int hnsw_mi355x_exact_knn_query_collapsed(void *handle, const float *vectors, int count, int dim, int k, const int *row_group, long long n_row_group,
+                                              int per_group, const uint32_t *allow_words, long long nbits, int *out_ids, float *out_dists)
+{
+    if (!handle) return 0;
+    if (count <= 0) return 0;
+    if (!vectors || !out_ids || !out_dists || dim <= 0) { set_error("System.ArgumentNullException: hnsw_mi355x_exact_knn_query_collapsed"); return -1; }
+    if (allow_words && nbits < 0) { set_error("System.ArgumentOutOfRangeException: hnsw_mi355x_exact_knn_query_collapsed: nbits < 0"); return -1; }
+    if (!row_group || n_row_group < 0) {
+        set_error("System.ArgumentException: hnsw_mi355x_exact_knn_query_collapsed: row_group must not be NULL and n_row_group must be >= 0");
+        return -1;
+    }
+    LOCK_INDEX(handle);
+    std::string err;
+    if (static_cast<HnswIndex *>(handle)->exact_knn_query_collapsed(vectors, count, dim, k, row_group, n_row_group, per_group, allow_words, nbits, out_ids, out_dists, err) < 0) {
+        set_error(err);
+        return -1;
+    }
+    return 0;
+}
+
+// KnnQuery with at most per_group results per label: the traversal at k = beam, collapsed to k.
+API int hnsw_mi355x_knn_query_collapsed(void *handle, const float *vectors, int count, int dim, int k, int beam, const int *row_group, long long n_row_group,
+                                        int per_group, int layer, const uint32_t *allow_words, long long nbits, int *out_ids, float *out_dists)
+{
+    if (!handle) return 0;
+    if (count <= 0) return 0;
+    if (!vectors || !out_ids || !out_dists || dim <= 0) { set_error("System.ArgumentNullException: hnsw_mi355x_knn_query_collapsed"); return -1; }
+    if (allow_words && nbits < 0) { set_error("System.ArgumentException: hnsw_mi355x_knn_query_collapsed: nbits must be >= 0"); return -1; }
+    if (!row_group || n_row_group < 0) {
+        set_error("System.ArgumentException: hnsw_mi355x_knn_query_collapsed: row_group must not be NULL and n_row_group must be >= 0");
+        return -1;
+    }
+    LOCK_INDEX(handle);
+    std::string err;
+    if (static_cast<HnswIndex *>(handle)->knn_query_collapsed(vectors, count, dim, k, beam, row_group, n_row_group, per_group, layer, allow_words, nbits, out_ids, out_dists, err) < 0) {
+        set_error(err); // (hnsw_index.cpp names the exception per case: a device failure is no argument error)
+        return -1;
+    }
+    return 0;
+}
+
 // The tagged calls: a tag word per id, a mask per query, `match` 0 any / 1 all.  The arguments both check here.
 static bool tagged_args(const char *who, bool pointers_ok, const uint32_t *row_tags, long long n_row_tags, int match)
 {
@@ -704,6 +746,13 @@ API int hnsw_mi355x_exact_range_grouped_info(void *h, uint64_t out[4])
     if (!h || !out) return -1;
     LOCK_INDEX(h);
     static_cast<HnswIndex *>(h)->exact_range_grouped_info(out);
+    return 0;
+}
+API int hnsw_mi355x_exact_collapsed_info(void *h, uint64_t out[4])
+{
+    if (!h || !out) return -1;
+    LOCK_INDEX(h);
+    static_cast<HnswIndex *>(h)->exact_collapsed_info(out);
     return 0;
 }
 API int hnsw_mi355x_exact_grouped_info(void *h, uint64_t out[4])

@@ -1681,6 +1681,67 @@ int HnswIndex::knn_query_general(const float *queries, int count, int dim, int k
         "search_filtered failed", err);
 }
 
+// The collapse walk over one answered row on the host (what collapse_rows_kernel does to a row on the device): the entries of
+// ids / d[0, width) in order, padding skipped, an entry kept while fewer than m kept entries have its label, until k are kept; the
+// rest of out_ids / out_d[0, k) is padding.
+static void collapse_host_row(const int *ids, const float *d, int width, const int *row_group, long long n_row_group, int m, int k, int *out_ids, float *out_d)
+{
+    int kept = 0;
+    for (int e = 0; e < width && kept < k; ++e) {
+        const int id = ids[e];
+        if (id < 0 || id >= n_row_group) continue;
+        int same = 0;
+        for (int j = 0; j < kept; ++j) same += row_group[out_ids[j]] == row_group[id];
+        if (same < m) { out_ids[kept] = id; out_d[kept] = d[e]; ++kept; }
+    }
+    pad_results(out_ids + kept, out_d + kept, (size_t)(k - kept));
+}
+
+// KnnQuery with a collapsed result: knn_query_general's traversal at k = beam, and of each row the first k survivors
+// of the walk.  The device way collapses the rows in device memory and copies k columns out; the host way (no device traversal, a
+// hand-back) answers rows of `beam` entries into an array of its own and walks them here.  Both are this one function's two lambdas.
+int HnswIndex::knn_query_collapsed(const float *queries, int count, int dim, int k, int beam, const int *row_group, long long n_row_group, int per_group,
+                                   int layer, const uint32_t *allow_bits, long long nbits, int *out_ids, float *out_dists, std::string &err)
+{
+    if (count <= 0) return 0;
+    if (failed(err)) return -1;
+    const std::string who = "hnsw_mi355x_knn_query_collapsed";
+    if (k >= 1 && (per_group < 1 || per_group > k)) { err = "System.ArgumentOutOfRangeException: " + who + ": per_group = " + std::to_string(per_group) + " is outside [1, k = " + std::to_string(k) + "]"; return -1; }
+    if (k >= 1 && beam < k) { err = "System.ArgumentOutOfRangeException: " + who + ": beam = " + std::to_string(beam) + " is below k = " + std::to_string(k); return -1; }
+    if (n_row_group < graph_.length) { err = "System.ArgumentException: " + who + ": row_group has " + std::to_string(n_row_group) + " entries, the index's length is " + std::to_string(graph_.length); return -1; }
+    const bool filtered = allow_bits != nullptr;
+    const AllowBits allow = filtered ? AllowBits{allow_bits, nbits} : AllowBits{};
+    const bool any = !filtered || allows_any(allow_bits, nbits, graph_.length);
+    const bool empty = k < 1 || graph_.entry < 0 || graph_.count <= 0;
+    if (!empty && !layer_ok(layer, err)) { err = "System.IndexOutOfRangeException: " + who + ": " + err; return -1; } // (as hnsw_mi355x_knn_query_at_layer)
+    if (empty || !any) {
+        pad_results(out_ids, out_dists, (size_t)count * (size_t)std::max(k, 0));
+        return 0;
+    }
+    if (set_resident_queries(queries, count, dim, err) < 0) return -1;
+    const int ef = std::max(p_.min_nn, beam); // HNSWIndex.cs:115, for the beam-wide call
+    const int ep = graph_.entry, top = graph_.top_layer();
+    std::vector<int> wide_ids;   // the host way's rows of `beam` entries, allocated when it is taken
+    std::vector<float> wide_d;
+    return answer_resident(count, ef,
+        [&](Device *ctx, int cnt, long long lo, int *flag) -> bool {
+            return ctx->search_collapsed(cnt, ep, top, ef, beam, k, row_group, n_row_group, per_group, allow_bits, nbits, out_ids + (size_t)lo * k,
+                                         out_dists + (size_t)lo * k, flag, layer);
+        },
+        [&](const int *which, int n) {
+            // (count rows even for a few hand-backs: knn_query_lockstep writes query qi's row at qi * beam of what it is given)
+            wide_ids.resize((size_t)count * (size_t)beam);
+            wide_d.resize((size_t)count * (size_t)beam);
+            if (knn_query_lockstep(which, n, beam, wide_ids.data(), wide_d.data(), err, allow, layer) < 0) return -1;
+            for (int i = 0; i < n; ++i) {
+                const size_t qi = (size_t)(which ? which[i] : i);
+                collapse_host_row(&wide_ids[qi * beam], &wide_d[qi * beam], beam, row_group, n_row_group, per_group, k, out_ids + qi * k, out_dists + qi * k);
+            }
+            return 0;
+        },
+        "search_collapsed failed", err);
+}
+
 // The grouped calls' argument rules (group_args_error, device_backend.h) as the ABI reports a breach: `who` is the ABI call.
 static bool group_args_ok(const char *who, const int *query_group, int count, int n_groups, std::string &err)
 {
@@ -1974,6 +2035,35 @@ int HnswIndex::exact_knn_query(const float *queries, int count, int dim, int k, 
     const long long length = exact_candidates(allow_bits, nbits, live);
     // (the scan stages its queries in a buffer of its own: the resident set, sharded or not, stays what it was)
     if (!dev_->exact_knn(queries, count, length, k, allow_bits, nbits, out_ids, out_dists)) { err = get_dev_error(); return -1; }
+    return 0;
+}
+
+// The flat scan with a collapsed result: exact_knn_query's candidates -- the live set is ANDed into the bitset as
+// there, so a removed id is no candidate and counts towards no label's cap -- and the labels as the caller gave them.
+int HnswIndex::exact_knn_query_collapsed(const float *queries, int count, int dim, int k, const int *row_group, long long n_row_group, int per_group,
+                                         const uint32_t *allow_bits, long long nbits, int *out_ids, float *out_dists, std::string &err)
+{
+    if (count <= 0) return 0;
+    if (failed(err)) return -1;
+    const std::string who = "hnsw_mi355x_exact_knn_query_collapsed";
+    if (k > kExactMaxK) { err = "System.ArgumentOutOfRangeException: " + who + ": k = " + std::to_string(k) + " is above the limit of " + std::to_string(kExactMaxK); return -1; }
+    if (k >= 1 && (per_group < 1 || per_group > k)) {
+        err = "System.ArgumentOutOfRangeException: " + who + ": per_group = " + std::to_string(per_group) + " is outside [1, k = " + std::to_string(k) + "]";
+        return -1;
+    }
+    if (n_row_group < graph_.length) {
+        err = "System.ArgumentException: " + who + ": row_group has " + std::to_string(n_row_group) + " entries, the index's length is " + std::to_string(graph_.length);
+        return -1;
+    }
+    if (k < 1 || graph_.count <= 0) {
+        pad_results(out_ids, out_dists, (size_t)count * (size_t)std::max(k, 0));
+        return 0;
+    }
+    if (!ensure_dim(dim, err)) return -1;
+    std::vector<uint32_t> live;
+    const long long length = exact_candidates(allow_bits, nbits, live);
+    // (the scan stages its queries in a buffer of its own: the resident set, sharded or not, stays what it was)
+    if (!dev_->exact_knn_collapsed(queries, count, length, k, row_group, n_row_group, per_group, allow_bits, nbits, out_ids, out_dists)) { err = get_dev_error(); return -1; }
     return 0;
 }
 

@@ -68,6 +68,16 @@ public:
     int exact_knn_query_grouped(const float *queries, int count, int dim, int k, const int *row_group, long long n_row_group, const int *query_group,
                                 int n_groups, int *out_ids, float *out_dists, std::string &err);
     void exact_grouped_info(uint64_t out[4]) const { if (dev_) dev_->exact_grouped_info(out); else out[0] = out[1] = out[2] = out[3] = 0; }
+    // hnsw_mi355x_exact_knn_query_collapsed: exact_knn_query's candidates, at most per_group results per label
+    // row_group[id] (Device::exact_knn_collapsed).  row_group must cover the index's length.
+    int exact_knn_query_collapsed(const float *queries, int count, int dim, int k, const int *row_group, long long n_row_group, int per_group,
+                                  const uint32_t *allow_bits, long long nbits, int *out_ids, float *out_dists, std::string &err);
+    void exact_collapsed_info(uint64_t out[4]) const { if (dev_) dev_->exact_collapsed_info(out); else out[0] = out[1] = out[2] = out[3] = 0; }
+    // hnsw_mi355x_knn_query_collapsed: per query the first k survivors of the collapse walk over the row that
+    // knn_query_general(queries, beam, layer, allow) returns -- the same traversal, through answer_resident; on the device the rows are
+    // collapsed before the copy-out (Device::search_collapsed), a host answer is walked by collapse_host_row.
+    int knn_query_collapsed(const float *queries, int count, int dim, int k, int beam, const int *row_group, long long n_row_group, int per_group, int layer,
+                            const uint32_t *allow_bits, long long nbits, int *out_ids, float *out_dists, std::string &err);
     // hnsw_mi355x_exact_knn_query_tagged: exact_knn_query with a tag mask per query (Device::exact_knn_tagged): query i's
     // candidates are the live ids j < n_row_tags whose word row_tags[j] matches query_tags[i] under `match` (0 any, 1 all).  0 or -1.
     int exact_knn_query_tagged(const float *queries, int count, int dim, int k, const uint32_t *row_tags, long long n_row_tags, const uint32_t *query_tags,

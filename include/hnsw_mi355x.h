@@ -301,6 +301,38 @@ int hnsw_mi355x_exact_knn_query_grouped(void *handle, const float *vectors, int 
  * 0, or -1 for a NULL argument. */
 int hnsw_mi355x_exact_grouped_info(void *handle, uint64_t out[4]);
 
+/* hnsw_mi355x_exact_knn_query with a collapsed result (no reference counterpart): at most per_group results per
+ * label.  row_group is int32[n_row_group], indexed by id: the label of a row -- the document a chunk belongs to.  Per query, the
+ * live (and, with allow_words, allowed) ids are taken in hnsw_mi355x_exact_knn_query's order, ascending (distance, id); an id is
+ * kept while fewer than per_group kept ids have its label; the row of the result is the first k kept ids and their distances,
+ * padded with -1 / NaN when they run out.  Labels are compared for equality: no value is special, negative values are labels like
+ * any.  The filter restricts the candidates and the labels shape the result: removed and disallowed ids never count towards a
+ * label's cap.  With per_group == k the rows are hnsw_mi355x_exact_knn_query's, byte for byte.  Exact: one scan, no retry, whatever
+ * the labels' sizes.  Everything else is hnsw_mi355x_exact_knn_query's contract: distances, -0 / NaN representation, 1 <= k <= 1024,
+ * no graph read, always on the device and on the primary context alone, the handle taken exclusively, the resident query set
+ * untouched.  -1 with a message, nothing written: row_group NULL; n_row_group below the index's length (the message says both
+ * numbers); per_group < 1 or per_group > k; k > 1024.  NULL handle, count <= 0 and k < 1 behave as in hnsw_mi355x_exact_knn_query. */
+int hnsw_mi355x_exact_knn_query_collapsed(void *handle, const float *vectors, int count, int dim, int k, const int *row_group,
+                                          long long n_row_group, int per_group, const uint32_t *allow_words, long long nbits, int *out_ids,
+                                          float *out_dists);
+/* The traversal form of the collapse: per query the first k survivors of the same walk over the row that
+ * hnsw_mi355x_knn_query_at_layer(vectors, k = beam, layer, allow_words) returns, byte for byte, in that row's own order (the
+ * reference's order among equal distances included); padding is skipped and the result padded with -1 / NaN.  beam >= k, any value
+ * the plain call accepts as k.  It is approximate exactly as far as the plain call at that beam is: an id the traversal does not
+ * reach at width beam is not in the result, and a label with more than per_group near rows uses up beam entries.  Where the
+ * traversal runs on the device its rows are collapsed there and k columns come back.  row_group, n_row_group (at least the index's
+ * length), per_group (1 .. k) and allow_words as hnsw_mi355x_exact_knn_query_collapsed; layer as hnsw_mi355x_knn_query_at_layer.
+ * -1 with a message and nothing written for a breach of these; NULL handle, count <= 0 and k < 1 as hnsw_knn_query. */
+int hnsw_mi355x_knn_query_collapsed(void *handle, const float *vectors, int count, int dim, int k, int beam, const int *row_group,
+                                    long long n_row_group, int per_group, int layer, const uint32_t *allow_words, long long nbits, int *out_ids,
+                                    float *out_dists);
+/* Counters of hnsw_mi355x_exact_knn_query_collapsed on the primary context since hnsw_mi355x_reset_stats: out[0] collapsed calls that
+ * scanned, out[1] queries they scanned, out[2] keys that reached a list and were dropped because per_group nearer keys of their label
+ * stood in it, out[3] list entries that a nearer key of their label evicted.  out[2] and out[3] are counted by the scan's and the
+ * merge's waves and depend on the order in which keys arrive; the results do not.  (Launches and measured pairs count in
+ * hnswdev_stats.exact_*.)  0, or -1 for a NULL argument. */
+int hnsw_mi355x_exact_collapsed_info(void *handle, uint64_t out[4]);
+
 /* hnsw_mi355x_exact_range_query with a candidate group per query (no reference counterpart): the group arguments of
  * hnsw_mi355x_exact_knn_query_grouped -- row_group int32[n_row_group] indexed by id, query_group int32[count], the candidates of
  * query i the live ids j < n_row_group with row_group[j] == query_group[i], a value outside [0, n_groups) or an id past the
@@ -872,6 +904,14 @@ int hnswdev_exact_range_info(void *ctx, uint64_t out[4]);
  * row_group and are unordered; the result does not depend on their order. */
 int hnswdev_exact_knn_grouped(void *ctx, const float *queries, int nq, long long n_rows, int k, const int *row_group, long long n_row_group,
                               const int *query_group, int n_groups, int *out_ids, float *out_dists);
+/* The flat scan behind hnsw_mi355x_exact_knn_query_collapsed: hnswdev_exact_knn (its candidates, allow_bits and queries == NULL)
+ * with at most per_group results per value of row_group[id].  n_row_group must be at least min(n_rows, uploaded rows): every
+ * candidate id needs a label; fewer, row_group == NULL, per_group outside [1, k] and k > 1024 are -1 with a message and nothing
+ * written.  The labels are uploaded once per call. */
+int hnswdev_exact_knn_collapsed(void *ctx, const float *queries, int nq, long long n_rows, int k, const int *row_group, long long n_row_group,
+                                int per_group, const uint32_t *allow_bits, long long nbits, int *out_ids, float *out_dists);
+/* out[0 .. 3] as hnsw_mi355x_exact_collapsed_info, of this context; zeroed by hnswdev_reset_stats. */
+int hnswdev_exact_collapsed_info(void *ctx, uint64_t out[4]);
 /* out[0 .. 3] as hnsw_mi355x_exact_grouped_info, of this context; zeroed by hnswdev_reset_stats. */
 int hnswdev_exact_grouped_info(void *ctx, uint64_t out[4]);
 /* Measurement aid: *out_ms = the HIP-event time, in milliseconds, of the list-building kernels (count, offsets, place) of the
