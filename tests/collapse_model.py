@@ -45,6 +45,35 @@ def collapsed_rows(id_lists, d_lists, row_group, k, m):
     return ids, d
 
 
+def same(a, b):
+    """(ids, distances) pairs with equal shapes, equal ids and byte-equal distances."""
+    return a[0].shape == b[0].shape and (a[0] == b[0]).all() and a[1].tobytes() == np.ascontiguousarray(b[1]).tobytes()
+
+
+# The case in which the traversal at a beam of the whole index and the flat scan must agree (tests/test_gpu_knn_collapsed_edges.py):
+# a graph small enough that a beam of FULL_N holds every row.  tests/test_collapse_model.py checks on the CPU oracle that at this
+# seed and M, built one row at a time, every query's traversal returns all FULL_N rows, no two at the same distance.
+FULL_N, FULL_DIM, FULL_NQ, FULL_M, FULL_SEED = 300, 20, 48, 8, 40
+FULL_METRICS = ("sq_euclid", "cosine", "sq_euclid_i8")
+
+
+def full_case():
+    """(rows, queries) of that case: uniform, as everywhere."""
+    rng_x, rng_q = np.random.default_rng(FULL_SEED), np.random.default_rng(FULL_SEED + 1000)
+    return rng_x.random((FULL_N, FULL_DIM), dtype=np.float32), rng_q.random((FULL_NQ, FULL_DIM), dtype=np.float32)
+
+
+def reached_from_entry(ref, layer=0):
+    """How many nodes of an oracle.OracleIndex the entry point reaches over the out-edges of `layer`."""
+    seen, todo = {ref.entry_point}, [ref.entry_point]
+    while todo:
+        for j in ref.edges(todo.pop(), layer).tolist():
+            if j not in seen:
+                seen.add(j)
+                todo.append(j)
+    return len(seen)
+
+
 class CollapsedList:
     """One (query, chunk) list of the scan, or the merge's: k slots of (key, label), ascending, EMPTY where there is none."""
 

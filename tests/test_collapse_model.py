@@ -122,6 +122,40 @@ def test_the_merge_leaves_a_list_where_nothing_more_can_enter():
     assert full.entries() == [1, 10, 11, 12] and full.evicted + full.dropped == 0
 
 
+def test_rows_with_padding_inside_and_caps_of_more_than_64():
+    """The inputs tests/test_gpu_knn_collapsed_edges.py adds: a row of 7 entries and 33 paddings of which two share a label, and a
+    row long enough that each of two labels is capped at 60 kept entries."""
+    ids = np.full((1, 40), -1, np.int32)
+    ids[0, :7] = [11, 3, 8, 0, 5, 9, 2]
+    d = np.full((1, 40), np.nan, np.float32)
+    d[0, :7] = np.arange(7)
+    lab = np.arange(12, dtype=np.int32)
+    lab[8] = lab[11]
+    out, od = collapsed_rows(ids, d, lab, 10, 1)
+    assert out[0].tolist() == [11, 3, 0, 5, 9, 2, -1, -1, -1, -1] and od[0, :6].tolist() == [0, 1, 3, 4, 5, 6] and np.isnan(od[0, 6:]).all()
+    order = np.random.default_rng(6).permutation(400).astype(np.int32)[None, :]
+    out, _ = collapsed_rows(order, np.arange(400, dtype=np.float32)[None, :], np.arange(400) % 2, 120, 60)
+    assert ((out[0] % 2) == 0).sum() == ((out[0] % 2) == 1).sum() == 60
+    assert out[0].tolist() == walk(order[0].tolist(), lambda i: i % 2, 120, 60)
+
+
+def test_the_case_of_the_two_forms_reaches_every_row_and_has_no_ties():
+    """tests/test_gpu_knn_collapsed_edges.py holds knn_query_collapsed at a beam of the whole index against the flat scan.  That needs
+    a graph on which the traversal returns every row, in the scan's order: here the oracle's graph of the case (one row at a time, as
+    the GPU test builds it) is walked from the entry point, and the oracle's knn_query at k = FULL_N must return all rows for every
+    query, ascending by (distance, id) with no two distances equal."""
+    import oracle
+    from collapse_model import FULL_DIM, FULL_M, FULL_METRICS, FULL_N, full_case, reached_from_entry
+    x, q = full_case()
+    for metric in FULL_METRICS:
+        ref = oracle.OracleIndex(FULL_DIM, metric, max_edges=FULL_M, collection_size=FULL_N)
+        assert (ref.add(x) == np.arange(FULL_N)).all()
+        assert reached_from_entry(ref) == FULL_N, metric
+        ids, d = ref.knn_query(q, FULL_N)
+        assert (np.sort(ids, axis=1) == np.arange(FULL_N)).all(), metric
+        assert (d[:, 1:] > d[:, :-1]).all(), metric
+
+
 def _header():
     return (ROOT / "include" / "hnsw_mi355x.h").read_text()
 
