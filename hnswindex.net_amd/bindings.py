@@ -119,45 +119,25 @@ lib.hnsw_mi355x_knn_query_filtered.restype = ct.c_int
 lib.hnsw_mi355x_knn_query_filtered.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_int, ct.c_int, _U32, ct.c_longlong, _I, _F]
 lib.hnsw_mi355x_exact_knn_query.restype = ct.c_int
 lib.hnsw_mi355x_exact_knn_query.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_int, ct.c_int, _U32, ct.c_longlong, _I, _F]
-_EXACT_RANGE_INFO = ("device_sorted", "host_sorted", "repeated_rounds", "results")   # hnswdev_exact_range_info's out[0 .. 3]
 lib.hnsw_mi355x_exact_range_query.restype = ct.c_int
 lib.hnsw_mi355x_exact_range_query.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_int, ct.c_float, _U32, ct.c_longlong, ct.POINTER(ct.c_void_p),
                                               ct.POINTER(ct.c_void_p), _I]
-_EXACT_RANGE_GROUPED_INFO = ("calls", "device_sorted", "host_sorted", "repeated_pieces")   # hnswdev_exact_range_grouped_info's out[0 .. 3]
 lib.hnsw_mi355x_exact_range_query_grouped.restype = ct.c_int
 lib.hnsw_mi355x_exact_range_query_grouped.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_int, ct.c_float, _I, ct.c_longlong, _I, ct.c_int,
                                                       ct.POINTER(ct.c_void_p), ct.POINTER(ct.c_void_p), ct.POINTER(ct.c_int)]
-lib.hnsw_mi355x_exact_range_grouped_info.restype = ct.c_int
-lib.hnsw_mi355x_exact_range_grouped_info.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
-lib.hnsw_mi355x_exact_range_info.restype = ct.c_int
-lib.hnsw_mi355x_exact_range_info.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
-_EXACT_GROUPED_INFO = ("calls", "groups_scanned", "scan_blocks", "ids_listed")   # hnswdev_exact_grouped_info's out[0 .. 3]
 lib.hnsw_mi355x_exact_knn_query_grouped.restype = ct.c_int
 lib.hnsw_mi355x_exact_knn_query_grouped.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_int, ct.c_int, _I, ct.c_longlong, _I, ct.c_int, _I, _F]
-_EXACT_COLLAPSED_INFO = ("calls", "queries", "dropped", "evicted")   # hnswdev_exact_collapsed_info's out[0 .. 3]
 lib.hnsw_mi355x_exact_knn_query_collapsed.restype = ct.c_int
 lib.hnsw_mi355x_exact_knn_query_collapsed.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_int, ct.c_int, _I, ct.c_longlong, ct.c_int, _U32, ct.c_longlong, _I, _F]
 lib.hnsw_mi355x_knn_query_collapsed.restype = ct.c_int
 lib.hnsw_mi355x_knn_query_collapsed.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_int, ct.c_int, ct.c_int, _I, ct.c_longlong, ct.c_int, ct.c_int, _U32, ct.c_longlong,
                                                 _I, _F]
-lib.hnsw_mi355x_exact_collapsed_info.restype = ct.c_int
-lib.hnsw_mi355x_exact_collapsed_info.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
-lib.hnsw_mi355x_exact_grouped_info.restype = ct.c_int
-lib.hnsw_mi355x_exact_grouped_info.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
-_KNN_GROUPED_INFO = ("calls", "launched", "skipped", "handbacks")   # hnswdev_knn_grouped_info's out[0 .. 3]
-_KNN_TAGGED_INFO = ("calls", "masks", "launched", "skipped", "handbacks")   # hnswdev_knn_tagged_info's out[0 .. 4]
-_EXACT_TAGGED_INFO = ("calls", "masks", "scanned", "skipped", "ids_listed", "batches")   # hnswdev_exact_tagged_info's out[0 .. 5]
 _TAG_MATCH = {"any": 0, "all": 1}   # the `match` argument of the tagged calls
 lib.hnsw_mi355x_knn_query_tagged.restype = ct.c_int
 lib.hnsw_mi355x_knn_query_tagged.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_int, ct.c_int, ct.c_int, _U32, ct.c_longlong, _U32, ct.c_int, _I, _F]
 lib.hnsw_mi355x_exact_knn_query_tagged.restype = ct.c_int
 lib.hnsw_mi355x_exact_knn_query_tagged.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_int, ct.c_int, _U32, ct.c_longlong, _U32, ct.c_int, _I, _F]
-lib.hnsw_mi355x_knn_tagged_info.restype = ct.c_int
-lib.hnsw_mi355x_knn_tagged_info.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
-lib.hnsw_mi355x_exact_tagged_info.restype = ct.c_int
-lib.hnsw_mi355x_exact_tagged_info.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
 # query by stored id
-_BY_ID_INFO = ("calls", "traversed", "handbacks", "scanned", "rows_gathered", "self_skipped")   # hnswdev_by_id_info's out[0 .. 5]
 _BY_ID_CHUNK = 65536   # ids per call of Index.exact_knn_graph: bounds the gathered query set
 lib.hnsw_mi355x_get_vectors.restype = ct.c_int
 lib.hnsw_mi355x_get_vectors.argtypes = [ct.c_void_p, _I, ct.c_int, _F]
@@ -165,31 +145,17 @@ lib.hnsw_mi355x_knn_query_by_id.restype = ct.c_int
 lib.hnsw_mi355x_knn_query_by_id.argtypes = [ct.c_void_p, _I, ct.c_int, ct.c_int, ct.c_int, _I, _F]
 lib.hnsw_mi355x_exact_knn_query_by_id.restype = ct.c_int
 lib.hnsw_mi355x_exact_knn_query_by_id.argtypes = [ct.c_void_p, _I, ct.c_int, ct.c_int, _U32, ct.c_longlong, _I, _F]
-lib.hnsw_mi355x_by_id_info.restype = ct.c_int
-lib.hnsw_mi355x_by_id_info.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
 lib.hnsw_mi355x_knn_query_grouped.restype = ct.c_int
 lib.hnsw_mi355x_knn_query_grouped.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_int, ct.c_int, ct.c_int, _I, ct.c_longlong, _I, ct.c_int, _I, _F]
-_RANGE_GROUPED_INFO = ("calls", "launched", "skipped", "host_finished")   # hnswdev_range_grouped_info's out[0 .. 3]
 lib.hnsw_mi355x_range_query_grouped.restype = ct.c_int
 lib.hnsw_mi355x_range_query_grouped.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_int, ct.c_float, ct.c_int, _I, ct.c_longlong, _I, ct.c_int,
                                                 ct.POINTER(ct.c_void_p), ct.POINTER(ct.c_void_p), ct.POINTER(ct.c_int)]
-lib.hnsw_mi355x_range_grouped_info.restype = ct.c_int
-lib.hnsw_mi355x_range_grouped_info.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
-lib.hnsw_mi355x_knn_grouped_info.restype = ct.c_int
-lib.hnsw_mi355x_knn_grouped_info.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
-_RANGE_TAGGED_INFO = ("calls", "masks", "launched", "skipped", "host_finished", "long_finished")   # hnswdev_range_tagged_info's out[0 .. 5]
-_EXACT_RANGE_TAGGED_INFO = ("calls", "masks", "scanned", "skipped", "ids_listed", "batches", "device_sorted", "host_sorted",
-                            "repeated_pieces")   # hnswdev_exact_range_tagged_info's out[0 .. 8]
 lib.hnsw_mi355x_range_query_tagged.restype = ct.c_int
 lib.hnsw_mi355x_range_query_tagged.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_int, ct.c_float, ct.c_int, _U32, ct.c_longlong, _U32, ct.c_int,
                                                ct.POINTER(ct.c_void_p), ct.POINTER(ct.c_void_p), ct.POINTER(ct.c_int)]
 lib.hnsw_mi355x_exact_range_query_tagged.restype = ct.c_int
 lib.hnsw_mi355x_exact_range_query_tagged.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_int, ct.c_float, _U32, ct.c_longlong, _U32, ct.c_int,
                                                      ct.POINTER(ct.c_void_p), ct.POINTER(ct.c_void_p), ct.POINTER(ct.c_int)]
-lib.hnsw_mi355x_range_tagged_info.restype = ct.c_int
-lib.hnsw_mi355x_range_tagged_info.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
-lib.hnsw_mi355x_exact_range_tagged_info.restype = ct.c_int
-lib.hnsw_mi355x_exact_range_tagged_info.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
 
 
 class LayerInfo(ct.Structure):
@@ -201,19 +167,14 @@ class LayerInfo(ct.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
-_GRAPH_INFO_COUNTERS = ("info_layers", "component_layers", "entries", "launches")   # hnswdev_graph_info_counters' out[0 .. 3]
 lib.hnsw_mi355x_get_info.restype = ct.c_int
 lib.hnsw_mi355x_get_info.argtypes = [ct.c_void_p, ct.POINTER(LayerInfo), ct.c_int]
 lib.hnsw_mi355x_connected_component_counts.restype = ct.c_int
 lib.hnsw_mi355x_connected_component_counts.argtypes = [ct.c_void_p, _I, ct.c_int]
-lib.hnsw_mi355x_graph_info_counters.restype = ct.c_int
-lib.hnsw_mi355x_graph_info_counters.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
 lib.hnswdev_graph_info.restype = ct.c_int
 lib.hnswdev_graph_info.argtypes = [ct.c_void_p, ct.c_int, _U32, ct.c_longlong, ct.c_int, ct.POINTER(LayerInfo)]
 lib.hnswdev_graph_components.restype = ct.c_int
 lib.hnswdev_graph_components.argtypes = [ct.c_void_p, ct.c_int, _U32, ct.c_longlong, _I]
-lib.hnswdev_graph_info_counters.restype = ct.c_int
-lib.hnswdev_graph_info_counters.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
 
 
 class LayerReach(ct.Structure):
@@ -224,7 +185,6 @@ class LayerReach(ct.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
-_GRAPH_REACH_COUNTERS = ("layers", "rounds", "entries", "launches")   # hnswdev_graph_reach_counters' out[0 .. 3]
 _GRAPH_REACH_SUMMARY = ("nodes_count", "seeds", "reached", "max_hops")   # hnswdev_graph_reach_layer's out_summary[0 .. 3]
 lib.hnsw_mi355x_reachability.restype = ct.c_int
 lib.hnsw_mi355x_reachability.argtypes = [ct.c_void_p, ct.POINTER(LayerReach), ct.c_int]
@@ -232,14 +192,10 @@ lib.hnsw_mi355x_unreachable_ids.restype = ct.c_int
 lib.hnsw_mi355x_unreachable_ids.argtypes = [ct.c_void_p, ct.c_int, _I, ct.c_int]
 lib.hnsw_mi355x_hop_counts.restype = ct.c_int
 lib.hnsw_mi355x_hop_counts.argtypes = [ct.c_void_p, ct.c_int, _I, ct.c_int]
-lib.hnsw_mi355x_graph_reach_counters.restype = ct.c_int
-lib.hnsw_mi355x_graph_reach_counters.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
 lib.hnswdev_graph_reach_layer.restype = ct.c_int
 lib.hnswdev_graph_reach_layer.argtypes = [ct.c_void_p, ct.c_int, _U32, ct.c_longlong, _U32, ct.c_longlong, _U32, _I, ct.POINTER(ct.c_uint64)]
 lib.hnswdev_graph_reach.restype = ct.c_int
 lib.hnswdev_graph_reach.argtypes = [ct.c_void_p, ct.c_int, _U32, ct.c_longlong, ct.c_int, ct.POINTER(LayerReach), ct.c_int, _U32, _I]
-lib.hnswdev_graph_reach_counters.restype = ct.c_int
-lib.hnswdev_graph_reach_counters.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
 
 
 class LayerRepair(ct.Structure):
@@ -250,15 +206,10 @@ class LayerRepair(ct.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
-_GRAPH_REPAIR_COUNTERS = ("rounds", "pairs", "distances", "lists_patched")   # hnswdev_graph_repair_counters' out[0 .. 3]
 lib.hnsw_mi355x_repair_reachability.restype = ct.c_int
 lib.hnsw_mi355x_repair_reachability.argtypes = [ct.c_void_p, ct.c_int, ct.c_int, ct.POINTER(LayerRepair), ct.c_int]
-lib.hnsw_mi355x_graph_repair_counters.restype = ct.c_int
-lib.hnsw_mi355x_graph_repair_counters.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
 lib.hnswdev_graph_repair_propose.restype = ct.c_int
 lib.hnswdev_graph_repair_propose.argtypes = [ct.c_void_p, ct.c_int, _U32, ct.c_longlong, _U32, ct.c_longlong, ct.c_int, ct.c_int, _I, _I, _I, _I, ct.c_int]
-lib.hnswdev_graph_repair_counters.restype = ct.c_int
-lib.hnswdev_graph_repair_counters.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
 lib.hnsw_mi355x_range_query_filtered.restype = ct.c_int
 lib.hnsw_mi355x_range_query_filtered.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_int, ct.c_float, _U32, ct.c_longlong, ct.POINTER(ct.c_void_p),
                                                  ct.POINTER(ct.c_void_p), ct.POINTER(ct.c_int)]
@@ -342,54 +293,32 @@ lib.hnswdev_exact_range_results.restype = ct.c_int
 lib.hnswdev_exact_range_results.argtypes = [ct.c_void_p, _I, _F]
 lib.hnswdev_exact_range_grouped.restype = ct.c_int
 lib.hnswdev_exact_range_grouped.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_longlong, ct.c_float, _I, ct.c_longlong, _I, ct.c_int, _I]
-lib.hnswdev_exact_range_grouped_info.restype = ct.c_int
-lib.hnswdev_exact_range_grouped_info.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
-lib.hnswdev_exact_range_info.restype = ct.c_int
-lib.hnswdev_exact_range_info.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
 lib.hnswdev_exact_knn_grouped.restype = ct.c_int
 lib.hnswdev_exact_knn_grouped.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_longlong, ct.c_int, _I, ct.c_longlong, _I, ct.c_int, _I, _F]
 lib.hnswdev_exact_knn_collapsed.restype = ct.c_int
 lib.hnswdev_exact_knn_collapsed.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_longlong, ct.c_int, _I, ct.c_longlong, ct.c_int, _U32, ct.c_longlong, _I, _F]
-lib.hnswdev_exact_collapsed_info.restype = ct.c_int
-lib.hnswdev_exact_collapsed_info.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
-lib.hnswdev_exact_grouped_info.restype = ct.c_int
-lib.hnswdev_exact_grouped_info.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
 lib.hnswdev_exact_grouped_list_ms.restype = ct.c_int
 lib.hnswdev_exact_grouped_list_ms.argtypes = [ct.c_void_p, ct.POINTER(ct.c_double)]
 lib.hnswdev_knn_search_tagged.restype = ct.c_int
 lib.hnswdev_knn_search_tagged.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int, _U32, ct.c_longlong, _U32, ct.c_int, _I, _F, _I]
-lib.hnswdev_knn_tagged_info.restype = ct.c_int
-lib.hnswdev_knn_tagged_info.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
 lib.hnswdev_exact_knn_tagged.restype = ct.c_int
 lib.hnswdev_exact_knn_tagged.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_longlong, ct.c_int, _U32, ct.c_longlong, _U32, ct.c_int, _I, _F]
-lib.hnswdev_exact_tagged_info.restype = ct.c_int
-lib.hnswdev_exact_tagged_info.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
 lib.hnswdev_gather_rows.restype = ct.c_int
 lib.hnswdev_gather_rows.argtypes = [ct.c_void_p, _I, ct.c_int, _F]
 lib.hnswdev_knn_search_by_id.restype = ct.c_int
 lib.hnswdev_knn_search_by_id.argtypes = [ct.c_void_p, _I, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int, _I, _F, _I]
 lib.hnswdev_exact_knn_by_id.restype = ct.c_int
 lib.hnswdev_exact_knn_by_id.argtypes = [ct.c_void_p, _I, ct.c_int, ct.c_longlong, ct.c_int, _U32, ct.c_longlong, _I, _F]
-lib.hnswdev_by_id_info.restype = ct.c_int
-lib.hnswdev_by_id_info.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
 lib.hnswdev_tag_list_ms.restype = ct.c_int
 lib.hnswdev_tag_list_ms.argtypes = [ct.c_void_p, ct.POINTER(ct.c_double)]
 lib.hnswdev_knn_search_grouped.restype = ct.c_int
 lib.hnswdev_knn_search_grouped.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int, _I, ct.c_longlong, _I, ct.c_int, _I, _F, _I]
 lib.hnswdev_range_search_grouped.restype = ct.c_int
 lib.hnswdev_range_search_grouped.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_int, ct.c_float, ct.c_int, _I, ct.c_longlong, _I, ct.c_int, _I, _I]
-lib.hnswdev_range_grouped_info.restype = ct.c_int
-lib.hnswdev_range_grouped_info.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
 lib.hnswdev_range_search_tagged.restype = ct.c_int
 lib.hnswdev_range_search_tagged.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_int, ct.c_float, ct.c_int, _U32, ct.c_longlong, _U32, ct.c_int, _I, _I]
-lib.hnswdev_range_tagged_info.restype = ct.c_int
-lib.hnswdev_range_tagged_info.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
 lib.hnswdev_exact_range_tagged.restype = ct.c_int
 lib.hnswdev_exact_range_tagged.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_longlong, ct.c_float, _U32, ct.c_longlong, _U32, ct.c_int, _I]
-lib.hnswdev_exact_range_tagged_info.restype = ct.c_int
-lib.hnswdev_exact_range_tagged_info.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
-lib.hnswdev_knn_grouped_info.restype = ct.c_int
-lib.hnswdev_knn_grouped_info.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
 lib.hnswdev_range_results.restype = ct.c_int
 lib.hnswdev_range_results.argtypes = [ct.c_void_p, _I, _F]
 lib.hnswdev_knn_search_at_layer.restype = ct.c_int
@@ -410,7 +339,55 @@ lib.hnswdev_step_submit.argtypes = [ct.c_void_p, ct.c_int, ct.c_int]
 lib.hnswdev_step_wait.argtypes = [ct.c_void_p, ct.c_int]
 lib.hnswdev_test_sqrt_rn.argtypes = [ct.c_int, ct.POINTER(ct.c_double), ct.POINTER(ct.c_double), ct.c_int]
 
-METRICS = {"sq_euclid": 0, "cosine": 1, "ucosine": 2, "sq_euclid_i8": 3, "sq_euclid_f16": 4, "ucosine_f16": 5}
+# ---- (C) the counter blocks ----------------------------------------------------------------
+# One row per block, in the order and with the slot names of csrc/counter_blocks.h (tests/test_counter_blocks.py holds the two
+# tables together): name -> (slot names, docstring).  hnsw_mi355x_<name> and hnswdev_<name> fill an array of one uint64 per slot;
+# Index.<name>() and DeviceBackend.<name>() return it as a dict keyed by the slot names (_install_counter_methods, below the
+# classes).  A new block is one row here and one there.
+COUNTER_BLOCKS = {
+    "knn_grouped_info": (("calls", "launched", "skipped", "handbacks"),
+        """Counters of knn_query_grouped's device launches since reset_stats (hnsw_mi355x_knn_grouped_info): calls that reached a
+        context, queries launched, queries skipped because their group holds no graph id, queries handed back to the host."""),
+    "knn_tagged_info": (("calls", "masks", "launched", "skipped", "handbacks"),
+        """Counters of knn_query_tagged's device launches since reset_stats (hnsw_mi355x_knn_tagged_info): calls that reached a
+        context, their distinct masks, queries launched, queries skipped because their mask has no candidate, queries handed back."""),
+    "by_id_info": (("calls", "traversed", "handbacks", "scanned", "rows_gathered", "self_skipped"),
+        """Counters of the by-id calls since reset_stats (hnsw_mi355x_by_id_info): calls that reached a device, queries traversed on
+        the device, of those handed back to the host, queries scanned, rows gathered, pairs the scan skipped as the query's own."""),
+    "range_grouped_info": (("calls", "launched", "skipped", "host_finished"),
+        """Counters of range_query_grouped since reset_stats (hnsw_mi355x_range_grouped_info): calls that reached the context, queries
+        launched, queries skipped because their group holds no graph id, lists the device left to the host."""),
+    "range_tagged_info": (("calls", "masks", "launched", "skipped", "host_finished", "long_finished"),
+        """Counters of range_query_tagged since reset_stats (hnsw_mi355x_range_tagged_info): calls that reached the context, their
+        distinct masks, queries launched, queries skipped because their mask matches no graph id, lists the device left to the host,
+        closures beyond the device's table that it finished all the same."""),
+    "exact_range_info": (("device_sorted", "host_sorted", "repeated_rounds", "results"),
+        """Counters of exact_range_query since reset_stats (hnsw_mi355x_exact_range_info)."""),
+    "exact_grouped_info": (("calls", "groups_scanned", "scan_blocks", "ids_listed"),
+        """Counters of exact_knn_query_grouped since reset_stats (hnsw_mi355x_exact_grouped_info)."""),
+    "exact_collapsed_info": (("calls", "queries", "dropped", "evicted"),
+        """Counters of exact_knn_query_collapsed since reset_stats (hnsw_mi355x_exact_collapsed_info): calls that scanned, queries
+        scanned, keys dropped by the cap at a list, list entries evicted by a nearer key of their label."""),
+    "exact_tagged_info": (("calls", "masks", "scanned", "skipped", "ids_listed", "batches"),
+        """Counters of exact_knn_query_tagged since reset_stats (hnsw_mi355x_exact_tagged_info): calls, their distinct masks, queries
+        scanned, queries skipped because their mask has no candidate, ids written into candidate lists, batches of masks."""),
+    "exact_range_grouped_info": (("calls", "device_sorted", "host_sorted", "repeated_pieces"),
+        """Counters of exact_range_query_grouped since reset_stats (hnsw_mi355x_exact_range_grouped_info)."""),
+    "exact_range_tagged_info": (("calls", "masks", "scanned", "skipped", "ids_listed", "batches", "device_sorted", "host_sorted", "repeated_pieces"),
+        """Counters of exact_range_query_tagged since reset_stats (hnsw_mi355x_exact_range_tagged_info)."""),
+    "graph_info_counters": (("info_layers", "component_layers", "entries", "launches"),
+        """Counters of get_info / connected_component_counts since reset_stats (hnsw_mi355x_graph_info_counters)."""),
+    "graph_reach_counters": (("layers", "rounds", "entries", "launches"),
+        """Counters of reachability / unreachable_ids / hop_counts since reset_stats (hnsw_mi355x_graph_reach_counters)."""),
+    "graph_repair_counters": (("rounds", "pairs", "distances", "lists_patched"),
+        """Counters of repair_reachability since reset_stats (hnsw_mi355x_graph_repair_counters)."""),
+}
+for _name in COUNTER_BLOCKS:
+    for _sym in ("hnsw_mi355x_" + _name, "hnswdev_" + _name):
+        getattr(lib, _sym).restype = ct.c_int
+        getattr(lib, _sym).argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
+
+METRICS = {"sq_euclid": 0,"cosine": 1, "ucosine": 2, "sq_euclid_i8": 3, "sq_euclid_f16": 4, "ucosine_f16": 5}
 
 
 class Options(ct.Structure):
@@ -863,21 +840,6 @@ class Index:
             raise RuntimeError(last_error())
         return ids, dists
 
-    def exact_collapsed_info(self) -> dict:
-        """Counters of exact_knn_query_collapsed since reset_stats (hnsw_mi355x_exact_collapsed_info): calls that scanned, queries
-        scanned, keys dropped by the cap at a list, list entries evicted by a nearer key of their label."""
-        out = (ct.c_uint64 * 4)()
-        if self._h:
-            lib.hnsw_mi355x_exact_collapsed_info(self._h, out)
-        return dict(zip(_EXACT_COLLAPSED_INFO, (int(v) for v in out)))
-
-    def exact_grouped_info(self) -> dict:
-        """Counters of exact_knn_query_grouped since reset_stats (hnsw_mi355x_exact_grouped_info)."""
-        out = (ct.c_uint64 * 4)()
-        if self._h:
-            lib.hnsw_mi355x_exact_grouped_info(self._h, out)
-        return dict(zip(_EXACT_GROUPED_INFO, (int(v) for v in out)))
-
     def knn_query_grouped(self, queries: npt.ArrayLike, k: int, row_group, query_group, n_groups=None,
                           layer: int = 0) -> Tuple[npt.NDArray[np.int32], npt.NDArray[np.float32]]:
         """knn_query with a group filter per query, every group in one device traversal (hnsw_mi355x_knn_query_grouped):
@@ -895,14 +857,6 @@ class Index:
         if status < 0:
             raise RuntimeError(last_error())
         return ids, dists
-
-    def knn_grouped_info(self) -> dict:
-        """Counters of knn_query_grouped's device launches since reset_stats (hnsw_mi355x_knn_grouped_info): calls that reached a
-        context, queries launched, queries skipped because their group holds no graph id, queries handed back to the host."""
-        out = (ct.c_uint64 * 4)()
-        if self._h:
-            lib.hnsw_mi355x_knn_grouped_info(self._h, out)
-        return dict(zip(_KNN_GROUPED_INFO, (int(v) for v in out)))
 
     def knn_query_tagged(self, queries: npt.ArrayLike, k: int, row_tags, query_tags, match: str = "any",
                          layer: int = 0) -> Tuple[npt.NDArray[np.int32], npt.NDArray[np.float32]]:
@@ -923,14 +877,6 @@ class Index:
             raise RuntimeError(last_error())
         return ids, dists
 
-    def knn_tagged_info(self) -> dict:
-        """Counters of knn_query_tagged's device launches since reset_stats (hnsw_mi355x_knn_tagged_info): calls that reached a
-        context, their distinct masks, queries launched, queries skipped because their mask has no candidate, queries handed back."""
-        out = (ct.c_uint64 * 5)()
-        if self._h:
-            lib.hnsw_mi355x_knn_tagged_info(self._h, out)
-        return dict(zip(_KNN_TAGGED_INFO, (int(v) for v in out)))
-
     def exact_knn_query_tagged(self, queries: npt.ArrayLike, k: int, row_tags, query_tags,
                                match: str = "any") -> Tuple[npt.NDArray[np.int32], npt.NDArray[np.float32]]:
         """exact_knn_query with knn_query_tagged's tag mask per query (hnsw_mi355x_exact_knn_query_tagged): per distinct mask m the rows
@@ -945,14 +891,6 @@ class Index:
         if status < 0:
             raise RuntimeError(last_error())
         return ids, dists
-
-    def exact_tagged_info(self) -> dict:
-        """Counters of exact_knn_query_tagged since reset_stats (hnsw_mi355x_exact_tagged_info): calls, their distinct masks, queries
-        scanned, queries skipped because their mask has no candidate, ids written into candidate lists, batches of masks."""
-        out = (ct.c_uint64 * 6)()
-        if self._h:
-            lib.hnsw_mi355x_exact_tagged_info(self._h, out)
-        return dict(zip(_EXACT_TAGGED_INFO, (int(v) for v in out)))
 
     # ---- query by stored id (DESIGN.md 3.27) ----
     def _by_id_list(self, ids, who: str) -> npt.NDArray[np.int32]:
@@ -1013,14 +951,6 @@ class Index:
             out_ids[lo:lo + _BY_ID_CHUNK], dists[lo:lo + _BY_ID_CHUNK] = self.exact_knn_query_by_id(a[lo:lo + _BY_ID_CHUNK], k)
         return out_ids, dists
 
-    def by_id_info(self) -> dict:
-        """Counters of the by-id calls since reset_stats (hnsw_mi355x_by_id_info): calls that reached a device, queries traversed on
-        the device, of those handed back to the host, queries scanned, rows gathered, pairs the scan skipped as the query's own."""
-        out = (ct.c_uint64 * 6)()
-        if self._h:
-            lib.hnsw_mi355x_by_id_info(self._h, out)
-        return dict(zip(_BY_ID_INFO, (int(v) for v in out)))
-
     def exact_range_query(self, queries: npt.ArrayLike, radius: float,
                           allowed=None) -> Tuple[List[npt.NDArray[np.int32]], List[npt.NDArray[np.float32]]]:
         """Per query every live (and, with `allowed`, allowed) id whose distance is <= radius, ascending by (distance, id), from
@@ -1078,20 +1008,6 @@ class Index:
         finally:
             lib.hnsw_free_results(ids_pp, dists_pp, n)
         return ids, dists
-
-    def exact_range_grouped_info(self) -> dict:
-        """Counters of exact_range_query_grouped since reset_stats (hnsw_mi355x_exact_range_grouped_info)."""
-        out = (ct.c_uint64 * 4)()
-        if self._h:
-            lib.hnsw_mi355x_exact_range_grouped_info(self._h, out)
-        return dict(zip(_EXACT_RANGE_GROUPED_INFO, (int(v) for v in out)))
-
-    def exact_range_info(self) -> dict:
-        """Counters of exact_range_query since reset_stats (hnsw_mi355x_exact_range_info)."""
-        out = (ct.c_uint64 * 4)()
-        if self._h:
-            lib.hnsw_mi355x_exact_range_info(self._h, out)
-        return dict(zip(_EXACT_RANGE_INFO, (int(v) for v in out)))
 
     def range_query(self, queries: npt.ArrayLike, radius: float,
                     allowed=None, layer: int = 0) -> Tuple[List[npt.NDArray[np.int32]], List[npt.NDArray[np.float32]]]:
@@ -1159,14 +1075,6 @@ class Index:
             lib.hnsw_free_results(ids_pp, dists_pp, n)
         return ids, dists
 
-    def range_grouped_info(self) -> dict:
-        """Counters of range_query_grouped since reset_stats (hnsw_mi355x_range_grouped_info): calls that reached the context, queries
-        launched, queries skipped because their group holds no graph id, lists the device left to the host."""
-        out = (ct.c_uint64 * 4)()
-        if self._h:
-            lib.hnsw_mi355x_range_grouped_info(self._h, out)
-        return dict(zip(_RANGE_GROUPED_INFO, (int(v) for v in out)))
-
     def range_query_tagged(self, queries: npt.ArrayLike, radius: float, row_tags, query_tags, match: str = "any",
                            layer: int = 0) -> Tuple[List[npt.NDArray[np.int32]], List[npt.NDArray[np.float32]]]:
         """range_query with a tag mask per query, every mask in one device traversal (hnsw_mi355x_range_query_tagged): row_tags /
@@ -1185,15 +1093,6 @@ class Index:
             raise RuntimeError(last_error())
         return _take_lists(ids_pp, dists_pp, counts, n)
 
-    def range_tagged_info(self) -> dict:
-        """Counters of range_query_tagged since reset_stats (hnsw_mi355x_range_tagged_info): calls that reached the context, their
-        distinct masks, queries launched, queries skipped because their mask matches no graph id, lists the device left to the host,
-        closures beyond the device's table that it finished all the same."""
-        out = (ct.c_uint64 * 6)()
-        if self._h:
-            lib.hnsw_mi355x_range_tagged_info(self._h, out)
-        return dict(zip(_RANGE_TAGGED_INFO, (int(v) for v in out)))
-
     def exact_range_query_tagged(self, queries: npt.ArrayLike, radius: float, row_tags, query_tags,
                                  match: str = "any") -> Tuple[List[npt.NDArray[np.int32]], List[npt.NDArray[np.float32]]]:
         """exact_range_query with a tag mask per query (hnsw_mi355x_exact_range_query_tagged): row_tags / query_tags / match as for
@@ -1210,13 +1109,6 @@ class Index:
         if status < 0:
             raise RuntimeError(last_error())
         return _take_lists(ids_pp, dists_pp, counts, n)
-
-    def exact_range_tagged_info(self) -> dict:
-        """Counters of exact_range_query_tagged since reset_stats (hnsw_mi355x_exact_range_tagged_info)."""
-        out = (ct.c_uint64 * 9)()
-        if self._h:
-            lib.hnsw_mi355x_exact_range_tagged_info(self._h, out)
-        return dict(zip(_EXACT_RANGE_TAGGED_INFO, (int(v) for v in out)))
 
     # ---- measurement aid: query set resident in HBM across calls ----
     def set_resident_queries(self, queries: npt.ArrayLike):
@@ -1331,13 +1223,6 @@ class Index:
                 return out[:n].copy()
             out = np.zeros(n, dtype=np.int32)
 
-    def graph_info_counters(self) -> dict:
-        """Counters of get_info / connected_component_counts since reset_stats (hnsw_mi355x_graph_info_counters)."""
-        out = (ct.c_uint64 * 4)()
-        if self._h:
-            lib.hnsw_mi355x_graph_info_counters(self._h, out)
-        return dict(zip(_GRAPH_INFO_COUNTERS, (int(v) for v in out)))
-
     # ---- reachability from the entry point over out-edges (DESIGN.md 3.19) ----
     def reachability(self) -> List[dict]:
         """One dict per layer 0 .. top with the fields of hnsw_mi355x_layer_reach: the layer's members, the seeds that arrive from the
@@ -1377,13 +1262,6 @@ class Index:
             raise RuntimeError(last_error())
         return out[:n].copy()
 
-    def graph_reach_counters(self) -> dict:
-        """Counters of reachability / unreachable_ids / hop_counts since reset_stats (hnsw_mi355x_graph_reach_counters)."""
-        out = (ct.c_uint64 * 4)()
-        if self._h:
-            lib.hnsw_mi355x_graph_reach_counters(self._h, out)
-        return dict(zip(_GRAPH_REACH_COUNTERS, (int(v) for v in out)))
-
     # ---- repair of reachability (DESIGN.md 3.21) ----
     def repair_reachability(self, cands: int = 8, max_rounds: int = 8) -> List[dict]:
         """Links the items that unreachable_ids() reports into the lists of their nearest reached members, on the device, layer by
@@ -1398,13 +1276,6 @@ class Index:
         if n < 0:
             raise RuntimeError(last_error())
         return [out[i].as_dict() for i in range(min(n, cap))]
-
-    def graph_repair_counters(self) -> dict:
-        """Counters of repair_reachability since reset_stats (hnsw_mi355x_graph_repair_counters)."""
-        out = (ct.c_uint64 * 4)()
-        if self._h:
-            lib.hnsw_mi355x_graph_repair_counters(self._h, out)
-        return dict(zip(_GRAPH_REPAIR_COUNTERS, (int(v) for v in out)))
 
     # ---- HNSWIndex.Serialize / Deserialize (src/HNSWIndex/HNSWIndex.cs:210-229) ----
     def serialize(self, path) -> None:
@@ -1529,12 +1400,6 @@ class DeviceBackend:
                                                 out_ids.ctypes.data_as(_I), d.ctypes.data_as(_F)))
         return out_ids, d
 
-    def by_id_info(self) -> dict:
-        """Counters of the by-id calls since reset_stats (hnswdev_by_id_info)."""
-        out = (ct.c_uint64 * 6)()
-        self._check(lib.hnswdev_by_id_info(self._ctx, out))
-        return dict(zip(_BY_ID_INFO, (int(v) for v in out)))
-
     def set_queries(self, queries):
         """Uploads the query set of a batch of searches once; records name queries by row index."""
         q = _as_2d_f32(queries, self.dim)
@@ -1615,12 +1480,6 @@ class DeviceBackend:
         self._check(lib.hnswdev_graph_components(self._ctx, int(layer), wp, nbits, ct.byref(out)))
         return int(out.value)
 
-    def graph_info_counters(self) -> dict:
-        """Counters of graph_info / graph_components since reset_stats (hnswdev_graph_info_counters)."""
-        out = (ct.c_uint64 * 4)()
-        self._check(lib.hnswdev_graph_info_counters(self._ctx, out))
-        return dict(zip(_GRAPH_INFO_COUNTERS, (int(v) for v in out)))
-
     def _reach_out(self):
         """(n, reached words, hops) for a reachability call on the committed graph."""
         n = int(self._graph_n)
@@ -1656,12 +1515,6 @@ class DeviceBackend:
                 return [out[i].as_dict() for i in range(int(min_layer), got)], self._reached_mask(words, n), hops
             cap = got
 
-    def graph_reach_counters(self) -> dict:
-        """Counters of graph_reach_layer / graph_reach since reset_stats (hnswdev_graph_reach_counters)."""
-        out = (ct.c_uint64 * 4)()
-        self._check(lib.hnswdev_graph_reach_counters(self._ctx, out))
-        return dict(zip(_GRAPH_REACH_COUNTERS, (int(v) for v in out)))
-
     def graph_repair_propose(self, layer: int, seeds, live=None, cands: int = 8, max_edges: Optional[int] = None):
         """hnswdev_graph_repair_propose: steps 1 - 3 of one repair round on one layer of the committed graph (read, not changed), from
         `seeds` (a bool mask or an id list, as `live`).  (U[n_u] ascending, cands[n_u, cands], codes[n_u, cands]).  max_edges:
@@ -1680,12 +1533,6 @@ class DeviceBackend:
                                                      cd.ctypes.data_as(_I), code.ctypes.data_as(_I), n))
         k = int(n_u.value)
         return ids[:k].copy(), cd[:k].copy(), code[:k].copy()
-
-    def graph_repair_counters(self) -> dict:
-        """Counters of graph_repair_propose since reset_stats (hnswdev_graph_repair_counters)."""
-        out = (ct.c_uint64 * 4)()
-        self._check(lib.hnswdev_graph_repair_counters(self._ctx, out))
-        return dict(zip(_GRAPH_REPAIR_COUNTERS, (int(v) for v in out)))
 
     def knn_search(self, queries, entry_point: int, k_beam: int, k_out: int, allowed=None, layer: int = 0):
         """allowed: as for Index.knn_query (hnswdev_knn_search_filtered); None runs hnswdev_knn_search.  layer != 0:
@@ -1725,12 +1572,6 @@ class DeviceBackend:
                                                    d.ctypes.data_as(_F), flags.ctypes.data_as(_I)))
         return ids, d, flags
 
-    def knn_grouped_info(self) -> dict:
-        """Counters of knn_search_grouped since reset_stats (hnswdev_knn_grouped_info)."""
-        out = (ct.c_uint64 * 4)()
-        self._check(lib.hnswdev_knn_grouped_info(self._ctx, out))
-        return dict(zip(_KNN_GROUPED_INFO, (int(v) for v in out)))
-
     def knn_search_tagged(self, queries, entry_point: int, k_beam: int, k_out: int, row_tags, query_tags, match: str = "any", layer: int = 0):
         """hnswdev_knn_search_tagged: knn_search with a tag mask per query -- query i is answered from the graph ids j whose word
         row_tags[j] matches query_tags[i] (Index.knn_query_tagged's rule).  (ids, dists, flags)."""
@@ -1745,12 +1586,6 @@ class DeviceBackend:
                                                   d.ctypes.data_as(_F), flags.ctypes.data_as(_I)))
         return ids, d, flags
 
-    def knn_tagged_info(self) -> dict:
-        """Counters of knn_search_tagged since reset_stats (hnswdev_knn_tagged_info)."""
-        out = (ct.c_uint64 * 5)()
-        self._check(lib.hnswdev_knn_tagged_info(self._ctx, out))
-        return dict(zip(_KNN_TAGGED_INFO, (int(v) for v in out)))
-
     def exact_knn_tagged(self, queries, k: int, row_tags, query_tags, match: str = "any", n_rows=None):
         """hnswdev_exact_knn_tagged: exact_knn with a tag mask per query -- query i is answered from the uploaded rows j of [0, n_rows)
         (None: all) whose word row_tags[j] matches query_tags[i].  queries None: the resident set (len(query_tags) of its rows)."""
@@ -1763,12 +1598,6 @@ class DeviceBackend:
                                                  int(k), rt.ctypes.data_as(_U32), rt.shape[0], qt.ctypes.data_as(_U32), mode, ids.ctypes.data_as(_I),
                                                  d.ctypes.data_as(_F)))
         return ids, d
-
-    def exact_tagged_info(self) -> dict:
-        """Counters of exact_knn_tagged since reset_stats (hnswdev_exact_tagged_info)."""
-        out = (ct.c_uint64 * 6)()
-        self._check(lib.hnswdev_exact_tagged_info(self._ctx, out))
-        return dict(zip(_EXACT_TAGGED_INFO, (int(v) for v in out)))
 
     def tag_list_ms(self) -> float:
         """HIP-event milliseconds of the tagged calls' list-building kernels while profiling was on, since reset_stats."""
@@ -1817,18 +1646,6 @@ class DeviceBackend:
                                                     rg.ctypes.data_as(_I), rg.shape[0], int(per_group), wp, nbits, ids.ctypes.data_as(_I), d.ctypes.data_as(_F)))
         return ids, d
 
-    def exact_collapsed_info(self) -> dict:
-        """Counters of exact_knn_collapsed since reset_stats (hnswdev_exact_collapsed_info)."""
-        out = (ct.c_uint64 * 4)()
-        self._check(lib.hnswdev_exact_collapsed_info(self._ctx, out))
-        return dict(zip(_EXACT_COLLAPSED_INFO, (int(v) for v in out)))
-
-    def exact_grouped_info(self) -> dict:
-        """Counters of exact_knn_grouped since reset_stats (hnswdev_exact_grouped_info)."""
-        out = (ct.c_uint64 * 4)()
-        self._check(lib.hnswdev_exact_grouped_info(self._ctx, out))
-        return dict(zip(_EXACT_GROUPED_INFO, (int(v) for v in out)))
-
     def exact_grouped_list_ms(self) -> float:
         """HIP-event milliseconds of exact_knn_grouped's list-building kernels while profiling was on, since reset_stats."""
         out = ct.c_double(0.0)
@@ -1869,18 +1686,6 @@ class DeviceBackend:
         self._check(lib.hnswdev_exact_range_results(self._ctx, ids.ctypes.data_as(_I), d.ctypes.data_as(_F)))
         cuts = np.cumsum(counts, dtype=np.int64)[:-1]
         return np.split(ids[:total], cuts), np.split(d[:total], cuts)
-
-    def exact_range_grouped_info(self) -> dict:
-        """Counters of exact_range_grouped since reset_stats (hnswdev_exact_range_grouped_info)."""
-        out = (ct.c_uint64 * 4)()
-        self._check(lib.hnswdev_exact_range_grouped_info(self._ctx, out))
-        return dict(zip(_EXACT_RANGE_GROUPED_INFO, (int(v) for v in out)))
-
-    def exact_range_info(self) -> dict:
-        """Counters of exact_range since reset_stats (hnswdev_exact_range_info)."""
-        out = (ct.c_uint64 * 4)()
-        self._check(lib.hnswdev_exact_range_info(self._ctx, out))
-        return dict(zip(_EXACT_RANGE_INFO, (int(v) for v in out)))
 
     def multilayer_search(self, queries, entry_point: int, k: int, max_layer=None, min_layer: int = 0, layers_cap=None):
         """hnswdev_multilayer_search: (ids, dists, flags), ids / dists of shape [nq, nlayers, k - 1] as Index.multilayer_knn_query;
@@ -1942,12 +1747,6 @@ class DeviceBackend:
         cuts = np.cumsum(counts)[:-1]
         return np.split(ids[:total], cuts), np.split(d[:total], cuts), flags
 
-    def range_grouped_info(self) -> dict:
-        """Counters of range_search_grouped since reset_stats (hnswdev_range_grouped_info)."""
-        out = (ct.c_uint64 * 4)()
-        self._check(lib.hnswdev_range_grouped_info(self._ctx, out))
-        return dict(zip(_RANGE_GROUPED_INFO, (int(v) for v in out)))
-
     def range_search_tagged(self, queries, entry_point: int, radius: float, row_tags, query_tags, match: str = "any", layer: int = 0):
         """hnswdev_range_search_tagged: range_search with a tag mask per query -- (ids, dists, flags) as range_search returns them,
         query i filtered by the ids whose word row_tags[id] matches query_tags[i]."""
@@ -1964,12 +1763,6 @@ class DeviceBackend:
         self._check(lib.hnswdev_range_results(self._ctx, ids.ctypes.data_as(_I), d.ctypes.data_as(_F)))
         cuts = np.cumsum(counts)[:-1]
         return np.split(ids[:total], cuts), np.split(d[:total], cuts), flags
-
-    def range_tagged_info(self) -> dict:
-        """Counters of range_search_tagged since reset_stats (hnswdev_range_tagged_info)."""
-        out = (ct.c_uint64 * 6)()
-        self._check(lib.hnswdev_range_tagged_info(self._ctx, out))
-        return dict(zip(_RANGE_TAGGED_INFO, (int(v) for v in out)))
 
     def exact_range_tagged(self, queries, radius: float, row_tags, query_tags, match: str = "any", n_rows=None):
         """hnswdev_exact_range_tagged: exact_range with a tag mask per query -- (list of ids, list of dists) in the caller's query
@@ -1989,12 +1782,6 @@ class DeviceBackend:
         cuts = np.cumsum(counts, dtype=np.int64)[:-1]
         return np.split(ids[:total], cuts), np.split(d[:total], cuts)
 
-    def exact_range_tagged_info(self) -> dict:
-        """Counters of exact_range_tagged since reset_stats (hnswdev_exact_range_tagged_info)."""
-        out = (ct.c_uint64 * 9)()
-        self._check(lib.hnswdev_exact_range_tagged_info(self._ctx, out))
-        return dict(zip(_EXACT_RANGE_TAGGED_INFO, (int(v) for v in out)))
-
     def set_profiling(self, on: bool):
         self._check(lib.hnswdev_set_profiling(self._ctx, int(on)))
 
@@ -2005,6 +1792,31 @@ class DeviceBackend:
 
     def reset_stats(self):
         self._check(lib.hnswdev_reset_stats(self._ctx))
+
+
+def _install_counter_methods(name, slots, doc):
+    """Index.<name>() and DeviceBackend.<name>() of one row of COUNTER_BLOCKS: the block as a dict keyed by its slot names.
+    Index: all zero while there is no native handle, and it never raises.  DeviceBackend: a failure raises, as every call of it."""
+    def index_block(self) -> dict:
+        out = (ct.c_uint64 * len(slots))()
+        if self._h:
+            getattr(lib, "hnsw_mi355x_" + name)(self._h, out)
+        return dict(zip(slots, (int(v) for v in out)))
+
+    def backend_block(self) -> dict:
+        out = (ct.c_uint64 * len(slots))()
+        self._check(getattr(lib, "hnswdev_" + name)(self._ctx, out))
+        return dict(zip(slots, (int(v) for v in out)))
+
+    index_block.__doc__ = doc
+    backend_block.__doc__ = f"This context's counters of that block since reset_stats (hnswdev_{name}): the slots of Index.{name}."
+    for cls, fn in ((Index, index_block), (DeviceBackend, backend_block)):
+        fn.__name__, fn.__qualname__ = name, f"{cls.__name__}.{name}"
+        setattr(cls, name, fn)
+
+
+for _name, (_slots, _doc) in COUNTER_BLOCKS.items():
+    _install_counter_methods(_name, _slots, _doc)
 
 
 def device_sqrt_rn(x, device=0):

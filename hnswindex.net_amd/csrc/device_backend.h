@@ -15,6 +15,7 @@
 #include <thread>
 
 #include "../../include/hnsw_mi355x.h"
+#include "counter_blocks.h"
 #include "dev_buf.h"
 
 namespace hnsw {
@@ -282,8 +283,6 @@ public:
     // (out_flag 0); the others are launched longest traversal first (ascending by their group's id count).  out_flag as search_filtered.
     bool search_grouped(int nq, int entry, int entry_layer, int k, int k_out, const int *row_group, long long n_row_group, const int *query_group,
                         int n_groups, int *out_ids, float *out_d, int *out_flag, int search_layer = 0);
-    // calls, queries launched, queries padded for an empty group, queries handed back -- of search_grouped on this context
-    void knn_grouped_info(uint64_t out[4]) const { for (int i = 0; i < 4; ++i) out[i] = kg_info_[i]; }
     // search_grouped with a tag mask per query (graph_search_tagged_kernel): resident query i is answered from the
     // graph ids j < n_row_tags whose word row_tags[j] matches query_tags[i] under `match` (0 any, 1 all) -- byte for byte what
     // search_filtered returns for it with those ids as the allow-set.  The words, the masks and the order table are uploaded to this
@@ -293,8 +292,6 @@ public:
     // anything runs.  out_flag as search_filtered.
     bool search_tagged(int nq, int entry, int entry_layer, int k, int k_out, const uint32_t *row_tags, long long n_row_tags, const uint32_t *query_tags,
                        int match, int *out_ids, float *out_d, int *out_flag, int search_layer = 0);
-    // calls, distinct masks, queries launched, queries padded for a mask without a candidate, queries handed back -- of search_tagged on this context
-    void knn_tagged_info(uint64_t out[5]) const { for (int i = 0; i < 5; ++i) out[i] = kt_info_[i]; }
     // MultiLayerKnnQuery's chains (graph_multilayer_kernel): resident query i searched with beam k (>= 2) on every layer from
     // first_layer (<= entry_layer) down to min_layer, each step entering at the nearest result of the one before.
     // out_ids / out_d: [nq][first_layer + 1][k - 1], padded; out_flag[i] = 1: handed back whole.
@@ -417,15 +414,9 @@ public:
     // the filtered call's.  The per-id array goes to s_allow_ / s_glabel_ / s_ttags_ -- the part that covers graph ids -- unless
     // f.resident says s_ttags_ holds it already.
     bool range_batch(const SearchJob *jobs, int njobs, float range, RangeResults *res, const RangeFilter &f);
-    // tagged range calls that reached this context, distinct masks, queries launched, queries skipped for a mask without a graph
-    // candidate, lists the device left to the host (closures and hand-backs), closures above kRangeSortMax entries that the device finished
-    void range_tagged_info(uint64_t out[6]) const { for (int i = 0; i < 6; ++i) out[i] = rt_info_[i]; }
     // The candidates of every distinct mask among ids [0, n) of row_tags, counted on the device (tag_count_kernel): cnt[d] for
     // masks[d].  The words stay in s_ttags_ for a range_batch that follows (RangeFilter::resident).  n <= 0: every count 0, no launch.
     bool tag_candidates(const uint32_t *row_tags, long long n, const std::vector<uint32_t> &masks, int match, std::vector<int> &cnt);
-    // grouped range calls that reached this context, queries launched, queries skipped for a group without graph ids, lists the
-    // device left to the host (closures to partition / sort / replay, and hand-backs)
-    void range_grouped_info(uint64_t out[4]) const { for (int i = 0; i < 4; ++i) out[i] = rg_info_[i]; }
     // the C ABI's form: sorted per query, equal distances handed back; results kept until the next call
     bool range_search(const float *queries, int nq, int entry_point, float range, int *out_counts, int *out_flags);
     // ... with an allow-set (ids >= nbits not allowed); false with "System.InvalidOperationException: Heap is empty" where the
@@ -455,9 +446,6 @@ public:
     // exact_knn's, byte for byte.  The labels go up once per call; queries == nullptr and the resident set as exact_knn.  Synchronous.
     bool exact_knn_collapsed(const float *queries, int nq, long long n_rows, int k, const int *row_group, long long n_row_group, int per_group,
                              const uint32_t *allow_bits, long long nbits, int *out_ids, float *out_d);
-    // collapsed calls that scanned, queries they scanned, keys the cap dropped at an insert, entries evicted by a nearer key of their
-    // label (the last two are counted by the scan's and the merge's waves and depend on the order the keys arrived in)
-    void exact_collapsed_info(uint64_t out[4]) const { for (int i = 0; i < 4; ++i) out[i] = xc_info_[i]; }
     // knn_query_collapsed on one context: search_filtered (allow_bits != nullptr) or search_batch's traversal of
     // resident queries 0 .. nq - 1 with a result of `beam` entries per query, which stays on the device: collapse_rows_kernel
     // walks every row there -- an entry is kept while fewer than per_group kept entries have its label row_group[id] -- and only
@@ -483,9 +471,6 @@ public:
     // resident set stays what it was) and whose candidates are exact_knn's minus ids[i] -- the scan's sink drops the pair
     // (exact_scan_kernel<M, ExactTopKSelf>), which is not counted in exact_evals.  An id outside the uploaded rows is an error.
     bool exact_knn_by_id(const int *ids, int nq, long long n_rows, int k, const uint32_t *allow_bits, long long nbits, int *out_ids, float *out_d);
-    // by-id calls (search_self, exact_knn_by_id), queries traversed on the device, hand-backs, queries scanned, rows gathered, pairs
-    // skipped as self -- on this context
-    void by_id_info(uint64_t out[6]) const { for (int i = 0; i < 6; ++i) out[i] = bi_info_[i]; }
     // hnswdev_exact_range: exact_knn's candidates, queries and distances; per query EVERY candidate with
     // distance <= range (the float compare), ascending by (distance, id), of any number.  out_counts[i]: query i's; the lists stay
     // in the context, concatenated in query order, until the next exact_range and are copied out by exact_range_results (the
@@ -493,8 +478,6 @@ public:
     bool exact_range(const float *queries, int nq, long long n_rows, float range, const uint32_t *allow_bits, long long nbits, int *out_counts);
     bool exact_range_results(int *out_ids, float *out_d);
     size_t exact_range_total() const { return xr_ids_.size(); }
-    // lists of >= 2 entries ordered on the device, lists ordered on the host, rounds repeated with exact capacities, results returned
-    void exact_range_info(uint64_t out[4]) const { for (int i = 0; i < 4; ++i) out[i] = xr_info_[i]; }
     // hnswdev_exact_knn_grouped: exact_knn with a candidate set per query.  Query i's candidates are the uploaded
     // ids j < min(n_rows, uploaded, n_row_group) with row_group[j] == query_group[i]; a row_group value outside [0, n_groups) puts
     // the id in no group, a query_group value outside it is an error (nothing is written).  The groups' id lists are built on the
@@ -502,9 +485,6 @@ public:
     // Everything else -- distances, order, padding, k, queries == nullptr, the untouched resident set -- is exact_knn's.  Synchronous.
     bool exact_knn_grouped(const float *queries, int nq, long long n_rows, int k, const int *row_group, long long n_row_group, const int *query_group,
                            int n_groups, int *out_ids, float *out_d);
-    // grouped calls that launched, groups scanned (a query and a candidate each), scan blocks launched, ids placed in group lists
-    // (all four count the calls that launched a scan only)
-    void exact_grouped_info(uint64_t out[4]) const { for (int i = 0; i < 4; ++i) out[i] = xg_info_[i]; }
     // hnswdev_exact_knn_tagged: exact_knn_grouped where query i's candidates are the uploaded ids
     // j < min(n_rows, uploaded, n_row_tags) whose word row_tags[j] matches query_tags[i] under `match` (0 any, 1 all).  Every
     // distinct mask is a list; the lists overlap, and are built on the device (dk_tag_lists.h) in batches of masks whose counts sum
@@ -513,9 +493,6 @@ public:
     // queries == nullptr and the untouched resident set as exact_knn.  Synchronous.
     bool exact_knn_tagged(const float *queries, int nq, long long n_rows, int k, const uint32_t *row_tags, long long n_row_tags, const uint32_t *query_tags,
                           int match, int *out_ids, float *out_d);
-    // calls that counted candidates, distinct masks, queries scanned, queries padded for a mask without a candidate, list entries
-    // built, batches of masks scanned
-    void exact_tagged_info(uint64_t out[6]) const { for (int i = 0; i < 6; ++i) out[i] = xt_info_[i]; }
     // HIP-event time of the tagged calls' list-building kernels (count, offsets, fill) made while profiling was on
     double tag_list_ms() const { return xt_list_ms_; }
     // hnswdev_exact_range_grouped: exact_range with exact_knn_grouped's candidate set per query -- the group
@@ -524,9 +501,6 @@ public:
     // false: no results are kept and every count is 0.  Synchronous.
     bool exact_range_grouped(const float *queries, int nq, long long n_rows, float range, const int *row_group, long long n_row_group,
                              const int *query_group, int n_groups, int *out_counts);
-    // grouped range calls that launched a scan, lists of >= 2 entries ordered on the device, lists ordered on the host, pieces
-    // scanned again with exact capacities
-    void exact_range_grouped_info(uint64_t out[4]) const { for (int i = 0; i < 4; ++i) out[i] = xrg_info_[i]; }
     // hnswdev_exact_range_tagged: exact_range with exact_knn_tagged's candidate set per query -- the tag arguments,
     // their errors, the lists and the batches of masks are that call's; each batch is one grouped range scan (exact_range_grouped's
     // rounds, capacities, pass B and sort limit) over the queries of its masks.  The lists are kept for exact_range_results
@@ -534,9 +508,6 @@ public:
     // without a scan.  false: no results are kept and every count is 0.  Synchronous.
     bool exact_range_tagged(const float *queries, int nq, long long n_rows, float range, const uint32_t *row_tags, long long n_row_tags,
                             const uint32_t *query_tags, int match, int *out_counts);
-    // calls that counted candidates, distinct masks, queries scanned, queries answered empty without a scan, list entries built,
-    // batches, lists of >= 2 entries ordered on the device, lists ordered on the host, pieces scanned again
-    void exact_range_tagged_info(uint64_t out[9]) const { for (int i = 0; i < 9; ++i) out[i] = xrt_info_[i]; }
     // HIP-event time of the list-building kernels (count, offsets, place) of the grouped calls made while profiling was on
     double exact_grouped_list_ms() const { return xg_list_ms_; }
     // hnswdev_graph_info / hnswdev_graph_components (dk_graph_info.h): HNSWInfo.LayerInfo (HNSWInfo.cs:18-43) and the
@@ -549,8 +520,6 @@ public:
     bool graph_info(int layer, const uint32_t *live_bits, long long nbits, bool with_in_edges, hnsw_mi355x_layer_info *out);
     bool graph_components(int layer, const uint32_t *live_bits, long long nbits, int *out_count);
     bool graph_info_layer(const char *who, int layer);
-    // layers summarised, layers whose components were counted, list entries read (counted by the kernels), kernel launches
-    void graph_info_counters(uint64_t out[4]) const { for (int i = 0; i < 4; ++i) out[i] = gi_info_[i]; }
     // hnswdev_graph_reach_layer / hnswdev_graph_reach (dk_graph_reach.h): what can be reached over OUT-edges.  Members
     // and the live set are graph_info's; an entry u -> v counts only between two members.  graph_reach_layer: one layer, the seeds a
     // bitset (seed_nbits bits, ids beyond it and ids that are no members are no seeds; an empty set reaches nothing and launches no
@@ -566,8 +535,6 @@ public:
     int graph_reach(int entry_point, int top, const uint32_t *live_bits, long long nbits, int min_layer, hnsw_mi355x_layer_reach *out_layers, int cap,
                     uint32_t *out_reached_bits, int *out_hops);
     bool graph_reach_top(const char *who, int entry_point, int *top);
-    // layers walked, rounds (expansion launches), list entries the expansions read (counted by the kernel), kernel launches
-    void graph_reach_counters(uint64_t out[4]) const { for (int i = 0; i < 4; ++i) out[i] = gr_info_[i]; }
 
     // One round of repair_reachability (dk_graph_repair.h), steps 1 - 3, on one layer of the mirror; the mirror is read,
     // never written.  Members and the live set are graph_info's.  The seeds: seed_mode kRepairSeedEntry: the one id entry_point,
@@ -583,8 +550,6 @@ public:
     // hnswdev_graph_repair_propose: a round with seed_bits on slot 0, copied out: *out_n = |U|, min(cap, |U|) rows written.  0 or -1.
     int graph_repair_propose(int layer, const uint32_t *live_bits, long long nbits, const uint32_t *seed_bits, long long seed_nbits, int cands, int max_edges,
                              int *out_n, int *out_ids, int *out_cands, int *out_codes, int cap);
-    // rounds that ran the proposal kernel, (u, candidate) pairs it judged, distances it measured (counted by the kernel), lists patched
-    void graph_repair_counters(uint64_t out[4]) const { for (int i = 0; i < 4; ++i) out[i] = rp_info_[i]; }
 
     void set_profiling(bool on) { profiling_ = on; }
 
@@ -593,6 +558,8 @@ public:
     void set_shadows_allowed(bool on) { shadows_allowed_ = on; }
     void get_stats(hnswdev_stats *out);
     void reset_stats();
+    // The counter blocks of counter_blocks.h: a block's kCounterSlots values since reset_stats, copied to out[]
+    void counters(CounterBlock b, uint64_t *out) const { std::copy_n(counters_[(int)b], kCounterSlots[(int)b], out); }
     // The row prefilter's counters (a view adds to its primary's): launches that ran with it, rows measured on the shadow, rows
     // measured again from f32, shadow rows packed.  All zero on a context that has none (every metric but sq_euclid, diag row_prefilter=0).
     void row_prefilter_stats(uint64_t out[4]);
@@ -708,22 +675,15 @@ private:
     DevBuf<unsigned> s_allow_;   // filtered searches: the call's allow-set
     DevBuf<int> s_glabel_;       // grouped searches: the call's row_group
     DevBuf<int> s_gquery_;       // ... [query_group of the call | order tables of its launches]
-    uint64_t kg_info_[4] = {0, 0, 0, 0};
-    uint64_t rg_info_[4] = {0, 0, 0, 0}; // range_grouped_info
-    uint64_t rt_info_[6] = {0, 0, 0, 0, 0, 0}; // range_tagged_info
-    uint64_t xrt_info_[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}; // exact_range_tagged_info
     DevBuf<unsigned> s_ttags_;   // tagged calls: the call's row_tags
     DevBuf<unsigned> s_tmask_;   // ... its distinct masks
     DevBuf<int> s_tcnt_;         // ... per distinct mask: [candidates | offset of its segment in x_ids_ | the filling kernel's cursor]
     DevBuf<int> s_tquery_;       // tagged searches: [query_tags of the call | order tables of its launches]
-    uint64_t kt_info_[5] = {0, 0, 0, 0, 0};
-    uint64_t xt_info_[6] = {0, 0, 0, 0, 0, 0};
     double xt_list_ms_ = 0.0;
     bool tag_counts(const unsigned *row_tags, long long n, const std::vector<uint32_t> &masks, int match, std::vector<int> &cnt);
     DevBuf<int> s_self_;         // by-id calls: the ids whose rows are the resident queries (valid while q_by_id_)
     DevBuf<int> x_self_;         // ... the ids of exact_knn_by_id's queries, and gather_rows' ids
     bool q_by_id_ = false;       // the resident set was made by set_queries_by_id and s_self_ holds its n_queries_ ids
-    uint64_t bi_info_[6] = {0, 0, 0, 0, 0, 0};
     bool query_room(int nq);
     bool upload_ids(const int *ids, int n, DevBuf<int> &d_ids);
     bool gather_launch(const int *d_ids, long long n, float *out);
@@ -741,7 +701,6 @@ private:
                           const int *d_self = nullptr, const ExactCollapseArgs *collapse = nullptr);
     DevBuf<int> x_clabels_;               // exact_knn_collapsed: row_group as uploaded
     DevBuf<unsigned long long> x_cinfo_;  // ... [keys dropped by the cap | entries evicted], counted on the device
-    uint64_t xc_info_[4] = {0, 0, 0, 0};
     // search_collapsed: while set, run_resident and search_batch_impl collapse a launch's rows on the device (width -> k columns)
     // before the copy-out and write rows of k entries to the caller's arrays
     struct RowCollapse { const int *d_labels; long long n_labels; int per_group, k; };
@@ -761,24 +720,21 @@ private:
     DevBuf<int> x_rout_;                  // ... the lists ordered on the device: [ids | distances]
     std::vector<int> xr_ids_;             // ... the call's results until the next call (exact_range_results)
     std::vector<float> xr_d_;
-    uint64_t xr_info_[4] = {0, 0, 0, 0};
     DevBuf<int> x_grow_;                  // exact_knn_grouped: row_group as uploaded
     DevBuf<int> x_gcnt_;                  // ... per group: [members | offset of its segment in x_ids_ | the placing kernel's cursor]
     DevBuf<int> x_gperm_;                 // ... queries == NULL: where each query of the sorted order is in the resident set
     DevBuf<unsigned char> x_gwork_;       // ... a round's tables: [ExactMergeItem per query | ExactWorkItem per scan block]
-    uint64_t xg_info_[4] = {0, 0, 0, 0};
-    uint64_t xrg_info_[4] = {0, 0, 0, 0}; // exact_range_grouped's counters
     bool exact_group_lists(const char *who, const int *row_group, long long n, int n_groups, std::vector<int> &cnt, std::vector<int> &goff, uint64_t *listed);
     bool exact_sorted_queries(const char *who, const float *queries, int nq, const std::vector<int> &order, const float **d_q, const double **d_qsn,
                               const int *resident = nullptr);
     bool exact_grouped_plan(const char *who, int k, ExactGroupedCall *gc);
     template <class OnBatch> // the batches of masks of exact_knn_tagged / exact_range_tagged, each handed to on_batch (device_backend.hip)
     bool exact_tag_batches(const char *who, const float *queries, int nq, long long n, int k, const uint32_t *row_tags, const TagCall &tc, int match,
-                           std::vector<int> &cnt, uint64_t info[6], OnBatch &&on_batch);
+                           std::vector<int> &cnt, uint64_t *info, OnBatch &&on_batch);
     bool exact_knn_grouped_scan(const char *who, const float *queries, const int *resident, int nq, int k, const int *query_group, int n_groups,
                                 const ExactGroupedCall &gc, int *out_ids, float *out_d, uint64_t *blocks);
     bool exact_range_grouped_scan(const char *who, const float *queries, const int *resident, int nq, float range, const int *query_group, int n_groups,
-                                  const ExactGroupedCall &gc, int *out_counts, uint64_t info[4]);
+                                  const ExactGroupedCall &gc, int *out_counts, uint64_t *info);
     ExactStart exact_grouped_begin(const char *who, bool args_ok, const float *queries, int nq, long long n_rows, int k, const int *row_group,
                                    long long n_row_group, const int *query_group, int n_groups, ExactGroupedCall *gc);
     double xg_list_ms_ = 0.0;
@@ -788,14 +744,12 @@ private:
     DevBuf<unsigned> gi_live_;          // ... its live set
     DevBuf<int> gi_indeg_, gi_parent_;  // ... per node: in-degree on the layer; parent in the union-find's forest
     DevBuf<int> gi_inhist_;             // ... nodes per in-degree, max in-degree + 1 bins
-    uint64_t gi_info_[4] = {0, 0, 0, 0};
     bool graph_reach_room();
     bool graph_reach_run(const LayerView &g, const ReachSeeds &seeds, int which, bool want_bits, uint64_t summary[4]);
     bool graph_reach_copy_out(int which, uint32_t *out_reached_bits, int *out_hops);
     DevBuf<int> gr_hop_[2], gr_q_[2];   // graph_reach: per node the hop (two arrays: a layer's is the seed set of the layer below); the two frontier queues
     DevBuf<unsigned> gr_bits_, gr_seed_; // ... the reached set as a bitset; graph_reach_layer's seed set
     DevBuf<unsigned long long> gr_acc_; // ... the layer's ReachAcc
-    uint64_t gr_info_[4] = {0, 0, 0, 0};
     DevBuf<unsigned> rp_bits_;          // graph_repair_round: [the unreached members | the reached set] as bitsets
     DevBuf<int> rp_bcnt_;               // ... their set bits per block of kExactCompactWords words
     DevBuf<long long> rp_boff_;         // ... and the exclusive prefix of those (exact_compact_kernel's block offsets)
@@ -804,7 +758,6 @@ private:
     DevBuf<double> rp_qsn_;
     DevBuf<unsigned long long> rp_meas_; // ... distances the proposal kernel measured
     PinBuf<int> rp_host_;               // ... [U | candidates | codes | measured] on the host
-    uint64_t rp_info_[4] = {0, 0, 0, 0};
     DevBuf<SearchHit> s_arena_; // range search: the launch's results, packed
     DevBuf<unsigned long long> s_roff_, s_arena_used_; // s_roff_ stands for the capacity of range_batch's per-job arrays
     DevBuf<int> s_rentry_;
@@ -854,6 +807,8 @@ private:
     DevStream stream_; // (destroyed by ~Device itself, before any holder lets go of its memory)
     bool profiling_ = false;
     hnswdev_stats stats_{};
+    uint64_t counters_[kCounterBlocks][kMaxCounterSlots] = {}; // the blocks of counter_blocks.h, a row each
+    uint64_t *counter_block(CounterBlock b) { return counters_[(int)b]; } // a block to count in, subscripted by its slot:: names
     bool shadows_allowed_ = true;
     int uj_len_ = 0, uj_entry_ = -1, uj_layer_ = -1; // s_jobs_ holds search_queries' jobs 0 .. uj_len_-1 for that entry point
     bool search_batch_impl(const SearchJob *jobs, int njobs, int k, int k_out, int *out_ids, float *out_d, int *out_flag, bool keep_repeat_flag,

@@ -1033,22 +1033,9 @@ void Device::reset_stats()
     uint64_t rb = stats_.row_bytes;
     stats_ = hnswdev_stats{};
     stats_.row_bytes = rb;
-    for (uint64_t &v : xr_info_) v = 0;
-    for (uint64_t &v : xg_info_) v = 0;
-    for (uint64_t &v : xc_info_) v = 0;
-    for (uint64_t &v : xrg_info_) v = 0;
-    for (uint64_t &v : kg_info_) v = 0;
-    for (uint64_t &v : rg_info_) v = 0;
-    for (uint64_t &v : rt_info_) v = 0;
-    for (uint64_t &v : xrt_info_) v = 0;
+    memset(counters_, 0, sizeof(counters_));
     xg_list_ms_ = 0.0;
-    for (uint64_t &v : kt_info_) v = 0;
-    for (uint64_t &v : bi_info_) v = 0;
-    for (uint64_t &v : xt_info_) v = 0;
     xt_list_ms_ = 0.0;
-    for (uint64_t &v : gi_info_) v = 0;
-    for (uint64_t &v : gr_info_) v = 0;
-    for (uint64_t &v : rp_info_) v = 0;
 #ifdef EXP_PHASE_CLOCKS
     (void)hipDeviceSynchronize();
     phase_report("reset_stats");
@@ -2240,10 +2227,12 @@ bool Device::search_grouped(int nq, int entry, int entry_layer, int k, int k_out
         if (!run_predicate_search(c, p, b_lab + 2 * b_q, upload, listed, filter)) return false;
     }
     pad_skipped(c, members); // (every row when nothing was launched: no flag is set then)
-    kg_info_[0] += 1;
-    kg_info_[1] += (uint64_t)lo.launched;
-    kg_info_[2] += (uint64_t)(nq - lo.launched);
-    kg_info_[3] += count_search_overflows(c);
+    using Slot = slot::knn_grouped_info;
+    uint64_t *ctr = counter_block(Slot::kBlock);
+    ctr[Slot::calls] += 1;
+    ctr[Slot::launched] += (uint64_t)lo.launched;
+    ctr[Slot::skipped] += (uint64_t)(nq - lo.launched);
+    ctr[Slot::handbacks] += count_search_overflows(c);
     return true;
 }
 
@@ -2334,11 +2323,13 @@ bool Device::search_tagged(int nq, int entry, int entry_layer, int k, int k_out,
         if (!run_predicate_search(c, p, 2 * b_q, upload, listed, filter)) return false;
     }
     pad_skipped(c, members); // (every row when nothing was launched: no flag is set then)
-    kt_info_[0] += 1;
-    kt_info_[1] += (uint64_t)tc.masks.size();
-    kt_info_[2] += (uint64_t)lo.launched;
-    kt_info_[3] += (uint64_t)(nq - lo.launched);
-    kt_info_[4] += count_search_overflows(c);
+    using Slot = slot::knn_tagged_info;
+    uint64_t *ctr = counter_block(Slot::kBlock);
+    ctr[Slot::calls] += 1;
+    ctr[Slot::masks] += (uint64_t)tc.masks.size();
+    ctr[Slot::launched] += (uint64_t)lo.launched;
+    ctr[Slot::skipped] += (uint64_t)(nq - lo.launched);
+    ctr[Slot::handbacks] += count_search_overflows(c);
     return true;
 }
 
@@ -2494,13 +2485,16 @@ bool Device::range_batch(const SearchJob *jobs, int njobs, float range, RangeRes
 {
     const bool filtered = f.kind != RangeFilter::kNone; // (labels, tags: the bit set's ranking, replay and packing, on their predicate)
     const bool keyed = f.per_query();
-    // The info counters of the two per-query kinds, range_grouped_info and range_tagged_info: the same quantities at each array's own
-    // places (-1: it keeps no such counter); the other kinds keep none.
-    enum { kCalls, kMasks, kLaunched, kSkipped, kHostFinished, kLongFinished };
-    const auto count = [&](int what, uint64_t by) {
-        static constexpr int kLabelSlot[6] = {0, -1, 1, 2, 3, -1};
-        if (f.kind == RangeFilter::kTags) rt_info_[what] += by;
-        else if (f.kind == RangeFilter::kLabels && kLabelSlot[what] >= 0) rg_info_[kLabelSlot[what]] += by;
+    // The counter blocks of the two per-query kinds, range_tagged_info and range_grouped_info: the same quantities under each block's
+    // own slot (-1: the grouped block keeps no such counter); the other kinds keep none.
+    using Tagged = slot::range_tagged_info;
+    using Grouped = slot::range_grouped_info;
+    struct What { int tagged, grouped; };
+    constexpr What kCalls{Tagged::calls, Grouped::calls}, kMasks{Tagged::masks, -1}, kLaunched{Tagged::launched, Grouped::launched},
+        kSkipped{Tagged::skipped, Grouped::skipped}, kHostFinished{Tagged::host_finished, Grouped::host_finished}, kLongFinished{Tagged::long_finished, -1};
+    const auto count = [&](What what, uint64_t by) {
+        if (f.kind == RangeFilter::kTags) counter_block(Tagged::kBlock)[what.tagged] += by;
+        else if (f.kind == RangeFilter::kLabels && what.grouped >= 0) counter_block(Grouped::kBlock)[what.grouped] += by;
     };
     if (keyed) {
         if (f.n < 0 || (f.match != 0 && f.match != 1) || (njobs > 0 && (!f.per_id || !f.keys))) { set_dev_error("range_batch: bad argument"); return false; }
@@ -3305,7 +3299,9 @@ bool Device::exact_knn_collapsed(const float *queries, int nq, long long n_rows,
     if (!h) return false;
     HIP_OK(hipMemcpyAsync(h, x_cinfo_, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
     HIP_OK(hipStreamSynchronize(st));
-    xc_info_[0] += 1; xc_info_[1] += (uint64_t)nq; xc_info_[2] += h[0]; xc_info_[3] += h[1];
+    using Slot = slot::exact_collapsed_info;
+    uint64_t *ctr = counter_block(Slot::kBlock);
+    ctr[Slot::calls] += 1; ctr[Slot::queries] += (uint64_t)nq; ctr[Slot::dropped] += h[0]; ctr[Slot::evicted] += h[1];
     return true;
 }
 
@@ -3527,7 +3523,9 @@ bool Device::exact_knn_grouped(const float *queries, int nq, long long n_rows, i
     if (s != ExactStart::ready) return s == ExactStart::nothing;
     uint64_t blocks = 0;
     if (!exact_knn_grouped_scan("exact_knn_grouped", queries, nullptr, nq, k, query_group, n_groups, gc, out_ids, out_d, &blocks)) return false;
-    if (blocks) { xg_info_[0] += 1; xg_info_[1] += gc.scanned; xg_info_[2] += blocks; xg_info_[3] += gc.listed; } // (a call that scans nothing counts nowhere)
+    using Slot = slot::exact_grouped_info;
+    uint64_t *ctr = counter_block(Slot::kBlock);
+    if (blocks) { ctr[Slot::calls] += 1; ctr[Slot::groups_scanned] += gc.scanned; ctr[Slot::scan_blocks] += blocks; ctr[Slot::ids_listed] += gc.listed; } // (a call that scans nothing counts nowhere)
     return true;
 }
 
@@ -3631,11 +3629,11 @@ bool Device::exact_knn_grouped_scan(const char *who, const float *queries, const
 // takes it), the lists built in x_ids_ (timed into xt_list_ms_ while profiling is on), and on_batch(gc, bq, resident, sel, qg) for
 // the batch's queries -- those of its masks that have a candidate, sel[j] their places in the caller's order and qg[j] their
 // lists: bq / resident name them as the grouped scans take queries, the caller's own when the batch is the whole call, a gathered
-// copy otherwise.  info: the six counters a tagged scan leads with -- calls that counted candidates, distinct masks, queries
-// scanned, queries without a scan, list entries built, batches -- added to when every batch went through.
+// copy otherwise.  info: the caller's counter block, exact_tagged_info or exact_range_tagged_info -- the six slots a tagged scan
+// leads with are added to when every batch went through.
 template <class OnBatch>
 bool Device::exact_tag_batches(const char *who, const float *queries, int nq, long long n, int k, const uint32_t *row_tags, const TagCall &tc, int match,
-                               std::vector<int> &cnt, uint64_t info[6], OnBatch &&on_batch)
+                               std::vector<int> &cnt, uint64_t *info, OnBatch &&on_batch)
 {
     if (!queries && (nq > n_queries_ || tail_.n > 0)) {
         set_dev_error(std::string(who) + ": queries == NULL needs a resident query set of at least nq rows (hnswdev_set_queries)");
@@ -3697,7 +3695,9 @@ bool Device::exact_tag_batches(const char *who, const float *queries, int nq, lo
         batches += 1;
         d0 = d1;
     }
-    info[0] += 1; info[1] += (uint64_t)D; info[2] += scanned_q; info[3] += (uint64_t)nq - scanned_q; info[4] += listed; info[5] += batches;
+    using Slot = slot::exact_tagged_info; // (exact_range_tagged_info leads with the same six: counter_blocks.h asserts it)
+    info[Slot::calls] += 1; info[Slot::masks] += (uint64_t)D; info[Slot::scanned] += scanned_q; info[Slot::skipped] += (uint64_t)nq - scanned_q;
+    info[Slot::ids_listed] += listed; info[Slot::batches] += batches;
     return true;
 }
 
@@ -3720,7 +3720,7 @@ bool Device::exact_knn_tagged(const float *queries, int nq, long long n_rows, in
     const int D = (int)tc.masks.size();
     std::vector<int> cnt, t_ids;
     std::vector<float> t_d;
-    const bool ok = exact_tag_batches(who, queries, nq, n, k, row_tags, tc, match, cnt, xt_info_, [&](const ExactGroupedCall &gc, const float *bq, const int *resident, const std::vector<int> &sel, const int *qg) {
+    const bool ok = exact_tag_batches(who, queries, nq, n, k, row_tags, tc, match, cnt, counter_block(CounterBlock::exact_tagged_info), [&](const ExactGroupedCall &gc, const float *bq, const int *resident, const std::vector<int> &sel, const int *qg) {
         const int nb = (int)sel.size();
         uint64_t blocks = 0;
         if (nb == nq) return exact_knn_grouped_scan(who, bq, resident, nq, k, qg, D, gc, out_ids, out_d, &blocks); // straight into the caller's arrays
@@ -3929,6 +3929,8 @@ bool Device::exact_range(const float *queries, int nq, long long n_rows, float r
         };
 
         // the lists of queries [q0, q0 + nr), every one inside its segment seg[i] .. : ordered and appended to the call's results
+        using Slot = slot::exact_range_info;
+        uint64_t *ctr = counter_block(Slot::kBlock);
         const auto finish = [&](long long q0, int nr, const unsigned *c) -> bool {
             size_t total = 0;
             for (int i = 0; i < nr; ++i) {
@@ -3939,8 +3941,8 @@ bool Device::exact_range(const float *queries, int nq, long long n_rows, float r
             const size_t base = xr_ids_.size();
             xr_ids_.resize(base + total);
             xr_d_.resize(base + total);
-            if (!exact_range_finish(w, nr, c, seg.data(), nullptr, obase.data(), base, true, &xr_info_[0], &xr_info_[1])) return false;
-            xr_info_[3] += total;
+            if (!exact_range_finish(w, nr, c, seg.data(), nullptr, obase.data(), base, true, &ctr[Slot::device_sorted], &ctr[Slot::host_sorted])) return false;
+            ctr[Slot::results] += total;
             return true;
         };
 
@@ -3958,7 +3960,7 @@ bool Device::exact_range(const float *queries, int nq, long long n_rows, float r
             cnt_b.resize((size_t)nr);
             for (size_t s0 = 0, s1; s0 < (size_t)nr; s0 = s1) {
                 if (!exact_range_piece("exact_range", cnt.data(), (size_t)nr, s0, w.arena_max, seg, &s1)) return false;
-                xr_info_[2] += 1;
+                ctr[Slot::repeated_rounds] += 1;
                 const int ns = (int)(s1 - s0);
                 if (!scan(off + (long long)s0, ns, cnt_b.data()) || !exact_range_recount_ok("exact_range", cnt_b.data(), cnt.data() + s0, (size_t)ns)) return false;
                 if (!finish(off + (long long)s0, ns, cnt_b.data())) return false;
@@ -3986,7 +3988,7 @@ bool Device::exact_range_grouped(const float *queries, int nq, long long n_rows,
         if (s == ExactStart::failed) return false;
         for (int i = 0; i < nq; ++i) out_counts[i] = 0;
         if (s == ExactStart::nothing) return true; // no query has a candidate: empty lists, no scan
-        return exact_range_grouped_scan("exact_range_grouped", queries, nullptr, nq, range, query_group, n_groups, gc, out_counts, xrg_info_);
+        return exact_range_grouped_scan("exact_range_grouped", queries, nullptr, nq, range, query_group, n_groups, gc, out_counts, counter_block(CounterBlock::exact_range_grouped_info));
     });
 }
 
@@ -3994,11 +3996,12 @@ bool Device::exact_range_grouped(const float *queries, int nq, long long n_rows,
 // the sorted upload, work items, pass A, the finish and pass B -- what exact_range_grouped and every batch of exact_range_tagged
 // run.  The nq queries are `queries`, or (nullptr) the resident queries resident[0 .. nq) (nullptr: 0 .. nq - 1); query_group[i]
 // names query i's list.  out_counts[0, nq) are written (zeroed by the caller) and the lists APPENDED to xr_ids_ / xr_d_ in the order
-// of the nq queries.  info: [calls that launched a scan, lists of >= 2 entries ordered on the device, lists ordered on the host,
-// pieces scanned again], added to.
+// of the nq queries.  info: a block of exact_range_grouped_info's slots, added to -- the context's own, or exact_range_tagged's
+// scratch of that shape.
 bool Device::exact_range_grouped_scan(const char *who, const float *queries, const int *resident, int nq, float range, const int *query_group, int n_groups,
-                                      const ExactGroupedCall &gc, int *out_counts, uint64_t info[4])
+                                      const ExactGroupedCall &gc, int *out_counts, uint64_t *info)
 {
+    using Slot = slot::exact_range_grouped_info;
     {
         hipStream_t st = S(stream_);
         const std::vector<int> &cnt = gc.cnt;
@@ -4113,7 +4116,7 @@ bool Device::exact_range_grouped_scan(const char *who, const float *queries, con
             }
             xr_ids_.resize(base + total);
             xr_d_.resize(base + total);
-            if (!exact_range_finish(w, nr, cnt_fit.data(), seg.data(), nullptr, obase.data(), base, ov.empty(), &info[1], &info[2])) return false;
+            if (!exact_range_finish(w, nr, cnt_fit.data(), seg.data(), nullptr, obase.data(), base, ov.empty(), &info[Slot::device_sorted], &info[Slot::host_sorted])) return false;
             // pass B: the queries whose count exceeded its capacity (ov, their counts in cnt_ov), in pieces whose exact counts fit the
             // arena, each with segments of exactly its counts; the other queries of their tiles are measured again and their keys dropped
             for (size_t s0 = 0, s1; s0 < ov.size(); s0 = s1) {
@@ -4123,14 +4126,14 @@ bool Device::exact_range_grouped_scan(const char *who, const float *queries, con
                 for (int s = 0; s < ns; ++s) slot_q[(size_t)ov[s0 + (size_t)s]] = s;
                 for (int p = 0; p < nr; ++p) dest[(size_t)p] = slot_q[(size_t)(order[(size_t)(off + p)] - off)];
                 items(off, nr);
-                info[3] += 1;
+                info[Slot::repeated_pieces] += 1;
                 cnt_b.resize((size_t)ns);
                 if (!scan(off, nr, ns, cnt_b.data()) || !exact_range_recount_ok(who, cnt_b.data(), cnt_ov.data() + s0, (size_t)ns)) return false;
-                if (!exact_range_finish(w, ns, cnt_b.data(), seg.data(), ov.data() + s0, obase.data(), base, true, &info[1], &info[2])) return false;
+                if (!exact_range_finish(w, ns, cnt_b.data(), seg.data(), ov.data() + s0, obase.data(), base, true, &info[Slot::device_sorted], &info[Slot::host_sorted])) return false;
             }
             off = r1;
         }
-        if (launched) info[0] += 1;
+        if (launched) info[Slot::calls] += 1;
         return true;
     }
 }
@@ -4156,18 +4159,21 @@ bool Device::exact_range_tagged(const float *queries, int nq, long long n_rows, 
         const long long n = std::min({n_rows, n_rows_hw_, n_row_tags});
         if (n <= 0) return true; // no candidate: empty lists, nothing launched
         const int D = (int)tc.masks.size();
-        uint64_t info[4] = {0, 0, 0, 0};
+        using Slot = slot::exact_range_tagged_info;
+        using Scan = slot::exact_range_grouped_info;
+        uint64_t *ctr = counter_block(Slot::kBlock);
+        uint64_t scan_info[Scan::kCount] = {}; // what the batches' scans count, folded into the call's block below
         int batches = 0;
         std::vector<int> cnt, t_cnt;
         std::vector<size_t> at_of((size_t)nq, 0); // where query i's list starts in xr_ids_ as the batches left it
-        const bool ok = exact_tag_batches(who, queries, nq, n, 0, row_tags, tc, match, cnt, xrt_info_, [&](const ExactGroupedCall &gc, const float *bq, const int *resident, const std::vector<int> &sel, const int *qg) {
+        const bool ok = exact_tag_batches(who, queries, nq, n, 0, row_tags, tc, match, cnt, ctr, [&](const ExactGroupedCall &gc, const float *bq, const int *resident, const std::vector<int> &sel, const int *qg) {
             const int nb = (int)sel.size();
             size_t o = xr_ids_.size();
             if (nb == nq) { // every query of the call: straight into the caller's counts
-                if (!exact_range_grouped_scan(who, bq, resident, nq, range, qg, D, gc, out_counts, info)) return false;
+                if (!exact_range_grouped_scan(who, bq, resident, nq, range, qg, D, gc, out_counts, scan_info)) return false;
             } else if (nb > 0) {
                 t_cnt.assign((size_t)nb, 0);
-                if (!exact_range_grouped_scan(who, bq, resident, nb, range, qg, D, gc, t_cnt.data(), info)) return false;
+                if (!exact_range_grouped_scan(who, bq, resident, nb, range, qg, D, gc, t_cnt.data(), scan_info)) return false;
                 for (int j = 0; j < nb; ++j) out_counts[sel[(size_t)j]] = t_cnt[(size_t)j];
             }
             for (int j = 0; j < nb; ++j) { at_of[(size_t)sel[(size_t)j]] = o; o += (size_t)out_counts[sel[(size_t)j]]; }
@@ -4187,7 +4193,9 @@ bool Device::exact_range_tagged(const float *queries, int nq, long long n_rows, 
             xr_ids_.swap(ids);
             xr_d_.swap(d);
         }
-        xrt_info_[6] += info[1]; xrt_info_[7] += info[2]; xrt_info_[8] += info[3];
+        ctr[Slot::device_sorted] += scan_info[Scan::device_sorted];
+        ctr[Slot::host_sorted] += scan_info[Scan::host_sorted];
+        ctr[Slot::repeated_pieces] += scan_info[Scan::repeated_pieces];
         return true;
     });
 }
@@ -4322,7 +4330,9 @@ bool Device::graph_info(int layer, const uint32_t *live_bits, long long nbits, b
         if (seen != nodes) { set_dev_error("graph_info: the in-degree histogram does not add up to the layer's nodes"); return false; }
         out->in_edges_median = hist_median(hist.data(), bins, nodes);
     }
-    gi_info_[0] += 1; gi_info_[2] += a.entries; gi_info_[3] += launches;
+    using Slot = slot::graph_info_counters;
+    uint64_t *ctr = counter_block(Slot::kBlock);
+    ctr[Slot::info_layers] += 1; ctr[Slot::entries] += a.entries; ctr[Slot::launches] += launches;
     return true;
 }
 
@@ -4345,7 +4355,9 @@ bool Device::graph_components(int layer, const uint32_t *live_bits, long long nb
     const GraphAcc *h;
     if (!graph_info_fetch(&h)) return false;
     *out_count = (int)h->roots;
-    gi_info_[1] += 1; gi_info_[2] += h->entries; gi_info_[3] += 3;
+    using Slot = slot::graph_info_counters;
+    uint64_t *ctr = counter_block(Slot::kBlock);
+    ctr[Slot::component_layers] += 1; ctr[Slot::entries] += h->entries; ctr[Slot::launches] += 3;
     return true;
 }
 
@@ -4409,7 +4421,9 @@ bool Device::graph_reach_run(const LayerView &g, const ReachSeeds &seeds, int wh
     HIP_OK(hipStreamSynchronize(st));
     if (h->reached != queued) { set_dev_error("graph_reach: the reached set is not what the rounds queued"); return false; }
     summary[0] = members; summary[1] = n_seeds; summary[2] = h->reached; summary[3] = (uint64_t)h->max_hop;
-    gr_info_[0] += 1; gr_info_[1] += rounds; gr_info_[2] += h->entries; gr_info_[3] += rounds + 2;
+    using Slot = slot::graph_reach_counters;
+    uint64_t *ctr = counter_block(Slot::kBlock);
+    ctr[Slot::layers] += 1; ctr[Slot::rounds] += rounds; ctr[Slot::entries] += h->entries; ctr[Slot::launches] += rounds + 2;
     return true;
 }
 
@@ -4558,7 +4572,9 @@ bool Device::graph_repair_round(int layer, const uint32_t *live_bits, long long 
     if (!exact_knn_rounds(rp_q_, metric_ == M_COS ? rp_qsn_.get() : nullptr, (int)n_u, x_ids_, reached, cands, h_cand, nullptr, d_cand)) return false;
 
     // the proposals
-    rp_info_[0] += 1;
+    using Slot = slot::graph_repair_counters;
+    uint64_t *ctr = counter_block(Slot::kBlock);
+    ctr[Slot::rounds] += 1;
     RepairProposeArgs a;
     a.g = g; a.rows = d_rows_; a.row_sn = d_row_sn_; a.dim = pitch_; a.n_rows = n_rows_hw_; a.hop = hop; a.cand = d_cand; a.n_pairs = (long long)pairs;
     a.max_edges = max_edges; a.code = d_code; a.measured = rp_meas_;
@@ -4572,14 +4588,14 @@ bool Device::graph_repair_round(int layer, const uint32_t *live_bits, long long 
     HIP_OK(hipStreamSynchronize(st));
     uint64_t real = 0;
     for (size_t i = 0; i < pairs; ++i) real += h_cand[i] >= 0;
-    rp_info_[1] += real; rp_info_[2] += *h_meas;
+    ctr[Slot::pairs] += real; ctr[Slot::distances] += *h_meas;
     return true;
 }
 
 bool Device::graph_repair_patch(const int *recs, int nrows, int row_stride)
 {
     if (!patch_lists(recs, nrows, row_stride)) return false;
-    rp_info_[3] += (uint64_t)std::max(nrows, 0);
+    counter_block(CounterBlock::graph_repair_counters)[slot::graph_repair_counters::lists_patched] += (uint64_t)std::max(nrows, 0);
     return true;
 }
 
@@ -4632,7 +4648,7 @@ bool Device::gather_rows(const int *ids, int n, float *out)
     if (!bind() || !q_stage_.grow((size_t)n * (size_t)dim_) || !upload_ids(ids, n, x_self_) || !gather_launch(x_self_, n, q_stage_)) return false;
     HIP_OK(hipMemcpyAsync(out, q_stage_, (size_t)n * dim_ * sizeof(float), hipMemcpyDeviceToHost, S(stream_)));
     HIP_OK(hipStreamSynchronize(S(stream_)));
-    bi_info_[4] += (uint64_t)n;
+    counter_block(CounterBlock::by_id_info)[slot::by_id_info::rows_gathered] += (uint64_t)n;
     return true;
 }
 
@@ -4653,7 +4669,7 @@ bool Device::gather_queries(const int *ids, int n, DevBuf<int> &d_ids, float *d_
         HIP_OK(hipGetLastError());
     }
     HIP_OK(hipStreamSynchronize(st));
-    bi_info_[4] += (uint64_t)n;
+    counter_block(CounterBlock::by_id_info)[slot::by_id_info::rows_gathered] += (uint64_t)n;
     return true;
 }
 
@@ -4693,9 +4709,11 @@ bool Device::search_self(int nq, int entry, int entry_layer, int k, int k_out, i
     const auto every_query = [](long long, int nj) { return nj; };
     const auto filter = [&](long long off) { return std::make_tuple(static_cast<const int *>(s_self_.get()) + off); };
     if (!run_predicate_search(c, p, 0, upload, every_query, filter)) return false;
-    bi_info_[0] += 1;
-    bi_info_[1] += (uint64_t)nq;
-    bi_info_[2] += count_search_overflows(c);
+    using Slot = slot::by_id_info;
+    uint64_t *ctr = counter_block(Slot::kBlock);
+    ctr[Slot::calls] += 1;
+    ctr[Slot::traversed] += (uint64_t)nq;
+    ctr[Slot::handbacks] += count_search_overflows(c);
     return true;
 }
 
@@ -4737,9 +4755,11 @@ bool Device::exact_knn_by_id(const int *ids, int nq, long long n_rows, int k, co
         skipped += (uint64_t)(id < n_allow && (!allow_bits || ((allow_bits[id >> 5] >> (id & 31)) & 1u)));
     }
     if (!exact_knn_rounds(x_queries_, d_qsn, nq, allow_bits ? x_ids_.get() : nullptr, m, k, out_ids, out_d, nullptr, x_self_)) return false;
-    bi_info_[0] += 1;
-    bi_info_[3] += (uint64_t)nq;
-    bi_info_[5] += skipped;
+    using Slot = slot::by_id_info;
+    uint64_t *ctr = counter_block(Slot::kBlock);
+    ctr[Slot::calls] += 1;
+    ctr[Slot::scanned] += (uint64_t)nq;
+    ctr[Slot::self_skipped] += skipped;
     return true;
 }
 
@@ -4930,38 +4950,17 @@ DEV_API int hnswdev_knn_search_grouped(void *ctx, const float *queries, int nq, 
     CTX_OR_FAIL();
     return d->knn_search_grouped(queries, nq, entry_point, k_beam, k_out, row_group, n_row_group, query_group, n_groups, out_ids, out_dists, out_flags, layer) ? 0 : -1;
 }
-DEV_API int hnswdev_knn_grouped_info(void *ctx, uint64_t out[4])
-{
-    CTX_OR_FAIL();
-    if (!out) return -1;
-    d->knn_grouped_info(out);
-    return 0;
-}
 DEV_API int hnswdev_knn_search_tagged(void *ctx, const float *queries, int nq, int entry_point, int k_beam, int k_out, int layer, const uint32_t *row_tags,
                                       long long n_row_tags, const uint32_t *query_tags, int match, int *out_ids, float *out_dists, int *out_flags)
 {
     CTX_OR_FAIL();
     return d->knn_search_tagged(queries, nq, entry_point, k_beam, k_out, row_tags, n_row_tags, query_tags, match, out_ids, out_dists, out_flags, layer) ? 0 : -1;
 }
-DEV_API int hnswdev_knn_tagged_info(void *ctx, uint64_t out[5])
-{
-    CTX_OR_FAIL();
-    if (!out) return -1;
-    d->knn_tagged_info(out);
-    return 0;
-}
 DEV_API int hnswdev_exact_knn_tagged(void *ctx, const float *queries, int nq, long long n_rows, int k, const uint32_t *row_tags, long long n_row_tags,
                                      const uint32_t *query_tags, int match, int *out_ids, float *out_dists)
 {
     CTX_OR_FAIL();
     return d->exact_knn_tagged(queries, nq, n_rows, k, row_tags, n_row_tags, query_tags, match, out_ids, out_dists) ? 0 : -1;
-}
-DEV_API int hnswdev_exact_tagged_info(void *ctx, uint64_t out[6])
-{
-    CTX_OR_FAIL();
-    if (!out) return -1;
-    d->exact_tagged_info(out);
-    return 0;
 }
 DEV_API int hnswdev_tag_list_ms(void *ctx, double *out_ms)
 {
@@ -5002,25 +5001,11 @@ DEV_API int hnswdev_range_search_grouped(void *ctx, const float *queries, int nq
     CTX_OR_FAIL();
     return d->range_search_grouped(queries, nq, entry_point, range, row_group, n_row_group, query_group, n_groups, out_counts, out_flags, layer) ? 0 : -1;
 }
-DEV_API int hnswdev_range_grouped_info(void *ctx, uint64_t out[4])
-{
-    CTX_OR_FAIL();
-    if (!out) return -1;
-    d->range_grouped_info(out);
-    return 0;
-}
 DEV_API int hnswdev_range_search_tagged(void *ctx, const float *queries, int nq, int entry_point, float range, int layer, const uint32_t *row_tags,
                                         long long n_row_tags, const uint32_t *query_tags, int match, int *out_counts, int *out_flags)
 {
     CTX_OR_FAIL();
     return d->range_search_tagged(queries, nq, entry_point, range, row_tags, n_row_tags, query_tags, match, out_counts, out_flags, layer) ? 0 : -1;
-}
-DEV_API int hnswdev_range_tagged_info(void *ctx, uint64_t out[6])
-{
-    CTX_OR_FAIL();
-    if (!out) return -1;
-    d->range_tagged_info(out);
-    return 0;
 }
 DEV_API int hnswdev_multilayer_search(void *ctx, const float *queries, int nq, int entry_point, int k, int max_layer, int min_layer, int layers_cap,
                                       int *out_ids, float *out_dists, int *out_flags)
@@ -5052,13 +5037,6 @@ DEV_API int hnswdev_exact_knn_by_id(void *ctx, const int *ids, int nq, long long
     CTX_OR_FAIL();
     return d->exact_knn_by_id(ids, nq, n_rows, k, allow_bits, nbits, out_ids, out_dists) ? 0 : -1;
 }
-DEV_API int hnswdev_by_id_info(void *ctx, uint64_t out[6])
-{
-    CTX_OR_FAIL();
-    if (!out) return -1;
-    d->by_id_info(out);
-    return 0;
-}
 DEV_API int hnswdev_exact_range(void *ctx, const float *queries, int nq, long long n_rows, float range, const uint32_t *allow_bits, long long nbits,
                                 int *out_counts)
 {
@@ -5066,13 +5044,6 @@ DEV_API int hnswdev_exact_range(void *ctx, const float *queries, int nq, long lo
     return d->exact_range(queries, nq, n_rows, range, allow_bits, nbits, out_counts) ? 0 : -1;
 }
 DEV_API int hnswdev_exact_range_results(void *ctx, int *out_ids, float *out_dists) { CTX_OR_FAIL(); return d->exact_range_results(out_ids, out_dists) ? 0 : -1; }
-DEV_API int hnswdev_exact_range_info(void *ctx, uint64_t out[4])
-{
-    CTX_OR_FAIL();
-    if (!out) return -1;
-    d->exact_range_info(out);
-    return 0;
-}
 DEV_API int hnswdev_exact_knn_grouped(void *ctx, const float *queries, int nq, long long n_rows, int k, const int *row_group, long long n_row_group,
                                       const int *query_group, int n_groups, int *out_ids, float *out_dists)
 {
@@ -5085,45 +5056,17 @@ DEV_API int hnswdev_exact_knn_collapsed(void *ctx, const float *queries, int nq,
     CTX_OR_FAIL();
     return d->exact_knn_collapsed(queries, nq, n_rows, k, row_group, n_row_group, per_group, allow_bits, nbits, out_ids, out_dists) ? 0 : -1;
 }
-DEV_API int hnswdev_exact_collapsed_info(void *ctx, uint64_t out[4])
-{
-    CTX_OR_FAIL();
-    if (!out) return -1;
-    d->exact_collapsed_info(out);
-    return 0;
-}
-DEV_API int hnswdev_exact_grouped_info(void *ctx, uint64_t out[4])
-{
-    CTX_OR_FAIL();
-    if (!out) return -1;
-    d->exact_grouped_info(out);
-    return 0;
-}
 DEV_API int hnswdev_exact_range_grouped(void *ctx, const float *queries, int nq, long long n_rows, float range, const int *row_group, long long n_row_group,
                                         const int *query_group, int n_groups, int *out_counts)
 {
     CTX_OR_FAIL();
     return d->exact_range_grouped(queries, nq, n_rows, range, row_group, n_row_group, query_group, n_groups, out_counts) ? 0 : -1;
 }
-DEV_API int hnswdev_exact_range_grouped_info(void *ctx, uint64_t out[4])
-{
-    CTX_OR_FAIL();
-    if (!out) return -1;
-    d->exact_range_grouped_info(out);
-    return 0;
-}
 DEV_API int hnswdev_exact_range_tagged(void *ctx, const float *queries, int nq, long long n_rows, float range, const uint32_t *row_tags, long long n_row_tags,
                                        const uint32_t *query_tags, int match, int *out_counts)
 {
     CTX_OR_FAIL();
     return d->exact_range_tagged(queries, nq, n_rows, range, row_tags, n_row_tags, query_tags, match, out_counts) ? 0 : -1;
-}
-DEV_API int hnswdev_exact_range_tagged_info(void *ctx, uint64_t out[9])
-{
-    CTX_OR_FAIL();
-    if (!out) return -1;
-    d->exact_range_tagged_info(out);
-    return 0;
 }
 DEV_API int hnswdev_exact_grouped_list_ms(void *ctx, double *out_ms)
 {
@@ -5142,13 +5085,6 @@ DEV_API int hnswdev_graph_components(void *ctx, int layer, const uint32_t *live_
     CTX_OR_FAIL();
     return d->graph_info_layer("hnswdev_graph_components", layer) && d->graph_components(layer, live_bits, nbits, out_count) ? 0 : -1;
 }
-DEV_API int hnswdev_graph_info_counters(void *ctx, uint64_t out[4])
-{
-    CTX_OR_FAIL();
-    if (!out) return -1;
-    d->graph_info_counters(out);
-    return 0;
-}
 DEV_API int hnswdev_graph_reach_layer(void *ctx, int layer, const uint32_t *live_bits, long long nbits, const uint32_t *seed_bits, long long seed_nbits,
                                      uint32_t *out_reached_bits, int *out_hops, uint64_t out_summary[4])
 {
@@ -5164,26 +5100,12 @@ DEV_API int hnswdev_graph_reach(void *ctx, int entry_point, const uint32_t *live
     if (!d->graph_reach_top("hnswdev_graph_reach", entry_point, &top)) return -1;
     return d->graph_reach(entry_point, top, live_bits, nbits, min_layer, out_layers, cap, out_reached_bits, out_hops);
 }
-DEV_API int hnswdev_graph_reach_counters(void *ctx, uint64_t out[4])
-{
-    CTX_OR_FAIL();
-    if (!out) return -1;
-    d->graph_reach_counters(out);
-    return 0;
-}
 DEV_API int hnswdev_graph_repair_propose(void *ctx, int layer, const uint32_t *live_bits, long long nbits, const uint32_t *seed_bits, long long seed_nbits, int cands,
                                          int max_edges, int *out_n, int *out_ids, int *out_cands, int *out_codes, int cap)
 {
     CTX_OR_FAIL();
     if (!d->graph_info_layer("hnswdev_graph_repair_propose", layer)) return -1;
     return d->graph_repair_propose(layer, live_bits, nbits, seed_bits, seed_nbits, cands, max_edges, out_n, out_ids, out_cands, out_codes, cap);
-}
-DEV_API int hnswdev_graph_repair_counters(void *ctx, uint64_t out[4])
-{
-    CTX_OR_FAIL();
-    if (!out) return -1;
-    d->graph_repair_counters(out);
-    return 0;
 }
 DEV_API int hnswdev_range_results(void *ctx, int *out_ids, float *out_dists) { CTX_OR_FAIL(); return d->range_results(out_ids, out_dists) ? 0 : -1; }
 DEV_API int hnswdev_sync(void *ctx) { CTX_OR_FAIL(); return d->sync() ? 0 : -1; }
@@ -5196,6 +5118,17 @@ DEV_API int hnswdev_get_stats(void *ctx, hnswdev_stats *out)
     return 0;
 }
 DEV_API int hnswdev_reset_stats(void *ctx) { CTX_OR_FAIL(); d->reset_stats(); return 0; }
+// The getters of the counter blocks, hnswdev_<block>(ctx, out[slots]), one per row of counter_blocks.h
+#define HNSW_COUNTER_GETTER(NAME, SCOPE, ...)                   \
+    DEV_API int hnswdev_##NAME(void *ctx, uint64_t *out)        \
+    {                                                           \
+        CTX_OR_FAIL();                                          \
+        if (!out) return -1;                                    \
+        d->counters(hnsw::CounterBlock::NAME, out);             \
+        return 0;                                               \
+    }
+HNSW_FOR_EACH_COUNTER_BLOCK(HNSW_COUNTER_GETTER)
+#undef HNSW_COUNTER_GETTER
 static int copy_error(const std::string &s, char *buf, int buf_len)
 {
     if (buf && buf_len > 0) {

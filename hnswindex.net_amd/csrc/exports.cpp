@@ -195,14 +195,6 @@ API int hnsw_mi355x_exact_knn_query_by_id(void *handle, const int *ids, int coun
     if (static_cast<HnswIndex *>(handle)->exact_knn_query_by_id(ids, count, k, allow_bits, nbits, out_ids, out_dists, err) < 0) { set_error(err); return -1; }
     return 0;
 }
-// by-id calls, queries traversed on the device, hand-backs, queries scanned, rows gathered, pairs skipped as self
-API int hnsw_mi355x_by_id_info(void *h, uint64_t out[6])
-{
-    if (!h || !out) return -1;
-    LOCK_INDEX(h);
-    static_cast<HnswIndex *>(h)->by_id_info(out);
-    return 0;
-}
 
 // Exact k nearest neighbours with a candidate group per query: one scan for every group.  Exclusive, like the call above.
 API int hnsw_mi355x_exact_knn_query_grouped(void *handle, const float *vectors, int count, int dim, int k, const int *row_group, long long n_row_group,
@@ -734,76 +726,6 @@ API int hnsw_mi355x_row_prefilter_peek(void *h, int first_id, int count, uint64_
     if (!static_cast<HnswIndex *>(h)->row_prefilter_peek(first_id, count, out, rows, err)) { set_error(err); return -1; }
     return 0;
 }
-API int hnsw_mi355x_exact_range_info(void *h, uint64_t out[4])
-{
-    if (!h || !out) return -1;
-    LOCK_INDEX(h);
-    static_cast<HnswIndex *>(h)->exact_range_info(out);
-    return 0;
-}
-API int hnsw_mi355x_exact_range_grouped_info(void *h, uint64_t out[4])
-{
-    if (!h || !out) return -1;
-    LOCK_INDEX(h);
-    static_cast<HnswIndex *>(h)->exact_range_grouped_info(out);
-    return 0;
-}
-API int hnsw_mi355x_exact_collapsed_info(void *h, uint64_t out[4])
-{
-    if (!h || !out) return -1;
-    LOCK_INDEX(h);
-    static_cast<HnswIndex *>(h)->exact_collapsed_info(out);
-    return 0;
-}
-API int hnsw_mi355x_exact_grouped_info(void *h, uint64_t out[4])
-{
-    if (!h || !out) return -1;
-    LOCK_INDEX(h);
-    static_cast<HnswIndex *>(h)->exact_grouped_info(out);
-    return 0;
-}
-API int hnsw_mi355x_range_grouped_info(void *h, uint64_t out[4])
-{
-    if (!h || !out) return -1;
-    LOCK_INDEX(h);
-    static_cast<HnswIndex *>(h)->range_grouped_info(out);
-    return 0;
-}
-API int hnsw_mi355x_range_tagged_info(void *h, uint64_t out[6])
-{
-    if (!h || !out) return -1;
-    LOCK_INDEX(h);
-    static_cast<HnswIndex *>(h)->range_tagged_info(out);
-    return 0;
-}
-API int hnsw_mi355x_exact_range_tagged_info(void *h, uint64_t out[9])
-{
-    if (!h || !out) return -1;
-    LOCK_INDEX(h);
-    static_cast<HnswIndex *>(h)->exact_range_tagged_info(out);
-    return 0;
-}
-API int hnsw_mi355x_knn_grouped_info(void *h, uint64_t out[4])
-{
-    if (!h || !out) return -1;
-    LOCK_INDEX(h);
-    static_cast<HnswIndex *>(h)->knn_grouped_info(out);
-    return 0;
-}
-API int hnsw_mi355x_knn_tagged_info(void *h, uint64_t out[5])
-{
-    if (!h || !out) return -1;
-    LOCK_INDEX(h);
-    static_cast<HnswIndex *>(h)->knn_tagged_info(out);
-    return 0;
-}
-API int hnsw_mi355x_exact_tagged_info(void *h, uint64_t out[6])
-{
-    if (!h || !out) return -1;
-    LOCK_INDEX(h);
-    static_cast<HnswIndex *>(h)->exact_tagged_info(out);
-    return 0;
-}
 // HNSWIndex.GetInfo() / GetConnectedComponentCounts() (HNSWIndex.cs:192-205) from the graph mirror on the device:
 // top + 1, with min(cap, top + 1) entries written.  Exclusive: Add edits the mirror.
 API int hnsw_mi355x_get_info(void *h, hnsw_mi355x_layer_info *out, int cap)
@@ -825,13 +747,6 @@ API int hnsw_mi355x_connected_component_counts(void *h, int *out, int cap)
     const int n = static_cast<HnswIndex *>(h)->connected_component_counts(out, cap, err);
     if (n < 0) set_error(err);
     return n;
-}
-API int hnsw_mi355x_graph_info_counters(void *h, uint64_t out[4])
-{
-    if (!h || !out) return -1;
-    LOCK_INDEX(h);
-    static_cast<HnswIndex *>(h)->graph_info_counters(out);
-    return 0;
 }
 // Reachability from the entry point over out-edges on the graph mirror.  Exclusive, as hnsw_mi355x_get_info.
 API int hnsw_mi355x_reachability(void *h, hnsw_mi355x_layer_reach *out, int cap)
@@ -865,13 +780,6 @@ API int hnsw_mi355x_hop_counts(void *h, int layer, int *out, int cap)
     if (n < 0) set_error(err);
     return n;
 }
-API int hnsw_mi355x_graph_reach_counters(void *h, uint64_t out[4])
-{
-    if (!h || !out) return -1;
-    LOCK_INDEX(h);
-    static_cast<HnswIndex *>(h)->graph_reach_counters(out);
-    return 0;
-}
 // repair_reachability.  Exclusive, as hnsw_mi355x_remove: it edits lists.
 API int hnsw_mi355x_repair_reachability(void *h, int cands, int max_rounds, hnsw_mi355x_layer_repair *out, int cap)
 {
@@ -887,13 +795,6 @@ API int hnsw_mi355x_repair_reachability(void *h, int cands, int max_rounds, hnsw
     const int n = static_cast<HnswIndex *>(h)->repair_reachability(cands, max_rounds, out, cap, err);
     if (n < 0) set_error(err);
     return n;
-}
-API int hnsw_mi355x_graph_repair_counters(void *h, uint64_t out[4])
-{
-    if (!h || !out) return -1;
-    LOCK_INDEX(h);
-    static_cast<HnswIndex *>(h)->graph_repair_counters(out);
-    return 0;
 }
 API int hnsw_mi355x_dim(void *h)
 {
@@ -1041,6 +942,17 @@ API int hnsw_mi355x_get_stats_at(void *h, int context, hnswdev_stats *out)
     d->get_stats(out);
     return 0;
 }
+// The getters of the counter blocks, hnsw_mi355x_<block>(handle, out[slots]), one per row of counter_blocks.h
+#define HNSW_COUNTER_GETTER(NAME, SCOPE, ...)                                       \
+    API int hnsw_mi355x_##NAME(void *h, uint64_t *out)                              \
+    {                                                                               \
+        if (!h || !out) return -1;                                                  \
+        LOCK_INDEX(h);                                                              \
+        static_cast<HnswIndex *>(h)->counters(hnsw::CounterBlock::NAME, out);       \
+        return 0;                                                                   \
+    }
+HNSW_FOR_EACH_COUNTER_BLOCK(HNSW_COUNTER_GETTER)
+#undef HNSW_COUNTER_GETTER
 API int hnsw_mi355x_reset_stats(void *h)
 {
     if (!h) return -1;

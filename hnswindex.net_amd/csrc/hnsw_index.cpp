@@ -1807,15 +1807,16 @@ int HnswIndex::answer_by_class(int count, int k, int layer, long long n_lab, siz
         fallback, err);
 }
 
-// A per-context counter array of n <= 8 entries, fetched by get(device, one), summed over the contexts.
-template <class Get>
-void HnswIndex::sum_over_contexts(uint64_t *out, int n, Get get) const
+// A counter block (counter_blocks.h) as the index reports it: the primary context's, plus the replicas' where the table says `summed`.
+void HnswIndex::counters(CounterBlock b, uint64_t *out) const
 {
+    const int n = kCounterSlots[(int)b];
     std::fill(out, out + n, (uint64_t)0);
-    uint64_t one[8];
-    const auto add = [&](const Device &d) { get(d, one); for (int i = 0; i < n; ++i) out[i] += one[i]; };
+    uint64_t one[kMaxCounterSlots];
+    const auto add = [&](const Device &d) { d.counters(b, one); for (int i = 0; i < n; ++i) out[i] += one[i]; };
     if (dev_) add(*dev_);
-    for (const auto &r : replicas_) add(*r);
+    if (kCounterScope[(int)b] == CounterScope::summed)
+        for (const auto &r : replicas_) add(*r);
 }
 
 // KnnQuery with a group filter per query: knn_query_general's filtered call for every group at once.  The labels go
@@ -1845,11 +1846,6 @@ int HnswIndex::knn_query_grouped(const float *queries, int count, int dim, int k
             return ctx->search_grouped(cnt, ep, top, ef, k, row_group, n_lab, query_group + lo, n_groups, ids, dists, flag, layer);
         },
         "search_grouped failed", out_ids, out_dists, err);
-}
-
-void HnswIndex::knn_grouped_info(uint64_t out[4]) const
-{
-    sum_over_contexts(out, 4, [](const Device &d, uint64_t *one) { d.knn_grouped_info(one); });
 }
 
 // The tagged calls' argument rules (tag_args_error, device_backend.h) as the ABI reports a breach: `who` is the ABI call.
@@ -1902,11 +1898,6 @@ int HnswIndex::knn_query_tagged(const float *queries, int count, int dim, int k,
             return ctx->search_tagged(cnt, ep, top, ef, k, row_tags, n_lab, query_tags + lo, match, ids, dists, flag, layer);
         },
         "search_tagged failed", out_ids, out_dists, err);
-}
-
-void HnswIndex::knn_tagged_info(uint64_t out[5]) const
-{
-    sum_over_contexts(out, 5, [](const Device &d, uint64_t *one) { d.knn_tagged_info(one); });
 }
 
 // ---- query by stored id ------------------------------------------------------------------------------------
@@ -1977,11 +1968,6 @@ int HnswIndex::exact_knn_query_by_id(const int *ids, int count, int k, const uin
     const long long length = exact_candidates(allow_bits, nbits, live);
     if (!dev_->exact_knn_by_id(ids, count, length, k, allow_bits, nbits, out_ids, out_dists)) { err = get_dev_error(); return -1; }
     return 0;
-}
-
-void HnswIndex::by_id_info(uint64_t out[6]) const
-{
-    sum_over_contexts(out, 6, [](const Device &d, uint64_t *one) { d.by_id_info(one); });
 }
 
 // The candidates of a flat scan as Device::exact_knn / exact_range take them: the row count, and allow_bits / nbits replaced by

@@ -67,12 +67,10 @@ public:
     // query i's candidates are the live ids j < n_row_group with row_group[j] == query_group[i].
     int exact_knn_query_grouped(const float *queries, int count, int dim, int k, const int *row_group, long long n_row_group, const int *query_group,
                                 int n_groups, int *out_ids, float *out_dists, std::string &err);
-    void exact_grouped_info(uint64_t out[4]) const { if (dev_) dev_->exact_grouped_info(out); else out[0] = out[1] = out[2] = out[3] = 0; }
     // hnsw_mi355x_exact_knn_query_collapsed: exact_knn_query's candidates, at most per_group results per label
     // row_group[id] (Device::exact_knn_collapsed).  row_group must cover the index's length.
     int exact_knn_query_collapsed(const float *queries, int count, int dim, int k, const int *row_group, long long n_row_group, int per_group,
                                   const uint32_t *allow_bits, long long nbits, int *out_ids, float *out_dists, std::string &err);
-    void exact_collapsed_info(uint64_t out[4]) const { if (dev_) dev_->exact_collapsed_info(out); else out[0] = out[1] = out[2] = out[3] = 0; }
     // hnsw_mi355x_knn_query_collapsed: per query the first k survivors of the collapse walk over the row that
     // knn_query_general(queries, beam, layer, allow) returns -- the same traversal, through answer_resident; on the device the rows are
     // collapsed before the copy-out (Device::search_collapsed), a host answer is walked by collapse_host_row.
@@ -82,7 +80,6 @@ public:
     // candidates are the live ids j < n_row_tags whose word row_tags[j] matches query_tags[i] under `match` (0 any, 1 all).  0 or -1.
     int exact_knn_query_tagged(const float *queries, int count, int dim, int k, const uint32_t *row_tags, long long n_row_tags, const uint32_t *query_tags,
                                int match, int *out_ids, float *out_dists, std::string &err);
-    void exact_tagged_info(uint64_t out[6]) const { for (int i = 0; i < 6; ++i) out[i] = 0; if (dev_) dev_->exact_tagged_info(out); }
     // ---- query by stored id.  Every id must be live: otherwise -1 with a message that names the first that is not,
     // before anything is launched.
     // hnsw_mi355x_get_vectors: out[i] = the stored row ids[i] as dim floats (Device::gather_rows: hnswdev_download_rows' values).
@@ -95,19 +92,14 @@ public:
     // hnsw_mi355x_exact_knn_query_by_id: row i is exact_knn_query's for that vector with allow_bits (nullptr: every live id) minus
     // ids[i] as the candidates (Device::exact_knn_by_id).  Runs on the primary context; the resident set stays what it was.
     int exact_knn_query_by_id(const int *ids, int count, int k, const uint32_t *allow_bits, long long nbits, int *out_ids, float *out_dists, std::string &err);
-    // Device::by_id_info summed over the contexts
-    void by_id_info(uint64_t out[6]) const;
     // hnsw_mi355x_exact_range_query_grouped: exact_range_query with exact_knn_query_grouped's group per query
     // (Device::exact_range_grouped); the labels of vacant slots are taken out as for that call
     int exact_range_query_grouped(const float *queries, int count, int dim, float range, const int *row_group, long long n_row_group, const int *query_group,
                                   int n_groups, int *counts, std::vector<int> &ids, std::vector<float> &dists, std::string &err);
-    void exact_range_grouped_info(uint64_t out[4]) const { if (dev_) dev_->exact_range_grouped_info(out); else out[0] = out[1] = out[2] = out[3] = 0; }
     // hnsw_mi355x_exact_range_query_tagged: exact_range_query with exact_knn_query_tagged's tag mask per query
     // (Device::exact_range_tagged); the words of vacant slots are taken out as for that call
     int exact_range_query_tagged(const float *queries, int count, int dim, float range, const uint32_t *row_tags, long long n_row_tags,
                                  const uint32_t *query_tags, int match, int *counts, std::vector<int> &ids, std::vector<float> &dists, std::string &err);
-    void exact_range_tagged_info(uint64_t out[9]) const { for (int i = 0; i < 9; ++i) out[i] = 0; if (dev_) dev_->exact_range_tagged_info(out); }
-    void exact_range_info(uint64_t out[4]) const { if (dev_) dev_->exact_range_info(out); else out[0] = out[1] = out[2] = out[3] = 0; }
     // hnsw_mi355x_get_info / hnsw_mi355x_connected_component_counts: HNSWIndex.GetInfo() / GetConnectedComponentCounts() for the
     // layers 0 .. top, computed by the primary context from the graph mirror (Device::graph_info / graph_components)
     // whatever device_traversal says.  The mirror is brought up to date first (sync_graph); when it is current the adjacency lists
@@ -115,7 +107,6 @@ public:
     // entries, or -1; an index with no live item: get_info -1 (the reference's IndexOutOfRangeException), the counts 0.
     int get_info(hnsw_mi355x_layer_info *out, int cap, std::string &err);
     int connected_component_counts(int *out, int cap, std::string &err);
-    void graph_info_counters(uint64_t out[4]) const { if (dev_) dev_->graph_info_counters(out); else out[0] = out[1] = out[2] = out[3] = 0; }
     // hnsw_mi355x_reachability / _unreachable_ids / _hop_counts: the chain of out-edge reachability from the entry
     // point (Device::graph_reach) down to layer 0, or down to `layer`.  Locking, sync_graph, the live set and "always on the device,
     // on the primary context" are connected_component_counts'.  reachability: top + 1 with min(cap, top + 1) entries written.
@@ -124,7 +115,6 @@ public:
     int reachability(hnsw_mi355x_layer_reach *out, int cap, std::string &err);
     int unreachable_ids(int layer, std::vector<int> &ids, std::string &err);
     int hop_counts(int layer, int *out, int cap, std::string &err);
-    void graph_reach_counters(uint64_t out[4]) const { if (dev_) dev_->graph_reach_counters(out); else out[0] = out[1] = out[2] = out[3] = 0; }
     // hnsw_mi355x_repair_reachability: links the members that reachability() reports as lost into the lists of their
     // nearest reached members, layer by layer from the top, at most max_rounds rounds per layer.  Locking, sync_graph, the live set
     // and "always on the device, on the primary context" are reachability's; the host lists are fetched first where the mirror is
@@ -132,7 +122,6 @@ public:
     // clone again, the in-edge sets are rebuilt by the next Remove.  top + 1 with min(cap, top + 1) entries written; an empty index: 0;
     // -1 on error, and once a list has been patched a device failure fails the index as a failed Remove does.
     int repair_reachability(int cands, int max_rounds, hnsw_mi355x_layer_repair *out, int cap, std::string &err);
-    void graph_repair_counters(uint64_t out[4]) const { if (dev_) dev_->graph_repair_counters(out); else out[0] = out[1] = out[2] = out[3] = 0; }
     int knn_query_general(const float *queries, int count, int dim, int k, int layer, const uint32_t *allow_bits, long long nbits, int *out_ids,
                           float *out_dists, std::string &err);
     // hnsw_mi355x_knn_query_grouped: KnnQuery on `layer` with a group filter per query -- query i is answered from the
@@ -141,8 +130,6 @@ public:
     // the traversal does not run on the device, go the lock-step way once per group.  Exclusive lock.  0 or -1.
     int knn_query_grouped(const float *queries, int count, int dim, int k, int layer, const int *row_group, long long n_row_group, const int *query_group,
                           int n_groups, int *out_ids, float *out_dists, std::string &err);
-    // Device::knn_grouped_info summed over the contexts
-    void knn_grouped_info(uint64_t out[4]) const;
     // hnsw_mi355x_knn_query_tagged: KnnQuery on `layer` with a tag mask per query -- query i is answered from the ids
     // j < n_row_tags whose word row_tags[j] matches query_tags[i] under `match` (0 any, 1 all), byte for byte what knn_query_general
     // returns for it with those ids as the allow-set.  One device traversal for every mask (Device::search_tagged); jobs handed back,
@@ -150,8 +137,6 @@ public:
     // lock.  0 or -1.
     int knn_query_tagged(const float *queries, int count, int dim, int k, int layer, const uint32_t *row_tags, long long n_row_tags, const uint32_t *query_tags,
                          int match, int *out_ids, float *out_dists, std::string &err);
-    // Device::knn_tagged_info summed over the contexts
-    void knn_tagged_info(uint64_t out[5]) const;
     // hnsw_mi355x_multilayer_knn_query: the number of layer slots (min(top, max_layer) + 1; 0 for an empty index, k < 1 or
     // max_layer == -1), or -1.  out_*: [count][layers_cap][k - 1].  Exclusive lock.
     int multilayer_knn_query(const float *queries, int count, int dim, int k, int max_layer, int min_layer, int layers_cap, int *out_ids,
@@ -178,7 +163,6 @@ public:
     // A query whose group holds no graph id is answered with an empty list without a traversal when range >= 0.  Exclusive lock.
     int range_query_grouped(const float *queries, int count, int dim, float range, int layer, const int *row_group, long long n_row_group,
                             const int *query_group, int n_groups, std::vector<std::vector<NodeDist>> &out, std::string &err);
-    void range_grouped_info(uint64_t out[4]) const { if (dev_) dev_->range_grouped_info(out); else out[0] = out[1] = out[2] = out[3] = 0; }
     // hnsw_mi355x_range_query_tagged: RangeQuery on `layer` with a tag mask per query -- query i's list is byte for
     // byte what range_query returns for it with the ids j < n_row_tags whose word row_tags[j] matches query_tags[i] under `match`
     // (0 any, 1 all) as the allow-set; the empty-heap rule fails the whole call as there.  One device traversal for every mask
@@ -187,7 +171,6 @@ public:
     // empty list without a traversal when range >= 0.  Primary context only.  Exclusive lock.
     int range_query_tagged(const float *queries, int count, int dim, float range, int layer, const uint32_t *row_tags, long long n_row_tags,
                            const uint32_t *query_tags, int match, std::vector<std::vector<NodeDist>> &out, std::string &err);
-    void range_tagged_info(uint64_t out[6]) const { for (int i = 0; i < 6; ++i) out[i] = 0; if (dev_) dev_->range_tagged_info(out); }
 
     // hnsw_remove (HNSWIndex.Remove, src/HNSWIndex/HNSWIndex.cs:83-102), ids in order.
     int remove(const int *ids, int count, std::string &err);
@@ -218,6 +201,9 @@ public:
     // container host that wants that bound passes it to hnsw_mi355x_set_insert_batch itself.)
     static int host_parallelism();
     int insert_batch_cap() const { return p_.insert_batch == 0 ? host_parallelism() : p_.insert_batch; }
+    // hnsw_mi355x_<block>: a counter block of counter_blocks.h, out[kCounterSlots of it] -- the primary context's values, plus every
+    // replica's where the table says `summed`; all zero before a context exists
+    void counters(CounterBlock b, uint64_t *out) const;
     void exact_window_stats(uint64_t out[4]) const { out[0] = xw_rounds_; out[1] = xw_searches_; out[2] = xw_alone_; out[3] = xw_linked_; }
     void row_prefilter_stats(uint64_t out[4]); // the primary context's (its views add to it) plus every replica's
     void row_prefilter_form_stats(uint64_t out[2]); // summed the same way
@@ -312,7 +298,7 @@ private:
     // every KnnQuery form over the resident set: on the device, one launch per context, or on the host, hand-backs included (hnsw_index.cpp)
     template <class OnDevice, class OnHost>
     int answer_resident(int count, int ef, OnDevice on_device, OnHost on_host, const char *fallback, std::string &err);
-    // what knn_query_grouped / knn_query_tagged share: the prologue, the lock-step way class by class, the answer_resident call, the counter sums
+    // what knn_query_grouped / knn_query_tagged share: the prologue, the lock-step way class by class, the answer_resident call
     template <class ArgsOk>
     int predicate_query_begin(const char *who, int count, int k, int layer, int *out_ids, float *out_dists, std::string &err, ArgsOk args_ok);
     template <class ClassOf, class Matches>
@@ -321,7 +307,6 @@ private:
     template <class Search, class ClassOf, class Matches>
     int answer_by_class(int count, int k, int layer, long long n_lab, size_t n_classes, ClassOf class_of, Matches matches, Search search, const char *fallback,
                         int *out_ids, float *out_dists, std::string &err);
-    template <class Get> void sum_over_contexts(uint64_t *out, int n, Get get) const;
     // exclude: nullptr, or per resident query the id that is no result of it (knn_query_by_id: the query's own)
     int knn_query_lockstep(const int *which, int count, int k, int *out_ids, float *out_dists, std::string &err, AllowBits allow = AllowBits{},
                            int layer = 0, const int *exclude = nullptr);
