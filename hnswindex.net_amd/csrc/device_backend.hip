@@ -1122,6 +1122,14 @@ static int cand_lds_cap(int k, int dim, bool heur, int nbcap)
     while (cap > 64 && search_lds_bytes(k, cap, dim, heur, nbcap) > 64 * 1024) cap /= 2;
     return cap;
 }
+// The LDS of a link launch (link_lds_bytes, dk_search_common.h), or 0 with the error set where it exceeds the budget: that launch
+// is not made.  (Device::traversal_fits keeps Add away from such shapes; this is the guard of the launch itself.)
+static size_t link_lds_or_error(const char *who, int pitch, int nbcap)
+{
+    const size_t lds = link_lds_bytes(pitch, nbcap);
+    if (lds > 64 * 1024) { set_dev_error(std::string(who) + ": row length / list length exceed the LDS budget of the link launch"); return 0; }
+    return lds;
+}
 static int spill_cap_for_tests()
 {
     const int c = diag("spill_cap", -1);
@@ -1413,6 +1421,8 @@ bool Device::insert_search_batch(const SearchJob *jobs, int njobs, int k, int ma
     const int cand_cap = cand_lds_cap(k, pitch_, true, nbcap());
     const size_t lds = search_lds_bytes(k, cand_cap, pitch_, true, nbcap());
     if (lds > 64 * 1024) { set_dev_error("insert_search_batch: beam width / dimension exceed the LDS budget"); return false; }
+    const size_t lds_link = windowed ? link_lds_or_error("insert_search_batch", pitch_, nbcap()) : 0; // the window's dry-run link launch
+    if (windowed && !lds_link) return false;
     if (!bind()) return false;
     hipStream_t st = S(stream_);
     const int sel_stride = max_edges0;
@@ -1494,7 +1504,6 @@ bool Device::insert_search_batch(const SearchJob *jobs, int njobs, int k, int ma
             }
             HIP_OK(hipMemsetAsync(d_dry0, 0xff, b_dry, st)); // every code "changed, set of lost ids unknown" unless the kernel says otherwise
             const int k_cap = nbcap();
-            const size_t lds_link = ((search_lds_bytes(k_cap, 0, pitch_, true, nbcap()) + 15) & ~(size_t)15) + 4u * (size_t)(kNewMax + 1) * nbcap();
             const int grid = (njobs + n_upper) * sel_stride;
             with_metric(metric_, [&](auto m) {
                 hipLaunchKernelGGL(graph_link_dry_sel_kernel<m>, dim3(grid), dim3(64), lds_link, st, d_rows_, d_row_sn_, pitch_, g_adj0_, g_stride0_,
@@ -1553,7 +1562,9 @@ bool Device::traversal_fits(int k, bool with_heuristic, int max_edges) const
     if (k < 1 || 2 * max_edges + 1 > 128) return false;
     const int nb = std::max(8, (2 * max_edges + 1 + 7) & ~7);
     const int cap = cand_lds_cap(k, pitch_, with_heuristic, nb);
-    return search_lds_bytes(k, cap, pitch_, with_heuristic, nb) <= 64 * 1024 && search_lds_bytes(nb, 0, pitch_, true, nb) <= 64 * 1024;
+    // with_heuristic: Add, whose selections the link launches apply -- their LDS is the relink's plus the shortcut's scratch
+    const bool link_ok = !with_heuristic || link_lds_bytes(pitch_, nb) <= 64 * 1024;
+    return search_lds_bytes(k, cap, pitch_, with_heuristic, nb) <= 64 * 1024 && search_lds_bytes(nb, 0, pitch_, true, nb) <= 64 * 1024 && link_ok;
 }
 
 bool Device::graph_append_nodes(long long first, long long n, const int *level, const int64_t *upper, const int *pool,
@@ -1611,6 +1622,8 @@ bool Device::link_batch_begin(int set, const int *rows, int nrows, int row_strid
     for (int t = 0; t < total; ++t)
         if (g_items[t] < 0 || g_items[t] >= g_n_) { set_dev_error("link_batch: item outside the graph"); return false; }
     if (list_stride < max_edges0 + 1 || max_edges0 + 1 > nbcap()) { set_dev_error("link_batch: list stride too small"); return false; }
+    const size_t lds = ngroups > 0 ? link_lds_or_error("link_batch", pitch_, nbcap()) : 0;
+    if (ngroups > 0 && !lds) return false;
     if (!bind()) return false;
     hipStream_t st = S(stream_);
     if (!ensure_search_scratch(1, 1, 0, 16)) return false;
@@ -1652,7 +1665,6 @@ bool Device::link_batch_begin(int set, const int *rows, int nrows, int row_strid
         ls.timed = profiling_;
         if (ls.timed) HIP_OK(hipEventRecord(E(ls.ev_start), st));
         const int k_cap = nbcap();
-        const size_t lds = ((search_lds_bytes(k_cap, 0, pitch_, true, nbcap()) + 15) & ~(size_t)15) + 4u * (size_t)(kNewMax + 1) * nbcap();
         with_metric(metric_, [&](auto m) {
             hipLaunchKernelGGL(graph_link_kernel<m>, dim3(ngroups), dim3(64), lds, st, d_rows_, d_row_sn_, pitch_, g_adj0_, g_stride0_, g_upper_, g_pool_,
                                g_strideU_, s_lk_[1], s_lk_[1] + ngroups, s_lk_[2], (const int *)nullptr, s_lk_[3], max_edges0, k_cap, s_lk_[4], list_stride,
@@ -1673,6 +1685,8 @@ bool Device::link_dry_run(const int *jobs3, int n, int max_edges0, int *changed)
     if (n <= 0) return true;
     if (!jobs3 || !changed || max_edges0 + 1 > nbcap()) { set_dev_error("link_dry_run: bad argument"); return false; }
     if (g_n_ <= 0) { set_dev_error("link_dry_run: no graph uploaded"); return false; }
+    const size_t lds = link_lds_or_error("link_dry_run", pitch_, nbcap());
+    if (!lds) return false;
     for (int i = 0; i < n; ++i) { // a bad id must be an error return, never a GPU fault
         const int nb = jobs3[3 * i], layer = jobs3[3 * i + 1], item = jobs3[3 * i + 2];
         if (nb < 0 || nb >= g_n_ || item < 0 || item >= g_n_ || layer < 0) { set_dev_error("link_dry_run: job outside the graph"); return false; }
@@ -1688,7 +1702,6 @@ bool Device::link_dry_run(const int *jobs3, int n, int max_edges0, int *changed)
     HIP_OK(hipMemcpyAsync(s_dry_, h, sizeof(int) * (size_t)n * 3, hipMemcpyHostToDevice, st));
     HIP_OK(hipMemsetAsync(s_evals_, 0, sizeof(unsigned long long), st));
     const int k_cap = nbcap();
-    const size_t lds = ((search_lds_bytes(k_cap, 0, pitch_, true, nbcap()) + 15) & ~(size_t)15) + 4u * (size_t)(kNewMax + 1) * nbcap();
     with_metric(metric_, [&](auto m) {
         hipLaunchKernelGGL(graph_link_dry_kernel<m>, dim3(n), dim3(64), lds, st, d_rows_, d_row_sn_, pitch_, g_adj0_, g_stride0_, g_upper_, g_pool_,
                            g_strideU_, s_dry_, max_edges0, k_cap, s_dry_ + (size_t)n * 3, s_evals_, nbcap(), g_tested0_, g_testedU_);
@@ -1711,6 +1724,8 @@ bool Device::link_batch_planned(int njobs, int n_upper, int max_edges0)
         set_dev_error("link_batch_planned: no matching insert_search_batch results on the device");
         return false;
     }
+    const size_t lds = link_lds_or_error("link_batch_planned", pitch_, nbcap());
+    if (!lds) return false;
     last_insert_jobs_ = 0;
     if (!bind()) return false;
     hipStream_t st = S(stream_);
@@ -1767,7 +1782,6 @@ bool Device::link_batch_planned(int njobs, int n_upper, int max_edges0)
         hipLaunchKernelGGL(link_order_kernel, dim3(G), dim3(64), 0, st, s_jobs_, g_upper_, g_strideU_, lp_grp_[5], P, bounded ? 1 : 0);
         HIP_OK(hipGetLastError());
         const int k_cap = nbcap();
-        const size_t lds = ((search_lds_bytes(k_cap, 0, pitch_, true, nbcap()) + 15) & ~(size_t)15) + 4u * (size_t)(kNewMax + 1) * nbcap();
         with_metric(metric_, [&](auto m) {
             hipLaunchKernelGGL(graph_link_kernel<m>, dim3(G), dim3(64), lds, st, d_rows_, d_row_sn_, pitch_, g_adj0_, g_stride0_, g_upper_, g_pool_,
                                g_strideU_, lp_grp_[0], lp_grp_[1], lp_grp_[2], lp_grp_[3], lp_grp_[5], max_edges0, k_cap, (int *)nullptr, 0, s_evals_,

@@ -27,6 +27,14 @@ __host__ __device__ inline size_t search_lds_bytes(int k, int cand_cap, int dim,
     if (heur) b += 2u * sizeof(float) * (size_t)((dim + 3) & ~3) + 4u * (size_t)nbcap + 4u * 3u * 40u;
     return b;
 }
+// LDS of a link launch (graph_link_kernel and its dry-run forms, dk_link.h): the carve-up for a list of nbcap entries with the
+// heuristic's regions, and behind it the shortcut's scratch -- kNewMax rows of nbcap distances and one of nbcap ranks.  THE one
+// place that sizes it: every link launch asks for this amount (and refuses above 64 KB), and Device::traversal_fits admits a
+// shape for Add only where it fits.
+__host__ __device__ inline size_t link_lds_bytes(int dim, int nbcap)
+{
+    return ((search_lds_bytes(nbcap, 0, dim, true, nbcap) + 15u) & ~(size_t)15u) + 4u * (size_t)(kNewMax + 1) * (size_t)nbcap;
+}
 __device__ __forceinline__ SearchLds carve_lds(unsigned char *smem, int k, int cand_cap, int dim, int nbcap)
 {
     SearchLds L;
