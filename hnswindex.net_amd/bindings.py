@@ -145,6 +145,12 @@ lib.hnsw_mi355x_knn_query_by_id.restype = ct.c_int
 lib.hnsw_mi355x_knn_query_by_id.argtypes = [ct.c_void_p, _I, ct.c_int, ct.c_int, ct.c_int, _I, _F]
 lib.hnsw_mi355x_exact_knn_query_by_id.restype = ct.c_int
 lib.hnsw_mi355x_exact_knn_query_by_id.argtypes = [ct.c_void_p, _I, ct.c_int, ct.c_int, _U32, ct.c_longlong, _I, _F]
+lib.hnsw_mi355x_exact_range_query_by_id.restype = ct.c_int
+lib.hnsw_mi355x_exact_range_query_by_id.argtypes = [ct.c_void_p, _I, ct.c_int, ct.c_float, _U32, ct.c_longlong, ct.POINTER(ct.c_void_p),
+                                                    ct.POINTER(ct.c_void_p), _I]
+lib.hnsw_mi355x_duplicate_groups.restype = ct.c_int
+lib.hnsw_mi355x_duplicate_groups.argtypes = [ct.c_void_p, ct.c_float, _U32, ct.c_longlong, _I, ct.c_longlong, ct.POINTER(ct.c_uint64)]
+_GROUPS_INFO = ("members", "groups", "pairs_within", "pairs_measured")   # out_info[0 .. 3] of hnsw_mi355x_duplicate_groups
 lib.hnsw_mi355x_knn_query_grouped.restype = ct.c_int
 lib.hnsw_mi355x_knn_query_grouped.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_int, ct.c_int, ct.c_int, _I, ct.c_longlong, _I, ct.c_int, _I, _F]
 lib.hnsw_mi355x_range_query_grouped.restype = ct.c_int
@@ -309,6 +315,10 @@ lib.hnswdev_knn_search_by_id.restype = ct.c_int
 lib.hnswdev_knn_search_by_id.argtypes = [ct.c_void_p, _I, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int, _I, _F, _I]
 lib.hnswdev_exact_knn_by_id.restype = ct.c_int
 lib.hnswdev_exact_knn_by_id.argtypes = [ct.c_void_p, _I, ct.c_int, ct.c_longlong, ct.c_int, _U32, ct.c_longlong, _I, _F]
+lib.hnswdev_exact_range_by_id.restype = ct.c_int
+lib.hnswdev_exact_range_by_id.argtypes = [ct.c_void_p, _I, ct.c_int, ct.c_longlong, ct.c_float, _U32, ct.c_longlong, _I]
+lib.hnswdev_exact_range_groups.restype = ct.c_int
+lib.hnswdev_exact_range_groups.argtypes = [ct.c_void_p, ct.c_longlong, ct.c_float, _U32, ct.c_longlong, _I, ct.POINTER(ct.c_uint64)]
 lib.hnswdev_tag_list_ms.restype = ct.c_int
 lib.hnswdev_tag_list_ms.argtypes = [ct.c_void_p, ct.POINTER(ct.c_double)]
 lib.hnswdev_knn_search_grouped.restype = ct.c_int
@@ -951,6 +961,60 @@ class Index:
             out_ids[lo:lo + _BY_ID_CHUNK], dists[lo:lo + _BY_ID_CHUNK] = self.exact_knn_query_by_id(a[lo:lo + _BY_ID_CHUNK], k)
         return out_ids, dists
 
+    # ---- near-duplicates of stored items ----
+    def exact_range_query_by_id(self, ids, radius: float,
+                                allowed=None) -> Tuple[List[npt.NDArray[np.int32]], List[npt.NDArray[np.float32]]]:
+        """"Which stored items lie within `radius` of item i": exact_range_query for the stored rows of `ids`
+        (hnsw_mi355x_exact_range_query_by_id).  List i is byte for byte
+        exact_range_query(get_vectors([ids[i]]), radius, allowed=<allowed, or every live id, minus ids[i]>): ascending by (distance, id);
+        a duplicate of the row under another id is an ordinary result.  ids may repeat and come in any order; one that is not live:
+        RuntimeError naming it."""
+        a = self._by_id_list(ids, "hnsw_mi355x_exact_range_query_by_id")
+        n = int(a.size)
+        ids_pp = (ct.c_void_p * max(n, 1))()
+        dists_pp = (ct.c_void_p * max(n, 1))()
+        counts = (ct.c_int * max(n, 1))()
+        words, nbits = allow_bits(allowed) if allowed is not None else (None, 0)
+        words, wp = _words_arg(words) if allowed is not None else (None, None)
+        if n and lib.hnsw_mi355x_exact_range_query_by_id(self._h, a.ctypes.data_as(_I), n, radius, wp, nbits, ids_pp, dists_pp, counts) < 0:
+            raise RuntimeError(last_error())
+        out_ids, dists = [], []
+        try:
+            for i in range(n):
+                m = counts[i]
+                out_ids.append(np.ctypeslib.as_array(ct.cast(ids_pp[i], _I), shape=(m,)).copy() if m else np.empty(0, dtype=np.int32))
+                dists.append(np.ctypeslib.as_array(ct.cast(dists_pp[i], _F), shape=(m,)).copy() if m else np.empty(0, dtype=np.float32))
+        finally:
+            if n:
+                lib.hnsw_free_results(ids_pp, dists_pp, n)
+        return out_ids, dists
+
+    def exact_radius_graph(self, radius: float, ids=None) -> Tuple[List[npt.NDArray[np.int32]], List[npt.NDArray[np.float32]]]:
+        """The exact radius graph of the index: exact_range_query_by_id over `ids` (None: every live id ascending), the lists
+        concatenated.  List i never holds ids[i].  The ids go down in pieces of 65 536, as exact_knn_graph's."""
+        a = np.sort(self.ids()) if ids is None else _id_list(ids)
+        out_ids, dists = [], []
+        for lo in range(0, a.size, _BY_ID_CHUNK):
+            got_ids, got_d = self.exact_range_query_by_id(a[lo:lo + _BY_ID_CHUNK], radius)
+            out_ids += got_ids
+            dists += got_d
+        return out_ids, dists
+
+    def duplicate_groups(self, radius: float, allowed=None) -> Tuple[npt.NDArray[np.int32], dict]:
+        """Groups of near-duplicates (hnsw_mi355x_duplicate_groups): (int32[length], info).  The members are the live ids `allowed`
+        allows (None: every live id); members a < b are joined when the distance from the stored row of a, taken as the query, to
+        row b is <= radius, and the groups are the connected components.  labels[v]: the smallest member id of v's group, -1 where v
+        is no member.  info: members, groups, pairs_within (a < b within the radius), pairs_measured (= m (m - 1) / 2).  One scan on
+        the device with a union-find as its sink: no list is built or copied."""
+        n = int(self.length)
+        labels = np.full(n, -1, dtype=np.int32)
+        info = (ct.c_uint64 * 4)()
+        words, nbits = allow_bits(allowed) if allowed is not None else (None, 0)
+        words, wp = _words_arg(words) if allowed is not None else (None, None)
+        if self._h and lib.hnsw_mi355x_duplicate_groups(self._h, radius, wp, nbits, labels.ctypes.data_as(_I), n, info) < 0:
+            raise RuntimeError(last_error())
+        return labels, {name: int(info[i]) for i, name in enumerate(_GROUPS_INFO)}
+
     def exact_range_query(self, queries: npt.ArrayLike, radius: float,
                           allowed=None) -> Tuple[List[npt.NDArray[np.int32]], List[npt.NDArray[np.float32]]]:
         """Per query every live (and, with `allowed`, allowed) id whose distance is <= radius, ascending by (distance, id), from
@@ -1399,6 +1463,35 @@ class DeviceBackend:
         self._check(lib.hnswdev_exact_knn_by_id(self._ctx, a.ctypes.data_as(_I), a.size, (1 << 62) if n_rows is None else int(n_rows), int(k), wp, nbits,
                                                 out_ids.ctypes.data_as(_I), d.ctypes.data_as(_F)))
         return out_ids, d
+
+    def exact_range_by_id(self, ids, radius: float, n_rows=None, allowed=None):
+        """hnswdev_exact_range_by_id: exact_range whose query i is the uploaded row ids[i] and whose candidates are exact_range's
+        minus ids[i].  (list of ids, list of dists)."""
+        a = _id_list(ids)
+        if a.size == 0:
+            return [], []
+        counts = np.zeros(a.size, dtype=np.int32)
+        words, nbits = allow_bits(allowed) if allowed is not None else (None, 0)
+        words, wp = _words_arg(words) if allowed is not None else (None, None)
+        self._check(lib.hnswdev_exact_range_by_id(self._ctx, a.ctypes.data_as(_I), a.size, (1 << 62) if n_rows is None else int(n_rows), float(radius), wp,
+                                                  nbits, counts.ctypes.data_as(_I)))
+        counts = counts[:a.size]
+        total = int(counts.sum(dtype=np.int64))
+        out_ids = np.empty(max(total, 1), dtype=np.int32)
+        d = np.empty(max(total, 1), dtype=np.float32)
+        self._check(lib.hnswdev_exact_range_results(self._ctx, out_ids.ctypes.data_as(_I), d.ctypes.data_as(_F)))
+        cuts = np.cumsum(counts, dtype=np.int64)[:-1]
+        return np.split(out_ids[:total], cuts), np.split(d[:total], cuts)
+
+    def exact_range_groups(self, radius: float, n_rows: int, allowed=None):
+        """hnswdev_exact_range_groups: (int32[n_rows] labels, info dict) -- the single-linkage groups of the uploaded rows of
+        [0, n_rows) that `allowed` allows, as Index.duplicate_groups returns them; an id that is no uploaded row is no member (-1)."""
+        labels = np.full(int(n_rows), -1, dtype=np.int32)
+        info = (ct.c_uint64 * 4)()
+        words, nbits = allow_bits(allowed) if allowed is not None else (None, 0)
+        words, wp = _words_arg(words) if allowed is not None else (None, None)
+        self._check(lib.hnswdev_exact_range_groups(self._ctx, int(n_rows), float(radius), wp, nbits, labels.ctypes.data_as(_I), info))
+        return labels, {name: int(info[i]) for i, name in enumerate(_GROUPS_INFO)}
 
     def set_queries(self, queries):
         """Uploads the query set of a batch of searches once; records name queries by row index."""

@@ -478,6 +478,18 @@ public:
     bool exact_range(const float *queries, int nq, long long n_rows, float range, const uint32_t *allow_bits, long long nbits, int *out_counts);
     bool exact_range_results(int *out_ids, float *out_d);
     size_t exact_range_total() const { return xr_ids_.size(); }
+    // hnswdev_exact_range_by_id: exact_range whose query i is the stored row ids[i] -- gathered into the scan's own
+    // query buffer as exact_knn_by_id gathers it, the resident set untouched -- and whose candidates are exact_range's minus ids[i]
+    // (exact_scan_kernel<M, ExactRangeSelf>: the pair is not counted in exact_evals).  Rounds, capacities, the repeated pass, the sort
+    // limit and exact_range_results are exact_range's.  An id outside the uploaded rows is an error, in front of any launch.
+    bool exact_range_by_id(const int *ids, int nq, long long n_rows, float range, const uint32_t *allow_bits, long long nbits, int *out_counts);
+    // hnswdev_exact_range_groups: the single-linkage groups of the MEMBERS -- exact_range's candidates, ascending.
+    // a < b are joined when the distance with the stored row of a as the query (handled as exact_range_by_id handles it) and row b as
+    // the candidate is <= range; out_labels[v] for v in [0, min(n_rows, uploaded)): the smallest member of v's group, -1 where v is
+    // no member.  out_info: [members, groups, pairs a < b within the range, pairs measured = m (m - 1) / 2].  One scan with a
+    // union-find as its sink (exact_scan_kernel<M, ExactRangeUnion>): no list is kept or copied.  Fewer than two members: no launch.
+    // Neither the resident set nor exact_range's pending results are touched.
+    bool exact_range_groups(long long n_rows, float range, const uint32_t *allow_bits, long long nbits, int *out_labels, uint64_t *out_info);
     // hnswdev_exact_knn_grouped: exact_knn with a candidate set per query.  Query i's candidates are the uploaded
     // ids j < min(n_rows, uploaded, n_row_group) with row_group[j] == query_group[i]; a row_group value outside [0, n_groups) puts
     // the id in no group, a query_group value outside it is an error (nothing is written).  The groups' id lists are built on the
@@ -712,6 +724,10 @@ private:
     template <class Enqueue, class Fetch> // the one timed, counted launch of the flat scan: every exact_* statistic is written there
     bool exact_timed_scan(unsigned long long *h_ev, Enqueue &&enqueue, Fetch &&fetch);
     bool exact_range_call(int nq, int *out_counts, const std::function<bool()> &body);
+    // the rounds of exact_range and exact_range_by_id: d_self nullptr, or the nq ids on the device whose rows the queries are
+    bool exact_range_rounds(const char *who, const ExactScanInput &in, int nq, float range, const int *d_self, int *out_counts);
+    DevBuf<int> x_uparent_;               // exact_range_groups: the union-find's parent[], then the labels behind it
+    DevBuf<unsigned long long> x_upairs_; // ... pairs within the range, counted on the device
     bool exact_range_finish(ExactRangeWork &w, int ns, const unsigned *c, const long long *seg, const int *sq, const long long *obase, size_t base,
                             bool counts_on_device, uint64_t *by_device, uint64_t *by_host);
     DevBuf<unsigned long long> x_rarena_; // exact_range: the round's keys, a segment per query: at most 1 GiB, grown on demand and kept

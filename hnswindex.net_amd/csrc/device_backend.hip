@@ -3902,86 +3902,99 @@ bool Device::exact_range(const float *queries, int nq, long long n_rows, float r
         ExactScanInput in;
         const ExactStart s = exact_scan_begin("exact_range", queries, nq, n_rows, allow_bits, nbits, &in);
         if (s != ExactStart::ready) return s == ExactStart::nothing; // (nothing to measure: empty lists, no launch)
-        hipStream_t st = S(stream_);
-        ExactPlan p = exact_plan(std::min(nq, 65536), in.m, 1, pitch_, num_cu_); // tile and chunks as for lists of one key: this sink keeps none
-        p.lds = exact_scan_lds(p.qtile, p.piece, pitch_, 0);
-        if (p.lds > 64 * 1024) { set_dev_error("exact_range: tile exceeds the LDS budget"); return false; }
-        ExactRangeWork w;
-        const long long cap = std::min<long long>({w.pick, in.m, w.arena_max});
-        const long long round = std::max<long long>(1, std::min<long long>({(long long)nq, 65536LL, w.arena_max / cap}));
-        if (!x_rcnt_.grow((size_t)round) || !x_rseg_.grow((size_t)round + 1) || !x_rooff_.grow((size_t)round)) return false;
-        std::vector<long long> seg((size_t)round + 1), obase((size_t)round);
-        std::vector<unsigned> cnt((size_t)round), cnt_b;
-
-        // one scan of queries [q0, q0 + nr) with the segments seg[0 .. nr]: the counts into c[0 .. nr)
-        const auto scan = [&](long long q0, int nr, unsigned *c) -> bool {
-            if (!x_rarena_.grow((size_t)std::max<long long>(seg[(size_t)nr], 1))) return false;
-            char *hs = static_cast<char *>(pinned_stage(8 * ((size_t)nr + 1) + 4 * (size_t)nr + 8));
-            if (!hs) return false;
-            unsigned long long *h_ev = reinterpret_cast<unsigned long long *>(hs);
-            long long *h_seg = reinterpret_cast<long long *>(hs + 8);
-            unsigned *h_cnt = reinterpret_cast<unsigned *>(hs + 8 + 8 * ((size_t)nr + 1));
-            memcpy(h_seg, seg.data(), 8 * ((size_t)nr + 1));
-            ExactScanArgs a;
-            if (!exact_scan_args(in.d_q, in.d_qsn, q0, nr, p.qtile, p.piece, &a)) return false;
-            a.ids = in.ids; a.m = in.m; a.chunk = p.chunk; a.n_chunks = p.n_chunks;
-            ExactRange sink;
-            sink.range = range; sink.counts = x_rcnt_; sink.seg_off = x_rseg_; sink.arena = x_rarena_;
-            const unsigned tiles = (unsigned)((nr + p.qtile - 1) / p.qtile);
-            HIP_OK(hipMemcpyAsync(x_rseg_, h_seg, 8 * ((size_t)nr + 1), hipMemcpyHostToDevice, st));
-            HIP_OK(hipMemsetAsync(x_rcnt_, 0, 4 * (size_t)nr, st));
-            const auto enqueue = [&]() -> bool {
-                hipError_t e = hipSuccess;
-                with_metric(metric_, [&](auto mt) { e = exact_range_scan_launch<mt>(a, sink, tiles, p.lds, st); });
-                HIP_OK(e);
-                return true;
-            };
-            const auto fetch = [&]() -> bool { HIP_OK(hipMemcpyAsync(h_cnt, x_rcnt_, 4 * (size_t)nr, hipMemcpyDeviceToHost, st)); return true; };
-            if (!exact_timed_scan(h_ev, enqueue, fetch)) return false;
-            memcpy(c, h_cnt, 4 * (size_t)nr);
-            return true;
-        };
-
-        // the lists of queries [q0, q0 + nr), every one inside its segment seg[i] .. : ordered and appended to the call's results
-        using Slot = slot::exact_range_info;
-        uint64_t *ctr = counter_block(Slot::kBlock);
-        const auto finish = [&](long long q0, int nr, const unsigned *c) -> bool {
-            size_t total = 0;
-            for (int i = 0; i < nr; ++i) {
-                obase[(size_t)i] = (long long)total;
-                total += c[i];
-                out_counts[q0 + i] = (int)c[i];
-            }
-            const size_t base = xr_ids_.size();
-            xr_ids_.resize(base + total);
-            xr_d_.resize(base + total);
-            if (!exact_range_finish(w, nr, c, seg.data(), nullptr, obase.data(), base, true, &ctr[Slot::device_sorted], &ctr[Slot::host_sorted])) return false;
-            ctr[Slot::results] += total;
-            return true;
-        };
-
-        for (long long off = 0; off < nq; off += round) {
-            const int nr = (int)std::min<long long>(round, nq - off);
-            for (int i = 0; i <= nr; ++i) seg[(size_t)i] = (long long)i * cap;
-            if (!scan(off, nr, cnt.data())) return false;
-            bool fits = true;
-            for (int i = 0; i < nr; ++i) fits = fits && cnt[(size_t)i] <= (unsigned long long)cap;
-            if (fits) {
-                if (!finish(off, nr, cnt.data())) return false;
-                continue;
-            }
-            // pass B: pieces of the round whose exact counts fit the arena, each with segments of exactly its counts
-            cnt_b.resize((size_t)nr);
-            for (size_t s0 = 0, s1; s0 < (size_t)nr; s0 = s1) {
-                if (!exact_range_piece("exact_range", cnt.data(), (size_t)nr, s0, w.arena_max, seg, &s1)) return false;
-                ctr[Slot::repeated_rounds] += 1;
-                const int ns = (int)(s1 - s0);
-                if (!scan(off + (long long)s0, ns, cnt_b.data()) || !exact_range_recount_ok("exact_range", cnt_b.data(), cnt.data() + s0, (size_t)ns)) return false;
-                if (!finish(off + (long long)s0, ns, cnt_b.data())) return false;
-            }
-        }
-        return true;
+        return exact_range_rounds("exact_range", in, nq, range, nullptr, out_counts);
     });
+}
+
+// The rounds of a range scan over the queries and the id list of `in`: pass A, the finish and pass B, the lists appended to the
+// call's results in query order and counted in exact_range_info.  d_self: nullptr, or the nq ids on the device whose stored rows
+// the queries are (exact_range_by_id) -- the sink is then ExactRangeSelf, and every launch gets the ids of ITS queries: a repeated
+// pass scans queries [q0, q0 + ns) of the call and reads d_self + q0, as it reads the queries from q0 on.  Runs inside
+// exact_range_call's body.
+bool Device::exact_range_rounds(const char *who, const ExactScanInput &in, int nq, float range, const int *d_self, int *out_counts)
+{
+    hipStream_t st = S(stream_);
+    ExactPlan p = exact_plan(std::min(nq, 65536), in.m, 1, pitch_, num_cu_); // tile and chunks as for lists of one key: this sink keeps none
+    p.lds = exact_scan_lds(p.qtile, p.piece, pitch_, 0);
+    if (p.lds > 64 * 1024) { set_dev_error(std::string(who) + ": tile exceeds the LDS budget"); return false; }
+    ExactRangeWork w;
+    const long long cap = std::min<long long>({w.pick, in.m, w.arena_max});
+    const long long round = std::max<long long>(1, std::min<long long>({(long long)nq, 65536LL, w.arena_max / cap}));
+    if (!x_rcnt_.grow((size_t)round) || !x_rseg_.grow((size_t)round + 1) || !x_rooff_.grow((size_t)round)) return false;
+    std::vector<long long> seg((size_t)round + 1), obase((size_t)round);
+    std::vector<unsigned> cnt((size_t)round), cnt_b;
+
+    // one scan of queries [q0, q0 + nr) with the segments seg[0 .. nr]: the counts into c[0 .. nr)
+    const auto scan = [&](long long q0, int nr, unsigned *c) -> bool {
+        if (!x_rarena_.grow((size_t)std::max<long long>(seg[(size_t)nr], 1))) return false;
+        char *hs = static_cast<char *>(pinned_stage(8 * ((size_t)nr + 1) + 4 * (size_t)nr + 8));
+        if (!hs) return false;
+        unsigned long long *h_ev = reinterpret_cast<unsigned long long *>(hs);
+        long long *h_seg = reinterpret_cast<long long *>(hs + 8);
+        unsigned *h_cnt = reinterpret_cast<unsigned *>(hs + 8 + 8 * ((size_t)nr + 1));
+        memcpy(h_seg, seg.data(), 8 * ((size_t)nr + 1));
+        ExactScanArgs a;
+        if (!exact_scan_args(in.d_q, in.d_qsn, q0, nr, p.qtile, p.piece, &a)) return false;
+        a.ids = in.ids; a.m = in.m; a.chunk = p.chunk; a.n_chunks = p.n_chunks;
+        ExactRange sink;
+        sink.range = range; sink.counts = x_rcnt_; sink.seg_off = x_rseg_; sink.arena = x_rarena_;
+        const unsigned tiles = (unsigned)((nr + p.qtile - 1) / p.qtile);
+        HIP_OK(hipMemcpyAsync(x_rseg_, h_seg, 8 * ((size_t)nr + 1), hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemsetAsync(x_rcnt_, 0, 4 * (size_t)nr, st));
+        const auto enqueue = [&]() -> bool {
+            hipError_t e = hipSuccess;
+            if (d_self) {
+                const ExactRangeSelf own{range, sink.counts, sink.seg_off, sink.arena, d_self + q0};
+                with_metric(metric_, [&](auto mt) { e = exact_range_self_scan_launch<mt>(a, own, tiles, p.lds, st); });
+            } else with_metric(metric_, [&](auto mt) { e = exact_range_scan_launch<mt>(a, sink, tiles, p.lds, st); });
+            HIP_OK(e);
+            return true;
+        };
+        const auto fetch = [&]() -> bool { HIP_OK(hipMemcpyAsync(h_cnt, x_rcnt_, 4 * (size_t)nr, hipMemcpyDeviceToHost, st)); return true; };
+        if (!exact_timed_scan(h_ev, enqueue, fetch)) return false;
+        memcpy(c, h_cnt, 4 * (size_t)nr);
+        return true;
+    };
+
+    // the lists of queries [q0, q0 + nr), every one inside its segment seg[i] .. : ordered and appended to the call's results
+    using Slot = slot::exact_range_info;
+    uint64_t *ctr = counter_block(Slot::kBlock);
+    const auto finish = [&](long long q0, int nr, const unsigned *c) -> bool {
+        size_t total = 0;
+        for (int i = 0; i < nr; ++i) {
+            obase[(size_t)i] = (long long)total;
+            total += c[i];
+            out_counts[q0 + i] = (int)c[i];
+        }
+        const size_t base = xr_ids_.size();
+        xr_ids_.resize(base + total);
+        xr_d_.resize(base + total);
+        if (!exact_range_finish(w, nr, c, seg.data(), nullptr, obase.data(), base, true, &ctr[Slot::device_sorted], &ctr[Slot::host_sorted])) return false;
+        ctr[Slot::results] += total;
+        return true;
+    };
+
+    for (long long off = 0; off < nq; off += round) {
+        const int nr = (int)std::min<long long>(round, nq - off);
+        for (int i = 0; i <= nr; ++i) seg[(size_t)i] = (long long)i * cap;
+        if (!scan(off, nr, cnt.data())) return false;
+        bool fits = true;
+        for (int i = 0; i < nr; ++i) fits = fits && cnt[(size_t)i] <= (unsigned long long)cap;
+        if (fits) {
+            if (!finish(off, nr, cnt.data())) return false;
+            continue;
+        }
+        // pass B: pieces of the round whose exact counts fit the arena, each with segments of exactly its counts
+        cnt_b.resize((size_t)nr);
+        for (size_t s0 = 0, s1; s0 < (size_t)nr; s0 = s1) {
+            if (!exact_range_piece(who, cnt.data(), (size_t)nr, s0, w.arena_max, seg, &s1)) return false;
+            ctr[Slot::repeated_rounds] += 1;
+            const int ns = (int)(s1 - s0);
+            if (!scan(off + (long long)s0, ns, cnt_b.data()) || !exact_range_recount_ok(who, cnt_b.data(), cnt.data() + s0, (size_t)ns)) return false;
+            if (!finish(off + (long long)s0, ns, cnt_b.data())) return false;
+        }
+    }
+    return true;
 }
 
 // ---- hnswdev_exact_range_grouped: the range sink behind exact_knn_grouped's work items ------------------
@@ -4777,6 +4790,123 @@ bool Device::exact_knn_by_id(const int *ids, int nq, long long n_rows, int k, co
     return true;
 }
 
+// ---- near-duplicates of stored rows ---------------------------------------------------------------------------------
+// The range scan by stored id: exact_range's rounds (exact_range_rounds) with the queries gathered as exact_knn_by_id gathers them
+// and ExactRangeSelf as the sink.
+bool Device::exact_range_by_id(const int *ids, int nq, long long n_rows, float range, const uint32_t *allow_bits, long long nbits, int *out_counts)
+{
+    return exact_range_call(nq, out_counts, [&]() -> bool {
+        if (nq <= 0) return true;
+        const char *who = "exact_range_by_id";
+        if (!ids || !out_counts || n_rows < 0 || (allow_bits && nbits < 0)) { set_dev_error(std::string(who) + ": bad argument"); return false; }
+        for (int i = 0; i < nq; ++i) out_counts[i] = 0;
+        if (const std::string why = by_id_rows_error(who, ids, nq, n_rows_hw_); !why.empty()) { set_dev_error(why); return false; }
+        if (!allow_bits) nbits = 0;
+        const long long n = std::min(n_rows, n_rows_hw_), n_allow = allow_bits ? std::min(nbits, n) : n;
+        if (n_allow <= 0 || (allow_bits && !allows_any(allow_bits, nbits, n))) return true; // no candidate: empty lists, no launch
+        if (!bind()) return false;
+        const size_t cap = (size_t)std::max(nq, 1024);
+        if (!x_queries_.grow((size_t)nq * pitch_, cap * pitch_) || (metric_ == M_COS && !x_q_sn_.grow((size_t)nq, cap))) return false;
+        if (!gather_queries(ids, nq, x_self_, x_queries_, x_q_sn_)) return false;
+        ExactScanInput in;
+        in.d_q = x_queries_; in.d_qsn = metric_ == M_COS ? x_q_sn_.get() : nullptr;
+        if (!exact_id_list(allow_bits, n_allow, &in.m)) return false;
+        in.ids = allow_bits ? x_ids_.get() : nullptr;
+        uint64_t skipped = 0; // the queries whose own id is a candidate: one pair each
+        for (int i = 0; i < nq; ++i) {
+            const long long id = ids[i];
+            skipped += (uint64_t)(id < n_allow && (!allow_bits || ((allow_bits[id >> 5] >> (id & 31)) & 1u)));
+        }
+        if (!exact_range_rounds(who, in, nq, range, x_self_, out_counts)) return false;
+        using Slot = slot::by_id_info;
+        uint64_t *ctr = counter_block(Slot::kBlock);
+        ctr[Slot::calls] += 1;
+        ctr[Slot::scanned] += (uint64_t)nq;
+        ctr[Slot::self_skipped] += skipped;
+        return true;
+    });
+}
+
+// The duplicate groups: the members' list goes up once and is both the candidates and, a round of `exact_union_round` (65 536) at a
+// time, the queries -- gathered as the by-id calls gather theirs.  Every round is one launch of the scan with ExactRangeUnion as
+// its sink, counted and timed like any (exact_timed_scan: exact_evals are the pairs measured); then one kernel turns parent[] into
+// labels.  The members are listed on the host -- the bitset is the host's -- so that the rounds' ids need no copy back.
+constexpr long long kExactUnionChunk = 2048; // rows of a chunk of the groups' scan unless `exact_chunk` forces them
+bool Device::exact_range_groups(long long n_rows, float range, const uint32_t *allow_bits, long long nbits, int *out_labels, uint64_t *out_info)
+{
+    const char *who = "exact_range_groups";
+    if (!out_info || n_rows < 0 || (allow_bits && nbits < 0)) { set_dev_error(std::string(who) + ": bad argument"); return false; }
+    for (int i = 0; i < 4; ++i) out_info[i] = 0;
+    if (!allow_bits) nbits = 0;
+    const long long n = std::min(n_rows, n_rows_hw_), n_allow = allow_bits ? std::min(nbits, n) : n;
+    if (n > 0 && !out_labels) { set_dev_error(std::string(who) + ": bad argument"); return false; }
+    std::vector<int> members;
+    for (long long id = 0; id < n_allow; ++id)
+        if (!allow_bits || ((allow_bits[id >> 5] >> (id & 31)) & 1u)) members.push_back((int)id);
+    const long long m = (long long)members.size();
+    for (long long v = 0; v < n; ++v) out_labels[v] = -1;
+    for (const int v : members) out_labels[v] = v; // (what fewer than two members leave; the device's labels replace it otherwise)
+    out_info[0] = (unsigned long long)m;
+    out_info[1] = (unsigned long long)m;
+    if (m < 2) return true; // nothing to measure: no launch
+    if (!bind()) return false;
+    hipStream_t st = S(stream_);
+    const int forced_round = diag("exact_union_round", 0);
+    const long long round = std::min<long long>(m, forced_round > 0 ? forced_round : 65536);
+    ExactPlan p = exact_plan((int)round, m, 1, pitch_, num_cu_); // the tile as for lists of one key: this sink keeps none
+    p.lds = exact_scan_lds(p.qtile, p.piece, pitch_, 0);
+    if (p.lds > 64 * 1024) { set_dev_error(std::string(who) + ": tile exceeds the LDS budget"); return false; }
+    if (diag("exact_chunk", 0) <= 0) {
+        // The picker's chunks exist to fill the chip, and a round of many tiles fills it alone: it would leave ONE chunk, whose last id
+        // is above every query's, so that no block could leave early and every pair were measured twice.  Here the chunks are what the
+        // blocks below the diagonal are cut off by: about kExactUnionChunk rows each, so that what is measured twice is the
+        // (tile, chunk) blocks on the diagonal alone.
+        const long long chunks = std::max<long long>(1, std::min<long long>(m / kExactUnionChunk, kExactMaxChunks));
+        p.chunk = ((m + chunks - 1) / chunks + kExactIterRows - 1) / kExactIterRows * kExactIterRows;
+        p.n_chunks = (int)((m + p.chunk - 1) / p.chunk);
+    }
+    const size_t cap = (size_t)std::max<long long>(round, 1024);
+    if (!x_queries_.grow((size_t)round * pitch_, cap * pitch_) || (metric_ == M_COS && !x_q_sn_.grow((size_t)round, cap))) return false;
+    if (!x_uparent_.grow(2 * (size_t)n) || !x_upairs_.grow(1)) return false;
+    if (!upload_ids(members.data(), (int)m, x_ids_)) return false;
+    HIP_OK(exact_union_init_launch(x_ids_, m, x_uparent_, n, st));
+    HIP_OK(hipMemsetAsync(x_upairs_, 0, sizeof(unsigned long long), st));
+    HIP_OK(hipStreamSynchronize(st)); // the pinned stage is used again by the rounds
+    unsigned long long measured = 0;
+    for (long long off = 0; off < m; off += round) {
+        const int nr = (int)std::min<long long>(round, m - off);
+        if (!gather_queries(members.data() + off, nr, x_self_, x_queries_, x_q_sn_)) return false;
+        unsigned long long *h_ev = static_cast<unsigned long long *>(pinned_stage(8));
+        if (!h_ev) return false;
+        ExactScanArgs a;
+        if (!exact_scan_args(x_queries_, metric_ == M_COS ? x_q_sn_.get() : nullptr, 0, nr, p.qtile, p.piece, &a)) return false;
+        a.ids = x_ids_; a.m = m; a.chunk = p.chunk; a.n_chunks = p.n_chunks;
+        const ExactRangeUnion sink{range, x_uparent_, x_self_, x_upairs_};
+        const unsigned tiles = (unsigned)((nr + p.qtile - 1) / p.qtile);
+        const auto enqueue = [&]() -> bool {
+            hipError_t e = hipSuccess;
+            with_metric(metric_, [&](auto mt) { e = exact_range_union_scan_launch<mt>(a, sink, tiles, p.lds, st); });
+            HIP_OK(e);
+            return true;
+        };
+        if (!exact_timed_scan(h_ev, enqueue, [] { return true; })) return false;
+        measured += *h_ev;
+    }
+    int *d_labels = x_uparent_.get() + n;
+    HIP_OK(exact_union_labels_launch(x_uparent_, n, d_labels, st));
+    if (!exact_copy_out(out_labels, d_labels, 4 * (size_t)n)) return false;
+    unsigned long long *h = static_cast<unsigned long long *>(pinned_stage(8));
+    if (!h) return false;
+    HIP_OK(hipMemcpyAsync(h, x_upairs_, 8, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    unsigned long long groups = 0;
+    for (const int v : members) groups += (unsigned long long)(out_labels[v] == v);
+    out_info[1] = groups;
+    out_info[2] = *h;
+    out_info[3] = measured;
+    return true;
+}
+
 // ---- synchronous conveniences behind the C ABI ---------------------------------------
 // Distance(int, TVector) for nq (query, candidate list) pairs.  Runs on the context's two step-
 // buffer sets, ping-pong: while the GPU measures one set the host packs the next and unpacks the
@@ -5058,6 +5188,18 @@ DEV_API int hnswdev_exact_range(void *ctx, const float *queries, int nq, long lo
     return d->exact_range(queries, nq, n_rows, range, allow_bits, nbits, out_counts) ? 0 : -1;
 }
 DEV_API int hnswdev_exact_range_results(void *ctx, int *out_ids, float *out_dists) { CTX_OR_FAIL(); return d->exact_range_results(out_ids, out_dists) ? 0 : -1; }
+DEV_API int hnswdev_exact_range_by_id(void *ctx, const int *ids, int nq, long long n_rows, float range, const uint32_t *allow_bits, long long nbits,
+                                      int *out_counts)
+{
+    CTX_OR_FAIL();
+    return d->exact_range_by_id(ids, nq, n_rows, range, allow_bits, nbits, out_counts) ? 0 : -1;
+}
+DEV_API int hnswdev_exact_range_groups(void *ctx, long long n_rows, float range, const uint32_t *allow_bits, long long nbits, int *out_labels,
+                                       uint64_t *out_info)
+{
+    CTX_OR_FAIL();
+    return d->exact_range_groups(n_rows, range, allow_bits, nbits, out_labels, out_info) ? 0 : -1;
+}
 DEV_API int hnswdev_exact_knn_grouped(void *ctx, const float *queries, int nq, long long n_rows, int k, const int *row_group, long long n_row_group,
                                       const int *query_group, int n_groups, int *out_ids, float *out_dists)
 {

@@ -22,6 +22,10 @@
 // and hnswdev_exact_knn_collapsed: at most per_group results per label row_group[id] -- the result is shaped, not the candidates.
 //   exact_scan_kernel<M, ExactTopKCollapse>     ExactTopK's lists with a label beside every key; exact_list_insert_collapsed drops, evicts or inserts
 //   exact_merge_collapsed_kernel                one wave per query: the chunks' collapsed lists -> the collapsed final k
+// and hnswdev_exact_range_by_id / hnswdev_exact_range_groups: near-duplicates of stored rows.
+//   exact_scan_kernel<M, ExactRangeSelf>        ExactRange, with ExactTopKSelf's rule: the query's own row offers no key and is not counted
+//   exact_scan_kernel<M, ExactRangeUnion>       no keys at all: a pair (a < b) within the range joins a and b in a union-find (dk_union_find.h)
+//   exact_union_init_kernel / exact_union_labels_kernel   every id its own root before the scans; labels = roots = smallest ids after them
 // The kernels are compiled in the exact_<metric> units (exact_unit.hip, HNSW_EXACT_UNIT) and reached through the launchers declared here, so
 // that device_backend.hip holds none of their code.
 #pragma once
@@ -71,6 +75,7 @@ struct ExactTopK {
     static constexpr bool kGrouped = false;
     static constexpr bool kSelf = false;
     static constexpr bool kCollapse = false;
+    static constexpr bool kUnion = false;
 };
 // ExactTopKSelf: ExactTopK where query q of the round is the stored row of id self[q] and that id is no candidate of it: the pair
 // produces no key and is not counted in ExactScanArgs::evals.  A duplicate of the row under another id is a candidate like any.
@@ -79,6 +84,7 @@ struct ExactTopKSelf {
     static constexpr bool kGrouped = false;
     static constexpr bool kSelf = true;
     static constexpr bool kCollapse = false;
+    static constexpr bool kUnion = false;
     const int *self;               // [nq of the round]
 };
 // ExactTopKCollapse: the lists hold the COLLAPSED k smallest keys -- the first k keys of the ascending order that
@@ -91,6 +97,7 @@ struct ExactTopKCollapse {
     static constexpr bool kGrouped = false;
     static constexpr bool kSelf = false;
     static constexpr bool kCollapse = true;
+    static constexpr bool kUnion = false;
     const int *row_group;          // [every id of the list]
     int per_group;                 // 1 <= per_group <= k
     unsigned long long *info;      // [2]
@@ -100,10 +107,44 @@ struct ExactRange {
     static constexpr bool kGrouped = false;
     static constexpr bool kSelf = false;
     static constexpr bool kCollapse = false;
+    static constexpr bool kUnion = false;
     float range;
     unsigned *counts;              // [nq]
     const long long *seg_off;      // [nq + 1]
     unsigned long long *arena;
+};
+// ExactRangeSelf: ExactRange where query q of the round is the stored row of id self[q] and that id is no candidate
+// of it -- ExactTopKSelf's rule in the range branch: the pair offers no key and is not counted in ExactScanArgs::evals.  A repeated
+// pass over a piece of a round brings the piece's own self: self[0] belongs to the first query the launch scans.
+struct ExactRangeSelf {
+    static constexpr bool kRange = true;
+    static constexpr bool kGrouped = false;
+    static constexpr bool kSelf = true;
+    static constexpr bool kCollapse = false;
+    static constexpr bool kUnion = false;
+    float range;
+    unsigned *counts;              // [nq]
+    const long long *seg_off;      // [nq + 1]
+    unsigned long long *arena;
+    const int *self;               // [nq of the launch]
+};
+// ExactRangeUnion: no key is kept.  The queries of a launch are a contiguous, ascending piece of the id list itself
+// -- query q is the stored row of id self[q] -- and a pair (self, rid) is measured where rid > self: counted in ExactScanArgs::evals,
+// and where its distance is <= range counted in *pairs and joined in parent[] (uf_union, from the lane that holds the distance).
+// A pair with rid <= self is skipped without being counted.  No pending list, no arena: the sink touches nothing of LDS behind the
+// staged queries.  A block whose chunk ends at or below its tile's first query id has nothing to measure and leaves before its first
+// barrier (the test is the same for the whole block).  parent[v] == v for every id of the list before the first launch
+// (exact_union_init_launch); labels[v] = uf_find(parent, v) after the last (exact_union_labels_launch).
+struct ExactRangeUnion {
+    static constexpr bool kRange = true;
+    static constexpr bool kGrouped = false;
+    static constexpr bool kSelf = true;
+    static constexpr bool kCollapse = false;
+    static constexpr bool kUnion = true;
+    float range;
+    int *parent;                   // [every id of the list]
+    const int *self;               // [nq of the launch]: ascending
+    unsigned long long *pairs;     // out: measured pairs within the range, added up over the blocks
 };
 struct ExactRangeSortArgs {
     const unsigned long long *arena;
@@ -129,6 +170,7 @@ struct ExactTopKGrouped {
     static constexpr bool kGrouped = true;
     static constexpr bool kSelf = false;
     static constexpr bool kCollapse = false;
+    static constexpr bool kUnion = false;
     const ExactWorkItem *items;
 };
 // ExactRangeGrouped: ExactRange's segments behind ExactTopKGrouped's work items (list0, n_chunks and slot of an item are not read).
@@ -141,6 +183,7 @@ struct ExactRangeGrouped {
     static constexpr bool kGrouped = true;
     static constexpr bool kSelf = false;
     static constexpr bool kCollapse = false;
+    static constexpr bool kUnion = false;
     float range;
     unsigned *counts;              // [segments]
     const long long *seg_off;      // [segments + 1]
@@ -171,6 +214,14 @@ template <int METRIC>
 hipError_t exact_range_scan_launch(const ExactScanArgs &a, const ExactRange &sink, unsigned n_qtiles, size_t lds, hipStream_t st);
 template <int METRIC>
 hipError_t exact_self_scan_launch(const ExactScanArgs &a, const ExactTopKSelf &sink, unsigned n_qtiles, size_t lds, hipStream_t st);
+template <int METRIC>
+hipError_t exact_range_self_scan_launch(const ExactScanArgs &a, const ExactRangeSelf &sink, unsigned n_qtiles, size_t lds, hipStream_t st);
+template <int METRIC>
+hipError_t exact_range_union_scan_launch(const ExactScanArgs &a, const ExactRangeUnion &sink, unsigned n_qtiles, size_t lds, hipStream_t st);
+// parent[0, n) = -1, then parent[id] = id for the m ids of the list (enqueued in this order)
+hipError_t exact_union_init_launch(const int *ids, long long m, int *parent, long long n, hipStream_t st);
+// labels[v] = the root of v's tree -- the smallest id of its group -- for v in [0, n); -1 where parent[v] is -1
+hipError_t exact_union_labels_launch(int *parent, long long n, int *labels, hipStream_t st);
 template <int METRIC> // lds: exact_scan_lds with kExactCollapseEntryBytes
 hipError_t exact_collapsed_scan_launch(const ExactScanArgs &a, const ExactTopKCollapse &sink, unsigned n_qtiles, size_t lds, hipStream_t st);
 // exact_merge_launch for the collapsed lists: the labels are looked up in row_group, info as ExactTopKCollapse::info
@@ -197,6 +248,7 @@ hipError_t exact_merge_grouped_launch(const unsigned long long *lists, const Exa
 #include "dk_base.h"
 #include "dk_metric.h"
 #include "dk_heaps.h"
+#include "dk_union_find.h"
 
 namespace hnsw {
 
@@ -318,8 +370,15 @@ __global__ void __launch_bounds__(kExactThreads) exact_scan_kernel(const ExactSc
         if constexpr (SINK::kGrouped) return q >= item_qend ? item_qend - 1 : q;
         else { if (q >= a.nq) q = a.nq - 1; return q; }
     };
+    if constexpr (SINK::kUnion) {
+        // nothing to measure where the chunk's last id is not above the tile's first query id (both lists ascend): the whole block
+        // leaves, in front of its first barrier
+        const int last = a.ids ? a.ids[hi - 1] : (int)(hi - 1);
+        if (__builtin_amdgcn_readfirstlane(last) <= __builtin_amdgcn_readfirstlane(sink.self[q0])) return;
+    }
     const int rw = row_words<METRIC>(dim);
     const int nblk = dim >> 3;
+    [[maybe_unused]] unsigned joined = 0; // ExactRangeUnion: pairs within the range that this lane met
 
     for (int i = tid; i < QTR * k; i += kExactThreads) lists[i] = kExactEmpty;
     if (tid < QTR) thr[tid] = kExactEmpty;
@@ -469,7 +528,26 @@ __global__ void __launch_bounds__(kExactThreads) exact_scan_kernel(const ExactSc
                     }
                 }
             }
-            if constexpr (SINK::kRange) {
+            if constexpr (SINK::kUnion) {
+                // no offers: a pair above the diagonal is counted and, within the range, joined from the lane that holds its distance.
+                // uf_union waits for no other lane, and the lanes meet again behind this branch, in front of the next step's barriers.
+                if (j == 0) {
+#pragma unroll
+                    for (int q = 0; q < RQ; ++q) {
+                        if (qsub + q >= QT || !q_in(q0 + qsub + q)) continue;
+                        const int self = sink.self[q0 + qsub + q];
+#pragma unroll
+                        for (int r = 0; r < RR; ++r) {
+                            if (!rvalid[r] || rid[r] <= self) continue; // the pair's other half, or the query's own row: not counted
+                            ++measured;
+                            if (dist[q][r] <= sink.range) {
+                                ++joined;
+                                uf_union(sink.parent, self, rid[r]);
+                            }
+                        }
+                    }
+                }
+            } else if constexpr (SINK::kRange) {
                 // offers: every key within the range goes to its query's pending list (kExactIterRows entries per query of the
                 // register tile: what one step can produce)
                 int offered = 0;
@@ -477,9 +555,12 @@ __global__ void __launch_bounds__(kExactThreads) exact_scan_kernel(const ExactSc
 #pragma unroll
                     for (int q = 0; q < RQ; ++q) {
                         if (qsub + q >= QT || !q_in(q0 + qsub + q)) continue;
+                        [[maybe_unused]] int self = -1;
+                        if constexpr (SINK::kSelf) self = sink.self[q0 + qsub + q]; // (a query of the round: q_in above)
 #pragma unroll
                         for (int r = 0; r < RR; ++r) {
                             if (!rvalid[r]) continue;
+                            if constexpr (SINK::kSelf) { if (rid[r] == self) continue; } // the query's own row: no key, not counted
                             ++measured;
                             if (dist[q][r] <= sink.range) {
                                 const int slot = atomicAdd(&pend_cnt[q], 1);
@@ -576,6 +657,9 @@ __global__ void __launch_bounds__(kExactThreads) exact_scan_kernel(const ExactSc
     }
     __syncthreads();
     if (measured) atomicAdd(a.evals, (unsigned long long)measured); // one atomic per group that measured anything
+    if constexpr (SINK::kUnion) {
+        if (joined) atomicAdd(sink.pairs, (unsigned long long)joined);
+    }
     if constexpr (SINK::kCollapse) {
         if (lane == 0 && dropped) atomicAdd(&sink.info[0], (unsigned long long)dropped);
         if (lane == 0 && evicted) atomicAdd(&sink.info[1], (unsigned long long)evicted);
@@ -602,6 +686,19 @@ template <int METRIC>
 hipError_t exact_range_scan_launch(const ExactScanArgs &a, const ExactRange &sink, unsigned n_qtiles, size_t lds, hipStream_t st)
 {
     hipLaunchKernelGGL((exact_scan_kernel<METRIC, ExactRange>), dim3(n_qtiles, (unsigned)a.n_chunks), dim3(kExactThreads), lds, st, a, sink);
+    return hipGetLastError();
+}
+
+template <int METRIC>
+hipError_t exact_range_self_scan_launch(const ExactScanArgs &a, const ExactRangeSelf &sink, unsigned n_qtiles, size_t lds, hipStream_t st)
+{
+    hipLaunchKernelGGL((exact_scan_kernel<METRIC, ExactRangeSelf>), dim3(n_qtiles, (unsigned)a.n_chunks), dim3(kExactThreads), lds, st, a, sink);
+    return hipGetLastError();
+}
+template <int METRIC>
+hipError_t exact_range_union_scan_launch(const ExactScanArgs &a, const ExactRangeUnion &sink, unsigned n_qtiles, size_t lds, hipStream_t st)
+{
+    hipLaunchKernelGGL((exact_scan_kernel<METRIC, ExactRangeUnion>), dim3(n_qtiles, (unsigned)a.n_chunks), dim3(kExactThreads), lds, st, a, sink);
     return hipGetLastError();
 }
 
@@ -764,6 +861,40 @@ __global__ void __launch_bounds__(256) exact_range_sort_kernel(const ExactRangeS
         a.out_ids[o + i] = (int)(unsigned)key;
         a.out_d[o + i] = exact_key_dist(key);
     }
+}
+
+// ---- the union-find around ExactRangeUnion's launches: grid-stride, no kernel waits for another wave ----
+// Every id of the list is the root of its own tree.  (parent[] was filled with -1 in front of this launch: an id outside the list
+// stays -1 and is never dereferenced, because the scan's candidates are the list's ids and nothing else.)
+__global__ void __launch_bounds__(256) exact_union_init_kernel(const int *__restrict__ ids, long long m, int *__restrict__ parent)
+{
+    const long long step = (long long)gridDim.x * 256;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < m; i += step) {
+        const int v = ids[i];
+        parent[v] = v;
+    }
+}
+// The label of every id: the root of its tree, which is the smallest id of its group (uf_union hooks the larger root under the
+// smaller); -1 for an id outside the list.  The finds of other threads halve paths meanwhile: parents only ever decrease towards the
+// same root, so the root found does not depend on them.
+__global__ void __launch_bounds__(256) exact_union_labels_kernel(int *parent, long long n, int *__restrict__ labels)
+{
+    const long long step = (long long)gridDim.x * 256;
+    for (long long v = (long long)blockIdx.x * 256 + threadIdx.x; v < n; v += step)
+        labels[v] = __hip_atomic_load(parent + v, GI_RELAXED) < 0 ? -1 : uf_find(parent, (int)v);
+}
+static inline unsigned exact_union_blocks(long long n) { return (unsigned)((n + 255) / 256 < (1LL << 16) ? (n + 255) / 256 : (1LL << 16)); }
+hipError_t exact_union_init_launch(const int *ids, long long m, int *parent, long long n, hipStream_t st)
+{
+    hipError_t e = hipMemsetAsync(parent, 0xff, sizeof(int) * (size_t)n, st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(exact_union_init_kernel, dim3(exact_union_blocks(m)), dim3(256), 0, st, ids, m, parent);
+    return hipGetLastError();
+}
+hipError_t exact_union_labels_launch(int *parent, long long n, int *labels, hipStream_t st)
+{
+    hipLaunchKernelGGL(exact_union_labels_kernel, dim3(exact_union_blocks(n)), dim3(256), 0, st, parent, n, labels);
+    return hipGetLastError();
 }
 
 // ---- the group lists of exact_knn_grouped: a CSR over the groups, built from row_group in three launches ----

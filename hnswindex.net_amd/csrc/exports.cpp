@@ -484,6 +484,44 @@ API int hnsw_mi355x_exact_range_query(void *handle, const float *vectors, int co
     return exact_range_hand_out("hnsw_mi355x_exact_range_query", count, counts, ids, ds, out_ids, out_dists);
 }
 
+// hnsw_mi355x_exact_range_query for the stored rows of ids: that call's lists and allocation contract; the
+// candidates are allow_bits (NULL: every live id) minus the query's own id.  Exclusive, like the other by-id calls.
+API int hnsw_mi355x_exact_range_query_by_id(void *handle, const int *ids, int count, float range, const uint32_t *allow_bits, long long nbits, void **out_ids,
+                                            void **out_dists, int *counts)
+{
+    if (!handle) return 0;
+    if (count <= 0) return 0;
+    if (!ids || !out_ids || !out_dists || !counts) { set_error("System.ArgumentNullException: hnsw_mi355x_exact_range_query_by_id"); return -1; }
+    for (int i = 0; i < count; ++i) { out_ids[i] = nullptr; out_dists[i] = nullptr; counts[i] = 0; }
+    if (allow_bits && nbits < 0) { set_error("System.ArgumentException: hnsw_mi355x_exact_range_query_by_id: nbits must be >= 0"); return -1; }
+    std::string err;
+    std::vector<int> found;
+    std::vector<float> ds;
+    {
+        LOCK_INDEX(handle);
+        if (static_cast<HnswIndex *>(handle)->exact_range_query_by_id(ids, count, range, allow_bits, nbits, counts, found, ds, err) < 0) {
+            for (int i = 0; i < count; ++i) counts[i] = 0;
+            set_error(err);
+            return -1;
+        }
+    }
+    return exact_range_hand_out("hnsw_mi355x_exact_range_query_by_id", count, counts, found, ds, out_ids, out_dists);
+}
+
+// The single-linkage groups of the live, allowed ids within `range` of each other: one scan whose sink is a
+// union-find on the device.  Exclusive: it uses the scan's buffers.
+API int hnsw_mi355x_duplicate_groups(void *handle, float range, const uint32_t *allow_bits, long long nbits, int *out_labels, long long cap, uint64_t *out_info)
+{
+    if (out_info) for (int i = 0; i < 4; ++i) out_info[i] = 0;
+    if (!handle) return 0;
+    if (!out_info) { set_error("System.ArgumentNullException: hnsw_mi355x_duplicate_groups: out_info"); return -1; }
+    if (allow_bits && nbits < 0) { set_error("System.ArgumentException: hnsw_mi355x_duplicate_groups: nbits must be >= 0"); return -1; }
+    LOCK_INDEX(handle);
+    std::string err;
+    if (static_cast<HnswIndex *>(handle)->duplicate_groups(range, allow_bits, nbits, out_labels, cap, out_info, err) < 0) { set_error(err); return -1; }
+    return 0;
+}
+
 // hnsw_mi355x_exact_range_query with a candidate group per query: that call's lists and allocation contract,
 // hnsw_mi355x_exact_knn_query_grouped's group arguments.
 API int hnsw_mi355x_exact_range_query_grouped(void *handle, const float *vectors, int count, int dim, float range, const int *row_group, long long n_row_group,

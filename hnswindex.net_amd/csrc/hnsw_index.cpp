@@ -2127,6 +2127,41 @@ int HnswIndex::exact_range_query(const float *queries, int count, int dim, float
     return exact_range_fetch(*dev_, dev_->exact_range(queries, count, length, range, allow_bits, nbits, counts), ids, dists, err);
 }
 
+// The range sink for stored rows: exact_range_query's candidates, the queries gathered on the device from ids.
+int HnswIndex::exact_range_query_by_id(const int *ids, int count, float range, const uint32_t *allow_bits, long long nbits, int *counts, std::vector<int> &out_ids,
+                                       std::vector<float> &out_dists, std::string &err)
+{
+    out_ids.clear();
+    out_dists.clear();
+    if (count <= 0) return 0;
+    for (int i = 0; i < count; ++i) counts[i] = 0;
+    if (failed(err) || !ids_live("hnsw_mi355x_exact_range_query_by_id", ids, count, err)) return -1;
+    std::vector<uint32_t> live;
+    const long long length = exact_candidates(allow_bits, nbits, live);
+    // (the scan gathers its queries into a buffer of its own: the resident set, sharded or not, stays what it was)
+    return exact_range_fetch(*dev_, dev_->exact_range_by_id(ids, count, length, range, allow_bits, nbits, counts), out_ids, out_dists, err);
+}
+
+// The duplicate groups: the members are exact_range_query's candidates; the labels come back from the device as they are.
+int HnswIndex::duplicate_groups(float range, const uint32_t *allow_bits, long long nbits, int *out_labels, long long cap, uint64_t *out_info, std::string &err)
+{
+    for (int i = 0; i < 4; ++i) out_info[i] = 0;
+    if (failed(err)) return -1;
+    const long long length_now = graph_.length;
+    if (cap < length_now) {
+        err = "System.ArgumentException: hnsw_mi355x_duplicate_groups: cap = " + std::to_string(cap) + " is below the index's length of " + std::to_string(length_now);
+        return -1;
+    }
+    if (length_now > 0 && !out_labels) { err = "System.ArgumentNullException: hnsw_mi355x_duplicate_groups: out_labels"; return -1; }
+    if (length_now <= 0) return 0;
+    std::vector<uint32_t> live;
+    const long long length = exact_candidates(allow_bits, nbits, live);
+    for (long long v = 0; v < length; ++v) out_labels[v] = -1;
+    if (graph_.count <= 0) return 0; // every slot is vacant: no member, and nothing needs the device
+    if (!dev_->exact_range_groups(length, range, allow_bits, nbits, out_labels, out_info)) { err = get_dev_error(); return -1; }
+    return 0;
+}
+
 // The range sink with a candidate group per query.  The labels go to the device as live_labels leaves them.
 int HnswIndex::exact_range_query_grouped(const float *queries, int count, int dim, float range, const int *row_group, long long n_row_group,
                                          const int *query_group, int n_groups, int *counts, std::vector<int> &ids, std::vector<float> &dists, std::string &err)

@@ -92,6 +92,13 @@ public:
     // hnsw_mi355x_exact_knn_query_by_id: row i is exact_knn_query's for that vector with allow_bits (nullptr: every live id) minus
     // ids[i] as the candidates (Device::exact_knn_by_id).  Runs on the primary context; the resident set stays what it was.
     int exact_knn_query_by_id(const int *ids, int count, int k, const uint32_t *allow_bits, long long nbits, int *out_ids, float *out_dists, std::string &err);
+    // hnsw_mi355x_exact_range_query_by_id: list i is exact_range_query's for the stored row of ids[i] with allow_bits
+    // (nullptr: every live id) minus ids[i] (Device::exact_range_by_id); counts / ids / dists as exact_range_query fills them.
+    int exact_range_query_by_id(const int *ids, int count, float range, const uint32_t *allow_bits, long long nbits, int *counts, std::vector<int> &out_ids,
+                                std::vector<float> &out_dists, std::string &err);
+    // hnsw_mi355x_duplicate_groups: the single-linkage groups of the live, allowed ids (Device::exact_range_groups);
+    // out_labels[0, length), cap >= length.
+    int duplicate_groups(float range, const uint32_t *allow_bits, long long nbits, int *out_labels, long long cap, uint64_t *out_info, std::string &err);
     // hnsw_mi355x_exact_range_query_grouped: exact_range_query with exact_knn_query_grouped's group per query
     // (Device::exact_range_grouped); the labels of vacant slots are taken out as for that call
     int exact_range_query_grouped(const float *queries, int count, int dim, float range, const int *row_group, long long n_row_group, const int *query_group,

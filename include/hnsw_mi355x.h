@@ -450,6 +450,29 @@ int hnsw_mi355x_knn_query_by_id(void *handle, const int *ids, int count, int k, 
  * query i.  1 <= k <= 1024 (k < 1: 0, nothing written; k > 1024: -1).  The resident query set stays what it was. */
 int hnsw_mi355x_exact_knn_query_by_id(void *handle, const int *ids, int count, int k, const uint32_t *allow_bits, long long nbits, int *out_ids,
                                       float *out_dists);
+/* NEAR-DUPLICATES OF STORED ITEMS: the exact range scan for stored rows, and single-linkage groups from one scan.
+ * Both run on the primary device context, take the handle exclusively and leave the resident query set as it was.
+ *
+ * hnsw_mi355x_exact_range_query_by_id: list i is byte for byte what hnsw_mi355x_exact_range_query returns for the vector
+ * hnsw_mi355x_get_vectors gives for ids[i] with the candidates "allow_bits (NULL: every live id) minus ids[i]": ascending by
+ * (distance, id), -0 and NaN as there, a NaN range gives empty lists, +inf every candidate whose distance is a number, a negative
+ * range is ordinary.  The pair (query i, row ids[i]) offers no key in the scan and is not counted in hnswdev_stats.exact_evals; a
+ * duplicate of the row under another id is an ordinary result at its distance.  ids may repeat and come in any order; one that is
+ * not live: -1 before anything is launched, with a message that names it.  A set that holds only ids[i] gives an empty list, one
+ * that does not hold ids[i] changes nothing for query i.  The allocation contract is hnsw_range_query's (hnsw_free_results); NULL
+ * handle, count <= 0, nbits < 0 and the state after an error (every pointer NULL, every count 0) as hnsw_mi355x_exact_range_query.
+ * Counted in hnsw_mi355x_by_id_info (calls, scanned, rows gathered, pairs skipped) and in hnsw_mi355x_exact_range_info. */
+int hnsw_mi355x_exact_range_query_by_id(void *handle, const int *ids, int count, float range, const uint32_t *allow_bits, long long nbits, void **out_ids,
+                                        void **out_dists, int *counts);
+/* hnsw_mi355x_duplicate_groups: the MEMBERS are the live ids that allow_bits allows (NULL: every live id), ascending.  Members
+ * a < b are joined when the distance measured with the stored row of a as the query -- handled as in the call above -- and row b as
+ * the candidate is <= range (the float compare of hnsw_mi355x_exact_range_query: a NaN distance or a NaN range joins nothing).  The
+ * groups are the connected components of that graph.  out_labels[v], v < length: the smallest member id of v's group, -1 where v is
+ * no member -- unique, whatever order the device finds the pairs in.  cap: the entries of out_labels; cap < length is -1 with a
+ * message.  out_info[0] members m, [1] groups, [2] pairs a < b within the range, [3] pairs measured = m (m - 1) / 2.  One scan
+ * whose sink is a union-find on the device: no list is built, sorted or copied.  Fewer than two members launch nothing.  NULL
+ * handle: 0, out_info zeroed.  NULL out_info, or NULL out_labels with length > 0: -1. */
+int hnsw_mi355x_duplicate_groups(void *handle, float range, const uint32_t *allow_bits, long long nbits, int *out_labels, long long cap, uint64_t out_info[4]);
 /* Counters of the by-id calls since creation or hnswdev_reset_stats / hnsw_mi355x_reset_stats, summed over the device contexts:
  * out[0] knn_query_by_id / exact_knn_query_by_id calls that reached a device, out[1] queries traversed on the device, out[2] of
  * those handed back to the host traversal, out[3] queries scanned, out[4] rows gathered (get_vectors' included), out[5] pairs
@@ -845,6 +868,16 @@ int hnswdev_knn_search_by_id(void *ctx, const int *ids, int nq, int entry_point,
  * an error that names it. */
 int hnswdev_exact_knn_by_id(void *ctx, const int *ids, int nq, long long n_rows, int k, const uint32_t *allow_bits, long long nbits, int *out_ids,
                             float *out_dists);
+/* hnswdev_exact_range whose query i is the uploaded row ids[i] and whose candidates are hnswdev_exact_range's minus ids[i]
+ * (exact_scan_kernel's ExactRangeSelf sink); the lists are kept and fetched as there (hnswdev_exact_range_results).  The resident
+ * set stays what it was.  An id that is no uploaded row is an error that names it, before any launch. */
+int hnswdev_exact_range_by_id(void *ctx, const int *ids, int nq, long long n_rows, float range, const uint32_t *allow_bits, long long nbits,
+                              int *out_counts);
+/* The scan behind hnsw_mi355x_duplicate_groups: the members are the uploaded rows [0, n_rows) that allow_bits allows, out_labels
+ * has min(n_rows, uploaded rows) entries, out_info as there.  Neither the resident set nor what hnswdev_exact_range_results has
+ * pending is touched. */
+int hnswdev_exact_range_groups(void *ctx, long long n_rows, float range, const uint32_t *allow_bits, long long nbits, int *out_labels,
+                               uint64_t out_info[4]);
 /* out[0 .. 5] as hnsw_mi355x_by_id_info, of this context; zeroed by hnswdev_reset_stats. */
 int hnswdev_by_id_info(void *ctx, uint64_t out[6]);
 /* Measurement aid: the HIP-event time, in ms, of the tagged calls' list-building kernels (count, offsets, fill) on this context
