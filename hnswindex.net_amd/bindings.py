@@ -266,6 +266,10 @@ lib.hnsw_mi355x_row_prefilter_stats.restype = ct.c_int
 lib.hnsw_mi355x_row_prefilter_stats.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
 lib.hnsw_mi355x_row_prefilter_form_stats.restype = ct.c_int
 lib.hnsw_mi355x_row_prefilter_form_stats.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
+lib.hnsw_mi355x_row_prefilter8_stats.restype = ct.c_int
+lib.hnsw_mi355x_row_prefilter8_stats.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
+lib.hnsw_mi355x_row_prefilter8_peek.restype = ct.c_int
+lib.hnsw_mi355x_row_prefilter8_peek.argtypes = [ct.c_void_p, ct.c_int, ct.c_int, ct.POINTER(ct.c_uint64), ct.POINTER(ct.c_uint8)]
 lib.hnsw_mi355x_row_prefilter_peek.restype = ct.c_int
 lib.hnsw_mi355x_row_prefilter_peek.argtypes = [ct.c_void_p, ct.c_int, ct.c_int, ct.POINTER(ct.c_uint64), ct.POINTER(ct.c_float)]
 
@@ -701,6 +705,28 @@ class Index:
         self._check(lib.hnsw_mi355x_row_prefilter_peek(self._h, int(first_id), int(count), out, rows.ctypes.data_as(ct.POINTER(ct.c_float))))
         bits = int(out[1]) & 0xffffffff
         return {"packed": int(out[0]), "e_bits": bits, "e": np.array([bits], dtype=np.uint32).view(np.float32)[0], "rows": rows}
+
+    def row_prefilter8_stats(self):
+        """Counters of the 8-bit shadow of KnnQuery's row prefilter (dim 128): launches on it, rows packed into it, rows measured on it,
+        rows re-read in f32, full packs (a fresh grid each), switches to the half-precision prefilter."""
+        names = ("launches", "rows_packed", "rows_on_shadow", "rows_reread", "full_packs", "fallbacks_to_f16")
+        out = (ct.c_uint64 * 6)()
+        if not self._h or lib.hnsw_mi355x_row_prefilter8_stats(self._h, out) != 0:
+            return dict.fromkeys(names, 0)
+        return {name: int(v) for name, v in zip(names, out)}
+
+    def row_prefilter8_peek(self, first_id: int = 0, count: int = 0):
+        """The 8-bit shadow as it stands, read only: {"packed": the watermark, "lo", "step": the grid (float32; code c stands for
+        fmaf(step, c, lo)), "e_bits" / "e": E8, "codes": the code bytes of rows [first_id, first_id + count), uint8 (count, 128)}."""
+        out = (ct.c_uint64 * 4)()
+        codes = np.zeros((max(int(count), 0), 128), dtype=np.uint8)
+        f32 = lambda v: np.array([int(v) & 0xffffffff], dtype=np.uint32).view(np.float32)[0]
+        if not self._h:
+            if count > 0:
+                raise RuntimeError("row_prefilter8_peek: the index has no 8-bit shadow rows")
+            return {"packed": 0, "lo": np.float32(0), "step": np.float32(0), "e_bits": 0, "e": np.float32(0), "codes": codes}
+        self._check(lib.hnsw_mi355x_row_prefilter8_peek(self._h, int(first_id), int(count), out, codes.ctypes.data_as(ct.POINTER(ct.c_uint8))))
+        return {"packed": int(out[0]), "lo": f32(out[1]), "step": f32(out[2]), "e_bits": int(out[3]) & 0xffffffff, "e": f32(out[3]), "codes": codes}
 
     def set_remove_batch(self, max_batch: int):
         """1 (default): remove() takes the ids one after the other; B > 1: removals with disjoint neighbourhoods together."""

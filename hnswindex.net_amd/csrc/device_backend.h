@@ -581,6 +581,11 @@ public:
     // out[1] the 32 bits of E; rows: the shadow rows [first_id, first_id + count) widened to f32, `count` x dim floats (count 0: none).
     // false for a range that is not below the watermark.  A context without a shadow has watermark 0.
     bool row_prefilter_peek(long long first_id, int count, uint64_t out[2], float *rows);
+    // The 8-bit shadow's own counters: launches, rows packed, rows measured on it, rows re-read, full packs (a fresh grid), switches to f16.
+    void row_prefilter8_stats(uint64_t out[6]);
+    // ... and the shadow as it stands, read only: out[0] the watermark, out[1] lo's bits, out[2] step's bits, out[3] E8's bits; codes: the
+    // code bytes of rows [first_id, first_id + count), kPfFixedDim each (count 0: none).  false for a range not below the watermark.
+    bool row_prefilter8_peek(long long first_id, int count, uint64_t out[4], unsigned char *codes);
 
     // C-ABI callers: one call at a time per context (hnswdev_* exports hold this), and the
     // context's own last-error string.
@@ -616,10 +621,21 @@ private:
         bool no_memory = false;            // the shadow could not be allocated: the lean form, no error
         uint64_t launches = 0, on_shadow = 0, reread = 0, rows_packed = 0;
         uint64_t form_launches[2] = {0, 0}; // of `launches`: in the run-time-length form, in the fixed-length form (kFormLeanPFFixed)
+        // The 8-bit shadow (kFormLeanPF8Fixed; rows of kPfFixedDim words): a watermark, a fallback and counters of its own beside the
+        // f16 ones, allocated by the first launch that takes it.  The counters above stay the f16 forms'; the ABI reports the totals.
+        struct Codes {
+            DevBuf<unsigned char> bytes;        // kPfFixedDim code bytes per row, `row_cap` rows
+            DevBuf<unsigned long long> words;   // [bits of E8, rows on the shadow, rows re-read, smallest | largest element key, .., word kPf8GridWord: lo | step << 32] (device-side)
+            long long row_cap = 0, packed = 0;
+            bool lost = false;                  // a launch re-read more than a quarter of its rows: the f16 prefilter until rows are written again
+            bool no_memory = false;
+            uint64_t launches = 0, on_shadow = 0, reread = 0, rows_packed = 0, full_packs = 0, fallbacks = 0;
+        } c8;
     };
     std::shared_ptr<RowPrefilter> pf_;
     void rows_written(long long first_id); // stored rows [first_id, ...) have changed, or the row matrix has moved
-    bool row_prefilter_ready();            // the shadow is allocated and current for rows [0, n_rows_hw_) (packs what is missing)
+    int row_prefilter_ready();             // 0: none; 1: the f16 shadow, 2: the 8-bit shadow is allocated and current for rows [0, n_rows_hw_) (packs what is missing)
+    bool row_prefilter8_ready();           // ... the 8-bit one (pf_->mu held)
     DevBuf<float> d_queries_;
     DevBuf<double> d_q_sn_;
     long long q_capacity() const { return (long long)(d_queries_.cap() / (size_t)pitch_); }

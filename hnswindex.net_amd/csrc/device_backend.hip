@@ -491,8 +491,13 @@ bool Device::upload_rows_wait(long long upto)
 }
 
 // ---- the row prefilter's shadow (dk_sorted_top.h) ----
-// 0: off, and nothing is ever allocated; 1 (default): on, until a launch re-reads more than half of its rows; 2: on regardless (tests)
+// 0: off, and nothing is ever allocated; 1 (default): the library chooses -- the 8-bit form where it is built for the row length
+// (pitch_ == kPfFixedDim, diag pf_fixed_dim != 0) until a launch re-reads more than a quarter of its rows, then (and everywhere else)
+// the f16 forms until a launch re-reads more than half, then the lean form; 2: the f16 forms regardless (tests: what this value always
+// selected); 3: the 8-bit form regardless, where built (tests; other row lengths: as 2)
 static int row_prefilter_mode() { return diag("row_prefilter", 1); }
+// Whether mode 1 takes the 8-bit form at all: what the A/B on C2 decided (profiles/pf8_ab_c2.json)
+constexpr bool kRowPrefilter8ByDefault = true;
 
 // THE one place that learns of a change to the stored rows: upload_rows, upload_rows_begin (the background upload of a large Add),
 // reserve (the matrix moves: everything), clone_from (everything: a re-used slot changes a row the replica already holds).
@@ -503,15 +508,65 @@ void Device::rows_written(long long first_id)
     std::lock_guard<std::mutex> lk(pf_->mu);
     pf_->packed = std::min(pf_->packed, std::max(0ll, first_id));
     pf_->lost = false; // the next launch repacks, and with other rows the prefilter may pay again
+    pf_->c8.packed = std::min(pf_->c8.packed, std::max(0ll, first_id)); // (a fallback left 0 here: the next try derives a fresh grid)
+    pf_->c8.lost = false;
 }
 
-bool Device::row_prefilter_ready()
+// The 8-bit shadow for rows [0, n_rows_hw_): allocated by the first launch that takes it; a FULL pack (watermark 0) derives the grid
+// from the rows as they stand, a partial one keeps it (rows outside are clamped, and E8 grows).  pf_->mu is held.
+bool Device::row_prefilter8_ready()
+{
+    RowPrefilter::Codes &C = pf_->c8;
+    hipStream_t st = S(stream_);
+    if (C.row_cap < capacity_ || !C.bytes) {
+        const std::string before = get_dev_error();
+        const bool first = !C.words;
+        if (!C.bytes.grow((size_t)capacity_ * kPfFixedDim) || !C.words.grow(kPf8GridWord + 1)) { // the next form down, and report nothing
+            (void)C.bytes.reset();
+            C.row_cap = C.packed = 0;
+            C.no_memory = true;
+            (void)hipGetLastError();
+            set_dev_error(before);
+            return false;
+        }
+        C.row_cap = capacity_;
+        C.packed = 0;
+        if (first) HIP_OK(hipMemsetAsync(C.words, 0, (kPf8GridWord + 1) * sizeof(unsigned long long), st));
+    }
+    const long long n = n_rows_hw_;
+    if (C.packed < n) {
+        if (C.packed == 0) { // a full pack: a fresh grid, and E8 starts over
+            static const unsigned key_start[2] = {0xffffffffu, 0u};
+            HIP_OK(hipMemcpyAsync(C.words.get() + 3, key_start, sizeof(key_start), hipMemcpyHostToDevice, st));
+            const long long elems = n * kPfFixedDim;
+            const unsigned blocks = (unsigned)std::min<long long>((elems + 255) / 256, 8192);
+            hipLaunchKernelGGL(shadow8_range_kernel, dim3(blocks), dim3(256), 0, st, d_rows_.get(), elems, reinterpret_cast<unsigned *>(C.words.get() + 3));
+            HIP_OK(hipGetLastError());
+            hipLaunchKernelGGL(shadow8_grid_kernel, dim3(1), dim3(1), 0, st, C.words.get());
+            HIP_OK(hipGetLastError());
+            C.full_packs++;
+        }
+        const long long more = n - C.packed;
+        hipLaunchKernelGGL(pack_shadow8_rows_kernel, dim3((unsigned)((more + 3) / 4)), dim3(256), 0, st, d_rows_.get(), C.packed, more, C.bytes.get(), C.words.get());
+        HIP_OK(hipGetLastError());
+        HIP_OK(hipStreamSynchronize(st)); // (the views launch on streams of their own)
+        C.rows_packed += (uint64_t)more;
+        C.packed = n;
+    }
+    return true;
+}
+
+int Device::row_prefilter_ready()
 {
     const int mode = row_prefilter_mode();
-    if (!pf_ || metric_ != M_SQ || mode == 0 || bg_.active.load() || n_rows_hw_ <= 0) return false;
+    if (!pf_ || metric_ != M_SQ || mode == 0 || bg_.active.load() || n_rows_hw_ <= 0) return 0;
     RowPrefilter &P = *pf_;
     std::lock_guard<std::mutex> lk(P.mu);
-    if (P.no_memory || (P.lost && mode != 2)) return false;
+    if (pitch_ == kPfFixedDim && !P.c8.no_memory && (mode == 3 || (mode == 1 && kRowPrefilter8ByDefault && diag("pf_fixed_dim", 1) != 0 && !P.c8.lost))) {
+        if (row_prefilter8_ready()) return 2;
+        if (!P.c8.no_memory) return 0; // (a HIP error, reported)
+    }
+    if (P.no_memory || (P.lost && mode != 2 && mode != 3)) return 0;
     hipStream_t st = S(stream_);
     const size_t words = (size_t)f16_row_words(dim_);
     if (P.row_cap < capacity_ || !P.rows) {
@@ -523,7 +578,7 @@ bool Device::row_prefilter_ready()
             P.no_memory = true;
             (void)hipGetLastError();
             set_dev_error(before);
-            return false;
+            return 0;
         }
         P.row_cap = capacity_;
         P.packed = 0;
@@ -540,7 +595,7 @@ bool Device::row_prefilter_ready()
         P.rows_packed += (uint64_t)more;
         P.packed = n;
     }
-    return true;
+    return 1;
 }
 
 void Device::row_prefilter_stats(uint64_t out[4])
@@ -548,7 +603,42 @@ void Device::row_prefilter_stats(uint64_t out[4])
     out[0] = out[1] = out[2] = out[3] = 0;
     if (!pf_) return;
     std::lock_guard<std::mutex> lk(pf_->mu);
-    out[0] = pf_->launches; out[1] = pf_->on_shadow; out[2] = pf_->reread; out[3] = pf_->rows_packed;
+    const RowPrefilter::Codes &C = pf_->c8; // (totals over both widths)
+    out[0] = pf_->launches + C.launches; out[1] = pf_->on_shadow + C.on_shadow; out[2] = pf_->reread + C.reread; out[3] = pf_->rows_packed + C.rows_packed;
+}
+
+void Device::row_prefilter8_stats(uint64_t out[6])
+{
+    std::fill_n(out, 6, (uint64_t)0);
+    if (!pf_) return;
+    std::lock_guard<std::mutex> lk(pf_->mu);
+    const RowPrefilter::Codes &C = pf_->c8;
+    out[0] = C.launches; out[1] = C.rows_packed; out[2] = C.on_shadow; out[3] = C.reread; out[4] = C.full_packs; out[5] = C.fallbacks;
+}
+
+bool Device::row_prefilter8_peek(long long first_id, int count, uint64_t out[4], unsigned char *codes)
+{
+    out[0] = out[1] = out[2] = out[3] = 0;
+    if (!pf_ || !pf_->c8.bytes || !pf_->c8.words) {
+        if (count > 0) set_dev_error("row_prefilter8_peek: the index has no 8-bit shadow rows");
+        return count <= 0;
+    }
+    if (!bind()) return false;
+    std::lock_guard<std::mutex> lk(pf_->mu); // (a pack runs under it, and waits for its kernel)
+    RowPrefilter::Codes &C = pf_->c8;
+    unsigned long long w[kPf8GridWord + 1] = {};
+    HIP_OK(hipMemcpy(w, C.words.get(), sizeof(w), hipMemcpyDeviceToHost));
+    out[0] = (uint64_t)C.packed;
+    out[1] = (uint64_t)(w[kPf8GridWord] & 0xffffffffull);
+    out[2] = (uint64_t)(w[kPf8GridWord] >> 32);
+    out[3] = (uint64_t)(w[0] & 0xffffffffull);
+    if (count <= 0) return true;
+    if (first_id < 0 || first_id + count > C.packed || !codes) {
+        set_dev_error("row_prefilter8_peek: range outside the packed shadow rows");
+        return false;
+    }
+    HIP_OK(hipMemcpy(codes, C.bytes.get() + (size_t)first_id * kPfFixedDim, (size_t)count * kPfFixedDim, hipMemcpyDeviceToHost));
+    return true;
 }
 
 void Device::row_prefilter_form_stats(uint64_t out[2])
@@ -1258,7 +1348,8 @@ struct TraversalLaunch {
     // per launch
     bool prefilter;      // the lean form's row prefilter may run: the index's shadow rows are current (search_batch_impl says so)
     bool pf_fixed;       // ... in its fixed-length form: the row length is kPfFixedDim words (diag pf_fixed_dim=0: the run-time form)
-    int form;            // kFormLat, kFormLean, kFormLeanPF, kFormLeanPFFixed, kFormPlain
+    bool pf8;            // ... on the 8-bit shadow (row_prefilter_ready() == 2; the row length then is kPfFixedDim words)
+    int form;            // kFormLat, kFormLean, kFormLeanPF, kFormLeanPFFixed, kFormLeanPF8Fixed, kFormPlain
     int slots, grid;     // the form's resident waves; grid = min(jobs, slots)
     unsigned block;      // 128 threads for the latency form (logic wave + memory wave), else 64
     size_t lds_total;    // lds, plus kTeamLds of mailbox for the latency form
@@ -1273,7 +1364,7 @@ bool Device::plan_traversal(bool insert, int k, bool two_heap, size_t lds, Trave
     t->num_cu = num_cu_;
     t->lds = lds;
     t->filtered = filtered;
-    t->prefilter = false;
+    t->prefilter = t->pf8 = false;
     t->pf_fixed = pitch_ == kPfFixedDim && diag("pf_fixed_dim", 1) != 0; // (pitch_: the kernels' `dim` argument)
     t->exact_only = ns == 0; // two_heap callers, beams beyond 512 entries, diag sorted_top=0, filtered searches
     t->ns = t->exact_only ? 2 : ns;
@@ -1306,7 +1397,8 @@ static auto traversal_form(int form)
         return form == kFormLat ? &graph_search_kernel<M, NS, H, kFormLat>
                : form == kFormLean ? &graph_search_kernel<M, NS, H, kFormLean>
                : form == kFormLeanPF ? &graph_search_kernel<M, NS, H, kFormLeanPF>
-               : form == kFormLeanPFFixed ? &graph_search_kernel<M, NS, H, kFormLeanPFFixed> : &graph_search_kernel<M, NS, H, kFormPlain>;
+               : form == kFormLeanPFFixed ? &graph_search_kernel<M, NS, H, kFormLeanPFFixed>
+               : form == kFormLeanPF8Fixed ? &graph_search_kernel<M, NS, H, kFormLeanPF8Fixed> : &graph_search_kernel<M, NS, H, kFormPlain>;
     else
         return form == kFormLat ? &graph_search_kernel<M, NS, H, kFormLat> : &graph_search_kernel<M, NS, H, kFormPlain>;
 }
@@ -1357,7 +1449,7 @@ static auto place_traversal(TraversalLaunch &t, int nj)
         const int slots = std::min(t.max_slots, resident_blocks(traversal_kernel<Insert>(t, kFormLat), t.lds + kTeamLds, t.num_cu, 128));
         if (slots > 0 && (lat == 2 || nj <= slots)) { t.form = kFormLat; t.slots = slots; }
     }
-    if (!Insert && t.form == kFormPlain && t.novis && !t.exact_only && lean_mode() && t.ns <= 4) t.form = !t.prefilter ? kFormLean : t.pf_fixed ? kFormLeanPFFixed : kFormLeanPF;
+    if (!Insert && t.form == kFormPlain && t.novis && !t.exact_only && lean_mode() && t.ns <= 4) t.form = !t.prefilter ? kFormLean : t.pf8 ? kFormLeanPF8Fixed : t.pf_fixed ? kFormLeanPFFixed : kFormLeanPF;
     const auto kernel = traversal_kernel<Insert>(t, t.form);
     if (t.form != kFormLat) t.slots = std::min(t.max_slots, resident_blocks(kernel, t.lds, t.num_cu));
     t.grid = std::min(nj, t.slots);
@@ -1913,11 +2005,16 @@ bool Device::search_batch_impl(const SearchJob *jobs, int njobs, int k, int k_ou
         // a launch that would take the lean form takes its row-prefilter variant where the index has current shadow rows (the
         // first such launch allocates and packs them, a launch after an Add packs what is new)
         auto kernel = place_traversal<false>(tl, nj);
-        if (tl.form == kFormLean && row_prefilter_ready()) {
-            tl.prefilter = true;
-            kernel = place_traversal<false>(tl, nj);
+        if (tl.form == kFormLean) {
+            const int shadow = row_prefilter_ready(); // 1: the f16 shadow, 2: the 8-bit one
+            if (shadow != 0) {
+                tl.prefilter = true;
+                tl.pf8 = shadow == 2;
+                kernel = place_traversal<false>(tl, nj);
+            }
         }
-        const bool prefiltered = form_is_pf(tl.form);
+        const bool prefiltered = form_is_pf(tl.form), pf8 = form_is_pf8(tl.form);
+        unsigned long long *const pf_words = !prefiltered ? nullptr : pf8 ? pf_->c8.words.get() : pf_->words.get();
         HIP_OK(hipMemsetAsync(s_jobctr_, 0, sizeof(int) * (4 + (size_t)nj), st));
         if (!compact) HIP_OK(hipMemsetAsync(s_evals_, 0, sizeof(unsigned long long), st));
         const bool timed = profiling_;
@@ -1925,13 +2022,13 @@ bool Device::search_batch_impl(const SearchJob *jobs, int njobs, int k, int k_ou
         hipLaunchKernelGGL(kernel, dim3(tl.grid), dim3(tl.block), tl.lds_total, st, d_rows_, d_row_sn_, d_queries_, d_q_sn_, pitch_, g_adj0_, g_stride0_,
                            g_upper_, g_pool_, g_strideU_, s_jobs_, k, cand_cap, reinterpret_cast<ND *>(s_spill_.get()), spill_cap_for_tests(), s_visited_,
                            tl.vis.words, tl.vis.tab, tl.vis.tab_cap, k_out, d_ids, d_d, s_cnt_, d_flag, d_ev, nbcap(), nj, s_jobctr_,
-                           tl.flags | (shadow_mode() && shadows_allowed_ ? 0x100 : 0), gate, prefiltered ? pf_->rows.get() : (const float *)nullptr,
-                           prefiltered ? pf_->words.get() : (unsigned long long *)nullptr);
+                           tl.flags | (shadow_mode() && shadows_allowed_ ? 0x100 : 0), gate,
+                           !prefiltered ? (const float *)nullptr : pf8 ? reinterpret_cast<const float *>(pf_->c8.bytes.get()) : pf_->rows.get(), pf_words);
         if (tl.form == kFormLat) stats_.lat_launches++;
         if (form_is_lean(tl.form)) stats_.lean_launches++;
         HIP_OK(hipGetLastError());
         if (timed) HIP_OK(hipEventRecord(E(ev1_), st));
-        if (prefiltered) HIP_OK(hipMemcpyAsync(h_pf, pf_->words.get() + 1, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+        if (prefiltered) HIP_OK(hipMemcpyAsync(h_pf, pf_words + 1, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
         if (tail_.n > 0 && !upload_tail()) return false; // the rest of the query set, while the launch above is running
         if (compact) { // [ids | distances | flags] in one piece (nj == chunk: the device slab and the staging are laid out alike)
             HIP_OK(hipMemcpyAsync(h_ids, d_ids, 2 * b_res + sizeof(int) * (size_t)nj, hipMemcpyDeviceToHost, st));
@@ -1961,6 +2058,15 @@ bool Device::search_batch_impl(const SearchJob *jobs, int njobs, int k, int k_ou
             else if (h_flag[i] == 4) { stats_.tie_windows++; h_flag[i] = 0; } // informational: a group window closed cleanly
         }
         memcpy(out_flag + off, h_flag, sizeof(int) * (size_t)nj);
+        if (pf8) { // 128 + p * 512 B against the f16 shadow's 256 B breaks even at p = 1/4: from there the f16 prefilter, and a fresh grid next time
+            std::lock_guard<std::mutex> lk(pf_->mu);
+            RowPrefilter::Codes &C = pf_->c8;
+            const uint64_t d_shadow = h_pf[0] > C.on_shadow ? h_pf[0] - C.on_shadow : 0, d_reread = h_pf[1] > C.reread ? h_pf[1] - C.reread : 0;
+            C.launches++;
+            C.on_shadow += d_shadow;
+            C.reread += d_reread;
+            if (4 * d_reread > d_shadow && row_prefilter_mode() == 1 && !C.lost) { C.lost = true; C.packed = 0; C.fallbacks++; }
+        } else
         if (prefiltered) { // the device words are cumulative; a launch that re-read more than half of its rows cost more than it saved
             std::lock_guard<std::mutex> lk(pf_->mu);
             const uint64_t d_shadow = h_pf[0] > pf_->on_shadow ? h_pf[0] - pf_->on_shadow : 0, d_reread = h_pf[1] > pf_->reread ? h_pf[1] - pf_->reread : 0;
@@ -1970,7 +2076,7 @@ bool Device::search_batch_impl(const SearchJob *jobs, int njobs, int k, int k_ou
             pf_->reread += d_reread;
             if (2 * d_reread > d_shadow && row_prefilter_mode() != 2) pf_->lost = true;
         }
-        tl.prefilter = false; // (decided per launch)
+        tl.prefilter = tl.pf8 = false; // (decided per launch)
         if (!count_launch(nullptr, *h_ev, tl.vis.tab != nullptr, timed, ev0_, ev1_)) return false;
     }
     for (int i = 0; i < njobs; ++i) stats_.search_overflows += (uint64_t)(out_flag[i] == 1);

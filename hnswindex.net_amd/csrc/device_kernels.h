@@ -53,12 +53,13 @@ namespace hnsw {
     X(M, 2, true, kFormLat) X(M, 4, true, kFormLat)
 // the lean forms of graph_search_kernel (round 5; kFormLean in dk_base.h): beams up to 256 entries, launches without visited sets;
 // units of their own.  (The insert kernel has none: measured, its f32 form loses 6 % that way.)  Beside them their row-prefilter
-// variants (kFormLeanPF, and kFormLeanPFFixed with the row length compiled in): real kernels for sq_euclid, empty ones for every other
+// variants (kFormLeanPF, kFormLeanPFFixed with the row length compiled in, and kFormLeanPF8Fixed on the 8-bit shadow): real kernels for sq_euclid, empty ones for every other
 // metric (graph_search_kernel), never launched there.
 #define HNSW_FOR_EACH_TRAVERSAL_LEAN(X, M) \
     X(M, 2, false, kFormLean) X(M, 4, false, kFormLean) X(M, 2, true, kFormLean) X(M, 4, true, kFormLean) \
     X(M, 2, false, kFormLeanPF) X(M, 4, false, kFormLeanPF) X(M, 2, true, kFormLeanPF) X(M, 4, true, kFormLeanPF) \
-    X(M, 2, false, kFormLeanPFFixed) X(M, 4, false, kFormLeanPFFixed) X(M, 2, true, kFormLeanPFFixed) X(M, 4, true, kFormLeanPFFixed)
+    X(M, 2, false, kFormLeanPFFixed) X(M, 4, false, kFormLeanPFFixed) X(M, 2, true, kFormLeanPFFixed) X(M, 4, true, kFormLeanPFFixed) \
+    X(M, 2, false, kFormLeanPF8Fixed) X(M, 4, false, kFormLeanPF8Fixed) X(M, 2, true, kFormLeanPF8Fixed) X(M, 4, true, kFormLeanPF8Fixed)
 
 // The kinds of kernel unit, X(kind, ...), and what each instantiates for a metric M: HNSW_UNIT_<kind>(DEFINE, M) is the unit's
 // content (kernel_unit.hip), HNSW_UNIT_<kind>(DECLARE, M) the extern template declarations of everyone else.  build.py's KINDS

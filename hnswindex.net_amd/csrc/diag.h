@@ -14,7 +14,8 @@
 //       exact_union_round [0 = 65 536 members are the queries of one launch of duplicate_groups' scan]
 //       tag_list_cap [0 = 2^28 ids in the candidate lists of one batch of masks of exact_knn_tagged]
 //       range_sort_long [1; 0 = range_sort_tagged_kernel hands a closure beyond its table to the host as the other two sorts do]
-//       graph_unchecked [0]  row_prefilter [1; 0 = off, nothing allocated; 2 = kept on after a launch that re-read most rows]
+//       graph_unchecked [0]  row_prefilter [1 = the library chooses the shadow width; 0 = off, nothing allocated;
+//       2 = the f16 forms, kept on after a launch that re-read most rows; 3 = the 8-bit form, where built (row length 128), kept on likewise]
 //       pf_fixed_dim [1; 0 = the row prefilter's run-time-length kernel form also where the row length is the compiled-in one]
 #pragma once
 #include <cstdlib>

@@ -23,6 +23,9 @@
 #ifndef HNSW_PF_FIXED_WAVES // waves per SIMD of the fixed-length row-prefilter kernels (kFormLeanPFFixed): 124-128 VGPRs, nothing spilled
 #define HNSW_PF_FIXED_WAVES 4
 #endif
+#ifndef HNSW_PF8_WAVES // waves per SIMD of the 8-bit row-prefilter kernels (kFormLeanPF8Fixed): the shadow pass holds 16 VGPRs of loads where the f16 pass holds 32
+#define HNSW_PF8_WAVES 4
+#endif
 
 namespace hnsw {
 
@@ -64,9 +67,13 @@ __device__ __forceinline__ void wave_lds_sync()
 // LEAN_PF_FIXED: LEAN_PF with the row length (in 32-bit words) compiled in -- kPfFixedDim, assigned to `dim` as graph_search_kernel's
 // first statement, so the trip counts of the measure passes are constants: four waves per SIMD without a spilled register, where
 // the run-time length spills 55-59 at that occupancy.  Launched where the index's row length is kPfFixedDim (place_traversal).
-constexpr int kFormPlain = 0, kFormLat = 1, kFormLean = 2, kFormLeanPF = 3, kFormLeanPFFixed = 4;
+// LEAN_PF8_FIXED: LEAN_PF_FIXED with the shadow pass on 8-bit codes -- 128 code bytes per row, ONE cache line, decoded on one
+// index-wide grid as fmaf(step, code, lo) (measure_shadow8, dk_sorted_top.h); the same decision with E8 for E.
+constexpr int kFormPlain = 0, kFormLat = 1, kFormLean = 2, kFormLeanPF = 3, kFormLeanPFFixed = 4, kFormLeanPF8Fixed = 5;
 constexpr int kPfFixedDim = 128; // the one length built (another one goes in with an A/B of its own)
-constexpr __host__ __device__ bool form_is_pf(int f) { return f == kFormLeanPF || f == kFormLeanPFFixed; }
+constexpr __host__ __device__ bool form_is_pf8(int f) { return f == kFormLeanPF8Fixed; }
+constexpr __host__ __device__ bool form_is_pf_fixed(int f) { return f == kFormLeanPFFixed || f == kFormLeanPF8Fixed; }
+constexpr __host__ __device__ bool form_is_pf(int f) { return f == kFormLeanPF || form_is_pf_fixed(f); }
 constexpr __host__ __device__ bool form_is_lean(int f) { return f == kFormLean || form_is_pf(f); }
 
 // A kernel argument read again from the kernarg segment at the point of use (a scalar load that hits the constant cache) instead of

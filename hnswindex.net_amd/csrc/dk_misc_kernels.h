@@ -148,6 +148,84 @@ pack_shadow_rows_kernel(const float *__restrict__ src, int dim, long long first,
         atomicMax(e_bits, bits);
     }
 }
+// ---- the 8-bit shadow of the row prefilter (kFormLeanPF8Fixed; dk_sorted_top.h) ----
+// words: [bits of E8, rows on the shadow, rows re-read, smallest key | largest key << 32, .., word kPf8GridWord: lo | step << 32] -- the
+// key word as two 32-bit halves (the ordered keys of f2key, so that negative elements order like their values).
+// 1. the smallest and the largest FINITE element of src[0 .. n_elems): keys start at {0xffffffff, 0}
+__global__ void __launch_bounds__(256)
+shadow8_range_kernel(const float *__restrict__ src, long long n_elems, unsigned *__restrict__ keys)
+{
+    unsigned kmin = 0xffffffffu, kmax = 0u;
+    for (long long t = (long long)blockIdx.x * 256 + threadIdx.x; t < n_elems; t += (long long)gridDim.x * 256) {
+        const float x = src[t];
+        if (x - x == 0.0f) { const unsigned k = f2key(x); kmin = k < kmin ? k : kmin; kmax = k > kmax ? k : kmax; }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned a = (unsigned)__shfl_xor((int)kmin, o, 64), b = (unsigned)__shfl_xor((int)kmax, o, 64);
+        kmin = a < kmin ? a : kmin; kmax = b > kmax ? b : kmax;
+    }
+    if ((threadIdx.x & 63) == 0 && kmin <= kmax) { atomicMin(keys, kmin); atomicMax(keys + 1, kmax); }
+}
+// 2. the grid of a FULL pack: lo = the smallest element, step = (hi - lo) / 255 rounded up (1 when hi == lo or no element is finite:
+// any positive value will do); E8 starts over.  One thread.
+__global__ void shadow8_grid_kernel(unsigned long long *__restrict__ words)
+{
+    const unsigned *keys = reinterpret_cast<const unsigned *>(words + 3);
+    float lo = 0.0f, step = 1.0f;
+    if (keys[0] <= keys[1]) {
+        lo = key2f(keys[0]);
+        const double s = ((double)key2f(keys[1]) - (double)lo) / 255.0;
+        if (s > 0.0) {
+            step = (float)s;
+            if ((double)step < s) step = __uint_as_float(__float_as_uint(step) + 1u); // (a range beyond 255 FLT_MAX: +inf, and E8 with it)
+        }
+    }
+    words[kPf8GridWord] = (unsigned long long)__float_as_uint(lo) | ((unsigned long long)__float_as_uint(step) << 32);
+    words[0] = 0ull;
+}
+// 3. rows [first, first + n) -> their code bytes (element i at byte i of record r, kPfFixedDim bytes per record), one wave per row:
+// the nearest grid point, clamped to [0, 255] -- rows packed later keep the grid and clamp.  Which point the encoder picks is not
+// part of the proof: the bound is taken from the DECODED value h8 = fmaf(step, (float)c, lo), the search kernel's own expression,
+// exactly as pack_shadow_rows_kernel takes E from h(x): squares of x - h8 summed in double, the root rounded up to float and raised
+// by 2^-20, atomicMax on the bits; an element or a decoded value that is not finite makes E8 = +inf.
+__global__ void __launch_bounds__(256)
+pack_shadow8_rows_kernel(const float *__restrict__ src, long long first, long long n, unsigned char *__restrict__ dst, unsigned long long *__restrict__ words)
+{
+    const int lane = threadIdx.x & 63;
+    const long long r = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= n) return;
+    const unsigned long long grid = words[kPf8GridWord];
+    const float lo = __uint_as_float((unsigned)grid), step = __uint_as_float((unsigned)(grid >> 32));
+    const float *x = src + (size_t)(first + r) * kPfFixedDim;
+    unsigned char *rec = dst + (size_t)(first + r) * kPfFixedDim;
+    double ss = 0.0;
+    bool finite = true;
+    for (int i = lane; i < kPfFixedDim; i += 64) {
+        const float xi = x[i];
+        const double t = ((double)xi - (double)lo) / (double)step; // (in double: a float quotient near 255 is off by 3e-5 of a step, which picks the wrong side of a midpoint)
+        const int c = t > 0.0 ? (t < 255.0 ? (int)__builtin_rint(t) : 255) : 0; // (NaN: 0)
+        rec[i] = (unsigned char)c;
+        const float h = __builtin_fmaf(step, (float)c, lo);
+        finite = finite && (h - h == 0.0f) && (xi - xi == 0.0f);
+        const double d = (double)xi - (double)h;
+        ss += d * d;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o, 64);
+    const bool all_finite = __ballot(!finite) == 0ull;
+    if (lane == 0) {
+        unsigned bits = 0x7f800000u; // +inf
+        if (all_finite && ss < 1e300) {
+            const double e = sqrt(ss);
+            float f = (float)e;
+            if ((double)f < e) f = __uint_as_float(__float_as_uint(f) + 1u); // (f >= 0: the next float up)
+            f = f * 1.00000095367431640625f + 1e-37f; // the double sum's own rounding, and away from the subnormals
+            bits = __float_as_uint(f);
+        }
+        atomicMax(reinterpret_cast<unsigned *>(words), bits);
+    }
+}
 // records -> the stored rows widened to float (hnswdev_download_rows on a half-precision context)
 __global__ void __launch_bounds__(256)
 unpack_f16_rows_kernel(const float *__restrict__ recs, long long first, int n, int dim, float *__restrict__ out)

@@ -21,7 +21,7 @@ struct SearchKernArgs {
     const int64_t *upper; const int *pool; int strideU; const SearchJob *jobs; int k, cand_cap; ND *spill; int spill_cap;
     unsigned *visited; long long vis_words; int *vis_tab; int vis_tab_cap, k_out; int *out_ids; float *out_d; int *out_cnt, *out_flag;
     unsigned long long *eval_counter; int nbcap, njobs; int *job_counter; int overlap; const int *ready;
-    const float *pf_rows; unsigned long long *pf_words; // the row prefilter (kFormLeanPF, kFormLeanPFFixed): shadow records; [E's bits, rows on the shadow, rows re-read]
+    const float *pf_rows; unsigned long long *pf_words; // the row prefilter (kFormLeanPF, kFormLeanPFFixed): shadow records; [E's bits, rows on the shadow, rows re-read]; kFormLeanPF8Fixed: the code bytes; [E8's bits, on the shadow, re-read, .., word kPf8GridWord: lo | step << 32]
 };
 static_assert(offsetof(SearchKernArgs, jobs) == 80 && offsetof(SearchKernArgs, out_ids) == 144 && offsetof(SearchKernArgs, ready) == 208 &&
               offsetof(SearchKernArgs, pf_rows) == 216 && offsetof(SearchKernArgs, pf_words) == 224 && sizeof(SearchKernArgs) == 232,
@@ -145,8 +145,9 @@ __device__ __forceinline__ void search_job(const float *__restrict__ rows, const
         else if constexpr (PF) {
             // E is read once per job (a scalar load); the job's two row counts go to the words behind it
             unsigned long long *const words = HNSW_KA(pf_words);
-            RowPrefilterIo pf{HNSW_KA(pf_rows), __uint_as_float(*reinterpret_cast<const unsigned *>(words)), row_prefilter_c(dim), 0u, 0u};
-            ok1 = traverse_sorted<METRIC, NS, HASHED, true, true>(rows, row_sn, dim, sb, G, jb, k, k_out + 1, V, L, lane, top_n, tie, evals, overlap, RL, nullptr, &window, &pf);
+            RowPrefilterIo pf{nullptr, 0.0f, row_prefilter_c(dim), 0u, 0u, (unsigned)offsetof(SearchKernArgs, pf_rows), (unsigned)offsetof(SearchKernArgs, pf_words)};
+            if constexpr (!form_is_pf8(FORM)) { pf.rows = HNSW_KA(pf_rows); pf.e = __uint_as_float(*reinterpret_cast<const unsigned *>(words)); }
+            ok1 = traverse_sorted<METRIC, NS, HASHED, true, true, form_is_pf8(FORM)>(rows, row_sn, dim, sb, G, jb, k, k_out + 1, V, L, lane, top_n, tie, evals, overlap, RL, nullptr, &window, &pf);
             if (lane == 0) { atomicAdd(words + 1, (unsigned long long)pf.n_shadow); atomicAdd(words + 2, (unsigned long long)pf.n_reread); }
         }
         else ok1 = traverse_sorted<METRIC, NS, HASHED, LEAN>(rows, row_sn, dim, sb, G, jb, k, k_out + 1, V, L, lane, top_n, tie, evals, overlap, RL, nullptr, &window);
@@ -237,9 +238,10 @@ __device__ __forceinline__ void search_job(const float *__restrict__ rows, const
 template <int METRIC, int NS, bool HASHED, int FORM = kFormPlain>
 // float rows: 168 VGPRs, three waves per SIMD; int8 records keep 16 registers of rows in flight, not 64: five waves.
 // The fixed-length row-prefilter form (kFormLeanPFFixed): 124-128 VGPRs, four waves.
+// Its 8-bit variant (kFormLeanPF8Fixed): four waves as well (profiles/pf8_kernel_resources.json).
 // LAT (launches that do not fill the chip): no occupancy to buy -- every spilled register is a memory round trip a lone wave
 // waits out in full -- so two waves per SIMD at most (256 VGPRs), one with eight register sets
-__global__ void __launch_bounds__(FORM == kFormLat ? 128 : 64) __attribute__((amdgpu_waves_per_eu(HNSW_WAVES(FORM == kFormLat ? (NS <= 4 ? 2 : 1) : FORM == kFormLeanPF ? HNSW_PF_WAVES : FORM == kFormLeanPFFixed ? HNSW_PF_FIXED_WAVES : METRIC == M_I8 ? (NS <= 2 ? HNSW_I8_WAVES : 4) : (NS <= 4 ? 3 : 2)))))
+__global__ void __launch_bounds__(FORM == kFormLat ? 128 : 64) __attribute__((amdgpu_waves_per_eu(HNSW_WAVES(FORM == kFormLat ? (NS <= 4 ? 2 : 1) : FORM == kFormLeanPF ? HNSW_PF_WAVES : FORM == kFormLeanPFFixed ? HNSW_PF_FIXED_WAVES : FORM == kFormLeanPF8Fixed ? HNSW_PF8_WAVES : METRIC == M_I8 ? (NS <= 2 ? HNSW_I8_WAVES : 4) : (NS <= 4 ? 3 : 2)))))
 graph_search_kernel(const float *__restrict__ rows, const double *__restrict__ row_sn, const float *__restrict__ queries,
                     const double *__restrict__ q_sn, int dim, const int *__restrict__ adj0, int stride0,
                     const int64_t *__restrict__ upper, const int *__restrict__ pool, int strideU,
@@ -252,7 +254,7 @@ graph_search_kernel(const float *__restrict__ rows, const double *__restrict__ r
     constexpr bool LAT = FORM == kFormLat, LEAN = form_is_lean(FORM);
     if constexpr (form_is_pf(FORM) && METRIC != M_SQ) return; // (the row prefilter exists for sq_euclid on f32 rows: never launched elsewhere)
     else {
-    if constexpr (FORM == kFormLeanPFFixed) dim = kPfFixedDim; // (the launch site checks that the argument is this value: place_traversal)
+    if constexpr (form_is_pf_fixed(FORM)) dim = kPfFixedDim; // (the launch site checks that the argument is this value: place_traversal)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x & 63;
     // (the lean form looks its visited set and spill area up when a job takes the exact traversal: search_job)

@@ -267,7 +267,18 @@ struct RowPrefilterIo {
     const float *rows; // the shadow records (f16_row_words(dim) words per row)
     float e, c;        // E and 1 + 1.5 g
     unsigned n_shadow, n_reread; // rows this job measured on the shadow / measured again from f32
+    // The 8-bit shadow (kFormLeanPF8Fixed) carries nothing from expansion to expansion: `rows` and `e` stay unset, and the code
+    // pointer, E8 and the grid are read where they are used (kernarg_load, then scalar loads that hit the constant cache) -- the four
+    // register sets of the bitset form spilled two VGPRs with them held in SGPRs.  Byte offsets of the two kernel arguments:
+    unsigned ka_codes, ka_words; // the code bytes (kPfFixedDim per row); [E8's bits, on the shadow, re-read, -, -, .., word kPf8GridWord: lo | step << 32]
 };
+// E8 and the grid are written before the launch and by nothing in it: read through the constant address space (uniform: scalar loads)
+constexpr int kPf8GridWord = 16; // (a line of its own: the counters in front of it take every job's atomics)
+__device__ __forceinline__ unsigned long long pf8_word(unsigned ka_words, int i)
+{
+    typedef const unsigned long long __attribute__((address_space(4))) *cptr;
+    return ((cptr)(unsigned long long)kernarg_load<unsigned long long *>(ka_words))[i];
+}
 __device__ __forceinline__ float row_prefilter_c(int dim) { return 1.0f + 1.5f * (1.001f * (float)((dim >> 3) + 16) * 5.9604644775390625e-8f); }
 __device__ __forceinline__ float row_prefilter_threshold(float far, float e, float c)
 {
@@ -287,9 +298,73 @@ __device__ __forceinline__ void measure_shadow(const float *shadow, int dim, con
     }
 }
 
+// ---- the 8-bit shadow (kFormLeanPF8Fixed; rows of kPfFixedDim elements) ---------------------------------------------------------
+// A row's record is its kPfFixedDim code bytes, element i at byte i: one 128-byte line.  The shadow value of code c is BY DEFINITION
+// the f32 number h8 = fmaf(step, (float)c, lo) -- the pack kernel (pack_shadow8_rows_kernel) bounds ||x - h8(x)||_2 with exactly
+// that expression, so decoding adds no rounding to the proof above, which holds with E8 for E.  Eight lanes per row, lane j holds
+// the 16 elements 16 j .. 16 j + 15 in ONE 16-byte load (an 8-lane group reads exactly one line); up to four rows per lane in flight
+// (16 VGPRs of loads where measure_pass_h holds 32).  Arithmetic: the codes are widened one by one (v_cvt_f32_ubyteN), decoding,
+// difference and square run two-wide (v_pk_fma_f32 / v_pk_add_f32 round each half like the scalar instruction).  A term passes
+// through the subtraction (counted twice), at most 8 fmas of its accumulator half, the sum of the two halves and the collapse (3):
+// 14 roundings, under the dim / 8 + 14 = 30 that g is derived for -- the lane chain is SHORTER than measure_pass_h's (16), g stays.
+template <int NP>
+__device__ __forceinline__ void measure_pass_c8(const unsigned char *__restrict__ codes, unsigned ka_words, const float *qs, const int *nbuf,
+                                                float *dbuf, int p0, int m, int lane)
+{
+    const int grp = lane >> 3, j = lane & 7;
+    u32x4 w[NP];
+    int cidx[NP];
+#pragma unroll
+    for (int p = 0; p < NP; ++p) {
+        const int c = p0 + grp + 8 * p;
+        cidx[p] = c;
+        const int id = nbuf[c < m ? c : p0]; // idle groups shadow a valid row
+        w[p] = *reinterpret_cast<const u32x4 *>(codes + (size_t)id * kPfFixedDim + 16 * j);
+    }
+    __builtin_amdgcn_sched_barrier(0); // every load of the pass before any arithmetic: one memory round trip
+    const unsigned long long grid = pf8_word(ka_words, kPf8GridWord);
+    const float lo = __uint_as_float((unsigned)grid), step = __uint_as_float((unsigned)(grid >> 32));
+    const f32x2 lo2 = {lo, lo}, step2 = {step, step};
+    f32x2 acc[NP];
+#pragma unroll
+    for (int p = 0; p < NP; ++p) acc[p] = f32x2{0.0f, 0.0f};
+    const float *q = qs + 16 * j;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        const f32x4 y = *reinterpret_cast<const f32x4 *>(q + 4 * t);
+        const f32x2 y01 = {y.x, y.y}, y23 = {y.z, y.w};
+#pragma unroll
+        for (int p = 0; p < NP; ++p) {
+            const unsigned ww = w[p][t];
+            const f32x2 c01 = {(float)(ww & 0xffu), (float)((ww >> 8) & 0xffu)}, c23 = {(float)((ww >> 16) & 0xffu), (float)(ww >> 24)};
+            const f32x2 h01 = __builtin_elementwise_fma(step2, c01, lo2), h23 = __builtin_elementwise_fma(step2, c23, lo2);
+            const f32x2 d01 = y01 - h01, d23 = y23 - h23;
+            acc[p] = __builtin_elementwise_fma(d01, d01, acc[p]);
+            acc[p] = __builtin_elementwise_fma(d23, d23, acc[p]);
+        }
+    }
+#pragma unroll
+    for (int p = 0; p < NP; ++p) {
+        const float lane_sum = acc[p].x + acc[p].y;
+        const float s = collapse_l2(lane_sum);
+        if (j == 0 && cidx[p] < m) dbuf[cidx[p]] = s;
+    }
+}
+// D_8 of nbuf[0..m) on the 8-bit shadow: measure_shadow's pass widths
+__device__ __forceinline__ void measure_shadow8(const unsigned char *codes, unsigned ka_words, const float *qs, const int *nbuf, float *dbuf, int m, int lane)
+{
+    for (int p0 = 0; p0 < m; p0 += 32) {
+        const int left = m - p0;
+        if (left > 24) measure_pass_c8<4>(codes, ka_words, qs, nbuf, dbuf, p0, m, lane);
+        else if (left > 16) measure_pass_c8<3>(codes, ka_words, qs, nbuf, dbuf, p0, m, lane);
+        else if (left > 8) measure_pass_c8<2>(codes, ka_words, qs, nbuf, dbuf, p0, m, lane);
+        else measure_pass_c8<1>(codes, ka_words, qs, nbuf, dbuf, p0, m, lane);
+    }
+}
+
 // Returns false on a NaN / -0 distance (exact host re-run); `tie` asks for the exact two-heap
 // traversal.  Result: L.top[0..top_n) ascending by distance.  The query must be staged in L.qs.
-template <int METRIC, int NS, bool HASHED, bool LEAN = false, bool PF = false>
+template <int METRIC, int NS, bool HASHED, bool LEAN = false, bool PF = false, bool PF8 = false>
 __device__ __forceinline__ bool traverse_sorted(const float *__restrict__ rows, const double *__restrict__ row_sn, int dim, double sb,
                                                 const GraphView &G, const SearchJob jb, int k, int ordered_prefix, VisitedSet<HASHED> &V,
                                                 const SearchLds &L, int lane, int &top_n_out, bool &tie_out, unsigned long long &evals,
@@ -409,10 +484,15 @@ __device__ __forceinline__ bool traverse_sorted(const float *__restrict__ rows, 
             int pf_pos = 0;
             if constexpr (PF) {
                 if (n > 0) {
+                    if constexpr (PF8) measure_shadow8(kernarg_load<const unsigned char *>(pf->ka_codes), pf->ka_words, qs, nbuf, dbuf, n, lane);
+                    else
                     measure_shadow(pf->rows, dim, qs, nbuf, dbuf, n, lane);
                     wave_sync();
                     const float dh = in ? dbuf[lane] : 0.0f;
-                    const float thr = top_n >= k ? row_prefilter_threshold(key2f(far_key), pf->e, pf->c) : __uint_as_float(0x7f800000u);
+                    float e_bound;
+                    if constexpr (PF8) e_bound = __uint_as_float((unsigned)pf8_word(pf->ka_words, 0));
+                    else e_bound = pf->e;
+                    const float thr = top_n >= k ? row_prefilter_threshold(key2f(far_key), e_bound, pf->c) : __uint_as_float(0x7f800000u);
                     pf_keep = in && !(dh > thr); // (nothing is turned away while the list is not full; NaN keeps the row)
                     const unsigned long long km = __ballot(pf_keep);
                     pf_pos = __builtin_amdgcn_mbcnt_hi((unsigned)(km >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)km, 0));

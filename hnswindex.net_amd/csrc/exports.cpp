@@ -764,6 +764,22 @@ API int hnsw_mi355x_row_prefilter_peek(void *h, int first_id, int count, uint64_
     if (!static_cast<HnswIndex *>(h)->row_prefilter_peek(first_id, count, out, rows, err)) { set_error(err); return -1; }
     return 0;
 }
+// The 8-bit shadow's own counters and read-back.  Argument errors: -1 with a message.
+API int hnsw_mi355x_row_prefilter8_stats(void *h, uint64_t out[6])
+{
+    if (!h || !out) { set_error("System.ArgumentNullException: hnsw_mi355x_row_prefilter8_stats"); return -1; }
+    LOCK_INDEX(h);
+    static_cast<HnswIndex *>(h)->row_prefilter8_stats(out);
+    return 0;
+}
+API int hnsw_mi355x_row_prefilter8_peek(void *h, int first_id, int count, uint64_t out[4], uint8_t *codes)
+{
+    if (!h || !out || (count > 0 && !codes)) { set_error("System.ArgumentNullException: hnsw_mi355x_row_prefilter8_peek"); return -1; }
+    LOCK_INDEX(h);
+    std::string err;
+    if (!static_cast<HnswIndex *>(h)->row_prefilter8_peek(first_id, count, out, codes, err)) { set_error(err); return -1; }
+    return 0;
+}
 // HNSWIndex.GetInfo() / GetConnectedComponentCounts() (HNSWIndex.cs:192-205) from the graph mirror on the device:
 // top + 1, with min(cap, top + 1) entries written.  Exclusive: Add edits the mirror.
 API int hnsw_mi355x_get_info(void *h, hnsw_mi355x_layer_info *out, int cap)

@@ -2582,6 +2582,29 @@ bool HnswIndex::row_prefilter_peek(long long first_id, int count, uint64_t out[2
     return false;
 }
 
+void HnswIndex::row_prefilter8_stats(uint64_t out[6])
+{
+    std::fill_n(out, 6, (uint64_t)0);
+    if (dev_) dev_->row_prefilter8_stats(out);
+    for (auto &r : replicas_) {
+        uint64_t v[6];
+        r->row_prefilter8_stats(v);
+        for (int i = 0; i < 6; ++i) out[i] += v[i];
+    }
+}
+
+bool HnswIndex::row_prefilter8_peek(long long first_id, int count, uint64_t out[4], unsigned char *codes, std::string &err)
+{
+    out[0] = out[1] = out[2] = out[3] = 0;
+    if (!dev_) {
+        if (count > 0) err = "row_prefilter8_peek: the index has no 8-bit shadow rows";
+        return count <= 0;
+    }
+    if (dev_->row_prefilter8_peek(first_id, count, out, codes)) return true;
+    err = get_dev_error();
+    return false;
+}
+
 void HnswIndex::reset_all_stats()
 {
     if (dev_) dev_->reset_stats();

@@ -215,6 +215,8 @@ public:
     void row_prefilter_stats(uint64_t out[4]); // the primary context's (its views add to it) plus every replica's
     void row_prefilter_form_stats(uint64_t out[2]); // summed the same way
     bool row_prefilter_peek(long long first_id, int count, uint64_t out[2], float *rows, std::string &err); // the primary context's shadow, read only
+    void row_prefilter8_stats(uint64_t out[6]); // the 8-bit shadow's counters, summed the same way
+    bool row_prefilter8_peek(long long first_id, int count, uint64_t out[4], unsigned char *codes, std::string &err); // the primary context's 8-bit shadow, read only
     void set_profiling(bool on)
     {
         profiling_ = on;

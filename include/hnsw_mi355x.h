@@ -143,12 +143,14 @@ int hnsw_mi355x_index_insert_batch(void *handle);
  * out[1] insert searches run (>= items: the re-searched ones count again), out[2] items inserted alone (entry-point
  * moves, hand-backs), out[3] items linked through windows. */
 int hnsw_mi355x_exact_window_stats(void *handle, uint64_t out[4]);
-/* Counters of the half-precision row prefilter of KnnQuery (sq_euclid indices) since the index was created:
- * out[0] search launches that ran with it, out[1] rows measured on the half-precision shadow, out[2] rows measured again from
- * their f32 row (the others were turned away on the shadow value), out[3] shadow rows packed.  All zero where it does not run. */
+/* Counters of the row prefilter of KnnQuery (sq_euclid indices) since the index was created, totals over both
+ * shadow widths (half precision and 8-bit): out[0] search launches that ran with it, out[1] rows measured on a shadow, out[2] rows
+ * measured again from their f32 row (the others were turned away on the shadow value), out[3] shadow rows packed.  All zero where
+ * it does not run. */
 int hnsw_mi355x_row_prefilter_stats(void *handle, uint64_t out[4]);
 /* Which kernel form those launches took: out[0] launches in the form that reads the row length at run time, out[1] launches in the
- * form with the row length compiled in (dim 128; four waves per SIMD).  out[0] + out[1] is out[0] above. */
+ * form with the row length compiled in (dim 128; four waves per SIMD).  Both are half-precision forms: a launch on the
+ * 8-bit shadow is neither (hnsw_mi355x_row_prefilter8_stats). */
 int hnsw_mi355x_row_prefilter_form_stats(void *handle, uint64_t out[2]);
 /* Diagnostic, read only: the half-precision shadow of the row prefilter as it stands (it packs nothing and allocates nothing).
  * out[0] the packed watermark (shadow rows [0, out[0]) are current), out[1] the 32 bits of E, the index-wide bound on
@@ -156,6 +158,17 @@ int hnsw_mi355x_row_prefilter_form_stats(void *handle, uint64_t out[2]);
  * shadow rows [first_id, first_id + count) widened to f32.  An index without a shadow (no lean launch yet, another metric, diag
  * row_prefilter=0) has watermark 0.  -1 for a NULL handle or out, or a range that does not lie below the watermark. */
 int hnsw_mi355x_row_prefilter_peek(void *handle, int first_id, int count, uint64_t out[2], float *rows);
+/* The 8-bit shadow's own counters (dim 128; one 128-byte line per row): out[0] launches on it, out[1] rows packed into
+ * it, out[2] rows measured on it, out[3] rows measured again from f32, out[4] full packs (each derives a fresh grid), out[5] launches
+ * that re-read more than a quarter of their rows and switched the index to the half-precision prefilter.  -1 (with a message) for a
+ * NULL handle or out. */
+int hnsw_mi355x_row_prefilter8_stats(void *handle, uint64_t out[6]);
+/* Diagnostic, read only: the 8-bit shadow as it stands.  out[0] the packed watermark, out[1] the bits of lo, out[2] the bits of step
+ * (floats: the shadow value of code c is fmaf(step, (float)c, lo)), out[3] the bits of E8, the index-wide bound on ||x - h8(x)||_2.
+ * codes (may be NULL when count is 0): count x 128 code bytes, rows [first_id, first_id + count), element i at byte i.  An index
+ * without an 8-bit shadow has watermark 0.  -1 (with a message) for a NULL handle or out, a NULL codes with count > 0, or a range that
+ * does not lie below the watermark. */
+int hnsw_mi355x_row_prefilter8_peek(void *handle, int first_id, int count, uint64_t out[4], uint8_t *codes);
 /* Pending: hnsw_remove's schedule.  1 (default): the ids one after the other, exactly HNSWIndex.Remove(int) per id.
  * B > 1: the deterministic counterpart of Remove(List<int>) = Parallel.For under region locks (HNSWIndex.cs:95-101,
  * GraphLocker.cs:28-72): removals whose neighbourhoods (the node, its out- and in-neighbours on every layer) are
