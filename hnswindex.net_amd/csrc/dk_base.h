@@ -23,8 +23,14 @@
 #ifndef HNSW_PF_FIXED_WAVES // waves per SIMD of the fixed-length row-prefilter kernels (kFormLeanPFFixed): 124-128 VGPRs, nothing spilled
 #define HNSW_PF_FIXED_WAVES 4
 #endif
-#ifndef HNSW_PF8_WAVES // waves per SIMD of the 8-bit row-prefilter kernels (kFormLeanPF8Fixed): the shadow pass holds 16 VGPRs of loads where the f16 pass holds 32
-#define HNSW_PF8_WAVES 4
+#ifndef HNSW_PF8_WAVES // waves per SIMD of the 8-bit row-prefilter kernels (kFormLeanPF8Fixed): the shadow pass holds 16 VGPRs of loads where the f16 pass holds 32, and the f32 pass, which only re-reads the shadow pass's survivors, 32 where the lean form holds 64 (HNSW_PF8_PASS_ROWS): 91-96 VGPRs, nothing spilled
+#define HNSW_PF8_WAVES 5
+#endif
+#ifndef HNSW_PF8_PASS_ROWS // rows per f32 pass of every measure_all inside the 8-bit row-prefilter kernels: 8, 16, 24 or 32 (form_measure_cap below)
+#define HNSW_PF8_PASS_ROWS 16
+#endif
+#ifndef HNSW_PF_FIXED_PASS_ROWS // ... and inside the f16 fixed-length row-prefilter kernels (32: the lean form's passes, the bytes these kernels had before the cap existed)
+#define HNSW_PF_FIXED_PASS_ROWS 32
 #endif
 
 namespace hnsw {
@@ -75,6 +81,11 @@ constexpr __host__ __device__ bool form_is_pf8(int f) { return f == kFormLeanPF8
 constexpr __host__ __device__ bool form_is_pf_fixed(int f) { return f == kFormLeanPFFixed || f == kFormLeanPF8Fixed; }
 constexpr __host__ __device__ bool form_is_pf(int f) { return f == kFormLeanPF || form_is_pf_fixed(f); }
 constexpr __host__ __device__ bool form_is_lean(int f) { return f == kFormLean || form_is_pf(f); }
+// The most rows a lane group keeps in flight in one f32 pass (measure_all's NPCAP, 8 rows each) anywhere in a kernel of form f: the
+// survivor re-read, the descent and the exact traversal a tied job falls into alike -- one 32-row pass left in the kernel and its 64
+// VGPRs of loads set the kernel's register count.  In the 8-bit row-prefilter form the f32 pass re-reads 5.7 survivors per expansion
+// on average and more than 16 in one expansion of fourteen: 16 rows per pass, and the kernel fits five waves.
+constexpr __host__ __device__ int form_measure_cap(int f) { return f == kFormLeanPF8Fixed ? HNSW_PF8_PASS_ROWS / 8 : f == kFormLeanPFFixed ? HNSW_PF_FIXED_PASS_ROWS / 8 : 4; }
 
 // A kernel argument read again from the kernarg segment at the point of use (a scalar load that hits the constant cache) instead of
 // being carried in SGPRs from the kernel's first instruction to its last: the lean search kernel does this for the two dozen

@@ -400,7 +400,10 @@ __device__ __forceinline__ void measure_pass2_h(const float *__restrict__ rows, 
     if (h == 0 && c < m) dbuf[c] = res;
 }
 
-template <int METRIC, bool TWO = false>
+// NPCAP: the largest number of rows a lane group keeps in flight in one pass (8 * NPCAP rows per pass).  4 everywhere but in the
+// fixed-length row-prefilter kernels, whose f32 pass only re-reads the survivors of the shadow pass (dk_base.h, form_measure_cap):
+// a row's value is its own accumulator, summed in k order, whatever the pass it rides in -- the width changes no bit.
+template <int METRIC, bool TWO = false, int NPCAP = 4>
 __device__ __forceinline__ void measure_all(const float *rows, const double *row_sn, int dim, const float *qs, double sb,
                                             const int *nbuf, float *dbuf, int m, int lane)
 {
@@ -411,11 +414,11 @@ __device__ __forceinline__ void measure_all(const float *rows, const double *row
                 return;
             }
         }
-        for (int p0 = 0; p0 < m; p0 += 32) {
+        for (int p0 = 0; p0 < m; p0 += 8 * NPCAP) {
             const int left = m - p0;
-            if (left > 24) measure_pass_h<METRIC, 4>(rows, dim, qs, nbuf, dbuf, p0, m, lane);
-            else if (left > 16) measure_pass_h<METRIC, 3>(rows, dim, qs, nbuf, dbuf, p0, m, lane);
-            else if (left > 8) measure_pass_h<METRIC, 2>(rows, dim, qs, nbuf, dbuf, p0, m, lane);
+            if (NPCAP > 3 && left > 24) measure_pass_h<METRIC, 4>(rows, dim, qs, nbuf, dbuf, p0, m, lane);
+            else if (NPCAP > 2 && left > 16) measure_pass_h<METRIC, 3>(rows, dim, qs, nbuf, dbuf, p0, m, lane);
+            else if (NPCAP > 1 && left > 8) measure_pass_h<METRIC, 2>(rows, dim, qs, nbuf, dbuf, p0, m, lane);
             else measure_pass_h<METRIC, 1>(rows, dim, qs, nbuf, dbuf, p0, m, lane);
         }
         return;
@@ -427,19 +430,19 @@ __device__ __forceinline__ void measure_all(const float *rows, const double *row
         }
     }
     if constexpr (METRIC == M_I8) {
-        for (int p0 = 0; p0 < m; p0 += 32) {
+        for (int p0 = 0; p0 < m; p0 += 8 * NPCAP) {
             const int left = m - p0;
-            if (left > 24) measure_pass_i8_any<4>(rows, dim, qs, nbuf, dbuf, p0, m, lane);
-            else if (left > 16) measure_pass_i8_any<3>(rows, dim, qs, nbuf, dbuf, p0, m, lane);
-            else if (left > 8) measure_pass_i8_any<2>(rows, dim, qs, nbuf, dbuf, p0, m, lane);
+            if (NPCAP > 3 && left > 24) measure_pass_i8_any<4>(rows, dim, qs, nbuf, dbuf, p0, m, lane);
+            else if (NPCAP > 2 && left > 16) measure_pass_i8_any<3>(rows, dim, qs, nbuf, dbuf, p0, m, lane);
+            else if (NPCAP > 1 && left > 8) measure_pass_i8_any<2>(rows, dim, qs, nbuf, dbuf, p0, m, lane);
             else measure_pass_i8_any<1>(rows, dim, qs, nbuf, dbuf, p0, m, lane);
         }
     } else {
-    for (int p0 = 0; p0 < m; p0 += 32) {
+    for (int p0 = 0; p0 < m; p0 += 8 * NPCAP) {
         int left = m - p0;
-        if (left > 24) measure_pass<METRIC, 4>(rows, row_sn, dim, qs, sb, nbuf, dbuf, p0, m, lane);
-        else if (left > 16) measure_pass<METRIC, 3>(rows, row_sn, dim, qs, sb, nbuf, dbuf, p0, m, lane);
-        else if (left > 8) measure_pass<METRIC, 2>(rows, row_sn, dim, qs, sb, nbuf, dbuf, p0, m, lane);
+        if (NPCAP > 3 && left > 24) measure_pass<METRIC, 4>(rows, row_sn, dim, qs, sb, nbuf, dbuf, p0, m, lane);
+        else if (NPCAP > 2 && left > 16) measure_pass<METRIC, 3>(rows, row_sn, dim, qs, sb, nbuf, dbuf, p0, m, lane);
+        else if (NPCAP > 1 && left > 8) measure_pass<METRIC, 2>(rows, row_sn, dim, qs, sb, nbuf, dbuf, p0, m, lane);
         else measure_pass<METRIC, 1>(rows, row_sn, dim, qs, sb, nbuf, dbuf, p0, m, lane);
     }
     }

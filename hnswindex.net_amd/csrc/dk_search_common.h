@@ -244,7 +244,7 @@ __device__ __forceinline__ double stage_query(const float *queries, const double
 // FindEntryPoint / FindEntryAtLayer (GraphNavigator.cs:27-82): greedy descent from jb.entry at
 // jb.entry_layer down to (not including) jb.search_layer.  Leaves the entry of the search layer
 // in `best` and its distance in `cur` (both wave-uniform).
-template <int METRIC, bool TWO = false>
+template <int METRIC, bool TWO = false, int NPCAP = 4> // NPCAP: measure_all's rows per pass (form_measure_cap)
 __device__ __forceinline__ void descend(const float *__restrict__ rows, const double *__restrict__ row_sn, int dim, double sb,
                                         const GraphView &G, const SearchJob jb, const SearchLds &L, int lane, int &best, float &cur,
                                         unsigned long long &evals, ReadLog &RL)
@@ -256,7 +256,7 @@ __device__ __forceinline__ void descend(const float *__restrict__ rows, const do
     wave_sync();
     if (lane == 0) nbuf[0] = best;
     wave_sync();
-    measure_all<METRIC>(rows, row_sn, dim, qs, sb, nbuf, dbuf, 1, lane);
+    measure_all<METRIC, false, NPCAP>(rows, row_sn, dim, qs, sb, nbuf, dbuf, 1, lane);
     wave_sync();
     cur = dbuf[0]; // :57
     evals += 1;
@@ -271,7 +271,7 @@ __device__ __forceinline__ void descend(const float *__restrict__ rows, const do
             wave_sync();
             for (int i = lane; i < n; i += 64) nbuf[i] = l[1 + i]; // :65 span taken once per pass
             wave_sync();
-            if (n > 0) measure_all<METRIC, TWO>(rows, row_sn, dim, qs, sb, nbuf, dbuf, n, lane);
+            if (n > 0) measure_all<METRIC, TWO, NPCAP>(rows, row_sn, dim, qs, sb, nbuf, dbuf, n, lane);
             wave_sync();
             evals += (unsigned long long)n;
             for (int i = 0; i < n; ++i) { // :67-78

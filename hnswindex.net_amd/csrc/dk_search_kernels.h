@@ -147,7 +147,7 @@ __device__ __forceinline__ void search_job(const float *__restrict__ rows, const
             unsigned long long *const words = HNSW_KA(pf_words);
             RowPrefilterIo pf{nullptr, 0.0f, row_prefilter_c(dim), 0u, 0u, (unsigned)offsetof(SearchKernArgs, pf_rows), (unsigned)offsetof(SearchKernArgs, pf_words)};
             if constexpr (!form_is_pf8(FORM)) { pf.rows = HNSW_KA(pf_rows); pf.e = __uint_as_float(*reinterpret_cast<const unsigned *>(words)); }
-            ok1 = traverse_sorted<METRIC, NS, HASHED, true, true, form_is_pf8(FORM)>(rows, row_sn, dim, sb, G, jb, k, k_out + 1, V, L, lane, top_n, tie, evals, overlap, RL, nullptr, &window, &pf);
+            ok1 = traverse_sorted<METRIC, NS, HASHED, true, true, form_is_pf8(FORM), form_measure_cap(FORM)>(rows, row_sn, dim, sb, G, jb, k, k_out + 1, V, L, lane, top_n, tie, evals, overlap, RL, nullptr, &window, &pf);
             if (lane == 0) { atomicAdd(words + 1, (unsigned long long)pf.n_shadow); atomicAdd(words + 2, (unsigned long long)pf.n_reread); }
         }
         else ok1 = traverse_sorted<METRIC, NS, HASHED, LEAN>(rows, row_sn, dim, sb, G, jb, k, k_out + 1, V, L, lane, top_n, tie, evals, overlap, RL, nullptr, &window);
@@ -197,7 +197,7 @@ __device__ __forceinline__ void search_job(const float *__restrict__ rows, const
         const int vis_tab_cap = HNSW_KA(vis_tab_cap);
         VisitedSet<HASHED> VE{HNSW_KA(visited) + (size_t)blockIdx.x * (size_t)vis_words, vis_words,
                               vis_tab ? vis_tab + (size_t)blockIdx.x * (size_t)vis_tab_cap : nullptr, (unsigned)(vis_tab_cap - 1), 0, vis_tab_cap / 4 * 3};
-        ok = traverse<METRIC, HASHED>(rows, row_sn, dim, sb, G, jb, k, cand_cap, HNSW_KA(spill) + (size_t)blockIdx.x * spill_cap_, spill_cap_, VE, L, lane, top_n, evals, RL,
+        ok = traverse<METRIC, HASHED, false, AllowSet, form_measure_cap(FORM)>(rows, row_sn, dim, sb, G, jb, k, cand_cap, HNSW_KA(spill) + (size_t)blockIdx.x * spill_cap_, spill_cap_, VE, L, lane, top_n, evals, RL,
                                       shadow ? job_word : nullptr, &aborted, true);
         VE.clear(lane);
         if (v_untouched) *v_untouched = true;
@@ -238,7 +238,9 @@ __device__ __forceinline__ void search_job(const float *__restrict__ rows, const
 template <int METRIC, int NS, bool HASHED, int FORM = kFormPlain>
 // float rows: 168 VGPRs, three waves per SIMD; int8 records keep 16 registers of rows in flight, not 64: five waves.
 // The fixed-length row-prefilter form (kFormLeanPFFixed): 124-128 VGPRs, four waves.
-// Its 8-bit variant (kFormLeanPF8Fixed): four waves as well (profiles/pf8_kernel_resources.json).
+// Its 8-bit variant (kFormLeanPF8Fixed): every f32 pass of the kernel -- survivor re-read, descent, the exact traversal of a tied
+// job -- takes 16 rows, not 32 (form_measure_cap: 32 VGPRs of rows in flight, not 64): 91-96 VGPRs, nothing spilled, FIVE waves
+// (profiles/pf8_waves_kernel_resources.json).
 // LAT (launches that do not fill the chip): no occupancy to buy -- every spilled register is a memory round trip a lone wave
 // waits out in full -- so two waves per SIMD at most (256 VGPRs), one with eight register sets
 __global__ void __launch_bounds__(FORM == kFormLat ? 128 : 64) __attribute__((amdgpu_waves_per_eu(HNSW_WAVES(FORM == kFormLat ? (NS <= 4 ? 2 : 1) : FORM == kFormLeanPF ? HNSW_PF_WAVES : FORM == kFormLeanPFFixed ? HNSW_PF_FIXED_WAVES : FORM == kFormLeanPF8Fixed ? HNSW_PF8_WAVES : METRIC == M_I8 ? (NS <= 2 ? HNSW_I8_WAVES : 4) : (NS <= 4 ? 3 : 2)))))

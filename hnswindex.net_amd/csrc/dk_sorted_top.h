@@ -364,7 +364,8 @@ __device__ __forceinline__ void measure_shadow8(const unsigned char *codes, unsi
 
 // Returns false on a NaN / -0 distance (exact host re-run); `tie` asks for the exact two-heap
 // traversal.  Result: L.top[0..top_n) ascending by distance.  The query must be staged in L.qs.
-template <int METRIC, int NS, bool HASHED, bool LEAN = false, bool PF = false, bool PF8 = false>
+// NPCAP: measure_all's rows per pass (form_measure_cap), for the descent, the survivor re-read and every other f32 pass here.
+template <int METRIC, int NS, bool HASHED, bool LEAN = false, bool PF = false, bool PF8 = false, int NPCAP = 4>
 __device__ __forceinline__ bool traverse_sorted(const float *__restrict__ rows, const double *__restrict__ row_sn, int dim, double sb,
                                                 const GraphView &G, const SearchJob jb, int k, int ordered_prefix, VisitedSet<HASHED> &V,
                                                 const SearchLds &L, int lane, int &top_n_out, bool &tie_out, unsigned long long &evals,
@@ -377,7 +378,7 @@ __device__ __forceinline__ bool traverse_sorted(const float *__restrict__ rows, 
     PH_DECL();
     int best;
     float cur;
-    descend<METRIC>(rows, row_sn, dim, sb, G, jb, L, lane, best, cur, evals, RL);
+    descend<METRIC, false, NPCAP>(rows, row_sn, dim, sb, G, jb, L, lane, best, cur, evals, RL);
     // ---- SearchLayer (GraphNavigator.cs:123-189) ----
     const int layer = jb.search_layer;
     RL.layer(layer, lane);
@@ -499,12 +500,12 @@ __device__ __forceinline__ bool traverse_sorted(const float *__restrict__ rows, 
                     const int kn = (int)__popcll(km);
                     if (pf_keep) nbuf[pf_pos] = nb_a; // (every lane holds its id in nb_a: the compaction is in place)
                     wave_sync();
-                    if (kn > 0) measure_all<METRIC>(rows, row_sn, dim, qs, sb, nbuf, dbuf, kn, lane); // :163, the lean form's bits
+                    if (kn > 0) measure_all<METRIC, false, NPCAP>(rows, row_sn, dim, qs, sb, nbuf, dbuf, kn, lane); // :163, the lean form's bits
                     pf->n_shadow += (unsigned)n;
                     pf->n_reread += (unsigned)kn;
                 }
             } else
-            if (n > 0) measure_all<METRIC>(rows, row_sn, dim, qs, sb, nbuf, dbuf, n, lane); // :163 (and the visited ones)
+            if (n > 0) measure_all<METRIC, false, NPCAP>(rows, row_sn, dim, qs, sb, nbuf, dbuf, n, lane); // :163 (and the visited ones)
             wave_sync();
             PHX(1);
             if constexpr (PF) lane_d = pf_keep ? dbuf[pf_pos] : __uint_as_float(0x7f800000u); // turned away: a key above the farthest
@@ -583,7 +584,7 @@ __device__ __forceinline__ bool traverse_sorted(const float *__restrict__ rows, 
         if (m == 0) continue;
         V.seen += m;
         if (V.crowded()) { hash_full = true; break; } // the id table is filling up: host traversal
-        measure_all<METRIC>(rows, row_sn, dim, qs, sb, nbuf, dbuf, m, lane); // :163
+        measure_all<METRIC, false, NPCAP>(rows, row_sn, dim, qs, sb, nbuf, dbuf, m, lane); // :163
         wave_sync();
         PH(4);
         evals += (unsigned long long)m;

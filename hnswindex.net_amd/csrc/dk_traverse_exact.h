@@ -11,7 +11,8 @@ namespace hnsw {
 // the result heap.  FILTERED = false (every other caller) compiles to the unfiltered traversal: the allow arguments are unused.
 // FILTER: the predicate's type -- AllowSet, or GroupSet (graph_search_grouped_kernel: the id's group label equals the job's group);
 // either is asked for word(id), one 4-byte gather, where the traversal can overlap it, and for has(id) where it cannot.
-template <int METRIC, bool HASHED, bool FILTERED = false, class FILTER = AllowSet>
+// NPCAP: measure_all's rows per pass (form_measure_cap: the traversal compiled into a row-prefilter kernel keeps that kernel's cap).
+template <int METRIC, bool HASHED, bool FILTERED = false, class FILTER = AllowSet, int NPCAP = 4>
 __device__ __forceinline__ bool traverse(const float *__restrict__ rows, const double *__restrict__ row_sn, int dim, double sb,
                                          const GraphView &G, const SearchJob jb, int k, int cand_cap, ND *spill, int spill_cap,
                                          VisitedSet<HASHED> &V, const SearchLds &L, int lane, int &top_n_out, unsigned long long &evals,
@@ -29,7 +30,7 @@ __device__ __forceinline__ bool traverse(const float *__restrict__ rows, const d
     wave_sync();
     if (lane == 0) nbuf[0] = best;
     wave_sync();
-    measure_all<METRIC>(rows, row_sn, dim, qs, sb, nbuf, dbuf, 1, lane);
+    measure_all<METRIC, false, NPCAP>(rows, row_sn, dim, qs, sb, nbuf, dbuf, 1, lane);
     wave_sync();
     float cur = dbuf[0]; // :57
     evals += 1;
@@ -44,7 +45,7 @@ __device__ __forceinline__ bool traverse(const float *__restrict__ rows, const d
             wave_sync();
             for (int i = lane; i < n; i += 64) nbuf[i] = l[1 + i]; // :65 span taken once per pass
             wave_sync();
-            if (n > 0) measure_all<METRIC>(rows, row_sn, dim, qs, sb, nbuf, dbuf, n, lane);
+            if (n > 0) measure_all<METRIC, false, NPCAP>(rows, row_sn, dim, qs, sb, nbuf, dbuf, n, lane);
             wave_sync();
             evals += (unsigned long long)n;
             for (int i = 0; i < n; ++i) { // :67-78
@@ -134,7 +135,7 @@ __device__ __forceinline__ bool traverse(const float *__restrict__ rows, const d
                 pre_a = lane < lstride ? pl[lane] : 0;
                 pre_b = lane + 64 < lstride ? pl[lane + 64] : 0;
             }
-            if (n > 0) measure_all<METRIC>(rows, row_sn, dim, qs, sb, nbuf, dbuf, n, lane); // :163 (and the visited ones)
+            if (n > 0) measure_all<METRIC, false, NPCAP>(rows, row_sn, dim, qs, sb, nbuf, dbuf, n, lane); // :163 (and the visited ones)
             wave_sync();
             if constexpr (HASHED) {
                 have = in && (int)old == -1;
@@ -181,7 +182,7 @@ __device__ __forceinline__ bool traverse(const float *__restrict__ rows, const d
         if (m == 0) continue;
         V.seen += m;
         if (V.crowded()) { hash_full = true; break; } // the id table is filling up: host traversal
-        measure_all<METRIC>(rows, row_sn, dim, qs, sb, nbuf, dbuf, m, lane); // :163
+        measure_all<METRIC, false, NPCAP>(rows, row_sn, dim, qs, sb, nbuf, dbuf, m, lane); // :163
         wave_sync();
         evals += (unsigned long long)m;
         }
