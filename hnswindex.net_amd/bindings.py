@@ -151,6 +151,13 @@ lib.hnsw_mi355x_exact_range_query_by_id.argtypes = [ct.c_void_p, _I, ct.c_int, c
 lib.hnsw_mi355x_duplicate_groups.restype = ct.c_int
 lib.hnsw_mi355x_duplicate_groups.argtypes = [ct.c_void_p, ct.c_float, _U32, ct.c_longlong, _I, ct.c_longlong, ct.POINTER(ct.c_uint64)]
 _GROUPS_INFO = ("members", "groups", "pairs_within", "pairs_measured")   # out_info[0 .. 3] of hnsw_mi355x_duplicate_groups
+lib.hnsw_mi355x_graph_duplicate_groups.restype = ct.c_int
+lib.hnsw_mi355x_graph_duplicate_groups.argtypes = [ct.c_void_p, ct.c_float, _U32, ct.c_longlong, _I, ct.c_longlong, ct.POINTER(ct.c_uint64)]
+lib.hnsw_mi355x_near_edges.restype = ct.c_int
+lib.hnsw_mi355x_near_edges.argtypes = [ct.c_void_p, ct.c_float, _U32, ct.c_longlong, ct.POINTER(ct.c_longlong)]
+lib.hnsw_mi355x_near_edges_results.restype = ct.c_int
+lib.hnsw_mi355x_near_edges_results.argtypes = [ct.c_void_p, _I, _I, _F, ct.c_longlong]
+_EDGE_GROUPS_INFO = ("members", "groups", "edges_within", "edges_measured", "launches")   # out_info[0 .. 4] of hnsw_mi355x_graph_duplicate_groups
 lib.hnsw_mi355x_knn_query_grouped.restype = ct.c_int
 lib.hnsw_mi355x_knn_query_grouped.argtypes = [ct.c_void_p, _F, ct.c_int, ct.c_int, ct.c_int, ct.c_int, _I, ct.c_longlong, _I, ct.c_int, _I, _F]
 lib.hnsw_mi355x_range_query_grouped.restype = ct.c_int
@@ -323,6 +330,12 @@ lib.hnswdev_exact_range_by_id.restype = ct.c_int
 lib.hnswdev_exact_range_by_id.argtypes = [ct.c_void_p, _I, ct.c_int, ct.c_longlong, ct.c_float, _U32, ct.c_longlong, _I]
 lib.hnswdev_exact_range_groups.restype = ct.c_int
 lib.hnswdev_exact_range_groups.argtypes = [ct.c_void_p, ct.c_longlong, ct.c_float, _U32, ct.c_longlong, _I, ct.POINTER(ct.c_uint64)]
+lib.hnswdev_graph_edge_groups.restype = ct.c_int
+lib.hnswdev_graph_edge_groups.argtypes = [ct.c_void_p, ct.c_longlong, ct.c_float, _U32, ct.c_longlong, _I, ct.POINTER(ct.c_uint64)]
+lib.hnswdev_graph_near_edges.restype = ct.c_int
+lib.hnswdev_graph_near_edges.argtypes = [ct.c_void_p, ct.c_longlong, ct.c_float, _U32, ct.c_longlong, ct.POINTER(ct.c_longlong)]
+lib.hnswdev_graph_near_edges_results.restype = ct.c_int
+lib.hnswdev_graph_near_edges_results.argtypes = [ct.c_void_p, _I, _I, _F, ct.c_longlong]
 lib.hnswdev_tag_list_ms.restype = ct.c_int
 lib.hnswdev_tag_list_ms.argtypes = [ct.c_void_p, ct.POINTER(ct.c_double)]
 lib.hnswdev_knn_search_grouped.restype = ct.c_int
@@ -1041,6 +1054,38 @@ class Index:
             raise RuntimeError(last_error())
         return labels, {name: int(info[i]) for i, name in enumerate(_GROUPS_INFO)}
 
+    # ---- near-duplicates over the graph's edges ----
+    def graph_duplicate_groups(self, radius: float, allowed=None) -> Tuple[npt.NDArray[np.int32], dict]:
+        """duplicate_groups asked of the graph (hnsw_mi355x_graph_duplicate_groups): (int32[length], info).  The members are
+        duplicate_groups'; what joins two of them is a layer-0 edge (i, j) -- j in i's list -- whose distance, the stored row of i
+        taken as the query, is <= radius; the groups are the connected components, labelled with their smallest member id, -1
+        where v is no member.  n x (at most 2 MaxEdges) distances instead of m (m - 1) / 2: duplicate_groups' grouping or a
+        refinement of it -- near-duplicates that no path of such edges connects stay apart.  info: members, groups, edges_within and
+        edges_measured (directed), launches (of the edge kernel)."""
+        n = int(self.length)
+        labels = np.full(n, -1, dtype=np.int32)
+        info = (ct.c_uint64 * 5)()
+        words, nbits = allow_bits(allowed) if allowed is not None else (None, 0)
+        words, wp = _words_arg(words) if allowed is not None else (None, None)
+        if self._h and lib.hnsw_mi355x_graph_duplicate_groups(self._h, radius, wp, nbits, labels.ctypes.data_as(_I), n, info) < 0:
+            raise RuntimeError(last_error())
+        return labels, {name: int(info[i]) for i, name in enumerate(_EDGE_GROUPS_INFO)}
+
+    def near_edges(self, radius: float, allowed=None) -> Tuple[npt.NDArray[np.int32], npt.NDArray[np.int32], npt.NDArray[np.float32]]:
+        """The layer-0 edges between members that lie within `radius` (hnsw_mi355x_near_edges + _results): (src, dst, dist), ascending
+        by src and, inside one src, by (distance, dst) -- that item's exact_range_query_by_id list restricted to its adjacency list,
+        with that list's distance bits.  Directed: two items that list each other appear twice."""
+        count = ct.c_longlong(0)
+        words, nbits = allow_bits(allowed) if allowed is not None else (None, 0)
+        words, wp = _words_arg(words) if allowed is not None else (None, None)
+        if self._h and lib.hnsw_mi355x_near_edges(self._h, radius, wp, nbits, ct.byref(count)) < 0:
+            raise RuntimeError(last_error())
+        n = int(count.value)
+        src, dst, d = np.empty(n, dtype=np.int32), np.empty(n, dtype=np.int32), np.empty(n, dtype=np.float32)
+        if n and lib.hnsw_mi355x_near_edges_results(self._h, src.ctypes.data_as(_I), dst.ctypes.data_as(_I), d.ctypes.data_as(_F), n) < 0:
+            raise RuntimeError(last_error())
+        return src, dst, d
+
     def exact_range_query(self, queries: npt.ArrayLike, radius: float,
                           allowed=None) -> Tuple[List[npt.NDArray[np.int32]], List[npt.NDArray[np.float32]]]:
         """Per query every live (and, with `allowed`, allowed) id whose distance is <= radius, ascending by (distance, id), from
@@ -1518,6 +1563,28 @@ class DeviceBackend:
         words, wp = _words_arg(words) if allowed is not None else (None, None)
         self._check(lib.hnswdev_exact_range_groups(self._ctx, int(n_rows), float(radius), wp, nbits, labels.ctypes.data_as(_I), info))
         return labels, {name: int(info[i]) for i, name in enumerate(_GROUPS_INFO)}
+
+    def graph_edge_groups(self, radius: float, n_rows: int, allowed=None):
+        """hnswdev_graph_edge_groups: (int32[n_rows] labels, info dict) -- Index.graph_duplicate_groups on the uploaded rows of
+        [0, n_rows) that `allowed` allows and the graph set_graph committed."""
+        labels = np.full(int(n_rows), -1, dtype=np.int32)
+        info = (ct.c_uint64 * 5)()
+        words, nbits = allow_bits(allowed) if allowed is not None else (None, 0)
+        words, wp = _words_arg(words) if allowed is not None else (None, None)
+        self._check(lib.hnswdev_graph_edge_groups(self._ctx, int(n_rows), float(radius), wp, nbits, labels.ctypes.data_as(_I), info))
+        return labels, {name: int(info[i]) for i, name in enumerate(_EDGE_GROUPS_INFO)}
+
+    def graph_near_edges(self, radius: float, n_rows: int, allowed=None):
+        """hnswdev_graph_near_edges + _results: (src, dst, dist) as Index.near_edges returns them, on the uploaded rows of [0, n_rows)."""
+        count = ct.c_longlong(0)
+        words, nbits = allow_bits(allowed) if allowed is not None else (None, 0)
+        words, wp = _words_arg(words) if allowed is not None else (None, None)
+        self._check(lib.hnswdev_graph_near_edges(self._ctx, int(n_rows), float(radius), wp, nbits, ct.byref(count)))
+        n = int(count.value)
+        src, dst, d = np.empty(n, dtype=np.int32), np.empty(n, dtype=np.int32), np.empty(n, dtype=np.float32)
+        if n:
+            self._check(lib.hnswdev_graph_near_edges_results(self._ctx, src.ctypes.data_as(_I), dst.ctypes.data_as(_I), d.ctypes.data_as(_F), n))
+        return src, dst, d
 
     def set_queries(self, queries):
         """Uploads the query set of a batch of searches once; records name queries by row index."""

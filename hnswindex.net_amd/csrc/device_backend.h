@@ -490,6 +490,20 @@ public:
     // union-find as its sink (exact_scan_kernel<M, ExactRangeUnion>): no list is kept or copied.  Fewer than two members: no launch.
     // Neither the resident set nor exact_range's pending results are touched.
     bool exact_range_groups(long long n_rows, float range, const uint32_t *allow_bits, long long nbits, int *out_labels, uint64_t *out_info);
+    // hnswdev_graph_edge_groups / hnswdev_graph_near_edges: near-duplicates over the EDGES of layer 0 of the
+    // committed graph.  The MEMBERS are exact_range_groups' -- the uploaded rows of [0, n_rows) that allow_bits allows -- that are
+    // nodes of the graph.  An edge (i, j): i a member, j in i's layer-0 list, j a member (directed); it is within the range when the
+    // distance with the stored row of i as the query (gathered as the by-id calls gather it) and row j as the candidate is
+    // <= range.  graph_edge_kernel<M, Sink> measures every edge once, in rounds of at most 65 536 owners (`edge_round`).
+    // graph_edge_groups (sink EdgeUnion): out_labels[v], v in [0, min(n_rows, uploaded)), the smallest member of v's component under
+    // the within-edges read both ways, -1 where v is no member; out_info: [members, groups, edges within, edges measured, launches
+    // of the edge kernel].  graph_near_edges (sink EdgeList): keeps the within-edges, ascending by owner and inside one owner by
+    // (distance, id), for graph_near_edges_results; *out_count is their number.  Fewer than two members: no launch.  No graph
+    // committed (and n_rows > 0): an error.  Neither the resident set nor exact_range's pending results are touched.
+    bool graph_edge_groups(long long n_rows, float range, const uint32_t *allow_bits, long long nbits, int *out_labels, uint64_t *out_info);
+    bool graph_near_edges(long long n_rows, float range, const uint32_t *allow_bits, long long nbits, long long *out_count);
+    bool graph_near_edges_results(int *out_src, int *out_dst, float *out_d);
+    size_t graph_near_edges_total() const { return ge_src_.size(); }
     // hnswdev_exact_knn_grouped: exact_knn with a candidate set per query.  Query i's candidates are the uploaded
     // ids j < min(n_rows, uploaded, n_row_group) with row_group[j] == query_group[i]; a row_group value outside [0, n_groups) puts
     // the id in no group, a query_group value outside it is an error (nothing is written).  The groups' id lists are built on the
@@ -727,6 +741,15 @@ private:
     bool exact_id_list(const uint32_t *allow_bits, long long n_allow, long long *m);
     bool exact_knn_rounds(const float *d_q, const double *d_qsn, int nq, const int *d_idlist, long long m, int k, int *out_ids, float *out_d, int *d_keep_ids,
                           const int *d_self = nullptr, const ExactCollapseArgs *collapse = nullptr);
+    // the two calls over the graph's edges: out_labels / out_info, or -- keep_list -- the edges into ge_*
+    bool graph_edges_run(const char *who, long long n_rows, float range, const uint32_t *allow_bits, long long nbits, int *out_labels, uint64_t *out_info,
+                         bool keep_list);
+    DevBuf<unsigned> e_bits_;             // graph_edges_run: the members as a bitset
+    DevBuf<unsigned long long> e_ctr_;    // ... [next job (an int) | edges within | edges measured]
+    DevBuf<int> e_cnt_;                   // ... EdgeList: within-edges per owner of a round
+    DevBuf<unsigned long long> e_keys_;   // ... EdgeList: a round's segments of stride0 - 1 keys
+    std::vector<int> ge_src_, ge_dst_;    // graph_near_edges' result, until the next graph_near_edges
+    std::vector<float> ge_d_;
     DevBuf<int> x_clabels_;               // exact_knn_collapsed: row_group as uploaded
     DevBuf<unsigned long long> x_cinfo_;  // ... [keys dropped by the cap | entries evicted], counted on the device
     // search_collapsed: while set, run_resident and search_batch_impl collapse a launch's rows on the device (width -> k columns)

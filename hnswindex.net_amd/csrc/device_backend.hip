@@ -53,6 +53,7 @@
 #include "dk_graph_info.h"
 #include "dk_graph_reach.h"
 #include "dk_graph_repair.h"
+#include "dk_edge_groups.h"
 #include "dk_tag_lists.h"
 #include "range_replay.h"
 
@@ -5013,6 +5014,154 @@ bool Device::exact_range_groups(long long n_rows, float range, const uint32_t *a
     return true;
 }
 
+// ---- near-duplicates over the graph's edges -------------------------------------------------------------------------
+// exact_range_groups' host loop around graph_edge_kernel: the members are listed on the host, go up once as ids (the union-find's
+// roots) and once as a bitset (the kernel's member test), and a round of `edge_round` (65 536) of them at a time are the OWNERS --
+// their rows gathered into the exact family's query buffer as the by-id calls gather theirs, their ids left in x_self_.  One launch
+// per round.  The union sink ends as exact_range_groups does; the list sink copies a round's counts and segments back and
+// appends the edges, which the kernel left in their final order, to ge_*.
+bool Device::graph_edges_run(const char *who, long long n_rows, float range, const uint32_t *allow_bits, long long nbits, int *out_labels, uint64_t *out_info,
+                             bool keep_list)
+{
+    if (n_rows < 0 || (allow_bits && nbits < 0)) { set_dev_error(std::string(who) + ": bad argument"); return false; }
+    if (!allow_bits) nbits = 0;
+    const long long n = std::min(n_rows, n_rows_hw_), n_allow = allow_bits ? std::min(nbits, n) : n;
+    if (n > 0 && !keep_list && !out_labels) { set_dev_error(std::string(who) + ": bad argument"); return false; }
+    if (n > 0 && (g_n_ <= 0 || !g_adj0_)) { set_dev_error(std::string(who) + ": no graph committed"); return false; }
+    const long long n_mem = std::min<long long>(n_allow, g_n_); // a member is a row, allowed, and a node of the graph
+    std::vector<int> members;
+    std::vector<unsigned> bits((size_t)((std::max<long long>(n_mem, 0) + 31) / 32), 0u);
+    for (long long id = 0; id < n_mem; ++id)
+        if (!allow_bits || ((allow_bits[id >> 5] >> (id & 31)) & 1u)) {
+            members.push_back((int)id);
+            bits[(size_t)(id >> 5)] |= 1u << (id & 31);
+        }
+    const long long m = (long long)members.size();
+    if (!keep_list) {
+        for (long long v = 0; v < n; ++v) out_labels[v] = -1;
+        for (const int v : members) out_labels[v] = v; // (what fewer than two members leave; the device's labels replace it otherwise)
+        out_info[0] = (unsigned long long)m;
+        out_info[1] = (unsigned long long)m;
+    }
+    if (m < 2) return true; // no edge between two members: no launch
+    if (!bind()) return false;
+    hipStream_t st = S(stream_);
+    const int seg = std::max(g_stride0_ - 1, 1);  // the longest layer-0 list
+    const int nbc = std::max((seg + 7) & ~7, 8);
+    const size_t lds = search_lds_bytes(0, 0, pitch_, false, nbc);
+    if (lds > 64 * 1024) { set_dev_error(std::string(who) + ": dimension exceeds the LDS budget"); return false; }
+    const int forced_round = diag("edge_round", 0);
+    const long long round = std::min<long long>(m, forced_round > 0 ? forced_round : 65536);
+    const size_t cap = (size_t)std::max<long long>(round, 1024);
+    if (!x_queries_.grow((size_t)round * pitch_, cap * pitch_) || (metric_ == M_COS && !x_q_sn_.grow((size_t)round, cap))) return false;
+    if (!e_bits_.grow(bits.size()) || !e_ctr_.grow(3)) return false;
+    if (keep_list ? !e_cnt_.grow((size_t)round) || !e_keys_.grow((size_t)round * (size_t)seg) : !x_uparent_.grow(2 * (size_t)n)) return false;
+    HIP_OK(hipMemcpyAsync(e_bits_, bits.data(), 4 * bits.size(), hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemsetAsync(e_ctr_, 0, 3 * sizeof(unsigned long long), st));
+    if (!keep_list) {
+        if (!upload_ids(members.data(), (int)m, x_ids_)) return false;
+        HIP_OK(exact_union_init_launch(x_ids_, m, x_uparent_, n, st));
+    }
+    HIP_OK(hipStreamSynchronize(st)); // (a pageable source; the pinned stage is used again by the rounds)
+    const AllowSet member_set{e_bits_, n_mem};
+    const double *d_qsn = metric_ == M_COS ? x_q_sn_.get() : nullptr;
+    int *job_counter = reinterpret_cast<int *>(e_ctr_.get());
+    unsigned long long launches = 0;
+    std::vector<int> h_cnt;
+    std::vector<unsigned long long> h_keys;
+    for (long long off = 0; off < m; off += round) {
+        const int nr = (int)std::min<long long>(round, m - off);
+        if (!gather_queries(members.data() + off, nr, x_self_, x_queries_, x_q_sn_)) return false;
+        HIP_OK(hipMemsetAsync(job_counter, 0, sizeof(int), st));
+        const auto launch = [&](auto kernel, const auto &sink) -> bool {
+            const int slots = std::min(max_slots(), resident_blocks(kernel, lds, num_cu_));
+            if (slots < 1) { set_dev_error(std::string(who) + ": the edge kernel does not fit a compute unit"); return false; }
+            hipLaunchKernelGGL(kernel, dim3(std::min(nr, slots)), dim3(64), lds, st, d_rows_, d_row_sn_, x_queries_.get(), d_qsn, pitch_, g_adj0_, g_stride0_,
+                               x_self_.get(), member_set, range, sink, nbc, nr, job_counter);
+            HIP_OK(hipGetLastError());
+            return true;
+        };
+        bool ok = false;
+        if (keep_list) {
+            const EdgeList sink{e_keys_, e_cnt_, seg};
+            with_metric(metric_, [&](auto mt) { ok = launch(&graph_edge_kernel<mt, EdgeList>, sink); });
+        } else {
+            const EdgeUnion sink{x_uparent_, e_ctr_.get() + 1};
+            with_metric(metric_, [&](auto mt) { ok = launch(&graph_edge_kernel<mt, EdgeUnion>, sink); });
+        }
+        if (!ok) return false;
+        launches += 1;
+        if (!keep_list) continue;
+        h_cnt.resize((size_t)nr);
+        h_keys.resize((size_t)nr * (size_t)seg);
+        if (!exact_copy_out(h_cnt.data(), e_cnt_, 4 * (size_t)nr) || !exact_copy_out(h_keys.data(), e_keys_, 8 * (size_t)nr * (size_t)seg)) return false;
+        for (int j = 0; j < nr; ++j) {
+            const int c = std::min(std::max(h_cnt[(size_t)j], 0), seg);
+            for (int e = 0; e < c; ++e) {
+                const unsigned long long key = h_keys[(size_t)j * (size_t)seg + (size_t)e];
+                const uint32_t db = (uint32_t)(key >> 32);
+                float d;
+                memcpy(&d, &db, 4);
+                ge_src_.push_back(members[(size_t)(off + j)]);
+                ge_dst_.push_back((int)(uint32_t)key);
+                ge_d_.push_back(d);
+            }
+        }
+    }
+    if (keep_list) {
+        HIP_OK(hipStreamSynchronize(st));
+        return true;
+    }
+    int *d_labels = x_uparent_.get() + n;
+    HIP_OK(exact_union_labels_launch(x_uparent_, n, d_labels, st));
+    if (!exact_copy_out(out_labels, d_labels, 4 * (size_t)n)) return false;
+    unsigned long long *h = static_cast<unsigned long long *>(pinned_stage(16));
+    if (!h) return false;
+    HIP_OK(hipMemcpyAsync(h, e_ctr_.get() + 1, 16, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    unsigned long long groups = 0;
+    for (const int v : members) groups += (unsigned long long)(out_labels[v] == v);
+    out_info[1] = groups;
+    out_info[2] = h[0];
+    out_info[3] = h[1];
+    out_info[4] = launches;
+    return true;
+}
+
+bool Device::graph_edge_groups(long long n_rows, float range, const uint32_t *allow_bits, long long nbits, int *out_labels, uint64_t *out_info)
+{
+    if (!out_info) { set_dev_error("graph_edge_groups: bad argument"); return false; }
+    for (int i = 0; i < 5; ++i) out_info[i] = 0;
+    return graph_edges_run("graph_edge_groups", n_rows, range, allow_bits, nbits, out_labels, out_info, false);
+}
+
+bool Device::graph_near_edges(long long n_rows, float range, const uint32_t *allow_bits, long long nbits, long long *out_count)
+{
+    ge_src_.clear();
+    ge_dst_.clear();
+    ge_d_.clear();
+    if (out_count) *out_count = 0;
+    if (!out_count) { set_dev_error("graph_near_edges: bad argument"); return false; }
+    if (!graph_edges_run("graph_near_edges", n_rows, range, allow_bits, nbits, nullptr, nullptr, true)) {
+        ge_src_.clear();
+        ge_dst_.clear();
+        ge_d_.clear();
+        return false;
+    }
+    *out_count = (long long)ge_src_.size();
+    return true;
+}
+
+bool Device::graph_near_edges_results(int *out_src, int *out_dst, float *out_d)
+{
+    if (ge_src_.empty()) return true;
+    if (!out_src || !out_dst || !out_d) { set_dev_error("graph_near_edges_results: null argument"); return false; }
+    memcpy(out_src, ge_src_.data(), 4 * ge_src_.size());
+    memcpy(out_dst, ge_dst_.data(), 4 * ge_dst_.size());
+    memcpy(out_d, ge_d_.data(), 4 * ge_d_.size());
+    return true;
+}
+
 // ---- synchronous conveniences behind the C ABI ---------------------------------------
 // Distance(int, TVector) for nq (query, candidate list) pairs.  Runs on the context's two step-
 // buffer sets, ping-pong: while the GPU measures one set the host packs the next and unpacks the
@@ -5305,6 +5454,26 @@ DEV_API int hnswdev_exact_range_groups(void *ctx, long long n_rows, float range,
 {
     CTX_OR_FAIL();
     return d->exact_range_groups(n_rows, range, allow_bits, nbits, out_labels, out_info) ? 0 : -1;
+}
+DEV_API int hnswdev_graph_edge_groups(void *ctx, long long n_rows, float range, const uint32_t *allow_bits, long long nbits, int *out_labels,
+                                      uint64_t *out_info)
+{
+    CTX_OR_FAIL();
+    return d->graph_edge_groups(n_rows, range, allow_bits, nbits, out_labels, out_info) ? 0 : -1;
+}
+DEV_API int hnswdev_graph_near_edges(void *ctx, long long n_rows, float range, const uint32_t *allow_bits, long long nbits, long long *out_count)
+{
+    CTX_OR_FAIL();
+    return d->graph_near_edges(n_rows, range, allow_bits, nbits, out_count) ? 0 : -1;
+}
+DEV_API int hnswdev_graph_near_edges_results(void *ctx, int *out_src, int *out_dst, float *out_dists, long long cap)
+{
+    CTX_OR_FAIL();
+    if (cap < (long long)d->graph_near_edges_total()) {
+        hnsw::set_dev_error("graph_near_edges_results: cap = " + std::to_string(cap) + " is below the " + std::to_string(d->graph_near_edges_total()) + " edges kept");
+        return -1;
+    }
+    return d->graph_near_edges_results(out_src, out_dst, out_dists) ? 0 : -1;
 }
 DEV_API int hnswdev_exact_knn_grouped(void *ctx, const float *queries, int nq, long long n_rows, int k, const int *row_group, long long n_row_group,
                                       const int *query_group, int n_groups, int *out_ids, float *out_dists)

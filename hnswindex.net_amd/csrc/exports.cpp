@@ -522,6 +522,43 @@ API int hnsw_mi355x_duplicate_groups(void *handle, float range, const uint32_t *
     return 0;
 }
 
+// Near-duplicates over the graph's edges: hnsw_mi355x_duplicate_groups' members and label convention, joined along
+// the layer-0 edges within `range`; and those edges themselves, counted and kept by the first call and fetched by the second, as
+// hnswdev_exact_range / hnswdev_exact_range_results do it.  Exclusive: they use the scan's query buffer and bring the mirror up to date.
+API int hnsw_mi355x_graph_duplicate_groups(void *handle, float range, const uint32_t *allow_bits, long long nbits, int *out_labels, long long cap,
+                                           uint64_t *out_info)
+{
+    if (out_info) for (int i = 0; i < 5; ++i) out_info[i] = 0;
+    if (!handle) return 0;
+    if (!out_info) { set_error("System.ArgumentNullException: hnsw_mi355x_graph_duplicate_groups: out_info"); return -1; }
+    if (allow_bits && nbits < 0) { set_error("System.ArgumentException: hnsw_mi355x_graph_duplicate_groups: nbits must be >= 0"); return -1; }
+    LOCK_INDEX(handle);
+    std::string err;
+    if (static_cast<HnswIndex *>(handle)->graph_duplicate_groups(range, allow_bits, nbits, out_labels, cap, out_info, err) < 0) { set_error(err); return -1; }
+    return 0;
+}
+
+API int hnsw_mi355x_near_edges(void *handle, float range, const uint32_t *allow_bits, long long nbits, long long *out_count)
+{
+    if (out_count) *out_count = 0;
+    if (!handle) return 0;
+    if (!out_count) { set_error("System.ArgumentNullException: hnsw_mi355x_near_edges: out_count"); return -1; }
+    if (allow_bits && nbits < 0) { set_error("System.ArgumentException: hnsw_mi355x_near_edges: nbits must be >= 0"); return -1; }
+    LOCK_INDEX(handle);
+    std::string err;
+    if (static_cast<HnswIndex *>(handle)->near_edges(range, allow_bits, nbits, out_count, err) < 0) { set_error(err); return -1; }
+    return 0;
+}
+
+API int hnsw_mi355x_near_edges_results(void *handle, int *out_src, int *out_dst, float *out_dists, long long cap)
+{
+    if (!handle) return 0;
+    LOCK_INDEX(handle);
+    std::string err;
+    if (static_cast<HnswIndex *>(handle)->near_edges_results(out_src, out_dst, out_dists, cap, err) < 0) { set_error(err); return -1; }
+    return 0;
+}
+
 // hnsw_mi355x_exact_range_query with a candidate group per query: that call's lists and allocation contract,
 // hnsw_mi355x_exact_knn_query_grouped's group arguments.
 API int hnsw_mi355x_exact_range_query_grouped(void *handle, const float *vectors, int count, int dim, float range, const int *row_group, long long n_row_group,

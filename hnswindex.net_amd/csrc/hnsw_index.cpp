@@ -2162,6 +2162,58 @@ int HnswIndex::duplicate_groups(float range, const uint32_t *allow_bits, long lo
     return 0;
 }
 
+// The duplicate groups over the graph's edges: duplicate_groups' members and labels; what joins two members is a
+// layer-0 edge of the mirror within the range.
+int HnswIndex::graph_duplicate_groups(float range, const uint32_t *allow_bits, long long nbits, int *out_labels, long long cap, uint64_t *out_info, std::string &err)
+{
+    for (int i = 0; i < 5; ++i) out_info[i] = 0;
+    if (failed(err)) return -1;
+    const long long length_now = graph_.length;
+    if (cap < length_now) {
+        err = "System.ArgumentException: hnsw_mi355x_graph_duplicate_groups: cap = " + std::to_string(cap) + " is below the index's length of " + std::to_string(length_now);
+        return -1;
+    }
+    if (length_now > 0 && !out_labels) { err = "System.ArgumentNullException: hnsw_mi355x_graph_duplicate_groups: out_labels"; return -1; }
+    if (length_now <= 0) return 0;
+    for (long long v = 0; v < length_now; ++v) out_labels[v] = -1;
+    if (graph_.count <= 0) return 0; // every slot is vacant: no member, and nothing needs the device
+    if (!sync_graph(err)) return -1;
+    std::vector<uint32_t> live;
+    const long long length = exact_candidates(allow_bits, nbits, live);
+    if (!dev_->graph_edge_groups(length, range, allow_bits, nbits, out_labels, out_info)) { err = get_dev_error(); return -1; }
+    return 0;
+}
+
+// The within-edges themselves: kept in the primary context until near_edges_results fetches them.
+int HnswIndex::near_edges(float range, const uint32_t *allow_bits, long long nbits, long long *out_count, std::string &err)
+{
+    *out_count = 0;
+    if (failed(err)) return -1;
+    if (graph_.length <= 0 || graph_.count <= 0) { // no member: the empty result, and a later near_edges_results finds nothing pending
+        long long none = 0;
+        if (dev_ && !dev_->graph_near_edges(0, range, nullptr, 0, &none)) { err = get_dev_error(); return -1; } // (no context yet: nothing was ever kept)
+        return 0;
+    }
+    if (!sync_graph(err)) return -1;
+    std::vector<uint32_t> live;
+    const long long length = exact_candidates(allow_bits, nbits, live);
+    if (!dev_->graph_near_edges(length, range, allow_bits, nbits, out_count)) { err = get_dev_error(); return -1; }
+    return 0;
+}
+
+int HnswIndex::near_edges_results(int *out_src, int *out_dst, float *out_dists, long long cap, std::string &err)
+{
+    if (failed(err)) return -1;
+    const long long total = dev_ ? (long long)dev_->graph_near_edges_total() : 0;
+    if (total == 0) return 0;
+    if (cap < total) {
+        err = "System.ArgumentException: hnsw_mi355x_near_edges_results: cap = " + std::to_string(cap) + " is below the " + std::to_string(total) + " edges kept";
+        return -1;
+    }
+    if (!dev_->graph_near_edges_results(out_src, out_dst, out_dists)) { err = get_dev_error(); return -1; }
+    return 0;
+}
+
 // The range sink with a candidate group per query.  The labels go to the device as live_labels leaves them.
 int HnswIndex::exact_range_query_grouped(const float *queries, int count, int dim, float range, const int *row_group, long long n_row_group,
                                          const int *query_group, int n_groups, int *counts, std::vector<int> &ids, std::vector<float> &dists, std::string &err)

@@ -99,6 +99,14 @@ public:
     // hnsw_mi355x_duplicate_groups: the single-linkage groups of the live, allowed ids (Device::exact_range_groups);
     // out_labels[0, length), cap >= length.
     int duplicate_groups(float range, const uint32_t *allow_bits, long long nbits, int *out_labels, long long cap, uint64_t *out_info, std::string &err);
+    // hnsw_mi355x_graph_duplicate_groups / hnsw_mi355x_near_edges: duplicate_groups' members, joined along the
+    // within-edges of layer 0 of the graph mirror (Device::graph_edge_groups / graph_near_edges), which is brought up to date first
+    // (sync_graph) as for get_info.  On the primary context; liveness and allow_bits go down as one bitset.  out_labels[0, length),
+    // cap >= length; out_info has five entries.  near_edges keeps the edges in the context (*out_count of them) until
+    // near_edges_results copies them out (cap >= that count) or the next near_edges replaces them.
+    int graph_duplicate_groups(float range, const uint32_t *allow_bits, long long nbits, int *out_labels, long long cap, uint64_t *out_info, std::string &err);
+    int near_edges(float range, const uint32_t *allow_bits, long long nbits, long long *out_count, std::string &err);
+    int near_edges_results(int *out_src, int *out_dst, float *out_dists, long long cap, std::string &err);
     // hnsw_mi355x_exact_range_query_grouped: exact_range_query with exact_knn_query_grouped's group per query
     // (Device::exact_range_grouped); the labels of vacant slots are taken out as for that call
     int exact_range_query_grouped(const float *queries, int count, int dim, float range, const int *row_group, long long n_row_group, const int *query_group,

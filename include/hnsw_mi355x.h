@@ -486,6 +486,32 @@ int hnsw_mi355x_exact_range_query_by_id(void *handle, const int *ids, int count,
  * whose sink is a union-find on the device: no list is built, sorted or copied.  Fewer than two members launch nothing.  NULL
  * handle: 0, out_info zeroed.  NULL out_info, or NULL out_labels with length > 0: -1. */
 int hnsw_mi355x_duplicate_groups(void *handle, float range, const uint32_t *allow_bits, long long nbits, int *out_labels, long long cap, uint64_t out_info[4]);
+/* NEAR-DUPLICATES OVER THE GRAPH'S EDGES: the question of the two calls above asked of layer 0 of the index's graph
+ * instead of every pair -- n x (at most 2 MaxEdges) distances instead of m (m - 1) / 2.  The MEMBERS are those of
+ * hnsw_mi355x_duplicate_groups.  An EDGE is a pair (i, j): i a member, j in i's layer-0 list, j a member; it is directed (j listing i
+ * too is a second edge).  It is WITHIN the range when the distance with the stored row of i as the query and row j as the candidate is
+ * <= range: the float compare, so a NaN range or distance admits nothing, +inf every edge whose distance is a number, a negative
+ * range is ordinary; the bits are those hnsw_mi355x_exact_range_query_by_id reports for j in i's list.  Both calls bring the graph
+ * mirror up to date first, run on the primary device context, take the handle exclusively and leave the resident query set and
+ * every other call's pending results as they were.
+ *
+ * hnsw_mi355x_graph_duplicate_groups: the groups are the connected components of the members under the within-edges read both ways.
+ * out_labels[v], v < length: the smallest member id of v's group, -1 where v is no member -- unique, whatever order the device
+ * joins in.  Where the metric's value does not depend on which of two rows is the query (DESIGN.md 3.30 says for which kinds that
+ * holds bit for bit) every within-edge is a pair hnsw_mi355x_duplicate_groups joins too, so these groups are that call's groups or
+ * a refinement of them: two near-duplicates with no path of within-edges between them stay apart.  cap: the entries of out_labels;
+ * cap < length is -1 with a message.  out_info[0] members, [1] groups, [2] edges within the range (directed), [3] edges measured
+ * (directed edges between members: the distances taken), [4] launches of the edge kernel.  Fewer than two members launch nothing.
+ * NULL handle: 0, out_info zeroed.  NULL out_info, or NULL out_labels with length > 0: -1. */
+int hnsw_mi355x_graph_duplicate_groups(void *handle, float range, const uint32_t *allow_bits, long long nbits, int *out_labels, long long cap,
+                                       uint64_t out_info[5]);
+/* hnsw_mi355x_near_edges: the within-edges themselves.  The call counts them into *out_count and keeps them in the index until
+ * hnsw_mi355x_near_edges_results copies them into out_src / out_dst / out_dists (cap entries each; cap below the count kept: -1 with a
+ * message, nothing written) or the next hnsw_mi355x_near_edges replaces them.  Order: ascending by src; the entries of one src
+ * ascending by (distance, dst) with -0 and +0 equal -- that item's hnsw_mi355x_exact_range_query_by_id list restricted to its
+ * layer-0 list, in that list's order and with its distance bits.  NULL handle: 0 and a count of 0.  NULL out_count: -1. */
+int hnsw_mi355x_near_edges(void *handle, float range, const uint32_t *allow_bits, long long nbits, long long *out_count);
+int hnsw_mi355x_near_edges_results(void *handle, int *out_src, int *out_dst, float *out_dists, long long cap);
 /* Counters of the by-id calls since creation or hnswdev_reset_stats / hnsw_mi355x_reset_stats, summed over the device contexts:
  * out[0] knn_query_by_id / exact_knn_query_by_id calls that reached a device, out[1] queries traversed on the device, out[2] of
  * those handed back to the host traversal, out[3] queries scanned, out[4] rows gathered (get_vectors' included), out[5] pairs
@@ -891,6 +917,15 @@ int hnswdev_exact_range_by_id(void *ctx, const int *ids, int nq, long long n_row
  * pending is touched. */
 int hnswdev_exact_range_groups(void *ctx, long long n_rows, float range, const uint32_t *allow_bits, long long nbits, int *out_labels,
                                uint64_t out_info[4]);
+/* The calls behind hnsw_mi355x_graph_duplicate_groups / hnsw_mi355x_near_edges, on the context's own rows and the graph it was given
+ * (hnswdev_graph_begin .. _commit): the members are the uploaded rows [0, n_rows) that allow_bits allows and that are nodes of the
+ * graph; out_labels has min(n_rows, uploaded rows) entries, out_info as there.  hnswdev_graph_near_edges counts and keeps,
+ * hnswdev_graph_near_edges_results fetches (cap below the count kept: -1 with a message).  No graph committed while n_rows > 0 rows
+ * are uploaded: -1.  Neither the resident set nor what hnswdev_exact_range_results has pending is touched. */
+int hnswdev_graph_edge_groups(void *ctx, long long n_rows, float range, const uint32_t *allow_bits, long long nbits, int *out_labels,
+                              uint64_t out_info[5]);
+int hnswdev_graph_near_edges(void *ctx, long long n_rows, float range, const uint32_t *allow_bits, long long nbits, long long *out_count);
+int hnswdev_graph_near_edges_results(void *ctx, int *out_src, int *out_dst, float *out_dists, long long cap);
 /* out[0 .. 5] as hnsw_mi355x_by_id_info, of this context; zeroed by hnswdev_reset_stats. */
 int hnswdev_by_id_info(void *ctx, uint64_t out[6]);
 /* Measurement aid: the HIP-event time, in ms, of the tagged calls' list-building kernels (count, offsets, fill) on this context
