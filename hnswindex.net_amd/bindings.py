@@ -151,6 +151,9 @@ lib.hnsw_mi355x_exact_range_query_by_id.argtypes = [ct.c_void_p, _I, ct.c_int, c
 lib.hnsw_mi355x_duplicate_groups.restype = ct.c_int
 lib.hnsw_mi355x_duplicate_groups.argtypes = [ct.c_void_p, ct.c_float, _U32, ct.c_longlong, _I, ct.c_longlong, ct.POINTER(ct.c_uint64)]
 _GROUPS_INFO = ("members", "groups", "pairs_within", "pairs_measured")   # out_info[0 .. 3] of hnsw_mi355x_duplicate_groups
+lib.hnsw_mi355x_density_clusters.restype = ct.c_int
+lib.hnsw_mi355x_density_clusters.argtypes = [ct.c_void_p, ct.c_float, ct.c_int, _U32, ct.c_longlong, _I, _I, ct.c_longlong, ct.POINTER(ct.c_uint64)]
+_DENSITY_INFO = ("members", "clusters", "core", "border", "noise", "pairs_within", "pairs_measured", "scans")   # out_info[0 .. 7] of hnsw_mi355x_density_clusters
 lib.hnsw_mi355x_graph_duplicate_groups.restype = ct.c_int
 lib.hnsw_mi355x_graph_duplicate_groups.argtypes = [ct.c_void_p, ct.c_float, _U32, ct.c_longlong, _I, ct.c_longlong, ct.POINTER(ct.c_uint64)]
 lib.hnsw_mi355x_near_edges.restype = ct.c_int
@@ -330,6 +333,8 @@ lib.hnswdev_exact_range_by_id.restype = ct.c_int
 lib.hnswdev_exact_range_by_id.argtypes = [ct.c_void_p, _I, ct.c_int, ct.c_longlong, ct.c_float, _U32, ct.c_longlong, _I]
 lib.hnswdev_exact_range_groups.restype = ct.c_int
 lib.hnswdev_exact_range_groups.argtypes = [ct.c_void_p, ct.c_longlong, ct.c_float, _U32, ct.c_longlong, _I, ct.POINTER(ct.c_uint64)]
+lib.hnswdev_exact_range_density.restype = ct.c_int
+lib.hnswdev_exact_range_density.argtypes = [ct.c_void_p, ct.c_longlong, ct.c_float, ct.c_int, _U32, ct.c_longlong, _I, _I, ct.POINTER(ct.c_uint64)]
 lib.hnswdev_graph_edge_groups.restype = ct.c_int
 lib.hnswdev_graph_edge_groups.argtypes = [ct.c_void_p, ct.c_longlong, ct.c_float, _U32, ct.c_longlong, _I, ct.POINTER(ct.c_uint64)]
 lib.hnswdev_graph_near_edges.restype = ct.c_int
@@ -1054,6 +1059,37 @@ class Index:
             raise RuntimeError(last_error())
         return labels, {name: int(info[i]) for i, name in enumerate(_GROUPS_INFO)}
 
+    # ---- density clusters ----
+    def _density(self, radius, min_samples, allowed, want_labels):
+        if int(min_samples) < 1:    # (said here as well: an index that holds nothing yet has no handle to say it)
+            raise ValueError("density_clusters: min_samples = %d is below 1" % int(min_samples))
+        n = int(self.length)
+        labels = np.full(n, -1, dtype=np.int32) if want_labels else None
+        counts = np.full(n, -1, dtype=np.int32)
+        info = (ct.c_uint64 * 8)()
+        words, nbits = allow_bits(allowed) if allowed is not None else (None, 0)
+        words, wp = _words_arg(words) if allowed is not None else (None, None)
+        lp = labels.ctypes.data_as(_I) if want_labels else None
+        if self._h and lib.hnsw_mi355x_density_clusters(self._h, radius, int(min_samples), wp, nbits, lp, counts.ctypes.data_as(_I), n, info) < 0:
+            raise RuntimeError(last_error())
+        return labels, counts, {name: int(info[i]) for i, name in enumerate(_DENSITY_INFO)}
+
+    def density_clusters(self, radius: float, min_samples: int, allowed=None) -> Tuple[npt.NDArray[np.int32], npt.NDArray[np.int32], dict]:
+        """DBSCAN over the stored rows (hnsw_mi355x_density_clusters): (labels int32[length], counts int32[length], info).  The
+        members and the pair rule are duplicate_groups', which is this call at min_samples = 1: members a < b are within when the
+        distance from the stored row of a, taken as the query, to row b is <= radius.  counts[v]: the within pairs that hold v, -1
+        where v is no member.  A member is core when counts[v] + 1 >= min_samples.  The clusters are the connected components of the
+        core members under the within pairs between two of them; labels[v] of a core member is the smallest core id of its cluster.
+        A member that is not core takes the label of its core within-neighbour of smallest (distance, id) -- a border -- or -1 -- noise;
+        a non-member has -1 as well.  info: members, clusters, core, border, noise, pairs_within, pairs_measured (m (m - 1) / 2 per
+        scan), scans (1, or 2 where the within pairs did not fit the device's pair arena; 0 with fewer than two members)."""
+        return self._density(radius, min_samples, allowed, True)
+
+    def neighbor_counts(self, radius: float, allowed=None) -> npt.NDArray[np.int32]:
+        """The local density alone (hnsw_mi355x_density_clusters with no labels): int32[length], counts[v] the members within
+        `radius` of member v -- density_clusters' counts -- and -1 where v is no member.  One scan; no pair is kept, nothing is joined."""
+        return self._density(radius, 1, allowed, False)[1]
+
     # ---- near-duplicates over the graph's edges (DESIGN.md 3.30) ----
     def graph_duplicate_groups(self, radius: float, allowed=None) -> Tuple[npt.NDArray[np.int32], dict]:
         """duplicate_groups asked of the graph (hnsw_mi355x_graph_duplicate_groups): (int32[length], info).  The members are
@@ -1563,6 +1599,18 @@ class DeviceBackend:
         words, wp = _words_arg(words) if allowed is not None else (None, None)
         self._check(lib.hnswdev_exact_range_groups(self._ctx, int(n_rows), float(radius), wp, nbits, labels.ctypes.data_as(_I), info))
         return labels, {name: int(info[i]) for i, name in enumerate(_GROUPS_INFO)}
+
+    def exact_range_density(self, radius: float, min_samples: int, n_rows: int, allowed=None, labels=True):
+        """hnswdev_exact_range_density: (int32[n_rows] labels or None, int32[n_rows] counts, info dict) -- Index.density_clusters on the
+        uploaded rows of [0, n_rows) that `allowed` allows; labels=False: the counts alone (one scan, the label slots of info 0)."""
+        out_labels = np.full(int(n_rows), -1, dtype=np.int32) if labels else None
+        counts = np.full(int(n_rows), -1, dtype=np.int32)
+        info = (ct.c_uint64 * 8)()
+        words, nbits = allow_bits(allowed) if allowed is not None else (None, 0)
+        words, wp = _words_arg(words) if allowed is not None else (None, None)
+        self._check(lib.hnswdev_exact_range_density(self._ctx, int(n_rows), float(radius), int(min_samples), wp, nbits,
+                                                    out_labels.ctypes.data_as(_I) if labels else None, counts.ctypes.data_as(_I), info))
+        return out_labels, counts, {name: int(info[i]) for i, name in enumerate(_DENSITY_INFO)}
 
     def graph_edge_groups(self, radius: float, n_rows: int, allowed=None):
         """hnswdev_graph_edge_groups: (int32[n_rows] labels, info dict) -- Index.graph_duplicate_groups on the uploaded rows of

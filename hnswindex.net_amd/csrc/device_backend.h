@@ -129,6 +129,8 @@ struct RangeFilter;      // ... the filter of one range call: its kind, per-id a
 struct PredicateCall;    // device_backend.hip: the arguments every KnnQuery with a predicate over ids has
 template <class K> struct PredicatePlan; // ... and what its launches need, K the kernel's type
 struct ExactScanArgs;    // dk_exact.h: what one launch of the flat scan reads
+struct ExactDensityPair; // ... a within pair of the density clusters: 16 bytes of the pair arena
+struct ExactTriangle;    // device_backend.hip: the members and the plan of a scan over the pairs a < b of an id list
 enum class ExactStart;   // device_backend.hip: how a flat-scan call begins -- failed, nothing to measure, ready
 struct ExactScanInput;   // ... the queries and the id list of an ungrouped flat scan
 struct ExactCollapseArgs; // ... the labels on the device, the cap and the device counters of a collapsed one
@@ -490,6 +492,16 @@ public:
     // union-find as its sink (exact_scan_kernel<M, ExactRangeUnion>): no list is kept or copied.  Fewer than two members: no launch.
     // Neither the resident set nor exact_range's pending results are touched.
     bool exact_range_groups(long long n_rows, float range, const uint32_t *allow_bits, long long nbits, int *out_labels, uint64_t *out_info);
+    // hnswdev_exact_range_density: DBSCAN over exact_range_groups' members and within pairs.  out_counts[v]: the
+    // within pairs that hold v, -1 where v is no member.  v is core when out_counts[v] + 1 >= min_samples (min_samples < 1: an error);
+    // the clusters are the components of the core members under the within pairs between two of them, labelled with their smallest
+    // core id; a member that is not core takes the label of its core within-neighbour of smallest (distance, id), -1 without one.
+    // out_info: [members, clusters, core, border, noise, pairs within, pairs measured, scans].  out_labels == nullptr: the counts
+    // alone -- one scan, no arena, no union-find, the slots that need labels 0.  Otherwise one scan (ExactRangeDensity) and the pairs
+    // kept in an arena, or two scans where the arena could not hold them (ExactRangeDensityJoin).  Fewer than two members: no launch.
+    // Neither the resident set nor exact_range's pending results are touched.
+    bool exact_range_density(long long n_rows, float range, int min_samples, const uint32_t *allow_bits, long long nbits, int *out_labels, int *out_counts,
+                             uint64_t *out_info);
     // hnswdev_graph_edge_groups / hnswdev_graph_near_edges: near-duplicates over the EDGES of layer 0 of the
     // committed graph.  The MEMBERS are exact_range_groups' -- the uploaded rows of [0, n_rows) that allow_bits allows -- that are
     // nodes of the graph.  An edge (i, j): i a member, j in i's layer-0 list, j a member (directed); it is within the range when the
@@ -767,6 +779,15 @@ private:
     bool exact_range_rounds(const char *who, const ExactScanInput &in, int nq, float range, const int *d_self, int *out_counts);
     DevBuf<int> x_uparent_;               // exact_range_groups: the union-find's parent[], then the labels behind it
     DevBuf<unsigned long long> x_upairs_; // ... pairs within the range, counted on the device
+    // what exact_range_groups and exact_range_density share (device_backend.hip): the members listed, the plan of the triangle's
+    // scans and their buffers; then one scan of the triangle, a timed launch per round of members
+    bool exact_triangle_begin(const char *who, long long n_rows, const uint32_t *allow_bits, long long nbits, ExactTriangle *t);
+    bool exact_triangle_ready(const char *who, ExactTriangle *t);
+    template <class Launch> // launch(args, tiles, stream) -> hipError_t: the scan with the call's sink, its queries' ids in x_self_
+    bool exact_triangle_scan(const ExactTriangle &t, Launch &&launch, unsigned long long *measured);
+    DevBuf<int> x_dcounts_;               // exact_range_density: within pairs per id, -1 off the members
+    DevBuf<unsigned long long> x_dattach_; // ... per id: the smallest (distance, core id) key offered to a member that is not core
+    DevBuf<ExactDensityPair> x_darena_;   // ... phase A's within pairs: 2^24 records (256 MiB) unless `density_pair_cap` says otherwise
     bool exact_range_finish(ExactRangeWork &w, int ns, const unsigned *c, const long long *seg, const int *sq, const long long *obase, size_t base,
                             bool counts_on_device, uint64_t *by_device, uint64_t *by_host);
     DevBuf<unsigned long long> x_rarena_; // exact_range: the round's keys, a segment per query: at most 1 GiB, grown on demand and kept

@@ -4939,28 +4939,38 @@ bool Device::exact_range_by_id(const int *ids, int nq, long long n_rows, float r
 // its sink, counted and timed like any (exact_timed_scan: exact_evals are the pairs measured); then one kernel turns parent[] into
 // labels.  The members are listed on the host -- the bitset is the host's -- so that the rounds' ids need no copy back.
 constexpr long long kExactUnionChunk = 2048; // rows of a chunk of the groups' scan unless `exact_chunk` forces them
-bool Device::exact_range_groups(long long n_rows, float range, const uint32_t *allow_bits, long long nbits, int *out_labels, uint64_t *out_info)
+
+// A scan over the pairs a < b of the members (exact_range_groups, exact_range_density): who they are, and how the triangle is cut.
+struct ExactTriangle {
+    std::vector<int> members; // ascending
+    long long n = 0, m = 0;   // the rows that exist below n_rows; the members
+    long long round = 0;      // members that are the queries of one launch
+    ExactPlan p;              // tile, piece, chunks; lds for a sink that keeps no list
+};
+
+// The members: the rows below min(n_rows, uploaded) that allow_bits allows.  No device work.
+bool Device::exact_triangle_begin(const char *who, long long n_rows, const uint32_t *allow_bits, long long nbits, ExactTriangle *t)
 {
-    const char *who = "exact_range_groups";
-    if (!out_info || n_rows < 0 || (allow_bits && nbits < 0)) { set_dev_error(std::string(who) + ": bad argument"); return false; }
-    for (int i = 0; i < 4; ++i) out_info[i] = 0;
+    if (n_rows < 0 || (allow_bits && nbits < 0)) { set_dev_error(std::string(who) + ": bad argument"); return false; }
     if (!allow_bits) nbits = 0;
-    const long long n = std::min(n_rows, n_rows_hw_), n_allow = allow_bits ? std::min(nbits, n) : n;
-    if (n > 0 && !out_labels) { set_dev_error(std::string(who) + ": bad argument"); return false; }
-    std::vector<int> members;
+    t->n = std::min(n_rows, n_rows_hw_);
+    const long long n_allow = allow_bits ? std::min(nbits, t->n) : t->n;
     for (long long id = 0; id < n_allow; ++id)
-        if (!allow_bits || ((allow_bits[id >> 5] >> (id & 31)) & 1u)) members.push_back((int)id);
-    const long long m = (long long)members.size();
-    for (long long v = 0; v < n; ++v) out_labels[v] = -1;
-    for (const int v : members) out_labels[v] = v; // (what fewer than two members leave; the device's labels replace it otherwise)
-    out_info[0] = (unsigned long long)m;
-    out_info[1] = (unsigned long long)m;
-    if (m < 2) return true; // nothing to measure: no launch
+        if (!allow_bits || ((allow_bits[id >> 5] >> (id & 31)) & 1u)) t->members.push_back((int)id);
+    t->m = (long long)t->members.size();
+    return true;
+}
+
+// Two members or more: the context bound, the round, the tile and the chunks, the query buffers, the members' ids in x_ids_ (enqueued:
+// the caller synchronises behind its own initialisation, before the first scan uses the pinned stage again).
+bool Device::exact_triangle_ready(const char *who, ExactTriangle *t)
+{
     if (!bind()) return false;
-    hipStream_t st = S(stream_);
+    const long long m = t->m;
     const int forced_round = diag("exact_union_round", 0);
-    const long long round = std::min<long long>(m, forced_round > 0 ? forced_round : 65536);
-    ExactPlan p = exact_plan((int)round, m, 1, pitch_, num_cu_); // the tile as for lists of one key: this sink keeps none
+    t->round = std::min<long long>(m, forced_round > 0 ? forced_round : 65536);
+    ExactPlan &p = t->p;
+    p = exact_plan((int)t->round, m, 1, pitch_, num_cu_); // the tile as for lists of one key: these sinks keep none
     p.lds = exact_scan_lds(p.qtile, p.piece, pitch_, 0);
     if (p.lds > 64 * 1024) { set_dev_error(std::string(who) + ": tile exceeds the LDS budget"); return false; }
     if (diag("exact_chunk", 0) <= 0) {
@@ -4972,33 +4982,66 @@ bool Device::exact_range_groups(long long n_rows, float range, const uint32_t *a
         p.chunk = ((m + chunks - 1) / chunks + kExactIterRows - 1) / kExactIterRows * kExactIterRows;
         p.n_chunks = (int)((m + p.chunk - 1) / p.chunk);
     }
-    const size_t cap = (size_t)std::max<long long>(round, 1024);
-    if (!x_queries_.grow((size_t)round * pitch_, cap * pitch_) || (metric_ == M_COS && !x_q_sn_.grow((size_t)round, cap))) return false;
-    if (!x_uparent_.grow(2 * (size_t)n) || !x_upairs_.grow(1)) return false;
-    if (!upload_ids(members.data(), (int)m, x_ids_)) return false;
-    HIP_OK(exact_union_init_launch(x_ids_, m, x_uparent_, n, st));
-    HIP_OK(hipMemsetAsync(x_upairs_, 0, sizeof(unsigned long long), st));
-    HIP_OK(hipStreamSynchronize(st)); // the pinned stage is used again by the rounds
-    unsigned long long measured = 0;
-    for (long long off = 0; off < m; off += round) {
-        const int nr = (int)std::min<long long>(round, m - off);
-        if (!gather_queries(members.data() + off, nr, x_self_, x_queries_, x_q_sn_)) return false;
+    const size_t cap = (size_t)std::max<long long>(t->round, 1024);
+    if (!x_queries_.grow((size_t)t->round * pitch_, cap * pitch_) || (metric_ == M_COS && !x_q_sn_.grow((size_t)t->round, cap))) return false;
+    return upload_ids(t->members.data(), (int)m, x_ids_);
+}
+
+// One scan of the triangle: a round of members at a time are gathered as the queries (their ids in x_self_) and `launch` enqueues the
+// scan with the caller's sink, counted and timed like any (exact_timed_scan).  *measured += the pairs the kernel counted.
+template <class Launch>
+bool Device::exact_triangle_scan(const ExactTriangle &t, Launch &&launch, unsigned long long *measured)
+{
+    hipStream_t st = S(stream_);
+    const ExactPlan &p = t.p;
+    for (long long off = 0; off < t.m; off += t.round) {
+        const int nr = (int)std::min<long long>(t.round, t.m - off);
+        if (!gather_queries(t.members.data() + off, nr, x_self_, x_queries_, x_q_sn_)) return false;
         unsigned long long *h_ev = static_cast<unsigned long long *>(pinned_stage(8));
         if (!h_ev) return false;
         ExactScanArgs a;
         if (!exact_scan_args(x_queries_, metric_ == M_COS ? x_q_sn_.get() : nullptr, 0, nr, p.qtile, p.piece, &a)) return false;
-        a.ids = x_ids_; a.m = m; a.chunk = p.chunk; a.n_chunks = p.n_chunks;
-        const ExactRangeUnion sink{range, x_uparent_, x_self_, x_upairs_};
+        a.ids = x_ids_; a.m = t.m; a.chunk = p.chunk; a.n_chunks = p.n_chunks;
         const unsigned tiles = (unsigned)((nr + p.qtile - 1) / p.qtile);
         const auto enqueue = [&]() -> bool {
-            hipError_t e = hipSuccess;
-            with_metric(metric_, [&](auto mt) { e = exact_range_union_scan_launch<mt>(a, sink, tiles, p.lds, st); });
-            HIP_OK(e);
+            HIP_OK(launch(a, tiles, st));
             return true;
         };
         if (!exact_timed_scan(h_ev, enqueue, [] { return true; })) return false;
-        measured += *h_ev;
+        *measured += *h_ev;
     }
+    return true;
+}
+
+bool Device::exact_range_groups(long long n_rows, float range, const uint32_t *allow_bits, long long nbits, int *out_labels, uint64_t *out_info)
+{
+    const char *who = "exact_range_groups";
+    if (!out_info) { set_dev_error(std::string(who) + ": bad argument"); return false; }
+    ExactTriangle t;
+    if (!exact_triangle_begin(who, n_rows, allow_bits, nbits, &t)) return false;
+    for (int i = 0; i < 4; ++i) out_info[i] = 0;
+    const long long n = t.n, m = t.m;
+    const std::vector<int> &members = t.members;
+    if (n > 0 && !out_labels) { set_dev_error(std::string(who) + ": bad argument"); return false; }
+    for (long long v = 0; v < n; ++v) out_labels[v] = -1;
+    for (const int v : members) out_labels[v] = v; // (what fewer than two members leave; the device's labels replace it otherwise)
+    out_info[0] = (unsigned long long)m;
+    out_info[1] = (unsigned long long)m;
+    if (m < 2) return true; // nothing to measure: no launch
+    if (!exact_triangle_ready(who, &t)) return false;
+    if (!x_uparent_.grow(2 * (size_t)n) || !x_upairs_.grow(1)) return false;
+    hipStream_t st = S(stream_);
+    HIP_OK(exact_union_init_launch(x_ids_, m, x_uparent_, n, st));
+    HIP_OK(hipMemsetAsync(x_upairs_, 0, sizeof(unsigned long long), st));
+    HIP_OK(hipStreamSynchronize(st)); // the pinned stage is used again by the rounds
+    unsigned long long measured = 0;
+    const auto launch = [&](const ExactScanArgs &a, unsigned tiles, hipStream_t s) {
+        const ExactRangeUnion sink{range, x_uparent_, x_self_, x_upairs_}; // (x_self_ as the round's gather left it)
+        hipError_t e = hipSuccess;
+        with_metric(metric_, [&](auto mt) { e = exact_range_union_scan_launch<mt>(a, sink, tiles, t.p.lds, s); });
+        return e;
+    };
+    if (!exact_triangle_scan(t, launch, &measured)) return false;
     int *d_labels = x_uparent_.get() + n;
     HIP_OK(exact_union_labels_launch(x_uparent_, n, d_labels, st));
     if (!exact_copy_out(out_labels, d_labels, 4 * (size_t)n)) return false;
@@ -5011,6 +5054,97 @@ bool Device::exact_range_groups(long long n_rows, float range, const uint32_t *a
     out_info[1] = groups;
     out_info[2] = *h;
     out_info[3] = measured;
+    return true;
+}
+
+// The density clusters: exact_range_groups' members, rounds, chunks and accounting, in two phases.  Phase A is one
+// scan of the triangle with ExactRangeDensity: counts[] and the number of within pairs are complete behind it whatever the arena
+// held.  The number comes to the host (8 bytes), which chooses phase B: density_pairs_kernel over the arena where every record
+// fitted, a second scan with ExactRangeDensityJoin where not.  Then one kernel turns parents and attach keys into labels, and the
+// host counts clusters, core, border and noise members from what it copied out, as exact_range_groups counts its groups.
+constexpr long long kDensityPairCap = 1LL << 24; // records of the pair arena (256 MiB) unless `density_pair_cap` says otherwise
+bool Device::exact_range_density(long long n_rows, float range, int min_samples, const uint32_t *allow_bits, long long nbits, int *out_labels, int *out_counts,
+                                 uint64_t *out_info)
+{
+    const char *who = "exact_range_density";
+    if (!out_info) { set_dev_error(std::string(who) + ": bad argument"); return false; }
+    if (min_samples < 1) { set_dev_error(std::string(who) + ": min_samples = " + std::to_string(min_samples) + " is below 1"); return false; }
+    ExactTriangle t;
+    if (!exact_triangle_begin(who, n_rows, allow_bits, nbits, &t)) return false;
+    for (int i = 0; i < 8; ++i) out_info[i] = 0;
+    const long long n = t.n, m = t.m;
+    const std::vector<int> &members = t.members;
+    if (n > 0 && !out_counts) { set_dev_error(std::string(who) + ": bad argument"); return false; }
+    for (long long v = 0; v < n; ++v) out_counts[v] = -1;
+    for (const int v : members) out_counts[v] = 0;
+    if (out_labels) {
+        for (long long v = 0; v < n; ++v) out_labels[v] = -1;
+        if (min_samples == 1) for (const int v : members) out_labels[v] = v; // (what fewer than two members leave: a lone member is core when it alone is enough)
+    }
+    // clusters, core, border and noise members from the labels and counts as they stand on the host
+    const auto count_kinds = [&]() {
+        unsigned long long clusters = 0, core = 0, border = 0;
+        for (const int v : members) {
+            const bool is_core = (long long)out_counts[v] + 1 >= (long long)min_samples;
+            core += (unsigned long long)is_core;
+            clusters += (unsigned long long)(is_core && out_labels[v] == v);
+            border += (unsigned long long)(!is_core && out_labels[v] >= 0);
+        }
+        out_info[1] = clusters; out_info[2] = core; out_info[3] = border; out_info[4] = (unsigned long long)m - core - border;
+    };
+    out_info[0] = (unsigned long long)m;
+    if (m < 2) { // nothing to measure: no launch
+        if (out_labels) count_kinds();
+        return true;
+    }
+    if (!exact_triangle_ready(who, &t)) return false;
+    hipStream_t st = S(stream_);
+    const int forced_cap = diag("density_pair_cap", 0);
+    // (no more records than there are pairs: a small member set does not allocate the whole arena)
+    const unsigned long long all_pairs = (unsigned long long)m * (unsigned long long)(m - 1) / 2;
+    const unsigned long long cap = !out_labels ? 0ull : forced_cap > 0 ? (unsigned long long)forced_cap : std::min<unsigned long long>(kDensityPairCap, all_pairs);
+    if (!x_dcounts_.grow((size_t)n) || !x_upairs_.grow(1)) return false;
+    if (out_labels && (!x_uparent_.grow(2 * (size_t)n) || !x_dattach_.grow((size_t)n) || !x_darena_.grow((size_t)cap))) return false;
+    HIP_OK(density_init_launch(x_ids_, m, x_dcounts_, out_labels ? x_dattach_.get() : nullptr, n, x_upairs_, st));
+    if (out_labels) HIP_OK(exact_union_init_launch(x_ids_, m, x_uparent_, n, st));
+    HIP_OK(hipStreamSynchronize(st)); // the pinned stage is used again by the rounds
+    const size_t lds_a = exact_density_lds(t.p.qtile, t.p.piece, pitch_);
+    if (lds_a > 64 * 1024) { set_dev_error(std::string(who) + ": tile exceeds the LDS budget"); return false; }
+    unsigned long long measured = 0, scans = 1;
+    const auto phase_a = [&](const ExactScanArgs &a, unsigned tiles, hipStream_t s) {
+        const ExactRangeDensity sink{range, x_self_, x_dcounts_, x_darena_, cap, x_upairs_}; // (x_self_ as the round's gather left it)
+        hipError_t e = hipSuccess;
+        with_metric(metric_, [&](auto mt) { e = exact_range_density_scan_launch<mt>(a, sink, tiles, lds_a, s); });
+        return e;
+    };
+    if (!exact_triangle_scan(t, phase_a, &measured)) return false;
+    unsigned long long *h = static_cast<unsigned long long *>(pinned_stage(8));
+    if (!h) return false;
+    HIP_OK(hipMemcpyAsync(h, x_upairs_, 8, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    const unsigned long long pairs_within = *h;
+    if (!exact_copy_out(out_counts, x_dcounts_, 4 * (size_t)n)) return false;
+    if (out_labels) {
+        if (pairs_within <= cap) {
+            HIP_OK(density_pairs_launch(x_darena_, pairs_within, x_dcounts_, min_samples, x_uparent_, x_dattach_, st));
+        } else { // the arena dropped records: the triangle once more, joined straight from the distances
+            const auto phase_b = [&](const ExactScanArgs &a, unsigned tiles, hipStream_t s) {
+                const ExactRangeDensityJoin sink{range, x_self_, x_dcounts_, min_samples, x_uparent_, x_dattach_};
+                hipError_t e = hipSuccess;
+                with_metric(metric_, [&](auto mt) { e = exact_range_density_join_scan_launch<mt>(a, sink, tiles, t.p.lds, s); });
+                return e;
+            };
+            if (!exact_triangle_scan(t, phase_b, &measured)) return false;
+            scans = 2;
+        }
+        int *d_labels = x_uparent_.get() + n;
+        HIP_OK(density_labels_launch(x_uparent_, x_dattach_, x_dcounts_, min_samples, n, d_labels, st));
+        if (!exact_copy_out(out_labels, d_labels, 4 * (size_t)n)) return false;
+        count_kinds();
+    }
+    out_info[5] = pairs_within;
+    out_info[6] = measured;
+    out_info[7] = scans;
     return true;
 }
 
@@ -5454,6 +5588,12 @@ DEV_API int hnswdev_exact_range_groups(void *ctx, long long n_rows, float range,
 {
     CTX_OR_FAIL();
     return d->exact_range_groups(n_rows, range, allow_bits, nbits, out_labels, out_info) ? 0 : -1;
+}
+DEV_API int hnswdev_exact_range_density(void *ctx, long long n_rows, float range, int min_samples, const uint32_t *allow_bits, long long nbits, int *out_labels,
+                                        int *out_counts, uint64_t *out_info)
+{
+    CTX_OR_FAIL();
+    return d->exact_range_density(n_rows, range, min_samples, allow_bits, nbits, out_labels, out_counts, out_info) ? 0 : -1;
 }
 DEV_API int hnswdev_graph_edge_groups(void *ctx, long long n_rows, float range, const uint32_t *allow_bits, long long nbits, int *out_labels,
                                       uint64_t *out_info)

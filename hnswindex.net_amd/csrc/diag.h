@@ -12,6 +12,7 @@
 //       xw_dry [1]  xw_stage [1]  trace [0]  lean [1]  exact_chunk [0 = the picker's]  exact_qtile [0 = the picker's]
 //       exact_range_cap [0 = the picker's]  exact_range_sort [0 = 4096]  exact_range_arena [0 = 1 GiB of keys]
 //       exact_union_round [0 = 65 536 members are the queries of one launch of duplicate_groups' scan]
+//       density_pair_cap [0 = 2^24 records (256 MiB) in the pair arena of density_clusters; fewer within pairs fit: one scan, more: two]
 //       edge_round [0 = 65 536 members are the owners of one launch of graph_duplicate_groups' / near_edges' edge kernel]
 //       tag_list_cap [0 = 2^28 ids in the candidate lists of one batch of masks of exact_knn_tagged]
 //       range_sort_long [1; 0 = range_sort_tagged_kernel hands a closure beyond its table to the host as the other two sorts do]

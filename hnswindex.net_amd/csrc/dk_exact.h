@@ -26,6 +26,11 @@
 //   exact_scan_kernel<M, ExactRangeSelf>        ExactRange, with ExactTopKSelf's rule: the query's own row offers no key and is not counted
 //   exact_scan_kernel<M, ExactRangeUnion>       no keys at all: a pair (a < b) within the range joins a and b in a union-find (dk_union_find.h)
 //   exact_union_init_kernel / exact_union_labels_kernel   every id its own root before the scans; labels = roots = smallest ids after them
+// and hnswdev_exact_range_density: DBSCAN over ExactRangeUnion's triangle, in two phases.
+//   exact_scan_kernel<M, ExactRangeDensity>      a pair within the range adds 1 to the counts of both ids and goes to a pair arena as a record
+//   density_pairs_kernel                         per record: both ends core -> uf_union; one end core -> a 64-bit min on the other's attach key
+//   exact_scan_kernel<M, ExactRangeDensityJoin>  the same per pair from a second scan, where the arena did not hold every record
+//   density_init_kernel / density_labels_kernel  counts 0 for the members before the scans; core: its root, border: its core's root, else -1
 // The kernels are compiled in the exact_<metric> units (exact_unit.hip, HNSW_EXACT_UNIT) and reached through the launchers declared here, so
 // that device_backend.hip holds none of their code.
 #pragma once
@@ -76,6 +81,7 @@ struct ExactTopK {
     static constexpr bool kSelf = false;
     static constexpr bool kCollapse = false;
     static constexpr bool kUnion = false;
+    static constexpr bool kDensity = false;
 };
 // ExactTopKSelf: ExactTopK where query q of the round is the stored row of id self[q] and that id is no candidate of it: the pair
 // produces no key and is not counted in ExactScanArgs::evals.  A duplicate of the row under another id is a candidate like any.
@@ -85,6 +91,7 @@ struct ExactTopKSelf {
     static constexpr bool kSelf = true;
     static constexpr bool kCollapse = false;
     static constexpr bool kUnion = false;
+    static constexpr bool kDensity = false;
     const int *self;               // [nq of the round]
 };
 // ExactTopKCollapse: the lists hold the COLLAPSED k smallest keys -- the first k keys of the ascending order that
@@ -98,6 +105,7 @@ struct ExactTopKCollapse {
     static constexpr bool kSelf = false;
     static constexpr bool kCollapse = true;
     static constexpr bool kUnion = false;
+    static constexpr bool kDensity = false;
     const int *row_group;          // [every id of the list]
     int per_group;                 // 1 <= per_group <= k
     unsigned long long *info;      // [2]
@@ -108,6 +116,7 @@ struct ExactRange {
     static constexpr bool kSelf = false;
     static constexpr bool kCollapse = false;
     static constexpr bool kUnion = false;
+    static constexpr bool kDensity = false;
     float range;
     unsigned *counts;              // [nq]
     const long long *seg_off;      // [nq + 1]
@@ -122,6 +131,7 @@ struct ExactRangeSelf {
     static constexpr bool kSelf = true;
     static constexpr bool kCollapse = false;
     static constexpr bool kUnion = false;
+    static constexpr bool kDensity = false;
     float range;
     unsigned *counts;              // [nq]
     const long long *seg_off;      // [nq + 1]
@@ -141,10 +151,58 @@ struct ExactRangeUnion {
     static constexpr bool kSelf = true;
     static constexpr bool kCollapse = false;
     static constexpr bool kUnion = true;
+    static constexpr bool kDensity = false;
     float range;
     int *parent;                   // [every id of the list]
     const int *self;               // [nq of the launch]: ascending
     unsigned long long *pairs;     // out: measured pairs within the range, added up over the blocks
+};
+// ExactRangeDensity, phase A of the density clusters: ExactRangeUnion's triangle -- the same queries, the same
+// rid > self rule, the same early leave, the same count in ExactScanArgs::evals -- but a pair within the range joins nothing yet.
+// Whether it joins depends on whether its two ends are CORE, and that is a matter of counts[] that are complete only when the whole
+// scan is: one pass cannot do it.  So a within pair (a = self, b = rid, distance d)
+//   * adds 1 to counts[a] and to counts[b] (0 for every id of the list before the first launch: density_init_launch).  The self side
+//     is added up in LDS over the block (an int per query of the tile behind the layout of exact_scan_lds: exact_density_lds) and
+//     leaves with one global atomic per query and block; the row side is added up in registers over all the tile's queries and
+//     leaves with one global atomic per row and step of kExactIterRows rows;
+//   * is appended to arena[] as the record {a, b, bits of d, 0}.  A wave takes the places of all its within pairs of a step with ONE
+//     atomic on *n_pairs: a ballot says whether the wave has any, the popcounts of the eight group leaders' pair masks are read
+//     lane by lane into the wave's total and into every leader's offset; a record whose place is at or past arena_cap is dropped
+//     while the counter goes on counting -- *n_pairs ends as the number of within pairs whatever the capacity, and the counts are
+//     complete either way.  arena_cap == 0: counts only.
+struct alignas(16) ExactDensityPair { int a, b; unsigned d_bits, zero; }; // 16 bytes: one vector store
+struct ExactRangeDensity {
+    static constexpr bool kRange = true;
+    static constexpr bool kGrouped = false;
+    static constexpr bool kSelf = true;
+    static constexpr bool kCollapse = false;
+    static constexpr bool kUnion = false;
+    static constexpr bool kDensity = true;
+    static constexpr bool kJoin = false;
+    float range;
+    const int *self;               // [nq of the launch]: ascending
+    int *counts;                   // [every id of the list]
+    ExactDensityPair *arena;       // [arena_cap]
+    unsigned long long arena_cap;
+    unsigned long long *n_pairs;   // out: within pairs, kept or dropped
+};
+// ExactRangeDensityJoin, phase B where the arena did not hold every record: the triangle once more, counts[] now
+// complete and read-only, every within pair handed to density_join straight from its distance (the bits are phase A's: the same
+// kernel body measures).  No LDS behind the staged queries, no arena.
+struct ExactRangeDensityJoin {
+    static constexpr bool kRange = true;
+    static constexpr bool kGrouped = false;
+    static constexpr bool kSelf = true;
+    static constexpr bool kCollapse = false;
+    static constexpr bool kUnion = false;
+    static constexpr bool kDensity = true;
+    static constexpr bool kJoin = true;
+    float range;
+    const int *self;               // [nq of the launch]: ascending
+    const int *counts;             // [every id of the list]: phase A's, complete
+    int min_samples;               // v is core when counts[v] + 1 >= min_samples
+    int *parent;                   // [every id of the list]: exact_union_init_launch
+    unsigned long long *attach;    // [every id of the list]: kExactEmpty before phase B
 };
 struct ExactRangeSortArgs {
     const unsigned long long *arena;
@@ -171,6 +229,7 @@ struct ExactTopKGrouped {
     static constexpr bool kSelf = false;
     static constexpr bool kCollapse = false;
     static constexpr bool kUnion = false;
+    static constexpr bool kDensity = false;
     const ExactWorkItem *items;
 };
 // ExactRangeGrouped: ExactRange's segments behind ExactTopKGrouped's work items (list0, n_chunks and slot of an item are not read).
@@ -184,6 +243,7 @@ struct ExactRangeGrouped {
     static constexpr bool kSelf = false;
     static constexpr bool kCollapse = false;
     static constexpr bool kUnion = false;
+    static constexpr bool kDensity = false;
     float range;
     unsigned *counts;              // [segments]
     const long long *seg_off;      // [segments + 1]
@@ -208,8 +268,26 @@ inline size_t exact_scan_lds(int qtile, int piece, int dim, int k, int entry_byt
     return ((qtr * qw * 4 + 15) & ~(size_t)15) + qtr * (size_t)k * (size_t)entry_bytes + qtr * 8 + pending + 16;
 }
 
+// ... of ExactRangeDensity: the layout above without lists (k = 0) and, where ExactTopKCollapse's labels would begin, an int per
+// query slot of the tile: the within pairs of the block that hold that query
+inline size_t exact_density_lds(int qtile, int piece, int dim)
+{
+    return exact_scan_lds(qtile, piece, dim, 0) + (size_t)((qtile + kExactRQ - 1) / kExactRQ * kExactRQ) * 4;
+}
+
 template <int METRIC>
 hipError_t exact_scan_launch(const ExactScanArgs &a, unsigned n_qtiles, size_t lds, hipStream_t st);
+template <int METRIC> // lds: exact_density_lds
+hipError_t exact_range_density_scan_launch(const ExactScanArgs &a, const ExactRangeDensity &sink, unsigned n_qtiles, size_t lds, hipStream_t st);
+template <int METRIC> // lds: exact_scan_lds with k = 0, as ExactRangeUnion's
+hipError_t exact_range_density_join_scan_launch(const ExactScanArgs &a, const ExactRangeDensityJoin &sink, unsigned n_qtiles, size_t lds, hipStream_t st);
+// counts[0, n) = -1, then counts[id] = 0 for the m ids of the list; attach (nullptr: counts only) [0, n) = kExactEmpty; *n_pairs = 0
+hipError_t density_init_launch(const int *ids, long long m, int *counts, unsigned long long *attach, long long n, unsigned long long *n_pairs, hipStream_t st);
+// phase B over the arena's n_pairs records (all of them were kept): what ExactRangeDensityJoin does per within pair
+hipError_t density_pairs_launch(const ExactDensityPair *arena, unsigned long long n_pairs, const int *counts, int min_samples, int *parent,
+                                unsigned long long *attach, hipStream_t st);
+// labels[v], v in [0, n): a core member its root; a member that is not core its attach key's id's root, -1 without a key; -1 where counts[v] < 0
+hipError_t density_labels_launch(int *parent, const unsigned long long *attach, const int *counts, int min_samples, long long n, int *labels, hipStream_t st);
 template <int METRIC>
 hipError_t exact_range_scan_launch(const ExactScanArgs &a, const ExactRange &sink, unsigned n_qtiles, size_t lds, hipStream_t st);
 template <int METRIC>
@@ -268,6 +346,17 @@ __device__ __forceinline__ float exact_key_dist(unsigned long long key)
 {
     const unsigned dk = (unsigned)(key >> 32);
     return dk == 0xffffffffu ? __uint_as_float(0x7fc00000u) : key2f(dk);
+}
+
+// One within pair (a < b, distance d with a's row as the query) of the density clusters, once counts[] is complete:
+// both ends core -- the pair is an edge of a cluster: uf_union; exactly one end core -- the other end is a border candidate and keeps
+// the smallest (distance, core id) it is offered, a relaxed agent-scope 64-bit min on attach[border] (kExactEmpty before the first);
+// neither core: nothing.  The minimum does not depend on the order the pairs arrive in, and neither do the roots.
+__device__ __forceinline__ void density_join(const int *counts, int min_samples, int *parent, unsigned long long *attach, int a, int b, float d)
+{
+    const bool ca = counts[a] + 1 >= min_samples, cb = counts[b] + 1 >= min_samples;
+    if (ca && cb) uf_union(parent, a, b);
+    else if (ca != cb) (void)__hip_atomic_fetch_min(attach + (ca ? b : a), exact_key(d, ca ? a : b), GI_RELAXED);
 }
 
 // x into the ascending list L[0, k) of one wave (x < L[k - 1]: the last entry drops out).  From the top down, 64 entries at a time:
@@ -348,6 +437,7 @@ __global__ void __launch_bounds__(kExactThreads) exact_scan_kernel(const ExactSc
     [[maybe_unused]] int *labels = pend_cnt + 4; // ExactTopKCollapse: [QTR][k], the label of every list entry (exact_scan_lds: behind the rest)
     [[maybe_unused]] int *pend_lab = labels + (size_t)QTR * k; // ... [RQ][kExactIterRows], the label of every pending key
     [[maybe_unused]] unsigned dropped = 0, evicted = 0; // ... what this wave's inserts dropped and evicted (the same in all its lanes)
+    [[maybe_unused]] int *dens_cnt = pend_cnt + 4; // ExactRangeDensity: [QTR], the block's within pairs per query slot (exact_density_lds: in the labels' place)
     // the block's queries [q0, q0 + its number) of the round and entries [lo, hi) of the id list: a work item's, or worked out from
     // blockIdx.  q_in: a query of the round that this block answers; q_clamp: past the last of them a slot shadows it.
     long long q0, lo, hi;
@@ -370,7 +460,7 @@ __global__ void __launch_bounds__(kExactThreads) exact_scan_kernel(const ExactSc
         if constexpr (SINK::kGrouped) return q >= item_qend ? item_qend - 1 : q;
         else { if (q >= a.nq) q = a.nq - 1; return q; }
     };
-    if constexpr (SINK::kUnion) {
+    if constexpr (SINK::kUnion || SINK::kDensity) {
         // nothing to measure where the chunk's last id is not above the tile's first query id (both lists ascend): the whole block
         // leaves, in front of its first barrier
         const int last = a.ids ? a.ids[hi - 1] : (int)(hi - 1);
@@ -383,6 +473,9 @@ __global__ void __launch_bounds__(kExactThreads) exact_scan_kernel(const ExactSc
     for (int i = tid; i < QTR * k; i += kExactThreads) lists[i] = kExactEmpty;
     if (tid < QTR) thr[tid] = kExactEmpty;
     if (tid < RQ) pend_cnt[tid] = 0;
+    if constexpr (SINK::kDensity) {
+        if constexpr (!SINK::kJoin) { if (tid < QTR) dens_cnt[tid] = 0; }
+    }
     // (the first staging's barriers order these writes before their first readers)
 
     unsigned measured = 0; // pairs this lane turned into keys (lane 0 of a group: shadows of rows and queries excluded)
@@ -403,6 +496,7 @@ __global__ void __launch_bounds__(kExactThreads) exact_scan_kernel(const ExactSc
             rp[r] = a.rows + (size_t)rid[r] * (size_t)rw;
             if constexpr (SINK::kCollapse) rlab[r] = sink.row_group[rid[r]];
         }
+        [[maybe_unused]] int rc[RR] = {}; // ExactRangeDensity: within pairs of this step that hold row r, over all the tile's queries
         for (int qsub = 0; qsub < QT && q_in(q0 + qsub); qsub += RQ) {
             float acc[RQ][RR];
             int iacc[RQ][RR], ta[RR], tb[RQ];
@@ -528,7 +622,66 @@ __global__ void __launch_bounds__(kExactThreads) exact_scan_kernel(const ExactSc
                     }
                 }
             }
-            if constexpr (SINK::kUnion) {
+            if constexpr (SINK::kDensity) {
+                // no offers: a pair above the diagonal is counted; within the range it is joined at once (the second scan) or leaves a
+                // bit in wmask -- bit q * RR + r -- for the counting and the arena, which the whole wave does together below
+                unsigned wmask = 0;
+                int selfq[RQ] = {};
+                if (j == 0) {
+#pragma unroll
+                    for (int q = 0; q < RQ; ++q) {
+                        if (qsub + q >= QT || !q_in(q0 + qsub + q)) continue;
+                        selfq[q] = sink.self[q0 + qsub + q];
+#pragma unroll
+                        for (int r = 0; r < RR; ++r) {
+                            if (!rvalid[r] || rid[r] <= selfq[q]) continue; // the pair's other half, or the query's own row: not counted
+                            ++measured;
+                            if (dist[q][r] <= sink.range) {
+                                if constexpr (SINK::kJoin) density_join(sink.counts, sink.min_samples, sink.parent, sink.attach, selfq[q], rid[r], dist[q][r]);
+                                else wmask |= 1u << (q * RR + r);
+                            }
+                        }
+                    }
+                }
+                if constexpr (!SINK::kJoin) {
+                    if (__ballot(wmask != 0)) { // (all 64 lanes are here, and the test is the same in all of them)
+#pragma unroll
+                        for (int q = 0; q < RQ; ++q) {
+                            const int qc = __popc((wmask >> (q * RR)) & ((1u << RR) - 1u));
+                            if (qc) atomicAdd(&dens_cnt[qsub + q], qc); // LDS: flushed once per query at the block's end
+                        }
+                        unsigned total = 0;
+#pragma unroll
+                        for (int r = 0; r < RR; ++r) {
+                            unsigned col = 0;
+#pragma unroll
+                            for (int q = 0; q < RQ; ++q) col += (wmask >> (q * RR + r)) & 1u;
+                            rc[r] += (int)col; // the row side: added up over the tile's queries, flushed behind their loop
+                        }
+                        // the places: the wave's within pairs of this step are those of its eight group leaders (lanes 0, 8, .. 56), so
+                        // the wave's total and the pairs in front of a leader's own are sums of eight lane reads -- nothing per pair
+                        const int mine = __popc(wmask);
+                        unsigned before = 0;
+#pragma unroll
+                        for (int g = 0; g < 8; ++g) {
+                            const unsigned cg = (unsigned)__builtin_amdgcn_readlane(mine, 8 * g);
+                            before += (lane >> 3) > g ? cg : 0u;
+                            total += cg;
+                        }
+                        unsigned long long first = 0;
+                        if (lane == 0) first = atomicAdd(sink.n_pairs, (unsigned long long)total); // one global atomic per (wave, step)
+                        first = ((unsigned long long)__builtin_amdgcn_readfirstlane((unsigned)(first >> 32)) << 32) | __builtin_amdgcn_readfirstlane((unsigned)first);
+#pragma unroll
+                        for (int q = 0; q < RQ; ++q)
+#pragma unroll
+                            for (int r = 0; r < RR; ++r) {
+                                if (!((wmask >> (q * RR + r)) & 1u)) continue;
+                                const unsigned long long place = first + before + (unsigned)__popc(wmask & ((1u << (q * RR + r)) - 1u));
+                                if (place < sink.arena_cap) sink.arena[place] = ExactDensityPair{selfq[q], rid[r], __float_as_uint(dist[q][r]), 0u};
+                            }
+                    }
+                }
+            } else if constexpr (SINK::kUnion) {
                 // no offers: a pair above the diagonal is counted and, within the range, joined from the lane that holds its distance.
                 // uf_union waits for no other lane, and the lanes meet again behind this branch, in front of the next step's barriers.
                 if (j == 0) {
@@ -654,9 +807,24 @@ __global__ void __launch_bounds__(kExactThreads) exact_scan_kernel(const ExactSc
                 }
             }
         }
+        if constexpr (SINK::kDensity) {
+            if constexpr (!SINK::kJoin) { // the row side of the step's within pairs: one global atomic per row that has any
+#pragma unroll
+                for (int r = 0; r < RR; ++r)
+                    if (rc[r]) atomicAdd(&sink.counts[rid[r]], rc[r]);
+            }
+        }
     }
     __syncthreads();
     if (measured) atomicAdd(a.evals, (unsigned long long)measured); // one atomic per group that measured anything
+    if constexpr (SINK::kDensity) {
+        if constexpr (!SINK::kJoin) { // the self side: one global atomic per query of the tile that has any (the barrier above orders the LDS adds)
+            if (tid < QT && q_in(q0 + tid)) {
+                const int c = dens_cnt[tid];
+                if (c) atomicAdd(&sink.counts[sink.self[q0 + tid]], c);
+            }
+        }
+    }
     if constexpr (SINK::kUnion) {
         if (joined) atomicAdd(sink.pairs, (unsigned long long)joined);
     }
@@ -699,6 +867,19 @@ template <int METRIC>
 hipError_t exact_range_union_scan_launch(const ExactScanArgs &a, const ExactRangeUnion &sink, unsigned n_qtiles, size_t lds, hipStream_t st)
 {
     hipLaunchKernelGGL((exact_scan_kernel<METRIC, ExactRangeUnion>), dim3(n_qtiles, (unsigned)a.n_chunks), dim3(kExactThreads), lds, st, a, sink);
+    return hipGetLastError();
+}
+
+template <int METRIC>
+hipError_t exact_range_density_scan_launch(const ExactScanArgs &a, const ExactRangeDensity &sink, unsigned n_qtiles, size_t lds, hipStream_t st)
+{
+    hipLaunchKernelGGL((exact_scan_kernel<METRIC, ExactRangeDensity>), dim3(n_qtiles, (unsigned)a.n_chunks), dim3(kExactThreads), lds, st, a, sink);
+    return hipGetLastError();
+}
+template <int METRIC>
+hipError_t exact_range_density_join_scan_launch(const ExactScanArgs &a, const ExactRangeDensityJoin &sink, unsigned n_qtiles, size_t lds, hipStream_t st)
+{
+    hipLaunchKernelGGL((exact_scan_kernel<METRIC, ExactRangeDensityJoin>), dim3(n_qtiles, (unsigned)a.n_chunks), dim3(kExactThreads), lds, st, a, sink);
     return hipGetLastError();
 }
 
@@ -894,6 +1075,60 @@ hipError_t exact_union_init_launch(const int *ids, long long m, int *parent, lon
 hipError_t exact_union_labels_launch(int *parent, long long n, int *labels, hipStream_t st)
 {
     hipLaunchKernelGGL(exact_union_labels_kernel, dim3(exact_union_blocks(n)), dim3(256), 0, st, parent, n, labels);
+    return hipGetLastError();
+}
+
+// ---- the density clusters around ExactRangeDensity's launches: grid-stride, no kernel waits for another wave ----
+// Every id of the list has no neighbour yet.  (counts[] was filled with -1 in front of this launch: an id outside the list stays -1.)
+__global__ void __launch_bounds__(256) density_init_kernel(const int *__restrict__ ids, long long m, int *__restrict__ counts)
+{
+    const long long step = (long long)gridDim.x * 256;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < m; i += step) counts[ids[i]] = 0;
+}
+// Phase B from the arena: one thread per record.  A record is one 16-byte load.
+__global__ void __launch_bounds__(256) density_pairs_kernel(const ExactDensityPair *__restrict__ arena, unsigned long long n_pairs, const int *__restrict__ counts,
+                                                            int min_samples, int *parent, unsigned long long *attach)
+{
+    const unsigned long long step = (unsigned long long)gridDim.x * 256;
+    for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < n_pairs; i += step) {
+        const ExactDensityPair p = arena[i];
+        density_join(counts, min_samples, parent, attach, p.a, p.b, __uint_as_float(p.d_bits));
+    }
+}
+// The label of every id.  A core member: the root of its tree, the smallest core id of its cluster (only cores were joined, and
+// uf_union hooks the larger root under the smaller).  Any other member: the root of the core its attach key names -- the core
+// neighbour with the smallest (distance, id) -- or -1 where no core offered itself.  No member: -1.
+__global__ void __launch_bounds__(256) density_labels_kernel(int *parent, const unsigned long long *__restrict__ attach, const int *__restrict__ counts,
+                                                             int min_samples, long long n, int *__restrict__ labels)
+{
+    const long long step = (long long)gridDim.x * 256;
+    for (long long v = (long long)blockIdx.x * 256 + threadIdx.x; v < n; v += step) {
+        const int c = counts[v];
+        int label = -1;
+        if (c >= 0 && c + 1 >= min_samples) label = uf_find(parent, (int)v);
+        else if (c >= 0 && attach[v] != kExactEmpty) label = uf_find(parent, (int)(unsigned)attach[v]);
+        labels[v] = label;
+    }
+}
+hipError_t density_init_launch(const int *ids, long long m, int *counts, unsigned long long *attach, long long n, unsigned long long *n_pairs, hipStream_t st)
+{
+    hipError_t e = hipMemsetAsync(counts, 0xff, sizeof(int) * (size_t)n, st);
+    if (e == hipSuccess && attach) e = hipMemsetAsync(attach, 0xff, sizeof(unsigned long long) * (size_t)n, st); // kExactEmpty
+    if (e == hipSuccess) e = hipMemsetAsync(n_pairs, 0, sizeof(unsigned long long), st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(density_init_kernel, dim3(exact_union_blocks(m)), dim3(256), 0, st, ids, m, counts);
+    return hipGetLastError();
+}
+hipError_t density_pairs_launch(const ExactDensityPair *arena, unsigned long long n_pairs, const int *counts, int min_samples, int *parent,
+                                unsigned long long *attach, hipStream_t st)
+{
+    if (n_pairs == 0) return hipSuccess;
+    hipLaunchKernelGGL(density_pairs_kernel, dim3(exact_union_blocks((long long)n_pairs)), dim3(256), 0, st, arena, n_pairs, counts, min_samples, parent, attach);
+    return hipGetLastError();
+}
+hipError_t density_labels_launch(int *parent, const unsigned long long *attach, const int *counts, int min_samples, long long n, int *labels, hipStream_t st)
+{
+    hipLaunchKernelGGL(density_labels_kernel, dim3(exact_union_blocks(n)), dim3(256), 0, st, parent, attach, counts, min_samples, n, labels);
     return hipGetLastError();
 }
 

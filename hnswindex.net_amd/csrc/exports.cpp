@@ -522,6 +522,25 @@ API int hnsw_mi355x_duplicate_groups(void *handle, float range, const uint32_t *
     return 0;
 }
 
+// DBSCAN over the live, allowed ids: hnsw_mi355x_duplicate_groups' members and pair rule; clusters grow through core
+// members only, the others are border or noise, and out_counts is every member's number of neighbours.  out_labels == NULL: the
+// counts alone.  Exclusive: it uses the scan's buffers.
+API int hnsw_mi355x_density_clusters(void *handle, float range, int min_samples, const uint32_t *allow_bits, long long nbits, int *out_labels, int *out_counts,
+                                     long long cap, uint64_t *out_info)
+{
+    if (out_info) for (int i = 0; i < 8; ++i) out_info[i] = 0;
+    if (!handle) return 0;
+    if (!out_info) { set_error("System.ArgumentNullException: hnsw_mi355x_density_clusters: out_info"); return -1; }
+    if (allow_bits && nbits < 0) { set_error("System.ArgumentException: hnsw_mi355x_density_clusters: nbits must be >= 0"); return -1; }
+    LOCK_INDEX(handle);
+    std::string err;
+    if (static_cast<HnswIndex *>(handle)->density_clusters(range, min_samples, allow_bits, nbits, out_labels, out_counts, cap, out_info, err) < 0) {
+        set_error(err);
+        return -1;
+    }
+    return 0;
+}
+
 // Near-duplicates over the graph's edges: hnsw_mi355x_duplicate_groups' members and label convention, joined along
 // the layer-0 edges within `range`; and those edges themselves, counted and kept by the first call and fetched by the second, as
 // hnswdev_exact_range / hnswdev_exact_range_results do it.  Exclusive: they use the scan's query buffer and bring the mirror up to date.

@@ -2162,6 +2162,34 @@ int HnswIndex::duplicate_groups(float range, const uint32_t *allow_bits, long lo
     return 0;
 }
 
+// The density clusters: duplicate_groups' members; labels (where asked for) and counts come back from the device as they are.
+int HnswIndex::density_clusters(float range, int min_samples, const uint32_t *allow_bits, long long nbits, int *out_labels, int *out_counts, long long cap,
+                                uint64_t *out_info, std::string &err)
+{
+    for (int i = 0; i < 8; ++i) out_info[i] = 0;
+    if (failed(err)) return -1;
+    if (min_samples < 1) {
+        err = "System.ArgumentException: hnsw_mi355x_density_clusters: min_samples = " + std::to_string(min_samples) + " is below 1";
+        return -1;
+    }
+    const long long length_now = graph_.length;
+    if (cap < length_now) {
+        err = "System.ArgumentException: hnsw_mi355x_density_clusters: cap = " + std::to_string(cap) + " is below the index's length of " + std::to_string(length_now);
+        return -1;
+    }
+    if (length_now > 0 && !out_counts) { err = "System.ArgumentNullException: hnsw_mi355x_density_clusters: out_counts"; return -1; }
+    if (length_now <= 0) return 0;
+    std::vector<uint32_t> live;
+    const long long length = exact_candidates(allow_bits, nbits, live);
+    for (long long v = 0; v < length; ++v) {
+        out_counts[v] = -1;
+        if (out_labels) out_labels[v] = -1;
+    }
+    if (graph_.count <= 0) return 0; // every slot is vacant: no member, and nothing needs the device
+    if (!dev_->exact_range_density(length, range, min_samples, allow_bits, nbits, out_labels, out_counts, out_info)) { err = get_dev_error(); return -1; }
+    return 0;
+}
+
 // The duplicate groups over the graph's edges: duplicate_groups' members and labels; what joins two members is a
 // layer-0 edge of the mirror within the range.
 int HnswIndex::graph_duplicate_groups(float range, const uint32_t *allow_bits, long long nbits, int *out_labels, long long cap, uint64_t *out_info, std::string &err)

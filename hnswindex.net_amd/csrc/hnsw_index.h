@@ -99,6 +99,10 @@ public:
     // hnsw_mi355x_duplicate_groups: the single-linkage groups of the live, allowed ids (Device::exact_range_groups);
     // out_labels[0, length), cap >= length.
     int duplicate_groups(float range, const uint32_t *allow_bits, long long nbits, int *out_labels, long long cap, uint64_t *out_info, std::string &err);
+    // hnsw_mi355x_density_clusters: DBSCAN over duplicate_groups' members and within pairs (Device::exact_range_density);
+    // out_counts[0, length) and, where given, out_labels[0, length), cap >= length; out_labels == nullptr: the neighbour counts alone.
+    int density_clusters(float range, int min_samples, const uint32_t *allow_bits, long long nbits, int *out_labels, int *out_counts, long long cap,
+                         uint64_t *out_info, std::string &err);
     // hnsw_mi355x_graph_duplicate_groups / hnsw_mi355x_near_edges: duplicate_groups' members, joined along the
     // within-edges of layer 0 of the graph mirror (Device::graph_edge_groups / graph_near_edges), which is brought up to date first
     // (sync_graph) as for get_info.  On the primary context; liveness and allow_bits go down as one bitset.  out_labels[0, length),

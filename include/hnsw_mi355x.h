@@ -486,6 +486,24 @@ int hnsw_mi355x_exact_range_query_by_id(void *handle, const int *ids, int count,
  * whose sink is a union-find on the device: no list is built, sorted or copied.  Fewer than two members launch nothing.  NULL
  * handle: 0, out_info zeroed.  NULL out_info, or NULL out_labels with length > 0: -1. */
 int hnsw_mi355x_duplicate_groups(void *handle, float range, const uint32_t *allow_bits, long long nbits, int *out_labels, long long cap, uint64_t out_info[4]);
+/* hnsw_mi355x_density_clusters: DBSCAN over the members and the pair rule of hnsw_mi355x_duplicate_groups, which is
+ * this call at min_samples = 1.  Members a < b are WITHIN when the distance with the stored row of a as the query and row b as the
+ * candidate is <= range (the float compare: a NaN distance or a NaN range admits nothing).
+ *   out_counts[v], v < length: the within pairs that hold v -- its neighbours; -1 where v is no member.
+ *   CORE: a member with out_counts[v] + 1 >= min_samples (the item counts itself).  min_samples < 1: -1 with a message.
+ *   CLUSTERS: the connected components of the core members under the within pairs whose two ends are both core; a cluster's label
+ *   is its smallest core id.
+ *   BORDER: a member that is not core and has a core within-neighbour; it takes the label of the one with the smallest
+ *   (distance, id) -- the pair's own distance, -0 equal to +0 -- so the result is unique, where textbook DBSCAN depends on the
+ *   order of its visits.
+ *   NOISE: every other member; its label is -1, as is every non-member's (out_counts tells the two apart).
+ * out_info[0] members m, [1] clusters, [2] core, [3] border, [4] noise, [5] pairs a < b within the range, [6] pairs measured --
+ * m (m - 1) / 2 per scan --, [7] scans: 0 with fewer than two members (nothing is launched), else 1, or 2 where the pairs found did
+ * not fit the device's pair arena and the scan ran once more.  out_labels == NULL: the counts alone -- one scan, and the slots that
+ * need labels ([1] .. [4]) are 0.  cap: the entries of out_counts, and of out_labels where given; cap < length is -1 with a message.
+ * NULL handle: 0, out_info zeroed.  NULL out_info, or NULL out_counts with length > 0: -1. */
+int hnsw_mi355x_density_clusters(void *handle, float range, int min_samples, const uint32_t *allow_bits, long long nbits, int *out_labels, int *out_counts,
+                                 long long cap, uint64_t out_info[8]);
 /* NEAR-DUPLICATES OVER THE GRAPH'S EDGES: the question of the two calls above asked of layer 0 of the index's graph
  * instead of every pair -- n x (at most 2 MaxEdges) distances instead of m (m - 1) / 2.  The MEMBERS are those of
  * hnsw_mi355x_duplicate_groups.  An EDGE is a pair (i, j): i a member, j in i's layer-0 list, j a member; it is directed (j listing i
@@ -917,6 +935,11 @@ int hnswdev_exact_range_by_id(void *ctx, const int *ids, int nq, long long n_row
  * pending is touched. */
 int hnswdev_exact_range_groups(void *ctx, long long n_rows, float range, const uint32_t *allow_bits, long long nbits, int *out_labels,
                                uint64_t out_info[4]);
+/* The scans behind hnsw_mi355x_density_clusters: the members are the uploaded rows [0, n_rows) that allow_bits allows, out_labels
+ * (NULL: the counts alone) and out_counts have min(n_rows, uploaded rows) entries, out_info as there.  min_samples < 1: -1 with a
+ * message.  Neither the resident set nor what hnswdev_exact_range_results has pending is touched. */
+int hnswdev_exact_range_density(void *ctx, long long n_rows, float range, int min_samples, const uint32_t *allow_bits, long long nbits, int *out_labels,
+                                int *out_counts, uint64_t out_info[8]);
 /* The calls behind hnsw_mi355x_graph_duplicate_groups / hnsw_mi355x_near_edges, on the context's own rows and the graph it was given
  * (hnswdev_graph_begin .. _commit): the members are the uploaded rows [0, n_rows) that allow_bits allows and that are nodes of the
  * graph; out_labels has min(n_rows, uploaded rows) entries, out_info as there.  hnswdev_graph_near_edges counts and keeps,
