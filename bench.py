@@ -12,9 +12,11 @@ a drop-in caller sees).  The same step with the query set already resident in HB
 One JSON line on rank 0.  `--sharding native`: ONE process, the library itself shards the call over N GPUs.
 
 The Add half of the metric (all on the same 1M index):
-  add_per_sec            the build: hnsw_add of the whole set under the library's DEFAULT schedule -- snapshot batches capped at the
-                         host's hardware threads T, an interleaving the reference's Parallel.For (HNSWIndex.cs:70-78) can produce on
-                         a host with >= T threads
+  add_per_sec            the build: hnsw_add of the whole set in snapshot batches capped at --insert-batch, 256 unless told otherwise -- an
+                         interleaving the reference's Parallel.For (HNSWIndex.cs:70-78) can produce on a host with >= 256 threads.
+                         --insert-batch 0 builds under the library's DEFAULT schedule, capped at the host's hardware threads T; that was
+                         the default here while T was 256, but under T = 16 the build is 62 500 dependent rounds of one traversal's
+                         latency each, 81 s, and a plain run has to set up in well under a minute
   add_modes.sequential   B = 1: the reference's HNSWIndex.Add(item), one call per item
   add_modes.exact_window the SAME graph as B = 1 (the only Add whose graph the reference defines) through
                          speculative windows with read-set validation, one call for the whole sample
@@ -66,7 +68,8 @@ def parse():
     p.add_argument("--max-edges", type=int, default=16)
     p.add_argument("--ef-construction", type=int, default=200)
     p.add_argument("--ef-search", type=int, default=128)
-    p.add_argument("--insert-batch", type=int, default=0, help="cap of Add's snapshot batches for the build (a batch is also <= linked/16): 0 = the library's default, "
+    p.add_argument("--insert-batch", type=int, default=256, help="cap of Add's snapshot batches for the build (a batch is also <= linked/16): 256 = the host threads of the "
+                   "committed figures, a 9-s build on any host; 0 = the library's default, "
                    "the host's hardware threads -- the items a Parallel.For on this host holds in flight; 65536 = the opt-in large snapshots of rounds 1-4")
     p.add_argument("--slots", type=int, default=0, help="lock-step search slots (0 = library default)")
     p.add_argument("--threads", type=int, default=0, help="host threads of the driver (0 = library default)")
@@ -861,9 +864,10 @@ def main():
         "add_per_sec": round(a.n / build_s, 1), "build_seconds": round(build_s, 3),
         "add_schedule": {"cap": ix.insert_batch_cap, "default": a.insert_batch == 0, "host_hardware_threads": hnswindex.net_amd.host_parallelism(), "cgroup_cpu_quota": cgroup_quota(),
                          "inside_reference_outcome_set_for_hosts_with_threads_at_least": ix.insert_batch_cap},
-        "add_schedule_in_reference_outcome_set": True, "add_schedule_reference_defined": False,
+        "add_schedule_in_reference_outcome_set": bool(ix.insert_batch_cap <= hnswindex.net_amd.host_parallelism()),   # on THIS host (a larger cap: on a host with that many threads)
+        "add_schedule_reference_defined": False,
         "add_per_sec_reference_graph": (add_modes or {}).get("exact_window", {}).get("adds_per_sec"),
-        "add_note": "add_per_sec: hnsw_add of the whole set in one call under the cap named in add_schedule -- by default the host's hardware threads T: snapshot batches of "
+        "add_note": "add_per_sec: hnsw_add of the whole set in one call under the cap T named in add_schedule (--insert-batch; 0 = the library's default, the host's hardware threads): snapshot batches of "
                     "at most T items (T searches on one snapshot, then T links in id order) are an interleaving HNSWIndex.Add(List)'s Parallel.For (HNSWIndex.cs:70-78) can produce "
                     "on a host with >= T threads, so an unchanged caller gets a graph from the reference's outcome set; checked bit for bit against the CPU restatement of the same "
                     "schedule (add_modes.bounded, every rung). The reference DEFINES a graph only for HNSWIndex.Add(item) one item after the other (HNSWIndex.cs:55-65): "

@@ -38,16 +38,20 @@ def _tight(n, dim, seed):
 
 class Graph:
     """One graph (M = 16, default schedule) built on the device with the prefilter off, its hash the oracle's; at(ef) is that graph in
-    an index and an oracle whose MinNN is ef (MinNN is fixed when an index is made), want(ef, k) the oracle's answer, computed once."""
+    an index and an oracle whose MinNN is ef (MinNN is fixed when an index is made), want(ef, k) the oracle's answer, computed once.
+    cap: the cap of Add's snapshot batches -- None is the default schedule, whose cap is the host's hardware threads, so the graph is
+    another one on another host; a test that asserts something of ONE graph names the cap."""
 
-    def __init__(self, Index, kind, dim):
+    def __init__(self, Index, kind, dim, cap=None):
         self.Index, self.dim = Index, dim
         self.x = uniform(N, dim, 40 + dim) if kind == "uniform" else _tight(N, dim, 41)
         self.q = uniform(NQ, dim, 50 + dim) if kind == "uniform" else _tight(NQ, dim, 51)
         ix = self._index(5)
+        if cap is not None:
+            ix.set_insert_batch(cap)
         ix.add(self.x)
         ref = oracle.OracleIndex(dim, "sq_euclid", max_edges=M, collection_size=N)
-        ref.add_batched(self.x, default_cap(), threads=8)
+        ref.add_batched(self.x, default_cap() if cap is None else cap, threads=8)
         assert ix.graph_hash() == ref.graph_hash()
         self.hash, self.lv, self.entry = ix.graph_hash(), ix.levels(), ix.entry_point
         self.layers = [ix.export_edges(L, 2 * M + 2 if L == 0 else M + 2) for L in range(int(self.lv.max()) + 1)]

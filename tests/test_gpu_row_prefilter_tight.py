@@ -218,13 +218,16 @@ def test_e_grows_with_a_partial_repack_and_starts_over_with_a_full_one(Index, mo
 # ---------------------------------------------------------------- more jobs than waves; the second lane
 @pytest.fixture(scope="module")
 def uniform_graph(Index):
-    """tests/test_gpu_row_prefilter.py's 6000 x 100 uniform graph (M 16), built once with the prefilter off."""
+    """tests/test_gpu_row_prefilter.py's 6000 x 100 uniform graph (M 16), built once with the prefilter off -- in snapshot batches of
+    at most 256 items, whatever the host: the test below requires that none of its 8192 queries meets equal distances where the
+    heap layout shows (search_repeats == 0), and that is a fact about ONE graph.  With the default cap (the host's hardware
+    threads) a 16-thread host builds another graph, on which one of the queries does meet them."""
     import os
     from test_gpu_row_prefilter import Graph
     old = os.environ.get("HNSW_MI355X_DIAG")
     os.environ["HNSW_MI355X_DIAG"] = ((old + ",") if old else "") + "row_prefilter=0"
     try:
-        return Graph(Index, "uniform", 100)
+        return Graph(Index, "uniform", 100, cap=256)
     finally:
         if old is None:
             del os.environ["HNSW_MI355X_DIAG"]
