@@ -770,13 +770,13 @@ private:
     const RowCollapse *row_collapse_ = nullptr;
     bool collapse_and_fetch(int *d_ids, float *d_d, int nj, size_t width, int *h_ids, float *h_d);
     bool exact_copy_out(void *dst, const void *src, size_t bytes);
-    ExactStart exact_scan_begin(const char *who, const float *queries, int nq, long long n_rows, const uint32_t *allow_bits, long long nbits, ExactScanInput *in);
+    ExactStart exact_scan_begin(const char *who, const float *queries, int nq, long long n_rows, const uint32_t *allow_bits, long long nbits, ExactScanInput *in,
+                                const int *by_id = nullptr);
     bool exact_scan_args(const float *d_q, const double *d_qsn, long long off, int nr, int qt, int piece, ExactScanArgs *a);
     template <class Enqueue, class Fetch> // the one timed, counted launch of the flat scan: every exact_* statistic is written there
     bool exact_timed_scan(unsigned long long *h_ev, Enqueue &&enqueue, Fetch &&fetch);
     bool exact_range_call(int nq, int *out_counts, const std::function<bool()> &body);
-    // the rounds of exact_range and exact_range_by_id: d_self nullptr, or the nq ids on the device whose rows the queries are
-    bool exact_range_rounds(const char *who, const ExactScanInput &in, int nq, float range, const int *d_self, int *out_counts);
+    bool exact_range_rounds(const char *who, const ExactScanInput &in, int nq, float range, int *out_counts); // of exact_range and exact_range_by_id
     DevBuf<int> x_uparent_;               // exact_range_groups: the union-find's parent[], then the labels behind it
     DevBuf<unsigned long long> x_upairs_; // ... pairs within the range, counted on the device
     // what exact_range_groups and exact_range_density share (device_backend.hip): the members listed, the plan of the triangle's
@@ -785,6 +785,8 @@ private:
     bool exact_triangle_ready(const char *who, ExactTriangle *t);
     template <class Launch> // launch(args, tiles, stream) -> hipError_t: the scan with the call's sink, its queries' ids in x_self_
     bool exact_triangle_scan(const ExactTriangle &t, Launch &&launch, unsigned long long *measured);
+    // the ending of exact_range_groups and graph_edges_run: parent[] -> labels, out; the groups and n_ctr counter words into out_info[1 ..]
+    bool exact_union_finish(long long n, const std::vector<int> &members, const unsigned long long *d_ctr, int n_ctr, int *out_labels, uint64_t *out_info);
     DevBuf<int> x_dcounts_;               // exact_range_density: within pairs per id, -1 off the members
     DevBuf<unsigned long long> x_dattach_; // ... per id: the smallest (distance, core id) key offered to a member that is not core
     DevBuf<ExactDensityPair> x_darena_;   // ... phase A's within pairs: 2^24 records (256 MiB) unless `density_pair_cap` says otherwise

@@ -3256,24 +3256,45 @@ bool Device::exact_id_list(const uint32_t *allow_bits, long long n_allow, long l
 enum class ExactStart { failed, nothing, ready };
 
 // What an ungrouped flat scan measures: the queries on the device (pitch_ words each; d_qsn their cosine norms or nullptr) and the
-// m entries of the id list `ids` (nullptr: the identity).
+// m entries of the id list `ids` (nullptr: the identity).  self: nullptr, or the nq ids on the device whose stored rows the
+// queries are (the Self sinks' `self`).
 struct ExactScanInput {
     const float *d_q;
     const double *d_qsn;
     const int *ids;
     long long m;
+    const int *self;
 };
 
 // The candidates and queries of an ungrouped flat scan, after the caller's own argument checks: the rows that exist and are
 // allowed (none: nothing to measure), then the queries, the device and the id list as exact_queries and exact_id_list leave them.
-ExactStart Device::exact_scan_begin(const char *who, const float *queries, int nq, long long n_rows, const uint32_t *allow_bits, long long nbits, ExactScanInput *in)
+// by_id: nullptr, or nq uploaded ids (by_id_rows_error) -- the queries are then their stored rows, gathered into the scan's own
+// buffer (the resident set stays what it was; `queries` is not read), their ids left in x_self_, and the call is counted in
+// by_id_info: self_skipped are the queries whose own id is a candidate, one pair each.
+ExactStart Device::exact_scan_begin(const char *who, const float *queries, int nq, long long n_rows, const uint32_t *allow_bits, long long nbits, ExactScanInput *in,
+                                    const int *by_id)
 {
     if (!allow_bits) nbits = 0; // no filter: nbits means nothing, whatever the caller left in it
     // rows that exist: a row beyond what was uploaded is never dereferenced, whatever n_rows and the bitset say
     const long long n = std::min(n_rows, n_rows_hw_), n_allow = allow_bits ? std::min(nbits, n) : n;
     if (n_allow <= 0 || (allow_bits && !allows_any(allow_bits, nbits, n))) return ExactStart::nothing;
-    if (!exact_queries(who, queries, nq, &in->d_q, &in->d_qsn) || !bind() || !exact_id_list(allow_bits, n_allow, &in->m)) return ExactStart::failed;
+    in->self = nullptr;
+    if (by_id) {
+        const size_t cap = (size_t)std::max(nq, 1024);
+        if (!bind() || !x_queries_.grow((size_t)nq * pitch_, cap * pitch_) || (metric_ == M_COS && !x_q_sn_.grow((size_t)nq, cap))) return ExactStart::failed;
+        if (!gather_queries(by_id, nq, x_self_, x_queries_, x_q_sn_)) return ExactStart::failed;
+        in->d_q = x_queries_; in->d_qsn = metric_ == M_COS ? x_q_sn_.get() : nullptr; in->self = x_self_;
+    } else if (!exact_queries(who, queries, nq, &in->d_q, &in->d_qsn) || !bind()) return ExactStart::failed;
+    if (!exact_id_list(allow_bits, n_allow, &in->m)) return ExactStart::failed;
     in->ids = allow_bits ? x_ids_.get() : nullptr;
+    if (by_id) {
+        using Slot = slot::by_id_info;
+        uint64_t *ctr = counter_block(Slot::kBlock);
+        const AllowBits allowed{allow_bits, n_allow};
+        ctr[Slot::calls] += 1;
+        ctr[Slot::scanned] += (uint64_t)nq;
+        for (int i = 0; i < nq; ++i) ctr[Slot::self_skipped] += (uint64_t)(by_id[i] < n_allow && allowed.has(by_id[i]));
+    }
     return ExactStart::ready;
 }
 
@@ -3289,6 +3310,15 @@ bool Device::exact_scan_args(const float *d_q, const double *d_qsn, long long of
     a->q_sn = d_qsn ? d_qsn + off : nullptr;
     a->dim = pitch_; a->nq = nr; a->qtile = qt; a->piece = piece; a->evals = x_evals_;
     return true;
+}
+
+// exact_scan_launch (dk_exact.h) with the context's metric as its template argument
+template <class SINK>
+static hipError_t exact_scan_enqueue(int metric, const ExactScanArgs &a, const SINK &sink, unsigned n_blocks, size_t lds, hipStream_t st)
+{
+    hipError_t e = hipSuccess;
+    with_metric(metric, [&](auto mt) { e = exact_scan_launch<mt>(a, sink, n_blocks, lds, st); });
+    return e;
 }
 
 // One launch of the flat scan, timed and counted -- the only place the exact_* statistics are written.  x_evals_ is zeroed;
@@ -3364,17 +3394,14 @@ bool Device::exact_knn_rounds(const float *d_q, const double *d_qsn, int nq, con
         int *d_ids = x_out_;
         float *d_d = reinterpret_cast<float *>(x_out_.get() + (size_t)p.round * k);
         const auto enqueue = [&]() -> bool {
-            hipError_t e = hipSuccess;
             if (collapse) {
                 const ExactTopKCollapse sink{collapse->d_row_group, collapse->per_group, collapse->d_info};
-                with_metric(metric_, [&](auto mt) { e = exact_collapsed_scan_launch<mt>(a, sink, tiles, p.lds, st); });
-                HIP_OK(e);
+                HIP_OK(exact_scan_enqueue(metric_, a, sink, tiles, p.lds, st));
                 HIP_OK(exact_merge_collapsed_launch(x_lists_, p.n_chunks, k, nr, sink.row_group, sink.per_group, sink.info, d_ids, d_d, st));
                 return true;
             }
-            if (d_self) with_metric(metric_, [&](auto mt) { e = exact_self_scan_launch<mt>(a, ExactTopKSelf{d_self + off}, tiles, p.lds, st); });
-            else with_metric(metric_, [&](auto mt) { e = exact_scan_launch<mt>(a, tiles, p.lds, st); });
-            HIP_OK(e);
+            if (d_self) HIP_OK(exact_scan_enqueue(metric_, a, ExactTopKSelf{d_self + off}, tiles, p.lds, st));
+            else HIP_OK(exact_scan_enqueue(metric_, a, ExactTopK{}, tiles, p.lds, st));
             HIP_OK(exact_merge_launch(x_lists_, p.n_chunks, k, nr, d_ids, d_d, st));
             return true;
         };
@@ -3718,9 +3745,7 @@ bool Device::exact_knn_grouped_scan(const char *who, const float *queries, const
         ExactTopKGrouped sink;
         sink.items = reinterpret_cast<const ExactWorkItem *>(x_gwork_.get() + b_mi);
         const auto enqueue = [&]() -> bool {
-            hipError_t e = hipSuccess;
-            with_metric(metric_, [&](auto mt) { e = exact_grouped_scan_launch<mt>(a, sink, (unsigned)wi.size(), tp.lds, st); });
-            HIP_OK(e);
+            HIP_OK(exact_scan_enqueue(metric_, a, sink, (unsigned)wi.size(), tp.lds, st));
             HIP_OK(exact_merge_grouped_launch(x_lists_, reinterpret_cast<const ExactMergeItem *>(x_gwork_.get()), k, nr, d_ids, d_d, st));
             return true;
         };
@@ -4009,16 +4034,15 @@ bool Device::exact_range(const float *queries, int nq, long long n_rows, float r
         ExactScanInput in;
         const ExactStart s = exact_scan_begin("exact_range", queries, nq, n_rows, allow_bits, nbits, &in);
         if (s != ExactStart::ready) return s == ExactStart::nothing; // (nothing to measure: empty lists, no launch)
-        return exact_range_rounds("exact_range", in, nq, range, nullptr, out_counts);
+        return exact_range_rounds("exact_range", in, nq, range, out_counts);
     });
 }
 
 // The rounds of a range scan over the queries and the id list of `in`: pass A, the finish and pass B, the lists appended to the
-// call's results in query order and counted in exact_range_info.  d_self: nullptr, or the nq ids on the device whose stored rows
-// the queries are (exact_range_by_id) -- the sink is then ExactRangeSelf, and every launch gets the ids of ITS queries: a repeated
-// pass scans queries [q0, q0 + ns) of the call and reads d_self + q0, as it reads the queries from q0 on.  Runs inside
-// exact_range_call's body.
-bool Device::exact_range_rounds(const char *who, const ExactScanInput &in, int nq, float range, const int *d_self, int *out_counts)
+// call's results in query order and counted in exact_range_info.  Where in.self says whose stored rows the queries are
+// (exact_range_by_id) the sink is ExactRangeSelf, and every launch gets the ids of ITS queries: a repeated pass scans queries
+// [q0, q0 + ns) of the call and reads in.self + q0, as it reads the queries from q0 on.  Runs inside exact_range_call's body.
+bool Device::exact_range_rounds(const char *who, const ExactScanInput &in, int nq, float range, int *out_counts)
 {
     hipStream_t st = S(stream_);
     ExactPlan p = exact_plan(std::min(nq, 65536), in.m, 1, pitch_, num_cu_); // tile and chunks as for lists of one key: this sink keeps none
@@ -4049,12 +4073,8 @@ bool Device::exact_range_rounds(const char *who, const ExactScanInput &in, int n
         HIP_OK(hipMemcpyAsync(x_rseg_, h_seg, 8 * ((size_t)nr + 1), hipMemcpyHostToDevice, st));
         HIP_OK(hipMemsetAsync(x_rcnt_, 0, 4 * (size_t)nr, st));
         const auto enqueue = [&]() -> bool {
-            hipError_t e = hipSuccess;
-            if (d_self) {
-                const ExactRangeSelf own{range, sink.counts, sink.seg_off, sink.arena, d_self + q0};
-                with_metric(metric_, [&](auto mt) { e = exact_range_self_scan_launch<mt>(a, own, tiles, p.lds, st); });
-            } else with_metric(metric_, [&](auto mt) { e = exact_range_scan_launch<mt>(a, sink, tiles, p.lds, st); });
-            HIP_OK(e);
+            if (in.self) HIP_OK(exact_scan_enqueue(metric_, a, ExactRangeSelf{range, sink.counts, sink.seg_off, sink.arena, in.self + q0}, tiles, p.lds, st));
+            else HIP_OK(exact_scan_enqueue(metric_, a, sink, tiles, p.lds, st));
             return true;
         };
         const auto fetch = [&]() -> bool { HIP_OK(hipMemcpyAsync(h_cnt, x_rcnt_, 4 * (size_t)nr, hipMemcpyDeviceToHost, st)); return true; };
@@ -4215,9 +4235,7 @@ bool Device::exact_range_grouped_scan(const char *who, const float *queries, con
             HIP_OK(hipMemcpyAsync(x_gwork_, h_tab, b_wi + b_dest, hipMemcpyHostToDevice, st));
             HIP_OK(hipMemsetAsync(x_rcnt_, 0, b_cnt, st));
             const auto enqueue = [&]() -> bool {
-                hipError_t e = hipSuccess;
-                with_metric(metric_, [&](auto mt) { e = exact_range_grouped_scan_launch<mt>(a, sink, (unsigned)wi.size(), tp.lds, st); });
-                HIP_OK(e);
+                HIP_OK(exact_scan_enqueue(metric_, a, sink, (unsigned)wi.size(), tp.lds, st));
                 return true;
             };
             const auto fetch = [&]() -> bool { HIP_OK(hipMemcpyAsync(h_cnt, x_rcnt_, b_cnt, hipMemcpyDeviceToHost, st)); return true; };
@@ -4870,31 +4888,11 @@ bool Device::exact_knn_by_id(const int *ids, int nq, long long n_rows, int k, co
     if (!ids || !out_ids || !out_d || k < 1 || n_rows < 0 || (allow_bits && nbits < 0)) { set_dev_error("exact_knn_by_id: bad argument"); return false; }
     if (k > kExactMaxK) { set_dev_error("exact_knn_by_id: k = " + std::to_string(k) + " is above the limit of " + std::to_string(kExactMaxK)); return false; }
     if (const std::string why = by_id_rows_error("exact_knn_by_id", ids, nq, n_rows_hw_); !why.empty()) { set_dev_error(why); return false; }
-    if (!allow_bits) nbits = 0;
-    const long long n = std::min(n_rows, n_rows_hw_), n_allow = allow_bits ? std::min(nbits, n) : n;
-    if (n_allow <= 0 || (allow_bits && !allows_any(allow_bits, nbits, n))) { // no candidate: padding, no launch
-        pad_results(out_ids, out_d, (size_t)nq * (size_t)k);
-        return true;
-    }
-    if (!bind()) return false;
-    const size_t cap = (size_t)std::max(nq, 1024);
-    if (!x_queries_.grow((size_t)nq * pitch_, cap * pitch_) || (metric_ == M_COS && !x_q_sn_.grow((size_t)nq, cap))) return false;
-    const double *d_qsn = metric_ == M_COS ? x_q_sn_.get() : nullptr;
-    if (!gather_queries(ids, nq, x_self_, x_queries_, x_q_sn_)) return false;
-    long long m = 0;
-    if (!exact_id_list(allow_bits, n_allow, &m)) return false;
-    uint64_t skipped = 0; // the queries whose own id is a candidate: one pair each
-    for (int i = 0; i < nq; ++i) {
-        const long long id = ids[i];
-        skipped += (uint64_t)(id < n_allow && (!allow_bits || ((allow_bits[id >> 5] >> (id & 31)) & 1u)));
-    }
-    if (!exact_knn_rounds(x_queries_, d_qsn, nq, allow_bits ? x_ids_.get() : nullptr, m, k, out_ids, out_d, nullptr, x_self_)) return false;
-    using Slot = slot::by_id_info;
-    uint64_t *ctr = counter_block(Slot::kBlock);
-    ctr[Slot::calls] += 1;
-    ctr[Slot::scanned] += (uint64_t)nq;
-    ctr[Slot::self_skipped] += skipped;
-    return true;
+    ExactScanInput in;
+    const ExactStart s = exact_scan_begin("exact_knn_by_id", nullptr, nq, n_rows, allow_bits, nbits, &in, ids);
+    if (s == ExactStart::nothing) pad_results(out_ids, out_d, (size_t)nq * (size_t)k); // padding, no launch
+    if (s != ExactStart::ready) return s == ExactStart::nothing;
+    return exact_knn_rounds(in.d_q, in.d_qsn, nq, in.ids, in.m, k, out_ids, out_d, nullptr, in.self);
 }
 
 // ---- near-duplicates of stored rows ---------------------------------------------------------------------------------
@@ -4908,29 +4906,10 @@ bool Device::exact_range_by_id(const int *ids, int nq, long long n_rows, float r
         if (!ids || !out_counts || n_rows < 0 || (allow_bits && nbits < 0)) { set_dev_error(std::string(who) + ": bad argument"); return false; }
         for (int i = 0; i < nq; ++i) out_counts[i] = 0;
         if (const std::string why = by_id_rows_error(who, ids, nq, n_rows_hw_); !why.empty()) { set_dev_error(why); return false; }
-        if (!allow_bits) nbits = 0;
-        const long long n = std::min(n_rows, n_rows_hw_), n_allow = allow_bits ? std::min(nbits, n) : n;
-        if (n_allow <= 0 || (allow_bits && !allows_any(allow_bits, nbits, n))) return true; // no candidate: empty lists, no launch
-        if (!bind()) return false;
-        const size_t cap = (size_t)std::max(nq, 1024);
-        if (!x_queries_.grow((size_t)nq * pitch_, cap * pitch_) || (metric_ == M_COS && !x_q_sn_.grow((size_t)nq, cap))) return false;
-        if (!gather_queries(ids, nq, x_self_, x_queries_, x_q_sn_)) return false;
         ExactScanInput in;
-        in.d_q = x_queries_; in.d_qsn = metric_ == M_COS ? x_q_sn_.get() : nullptr;
-        if (!exact_id_list(allow_bits, n_allow, &in.m)) return false;
-        in.ids = allow_bits ? x_ids_.get() : nullptr;
-        uint64_t skipped = 0; // the queries whose own id is a candidate: one pair each
-        for (int i = 0; i < nq; ++i) {
-            const long long id = ids[i];
-            skipped += (uint64_t)(id < n_allow && (!allow_bits || ((allow_bits[id >> 5] >> (id & 31)) & 1u)));
-        }
-        if (!exact_range_rounds(who, in, nq, range, x_self_, out_counts)) return false;
-        using Slot = slot::by_id_info;
-        uint64_t *ctr = counter_block(Slot::kBlock);
-        ctr[Slot::calls] += 1;
-        ctr[Slot::scanned] += (uint64_t)nq;
-        ctr[Slot::self_skipped] += skipped;
-        return true;
+        const ExactStart s = exact_scan_begin(who, nullptr, nq, n_rows, allow_bits, nbits, &in, ids);
+        if (s != ExactStart::ready) return s == ExactStart::nothing; // nothing: empty lists, no launch
+        return exact_range_rounds(who, in, nq, range, out_counts);
     });
 }
 
@@ -4939,6 +4918,29 @@ bool Device::exact_range_by_id(const int *ids, int nq, long long n_rows, float r
 // its sink, counted and timed like any (exact_timed_scan: exact_evals are the pairs measured); then one kernel turns parent[] into
 // labels.  The members are listed on the host -- the bitset is the host's -- so that the rounds' ids need no copy back.
 constexpr long long kExactUnionChunk = 2048; // rows of a chunk of the groups' scan unless `exact_chunk` forces them
+
+// The members of a stored-row call: the ids below `bound` that allow_bits allows (nullptr: all of them), ascending; bits: nullptr,
+// or where the same set goes as a bitset of `bound` bits.
+static std::vector<int> list_members(const uint32_t *allow_bits, long long bound, std::vector<unsigned> *bits = nullptr)
+{
+    const AllowBits allowed{allow_bits, bound};
+    std::vector<int> members;
+    if (bits) bits->assign((size_t)((std::max<long long>(bound, 0) + 31) / 32), 0u);
+    for (long long id = 0; id < bound; ++id)
+        if (allowed.has((int)id)) {
+            members.push_back((int)id);
+            if (bits) (*bits)[(size_t)(id >> 5)] |= 1u << (id & 31);
+        }
+    return members;
+}
+
+// labels[0, n) on the host before any launch: -1 everywhere and, where `own`, a member its own id -- what fewer than two members
+// leave; the device's labels replace it otherwise.
+static void init_member_labels(int *labels, long long n, const std::vector<int> &members, bool own)
+{
+    for (long long v = 0; v < n; ++v) labels[v] = -1;
+    if (own) for (const int v : members) labels[v] = v;
+}
 
 // A scan over the pairs a < b of the members (exact_range_groups, exact_range_density): who they are, and how the triangle is cut.
 struct ExactTriangle {
@@ -4954,9 +4956,7 @@ bool Device::exact_triangle_begin(const char *who, long long n_rows, const uint3
     if (n_rows < 0 || (allow_bits && nbits < 0)) { set_dev_error(std::string(who) + ": bad argument"); return false; }
     if (!allow_bits) nbits = 0;
     t->n = std::min(n_rows, n_rows_hw_);
-    const long long n_allow = allow_bits ? std::min(nbits, t->n) : t->n;
-    for (long long id = 0; id < n_allow; ++id)
-        if (!allow_bits || ((allow_bits[id >> 5] >> (id & 31)) & 1u)) t->members.push_back((int)id);
+    t->members = list_members(allow_bits, allow_bits ? std::min(nbits, t->n) : t->n);
     t->m = (long long)t->members.size();
     return true;
 }
@@ -5023,8 +5023,7 @@ bool Device::exact_range_groups(long long n_rows, float range, const uint32_t *a
     const long long n = t.n, m = t.m;
     const std::vector<int> &members = t.members;
     if (n > 0 && !out_labels) { set_dev_error(std::string(who) + ": bad argument"); return false; }
-    for (long long v = 0; v < n; ++v) out_labels[v] = -1;
-    for (const int v : members) out_labels[v] = v; // (what fewer than two members leave; the device's labels replace it otherwise)
+    init_member_labels(out_labels, n, members, true);
     out_info[0] = (unsigned long long)m;
     out_info[1] = (unsigned long long)m;
     if (m < 2) return true; // nothing to measure: no launch
@@ -5037,23 +5036,26 @@ bool Device::exact_range_groups(long long n_rows, float range, const uint32_t *a
     unsigned long long measured = 0;
     const auto launch = [&](const ExactScanArgs &a, unsigned tiles, hipStream_t s) {
         const ExactRangeUnion sink{range, x_uparent_, x_self_, x_upairs_}; // (x_self_ as the round's gather left it)
-        hipError_t e = hipSuccess;
-        with_metric(metric_, [&](auto mt) { e = exact_range_union_scan_launch<mt>(a, sink, tiles, t.p.lds, s); });
-        return e;
+        return exact_scan_enqueue(metric_, a, sink, tiles, t.p.lds, s);
     };
     if (!exact_triangle_scan(t, launch, &measured)) return false;
-    int *d_labels = x_uparent_.get() + n;
-    HIP_OK(exact_union_labels_launch(x_uparent_, n, d_labels, st));
-    if (!exact_copy_out(out_labels, d_labels, 4 * (size_t)n)) return false;
-    unsigned long long *h = static_cast<unsigned long long *>(pinned_stage(8));
-    if (!h) return false;
-    HIP_OK(hipMemcpyAsync(h, x_upairs_, 8, hipMemcpyDeviceToHost, st));
-    HIP_OK(hipStreamSynchronize(st));
-    unsigned long long groups = 0;
-    for (const int v : members) groups += (unsigned long long)(out_labels[v] == v);
-    out_info[1] = groups;
-    out_info[2] = *h;
+    if (!exact_union_finish(n, members, x_upairs_, 1, out_labels, out_info)) return false;
     out_info[3] = measured;
+    return true;
+}
+
+// How a union-find call ends (exact_range_groups, graph_edges_run): one kernel turns parent[] into the labels behind it in x_uparent_,
+// and they come out; then the n_ctr 64-bit words of d_ctr come out into out_info[2, 2 + n_ctr), and out_info[1] is the groups: the
+// members that are their own root.
+bool Device::exact_union_finish(long long n, const std::vector<int> &members, const unsigned long long *d_ctr, int n_ctr, int *out_labels, uint64_t *out_info)
+{
+    int *d_labels = x_uparent_.get() + n;
+    uint64_t ctr[2], groups = 0; // (n_ctr <= 2)
+    HIP_OK(exact_union_labels_launch(x_uparent_, n, d_labels, S(stream_)));
+    if (!exact_copy_out(out_labels, d_labels, 4 * (size_t)n) || !exact_copy_out(ctr, d_ctr, 8 * (size_t)n_ctr)) return false;
+    for (const int v : members) groups += (uint64_t)(out_labels[v] == v);
+    out_info[1] = groups;
+    for (int i = 0; i < n_ctr; ++i) out_info[2 + i] = ctr[i];
     return true;
 }
 
@@ -5077,10 +5079,7 @@ bool Device::exact_range_density(long long n_rows, float range, int min_samples,
     if (n > 0 && !out_counts) { set_dev_error(std::string(who) + ": bad argument"); return false; }
     for (long long v = 0; v < n; ++v) out_counts[v] = -1;
     for (const int v : members) out_counts[v] = 0;
-    if (out_labels) {
-        for (long long v = 0; v < n; ++v) out_labels[v] = -1;
-        if (min_samples == 1) for (const int v : members) out_labels[v] = v; // (what fewer than two members leave: a lone member is core when it alone is enough)
-    }
+    if (out_labels) init_member_labels(out_labels, n, members, min_samples == 1); // (a lone member is core when it alone is enough)
     // clusters, core, border and noise members from the labels and counts as they stand on the host
     const auto count_kinds = [&]() {
         unsigned long long clusters = 0, core = 0, border = 0;
@@ -5113,26 +5112,18 @@ bool Device::exact_range_density(long long n_rows, float range, int min_samples,
     unsigned long long measured = 0, scans = 1;
     const auto phase_a = [&](const ExactScanArgs &a, unsigned tiles, hipStream_t s) {
         const ExactRangeDensity sink{range, x_self_, x_dcounts_, x_darena_, cap, x_upairs_}; // (x_self_ as the round's gather left it)
-        hipError_t e = hipSuccess;
-        with_metric(metric_, [&](auto mt) { e = exact_range_density_scan_launch<mt>(a, sink, tiles, lds_a, s); });
-        return e;
+        return exact_scan_enqueue(metric_, a, sink, tiles, lds_a, s);
     };
     if (!exact_triangle_scan(t, phase_a, &measured)) return false;
-    unsigned long long *h = static_cast<unsigned long long *>(pinned_stage(8));
-    if (!h) return false;
-    HIP_OK(hipMemcpyAsync(h, x_upairs_, 8, hipMemcpyDeviceToHost, st));
-    HIP_OK(hipStreamSynchronize(st));
-    const unsigned long long pairs_within = *h;
-    if (!exact_copy_out(out_counts, x_dcounts_, 4 * (size_t)n)) return false;
+    unsigned long long pairs_within = 0;
+    if (!exact_copy_out(&pairs_within, x_upairs_, 8) || !exact_copy_out(out_counts, x_dcounts_, 4 * (size_t)n)) return false;
     if (out_labels) {
         if (pairs_within <= cap) {
             HIP_OK(density_pairs_launch(x_darena_, pairs_within, x_dcounts_, min_samples, x_uparent_, x_dattach_, st));
         } else { // the arena dropped records: the triangle once more, joined straight from the distances
             const auto phase_b = [&](const ExactScanArgs &a, unsigned tiles, hipStream_t s) {
                 const ExactRangeDensityJoin sink{range, x_self_, x_dcounts_, min_samples, x_uparent_, x_dattach_};
-                hipError_t e = hipSuccess;
-                with_metric(metric_, [&](auto mt) { e = exact_range_density_join_scan_launch<mt>(a, sink, tiles, t.p.lds, s); });
-                return e;
+                return exact_scan_enqueue(metric_, a, sink, tiles, t.p.lds, s);
             };
             if (!exact_triangle_scan(t, phase_b, &measured)) return false;
             scans = 2;
@@ -5163,17 +5154,11 @@ bool Device::graph_edges_run(const char *who, long long n_rows, float range, con
     if (n > 0 && !keep_list && !out_labels) { set_dev_error(std::string(who) + ": bad argument"); return false; }
     if (n > 0 && (g_n_ <= 0 || !g_adj0_)) { set_dev_error(std::string(who) + ": no graph committed"); return false; }
     const long long n_mem = std::min<long long>(n_allow, g_n_); // a member is a row, allowed, and a node of the graph
-    std::vector<int> members;
-    std::vector<unsigned> bits((size_t)((std::max<long long>(n_mem, 0) + 31) / 32), 0u);
-    for (long long id = 0; id < n_mem; ++id)
-        if (!allow_bits || ((allow_bits[id >> 5] >> (id & 31)) & 1u)) {
-            members.push_back((int)id);
-            bits[(size_t)(id >> 5)] |= 1u << (id & 31);
-        }
+    std::vector<unsigned> bits;
+    const std::vector<int> members = list_members(allow_bits, n_mem, &bits);
     const long long m = (long long)members.size();
     if (!keep_list) {
-        for (long long v = 0; v < n; ++v) out_labels[v] = -1;
-        for (const int v : members) out_labels[v] = v; // (what fewer than two members leave; the device's labels replace it otherwise)
+        init_member_labels(out_labels, n, members, true);
         out_info[0] = (unsigned long long)m;
         out_info[1] = (unsigned long long)m;
     }
@@ -5246,18 +5231,7 @@ bool Device::graph_edges_run(const char *who, long long n_rows, float range, con
         HIP_OK(hipStreamSynchronize(st));
         return true;
     }
-    int *d_labels = x_uparent_.get() + n;
-    HIP_OK(exact_union_labels_launch(x_uparent_, n, d_labels, st));
-    if (!exact_copy_out(out_labels, d_labels, 4 * (size_t)n)) return false;
-    unsigned long long *h = static_cast<unsigned long long *>(pinned_stage(16));
-    if (!h) return false;
-    HIP_OK(hipMemcpyAsync(h, e_ctr_.get() + 1, 16, hipMemcpyDeviceToHost, st));
-    HIP_OK(hipStreamSynchronize(st));
-    unsigned long long groups = 0;
-    for (const int v : members) groups += (unsigned long long)(out_labels[v] == v);
-    out_info[1] = groups;
-    out_info[2] = h[0];
-    out_info[3] = h[1];
+    if (!exact_union_finish(n, members, e_ctr_.get() + 1, 2, out_labels, out_info)) return false;
     out_info[4] = launches;
     return true;
 }

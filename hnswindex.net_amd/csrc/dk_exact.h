@@ -75,23 +75,22 @@ struct ExactScanArgs {
 // arena[seg_off[q], seg_off[q + 1]); counts[q] (zeroed before the launch) ends as the number of keys within range, whether they
 // fitted the segment or not -- keys past the segment's end are dropped, in no particular order.  (ExactScanArgs::k is 0 and lists
 // unused for this sink.)
+// What a sink is: the bits of its kKind.  A sink names the ones that are true of it and exact_scan_kernel reads them through
+// ExactSinkIs<SINK>, so a new bit is added here and in the sinks that have it.  kSinkJoin is read where kSinkDensity is set.
+enum : unsigned { kSinkRange = 1u, kSinkGrouped = 2u, kSinkSelf = 4u, kSinkCollapse = 8u, kSinkUnion = 16u, kSinkDensity = 32u, kSinkJoin = 64u };
+template <class SINK>
+struct ExactSinkIs {
+    static constexpr bool kRange = (SINK::kKind & kSinkRange) != 0u, kGrouped = (SINK::kKind & kSinkGrouped) != 0u, kSelf = (SINK::kKind & kSinkSelf) != 0u;
+    static constexpr bool kCollapse = (SINK::kKind & kSinkCollapse) != 0u, kUnion = (SINK::kKind & kSinkUnion) != 0u;
+    static constexpr bool kDensity = (SINK::kKind & kSinkDensity) != 0u, kJoin = (SINK::kKind & kSinkJoin) != 0u;
+};
 struct ExactTopK {
-    static constexpr bool kRange = false;
-    static constexpr bool kGrouped = false;
-    static constexpr bool kSelf = false;
-    static constexpr bool kCollapse = false;
-    static constexpr bool kUnion = false;
-    static constexpr bool kDensity = false;
+    static constexpr unsigned kKind = 0;
 };
 // ExactTopKSelf: ExactTopK where query q of the round is the stored row of id self[q] and that id is no candidate of it: the pair
 // produces no key and is not counted in ExactScanArgs::evals.  A duplicate of the row under another id is a candidate like any.
 struct ExactTopKSelf {
-    static constexpr bool kRange = false;
-    static constexpr bool kGrouped = false;
-    static constexpr bool kSelf = true;
-    static constexpr bool kCollapse = false;
-    static constexpr bool kUnion = false;
-    static constexpr bool kDensity = false;
+    static constexpr unsigned kKind = kSinkSelf;
     const int *self;               // [nq of the round]
 };
 // ExactTopKCollapse: the lists hold the COLLAPSED k smallest keys -- the first k keys of the ascending order that
@@ -100,23 +99,13 @@ struct ExactTopKSelf {
 // info[0]: keys below their list's k-th that the cap dropped; info[1]: entries a key of their label evicted -- added up over
 // the scan's and the merge's waves (what they are depends on the order the keys arrive in; the lists do not).
 struct ExactTopKCollapse {
-    static constexpr bool kRange = false;
-    static constexpr bool kGrouped = false;
-    static constexpr bool kSelf = false;
-    static constexpr bool kCollapse = true;
-    static constexpr bool kUnion = false;
-    static constexpr bool kDensity = false;
+    static constexpr unsigned kKind = kSinkCollapse;
     const int *row_group;          // [every id of the list]
     int per_group;                 // 1 <= per_group <= k
     unsigned long long *info;      // [2]
 };
 struct ExactRange {
-    static constexpr bool kRange = true;
-    static constexpr bool kGrouped = false;
-    static constexpr bool kSelf = false;
-    static constexpr bool kCollapse = false;
-    static constexpr bool kUnion = false;
-    static constexpr bool kDensity = false;
+    static constexpr unsigned kKind = kSinkRange;
     float range;
     unsigned *counts;              // [nq]
     const long long *seg_off;      // [nq + 1]
@@ -126,12 +115,7 @@ struct ExactRange {
 // of it -- ExactTopKSelf's rule in the range branch: the pair offers no key and is not counted in ExactScanArgs::evals.  A repeated
 // pass over a piece of a round brings the piece's own self: self[0] belongs to the first query the launch scans.
 struct ExactRangeSelf {
-    static constexpr bool kRange = true;
-    static constexpr bool kGrouped = false;
-    static constexpr bool kSelf = true;
-    static constexpr bool kCollapse = false;
-    static constexpr bool kUnion = false;
-    static constexpr bool kDensity = false;
+    static constexpr unsigned kKind = kSinkRange | kSinkSelf;
     float range;
     unsigned *counts;              // [nq]
     const long long *seg_off;      // [nq + 1]
@@ -146,12 +130,7 @@ struct ExactRangeSelf {
 // barrier (the test is the same for the whole block).  parent[v] == v for every id of the list before the first launch
 // (exact_union_init_launch); labels[v] = uf_find(parent, v) after the last (exact_union_labels_launch).
 struct ExactRangeUnion {
-    static constexpr bool kRange = true;
-    static constexpr bool kGrouped = false;
-    static constexpr bool kSelf = true;
-    static constexpr bool kCollapse = false;
-    static constexpr bool kUnion = true;
-    static constexpr bool kDensity = false;
+    static constexpr unsigned kKind = kSinkRange | kSinkSelf | kSinkUnion;
     float range;
     int *parent;                   // [every id of the list]
     const int *self;               // [nq of the launch]: ascending
@@ -172,13 +151,7 @@ struct ExactRangeUnion {
 //     complete either way.  arena_cap == 0: counts only.
 struct alignas(16) ExactDensityPair { int a, b; unsigned d_bits, zero; }; // 16 bytes: one vector store
 struct ExactRangeDensity {
-    static constexpr bool kRange = true;
-    static constexpr bool kGrouped = false;
-    static constexpr bool kSelf = true;
-    static constexpr bool kCollapse = false;
-    static constexpr bool kUnion = false;
-    static constexpr bool kDensity = true;
-    static constexpr bool kJoin = false;
+    static constexpr unsigned kKind = kSinkRange | kSinkSelf | kSinkDensity;
     float range;
     const int *self;               // [nq of the launch]: ascending
     int *counts;                   // [every id of the list]
@@ -190,13 +163,7 @@ struct ExactRangeDensity {
 // complete and read-only, every within pair handed to density_join straight from its distance (the bits are phase A's: the same
 // kernel body measures).  No LDS behind the staged queries, no arena.
 struct ExactRangeDensityJoin {
-    static constexpr bool kRange = true;
-    static constexpr bool kGrouped = false;
-    static constexpr bool kSelf = true;
-    static constexpr bool kCollapse = false;
-    static constexpr bool kUnion = false;
-    static constexpr bool kDensity = true;
-    static constexpr bool kJoin = true;
+    static constexpr unsigned kKind = kSinkRange | kSinkSelf | kSinkDensity | kSinkJoin;
     float range;
     const int *self;               // [nq of the launch]: ascending
     const int *counts;             // [every id of the list]: phase A's, complete
@@ -224,12 +191,7 @@ struct ExactWorkItem {
     int n_chunks, slot;  // chunks of this group's list, and which of them this is
 };
 struct ExactTopKGrouped {
-    static constexpr bool kRange = false;
-    static constexpr bool kGrouped = true;
-    static constexpr bool kSelf = false;
-    static constexpr bool kCollapse = false;
-    static constexpr bool kUnion = false;
-    static constexpr bool kDensity = false;
+    static constexpr unsigned kKind = kSinkGrouped;
     const ExactWorkItem *items;
 };
 // ExactRangeGrouped: ExactRange's segments behind ExactTopKGrouped's work items (list0, n_chunks and slot of an item are not read).
@@ -238,12 +200,7 @@ struct ExactTopKGrouped {
 // nothing is permuted afterwards; in a repeated pass it numbers the queries that are scanned again and is -1 for the others of a
 // tile, whose keys are dropped.
 struct ExactRangeGrouped {
-    static constexpr bool kRange = true;
-    static constexpr bool kGrouped = true;
-    static constexpr bool kSelf = false;
-    static constexpr bool kCollapse = false;
-    static constexpr bool kUnion = false;
-    static constexpr bool kDensity = false;
+    static constexpr unsigned kKind = kSinkRange | kSinkGrouped;
     float range;
     unsigned *counts;              // [segments]
     const long long *seg_off;      // [segments + 1]
@@ -251,6 +208,10 @@ struct ExactRangeGrouped {
     const ExactWorkItem *items;
     const int *dest;               // [nq of the round, sorted order]: the query's segment, or -1
 };
+// Every sink, once: exact_unit.hip instantiates exact_scan_launch, and with it exact_scan_kernel, for each row and its unit's metric.
+#define HNSW_FOR_EACH_EXACT_SINK(X)                                                                                                       \
+    X(ExactTopK) X(ExactRange) X(ExactTopKSelf) X(ExactRangeSelf) X(ExactRangeUnion) X(ExactRangeDensity) X(ExactRangeDensityJoin)      \
+    X(ExactTopKCollapse) X(ExactTopKGrouped) X(ExactRangeGrouped)
 // what exact_merge_grouped_kernel reads per query of the round (in sorted order)
 struct ExactMergeItem {
     long long list0;     // its first list
@@ -275,12 +236,11 @@ inline size_t exact_density_lds(int qtile, int piece, int dim)
     return exact_scan_lds(qtile, piece, dim, 0) + (size_t)((qtile + kExactRQ - 1) / kExactRQ * kExactRQ) * 4;
 }
 
-template <int METRIC>
-hipError_t exact_scan_launch(const ExactScanArgs &a, unsigned n_qtiles, size_t lds, hipStream_t st);
-template <int METRIC> // lds: exact_density_lds
-hipError_t exact_range_density_scan_launch(const ExactScanArgs &a, const ExactRangeDensity &sink, unsigned n_qtiles, size_t lds, hipStream_t st);
-template <int METRIC> // lds: exact_scan_lds with k = 0, as ExactRangeUnion's
-hipError_t exact_range_density_join_scan_launch(const ExactScanArgs &a, const ExactRangeDensityJoin &sink, unsigned n_qtiles, size_t lds, hipStream_t st);
+// One launch of exact_scan_kernel<METRIC, SINK>: n_blocks x a.n_chunks blocks, n_blocks alone for a grouped sink (its work items).  lds:
+// exact_scan_lds -- with kExactCollapseEntryBytes for ExactTopKCollapse, with k = 0 for the sinks that keep no list -- or exact_density_lds
+// for ExactRangeDensity.
+template <int METRIC, class SINK>
+hipError_t exact_scan_launch(const ExactScanArgs &a, const SINK &sink, unsigned n_blocks, size_t lds, hipStream_t st);
 // counts[0, n) = -1, then counts[id] = 0 for the m ids of the list; attach (nullptr: counts only) [0, n) = kExactEmpty; *n_pairs = 0
 hipError_t density_init_launch(const int *ids, long long m, int *counts, unsigned long long *attach, long long n, unsigned long long *n_pairs, hipStream_t st);
 // phase B over the arena's n_pairs records (all of them were kept): what ExactRangeDensityJoin does per within pair
@@ -288,20 +248,10 @@ hipError_t density_pairs_launch(const ExactDensityPair *arena, unsigned long lon
                                 unsigned long long *attach, hipStream_t st);
 // labels[v], v in [0, n): a core member its root; a member that is not core its attach key's id's root, -1 without a key; -1 where counts[v] < 0
 hipError_t density_labels_launch(int *parent, const unsigned long long *attach, const int *counts, int min_samples, long long n, int *labels, hipStream_t st);
-template <int METRIC>
-hipError_t exact_range_scan_launch(const ExactScanArgs &a, const ExactRange &sink, unsigned n_qtiles, size_t lds, hipStream_t st);
-template <int METRIC>
-hipError_t exact_self_scan_launch(const ExactScanArgs &a, const ExactTopKSelf &sink, unsigned n_qtiles, size_t lds, hipStream_t st);
-template <int METRIC>
-hipError_t exact_range_self_scan_launch(const ExactScanArgs &a, const ExactRangeSelf &sink, unsigned n_qtiles, size_t lds, hipStream_t st);
-template <int METRIC>
-hipError_t exact_range_union_scan_launch(const ExactScanArgs &a, const ExactRangeUnion &sink, unsigned n_qtiles, size_t lds, hipStream_t st);
 // parent[0, n) = -1, then parent[id] = id for the m ids of the list (enqueued in this order)
 hipError_t exact_union_init_launch(const int *ids, long long m, int *parent, long long n, hipStream_t st);
 // labels[v] = the root of v's tree -- the smallest id of its group -- for v in [0, n); -1 where parent[v] is -1
 hipError_t exact_union_labels_launch(int *parent, long long n, int *labels, hipStream_t st);
-template <int METRIC> // lds: exact_scan_lds with kExactCollapseEntryBytes
-hipError_t exact_collapsed_scan_launch(const ExactScanArgs &a, const ExactTopKCollapse &sink, unsigned n_qtiles, size_t lds, hipStream_t st);
 // exact_merge_launch for the collapsed lists: the labels are looked up in row_group, info as ExactTopKCollapse::info
 hipError_t exact_merge_collapsed_launch(const unsigned long long *lists, int n_chunks, int k, int nq, const int *row_group, int per_group,
                                         unsigned long long *info, int *out_ids, float *out_d, hipStream_t st);
@@ -309,10 +259,6 @@ hipError_t exact_merge_collapsed_launch(const unsigned long long *lists, int n_c
 hipError_t exact_compact_launch(const unsigned *words, long long n_words, const long long *block_off, int *out_ids, hipStream_t st);
 hipError_t exact_merge_launch(const unsigned long long *lists, int n_chunks, int k, int nq, int *out_ids, float *out_d, hipStream_t st);
 hipError_t exact_range_sort_launch(const ExactRangeSortArgs &a, int nq, hipStream_t st);
-template <int METRIC>
-hipError_t exact_grouped_scan_launch(const ExactScanArgs &a, const ExactTopKGrouped &sink, unsigned n_items, size_t lds, hipStream_t st);
-template <int METRIC>
-hipError_t exact_range_grouped_scan_launch(const ExactScanArgs &a, const ExactRangeGrouped &sink, unsigned n_items, size_t lds, hipStream_t st);
 // row_group[0, n) -> counts[g] (zeroed here), offsets[g] (exclusive prefix), ids: group g's members in [offsets[g], offsets[g] + counts[g]),
 // in no particular order; values outside [0, n_groups) are in no group.  cursors: n_groups ints of scratch.
 hipError_t exact_group_lists_launch(const int *row_group, long long n, int n_groups, int *counts, int *offsets, int *cursors, int *ids, hipStream_t st);
@@ -424,6 +370,7 @@ template <int METRIC, class SINK>
 __global__ void __launch_bounds__(kExactThreads) exact_scan_kernel(const ExactScanArgs a, const SINK sink)
 {
     static_assert(kExactRQ == kExactThreads / 64, "wave w merges query w of a register tile");
+    using IS = ExactSinkIs<SINK>;
     constexpr int RQ = kExactRQ, RR = kExactRR;
     extern __shared__ __align__(16) unsigned char exact_lds[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, grp = tid >> 3, j = tid & 7;
@@ -442,7 +389,7 @@ __global__ void __launch_bounds__(kExactThreads) exact_scan_kernel(const ExactSc
     // blockIdx.  q_in: a query of the round that this block answers; q_clamp: past the last of them a slot shadows it.
     long long q0, lo, hi;
     [[maybe_unused]] int item_qend = 0;
-    if constexpr (SINK::kGrouped) { // (the item is the same for the whole block: its fields are kept in scalar registers)
+    if constexpr (IS::kGrouped) { // (the item is the same for the whole block: its fields are kept in scalar registers)
         const ExactWorkItem &it = sink.items[blockIdx.x];
         const int iq0 = __builtin_amdgcn_readfirstlane(it.q0), ioff = __builtin_amdgcn_readfirstlane(it.off);
         item_qend = iq0 + __builtin_amdgcn_readfirstlane(it.nq);
@@ -453,14 +400,14 @@ __global__ void __launch_bounds__(kExactThreads) exact_scan_kernel(const ExactSc
         lo = (long long)blockIdx.y * a.chunk; hi = lo + a.chunk < a.m ? lo + a.chunk : a.m;
     }
     const auto q_in = [&](long long q) {
-        if constexpr (SINK::kGrouped) return q < item_qend;
+        if constexpr (IS::kGrouped) return q < item_qend;
         else return q < a.nq;
     };
     const auto q_clamp = [&](long long q) {
-        if constexpr (SINK::kGrouped) return q >= item_qend ? item_qend - 1 : q;
+        if constexpr (IS::kGrouped) return q >= item_qend ? item_qend - 1 : q;
         else { if (q >= a.nq) q = a.nq - 1; return q; }
     };
-    if constexpr (SINK::kUnion || SINK::kDensity) {
+    if constexpr (IS::kUnion || IS::kDensity) {
         // nothing to measure where the chunk's last id is not above the tile's first query id (both lists ascend): the whole block
         // leaves, in front of its first barrier
         const int last = a.ids ? a.ids[hi - 1] : (int)(hi - 1);
@@ -473,8 +420,8 @@ __global__ void __launch_bounds__(kExactThreads) exact_scan_kernel(const ExactSc
     for (int i = tid; i < QTR * k; i += kExactThreads) lists[i] = kExactEmpty;
     if (tid < QTR) thr[tid] = kExactEmpty;
     if (tid < RQ) pend_cnt[tid] = 0;
-    if constexpr (SINK::kDensity) {
-        if constexpr (!SINK::kJoin) { if (tid < QTR) dens_cnt[tid] = 0; }
+    if constexpr (IS::kDensity) {
+        if constexpr (!IS::kJoin) { if (tid < QTR) dens_cnt[tid] = 0; }
     }
     // (the first staging's barriers order these writes before their first readers)
 
@@ -494,7 +441,7 @@ __global__ void __launch_bounds__(kExactThreads) exact_scan_kernel(const ExactSc
             if (!rvalid[r]) idx = hi - 1;
             rid[r] = a.ids ? a.ids[idx] : (int)idx;
             rp[r] = a.rows + (size_t)rid[r] * (size_t)rw;
-            if constexpr (SINK::kCollapse) rlab[r] = sink.row_group[rid[r]];
+            if constexpr (IS::kCollapse) rlab[r] = sink.row_group[rid[r]];
         }
         [[maybe_unused]] int rc[RR] = {}; // ExactRangeDensity: within pairs of this step that hold row r, over all the tile's queries
         for (int qsub = 0; qsub < QT && q_in(q0 + qsub); qsub += RQ) {
@@ -622,7 +569,7 @@ __global__ void __launch_bounds__(kExactThreads) exact_scan_kernel(const ExactSc
                     }
                 }
             }
-            if constexpr (SINK::kDensity) {
+            if constexpr (IS::kDensity) {
                 // no offers: a pair above the diagonal is counted; within the range it is joined at once (the second scan) or leaves a
                 // bit in wmask -- bit q * RR + r -- for the counting and the arena, which the whole wave does together below
                 unsigned wmask = 0;
@@ -637,13 +584,13 @@ __global__ void __launch_bounds__(kExactThreads) exact_scan_kernel(const ExactSc
                             if (!rvalid[r] || rid[r] <= selfq[q]) continue; // the pair's other half, or the query's own row: not counted
                             ++measured;
                             if (dist[q][r] <= sink.range) {
-                                if constexpr (SINK::kJoin) density_join(sink.counts, sink.min_samples, sink.parent, sink.attach, selfq[q], rid[r], dist[q][r]);
+                                if constexpr (IS::kJoin) density_join(sink.counts, sink.min_samples, sink.parent, sink.attach, selfq[q], rid[r], dist[q][r]);
                                 else wmask |= 1u << (q * RR + r);
                             }
                         }
                     }
                 }
-                if constexpr (!SINK::kJoin) {
+                if constexpr (!IS::kJoin) {
                     if (__ballot(wmask != 0)) { // (all 64 lanes are here, and the test is the same in all of them)
 #pragma unroll
                         for (int q = 0; q < RQ; ++q) {
@@ -681,7 +628,7 @@ __global__ void __launch_bounds__(kExactThreads) exact_scan_kernel(const ExactSc
                             }
                     }
                 }
-            } else if constexpr (SINK::kUnion) {
+            } else if constexpr (IS::kUnion) {
                 // no offers: a pair above the diagonal is counted and, within the range, joined from the lane that holds its distance.
                 // uf_union waits for no other lane, and the lanes meet again behind this branch, in front of the next step's barriers.
                 if (j == 0) {
@@ -700,7 +647,7 @@ __global__ void __launch_bounds__(kExactThreads) exact_scan_kernel(const ExactSc
                         }
                     }
                 }
-            } else if constexpr (SINK::kRange) {
+            } else if constexpr (IS::kRange) {
                 // offers: every key within the range goes to its query's pending list (kExactIterRows entries per query of the
                 // register tile: what one step can produce)
                 int offered = 0;
@@ -709,11 +656,11 @@ __global__ void __launch_bounds__(kExactThreads) exact_scan_kernel(const ExactSc
                     for (int q = 0; q < RQ; ++q) {
                         if (qsub + q >= QT || !q_in(q0 + qsub + q)) continue;
                         [[maybe_unused]] int self = -1;
-                        if constexpr (SINK::kSelf) self = sink.self[q0 + qsub + q]; // (a query of the round: q_in above)
+                        if constexpr (IS::kSelf) self = sink.self[q0 + qsub + q]; // (a query of the round: q_in above)
 #pragma unroll
                         for (int r = 0; r < RR; ++r) {
                             if (!rvalid[r]) continue;
-                            if constexpr (SINK::kSelf) { if (rid[r] == self) continue; } // the query's own row: no key, not counted
+                            if constexpr (IS::kSelf) { if (rid[r] == self) continue; } // the query's own row: no key, not counted
                             ++measured;
                             if (dist[q][r] <= sink.range) {
                                 const int slot = atomicAdd(&pend_cnt[q], 1);
@@ -724,7 +671,7 @@ __global__ void __launch_bounds__(kExactThreads) exact_scan_kernel(const ExactSc
                     }
                 }
                 if (__syncthreads_or(offered)) {
-                    if constexpr (SINK::kGrouped) {
+                    if constexpr (IS::kGrouped) {
                         // wave w: query qsub + w of the item.  Everything but the lane's place is the same for the whole wave and is
                         // kept in scalar registers.  seg: the query's segment; -1: its keys are not wanted.  (A second copy of the
                         // flush below, to be kept in step with it: addressing the segment through the branch-free form of both costs
@@ -771,17 +718,17 @@ __global__ void __launch_bounds__(kExactThreads) exact_scan_kernel(const ExactSc
                         if (qsub + q >= QT || !q_in(q0 + qsub + q)) continue;
                         const unsigned long long t = thr[qsub + q];
                         [[maybe_unused]] int self = -1;
-                        if constexpr (SINK::kSelf) self = sink.self[q0 + qsub + q]; // (a query of the round: q_in above)
+                        if constexpr (IS::kSelf) self = sink.self[q0 + qsub + q]; // (a query of the round: q_in above)
 #pragma unroll
                         for (int r = 0; r < RR; ++r) {
                             if (!rvalid[r]) continue;
-                            if constexpr (SINK::kSelf) { if (rid[r] == self) continue; } // the query's own row: no key, not counted
+                            if constexpr (IS::kSelf) { if (rid[r] == self) continue; } // the query's own row: no key, not counted
                             ++measured;
                             const unsigned long long key = exact_key(dist[q][r], rid[r]);
                             if (key < t) {
                                 const int slot = atomicAdd(&pend_cnt[q], 1);
                                 pend[q * kExactIterRows + slot] = key;
-                                if constexpr (SINK::kCollapse) pend_lab[q * kExactIterRows + slot] = rlab[r];
+                                if constexpr (IS::kCollapse) pend_lab[q * kExactIterRows + slot] = rlab[r];
                                 offered = 1;
                             }
                         }
@@ -793,7 +740,7 @@ __global__ void __launch_bounds__(kExactThreads) exact_scan_kernel(const ExactSc
                         unsigned long long *L = lists + (size_t)(qsub + wave) * k;
                         for (int i = 0; i < cnt; ++i) {
                             const unsigned long long x = pend[wave * kExactIterRows + i];
-                            if constexpr (SINK::kCollapse) { // (the label travelled with the key: no flush waits for memory)
+                            if constexpr (IS::kCollapse) { // (the label travelled with the key: no flush waits for memory)
                                 const int g = pend_lab[wave * kExactIterRows + i];
                                 if (x < L[k - 1]) exact_list_insert_collapsed(L, labels + (size_t)(qsub + wave) * k, k, sink.per_group, x, g, lane, dropped, evicted);
                             } else {
@@ -807,8 +754,8 @@ __global__ void __launch_bounds__(kExactThreads) exact_scan_kernel(const ExactSc
                 }
             }
         }
-        if constexpr (SINK::kDensity) {
-            if constexpr (!SINK::kJoin) { // the row side of the step's within pairs: one global atomic per row that has any
+        if constexpr (IS::kDensity) {
+            if constexpr (!IS::kJoin) { // the row side of the step's within pairs: one global atomic per row that has any
 #pragma unroll
                 for (int r = 0; r < RR; ++r)
                     if (rc[r]) atomicAdd(&sink.counts[rid[r]], rc[r]);
@@ -817,25 +764,25 @@ __global__ void __launch_bounds__(kExactThreads) exact_scan_kernel(const ExactSc
     }
     __syncthreads();
     if (measured) atomicAdd(a.evals, (unsigned long long)measured); // one atomic per group that measured anything
-    if constexpr (SINK::kDensity) {
-        if constexpr (!SINK::kJoin) { // the self side: one global atomic per query of the tile that has any (the barrier above orders the LDS adds)
+    if constexpr (IS::kDensity) {
+        if constexpr (!IS::kJoin) { // the self side: one global atomic per query of the tile that has any (the barrier above orders the LDS adds)
             if (tid < QT && q_in(q0 + tid)) {
                 const int c = dens_cnt[tid];
                 if (c) atomicAdd(&sink.counts[sink.self[q0 + tid]], c);
             }
         }
     }
-    if constexpr (SINK::kUnion) {
+    if constexpr (IS::kUnion) {
         if (joined) atomicAdd(sink.pairs, (unsigned long long)joined);
     }
-    if constexpr (SINK::kCollapse) {
+    if constexpr (IS::kCollapse) {
         if (lane == 0 && dropped) atomicAdd(&sink.info[0], (unsigned long long)dropped);
         if (lane == 0 && evicted) atomicAdd(&sink.info[1], (unsigned long long)evicted);
     }
-    if constexpr (!SINK::kRange) {
+    if constexpr (!IS::kRange) {
         for (int qi = 0; qi < QT && q_in(q0 + qi); ++qi) {
             unsigned long long *dst;
-            if constexpr (SINK::kGrouped) { // (the item is read again here rather than kept in registers through the scan)
+            if constexpr (IS::kGrouped) { // (the item is read again here rather than kept in registers through the scan)
                 const ExactWorkItem &it = sink.items[blockIdx.x];
                 dst = a.lists + (size_t)(it.list0 + (long long)qi * it.n_chunks + it.slot) * (size_t)k;
             } else dst = a.lists + ((size_t)(q0 + qi) * a.n_chunks + blockIdx.y) * (size_t)k;
@@ -844,69 +791,11 @@ __global__ void __launch_bounds__(kExactThreads) exact_scan_kernel(const ExactSc
     }
 }
 
-template <int METRIC>
-hipError_t exact_scan_launch(const ExactScanArgs &a, unsigned n_qtiles, size_t lds, hipStream_t st)
+template <int METRIC, class SINK>
+hipError_t exact_scan_launch(const ExactScanArgs &a, const SINK &sink, unsigned n_blocks, size_t lds, hipStream_t st)
 {
-    hipLaunchKernelGGL((exact_scan_kernel<METRIC, ExactTopK>), dim3(n_qtiles, (unsigned)a.n_chunks), dim3(kExactThreads), lds, st, a, ExactTopK{});
-    return hipGetLastError();
-}
-template <int METRIC>
-hipError_t exact_range_scan_launch(const ExactScanArgs &a, const ExactRange &sink, unsigned n_qtiles, size_t lds, hipStream_t st)
-{
-    hipLaunchKernelGGL((exact_scan_kernel<METRIC, ExactRange>), dim3(n_qtiles, (unsigned)a.n_chunks), dim3(kExactThreads), lds, st, a, sink);
-    return hipGetLastError();
-}
-
-template <int METRIC>
-hipError_t exact_range_self_scan_launch(const ExactScanArgs &a, const ExactRangeSelf &sink, unsigned n_qtiles, size_t lds, hipStream_t st)
-{
-    hipLaunchKernelGGL((exact_scan_kernel<METRIC, ExactRangeSelf>), dim3(n_qtiles, (unsigned)a.n_chunks), dim3(kExactThreads), lds, st, a, sink);
-    return hipGetLastError();
-}
-template <int METRIC>
-hipError_t exact_range_union_scan_launch(const ExactScanArgs &a, const ExactRangeUnion &sink, unsigned n_qtiles, size_t lds, hipStream_t st)
-{
-    hipLaunchKernelGGL((exact_scan_kernel<METRIC, ExactRangeUnion>), dim3(n_qtiles, (unsigned)a.n_chunks), dim3(kExactThreads), lds, st, a, sink);
-    return hipGetLastError();
-}
-
-template <int METRIC>
-hipError_t exact_range_density_scan_launch(const ExactScanArgs &a, const ExactRangeDensity &sink, unsigned n_qtiles, size_t lds, hipStream_t st)
-{
-    hipLaunchKernelGGL((exact_scan_kernel<METRIC, ExactRangeDensity>), dim3(n_qtiles, (unsigned)a.n_chunks), dim3(kExactThreads), lds, st, a, sink);
-    return hipGetLastError();
-}
-template <int METRIC>
-hipError_t exact_range_density_join_scan_launch(const ExactScanArgs &a, const ExactRangeDensityJoin &sink, unsigned n_qtiles, size_t lds, hipStream_t st)
-{
-    hipLaunchKernelGGL((exact_scan_kernel<METRIC, ExactRangeDensityJoin>), dim3(n_qtiles, (unsigned)a.n_chunks), dim3(kExactThreads), lds, st, a, sink);
-    return hipGetLastError();
-}
-
-template <int METRIC>
-hipError_t exact_self_scan_launch(const ExactScanArgs &a, const ExactTopKSelf &sink, unsigned n_qtiles, size_t lds, hipStream_t st)
-{
-    hipLaunchKernelGGL((exact_scan_kernel<METRIC, ExactTopKSelf>), dim3(n_qtiles, (unsigned)a.n_chunks), dim3(kExactThreads), lds, st, a, sink);
-    return hipGetLastError();
-}
-
-template <int METRIC>
-hipError_t exact_collapsed_scan_launch(const ExactScanArgs &a, const ExactTopKCollapse &sink, unsigned n_qtiles, size_t lds, hipStream_t st)
-{
-    hipLaunchKernelGGL((exact_scan_kernel<METRIC, ExactTopKCollapse>), dim3(n_qtiles, (unsigned)a.n_chunks), dim3(kExactThreads), lds, st, a, sink);
-    return hipGetLastError();
-}
-
-template <int METRIC>
-hipError_t exact_grouped_scan_launch(const ExactScanArgs &a, const ExactTopKGrouped &sink, unsigned n_items, size_t lds, hipStream_t st)
-{
-    hipLaunchKernelGGL((exact_scan_kernel<METRIC, ExactTopKGrouped>), dim3(n_items), dim3(kExactThreads), lds, st, a, sink);
-    return hipGetLastError();
-}
-template <int METRIC>
-hipError_t exact_range_grouped_scan_launch(const ExactScanArgs &a, const ExactRangeGrouped &sink, unsigned n_items, size_t lds, hipStream_t st)
-{
-    hipLaunchKernelGGL((exact_scan_kernel<METRIC, ExactRangeGrouped>), dim3(n_items), dim3(kExactThreads), lds, st, a, sink);
+    const dim3 grid = ExactSinkIs<SINK>::kGrouped ? dim3(n_blocks) : dim3(n_blocks, (unsigned)a.n_chunks);
+    hipLaunchKernelGGL((exact_scan_kernel<METRIC, SINK>), grid, dim3(kExactThreads), lds, st, a, sink);
     return hipGetLastError();
 }
 

@@ -15,15 +15,8 @@
 namespace hnsw {
 constexpr int kUnitMetric = HNSW_UNIT_METRIC_ID;
 static_assert(kUnitMetric >= 0, "HNSW_UNIT_METRIC is no tag of HNSW_FOR_EACH_METRIC");
-template hipError_t exact_scan_launch<kUnitMetric>(const ExactScanArgs &, unsigned, size_t, hipStream_t);
-template hipError_t exact_range_scan_launch<kUnitMetric>(const ExactScanArgs &, const ExactRange &, unsigned, size_t, hipStream_t);
-template hipError_t exact_self_scan_launch<kUnitMetric>(const ExactScanArgs &, const ExactTopKSelf &, unsigned, size_t, hipStream_t);
-template hipError_t exact_range_self_scan_launch<kUnitMetric>(const ExactScanArgs &, const ExactRangeSelf &, unsigned, size_t, hipStream_t);
-template hipError_t exact_range_union_scan_launch<kUnitMetric>(const ExactScanArgs &, const ExactRangeUnion &, unsigned, size_t, hipStream_t);
-template hipError_t exact_range_density_scan_launch<kUnitMetric>(const ExactScanArgs &, const ExactRangeDensity &, unsigned, size_t, hipStream_t);
-template hipError_t exact_range_density_join_scan_launch<kUnitMetric>(const ExactScanArgs &, const ExactRangeDensityJoin &, unsigned, size_t, hipStream_t);
-template hipError_t exact_collapsed_scan_launch<kUnitMetric>(const ExactScanArgs &, const ExactTopKCollapse &, unsigned, size_t, hipStream_t);
-template hipError_t exact_grouped_scan_launch<kUnitMetric>(const ExactScanArgs &, const ExactTopKGrouped &, unsigned, size_t, hipStream_t);
-template hipError_t exact_range_grouped_scan_launch<kUnitMetric>(const ExactScanArgs &, const ExactRangeGrouped &, unsigned, size_t, hipStream_t);
+#define HNSW_EXACT_SINK_UNIT(SINK) template hipError_t exact_scan_launch<kUnitMetric, SINK>(const ExactScanArgs &, const SINK &, unsigned, size_t, hipStream_t);
+HNSW_FOR_EACH_EXACT_SINK(HNSW_EXACT_SINK_UNIT)
+#undef HNSW_EXACT_SINK_UNIT
 template hipError_t graph_repair_propose_launch<kUnitMetric>(const RepairProposeArgs &, unsigned, hipStream_t);
 } // namespace hnsw

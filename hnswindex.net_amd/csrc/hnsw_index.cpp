@@ -2003,20 +2003,30 @@ bool HnswIndex::live_labels(const int *&row_group, long long &n_row_group, std::
     return true;
 }
 
+// The opening of the exact top-k calls that bring their queries.  who: the ABI call; args_ok(): the call's own argument rules, filing
+// err.  1: go on; 0: answered (no query, or nothing to find: padded); -1: failed.
+template <class ArgsOk>
+int HnswIndex::exact_knn_begin(const char *who, int count, int dim, int k, int *out_ids, float *out_dists, std::string &err, ArgsOk args_ok)
+{
+    if (count <= 0) return 0;
+    if (failed(err)) return -1;
+    if (k > kExactMaxK) { err = std::string("System.ArgumentOutOfRangeException: ") + who + ": k = " + std::to_string(k) + " is above the limit of " + std::to_string(kExactMaxK); return -1; }
+    if (!args_ok()) return -1;
+    if (k < 1 || graph_.count <= 0) {
+        pad_results(out_ids, out_dists, (size_t)count * (size_t)std::max(k, 0));
+        return 0;
+    }
+    return ensure_dim(dim, err) ? 1 : -1;
+}
+
 // The flat scan: every live, allowed row measured against every query.  The candidates are the live ids: while
 // nothing has been removed they are 0 .. length - 1 and the caller's bitset goes to the device as it is (none: the scan addresses
 // rows directly); once slots are vacant the live set is ANDed into it here.
 int HnswIndex::exact_knn_query(const float *queries, int count, int dim, int k, const uint32_t *allow_bits, long long nbits, int *out_ids, float *out_dists,
                                std::string &err)
 {
-    if (count <= 0) return 0;
-    if (failed(err)) return -1;
-    if (k > kExactMaxK) { err = "System.ArgumentOutOfRangeException: hnsw_mi355x_exact_knn_query: k = " + std::to_string(k) + " is above the limit of " + std::to_string(kExactMaxK); return -1; }
-    if (k < 1 || graph_.count <= 0) {
-        pad_results(out_ids, out_dists, (size_t)count * (size_t)std::max(k, 0));
-        return 0;
-    }
-    if (!ensure_dim(dim, err)) return -1;
+    const int go = exact_knn_begin("hnsw_mi355x_exact_knn_query", count, dim, k, out_ids, out_dists, err, [] { return true; });
+    if (go <= 0) return go;
     std::vector<uint32_t> live;
     const long long length = exact_candidates(allow_bits, nbits, live);
     // (the scan stages its queries in a buffer of its own: the resident set, sharded or not, stays what it was)
@@ -2029,23 +2039,16 @@ int HnswIndex::exact_knn_query(const float *queries, int count, int dim, int k, 
 int HnswIndex::exact_knn_query_collapsed(const float *queries, int count, int dim, int k, const int *row_group, long long n_row_group, int per_group,
                                          const uint32_t *allow_bits, long long nbits, int *out_ids, float *out_dists, std::string &err)
 {
-    if (count <= 0) return 0;
-    if (failed(err)) return -1;
     const std::string who = "hnsw_mi355x_exact_knn_query_collapsed";
-    if (k > kExactMaxK) { err = "System.ArgumentOutOfRangeException: " + who + ": k = " + std::to_string(k) + " is above the limit of " + std::to_string(kExactMaxK); return -1; }
-    if (k >= 1 && (per_group < 1 || per_group > k)) {
-        err = "System.ArgumentOutOfRangeException: " + who + ": per_group = " + std::to_string(per_group) + " is outside [1, k = " + std::to_string(k) + "]";
-        return -1;
-    }
-    if (n_row_group < graph_.length) {
-        err = "System.ArgumentException: " + who + ": row_group has " + std::to_string(n_row_group) + " entries, the index's length is " + std::to_string(graph_.length);
-        return -1;
-    }
-    if (k < 1 || graph_.count <= 0) {
-        pad_results(out_ids, out_dists, (size_t)count * (size_t)std::max(k, 0));
-        return 0;
-    }
-    if (!ensure_dim(dim, err)) return -1;
+    const int go = exact_knn_begin(who.c_str(), count, dim, k, out_ids, out_dists, err, [&] {
+        if (k >= 1 && (per_group < 1 || per_group > k))
+            err = "System.ArgumentOutOfRangeException: " + who + ": per_group = " + std::to_string(per_group) + " is outside [1, k = " + std::to_string(k) + "]";
+        else if (n_row_group < graph_.length)
+            err = "System.ArgumentException: " + who + ": row_group has " + std::to_string(n_row_group) + " entries, the index's length is " + std::to_string(graph_.length);
+        else return true;
+        return false;
+    });
+    if (go <= 0) return go;
     std::vector<uint32_t> live;
     const long long length = exact_candidates(allow_bits, nbits, live);
     // (the scan stages its queries in a buffer of its own: the resident set, sharded or not, stays what it was)
@@ -2057,16 +2060,9 @@ int HnswIndex::exact_knn_query_collapsed(const float *queries, int count, int di
 int HnswIndex::exact_knn_query_grouped(const float *queries, int count, int dim, int k, const int *row_group, long long n_row_group, const int *query_group,
                                        int n_groups, int *out_ids, float *out_dists, std::string &err)
 {
-    if (count <= 0) return 0;
-    if (failed(err)) return -1;
     const char *who = "hnsw_mi355x_exact_knn_query_grouped";
-    if (k > kExactMaxK) { err = std::string("System.ArgumentOutOfRangeException: ") + who + ": k = " + std::to_string(k) + " is above the limit of " + std::to_string(kExactMaxK); return -1; }
-    if (!group_args_ok(who, query_group, count, n_groups, err)) return -1;
-    if (k < 1 || graph_.count <= 0) {
-        pad_results(out_ids, out_dists, (size_t)count * (size_t)std::max(k, 0));
-        return 0;
-    }
-    if (!ensure_dim(dim, err)) return -1;
+    const int go = exact_knn_begin(who, count, dim, k, out_ids, out_dists, err, [&] { return group_args_ok(who, query_group, count, n_groups, err); });
+    if (go <= 0) return go;
     const long long length = graph_.length;
     std::vector<int> live;
     if (live_labels(row_group, n_row_group, live) && n_row_group == 0) { pad_results(out_ids, out_dists, (size_t)count * (size_t)k); return 0; } // vacant slots and no label: no candidate
@@ -2080,17 +2076,10 @@ int HnswIndex::exact_knn_query_grouped(const float *queries, int count, int dim,
 int HnswIndex::exact_knn_query_tagged(const float *queries, int count, int dim, int k, const uint32_t *row_tags, long long n_row_tags, const uint32_t *query_tags,
                                       int match, int *out_ids, float *out_dists, std::string &err)
 {
-    if (count <= 0) return 0;
-    if (failed(err)) return -1;
     const char *who = "hnsw_mi355x_exact_knn_query_tagged";
-    if (k > kExactMaxK) { err = std::string("System.ArgumentOutOfRangeException: ") + who + ": k = " + std::to_string(k) + " is above the limit of " + std::to_string(kExactMaxK); return -1; }
     TagCall tc;
-    if (!tag_args_ok(who, query_tags, count, match, &tc, err)) return -1;
-    if (k < 1 || graph_.count <= 0) {
-        pad_results(out_ids, out_dists, (size_t)count * (size_t)std::max(k, 0));
-        return 0;
-    }
-    if (!ensure_dim(dim, err)) return -1;
+    const int go = exact_knn_begin(who, count, dim, k, out_ids, out_dists, err, [&] { return tag_args_ok(who, query_tags, count, match, &tc, err); });
+    if (go <= 0) return go;
     const long long length = graph_.length;
     std::vector<uint32_t> live;
     if (live_tags(row_tags, n_row_tags, live) && n_row_tags == 0) { pad_results(out_ids, out_dists, (size_t)count * (size_t)k); return 0; } // vacant slots and no word: no candidate
@@ -2142,22 +2131,35 @@ int HnswIndex::exact_range_query_by_id(const int *ids, int count, float range, c
     return exact_range_fetch(*dev_, dev_->exact_range_by_id(ids, count, length, range, allow_bits, nbits, counts), out_ids, out_dists, err);
 }
 
+// The opening of the label calls (duplicate_groups, density_clusters, graph_duplicate_groups).  who: the ABI call; out_info's n_info words
+// are zeroed first; args_ok(): the call's own argument rules, filing err; `out`, named out_name, must hold the index's length of
+// entries within cap and is filled with -1, as `also` is where there is one.  1: go on; 0: answered (no slot, or every slot vacant: no
+// member, and nothing needs the device); -1: failed.
+template <class ArgsOk>
+int HnswIndex::label_call_begin(const char *who, uint64_t *out_info, int n_info, long long cap, int *out, const char *out_name, int *also, std::string &err, ArgsOk args_ok)
+{
+    for (int i = 0; i < n_info; ++i) out_info[i] = 0;
+    if (failed(err) || !args_ok()) return -1;
+    const long long length = graph_.length;
+    if (cap < length) {
+        err = std::string("System.ArgumentException: ") + who + ": cap = " + std::to_string(cap) + " is below the index's length of " + std::to_string(length);
+        return -1;
+    }
+    if (length > 0 && !out) { err = std::string("System.ArgumentNullException: ") + who + ": " + out_name; return -1; }
+    for (long long v = 0; v < length; ++v) {
+        out[v] = -1;
+        if (also) also[v] = -1;
+    }
+    return length > 0 && graph_.count > 0 ? 1 : 0;
+}
+
 // The duplicate groups: the members are exact_range_query's candidates; the labels come back from the device as they are.
 int HnswIndex::duplicate_groups(float range, const uint32_t *allow_bits, long long nbits, int *out_labels, long long cap, uint64_t *out_info, std::string &err)
 {
-    for (int i = 0; i < 4; ++i) out_info[i] = 0;
-    if (failed(err)) return -1;
-    const long long length_now = graph_.length;
-    if (cap < length_now) {
-        err = "System.ArgumentException: hnsw_mi355x_duplicate_groups: cap = " + std::to_string(cap) + " is below the index's length of " + std::to_string(length_now);
-        return -1;
-    }
-    if (length_now > 0 && !out_labels) { err = "System.ArgumentNullException: hnsw_mi355x_duplicate_groups: out_labels"; return -1; }
-    if (length_now <= 0) return 0;
+    const int go = label_call_begin("hnsw_mi355x_duplicate_groups", out_info, 4, cap, out_labels, "out_labels", nullptr, err, [] { return true; });
+    if (go <= 0) return go;
     std::vector<uint32_t> live;
     const long long length = exact_candidates(allow_bits, nbits, live);
-    for (long long v = 0; v < length; ++v) out_labels[v] = -1;
-    if (graph_.count <= 0) return 0; // every slot is vacant: no member, and nothing needs the device
     if (!dev_->exact_range_groups(length, range, allow_bits, nbits, out_labels, out_info)) { err = get_dev_error(); return -1; }
     return 0;
 }
@@ -2166,26 +2168,13 @@ int HnswIndex::duplicate_groups(float range, const uint32_t *allow_bits, long lo
 int HnswIndex::density_clusters(float range, int min_samples, const uint32_t *allow_bits, long long nbits, int *out_labels, int *out_counts, long long cap,
                                 uint64_t *out_info, std::string &err)
 {
-    for (int i = 0; i < 8; ++i) out_info[i] = 0;
-    if (failed(err)) return -1;
-    if (min_samples < 1) {
-        err = "System.ArgumentException: hnsw_mi355x_density_clusters: min_samples = " + std::to_string(min_samples) + " is below 1";
-        return -1;
-    }
-    const long long length_now = graph_.length;
-    if (cap < length_now) {
-        err = "System.ArgumentException: hnsw_mi355x_density_clusters: cap = " + std::to_string(cap) + " is below the index's length of " + std::to_string(length_now);
-        return -1;
-    }
-    if (length_now > 0 && !out_counts) { err = "System.ArgumentNullException: hnsw_mi355x_density_clusters: out_counts"; return -1; }
-    if (length_now <= 0) return 0;
+    const int go = label_call_begin("hnsw_mi355x_density_clusters", out_info, 8, cap, out_counts, "out_counts", out_labels, err, [&] {
+        if (min_samples < 1) err = "System.ArgumentException: hnsw_mi355x_density_clusters: min_samples = " + std::to_string(min_samples) + " is below 1";
+        return min_samples >= 1;
+    });
+    if (go <= 0) return go;
     std::vector<uint32_t> live;
     const long long length = exact_candidates(allow_bits, nbits, live);
-    for (long long v = 0; v < length; ++v) {
-        out_counts[v] = -1;
-        if (out_labels) out_labels[v] = -1;
-    }
-    if (graph_.count <= 0) return 0; // every slot is vacant: no member, and nothing needs the device
     if (!dev_->exact_range_density(length, range, min_samples, allow_bits, nbits, out_labels, out_counts, out_info)) { err = get_dev_error(); return -1; }
     return 0;
 }
@@ -2194,17 +2183,8 @@ int HnswIndex::density_clusters(float range, int min_samples, const uint32_t *al
 // layer-0 edge of the mirror within the range.
 int HnswIndex::graph_duplicate_groups(float range, const uint32_t *allow_bits, long long nbits, int *out_labels, long long cap, uint64_t *out_info, std::string &err)
 {
-    for (int i = 0; i < 5; ++i) out_info[i] = 0;
-    if (failed(err)) return -1;
-    const long long length_now = graph_.length;
-    if (cap < length_now) {
-        err = "System.ArgumentException: hnsw_mi355x_graph_duplicate_groups: cap = " + std::to_string(cap) + " is below the index's length of " + std::to_string(length_now);
-        return -1;
-    }
-    if (length_now > 0 && !out_labels) { err = "System.ArgumentNullException: hnsw_mi355x_graph_duplicate_groups: out_labels"; return -1; }
-    if (length_now <= 0) return 0;
-    for (long long v = 0; v < length_now; ++v) out_labels[v] = -1;
-    if (graph_.count <= 0) return 0; // every slot is vacant: no member, and nothing needs the device
+    const int go = label_call_begin("hnsw_mi355x_graph_duplicate_groups", out_info, 5, cap, out_labels, "out_labels", nullptr, err, [] { return true; });
+    if (go <= 0) return go;
     if (!sync_graph(err)) return -1;
     std::vector<uint32_t> live;
     const long long length = exact_candidates(allow_bits, nbits, live);

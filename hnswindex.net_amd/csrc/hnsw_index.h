@@ -322,6 +322,10 @@ private:
     // what knn_query_grouped / knn_query_tagged share: the prologue, the lock-step way class by class, the answer_resident call
     template <class ArgsOk>
     int predicate_query_begin(const char *who, int count, int k, int layer, int *out_ids, float *out_dists, std::string &err, ArgsOk args_ok);
+    template <class ArgsOk> // the opening of the exact top-k calls that bring their queries, and of the three label calls (hnsw_index.cpp)
+    int exact_knn_begin(const char *who, int count, int dim, int k, int *out_ids, float *out_dists, std::string &err, ArgsOk args_ok);
+    template <class ArgsOk>
+    int label_call_begin(const char *who, uint64_t *out_info, int n_info, long long cap, int *out, const char *out_name, int *also, std::string &err, ArgsOk args_ok);
     template <class ClassOf, class Matches>
     int lockstep_by_class(const int *which, int n, int k, int layer, long long n_lab, size_t n_classes, ClassOf class_of, Matches matches, int *out_ids,
                           float *out_dists, std::string &err);

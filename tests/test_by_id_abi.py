@@ -105,6 +105,10 @@ def test_the_self_kernel_is_built_where_the_filtered_kernels_are_and_the_gather_
     csrc = ROOT / "hnswindex.net_amd" / "csrc"
     unit = re.search(r"#define HNSW_UNIT_filtered\(DO, M\)(.*)", (csrc / "device_kernels.h").read_text()).group(1)
     assert all(f"HNSW_##DO##_{kind}" in unit for kind in ("FILTERED", "GROUPED", "TAGGED", "SELF"))
-    assert "exact_self_scan_launch<kUnitMetric>" in (csrc / "exact_unit.hip").read_text()
+    # ExactTopKSelf is a row of the sink list that the exact units instantiate the one launcher from, a self sink and nothing else
+    unit, scan = (csrc / "exact_unit.hip").read_text(), (csrc / "dk_exact.h").read_text()
+    assert "template hipError_t exact_scan_launch<kUnitMetric, SINK>(" in unit and "HNSW_FOR_EACH_EXACT_SINK(HNSW_EXACT_SINK_UNIT)" in unit
+    assert "X(ExactTopKSelf)" in re.search(r"#define HNSW_FOR_EACH_EXACT_SINK\(X\)((?:.*\\\n)*.*)", scan).group(1)
+    assert re.search(r"struct ExactTopKSelf \{\s*static constexpr unsigned kKind = kSinkSelf;[^}]*const int \*self;", scan)
     assert "gather_rows_kernel(" in (csrc / "dk_misc_kernels.h").read_text()
     assert "graph_repair_gather_kernel" not in "".join(f.read_text() for f in csrc.iterdir() if f.is_file())

@@ -87,14 +87,21 @@ def test_null_handle_returns_zeros():
 
 
 def test_the_sinks_are_instantiated_in_the_exact_units():
+    # the units instantiate the one launcher, and with it exact_scan_kernel<METRIC, SINK>, for every row of the sink list
     unit = (CSRC / "exact_unit.hip").read_text()
-    assert "exact_range_density_scan_launch<kUnitMetric>" in unit and "exact_range_density_join_scan_launch<kUnitMetric>" in unit
+    assert "template hipError_t exact_scan_launch<kUnitMetric, SINK>(" in unit and "HNSW_FOR_EACH_EXACT_SINK(HNSW_EXACT_SINK_UNIT)" in unit
     scan = (CSRC / "dk_exact.h").read_text()
-    for sink in ("ExactRangeDensity", "ExactRangeDensityJoin"):
-        assert re.search(r"struct " + sink + r" \{[^}]*kRange = true;[^}]*kSelf = true;[^}]*kDensity = true;[^}]*const int \*self;", scan), sink
-        assert f"exact_scan_kernel<METRIC, {sink}>" in scan, sink
-    # every sink says whether it is a density sink, so that the others compile as they did
-    assert len(re.findall(r"static constexpr bool kDensity = (?:true|false);", scan)) == len(re.findall(r"static constexpr bool kUnion = (?:true|false);", scan)) == 10
+    assert "hipLaunchKernelGGL((exact_scan_kernel<METRIC, SINK>)" in scan
+    rows = re.findall(r"X\((\w+)\)", re.search(r"#define HNSW_FOR_EACH_EXACT_SINK\(X\)((?:.*\\\n)*.*)", scan).group(1))
+    kinds = {sink: set(kind.split(" | ")) for sink, kind in re.findall(r"struct (\w+) \{\s*static constexpr unsigned kKind = ([^;]*);", scan)}
+    for sink, join in (("ExactRangeDensity", set()), ("ExactRangeDensityJoin", {"kSinkJoin"})):
+        assert rows.count(sink) == 1, sink
+        assert kinds[sink] == {"kSinkRange", "kSinkSelf", "kSinkDensity"} | join, sink
+        assert re.search(r"struct " + sink + r" \{[^}]*const int \*self;", scan), sink
+    # every sink is a row of the list and says what it is; the density sinks are these two, so that the others compile as they did
+    assert sorted(rows) == sorted(kinds) and len(rows) == 10
+    assert sorted(s for s in kinds if kinds[s] & {"kSinkDensity", "kSinkJoin"}) == ["ExactRangeDensity", "ExactRangeDensityJoin"]
+    assert all(f"k{bit[5:]} = (SINK::kKind & {bit}) != 0u" in scan for bit in set().union(*kinds.values()) - {"0"})   # ... and the kernel reads each bit
     for kernel in ("density_init_kernel", "density_pairs_kernel", "density_labels_kernel"):
         assert "void __launch_bounds__(256) " + kernel in scan, kernel
     assert "density_pair_cap" in (CSRC / "diag.h").read_text() and 'diag("density_pair_cap"' in (CSRC / "device_backend.hip").read_text()

@@ -92,12 +92,16 @@ def test_null_handle_and_count_behave_like_exact_range_query():
 
 
 def test_the_sinks_are_instantiated_in_the_exact_units_and_the_union_find_has_a_header_of_its_own():
+    # the units instantiate the one launcher, and with it exact_scan_kernel<METRIC, SINK>, for every row of the sink list
     unit = (CSRC / "exact_unit.hip").read_text()
-    assert "exact_range_self_scan_launch<kUnitMetric>" in unit and "exact_range_union_scan_launch<kUnitMetric>" in unit
+    assert "template hipError_t exact_scan_launch<kUnitMetric, SINK>(" in unit and "HNSW_FOR_EACH_EXACT_SINK(HNSW_EXACT_SINK_UNIT)" in unit
     scan = (CSRC / "dk_exact.h").read_text()
-    for sink in ("ExactRangeSelf", "ExactRangeUnion"):
-        assert re.search(r"struct " + sink + r" \{[^}]*kRange = true;[^}]*kSelf = true;[^}]*const int \*self;", scan), sink
-        assert f"exact_scan_kernel<METRIC, {sink}>" in scan, sink
+    assert "hipLaunchKernelGGL((exact_scan_kernel<METRIC, SINK>)" in scan
+    rows = re.findall(r"X\((\w+)\)", re.search(r"#define HNSW_FOR_EACH_EXACT_SINK\(X\)((?:.*\\\n)*.*)", scan).group(1))
+    for sink, kinds in (("ExactRangeSelf", {"kSinkRange", "kSinkSelf"}), ("ExactRangeUnion", {"kSinkRange", "kSinkSelf", "kSinkUnion"})):
+        assert rows.count(sink) == 1, sink
+        kind = re.search(r"struct " + sink + r" \{\s*static constexpr unsigned kKind = ([^;]*);[^}]*const int \*self;", scan)
+        assert kind and set(kind.group(1).split(" | ")) == kinds, sink
     assert '#include "dk_union_find.h"' in scan and '#include "dk_union_find.h"' in (CSRC / "dk_graph_info.h").read_text()
     uf = (CSRC / "dk_union_find.h").read_text()
     assert "int uf_find(int *parent, int v)" in uf and "void uf_union(int *parent, int a, int b)" in uf
