@@ -154,6 +154,9 @@ _GROUPS_INFO = ("members", "groups", "pairs_within", "pairs_measured")   # out_i
 lib.hnsw_mi355x_density_clusters.restype = ct.c_int
 lib.hnsw_mi355x_density_clusters.argtypes = [ct.c_void_p, ct.c_float, ct.c_int, _U32, ct.c_longlong, _I, _I, ct.c_longlong, ct.POINTER(ct.c_uint64)]
 _DENSITY_INFO = ("members", "clusters", "core", "border", "noise", "pairs_within", "pairs_measured", "scans")   # out_info[0 .. 7] of hnsw_mi355x_density_clusters
+lib.hnsw_mi355x_single_linkage_tree.restype = ct.c_int
+lib.hnsw_mi355x_single_linkage_tree.argtypes = [ct.c_void_p, _U32, ct.c_longlong, _I, _I, _F, ct.c_longlong, ct.POINTER(ct.c_uint64)]
+_SPAN_INFO = ("members", "edges", "components", "rounds", "pairs_measured", "pairs_skipped", "launches", "reserved")   # out_info[0 .. 7] of hnsw_mi355x_single_linkage_tree
 lib.hnsw_mi355x_graph_duplicate_groups.restype = ct.c_int
 lib.hnsw_mi355x_graph_duplicate_groups.argtypes = [ct.c_void_p, ct.c_float, _U32, ct.c_longlong, _I, ct.c_longlong, ct.POINTER(ct.c_uint64)]
 lib.hnsw_mi355x_near_edges.restype = ct.c_int
@@ -333,6 +336,8 @@ lib.hnswdev_exact_range_by_id.restype = ct.c_int
 lib.hnswdev_exact_range_by_id.argtypes = [ct.c_void_p, _I, ct.c_int, ct.c_longlong, ct.c_float, _U32, ct.c_longlong, _I]
 lib.hnswdev_exact_range_groups.restype = ct.c_int
 lib.hnswdev_exact_range_groups.argtypes = [ct.c_void_p, ct.c_longlong, ct.c_float, _U32, ct.c_longlong, _I, ct.POINTER(ct.c_uint64)]
+lib.hnswdev_exact_span_tree.restype = ct.c_int
+lib.hnswdev_exact_span_tree.argtypes = [ct.c_void_p, ct.c_longlong, _U32, ct.c_longlong, _I, _I, _F, ct.c_longlong, ct.POINTER(ct.c_uint64)]
 lib.hnswdev_exact_range_density.restype = ct.c_int
 lib.hnswdev_exact_range_density.argtypes = [ct.c_void_p, ct.c_longlong, ct.c_float, ct.c_int, _U32, ct.c_longlong, _I, _I, ct.POINTER(ct.c_uint64)]
 lib.hnswdev_graph_edge_groups.restype = ct.c_int
@@ -1090,6 +1095,52 @@ class Index:
         `radius` of member v -- density_clusters' counts -- and -1 where v is no member.  One scan; no pair is kept, nothing is joined."""
         return self._density(radius, 1, allowed, False)[1]
 
+    # ---- the single-linkage tree (DESIGN.md 3.33) ----
+    def single_linkage_tree(self, allowed=None) -> Tuple[npt.NDArray[np.int32], npt.NDArray[np.int32], npt.NDArray[np.float32], dict]:
+        """The single-linkage dendrogram of the stored rows as its minimum spanning forest (hnsw_mi355x_single_linkage_tree):
+        (a int32[e], b int32[e], dist float32[e], info).  The members are duplicate_groups'; the weight of members a < b is the
+        distance from the stored row of a, taken as the query, to row b -- the bits duplicate_groups compares with its radius; a NaN
+        distance is no edge.  Edges are ordered by (dist, a, b), -0 equal to +0: a strict order, so the forest is unique.  a[e] < b[e],
+        ascending in that order, e = members - components.  Every radius of duplicate_groups is a cut of it (single_linkage_cut), and
+        the largest gaps in dist are where a radius belongs.  info: members, edges, components, rounds (Boruvka's), pairs_measured,
+        pairs_skipped (both ends already in one component), launches (of the scan kernel), reserved (0)."""
+        n = max(int(self.length) - 1, 0)
+        a, b, d = np.empty(n, dtype=np.int32), np.empty(n, dtype=np.int32), np.empty(n, dtype=np.float32)
+        info = (ct.c_uint64 * 8)()
+        words, nbits = allow_bits(allowed) if allowed is not None else (None, 0)
+        words, wp = _words_arg(words) if allowed is not None else (None, None)
+        if self._h and lib.hnsw_mi355x_single_linkage_tree(self._h, wp, nbits, a.ctypes.data_as(_I), b.ctypes.data_as(_I), d.ctypes.data_as(_F), n, info) < 0:
+            raise RuntimeError(last_error())
+        e = int(info[1])
+        return a[:e].copy(), b[:e].copy(), d[:e].copy(), {name: int(info[i]) for i, name in enumerate(_SPAN_INFO)}
+
+    def single_linkage_cut(self, tree, radius: float, allowed=None) -> npt.NDArray[np.int32]:
+        """The groups of duplicate_groups(radius, allowed) read off single_linkage_tree(allowed)'s result, on the host: the tree's
+        edges with dist <= radius are joined, labels[v] is the smallest member id of v's group and -1 where v is no member --
+        duplicate_groups' labels byte for byte, for every radius from one tree."""
+        a, b, d = tree[0], tree[1], tree[2]
+        n = int(self.length)
+        member = np.zeros(n, dtype=bool)
+        member[self.ids()] = True
+        if allowed is not None:
+            words, nbits = allow_bits(allowed)
+            mask = np.unpackbits(words.view(np.uint8), bitorder="little")[:nbits].astype(bool)
+            member[min(n, nbits):] = False
+            member[:min(n, nbits)] &= mask[:n]
+        parent = np.arange(n, dtype=np.int64)
+
+        def find(v):
+            while parent[v] != v:
+                parent[v] = parent[parent[v]]
+                v = parent[v]
+            return v
+        for e in np.flatnonzero(d <= np.float32(radius)):   # (a NaN radius admits nothing)
+            ra, rb = find(int(a[e])), find(int(b[e]))
+            parent[max(ra, rb)] = min(ra, rb)               # the smaller root stays: a root is its group's smallest id
+        labels = np.array([find(v) for v in range(n)], dtype=np.int32) if n else np.empty(0, dtype=np.int32)
+        labels[~member] = -1
+        return labels
+
     # ---- near-duplicates over the graph's edges (DESIGN.md 3.30) ----
     def graph_duplicate_groups(self, radius: float, allowed=None) -> Tuple[npt.NDArray[np.int32], dict]:
         """duplicate_groups asked of the graph (hnsw_mi355x_graph_duplicate_groups): (int32[length], info).  The members are
@@ -1611,6 +1662,18 @@ class DeviceBackend:
         self._check(lib.hnswdev_exact_range_density(self._ctx, int(n_rows), float(radius), int(min_samples), wp, nbits,
                                                     out_labels.ctypes.data_as(_I) if labels else None, counts.ctypes.data_as(_I), info))
         return out_labels, counts, {name: int(info[i]) for i, name in enumerate(_DENSITY_INFO)}
+
+    def exact_span_tree(self, n_rows: int, allowed=None):
+        """hnswdev_exact_span_tree: (a int32[e], b int32[e], dist float32[e], info dict) -- Index.single_linkage_tree on the uploaded
+        rows of [0, n_rows) that `allowed` allows."""
+        n = max(int(n_rows) - 1, 0)
+        a, b, d = np.empty(n, dtype=np.int32), np.empty(n, dtype=np.int32), np.empty(n, dtype=np.float32)
+        info = (ct.c_uint64 * 8)()
+        words, nbits = allow_bits(allowed) if allowed is not None else (None, 0)
+        words, wp = _words_arg(words) if allowed is not None else (None, None)
+        self._check(lib.hnswdev_exact_span_tree(self._ctx, int(n_rows), wp, nbits, a.ctypes.data_as(_I), b.ctypes.data_as(_I), d.ctypes.data_as(_F), n, info))
+        e = int(info[1])
+        return a[:e].copy(), b[:e].copy(), d[:e].copy(), {name: int(info[i]) for i, name in enumerate(_SPAN_INFO)}
 
     def graph_edge_groups(self, radius: float, n_rows: int, allowed=None):
         """hnswdev_graph_edge_groups: (int32[n_rows] labels, info dict) -- Index.graph_duplicate_groups on the uploaded rows of

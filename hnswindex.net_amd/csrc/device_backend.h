@@ -130,6 +130,7 @@ struct PredicateCall;    // device_backend.hip: the arguments every KnnQuery wit
 template <class K> struct PredicatePlan; // ... and what its launches need, K the kernel's type
 struct ExactScanArgs;    // dk_exact.h: what one launch of the flat scan reads
 struct ExactDensityPair; // ... a within pair of the density clusters: 16 bytes of the pair arena
+struct SpanEdge;         // dk_span_tree.h: an edge of the spanning forest as the device appends it, 16 bytes
 struct ExactTriangle;    // device_backend.hip: the members and the plan of a scan over the pairs a < b of an id list
 enum class ExactStart;   // device_backend.hip: how a flat-scan call begins -- failed, nothing to measure, ready
 struct ExactScanInput;   // ... the queries and the id list of an ungrouped flat scan
@@ -502,6 +503,14 @@ public:
     // Neither the resident set nor exact_range's pending results are touched.
     bool exact_range_density(long long n_rows, float range, int min_samples, const uint32_t *allow_bits, long long nbits, int *out_labels, int *out_counts,
                              uint64_t *out_info);
+    // hnswdev_exact_span_tree: the minimum spanning forest of exact_range_groups' members.  The weight of a pair
+    // a < b is the distance with the stored row of a as the query; a NaN distance is no edge; edges are ordered by (exact_key's
+    // distance key, a, b), a strict order, so the forest is unique.  out_a[e] < out_b[e], out_dist[e], e < members - components,
+    // ascending in that order; cap: the entries of each array, cap < members - 1 is an error.  out_info: [members, edges,
+    // components, rounds, pairs measured, pairs skipped, launches of the scan kernel, 0].  Boruvka's rounds of span_scan_kernel<M>
+    // over the triangle, at most 65 536 members as the queries of one launch (`span_round`).  Fewer than two members: no launch.
+    // Neither the resident set nor exact_range's pending results are touched.
+    bool exact_span_tree(long long n_rows, const uint32_t *allow_bits, long long nbits, int *out_a, int *out_b, float *out_dist, long long cap, uint64_t *out_info);
     // hnswdev_graph_edge_groups / hnswdev_graph_near_edges: near-duplicates over the EDGES of layer 0 of the
     // committed graph.  The MEMBERS are exact_range_groups' -- the uploaded rows of [0, n_rows) that allow_bits allows -- that are
     // nodes of the graph.  An edge (i, j): i a member, j in i's layer-0 list, j a member (directed); it is within the range when the
@@ -782,7 +791,7 @@ private:
     // what exact_range_groups and exact_range_density share (device_backend.hip): the members listed, the plan of the triangle's
     // scans and their buffers; then one scan of the triangle, a timed launch per round of members
     bool exact_triangle_begin(const char *who, long long n_rows, const uint32_t *allow_bits, long long nbits, ExactTriangle *t);
-    bool exact_triangle_ready(const char *who, ExactTriangle *t);
+    bool exact_triangle_ready(const char *who, ExactTriangle *t, const char *round_knob = "exact_union_round");
     template <class Launch> // launch(args, tiles, stream) -> hipError_t: the scan with the call's sink, its queries' ids in x_self_
     bool exact_triangle_scan(const ExactTriangle &t, Launch &&launch, unsigned long long *measured);
     // the ending of exact_range_groups and graph_edges_run: parent[] -> labels, out; the groups and n_ctr counter words into out_info[1 ..]
@@ -790,6 +799,13 @@ private:
     DevBuf<int> x_dcounts_;               // exact_range_density: within pairs per id, -1 off the members
     DevBuf<unsigned long long> x_dattach_; // ... per id: the smallest (distance, core id) key offered to a member that is not core
     DevBuf<ExactDensityPair> x_darena_;   // ... phase A's within pairs: 2^24 records (256 MiB) unless `density_pair_cap` says otherwise
+    // exact_span_tree's rounds (device_backend.hip): parent[] and the labels are x_uparent_'s, the counters x_upairs_'s
+    bool exact_span_tree_run(const ExactTriangle &t, std::vector<SpanEdge> &edges, uint64_t *out_info);
+    DevBuf<unsigned long long> x_sbest_;  // exact_span_tree: per id, the smallest (distance, other id) key of the round
+    DevBuf<unsigned long long> x_sedge_;  // ... per component (its root's slot): the lightest outgoing edge as lo << 32 | hi
+    DevBuf<unsigned> x_sweight_;          // ... per component: that edge's distance key
+    DevBuf<int> x_sseg_;                  // ... per kExactIterRows entries of the member list: their one label, or -1
+    DevBuf<SpanEdge> x_sedges_;           // ... the forest's edges in the order the rounds found them: members - 1 at the most
     bool exact_range_finish(ExactRangeWork &w, int ns, const unsigned *c, const long long *seg, const int *sq, const long long *obase, size_t base,
                             bool counts_on_device, uint64_t *by_device, uint64_t *by_host);
     DevBuf<unsigned long long> x_rarena_; // exact_range: the round's keys, a segment per query: at most 1 GiB, grown on demand and kept

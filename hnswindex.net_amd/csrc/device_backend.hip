@@ -50,6 +50,7 @@
 #define HNSW_HOST_TU
 #include "device_kernels.h"
 #include "dk_exact.h"
+#include "dk_span_tree.h"
 #include "dk_graph_info.h"
 #include "dk_graph_reach.h"
 #include "dk_graph_repair.h"
@@ -4963,11 +4964,11 @@ bool Device::exact_triangle_begin(const char *who, long long n_rows, const uint3
 
 // Two members or more: the context bound, the round, the tile and the chunks, the query buffers, the members' ids in x_ids_ (enqueued:
 // the caller synchronises behind its own initialisation, before the first scan uses the pinned stage again).
-bool Device::exact_triangle_ready(const char *who, ExactTriangle *t)
+bool Device::exact_triangle_ready(const char *who, ExactTriangle *t, const char *round_knob)
 {
     if (!bind()) return false;
     const long long m = t->m;
-    const int forced_round = diag("exact_union_round", 0);
+    const int forced_round = diag(round_knob, 0);
     t->round = std::min<long long>(m, forced_round > 0 ? forced_round : 65536);
     ExactPlan &p = t->p;
     p = exact_plan((int)t->round, m, 1, pitch_, num_cu_); // the tile as for lists of one key: these sinks keep none
@@ -5136,6 +5137,88 @@ bool Device::exact_range_density(long long n_rows, float range, int min_samples,
     out_info[5] = pairs_within;
     out_info[6] = measured;
     out_info[7] = scans;
+    return true;
+}
+
+// ---- the minimum spanning forest of the members ---------------------------------------------------------------------
+// Boruvka's rounds around exact_range_groups' loop: the members go up once; a round resets the keys and the component tables
+// (span_reset_kernel, which also writes the segments' labels), scans the triangle with span_scan_kernel -- a timed, counted launch per
+// `span_round` (65 536) members, as every scan of the triangle -- and then lets every component take its lightest outgoing edge
+// (span_weight / span_edge / span_join) and relabels (exact_union_labels_kernel: labels are roots, which are smallest ids).  Eight
+// bytes come back per round: the edge cursor.  The rounds end when the forest has members - 1 edges, or when a round joined nothing
+// (what is left apart has only NaN distances between it); the components at least halve per round, so 32 rounds are never reached.
+constexpr int kSpanMaxRounds = 32;
+bool Device::exact_span_tree_run(const ExactTriangle &t, std::vector<SpanEdge> &edges, uint64_t *out_info)
+{
+    const char *who = "exact_span_tree";
+    const long long n = t.n, m = t.m;
+    const size_t lds = span_scan_lds(t.p.qtile, t.p.piece, pitch_), n_seg = (size_t)((m + kExactIterRows - 1) / kExactIterRows);
+    if (lds > 64 * 1024) { set_dev_error(std::string(who) + ": tile exceeds the LDS budget"); return false; }
+    if (!x_uparent_.grow(2 * (size_t)n) || !x_upairs_.grow(2) || !x_sbest_.grow((size_t)n) || !x_sedge_.grow((size_t)n) || !x_sweight_.grow((size_t)n) ||
+        !x_sseg_.grow(n_seg) || !x_sedges_.grow((size_t)(m - 1)))
+        return false;
+    hipStream_t st = S(stream_);
+    int *d_labels = x_uparent_.get() + n;
+    unsigned long long *d_skipped = x_upairs_.get(), *d_cursor = x_upairs_.get() + 1;
+    HIP_OK(exact_union_init_launch(x_ids_, m, x_uparent_, n, st));
+    HIP_OK(exact_union_labels_launch(x_uparent_, n, d_labels, st));
+    HIP_OK(hipMemsetAsync(x_upairs_, 0, 2 * sizeof(unsigned long long), st));
+    HIP_OK(hipStreamSynchronize(st)); // the pinned stage is used again by the rounds
+    unsigned long long measured = 0, skipped = 0, launches = 0, n_edges = 0, rounds = 0;
+    while (n_edges < (unsigned long long)(m - 1)) {
+        if (rounds == (unsigned long long)kSpanMaxRounds) { set_dev_error(std::string(who) + ": more than " + std::to_string(kSpanMaxRounds) + " rounds"); return false; }
+        HIP_OK(span_reset_launch(x_ids_, m, d_labels, x_sbest_, x_sweight_, x_sedge_, x_sseg_, st));
+        long long q_off = 0; // the launches of a scan take the member list's pieces in order: where this one's queries begin
+        const auto launch = [&](const ExactScanArgs &a, unsigned tiles, hipStream_t s) {
+            const SpanScanArgs sa{d_labels, x_sbest_, x_sseg_, q_off, d_skipped};
+            q_off += a.nq;
+            launches += 1;
+            hipError_t e = hipSuccess;
+            with_metric(metric_, [&](auto mt) { e = span_scan_launch<mt>(a, sa, tiles, lds, s); });
+            return e;
+        };
+        if (!exact_triangle_scan(t, launch, &measured)) return false;
+        rounds += 1;
+        HIP_OK(span_join_launch(x_ids_, m, d_labels, x_sbest_, x_sweight_, x_sedge_, x_uparent_, x_sedges_, (unsigned long long)(m - 1), d_cursor, st));
+        HIP_OK(exact_union_labels_launch(x_uparent_, n, d_labels, st));
+        unsigned long long now = 0;
+        if (!exact_copy_out(&now, d_cursor, 8)) return false;
+        if (now > (unsigned long long)(m - 1)) { set_dev_error(std::string(who) + ": the rounds wrote more edges than a forest has"); return false; }
+        if (now == n_edges) break; // a forest: nothing is left to join
+        n_edges = now;
+    }
+    edges.resize((size_t)n_edges);
+    if (!exact_copy_out(edges.data(), x_sedges_, sizeof(SpanEdge) * (size_t)n_edges) || !exact_copy_out(&skipped, d_skipped, 8)) return false;
+    out_info[1] = n_edges; out_info[2] = (unsigned long long)m - n_edges; out_info[3] = rounds;
+    out_info[4] = measured; out_info[5] = skipped; out_info[6] = launches;
+    return true;
+}
+
+bool Device::exact_span_tree(long long n_rows, const uint32_t *allow_bits, long long nbits, int *out_a, int *out_b, float *out_dist, long long cap, uint64_t *out_info)
+{
+    const char *who = "exact_span_tree";
+    if (!out_info) { set_dev_error(std::string(who) + ": bad argument"); return false; }
+    ExactTriangle t;
+    if (!exact_triangle_begin(who, n_rows, allow_bits, nbits, &t)) return false;
+    for (int i = 0; i < 8; ++i) out_info[i] = 0;
+    const long long m = t.m;
+    out_info[0] = (unsigned long long)m;
+    out_info[2] = (unsigned long long)m; // every member is a component of its own until an edge joins it
+    if (m < 2) return true; // nothing to measure: no launch
+    if (cap < m - 1) { set_dev_error(std::string(who) + ": cap = " + std::to_string(cap) + " is below members - 1 = " + std::to_string(m - 1)); return false; }
+    if (!out_a || !out_b || !out_dist) { set_dev_error(std::string(who) + ": bad argument"); return false; }
+    if (!exact_triangle_ready(who, &t, "span_round")) return false;
+    std::vector<SpanEdge> edges;
+    if (!exact_span_tree_run(t, edges, out_info)) return false;
+    // the contract's order: (distance key, a, b) -- the rounds found the edges in another
+    std::sort(edges.begin(), edges.end(), [](const SpanEdge &x, const SpanEdge &y) {
+        return x.dkey != y.dkey ? x.dkey < y.dkey : x.a != y.a ? x.a < y.a : x.b < y.b;
+    });
+    for (size_t e = 0; e < edges.size(); ++e) {
+        out_a[e] = edges[e].a;
+        out_b[e] = edges[e].b;
+        out_dist[e] = exact_host_key_dist((unsigned long long)edges[e].dkey << 32);
+    }
     return true;
 }
 
@@ -5568,6 +5651,12 @@ DEV_API int hnswdev_exact_range_density(void *ctx, long long n_rows, float range
 {
     CTX_OR_FAIL();
     return d->exact_range_density(n_rows, range, min_samples, allow_bits, nbits, out_labels, out_counts, out_info) ? 0 : -1;
+}
+DEV_API int hnswdev_exact_span_tree(void *ctx, long long n_rows, const uint32_t *allow_words, long long nbits, int *out_a, int *out_b, float *out_dist,
+                                    long long cap, uint64_t *out_info)
+{
+    CTX_OR_FAIL();
+    return d->exact_span_tree(n_rows, allow_words, nbits, out_a, out_b, out_dist, cap, out_info) ? 0 : -1;
 }
 DEV_API int hnswdev_graph_edge_groups(void *ctx, long long n_rows, float range, const uint32_t *allow_bits, long long nbits, int *out_labels,
                                       uint64_t *out_info)

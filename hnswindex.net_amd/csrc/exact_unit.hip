@@ -11,6 +11,7 @@
 #define HNSW_EXACT_UNIT
 #include "dk_exact.h"
 #include "dk_graph_repair.h"
+#include "dk_span_tree.h" // span_scan_kernel: a kernel of its own over the scan's triangle, no sink; its round kernels sit with the common ones
 
 namespace hnsw {
 constexpr int kUnitMetric = HNSW_UNIT_METRIC_ID;
@@ -19,4 +20,5 @@ static_assert(kUnitMetric >= 0, "HNSW_UNIT_METRIC is no tag of HNSW_FOR_EACH_MET
 HNSW_FOR_EACH_EXACT_SINK(HNSW_EXACT_SINK_UNIT)
 #undef HNSW_EXACT_SINK_UNIT
 template hipError_t graph_repair_propose_launch<kUnitMetric>(const RepairProposeArgs &, unsigned, hipStream_t);
+template hipError_t span_scan_launch<kUnitMetric>(const ExactScanArgs &, const SpanScanArgs &, unsigned, size_t, hipStream_t);
 } // namespace hnsw

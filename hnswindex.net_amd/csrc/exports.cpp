@@ -541,6 +541,21 @@ API int hnsw_mi355x_density_clusters(void *handle, float range, int min_samples,
     return 0;
 }
 
+// The single-linkage dendrogram of the live, allowed ids as its minimum spanning forest: every radius of
+// hnsw_mi355x_duplicate_groups is a cut of it.  Boruvka's rounds on the device.  Exclusive: it uses the scan's buffers.
+API int hnsw_mi355x_single_linkage_tree(void *handle, const uint32_t *allow_words, long long nbits, int *out_a, int *out_b, float *out_dist, long long cap,
+                                        uint64_t *out_info)
+{
+    if (out_info) for (int i = 0; i < 8; ++i) out_info[i] = 0;
+    if (!handle) return 0;
+    if (!out_info) { set_error("System.ArgumentNullException: hnsw_mi355x_single_linkage_tree: out_info"); return -1; }
+    if (allow_words && nbits < 0) { set_error("System.ArgumentException: hnsw_mi355x_single_linkage_tree: nbits must be >= 0"); return -1; }
+    LOCK_INDEX(handle);
+    std::string err;
+    if (static_cast<HnswIndex *>(handle)->single_linkage_tree(allow_words, nbits, out_a, out_b, out_dist, cap, out_info, err) < 0) { set_error(err); return -1; }
+    return 0;
+}
+
 // Near-duplicates over the graph's edges: hnsw_mi355x_duplicate_groups' members and label convention, joined along
 // the layer-0 edges within `range`; and those edges themselves, counted and kept by the first call and fetched by the second, as
 // hnswdev_exact_range / hnswdev_exact_range_results do it.  Exclusive: they use the scan's query buffer and bring the mirror up to date.

@@ -2179,6 +2179,34 @@ int HnswIndex::density_clusters(float range, int min_samples, const uint32_t *al
     return 0;
 }
 
+// The minimum spanning forest: duplicate_groups' members, counted here so that the caller's arrays are checked
+// against members - 1 before anything is launched; the edges come back from the device in the contract's order.
+int HnswIndex::single_linkage_tree(const uint32_t *allow_bits, long long nbits, int *out_a, int *out_b, float *out_dist, long long cap, uint64_t *out_info,
+                                   std::string &err)
+{
+    const char *who = "hnsw_mi355x_single_linkage_tree";
+    for (int i = 0; i < 8; ++i) out_info[i] = 0;
+    if (failed(err)) return -1;
+    if (graph_.length <= 0 || graph_.count <= 0) return 0; // no member, and nothing needs the device
+    std::vector<uint32_t> live;
+    const long long length = exact_candidates(allow_bits, nbits, live);
+    long long members = length;
+    if (allow_bits) {
+        members = 0;
+        for (long long id = 0, n = std::min(nbits, length); id < n; ++id) members += (allow_bits[id >> 5] >> (id & 31)) & 1u;
+    }
+    if (members >= 2 && cap < members - 1) {
+        err = std::string("System.ArgumentException: ") + who + ": cap = " + std::to_string(cap) + " is below members - 1 = " + std::to_string(members - 1);
+        return -1;
+    }
+    if (members >= 2 && (!out_a || !out_b || !out_dist)) {
+        err = std::string("System.ArgumentNullException: ") + who + ": " + (!out_a ? "out_a" : !out_b ? "out_b" : "out_dist");
+        return -1;
+    }
+    if (!dev_->exact_span_tree(length, allow_bits, nbits, out_a, out_b, out_dist, cap, out_info)) { err = get_dev_error(); return -1; }
+    return 0;
+}
+
 // The duplicate groups over the graph's edges: duplicate_groups' members and labels; what joins two members is a
 // layer-0 edge of the mirror within the range.
 int HnswIndex::graph_duplicate_groups(float range, const uint32_t *allow_bits, long long nbits, int *out_labels, long long cap, uint64_t *out_info, std::string &err)

@@ -103,6 +103,9 @@ public:
     // out_counts[0, length) and, where given, out_labels[0, length), cap >= length; out_labels == nullptr: the neighbour counts alone.
     int density_clusters(float range, int min_samples, const uint32_t *allow_bits, long long nbits, int *out_labels, int *out_counts, long long cap,
                          uint64_t *out_info, std::string &err);
+    // hnsw_mi355x_single_linkage_tree: the minimum spanning forest of duplicate_groups' members
+    // (Device::exact_span_tree); out_a / out_b / out_dist hold members - components edges, cap >= members - 1.
+    int single_linkage_tree(const uint32_t *allow_bits, long long nbits, int *out_a, int *out_b, float *out_dist, long long cap, uint64_t *out_info, std::string &err);
     // hnsw_mi355x_graph_duplicate_groups / hnsw_mi355x_near_edges: duplicate_groups' members, joined along the
     // within-edges of layer 0 of the graph mirror (Device::graph_edge_groups / graph_near_edges), which is brought up to date first
     // (sync_graph) as for get_info.  On the primary context; liveness and allow_bits go down as one bitset.  out_labels[0, length),

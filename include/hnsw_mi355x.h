@@ -504,6 +504,18 @@ int hnsw_mi355x_duplicate_groups(void *handle, float range, const uint32_t *allo
  * NULL handle: 0, out_info zeroed.  NULL out_info, or NULL out_counts with length > 0: -1. */
 int hnsw_mi355x_density_clusters(void *handle, float range, int min_samples, const uint32_t *allow_bits, long long nbits, int *out_labels, int *out_counts,
                                  long long cap, uint64_t out_info[8]);
+/* hnsw_mi355x_single_linkage_tree: the single-linkage dendrogram of the members of hnsw_mi355x_duplicate_groups, as
+ * its minimum spanning forest -- every radius of that call is a cut of it.  The WEIGHT of members a < b is the distance with the
+ * stored row of a as the query and row b as the candidate: the bits hnsw_mi355x_duplicate_groups compares with its range.  A pair
+ * whose distance is NaN is no edge; +inf is an ordinary weight.  Edges are ordered by (distance, a, b) with -0 equal to +0 and
+ * numbers ordered as floats: a strict order, so the forest is unique whatever order the device works in.  out_a[e] < out_b[e] and
+ * out_dist[e] (a -0 weight reads +0), e < members - components, ascending in that order.  cap: the entries of each of the three
+ * arrays; cap < members - 1, or a NULL array with two members or more: -1 with a message.  out_info[0] members, [1] edges,
+ * [2] components, [3] Boruvka rounds, [4] pairs measured, [5] pairs of the triangle not measured because both ends already shared a
+ * component ([4] + [5] = rounds x m (m - 1) / 2), [6] launches of the scan kernel, [7] 0.  Fewer than two members launch nothing.
+ * NULL handle: 0, out_info zeroed.  NULL out_info, or allow_words with nbits < 0: -1. */
+int hnsw_mi355x_single_linkage_tree(void *handle, const uint32_t *allow_words, long long nbits, int *out_a, int *out_b, float *out_dist, long long cap,
+                                    uint64_t out_info[8]);
 /* NEAR-DUPLICATES OVER THE GRAPH'S EDGES: the question of the two calls above asked of layer 0 of the index's graph
  * instead of every pair -- n x (at most 2 MaxEdges) distances instead of m (m - 1) / 2.  The MEMBERS are those of
  * hnsw_mi355x_duplicate_groups.  An EDGE is a pair (i, j): i a member, j in i's layer-0 list, j a member; it is directed (j listing i
@@ -940,6 +952,11 @@ int hnswdev_exact_range_groups(void *ctx, long long n_rows, float range, const u
  * message.  Neither the resident set nor what hnswdev_exact_range_results has pending is touched. */
 int hnswdev_exact_range_density(void *ctx, long long n_rows, float range, int min_samples, const uint32_t *allow_bits, long long nbits, int *out_labels,
                                 int *out_counts, uint64_t out_info[8]);
+/* The rounds behind hnsw_mi355x_single_linkage_tree (span_scan_kernel): the members are the uploaded rows [0, n_rows) that allow_words
+ * allows; out_a / out_b / out_dist have cap entries each, cap >= members - 1; out_info as there.  A NULL context: -1, nothing
+ * written.  Neither the resident set nor what hnswdev_exact_range_results has pending is touched. */
+int hnswdev_exact_span_tree(void *ctx, long long n_rows, const uint32_t *allow_words, long long nbits, int *out_a, int *out_b, float *out_dist,
+                            long long cap, uint64_t out_info[8]);
 /* The calls behind hnsw_mi355x_graph_duplicate_groups / hnsw_mi355x_near_edges, on the context's own rows and the graph it was given
  * (hnswdev_graph_begin .. _commit): the members are the uploaded rows [0, n_rows) that allow_bits allows and that are nodes of the
  * graph; out_labels has min(n_rows, uploaded rows) entries, out_info as there.  hnswdev_graph_near_edges counts and keeps,
