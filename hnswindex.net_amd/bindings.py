@@ -277,6 +277,11 @@ lib.hnsw_mi355x_exact_window_stats.restype = ct.c_int
 lib.hnsw_mi355x_exact_window_stats.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
 lib.hnsw_mi355x_row_prefilter_stats.restype = ct.c_int
 lib.hnsw_mi355x_row_prefilter_stats.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
+EXACT_PREFILTER_SLOTS = ("launches", "pairs_on_tile", "pairs_remeasured", "reserved")
+lib.hnsw_mi355x_exact_prefilter_stats.restype = ct.c_int
+lib.hnsw_mi355x_exact_prefilter_stats.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
+lib.hnswdev_exact_prefilter_stats.restype = ct.c_int
+lib.hnswdev_exact_prefilter_stats.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
 lib.hnsw_mi355x_row_prefilter_form_stats.restype = ct.c_int
 lib.hnsw_mi355x_row_prefilter_form_stats.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
 lib.hnsw_mi355x_row_prefilter8_stats.restype = ct.c_int
@@ -707,6 +712,14 @@ class Index:
         if not self._h or lib.hnsw_mi355x_row_prefilter_stats(self._h, out) != 0:
             return {"launches": 0, "rows_on_shadow": 0, "rows_reread": 0, "rows_packed": 0}
         return {"launches": int(out[0]), "rows_on_shadow": int(out[1]), "rows_reread": int(out[2]), "rows_packed": int(out[3])}
+
+    def exact_prefilter_stats(self):
+        """Counters of the flat scan's MFMA prefilter (exact_knn_query): scan launches that took the form, pairs its
+        half-precision tile judged, pairs of them then measured exactly, and a reserved 0."""
+        out = (ct.c_uint64 * 4)()
+        if not self._h or lib.hnsw_mi355x_exact_prefilter_stats(self._h, out) != 0:
+            return dict.fromkeys(EXACT_PREFILTER_SLOTS, 0)
+        return dict(zip(EXACT_PREFILTER_SLOTS, (int(v) for v in out)))
 
     def row_prefilter_form_stats(self):
         """Which kernel form the row prefilter's launches took: the one that reads the row length at run time, the one with it compiled in."""
@@ -2078,6 +2091,13 @@ class DeviceBackend:
         self._check(lib.hnswdev_exact_range_results(self._ctx, ids.ctypes.data_as(_I), d.ctypes.data_as(_F)))
         cuts = np.cumsum(counts, dtype=np.int64)[:-1]
         return np.split(ids[:total], cuts), np.split(d[:total], cuts)
+
+    def exact_prefilter_stats(self) -> dict:
+        """hnswdev_exact_prefilter_stats: this context's counters of the flat scan's MFMA prefilter, the slots of
+        Index.exact_prefilter_stats."""
+        out = (ct.c_uint64 * 4)()
+        self._check(lib.hnswdev_exact_prefilter_stats(self._ctx, out))
+        return dict(zip(EXACT_PREFILTER_SLOTS, (int(v) for v in out)))
 
     def set_profiling(self, on: bool):
         self._check(lib.hnswdev_set_profiling(self._ctx, int(on)))

@@ -610,6 +610,8 @@ public:
     // The row prefilter's counters (a view adds to its primary's): launches that ran with it, rows measured on the shadow, rows
     // measured again from f32, shadow rows packed.  All zero on a context that has none (every metric but sq_euclid, diag row_prefilter=0).
     void row_prefilter_stats(uint64_t out[4]);
+    // the flat scan's MFMA prefilter since the context was created: launches, pairs on the tile, pairs measured, 0
+    void exact_prefilter_stats(uint64_t out[4]) const;
     // Which kernel form those launches took: out[0] the run-time-length form (kFormLeanPF), out[1] the fixed-length one (kFormLeanPFFixed).
     void row_prefilter_form_stats(uint64_t out[2]);
     // The shadow as it stands, read only (nothing is packed or allocated): out[0] the watermark (shadow rows [0, out[0]) are current),
@@ -755,6 +757,8 @@ private:
     DevBuf<long long> x_boff_;          // ... set bits in front of each block of bitset words
     DevBuf<unsigned long long> x_lists_; // ... the per-(query, chunk) lists of a round: at most 1 GiB, allocated by the first call and kept
     DevBuf<int> x_out_;                 // ... a round's [ids | distances]
+    DevBuf<unsigned long long> x_pfctr_; // ... the MFMA prefilter's two device counters of a launch: pairs on the tile, pairs measured
+    uint64_t xpf_stats_[4] = {0, 0, 0, 0}; // ... and their totals with the launches in front (exact_prefilter_stats)
     DevBuf<unsigned long long> x_evals_; // ... (query, row) pairs the scan kernel measured, counted on the device
     DevBuf<float> x_queries_;           // ... its own query set (set_queries writes it while it stands in for d_queries_)
     DevBuf<double> x_q_sn_;

@@ -50,6 +50,7 @@
 #define HNSW_HOST_TU
 #include "device_kernels.h"
 #include "dk_exact.h"
+#include "dk_exact_mfma.h"
 #include "dk_span_tree.h"
 #include "dk_graph_info.h"
 #include "dk_graph_reach.h"
@@ -3199,6 +3200,33 @@ static ExactPlan exact_plan(int nq, long long m, int k, int pitch, int num_cu, i
     return p;
 }
 
+// Whether a plain top-k scan takes the MFMA-prefilter form (exact_scan_pf_kernel, dk_exact_mfma.h), and its plan: a
+// tile of kExactPfQTile queries staged whole, chunks by exact_plan's rule.  diag exact_prefilter: 0 never; 2 wherever the form is
+// built (the metric, dim % 32 == 0 within its limits, k up to what its LDS holds; `exact_chunk` still sets the rows of a chunk);
+// 1, the default: there, when neither `exact_chunk` nor `exact_qtile` is forced, k <= kExactPfPickerMaxK and the call has
+// kExactPfMinQueries queries, kExactPfMinRows candidates and kExactPfMinPairs pairs of them -- where the A/B found it ahead.
+static bool exact_pf_plan(int metric, int nq, long long m, int k, int pitch, int num_cu, ExactPlan *p)
+{
+    const int mode = diag("exact_prefilter", 1);
+    if (mode <= 0 || !exact_pf_metric(metric) || !exact_pf_dim(pitch) || k > exact_pf_max_k(pitch)) return false;
+    const long long forced_c = diag("exact_chunk", 0);
+    if (mode == 1 && (forced_c > 0 || diag("exact_qtile", 0) > 0 || nq < kExactPfMinQueries || m < kExactPfMinRows ||
+                      (long long)nq * m < kExactPfMinPairs || k > kExactPfPickerMaxK)) return false;
+    p->qtile = kExactPfQTile; p->piece = pitch;
+    p->lds = exact_pf_lds(pitch, k);
+    const long long tiles = (std::min<long long>(nq, 65536) + p->qtile - 1) / p->qtile;
+    long long chunks = forced_c > 0 ? (m + forced_c - 1) / forced_c : std::max<long long>(1, std::min<long long>((2LL * num_cu + tiles - 1) / tiles, m / 1024));
+    chunks = std::min<long long>(chunks, kExactMaxChunks);
+    p->chunk = (m + chunks - 1) / chunks;
+    if (forced_c <= 0) p->chunk = (p->chunk + kExactIterRows - 1) / kExactIterRows * kExactIterRows;
+    p->n_chunks = (int)((m + p->chunk - 1) / p->chunk);
+    const long long by_lists = (1LL << 30) / ((long long)p->n_chunks * k * 8), by_out = (1LL << 24) / k;
+    p->round = std::max<long long>(1, std::min<long long>({(long long)nq, by_lists, by_out}));
+    return true;
+}
+
+void Device::exact_prefilter_stats(uint64_t out[4]) const { std::copy_n(xpf_stats_, 4, out); }
+
 // The queries of a flat scan: the resident set, or the scan's own -- uploaded by set_queries (the one staging path: pinned copy,
 // int8 quantisation, cosine norms) while the scan's buffers stand in for the resident set's, which is then put back untouched.
 bool Device::exact_queries(const char *who, const float *queries, int nq, const float **d_q, const double **d_qsn)
@@ -3379,12 +3407,14 @@ bool Device::exact_knn_rounds(const float *d_q, const double *d_qsn, int nq, con
                               const int *d_self, const ExactCollapseArgs *collapse)
 {
     hipStream_t st = S(stream_);
-    const ExactPlan p = exact_plan(nq, m, k, pitch_, num_cu_, collapse ? kExactCollapseEntryBytes : kExactKeyBytes);
+    ExactPlan p;
+    const bool pf = !d_keep_ids && !d_self && !collapse && exact_pf_plan(metric_, nq, m, k, pitch_, num_cu_, &p); // the plain sink of exact_knn alone
+    if (!pf) p = exact_plan(nq, m, k, pitch_, num_cu_, collapse ? kExactCollapseEntryBytes : kExactKeyBytes);
     if (p.lds > 64 * 1024) { set_dev_error("exact_knn: tile exceeds the LDS budget"); return false; }
-    if (!x_lists_.grow((size_t)p.round * p.n_chunks * k) || !x_out_.grow(2 * (size_t)p.round * k)) return false;
-    char *hs = static_cast<char *>(pinned_stage(8 * (size_t)p.round * k + 8));
+    if (!x_lists_.grow((size_t)p.round * p.n_chunks * k) || !x_out_.grow(2 * (size_t)p.round * k) || (pf && !x_pfctr_.grow(2))) return false;
+    char *hs = static_cast<char *>(pinned_stage(8 * (size_t)p.round * k + 24));
     if (!hs) return false;
-    unsigned long long *h_ev = reinterpret_cast<unsigned long long *>(hs + 8 * (size_t)p.round * k);
+    unsigned long long *h_ev = reinterpret_cast<unsigned long long *>(hs + 8 * (size_t)p.round * k); // [0]: the pairs; [1], [2]: the prefilter's two
     for (long long off = 0; off < nq; off += p.round) {
         const int nr = (int)std::min<long long>(p.round, nq - off);
         ExactScanArgs a;
@@ -3401,7 +3431,12 @@ bool Device::exact_knn_rounds(const float *d_q, const double *d_qsn, int nq, con
                 HIP_OK(exact_merge_collapsed_launch(x_lists_, p.n_chunks, k, nr, sink.row_group, sink.per_group, sink.info, d_ids, d_d, st));
                 return true;
             }
-            if (d_self) HIP_OK(exact_scan_enqueue(metric_, a, ExactTopKSelf{d_self + off}, tiles, p.lds, st));
+            if (pf) {
+                HIP_OK(hipMemsetAsync(x_pfctr_, 0, 2 * sizeof(unsigned long long), st));
+                hipError_t e = hipSuccess;
+                with_metric(metric_, [&](auto mt) { e = exact_scan_pf_launch<mt>(a, x_pfctr_, tiles, p.lds, st); });
+                HIP_OK(e);
+            } else if (d_self) HIP_OK(exact_scan_enqueue(metric_, a, ExactTopKSelf{d_self + off}, tiles, p.lds, st));
             else HIP_OK(exact_scan_enqueue(metric_, a, ExactTopK{}, tiles, p.lds, st));
             HIP_OK(exact_merge_launch(x_lists_, p.n_chunks, k, nr, d_ids, d_d, st));
             return true;
@@ -3410,9 +3445,11 @@ bool Device::exact_knn_rounds(const float *d_q, const double *d_qsn, int nq, con
             HIP_OK(hipMemcpyAsync(hs, d_ids, res, hipMemcpyDeviceToHost, st));
             HIP_OK(hipMemcpyAsync(hs + 4u * (size_t)p.round * k, d_d, res, hipMemcpyDeviceToHost, st));
             if (d_keep_ids) HIP_OK(hipMemcpyAsync(d_keep_ids + (size_t)off * k, d_ids, res, hipMemcpyDeviceToDevice, st));
+            if (pf) HIP_OK(hipMemcpyAsync(h_ev + 1, x_pfctr_, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
             return true;
         };
         if (!exact_timed_scan(h_ev, enqueue, fetch)) return false;
+        if (pf) { xpf_stats_[0] += 1; xpf_stats_[1] += h_ev[1]; xpf_stats_[2] += h_ev[2]; }
         memcpy(out_ids + (size_t)off * k, hs, res);
         if (out_d) memcpy(out_d + (size_t)off * k, hs + 4u * (size_t)p.round * k, res);
     }
@@ -5752,6 +5789,15 @@ DEV_API int hnswdev_get_stats(void *ctx, hnswdev_stats *out)
     return 0;
 }
 DEV_API int hnswdev_reset_stats(void *ctx) { CTX_OR_FAIL(); d->reset_stats(); return 0; }
+// The counters of the flat scan's MFMA prefilter since the context was created: launches that took the form, pairs
+// the tile judged, pairs of them measured exactly, 0.  Hand-written like the row prefilter's getter: it belongs to no counter block.
+DEV_API int hnswdev_exact_prefilter_stats(void *ctx, uint64_t out[4])
+{
+    CTX_OR_FAIL();
+    if (!out) return -1;
+    d->exact_prefilter_stats(out);
+    return 0;
+}
 // The getters of the counter blocks, hnswdev_<block>(ctx, out[slots]), one per row of counter_blocks.h
 #define HNSW_COUNTER_GETTER(NAME, SCOPE, ...)                   \
     DEV_API int hnswdev_##NAME(void *ctx, uint64_t *out)        \

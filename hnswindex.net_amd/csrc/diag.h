@@ -20,6 +20,8 @@
 //       graph_unchecked [0]  row_prefilter [1 = the library chooses the shadow width; 0 = off, nothing allocated;
 //       2 = the f16 forms, kept on after a launch that re-read most rows; 3 = the 8-bit form, where built (row length 128), kept on likewise]
 //       pf_fixed_dim [1; 0 = the row prefilter's run-time-length kernel form also where the row length is the compiled-in one]
+//       exact_prefilter [1 = the picker decides whether exact_knn's plain scan runs behind the f16 MFMA tile; 0 = never;
+//       2 = wherever that form is built (sq_euclid / sq_euclid_f16, dim % 32 == 0 in [64, 256], k within its LDS), any nq and m]
 #pragma once
 #include <cstdlib>
 #include <cstring>

@@ -11,6 +11,7 @@
 #define HNSW_EXACT_UNIT
 #include "dk_exact.h"
 #include "dk_graph_repair.h"
+#include "dk_exact_mfma.h" // exact_scan_pf_kernel: the plain top-k scan behind an f16 MFMA tile; a kernel of its own, no sink
 #include "dk_span_tree.h" // span_scan_kernel: a kernel of its own over the scan's triangle, no sink; its round kernels sit with the common ones
 
 namespace hnsw {
@@ -21,4 +22,5 @@ HNSW_FOR_EACH_EXACT_SINK(HNSW_EXACT_SINK_UNIT)
 #undef HNSW_EXACT_SINK_UNIT
 template hipError_t graph_repair_propose_launch<kUnitMetric>(const RepairProposeArgs &, unsigned, hipStream_t);
 template hipError_t span_scan_launch<kUnitMetric>(const ExactScanArgs &, const SpanScanArgs &, unsigned, size_t, hipStream_t);
+template hipError_t exact_scan_pf_launch<kUnitMetric>(const ExactScanArgs &, unsigned long long *, unsigned, size_t, hipStream_t); // a kernel for sq and sqh, an error for the rest
 } // namespace hnsw

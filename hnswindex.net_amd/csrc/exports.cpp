@@ -820,6 +820,14 @@ API int hnsw_mi355x_row_prefilter_stats(void *h, uint64_t out[4])
     static_cast<HnswIndex *>(h)->row_prefilter_stats(out);
     return 0;
 }
+// The flat scan's MFMA prefilter: launches that took the form, pairs its tile judged, pairs of them measured, 0
+API int hnsw_mi355x_exact_prefilter_stats(void *h, uint64_t out[4])
+{
+    if (!h || !out) return -1;
+    LOCK_INDEX(h);
+    static_cast<HnswIndex *>(h)->exact_prefilter_stats(out);
+    return 0;
+}
 API int hnsw_mi355x_row_prefilter_form_stats(void *h, uint64_t out[2])
 {
     if (!h || !out) return -1;
