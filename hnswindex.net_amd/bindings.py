@@ -282,6 +282,10 @@ lib.hnsw_mi355x_exact_prefilter_stats.restype = ct.c_int
 lib.hnsw_mi355x_exact_prefilter_stats.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
 lib.hnswdev_exact_prefilter_stats.restype = ct.c_int
 lib.hnswdev_exact_prefilter_stats.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
+lib.hnsw_mi355x_triangle_prefilter_stats.restype = ct.c_int
+lib.hnsw_mi355x_triangle_prefilter_stats.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
+lib.hnswdev_triangle_prefilter_stats.restype = ct.c_int
+lib.hnswdev_triangle_prefilter_stats.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
 lib.hnsw_mi355x_row_prefilter_form_stats.restype = ct.c_int
 lib.hnsw_mi355x_row_prefilter_form_stats.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
 lib.hnsw_mi355x_row_prefilter8_stats.restype = ct.c_int
@@ -718,6 +722,14 @@ class Index:
         half-precision tile judged, pairs of them then measured exactly, and a reserved 0."""
         out = (ct.c_uint64 * 4)()
         if not self._h or lib.hnsw_mi355x_exact_prefilter_stats(self._h, out) != 0:
+            return dict.fromkeys(EXACT_PREFILTER_SLOTS, 0)
+        return dict(zip(EXACT_PREFILTER_SLOTS, (int(v) for v in out)))
+
+    def triangle_prefilter_stats(self):
+        """Counters of the same tile in front of duplicate_groups, neighbor_counts and density_clusters: scan
+        launches that took the form, pairs its half-precision tile judged, pairs of them then measured exactly, and a reserved 0."""
+        out = (ct.c_uint64 * 4)()
+        if not self._h or lib.hnsw_mi355x_triangle_prefilter_stats(self._h, out) != 0:
             return dict.fromkeys(EXACT_PREFILTER_SLOTS, 0)
         return dict(zip(EXACT_PREFILTER_SLOTS, (int(v) for v in out)))
 
@@ -2097,6 +2109,13 @@ class DeviceBackend:
         Index.exact_prefilter_stats."""
         out = (ct.c_uint64 * 4)()
         self._check(lib.hnswdev_exact_prefilter_stats(self._ctx, out))
+        return dict(zip(EXACT_PREFILTER_SLOTS, (int(v) for v in out)))
+
+    def triangle_prefilter_stats(self) -> dict:
+        """hnswdev_triangle_prefilter_stats: this context's counters of the MFMA prefilter of exact_range_groups and
+        exact_range_density, the slots of Index.triangle_prefilter_stats."""
+        out = (ct.c_uint64 * 4)()
+        self._check(lib.hnswdev_triangle_prefilter_stats(self._ctx, out))
         return dict(zip(EXACT_PREFILTER_SLOTS, (int(v) for v in out)))
 
     def set_profiling(self, on: bool):

@@ -612,6 +612,8 @@ public:
     void row_prefilter_stats(uint64_t out[4]);
     // the flat scan's MFMA prefilter since the context was created: launches, pairs on the tile, pairs measured, 0
     void exact_prefilter_stats(uint64_t out[4]) const;
+    // ... and the same tile in front of the fixed-radius triangle scans, in the same slots
+    void triangle_prefilter_stats(uint64_t out[4]) const;
     // Which kernel form those launches took: out[0] the run-time-length form (kFormLeanPF), out[1] the fixed-length one (kFormLeanPFFixed).
     void row_prefilter_form_stats(uint64_t out[2]);
     // The shadow as it stands, read only (nothing is packed or allocated): out[0] the watermark (shadow rows [0, out[0]) are current),
@@ -759,6 +761,10 @@ private:
     DevBuf<int> x_out_;                 // ... a round's [ids | distances]
     DevBuf<unsigned long long> x_pfctr_; // ... the MFMA prefilter's two device counters of a launch: pairs on the tile, pairs measured
     uint64_t xpf_stats_[4] = {0, 0, 0, 0}; // ... and their totals with the launches in front (exact_prefilter_stats)
+    DevBuf<unsigned long long> x_tpfctr_; // ... the same two of the triangle scans' form, added up over the launches of a call
+    uint64_t xtpf_stats_[4] = {0, 0, 0, 0}; // ... and their totals (triangle_prefilter_stats)
+    bool exact_tri_pf_reset();
+    bool exact_tri_pf_collect(unsigned long long launches);
     DevBuf<unsigned long long> x_evals_; // ... (query, row) pairs the scan kernel measured, counted on the device
     DevBuf<float> x_queries_;           // ... its own query set (set_queries writes it while it stands in for d_queries_)
     DevBuf<double> x_q_sn_;

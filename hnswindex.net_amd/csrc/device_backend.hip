@@ -51,6 +51,7 @@
 #include "device_kernels.h"
 #include "dk_exact.h"
 #include "dk_exact_mfma.h"
+#include "dk_exact_tri.h"
 #include "dk_span_tree.h"
 #include "dk_graph_info.h"
 #include "dk_graph_reach.h"
@@ -5051,6 +5052,54 @@ bool Device::exact_triangle_scan(const ExactTriangle &t, Launch &&launch, unsign
     return true;
 }
 
+// Whether a scan of the triangle with one fixed radius takes the MFMA-prefilter form (exact_tri_pf_kernel, dk_exact_tri.h; DESIGN.md
+// 3.35), beside exact_pf_plan, and then its plan in exact_triangle_ready's place: a tile of kExactPfQTile queries staged whole, chunks
+// of about kExactTriPfChunk rows.  diag exact_prefilter: 0 never; 2 wherever the form is built (the metric, dim % 32 == 0 within its
+// limits), at any member count; 1, the default: there, when neither `exact_chunk` nor `exact_qtile` is forced and the scan has `floor`
+// members -- the sink's measured floor.  `exact_chunk` still sets the rows of a chunk (exact_plan's, as *p holds them).
+static bool exact_tri_pf_plan(int metric, long long m, int pitch, long long floor, ExactPlan *p)
+{
+    const int mode = diag("exact_prefilter", 1);
+    if (mode <= 0 || !exact_pf_metric(metric) || !exact_pf_dim(pitch)) return false;
+    const bool forced_c = diag("exact_chunk", 0) > 0;
+    if (mode == 1 && (forced_c || diag("exact_qtile", 0) > 0 || m < floor)) return false;
+    p->qtile = kExactPfQTile; p->piece = pitch;
+    p->lds = exact_tri_pf_lds(pitch);
+    if (!forced_c) {
+        // A block on the diagonal skips the steps below its tile, so the chunk does not decide what is measured in vain: it is chosen
+        // for the blocks it leaves (below the diagonal they cost a launch slot each) and for how often the queries are staged.
+        const long long chunks = std::max<long long>(1, std::min<long long>(m / kExactTriPfChunk, kExactMaxChunks));
+        p->chunk = ((m + chunks - 1) / chunks + kExactIterRows - 1) / kExactIterRows * kExactIterRows;
+        p->n_chunks = (int)((m + p->chunk - 1) / p->chunk);
+    }
+    return true;
+}
+
+void Device::triangle_prefilter_stats(uint64_t out[4]) const { std::copy_n(xtpf_stats_, 4, out); }
+
+// The form's two device counters of a call: zeroed before its first launch (enqueued), added to the totals behind its last
+bool Device::exact_tri_pf_reset()
+{
+    if (!x_tpfctr_.grow(2)) return false;
+    HIP_OK(hipMemsetAsync(x_tpfctr_, 0, 2 * sizeof(unsigned long long), S(stream_)));
+    return true;
+}
+bool Device::exact_tri_pf_collect(unsigned long long launches)
+{
+    uint64_t ctr[2];
+    if (!exact_copy_out(ctr, x_tpfctr_, sizeof ctr)) return false;
+    xtpf_stats_[0] += launches; xtpf_stats_[1] += ctr[0]; xtpf_stats_[2] += ctr[1];
+    return true;
+}
+// exact_tri_pf_launch (dk_exact_tri.h) with the context's metric as its template argument
+template <class SINK>
+static hipError_t exact_tri_pf_enqueue(int metric, const ExactScanArgs &a, const SINK &sink, unsigned long long *ctr, unsigned n_blocks, size_t lds, hipStream_t st)
+{
+    hipError_t e = hipSuccess;
+    with_metric(metric, [&](auto mt) { e = exact_tri_pf_launch<mt>(a, sink, ctr, n_blocks, lds, st); });
+    return e;
+}
+
 bool Device::exact_range_groups(long long n_rows, float range, const uint32_t *allow_bits, long long nbits, int *out_labels, uint64_t *out_info)
 {
     const char *who = "exact_range_groups";
@@ -5066,17 +5115,21 @@ bool Device::exact_range_groups(long long n_rows, float range, const uint32_t *a
     out_info[1] = (unsigned long long)m;
     if (m < 2) return true; // nothing to measure: no launch
     if (!exact_triangle_ready(who, &t)) return false;
+    const bool pf = exact_tri_pf_plan(metric_, m, pitch_, kExactTriPfMinMembersUnion, &t.p);
+    if (pf && !exact_tri_pf_reset()) return false;
     if (!x_uparent_.grow(2 * (size_t)n) || !x_upairs_.grow(1)) return false;
     hipStream_t st = S(stream_);
     HIP_OK(exact_union_init_launch(x_ids_, m, x_uparent_, n, st));
     HIP_OK(hipMemsetAsync(x_upairs_, 0, sizeof(unsigned long long), st));
     HIP_OK(hipStreamSynchronize(st)); // the pinned stage is used again by the rounds
-    unsigned long long measured = 0;
+    unsigned long long measured = 0, pf_launches = 0;
     const auto launch = [&](const ExactScanArgs &a, unsigned tiles, hipStream_t s) {
         const ExactRangeUnion sink{range, x_uparent_, x_self_, x_upairs_}; // (x_self_ as the round's gather left it)
+        if (pf) { ++pf_launches; return exact_tri_pf_enqueue(metric_, a, sink, x_tpfctr_, tiles, t.p.lds, s); }
         return exact_scan_enqueue(metric_, a, sink, tiles, t.p.lds, s);
     };
     if (!exact_triangle_scan(t, launch, &measured)) return false;
+    if (pf && !exact_tri_pf_collect(pf_launches)) return false;
     if (!exact_union_finish(n, members, x_upairs_, 1, out_labels, out_info)) return false;
     out_info[3] = measured;
     return true;
@@ -5135,6 +5188,8 @@ bool Device::exact_range_density(long long n_rows, float range, int min_samples,
         return true;
     }
     if (!exact_triangle_ready(who, &t)) return false;
+    const bool pf = exact_tri_pf_plan(metric_, m, pitch_, kExactTriPfMinMembersDensity, &t.p);
+    if (pf && !exact_tri_pf_reset()) return false;
     hipStream_t st = S(stream_);
     const int forced_cap = diag("density_pair_cap", 0);
     // (no more records than there are pairs: a small member set does not allocate the whole arena)
@@ -5145,11 +5200,12 @@ bool Device::exact_range_density(long long n_rows, float range, int min_samples,
     HIP_OK(density_init_launch(x_ids_, m, x_dcounts_, out_labels ? x_dattach_.get() : nullptr, n, x_upairs_, st));
     if (out_labels) HIP_OK(exact_union_init_launch(x_ids_, m, x_uparent_, n, st));
     HIP_OK(hipStreamSynchronize(st)); // the pinned stage is used again by the rounds
-    const size_t lds_a = exact_density_lds(t.p.qtile, t.p.piece, pitch_);
+    const size_t lds_a = pf ? t.p.lds : exact_density_lds(t.p.qtile, t.p.piece, pitch_);
     if (lds_a > 64 * 1024) { set_dev_error(std::string(who) + ": tile exceeds the LDS budget"); return false; }
-    unsigned long long measured = 0, scans = 1;
+    unsigned long long measured = 0, scans = 1, pf_launches = 0;
     const auto phase_a = [&](const ExactScanArgs &a, unsigned tiles, hipStream_t s) {
         const ExactRangeDensity sink{range, x_self_, x_dcounts_, x_darena_, cap, x_upairs_}; // (x_self_ as the round's gather left it)
+        if (pf) { ++pf_launches; return exact_tri_pf_enqueue(metric_, a, sink, x_tpfctr_, tiles, lds_a, s); }
         return exact_scan_enqueue(metric_, a, sink, tiles, lds_a, s);
     };
     if (!exact_triangle_scan(t, phase_a, &measured)) return false;
@@ -5161,6 +5217,7 @@ bool Device::exact_range_density(long long n_rows, float range, int min_samples,
         } else { // the arena dropped records: the triangle once more, joined straight from the distances
             const auto phase_b = [&](const ExactScanArgs &a, unsigned tiles, hipStream_t s) {
                 const ExactRangeDensityJoin sink{range, x_self_, x_dcounts_, min_samples, x_uparent_, x_dattach_};
+                if (pf) { ++pf_launches; return exact_tri_pf_enqueue(metric_, a, sink, x_tpfctr_, tiles, t.p.lds, s); }
                 return exact_scan_enqueue(metric_, a, sink, tiles, t.p.lds, s);
             };
             if (!exact_triangle_scan(t, phase_b, &measured)) return false;
@@ -5171,6 +5228,7 @@ bool Device::exact_range_density(long long n_rows, float range, int min_samples,
         if (!exact_copy_out(out_labels, d_labels, 4 * (size_t)n)) return false;
         count_kinds();
     }
+    if (pf && !exact_tri_pf_collect(pf_launches)) return false;
     out_info[5] = pairs_within;
     out_info[6] = measured;
     out_info[7] = scans;
@@ -5796,6 +5854,15 @@ DEV_API int hnswdev_exact_prefilter_stats(void *ctx, uint64_t out[4])
     CTX_OR_FAIL();
     if (!out) return -1;
     d->exact_prefilter_stats(out);
+    return 0;
+}
+// ... and of the same tile in front of the fixed-radius triangle scans (hnswdev_exact_range_groups and
+// hnswdev_exact_range_density): launches that took the form, pairs the tile judged, pairs of them measured exactly, 0
+DEV_API int hnswdev_triangle_prefilter_stats(void *ctx, uint64_t out[4])
+{
+    CTX_OR_FAIL();
+    if (!out) return -1;
+    d->triangle_prefilter_stats(out);
     return 0;
 }
 // The getters of the counter blocks, hnswdev_<block>(ctx, out[slots]), one per row of counter_blocks.h

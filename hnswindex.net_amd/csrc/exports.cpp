@@ -828,6 +828,14 @@ API int hnsw_mi355x_exact_prefilter_stats(void *h, uint64_t out[4])
     static_cast<HnswIndex *>(h)->exact_prefilter_stats(out);
     return 0;
 }
+// ... and the same tile in front of duplicate_groups, neighbor_counts and density_clusters, in the same slots
+API int hnsw_mi355x_triangle_prefilter_stats(void *h, uint64_t out[4])
+{
+    if (!h || !out) return -1;
+    LOCK_INDEX(h);
+    static_cast<HnswIndex *>(h)->triangle_prefilter_stats(out);
+    return 0;
+}
 API int hnsw_mi355x_row_prefilter_form_stats(void *h, uint64_t out[2])
 {
     if (!h || !out) return -1;

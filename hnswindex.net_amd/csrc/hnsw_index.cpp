@@ -2658,6 +2658,17 @@ void HnswIndex::exact_prefilter_stats(uint64_t out[4])
     }
 }
 
+void HnswIndex::triangle_prefilter_stats(uint64_t out[4])
+{
+    out[0] = out[1] = out[2] = out[3] = 0;
+    if (dev_) dev_->triangle_prefilter_stats(out);
+    for (auto &r : replicas_) {
+        uint64_t v[4];
+        r->triangle_prefilter_stats(v);
+        for (int i = 0; i < 4; ++i) out[i] += v[i];
+    }
+}
+
 void HnswIndex::row_prefilter_form_stats(uint64_t out[2])
 {
     out[0] = out[1] = 0;

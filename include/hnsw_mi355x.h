@@ -153,6 +153,12 @@ int hnsw_mi355x_row_prefilter_stats(void *handle, uint64_t out[4]);
  * them that were then measured exactly (the others were turned away on a proven lower bound), out[3] reserved, 0.  Ids and distance
  * bits are the plain scan's either way.  All zero where the form does not run. */
 int hnsw_mi355x_exact_prefilter_stats(void *handle, uint64_t out[4]);
+/* Counters of the same tile in front of the fixed-radius triangle scans (duplicate_groups, neighbor_counts and density_clusters on
+ * sq_euclid and sq_euclid_f16 indices) since the index was created: out[0] scan launches that took the form, out[1]
+ * pairs (a < b) its half-precision tile judged -- every pair the call counts as measured --, out[2] pairs of them that were then
+ * measured exactly, out[3] reserved, 0.  Labels, counts and info are the plain scan's either way.  All zero where the form does not
+ * run; hnsw_mi355x_exact_prefilter_stats does not count these launches.  NULL handle or out: -1, nothing written. */
+int hnsw_mi355x_triangle_prefilter_stats(void *handle, uint64_t out[4]);
 /* Which kernel form those launches took: out[0] launches in the form that reads the row length at run time, out[1] launches in the
  * form with the row length compiled in (dim 128; four waves per SIMD).  Both are half-precision forms: a launch on the
  * 8-bit shadow is neither (hnsw_mi355x_row_prefilter8_stats). */
@@ -1039,6 +1045,9 @@ int hnswdev_exact_knn_collapsed(void *ctx, const float *queries, int nq, long lo
                                 int per_group, const uint32_t *allow_bits, long long nbits, int *out_ids, float *out_dists);
 /* out[0 .. 3] as hnsw_mi355x_exact_prefilter_stats, of this context's hnswdev_exact_knn calls since it was created. */
 int hnswdev_exact_prefilter_stats(void *ctx, uint64_t out[4]);
+/* out[0 .. 3] as hnsw_mi355x_triangle_prefilter_stats, of this context's hnswdev_exact_range_groups and hnswdev_exact_range_density
+ * calls since it was created. */
+int hnswdev_triangle_prefilter_stats(void *ctx, uint64_t out[4]);
 /* out[0 .. 3] as hnsw_mi355x_exact_collapsed_info, of this context; zeroed by hnswdev_reset_stats. */
 int hnswdev_exact_collapsed_info(void *ctx, uint64_t out[4]);
 /* out[0 .. 3] as hnsw_mi355x_exact_grouped_info, of this context; zeroed by hnswdev_reset_stats. */
