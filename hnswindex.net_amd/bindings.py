@@ -156,6 +156,9 @@ lib.hnsw_mi355x_density_clusters.argtypes = [ct.c_void_p, ct.c_float, ct.c_int, 
 _DENSITY_INFO = ("members", "clusters", "core", "border", "noise", "pairs_within", "pairs_measured", "scans")   # out_info[0 .. 7] of hnsw_mi355x_density_clusters
 lib.hnsw_mi355x_single_linkage_tree.restype = ct.c_int
 lib.hnsw_mi355x_single_linkage_tree.argtypes = [ct.c_void_p, _U32, ct.c_longlong, _I, _I, _F, ct.c_longlong, ct.POINTER(ct.c_uint64)]
+lib.hnsw_mi355x_mutual_reachability_tree.restype = ct.c_int
+lib.hnsw_mi355x_mutual_reachability_tree.argtypes = [ct.c_void_p, ct.c_int, _U32, ct.c_longlong, _I, _I, _F, ct.c_longlong, _F, ct.c_longlong, ct.POINTER(ct.c_uint64)]
+_MREACH_INFO = ("members", "edges", "components", "rounds", "pairs_measured", "pairs_skipped", "launches", "core_launches")   # out_info[0 .. 7] of hnsw_mi355x_mutual_reachability_tree
 _SPAN_INFO = ("members", "edges", "components", "rounds", "pairs_measured", "pairs_skipped", "launches", "reserved")   # out_info[0 .. 7] of hnsw_mi355x_single_linkage_tree
 lib.hnsw_mi355x_graph_duplicate_groups.restype = ct.c_int
 lib.hnsw_mi355x_graph_duplicate_groups.argtypes = [ct.c_void_p, ct.c_float, _U32, ct.c_longlong, _I, ct.c_longlong, ct.POINTER(ct.c_uint64)]
@@ -347,6 +350,8 @@ lib.hnswdev_exact_range_groups.restype = ct.c_int
 lib.hnswdev_exact_range_groups.argtypes = [ct.c_void_p, ct.c_longlong, ct.c_float, _U32, ct.c_longlong, _I, ct.POINTER(ct.c_uint64)]
 lib.hnswdev_exact_span_tree.restype = ct.c_int
 lib.hnswdev_exact_span_tree.argtypes = [ct.c_void_p, ct.c_longlong, _U32, ct.c_longlong, _I, _I, _F, ct.c_longlong, ct.POINTER(ct.c_uint64)]
+lib.hnswdev_exact_mreach_tree.restype = ct.c_int
+lib.hnswdev_exact_mreach_tree.argtypes = [ct.c_void_p, ct.c_longlong, ct.c_int, _U32, ct.c_longlong, _I, _I, _F, ct.c_longlong, _F, ct.c_longlong, ct.POINTER(ct.c_uint64)]
 lib.hnswdev_exact_range_density.restype = ct.c_int
 lib.hnswdev_exact_range_density.argtypes = [ct.c_void_p, ct.c_longlong, ct.c_float, ct.c_int, _U32, ct.c_longlong, _I, _I, ct.POINTER(ct.c_uint64)]
 lib.hnswdev_graph_edge_groups.restype = ct.c_int
@@ -1166,6 +1171,29 @@ class Index:
         labels[~member] = -1
         return labels
 
+    # ---- the mutual reachability tree ----
+    def mutual_reachability_tree(self, min_samples: int, allowed=None):
+        """HDBSCAN*'s tree (hnsw_mi355x_mutual_reachability_tree): (a int32[e], b int32[e], dist float32[e], core float32[length],
+        info) -- single_linkage_tree's forest, over the same members, under the mutual reachability distance.  core[v] is NaN where v
+        is no member, -inf at min_samples == 1, and otherwise the distance from the stored row of v to its (min_samples - 1)-th
+        nearest other member (column min_samples - 2 of exact_knn_query_by_id over the members; +inf where there is none): the item
+        counts itself, as in density_clusters.  The weight of members a < b is the largest of their distance -- the stored row of a as
+        the query -- and the two core distances; a NaN distance is no edge.  Edges are ordered by (dist, a, b).  1 <= min_samples <=
+        1025.  single_linkage_cut((a, b, dist, info), radius, allowed) gives, at the ids with core <= radius, the labels of
+        density_clusters(radius, min_samples, allowed).  info: single_linkage_tree's slots for the tree's scans, and core_launches."""
+        length = int(self.length)
+        n = max(length - 1, 0)
+        a, b, d = np.empty(n, dtype=np.int32), np.empty(n, dtype=np.int32), np.empty(n, dtype=np.float32)
+        core = np.full(length, np.nan, dtype=np.float32)
+        info = (ct.c_uint64 * 8)()
+        words, nbits = allow_bits(allowed) if allowed is not None else (None, 0)
+        words, wp = _words_arg(words) if allowed is not None else (None, None)
+        if self._h and lib.hnsw_mi355x_mutual_reachability_tree(self._h, int(min_samples), wp, nbits, a.ctypes.data_as(_I), b.ctypes.data_as(_I), d.ctypes.data_as(_F),
+                                                                 n, core.ctypes.data_as(_F), length, info) < 0:
+            raise RuntimeError(last_error())
+        e = int(info[1])
+        return a[:e].copy(), b[:e].copy(), d[:e].copy(), core, {name: int(info[i]) for i, name in enumerate(_MREACH_INFO)}
+
     # ---- near-duplicates over the graph's edges (DESIGN.md 3.30) ----
     def graph_duplicate_groups(self, radius: float, allowed=None) -> Tuple[npt.NDArray[np.int32], dict]:
         """duplicate_groups asked of the graph (hnsw_mi355x_graph_duplicate_groups): (int32[length], info).  The members are
@@ -1699,6 +1727,20 @@ class DeviceBackend:
         self._check(lib.hnswdev_exact_span_tree(self._ctx, int(n_rows), wp, nbits, a.ctypes.data_as(_I), b.ctypes.data_as(_I), d.ctypes.data_as(_F), n, info))
         e = int(info[1])
         return a[:e].copy(), b[:e].copy(), d[:e].copy(), {name: int(info[i]) for i, name in enumerate(_SPAN_INFO)}
+
+    def exact_mreach_tree(self, n_rows: int, min_samples: int, allowed=None):
+        """hnswdev_exact_mreach_tree: (a int32[e], b int32[e], dist float32[e], core float32[n_rows], info dict) --
+        Index.mutual_reachability_tree on the uploaded rows of [0, n_rows) that `allowed` allows."""
+        n = max(int(n_rows) - 1, 0)
+        a, b, d = np.empty(n, dtype=np.int32), np.empty(n, dtype=np.int32), np.empty(n, dtype=np.float32)
+        core = np.full(max(int(n_rows), 0), np.nan, dtype=np.float32)
+        info = (ct.c_uint64 * 8)()
+        words, nbits = allow_bits(allowed) if allowed is not None else (None, 0)
+        words, wp = _words_arg(words) if allowed is not None else (None, None)
+        self._check(lib.hnswdev_exact_mreach_tree(self._ctx, int(n_rows), int(min_samples), wp, nbits, a.ctypes.data_as(_I), b.ctypes.data_as(_I), d.ctypes.data_as(_F), n,
+                                                  core.ctypes.data_as(_F), core.size, info))
+        e = int(info[1])
+        return a[:e].copy(), b[:e].copy(), d[:e].copy(), core, {name: int(info[i]) for i, name in enumerate(_MREACH_INFO)}
 
     def graph_edge_groups(self, radius: float, n_rows: int, allowed=None):
         """hnswdev_graph_edge_groups: (int32[n_rows] labels, info dict) -- Index.graph_duplicate_groups on the uploaded rows of

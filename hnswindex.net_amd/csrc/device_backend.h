@@ -511,6 +511,15 @@ public:
     // over the triangle, at most 65 536 members as the queries of one launch (`span_round`).  Fewer than two members: no launch.
     // Neither the resident set nor exact_range's pending results are touched.
     bool exact_span_tree(long long n_rows, const uint32_t *allow_bits, long long nbits, int *out_a, int *out_b, float *out_dist, long long cap, uint64_t *out_info);
+    // hnswdev_exact_mreach_tree: exact_span_tree under the mutual reachability distance.  out_core[v], v < min(n_rows,
+    // uploaded rows) <= core_len: NaN for a non-member, -inf for every member at min_samples == 1, otherwise the distance from the stored
+    // row of v to its (min_samples - 1)-th nearest other member -- column min_samples - 2 of exact_knn_by_id over the members, +inf
+    // where that is padding or NaN.  The weight of a < b whose distance is a number is the largest of the distance and the two core
+    // distances, taken on exact_key's distance keys; edges, order, outputs and cap as exact_span_tree's.  min_samples outside
+    // [1, kExactMaxK + 1] is an error.  out_info: exact_span_tree's seven slots for the tree's rounds of mreach_scan_kernel<M>, and
+    // [7] the scan launches that produced the core distances (0 at min_samples == 1).  Fewer than two members: no launch.
+    bool exact_mreach_tree(long long n_rows, int min_samples, const uint32_t *allow_bits, long long nbits, int *out_a, int *out_b, float *out_dist, long long cap,
+                           float *out_core, long long core_len, uint64_t *out_info);
     // hnswdev_graph_edge_groups / hnswdev_graph_near_edges: near-duplicates over the EDGES of layer 0 of the
     // committed graph.  The MEMBERS are exact_range_groups' -- the uploaded rows of [0, n_rows) that allow_bits allows -- that are
     // nodes of the graph.  An edge (i, j): i a member, j in i's layer-0 list, j a member (directed); it is within the range when the
@@ -771,7 +780,7 @@ private:
     bool exact_queries(const char *who, const float *queries, int nq, const float **d_q, const double **d_qsn);
     bool exact_id_list(const uint32_t *allow_bits, long long n_allow, long long *m);
     bool exact_knn_rounds(const float *d_q, const double *d_qsn, int nq, const int *d_idlist, long long m, int k, int *out_ids, float *out_d, int *d_keep_ids,
-                          const int *d_self = nullptr, const ExactCollapseArgs *collapse = nullptr);
+                          const int *d_self = nullptr, const ExactCollapseArgs *collapse = nullptr, unsigned *d_core = nullptr);
     // the two calls over the graph's edges: out_labels / out_info, or -- keep_list -- the edges into ge_*
     bool graph_edges_run(const char *who, long long n_rows, float range, const uint32_t *allow_bits, long long nbits, int *out_labels, uint64_t *out_info,
                          bool keep_list);
@@ -810,12 +819,14 @@ private:
     DevBuf<unsigned long long> x_dattach_; // ... per id: the smallest (distance, core id) key offered to a member that is not core
     DevBuf<ExactDensityPair> x_darena_;   // ... phase A's within pairs: 2^24 records (256 MiB) unless `density_pair_cap` says otherwise
     // exact_span_tree's rounds (device_backend.hip): parent[] and the labels are x_uparent_'s, the counters x_upairs_'s
-    bool exact_span_tree_run(const ExactTriangle &t, std::vector<SpanEdge> &edges, uint64_t *out_info);
+    // (d_core: nullptr, or exact_mreach_tree's core keys by id -- the scan is then mreach_scan_kernel; who: the call, for messages)
+    bool exact_span_tree_run(const char *who, const ExactTriangle &t, const unsigned *d_core, std::vector<SpanEdge> &edges, uint64_t *out_info);
     DevBuf<unsigned long long> x_sbest_;  // exact_span_tree: per id, the smallest (distance, other id) key of the round
     DevBuf<unsigned long long> x_sedge_;  // ... per component (its root's slot): the lightest outgoing edge as lo << 32 | hi
     DevBuf<unsigned> x_sweight_;          // ... per component: that edge's distance key
     DevBuf<int> x_sseg_;                  // ... per kExactIterRows entries of the member list: their one label, or -1
     DevBuf<SpanEdge> x_sedges_;           // ... the forest's edges in the order the rounds found them: members - 1 at the most
+    DevBuf<unsigned> x_mcore_;            // exact_mreach_tree: per id, the core distance as exact_key's 32-bit distance key
     bool exact_range_finish(ExactRangeWork &w, int ns, const unsigned *c, const long long *seg, const int *sq, const long long *obase, size_t base,
                             bool counts_on_device, uint64_t *by_device, uint64_t *by_host);
     DevBuf<unsigned long long> x_rarena_; // exact_range: the round's keys, a segment per query: at most 1 GiB, grown on demand and kept

@@ -53,6 +53,7 @@
 #include "dk_exact_mfma.h"
 #include "dk_exact_tri.h"
 #include "dk_span_tree.h"
+#include "dk_mreach_tree.h"
 #include "dk_graph_info.h"
 #include "dk_graph_reach.h"
 #include "dk_graph_repair.h"
@@ -3404,8 +3405,10 @@ struct ExactCollapseArgs {
 // that receive the ids as well (graph_repair_round's candidates stay there for the proposal kernel).
 // d_self: nullptr, or nq ids on the device -- query i is the stored row d_self[i], which is no candidate of it (ExactTopKSelf).
 // collapse: nullptr, or the collapsed sink's arguments -- scan and merge are then ExactTopKCollapse's, the tile planned for its entries.
+// d_core: nullptr, or the core keys by id of exact_mreach_tree (d_self is then given): mreach_core_take_kernel reads column k - 1 of
+// every round's result where it lies on the device, and nothing comes to the host -- out_ids and out_d are not written.
 bool Device::exact_knn_rounds(const float *d_q, const double *d_qsn, int nq, const int *d_idlist, long long m, int k, int *out_ids, float *out_d, int *d_keep_ids,
-                              const int *d_self, const ExactCollapseArgs *collapse)
+                              const int *d_self, const ExactCollapseArgs *collapse, unsigned *d_core)
 {
     hipStream_t st = S(stream_);
     ExactPlan p;
@@ -3443,6 +3446,10 @@ bool Device::exact_knn_rounds(const float *d_q, const double *d_qsn, int nq, con
             return true;
         };
         const auto fetch = [&]() -> bool {
+            if (d_core) { // (behind the timed window: the scan and its merge are what is timed)
+                HIP_OK(mreach_core_take_launch(d_d, nr, k, d_self + off, d_core, st));
+                return true;
+            }
             HIP_OK(hipMemcpyAsync(hs, d_ids, res, hipMemcpyDeviceToHost, st));
             HIP_OK(hipMemcpyAsync(hs + 4u * (size_t)p.round * k, d_d, res, hipMemcpyDeviceToHost, st));
             if (d_keep_ids) HIP_OK(hipMemcpyAsync(d_keep_ids + (size_t)off * k, d_ids, res, hipMemcpyDeviceToDevice, st));
@@ -3451,6 +3458,7 @@ bool Device::exact_knn_rounds(const float *d_q, const double *d_qsn, int nq, con
         };
         if (!exact_timed_scan(h_ev, enqueue, fetch)) return false;
         if (pf) { xpf_stats_[0] += 1; xpf_stats_[1] += h_ev[1]; xpf_stats_[2] += h_ev[2]; }
+        if (d_core) continue;
         memcpy(out_ids + (size_t)off * k, hs, res);
         if (out_d) memcpy(out_d + (size_t)off * k, hs + 4u * (size_t)p.round * k, res);
     }
@@ -5242,12 +5250,13 @@ bool Device::exact_range_density(long long n_rows, float range, int min_samples,
 // (span_weight / span_edge / span_join) and relabels (exact_union_labels_kernel: labels are roots, which are smallest ids).  Eight
 // bytes come back per round: the edge cursor.  The rounds end when the forest has members - 1 edges, or when a round joined nothing
 // (what is left apart has only NaN distances between it); the components at least halve per round, so 32 rounds are never reached.
+// d_core: nullptr, or the members' core keys by id -- the scan is then mreach_scan_kernel and the keys are mutual
+// reachability weights; everything around the scan launch is the same, because the round kernels only see keys.
 constexpr int kSpanMaxRounds = 32;
-bool Device::exact_span_tree_run(const ExactTriangle &t, std::vector<SpanEdge> &edges, uint64_t *out_info)
+bool Device::exact_span_tree_run(const char *who, const ExactTriangle &t, const unsigned *d_core, std::vector<SpanEdge> &edges, uint64_t *out_info)
 {
-    const char *who = "exact_span_tree";
     const long long n = t.n, m = t.m;
-    const size_t lds = span_scan_lds(t.p.qtile, t.p.piece, pitch_), n_seg = (size_t)((m + kExactIterRows - 1) / kExactIterRows);
+    const size_t lds = d_core ? mreach_scan_lds(t.p.qtile, t.p.piece, pitch_) : span_scan_lds(t.p.qtile, t.p.piece, pitch_), n_seg = (size_t)((m + kExactIterRows - 1) / kExactIterRows);
     if (lds > 64 * 1024) { set_dev_error(std::string(who) + ": tile exceeds the LDS budget"); return false; }
     if (!x_uparent_.grow(2 * (size_t)n) || !x_upairs_.grow(2) || !x_sbest_.grow((size_t)n) || !x_sedge_.grow((size_t)n) || !x_sweight_.grow((size_t)n) ||
         !x_sseg_.grow(n_seg) || !x_sedges_.grow((size_t)(m - 1)))
@@ -5266,10 +5275,11 @@ bool Device::exact_span_tree_run(const ExactTriangle &t, std::vector<SpanEdge> &
         long long q_off = 0; // the launches of a scan take the member list's pieces in order: where this one's queries begin
         const auto launch = [&](const ExactScanArgs &a, unsigned tiles, hipStream_t s) {
             const SpanScanArgs sa{d_labels, x_sbest_, x_sseg_, q_off, d_skipped};
+            const MreachScanArgs ma{d_labels, x_sbest_, x_sseg_, d_core, q_off, d_skipped};
             q_off += a.nq;
             launches += 1;
             hipError_t e = hipSuccess;
-            with_metric(metric_, [&](auto mt) { e = span_scan_launch<mt>(a, sa, tiles, lds, s); });
+            with_metric(metric_, [&](auto mt) { e = d_core ? mreach_scan_launch<mt>(a, ma, tiles, lds, s) : span_scan_launch<mt>(a, sa, tiles, lds, s); });
             return e;
         };
         if (!exact_triangle_scan(t, launch, &measured)) return false;
@@ -5289,6 +5299,19 @@ bool Device::exact_span_tree_run(const ExactTriangle &t, std::vector<SpanEdge> &
     return true;
 }
 
+// The forest as the contract orders it, (weight key, a, b) -- the rounds found the edges in another -- into the caller's arrays
+static void span_edges_out(std::vector<SpanEdge> &edges, int *out_a, int *out_b, float *out_dist)
+{
+    std::sort(edges.begin(), edges.end(), [](const SpanEdge &x, const SpanEdge &y) {
+        return x.dkey != y.dkey ? x.dkey < y.dkey : x.a != y.a ? x.a < y.a : x.b < y.b;
+    });
+    for (size_t e = 0; e < edges.size(); ++e) {
+        out_a[e] = edges[e].a;
+        out_b[e] = edges[e].b;
+        out_dist[e] = exact_host_key_dist((unsigned long long)edges[e].dkey << 32);
+    }
+}
+
 bool Device::exact_span_tree(long long n_rows, const uint32_t *allow_bits, long long nbits, int *out_a, int *out_b, float *out_dist, long long cap, uint64_t *out_info)
 {
     const char *who = "exact_span_tree";
@@ -5304,15 +5327,65 @@ bool Device::exact_span_tree(long long n_rows, const uint32_t *allow_bits, long 
     if (!out_a || !out_b || !out_dist) { set_dev_error(std::string(who) + ": bad argument"); return false; }
     if (!exact_triangle_ready(who, &t, "span_round")) return false;
     std::vector<SpanEdge> edges;
-    if (!exact_span_tree_run(t, edges, out_info)) return false;
-    // the contract's order: (distance key, a, b) -- the rounds found the edges in another
-    std::sort(edges.begin(), edges.end(), [](const SpanEdge &x, const SpanEdge &y) {
-        return x.dkey != y.dkey ? x.dkey < y.dkey : x.a != y.a ? x.a < y.a : x.b < y.b;
-    });
-    for (size_t e = 0; e < edges.size(); ++e) {
-        out_a[e] = edges[e].a;
-        out_b[e] = edges[e].b;
-        out_dist[e] = exact_host_key_dist((unsigned long long)edges[e].dkey << 32);
+    if (!exact_span_tree_run(who, t, nullptr, edges, out_info)) return false;
+    span_edges_out(edges, out_a, out_b, out_dist);
+    return true;
+}
+
+// ---- the minimum spanning forest under the mutual reachability distance -------------------------------------------
+// exact_span_tree with a stage in front: the members' core distances.  The members go up once (exact_triangle_ready); a round of
+// `span_round` members at a time is gathered as queries, as the triangle's scans gather theirs, and exact_knn_rounds runs the by-id
+// top-(min_samples - 1) scan over the member list with ExactTopKSelf -- exact_knn_by_id's kernels, list and merge, so column
+// min_samples - 2 holds that call's bits -- and mreach_core_take_kernel turns the column into keys by id on the device: no distance
+// crosses the bus but the n keys that come back as out_core.  min_samples == 1: no scan, every member's key is -inf's
+// (mreach_core_fill_kernel).  Then exact_span_tree_run's rounds with mreach_scan_kernel as the scan.
+bool Device::exact_mreach_tree(long long n_rows, int min_samples, const uint32_t *allow_bits, long long nbits, int *out_a, int *out_b, float *out_dist, long long cap,
+                               float *out_core, long long core_len, uint64_t *out_info)
+{
+    const char *who = "exact_mreach_tree";
+    if (!out_info) { set_dev_error(std::string(who) + ": bad argument"); return false; }
+    if (min_samples < 1 || min_samples > kExactMaxK + 1) {
+        set_dev_error(std::string(who) + ": min_samples = " + std::to_string(min_samples) + " is outside [1, " + std::to_string(kExactMaxK + 1) + "]");
+        return false;
+    }
+    ExactTriangle t;
+    if (!exact_triangle_begin(who, n_rows, allow_bits, nbits, &t)) return false;
+    for (int i = 0; i < 8; ++i) out_info[i] = 0;
+    const long long n = t.n, m = t.m;
+    if (core_len < n) { set_dev_error(std::string(who) + ": core_len = " + std::to_string(core_len) + " is below the " + std::to_string(n) + " rows"); return false; }
+    if (n > 0 && !out_core) { set_dev_error(std::string(who) + ": bad argument"); return false; }
+    const float lone = min_samples == 1 ? -std::numeric_limits<float>::infinity() : std::numeric_limits<float>::infinity();
+    for (long long v = 0; v < n; ++v) out_core[v] = std::numeric_limits<float>::quiet_NaN();
+    for (const int v : t.members) out_core[v] = lone; // (what a lone member keeps: it has no other member to measure)
+    out_info[0] = (unsigned long long)m;
+    out_info[2] = (unsigned long long)m; // every member is a component of its own until an edge joins it
+    if (m < 2) return true; // nothing to measure: no launch
+    if (cap < m - 1) { set_dev_error(std::string(who) + ": cap = " + std::to_string(cap) + " is below members - 1 = " + std::to_string(m - 1)); return false; }
+    if (!out_a || !out_b || !out_dist) { set_dev_error(std::string(who) + ": bad argument"); return false; }
+    if (!exact_triangle_ready(who, &t, "span_round")) return false;
+    if (!x_mcore_.grow((size_t)n)) return false;
+    hipStream_t st = S(stream_);
+    unsigned long long core_launches = 0;
+    if (min_samples == 1) HIP_OK(mreach_core_fill_launch(x_ids_, m, lone, x_mcore_, st));
+    else {
+        HIP_OK(hipStreamSynchronize(st)); // the members' ids have left the pinned stage, which the gathers use again
+        const unsigned long long before = stats_.exact_launches;
+        for (long long off = 0; off < m; off += t.round) {
+            const int nr = (int)std::min<long long>(t.round, m - off);
+            if (!gather_queries(t.members.data() + off, nr, x_self_, x_queries_, x_q_sn_)) return false;
+            if (!exact_knn_rounds(x_queries_, metric_ == M_COS ? x_q_sn_.get() : nullptr, nr, x_ids_, m, min_samples - 1, nullptr, nullptr, nullptr, x_self_, nullptr, x_mcore_))
+                return false;
+        }
+        core_launches = stats_.exact_launches - before;
+    }
+    std::vector<SpanEdge> edges;
+    if (!exact_span_tree_run(who, t, x_mcore_, edges, out_info)) return false;
+    out_info[7] = core_launches;
+    span_edges_out(edges, out_a, out_b, out_dist);
+    if (min_samples > 1) {
+        std::vector<unsigned> keys((size_t)n);
+        if (!exact_copy_out(keys.data(), x_mcore_, 4 * (size_t)n)) return false;
+        for (const int v : t.members) out_core[v] = exact_host_key_dist((unsigned long long)keys[(size_t)v] << 32);
     }
     return true;
 }
@@ -5752,6 +5825,12 @@ DEV_API int hnswdev_exact_span_tree(void *ctx, long long n_rows, const uint32_t 
 {
     CTX_OR_FAIL();
     return d->exact_span_tree(n_rows, allow_words, nbits, out_a, out_b, out_dist, cap, out_info) ? 0 : -1;
+}
+DEV_API int hnswdev_exact_mreach_tree(void *ctx, long long n_rows, int min_samples, const uint32_t *allow_words, long long nbits, int *out_a, int *out_b,
+                                      float *out_dist, long long cap, float *out_core, long long core_len, uint64_t *out_info)
+{
+    CTX_OR_FAIL();
+    return d->exact_mreach_tree(n_rows, min_samples, allow_words, nbits, out_a, out_b, out_dist, cap, out_core, core_len, out_info) ? 0 : -1;
 }
 DEV_API int hnswdev_graph_edge_groups(void *ctx, long long n_rows, float range, const uint32_t *allow_bits, long long nbits, int *out_labels,
                                       uint64_t *out_info)

@@ -556,6 +556,24 @@ API int hnsw_mi355x_single_linkage_tree(void *handle, const uint32_t *allow_word
     return 0;
 }
 
+// HDBSCAN*'s tree: that forest under the mutual reachability distance -- every density_clusters(radius, min_samples)
+// partition of the cores is a cut of it -- and the members' core distances.  Exclusive: it uses the scan's buffers.
+API int hnsw_mi355x_mutual_reachability_tree(void *handle, int min_samples, const uint32_t *allow_words, long long nbits, int *out_a, int *out_b, float *out_dist,
+                                             long long cap, float *out_core, long long core_len, uint64_t *out_info)
+{
+    if (out_info) for (int i = 0; i < 8; ++i) out_info[i] = 0;
+    if (!handle) return 0;
+    if (!out_info) { set_error("System.ArgumentNullException: hnsw_mi355x_mutual_reachability_tree: out_info"); return -1; }
+    if (allow_words && nbits < 0) { set_error("System.ArgumentException: hnsw_mi355x_mutual_reachability_tree: nbits must be >= 0"); return -1; }
+    LOCK_INDEX(handle);
+    std::string err;
+    if (static_cast<HnswIndex *>(handle)->mutual_reachability_tree(min_samples, allow_words, nbits, out_a, out_b, out_dist, cap, out_core, core_len, out_info, err) < 0) {
+        set_error(err);
+        return -1;
+    }
+    return 0;
+}
+
 // Near-duplicates over the graph's edges: hnsw_mi355x_duplicate_groups' members and label convention, joined along
 // the layer-0 edges within `range`; and those edges themselves, counted and kept by the first call and fetched by the second, as
 // hnswdev_exact_range / hnswdev_exact_range_results do it.  Exclusive: they use the scan's query buffer and bring the mirror up to date.

@@ -2179,17 +2179,11 @@ int HnswIndex::density_clusters(float range, int min_samples, const uint32_t *al
     return 0;
 }
 
-// The minimum spanning forest: duplicate_groups' members, counted here so that the caller's arrays are checked
-// against members - 1 before anything is launched; the edges come back from the device in the contract's order.
-int HnswIndex::single_linkage_tree(const uint32_t *allow_bits, long long nbits, int *out_a, int *out_b, float *out_dist, long long cap, uint64_t *out_info,
-                                   std::string &err)
+// The edge arrays of a tree call: the members (exact_candidates' bits below `length`) are counted here so that the caller's arrays
+// are checked against members - 1 before anything is launched.
+static bool tree_arrays_ok(const char *who, const uint32_t *allow_bits, long long nbits, long long length, const int *out_a, const int *out_b, const float *out_dist,
+                           long long cap, std::string &err)
 {
-    const char *who = "hnsw_mi355x_single_linkage_tree";
-    for (int i = 0; i < 8; ++i) out_info[i] = 0;
-    if (failed(err)) return -1;
-    if (graph_.length <= 0 || graph_.count <= 0) return 0; // no member, and nothing needs the device
-    std::vector<uint32_t> live;
-    const long long length = exact_candidates(allow_bits, nbits, live);
     long long members = length;
     if (allow_bits) {
         members = 0;
@@ -2197,13 +2191,53 @@ int HnswIndex::single_linkage_tree(const uint32_t *allow_bits, long long nbits, 
     }
     if (members >= 2 && cap < members - 1) {
         err = std::string("System.ArgumentException: ") + who + ": cap = " + std::to_string(cap) + " is below members - 1 = " + std::to_string(members - 1);
-        return -1;
+        return false;
     }
     if (members >= 2 && (!out_a || !out_b || !out_dist)) {
         err = std::string("System.ArgumentNullException: ") + who + ": " + (!out_a ? "out_a" : !out_b ? "out_b" : "out_dist");
+        return false;
+    }
+    return true;
+}
+
+// The minimum spanning forest: duplicate_groups' members; the edges come back from the device in the contract's order.
+int HnswIndex::single_linkage_tree(const uint32_t *allow_bits, long long nbits, int *out_a, int *out_b, float *out_dist, long long cap, uint64_t *out_info,
+                                   std::string &err)
+{
+    for (int i = 0; i < 8; ++i) out_info[i] = 0;
+    if (failed(err)) return -1;
+    if (graph_.length <= 0 || graph_.count <= 0) return 0; // no member, and nothing needs the device
+    std::vector<uint32_t> live;
+    const long long length = exact_candidates(allow_bits, nbits, live);
+    if (!tree_arrays_ok("hnsw_mi355x_single_linkage_tree", allow_bits, nbits, length, out_a, out_b, out_dist, cap, err)) return -1;
+    if (!dev_->exact_span_tree(length, allow_bits, nbits, out_a, out_b, out_dist, cap, out_info)) { err = get_dev_error(); return -1; }
+    return 0;
+}
+
+// The mutual reachability tree: single_linkage_tree's members and arrays; out_core is filled with NaN -- no member --
+// over the index's length first, and the device writes the members' core distances over it.
+int HnswIndex::mutual_reachability_tree(int min_samples, const uint32_t *allow_bits, long long nbits, int *out_a, int *out_b, float *out_dist, long long cap,
+                                        float *out_core, long long core_len, uint64_t *out_info, std::string &err)
+{
+    const char *who = "hnsw_mi355x_mutual_reachability_tree";
+    for (int i = 0; i < 8; ++i) out_info[i] = 0;
+    if (failed(err)) return -1;
+    if (min_samples < 1 || min_samples > kExactMaxK + 1) {
+        err = std::string("System.ArgumentOutOfRangeException: ") + who + ": min_samples = " + std::to_string(min_samples) + " is outside [1, " +
+              std::to_string(kExactMaxK + 1) + "]";
         return -1;
     }
-    if (!dev_->exact_span_tree(length, allow_bits, nbits, out_a, out_b, out_dist, cap, out_info)) { err = get_dev_error(); return -1; }
+    if (core_len < graph_.length) {
+        err = std::string("System.ArgumentException: ") + who + ": core_len = " + std::to_string(core_len) + " is below the index's length of " + std::to_string(graph_.length);
+        return -1;
+    }
+    if (graph_.length > 0 && !out_core) { err = std::string("System.ArgumentNullException: ") + who + ": out_core"; return -1; }
+    for (long long v = 0; v < graph_.length; ++v) out_core[v] = std::numeric_limits<float>::quiet_NaN();
+    if (graph_.length <= 0 || graph_.count <= 0) return 0; // no member, and nothing needs the device
+    std::vector<uint32_t> live;
+    const long long length = exact_candidates(allow_bits, nbits, live);
+    if (!tree_arrays_ok(who, allow_bits, nbits, length, out_a, out_b, out_dist, cap, err)) return -1;
+    if (!dev_->exact_mreach_tree(length, min_samples, allow_bits, nbits, out_a, out_b, out_dist, cap, out_core, core_len, out_info)) { err = get_dev_error(); return -1; }
     return 0;
 }
 

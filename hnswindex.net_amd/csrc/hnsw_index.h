@@ -106,6 +106,10 @@ public:
     // hnsw_mi355x_single_linkage_tree: the minimum spanning forest of duplicate_groups' members
     // (Device::exact_span_tree); out_a / out_b / out_dist hold members - components edges, cap >= members - 1.
     int single_linkage_tree(const uint32_t *allow_bits, long long nbits, int *out_a, int *out_b, float *out_dist, long long cap, uint64_t *out_info, std::string &err);
+    // hnsw_mi355x_mutual_reachability_tree: that forest under the mutual reachability distance
+    // (Device::exact_mreach_tree); out_core holds the index's length of entries within core_len.
+    int mutual_reachability_tree(int min_samples, const uint32_t *allow_bits, long long nbits, int *out_a, int *out_b, float *out_dist, long long cap, float *out_core,
+                                 long long core_len, uint64_t *out_info, std::string &err);
     // hnsw_mi355x_graph_duplicate_groups / hnsw_mi355x_near_edges: duplicate_groups' members, joined along the
     // within-edges of layer 0 of the graph mirror (Device::graph_edge_groups / graph_near_edges), which is brought up to date first
     // (sync_graph) as for get_info.  On the primary context; liveness and allow_bits go down as one bitset.  out_labels[0, length),

@@ -527,6 +527,21 @@ int hnsw_mi355x_density_clusters(void *handle, float range, int min_samples, con
  * NULL handle: 0, out_info zeroed.  NULL out_info, or allow_words with nbits < 0: -1. */
 int hnsw_mi355x_single_linkage_tree(void *handle, const uint32_t *allow_words, long long nbits, int *out_a, int *out_b, float *out_dist, long long cap,
                                     uint64_t out_info[8]);
+/* hnsw_mi355x_mutual_reachability_tree: HDBSCAN*'s tree -- the forest of hnsw_mi355x_single_linkage_tree, over the same
+ * members, under the MUTUAL REACHABILITY distance.  1 <= min_samples <= 1025, else -1 with a message.
+ *   out_core[v], v < length (core_len: its entries; core_len < length is -1 with a message): NaN where v is no member; -inf for every
+ *   member at min_samples = 1; otherwise the distance from the stored row of v to its (min_samples - 1)-th nearest other member --
+ *   column min_samples - 2 of hnsw_mi355x_exact_knn_query_by_id for v over the members, those bits -- and +inf where that entry is
+ *   padding or NaN.  The item counts itself, as hnsw_mi355x_density_clusters counts it.
+ *   The WEIGHT of members a < b whose distance d (the stored row of a as the query) is a number is the largest of d, out_core[a] and
+ *   out_core[b], taken on the order of the single-linkage tree (-0 equal to +0).  A NaN d is no edge; a +inf core makes +inf edges,
+ *   which are edges.
+ * Edges, their order (weight, a, b), out_a / out_b / out_dist, cap and the NULL conventions are those of the single-linkage tree; at
+ * min_samples = 1 so are the bytes.  Every hnsw_mi355x_density_clusters(radius, min_samples) partition of the core members -- those
+ * with out_core[v] <= radius -- is the cut of this tree at radius.  out_info[0] .. [6] as there, counting the tree's scans;
+ * [7] the scan launches that produced out_core, 0 at min_samples = 1. */
+int hnsw_mi355x_mutual_reachability_tree(void *handle, int min_samples, const uint32_t *allow_words, long long nbits, int *out_a, int *out_b, float *out_dist,
+                                         long long cap, float *out_core, long long core_len, uint64_t out_info[8]);
 /* NEAR-DUPLICATES OVER THE GRAPH'S EDGES: the question of the two calls above asked of layer 0 of the index's graph
  * instead of every pair -- n x (at most 2 MaxEdges) distances instead of m (m - 1) / 2.  The MEMBERS are those of
  * hnsw_mi355x_duplicate_groups.  An EDGE is a pair (i, j): i a member, j in i's layer-0 list, j a member; it is directed (j listing i
@@ -968,6 +983,11 @@ int hnswdev_exact_range_density(void *ctx, long long n_rows, float range, int mi
  * written.  Neither the resident set nor what hnswdev_exact_range_results has pending is touched. */
 int hnswdev_exact_span_tree(void *ctx, long long n_rows, const uint32_t *allow_words, long long nbits, int *out_a, int *out_b, float *out_dist,
                             long long cap, uint64_t out_info[8]);
+/* The stages behind hnsw_mi355x_mutual_reachability_tree (the by-id top-k scan for the core distances, then rounds of
+ * mreach_scan_kernel): members, edge arrays and cap as hnswdev_exact_span_tree; out_core has core_len >= min(n_rows, uploaded rows)
+ * entries; out_info as there.  A NULL context: -1, nothing written. */
+int hnswdev_exact_mreach_tree(void *ctx, long long n_rows, int min_samples, const uint32_t *allow_words, long long nbits, int *out_a, int *out_b,
+                              float *out_dist, long long cap, float *out_core, long long core_len, uint64_t out_info[8]);
 /* The calls behind hnsw_mi355x_graph_duplicate_groups / hnsw_mi355x_near_edges, on the context's own rows and the graph it was given
  * (hnswdev_graph_begin .. _commit): the members are the uploaded rows [0, n_rows) that allow_bits allows and that are nodes of the
  * graph; out_labels has min(n_rows, uploaded rows) entries, out_info as there.  hnswdev_graph_near_edges counts and keeps,
