@@ -289,6 +289,10 @@ lib.hnsw_mi355x_triangle_prefilter_stats.restype = ct.c_int
 lib.hnsw_mi355x_triangle_prefilter_stats.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
 lib.hnswdev_triangle_prefilter_stats.restype = ct.c_int
 lib.hnswdev_triangle_prefilter_stats.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
+lib.hnsw_mi355x_span_prefilter_stats.restype = ct.c_int
+lib.hnsw_mi355x_span_prefilter_stats.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
+lib.hnswdev_span_prefilter_stats.restype = ct.c_int
+lib.hnswdev_span_prefilter_stats.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
 lib.hnsw_mi355x_row_prefilter_form_stats.restype = ct.c_int
 lib.hnsw_mi355x_row_prefilter_form_stats.argtypes = [ct.c_void_p, ct.POINTER(ct.c_uint64)]
 lib.hnsw_mi355x_row_prefilter8_stats.restype = ct.c_int
@@ -735,6 +739,15 @@ class Index:
         launches that took the form, pairs its half-precision tile judged, pairs of them then measured exactly, and a reserved 0."""
         out = (ct.c_uint64 * 4)()
         if not self._h or lib.hnsw_mi355x_triangle_prefilter_stats(self._h, out) != 0:
+            return dict.fromkeys(EXACT_PREFILTER_SLOTS, 0)
+        return dict(zip(EXACT_PREFILTER_SLOTS, (int(v) for v in out)))
+
+    def span_prefilter_stats(self):
+        """Counters of the same tile in front of the Boruvka scans of single_linkage_tree and mutual_reachability_tree (DESIGN.md
+        3.37): scan launches that took the form, foreign pairs its half-precision tile judged, pairs of them then measured exactly,
+        and a reserved 0."""
+        out = (ct.c_uint64 * 4)()
+        if not self._h or lib.hnsw_mi355x_span_prefilter_stats(self._h, out) != 0:
             return dict.fromkeys(EXACT_PREFILTER_SLOTS, 0)
         return dict(zip(EXACT_PREFILTER_SLOTS, (int(v) for v in out)))
 
@@ -2158,6 +2171,13 @@ class DeviceBackend:
         exact_range_density, the slots of Index.triangle_prefilter_stats."""
         out = (ct.c_uint64 * 4)()
         self._check(lib.hnswdev_triangle_prefilter_stats(self._ctx, out))
+        return dict(zip(EXACT_PREFILTER_SLOTS, (int(v) for v in out)))
+
+    def span_prefilter_stats(self) -> dict:
+        """hnswdev_span_prefilter_stats: this context's counters of the MFMA prefilter of exact_span_tree and exact_mreach_tree, the
+        slots of Index.span_prefilter_stats."""
+        out = (ct.c_uint64 * 4)()
+        self._check(lib.hnswdev_span_prefilter_stats(self._ctx, out))
         return dict(zip(EXACT_PREFILTER_SLOTS, (int(v) for v in out)))
 
     def set_profiling(self, on: bool):

@@ -623,6 +623,8 @@ public:
     void exact_prefilter_stats(uint64_t out[4]) const;
     // ... and the same tile in front of the fixed-radius triangle scans, in the same slots
     void triangle_prefilter_stats(uint64_t out[4]) const;
+    // ... and in front of the Boruvka scans of exact_span_tree and exact_mreach_tree: launches, foreign pairs on the tile, pairs measured, 0
+    void span_prefilter_stats(uint64_t out[4]) const;
     // Which kernel form those launches took: out[0] the run-time-length form (kFormLeanPF), out[1] the fixed-length one (kFormLeanPFFixed).
     void row_prefilter_form_stats(uint64_t out[2]);
     // The shadow as it stands, read only (nothing is packed or allocated): out[0] the watermark (shadow rows [0, out[0]) are current),
@@ -820,12 +822,15 @@ private:
     DevBuf<ExactDensityPair> x_darena_;   // ... phase A's within pairs: 2^24 records (256 MiB) unless `density_pair_cap` says otherwise
     // exact_span_tree's rounds (device_backend.hip): parent[] and the labels are x_uparent_'s, the counters x_upairs_'s
     // (d_core: nullptr, or exact_mreach_tree's core keys by id -- the scan is then mreach_scan_kernel; who: the call, for messages)
-    bool exact_span_tree_run(const char *who, const ExactTriangle &t, const unsigned *d_core, std::vector<SpanEdge> &edges, uint64_t *out_info);
+    // (t.p becomes span_pf_kernel's plan where the picker takes that form)
+    bool exact_span_tree_run(const char *who, ExactTriangle &t, const unsigned *d_core, std::vector<SpanEdge> &edges, uint64_t *out_info);
     DevBuf<unsigned long long> x_sbest_;  // exact_span_tree: per id, the smallest (distance, other id) key of the round
     DevBuf<unsigned long long> x_sedge_;  // ... per component (its root's slot): the lightest outgoing edge as lo << 32 | hi
     DevBuf<unsigned> x_sweight_;          // ... per component: that edge's distance key
     DevBuf<int> x_sseg_;                  // ... per kExactIterRows entries of the member list: their one label, or -1
     DevBuf<SpanEdge> x_sedges_;           // ... the forest's edges in the order the rounds found them: members - 1 at the most
+    DevBuf<unsigned long long> x_spfctr_; // ... span_pf_kernel's two device counters, added up over the launches of a call
+    uint64_t xspf_stats_[4] = {0, 0, 0, 0}; // ... and their totals with the launches in front (span_prefilter_stats)
     DevBuf<unsigned> x_mcore_;            // exact_mreach_tree: per id, the core distance as exact_key's 32-bit distance key
     bool exact_range_finish(ExactRangeWork &w, int ns, const unsigned *c, const long long *seg, const int *sq, const long long *obase, size_t base,
                             bool counts_on_device, uint64_t *by_device, uint64_t *by_host);

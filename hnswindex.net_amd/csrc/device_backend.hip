@@ -54,6 +54,7 @@
 #include "dk_exact_tri.h"
 #include "dk_span_tree.h"
 #include "dk_mreach_tree.h"
+#include "dk_span_tree_pf.h"
 #include "dk_graph_info.h"
 #include "dk_graph_reach.h"
 #include "dk_graph_repair.h"
@@ -5083,7 +5084,27 @@ static bool exact_tri_pf_plan(int metric, long long m, int pitch, long long floo
     return true;
 }
 
+// The same for the Boruvka scans of the two spanning trees (span_pf_kernel, dk_span_tree_pf.h): the same knob with
+// the same three values, `floor` the tree's measured member floor, chunks of about kSpanPfChunk rows.  The plan replaces
+// exact_triangle_ready's in *p.
+static bool exact_span_pf_plan(int metric, long long m, int pitch, long long floor, ExactPlan *p)
+{
+    const int mode = diag("exact_prefilter", 1);
+    if (mode <= 0 || !exact_pf_metric(metric) || !exact_pf_dim(pitch)) return false;
+    const bool forced_c = diag("exact_chunk", 0) > 0;
+    if (mode == 1 && (forced_c || diag("exact_qtile", 0) > 0 || m < floor)) return false;
+    p->qtile = kExactPfQTile; p->piece = pitch;
+    p->lds = span_pf_lds(pitch);
+    if (!forced_c) {
+        const long long chunks = std::max<long long>(1, std::min<long long>(m / kSpanPfChunk, kExactMaxChunks));
+        p->chunk = ((m + chunks - 1) / chunks + kExactIterRows - 1) / kExactIterRows * kExactIterRows;
+        p->n_chunks = (int)((m + p->chunk - 1) / p->chunk);
+    }
+    return true;
+}
+
 void Device::triangle_prefilter_stats(uint64_t out[4]) const { std::copy_n(xtpf_stats_, 4, out); }
+void Device::span_prefilter_stats(uint64_t out[4]) const { std::copy_n(xspf_stats_, 4, out); }
 
 // The form's two device counters of a call: zeroed before its first launch (enqueued), added to the totals behind its last
 bool Device::exact_tri_pf_reset()
@@ -5253,11 +5274,14 @@ bool Device::exact_range_density(long long n_rows, float range, int min_samples,
 // d_core: nullptr, or the members' core keys by id -- the scan is then mreach_scan_kernel and the keys are mutual
 // reachability weights; everything around the scan launch is the same, because the round kernels only see keys.
 constexpr int kSpanMaxRounds = 32;
-bool Device::exact_span_tree_run(const char *who, const ExactTriangle &t, const unsigned *d_core, std::vector<SpanEdge> &edges, uint64_t *out_info)
+bool Device::exact_span_tree_run(const char *who, ExactTriangle &t, const unsigned *d_core, std::vector<SpanEdge> &edges, uint64_t *out_info)
 {
     const long long n = t.n, m = t.m;
-    const size_t lds = d_core ? mreach_scan_lds(t.p.qtile, t.p.piece, pitch_) : span_scan_lds(t.p.qtile, t.p.piece, pitch_), n_seg = (size_t)((m + kExactIterRows - 1) / kExactIterRows);
+    // behind the f16 MFMA tile (span_pf_kernel) where the picker says so: the plan is then that form's
+    const bool pf = exact_span_pf_plan(metric_, m, pitch_, d_core ? kSpanPfMinMembersMreach : kSpanPfMinMembersSpan, &t.p);
+    const size_t lds = pf ? t.p.lds : d_core ? mreach_scan_lds(t.p.qtile, t.p.piece, pitch_) : span_scan_lds(t.p.qtile, t.p.piece, pitch_), n_seg = (size_t)((m + kExactIterRows - 1) / kExactIterRows);
     if (lds > 64 * 1024) { set_dev_error(std::string(who) + ": tile exceeds the LDS budget"); return false; }
+    if (pf && !x_spfctr_.grow(2)) return false;
     if (!x_uparent_.grow(2 * (size_t)n) || !x_upairs_.grow(2) || !x_sbest_.grow((size_t)n) || !x_sedge_.grow((size_t)n) || !x_sweight_.grow((size_t)n) ||
         !x_sseg_.grow(n_seg) || !x_sedges_.grow((size_t)(m - 1)))
         return false;
@@ -5267,6 +5291,7 @@ bool Device::exact_span_tree_run(const char *who, const ExactTriangle &t, const 
     HIP_OK(exact_union_init_launch(x_ids_, m, x_uparent_, n, st));
     HIP_OK(exact_union_labels_launch(x_uparent_, n, d_labels, st));
     HIP_OK(hipMemsetAsync(x_upairs_, 0, 2 * sizeof(unsigned long long), st));
+    if (pf) HIP_OK(hipMemsetAsync(x_spfctr_, 0, 2 * sizeof(unsigned long long), st)); // the form's two counters add up over the call's launches
     HIP_OK(hipStreamSynchronize(st)); // the pinned stage is used again by the rounds
     unsigned long long measured = 0, skipped = 0, launches = 0, n_edges = 0, rounds = 0;
     while (n_edges < (unsigned long long)(m - 1)) {
@@ -5276,10 +5301,13 @@ bool Device::exact_span_tree_run(const char *who, const ExactTriangle &t, const 
         const auto launch = [&](const ExactScanArgs &a, unsigned tiles, hipStream_t s) {
             const SpanScanArgs sa{d_labels, x_sbest_, x_sseg_, q_off, d_skipped};
             const MreachScanArgs ma{d_labels, x_sbest_, x_sseg_, d_core, q_off, d_skipped};
+            const SpanPfArgs pa{d_labels, x_sbest_, x_sseg_, d_core, x_sweight_, q_off, d_skipped, x_spfctr_};
             q_off += a.nq;
             launches += 1;
             hipError_t e = hipSuccess;
-            with_metric(metric_, [&](auto mt) { e = d_core ? mreach_scan_launch<mt>(a, ma, tiles, lds, s) : span_scan_launch<mt>(a, sa, tiles, lds, s); });
+            with_metric(metric_, [&](auto mt) {
+                e = pf ? span_pf_launch<mt>(a, pa, d_core != nullptr, tiles, lds, s) : d_core ? mreach_scan_launch<mt>(a, ma, tiles, lds, s) : span_scan_launch<mt>(a, sa, tiles, lds, s);
+            });
             return e;
         };
         if (!exact_triangle_scan(t, launch, &measured)) return false;
@@ -5294,6 +5322,11 @@ bool Device::exact_span_tree_run(const char *who, const ExactTriangle &t, const 
     }
     edges.resize((size_t)n_edges);
     if (!exact_copy_out(edges.data(), x_sedges_, sizeof(SpanEdge) * (size_t)n_edges) || !exact_copy_out(&skipped, d_skipped, 8)) return false;
+    if (pf) { // the form's counters come out once, behind the call's last launch
+        uint64_t ctr[2];
+        if (!exact_copy_out(ctr, x_spfctr_, sizeof ctr)) return false;
+        xspf_stats_[0] += launches; xspf_stats_[1] += ctr[0]; xspf_stats_[2] += ctr[1];
+    }
     out_info[1] = n_edges; out_info[2] = (unsigned long long)m - n_edges; out_info[3] = rounds;
     out_info[4] = measured; out_info[5] = skipped; out_info[6] = launches;
     return true;
@@ -5942,6 +5975,15 @@ DEV_API int hnswdev_triangle_prefilter_stats(void *ctx, uint64_t out[4])
     CTX_OR_FAIL();
     if (!out) return -1;
     d->triangle_prefilter_stats(out);
+    return 0;
+}
+// ... and in front of the Boruvka scans of the two spanning trees (hnswdev_exact_span_tree and
+// hnswdev_exact_mreach_tree): launches that took the form, foreign pairs the tile judged, pairs of them measured exactly, 0
+DEV_API int hnswdev_span_prefilter_stats(void *ctx, uint64_t out[4])
+{
+    CTX_OR_FAIL();
+    if (!out) return -1;
+    d->span_prefilter_stats(out);
     return 0;
 }
 // The getters of the counter blocks, hnswdev_<block>(ctx, out[slots]), one per row of counter_blocks.h

@@ -25,7 +25,9 @@
 //       2 = wherever that form is built (sq_euclid / sq_euclid_f16, dim % 32 == 0 in [64, 256], k within its LDS), any nq and m.
 //       The same knob, with the same three values, decides whether the fixed-radius triangle scans -- exact_range_groups and both
 //       phases of exact_range_density -- run behind the tile (exact_tri_pf_kernel): 1 = above the sink's measured
-//       member floor; 2 = at any member count]
+//       member floor; 2 = at any member count.  And whether the Boruvka scans of exact_span_tree and exact_mreach_tree do
+//       (span_pf_kernel): 0 = never; 2 = wherever the form is built, at any member count; 1 = there, from the tree's
+//       measured member floor on, when neither exact_chunk nor exact_qtile is forced]
 #pragma once
 #include <cstdlib>
 #include <cstring>

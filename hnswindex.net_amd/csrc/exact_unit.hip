@@ -15,6 +15,7 @@
 #include "dk_exact_tri.h" // exact_tri_pf_kernel: the fixed-radius triangle scans behind the same tile, with the three pair sinks
 #include "dk_span_tree.h" // span_scan_kernel: a kernel of its own over the scan's triangle, no sink; its round kernels sit with the common ones
 #include "dk_mreach_tree.h" // mreach_scan_kernel: that scan under the mutual reachability distance, the offers on all eight lanes; its two core-key kernels likewise
+#include "dk_span_tree_pf.h" // span_pf_kernel: both trees' scans behind the f16 MFMA tile, the bound per component and live
 
 namespace hnsw {
 constexpr int kUnitMetric = HNSW_UNIT_METRIC_ID;
@@ -29,4 +30,5 @@ template hipError_t exact_scan_pf_launch<kUnitMetric>(const ExactScanArgs &, uns
 #define HNSW_EXACT_TRI_UNIT(SINK) template hipError_t exact_tri_pf_launch<kUnitMetric, SINK>(const ExactScanArgs &, const SINK &, unsigned long long *, unsigned, size_t, hipStream_t);
 HNSW_EXACT_TRI_UNIT(ExactRangeUnion) HNSW_EXACT_TRI_UNIT(ExactRangeDensity) HNSW_EXACT_TRI_UNIT(ExactRangeDensityJoin) // ... likewise
 #undef HNSW_EXACT_TRI_UNIT
+template hipError_t span_pf_launch<kUnitMetric>(const ExactScanArgs &, const SpanPfArgs &, bool, unsigned, size_t, hipStream_t); // ... likewise, with and without core keys
 } // namespace hnsw

@@ -854,6 +854,14 @@ API int hnsw_mi355x_triangle_prefilter_stats(void *h, uint64_t out[4])
     static_cast<HnswIndex *>(h)->triangle_prefilter_stats(out);
     return 0;
 }
+// ... and in front of the Boruvka scans of single_linkage_tree and mutual_reachability_tree, in the same slots
+API int hnsw_mi355x_span_prefilter_stats(void *h, uint64_t out[4])
+{
+    if (!h || !out) return -1;
+    LOCK_INDEX(h);
+    static_cast<HnswIndex *>(h)->span_prefilter_stats(out);
+    return 0;
+}
 API int hnsw_mi355x_row_prefilter_form_stats(void *h, uint64_t out[2])
 {
     if (!h || !out) return -1;

@@ -2703,6 +2703,17 @@ void HnswIndex::triangle_prefilter_stats(uint64_t out[4])
     }
 }
 
+void HnswIndex::span_prefilter_stats(uint64_t out[4])
+{
+    out[0] = out[1] = out[2] = out[3] = 0;
+    if (dev_) dev_->span_prefilter_stats(out);
+    for (auto &r : replicas_) {
+        uint64_t v[4];
+        r->span_prefilter_stats(v);
+        for (int i = 0; i < 4; ++i) out[i] += v[i];
+    }
+}
+
 void HnswIndex::row_prefilter_form_stats(uint64_t out[2])
 {
     out[0] = out[1] = 0;

@@ -235,6 +235,7 @@ public:
     void row_prefilter_form_stats(uint64_t out[2]); // summed the same way
     void exact_prefilter_stats(uint64_t out[4]); // the flat scan's MFMA prefilter, summed the same way
     void triangle_prefilter_stats(uint64_t out[4]); // ... and the triangle scans' 
+    void span_prefilter_stats(uint64_t out[4]);     // ... and the two spanning trees' 
     bool row_prefilter_peek(long long first_id, int count, uint64_t out[2], float *rows, std::string &err); // the primary context's shadow, read only
     void row_prefilter8_stats(uint64_t out[6]); // the 8-bit shadow's counters, summed the same way
     bool row_prefilter8_peek(long long first_id, int count, uint64_t out[4], unsigned char *codes, std::string &err); // the primary context's 8-bit shadow, read only
