@@ -727,6 +727,7 @@ private:
     uint64_t count_search_overflows(const PredicateCall &c);
     bool count_launch(const LaunchFamily *family, unsigned long long evals, bool hashed, bool timed, void *t0, void *t1);
     int num_cu_ = 256;
+    size_t max_lds_ = 64 * 1024; // LDS a block may ask for (hipDeviceAttributeMaxSharedMemoryPerBlock), read once at creation: exact_ip_pf_plan
     // Persistent launches never use more than 16 one-wave blocks per CU (the traversal kernels need
     // >= 128 VGPRs): the per-wave scratch (visited bitsets, spill areas, logs) is sized for that.
     int max_slots() const { return num_cu_ * max_waves_per_cu(); }

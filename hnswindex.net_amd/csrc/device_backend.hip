@@ -51,6 +51,7 @@
 #include "device_kernels.h"
 #include "dk_exact.h"
 #include "dk_exact_mfma.h"
+#include "dk_exact_mfma_ip.h"
 #include "dk_exact_tri.h"
 #include "dk_span_tree.h"
 #include "dk_mreach_tree.h"
@@ -298,6 +299,8 @@ Device *Device::create(int device, int dim, int metric, long long capacity)
     {
         int cus = 0;
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0) d->num_cu_ = cus;
+        int lds = 0;
+        if (hipDeviceGetAttribute(&lds, hipDeviceAttributeMaxSharedMemoryPerBlock, device) == hipSuccess && lds > 64 * 1024) d->max_lds_ = (size_t)lds;
     }
     if (!d->reserve(capacity > 0 ? capacity : 1)) return fail();
 #ifdef EXP_PHASE_CLOCKS
@@ -317,6 +320,7 @@ Device *Device::create_view(Device *primary)
     d->metric_ = primary->metric_;
     d->stats_.row_bytes = primary->stats_.row_bytes;
     d->num_cu_ = primary->num_cu_;
+    d->max_lds_ = primary->max_lds_;
     if (hipSetDevice(d->device_) != hipSuccess) { set_dev_error("hipSetDevice failed"); delete d; return nullptr; }
     if (!d->stream_.create(false)) { delete d; return nullptr; }
     d->rebind(primary);
@@ -3175,6 +3179,7 @@ struct ExactPlan {
     int qtile, piece, n_chunks;
     long long chunk, round; // rows per chunk, queries per round
     size_t lds;
+    int waves = 0; // exact_ip_pf_plan's form alone: the waves of a block
 };
 static ExactPlan exact_plan(int nq, long long m, int k, int pitch, int num_cu, int entry_bytes = kExactKeyBytes)
 {
@@ -3222,6 +3227,34 @@ static bool exact_pf_plan(int metric, int nq, long long m, int k, int pitch, int
     chunks = std::min<long long>(chunks, kExactMaxChunks);
     p->chunk = (m + chunks - 1) / chunks;
     if (forced_c <= 0) p->chunk = (p->chunk + kExactIterRows - 1) / kExactIterRows * kExactIterRows;
+    p->n_chunks = (int)((m + p->chunk - 1) / p->chunk);
+    const long long by_lists = (1LL << 30) / ((long long)p->n_chunks * k * 8), by_out = (1LL << 24) / k;
+    p->round = std::max<long long>(1, std::min<long long>({(long long)nq, by_lists, by_out}));
+    return true;
+}
+
+// ... and the same question for the cosine family (exact_scan_ip_pf_kernel, dk_exact_mfma_ip.h), under the same knob with
+// the same meanings.  The served row lengths and k follow from lds_limit, what the device lets a block ask for: dim % 32 == 0 up to 1 024
+// with 160 KB, up to 256 with 64 KB.  A block is 4 waves while two blocks fit a CU, else 8 (exact_ip_pf_waves); under exact_prefilter = 2
+// `exact_qtile` = 4 or 8 forces either (the A/B of 3.38), any other value is not read.  The default's floors are 3.34's, where 3.38's A/B
+// found the form ahead of the plain scan in every run: kExactIpPfPicker* say for which metrics and row lengths.
+static bool exact_ip_pf_plan(int metric, int nq, long long m, int k, int pitch, int num_cu, size_t lds_limit, ExactPlan *p)
+{
+    const int mode = diag("exact_prefilter", 1);
+    if (mode <= 0 || !exact_ip_pf_metric(metric) || !exact_ip_pf_dim(pitch)) return false;
+    const long long forced_c = diag("exact_chunk", 0);
+    const int forced_q = diag("exact_qtile", 0);
+    const int waves = exact_ip_pf_waves(pitch, k, lds_limit, mode >= 2 ? forced_q : 0);
+    if (k > exact_ip_pf_max_k(pitch, waves, lds_limit)) return false;
+    if (mode == 1 && (forced_c > 0 || forced_q > 0 || nq < kExactPfMinQueries || m < kExactPfMinRows || (long long)nq * m < kExactPfMinPairs ||
+                      k > kExactPfPickerMaxK || !exact_ip_pf_picker(metric, pitch))) return false;
+    p->qtile = kExactPfQTile; p->piece = pitch; p->waves = waves;
+    p->lds = exact_ip_pf_lds(pitch, k, waves);
+    const long long tiles = (std::min<long long>(nq, 65536) + p->qtile - 1) / p->qtile, step = 32 * waves;
+    long long chunks = forced_c > 0 ? (m + forced_c - 1) / forced_c : std::max<long long>(1, std::min<long long>((2LL * num_cu + tiles - 1) / tiles, m / 1024));
+    chunks = std::min<long long>(chunks, kExactMaxChunks);
+    p->chunk = (m + chunks - 1) / chunks;
+    if (forced_c <= 0) p->chunk = (p->chunk + step - 1) / step * step;
     p->n_chunks = (int)((m + p->chunk - 1) / p->chunk);
     const long long by_lists = (1LL << 30) / ((long long)p->n_chunks * k * 8), by_out = (1LL << 24) / k;
     p->round = std::max<long long>(1, std::min<long long>({(long long)nq, by_lists, by_out}));
@@ -3413,9 +3446,10 @@ bool Device::exact_knn_rounds(const float *d_q, const double *d_qsn, int nq, con
 {
     hipStream_t st = S(stream_);
     ExactPlan p;
-    const bool pf = !d_keep_ids && !d_self && !collapse && exact_pf_plan(metric_, nq, m, k, pitch_, num_cu_, &p); // the plain sink of exact_knn alone
+    const bool pf = !d_keep_ids && !d_self && !collapse && (exact_pf_plan(metric_, nq, m, k, pitch_, num_cu_, &p) ||
+                                                            exact_ip_pf_plan(metric_, nq, m, k, pitch_, num_cu_, max_lds_, &p)); // the plain sink of exact_knn alone
     if (!pf) p = exact_plan(nq, m, k, pitch_, num_cu_, collapse ? kExactCollapseEntryBytes : kExactKeyBytes);
-    if (p.lds > 64 * 1024) { set_dev_error("exact_knn: tile exceeds the LDS budget"); return false; }
+    if (p.lds > (p.waves ? max_lds_ : (size_t)64 * 1024)) { set_dev_error("exact_knn: tile exceeds the LDS budget"); return false; }
     if (!x_lists_.grow((size_t)p.round * p.n_chunks * k) || !x_out_.grow(2 * (size_t)p.round * k) || (pf && !x_pfctr_.grow(2))) return false;
     char *hs = static_cast<char *>(pinned_stage(8 * (size_t)p.round * k + 24));
     if (!hs) return false;
@@ -3439,7 +3473,8 @@ bool Device::exact_knn_rounds(const float *d_q, const double *d_qsn, int nq, con
             if (pf) {
                 HIP_OK(hipMemsetAsync(x_pfctr_, 0, 2 * sizeof(unsigned long long), st));
                 hipError_t e = hipSuccess;
-                with_metric(metric_, [&](auto mt) { e = exact_scan_pf_launch<mt>(a, x_pfctr_, tiles, p.lds, st); });
+                if (p.waves) with_metric(metric_, [&](auto mt) { e = exact_scan_ip_pf_launch<mt>(a, x_pfctr_, tiles, p.waves, p.lds, max_lds_, st); });
+                else with_metric(metric_, [&](auto mt) { e = exact_scan_pf_launch<mt>(a, x_pfctr_, tiles, p.lds, st); });
                 HIP_OK(e);
             } else if (d_self) HIP_OK(exact_scan_enqueue(metric_, a, ExactTopKSelf{d_self + off}, tiles, p.lds, st));
             else HIP_OK(exact_scan_enqueue(metric_, a, ExactTopK{}, tiles, p.lds, st));
