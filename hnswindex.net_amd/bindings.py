@@ -728,7 +728,8 @@ class Index:
 
     def exact_prefilter_stats(self):
         """Counters of the flat scan's MFMA prefilter (exact_knn_query): scan launches that took the form, pairs its
-        half-precision tile judged, pairs of them then measured exactly, and a reserved 0."""
+        half-precision tile judged, pairs of them then measured exactly, and a reserved 0.  On sq_euclid_i8 the tile
+        is the i8 MFMA's exact dot product: pairs on it, and pairs of them handed on to be measured by the plain scan's code and inserted."""
         out = (ct.c_uint64 * 4)()
         if not self._h or lib.hnsw_mi355x_exact_prefilter_stats(self._h, out) != 0:
             return dict.fromkeys(EXACT_PREFILTER_SLOTS, 0)

@@ -52,6 +52,7 @@
 #include "dk_exact.h"
 #include "dk_exact_mfma.h"
 #include "dk_exact_mfma_ip.h"
+#include "dk_exact_mfma_i8.h"
 #include "dk_exact_tri.h"
 #include "dk_span_tree.h"
 #include "dk_mreach_tree.h"
@@ -3261,6 +3262,30 @@ static bool exact_ip_pf_plan(int metric, int nq, long long m, int k, int pitch, 
     return true;
 }
 
+// ... and for the int8 rows (exact_scan_i8_mfma_kernel, dk_exact_mfma_i8.h), under the same knob with the same meanings: the
+// tile there holds the library's own dot product, not an estimate.  Served: every pitch whose plan fits 64 KB of LDS (dim 520 at k = 10);
+// larger pitches stay on the plain kernel.  The default's floors are 3.34's, and exact_i8_mfma_picker says at which pitches 3.39's A/B
+// found every run of the form below every run of the plain scan.
+static bool exact_i8_mfma_plan(int metric, int nq, long long m, int k, int pitch, int num_cu, ExactPlan *p)
+{
+    const int mode = diag("exact_prefilter", 1);
+    if (mode <= 0 || !exact_i8_mfma_metric(metric) || !exact_i8_mfma_pitch(pitch) || k > exact_i8_mfma_max_k(pitch)) return false;
+    const long long forced_c = diag("exact_chunk", 0);
+    if (mode == 1 && (forced_c > 0 || diag("exact_qtile", 0) > 0 || nq < kExactPfMinQueries || m < kExactPfMinRows ||
+                      (long long)nq * m < kExactPfMinPairs || k > kExactPfPickerMaxK || !exact_i8_mfma_picker(pitch))) return false;
+    p->qtile = kExactPfQTile; p->piece = pitch;
+    p->lds = exact_i8_mfma_lds(pitch, k);
+    const long long tiles = (std::min<long long>(nq, 65536) + p->qtile - 1) / p->qtile;
+    long long chunks = forced_c > 0 ? (m + forced_c - 1) / forced_c : std::max<long long>(1, std::min<long long>((2LL * num_cu + tiles - 1) / tiles, m / 1024));
+    chunks = std::min<long long>(chunks, kExactMaxChunks);
+    p->chunk = (m + chunks - 1) / chunks;
+    if (forced_c <= 0) p->chunk = (p->chunk + kExactIterRows - 1) / kExactIterRows * kExactIterRows;
+    p->n_chunks = (int)((m + p->chunk - 1) / p->chunk);
+    const long long by_lists = (1LL << 30) / ((long long)p->n_chunks * k * 8), by_out = (1LL << 24) / k;
+    p->round = std::max<long long>(1, std::min<long long>({(long long)nq, by_lists, by_out}));
+    return true;
+}
+
 void Device::exact_prefilter_stats(uint64_t out[4]) const { std::copy_n(xpf_stats_, 4, out); }
 
 // The queries of a flat scan: the resident set, or the scan's own -- uploaded by set_queries (the one staging path: pinned copy,
@@ -3447,7 +3472,8 @@ bool Device::exact_knn_rounds(const float *d_q, const double *d_qsn, int nq, con
     hipStream_t st = S(stream_);
     ExactPlan p;
     const bool pf = !d_keep_ids && !d_self && !collapse && (exact_pf_plan(metric_, nq, m, k, pitch_, num_cu_, &p) ||
-                                                            exact_ip_pf_plan(metric_, nq, m, k, pitch_, num_cu_, max_lds_, &p)); // the plain sink of exact_knn alone
+                                                            exact_ip_pf_plan(metric_, nq, m, k, pitch_, num_cu_, max_lds_, &p) ||
+                                                            exact_i8_mfma_plan(metric_, nq, m, k, pitch_, num_cu_, &p)); // the plain sink of exact_knn alone
     if (!pf) p = exact_plan(nq, m, k, pitch_, num_cu_, collapse ? kExactCollapseEntryBytes : kExactKeyBytes);
     if (p.lds > (p.waves ? max_lds_ : (size_t)64 * 1024)) { set_dev_error("exact_knn: tile exceeds the LDS budget"); return false; }
     if (!x_lists_.grow((size_t)p.round * p.n_chunks * k) || !x_out_.grow(2 * (size_t)p.round * k) || (pf && !x_pfctr_.grow(2))) return false;
@@ -3473,7 +3499,8 @@ bool Device::exact_knn_rounds(const float *d_q, const double *d_qsn, int nq, con
             if (pf) {
                 HIP_OK(hipMemsetAsync(x_pfctr_, 0, 2 * sizeof(unsigned long long), st));
                 hipError_t e = hipSuccess;
-                if (p.waves) with_metric(metric_, [&](auto mt) { e = exact_scan_ip_pf_launch<mt>(a, x_pfctr_, tiles, p.waves, p.lds, max_lds_, st); });
+                if (exact_i8_mfma_metric(metric_)) with_metric(metric_, [&](auto mt) { e = exact_scan_i8_mfma_launch<mt>(a, x_pfctr_, tiles, p.lds, st); });
+                else if (p.waves) with_metric(metric_, [&](auto mt) { e = exact_scan_ip_pf_launch<mt>(a, x_pfctr_, tiles, p.waves, p.lds, max_lds_, st); });
                 else with_metric(metric_, [&](auto mt) { e = exact_scan_pf_launch<mt>(a, x_pfctr_, tiles, p.lds, st); });
                 HIP_OK(e);
             } else if (d_self) HIP_OK(exact_scan_enqueue(metric_, a, ExactTopKSelf{d_self + off}, tiles, p.lds, st));

@@ -24,7 +24,9 @@
 //       exact_prefilter [1 = the picker decides whether exact_knn's plain scan runs behind the f16 MFMA tile; 0 = never;
 //       2 = wherever that form is built (sq_euclid / sq_euclid_f16, dim % 32 == 0 in [64, 256], k within its LDS; cosine / ucosine /
 //       ucosine_f16, exact_scan_ip_pf_kernel of DESIGN.md 3.38: dim % 32 == 0 in [64, 1024] and k as far as the LDS the device grants a
-//       block goes, exact_qtile = 4 or 8 then forcing the waves of its block), any nq and m.
+//       block goes, exact_qtile = 4 or 8 then forcing the waves of its block; sq_euclid_i8, exact_scan_i8_mfma_kernel of DESIGN.md 3.39,
+//       where the i8 MFMA tile holds the library's own int32 dot product: every record of up to 208 words and k as far as 64 KB of LDS
+//       go -- dim 520 at k <= 40 -- and the picker takes it up to 144 words), any nq and m.
 //       The same knob, with the same three values, decides whether the fixed-radius triangle scans -- exact_range_groups and both
 //       phases of exact_range_density -- run behind the tile (exact_tri_pf_kernel): 1 = above the sink's measured
 //       member floor; 2 = at any member count.  And whether the Boruvka scans of exact_span_tree and exact_mreach_tree do

@@ -13,6 +13,7 @@
 #include "dk_graph_repair.h"
 #include "dk_exact_mfma.h" // exact_scan_pf_kernel: the plain top-k scan behind an f16 MFMA tile; a kernel of its own, no sink
 #include "dk_exact_mfma_ip.h" // exact_scan_ip_pf_kernel: that scan for the cosine family, the bound on the dot product, LDS up to the device's limit
+#include "dk_exact_mfma_i8.h" // exact_scan_i8_mfma_kernel: that scan for the int8 rows, the exact dot product on the i8 MFMA tile
 #include "dk_exact_tri.h" // exact_tri_pf_kernel: the fixed-radius triangle scans behind the same tile, with the three pair sinks
 #include "dk_span_tree.h" // span_scan_kernel: a kernel of its own over the scan's triangle, no sink; its round kernels sit with the common ones
 #include "dk_mreach_tree.h" // mreach_scan_kernel: that scan under the mutual reachability distance, the offers on all eight lanes; its two core-key kernels likewise
@@ -29,6 +30,7 @@ template hipError_t span_scan_launch<kUnitMetric>(const ExactScanArgs &, const S
 template hipError_t mreach_scan_launch<kUnitMetric>(const ExactScanArgs &, const MreachScanArgs &, unsigned, size_t, hipStream_t);
 template hipError_t exact_scan_pf_launch<kUnitMetric>(const ExactScanArgs &, unsigned long long *, unsigned, size_t, hipStream_t); // a kernel for sq and sqh, an error for the rest
 template hipError_t exact_scan_ip_pf_launch<kUnitMetric>(const ExactScanArgs &, unsigned long long *, unsigned, int, size_t, size_t, hipStream_t); // a kernel for cos, ucos and ucosh, an error for the rest
+template hipError_t exact_scan_i8_mfma_launch<kUnitMetric>(const ExactScanArgs &, unsigned long long *, unsigned, size_t, hipStream_t); // a kernel for i8, an error for the rest
 #define HNSW_EXACT_TRI_UNIT(SINK) template hipError_t exact_tri_pf_launch<kUnitMetric, SINK>(const ExactScanArgs &, const SINK &, unsigned long long *, unsigned, size_t, hipStream_t);
 HNSW_EXACT_TRI_UNIT(ExactRangeUnion) HNSW_EXACT_TRI_UNIT(ExactRangeDensity) HNSW_EXACT_TRI_UNIT(ExactRangeDensityJoin) // ... likewise
 #undef HNSW_EXACT_TRI_UNIT

@@ -151,7 +151,9 @@ int hnsw_mi355x_row_prefilter_stats(void *handle, uint64_t out[4]);
 /* Counters of the flat scan's MFMA prefilter (exact_knn_query on sq_euclid and sq_euclid_f16 indices) since the index
  * was created: out[0] scan launches that took the form, out[1] (query, row) pairs its half-precision tile judged, out[2] pairs of
  * them that were then measured exactly (the others were turned away on a proven lower bound), out[3] reserved, 0.  Ids and distance
- * bits are the plain scan's either way.  All zero where the form does not run. */
+ * bits are the plain scan's either way.  All zero where the form does not run.  The cosine metrics' tile counts
+ * here as well, and so does the sq_euclid_i8 form, whose i8 MFMA tile holds the exact dot product: out[1] the pairs
+ * on its tile, out[2] the pairs of them whose key was below their query's k-th and went on to be inserted. */
 int hnsw_mi355x_exact_prefilter_stats(void *handle, uint64_t out[4]);
 /* Counters of the same tile in front of the fixed-radius triangle scans (duplicate_groups, neighbor_counts and density_clusters on
  * sq_euclid and sq_euclid_f16 indices) since the index was created: out[0] scan launches that took the form, out[1]
